@@ -21,6 +21,7 @@ Two decompositions, one JSON line each:
     A 50-iteration BFGS solve over the pyramid is timed beside it (`solve_50_iters_s`).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs out/    (also writes out/loss.npy, out/grad.npy of the last timed step)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
     EINCM_BENCH_BACKEND=gloo python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2 --mode event-sharded   (1-GPU rehearsal)
 """
@@ -68,7 +69,11 @@ def parse_args(argv=None):
     ap.add_argument('--no-latency', action='store_true')
     ap.add_argument('--solve-iters', type=int, default=50, help='event-sharded: BFGS iterations of the end-to-end leg (0 = skip)')
     ap.add_argument('--groups', type=int, default=1, help='contexts (HIP streams) the windows of a rank are spread over')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the loss values and gradients of the last timed step to DIR/<name>.npy (float64)')
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
     sharded = a.mode == 'event-sharded'
     if a.events is None:
         a.events = 10_000_000 if sharded else 1_000_000
@@ -107,6 +112,21 @@ def init_dist(a):
         dist.barrier()
     ge.build()
     return rank, world, dev_index, dev, red_dev, backend
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Write what the timed path returned in its last step as DIR/<name>.npy, float32 or float64, 64 MB at most in all."""
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+              for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f'--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit')
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), v)
 
 
 def load_traffic(workload):
@@ -532,6 +552,9 @@ def bench_windows(a):
     # ---- CPU baselines: ports of the reference arithmetic (the reference itself, JAX, cannot run here or on the GPU box) ----
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(wins[0], theta_at, alpha, beta, (H, W), N, R, dense)
+    if a.dump_outputs:                  # every rank's own windows
+        sfx = f'_rank{rank}' if world > 1 else ''
+        dump_outputs(a.dump_outputs, {'loss' + sfx: v, 'grad' + sfx: g})
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
@@ -698,6 +721,8 @@ def bench_event_sharded(a):
             'note': 'hardware scaling of this mode is unmeasured until an N > 1 run on a multi-GPU node exists; with EINCM_BENCH_BACKEND=gloo '
                     'the collective bounces through host memory (1-GPU rehearsal only)',
         }
+        if a.dump_outputs:            # the loss and gradient are all-reduced: every rank holds the same arrays
+            dump_outputs(a.dump_outputs, {'loss': v, 'grad': g})
         print(json.dumps(out))
     eng.close()
     if world > 1:

@@ -1,6 +1,6 @@
 """Lockstep solver for a BATCH of independent event windows: the caller of the engine's batch path (BASELINE config C4).
 
-The reference solves one window at a time (/root/reference/src/eincm/solver.py:197-267, src/experiments/e00/exp_mgr.py:615-659):
+The reference solves one window at a time (upstream src/eincm/solver.py:197-267, src/experiments/e00/exp_mgr.py:615-659):
 every BFGS function evaluation is one loss+grad of one window.  The HIP engine evaluates B windows in ONE call at 2-3 times the
 per-window rate of B single calls (bench.py: 8 x 10^6 events in 0.24 ms against 8 x 0.07 ms), but only a caller that has B thetas
 ready at the same moment can use that.  This module is that caller:

@@ -23,7 +23,7 @@ def _dp(a):
 def as_int16_coords(a, what='coordinates'):
     """Event coordinates as int16, the reference's wire format.  Integer arrays are range-checked and cast; float arrays
     (e.g. rectified coordinates handed straight to loss_func) are rounded half-to-even first, like ``jnp.round(xs).astype(int16)``
-    in per_pix_warp (/root/reference/src/eincm/event_warpers.py:29-30).  Values outside the int16 range raise instead of wrapping."""
+    in per_pix_warp (upstream src/eincm/event_warpers.py:29-30).  Values outside the int16 range raise instead of wrapping."""
     a = np.asarray(a)
     if a.dtype == np.int16:
         return a

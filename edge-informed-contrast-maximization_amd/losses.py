@@ -1,6 +1,6 @@
 """Host-side mirror of the reference's objective callables, backed by the HIP engine.
 
-Same names, argument order and meaning as /root/reference/src/eincm/losses.py:
+Same names, argument order and meaning as upstream src/eincm/losses.py:
     loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls,
               sensor_size, scale_to_sensor_size_method) -> (final_loss, aux_info)          losses.py:108-205
     handover_loss_func(alpha_handover, prev_theta, theta, xs, ..., method) -> loss          losses.py:208-276

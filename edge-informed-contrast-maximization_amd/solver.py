@@ -1,6 +1,6 @@
 """Host-side callers of the loss+grad path: the jaxopt-shaped SciPy wrappers and the multi-level solver.
 
-Mirrors /root/reference/src/eincm/solver.py (MultipleLevelEINCMSolver :10-383) and the two jaxopt classes it uses
+Mirrors upstream src/eincm/solver.py (MultipleLevelEINCMSolver :10-383) and the two jaxopt classes it uses
 (jaxopt.ScipyMinimize / ScipyBoundedMinimize, call sites solver.py:165-183,209-216,325-335; wrapper shape shown in
 README.md:108-126).  jaxopt differentiates ``fun`` with JAX; the HIP engine delivers the gradient itself, so the wrappers
 here are used in jaxopt's own ``value_and_grad=True`` mode: ``fun(params, *args)`` returns ``(value, grad)`` — or

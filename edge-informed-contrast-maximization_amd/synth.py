@@ -1,7 +1,7 @@
 """Deterministic synthetic event windows with the wire format the EINCM path consumes.
 
 The reference stages a window as ``(xs:int16, ys:int16, ts:float64 in ~[0,1], edges:float64 (R,H,W) in
-[0,1], edge_ts:float64 (R,))`` (/root/reference/src/experiments/e00/exp_mgr.py:278-376: time
+[0,1], edge_ts:float64 (R,))`` (upstream src/experiments/e00/exp_mgr.py:278-376: time
 normalisation ``(t - t0)/(t1 - t0 + eps)`` at :322-324, edge maps min-max normalised at :343-350; events
 arrive time-sorted from every loader, src/dataloaders/mvsec_loader.py:272-295).  No dataset is
 available offline, so this module generates windows of that exact shape: moving-edge scenes

@@ -15,7 +15,7 @@ in ``tests/test_oracle_known_answers.py`` (tap constants, multi-reference weight
 integer-shift identities), (b) an independent torch-float64 autograd restatement
 (``oracle/eincm_torch.py``) and (c) central finite differences.
 
-Reference lines followed (relative to /root/reference/src):
+Reference lines followed (relative to the upstream repository's src/):
   eincm/losses.py:39-46      compute_weights_for_multi_reference
   eincm/losses.py:49-105     compute_loss_objectives
   eincm/losses.py:108-205    loss_func

@@ -7,7 +7,7 @@ tolerance 1e-5 (relative; images and gradients max-norm relative).  The C port c
 bench evaluates; the TV / divergence terms are image-sized work whose parity does not depend on the event count
 (tests/test_gpu_parity.py covers them).
 
-Follows /root/reference/src/eincm/losses.py:108-205, src/utils/event_utils.py:31-61 (via the oracle restatement).
+Follows upstream src/eincm/losses.py:108-205, src/utils/event_utils.py:31-61 (via the oracle restatement).
 """
 import importlib
 import os

@@ -607,7 +607,7 @@ def test_long_splat_segments_use_two_lds_windows(monkeypatch):
 def fma_tie_events(v, W, n_want, rng):
     """Events (x, t) for which fl(x - fl(v*t)) sits exactly on a half-integer while the unrounded x - v*t does not, chosen so that
     the two round to DIFFERENT pixels: what a fused multiply-add (one rounding) gets wrong against the reference's two roundings
-    (/root/reference/src/eincm/event_warpers.py:34, `xs - theta * dts * delta_time`).  Exact arithmetic with fractions."""
+    (upstream src/eincm/event_warpers.py:34, `xs - theta * dts * delta_time`).  Exact arithmetic with fractions."""
     from fractions import Fraction
     xs, ts = [], []
     fv = Fraction(v)

@@ -84,7 +84,7 @@ def _oracle_pfuncs(H, W, alpha=20.0, beta=35.0, gamma=0.0):
     return vg, ho
 
 
-def test_multi_level_solver_two_windows():
+def test_multi_level_solver_two_windows(built_lib):
     H, W, n_lvls = 32, 40, 3
     vg, ho = _oracle_pfuncs(H, W)
     cb = sol.CollectingCallback()
@@ -126,7 +126,7 @@ def test_multi_level_solver_two_windows():
                                    a * out2['prior_theta_pyr'][key] + (1 - a) * out2['pre_handover_theta_pyr'][key])
 
 
-def test_rescale_theta_matches_oracle_resampling():
+def test_rescale_theta_matches_oracle_resampling(built_lib):
     th = np.random.default_rng(0).normal(size=(4, 4, 2))
     up = sol.rescale_theta(th, (8, 8), 'bilinear')
     A = O.resample_matrix(4, 8, 2.0, 'bilinear')
@@ -205,10 +205,13 @@ def test_yaml_config_reader(tmp_path):
     assert cfg.dataset.sensor_size == [256, 336] and cfg.theta_loss_func.alpha == 60 and cfg.solver_params.theta_opt.miniter == 10.0
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/src/experiments/e00/configs'), reason='reference tree not present')
 def test_yaml_reader_on_the_reference_tree():
-    cfg = config.load_config('/root/reference/src/experiments/e00/configs', 'main', ['dataset=mvsec'])
+    """The reference's e00 MVSEC defaults, read from a tree of the same layout stored under tests/golden/eincm_configs."""
+    tree = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'eincm_configs')
+    cfg = config.load_config(tree, 'main', ['dataset=mvsec'])
     assert cfg.dataset.sensor_size == [256, 336] and (cfg.alpha, cfg.beta, cfg.gamma, cfg.delta) == (20, 35, 0.00025, 0.0)
+    assert cfg.edge_extraction.smoothen.alpha_iedt == pytest.approx(6 / 5.541) and cfg.solver_params.theta_opt.options.gtol == 1e-7
+    assert config.load_config(tree, 'main').dataset.loader.data_split == 'test'
     assert cfg.theta_loss_func._target_ == 'eincm.losses.loss_func' and cfg.theta_loss_func.scale_to_sensor_size_method == 'bilinear'
     assert cfg.solver_params.theta_opt.miniter == 8.0 and cfg.handover_settings.solve_handover_for_levels == [1, 0]
     mi = sol.growing_maxiters(cfg.n_pyr_lvls, cfg.solver_params.theta_opt.miniter, cfg.solver_params.theta_opt.maxiter,
@@ -246,3 +249,20 @@ def test_bench_argument_paths():
     assert bench.event_kernel_algorithmic_bytes(1_000_000, 5, 260, 346) == 8_000_000 + 4 * 5 * 260 * 346
     r = bench.kernel_roofline('k_x', 0.1, 80_000_000, None)
     assert r['achieved'] == pytest.approx(800.0) and r['frac'] == pytest.approx(0.1) and r['peak'] == 8000.0
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 .npy files named after the outputs, 64 MB at most in all; --steps >= 1."""
+    import bench
+    assert bench.parse_args([]).dump_outputs is None
+    assert bench.parse_args(['--dump-outputs', str(tmp_path)]).dump_outputs == str(tmp_path)
+    with pytest.raises(SystemExit):
+        bench.parse_args(['--steps', '0'])
+    v, g = np.array([1.5, -2.0]), np.arange(8, dtype=np.float32).reshape(2, 1, 2, 2)
+    bench.dump_outputs(str(tmp_path / 'out'), {'loss': v, 'grad': g, 'count': np.arange(3)})
+    lv, lg, lc = (np.load(tmp_path / 'out' / f'{k}.npy') for k in ('loss', 'grad', 'count'))
+    assert lv.dtype == np.float64 and np.array_equal(lv, v) and lg.dtype == np.float32 and np.array_equal(lg, g)
+    assert lc.dtype == np.float64 and np.array_equal(lc, [0, 1, 2])
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / 'big'), {'x': np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1)})
+    assert not (tmp_path / 'big').exists()

@@ -1,6 +1,6 @@
 import importlib, os, sys, time
 import numpy as np
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 engine = importlib.import_module('edge-informed-contrast-maximization_amd.engine')
 synth = importlib.import_module('edge-informed-contrast-maximization_amd.synth')
 H, W, N, R, B = 260, 346, 1000000, 5, 8
