@@ -17,6 +17,8 @@ PF_NO_TV_GRAD = 2
 SW_DEFER_CONSTANTS = 1
 CF_TIMING = 1
 CF_TIMING_DOMINANT = 2
+CF_FP64 = 4                # float64 mode (Engine(..., precision='fp64'))
+PRECISIONS = ('fp32', 'fp64')
 
 
 class Params(C.Structure):
@@ -75,6 +77,9 @@ SIGNATURES = [
     ('eincm_get_image_grad', C.c_int, [_P, C.POINTER(C.c_float)]),
     ('eincm_get_scaled_theta', C.c_int, [_P, _D]),
     ('eincm_get_count_images', C.c_int, [_P, C.POINTER(C.c_uint32)]),
+    ('eincm_get_iwes_f64', C.c_int, [_P, _D]),
+    ('eincm_get_zero_iwe_f64', C.c_int, [_P, _D]),
+    ('eincm_get_image_grad_f64', C.c_int, [_P, _D]),
     ('eincm_loss_grad_device', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.POINTER(Params), C.c_double, C.POINTER(C.c_double), C.c_void_p,
                                         C.POINTER(Aux)]),
     ('eincm_set_timing_period', C.c_int, [_P, C.c_int]),

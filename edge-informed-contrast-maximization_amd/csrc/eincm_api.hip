@@ -20,6 +20,7 @@
 
 #include "eincm.h"
 #include "eincm_kernels.hip.h"
+#include "eincm_kernels_f64.hip.h"
 #include "eincm_binning.hip.h"
 #include "eincm_edges.hip.h"
 
@@ -198,6 +199,28 @@ struct eincm_ctx {
     bool acc_dirty = false;        // a forward half was launched and its consumers were not: accumulators must be memset before reuse
     bool Theta_valid = false;      // d_Theta holds the upsampled theta of the last evaluation (2-DoF evaluations skip the image)
     std::vector<double> last_theta11;   // (B,2) theta of the last 2-DoF evaluation (to build d_Theta on demand)
+
+    // float64 mode (EINCM_CF_FP64, eincm_kernels_f64.hip.h): its own images and accumulators, sized at create
+    bool fp64 = false;
+    struct {
+        unsigned long long* acc = nullptr;   // (B,R,H,W) u64 IWE accumulator at 2^ishift[b], zero between evaluations (k64_img_a clears)
+        double* iwe = nullptr;               // (B,R,H,W)
+        double* zero_iwe = nullptr;          // (B,H,W)
+        double* edges = nullptr;             // (B,R,H,W) the edges as handed over
+        double* G = nullptr;                 // (B,R,H,W) dL/dIWE
+        double* sgn = nullptr;               // (B,R,H,W) sign of the divergence image (delta != 0 gradients)
+        unsigned long long* gacc = nullptr;  // (B,H,W,2) x 2 words: i128 dL/dTheta, zero between evaluations (k64_gfin clears)
+        double* gTh = nullptr;               // (B,H,W,2) dL/dTheta
+        double* T = nullptr;                 // (B,H,W,2) capacity: the half-projected gradient (k64_proj_w)
+        double* grad = nullptr;              // (B,H,W,2) capacity: dL/dtheta
+        double* partA = nullptr; double* partB = nullptr; double* partC = nullptr;   // per-workgroup partials of the image passes
+        F64Scal* scal = nullptr;             // (B,R)
+        F64Scal* h_scal = nullptr;           // pinned copy
+        unsigned long long* gmax = nullptr;  // (B) max |dL/dIWE| as double bits
+        int* ishift = nullptr;               // (B)
+        unsigned* bad = nullptr;             // (B) a non-finite dL/dIWE or event term in this evaluation (gradient -> NaN)
+        int P = 0;                           // image-pass workgroups per image
+    } f64;
 };
 
 namespace {
@@ -296,8 +319,11 @@ void free_all(eincm_ctx* c) {
     F(c->d_Theta); F(c->d_theta_in); F(c->d_gTheta); F(c->d_tvg); F(c->d_mask); F(c->d_tmm); F(c->d_parts);
     F(c->d_divparts); F(c->d_g2parts); F(c->d_gdiv); F(c->d_dgparts); F(c->d_tvparts); F(c->d_wc); F(c->d_outs); c->d_grad = nullptr; F(c->d_gth); F(c->d_AH); F(c->d_AW);
     F(c->d_rowtap); F(c->d_coltap); F(c->d_tilerng);
+    F(c->f64.acc); F(c->f64.iwe); F(c->f64.zero_iwe); F(c->f64.edges); F(c->f64.G); F(c->f64.sgn); F(c->f64.gacc); F(c->f64.gTh); F(c->f64.T);
+    F(c->f64.grad); F(c->f64.partA); F(c->f64.partB); F(c->f64.partC); F(c->f64.scal); F(c->f64.gmax); F(c->f64.ishift); F(c->f64.bad);
     for (DevBuf* b : {&c->e_u8, &c->e_g, &c->e_sq, &c->e_misc, &c->e_a, &c->e_b, &c->e_kern, &c->e_out}) { F(b->p); b->bytes = 0; }
     auto FH = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
+    FH(c->f64.h_scal);
     FH(c->h_theta); FH(c->h_outs); c->h_grad = nullptr; FH(c->h_wc); FH(c->h_g11); FH(c->h_g2); FH(c->h_img); FH(c->h_tvparts);
     if (c->have_events) {
         for (int k = 0; k < eincm_ctx::EV_RING; ++k)
@@ -605,6 +631,110 @@ int collect_timings(eincm_ctx* c) {
     return (c->ring_size == 1) ? drain_event_ring(c, 0) : EINCM_OK;
 }
 
+// The whole evaluation of a float64 context (EINCM_CF_FP64), enqueued at once: theta -> Theta (k_theta) -> k64_splat -> image passes
+// [-> k_tv] [-> dL/dIWE -> k64_gather -> k64_gfin -> projection] -> results into pinned memory.  eval_end_collect waits and f64_assemble
+// adds the scalars up on the host in index order.  None of the fp32 path's launch policy applies: one segment list, one launch form.
+int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalParams& ep, bool want_grad, bool full_aux, bool div_grad,
+               bool identity) {
+    const Geom& g = c->g;
+    const size_t img = (size_t)g.H * g.W, nth = (size_t)h * w * 2;
+    c->theta_nan.assign((size_t)g.B, 0);
+    for (int b = 0; b < g.B; ++b)
+        for (size_t i = 0; i < nth; ++i) if (!std::isfinite(theta_host[(size_t)b * nth + i])) { c->theta_nan[b] = 1; break; }
+    memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double));
+    HIPCHK(c, hipMemcpyAsync(c->d_theta_in, c->h_theta, (size_t)g.B * nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    static const ThetaArgBig targ{};
+    launch_theta_image(c, h, w, identity, false, targ, c->d_theta_in, false);
+    if (!identity && h == 1 && w == 1) c->last_theta11.assign(theta_host, theta_host + (size_t)g.B * 2);
+    HIPCHK(c, hipMemsetAsync(c->f64.gmax, 0, (size_t)g.B * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->f64.bad, 0, (size_t)g.B * sizeof(unsigned), c->stream));
+    // both event kernels walk the gather's list and copy of the events (sorted by source pixel; the splat's spread copy measured
+    // slower with these global atomics: 13.6 vs 10.9 ms of k64_splat on the bench batch, profiles/r04/fp64_mode.txt)
+    if (c->n_items > 0)
+        hipLaunchKernelGGL(k64_splat, dim3(event_grid(c)), dim3(NT), 0, c->stream, g, c->n_items, c->d_items, c->d_xy_g, c->d_t_g, c->d_Theta,
+                           c->d_edge_ts, c->f64.ishift, c->f64.acc);
+    const dim3 gimg(c->f64.P, g.R, g.B);
+    hipLaunchKernelGGL(k64_img_a, gimg, dim3(NT), 0, c->stream, g, c->f64.ishift, c->f64.acc, c->f64.iwe, c->f64.partA);
+    hipLaunchKernelGGL(k64_img_b, gimg, dim3(NT), 0, c->stream, g, c->f64.iwe, c->f64.edges, c->f64.partA, c->f64.partB, ep.want_div,
+                       div_grad ? c->f64.sgn : nullptr);
+    hipLaunchKernelGGL(k64_scal, dim3(g.R, g.B), dim3(NT), 0, c->stream, g, c->f64.P, c->f64.partA, c->f64.partB, c->f64.scal);
+    HIPCHK(c, hipMemcpyAsync(c->f64.h_scal, c->f64.scal, (size_t)g.B * g.R * sizeof(F64Scal), hipMemcpyDeviceToHost, c->stream));
+    if (ep.want_tv)            // shared with the fp32 path: k_tv is fp64 throughout; its partials also land in pinned memory for f64_assemble
+        hipLaunchKernelGGL(k_tv<0>, dim3(g.ntiles, g.B), dim3(NT), 0, c->stream, g, c->d_Theta, c->d_mask, c->d_tvg, c->d_tvparts,
+                           full_aux ? 1 : 0, h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth + (size_t)c->maxB * c->coarse_cap,
+                           (int)c->coarse_cap, c->h_tvparts);
+    if (want_grad) {
+        hipLaunchKernelGGL(k64_grad1, gimg, dim3(NT), 0, c->stream, g, ep, c->f64.iwe, c->f64.edges, c->f64.scal, c->d_wc,
+                           div_grad ? c->f64.sgn : nullptr, c->f64.G, c->f64.partC);
+        hipLaunchKernelGGL(k64_grad2, gimg, dim3(NT), 0, c->stream, g, c->f64.iwe, c->f64.scal, c->f64.partC, c->f64.G, c->f64.gmax,
+                           c->f64.bad);
+        if (c->n_items > 0)
+            hipLaunchKernelGGL(k64_gather, dim3(c->n_items), dim3(NT), 0, c->stream, g, c->n_items, c->d_items, c->d_xy_g, c->d_t_g,
+                               c->d_Theta, c->d_edge_ts, c->f64.G, c->d_wc, c->f64.gmax, c->f64.gacc, c->f64.bad);
+        const unsigned nblk = (unsigned)std::min<size_t>((img * 2 + NT - 1) / NT, 512);
+        hipLaunchKernelGGL(k64_gfin, dim3(nblk, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, ep.gamma, c->d_tvparts, c->d_tvg, c->d_wc,
+                           c->f64.gmax, c->f64.gacc, c->f64.bad, c->f64.gTh);
+        const double* out = c->f64.gTh;
+        if (!identity) {
+            const size_t nT = (size_t)g.B * g.H * w * 2, nO = (size_t)g.B * nth;
+            hipLaunchKernelGGL(k64_proj_w, dim3((unsigned)std::min<size_t>((nT + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, w, c->d_AW,
+                               c->f64.gTh, c->f64.T);
+            hipLaunchKernelGGL(k64_proj_h, dim3((unsigned)std::min<size_t>((nO + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h, w, c->d_AH,
+                               c->f64.T, c->f64.grad);
+            out = c->f64.grad;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->h_grad, out, (size_t)g.B * nth * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipGetLastError());
+    c->n_pieces = 0;
+    c->pend.active = true; c->pend.launched = true; c->pend.ep = ep; c->pend.h = h; c->pend.w = w; c->pend.identity = identity;
+    c->pend.want_grad = want_grad; c->pend.full_aux = full_aux; c->pend.div_grad = div_grad; c->pend.host_asm = false;
+    c->pend.composed = false; c->pend.copy_mode = 0;
+    c->last_composed = false;
+    return EINCM_OK;
+}
+
+// What k_final does, for a float64 evaluation: losses.py:176-203 from the per-image scalars and k_tv's partials, sums in index order.
+void f64_assemble(eincm_ctx* c) {
+    const Geom& g = c->g;
+    const EvalParams& ep = c->pend.ep;
+    const double Rd = (double)g.R;
+    for (int b = 0; b < g.B; ++b) {
+        const WinConst& wc = c->h_wc[b];
+        OutScal& o = c->h_outs[b];
+        memset(&o, 0, sizeof o);
+        if (b < 64 && !((g.wmask >> b) & 1ull)) continue;
+        double src = 0.0, srr = 0.0, srd = 0.0;
+        for (int r = 0; r < g.R; ++r) {
+            const F64Scal& s = c->f64.h_scal[(size_t)b * g.R + r];
+            const double corr = -s.mse, div = ep.want_div ? s.div : NAN;
+            o.corr[r] = corr; o.contrast_gm[r] = s.g2; o.var[r] = s.var; o.div[r] = div;
+            const double con = (ep.contrast_kind == EINCM_CONTRAST_VARIANCE) ? s.var : s.g2;
+            const double c0 = (ep.contrast_kind == EINCM_CONTRAST_VARIANCE) ? wc.c0_var : wc.c0_gradmag;
+            src += wc.mrw[r] * con / (c0 + EPSN);
+            srr += wc.mrw[r] * corr / (wc.zc[r] + EPSN);
+            srd += wc.mrw[r] * div / (wc.d0 + EPSN);
+        }
+        const double mrc = src / Rd, mrr = srr / Rd, mrd = ep.want_div ? srd / Rd : NAN;
+        double val = ep.alpha * (-mrc) + ep.beta * (-mrr);
+        double tv = 0.0;
+        if (ep.want_tv) {
+            double a = 0.0, nz = 0.0;
+            for (int i = 0; i < g.ntiles; ++i) { a += c->h_tvparts[((size_t)b * g.ntiles + i) * 3]; nz += c->h_tvparts[((size_t)b * g.ntiles + i) * 3 + 1]; }
+            tv = a / (nz + EPSN);
+        }
+        double reg = 0.0;
+        if (ep.gamma != 0.0) reg += ep.gamma * ((ep.cur_pyr_lvl <= 0) ? tv : 0.0);
+        if (ep.delta != 0.0) reg += ep.delta * mrd;
+        val += reg;
+        if (c->theta_nan[b]) val = NAN;
+        o.mean_rel_contrast = mrc; o.mean_rel_corr = mrr; o.mean_rel_div = mrd;
+        o.tv = (ep.cur_pyr_lvl <= 0) ? (ep.want_tv ? tv : NAN) : 0.0;
+        o.value = val;
+        o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
+    }
+}
+
 // First half of an evaluation: theta -> Theta -> IWE stack (k_theta, k_splat).  theta_host: (B,h,w,2) doubles.
 int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad, const uint8_t* active = nullptr) {
     HostPhase hp(c, EINCM_HP_BEGIN);
@@ -622,7 +752,7 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
     if (c->pend.active && c->pend.launched)
         return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
     c->pend.active = false; c->pend.launched = false;
-    if (div_grad && !c->d_gdiv) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocate lazily
+    if (div_grad && !c->d_gdiv && !c->fp64) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocate lazily
         HIPCHK(c, dalloc(&c->d_gdiv, (size_t)c->maxB * c->maxR * img));
         HIPCHK(c, dalloc(&c->d_dgparts, (size_t)c->maxB * c->maxR * g.ntiles * 2));
     }
@@ -640,6 +770,16 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         }
         int rc = ensure_resample(c, h, w, p->method);
         if (rc) return rc;
+    }
+    if (c->fp64) {
+        EvalParams ep{};
+        ep.alpha = p->alpha; ep.beta = p->beta; ep.gamma = p->gamma; ep.delta = p->delta;
+        ep.cur_pyr_lvl = p->cur_pyr_lvl; ep.contrast_kind = p->contrast_kind;
+        ep.want_div = (full_aux || p->delta != 0.0) ? 1 : 0;
+        ep.want_tv = ((p->cur_pyr_lvl <= 0) && (p->gamma != 0.0 || full_aux)) ? 1 : 0;
+        ep.use_tv_grad = (ep.want_tv && p->gamma != 0.0 && want_grad && !(p->flags & EINCM_PF_NO_TV_GRAD)) ? 1 : 0;
+        ep.h = h; ep.w = w; ep.identity = identity ? 1 : 0;
+        return f64_launch(c, theta_host, h, w, ep, want_grad, full_aux, div_grad, identity);
     }
     if (c->acc_dirty) { const int rcd = clear_accumulators(c); if (rcd) return rcd; }
     if (c->cflags & EINCM_CF_TIMING_DOMINANT) c->timed_now = (c->time_counter++ % c->time_period) == 0;
@@ -1074,6 +1214,7 @@ int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) 
     if (want_grad && !grad && !dev_io) return fail(c, EINCM_ERR_ARG, "the evaluation was begun with a gradient but grad is NULL");
     HostPhase hp(c, EINCM_HP_COLLECT);
     if (c->pend.host_asm) host_assemble(c);
+    else if (c->fp64) f64_assemble(c);
     int rc = collect_timings(c);
     if (rc) return rc;
     c->have_eval = true;
@@ -1157,7 +1298,10 @@ int store_constants(eincm_ctx* c) {
         wc.inv_c0_gradmag = 1.0 / (wc.c0_gradmag + EPSN); wc.inv_c0_var = 1.0 / (wc.c0_var + EPSN);
     }
     HIPCHK(c, hipMemcpyAsync(c->d_wc, c->h_wc, (size_t)g.B * sizeof(WinConst), hipMemcpyHostToDevice, c->stream));
-    for (int b = 0; b < g.B; ++b)      // keep the IUE of every window (first reference image of the theta = 0 pass)
+    for (int b = 0; b < g.B && c->fp64; ++b)
+        HIPCHK(c, hipMemcpyAsync(c->f64.zero_iwe + (size_t)b * img, c->f64.iwe + (size_t)b * g.R * img, img * sizeof(double),
+                                 hipMemcpyDeviceToDevice, c->stream));
+    for (int b = 0; b < g.B && !c->fp64; ++b)      // keep the IUE of every window (first reference image of the theta = 0 pass)
         HIPCHK(c, hipMemcpyAsync(c->d_zero_iwe + (size_t)b * img, c->d_iwe + (size_t)b * g.R * img, img * sizeof(float),
                                  hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1209,7 +1353,12 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
         fail(nullptr, EINCM_ERR_ARG, "eincm_create: device %d out of range (0..%d)", device, ndev - 1);
         return nullptr;
     }
+    if ((flags & EINCM_CF_FP64) && (flags & (EINCM_CF_TIMING | EINCM_CF_TIMING_DOMINANT))) {
+        fail(nullptr, EINCM_ERR_UNSUPPORTED, "eincm_create: the timing flags are not supported with EINCM_CF_FP64");
+        return nullptr;
+    }
     eincm_ctx* c = new eincm_ctx();
+    c->fp64 = (flags & EINCM_CF_FP64) != 0;
     c->device = device; c->H = H; c->W = W; c->maxR = max_refs; c->maxB = max_windows; c->maxN = max_events_total;
     c->cflags = flags;
     if (const char* s = getenv("EINCM_CHUNK")) { int v = atoi(s); if (v >= NT && v <= MAX_CHUNK) { c->chunk = (v / NT) * NT; c->chunk_fixed = true; } }
@@ -1327,6 +1476,30 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
                 const bool needed = (flags & EINCM_CF_TIMING) || i == EINCM_STAGE_SPLAT || i == EINCM_STAGE_GATHER || i == EINCM_N_STAGES;
                 if (needed) { TRY(hipEventCreate(&c->ev[k][i][0])); TRY(hipEventCreate(&c->ev[k][i][1])); }
             }
+    if (c->fp64) {             // the float64 mode's own buffers (eincm_kernels_f64.hip.h): nothing is allocated per evaluation
+        const int P = (int)((img + F64_PIX - 1) / F64_PIX);
+        c->f64.P = P;
+        TRY(dalloc(&c->f64.acc, B * R * img));
+        TRY(hipMemset(c->f64.acc, 0, B * R * img * sizeof(unsigned long long)));
+        TRY(dalloc(&c->f64.iwe, B * R * img));
+        TRY(dalloc(&c->f64.zero_iwe, B * img));
+        TRY(dalloc(&c->f64.edges, B * R * img));
+        TRY(dalloc(&c->f64.G, B * R * img));
+        TRY(dalloc(&c->f64.sgn, B * R * img));
+        TRY(dalloc(&c->f64.gacc, B * img * 4));
+        TRY(hipMemset(c->f64.gacc, 0, B * img * 4 * sizeof(unsigned long long)));
+        TRY(dalloc(&c->f64.gTh, B * img * 2));
+        TRY(dalloc(&c->f64.T, B * img * 2));
+        TRY(dalloc(&c->f64.grad, B * img * 2));
+        TRY(dalloc(&c->f64.partA, B * R * P * F64_PA));
+        TRY(dalloc(&c->f64.partB, B * R * P * F64_PB));
+        TRY(dalloc(&c->f64.partC, B * R * P * F64_PC));
+        TRY(dalloc(&c->f64.scal, B * R));
+        TRY(hipHostMalloc(reinterpret_cast<void**>(&c->f64.h_scal), B * R * sizeof(F64Scal), hipHostMallocDefault));
+        TRY(dalloc(&c->f64.gmax, B));
+        TRY(dalloc(&c->f64.ishift, B));
+        TRY(dalloc(&c->f64.bad, B));
+    }
     // both event kernels need > 32 KiB... (<= 64 KiB default limit is fine on gfx950, no attribute needed)
 #undef TRY
     return c;
@@ -1736,6 +1909,21 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         HIPCHK(c, hipGetLastError());
     }
 
+    if (c->fp64) {
+        // float64 mode: the edges as handed over, and the scale of each window's u64 IWE accumulator: no pixel can exceed
+        // N_b / (2 pi) (one tap per event and pixel), so 2^ishift with N_b / (2 pi) * 2^ishift < 2^62, capped at 2^52
+        if (sw_flags & EINCM_SW_DEFER_CONSTANTS) { c->staged = false; return fail(c, EINCM_ERR_UNSUPPORTED, "event-sharded staging is not supported in fp64 mode"); }
+        std::vector<int> ish((size_t)n_windows);
+        for (int b = 0; b < n_windows; ++b) {
+            const double bound = std::max(1.0, (double)n_events[b] * 0.15915494309189535);
+            ish[b] = std::min(52, 62 - (int)std::ceil(std::log2(bound)));
+            if (ish[b] < 40) { c->staged = false; return fail(c, EINCM_ERR_UNSUPPORTED, "window %d: %lld events exceed the fp64 mode's IWE scale (2^-40 per tap)", b, (long long)n_events[b]); }
+        }
+        HIPCHK(c, hipMemcpyAsync(c->f64.ishift, ish.data(), ish.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+        for (int b = 0; b < n_windows; ++b)
+            HIPCHK(c, hipMemcpyAsync(c->f64.edges + (size_t)b * n_refs * img, edges_w[b], (size_t)n_refs * img * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));      // ish goes out of scope; the caller's edges may be freed after return
+    }
     // ---- zero-warp constants: one forward pass at theta = 0 (then IWE_r == IUE for every r) ----
     // c0, zc[r], d0 are temporarily 1 so the pass is well defined; store_constants() overwrites them.
     for (int b = 0; b < n_windows; ++b) {
@@ -1804,6 +1992,7 @@ int eincm_set_windows_ptrs(eincm_ctx* c, int n_windows, int n_refs, const int64_
 // ---- event-sharded evaluation: forward half / [caller all-reduces the IWE stack] / finishing half ----
 int eincm_forward_iwe(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, int want_grad) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_forward_iwe (event-sharded mode) is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_forward_iwe called before eincm_set_windows");
     if (!p || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "bad argument");
     if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
@@ -1824,6 +2013,7 @@ int eincm_forward_iwe(eincm_ctx* c, const double* theta, int h, int w, const ein
 
 int eincm_finish_loss_grad(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_finish_loss_grad (event-sharded mode) is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1834,6 +2024,7 @@ int eincm_finish_loss_grad(eincm_ctx* c, double* value, double* grad, eincm_aux*
 int eincm_loss_grad_device(eincm_ctx* c, const double* theta_dev, int h, int w, const eincm_params* p, double theta_abs_max,
                            double* value, double* grad_dev, eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_loss_grad_device is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_loss_grad_device called before eincm_set_windows");
     if (!theta_dev || !p || !value || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "bad argument");
     if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
@@ -1860,6 +2051,7 @@ int eincm_loss_grad_device(eincm_ctx* c, const double* theta_dev, int h, int w, 
 
 int eincm_set_device_results(eincm_ctx* c, int on) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_set_device_results is not supported in fp64 mode (EINCM_CF_FP64)");
     if (c->pend.active) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
     c->device_results = on != 0;
     return EINCM_OK;
@@ -1867,6 +2059,7 @@ int eincm_set_device_results(eincm_ctx* c, int on) {
 
 int eincm_finish_launch(eincm_ctx* c) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_finish_launch is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!c->device_results) return fail(c, EINCM_ERR_STATE, "eincm_finish_launch needs eincm_set_device_results(ctx, 1)");
     if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1878,6 +2071,7 @@ int eincm_finish_launch(eincm_ctx* c) {
 
 int eincm_grad_device_ptr(eincm_ctx* c, void** dptr, int64_t* n_doubles) {
     if (!c || !dptr || !n_doubles) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_grad_device_ptr is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!c->pend.active || !c->pend.launched || !c->pend.want_grad) return fail(c, EINCM_ERR_STATE, "no launched gradient evaluation (eincm_finish_launch)");
     *dptr = c->d_grad; *n_doubles = (int64_t)c->g.B * c->pend.h * c->pend.w * 2;
     return EINCM_OK;
@@ -1885,6 +2079,7 @@ int eincm_grad_device_ptr(eincm_ctx* c, void** dptr, int64_t* n_doubles) {
 
 int eincm_finish_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_finish_collect is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (!c->pend.active || !c->pend.launched) return fail(c, EINCM_ERR_STATE, "eincm_finish_collect without eincm_finish_launch");
     HIPCHK(c, hipSetDevice(c->device));
@@ -1893,6 +2088,7 @@ int eincm_finish_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* a
 
 int eincm_finish_constants(eincm_ctx* c) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_finish_constants (event-sharded mode) is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!c->constants_pending) return fail(c, EINCM_ERR_STATE, "no deferred window constants");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<double> val((size_t)c->g.B);
@@ -1905,6 +2101,7 @@ int eincm_finish_constants(eincm_ctx* c) {
 
 int eincm_iwe_device_ptr(eincm_ctx* c, void** dptr, int64_t* n_words) {
     if (!c || !dptr || !n_words) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_iwe_device_ptr is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!c->staged) return fail(c, EINCM_ERR_STATE, "no staged windows");
     *dptr = c->d_acc; *n_words = (int64_t)c->g.B * c->g.R * c->g.H * c->g.W;
     return EINCM_OK;
@@ -2044,16 +2241,61 @@ static int copy_out(eincm_ctx* c, void* dst, const void* src, size_t bytes) {
     return EINCM_OK;
 }
 
+// The images of a float64 context in either width, and those of an fp32 context widened (the _f64 accessors work in both modes)
+static int copy_image(eincm_ctx* c, const float* src32, const double* src64, size_t n, float* dst32, double* dst64) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!dst32 && !dst64) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (!c->staged) return fail(c, EINCM_ERR_STATE, "no staged windows");
+    if (c->fp64 ? (dst64 != nullptr) : (dst32 != nullptr))
+        return c->fp64 ? copy_out(c, dst64, src64, n * sizeof(double)) : copy_out(c, dst32, src32, n * sizeof(float));
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->fp64) {
+        std::vector<double> tmp(n);
+        HIPCHK(c, hipMemcpy(tmp.data(), src64, n * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) dst32[i] = (float)tmp[i];
+    } else {
+        std::vector<float> tmp(n);
+        HIPCHK(c, hipMemcpy(tmp.data(), src32, n * sizeof(float), hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i) dst64[i] = (double)tmp[i];
+    }
+    return EINCM_OK;
+}
+int eincm_get_iwes_f64(eincm_ctx* c, double* iwes) {
+    if (c && !c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
+    return c ? copy_image(c, c->d_iwe, c->f64.iwe, (size_t)c->g.B * c->g.R * c->g.H * c->g.W, nullptr, iwes) : EINCM_ERR_ARG;
+}
+int eincm_get_zero_iwe_f64(eincm_ctx* c, double* z) {
+    return c ? copy_image(c, c->d_zero_iwe, c->f64.zero_iwe, (size_t)c->g.B * c->g.H * c->g.W, nullptr, z) : EINCM_ERR_ARG;
+}
+int eincm_get_image_grad_f64(eincm_ctx* c, double* G) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!c->fp64) {
+        std::vector<float> tmp((size_t)c->g.B * c->g.R * c->g.H * c->g.W);
+        const int rc = eincm_get_image_grad(c, tmp.data());
+        if (rc) return rc;
+        if (!G) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+        for (size_t i = 0; i < tmp.size(); ++i) G[i] = (double)tmp[i];
+        return EINCM_OK;
+    }
+    if (!c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
+    if (!c->G_valid) return fail(c, EINCM_ERR_STATE, "no dL/dIWE image: the last evaluation had no gradient");
+    return copy_image(c, nullptr, c->f64.G, (size_t)c->g.B * c->g.R * c->g.H * c->g.W, nullptr, G);
+}
+
 int eincm_get_iwes(eincm_ctx* c, float* iwes) {
     if (c && !c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
+    if (c && c->fp64) return copy_image(c, nullptr, c->f64.iwe, (size_t)c->g.B * c->g.R * c->g.H * c->g.W, iwes, nullptr);
     return copy_out(c, iwes, c ? c->d_iwe : nullptr, c ? (size_t)c->g.B * c->g.R * c->g.H * c->g.W * sizeof(float) : 0);
 }
 int eincm_get_zero_iwe(eincm_ctx* c, float* z) {
+    if (c && c->fp64) return copy_image(c, nullptr, c->f64.zero_iwe, (size_t)c->g.B * c->g.H * c->g.W, z, nullptr);
     return copy_out(c, z, c ? c->d_zero_iwe : nullptr, c ? (size_t)c->g.B * c->g.H * c->g.W * sizeof(float) : 0);
 }
 int eincm_get_image_grad(eincm_ctx* c, float* G) {
     if (c && !c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
     if (c && !c->G_valid) return fail(c, EINCM_ERR_STATE, "no dL/dIWE image: the last evaluation had no gradient, or eincm_get_count_images reused the buffer");
+    if (c && c->fp64) return copy_image(c, nullptr, c->f64.G, (size_t)c->g.B * c->g.R * c->g.H * c->g.W, G, nullptr);
     if (c && c->last_composed) {
         // the gather composed dL/dIWE while staging its windows; materialise the same image (same function, same scalars) on demand
         HIPCHK(c, hipSetDevice(c->device));
@@ -2099,7 +2341,7 @@ int eincm_get_count_images(eincm_ctx* c, uint32_t* counts) {
     const size_t n = (size_t)g.B * g.R * g.H * g.W;
     // the dL/dIWE buffer is free between evaluations and has exactly this many 4-byte cells
     uint32_t* d = reinterpret_cast<uint32_t*>(c->d_G);
-    c->G_valid = false;
+    if (!c->fp64) c->G_valid = false;               // (an fp64 context keeps dL/dIWE in its own buffer)
     HIPCHK(c, hipMemsetAsync(d, 0, n * sizeof(uint32_t), c->stream));
     if (c->n_items > 0)
         hipLaunchKernelGGL(k_count, dim3(event_grid(c)), dim3(NT), 0, c->stream, g, c->n_items, c->d_items, c->d_xy, c->d_t, c->d_Theta,
@@ -2224,6 +2466,7 @@ int eincm_gaussian_blur(eincm_ctx* c, const double* src, int n, double sigma, do
 
 int eincm_tiled_objectives(eincm_ctx* c, int tile_h, int tile_w, eincm_tiled_out* out) {
     if (!c) return EINCM_ERR_ARG;
+    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_tiled_objectives is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!out) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (!c->staged || !c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
     Geom g = c->g;

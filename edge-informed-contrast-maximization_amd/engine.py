@@ -48,11 +48,22 @@ def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contr
                     int(contrast_kind), L.PF_FULL_AUX if full_aux else 0)
 
 
+def check_precision(precision):
+    """'fp32' or 'fp64'; anything else is a ValueError."""
+    if precision not in L.PRECISIONS:
+        raise ValueError(f"precision {precision!r}: 'fp32' or 'fp64'")
+    return precision
+
+
 class Engine:
     """One GPU context.  ``set_windows`` stages a batch of B independent windows (B = 1 for the reference's
     single-window solver, solver.py:185-194); ``loss_grad`` evaluates value_and_grad(loss_func) for all of them."""
 
-    def __init__(self, sensor_size, max_events_total, max_refs=8, max_windows=1, device=0, timing=False):
+    def __init__(self, sensor_size, max_events_total, max_refs=8, max_windows=1, device=0, timing=False, precision='fp32'):
+        # precision: 'fp32' (default) or 'fp64' - the same objective with fp64 arithmetic after the warp (DESIGN.md section 10; the
+        # reference's jax_enable_x64: true).  Checked before the GPU is touched.
+        self.precision = check_precision(precision)
+        self._ctx = None
         self._lib = L.load()
         self.H, self.W = int(sensor_size[0]), int(sensor_size[1])
         self.max_windows = int(max_windows)
@@ -60,6 +71,8 @@ class Engine:
         # timing: False | True (every stage bracketed by marker events, ~20 % slower) | 'dominant' (the two event kernels
         # launched with their own start/stop events, read out on demand: see set_timed_kernels)
         flags = 0 if not timing else (L.CF_TIMING_DOMINANT if timing == 'dominant' else L.CF_TIMING)
+        if self.precision == 'fp64':
+            flags |= L.CF_FP64
         self._ctx = self._lib.eincm_create(int(device), self.H, self.W, int(max_refs), int(max_windows),
                                            int(max_events_total), flags)
         if not self._ctx:
@@ -380,16 +393,28 @@ class Engine:
 
     # -- device images ----------------------------------------------------------------------------
     def iwes(self):
+        if self.precision == 'fp64':
+            a = np.empty((self.B, self.R, self.H, self.W), dtype=np.float64)
+            self._check(self._lib.eincm_get_iwes_f64(self._ctx, a.ctypes.data_as(C.POINTER(C.c_double))))
+            return a
         a = np.empty((self.B, self.R, self.H, self.W), dtype=np.float32)
         self._check(self._lib.eincm_get_iwes(self._ctx, a.ctypes.data_as(C.POINTER(C.c_float))))
         return a
 
     def zero_iwe(self):
+        if self.precision == 'fp64':
+            a = np.empty((self.B, self.H, self.W), dtype=np.float64)
+            self._check(self._lib.eincm_get_zero_iwe_f64(self._ctx, a.ctypes.data_as(C.POINTER(C.c_double))))
+            return a
         a = np.empty((self.B, self.H, self.W), dtype=np.float32)
         self._check(self._lib.eincm_get_zero_iwe(self._ctx, a.ctypes.data_as(C.POINTER(C.c_float))))
         return a
 
     def image_grad(self):
+        if self.precision == 'fp64':
+            a = np.empty((self.B, self.R, self.H, self.W), dtype=np.float64)
+            self._check(self._lib.eincm_get_image_grad_f64(self._ctx, a.ctypes.data_as(C.POINTER(C.c_double))))
+            return a
         a = np.empty((self.B, self.R, self.H, self.W), dtype=np.float32)
         self._check(self._lib.eincm_get_image_grad(self._ctx, a.ctypes.data_as(C.POINTER(C.c_float))))
         return a
@@ -476,10 +501,12 @@ class EngineGroup:
     another: on MI355X the 8-window / 10^6-event batch gains 18 % (2 groups) to 25 % (4 groups) over a single context.
     Same call shapes as ``Engine`` for set_windows / loss_grad; results are concatenated in window order."""
 
-    def __init__(self, sensor_size, max_events_total, max_refs=8, max_windows=1, n_groups=2, device=0, timing=False):
+    def __init__(self, sensor_size, max_events_total, max_refs=8, max_windows=1, n_groups=2, device=0, timing=False, precision='fp32'):
+        self.precision = check_precision(precision)
         self.n_groups = max(1, min(int(n_groups), int(max_windows)))
         per = -(-int(max_windows) // self.n_groups)
-        self.engines = [Engine(sensor_size, max_events_total, max_refs=max_refs, max_windows=per, device=device, timing=timing)
+        self.engines = [Engine(sensor_size, max_events_total, max_refs=max_refs, max_windows=per, device=device, timing=timing,
+                               precision=precision)
                         for _ in range(self.n_groups)]
         self.H, self.W = self.engines[0].H, self.engines[0].W
         self.B = 0

@@ -22,7 +22,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, make_params
+from .engine import Engine, check_precision, make_params
 
 _CACHE = []            # [(refs tuple, key, Engine)] most-recent first
 _CACHE_SIZE = 2
@@ -46,11 +46,13 @@ def _fingerprint(arrs):
     return hash(tuple(parts))
 
 
-def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0):
-    """Engine holding this window (staged on first use; reused while the same, unmodified array objects are passed)."""
+def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp32'):
+    """Engine holding this window (staged on first use; reused while the same, unmodified array objects are passed).  One engine per
+    precision: 'fp64' is the float64 mode (Engine(..., precision='fp64'))."""
+    check_precision(precision)
     arrs = tuple(_as_np(a) for a in (xs, ys, ts, edges, edge_ts))
     fp = _fingerprint(arrs)
-    key = (tuple(int(s) for s in sensor_size), device) + tuple((a.shape, a.dtype.str) for a in arrs)
+    key = (tuple(int(s) for s in sensor_size), device, precision) + tuple((a.shape, a.dtype.str) for a in arrs)
     for i, (refs, k, eng) in enumerate(_CACHE):
         if k[:-1] == key and all(r() is a for r, a in zip(refs, arrs)):
             if k[-1] != fp:                       # same objects, edited in place: stage again
@@ -61,7 +63,7 @@ def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0):
             return eng
     key = key + (fp,)
     eng = Engine(sensor_size, max_events_total=max(len(arrs[0]), 1), max_refs=max(len(np.atleast_1d(arrs[4])), 1),
-                 max_windows=1, device=device)
+                 max_windows=1, device=device, precision=precision)
     eng.set_window(*arrs)
     try:
         refs = tuple(weakref.ref(a) for a in arrs)
@@ -90,18 +92,19 @@ def _aux_dict(eng, a, with_arrays):
 
 def value_and_grad_loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls,
                              sensor_size, scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
-                             full_aux=False, aux_arrays=False):
-    """((final_loss, aux_info), grad) — the shape jax.value_and_grad(loss_func, has_aux=True) returns."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size)
+                             full_aux=False, aux_arrays=False, precision='fp32'):
+    """((final_loss, aux_info), grad) — the shape jax.value_and_grad(loss_func, has_aux=True) returns.  precision='fp64': the engine's
+    float64 mode (what the reference computes with jax_enable_x64: true)."""
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux)
     v, g, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=True, want_aux=True)
     return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
 
 
 def loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
-              scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG):
+              scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, precision='fp32'):
     """(final_loss, aux_info) as losses.py:108-205; forward only, every aux entry evaluated."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True)
     v, _, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=False, want_aux=True)
     return float(v[0]), _aux_dict(eng, aux[0], True)
@@ -109,9 +112,9 @@ def loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_
 
 def value_and_grad_handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma,
                                       delta, cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
-                                      contrast_kind=L.CONTRAST_GRAD_MAG):
+                                      contrast_kind=L.CONTRAST_GRAD_MAG, precision='fp32'):
     """(loss, d loss / d alpha_handover) of losses.py:269-276."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False)
     v, dv = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=True)
     return float(v[0]), float(dv[0])
@@ -119,18 +122,18 @@ def value_and_grad_handover_loss_func(alpha_handover, prev_theta, theta, xs, ys,
 
 def handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta,
                        cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
-                       contrast_kind=L.CONTRAST_GRAD_MAG):
+                       contrast_kind=L.CONTRAST_GRAD_MAG, precision='fp32'):
     """loss only, as losses.py:208-276."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False)
     v, _ = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=False)
     return float(v[0])
 
 
-def compute_loss_objectives(theta, xs, ys, ts, edges, edge_ts, sensor_size, warped_events=True):
+def compute_loss_objectives(theta, xs, ys, ts, edges, edge_ts, sensor_size, warped_events=True, precision='fp32'):
     """losses.py:49-105 on a full-resolution theta (H,W,2): every key of the reference dict.  The per-event ``warped_xs`` /
     ``warped_ys`` ((R, n_events) float64, read by plotters only) cost a 2*R*n_events*8-byte copy: ``warped_events=False`` skips them."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
     d = eng.objectives(np.asarray(theta, dtype=np.float64))[0]
     if warped_events:
         d['warped_xs'], d['warped_ys'] = eng.warped_events(0)

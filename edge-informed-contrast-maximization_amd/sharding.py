@@ -95,6 +95,9 @@ class ShardedEngine:
         pays 2 (n - 1) hops).  device_results: keep the gradient in HBM and all-reduce it there (default: whenever the backend is
         'nccl').  NOTE: the 'nccl' (= RCCL) branches and 'rs_ag' have never run on hardware - the builder had no multi-GPU node - and
         are covered only as far as a single process can (tests/test_gpu_sharded.py); gloo rehearsals take the host-bounced branches."""
+        if getattr(engine, 'precision', 'fp32') != 'fp32':
+            raise ValueError(f"ShardedEngine: an engine of precision {engine.precision!r} cannot be sharded (event-sharded evaluation is "
+                             "fp32 only: the fp64 mode has no device-resident entry points)")
         import torch.distributed as dist
         if iwe_collective not in ('all_reduce', 'rs_ag'):
             raise ValueError(f'iwe_collective {iwe_collective!r}: all_reduce or rs_ag')

@@ -42,13 +42,15 @@ def main():
     ap.add_argument('--sequences', type=int, default=1,
                     help='> 1: that many independent sequences side by side on the lockstep batch solver (one masked engine call per tick)')
     ap.add_argument('--rank2', action='store_true', help="sequential driver with the O(n^2) BFGS update (theta_opt_solver_params['bfgs_update'] = 'rank2')")
+    ap.add_argument('--precision', choices=('fp32', 'fp64'), default='fp32',
+                    help="fp64: the engine's float64 mode (the reference config's jax_enable_x64: true; the config reader does not switch it)")
     ap.add_argument('overrides', nargs='*')
     a = ap.parse_args()
     cfg = config.load_config(a.config_dir, 'main', a.overrides) if a.config_dir else config._wrap(DEFAULTS)
     H, W = cfg.dataset.sensor_size
     n_lvls = cfg.n_pyr_lvls
     kw = dict(alpha=cfg.alpha, beta=cfg.beta, gamma=cfg.gamma, delta=cfg.delta, n_pyr_lvls=n_lvls, sensor_size=(H, W),
-              scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method)
+              scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method, precision=a.precision)
     sp = cfg.solver_params
     if a.sequences > 1:
         return run_batched(a, cfg, H, W, n_lvls)
@@ -81,7 +83,7 @@ def main():
         theta = out['final_theta_pyr']['pyr_lvl_0']
         Theta = sol.rescale_theta(theta, (H, W), 'bilinear')
         ev, _ = evaluation.evaluate_theta_array(Theta, xs, ys, ts, edges, edge_ts, win['flow_gt'], cfg.alpha, cfg.beta, cfg.gamma, cfg.delta,
-                                                (H, W), evaluation.make_event_mask(xs, ys, (H, W)))
+                                                (H, W), evaluation.make_event_mask(xs, ys, (H, W)), precision=a.precision)
         n_it = sum(st.iter_num for st in out['theta_opt_state_pyr'].values())
         ho = {k: round(float(v), 3) for k, v in out['final_handover_weight_pyr'].items() if k in out['ho_opt_state_pyr']}
         print(f'window {i}: {n_it} BFGS iterations in {t_solve*1e3:.1f} ms | loss {ev["loss"]:.4f} FWL {ev["fwl"]:.4f} AEE {ev["AEE"]:.3f} '
@@ -107,7 +109,8 @@ def run_batched(a, cfg, H, W, n_lvls):
     from its own previous window (batch_solver.BatchedMultipleLevelEINCMSolver; two engine contexts, pipelined)."""
     from eincm_amd import batch_solver as bsol
     B, sp = a.sequences, cfg.solver_params
-    loss = dict(alpha=cfg.alpha, beta=cfg.beta, gamma=cfg.gamma, delta=cfg.delta, scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method)
+    loss = dict(alpha=cfg.alpha, beta=cfg.beta, gamma=cfg.gamma, delta=cfg.delta, scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method,
+                precision=a.precision)
     bs = bsol.BatchedMultipleLevelEINCMSolver(
         B, (H, W), n_lvls,
         sol.growing_maxiters(n_lvls, sp.theta_opt.miniter, sp.theta_opt.maxiter, cfg.maxiters_grow_order, cfg.use_growing_maxiters), loss,
@@ -127,7 +130,7 @@ def run_batched(a, cfg, H, W, n_lvls):
         for b, ((xs, ys, ts, edges, edge_ts), win) in enumerate(staged):
             Theta = sol.rescale_theta(outs[b]['final_theta_pyr']['pyr_lvl_0'], (H, W), 'bilinear')
             ev, _ = evaluation.evaluate_theta_array(Theta, xs, ys, ts, edges, edge_ts, win['flow_gt'], cfg.alpha, cfg.beta, cfg.gamma, cfg.delta,
-                                                    (H, W), evaluation.make_event_mask(xs, ys, (H, W)))
+                                                    (H, W), evaluation.make_event_mask(xs, ys, (H, W)), precision=a.precision)
             scores.append((ev['fwl'], ev['AEE']))
             print(f'window {i} of sequence {b}: loss {ev["loss"]:.4f} FWL {ev["fwl"]:.4f} AEE {ev["AEE"]:.3f}')
         print(f'window {i}: {B} windows solved in {t_solve * 1e3:.1f} ms ({bs.n_batch_evals} engine calls so far)')

@@ -33,7 +33,7 @@ extern "C" {
 #define EINCM_ERR_HIP         -2   /* HIP runtime error (message holds hipGetErrorString) */
 #define EINCM_ERR_STATE       -3   /* call out of order (e.g. loss_grad before set_windows) */
 #define EINCM_ERR_NONFINITE   -4   /* loss or gradient is NaN/Inf (outputs are still written) */
-#define EINCM_ERR_UNSUPPORTED -5   /* valid request this build does not implement (currently unused) */
+#define EINCM_ERR_UNSUPPORTED -5   /* valid request this build does not implement (e.g. a device-resident entry point of an EINCM_CF_FP64 context) */
 
 /* contrast objective: 0 = mean squared Scharr gradient magnitude of the raw IWE (losses.py:70, the reference's
  * live objective); 1 = variance of the IWE (contrast_objectives.py:29-39; BASELINE config "variance-only") */
@@ -59,6 +59,12 @@ extern "C" {
                                      * (hipExtLaunchKernelGGL: no marker packets on the stream) and the events are read when the
                                      * timings are asked for, not after every evaluation; total_ms stays 0 in this mode.
                                      * eincm_set_timed_kernels narrows it to one of the two */
+
+#define EINCM_CF_FP64 4u          /* float64 mode: the same objective and gradient with fp64 arithmetic after the warp (fp64 taps, a u64 IWE
+                                    * accumulator at >= 2^40 per unit, fp64 images, an exact 128-bit fixed-point gradient sum; DESIGN.md
+                                    * section 10).  The reference's jax_enable_x64: true.  Not with the timing flags, the device-resident
+                                    * entry points (eincm_loss_grad_device, eincm_set_device_results ... eincm_finish_collect,
+                                    * eincm_iwe_device_ptr), event-sharded staging or eincm_tiled_objectives: those return EINCM_ERR_UNSUPPORTED */
 
 typedef struct eincm_ctx eincm_ctx;
 
@@ -197,12 +203,18 @@ int eincm_get_iwes(eincm_ctx* ctx, float* iwes);
 int eincm_get_zero_iwe(eincm_ctx* ctx, float* zero_iwe);
 int eincm_get_image_grad(eincm_ctx* ctx, float* image_grad);
 int eincm_get_scaled_theta(eincm_ctx* ctx, double* scaled_theta);
+/* The same images as float64 (the fp64 images of an EINCM_CF_FP64 context; an fp32 context's images widened).  The float forms
+ * above return an EINCM_CF_FP64 context's images rounded to float. */
+int eincm_get_iwes_f64(eincm_ctx* ctx, double* iwes);
+int eincm_get_zero_iwe_f64(eincm_ctx* ctx, double* zero_iwe);
+int eincm_get_image_grad_f64(eincm_ctx* ctx, double* image_grad);
 
 /* Integer image of the rounded warped coordinates under the Theta of the last evaluation:
  * counts[b,r,ry,rx] = #{events of window b with round(warp(x,y,t; tau_r)) = (rx,ry)}, JAX wrap/drop index rule
  * (the centre tap of events_to_pdf_frame, src/utils/event_utils.py:32-33,59).  counts (n_windows, n_refs, H, W) uint32.
  * The IWE is a float image; this is its integer skeleton and must equal the reference's bit for bit.
- * Overwrites the dL/dIWE image of the last evaluation (eincm_get_image_grad must be called before it). */
+ * Overwrites the dL/dIWE image of the last evaluation (eincm_get_image_grad must be called before it) in fp32 contexts;
+ * an EINCM_CF_FP64 context keeps it. */
 int eincm_get_count_images(eincm_ctx* ctx, uint32_t* counts);
 
 /* The warped coordinates themselves: warped_xs[r,i] = x_i - Theta[y_i,x_i,0]*(t_i - tau_r) (and ys with component 1) of ONE window's events,

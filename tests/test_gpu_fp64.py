@@ -1,0 +1,297 @@
+"""The float64 mode (Engine(..., precision='fp64'), EINCM_CF_FP64) against the float64 C port and the numpy oracle, its determinism, its
+batch form, the optimiser behaviour it exists for, and what it refuses.  Tolerances are max-norm relative."""
+import ctypes as C
+import importlib
+from functools import partial
+
+import numpy as np
+import pytest
+
+from oracle import eincm_c_port as CP
+from oracle import eincm_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+synth = importlib.import_module('edge-informed-contrast-maximization_amd.synth')
+engine = importlib.import_module('edge-informed-contrast-maximization_amd.engine')
+losses = importlib.import_module('edge-informed-contrast-maximization_amd.losses')
+solver = importlib.import_module('edge-informed-contrast-maximization_amd.solver')
+L = importlib.import_module('edge-informed-contrast-maximization_amd._lib')
+
+A, BETA = 20.0, 35.0
+
+
+def args_of(win):
+    return (win['xs'], win['ys'], win['ts'], win['edges'], win['edge_ts'])
+
+
+def rel(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+
+
+def run_engine(win, theta, precision, gamma=0.0, delta=0.0, lvl=1, method='bilinear', kind=L.CONTRAST_GRAD_MAG):
+    H, W = win['sensor_size']
+    with engine.Engine((H, W), len(win['xs']), max_refs=len(win['edge_ts']), precision=precision) as eng:
+        eng.set_window(*args_of(win))
+        v, g, _ = eng.loss_grad(theta, engine.make_params(A, BETA, gamma, delta, lvl, method, kind))
+        return float(v[0]), g[0], eng.iwes()[0], eng.image_grad()[0]
+
+
+def hot_pixel_window():
+    win = synth.make_window(5, (180, 240), 20_000, 3, flow='constant', flow_mag=8.0)
+    win['xs'] = win['xs'].copy(); win['ys'] = win['ys'].copy()
+    win['xs'][:4000] = 100; win['ys'][:4000] = 60          # a hot pixel: a fifth of the events on one source pixel
+    return win
+
+
+# id, window factory, theta factory, method
+PORT_CASES = [
+    ('180x240_1e4_R1_2dof', lambda: synth.make_window(1, (180, 240), 10_000, 1, flow='constant', flow_mag=10.0), (1, 1), 'bilinear'),
+    ('260x346_1e5_R5_2dof', lambda: synth.make_window(2, (260, 346), 100_000, 5, flow='constant', flow_mag=20.0), (1, 1), 'bilinear'),
+    ('260x346_1e5_R5_16x16_bilinear', lambda: synth.make_window(3, (260, 346), 100_000, 5, flow='smooth', flow_mag=20.0), (16, 16), 'bilinear'),
+    ('260x346_1e5_R5_16x16_lanczos3', lambda: synth.make_window(3, (260, 346), 100_000, 5, flow='smooth', flow_mag=20.0), (16, 16), 'lanczos3'),
+    ('480x640_1e5_R3_dense', lambda: synth.make_window(4, (480, 640), 100_000, 3, flow='smooth', flow_mag=15.0), 'dense', 'bilinear'),
+    ('hot_pixel', hot_pixel_window, (1, 1), 'bilinear'),
+    ('large_displacement', lambda: synth.make_window(6, (180, 240), 50_000, 3, flow='constant', flow_mag=10.0), 'far', 'bilinear'),
+    ('1e6_window', lambda: synth.make_window(7, (260, 346), 1_000_000, 5, flow='constant', flow_mag=20.0), (1, 1), 'bilinear'),
+]
+
+
+def theta_for(win, spec):
+    if spec == 'dense':
+        return win['flow_gt'] * 0.9
+    if spec == 'far':
+        return np.array([[[60.0, -45.0]]])
+    return synth.theta_near_truth(11, win, spec)
+
+
+@pytest.mark.parametrize('case', PORT_CASES, ids=[c[0] for c in PORT_CASES])
+def test_parity_with_the_fp64_port(built_lib, case):
+    _, make, spec, method = case
+    win = make()
+    H, W = win['sensor_size']
+    theta = theta_for(win, spec)
+    if spec == 'far':          # about a fifth of the warped events leave the frame (JAX wrap/drop)
+        dts = win['ts'][None, :] - win['edge_ts'][:, None]
+        wx = win['xs'][None, :] - theta[0, 0, 0] * dts
+        wy = win['ys'][None, :] - theta[0, 0, 1] * dts
+        out = np.mean((np.rint(wx) < 0) | (np.rint(wx) >= W) | (np.rint(wy) < 0) | (np.rint(wy) >= H))
+        assert 0.1 < out < 0.4, out
+    v_p, g_p, im = CP.loss_and_grad(theta, *args_of(win), A, BETA, (H, W), method, return_images=True)
+    v64, g64, I64, G64 = run_engine(win, theta, 'fp64', method=method)
+    v32, g32, I32, G32 = run_engine(win, theta, 'fp32', method=method)
+    assert I64.dtype == np.float64 and G64.dtype == np.float64
+    ev, eg, ei, eG = abs(v64 - v_p) / abs(v_p), rel(g64, g_p), rel(I64, im['iwes']), rel(G64, im['G'])
+    assert ev <= 1e-10, ev
+    assert eg <= 1e-9, eg
+    assert ei <= 1e-11, ei
+    assert eG <= 1e-10, eG
+    # the mode is really in effect: at least 100x below the fp32 engine's errors on the same case
+    assert ei * 100 <= rel(I32, im['iwes']), (ei, rel(I32, im['iwes']))
+    assert eg * 100 <= rel(g32, g_p), (eg, rel(g32, g_p))
+
+
+ORACLE_CASES = [
+    # id, theta spec, gamma, delta, lvl, kind
+    ('tv_level0', (4, 4), 2.5e-3, 0.0, 0, L.CONTRAST_GRAD_MAG),
+    ('delta', (4, 4), 0.0, 0.7, 1, L.CONTRAST_GRAD_MAG),
+    ('variance', (1, 1), 0.0, 0.0, 1, L.CONTRAST_VARIANCE),
+    ('dense_tv_delta', 'dense', 1e-3, 0.3, 0, L.CONTRAST_GRAD_MAG),
+]
+
+
+@pytest.mark.parametrize('case', ORACLE_CASES, ids=[c[0] for c in ORACLE_CASES])
+def test_parity_with_the_oracle(built_lib, case):
+    _, spec, gamma, delta, lvl, kind = case
+    win = synth.make_window(21, (48, 64), 6_000, 3, flow='smooth', flow_mag=6.0)
+    theta = theta_for(win, spec)
+    v_o, g_o, aux = O.loss_and_grad(theta, *args_of(win), A, BETA, gamma, delta, lvl, 5, (48, 64), 'bilinear', kind,
+                                    return_intermediates=True)
+    v, g, I, G = run_engine(win, theta, 'fp64', gamma, delta, lvl, kind=kind)
+    assert abs(v - v_o) / abs(v_o) <= 1e-10
+    assert rel(g, g_o) <= 1e-9, rel(g, g_o)
+    assert rel(I, aux['_iwes']) <= 1e-11
+    assert rel(G, aux['_G']) <= 1e-10, rel(G, aux['_G'])
+
+
+def test_handover_and_objectives_against_the_oracle(built_lib):
+    win = synth.make_window(22, (48, 64), 6_000, 3, flow='smooth', flow_mag=6.0)
+    a = args_of(win)
+    prev = synth.theta_near_truth(1, win, (4, 4)); th = synth.theta_near_truth(2, win, (4, 4))
+    kw = dict(alpha=A, beta=BETA, gamma=0.0, delta=0.0, cur_pyr_lvl=1, n_pyr_lvls=3, sensor_size=(48, 64), precision='fp64')
+    v, dv = losses.value_and_grad_handover_loss_func(0.4, prev, th, *a, **kw)
+    v_o, dv_o = O.handover_loss_and_grad(0.4, prev, th, *a, A, BETA, 0.0, 0.0, 1, 3, (48, 64))
+    assert abs(v - v_o) / abs(v_o) <= 1e-10
+    assert abs(dv - dv_o) / abs(dv_o) <= 1e-9
+    Theta = O.scale_theta_to_sensor_size(th, (48, 64))
+    d = losses.compute_loss_objectives(Theta, *a, (48, 64), precision='fp64')
+    ref = O.compute_loss_objectives(Theta, *a, (48, 64))
+    for k in ('correlations', 'zero_correlations', 'rel_correlations', 'contrasts', 'zero_contrast', 'rel_contrasts', 'iwe_divergences',
+              'zero_iwe_divergence', 'rel_iwe_divergences', 'flow_warp_losses', 'theta_total_variation', 'theta_divergence'):
+        assert rel(d[k], ref[k]) <= 1e-10, (k, rel(d[k], ref[k]))
+    losses.clear_engine_cache()
+
+
+DET_CASES = [('2dof', (1, 1), 0.0, 0.0, 4), ('16x16_tv', (16, 16), 2.5e-4, 0.0, 0), ('dense_tv', 'dense', 2.5e-4, 0.0, 0),
+             ('delta', (4, 4), 0.0, 0.5, 2)]
+
+
+@pytest.mark.parametrize('case', DET_CASES, ids=[c[0] for c in DET_CASES])
+def test_fp64_is_bit_reproducible(built_lib, case):
+    _, spec, gamma, delta, lvl = case
+    win = synth.make_window(31, (120, 160), 100_000, 3, flow='smooth', flow_mag=15.0)
+    theta = theta_for(win, spec)
+    p = engine.make_params(A, BETA, gamma, delta, lvl)
+    outs = []
+    for fresh in range(2):
+        with engine.Engine((120, 160), 100_000, max_refs=3, precision='fp64') as eng:
+            for stage in range(2):
+                eng.set_window(*args_of(win))
+                for _ in range(2):
+                    v, g, _ = eng.loss_grad(theta, p)
+                    outs.append((v.tobytes(), g.tobytes(), eng.iwes().tobytes(), eng.image_grad().tobytes()))
+    assert all(o == outs[0] for o in outs)
+
+
+def test_masked_batch_matches_single_windows(built_lib):
+    wins = [synth.make_window(40 + b, (120, 160), 30_000 + 1000 * b, 3, flow='constant', flow_mag=10.0) for b in range(8)]
+    thetas = np.stack([synth.theta_near_truth(b, w, (4, 4)) for b, w in enumerate(wins)])
+    p = engine.make_params(A, BETA, 0.0, 0.0, 1)
+    active = np.array([1, 0, 1, 1, 0, 1, 1, 1], dtype=np.uint8)
+    with engine.Engine((120, 160), sum(len(w['xs']) for w in wins), max_refs=3, max_windows=8, precision='fp64') as eng:
+        eng.set_windows([args_of(w) for w in wins])
+        vb, gb, _ = eng.loss_grad(thetas, p, active=active)
+        eng.loss_grad_async(thetas, p, active=active)
+        va, ga, _ = eng.loss_grad_wait()
+    assert np.array_equal(vb, va, equal_nan=True) and np.array_equal(gb, ga)
+    for b, w in enumerate(wins):
+        if not active[b]:
+            assert np.isnan(vb[b]) and not gb[b].any()
+            continue
+        v, g, _, _ = run_engine(w, thetas[b], 'fp64')
+        assert abs(vb[b] - v) / abs(v) <= 1e-12
+        assert rel(gb[b], g) <= 1e-10
+
+
+def _bfgs(fun, x0, args, lvl, maxiter):
+    n = [0]
+
+    def cnt(theta, *a, **k):
+        n[0] += 1
+        return fun(theta, *a, **k)
+    s = solver.ScipyMinimize(fun=partial(cnt, cur_pyr_lvl=lvl), method='BFGS', maxiter=maxiter, has_aux=True, options={'gtol': 1e-7})
+    th, st = s.run(x0, *args)
+    return th, st, n[0]
+
+
+def test_bfgs_on_fp64_behaves_like_the_fp64_port(built_lib):
+    H, W = 260, 346
+    win = synth.make_window(1, (H, W), 100_000, 5, flow='constant', flow_mag=20.0)
+    a = args_of(win)
+
+    def port_vg(theta, xs, ys, ts, edges, edge_ts, cur_pyr_lvl):
+        v, g = CP.loss_and_grad(theta, xs, ys, ts, edges, edge_ts, A, BETA, (H, W))
+        return (v, {}), g
+    hip_vg = partial(losses.value_and_grad_loss_func, alpha=A, beta=BETA, gamma=0.0, delta=0.0, n_pyr_lvls=5, sensor_size=(H, W),
+                     precision='fp64')
+    start = np.zeros((1, 1, 2))
+    for lvl, hw, maxiter in ((4, (1, 1), 8), (3, (2, 2), 11)):
+        x0 = np.repeat(np.repeat(start, hw[0] // start.shape[0], 0), hw[1] // start.shape[1], 1)
+        th_h, st_h, n_h = _bfgs(hip_vg, x0, a, lvl, maxiter)
+        th_p, st_p, n_p = _bfgs(port_vg, x0, a, lvl, maxiter)
+        assert st_h.status == st_p.status and st_h.iter_num == st_p.iter_num, (lvl, st_h.status, st_p.status, st_h.iter_num, st_p.iter_num)
+        assert abs(n_h - n_p) <= 2, (lvl, n_h, n_p)
+        assert np.abs(th_h - th_p).max() <= 1e-5, (lvl, np.abs(th_h - th_p).max())
+        start = th_p
+    losses.clear_engine_cache()
+
+
+def test_refusals(built_lib):
+    win = synth.make_window(50, (48, 64), 3_000, 2, flow='constant', flow_mag=4.0)
+    lib = L.load()
+    with engine.Engine((48, 64), 3_000, max_refs=2, precision='fp64') as eng:
+        assert eng.precision == 'fp64'
+        eng.set_window(*args_of(win))
+        eng.loss_grad(np.zeros((1, 1, 2)), engine.make_params(A, BETA, 0.0, 0.0, 1))
+        ptr, n = C.c_void_p(), C.c_int64()
+        for rc in (lib.eincm_iwe_device_ptr(eng._ctx, C.byref(ptr), C.byref(n)),
+                   lib.eincm_grad_device_ptr(eng._ctx, C.byref(ptr), C.byref(n)),
+                   lib.eincm_set_device_results(eng._ctx, 1),
+                   lib.eincm_finish_launch(eng._ctx)):
+            assert rc == L.ERR_UNSUPPORTED
+            assert 'fp64' in lib.eincm_last_error(eng._ctx).decode()
+        prm = engine.make_params(A, BETA, 0.0, 0.0, 1)
+        val = np.zeros(1)
+        assert lib.eincm_loss_grad_device(eng._ctx, None, 1, 1, C.byref(prm), -1.0, val.ctypes.data_as(C.POINTER(C.c_double)), None,
+                                          None) == L.ERR_UNSUPPORTED
+        with pytest.raises(engine.EincmError, match='fp64'):
+            eng.tiled_objectives()
+        th = np.zeros(2)
+        for rc in (lib.eincm_finish_collect(eng._ctx, val.ctypes.data_as(C.POINTER(C.c_double)), None, None),
+                   lib.eincm_forward_iwe(eng._ctx, th.ctypes.data_as(C.POINTER(C.c_double)), 1, 1, C.byref(prm), 1),
+                   lib.eincm_finish_loss_grad(eng._ctx, val.ctypes.data_as(C.POINTER(C.c_double)), None, None),
+                   lib.eincm_finish_constants(eng._ctx)):
+            assert rc == L.ERR_UNSUPPORTED
+            assert 'fp64' in lib.eincm_last_error(eng._ctx).decode()
+        sharding = importlib.import_module('edge-informed-contrast-maximization_amd.sharding')
+        with pytest.raises(ValueError, match='fp64'):
+            sharding.ShardedEngine(eng, rank=0, world_size=1)
+        # the count image borrows no fp64 buffer: dL/dIWE of the last gradient evaluation stays readable
+        G0 = eng.image_grad()
+        eng.count_images()
+        assert np.array_equal(eng.image_grad(), G0)
+        # event-sharded staging is refused as well (and leaves the context unstaged)
+        with pytest.raises(engine.EincmError, match='fp64'):
+            eng.set_windows([args_of(win)], defer_constants=True)
+
+
+def test_nonfinite_gradient_is_reported(built_lib):
+    """A NaN that enters through the data (here one edge pixel) reaches dL/dIWE: the gradient comes back NaN, not as a finite partial sum
+    (the fixed-point accumulators cannot hold a NaN: a per-window flag carries it to the gradient), and the call reports NONFINITE."""
+    win = synth.make_window(51, (48, 64), 3_000, 2, flow='constant', flow_mag=4.0)
+    win['edges'] = win['edges'].copy()
+    win['edges'][1, 10, 20] = np.nan
+    with engine.Engine((48, 64), 3_000, max_refs=2, precision='fp64') as eng:
+        eng.set_window(*args_of(win))
+        for hw in ((1, 1), (4, 4)):
+            th = synth.theta_near_truth(3, win, hw)
+            v, g, _ = eng.loss_grad(th, engine.make_params(A, BETA, 0.0, 0.0, 1))
+            assert np.isnan(v[0]) and np.isnan(g).all()
+            with pytest.raises(engine.NonFiniteLoss):
+                eng.loss_grad(th, engine.make_params(A, BETA, 0.0, 0.0, 1), allow_nonfinite=False)
+
+
+def test_lockstep_fp64_matches_sequential_fp64_solves(built_lib):
+    """The lockstep BatchedMultipleLevelEINCMSolver with precision='fp64' against sequential fp64 solves (MultipleLevelEINCMSolver on
+    value_and_grad_loss_func(precision='fp64')) of the same 4 windows, pyramid 1x1 -> 2x2 -> 4x4 (the shapes of levels 4 -> 2 of the
+    reference's 5-level pyramid; gamma = 0, so the level index changes nothing else): same status and iterations at every level, theta
+    within 1e-6 px.  In fp32 the two drivers part ways where a line search fails on the objective's rounding noise."""
+    B, H, W, N, R, n_lvls = 4, 120, 160, 30_000, 3, 3
+    loss = dict(alpha=A, beta=BETA, gamma=0.0, delta=0.0, scale_to_sensor_size_method='bilinear', precision='fp64')
+    wins = [synth.make_window(80 + b, (H, W), N, R, flow='constant', flow_mag=4.0 + b) for b in range(B)]
+    args = [args_of(w) for w in wins]
+    maxiters = solver.growing_maxiters(n_lvls, 8, 16)
+    params = {'method': 'BFGS', 'options': {'gtol': 1e-7}}
+    bsol = importlib.import_module('edge-informed-contrast-maximization_amd.batch_solver')
+    bs = bsol.BatchedMultipleLevelEINCMSolver(B, (H, W), n_lvls, maxiters, loss, params, pyramid_downscale_method='lanczos3',
+                                              pyramid_upscale_method='repeat', pyramid_bases=[2] * (n_lvls - 1))
+    bs.set_datasamples(args)
+    assert bs.engines and all(e.precision == 'fp64' for e in bs.engines)
+    out_b = bs.solve()
+    bs.close()
+    for b in range(B):
+        s = solver.MultipleLevelEINCMSolver(
+            n_pyr_lvls=n_lvls, theta_opt_maxiters=maxiters,
+            theta_loss_pfunc=partial(losses.value_and_grad_loss_func, n_pyr_lvls=n_lvls, sensor_size=(H, W), **loss),
+            theta_opt_solver_params=params, pyramid_downscale_method='lanczos3', pyramid_upscale_method='repeat',
+            pyramid_bases=[2] * (n_lvls - 1))
+        s.set_datasample(*args[b])
+        out_s = s.solve()
+        for k in range(n_lvls - 1, -1, -1):
+            key = f'pyr_lvl_{k}'
+            st_s, st_b = out_s['theta_opt_state_pyr'][key], out_b[b]['theta_opt_state_pyr'][key]
+            assert (st_b.status, st_b.iter_num) == (st_s.status, st_s.iter_num), (b, key, st_b.status, st_s.status, st_b.iter_num, st_s.iter_num)
+            d = np.abs(out_b[b]['final_theta_pyr'][key] - out_s['final_theta_pyr'][key]).max()
+            assert d <= 1e-6, (b, key, d)
+    losses.clear_engine_cache()
