@@ -11,6 +11,13 @@ STAGE_NAMES = ('clear', 'theta', 'splat', 'stats', 'imgrad', 'gather', 'tv', 'pr
 
 OK, ERR_ARG, ERR_HIP, ERR_STATE, ERR_NONFINITE, ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5
 CONTRAST_GRAD_MAG, CONTRAST_VARIANCE = 0, 1
+CONTRAST_ADAPTIVE_GRAD_MAG, CONTRAST_ADAPTIVE_VARIANCE = 2, 3
+CONTRAST_KINDS = {'grad_mag': 0, 'variance': 1, 'adaptive_grad_mag': 2, 'adaptive_variance': 3}
+CORRELATION_MSE, CORRELATION_ADAPTIVE_MSE, CORRELATION_HADAMARD, CORRELATION_JOINT_CONTRAST = 0, 1, 2, 3
+CORRELATION_KINDS = {'mse': 0, 'adaptive_mse': 1, 'hadamard': 2, 'joint_contrast': 3}
+PF_CORRELATION_SHIFT = 8
+PF_CORRELATION_MASK = 0x700    # eincm_params.flags bits 8-10: the correlation kind
+DEFAULT_OBJECTIVE_TILE = (32, 42)
 METHODS = {'linear': 0, 'bilinear': 0, 'triangle': 0, 'lanczos3': 1, 'lanczos5': 2, 'cubic': 3, 'bicubic': 3}
 PF_FULL_AUX = 1
 PF_NO_TV_GRAD = 2
@@ -110,6 +117,7 @@ SIGNATURES = [
                                            C.POINTER(C.c_int32)]),
     ('eincm_gaussian_blur', C.c_int, [_P, _D, C.c_int, C.c_double, _D]),
     ('eincm_tiled_objectives', C.c_int, [_P, C.c_int, C.c_int, C.POINTER(TiledOut)]),
+    ('eincm_set_objective_tiles', C.c_int, [_P, C.c_int, C.c_int]),
 ]
 
 _lib = None

@@ -437,7 +437,7 @@ class BatchedMultipleLevelEINCMSolver:
     """The coarse-to-fine theta pyramid of B windows, solved level by level in lockstep on one engine context (or ``n_groups`` of them).
 
     Constructor keywords follow ``solver.MultipleLevelEINCMSolver`` (reference solver.py:16-126); instead of loss callables it
-    takes the loss parameters (``loss_kwargs``: alpha, beta, gamma, delta, scale_to_sensor_size_method[, contrast_kind][, precision]), because
+    takes the loss parameters (``loss_kwargs``: alpha, beta, gamma, delta, scale_to_sensor_size_method[, contrast_kind][, correlation_kind][, tile_size][, precision]), because
     the objective is the engine's batched loss+grad.  ``set_datasamples`` stages the B windows (one per sequence, or B independent
     windows); ``solve`` returns one result dict per window with the reference's keys (solver.py:254-267).  Calling set_datasamples /
     solve again continues every sequence with its own prior (handover), exactly as the single-window solver does window after window.
@@ -507,7 +507,10 @@ class BatchedMultipleLevelEINCMSolver:
             self.engines = [Engine(self.sensor_size, self._cap, max_refs=R, max_windows=len(ix), device=self.device,
                                    precision=self.loss_kwargs.get('precision', 'fp32')) for ix in self.groups]
             self.engine = self.engines[0]
+        tiles = self.loss_kwargs.get('tile_size')
         for eng, ix in zip(self.engines, self.groups):
+            if tiles is not None and eng.objective_tiles != tuple(tiles):
+                eng.set_objective_tiles(tiles)
             eng.set_windows([windows[b] for b in ix])
 
     def close(self):
@@ -518,7 +521,7 @@ class BatchedMultipleLevelEINCMSolver:
     def _params(self, lvl):
         kw = self.loss_kwargs
         return make_params(kw['alpha'], kw['beta'], kw['gamma'], kw['delta'], lvl, kw.get('scale_to_sensor_size_method', 'bilinear'),
-                           kw.get('contrast_kind', 0))
+                           kw.get('contrast_kind', 0), False, kw.get('correlation_kind', 'mse'))
 
     # -- one level: B BFGS solves in lockstep, with the reference's retries (solver.py:209-239) ---------------------------
     def _solve_level(self, k, starts):

@@ -23,6 +23,7 @@
 #include "eincm_kernels_f64.hip.h"
 #include "eincm_binning.hip.h"
 #include "eincm_edges.hip.h"
+#include "eincm_objectives.hip.h"
 
 using namespace eincm;
 
@@ -142,6 +143,16 @@ struct eincm_ctx {
     int cur_h = -1, cur_w = -1, cur_method = -1;
     int64_t coarse_cap = 0;        // doubles per window in d_gth halves
 
+    // selectable objective kinds (eincm_objectives.hip.h): tile size of the adaptive kinds, the zero-warp values of every kind
+    // (computed on the first evaluation that needs them, dropped by set_windows and by a tile-size change) and the per-cell partials
+    int obj_th = 32, obj_tw = 42;
+    bool objc_valid = false;
+    std::vector<ObjConst> h_objc;
+    ObjConst* d_objc = nullptr;    // (maxB)
+    double* d_oparts = nullptr;    // (B,R,ncells,OBJ_NP), grown on demand
+    size_t oparts_cap = 0;
+    double* h_ovals = nullptr;     // (maxB,maxR,2) pinned: contrast and signed correlation of every image (k_obj_grad)
+
     // scratch of the edge-smoothing / tiled-objective entry points (eincm_edges.hip.h), grown on demand
     DevBuf e_u8, e_g, e_sq, e_misc, e_a, e_b, e_kern, e_out;
 
@@ -190,6 +201,7 @@ struct eincm_ctx {
              bool tv_projected = false;             // k_tv projected its gradient onto the theta cells itself (no k_project for it)
              int copy_mode = 0;                     // 1: the D2H copies of the results are still to be enqueued (device_results)
              bool use_arg = false; const double* theta_dev = nullptr; ThetaArg targ{};      // where the event kernels find a 2-DoF theta
+             bool obj = false; ObjGeom og{};        // a contrast / correlation kind other than the defaults (eincm_objectives.hip.h)
              } pend;
     std::vector<uint8_t> theta_nan;    // (B) a NaN / Inf somewhere in window b's theta (host-assembled evaluations)
     // host-side wall time of the phases of an evaluation (eincm_get_host_profile): a few clock reads per evaluation, always on
@@ -321,9 +333,10 @@ void free_all(eincm_ctx* c) {
     F(c->d_rowtap); F(c->d_coltap); F(c->d_tilerng);
     F(c->f64.acc); F(c->f64.iwe); F(c->f64.zero_iwe); F(c->f64.edges); F(c->f64.G); F(c->f64.sgn); F(c->f64.gacc); F(c->f64.gTh); F(c->f64.T);
     F(c->f64.grad); F(c->f64.partA); F(c->f64.partB); F(c->f64.partC); F(c->f64.scal); F(c->f64.gmax); F(c->f64.ishift); F(c->f64.bad);
+    F(c->d_objc); F(c->d_oparts); c->oparts_cap = 0;
     for (DevBuf* b : {&c->e_u8, &c->e_g, &c->e_sq, &c->e_misc, &c->e_a, &c->e_b, &c->e_kern, &c->e_out}) { F(b->p); b->bytes = 0; }
     auto FH = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
-    FH(c->f64.h_scal);
+    FH(c->f64.h_scal); FH(c->h_ovals);
     FH(c->h_theta); FH(c->h_outs); c->h_grad = nullptr; FH(c->h_wc); FH(c->h_g11); FH(c->h_g2); FH(c->h_img); FH(c->h_tvparts);
     if (c->have_events) {
         for (int k = 0; k < eincm_ctx::EV_RING; ++k)
@@ -736,6 +749,87 @@ void f64_assemble(eincm_ctx* c) {
 }
 
 // First half of an evaluation: theta -> Theta -> IWE stack (k_theta, k_splat).  theta_host: (B,h,w,2) doubles.
+// ---- selectable objective kinds (eincm_objectives.hip.h) ----
+ObjGeom obj_geom(const eincm_ctx* c, int ck, int rk, int need) {
+    ObjGeom og{};
+    og.th = c->obj_th; og.tw = c->obj_tw;
+    og.nty = c->g.H / og.th; og.ntx = c->g.W / og.tw; og.ncells = og.nty * og.ntx;
+    og.ck = ck; og.rk = rk; og.need = need;
+    return og;
+}
+
+int obj_buffers(eincm_ctx* c, const ObjGeom& og) {
+    const size_t n = (size_t)c->g.B * c->g.R * og.ncells * OBJ_NP;
+    if (n > c->oparts_cap) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->d_oparts) { (void)hipFree(c->d_oparts); c->d_oparts = nullptr; c->oparts_cap = 0; }
+        HIPCHK(c, dalloc(&c->d_oparts, n));
+        c->oparts_cap = n;
+    }
+    if (!c->d_objc) HIPCHK(c, dalloc(&c->d_objc, (size_t)c->maxB));
+    if (!c->h_ovals) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ovals), (size_t)c->maxB * c->maxR * 2 * sizeof(double)));
+    return EINCM_OK;
+}
+
+// The zero-warp values of every kind for the staged windows and the current tile size: k_obj_parts on (zero-warp IWE, E_r),
+// k_obj_const; the default kinds' values come from the window constants of staging.  Synchronous (once per staging / tile size).
+int obj_constants(eincm_ctx* c) {
+    if (c->objc_valid) return EINCM_OK;
+    const ObjGeom og = obj_geom(c, 0, 0, OBJ_NEED_TILE_GM | OBJ_NEED_GM | OBJ_NEED_JOINT);
+    int rc = obj_buffers(c, og);
+    if (rc) return rc;
+    Geom g = c->g;
+    g.wmask = ~0ull;
+    hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_zero_iwe, 0, c->d_edges, c->d_oparts);
+    hipLaunchKernelGGL(k_obj_const, dim3(g.B), dim3(64), 0, c->stream, g, og, c->d_oparts, c->d_objc);
+    HIPCHK(c, hipGetLastError());
+    c->h_objc.assign((size_t)c->maxB, ObjConst{});
+    HIPCHK(c, hipMemcpyAsync(c->h_objc.data(), c->d_objc, (size_t)g.B * sizeof(ObjConst), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int b = 0; b < g.B; ++b) {
+        ObjConst& o = c->h_objc[b];
+        const WinConst& wc = c->h_wc[b];
+        o.c0[0] = wc.c0_gradmag; o.c0[1] = wc.c0_var;
+        for (int r = 0; r < g.R; ++r) o.zc[0][r] = wc.zc[r];
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_objc, c->h_objc.data(), (size_t)g.B * sizeof(ObjConst), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->objc_valid = true;
+    return EINCM_OK;
+}
+
+// After the kernels of an evaluation with a new kind: the scalar assembly of losses.py:176-193 with the kinds' values (k_obj_grad's
+// per-image values, the zero-warp values), on top of what k_final / host_assemble left for the TV and divergence terms.
+void obj_assemble(eincm_ctx* c) {
+    const Geom& g = c->g;
+    const EvalParams& ep = c->pend.ep;
+    const int ck = c->pend.og.ck, rk = c->pend.og.rk;
+    for (int b = 0; b < g.B; ++b) {
+        if (b < 64 && !((g.wmask >> b) & 1ull)) continue;
+        OutScal& o = c->h_outs[b];
+        const ObjConst& oc = c->h_objc[b];
+        const WinConst& wc = c->h_wc[b];
+        // a NaN theta: host_assemble marks it in theta_nan, k_final in its (default-kind) value
+        const bool bad = c->pend.host_asm ? c->theta_nan[b] != 0 : std::isnan(o.value);
+        double sum_rel_con = 0.0, sum_rel_corr = 0.0;
+        for (int r = 0; r < g.R; ++r) {
+            const double con = c->h_ovals[((size_t)b * g.R + r) * 2], corr = c->h_ovals[((size_t)b * g.R + r) * 2 + 1];
+            sum_rel_con += wc.mrw[r] * con / (oc.c0[ck] + EPSN);
+            sum_rel_corr += wc.mrw[r] * corr / (oc.zc[rk][r] + EPSN);
+        }
+        const double mrc = sum_rel_con / (double)g.R, mrr = sum_rel_corr / (double)g.R;
+        double val = ep.alpha * (-mrc) + ep.beta * (-mrr);
+        double reg = 0.0;
+        if (ep.gamma != 0.0) reg += ep.gamma * ((ep.cur_pyr_lvl <= 0) ? o.tv : 0.0);
+        if (ep.delta != 0.0) reg += ep.delta * o.mean_rel_div;
+        val += reg;
+        if (bad) val = NAN;
+        o.mean_rel_contrast = mrc; o.mean_rel_corr = mrr;
+        o.value = val;
+        o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
+    }
+}
+
 int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad, const uint8_t* active = nullptr) {
     HostPhase hp(c, EINCM_HP_BEGIN);
     {   // which windows take part (eincm_loss_grad_masked); the others' workgroups leave at once, their outputs are not written
@@ -756,8 +850,24 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         HIPCHK(c, dalloc(&c->d_gdiv, (size_t)c->maxB * c->maxR * img));
         HIPCHK(c, dalloc(&c->d_dgparts, (size_t)c->maxB * c->maxR * g.ntiles * 2));
     }
-    if (p->contrast_kind != EINCM_CONTRAST_GRAD_MAG && p->contrast_kind != EINCM_CONTRAST_VARIANCE)
+    if (p->contrast_kind < EINCM_CONTRAST_GRAD_MAG || p->contrast_kind > EINCM_CONTRAST_ADAPTIVE_VARIANCE)
         return fail(c, EINCM_ERR_ARG, "contrast_kind %d unknown", p->contrast_kind);
+    const int corr_kind = (int)((p->flags & EINCM_PF_CORRELATION_MASK) >> 8);
+    if (corr_kind > EINCM_CORRELATION_JOINT_CONTRAST) return fail(c, EINCM_ERR_ARG, "correlation kind %d unknown", corr_kind);
+    const bool obj = p->contrast_kind > EINCM_CONTRAST_VARIANCE || corr_kind != EINCM_CORRELATION_MSE;
+    if (obj && c->fp64)
+        return fail(c, EINCM_ERR_UNSUPPORTED, "contrast kind %d / correlation kind %d: not supported in fp64 mode (EINCM_CF_FP64)",
+                    p->contrast_kind, corr_kind);
+    if (obj) {
+        if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
+        const int rco = obj_constants(c);
+        if (rco) return rco;
+        const int need = (p->contrast_kind == EINCM_CONTRAST_ADAPTIVE_GRAD_MAG ? OBJ_NEED_TILE_GM : 0) |
+                         ((p->contrast_kind == EINCM_CONTRAST_GRAD_MAG || corr_kind == EINCM_CORRELATION_JOINT_CONTRAST) ? OBJ_NEED_GM : 0) |
+                         (corr_kind == EINCM_CORRELATION_JOINT_CONTRAST ? OBJ_NEED_JOINT : 0);
+        c->pend.og = obj_geom(c, p->contrast_kind, corr_kind, need);
+    }
+    c->pend.obj = obj;
     if (!identity) {
         if ((int64_t)h * w > (int64_t)g.H * g.W)
             return fail(c, EINCM_ERR_ARG, "theta (%d,%d,2) has more cells than the %dx%d sensor has pixels: not supported", h, w, g.H, g.W);
@@ -941,10 +1051,13 @@ int eval_end_launch(eincm_ctx* c) {
     // and k_imstat's tail as much as the kernel boundary it saves), so it stays an option.
     // delta != 0 and forward-only evaluations always take the unfused kernels.
     static const bool compose_env = getenv("EINCM_COMPOSE") != nullptr;
-    const bool compose = want_grad && !div_grad && compose_env;
-    const bool g2_from_imgrad = !compose && want_grad && ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG;
+    // A new objective kind (pend.obj): k_stats_stream -> k_obj_parts -> k_obj_grad -> gather; k_final / host_assemble still do the
+    // gradient sums and the TV / divergence terms, obj_assemble replaces the contrast and correlation terms of their value.
+    const bool obj = c->pend.obj;
+    const bool compose = want_grad && !div_grad && compose_env && !obj;
+    const bool g2_from_imgrad = !compose && want_grad && ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG && !obj;
     const bool zero_copy_out = !c->device_results && !c->theta_dev_in && !identity && (size_t)g.B * nth <= ZERO_COPY_MAX;
-    const bool stream_stats = host_asm || (g2_from_imgrad && g.ntiles >= NSPART);
+    const bool stream_stats = host_asm || (g2_from_imgrad && g.ntiles >= NSPART) || obj;
     const int n_imwg = (g.nig + IG_NT / 64 - 1) / (IG_NT / 64);
     unsigned* gmax_buf = compose ? c->d_gbound : c->d_gmax;
     g.gmax_n = compose ? g.R : g.R * g.nig;
@@ -989,6 +1102,12 @@ int eval_end_launch(eincm_ctx* c) {
 #undef TV_ARGS
         c->pend.tv_projected = tv_proj;
     }
+    if (obj && !want_grad) {          // forward only: the per-image values alone
+        const ObjGeom& og = c->pend.og;
+        hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts);
+        hipLaunchKernelGGL(k_obj_grad, dim3(1, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts,
+                           c->d_wc, c->d_objc, c->d_gdiv, c->d_dgparts, c->d_G, c->d_gmax, c->h_ovals, 0);
+    }
     const bool direct11 = want_grad && !identity && h == 1 && w == 1;
     const bool proj = want_grad && !identity && !direct11 && c->proj_in_gather;      // k_gather projects its tile's sums itself
     // a window with a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel); speed is irrelevant there
@@ -996,13 +1115,20 @@ int eval_end_launch(eincm_ctx* c) {
     for (int b = 0; b < g.B; ++b) wide = wide || (c->win_events[b] * (int64_t)g.R < 4096);
     if (want_grad) {
         if (!compose) {
-            StageTimer t(c, EINCM_STAGE_IMGRAD, !div_grad);
+            StageTimer t(c, EINCM_STAGE_IMGRAD, !div_grad && !obj);
             if (div_grad)
                 hipLaunchKernelGGL(k_divgrad, dim3(g.ntiles, g.R, g.B), dim3(NT), 0, c->stream, g, c->d_iwe, c->d_parts,
                                    c->d_gdiv, c->d_dgparts);
-            launch_timed(c, EINCM_STAGE_IMGRAD, k_imgrad, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, g, ep, c->d_iwe, c->d_edges,
-                               c->d_parts, c->d_wc, c->d_gdiv, c->d_dgparts, host_asm ? c->h_g2 : c->d_g2parts, c->d_G, c->d_gmax,
-                               host_asm ? c->h_img : nullptr, host_asm ? 1 : 0);
+            if (obj) {
+                const ObjGeom& og = c->pend.og;
+                hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts);
+                hipLaunchKernelGGL(k_obj_grad, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts,
+                                   c->d_wc, c->d_objc, c->d_gdiv, c->d_dgparts, c->d_G, c->d_gmax, c->h_ovals, 1);
+            } else {
+                launch_timed(c, EINCM_STAGE_IMGRAD, k_imgrad, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, g, ep, c->d_iwe, c->d_edges,
+                                   c->d_parts, c->d_wc, c->d_gdiv, c->d_dgparts, host_asm ? c->h_g2 : c->d_g2parts, c->d_G, c->d_gmax,
+                                   host_asm ? c->h_img : nullptr, host_asm ? 1 : 0);
+            }
         }
         {
             StageTimer t(c, EINCM_STAGE_GATHER, true);
@@ -1215,6 +1341,7 @@ int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) 
     HostPhase hp(c, EINCM_HP_COLLECT);
     if (c->pend.host_asm) host_assemble(c);
     else if (c->fp64) f64_assemble(c);
+    if (c->pend.obj) obj_assemble(c);
     int rc = collect_timings(c);
     if (rc) return rc;
     c->have_eval = true;
@@ -1546,6 +1673,7 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         for (int b = 0; b < n_windows; ++b)
             if (!edges_w[b] || (n_events[b] > 0 && (!xs_w[b] || !ys_w[b] || !ts_w[b]))) return fail(c, EINCM_ERR_ARG, "null pointer argument (window %d)", b);
     HIPCHK(c, hipSetDevice(c->device));
+    c->objc_valid = false;         // the zero-warp values of the objective kinds belong to the windows staged before
     const int H = c->H, W = c->W;
     int64_t N = 0;
     for (int b = 0; b < n_windows; ++b) {
@@ -2461,6 +2589,15 @@ int eincm_gaussian_blur(eincm_ctx* c, const double* src, int n, double sigma, do
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(dst, c->e_a.p, tot * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // k (host vector) stays alive until here
+    return EINCM_OK;
+}
+
+int eincm_set_objective_tiles(eincm_ctx* c, int tile_h, int tile_w) {
+    if (!c) return EINCM_ERR_ARG;
+    if (tile_h < 1 || tile_w < 1 || tile_h > c->H || tile_w > c->W)
+        return fail(c, EINCM_ERR_ARG, "objective tile %dx%d outside 1x1 .. %dx%d (the sensor)", tile_h, tile_w, c->H, c->W);
+    if (c->pend.active && c->pend.launched) return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
+    if (tile_h != c->obj_th || tile_w != c->obj_tw) { c->obj_th = tile_h; c->obj_tw = tile_w; c->objc_valid = false; }
     return EINCM_OK;
 }
 

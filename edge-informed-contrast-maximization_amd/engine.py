@@ -38,14 +38,51 @@ def as_int16_coords(a, what='coordinates'):
     return a.astype(np.int16)
 
 
+def _kind_code(kind, names, what):
+    """A kind given by name or integer code -> its code; anything else is a ValueError."""
+    if isinstance(kind, str):
+        if kind not in names:
+            raise ValueError(f'{what} {kind!r} unknown; one of {sorted(names)}')
+        return names[kind]
+    if isinstance(kind, (bool, np.bool_)) or not isinstance(kind, (int, np.integer)) or int(kind) not in names.values():
+        raise ValueError(f'{what} {kind!r} unknown; a name of {sorted(names)} or a code 0..{len(names) - 1}')
+    return int(kind)
+
+
+def contrast_kind_code(kind):
+    """'grad_mag' | 'variance' | 'adaptive_grad_mag' | 'adaptive_variance', or 0..3."""
+    return _kind_code(kind, L.CONTRAST_KINDS, 'contrast_kind')
+
+
+def correlation_kind_code(kind):
+    """'mse' | 'adaptive_mse' | 'hadamard' | 'joint_contrast', or 0..3."""
+    return _kind_code(kind, L.CORRELATION_KINDS, 'correlation_kind')
+
+
+def check_tile_size(tile_size, sensor_size=None):
+    """(tile_h, tile_w) of the adaptive objective kinds: positive integers, at most the sensor size when it is given."""
+    try:
+        th, tw = (int(v) for v in tile_size)
+        ok = all(float(v) == int(v) for v in tile_size)
+    except (TypeError, ValueError):
+        raise ValueError(f'tile_size {tile_size!r}: a pair of positive integers (tile_h, tile_w)') from None
+    if not ok or th < 1 or tw < 1 or (sensor_size is not None and (th > sensor_size[0] or tw > sensor_size[1])):
+        raise ValueError(f'tile_size {tile_size!r}: 1 <= tile <= sensor {tuple(sensor_size) if sensor_size is not None else ""}')
+    return th, tw
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
-                full_aux=False):
+                full_aux=False, correlation_kind='mse'):
+    """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
+    flags bits 8-10.  The defaults are the reference's loss_func (grad_mag, mse)."""
     if isinstance(method, str):
         if method not in L.METHODS:
             raise ValueError(f'scale_to_sensor_size_method {method!r} not supported; one of {sorted(L.METHODS)}')
         method = L.METHODS[method]
-    return L.Params(float(alpha), float(beta), float(gamma), float(delta), int(cur_pyr_lvl), int(method),
-                    int(contrast_kind), L.PF_FULL_AUX if full_aux else 0)
+    ck = contrast_kind_code(contrast_kind)
+    rk = correlation_kind_code(correlation_kind)
+    flags = (L.PF_FULL_AUX if full_aux else 0) | (rk << L.PF_CORRELATION_SHIFT)
+    return L.Params(float(alpha), float(beta), float(gamma), float(delta), int(cur_pyr_lvl), int(method), ck, flags)
 
 
 def check_precision(precision):
@@ -80,6 +117,7 @@ class Engine:
         self.B = 0
         self.R = 0
         self.timing = bool(timing)
+        self.objective_tiles = L.DEFAULT_OBJECTIVE_TILE
         self._io = {}                      # (h, w) -> staging buffers of loss_grad with their addresses
 
     # -- lifetime ---------------------------------------------------------------------------------
@@ -344,6 +382,12 @@ class Engine:
                 d[k] = np.array(v[:o.n_refs]) if t is L._A else float(v)
             res.append(d)
         return res
+
+    def set_objective_tiles(self, tile_size):
+        """Tile size (tile_h, tile_w) of the adaptive objective kinds of loss_grad (default 32 x 42, contrast_objectives.py:56-59)."""
+        th, tw = check_tile_size(tile_size, (self.H, self.W))
+        self._check(self._lib.eincm_set_objective_tiles(self._ctx, th, tw))
+        self.objective_tiles = (th, tw)
 
     def tiled_objectives(self, tile_size=None):
         """extract_tiles + compute_adaptive_* and their pairwise siblings (contrast_objectives.py:42-87,

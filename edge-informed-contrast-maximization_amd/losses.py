@@ -22,7 +22,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, check_precision, make_params
+from .engine import Engine, check_precision, check_tile_size, make_params
 
 _CACHE = []            # [(refs tuple, key, Engine)] most-recent first
 _CACHE_SIZE = 2
@@ -46,10 +46,19 @@ def _fingerprint(arrs):
     return hash(tuple(parts))
 
 
-def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp32'):
+def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp32', tile_size=None):
     """Engine holding this window (staged on first use; reused while the same, unmodified array objects are passed).  One engine per
-    precision: 'fp64' is the float64 mode (Engine(..., precision='fp64'))."""
+    precision: 'fp64' is the float64 mode (Engine(..., precision='fp64')).  tile_size: (tile_h, tile_w) of the adaptive objective
+    kinds, set on the engine (None: the default 32 x 42)."""
     check_precision(precision)
+    tiles = L.DEFAULT_OBJECTIVE_TILE if tile_size is None else check_tile_size(tile_size, sensor_size)
+    eng = _engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device, precision)
+    if eng.objective_tiles != tiles:
+        eng.set_objective_tiles(tiles)
+    return eng
+
+
+def _engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device, precision):
     arrs = tuple(_as_np(a) for a in (xs, ys, ts, edges, edge_ts))
     fp = _fingerprint(arrs)
     key = (tuple(int(s) for s in sensor_size), device, precision) + tuple((a.shape, a.dtype.str) for a in arrs)
@@ -92,40 +101,41 @@ def _aux_dict(eng, a, with_arrays):
 
 def value_and_grad_loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls,
                              sensor_size, scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
-                             full_aux=False, aux_arrays=False, precision='fp32'):
+                             full_aux=False, aux_arrays=False, correlation_kind='mse', tile_size=None, precision='fp32'):
     """((final_loss, aux_info), grad) — the shape jax.value_and_grad(loss_func, has_aux=True) returns.  precision='fp64': the engine's
     float64 mode (what the reference computes with jax_enable_x64: true)."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
-    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux)
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux, correlation_kind)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
     v, g, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=True, want_aux=True)
     return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
 
 
 def loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
-              scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, precision='fp32'):
+              scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse',
+              tile_size=None, precision='fp32'):
     """(final_loss, aux_info) as losses.py:108-205; forward only, every aux entry evaluated."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
-    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True)
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
     v, _, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=False, want_aux=True)
     return float(v[0]), _aux_dict(eng, aux[0], True)
 
 
 def value_and_grad_handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma,
                                       delta, cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
-                                      contrast_kind=L.CONTRAST_GRAD_MAG, precision='fp32'):
+                                      contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None, precision='fp32'):
     """(loss, d loss / d alpha_handover) of losses.py:269-276."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
-    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False)
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False, correlation_kind)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
     v, dv = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=True)
     return float(v[0]), float(dv[0])
 
 
 def handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta,
                        cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
-                       contrast_kind=L.CONTRAST_GRAD_MAG, precision='fp32'):
+                       contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None, precision='fp32'):
     """loss only, as losses.py:208-276."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
-    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False)
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False, correlation_kind)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
     v, _ = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=False)
     return float(v[0])
 

@@ -44,13 +44,20 @@ def main():
     ap.add_argument('--rank2', action='store_true', help="sequential driver with the O(n^2) BFGS update (theta_opt_solver_params['bfgs_update'] = 'rank2')")
     ap.add_argument('--precision', choices=('fp32', 'fp64'), default='fp32',
                     help="fp64: the engine's float64 mode (the reference config's jax_enable_x64: true; the config reader does not switch it)")
+    ap.add_argument('--contrast-kind', choices=('grad_mag', 'variance', 'adaptive_grad_mag', 'adaptive_variance'), default='grad_mag',
+                    help='contrast objective of the loss (DESIGN.md section 11); the reference wires grad_mag')
+    ap.add_argument('--correlation-kind', choices=('mse', 'adaptive_mse', 'hadamard', 'joint_contrast'), default='mse',
+                    help='correlation objective of the loss (DESIGN.md section 11); the reference wires mse')
+    ap.add_argument('--tile-size', type=int, nargs=2, default=(32, 42), metavar=('TH', 'TW'),
+                    help='tile of the adaptive kinds (contrast_objectives.py:56-59)')
     ap.add_argument('overrides', nargs='*')
     a = ap.parse_args()
     cfg = config.load_config(a.config_dir, 'main', a.overrides) if a.config_dir else config._wrap(DEFAULTS)
     H, W = cfg.dataset.sensor_size
     n_lvls = cfg.n_pyr_lvls
     kw = dict(alpha=cfg.alpha, beta=cfg.beta, gamma=cfg.gamma, delta=cfg.delta, n_pyr_lvls=n_lvls, sensor_size=(H, W),
-              scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method, precision=a.precision)
+              scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method, precision=a.precision,
+              contrast_kind=a.contrast_kind, correlation_kind=a.correlation_kind, tile_size=tuple(a.tile_size))
     sp = cfg.solver_params
     if a.sequences > 1:
         return run_batched(a, cfg, H, W, n_lvls)
@@ -110,7 +117,7 @@ def run_batched(a, cfg, H, W, n_lvls):
     from eincm_amd import batch_solver as bsol
     B, sp = a.sequences, cfg.solver_params
     loss = dict(alpha=cfg.alpha, beta=cfg.beta, gamma=cfg.gamma, delta=cfg.delta, scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method,
-                precision=a.precision)
+                precision=a.precision, contrast_kind=a.contrast_kind, correlation_kind=a.correlation_kind, tile_size=tuple(a.tile_size))
     bs = bsol.BatchedMultipleLevelEINCMSolver(
         B, (H, W), n_lvls,
         sol.growing_maxiters(n_lvls, sp.theta_opt.miniter, sp.theta_opt.maxiter, cfg.maxiters_grow_order, cfg.use_growing_maxiters), loss,

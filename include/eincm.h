@@ -39,6 +39,20 @@ extern "C" {
  * live objective); 1 = variance of the IWE (contrast_objectives.py:29-39; BASELINE config "variance-only") */
 #define EINCM_CONTRAST_GRAD_MAG 0
 #define EINCM_CONTRAST_VARIANCE 1
+/* the tiled ("adaptive") contrasts of contrast_objectives.py:42-87: the sum over the whole th x tw tiles (eincm_set_objective_tiles,
+ * default 32 x 42; the ragged right / bottom remainder is ignored) of the tile's mean squared Scharr gradient magnitude, the Scharr
+ * taken on each tile alone with zero padding at the tile border (2), or of the tile's population variance (3) */
+#define EINCM_CONTRAST_ADAPTIVE_GRAD_MAG 2
+#define EINCM_CONTRAST_ADAPTIVE_VARIANCE 3
+
+/* correlation objective K(E_r, n_r) on the edge map and the min-max-normalised IWE (correlation_objectives.py:46-130), selected by
+ * EINCM_PF_CORRELATION(kind) in eincm_params.flags.  Sign rule: error-type kinds enter the loss as -K (mse, adaptive_mse, as
+ * losses.py:65 does), similarity-type kinds as +K (hadamard, joint_contrast), so that every kind rewards a larger relative
+ * correlation.  Not in EINCM_CF_FP64 contexts (EINCM_ERR_UNSUPPORTED) for any kind but the defaults. */
+#define EINCM_CORRELATION_MSE            0   /* mean((E - n)^2)                                     (default) */
+#define EINCM_CORRELATION_ADAPTIVE_MSE   1   /* sum over the whole tiles of mean((E - n)^2)                   */
+#define EINCM_CORRELATION_HADAMARD       2   /* mean(E * n)                                                   */
+#define EINCM_CORRELATION_JOINT_CONTRAST 3   /* mean squared Scharr gradient magnitude of E + n (zero padding) */
 
 /* scale_to_sensor_size_method (theta_utils.py:25-35 -> jax.image.scale_and_translate kernels) */
 #define EINCM_METHOD_BILINEAR 0    /* 'linear' / 'bilinear' / 'triangle' */
@@ -51,6 +65,8 @@ extern "C" {
                                       evaluation adds the replicated TV gradient on one shard only */
 #define EINCM_PF_FULL_AUX   1u     /* also evaluate the report-only terms: IWE divergence (losses.py:79-81),
                                       TV at any gamma (losses.py:75), FWL (losses.py:84) */
+#define EINCM_PF_CORRELATION_MASK 0x700u                                   /* bits 8-10: EINCM_CORRELATION_* */
+#define EINCM_PF_CORRELATION(k)   ((((uint32_t)(k)) << 8) & EINCM_PF_CORRELATION_MASK)
 
 /* eincm_create flags */
 #define EINCM_CF_TIMING     1u     /* every stage timed with HIP events (eincm_get_timings): attached to the launch where a stage is one
@@ -343,6 +359,12 @@ typedef struct eincm_tiled_out {
     double joint_contrast[EINCM_MAX_REFS];
 } eincm_tiled_out;
 int eincm_tiled_objectives(eincm_ctx* ctx, int tile_h, int tile_w, eincm_tiled_out* out /* n_windows */);
+
+/* Tile size of the adaptive objective kinds in the differentiable loss (EINCM_CONTRAST_ADAPTIVE_*, EINCM_CORRELATION_ADAPTIVE_MSE),
+ * per context, default 32 x 42 (contrast_objectives.py:56-59); 1 <= tile <= sensor in each dimension, else EINCM_ERR_ARG.  The
+ * zero-warp values of the kinds are computed again on the next evaluation that needs them.  eincm_tiled_objectives keeps its own
+ * arguments. */
+int eincm_set_objective_tiles(eincm_ctx* ctx, int tile_h, int tile_w);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,277 @@
+"""The selectable objective kinds on the GPU: parity with the fp64 autograd witness
+(tests/_objective_kinds_witness.py) for every contrast x correlation combination, determinism, the entry points, the refusals and a
+lockstep solve.  Tolerance and `rel` as tests/test_gpu_parity.py: 1e-5, max-norm relative."""
+import importlib
+
+import numpy as np
+import pytest
+
+from oracle import eincm_oracle as O
+import _objective_kinds_witness as WIT
+
+pytestmark = pytest.mark.gpu
+
+TOL = 1e-5
+
+synth = importlib.import_module('edge-informed-contrast-maximization_amd.synth')
+engine = importlib.import_module('edge-informed-contrast-maximization_amd.engine')
+losses = importlib.import_module('edge-informed-contrast-maximization_amd.losses')
+L = importlib.import_module('edge-informed-contrast-maximization_amd._lib')
+
+A, B_, GAMMA = 20.0, 35.0, 2.5e-3
+
+
+def rel(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return np.abs(a - b).max() / max(np.abs(b).max(), 1e-300)
+
+
+def same_aux(a, b):
+    """aux lists equal bit for bit (NaN entries included)"""
+    return len(a) == len(b) and all(x.keys() == y.keys() and all(np.array_equal(x[k], y[k], equal_nan=True) for k in x) for x, y in zip(a, b))
+
+
+def win_args(win):
+    return (win['xs'], win['ys'], win['ts'], win['edges'], win['edge_ts'])
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _lib(built_lib):
+    yield built_lib
+    losses.clear_engine_cache()
+
+
+_WINS = {}
+
+
+def window(shape=(120, 160), n=30000, R=3, seed=5):
+    key = (shape, n, R, seed)
+    if key not in _WINS:
+        _WINS[key] = synth.make_window(seed, shape, n, R, flow='smooth', flow_mag=8.0)
+    return _WINS[key]
+
+
+def witness(win, theta, ck, rk, tile=(32, 42), method='bilinear', gamma=0.0, delta=0.0, lvl=1):
+    H, W = win['sensor_size']
+    h, w = theta.shape[:2]
+    AH = O.resample_matrix(h, H, H / h, method)
+    AW = O.resample_matrix(w, W, W / w, method)
+    return WIT.loss_and_grad(theta, *win_args(win), A, B_, gamma, delta, lvl, AH, AW, ck, rk, tile)
+
+
+def check_parity(win, theta, ck, rk, tile=(32, 42), method='bilinear', gamma=0.0, delta=0.0, lvl=1):
+    H, W = win['sensor_size']
+    v_w, g_w, G_w, aux_w = witness(win, theta, ck, rk, tile, method, gamma, delta, lvl)
+    with engine.Engine((H, W), len(win['xs']), max_refs=len(win['edge_ts'])) as eng:
+        eng.set_window(*win_args(win))
+        if tile != (32, 42):
+            eng.set_objective_tiles(tile)
+        p = engine.make_params(A, B_, gamma, delta, lvl, method, ck, correlation_kind=rk)
+        v, g, aux = eng.loss_grad(theta, p, want_aux=True)
+        G = eng.image_grad()[0]
+        v_f, _, aux_f = eng.loss_grad(theta, p, want_grad=False, want_aux=True)      # forward only: the same value
+    tag = (ck, rk, tile, theta.shape)
+    assert abs(v[0] - v_w) <= TOL * abs(v_w), (tag, v[0], v_w)
+    assert rel(g[0], g_w) <= TOL, (tag, rel(g[0], g_w))
+    assert rel(G, G_w) <= TOL, (tag, rel(G, G_w))
+    assert aux[0]['mean_rel_corr'] == pytest.approx(aux_w['mean_rel_corr'], rel=TOL), tag
+    assert aux[0]['mean_rel_contrast'] == pytest.approx(aux_w['mean_rel_contrast'], rel=TOL), tag
+    if ck > 1 or rk > 0:      # a new kind: the forward-only evaluation runs the same value kernels
+        assert v_f[0] == v[0] and aux_f[0]['mean_rel_corr'] == aux[0]['mean_rel_corr'], tag
+    else:                     # the default image pass forms the contrast in another kernel without a gradient
+        assert abs(v_f[0] - v_w) <= TOL * abs(v_w), tag
+
+
+# ---- 1. parity ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('rk', [0, 1, 2, 3])
+@pytest.mark.parametrize('ck', [0, 1, 2, 3])
+def test_all_combinations_2dof(ck, rk):
+    win = window()
+    check_parity(win, synth.theta_near_truth(1, win, (1, 1)), ck, rk)
+
+
+@pytest.mark.parametrize('ck,rk', [(2, 0), (3, 1), (0, 2), (1, 3)])
+def test_lanczos3_grid(ck, rk):
+    win = window()
+    check_parity(win, synth.theta_near_truth(2, win, (4, 4)), ck, rk, method='lanczos3')
+
+
+@pytest.mark.parametrize('ck,rk', [(2, 1), (3, 3), (0, 2)])
+def test_dense_theta(ck, rk):
+    win = window((48, 64), 6000, 2, seed=7)
+    check_parity(win, win['flow_gt'] * 0.9, ck, rk)
+
+
+@pytest.mark.parametrize('ck,rk', [(2, 1), (3, 2), (1, 3)])
+def test_ragged_remainder(ck, rk):
+    win = window((100, 150), 20000, 3, seed=9)
+    check_parity(win, synth.theta_near_truth(3, win, (1, 1)), ck, rk, tile=(32, 42))
+
+
+@pytest.mark.parametrize('ck,rk', [(2, 1), (3, 1), (2, 3)])
+def test_custom_tile(ck, rk):
+    win = window()
+    check_parity(win, synth.theta_near_truth(4, win, (2, 2)), ck, rk, tile=(24, 40))
+
+
+@pytest.mark.parametrize('ck,rk', [(2, 1), (3, 2)])
+def test_tile_equal_to_sensor(ck, rk):
+    win = window((60, 80), 8000, 3, seed=11)
+    check_parity(win, synth.theta_near_truth(5, win, (1, 1)), ck, rk, tile=(60, 80))
+
+
+@pytest.mark.parametrize('ck,rk', [(2, 3), (3, 1)])
+def test_level0_with_tv_and_divergence(ck, rk):
+    win = window()
+    check_parity(win, synth.theta_near_truth(6, win, (4, 4)), ck, rk, gamma=GAMMA, delta=0.3, lvl=0)
+
+
+# ---- 2. determinism -------------------------------------------------------------------------------------------------------------
+def _batch(n=4):
+    return [synth.make_window(40 + b, (120, 160), 30000, 3, flow='smooth', flow_mag=6.0 + b) for b in range(n)]
+
+
+def test_repeat_batch_and_mask_bits():
+    wins = _batch()
+    thetas = np.stack([synth.theta_near_truth(b, wins[b], (2, 2)) for b in range(4)])
+    p = engine.make_params(A, B_, 0.0, 0.0, 1, 'bilinear', 'adaptive_variance', correlation_kind='joint_contrast')
+    with engine.Engine((120, 160), 30000 * 4, max_refs=3, max_windows=4) as eng:
+        eng.set_windows([win_args(w) for w in wins])
+        v1, g1, a1 = eng.loss_grad(thetas, p, want_aux=True)
+        G1 = eng.image_grad()
+        v2, g2, a2 = eng.loss_grad(thetas, p, want_aux=True)
+        assert np.array_equal(v1, v2) and np.array_equal(g1, g2) and np.array_equal(G1, eng.image_grad()) and same_aux(a1, a2)
+        act = np.array([1, 0, 1, 0], dtype=np.uint8)
+        vm, gm, _ = eng.loss_grad(thetas, p, active=act)
+        assert np.array_equal(vm[act == 1], v1[act == 1]) and np.array_equal(gm[act == 1], g1[act == 1])
+        assert np.all(np.isnan(vm[act == 0]))
+    for b in range(4):
+        with engine.Engine((120, 160), 30000, max_refs=3) as e1:
+            e1.set_window(*win_args(wins[b]))
+            v, g, a = e1.loss_grad(thetas[b], p, want_aux=True)
+            assert v[0] == v1[b] and same_aux(a, a1[b:b + 1]), b
+            assert np.array_equal(e1.image_grad()[0], G1[b]), b
+            # the gradient sums the gather's per-workgroup partials, whose split follows the batch size (untouched event kernels)
+            assert rel(g[0], g1[b]) <= 1e-12, b
+
+
+# ---- 3. entry points ------------------------------------------------------------------------------------------------------------
+def test_async_equals_sync():
+    win = window()
+    th = synth.theta_near_truth(7, win, (4, 4))
+    p = engine.make_params(A, B_, GAMMA, 0.0, 0, 'bilinear', 'adaptive_grad_mag', correlation_kind='adaptive_mse')
+    with engine.Engine((120, 160), 30000, max_refs=3) as eng:
+        eng.set_window(*win_args(win))
+        v, g, a = eng.loss_grad(th, p, want_aux=True)
+        eng.loss_grad_async(th, p)
+        va, ga, aa = eng.loss_grad_wait(want_aux=True)
+        assert np.array_equal(v, va) and np.array_equal(g, ga) and same_aux(a, aa)
+
+
+def test_handover_matches_witness():
+    win = window()
+    H, W = win['sensor_size']
+    prev = synth.theta_near_truth(8, win, (2, 2))
+    th = synth.theta_near_truth(9, win, (2, 2))
+    AH = O.resample_matrix(2, H, H / 2, 'bilinear')
+    AW = O.resample_matrix(2, W, W / 2, 'bilinear')
+    v_w, dv_w = WIT.handover_loss_and_grad(0.4, prev, th, *win_args(win), A, B_, 0.0, 0.0, 1, AH, AW, contrast_kind=3,
+                                           correlation_kind=2, tile=(24, 40))
+    kw = dict(contrast_kind='adaptive_variance', correlation_kind='hadamard', tile_size=(24, 40))
+    v, dv = losses.value_and_grad_handover_loss_func(0.4, prev, th, *win_args(win), A, B_, 0.0, 0.0, 1, 3, (H, W), **kw)
+    assert abs(v - v_w) <= TOL * abs(v_w)
+    assert abs(dv - dv_w) <= TOL * max(abs(dv_w), 1e-12 * abs(v_w))
+    v2 = losses.handover_loss_func(0.4, prev, th, *win_args(win), A, B_, 0.0, 0.0, 1, 3, (H, W), **kw)
+    assert v2 == v
+
+
+def test_device_entry_point_equals_host():
+    import torch
+    win = window()
+    th = synth.theta_near_truth(10, win, (4, 4))
+    p = engine.make_params(A, B_, 0.0, 0.0, 1, 'bilinear', 'adaptive_grad_mag', correlation_kind='joint_contrast')
+    with engine.Engine((120, 160), 30000, max_refs=3) as eng:
+        eng.set_window(*win_args(win))
+        v, g, a = eng.loss_grad(th, p, want_aux=True)
+        vd, gd, ad = eng.loss_grad_device(torch.from_numpy(th[None].copy()).cuda(), p, theta_abs_max=float(np.abs(th).max()),
+                                          want_aux=True)
+        assert np.array_equal(v, vd) and same_aux(a, ad)
+        # (the host path sums a theta grid's gradient in the gather's tail, the device path in k_project: the same fixed-point
+        # partials in another association)
+        assert rel(gd.cpu().numpy(), g) <= 1e-12
+
+
+def test_sharded_world1_equals_engine():
+    sh = importlib.import_module('edge-informed-contrast-maximization_amd.sharding')
+    win = window()
+    a = win_args(win)
+    with engine.Engine((120, 160), 30000, max_refs=3) as e1, engine.Engine((120, 160), 30000, max_refs=3) as e2:
+        e1.set_window(*a)
+        se = sh.ShardedEngine(e2)
+        se.set_windows([a])
+        for ck, rk, hw in [(3, 2, (1, 1)), (2, 3, (4, 4)), (0, 1, (2, 2))]:
+            th = synth.theta_near_truth(11, win, hw)
+            p = engine.make_params(A, B_, 0.0, 0.0, 1, 'bilinear', ck, correlation_kind=rk)
+            v1, g1, _ = e1.loss_grad(th, p)
+            v2, g2 = se.loss_grad(th, p)
+            assert v2[0] == v1[0], (ck, rk)
+            assert np.array_equal(np.asarray(g2).reshape(g1.shape), g1), (ck, rk)
+
+
+# ---- 4. refusals and unchanged defaults -----------------------------------------------------------------------------------------
+def test_fp64_refuses_new_kinds():
+    win = window((48, 64), 4000, 2, seed=13)
+    th = synth.theta_near_truth(12, win, (1, 1))
+    with engine.Engine((48, 64), 4000, max_refs=2, precision='fp64') as eng:
+        eng.set_window(*win_args(win))
+        eng.loss_grad(th, engine.make_params(A, B_, 0.0, 0.0, 1))                   # the defaults run
+        for ck, rk in [(2, 0), (3, 0), (0, 1), (0, 2), (0, 3), (1, 3)]:
+            with pytest.raises(engine.EincmError) as ei:
+                eng.loss_grad(th, engine.make_params(A, B_, 0.0, 0.0, 1, 'bilinear', ck, correlation_kind=rk))
+            assert ei.value.code == L.ERR_UNSUPPORTED and 'fp64' in str(ei.value)
+
+
+def test_tile_size_leaves_default_kinds_bitwise():
+    win = window()
+    th = synth.theta_near_truth(13, win, (4, 4))
+    with engine.Engine((120, 160), 30000, max_refs=3) as eng:
+        eng.set_window(*win_args(win))
+        for ck in (0, 1):
+            p = engine.make_params(A, B_, GAMMA, 0.0, 0, 'bilinear', ck)
+            eng.set_objective_tiles((32, 42))
+            v0, g0, a0 = eng.loss_grad(th, p, want_aux=True)
+            G0 = eng.image_grad()
+            eng.set_objective_tiles((7, 11))
+            v1, g1, a1 = eng.loss_grad(th, p, want_aux=True)
+            assert np.array_equal(v0, v1) and np.array_equal(g0, g1) and same_aux(a0, a1) and np.array_equal(G0, eng.image_grad())
+        with pytest.raises(ValueError):
+            eng.set_objective_tiles((121, 4))
+        with pytest.raises(engine.EincmError):     # the C function checks too
+            eng._check(eng._lib.eincm_set_objective_tiles(eng._ctx, 0, 4))
+
+
+# ---- 5. solver ------------------------------------------------------------------------------------------------------------------
+def test_lockstep_solve_with_new_kinds():
+    sol = importlib.import_module('edge-informed-contrast-maximization_amd.solver')
+    bsol = importlib.import_module('edge-informed-contrast-maximization_amd.batch_solver')
+    H, W, N, R, n_lvls = 96, 128, 12000, 3, 2
+    wins = [synth.make_window(80 + b, (H, W), N, R, flow='constant', flow_mag=3.0 + b) for b in range(2)]
+    loss = dict(alpha=A, beta=B_, gamma=0.0, delta=0.0, scale_to_sensor_size_method='bilinear', contrast_kind='adaptive_variance',
+                correlation_kind='hadamard', tile_size=(32, 42))
+    bs = bsol.BatchedMultipleLevelEINCMSolver(
+        2, (H, W), n_lvls, sol.growing_maxiters(n_lvls, 3, 12), loss,
+        {'method': 'BFGS', 'options': {'gtol': 1e-7}, 'n_extra_attempts': {'pyr_lvl_0': 0, 'pyr_lvl_1': 0}},
+        handover_opt_maxiters=sol.growing_maxiters(n_lvls, 4, 20), handover_opt_solver_params={'method': 'L-BFGS-B', 'options': {'gtol': 1e-6}},
+        handover_settings=None, pyramid_downscale_method='lanczos3', pyramid_upscale_method='repeat', pyramid_bases=[2])
+    bs.set_datasamples([win_args(w) for w in wins])
+    out = bs.solve()
+    bs.close()
+    for b in range(2):
+        for k in range(n_lvls):
+            key = f'pyr_lvl_{k}'
+            fv = out[b]['theta_opt_state_pyr'][key].fun_val
+            start = out[b]['pre_opt_theta_pyr'][key]
+            (v0, _), _ = losses.value_and_grad_loss_func(start, *win_args(wins[b]), A, B_, 0.0, 0.0, k, n_lvls, (H, W),
+                                                         contrast_kind='adaptive_variance', correlation_kind='hadamard')
+            assert np.isfinite(fv) and np.all(np.isfinite(out[b]['final_theta_pyr'][key])), (b, key)
+            assert fv <= v0 + 1e-9 * abs(v0), (b, key, fv, v0)

@@ -1,0 +1,165 @@
+"""The selectable objective kinds without a GPU: name <-> code maps, the packing of the correlation kind into eincm_params.flags,
+header constants against the binding, refusals of bad names and tile sizes, defaults byte for byte, and self-checks of the fp64
+witness (tests/_objective_kinds_witness.py) against the oracle."""
+import ctypes as C
+import importlib
+import os
+import re
+
+import numpy as np
+import pytest
+
+from oracle import eincm_oracle as O
+from oracle import edge_smoothing as ES
+import _objective_kinds_witness as WIT
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+L = importlib.import_module('edge-informed-contrast-maximization_amd._lib')
+engine = importlib.import_module('edge-informed-contrast-maximization_amd.engine')
+losses = importlib.import_module('edge-informed-contrast-maximization_amd.losses')
+synth = importlib.import_module('edge-informed-contrast-maximization_amd.synth')
+
+
+def _header_defines():
+    txt = open(os.path.join(ROOT, 'include', 'eincm.h')).read()
+    return {k: v for k, v in re.findall(r'#define\s+(EINCM_[A-Z0-9_]+)\s+(0x[0-9a-fA-F]+|\d+)u?\b', txt)}
+
+
+def test_kind_maps():
+    assert L.CONTRAST_KINDS == {'grad_mag': 0, 'variance': 1, 'adaptive_grad_mag': 2, 'adaptive_variance': 3}
+    assert L.CORRELATION_KINDS == {'mse': 0, 'adaptive_mse': 1, 'hadamard': 2, 'joint_contrast': 3}
+    for name, code in L.CONTRAST_KINDS.items():
+        assert engine.contrast_kind_code(name) == code == engine.contrast_kind_code(code)
+    for name, code in L.CORRELATION_KINDS.items():
+        assert engine.correlation_kind_code(name) == code == engine.correlation_kind_code(code)
+
+
+@pytest.mark.parametrize('rk', [0, 1, 2, 3])
+def test_correlation_packed_in_flags(rk):
+    for full_aux in (False, True):
+        p = engine.make_params(1.0, 2.0, 0.0, 0.0, 1, 'bilinear', 'variance', full_aux, correlation_kind=rk)
+        assert (p.flags & L.PF_CORRELATION_MASK) >> L.PF_CORRELATION_SHIFT == rk
+        assert p.flags & ~L.PF_CORRELATION_MASK == (L.PF_FULL_AUX if full_aux else 0)
+        assert p.contrast_kind == 1
+
+
+def test_header_constants_match_binding():
+    d = _header_defines()
+    assert int(d['EINCM_CONTRAST_ADAPTIVE_GRAD_MAG']) == L.CONTRAST_ADAPTIVE_GRAD_MAG == 2
+    assert int(d['EINCM_CONTRAST_ADAPTIVE_VARIANCE']) == L.CONTRAST_ADAPTIVE_VARIANCE == 3
+    for name, code in L.CORRELATION_KINDS.items():
+        assert int(d['EINCM_CORRELATION_' + name.upper()]) == code
+    assert int(d['EINCM_PF_CORRELATION_MASK'], 16) == L.PF_CORRELATION_MASK == 0x700
+    assert 'eincm_set_objective_tiles' in [n for n, _, _ in L.SIGNATURES]
+    txt = open(os.path.join(ROOT, 'include', 'eincm.h')).read()
+    assert '#define EINCM_PF_CORRELATION(k)' in txt
+
+
+@pytest.mark.parametrize('bad', ['MSE', 'ssd', 4, -1, 1.0, None, True])
+def test_bad_correlation_kind_rejected(bad):
+    with pytest.raises(ValueError):
+        engine.make_params(1.0, 1.0, 0.0, 0.0, 1, correlation_kind=bad)
+
+
+@pytest.mark.parametrize('bad', ['adaptive', 'Variance', 4, -1, 2.0])
+def test_bad_contrast_kind_rejected(bad):
+    with pytest.raises(ValueError):
+        engine.make_params(1.0, 1.0, 0.0, 0.0, 1, contrast_kind=bad)
+
+
+@pytest.mark.parametrize('tile', [(0, 4), (4, 0), (-1, 3), (121, 4), (4, 161), (2.5, 4), 'ab', (3,), None])
+def test_bad_tile_size_rejected(tile):
+    with pytest.raises(ValueError):
+        engine.check_tile_size(tile, (120, 160))
+
+
+def test_tile_size_bounds_accepted():
+    assert engine.check_tile_size((1, 1), (120, 160)) == (1, 1)
+    assert engine.check_tile_size((120, 160), (120, 160)) == (120, 160)
+    assert engine.check_tile_size(np.array([32, 42]), (120, 160)) == (32, 42)
+
+
+def test_losses_reject_bad_names_before_the_gpu():
+    win = synth.make_window(0, (24, 32), 200, 2)
+    args = (win['xs'], win['ys'], win['ts'], win['edges'], win['edge_ts'])
+    th = np.zeros((1, 1, 2))
+    with pytest.raises(ValueError):
+        losses.value_and_grad_loss_func(th, *args, 1.0, 1.0, 0.0, 0.0, 1, 3, (24, 32), correlation_kind='nope')
+    with pytest.raises(ValueError):
+        losses.loss_func(th, *args, 1.0, 1.0, 0.0, 0.0, 1, 3, (24, 32), contrast_kind='nope')
+    with pytest.raises(ValueError):
+        losses.value_and_grad_loss_func(th, *args, 1.0, 1.0, 0.0, 0.0, 1, 3, (24, 32), tile_size=(0, 3))
+    with pytest.raises(ValueError):
+        losses.handover_loss_func(0.5, th, th, *args, 1.0, 1.0, 0.0, 0.0, 1, 3, (24, 32), tile_size=(25, 3))
+
+
+def test_defaults_byte_for_byte():
+    new = engine.make_params(20.0, 35.0, 2.5e-4, 0.0, 0, 'lanczos3', 0, True)
+    explicit = engine.make_params(20.0, 35.0, 2.5e-4, 0.0, 0, 'lanczos3', 'grad_mag', True, correlation_kind='mse')
+    old = L.Params(20.0, 35.0, 2.5e-4, 0.0, 0, 1, 0, L.PF_FULL_AUX)
+    assert bytes(new) == bytes(old) == bytes(explicit)
+    v = engine.make_params(1.0, 2.0, 0.0, 0.0, 2, 'bilinear', 1)
+    assert bytes(v) == bytes(L.Params(1.0, 2.0, 0.0, 0.0, 2, 0, 1, 0))
+    assert C.sizeof(L.Params) == 48
+
+
+# ---- witness self-checks ---------------------------------------------------------------------------------------------------
+def _case(H=40, W=50, n=2500, R=2, seed=3):
+    win = synth.make_window(seed, (H, W), n, R, flow='smooth', flow_mag=6.0)
+    return win, (win['xs'], win['ys'], win['ts'], win['edges'], win['edge_ts'])
+
+
+@pytest.mark.parametrize('ck', [0, 1])
+@pytest.mark.parametrize('theta_hw,lvl,gamma', [((1, 1), 1, 0.0), ((2, 2), 0, 2.5e-3)])
+def test_witness_default_kinds_match_oracle(ck, theta_hw, lvl, gamma):
+    win, args = _case()
+    H, W = win['sensor_size']
+    theta = synth.theta_near_truth(1, win, theta_hw)
+    v_o, g_o, aux_o = O.loss_and_grad(theta, *args, 20.0, 35.0, gamma, 0.0, lvl, 5, (H, W), 'bilinear', ck)
+    AH = O.resample_matrix(theta_hw[0], H, H / theta_hw[0], 'bilinear')
+    AW = O.resample_matrix(theta_hw[1], W, W / theta_hw[1], 'bilinear')
+    v, g, G, aux = WIT.loss_and_grad(theta, *args, 20.0, 35.0, gamma, 0.0, lvl, AH, AW, ck, 0)
+    assert abs(v - v_o) <= 1e-12 * abs(v_o)
+    assert np.abs(g - g_o).max() <= 1e-12 * np.abs(g_o).max()
+    assert aux['mean_rel_corr'] == pytest.approx(float(aux_o['mean_rel_corr']), rel=1e-12)
+    assert aux['mean_rel_contrast'] == pytest.approx(float(aux_o['mean_rel_contrast']), rel=1e-12)
+
+
+@pytest.mark.parametrize('shape,tile', [((40, 50), (32, 42)), ((100, 150), (32, 42)), ((30, 44), (7, 9)), ((24, 32), (24, 32)),
+                                        ((24, 32), (1, 1))])
+def test_witness_terms_match_edge_smoothing_oracle(shape, tile):
+    rng = np.random.default_rng(11)
+    I = rng.random(shape) ** 3 * 4.0
+    E = rng.random(shape)
+    n = ES.normalize_to_unit_range(I)
+    assert WIT.contrast_value(I, 2, tile) == pytest.approx(ES.compute_adaptive_mean_gradient_magnitude(I, tile), rel=1e-12)
+    assert WIT.contrast_value(I, 3, tile) == pytest.approx(ES.compute_adaptive_variance(I, tile), rel=1e-12)
+    assert WIT.correlation_value(E, n, 1, tile) == pytest.approx(-ES.compute_adaptive_mean_squared_error(E, n, tile), rel=1e-12)
+    assert WIT.correlation_value(E, n, 2, tile) == pytest.approx(ES.compute_mean_hadamard_product(E, n), rel=1e-12)
+    assert WIT.correlation_value(E, n, 3, tile) == pytest.approx(ES.compute_joint_contrast(E, n), rel=1e-12)
+    assert WIT.contrast_value(I, 0) == pytest.approx(O.compute_mean_gradient_magnitude(I), rel=1e-12)
+    assert WIT.contrast_value(I, 1) == pytest.approx(O.compute_variance(I), rel=1e-12)
+    assert WIT.correlation_value(E, n, 0) == pytest.approx(-O.compute_mean_squared_error(E, n), rel=1e-12)
+
+
+def test_witness_tile_equal_to_sensor_is_whole_image():
+    rng = np.random.default_rng(5)
+    I = rng.random((24, 32))
+    E = rng.random((24, 32))
+    assert WIT.contrast_value(I, 2, (24, 32)) == pytest.approx(WIT.contrast_value(I, 0), rel=1e-14)
+    assert WIT.contrast_value(I, 3, (24, 32)) == pytest.approx(WIT.contrast_value(I, 1), rel=1e-14)
+    assert WIT.correlation_value(E, I, 1, (24, 32)) == pytest.approx(WIT.correlation_value(E, I, 0), rel=1e-14)
+
+
+def test_witness_handover_derivative_by_differences():
+    win, args = _case(R=2)
+    H, W = win['sensor_size']
+    prev = synth.theta_near_truth(2, win, (1, 1))
+    theta = synth.theta_near_truth(4, win, (1, 1))
+    AH = O.resample_matrix(1, H, H, 'bilinear')
+    AW = O.resample_matrix(1, W, W, 'bilinear')
+    kw = dict(contrast_kind=3, correlation_kind=2, tile=(16, 20))
+    v, dv = WIT.handover_loss_and_grad(0.3, prev, theta, *args, 20.0, 35.0, 0.0, 0.0, 1, AH, AW, **kw)
+    v_o = WIT.loss_and_grad(0.3 * prev + 0.7 * theta, *args, 20.0, 35.0, 0.0, 0.0, 1, AH, AW, **kw)[0]
+    assert v == v_o
+    assert np.isfinite(dv)
