@@ -109,19 +109,11 @@ struct eincm_ctx {
     double* d_dtmax = nullptr;     // (B) staging scratch: max |t - tau| per window
     unsigned* d_gmax = nullptr;    // (B,R,nig) per-strip max |dL/dIWE| as float bits (scale of the i64 gradient accumulators)
     unsigned* d_cntmax = nullptr;  // (B) staging scratch: most events on one source pixel
-    unsigned* d_amax = nullptr;    // (B,R,pstride) max |A| per k_imstat workgroup (float bits)
-    unsigned* d_gbound = nullptr;  // (B,R) bound of max |dL/dIWE| per image from k_imstat's tail (float bits): what gmax is when gmax_n == R
-    unsigned* d_ticket = nullptr;  // (B,R) arrival counters of k_imstat, zero between launches
     unsigned* d_gticket = nullptr; // (B) arrival counters of the gather's tail (theta grids), zero between launches
-    ImgCoef* d_coef = nullptr;     // (B,R) what the gather composes dL/dIWE with
-    float* d_Gimg = nullptr;       // (B,R,H,W) dL/dIWE materialised for eincm_get_image_grad after a composed evaluation (allocated on demand)
-    bool last_composed = false;    // the last gradient evaluation left A in d_G (the gather composed dL/dIWE on the fly)
-    EvalParams last_ep{};
-    Geom last_g{};                 // geometry of the last gradient evaluation (nparts, gmax_n)
     double* d_tvg = nullptr;       // (B,H,W,2)
     uint8_t* d_mask = nullptr;     // (B,H,W)
     double* d_tmm = nullptr;       // (B,ntiles,4)
-    StatPart* d_parts = nullptr;   // (B,R,ntiles)
+    StatPart* d_parts = nullptr;   // (B,R,pstride)
     double* d_divparts = nullptr;  // (B,R,ntiles)
     double* d_g2parts = nullptr;   // (B,R,nig) contrast energy partials written by k_imgrad
     float* d_gdiv = nullptr;       // (B,R,H,W) divergence adjoint image, allocated on first delta != 0 gradient
@@ -197,7 +189,6 @@ struct eincm_ctx {
              bool pal_2 = false;                    // the 2-DoF gather's windows at the bank-aligned pitch in this evaluation
              bool splat_short = false;              // this evaluation's k_splat walks the short segment list (d_items_sh)
              bool host_asm = false;                 // scalar assembly and the 2-DoF gradient sum on the host (see h_g11)
-             bool composed = false;                 // k_imstat + composing gather (host_assemble: the contrast energy rides in h_img)
              bool tv_projected = false;             // k_tv projected its gradient onto the theta cells itself (no k_project for it)
              int copy_mode = 0;                     // 1: the D2H copies of the results are still to be enqueued (device_results)
              bool use_arg = false; const double* theta_dev = nullptr; ThetaArg targ{};      // where the event kernels find a 2-DoF theta
@@ -327,7 +318,7 @@ void free_all(eincm_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
     F(c->d_xy); F(c->d_t); F(c->d_xy_g); F(c->d_t_g); F(c->d_items); F(c->d_items_s); F(c->d_items_2); F(c->d_order_2); F(c->d_win_item0_2); F(c->d_items_sh); F(c->d_order_sh); F(c->d_order); F(c->d_order_s); F(c->d_wins); F(c->d_wins_s); F(c->d_raw_x); F(c->d_raw_y); F(c->d_raw_t); F(c->d_binblocks); F(c->d_win_blk);
     F(c->d_blockhist); F(c->d_tilecount); F(c->d_tilebase); F(c->d_itembase); F(c->d_itembase_s); F(c->d_bin_misc); F(c->d_edges_raw); F(c->d_edge_moments); F(c->d_edges); F(c->d_edge_ts); F(c->d_acc); F(c->d_iwe); F(c->d_G); F(c->d_zero_iwe);
-    F(c->d_g11); F(c->d_win_item0); F(c->d_dtmax); F(c->d_gmax); F(c->d_cntmax); F(c->d_amax); F(c->d_gbound); F(c->d_ticket); F(c->d_gticket); F(c->d_coef); F(c->d_Gimg);
+    F(c->d_g11); F(c->d_win_item0); F(c->d_dtmax); F(c->d_gmax); F(c->d_cntmax); F(c->d_gticket);
     F(c->d_Theta); F(c->d_theta_in); F(c->d_gTheta); F(c->d_tvg); F(c->d_mask); F(c->d_tmm); F(c->d_parts);
     F(c->d_divparts); F(c->d_g2parts); F(c->d_gdiv); F(c->d_dgparts); F(c->d_tvparts); F(c->d_wc); F(c->d_outs); c->d_grad = nullptr; F(c->d_gth); F(c->d_AH); F(c->d_AW);
     F(c->d_rowtap); F(c->d_coltap); F(c->d_tilerng);
@@ -590,23 +581,11 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
 #define SPLAT_ARGS(NTH) dim3(grid_sp), dim3(NTH), lds_bytes, g, n_sp, c->chunk, theta_mode, lds_multi, \
                    items_sp, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_wins_s, c->d_acc, order_sp, \
                    use_arg ? 1 : 0, theta_dev, targ
-            static const bool merge_env = getenv("EINCM_SPLAT_MERGE") != nullptr;
-            if (merge_env && !lds_multi && c->seg_used <= MAX_CHUNK && c->n_items > 0) {
-                // experiment: the splat walks the gather's list and copy and merges same-destination taps in registers
-                Geom gs = g; gs.wincap = g.wincap_a; gs.winmaxw = g.winmaxw_a;
-                const size_t lds_m = (size_t)gs.wincap * sizeof(float) + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
-#define MERGE_ARGS dim3(event_grid(c)), dim3(512), lds_m, gs, c->n_items, MAX_CHUNK, theta_mode, 0, \
-                   c->d_items, c->d_xy_g, c->d_t_g, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_wins, c->d_acc, c->d_order, \
-                   use_arg ? 1 : 0, theta_dev, targ
-                if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 0, 512, 1>, MERGE_ARGS);
-                else                           launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_TILE, 0, 512, 1>, MERGE_ARGS);
-#undef MERGE_ARGS
-            } else
-            if (lds_multi)                      launch_timed(c, EINCM_STAGE_SPLAT, k_splat<0, 1, NT, 0>, SPLAT_ARGS(NT));      // long segments (EINCM_SEG_SPLAT > EINCM_CHUNK)
+            if (lds_multi)                      launch_timed(c, EINCM_STAGE_SPLAT, k_splat<0, 1, NT>, SPLAT_ARGS(NT));      // long segments (EINCM_SEG_SPLAT > EINCM_CHUNK)
             // 512 threads per workgroup in both compile-time modes: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
             // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
-            else if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 0, 512, 0>, SPLAT_ARGS(512));
-            else                                launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_TILE, 0, 512, 0>, SPLAT_ARGS(512));
+            else if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 0, 512>, SPLAT_ARGS(512));
+            else                                launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_TILE, 0, 512>, SPLAT_ARGS(512));
 #undef SPLAT_ARGS
         }
     }
@@ -702,8 +681,7 @@ int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalP
     c->n_pieces = 0;
     c->pend.active = true; c->pend.launched = true; c->pend.ep = ep; c->pend.h = h; c->pend.w = w; c->pend.identity = identity;
     c->pend.want_grad = want_grad; c->pend.full_aux = full_aux; c->pend.div_grad = div_grad; c->pend.host_asm = false;
-    c->pend.composed = false; c->pend.copy_mode = 0;
-    c->last_composed = false;
+    c->pend.copy_mode = 0;
     return EINCM_OK;
 }
 
@@ -952,7 +930,7 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         c->g.winmaxw = std::max(40, (int)std::lround(std::sqrt((double)cap * 1.4)));
         c->g.pitch_aligned = pal_s ? 1 : 0;
         // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
-        // sends taps down the direct path, where a composed dL/dIWE costs three loads per tap
+        // sends taps down the direct path
         const double side_a = TS + 4 + vmax * c->tspan_a;
         const int cap_a = cap_of(side_a * side_a, 2);          // (the theta-grid gather's windows: pitch = width)
         c->g.wincap_a = cap_a;
@@ -1044,34 +1022,20 @@ int eval_end_launch(eincm_ctx* c) {
     const size_t nth = (size_t)h * w * 2;
     const bool timing = timing_on(c);
     const bool host_asm = c->pend.host_asm;
-    // The image pass of a gradient evaluation.  Default: k_stats_stream -> k_imgrad -> gather.  EINCM_COMPOSE=1 selects the fused
-    // form built in round 3: k_imstat (statistics + the stats-independent part of dL/dIWE in one kernel, the per-image scalars in its
-    // tail) and a gather that composes dL/dIWE while staging its windows - one dependent kernel fewer, but measured no faster
-    // (one window of 10^6 events: 72.4 vs 72.2 us; the 8-window batch 236 vs 231 us: the gather pays three loads per window pixel
-    // and k_imstat's tail as much as the kernel boundary it saves), so it stays an option.
-    // delta != 0 and forward-only evaluations always take the unfused kernels.
-    static const bool compose_env = getenv("EINCM_COMPOSE") != nullptr;
+    // The image pass of a gradient evaluation: k_stats_stream -> k_imgrad -> gather.
     // A new objective kind (pend.obj): k_stats_stream -> k_obj_parts -> k_obj_grad -> gather; k_final / host_assemble still do the
     // gradient sums and the TV / divergence terms, obj_assemble replaces the contrast and correlation terms of their value.
     const bool obj = c->pend.obj;
-    const bool compose = want_grad && !div_grad && compose_env && !obj;
-    const bool g2_from_imgrad = !compose && want_grad && ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG && !obj;
+    const bool g2_from_imgrad = want_grad && ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG && !obj;
     const bool zero_copy_out = !c->device_results && !c->theta_dev_in && !identity && (size_t)g.B * nth <= ZERO_COPY_MAX;
     const bool stream_stats = host_asm || (g2_from_imgrad && g.ntiles >= NSPART) || obj;
     const int n_imwg = (g.nig + IG_NT / 64 - 1) / (IG_NT / 64);
-    unsigned* gmax_buf = compose ? c->d_gbound : c->d_gmax;
-    g.gmax_n = compose ? g.R : g.R * g.nig;
-    c->pend.composed = compose;
+    g.gmax_n = g.R * g.nig;
     {
-        StageTimer t(c, EINCM_STAGE_STATS, compose || stream_stats);
-        // Either way the statistics pass is the consumer of the u64 accumulator: it leaves the fp32 IWE stack in d_iwe (k_imstat
-        // leaves the clearing to the gather, the others clear the accumulator themselves).
-        if (compose) {
-            g.nparts = n_imwg;
-            launch_timed(c, EINCM_STAGE_STATS, k_imstat, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, g, ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG ? 1 : 0,
-                         c->d_acc, c->d_edges, c->d_iwe, c->d_G, c->d_parts, c->d_amax, c->d_ticket, ep, c->d_wc, c->d_coef, c->d_gbound,
-                         host_asm ? c->h_img : nullptr);
-        } else if (stream_stats) {
+        StageTimer t(c, EINCM_STAGE_STATS, stream_stats);
+        // Either way the statistics pass is the consumer of the u64 accumulator: it leaves the fp32 IWE stack in d_iwe and clears
+        // the accumulator.
+        if (stream_stats) {
             // gradient evaluations with the grad-mag contrast take the contrast energy from k_imgrad (which computes the Scharr
             // images anyway), so the statistics are a pure streaming reduction with NSPART fat partials per image
             g.nparts = NSPART;
@@ -1114,7 +1078,7 @@ int eval_end_launch(eincm_ctx* c) {
     bool wide = false;
     for (int b = 0; b < g.B; ++b) wide = wide || (c->win_events[b] * (int64_t)g.R < 4096);
     if (want_grad) {
-        if (!compose) {
+        {
             StageTimer t(c, EINCM_STAGE_IMGRAD, !div_grad && !obj);
             if (div_grad)
                 hipLaunchKernelGGL(k_divgrad, dim3(g.ntiles, g.R, g.B), dim3(NT), 0, c->stream, g, c->d_iwe, c->d_parts,
@@ -1152,8 +1116,8 @@ int eval_end_launch(eincm_ctx* c) {
                 static const int all_r_env = getenv("EINCM_GATHER_ALL_R") ? atoi(getenv("EINCM_GATHER_ALL_R")) : -1;
                 // (8 windows of 10^6 events at 16x16: 792 workgroups of 5 reference times each instead of 3960: 148 -> 135 us; one window:
                 // 99 workgroups, 29 -> 84 us - so only where the segments alone fill the chip's 768 workgroup slots of this kernel)
-                int all_r = (!direct11 && proj && !compose && !identity && n_g >= 700) ? 1 : 0;
-                if (all_r_env >= 0) all_r = (all_r_env && !direct11 && proj && !compose && !identity) ? 1 : 0;
+                int all_r = (!direct11 && proj && !identity && n_g >= 700) ? 1 : 0;
+                if (all_r_env >= 0) all_r = (all_r_env && !direct11 && proj && !identity) ? 1 : 0;
                 const unsigned grid_g = (unsigned)(((n_g + NXCD - 1) / NXCD) * NXCD * (all_r ? 1 : g.R));
                 // 2-DoF theta: workgroups per segment, so that a workgroup takes about what the round-2 tuning found best for this
                 // kernel (4096 events on one window, 16384 on the 8-window batch) whatever the segment length of the list
@@ -1168,26 +1132,23 @@ int eval_end_launch(eincm_ctx* c) {
 #define GATHER_ARGS(NTH) dim3(grid_g, nparts), dim3(NTH), \
                     gg.wincap_a * sizeof(float) + (direct11 ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2)), \
                     gg, n_g, items_g, xy_g, t_g, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_G, wins_g, c->d_gTheta, \
-                    direct11 ? 1 : 0, host_asm ? c->h_g11 : c->d_g11, c->d_wc, gmax_buf, direct11 ? THETA_CONST : THETA_TILE, order_g, \
+                    direct11 ? 1 : 0, host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, direct11 ? THETA_CONST : THETA_TILE, order_g, \
                     c->pend.use_arg ? 1 : 0, c->pend.theta_dev, c->pend.targ, \
-                    ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG ? 1 : 0, c->d_edges, c->d_iwe, c->d_coef, c->d_acc, 1, nparts, \
+                    1, nparts, \
                     h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth, (int)c->coarse_cap, \
                     (host_asm && proj) ? 1 : 0, c->d_gticket, c->d_win_item0, c->h_grad, \
                     (host_asm && proj && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap, all_r
-#define GATHER_TILE(WIDE_, COMPOSE_, PROJ_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, COMPOSE_, PROJ_>, GATHER_ARGS(NT_TILE))
-#define GATHER_ALLR(WIDE_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, 0, 1, 1>, GATHER_ARGS(NT_TILE))
+#define GATHER_TILE(WIDE_, PROJ_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, PROJ_>, GATHER_ARGS(NT_TILE))
+#define GATHER_ALLR(WIDE_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, 1, 1>, GATHER_ARGS(NT_TILE))
                 if (direct11) {
-                    if (compose) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_CONST, 0, NT, 1, 0>, GATHER_ARGS(NT));
-                    else         launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_CONST, 0, NT, 0, 0>, GATHER_ARGS(NT));
+                    launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_CONST, 0, NT, 0>, GATHER_ARGS(NT));
                     c->g11_per_item = g.R * nparts;
                 } else if (all_r) {
                     if (wide) GATHER_ALLR(1); else GATHER_ALLR(0);
                 } else if (wide) {
-                    if (compose) { if (proj) GATHER_TILE(1, 1, 1); else GATHER_TILE(1, 1, 0); }
-                    else         { if (proj) GATHER_TILE(1, 0, 1); else GATHER_TILE(1, 0, 0); }
+                    if (proj) GATHER_TILE(1, 1); else GATHER_TILE(1, 0);
                 } else {
-                    if (compose) { if (proj) GATHER_TILE(0, 1, 1); else GATHER_TILE(0, 1, 0); }
-                    else         { if (proj) GATHER_TILE(0, 0, 1); else GATHER_TILE(0, 0, 0); }
+                    if (proj) GATHER_TILE(0, 1); else GATHER_TILE(0, 0);
                 }
 #undef GATHER_TILE
 #undef GATHER_ALLR
@@ -1204,7 +1165,7 @@ int eval_end_launch(eincm_ctx* c) {
             StageTimer t(c, EINCM_STAGE_PROJECT, true);
             launch_timed(c, EINCM_STAGE_PROJECT, k_project, dim3(g.ntiles, g.B, nsrc), dim3(NT), 0, g, h, w,
                                (int)c->coarse_cap, events_projected ? 1 : 0, wide ? 1 : 0, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_gTheta, c->d_tvg,
-                               c->d_wc, gmax_buf, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap);
+                               c->d_wc, c->d_gmax, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap);
         }
     }
     if (!host_asm) {
@@ -1212,14 +1173,13 @@ int eval_end_launch(eincm_ctx* c) {
         // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
         launch_timed(c, EINCM_STAGE_FINAL, k_final, dim3(g.B), dim3(FT), 0, g, ep, c->d_parts, c->d_divparts, c->d_tvparts,
                            c->d_tmm, c->d_wc, g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
-                           c->d_g11, c->d_win_item0_2, c->n_items_2, c->g11_per_item, gmax_buf,
+                           c->d_g11, c->d_win_item0_2, c->n_items_2, c->g11_per_item, c->d_gmax,
                            zero_copy_out ? c->h_outs : c->d_outs, zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
         if (want_grad && identity) {
             hipLaunchKernelGGL(k_final_dense, dim3(256, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, wide ? 1 : 0, c->d_gTheta,
-                               c->d_tvg, c->d_wc, gmax_buf, c->d_outs, c->d_grad);
+                               c->d_tvg, c->d_wc, c->d_gmax, c->d_outs, c->d_grad);
         }
     }
-    if (want_grad) { c->last_composed = compose; c->last_ep = ep; c->last_g = g; }
     HIPCHK(c, hipGetLastError());
     c->n_pieces = 0;
     c->pend.copy_mode = (zero_copy_out || host_asm) ? 0 : 1;
@@ -1246,18 +1206,12 @@ void host_assemble(eincm_ctx* c) {
         double sum_rel_con = 0.0, sum_rel_corr = 0.0;
         for (int r = 0; r < g.R; ++r) {
             const double* q = c->h_img + ((size_t)b * g.R + r) * IMGSCAL_N;
-            double zero_img[IMGSCAL_N] = {0.0, 0.0, EPSN, HW, HW, 0.0, 0.0, 0.0, 0.0};
-            if (c->pend.composed && c->win_events[b] == 0) q = zero_img;      // no segment, no gather workgroup: the IWE is identically zero
             ImgScal s{};
             s.m = q[0]; s.M = q[1]; s.D = q[2]; s.cm = q[3]; s.cM = q[4]; s.sI = q[5]; s.sII = q[6]; s.sEI = q[7];
             double g2 = 0.0;
-            if (c->pend.composed) {
-                g2 = q[8];                           // k_imstat's per-workgroup energies, reduced with the other image scalars
-            } else {
-                const int nwg = (g.nig + IG_NT / 64 - 1) / (IG_NT / 64);          // one partial per k_imgrad workgroup
-                const double* g2p = c->h_g2 + ((size_t)b * g.R + r) * nwg;
-                for (int i = 0; i < nwg; ++i) g2 += g2p[i];
-            }
+            const int nwg = (g.nig + IG_NT / 64 - 1) / (IG_NT / 64);          // one partial per k_imgrad workgroup
+            const double* g2p = c->h_g2 + ((size_t)b * g.R + r) * nwg;
+            for (int i = 0; i < nwg; ++i) g2 += g2p[i];
             const double mse = mse_from_moments(s, wc.sE[r], wc.sEE[r], HW);
             const double mean = s.sI / HW;
             const double var = s.sII / HW - mean * mean;
@@ -1559,14 +1513,8 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     TRY(dalloc(&c->d_tvg, B * img * 2));
     TRY(dalloc(&c->d_mask, B * img));
     TRY(dalloc(&c->d_tmm, B * ntiles * 4));
-    const size_t pstride = (size_t)std::max(std::max(ntiles, NSPART), (int)((nig + IG_NT / 64 - 1) / (IG_NT / 64)));
+    const size_t pstride = (size_t)std::max(ntiles, NSPART);
     TRY(dalloc(&c->d_parts, B * R * pstride));
-    TRY(dalloc(&c->d_amax, B * R * pstride));
-    TRY(dalloc(&c->d_gbound, B * R));
-    TRY(hipMemset(c->d_gbound, 0, B * R * sizeof(unsigned)));
-    TRY(dalloc(&c->d_ticket, B * R));
-    TRY(hipMemset(c->d_ticket, 0, B * R * sizeof(unsigned)));
-    TRY(dalloc(&c->d_coef, B * R));
     TRY(dalloc(&c->d_gticket, B));
     TRY(hipMemset(c->d_gticket, 0, B * sizeof(unsigned)));
     TRY(dalloc(&c->d_divparts, B * R * ntiles));
@@ -1691,7 +1639,7 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     g.H = H; g.W = W; g.R = n_refs; g.B = n_windows;
     g.tilesX = (W + TS - 1) / TS; g.tilesY = (H + TS - 1) / TS; g.ntiles = g.tilesX * g.tilesY;
     g.igx = (W + IG_COLS - 1) / IG_COLS; g.nig = g.igx * ((H + IG_ROWS - 1) / IG_ROWS);
-    g.pstride = std::max(std::max(g.ntiles, NSPART), (g.nig + IG_NT / 64 - 1) / (IG_NT / 64));
+    g.pstride = std::max(g.ntiles, NSPART);
     g.gmax_n = g.R * g.nig;
     g.wincap = c->wincap; g.winmaxw = std::max(40, (int)std::lround(std::sqrt((double)c->wincap * 1.4)));
     g.wincap_a = g.wincap; g.winmaxw_a = g.winmaxw; c->wincap_2 = g.wincap;
@@ -2424,17 +2372,6 @@ int eincm_get_image_grad(eincm_ctx* c, float* G) {
     if (c && !c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
     if (c && !c->G_valid) return fail(c, EINCM_ERR_STATE, "no dL/dIWE image: the last evaluation had no gradient, or eincm_get_count_images reused the buffer");
     if (c && c->fp64) return copy_image(c, nullptr, c->f64.G, (size_t)c->g.B * c->g.R * c->g.H * c->g.W, G, nullptr);
-    if (c && c->last_composed) {
-        // the gather composed dL/dIWE while staging its windows; materialise the same image (same function, same scalars) on demand
-        HIPCHK(c, hipSetDevice(c->device));
-        const Geom& g = c->last_g;
-        const size_t n = (size_t)c->maxB * c->maxR * c->H * c->W;
-        if (!c->d_Gimg) HIPCHK(c, dalloc(&c->d_Gimg, n));
-        hipLaunchKernelGGL(k_compose, dim3(64, g.R, g.B), dim3(NT), 0, c->stream, g, c->last_ep, c->d_G, c->d_edges, c->d_iwe, c->d_parts,
-                           c->d_wc, c->d_Gimg);
-        HIPCHK(c, hipGetLastError());
-        return copy_out(c, G, c->d_Gimg, (size_t)g.B * g.R * g.H * g.W * sizeof(float));
-    }
     return copy_out(c, G, c ? c->d_G : nullptr, c ? (size_t)c->g.B * c->g.R * c->g.H * c->g.W * sizeof(float) : 0);
 }
 // 2-DoF evaluations skip the Theta image; build it when somebody asks for it

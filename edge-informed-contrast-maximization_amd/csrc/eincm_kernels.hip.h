@@ -66,8 +66,8 @@ struct Geom {
     int wincap, winmaxw;      // LDS destination-window capacity (pixels) and maximum width: the splat's segment list (items_s, "list b")
     int wincap_a, winmaxw_a;  // the same for the gather's own list (items, "list a"): its segments are longer, so they span more time and move further
     int nparts;               // StatParts per image written by the statistics kernel of this evaluation (ntiles or NSPART)
-    int pstride;              // StatPart slots per image: max(ntiles, NSPART, k_imstat workgroups per image)
-    int gmax_n;               // words of `gmax` per window: R * nig per-strip maxima of k_imgrad, or R bounds from k_imstat's tail
+    int pstride;              // StatPart slots per image: max(ntiles, NSPART)
+    int gmax_n;               // words of `gmax` per window: R * nig per-strip maxima of k_imgrad
     unsigned long long wmask; // bit b: window b takes part in this evaluation (eincm_loss_grad_masked: a lockstep solver's converged windows
                               // sit out; their workgroups leave at once and their outputs are not written).  Windows >= 64 always take part.
     int igx, nig;             // k_imgrad strips per image row / per image (IG_COLS x IG_ROWS pixels each): slots of g2parts and gmax
@@ -95,8 +95,9 @@ struct WinConst {                 // theta-independent constants of a window (lo
     double c0_gradmag, c0_var, d0;
     double zc[16];                // zero_corrs[r] = -MSE(E_r, n0)
     double sE[16], sEE[16];       // sum E_r, sum E_r^2
-    double eabs[16];              // max |E_r| (bounds dL/dIWE: gbound_from)
-    double inv_c0_gradmag, inv_c0_var, inv_zc[16];   // 1 / (c0 + eps), 1 / (zc[r] + eps): gcoef_from multiplies
+    double eabs[16];              // max |E_r|
+    double inv_c0_gradmag, inv_c0_var, inv_zc[16];   // 1 / (c0 + eps), 1 / (zc[r] + eps)
+    // (no kernel reads eabs or inv_*: they stay so that the layout, and with it every kernel's code, does not move)
     double mrw[16];               // multi-reference weights (losses.py:39-46)
     double dtmax;                 // max |t_e - tau_r| over the window's events and reference times (bounds a gradient term)
     double nev;                   // events staged in this window of this context
@@ -652,10 +653,7 @@ template <int NTH> struct SegWalk {
 // A segment is walked in chunks of <= chunk events; each chunk is accumulated in u32 fixed point (exact integer
 // ds_add_u32) and committed into the segment's f32 window; the window is flushed to HBM once per segment.
 // ------------------------------------------------------------------------------------------------
-// MERGE = 1 is the round-3 experiment "run-merged forward accumulation" (EINCM_SPLAT_MERGE=1): the kernel
-// walks the GATHER's copy of the events (sorted by source pixel inside a segment, a run per thread: SegWalk) and sums the taps of
-// consecutive events of a thread that round to the same destination pixel in nine registers before the nine ds_add_u32.
-template <int TM, int MULTI, int NTH, int MERGE>   // TM: the theta mode as a compile-time constant (0 = run-time argument); MULTI = 0: no segment is longer than a chunk
+template <int TM, int MULTI, int NTH>   // TM: the theta mode as a compile-time constant (0 = run-time argument); MULTI = 0: no segment is longer than a chunk
 __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, int theta_mode, int lds_multi,
         const Item* __restrict__ items,
         const uint32_t* __restrict__ ev_xy,    // x | y << 16, binned by (window, tile)
@@ -695,8 +693,7 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
         wn = wins[(size_t)item * g.R + r];
     }
     const int nwin = wn.ww * wn.wh;
-    const int wp = MERGE ? wn.ww : win_pitch(g, wn.ww), wp4 = wp * 4, nlds = wp * wn.wh;     // LDS row pitch and words (win_pitch; the MERGE experiment walks the
-                                                                            // gather's list, whose window table is sized for pitch = width)
+    const int wp = win_pitch(g, wn.ww), wp4 = wp * 4, nlds = wp * wn.wh;     // LDS row pitch and words (win_pitch)
     const bool multi = MULTI != 0 && it.count > chunk;       // MULTI == 0: the commit logic in the loop folds away
     {   // clear the window(s), 16 B per lane
         uint4* z = reinterpret_cast<uint4*>(ldsu);
@@ -788,54 +785,6 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
             __syncthreads();
         }
     };
-    if (MERGE) {
-        int cur_off = -1;                            // LDS word of the top-left tap of the run in the registers (-1: none)
-        uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0, m5 = 0, m6 = 0, m7 = 0, m8 = 0;
-        auto flush9 = [&]() {
-            if (cur_off < 0) return;
-            uint32_t* p = ldsu + cur_off; uint32_t* p1 = p + wp; uint32_t* p2 = p1 + wp;
-            atomicAdd(p, m0); atomicAdd(p + 1, m1); atomicAdd(p + 2, m2);
-            atomicAdd(p1, m3); atomicAdd(p1 + 1, m4); atomicAdd(p1 + 2, m5);
-            atomicAdd(p2, m6); atomicAdd(p2 + 1, m7); atomicAdd(p2 + 2, m8);
-        };
-        auto merge_ev = [&](const EvReg& ev) {
-            const double dt = ev.t - tau;
-            const int x = ev.xy & 0xffff, y = ev.xy >> 16;
-            const double2 v = (theta_mode == THETA_CONST) ? vconst : thtile[((ev.xy >> 11) & (31u << 5)) | (ev.xy & 31u)];
-            int irx, iry; float fx, fy;
-            warp_axis(x, v.x, dt, irx, fx);
-            warp_axis(y, v.y, dt, iry, fy);
-            const int lx = irx - 1 - wn.ox, ly = iry - 1 - wn.oy;
-            if ((unsigned)lx < (unsigned)(wn.ww - 2) && (unsigned)ly < (unsigned)(wn.wh - 2)) {
-                f2v km, k0, kp;
-                taps3x2(fx, fy, scy, km, k0, kp);
-                const int off = __mul24(ly, wp) + lx;
-                const uint32_t t0 = fix_u32(km.y, km.x), t1 = fix_u32(km.y, k0.x), t2 = fix_u32(km.y, kp.x);
-                const uint32_t t3 = fix_u32(k0.y, km.x), t4 = fix_u32(k0.y, k0.x), t5 = fix_u32(k0.y, kp.x);
-                const uint32_t t6 = fix_u32(kp.y, km.x), t7 = fix_u32(kp.y, k0.x), t8 = fix_u32(kp.y, kp.x);
-                if (off == cur_off) {                // exact integer adds: the image is bit-identical to the unmerged one
-                    m0 += t0; m1 += t1; m2 += t2; m3 += t3; m4 += t4; m5 += t5; m6 += t6; m7 += t7; m8 += t8;
-                } else {
-                    flush9();
-                    cur_off = off;
-                    m0 = t0; m1 = t1; m2 = t2; m3 = t3; m4 = t4; m5 = t5; m6 = t6; m7 = t7; m8 = t8;
-                }
-            } else {
-                flush9();
-                cur_off = -1;
-                splat_ev(ev);                        // the direct path for taps outside the window
-            }
-        };
-        const SegWalk<512> walk(n, tid);
-        const int c = walk.half;
-        const int K = c ? walk.K1 : walk.K0, rem = c ? walk.rem1 : walk.rem0;
-        const uint32_t* __restrict__ px = exy + (c ? walk.n0 : 0) + walk.tt;
-        const double* __restrict__ pt = et + (c ? walk.n0 : 0) + walk.tt;
-#pragma unroll 2
-        for (int j = 0; j < K - 1; ++j) { EvReg ev; ev.xy = px[j * 256]; ev.t = pt[j * 256]; merge_ev(ev); }
-        if (K > 0 && walk.tt < rem) { EvReg ev; ev.xy = px[(K - 1) * 256]; ev.t = pt[(K - 1) * 256]; merge_ev(ev); }
-        flush9();
-    } else {
     EvReg A, B, C;
     load_ev(A, tid);
     load_ev(B, tid + NTH);
@@ -847,7 +796,6 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
         if (j + 2 < iters) step(C, A, B, j + 2);
     }
 #endif
-    }
     if (!multi) __syncthreads();
 #ifdef EINCM_ABL_S_NOFLUSH
     return;
@@ -1229,202 +1177,6 @@ __global__ __launch_bounds__(IG_NT) void k_imgrad(Geom g, EvalParams ep,
     }
 }
 
-// The per-image scalars G is composed from (see k_imstat), in the precision the composition runs in (fp32 like the image itself;
-// the fp64 originals are the formulas of k_imgrad).  gradmag = 0: the variance contrast, dc = I - mean I.
-struct GCoef { float m, M, invD, k_c, k_n, k_m, k_M, meanI; };
-struct ImgCoef { GCoef q; float bound; float pad_[7]; };      // one 64-byte record per image: what the gather loads (uniformly: scalar registers)
-__device__ __forceinline__ GCoef gcoef_from(const ImgScal& s, const WinConst& c, const EvalParams& ep, int r, int R, double HW) {
-    // Three divisions (1/D and the two tie counts): the window constants come as reciprocals (WinConst.inv_*), everything else is
-    // multiplied by the one 1/D.  A division costs ~10 instructions and ~8 live registers; a dozen of them interleaved took the
-    // composing gather from 66 to 106 VGPRs (7 -> 4 waves per SIMD).  The results are rounded to fp32 anyway.
-    const double iD = 1.0 / s.D;
-    const double a_r = -ep.alpha * c.mrw[r] * ((ep.contrast_kind == 1) ? c.inv_c0_var : c.inv_c0_gradmag) / (double)R;
-    const double k = -ep.beta * c.mrw[r] * c.inv_zc[r] * (2.0 / ((double)R * HW));
-    const double a = s.m * iD;
-    const double S_n = s.sI * iD - HW * a;
-    const double S_En = s.sEI * iD - a * c.sE[r];
-    const double S_nn = (s.sII * iD - 2.0 * a * s.sI) * iD + HW * a * a;
-    const double sGn_n = k * (S_En - S_nn);                  // sum Gn*n
-    const double sGn = k * (c.sE[r] - S_n);                  // sum Gn
-    GCoef q;
-    q.m = (float)s.m; q.M = (float)s.M;                      // exact: extrema of fp32 pixels
-    q.invD = (float)iD;
-    q.k_c = (float)(a_r * (2.0 / HW));
-    q.k_n = (float)(k * iD);
-    q.k_m = (float)(((sGn_n - sGn) * iD) / s.cm);            // dm / #argmin
-    q.k_M = (float)((-sGn_n * iD) / s.cM);                   // dM / #argmax
-    q.meanI = (float)(s.sI * (1.0 / HW));
-    return q;
-}
-// An upper bound of max |G| over one image from its scalars: |dc| <= max|A| (grad-mag) or D (variance), |E - n| <= max|E| + 1.
-// The fixed-point scale of the gradient accumulators needs SOME bound of what is added (grad_shift_pixel / grad_shift); the tie terms
-// k_m, k_M dominate it by orders of magnitude, so this one costs at most a bit against the exact maximum k_imgrad used to measure.
-__device__ __forceinline__ double gbound_from(const GCoef& q, const ImgScal& s, bool gradmag, double amax, double emax) {
-    return 1.0001 * (fabs((double)q.k_c) * (gradmag ? amax : s.D) + fabs((double)q.k_n) * (emax + 1.0) + fabs((double)q.k_m) + fabs((double)q.k_M));
-}
-// G = dL/dIWE at one pixel from (A, E, I): 3 loads + 8 fp32 operations; every gradient evaluation of the composed path and
-// eincm_get_image_grad (k_compose) use this one function, so they see the same image.
-__device__ __forceinline__ float compose_G(const GCoef& q, bool gradmag, float a, float e, float v) {
-    const float dc = gradmag ? a : v - q.meanI;
-    const float n = (v - q.m) * q.invD;
-    float gv = fmaf(q.k_c, dc, q.k_n * (e - n));
-    gv += (v == q.m) ? q.k_m : 0.0f;
-    gv += (v == q.M) ? q.k_M : 0.0f;
-    return gv;
-}
-
-// ------------------------------------------------------------------------------------------------
-// k_imstat: the image pass of a gradient evaluation in ONE kernel (round 3): consumer of the u64 accumulator (exact sum -> fp32 IWE,
-// one rounding), image statistics (min / max with tie counts, sum I, sum I^2, sum E I) and the stats-INDEPENDENT part of dL/dIWE:
-//   A = adj_Sx(gx) + adj_Sy(gy) = -(conv(gx, Sx) + conv(gy, Sy)),  (gx, gy) = Scharr(I)      [reverse of contrast_objectives.py:22-25]
-// with the contrast energy sum(gx^2 + gy^2) and max |A| as by-products.  What depends on the statistics,
-//   G = k_c A + k_n (E - n) + k_m [I == m] + k_M [I == M],   n = (I - m) / D                  [reverse of img_utils.py:24-25, losses.py:62-67]
-// is linear in per-image scalars, so the gather composes G while it stages its window (compose_G) and no kernel has to wait for the
-// statistics in between: splat -> imstat -> gather instead of splat -> stats -> imgrad -> gather (a dependent kernel costs 6-8 us
-// here whatever its work: profiles/r03/latency_chain.md).  Same register sliding window as k_imgrad (a lane owns a column, DPP
-// neighbours, no LDS).  The accumulator is NOT cleared here (a neighbour strip still reads its halo from it): the gather does that.
-// grid (ceil(nig / 4), R, B); one StatPart per workgroup (its <= 4 strips combined), sG2 = contrast energy.
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(IG_NT) void k_imstat(Geom g, int gradmag,
-        const unsigned long long* __restrict__ acc, const float* __restrict__ edges,
-        float* __restrict__ iwe, float* __restrict__ A,
-        StatPart* __restrict__ parts,          // (B,R,pstride): slot blockIdx.x
-        unsigned* __restrict__ amax,           // (B,R,pstride): max |A| of the workgroup's strips as float bits
-        // the tail: the workgroup of an image that arrives LAST reduces the image's partials and derives what the gather composes
-        // dL/dIWE with (one ImgCoef per image, instead of every gather workgroup doing that in its prologue: there it cost the gather
-        // 40 VGPRs, 7 -> 4 waves per SIMD)
-        unsigned* __restrict__ ticket,         // (B,R) arrival counters, zero between launches (the last arriver resets its own)
-        EvalParams ep, const WinConst* __restrict__ wc,
-        ImgCoef* __restrict__ coef,            // (B,R)
-        unsigned* __restrict__ gbound,         // (B,R) bound of max |dL/dIWE| of the image as float bits (the gmax of a composed evaluation)
-        double* __restrict__ imgscal_out)      // (B,R,IMGSCAL_N) or nullptr: the reduced image scalars for the host (pinned memory)
-{
-    __shared__ double red[IG_NT / 64][8];
-    __shared__ unsigned redm[IG_NT / 64];
-    __shared__ int s_last;
-    const int r = blockIdx.y, b = blockIdx.z, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int strip = __builtin_amdgcn_readfirstlane(blockIdx.x * (IG_NT / 64) + wv);   // wave-uniform: row tests stay scalar
-    if (!win_active(g, b)) return;
-    const size_t img = ((size_t)b * g.R + r) * g.H * g.W;
-    const unsigned long long* __restrict__ Ac = acc + img;
-    const float* __restrict__ E = edges + img;
-    float* __restrict__ Io = iwe + img;
-    float* __restrict__ Ao = A + img;
-    const bool live = strip < g.nig;                          // wave-uniform; dead waves run the loop on clamped addresses and contribute nothing
-    const int sidx = live ? strip : 0;
-    const int cx0 = (sidx % g.igx) * IG_COLS, cy0 = (sidx / g.igx) * IG_ROWS;
-    const int x = cx0 - 2 + lane;
-    const int xc = min(max(x, 0), g.W - 1);
-    unsigned long long arow[IG_ROWS + 4];
-    float erow[IG_ROWS];
-#pragma unroll
-    for (int k = 0; k < IG_ROWS + 4; ++k) arow[k] = Ac[(size_t)min(max(cy0 - 2 + k, 0), g.H - 1) * g.W + xc];
-#pragma unroll
-    for (int k = 0; k < IG_ROWS; ++k) erow[k] = E[(size_t)min(cy0 + k, g.H - 1) * g.W + xc];
-    const bool col_in = (x >= 0 && x < g.W);
-    const bool own = live && col_in && lane >= 2 && lane < 2 + IG_COLS;
-    const int yend = min(cy0 + IG_ROWS, g.H);                // own rows [cy0, yend)
-
-    float tA = 0.f, tB = 0.f, dA = 0.f, dB = 0.f, gyA = 0.f, gyB = 0.f, qA = 0.f, qB = 0.f;
-    float g2f = 0.f;
-    unsigned am = 0u;
-    double mn = INFINITY, mx = -INFINITY, cmn = 0.0, cmx = 0.0, sI = 0.0, sII = 0.0, sEI = 0.0;
-#pragma unroll
-    for (int k = 0; k < IG_ROWS + 4; ++k) {
-        const int i = cy0 - 2 + k;
-        const float tv = (float)((double)arow[k] * ACC_INV);                  // exact u64 sum -> fp32 pixel (one rounding), as k_stats_stream
-        const float tC = (i >= 0 && i < g.H && col_in) ? tv : 0.0f;           // zero padding (Scharr 'same')
-        float ax = 0.f, ay = 0.f, dC = 0.f, gy = 0.f, qC = 0.f;
-        if (gradmag) {                                       // uniform: the DPP moves below always run with every lane enabled
-            dC = lane_p1(tC) - lane_m1(tC);
-            float gx = 3.0f * dC + 10.0f * dB + 3.0f * dA;
-            const float e = tC - tA;
-            gy = 3.0f * lane_p1(e) + 10.0f * e + 3.0f * lane_m1(e);
-            const bool in1 = (i - 1 >= 0 && i - 1 < g.H) && col_in;
-            gx = in1 ? gx : 0.0f; gy = in1 ? gy : 0.0f;
-            const bool own1 = own && (i - 1 >= cy0 && i - 1 < yend);
-            g2f += own1 ? (gx * gx + gy * gy) : 0.0f;
-            qC = lane_p1(gx) - lane_m1(gx);
-            ax = 3.0f * qC + 10.0f * qB + 3.0f * qA;
-            const float eg = gy - gyA;
-            ay = 3.0f * lane_p1(eg) + 10.0f * eg + 3.0f * lane_m1(eg);
-        }
-        const int o = i - 2;
-        if (o >= cy0 && o < yend && own) {
-            const float af = -(ax + ay);
-            Io[(size_t)o * g.W + x] = tA;
-            if (gradmag) { Ao[(size_t)o * g.W + x] = af; am = max(am, __float_as_uint(af) & 0x7fffffffu); }
-            const double v = (double)tA, e = (double)erow[k >= 4 ? k - 4 : 0];
-            cmn = (v < mn) ? 1.0 : cmn + (v == mn ? 1.0 : 0.0);
-            cmx = (v > mx) ? 1.0 : cmx + (v == mx ? 1.0 : 0.0);
-            mn = fmin(mn, v); mx = fmax(mx, v);
-            sI += v; sII += v * v; sEI += e * v;
-        }
-        tA = tB; tB = tC; dA = dB; dB = dC; gyA = gyB; gyB = gy; qA = qB; qB = qC;
-    }
-    // wave, then workgroup: (min, #ties) and (max, #ties) combine associatively; sums in the fixed order of the trees
-    const double wmn = wave_min(mn), wmx = wave_max(mx);
-    const double bmn = __shfl(wmn, 0, 64), bmx = __shfl(wmx, 0, 64);
-    cmn = wave_sum(mn == bmn ? cmn : 0.0);
-    cmx = wave_sum(mx == bmx ? cmx : 0.0);
-    sI = wave_sum(sI); sII = wave_sum(sII); sEI = wave_sum(sEI);
-    const double g2 = wave_sum((double)g2f);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) am = max(am, (unsigned)__shfl_down((int)am, o, 64));
-    if (lane == 0) {
-        red[wv][0] = bmn; red[wv][1] = bmx; red[wv][2] = cmn; red[wv][3] = cmx; red[wv][4] = sI; red[wv][5] = sII; red[wv][6] = sEI; red[wv][7] = g2;
-        redm[wv] = am;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        StatPart o;
-        o.mn = red[0][0]; o.mx = red[0][1]; o.cmn = red[0][2]; o.cmx = red[0][3]; o.sI = red[0][4]; o.sII = red[0][5]; o.sEI = red[0][6]; o.sG2 = red[0][7];
-        unsigned m = redm[0];
-        for (int i = 1; i < IG_NT / 64; ++i) {
-            if (red[i][0] < o.mn) { o.mn = red[i][0]; o.cmn = red[i][2]; } else if (red[i][0] == o.mn) o.cmn += red[i][2];
-            if (red[i][1] > o.mx) { o.mx = red[i][1]; o.cmx = red[i][3]; } else if (red[i][1] == o.mx) o.cmx += red[i][3];
-            o.sI += red[i][4]; o.sII += red[i][5]; o.sEI += red[i][6]; o.sG2 += red[i][7];
-            m = max(m, redm[i]);
-        }
-        // publish: write-through (agent-scope) stores by this ONE lane, drained, then the ticket (cdna_hip_programming.md Guideline 16, R1)
-        const size_t slot = ((size_t)b * g.R + r) * g.pstride + blockIdx.x;
-        double* po = reinterpret_cast<double*>(parts + slot);
-        const double ov[8] = {o.mn, o.mx, o.cmn, o.cmx, o.sI, o.sII, o.sEI, o.sG2};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) __hip_atomic_store(po + i, ov[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(amax + slot, m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned old = __hip_atomic_fetch_add(ticket + b * g.R + r, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = (old == gridDim.x - 1u) ? 1 : 0;
-        if (old == gridDim.x - 1u) __hip_atomic_store(ticket + b * g.R + r, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-    }
-    __syncthreads();
-    if (!s_last) return;                                     // uniform
-    if (threadIdx.x < 64) {                                  // one wave: acquire (this CU's L1 may hold stale lines of the partials), then reduce
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const size_t slot0 = ((size_t)b * g.R + r) * g.pstride;
-        const ImgScal s = reduce_parts(parts + slot0, g.nparts);
-        unsigned am2 = 0u;
-        for (int i = lane; i < g.nparts; i += 64) am2 = max(am2, amax[slot0 + i]);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) am2 = max(am2, (unsigned)__shfl_xor((int)am2, o, 64));
-        if (lane == 0) {
-            const WinConst& c = wc[b];
-            ImgCoef ic;
-            ic.q = gcoef_from(s, c, ep, r, g.R, (double)g.H * (double)g.W);
-            const float bound = (float)gbound_from(ic.q, s, gradmag != 0, (double)__uint_as_float(am2), c.eabs[r]);
-            ic.bound = bound;
-            coef[b * g.R + r] = ic;
-            gbound[b * g.R + r] = __float_as_uint(bound);
-            if (imgscal_out) {
-                double* o = imgscal_out + ((size_t)b * g.R + r) * IMGSCAL_N;
-                o[0] = s.m; o[1] = s.M; o[2] = s.D; o[3] = s.cm; o[4] = s.cM; o[5] = s.sI; o[6] = s.sII; o[7] = s.sEI; o[8] = s.sG2;
-            }
-        }
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // k_div: IWE divergence of the normalised IWE (event_collapse_objectives.py:8-20), forward only.
 //   d = mean | K (*) (n (*) Sx) + K (*) (n (*) Sy) | = mean | K (*) (gx_n + gy_n) |, every stage zero padded.
@@ -1699,21 +1451,17 @@ __device__ __forceinline__ void project_tile_to_cells(const Geom& g, int h, int 
         if (ay != 0.0) atomicAdd(o + 1, (unsigned long long)fix64_wide(ay));
     }
 }
-template <int TM, int WIDE, int NTH, int COMPOSE, int PROJ, int ALLR = 0>      // NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE); 0 = take the run-time argument
+template <int TM, int WIDE, int NTH, int PROJ, int ALLR = 0>      // NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE); 0 = take the run-time argument
 __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_items,      // WIDE: 61-bit fixed point per event (tiny windows, see grad_shift_pixel)
         const Item* __restrict__ items, const uint32_t* __restrict__ ev_xy, const double* __restrict__ ev_t,
         const double* __restrict__ Theta, const double* __restrict__ tmm, const double* __restrict__ edge_ts,
-        const float* __restrict__ G,           // (B,R,H,W) dL/dIWE written by k_imgrad (COMPOSE = 0), or the A image of k_imstat (COMPOSE = 1)
+        const float* __restrict__ G,           // (B,R,H,W) dL/dIWE written by k_imgrad
         const Window* __restrict__ wins,       // (n_items, R) windows of this evaluation
         long long* __restrict__ gTheta,        // (B,H,W,2) i64 fixed point, zero on entry (cleared by its consumer)
         int direct11, double* __restrict__ g11,                     // 2-DoF theta: (n_items, R, 2) per-workgroup partials of dL/dtheta
-        const WinConst* __restrict__ wc, const unsigned* __restrict__ gmax,   // scale of the i64 accumulators (grad_shift), COMPOSE = 0
+        const WinConst* __restrict__ wc, const unsigned* __restrict__ gmax,   // scale of the i64 accumulators (grad_shift)
         int theta_mode, const int32_t* __restrict__ order,
         int use_arg, const double* __restrict__ theta_c, ThetaArg targ,   // 2-DoF theta (B,2): in the kernel arguments, or behind theta_c
-        // COMPOSE = 1 (k_imstat in front instead of k_stats_stream + k_imgrad): G is composed from (A, E, I) while the window is staged
-        int gradmag_i, const float* __restrict__ edges, const float* __restrict__ iwe,
-        const ImgCoef* __restrict__ coef,      // (B,R) per-image scalars and |G| bounds from k_imstat's tail
-        unsigned long long* __restrict__ acc,  // the u64 IWE accumulator: consumed by k_imstat, cleared here (a slice per workgroup)
         int list_a,                            // the segments walked are the gather's own list (window capacity wincap_a), not the splat's
         int nparts,                            // 1, 2 or 4 = gridDim.y: workgroups sharing a segment (256-thread form only)
         // PROJ = 1 (theta grids whose tiles touch <= PG_MAXC x PG_MAXC cells): the workgroup projects its tile's sums onto the theta
@@ -1738,14 +1486,6 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     unsigned long long* accum = reinterpret_cast<unsigned long long*>(lds + wincap);   // i64 fixed point: ds_add_u64 (3.7 lane-ops/clk/CU; ds_add_f32: 0.33)
     double2* thtile = reinterpret_cast<double2*>(lds + wincap + (direct11 ? 0 : TS * TS * 4));
     float f11x = 0.0f, f11y = 0.0f;             // direct11: this thread's share of sum_e -dt * dL/dw
-    if (COMPOSE) {
-        // consumer-clears, delegated: k_imstat has read the accumulator (halos included), so every workgroup of this launch zeroes
-        // an equal share of it with plain stores (fire and forget; nothing in this kernel reads it)
-        const size_t total = (size_t)g.B * g.R * g.H * g.W;
-        const size_t nb = (size_t)gridDim.x * gridDim.y, bid = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-        const size_t lo = total * bid / nb, hi = total * (bid + 1) / nb;
-        for (size_t i = lo + threadIdx.x; i < hi; i += NTH) acc[i] = 0ull;
-    }
     int item, r;
     constexpr bool all_r = ALLR != 0;
     if (!block_to_work(n_items, all_r ? 1 : g.R, order, item, r)) return;
@@ -1753,7 +1493,6 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     if (!win_active(g, it.win)) return;
     double tau = edge_ts[it.win * g.R + r];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const bool gradmag = gradmag_i != 0;
     double2 vconst = make_double2(0.0, 0.0);
     Window wn;
     if (theta_mode == THETA_CONST) {              // the same window k_splat derived for itself (see there)
@@ -1766,8 +1505,6 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     int wp = (theta_mode == THETA_CONST) ? win_pitch(g, wn.ww) : wn.ww;      // LDS row pitch of the G window (see item_window)
     size_t img = ((size_t)it.win * g.R + r) * g.H * g.W;
     const float* __restrict__ Gi = G + img;
-    const float* __restrict__ Ei = edges + img;
-    const float* __restrict__ Ii = iwe + img;
     const int tx = it.tile % g.tilesX, ty = it.tile / g.tilesX;
     const int x0 = tx * TS, y0 = ty * TS;
     if (theta_mode != THETA_CONST) {
@@ -1778,17 +1515,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         }
     }
     if (!direct11) for (int i = threadIdx.x; i < TS * TS * 2; i += NTH) accum[i] = 0ull;
-    const ImgCoef* __restrict__ cw = coef + (COMPOSE ? it.win * g.R : 0);
-    GCoef q{};
-    if (COMPOSE) q = cw[r].q;                      // uniform address: scalar loads, the coefficients live in SGPRs
-    auto G_at = [&](size_t p) -> float {          // dL/dIWE at pixel p of this (window, reference time)
-        if (COMPOSE) return compose_G(q, gradmag, gradmag ? Gi[p] : 0.0f, Ei[p], Ii[p]);
-        return Gi[p];
-    };
-    auto G_far = [&](size_t p) -> float {         // the same for the rare taps outside the LDS window, inside the event loop
-        if (!COMPOSE) return Gi[p];
-        return compose_G(q, gradmag, gradmag ? Gi[p] : 0.0f, Ei[p], Ii[p]);
-    };
+    auto G_at = [&](size_t p) -> float { return Gi[p]; };     // dL/dIWE at pixel p of this (window, reference time)
     auto load_window = [&]() {                    // the G window of the current reference time into LDS
     if (wn.ox >= 0 && wn.oy >= 0 && wn.ox + wn.ww <= g.W && wn.oy + wn.wh <= g.H) {      // the usual case: window inside the image
         const size_t o0 = (size_t)wn.oy * g.W + wn.ox;
@@ -1805,17 +1532,10 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     };
     load_window();
     double gscale = 0.0;                          // 2^eg of this window's gradient accumulators
-    double gm_used = 0.0;                         // max |G| (or its bound) the scales derive from
+    double gm_used = 0.0;                         // max |G| the scales derive from
     if (!direct11) {
-        double gm;
-        if (COMPOSE) {                            // the same R words k_project / k_final* read through gmax_of (gmax_n = R)
-            float gmf = cw[0].bound;
-            for (int rr = 1; rr < g.R; ++rr) gmf = fmaxf(gmf, cw[rr].bound);
-            gm = (double)gmf;
-        } else {
-            __shared__ unsigned gms[NTH / 64];
-            gm = gmax_of(gmax + (size_t)it.win * g.gmax_n, g.gmax_n, gms);
-        }
+        __shared__ unsigned gms[NTH / 64];
+        const double gm = gmax_of(gmax + (size_t)it.win * g.gmax_n, g.gmax_n, gms);
         gscale = ldexp(1.0, grad_shift_pixel(wc[it.win], gm, g.R, WIDE != 0));
         gm_used = gm;
     }
@@ -1853,7 +1573,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
 #endif
         }
         float gwx, gwy;
-        event_dLdw(g, wn, wp, lds, G_far, x, y, vcur, dt, gwx, gwy);
+        event_dLdw(g, wn, wp, lds, G_at, x, y, vcur, dt, gwx, gwy);
         if (direct11) {          // theta (1,1,2): Theta is constant, dL/dtheta = sum over all events; no per-pixel image needed.
             // fp32 over the thread's own <= 64 terms (their rounding errors are independent across 10^6 threads and average out:
             // measured 1e-9 relative on the gradient), fp64 from there on
@@ -1897,7 +1617,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     wn = wins[(size_t)item * g.R + rr];
     wp = wn.ww;
     img = ((size_t)it.win * g.R + rr) * g.H * g.W;
-    Gi = G + img; Ei = edges + img; Ii = iwe + img;
+    Gi = G + img;
     load_window();
     __syncthreads();
     }
@@ -1973,27 +1693,6 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         const unsigned long long v = accum[i];
         if (px < tw && py < th && v != 0ull) atomicAdd(gT + ((size_t)(y0 + py) * g.W + (x0 + px)) * 2 + c, v);
     }
-}
-
-// k_compose: dL/dIWE as an image, for eincm_get_image_grad after an evaluation whose gather composed it on the fly (the same
-// compose_G on the same scalars).  grid (blocks, R, B), grid-stride over the pixels of image (b, r).
-__global__ __launch_bounds__(NT) void k_compose(Geom g, EvalParams ep, const float* __restrict__ A, const float* __restrict__ edges,
-                                                 const float* __restrict__ iwe, const StatPart* __restrict__ parts,
-                                                 const WinConst* __restrict__ wc, float* __restrict__ G)
-{
-    __shared__ GCoef sq;
-    const int r = blockIdx.y, b = blockIdx.z;
-    if (!win_active(g, b)) return;
-    if (threadIdx.x < 64) {
-        const ImgScal s = reduce_parts(parts + ((size_t)b * g.R + r) * g.pstride, g.nparts);
-        if (threadIdx.x == 0) sq = gcoef_from(s, wc[b], ep, r, g.R, (double)g.H * (double)g.W);
-    }
-    __syncthreads();
-    const GCoef q = sq;
-    const bool gradmag = (ep.contrast_kind == 0);
-    const size_t n = (size_t)g.H * g.W, img = ((size_t)b * g.R + r) * n;
-    for (size_t i = (size_t)blockIdx.x * NT + threadIdx.x; i < n; i += (size_t)gridDim.x * NT)
-        G[img + i] = compose_G(q, gradmag, gradmag ? A[img + i] : 0.0f, edges[img + i], iwe[img + i]);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""The environment switches DESIGN.md documents (experiments kept as a record, fallbacks, tuning knobs) still produce the objective:
+"""The environment switches DESIGN.md documents (fallbacks, tuning knobs) still produce the objective:
 every one of them is run in its own process (three are read once per process) on a two-window batch over four theta shapes and
 compared with the default configuration and with the oracle.  Integer accumulation makes the IWE stack independent of layouts and
 window capacities; segment lengths change the fixed-point scale of a tap, hence 'equal to ~1e-7' rather than bit for bit there."""
@@ -17,8 +17,6 @@ probe = importlib.util.module_from_spec(spec)
 spec.loader.exec_module(probe)
 
 SWITCHES = [
-    ({'EINCM_COMPOSE': '1'}, 'fused statistics + composing gather (DESIGN 4.3)'),
-    ({'EINCM_SPLAT_MERGE': '1'}, 'run-merged forward accumulation (DESIGN 4.4)'),
     ({'EINCM_NO_HOST_ASM': '1'}, 'scalar assembly on the device (k_final)'),
     ({'EINCM_NO_BIG_THETA_ARG': '1'}, 'k_theta reads theta from the pinned staging buffer instead of its kernel arguments'),
     ({'EINCM_NO_PROJ_IN_GATHER': '1'}, 'dL/dTheta image + k_project instead of the in-gather projection'),
