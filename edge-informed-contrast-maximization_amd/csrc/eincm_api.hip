@@ -43,8 +43,7 @@ struct eincm_ctx {
     int H = 0, W = 0, maxR = 0, maxB = 0;
     int64_t maxN = 0;
     uint32_t cflags = 0;
-    int chunk = 4096;              // events per inner chunk of k_splat (u32 accumulation bound): = default splat segment, so no commit pass
-    int seg = 0;                   // events per segment (0 = choose per batch); EINCM_SEG / EINCM_CHUNK override
+    int seg = 0;                   // events per segment (0 = choose per batch); EINCM_SEG overrides
     int seg_used = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -83,9 +82,6 @@ struct eincm_ctx {
     int wincap_2 = WIN_CAP_DEFAULT;
     int wincap = WIN_CAP_DEFAULT;
     bool wincap_fixed = false;     // EINCM_WINCAP pins the capacity; otherwise it is chosen per evaluation from max|theta|
-    bool chunk_fixed = false;      // EINCM_CHUNK given
-    int g11_per_item = 1;          // slots per segment in d_g11 written by the last gather launch
-    double gather_wg_events = 4096.0;   // events a 2-DoF gather workgroup should take (set_windows: by batch size)
     // device-side staging (eincm_binning.hip.h)
     int16_t* d_raw_x = nullptr; int16_t* d_raw_y = nullptr; double* d_raw_t = nullptr;   // (maxN) events as handed over
     BinBlock* d_binblocks = nullptr; int32_t* d_win_blk = nullptr; uint32_t* d_blockhist = nullptr;
@@ -570,22 +566,19 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
         c->acc_dirty = true;
         if (c->n_items_s > 0) {
             const int theta_mode = const_theta ? THETA_CONST : THETA_TILE;
-            const int lds_multi = (c->seg_s_used > c->chunk) ? 1 : 0;      // segments longer than a chunk need the f32 commit window
-            const size_t lds_bytes = (size_t)(lds_multi ? 2 : 1) * g.wincap * sizeof(float)
-                                   + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
+            const size_t lds_bytes = (size_t)g.wincap * sizeof(float) + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
             const bool sshort = c->pend.splat_short && const_theta;
             const int n_sp = sshort ? c->n_items_sh : c->n_items_s;
             const Item* items_sp = sshort ? c->d_items_sh : c->d_items_s;
             const int32_t* order_sp = sshort ? c->d_order_sh : c->d_order_s;
             const unsigned grid_sp = (unsigned)(((n_sp + NXCD - 1) / NXCD) * NXCD * g.R);
-#define SPLAT_ARGS(NTH) dim3(grid_sp), dim3(NTH), lds_bytes, g, n_sp, c->chunk, theta_mode, lds_multi, \
-                   items_sp, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_wins_s, c->d_acc, order_sp, \
+#define SPLAT_ARGS(NTH) dim3(grid_sp), dim3(NTH), lds_bytes, g, n_sp, \
+                   items_sp, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->d_wins_s, c->d_acc, order_sp, \
                    use_arg ? 1 : 0, theta_dev, targ
-            if (lds_multi)                      launch_timed(c, EINCM_STAGE_SPLAT, k_splat<0, 1, NT>, SPLAT_ARGS(NT));      // long segments (EINCM_SEG_SPLAT > EINCM_CHUNK)
             // 512 threads per workgroup in both compile-time modes: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
             // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
-            else if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 0, 512>, SPLAT_ARGS(512));
-            else                                launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_TILE, 0, 512>, SPLAT_ARGS(512));
+            if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 512>, SPLAT_ARGS(512));
+            else                           launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_TILE, 512>, SPLAT_ARGS(512));
 #undef SPLAT_ARGS
         }
     }
@@ -923,9 +916,6 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         const int floor_k = two_dof ? 2 : 0;
         int cap = cap_of(lds_words(false, side), floor_k);
         const bool pal_s = c->pitch_policy != 0 && lds_words(true, side) <= (double)cap;
-        // long splat segments (EINCM_SEG_SPLAT > EINCM_CHUNK) keep a second, f32 window: 2 * cap * 4 B + the 16 KiB Theta tile must
-        // stay within the 64 KiB of dynamic LDS a launch gets without an attribute
-        if (c->seg_s_used > c->chunk) cap = std::min(cap, 4608);
         c->g.wincap = cap;
         c->g.winmaxw = std::max(40, (int)std::lround(std::sqrt((double)cap * 1.4)));
         c->g.pitch_aligned = pal_s ? 1 : 0;
@@ -1119,30 +1109,18 @@ int eval_end_launch(eincm_ctx* c) {
                 int all_r = (!direct11 && proj && !identity && n_g >= 700) ? 1 : 0;
                 if (all_r_env >= 0) all_r = (all_r_env && !direct11 && proj && !identity) ? 1 : 0;
                 const unsigned grid_g = (unsigned)(((n_g + NXCD - 1) / NXCD) * NXCD * (all_r ? 1 : g.R));
-                // 2-DoF theta: workgroups per segment, so that a workgroup takes about what the round-2 tuning found best for this
-                // kernel (4096 events on one window, 16384 on the 8-window batch) whatever the segment length of the list
-                int nparts = 1;
-                if (direct11) {
-                    const double per_tile = (double)std::max<int64_t>(c->n_events, 1) / ((double)g.B * g.ntiles);
-                    const double seg_eff = std::min((double)c->seg_2_used, per_tile);
-                    const double target = c->gather_wg_events;
-                    nparts = seg_eff >= 3.0 * target ? 4 : (seg_eff >= 1.5 * target ? 2 : 1);
-                    if (const char* e = getenv("EINCM_GATHER_PARTS")) { const int v = atoi(e); if (v == 1 || v == 2 || v == 4) nparts = v; }
-                }
-#define GATHER_ARGS(NTH) dim3(grid_g, nparts), dim3(NTH), \
+#define GATHER_ARGS(NTH) dim3(grid_g), dim3(NTH), \
                     gg.wincap_a * sizeof(float) + (direct11 ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2)), \
-                    gg, n_g, items_g, xy_g, t_g, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_G, wins_g, c->d_gTheta, \
-                    direct11 ? 1 : 0, host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, direct11 ? THETA_CONST : THETA_TILE, order_g, \
+                    gg, n_g, items_g, xy_g, t_g, c->d_Theta, c->d_edge_ts, c->d_G, wins_g, c->d_gTheta, \
+                    host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, order_g, \
                     c->pend.use_arg ? 1 : 0, c->pend.theta_dev, c->pend.targ, \
-                    1, nparts, \
                     h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth, (int)c->coarse_cap, \
                     (host_asm && proj) ? 1 : 0, c->d_gticket, c->d_win_item0, c->h_grad, \
-                    (host_asm && proj && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap, all_r
+                    (host_asm && proj && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap
 #define GATHER_TILE(WIDE_, PROJ_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, PROJ_>, GATHER_ARGS(NT_TILE))
 #define GATHER_ALLR(WIDE_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, 1, 1>, GATHER_ARGS(NT_TILE))
                 if (direct11) {
                     launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_CONST, 0, NT, 0>, GATHER_ARGS(NT));
-                    c->g11_per_item = g.R * nparts;
                 } else if (all_r) {
                     if (wide) GATHER_ALLR(1); else GATHER_ALLR(0);
                 } else if (wide) {
@@ -1173,7 +1151,7 @@ int eval_end_launch(eincm_ctx* c) {
         // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
         launch_timed(c, EINCM_STAGE_FINAL, k_final, dim3(g.B), dim3(FT), 0, g, ep, c->d_parts, c->d_divparts, c->d_tvparts,
                            c->d_tmm, c->d_wc, g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
-                           c->d_g11, c->d_win_item0_2, c->n_items_2, c->g11_per_item, c->d_gmax,
+                           c->d_g11, c->d_win_item0_2, c->n_items_2, c->d_gmax,
                            zero_copy_out ? c->h_outs : c->d_outs, zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
         if (want_grad && identity) {
             hipLaunchKernelGGL(k_final_dense, dim3(256, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, wide ? 1 : 0, c->d_gTheta,
@@ -1238,8 +1216,8 @@ void host_assemble(eincm_ctx* c) {
         o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
         if (c->pend.h == 1 && c->pend.w == 1) {              // 2-DoF: the gather's per-workgroup partials, added in index order
             const int lo = c->h_win_item0_2[b], hi = c->h_win_item0_2[b + 1];
-            const double* p = c->h_g11 + (size_t)lo * c->g11_per_item * 2;
-            const size_t n = (size_t)(hi - lo) * c->g11_per_item;
+            const double* p = c->h_g11 + (size_t)lo * g.R * 2;
+            const size_t n = (size_t)(hi - lo) * g.R;
             // four interleaved chains per component (a fixed association, so still a function of the partials alone): one chain is
             // bound by the latency of the add, 4000 partials of the 8-window batch took 6 us
             double ax[4] = {0.0, 0.0, 0.0, 0.0}, ay[4] = {0.0, 0.0, 0.0, 0.0};
@@ -1442,11 +1420,9 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     c->fp64 = (flags & EINCM_CF_FP64) != 0;
     c->device = device; c->H = H; c->W = W; c->maxR = max_refs; c->maxB = max_windows; c->maxN = max_events_total;
     c->cflags = flags;
-    if (const char* s = getenv("EINCM_CHUNK")) { int v = atoi(s); if (v >= NT && v <= MAX_CHUNK) { c->chunk = (v / NT) * NT; c->chunk_fixed = true; } }
     if (const char* s = getenv("EINCM_SEG")) { int v = atoi(s); if (v >= 64 && v <= MAX_SEG) c->seg = v; }
-    if (const char* s = getenv("EINCM_SEG_SPLAT")) { int v = atoi(s); if (v >= 64 && v <= MAX_SEG) c->seg_s = v; }
+    if (const char* s = getenv("EINCM_SEG_SPLAT")) { int v = atoi(s); if (v >= 64 && v <= MAX_CHUNK) c->seg_s = v; }   // k_splat's u32 sums bound a segment
     if (const char* s = getenv("EINCM_WINCAP")) { int v = atoi(s); if (v >= 1024 && v <= 6912) { c->wincap = (v / 4) * 4; c->wincap_fixed = true; } }
-    if (c->seg_s > c->chunk && c->wincap > 4608) c->wincap = 4608;       // two LDS windows in k_splat's long-segment form
     auto bail = [&](const char* what, hipError_t err) -> eincm_ctx* {
         fail(nullptr, EINCM_ERR_HIP, "eincm_create: %s failed: %s", what, hipGetErrorString(err));
         free_all(c);
@@ -1498,7 +1474,7 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     TRY(hipMemset(c->d_acc, 0, B * R * img * sizeof(unsigned long long)));
     TRY(dalloc(&c->d_iwe, B * R * img));
     TRY(dalloc(&c->d_G, B * R * img));
-    TRY(dalloc(&c->d_g11, (size_t)(c->max_items + NXCD) * R * 2 * 4));      // x4: up to four workgroups share a segment
+    TRY(dalloc(&c->d_g11, (size_t)(c->max_items + NXCD) * R * 2));
     TRY(dalloc(&c->d_win_item0, B + 1));
     TRY(dalloc(&c->d_dtmax, B));
     TRY(dalloc(&c->d_cntmax, B));
@@ -1538,7 +1514,7 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     TRY(dalloc(&c->d_tilerng, (size_t)ntiles));
     TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_theta), B * img * 2 * sizeof(double), hipHostMallocDefault));
     TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_wc), B * sizeof(WinConst), hipHostMallocDefault));
-    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_g11), (size_t)(c->max_items + NXCD) * R * 2 * 4 * sizeof(double), hipHostMallocDefault));
+    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_g11), (size_t)(c->max_items + NXCD) * R * 2 * sizeof(double), hipHostMallocDefault));
     TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_g2), B * R * nig * sizeof(double), hipHostMallocDefault));
     TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_img), B * R * IMGSCAL_N * sizeof(double), hipHostMallocDefault));
     TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_tvparts), B * ntiles * 3 * sizeof(double), hipHostMallocDefault));
@@ -1656,9 +1632,8 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     //             with 4096, 30.3 with 8192, 28.6 with 16384; the 8-window batch 157 / 144 / 139 with 8192 / 16384 / 32768).
     const double x_wg = ((double)N / 8192.0 + 0.5 * n_windows * g.ntiles) * n_refs;
     // Round 3: the gather's list always has long segments (what its theta-grid form wants: thtile, accumulator clear and flush per
-    // workgroup); its 2-DoF form shares a segment among up to four workgroups instead (gather_wg_events, k_gather's nparts).
+    // workgroup); its 2-DoF form walks a list of its own (seg_2).
     int seg = c->seg > 0 ? c->seg : 16384;
-    c->gather_wg_events = 1e30;              // (k_gather's nparts: an experiment, EINCM_GATHER_PARTS)
     int seg_2 = (x_wg >= 4000.0 && (double)N / ((double)n_windows * g.ntiles) < 16384.0) ? 16384 : (x_wg < 1000.0 ? 4096 : 8192);   // (tiles of several segments: as seg_s below; 480x640 with 10^7 events 90 -> 82 us)       // the 2-DoF gather's own list (round-2 tuning)
     if (const char* e = getenv("EINCM_SEG_2DOF")) { const int v = atoi(e); if (v >= 64 && v <= MAX_SEG) seg_2 = v; }
     c->seg_2_used = seg_2;
@@ -1676,7 +1651,6 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     if (const char* e = getenv("EINCM_PITCH_ALIGNED")) g.pitch_aligned = std::max(0, std::min(2, atoi(e)));      // 0: never, 1: k_splat where it costs no capacity class, 2: the 2-DoF gather too
     c->seg_s_used = seg_s;
     const bool sort_segments = getenv("EINCM_NO_SEGSORT") == nullptr;
-    if (!c->chunk_fixed) c->chunk = std::max(4096, std::min(seg_s, MAX_CHUNK));     // single-chunk segments: no f32 commit pass
     const size_t img = (size_t)H * W;
     for (int b = 0; b < n_windows; ++b) {
         memset(&c->h_wc[b], 0, sizeof(WinConst));

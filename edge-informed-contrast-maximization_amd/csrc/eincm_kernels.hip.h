@@ -30,17 +30,17 @@ namespace eincm {
 constexpr int TS = 32;            // source tile edge (pixels)
 constexpr int NT = 256;           // threads per workgroup = 4 waves of 64
 constexpr int NWAVE = NT / 64;
-constexpr int WIN_CAP_DEFAULT = 2304;   // pixels of LDS for a segment's destination window: u32 chunk + f32 sum = 18 KiB -> 8 workgroups/CU
+constexpr int WIN_CAP_DEFAULT = 2304;   // pixels of LDS for a segment's destination window
 constexpr int WIN_CAP_MAX = 9216;
 constexpr int NXCD = 8;           // XCDs: blocks b and b+8 share an L2 (round-robin dispatch; speed only, never correctness)
 constexpr double EPSN = 2.220446049250313e-16;   // sys.float_info.epsilon (losses.py:24)
 constexpr float INV_2PI = 0.15915494309189535f;
 // LDS accumulation of the splat is u32 fixed point: on gfx950 ds_add_f32 retires ~1 lane per 3 clocks whatever the
 // address pattern (0.33 lane-ops/clk/CU measured, tools/lds_atomic_bench.hip) while ds_add_u32 sustains 5-7.4.
-// One tap is <= 1/(2*pi) = 0.1592 and a chunk holds <= MAX_CHUNK events, so with the scale 2^k of fix_shift (the largest power of two
+// One tap is <= 1/(2*pi) = 0.1592 and a splat segment holds <= MAX_CHUNK events, so with the scale 2^k of fix_shift (the largest power of two
 // with count * 0.16 * 2^k <= 2^32: k = 21 at 8192 events, 22 at 4096) the integer sum of a window pixel cannot overflow.
 // Resolution 2^-k (round to nearest, unbiased): 4.8e-7 absolute per tap at 8192 events.
-constexpr int MAX_CHUNK = 16384;   // events per inner chunk (bounds the u32 sums; the fixed-point scale follows the count, fix_shift)
+constexpr int MAX_CHUNK = 16384;   // events per splat segment (bounds the u32 sums; the fixed-point scale follows the count, fix_shift)
 constexpr int MAX_SEG = 1 << 20;   // events per segment (one window flush per segment and reference time)
 // Per-item scale 2^k, the largest power of two with count * 0.16 * 2^k <= 2^32 (k capped at 30, where the smallest
 // tap 0.0137 still keeps its full fp32 mantissa): k = 23 for 2048 events, 22 for 4096, 30 for <= 25 events — sparse
@@ -649,27 +649,25 @@ template <int NTH> struct SegWalk {
 };
 
 // ------------------------------------------------------------------------------------------------
-// k_splat: the dominant kernel.  grid ceil(n_items/8)*8*R blocks (block_to_work), LDS 2*WIN_CAP*4 bytes.
-// A segment is walked in chunks of <= chunk events; each chunk is accumulated in u32 fixed point (exact integer
-// ds_add_u32) and committed into the segment's f32 window; the window is flushed to HBM once per segment.
+// k_splat: the dominant kernel.  grid ceil(n_items/8)*8*R blocks (block_to_work), LDS wincap*4 bytes (+ the Theta tile).
+// A segment (<= MAX_CHUNK events) is accumulated in its u32 fixed-point window in LDS (exact integer ds_add_u32, scale
+// fix_shift(count)); the window is flushed to HBM once per segment.
 // ------------------------------------------------------------------------------------------------
-template <int TM, int MULTI, int NTH>   // TM: the theta mode as a compile-time constant (0 = run-time argument); MULTI = 0: no segment is longer than a chunk
-__global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, int theta_mode, int lds_multi,
+template <int TM, int NTH>   // TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE)
+__global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
         const Item* __restrict__ items,
         const uint32_t* __restrict__ ev_xy,    // x | y << 16, binned by (window, tile)
         const double* __restrict__ ev_t,
         const double* __restrict__ Theta,      // (B,H,W,2)
-        const double* __restrict__ tmm,        // (B,ntiles,4)
         const double* __restrict__ edge_ts,    // (B,R)
         const Window* __restrict__ wins,       // (n_items, R) destination windows of this evaluation (k_theta / k_windows); unused for 2-DoF theta
         unsigned long long* __restrict__ acc,  // (B,R,H,W) u64 fixed point at 2^ACC_SHIFT, zero on entry (cleared by its consumer)
         const int32_t* __restrict__ order,     // (n_items) segments by decreasing length (block_to_work)
         int use_arg, const double* __restrict__ theta_c, ThetaArg targ)   // 2-DoF theta (B,2): in the kernel arguments, or behind theta_c
 {
-    if (TM != 0) theta_mode = TM;                 // every branch on it below folds away: 8 % on both event kernels
+    constexpr int theta_mode = TM;                // every branch on it below folds away: 8 % on both event kernels
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsu[];
-    float* ldsf = reinterpret_cast<float*>(ldsu + g.wincap);                       // present only when lds_multi
-    double2* thtile = reinterpret_cast<double2*>(ldsu + (lds_multi ? 2 : 1) * g.wincap);   // present only for THETA_TILE
+    double2* thtile = reinterpret_cast<double2*>(ldsu + g.wincap);                 // present only for THETA_TILE
     int item, r;
     if (!block_to_work(n_items, g.R, order, item, r)) return;
     const Item it = items[item];
@@ -694,12 +692,10 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
     }
     const int nwin = wn.ww * wn.wh;
     const int wp = win_pitch(g, wn.ww), wp4 = wp * 4, nlds = wp * wn.wh;     // LDS row pitch and words (win_pitch)
-    const bool multi = MULTI != 0 && it.count > chunk;       // MULTI == 0: the commit logic in the loop folds away
-    {   // clear the window(s), 16 B per lane
+    {   // clear the window, 16 B per lane
         uint4* z = reinterpret_cast<uint4*>(ldsu);
         const int nq = (nlds + 3) >> 2;
         for (int i = threadIdx.x; i < nq; i += NTH) z[i] = make_uint4(0u, 0u, 0u, 0u);
-        if (multi) { uint4* zf = reinterpret_cast<uint4*>(ldsf); for (int i = threadIdx.x; i < nq; i += NTH) zf[i] = make_uint4(0u, 0u, 0u, 0u); }
     }
     __syncthreads();
 
@@ -708,8 +704,7 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
     const double* __restrict__ et = ev_t + it.begin;
     const int n = it.count;
     const int iters = (n + NTH - 1) / NTH;            // uniform over the workgroup
-    const int ipc = chunk / NTH;                     // iterations per chunk (chunk is a multiple of NTH)
-    const int fshift = fix_shift(min(chunk, n));
+    const int fshift = fix_shift(n);
     const float FIX_SCALE = ldexpf(1.0f, fshift), FIX_INV = ldexpf(1.0f, -fshift);
 
     // Software pipeline over the segment's events, unrolled x3 with renamed register sets (no rotation moves, so no forced
@@ -722,7 +717,7 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
 #else
     auto load_ev = [&](EvReg& r, int e) { if (e < n) { r.xy = exy[e]; r.t = et[e]; } else { r.xy = 0u; r.t = 0.0; } };
 #endif
-    const float scy = INV_2PI * FIX_SCALE;          // one fixed-point scale per segment: every chunk holds <= min(chunk, n) events
+    const float scy = INV_2PI * FIX_SCALE;          // one fixed-point scale per segment
     auto splat_ev = [&](const EvReg& ev) {
         const double dt = ev.t - tau;
         const int x = ev.xy & 0xffff, y = ev.xy >> 16;
@@ -776,14 +771,6 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
         const int e = j * NTH + tid;
         load_ev(nxt, e + 2 * NTH);
         if (e < n) splat_ev(cur);
-        if (multi && ((j + 1) % ipc == 0 || j + 1 == iters)) {     // chunk boundary (uniform): commit u32 -> f32 window
-            __syncthreads();
-            for (int i = tid; i < nlds; i += NTH) {
-                const uint32_t u = ldsu[i];
-                if (u != 0u) { ldsf[i] += (float)u * FIX_INV; ldsu[i] = 0u; }
-            }
-            __syncthreads();
-        }
     };
     EvReg A, B, C;
     load_ev(A, tid);
@@ -796,7 +783,7 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
         if (j + 2 < iters) step(C, A, B, j + 2);
     }
 #endif
-    if (!multi) __syncthreads();
+    __syncthreads();
 #ifdef EINCM_ABL_S_NOFLUSH
     return;
 #endif
@@ -805,10 +792,7 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items, int chunk, i
     // does not depend on the order in which the workgroups arrive.
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int up = ACC_SHIFT - fshift;               // >= 0 (fix_shift caps at 30)
-    auto to_acc = [&](int i) -> unsigned long long {
-        if (multi) return (unsigned long long)fix64((double)ldsf[i] * 1073741824.0);     // f32 segment sums of the multi-chunk form
-        return (unsigned long long)ldsu[i] << up;
-    };
+    auto to_acc = [&](int i) -> unsigned long long { return (unsigned long long)ldsu[i] << up; };
     if (wn.ox >= 0 && wn.oy >= 0 && wn.ox + wn.ww <= g.W && wn.oy + wn.wh <= g.H) {
         // the usual case, the window lies inside the image: no index rule per pixel
         unsigned long long* __restrict__ dst = img + (size_t)wn.oy * g.W + wn.ox;
@@ -1451,19 +1435,17 @@ __device__ __forceinline__ void project_tile_to_cells(const Geom& g, int h, int 
         if (ay != 0.0) atomicAdd(o + 1, (unsigned long long)fix64_wide(ay));
     }
 }
-template <int TM, int WIDE, int NTH, int PROJ, int ALLR = 0>      // NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE); 0 = take the run-time argument
+template <int TM, int WIDE, int NTH, int PROJ, int ALLR = 0>      // NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE)
 __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_items,      // WIDE: 61-bit fixed point per event (tiny windows, see grad_shift_pixel)
         const Item* __restrict__ items, const uint32_t* __restrict__ ev_xy, const double* __restrict__ ev_t,
-        const double* __restrict__ Theta, const double* __restrict__ tmm, const double* __restrict__ edge_ts,
+        const double* __restrict__ Theta, const double* __restrict__ edge_ts,
         const float* __restrict__ G,           // (B,R,H,W) dL/dIWE written by k_imgrad
         const Window* __restrict__ wins,       // (n_items, R) windows of this evaluation
         long long* __restrict__ gTheta,        // (B,H,W,2) i64 fixed point, zero on entry (cleared by its consumer)
-        int direct11, double* __restrict__ g11,                     // 2-DoF theta: (n_items, R, 2) per-workgroup partials of dL/dtheta
+        double* __restrict__ g11,              // 2-DoF theta: (n_items, R, 2) per-workgroup partials of dL/dtheta
         const WinConst* __restrict__ wc, const unsigned* __restrict__ gmax,   // scale of the i64 accumulators (grad_shift)
-        int theta_mode, const int32_t* __restrict__ order,
+        const int32_t* __restrict__ order,
         int use_arg, const double* __restrict__ theta_c, ThetaArg targ,   // 2-DoF theta (B,2): in the kernel arguments, or behind theta_c
-        int list_a,                            // the segments walked are the gather's own list (window capacity wincap_a), not the splat's
-        int nparts,                            // 1, 2 or 4 = gridDim.y: workgroups sharing a segment (256-thread form only)
         // PROJ = 1 (theta grids whose tiles touch <= PG_MAXC x PG_MAXC cells): the workgroup projects its tile's sums onto the theta
         // cells itself, dL/dtheta[i,j] += sum_{y,x} AH[y,i] AW[x,j] dL/dTheta[y,x] (reverse of theta_utils.py:25-35), instead of
         // flushing them into the dL/dTheta image for k_project: 2 x 32 x 32 global atomics per workgroup become <= 2 ni nj
@@ -1472,14 +1454,14 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         // tail (PROJ only, tail != 0): the workgroup of a window that finishes LAST turns the window's i64 cell sums into dL/dtheta and
         // writes it where the host reads it - what k_final did in a launch of its own (7-8 us of a 65 us evaluation)
         int tail, unsigned* __restrict__ ticket, const int32_t* __restrict__ win_item0, double* __restrict__ grad_out,
-        double tv_gamma, const double* __restrict__ tvparts, long long* __restrict__ gth_tv,   // tail with the TV term (gamma != 0 at level 0)
-        int all_r_unused)   // (ALLR = 1, theta grids on big batches: ONE workgroup per segment walks all R reference times - grid = segments,
-                     // not segments x R -, so that the Theta tile, the accumulator clear, the projection and the ticket are paid once per segment)
+        double tv_gamma, const double* __restrict__ tvparts, long long* __restrict__ gth_tv)   // tail with the TV term (gamma != 0 at level 0)
 {
-    const int part = blockIdx.y;
-    if (TM != 0) theta_mode = TM;                 // every branch on it below folds away: 8 % on both event kernels
-    if (TM != 0) direct11 = (TM == THETA_CONST) ? 1 : 0;     // the host ties the two (2-DoF theta <=> per-workgroup partials)
-    const int wincap = list_a ? g.wincap_a : g.wincap, winmaxw = list_a ? g.winmaxw_a : g.winmaxw;
+    // (ALLR = 1, theta grids on big batches: ONE workgroup per segment walks all R reference times - grid = segments, not
+    // segments x R -, so that the Theta tile, the accumulator clear, the projection and the ticket are paid once per segment)
+    constexpr int theta_mode = TM;                // every branch on it below folds away: 8 % on both event kernels
+    constexpr bool direct11 = TM == THETA_CONST;  // 2-DoF theta <=> per-workgroup partials
+    // the segments walked are the gather's own lists (window capacity wincap_a), not the splat's
+    const int wincap = g.wincap_a, winmaxw = g.winmaxw_a;
     // LDS: [G window: wincap floats][accum: TS*TS*2 doubles unless direct11][Theta tile: TS*TS double2 if THETA_TILE]
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double red11[NTH / 64];
@@ -1586,29 +1568,24 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     };
     // the staged layout (SegWalk): a half of the segment is K coalesced steps of 256 threads, the last one a prefix
     const SegWalk<NTH> walk(n, tid);
-    auto walk_half = [&](int c, int sub, int nsub) {      // steps [K sub / nsub, K (sub + 1) / nsub) of half c
+    auto walk_half = [&](int c) {                 // steps [0, K) of half c
         const int K = c ? walk.K1 : walk.K0, rem = c ? walk.rem1 : walk.rem0;
-        const int j0 = K * sub / nsub, j1 = K * (sub + 1) / nsub;
         const uint32_t* __restrict__ px = exy + (c ? walk.n0 : 0) + walk.tt;
         const double* __restrict__ pt = et + (c ? walk.n0 : 0) + walk.tt;
-        const int jfull = min(j1, K - 1);
 #pragma unroll 2
-        for (int j = j0; j < jfull; ++j) {
+        for (int j = 0; j < K - 1; ++j) {
             EvReg ev; ev.xy = px[j * 256]; ev.t = pt[j * 256];
             gather_ev(ev);
         }
-        if (j1 == K && K > 0 && j0 < K && walk.tt < rem) {
+        if (K > 0 && walk.tt < rem) {
             EvReg ev; ev.xy = px[(K - 1) * 256]; ev.t = pt[(K - 1) * 256];
             gather_ev(ev);
         }
     };
     for (int rr = r; ; ) {                        // one reference time, or all of them (all_r)
 #ifndef EINCM_ABL_G_NOEVENTS
-    // nparts > 1 (2-DoF theta, few windows): a segment is shared by nparts workgroups (blockIdx.y), so that the segments can be long
-    // (what the theta-grid gather wants from the one list both walk) and the chip still sees enough workgroups
-    if (NTH == 512) walk_half(walk.half, 0, 1);
-    else if (nparts == 1) { walk_half(0, 0, 1); walk_half(1, 0, 1); }
-    else { const int nsub = nparts >> 1; walk_half(part / nsub, part % nsub, nsub); }
+    if (NTH == 512) walk_half(walk.half);
+    else { walk_half(0); walk_half(1); }
     if (!direct11) { flush_run(); cur_key = 0xffffffffu; run_x = 0.0; run_y = 0.0; }
 #endif
     if (!all_r || ++rr >= g.R) break;
@@ -1625,7 +1602,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         double sum11x = block_sum<NTH / 64>((double)f11x, red11);
         double sum11y = block_sum<NTH / 64>((double)f11y, red11);
         if (threadIdx.x == 0) {          // own slot, plain store, written unconditionally: nothing to clear, nothing to order
-            double* dst = g11 + (((size_t)item * nparts + part) * g.R + r) * 2;
+            double* dst = g11 + ((size_t)item * g.R + r) * 2;
             dst[0] = sum11x; dst[1] = sum11y;
         }
         return;
@@ -2118,7 +2095,7 @@ __global__ __launch_bounds__(FT) void k_final(Geom g, EvalParams ep,
         const double* __restrict__ tmm, const WinConst* __restrict__ wc,
         const double* __restrict__ g2parts,    // contrast energy partials from k_imgrad, or nullptr (then parts[].sG2 holds it)
         long long* __restrict__ gth_main, long long* __restrict__ gth_tv, int gth_cap,     // i64 cells (consumed and cleared here)
-        const double* __restrict__ g11, const int32_t* __restrict__ win_item0, int n_items, int g11_per_item,  // 2-DoF: per-workgroup partials of the gather kernel
+        const double* __restrict__ g11, const int32_t* __restrict__ win_item0, int n_items,  // 2-DoF: per-workgroup partials of the gather kernel
         const unsigned* __restrict__ gmax,
         OutScal* __restrict__ outs, double* __restrict__ grad_out, int want_grad)
 {
@@ -2144,8 +2121,8 @@ __global__ __launch_bounds__(FT) void k_final(Geom g, EvalParams ep,
         // fixed tree of block_sum): bit-reproducible without any atomic.  Four loads in flight per trip.
         const int lo = win_item0[b], hi = (b + 1 < g.B) ? win_item0[b + 1] : n_items;
         const double2* __restrict__ q = reinterpret_cast<const double2*>(g11);
-        const int kend = hi * g11_per_item;
-        int k = lo * g11_per_item + threadIdx.x;
+        const int kend = hi * g.R;
+        int k = lo * g.R + threadIdx.x;
         for (; k + 3 * FT < kend; k += 4 * FT) {
             const double2 a0 = q[k], a1 = q[k + FT], a2 = q[k + 2 * FT], a3 = q[k + 3 * FT];
             sx11 += (a0.x + a1.x) + (a2.x + a3.x); sy11 += (a0.y + a1.y) + (a2.y + a3.y);

@@ -44,9 +44,11 @@ def test_many_windows_one_segment_per_tile(built_lib):
         assert pol['cap_splat'] == 4608 and pol['pitch_aligned'] == 1
 
 
-def test_tiles_of_several_segments(built_lib):
+def test_tiles_of_several_segments(built_lib, monkeypatch):
     """5 * 10^6 events on 9 tiles: a long segment would double every workgroup, so 8192-event lists and pitch = width; a segment spans
-    1 / 68 of the window, so a 20 px theta needs the smallest windows only."""
+    1 / 68 of the window, so a 20 px theta needs the smallest windows only.  An EINCM_SEG_SPLAT above the 16384 events whose u32 sums
+    k_splat can hold is ignored: the default stands."""
+    monkeypatch.setenv('EINCM_SEG_SPLAT', '32768')                              # read by eincm_create
     rng = np.random.default_rng(2)
     H, W, N, R = 96, 96, 5_000_000, 5
     with engine.Engine((H, W), N, max_refs=R) as e:

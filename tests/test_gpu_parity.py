@@ -586,12 +586,11 @@ def test_half_pixel_ties_and_near_ties():
                 assert np.array_equal(cnt[r], O.rounded_count_image(wx, wy, (H, W))), theta
 
 
-def test_long_splat_segments_use_two_lds_windows(monkeypatch):
-    """EINCM_SEG_SPLAT > EINCM_CHUNK selects k_splat's multi-chunk form (u32 chunk window + f32 segment window in LDS).  With a
-    large-flow 16x16 theta the per-evaluation window capacity is raised; it must stay within the 64 KiB of dynamic LDS a launch
-    gets (2 x 6912 x 4 B + the 16 KiB Theta tile did not)."""
+def test_long_splat_segments_under_a_large_flow(monkeypatch):
+    """8192-event splat segments (EINCM_SEG_SPLAT; 4096 by default for this window) under a 90-px 16x16 flow: the per-evaluation
+    window capacity follows the flow up to the largest class, uncapped, and the splat's LDS (that window + the 16 KiB Theta tile)
+    stays within the 64 KiB of dynamic LDS a launch gets."""
     monkeypatch.setenv('EINCM_SEG_SPLAT', '8192')
-    monkeypatch.setenv('EINCM_CHUNK', '4096')
     H, W, N, R = 130, 170, 150000, 3
     win = synth.make_window(17, (H, W), N, R, flow='smooth', flow_mag=90.0)
     th = synth.theta_near_truth(17, win, (16, 16))

@@ -22,7 +22,6 @@ SWITCHES = [
     ({'EINCM_NO_PROJ_IN_GATHER': '1'}, 'dL/dTheta image + k_project instead of the in-gather projection'),
     ({'EINCM_NO_SEGSORT': '1', 'EINCM_NO_SPREAD': '1'}, 'both event copies in plain time order'),
     ({'EINCM_SEG': '4096', 'EINCM_SEG_SPLAT': '2048', 'EINCM_SEG_2DOF': '8192'}, 'other segment lengths'),
-    ({'EINCM_GATHER_PARTS': '2'}, '2-DoF gather segments shared by two workgroups'),
     ({'EINCM_HOST_BINNING': '1'}, 'host-side counting sort'),
     ({'EINCM_GATHER_ALL_R': '1'}, 'theta-grid gather: one workgroup per segment walks all reference times'),
     ({'EINCM_PITCH_ALIGNED': '2'}, 'LDS windows of both 2-DoF event kernels at the bank-aligned row pitch (k_splat: the policy of a large batch, forced on a small one)'),

@@ -54,9 +54,9 @@ def blocks(body):
 
 def main():
     text = open(sys.argv[1]).read()
-    want = [('k_splat<THETA_CONST, 0>  (2-DoF theta, the bench configuration)', 'k_splatILi1ELi0E', 'ds_add_u32', 3),
+    want = [('k_splat<THETA_CONST>  (2-DoF theta, the bench configuration)', 'k_splatILi1E', 'ds_add_u32', 3),
             ('k_gather<THETA_CONST, 0>  (2-DoF theta)', 'k_gatherILi1ELi0E', 'ds_read_b32', 1),
-            ('k_splat<THETA_TILE, 0>  (pyramid levels >= 1, dense)', 'k_splatILi2ELi0E', 'ds_add_u32', 3),
+            ('k_splat<THETA_TILE>  (pyramid levels >= 1, dense)', 'k_splatILi2E', 'ds_add_u32', 3),
             ('k_gather<THETA_TILE, 0>', 'k_gatherILi2ELi0E', 'ds_read_b32', 1)]
     print('# Instruction mix of the event kernels\' inner loops (gfx950 ISA, hipcc -O3, `tools/isa_mix.py`)\n')
     print('Counted from the disassembly: the basic blocks of the event loop that run in the common case (every tap of the event inside the LDS\n'
