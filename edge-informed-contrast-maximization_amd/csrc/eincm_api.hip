@@ -524,7 +524,9 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
         memcpy(targ.v, theta_host, (size_t)g.B * nth * sizeof(double));     // theta rides in the kernel arguments
         if (!use_arg_big) { memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double)); theta_dev = c->h_theta; }   // (k_theta reads memory then)
     } else if (use_arg_big) {
-        theta_dev = c->h_theta;                      // (not read: k_theta has theta in its arguments)
+        // k_theta has theta in its arguments; a 2-DoF theta is also read by k_theta_const, k_splat and the gather (B * 2 doubles)
+        if (const_theta) memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double));
+        theta_dev = c->h_theta;
     } else if ((size_t)g.B * nth <= ZERO_COPY_MAX) {
         // medium theta (e.g. 16x16): k_theta reads it straight from the pinned, GPU-mapped staging buffer (no copy command)
         memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double));
@@ -978,6 +980,15 @@ int enqueue_result_copies(eincm_ctx* c) {
         // a dense gradient (4.9 MB at 480x640): in pieces, an event behind each, so that eval_end_collect hands piece k over
         // (copy + finite scan on the host) while piece k + 1 is still crossing PCIe
         HIPCHK(c, hipMemcpyAsync(c->h_outs, c->d_outs, (size_t)g.B * sizeof(OutScal), hipMemcpyDeviceToHost, c->stream));
+        // the rows of windows that sat this evaluation out were not written: clear them, so that they come back as 0 and pass the
+        // host's finite scan (eval_end_collect zeroes them on the host only when the gradient comes in one piece)
+        for (int b = 0; b < g.B && b < 64; ) {
+            if ((g.wmask >> b) & 1ull) { ++b; continue; }
+            int e = b + 1;
+            while (e < g.B && e < 64 && !((g.wmask >> e) & 1ull)) ++e;
+            HIPCHK(c, hipMemsetAsync(c->d_grad + (size_t)b * nth, 0, (size_t)(e - b) * nth * sizeof(double), c->stream));
+            b = e;
+        }
         const size_t total = (size_t)g.B * nth;
         c->piece_len = (total + eincm_ctx::GRAD_PIECES - 1) / eincm_ctx::GRAD_PIECES;
         for (int k = 0; k < eincm_ctx::GRAD_PIECES; ++k) {
