@@ -663,11 +663,22 @@ int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalP
                            c->f64.gmax, c->f64.gacc, c->f64.bad, c->f64.gTh);
         const double* out = c->f64.gTh;
         if (!identity) {
-            const size_t nT = (size_t)g.B * g.H * w * 2, nO = (size_t)g.B * nth;
-            hipLaunchKernelGGL(k64_proj_w, dim3((unsigned)std::min<size_t>((nT + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, w, c->d_AW,
-                               c->f64.gTh, c->f64.T);
-            hipLaunchKernelGGL(k64_proj_h, dim3((unsigned)std::min<size_t>((nO + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h, w, c->d_AH,
-                               c->f64.T, c->f64.grad);
+            // the intermediate goes through T, of capacity (B,H,W,2): columns first, (B,H,w,2), unless theta is wider than the sensor;
+            // then h < H (h * w <= H * W) and the rows go first, (B,h,W,2)
+            const size_t nO = (size_t)g.B * nth;
+            if (w <= g.W) {
+                const size_t nT = (size_t)g.B * g.H * w * 2;
+                hipLaunchKernelGGL(k64_proj_w, dim3((unsigned)std::min<size_t>((nT + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, w, c->d_AW,
+                                   c->f64.gTh, c->f64.T);
+                hipLaunchKernelGGL(k64_proj_h, dim3((unsigned)std::min<size_t>((nO + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h, w,
+                                   c->d_AH, c->f64.T, c->f64.grad);
+            } else {
+                const size_t nT = (size_t)g.B * h * g.W * 2;
+                hipLaunchKernelGGL(k64_proj_h_first, dim3((unsigned)std::min<size_t>((nT + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h,
+                                   c->d_AH, c->f64.gTh, c->f64.T);
+                hipLaunchKernelGGL(k64_proj_w_second, dim3((unsigned)std::min<size_t>((nO + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h,
+                                   w, c->d_AW, c->f64.T, c->f64.grad);
+            }
             out = c->f64.grad;
         }
         HIPCHK(c, hipMemcpyAsync(c->h_grad, out, (size_t)g.B * nth * sizeof(double), hipMemcpyDeviceToHost, c->stream));

@@ -13,6 +13,7 @@
 //   k64_gfin     accumulator -> fp64 dL/dTheta (+ gamma * TV gradient of k_tv) (consumer clears); NaN where a window was flagged
 //                non-finite (k64_grad2, k64_gather), so the fp32 path's NONFINITE contract holds
 //   k64_proj_w / k64_proj_h   separable adjoint resample dL/dTheta -> dL/dtheta, sequential sums     [reverse of theta_utils.py:25-35]
+//                (k64_proj_h_first / k64_proj_w_second: the rows first, for theta grids wider than the sensor)
 // The staging (event copies, segment lists), k_theta's Theta image and k_tv are shared with the fp32 path.  Every cross-workgroup
 // sum is integer (u64 IWE, i128 gradient) or a per-workgroup partial reduced in index order, so results are bit-reproducible.
 // A first pass: both event kernels sum in LDS and flush once per segment, the image passes are plain pixel-parallel kernels;
@@ -575,6 +576,43 @@ __global__ __launch_bounds__(NT) void k64_proj_h(Geom g, int h, int w, const dou
         const double* __restrict__ col = T + ((size_t)b * g.H * w + j) * 2 + c;
         double s = 0.0;
         for (int y = 0; y < g.H; ++y) s += AH[(size_t)y * h + i] * col[(size_t)y * w * 2];
+        out[k] = s;
+    }
+}
+
+// The same adjoint rows first, for a grid finer than the sensor in x (w > W, so h < H since h * w <= H * W): the intermediate
+// (B,h,W,2) fits T's (B,H,W,2) capacity where k64_proj_w's (B,H,w,2) would overrun it.
+__global__ __launch_bounds__(NT) void k64_proj_h_first(Geom g, int h, const double* __restrict__ AH, const double* __restrict__ gTh,
+                                                        double* __restrict__ T)
+{
+    const size_t n = (size_t)g.B * h * g.W * 2;
+    for (size_t k = (size_t)blockIdx.x * NT + threadIdx.x; k < n; k += (size_t)gridDim.x * NT) {
+        const int c = (int)(k & 1);
+        const size_t q = k >> 1;
+        const int x = (int)(q % g.W);
+        const size_t bi = q / g.W;                      // b * h + i
+        const int i = (int)(bi % h), b = (int)(bi / h);
+        if (!win_active(g, b)) continue;
+        const double* __restrict__ col = gTh + ((size_t)b * g.H * g.W + x) * 2 + c;
+        double s = 0.0;
+        for (int y = 0; y < g.H; ++y) s += AH[(size_t)y * h + i] * col[(size_t)y * g.W * 2];
+        T[k] = s;
+    }
+}
+__global__ __launch_bounds__(NT) void k64_proj_w_second(Geom g, int h, int w, const double* __restrict__ AW, const double* __restrict__ T,
+                                                         double* __restrict__ out)
+{
+    const size_t n = (size_t)g.B * h * w * 2;
+    for (size_t k = (size_t)blockIdx.x * NT + threadIdx.x; k < n; k += (size_t)gridDim.x * NT) {
+        const int c = (int)(k & 1);
+        const size_t q = k >> 1;
+        const int j = (int)(q % w);
+        const size_t bi = q / w;                        // b * h + i
+        const int b = (int)(bi / h);
+        if (!win_active(g, b)) continue;
+        const double* __restrict__ row = T + bi * g.W * 2 + c;
+        double s = 0.0;
+        for (int x = 0; x < g.W; ++x) s += AW[(size_t)x * w + j] * row[(size_t)x * 2];
         out[k] = s;
     }
 }

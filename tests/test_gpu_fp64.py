@@ -9,6 +9,7 @@ import pytest
 
 from oracle import eincm_c_port as CP
 from oracle import eincm_oracle as O
+import _ties as TIES
 
 pytestmark = pytest.mark.gpu
 
@@ -295,3 +296,127 @@ def test_lockstep_fp64_matches_sequential_fp64_solves(built_lib):
             d = np.abs(out_b[b]['final_theta_pyr'][key] - out_s['final_theta_pyr'][key]).max()
             assert d <= 1e-6, (b, key, d)
     losses.clear_engine_cache()
+
+
+# ---- limits the hand-picked cases above do not reach ----------------------------------------------------------------------------
+def _check_against_oracle(win, theta, method='bilinear', gamma=0.0, delta=0.0, lvl=1):
+    H, W = win['sensor_size']
+    v_o, g_o, aux = O.loss_and_grad(theta, *args_of(win), A, BETA, gamma, delta, lvl, 5, (H, W), method, return_intermediates=True)
+    v, g, I, G = run_engine(win, theta, 'fp64', gamma, delta, lvl, method=method)
+    assert abs(v - v_o) / abs(v_o) <= 1e-10, abs(v - v_o) / abs(v_o)
+    assert rel(g, g_o) <= 1e-9, rel(g, g_o)
+    assert rel(I, aux['_iwes']) <= 1e-11, rel(I, aux['_iwes'])
+    assert rel(G, aux['_G']) <= 1e-10, rel(G, aux['_G'])
+
+
+LIMIT_CASES = [
+    # id, sensor, N, R, theta shape, method
+    ('R16', (48, 64), 6_000, 16, (4, 4), 'bilinear'),
+    ('sensor_3x3', (3, 3), 400, 3, (1, 1), 'bilinear'),
+    ('lanczos5', (60, 80), 8_000, 3, (5, 6), 'lanczos5'),
+    ('cubic', (60, 80), 8_000, 3, (5, 6), 'cubic'),
+    ('finer_rows', (40, 56), 6_000, 2, (43, 20), 'lanczos3'),
+    ('finer_cols', (40, 56), 6_000, 2, (12, 61), 'bilinear'),
+]
+
+
+@pytest.mark.parametrize('case', LIMIT_CASES, ids=[c[0] for c in LIMIT_CASES])
+def test_limits_against_the_oracle(built_lib, case):
+    _, shape, n, R, hw, method = case
+    win = synth.make_window(23, shape, n, R, flow='smooth', flow_mag=4.0)
+    theta = synth.theta_near_truth(5, win, hw) if max(hw) <= min(shape) else np.random.default_rng(9).normal(0.0, 2.0, hw + (2,))
+    _check_against_oracle(win, theta, method, gamma=2.5e-4, lvl=0)
+
+
+def test_65_windows_masked_against_the_oracle(built_lib):
+    """B = 65: past the 64-bit window mask of the kernels.  Windows masked below index 64 return NaN and a zero gradient, the active
+    ones the unmasked evaluation's bits, and windows 0, 63 and 64 match the oracle."""
+    H, W, R, B = 40, 50, 2, 65
+    wins = [synth.make_window(300 + b, (H, W), 1500 + 37 * b, R, flow='constant', flow_mag=3.0 + 0.05 * b) for b in range(B)]
+    thetas = np.stack([synth.theta_near_truth(b, w, (2, 2)) for b, w in enumerate(wins)])
+    p = engine.make_params(A, BETA, 0.0, 0.0, 1)
+    active = np.ones(B, dtype=np.uint8)
+    active[[0, 5, 31, 32, 62]] = 0
+    with engine.Engine((H, W), sum(len(w['xs']) for w in wins), max_refs=R, max_windows=B, precision='fp64') as eng:
+        eng.set_windows([args_of(w) for w in wins])
+        v, g, _ = eng.loss_grad(thetas, p)
+        I, G = eng.iwes(), eng.image_grad()
+        vm, gm, _ = eng.loss_grad(thetas, p, active=active)
+    assert np.all(np.isfinite(v))
+    on = active == 1
+    assert np.all(np.isnan(vm[~on])) and not gm[~on].any()
+    assert np.array_equal(vm[on], v[on]) and np.array_equal(gm[on], g[on])
+    for b in (0, 63, 64):
+        v_o, g_o, aux = O.loss_and_grad(thetas[b], *args_of(wins[b]), A, BETA, 0.0, 0.0, 1, 5, (H, W), return_intermediates=True)
+        assert abs(v[b] - v_o) / abs(v_o) <= 1e-10, b
+        assert rel(g[b], g_o) <= 1e-9, (b, rel(g[b], g_o))
+        assert rel(I[b], aux['_iwes']) <= 1e-11, b
+        assert rel(G[b], aux['_G']) <= 1e-10, b
+
+
+def test_windows_on_both_sides_of_a_scale_step(built_lib):
+    """The IWE accumulator's scale is per window: 2^ishift with ishift = 62 - ceil(log2(N / 2 pi)).  N = 102943 and 102944 sit on
+    the two sides of N / 2 pi = 2^14 (ishift 48 and 47); both in one batch, each against the oracle."""
+    H, W, R = 96, 128, 3
+    wins = [synth.make_window(60 + b, (H, W), n, R, flow='constant', flow_mag=6.0) for b, n in enumerate((102_943, 102_944))]
+    assert [int(np.ceil(np.log2(len(w['xs']) / (2 * np.pi)))) for w in wins] == [14, 15]
+    thetas = np.stack([synth.theta_near_truth(b, w, (2, 2)) for b, w in enumerate(wins)])
+    with engine.Engine((H, W), 2 * 102_944, max_refs=R, max_windows=2, precision='fp64') as eng:
+        eng.set_windows([args_of(w) for w in wins])
+        v, g, _ = eng.loss_grad(thetas, engine.make_params(A, BETA, 0.0, 0.0, 1))
+        I, G = eng.iwes(), eng.image_grad()
+    for b, w in enumerate(wins):
+        v_o, g_o, aux = O.loss_and_grad(thetas[b], *args_of(w), A, BETA, 0.0, 0.0, 1, 5, (H, W), return_intermediates=True)
+        assert abs(v[b] - v_o) / abs(v_o) <= 1e-10, b
+        assert rel(g[b], g_o) <= 1e-9, (b, rel(g[b], g_o))
+        assert rel(I[b], aux['_iwes']) <= 1e-11, (b, rel(I[b], aux['_iwes']))
+        assert rel(G[b], aux['_G']) <= 1e-10, (b, rel(G[b], aux['_G']))
+
+
+N_TOP = 26_353_589      # the largest N with ceil(log2(N / 2 pi)) <= 22, i.e. ishift >= 40
+
+
+def test_top_of_the_iwe_scale(built_lib):
+    """One window at the largest event count the scale guard (ishift >= 40) accepts, a fifth of its events on one hot source pixel,
+    against the C port.  One event more is refused with UNSUPPORTED, and the context stays usable: the same window again gives
+    the same bits."""
+    import os
+    assert np.ceil(np.log2(N_TOP / (2 * np.pi))) == 22 and np.ceil(np.log2((N_TOP + 1) / (2 * np.pi))) == 23
+    H, W, R = 180, 240, 1
+    win = synth.make_window(70, (H, W), N_TOP, R, flow='constant', flow_mag=8.0)
+    win['xs'] = win['xs'].copy(); win['ys'] = win['ys'].copy()
+    win['xs'][:N_TOP // 5] = 100; win['ys'][:N_TOP // 5] = 60
+    theta = synth.theta_near_truth(3, win, (1, 1))
+    v_p, g_p, im = CP.loss_and_grad(theta, *args_of(win), A, BETA, (H, W), nthreads=min(os.cpu_count() or 1, 16), return_images=True)
+    p = engine.make_params(A, BETA, 0.0, 0.0, 1)
+    with engine.Engine((H, W), N_TOP + 1, max_refs=R, precision='fp64') as eng:
+        eng.set_window(*args_of(win))
+        v, g, _ = eng.loss_grad(theta, p)
+        I, G = eng.iwes()[0], eng.image_grad()[0]
+        assert abs(v[0] - v_p) / abs(v_p) <= 1e-10
+        assert rel(g[0], g_p) <= 1e-9, rel(g[0], g_p)
+        assert rel(I, im['iwes']) <= 1e-11, rel(I, im['iwes'])
+        assert rel(G, im['G']) <= 1e-10, rel(G, im['G'])
+        big = [np.append(a, a[-1:]) for a in (win['xs'], win['ys'], win['ts'])] + [win['edges'], win['edge_ts']]
+        with pytest.raises(engine.EincmError) as ei:
+            eng.set_window(*big)
+        assert ei.value.code == L.ERR_UNSUPPORTED and 'scale' in str(ei.value)
+        eng.set_window(*args_of(win))
+        v2, g2, _ = eng.loss_grad(theta, p)
+        assert v2[0] == v[0] and np.array_equal(g2, g)
+
+
+
+def test_ties_at_the_maximum(built_lib):
+    """The cotangent of max(IWE) is shared equally among the tied pixels (k64_grad2).  The gradient at theta = 0 cancels by symmetry,
+    so dL/dIWE carries the check, with the value and the IWE."""
+    win = TIES.tied_window()
+    H, W = win['sensor_size']
+    theta = np.zeros((1, 1, 2))
+    v_o, _, aux = O.loss_and_grad(theta, *args_of(win), A, BETA, 0.0, 0.0, 1, 5, (H, W), return_intermediates=True)
+    I_o = aux['_iwes']
+    assert all((I_o[r] == I_o[r].max()).sum() == 6 for r in range(len(I_o)))
+    v, _, I, G = run_engine(win, theta, 'fp64')
+    assert abs(v - v_o) / abs(v_o) <= 1e-10
+    assert rel(I, I_o) <= 1e-11
+    assert rel(G, aux['_G']) <= 1e-10, rel(G, aux['_G'])

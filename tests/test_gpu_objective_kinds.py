@@ -2,12 +2,18 @@
 (tests/_objective_kinds_witness.py) for every contrast x correlation combination, determinism, the entry points, the refusals and a
 lockstep solve.  Tolerance and `rel` as tests/test_gpu_parity.py: 1e-5, max-norm relative."""
 import importlib
+import os
+import sys
 
 import numpy as np
 import pytest
 
 from oracle import eincm_oracle as O
 import _objective_kinds_witness as WIT
+import _ties as TIES
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'dev'))
+import fuzz_gpu  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -124,6 +130,58 @@ def test_tile_equal_to_sensor(ck, rk):
 def test_level0_with_tv_and_divergence(ck, rk):
     win = window()
     check_parity(win, synth.theta_near_truth(6, win, (4, 4)), ck, rk, gamma=GAMMA, delta=0.3, lvl=0)
+
+
+# the cell reduction (obj_reduce: one wave strides over the cells and merges the min / max tie counts across lanes) past 64 cells,
+# and the per-reference constants up to R = 16; each case pairs a stencil kind (ck 2 / rk 3) with a moment kind
+@pytest.mark.parametrize('ck,rk', [(2, 1), (3, 3)])
+@pytest.mark.parametrize('shape,n,R,tile', [((480, 640), 100_000, 3, (32, 42)), ((60, 80), 8000, 3, (4, 4)), ((60, 80), 8000, 16, (7, 9))],
+                         ids=['480x640_225cells', '60x80_300cells', '60x80_R16'])
+def test_many_cells_and_references(shape, n, R, tile, ck, rk):
+    win = window(shape, n, R, seed=17)
+    ncells = (shape[0] // tile[0]) * (shape[1] // tile[1])
+    assert ncells > 64 or R == 16
+    check_parity(win, synth.theta_near_truth(14, win, (2, 2)), ck, rk, tile=tile)
+
+
+@pytest.mark.parametrize('ck,rk,tile', [(3, 1, (10, 13)), (2, 3, (32, 42)), (1, 2, (1, 5))])
+def test_batch_of_unequal_windows_against_witness(built_lib, ck, rk, tile):
+    """8 windows of 1 .. 1e5 events in one context, each against the witness (value, gradient, dL/dIWE, the two mean relative terms;
+    fuzz_gpu.run_case, with its conditioning rule for the windows of a handful of events), count images bit-exact."""
+    c = dict(H=96, W=128, R=3, B=8, hw=(2, 2), method='bilinear', mag=6.0, flow='smooth', alpha=A, beta=B_, gamma=0.0, delta=0.0,
+             lvl=1, ck=ck, N=[1, 7, 40, 300, 2000, 10_000, 40_000, 100_000])
+    res = fuzz_gpu.run_case(c, 700, kinds=(ck, rk, tile))
+    assert not fuzz_gpu.failures(res, 'kinds'), res
+
+
+def test_65_windows_masked_against_witness():
+    """B = 65: past the 64-bit window mask of the kernels.  Windows masked below index 64 return NaN and a zero gradient, the active
+    ones the unmasked evaluation's bits, and windows 0, 63 and 64 match the witness."""
+    H, W, R, B = 40, 50, 2, 65
+    wins = [synth.make_window(300 + b, (H, W), 1500 + 37 * b, R, flow='constant', flow_mag=3.0 + 0.05 * b) for b in range(B)]
+    thetas = np.stack([synth.theta_near_truth(b, w, (2, 2)) for b, w in enumerate(wins)])
+    tile = (9, 11)
+    p = engine.make_params(A, B_, 0.0, 0.0, 1, 'bilinear', 'adaptive_grad_mag', correlation_kind='adaptive_mse')
+    active = np.ones(B, dtype=np.uint8)
+    active[[0, 5, 31, 32, 62]] = 0
+    with engine.Engine((H, W), sum(len(w['xs']) for w in wins), max_refs=R, max_windows=B) as eng:
+        eng.set_windows([win_args(w) for w in wins])
+        eng.set_objective_tiles(tile)
+        v, g, aux = eng.loss_grad(thetas, p, want_aux=True)
+        G = eng.image_grad()
+        vm, gm, _ = eng.loss_grad(thetas, p, active=active)
+    assert np.all(np.isfinite(v))
+    on = active == 1
+    assert np.all(np.isnan(vm[~on])) and not gm[~on].any()
+    assert np.array_equal(vm[on], v[on]) and np.array_equal(gm[on], g[on])
+    for b in (0, 63, 64):
+        AH = O.resample_matrix(2, H, H / 2, 'bilinear')
+        AW = O.resample_matrix(2, W, W / 2, 'bilinear')
+        v_w, g_w, G_w, aux_w = WIT.loss_and_grad(thetas[b], *win_args(wins[b]), A, B_, 0.0, 0.0, 1, AH, AW, 2, 1, tile)
+        assert abs(v[b] - v_w) <= TOL * abs(v_w), (b, v[b], v_w)
+        assert rel(g[b], g_w) <= TOL, (b, rel(g[b], g_w))
+        assert rel(G[b], G_w) <= TOL, (b, rel(G[b], G_w))
+        assert aux[b]['mean_rel_corr'] == pytest.approx(aux_w['mean_rel_corr'], rel=TOL), b
 
 
 # ---- 2. determinism -------------------------------------------------------------------------------------------------------------
@@ -275,3 +333,24 @@ def test_lockstep_solve_with_new_kinds():
                                                          contrast_kind='adaptive_variance', correlation_kind='hadamard')
             assert np.isfinite(fv) and np.all(np.isfinite(out[b]['final_theta_pyr'][key])), (b, key)
             assert fv <= v0 + 1e-9 * abs(v0), (b, key, fv, v0)
+
+
+
+@pytest.mark.parametrize('ck,rk,tile', [(2, 1, (5, 7)), (3, 3, (24, 32)), (1, 2, (3, 4))])
+def test_ties_at_the_maximum(ck, rk, tile):
+    """The max-tie counts of k_obj_parts (merged across waves) and obj_reduce (across cells): the cotangent of max(IWE) is shared
+    among six tied pixels.  The gradient at theta = 0 cancels by symmetry, so dL/dIWE carries the check, with the value."""
+    win = TIES.tied_window()
+    H, W = win['sensor_size']
+    theta = np.zeros((1, 1, 2))
+    v_w, _, G_w, aux_w = witness(win, theta, ck, rk, tile)
+    with engine.Engine((H, W), len(win['xs']), max_refs=2) as eng:
+        eng.set_window(*win_args(win))
+        eng.set_objective_tiles(tile)
+        v, _, aux = eng.loss_grad(theta, engine.make_params(A, B_, 0.0, 0.0, 1, 'bilinear', ck, correlation_kind=rk), want_aux=True)
+        G = eng.image_grad()[0]
+        I = eng.iwes()[0]
+    assert all((I[r] == I[r].max()).sum() == 6 for r in range(2))
+    assert abs(v[0] - v_w) <= TOL * abs(v_w), (v[0], v_w)
+    assert rel(G, G_w) <= TOL, rel(G, G_w)
+    assert aux[0]['mean_rel_corr'] == pytest.approx(aux_w['mean_rel_corr'], rel=TOL)

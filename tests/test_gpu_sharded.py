@@ -32,7 +32,7 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _worker(rank, world, port, q, iwe_collective='all_reduce'):
+def _worker(rank, world, port, q, iwe_collective='all_reduce', kinds=(0, 0)):
     sys.path.insert(0, ROOT)
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
@@ -50,7 +50,7 @@ def _worker(rank, world, port, q, iwe_collective='all_reduce'):
         se.set_windows([(win['xs'][sl], win['ys'][sl], win['ts'][sl], win['edges'], win['edge_ts'])])
         out = []
         for th, (hw, gamma, lvl) in zip(thetas, CASES):
-            v, g = se.loss_grad(th, engine.make_params(20.0, 35.0, gamma, 0.0, lvl))
+            v, g = se.loss_grad(th, engine.make_params(20.0, 35.0, gamma, 0.0, lvl, 'bilinear', kinds[0], correlation_kind=kinds[1]))
             out.append((float(v[0]), g[0].copy()))
     q.put((rank, out))
     dist.barrier()
@@ -138,3 +138,35 @@ def test_two_ranks_split_events_match_unsharded(built_lib, iwe_collective):
             v1, g1, _ = e1.loss_grad(th, engine.make_params(20.0, 35.0, gamma, 0.0, lvl))
             assert res[0][i][0] == pytest.approx(v1[0], rel=2e-6), (hw, res[0][i][0], v1[0])
             assert np.abs(res[0][i][1] - g1[0]).max() <= 2e-5 * np.abs(g1[0]).max()
+
+
+@pytest.mark.timeout(300)
+@pytest.mark.parametrize('ck', [2, 3])
+def test_two_ranks_split_events_new_kinds_match_witness(built_lib, ck):
+    """The IWE summed over two ranks, then evaluated with an adaptive contrast kind and the joint contrast (whose Scharr stencils
+    read the reduced image across the ranks' event halves), against the fp64 autograd witness."""
+    from oracle import eincm_oracle as O
+    import _objective_kinds_witness as WIT
+    world = 2
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, q, 'all_reduce', (ck, 3))) for r in range(world)]
+    for p in procs:
+        p.start()
+    res = dict(q.get(timeout=240) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    win, thetas = _inputs()
+    a = (win['xs'], win['ys'], win['ts'], win['edges'], win['edge_ts'])
+    for i, (th, (hw, gamma, lvl)) in enumerate(zip(thetas, CASES)):
+        h, w = th.shape[:2]
+        AH = O.resample_matrix(h, H, H / h, 'bilinear')
+        AW = O.resample_matrix(w, W, W / w, 'bilinear')
+        v_ref, g_ref, _, _ = WIT.loss_and_grad(th, *a, 20.0, 35.0, gamma, 0.0, lvl, AH, AW, ck, 3)
+        for r in range(world):
+            v, g = res[r][i]
+            assert abs(v - v_ref) <= 1e-5 * abs(v_ref), (hw, r, v, v_ref)
+            assert np.abs(g - g_ref).max() <= 1e-5 * np.abs(g_ref).max(), (hw, r)
+        assert res[0][i][0] == res[1][i][0]

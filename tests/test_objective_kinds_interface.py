@@ -163,3 +163,35 @@ def test_witness_handover_derivative_by_differences():
     v_o = WIT.loss_and_grad(0.3 * prev + 0.7 * theta, *args, 20.0, 35.0, 0.0, 0.0, 1, AH, AW, **kw)[0]
     assert v == v_o
     assert np.isfinite(dv)
+
+
+@pytest.mark.parametrize('shape,tile', [((30, 44), (7, 9)), ((23, 31), (1, 6)), ((23, 31), (5, 1)), ((12, 17), (1, 1)),
+                                        ((24, 32), (24, 32)), ((20, 27), (2, 27)), ((20, 27), (20, 2))])
+def test_witness_vector_tiles_equal_loop_tiles(shape, tile):
+    """The batched tile form of the witness (the default) against the one-slice-per-tile form: every tiled term's value, and the
+    whole objective's value, gradient and dL/dIWE by autograd, at ragged, 1xN, Nx1, side-2 and tile = sensor tiles."""
+    rng = np.random.default_rng(17)
+    I = rng.random(shape) ** 3 * 4.0
+    E = rng.random(shape)
+    n = ES.normalize_to_unit_range(I)
+    for ck in (2, 3):
+        a, b = WIT.contrast_value(I, ck, tile, 'vector'), WIT.contrast_value(I, ck, tile, 'loop')
+        assert abs(a - b) <= 1e-13 * abs(b), (ck, a, b)
+    a, b = WIT.correlation_value(E, n, 1, tile, 'vector'), WIT.correlation_value(E, n, 1, tile, 'loop')
+    assert abs(a - b) <= 1e-13 * abs(b), (a, b)
+    H, W = shape
+    win = synth.make_window(8, (H, W), 600, 2, flow='smooth', flow_mag=3.0)
+    args = (win['xs'], win['ys'], win['ts'], win['edges'], win['edge_ts'])
+    theta = synth.theta_near_truth(3, win, (2, 2))
+    AH = O.resample_matrix(2, H, H / 2, 'bilinear')
+    AW = O.resample_matrix(2, W, W / 2, 'bilinear')
+    for ck, rk in ((2, 1), (3, 0), (0, 1), (3, 1)):
+        vv, gv, Gv, av = WIT.loss_and_grad(theta, *args, 20.0, 35.0, 0.0, 0.0, 1, AH, AW, ck, rk, tile, form='vector')
+        vl, gl, Gl, al = WIT.loss_and_grad(theta, *args, 20.0, 35.0, 0.0, 0.0, 1, AH, AW, ck, rk, tile, form='loop')
+        assert abs(vv - vl) <= 1e-13 * abs(vl), (ck, rk)
+        assert np.abs(gv - gl).max() <= 1e-13 * np.abs(gl).max(), (ck, rk)
+        assert np.abs(Gv - Gl).max() <= 1e-13 * np.abs(Gl).max(), (ck, rk)
+        for k in ('mean_rel_corr', 'mean_rel_contrast'):
+            assert abs(av[k] - al[k]) <= 1e-13 * abs(al[k]), (ck, rk, k)
+    with pytest.raises(ValueError):
+        WIT.contrast_value(I, 2, tile, 'loops')
