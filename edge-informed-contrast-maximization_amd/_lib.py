@@ -18,6 +18,8 @@ CORRELATION_KINDS = {'mse': 0, 'adaptive_mse': 1, 'hadamard': 2, 'joint_contrast
 PF_CORRELATION_SHIFT = 8
 PF_CORRELATION_MASK = 0x700    # eincm_params.flags bits 8-10: the correlation kind
 DEFAULT_OBJECTIVE_TILE = (32, 42)
+SPLAT_WINDOW_MAX = 7         # EINCM_SPLAT_WINDOW_MAX: splat window sizes 1..7 (eincm_set_splat_window)
+DEFAULT_SPLAT_WINDOW = 3
 METHODS = {'linear': 0, 'bilinear': 0, 'triangle': 0, 'lanczos3': 1, 'lanczos5': 2, 'cubic': 3, 'bicubic': 3}
 PF_FULL_AUX = 1
 PF_NO_TV_GRAD = 2
@@ -118,6 +120,7 @@ SIGNATURES = [
     ('eincm_gaussian_blur', C.c_int, [_P, _D, C.c_int, C.c_double, _D]),
     ('eincm_tiled_objectives', C.c_int, [_P, C.c_int, C.c_int, C.POINTER(TiledOut)]),
     ('eincm_set_objective_tiles', C.c_int, [_P, C.c_int, C.c_int]),
+    ('eincm_set_splat_window', C.c_int, [_P, C.c_int]),
 ]
 
 _lib = None

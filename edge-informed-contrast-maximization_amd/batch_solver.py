@@ -37,7 +37,7 @@ try:                                                 # level-2 BLAS on a 512 x 5
 except ImportError:                                  # without it the update stays in plain numpy
     threadpool_limits = None
 
-from .engine import Engine, check_precision, make_params
+from .engine import Engine, check_precision, check_window_size, make_params
 from .solver import ScipyMinimizeInfo, EmptyCallback, rescale_theta, _canon
 
 _BFGS_C1, _BFGS_C2, _BFGS_XTOL, _BFGS_AMIN, _BFGS_AMAX, _LS_MAXITER = 1e-4, 0.9, 1e-14, 1e-100, 1e100, 100
@@ -437,7 +437,7 @@ class BatchedMultipleLevelEINCMSolver:
     """The coarse-to-fine theta pyramid of B windows, solved level by level in lockstep on one engine context (or ``n_groups`` of them).
 
     Constructor keywords follow ``solver.MultipleLevelEINCMSolver`` (reference solver.py:16-126); instead of loss callables it
-    takes the loss parameters (``loss_kwargs``: alpha, beta, gamma, delta, scale_to_sensor_size_method[, contrast_kind][, correlation_kind][, tile_size][, precision]), because
+    takes the loss parameters (``loss_kwargs``: alpha, beta, gamma, delta, scale_to_sensor_size_method[, contrast_kind][, correlation_kind][, tile_size][, window_size][, precision]), because
     the objective is the engine's batched loss+grad.  ``set_datasamples`` stages the B windows (one per sequence, or B independent
     windows); ``solve`` returns one result dict per window with the reference's keys (solver.py:254-267).  Calling set_datasamples /
     solve again continues every sequence with its own prior (handover), exactly as the single-window solver does window after window.
@@ -464,6 +464,8 @@ class BatchedMultipleLevelEINCMSolver:
         self.handover_settings = hs
         self.loss_kwargs = dict(loss_kwargs)
         check_precision(self.loss_kwargs.get('precision', 'fp32'))
+        if 'window_size' in self.loss_kwargs:
+            check_window_size(self.loss_kwargs['window_size'])
         self.pyramid_downscale_method, self.pyramid_upscale_method = pyramid_downscale_method, pyramid_upscale_method
         self.pyramid_bases = pyramid_bases if pyramid_bases is not None else [2] * (n_pyr_lvls - 1)
         self.callbacks = theta_solver_callbacks if theta_solver_callbacks is not None else [EmptyCallback() for _ in range(self.B)]
@@ -508,9 +510,12 @@ class BatchedMultipleLevelEINCMSolver:
                                    precision=self.loss_kwargs.get('precision', 'fp32')) for ix in self.groups]
             self.engine = self.engines[0]
         tiles = self.loss_kwargs.get('tile_size')
+        window = self.loss_kwargs.get('window_size')
         for eng, ix in zip(self.engines, self.groups):
             if tiles is not None and eng.objective_tiles != tuple(tiles):
                 eng.set_objective_tiles(tiles)
+            if window is not None and eng.splat_window != window:
+                eng.set_splat_window(window)
             eng.set_windows([windows[b] for b in ix])
 
     def close(self):

@@ -24,6 +24,7 @@
 #include "eincm_binning.hip.h"
 #include "eincm_edges.hip.h"
 #include "eincm_objectives.hip.h"
+#include "eincm_splat_window.hip.h"
 
 using namespace eincm;
 
@@ -195,6 +196,9 @@ struct eincm_ctx {
     double hp_us[EINCM_N_HOST_PHASES] = {};
     int64_t hp_n = 0;
     bool constants_pending = false;   // staged with EINCM_SW_DEFER_CONSTANTS and not finished yet
+    bool sharded_staging = false;     // the staged batch's constants came from EINCM_SW_DEFER_CONSTANTS (summed IUEs of all shards)
+    int splat_size = 3;               // eincm_set_splat_window: events_to_pdf_frame's window_size
+    int splat_rad = 1;                // its radius splat_size / 2: 1 runs k_splat / k_gather, any other k_splat_r / k_gather_r
     bool acc_dirty = false;        // a forward half was launched and its consumers were not: accumulators must be memset before reuse
     bool Theta_valid = false;      // d_Theta holds the upsampled theta of the last evaluation (2-DoF evaluations skip the image)
     std::vector<double> last_theta11;   // (B,2) theta of the last 2-DoF evaluation (to build d_Theta on demand)
@@ -579,7 +583,21 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
                    use_arg ? 1 : 0, theta_dev, targ
             // 512 threads per workgroup in both compile-time modes: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
             // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
-            if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 512>, SPLAT_ARGS(512));
+            if (c->splat_rad != 1) {
+                // another splat window (eincm_splat_window.hip.h): u64 LDS windows, capped so that they fit beside the Theta tile
+                Geom gs = g;
+                gs.wincap = std::min(g.wincap, theta_mode == THETA_TILE ? SW_CAP_TILE : SW_CAP_CONST);
+                gs.winmaxw = std::max(40, (int)std::lround(std::sqrt((double)gs.wincap * 1.4)));
+                const size_t lds_r = (size_t)gs.wincap * sizeof(unsigned long long) + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
+#define SPLAT_R_ARGS dim3(grid_sp), dim3(NT), lds_r, gs, n_sp, items_sp, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_acc, \
+                     order_sp, use_arg ? 1 : 0, theta_dev, targ
+#define SPLAT_R(TM_) do { if (c->splat_rad == 0) launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 0>, SPLAT_R_ARGS); \
+                          else if (c->splat_rad == 2) launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 2>, SPLAT_R_ARGS); \
+                          else launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 3>, SPLAT_R_ARGS); } while (0)
+                if (theta_mode == THETA_CONST) SPLAT_R(THETA_CONST); else SPLAT_R(THETA_TILE);
+#undef SPLAT_R
+#undef SPLAT_R_ARGS
+            } else if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 512>, SPLAT_ARGS(512));
             else                           launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_TILE, 512>, SPLAT_ARGS(512));
 #undef SPLAT_ARGS
         }
@@ -916,12 +934,14 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         auto lds_words = [](bool pal, double side_px) { const double sd = std::ceil(side_px); return (pal ? std::ceil(sd / 32.0) * 32.0 : sd) * sd; };
         static const int caps[] = {2304, 3072, 4608, 6912};      // 6912 keeps k_gather's LDS (window + accumulators + Theta tile) under 64 KiB
         auto cap_of = [&](double need, int floor_k) { for (int k = floor_k; k < 4; ++k) if (need <= caps[k]) return caps[k]; return caps[3]; };
-        double side = TS + 4 + vmax * tspan;
+        // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
+        const double margin = 2.0 * (c->splat_rad + 1);
+        double side = TS + margin + vmax * tspan;
         const bool two_dof = h == 1 && w == 1 && !identity;
         // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
         // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
         c->pend.splat_short = (two_dof && c->n_items_sh > 0 && lds_words(false, side) > 6912.0);
-        if (c->pend.splat_short) side = TS + 4 + vmax * c->tspan_sh;
+        if (c->pend.splat_short) side = TS + margin + vmax * c->tspan_sh;
         // Where a larger window costs no residency it is taken at once (a capacity is an allocation, the windows themselves stay as small
         // as their segments need): the 2-DoF kernels hold nothing but the window in LDS, 4608 words = 18 KiB still gives the 8 workgroups
         // of 4 waves a CU can hold; the theta-grid gather carries 32 KiB beside its window and runs 3 workgroups per CU up to 5461 words.
@@ -934,12 +954,12 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         c->g.pitch_aligned = pal_s ? 1 : 0;
         // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
         // sends taps down the direct path
-        const double side_a = TS + 4 + vmax * c->tspan_a;
+        const double side_a = TS + margin + vmax * c->tspan_a;
         const int cap_a = cap_of(side_a * side_a, 2);          // (the theta-grid gather's windows: pitch = width)
         c->g.wincap_a = cap_a;
         c->g.winmaxw_a = std::max(40, (int)std::lround(std::sqrt((double)cap_a * 1.4)));
         // and the 2-DoF gather's list
-        const double side_2 = TS + 4 + vmax * c->tspan_2;
+        const double side_2 = TS + margin + vmax * c->tspan_2;
         const int cap_2 = cap_of(lds_words(false, side_2), 2);
         // (the 2-DoF gather keeps pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another batch
         // of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
@@ -949,7 +969,8 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
     // 2-DoF theta with nothing but the contrast and correlation terms (every level above 0 of the reference's pyramid at its first
     // level, and the bench workload): the scalar assembly and the sum of the gather's per-workgroup partials run on the host
     static const bool no_host_asm = getenv("EINCM_NO_HOST_ASM") != nullptr;
-    const bool grid_tail = !(h == 1 && w == 1) && c->proj_in_gather && c->itembase_valid && (size_t)g.B * nth <= ZERO_COPY_MAX && !c->theta_dev_in;
+    // (another splat window: its gather leaves the theta-grid sums to k_project and k_final, so no tail)
+    const bool grid_tail = c->splat_rad == 1 && !(h == 1 && w == 1) && c->proj_in_gather && c->itembase_valid && (size_t)g.B * nth <= ZERO_COPY_MAX && !c->theta_dev_in;
     // (the TV term rides along on a theta grid: k_tv projects its own gradient and the gather's tail combines it; a 2-DoF theta with
     // TV - no level of the reference's pyramid - keeps k_final)
     const bool host_asm = want_grad && !identity && (((h == 1 && w == 1) && !ep.want_tv) || grid_tail) && !ep.want_div && !full_aux && !no_host_asm &&
@@ -1085,7 +1106,7 @@ int eval_end_launch(eincm_ctx* c) {
                            c->d_wc, c->d_objc, c->d_gdiv, c->d_dgparts, c->d_G, c->d_gmax, c->h_ovals, 0);
     }
     const bool direct11 = want_grad && !identity && h == 1 && w == 1;
-    const bool proj = want_grad && !identity && !direct11 && c->proj_in_gather;      // k_gather projects its tile's sums itself
+    const bool proj = want_grad && !identity && !direct11 && c->proj_in_gather && c->splat_rad == 1;      // k_gather projects its tile's sums itself
     // a window with a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel); speed is irrelevant there
     bool wide = false;
     for (int b = 0; b < g.B; ++b) wide = wide || (c->win_events[b] * (int64_t)g.R < 4096);
@@ -1141,7 +1162,19 @@ int eval_end_launch(eincm_ctx* c) {
                     (host_asm && proj && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap
 #define GATHER_TILE(WIDE_, PROJ_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, PROJ_>, GATHER_ARGS(NT_TILE))
 #define GATHER_ALLR(WIDE_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, 1, 1>, GATHER_ARGS(NT_TILE))
-                if (direct11) {
+                if (c->splat_rad != 1) {
+                    // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
+                    const size_t lds_r = gg.wincap_a * sizeof(float) + (direct11 ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2));
+#define GATHER_R_ARGS dim3((unsigned)(((n_g + NXCD - 1) / NXCD) * NXCD * g.R)), dim3(NT), lds_r, gg, n_g, items_g, xy_g, t_g, c->d_Theta, \
+                      c->d_tmm, c->d_edge_ts, c->d_G, c->d_gTheta, host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, wide ? 1 : 0, \
+                      c->pend.use_arg ? 1 : 0, c->pend.theta_dev, c->pend.targ
+#define GATHER_R(TM_) do { if (c->splat_rad == 0) launch_timed(c, EINCM_STAGE_GATHER, k_gather_r<TM_, 0>, GATHER_R_ARGS); \
+                           else if (c->splat_rad == 2) launch_timed(c, EINCM_STAGE_GATHER, k_gather_r<TM_, 2>, GATHER_R_ARGS); \
+                           else launch_timed(c, EINCM_STAGE_GATHER, k_gather_r<TM_, 3>, GATHER_R_ARGS); } while (0)
+                    if (direct11) GATHER_R(THETA_CONST); else GATHER_R(THETA_TILE);
+#undef GATHER_R
+#undef GATHER_R_ARGS
+                } else if (direct11) {
                     launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_CONST, 0, NT, 0>, GATHER_ARGS(NT));
                 } else if (all_r) {
                     if (wide) GATHER_ALLR(1); else GATHER_ALLR(0);
@@ -2011,6 +2044,7 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     c->staged = true;
     c->have_eval = false;
     c->err.clear();
+    c->sharded_staging = (sw_flags & EINCM_SW_DEFER_CONSTANTS) != 0;
     if (sw_flags & EINCM_SW_DEFER_CONSTANTS) {       // event-sharded mode: the caller sums the shards' IUEs first
         c->constants_pending = true;
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2532,6 +2566,38 @@ int eincm_set_objective_tiles(eincm_ctx* c, int tile_h, int tile_w) {
     if (c->pend.active && c->pend.launched) return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
     if (tile_h != c->obj_th || tile_w != c->obj_tw) { c->obj_th = tile_h; c->obj_tw = tile_w; c->objc_valid = false; }
     return EINCM_OK;
+}
+
+int eincm_set_splat_window(eincm_ctx* c, int window_size) {
+    if (!c) return EINCM_ERR_ARG;
+    if (window_size < 1 || window_size > EINCM_SPLAT_WINDOW_MAX)
+        return fail(c, EINCM_ERR_ARG, "splat window size %d outside 1..%d", window_size, EINCM_SPLAT_WINDOW_MAX);
+    if (c->pend.active && c->pend.launched) return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
+    if (c->fp64 && window_size != 3)
+        return fail(c, EINCM_ERR_UNSUPPORTED, "splat window size %d: fp64 mode (EINCM_CF_FP64) supports size 3 only", window_size);
+    if (window_size == c->splat_size) return EINCM_OK;
+    if (c->staged && (c->sharded_staging || c->constants_pending))
+        return fail(c, EINCM_ERR_STATE, "the staged batch's window constants come from an event-sharded staging: set the splat window "
+                                        "before eincm_set_windows");
+    HIPCHK(c, hipSetDevice(c->device));
+    c->splat_size = window_size;
+    c->splat_rad = window_size / 2;
+    c->objc_valid = false;                           // the objective kinds' zero-warp values come from the zero-warp IWE
+    if (!c->staged) return EINCM_OK;
+    // the window constants of the staged batch with the new splat: the theta = 0 pass of staging again
+    for (int b = 0; b < c->g.B; ++b) {
+        WinConst& wc = c->h_wc[b];
+        wc.c0_gradmag = 1.0; wc.c0_var = 1.0; wc.d0 = 1.0;
+        for (int r = 0; r < c->g.R; ++r) wc.zc[r] = 1.0;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_wc, c->h_wc, (size_t)c->g.B * sizeof(WinConst), hipMemcpyHostToDevice, c->stream));
+    std::vector<double> zero((size_t)c->g.B * 2, 0.0), val((size_t)c->g.B);
+    const eincm_params p = zero_pass_params();
+    const int rc = evaluate(c, zero.data(), 1, 1, &p, val.data(), nullptr, nullptr, true);
+    if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) { c->staged = false; return rc; }
+    const int rc2 = store_constants(c);
+    c->err.clear();
+    return rc2;
 }
 
 int eincm_tiled_objectives(eincm_ctx* c, int tile_h, int tile_w, eincm_tiled_out* out) {

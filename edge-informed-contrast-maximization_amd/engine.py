@@ -71,6 +71,13 @@ def check_tile_size(tile_size, sensor_size=None):
     return th, tw
 
 
+def check_window_size(window_size):
+    """Splat window size of events_to_pdf_frame (event_utils.py:13-61): an int in 1..7 (bool and float are refused); radius size // 2."""
+    if isinstance(window_size, bool) or not isinstance(window_size, (int, np.integer)) or not 1 <= int(window_size) <= L.SPLAT_WINDOW_MAX:
+        raise ValueError(f'window_size {window_size!r}: an integer in 1..{L.SPLAT_WINDOW_MAX}')
+    return int(window_size)
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                 full_aux=False, correlation_kind='mse'):
     """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
@@ -118,6 +125,7 @@ class Engine:
         self.R = 0
         self.timing = bool(timing)
         self.objective_tiles = L.DEFAULT_OBJECTIVE_TILE
+        self.splat_window = L.DEFAULT_SPLAT_WINDOW
         self._io = {}                      # (h, w) -> staging buffers of loss_grad with their addresses
 
     # -- lifetime ---------------------------------------------------------------------------------
@@ -388,6 +396,13 @@ class Engine:
         th, tw = check_tile_size(tile_size, (self.H, self.W))
         self._check(self._lib.eincm_set_objective_tiles(self._ctx, th, tw))
         self.objective_tiles = (th, tw)
+
+    def set_splat_window(self, window_size):
+        """Splat window size of every IWE of this context (events_to_pdf_frame's window_size, default 3).  On a
+        staged batch the window constants are formed again.  fp64 engines accept 3 only."""
+        s = check_window_size(window_size)
+        self._check(self._lib.eincm_set_splat_window(self._ctx, s))
+        self.splat_window = s
 
     def tiled_objectives(self, tile_size=None):
         """extract_tiles + compute_adaptive_* and their pairwise siblings (contrast_objectives.py:42-87,

@@ -51,11 +51,12 @@ def sparse_flow_error(pred_flow, gt_flow, event_mask=None):
 
 
 def evaluate_theta_array(theta_array, eval_xs, eval_ys, eval_ts, edges, edge_ts, gt_flow, alpha, beta, gamma, delta,
-                         sensor_size, err_eval_event_mask=None, precision='fp32'):
+                         sensor_size, err_eval_event_mask=None, window_size=3, precision='fp32'):
     """theta_eval.py:14-95 -> (evals dict, loss_obj dict).  The per-event warped coordinates (not used by the evaluation) and the IWE stay on the GPU;
-    ``iwe_var`` is var(IWE at the first reference time) = flow_warp_losses[0] * var(IUE).  precision='fp64': the engine's float64 mode."""
+    ``iwe_var`` is var(IWE at the first reference time) = flow_warp_losses[0] * var(IUE).  precision='fp64': the engine's float64 mode.
+    window_size: the splat window of the evaluation IWE (theta_eval.py:36 keeps events_to_pdf_frame's default, 3)."""
     lo = losses.compute_loss_objectives(theta_array, eval_xs, eval_ys, eval_ts, edges, edge_ts, sensor_size, warped_events=False,
-                                        precision=precision)
+                                        precision=precision, window_size=window_size)
     mean_rel_contrast = float(lo['rel_contrasts'].mean())
     mean_rel_corr = float(lo['rel_correlations'].mean())
     mean_rel_iwe_div = float(lo['rel_iwe_divergences'].mean())

@@ -22,7 +22,7 @@ import weakref
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, check_precision, check_tile_size, make_params
+from .engine import Engine, check_precision, check_tile_size, check_window_size, make_params
 
 _CACHE = []            # [(refs tuple, key, Engine)] most-recent first
 _CACHE_SIZE = 2
@@ -46,15 +46,19 @@ def _fingerprint(arrs):
     return hash(tuple(parts))
 
 
-def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp32', tile_size=None):
+def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp32', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW):
     """Engine holding this window (staged on first use; reused while the same, unmodified array objects are passed).  One engine per
     precision: 'fp64' is the float64 mode (Engine(..., precision='fp64')).  tile_size: (tile_h, tile_w) of the adaptive objective
-    kinds, set on the engine (None: the default 32 x 42)."""
+    kinds, set on the engine (None: the default 32 x 42).  window_size: the splat window of every IWE (events_to_pdf_frame's
+    window_size, 1..7, default 3), set on the engine."""
     check_precision(precision)
     tiles = L.DEFAULT_OBJECTIVE_TILE if tile_size is None else check_tile_size(tile_size, sensor_size)
+    window = check_window_size(window_size)
     eng = _engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device, precision)
     if eng.objective_tiles != tiles:
         eng.set_objective_tiles(tiles)
+    if eng.splat_window != window:
+        eng.set_splat_window(window)
     return eng
 
 
@@ -101,49 +105,53 @@ def _aux_dict(eng, a, with_arrays):
 
 def value_and_grad_loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls,
                              sensor_size, scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
-                             full_aux=False, aux_arrays=False, correlation_kind='mse', tile_size=None, precision='fp32'):
+                             full_aux=False, aux_arrays=False, correlation_kind='mse', tile_size=None,
+                             window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
     """((final_loss, aux_info), grad) — the shape jax.value_and_grad(loss_func, has_aux=True) returns.  precision='fp64': the engine's
     float64 mode (what the reference computes with jax_enable_x64: true)."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
     v, g, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=True, want_aux=True)
     return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
 
 
 def loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
               scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse',
-              tile_size=None, precision='fp32'):
+              tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
     """(final_loss, aux_info) as losses.py:108-205; forward only, every aux entry evaluated."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
     v, _, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=False, want_aux=True)
     return float(v[0]), _aux_dict(eng, aux[0], True)
 
 
 def value_and_grad_handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma,
                                       delta, cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
-                                      contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None, precision='fp32'):
+                                      contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None,
+                                      window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
     """(loss, d loss / d alpha_handover) of losses.py:269-276."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
     v, dv = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=True)
     return float(v[0]), float(dv[0])
 
 
 def handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta,
                        cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
-                       contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None, precision='fp32'):
+                       contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None,
+                       window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
     """loss only, as losses.py:208-276."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
     v, _ = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=False)
     return float(v[0])
 
 
-def compute_loss_objectives(theta, xs, ys, ts, edges, edge_ts, sensor_size, warped_events=True, precision='fp32'):
+def compute_loss_objectives(theta, xs, ys, ts, edges, edge_ts, sensor_size, warped_events=True,
+                            window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
     """losses.py:49-105 on a full-resolution theta (H,W,2): every key of the reference dict.  The per-event ``warped_xs`` /
     ``warped_ys`` ((R, n_events) float64, read by plotters only) cost a 2*R*n_events*8-byte copy: ``warped_events=False`` skips them."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, window_size=window_size)
     d = eng.objectives(np.asarray(theta, dtype=np.float64))[0]
     if warped_events:
         d['warped_xs'], d['warped_ys'] = eng.warped_events(0)

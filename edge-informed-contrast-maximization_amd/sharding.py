@@ -89,12 +89,14 @@ class ShardedEngine:
     (= RCCL over xGMI) reduces the engine's HBM buffer in place; 'gloo' (CPU rehearsal) bounces through host memory.
     """
 
-    def __init__(self, engine, rank=None, world_size=None, iwe_collective='all_reduce', device_results=None):
+    def __init__(self, engine, rank=None, world_size=None, iwe_collective='all_reduce', device_results=None, window_size=None):
         """iwe_collective: 'all_reduce' (the backend's default algorithm) or 'rs_ag' - reduce_scatter + all_gather of the int64
         accumulator, the one-hop form SURVEY 8(e) argues for on point-to-point xGMI (a few MB per evaluation are latency-bound, a ring
         pays 2 (n - 1) hops).  device_results: keep the gradient in HBM and all-reduce it there (default: whenever the backend is
         'nccl').  NOTE: the 'nccl' (= RCCL) branches and 'rs_ag' have never run on hardware - the builder had no multi-GPU node - and
-        are covered only as far as a single process can (tests/test_gpu_sharded.py); gloo rehearsals take the host-bounced branches."""
+        are covered only as far as a single process can (tests/test_gpu_sharded.py); gloo rehearsals take the host-bounced branches.
+        window_size: the splat window of every IWE (Engine.set_splat_window), set on the engine here - before the sharded staging,
+        whose window constants come from the summed IUEs and cannot be formed again by one rank."""
         if getattr(engine, 'precision', 'fp32') != 'fp32':
             raise ValueError(f"ShardedEngine: an engine of precision {engine.precision!r} cannot be sharded (event-sharded evaluation is "
                              "fp32 only: the fp64 mode has no device-resident entry points)")
@@ -103,6 +105,8 @@ class ShardedEngine:
             raise ValueError(f'iwe_collective {iwe_collective!r}: all_reduce or rs_ag')
         self.eng = engine
         self.dist = dist
+        if window_size is not None and engine.splat_window != window_size:
+            engine.set_splat_window(window_size)
         self.on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         self.rank = dist.get_rank() if self.on else 0
         self.world = dist.get_world_size() if self.on else 1

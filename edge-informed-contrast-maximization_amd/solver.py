@@ -173,7 +173,9 @@ class MultipleLevelEINCMSolver:
     """Coarse-to-fine theta pyramid solver; same constructor keywords, state and result dict as the reference
     (solver.py:16-126, solve :197-267, handover :302-347).  ``theta_loss_pfunc`` / ``handover_loss_pfunc`` are
     functools.partial objects over the value-and-grad callables of losses.py with everything bound except
-    (theta, xs, ys, ts, edges, edge_ts, cur_pyr_lvl) / (alpha_handover, prev_theta, theta, ..., cur_pyr_lvl)."""
+    (theta, xs, ys, ts, edges, edge_ts, cur_pyr_lvl) / (alpha_handover, prev_theta, theta, ..., cur_pyr_lvl).  Keywords bound in
+    them (contrast_kind, correlation_kind, tile_size, window_size, precision) reach the engine through losses.engine_for; bind the
+    same window_size in both, or every switch between the theta and handover solves forms the window constants again."""
 
     _SCALE_METHODS = ['linear', 'bilinear', 'trilinear', 'cubic', 'bicubic', 'tricubic', 'lanczos3', 'lanczos5']
 

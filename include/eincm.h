@@ -366,6 +366,16 @@ int eincm_tiled_objectives(eincm_ctx* ctx, int tile_h, int tile_w, eincm_tiled_o
  * arguments. */
 int eincm_set_objective_tiles(eincm_ctx* ctx, int tile_h, int tile_w);
 
+/* Size s of the Gaussian splat that forms every IWE of the context (events_to_pdf_frame's window_size, event_utils.py:13-61): every
+ * event adds exp(-|q|^2 / 2) / (2 pi) at the (2w+1)^2 pixels round(x) + d, d in [-w, w]^2, w = s / 2 (integer division: 2 behaves as 3,
+ * 4 as 5, 6 as 7, 1 is the centre tap alone).  1 <= s <= EINCM_SPLAT_WINDOW_MAX, else EINCM_ERR_ARG; default 3.  It applies to the
+ * zero-warp, warped, forward-only and handover IWEs; the count images and eincm_get_warped_events do not depend on it.  On a staged
+ * batch the window constants (c0, zero_corrs, d0, the zero-warp values of the objective kinds) are formed again at once; after an
+ * event-sharded staging (EINCM_SW_DEFER_CONSTANTS) a change is EINCM_ERR_STATE, so is a call while an asynchronous evaluation is in
+ * flight.  An EINCM_CF_FP64 context accepts 3 only (EINCM_ERR_UNSUPPORTED). */
+#define EINCM_SPLAT_WINDOW_MAX 7
+int eincm_set_splat_window(eincm_ctx* ctx, int window_size);
+
 #ifdef __cplusplus
 }
 #endif
