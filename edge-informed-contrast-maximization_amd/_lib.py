@@ -118,6 +118,7 @@ SIGNATURES = [
     ('eincm_inv_dist_transform', C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.c_double, C.c_double, _D,
                                            C.POINTER(C.c_int32)]),
     ('eincm_gaussian_blur', C.c_int, [_P, _D, C.c_int, C.c_double, _D]),
+    ('eincm_canny', C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     ('eincm_tiled_objectives', C.c_int, [_P, C.c_int, C.c_int, C.POINTER(TiledOut)]),
     ('eincm_set_objective_tiles', C.c_int, [_P, C.c_int, C.c_int]),
     ('eincm_set_splat_window', C.c_int, [_P, C.c_int]),

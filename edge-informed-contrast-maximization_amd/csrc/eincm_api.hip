@@ -25,6 +25,7 @@
 #include "eincm_edges.hip.h"
 #include "eincm_objectives.hip.h"
 #include "eincm_splat_window.hip.h"
+#include "eincm_canny.hip.h"
 
 using namespace eincm;
 
@@ -142,7 +143,7 @@ struct eincm_ctx {
     size_t oparts_cap = 0;
     double* h_ovals = nullptr;     // (maxB,maxR,2) pinned: contrast and signed correlation of every image (k_obj_grad)
 
-    // scratch of the edge-smoothing / tiled-objective entry points (eincm_edges.hip.h), grown on demand
+    // scratch of the edge-smoothing / Canny / tiled-objective entry points (eincm_edges.hip.h, eincm_canny.hip.h), grown on demand
     DevBuf e_u8, e_g, e_sq, e_misc, e_a, e_b, e_kern, e_out;
 
     // pinned host staging
@@ -2448,7 +2449,7 @@ int eincm_get_count_images(eincm_ctx* c, uint32_t* counts) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// SURVEY row f-4 (eincm_edges.hip.h)
+// SURVEY row f-4 (eincm_edges.hip.h, eincm_canny.hip.h)
 // ---------------------------------------------------------------------------------------------
 static int ensure_buf(eincm_ctx* c, DevBuf& b, size_t bytes) {
     if (b.bytes >= bytes) return EINCM_OK;
@@ -2556,6 +2557,44 @@ int eincm_gaussian_blur(eincm_ctx* c, const double* src, int n, double sigma, do
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(dst, c->e_a.p, tot * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // k (host vector) stays alive until here
+    return EINCM_OK;
+}
+
+int eincm_canny(eincm_ctx* c, const uint8_t* src, int n, double threshold1, double threshold2, int aperture_size, int l2_gradient,
+                uint8_t* dst) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!src || !dst) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n < 1 || n > 65535) return fail(c, EINCM_ERR_ARG, "n = %d images (1..65535)", n);
+    if (!std::isfinite(threshold1) || !std::isfinite(threshold2) || threshold1 < 0.0 || threshold2 < 0.0)
+        return fail(c, EINCM_ERR_ARG, "thresholds %g, %g must be finite and non-negative", threshold1, threshold2);
+    if (aperture_size != 3) return fail(c, EINCM_ERR_UNSUPPORTED, "aperture_size %d: only 3 is implemented", aperture_size);
+    // cv::Canny: swap, then for L2 clamp to 32767 and square the positive ones; low/high = cvFloor.  For L1 |dx| + |dy| <= 2040, so
+    // the same clamp changes no decision and keeps the floor inside int.
+    if (threshold1 > threshold2) std::swap(threshold1, threshold2);
+    threshold1 = std::min(threshold1, 32767.0);
+    threshold2 = std::min(threshold2, 32767.0);
+    if (l2_gradient) {
+        if (threshold1 > 0) threshold1 *= threshold1;
+        if (threshold2 > 0) threshold2 *= threshold2;
+    }
+    const int low = (int)std::floor(threshold1), high = (int)std::floor(threshold2);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int H = c->H, W = c->W;
+    const size_t npix = (size_t)H * W, tot = npix * n;
+    ENSURE(c, c->e_u8, tot); ENSURE(c, c->e_g, tot * 4); ENSURE(c, c->e_sq, tot);
+    uint8_t* d_img = static_cast<uint8_t*>(c->e_u8.p);             // the source, then the edge image
+    int32_t* d_parent = static_cast<int32_t*>(c->e_g.p);
+    uint8_t* d_state = static_cast<uint8_t*>(c->e_sq.p);
+    HIPCHK(c, hipMemcpyAsync(d_img, src, tot, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_canny_nms, dim3((W + CANNY_TW - 1) / CANNY_TW, (H + CANNY_TH - 1) / CANNY_TH, n), dim3(NT), 0, c->stream,
+                       H, W, low, high, l2_gradient ? 1 : 0, d_img, d_state, d_parent);
+    const dim3 grid((unsigned)std::min<size_t>((npix + NT - 1) / NT, 1024), n);
+    hipLaunchKernelGGL(k_canny_merge, grid, dim3(NT), 0, c->stream, H, W, d_state, d_parent);
+    hipLaunchKernelGGL(k_canny_resolve, grid, dim3(NT), 0, c->stream, H, W, d_state, d_parent);
+    hipLaunchKernelGGL(k_canny_output, grid, dim3(NT), 0, c->stream, H, W, d_state, d_parent, d_img);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(dst, d_img, tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return EINCM_OK;
 }
 

@@ -1,18 +1,24 @@
-"""Edge smoothing on the GPU: the last step that produces the ``edges`` stack the loss consumes (SURVEY f-4).
+"""Edge extraction on the GPU: grayscale frames -> the ``edges`` stack the loss consumes (SURVEY f-4).
 
-Mirrors the smoothing callables the reference's hydra group ``edge_extraction/smoothen`` binds
-(src/experiments/e00/configs/edge_extraction/smoothen/{gaussian,iedt}.yaml), same names and arguments:
+Mirrors the callables the reference's hydra group ``edge_extraction`` binds (src/experiments/e00/configs/edge_extraction/),
+same names and arguments:
 
+  to_canny_input(image)                                                jnp_to_ocv_n255, src/utils/img_utils.py:87-93 (host)
+  image_to_edge(img, apert_size=3, th1=30, th2=80)                     src/utils/img_utils.py:192-208 (cv.Canny, L2)
   smoothen_edges(edge_img, k_size=1, sigma=1)                         src/utils/img_utils.py:210-220
   eincm_inv_exp_dist_transform(edge_img, alpha=6)                      src/utils/img_utils.py:229-233
   rtef_inv_exp_dist_transform(edge_img, d_sat, alpha_iedt, formulation)   src/utils/img_utils.py:223-226, :236-410
+  frames_to_edges(images, ...)                                         the chain of src/experiments/e00/exp_mgr.py:334-350
 
-The Canny detector and the photometric clean-up in front of it (OpenCV, img_utils.py:131-207) are not part of this
-package: ``edge_img`` is the binary image they produce.  Everything here runs in libeincm_hip.so; no CPU fallback.
+The photometric clean-up in front of Canny (preprocess_image: NL-means, CLAHE, unsharp masking, bilateral filter;
+img_utils.py:131-189) is not part of this package; frames_to_edges accepts it as a caller-supplied callable.  Canny and the
+smoothing run in libeincm_hip.so; no CPU fallback.
 """
+import sys
+
 import numpy as np
 
-from .engine import Engine
+from .engine import Engine, check_canny_args
 
 _engines = {}
 
@@ -63,3 +69,46 @@ def smooth_edge_stack(edge_imgs, smoothen_edges_func=smoothen_edges, **kw):
     """exp_mgr.py:343-350 for a stack of binary edge images: smooth each, then min-max normalise each to [0, 1]."""
     from .staging import normalize_edges
     return normalize_edges([smoothen_edges_func(e, **kw) for e in edge_imgs])
+
+
+def to_canny_input(image):
+    """jnp_to_ocv_n255 (img_utils.py:87-93): the image as float32, cv.normalize(NORM_MINMAX) to [0, 255], then .astype(uint8).
+    cv.normalize takes scale = 255 * (1 / (max - min)), or 0 when max - min <= DBL_EPSILON, and shift = -min * scale (in double),
+    and converts with x * scale + shift; here that is float32 arithmetic with scale and shift rounded to float32, then numpy's
+    truncating cast.  Whether this equals OpenCV's float32 conversion bit for bit at pixels that land exactly on an integer is not
+    checked (no OpenCV to compare with)."""
+    x = np.asarray(image).astype(np.float32)
+    lo, hi = float(x.min()), float(x.max())
+    scale = 255.0 * (1.0 / (hi - lo)) if hi - lo > sys.float_info.epsilon else 0.0
+    shift = -lo * scale
+    return (x * np.float32(scale) + np.float32(shift)).astype(np.uint8)
+
+
+def image_to_edge(img, apert_size=3, th1=30, th2=80, engine=None):
+    """cv.Canny(img, th1, th2, None, apert_size, L2gradient=True) (img_utils.py:192-208) on the GPU.  img: (H,W) or (n,H,W)
+    uint8; returns 0 / 255 uint8 of the same shape.  Only apert_size 3 is implemented (the reference's only setting)."""
+    th1, th2, apert_size = check_canny_args(th1, th2, apert_size)
+    e = np.asarray(img)
+    eng = engine or _engine(e.shape[-2:])
+    return eng.canny(e, th1, th2, apert_size, l2_gradient=True)
+
+
+def _normalize_to_unit_range(a):
+    """img_utils.py:24-25."""
+    from .staging import EPSN
+    return (a - a.min()) / (a.max() - a.min() + EPSN)
+
+
+def frames_to_edges(images, image_to_edge_func=image_to_edge, smoothen_edges_func=smoothen_edges, preprocess_image_func=None,
+                    **smoothen_kw):
+    """exp_mgr.py:334-350 for a stack of grayscale frames: [preprocess_image_func] -> normalize_to_unit_range (float64) ->
+    to_canny_input -> image_to_edge_func -> smoothen_edges_func(**smoothen_kw) -> normalize_to_unit_range.  Returns the (R,H,W)
+    float64 stack in [0, 1].  image_to_edge (or a functools.partial of it) runs once for the whole stack."""
+    frames = [_normalize_to_unit_range(np.asarray(im if preprocess_image_func is None else preprocess_image_func(im)).astype(np.float64))
+              for im in images]
+    canny_in = np.stack([to_canny_input(f) for f in frames])
+    if image_to_edge_func is image_to_edge or getattr(image_to_edge_func, 'func', None) is image_to_edge:
+        edge_imgs = list(image_to_edge_func(canny_in))
+    else:
+        edge_imgs = [image_to_edge_func(c) for c in canny_in]
+    return smooth_edge_stack(edge_imgs, smoothen_edges_func, **smoothen_kw)

@@ -78,6 +78,19 @@ def check_window_size(window_size):
     return int(window_size)
 
 
+def check_canny_args(threshold1, threshold2, aperture_size):
+    """cv.Canny's arguments as eincm_canny takes them: finite, non-negative thresholds and aperture 3 (5, 7 and Scharr are not
+    implemented).  Checked before any GPU call."""
+    ths = []
+    for name, v in (('threshold1', threshold1), ('threshold2', threshold2)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0:
+            raise ValueError(f'{name} {v!r}: a finite, non-negative number')
+        ths.append(float(v))
+    if isinstance(aperture_size, bool) or not isinstance(aperture_size, (int, np.integer)) or int(aperture_size) != 3:
+        raise ValueError(f'aperture_size {aperture_size!r}: only 3 is implemented')
+    return ths[0], ths[1], 3
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                 full_aux=False, correlation_kind='mse'):
     """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
@@ -448,6 +461,23 @@ class Engine:
             raise ValueError(f'images must be ({self.H},{self.W}), got {a.shape[1:]}')
         out = np.empty_like(a)
         self._check(self._lib.eincm_gaussian_blur(self._ctx, _dp(a), a.shape[0], float(sigma), _dp(out)))
+        return out[0] if single else out
+
+    def canny(self, imgs, threshold1, threshold2, aperture_size=3, l2_gradient=True):
+        """cv.Canny(img, threshold1, threshold2, None, aperture_size, l2_gradient) (img_utils.py:192-208).
+        imgs: (n,H,W) or (H,W) uint8.  Returns the same shape, uint8 0 / 255."""
+        th1, th2, ap = check_canny_args(threshold1, threshold2, aperture_size)
+        a = np.asarray(imgs)
+        if a.dtype != np.uint8:
+            raise ValueError(f'Canny input must be uint8, got {a.dtype}')
+        single = a.ndim == 2
+        a = np.ascontiguousarray(a[None] if single else a)
+        if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
+            raise ValueError(f'images must be ({self.H},{self.W}), got {a.shape[1:]}')
+        out = np.empty_like(a)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.eincm_canny(self._ctx, a.ctypes.data_as(u8), a.shape[0], th1, th2, ap, 1 if l2_gradient else 0,
+                                          out.ctypes.data_as(u8)))
         return out[0] if single else out
 
     # -- device images ----------------------------------------------------------------------------

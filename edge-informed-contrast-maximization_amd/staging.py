@@ -6,8 +6,8 @@ Restates, for numpy inputs, the two rules of the reference that define the hot p
     clamped to the stream) and cut to the latest / earliest ``des_n_events`` events when long;
   * time normalisation (src/experiments/e00/exp_mgr.py:318-327): ``(t - t0) / (t1 - t0 + eps)`` for event and image
     timestamps, so events of the evaluation window land in [0, 1) and a grown window slightly outside it.
-Edge extraction itself (OpenCV chain, src/utils/img_utils.py:131-233) is out of scope; ``edges`` must arrive as the
-(R, H, W) float64 stack in [0, 1] that chain produces (exp_mgr.py:343-350); ``normalize_edges`` applies the last step.
+Edge extraction (exp_mgr.py:334-350) is edges.frames_to_edges: stage_datasample runs it on ``datasample['images']`` unless
+the caller passes ``edges``, a stack of smoothed edge images that ``normalize_edges`` takes through the chain's last step.
 """
 import sys
 
@@ -58,13 +58,20 @@ def normalize_edges(edge_images):
     return np.stack(out)
 
 
-def stage_datasample(datasample, edges):
+def stage_datasample(datasample, edges=None, **edge_kw):
     """The part of EINCMExperiment.stage_datasample (exp_mgr.py:278-376) that feeds the loss: returns
-    (xs:int16, ys:int16, ts:float64, edges:(R,H,W) float64, edge_ts:float64) ready for solver.set_datasample."""
+    (xs:int16, ys:int16, ts:float64, edges:(R,H,W) float64, edge_ts:float64) ready for solver.set_datasample.
+    edges None: built from datasample['images'] by edges.frames_to_edges(images, **edge_kw) (Canny and smoothing on the GPU).
+    Otherwise each given edge image is min-max normalised (normalize_edges), and edge_kw must be empty."""
+    if edges is not None and edge_kw:
+        raise TypeError(f'edge extraction arguments {sorted(edge_kw)} given with ready edges')
     ev = datasample['events']
     start_time, end_time = datasample['eval_ts_us'] if 'eval_ts_us' in datasample else datasample['eval_ts']
     ts, image_ts = normalize_times(ev['t'], datasample['image_ts'], float(start_time), float(end_time))
     from .engine import as_int16_coords       # rounds float coordinates half-to-even (event_warpers.py:29-30), range-checks
     xs = np.ascontiguousarray(as_int16_coords(ev['x'], 'x'))
     ys = np.ascontiguousarray(as_int16_coords(ev['y'], 'y'))
+    if edges is None:
+        from .edges import frames_to_edges
+        return xs, ys, ts, frames_to_edges(datasample['images'], **edge_kw), image_ts
     return xs, ys, ts, normalize_edges(edges), image_ts

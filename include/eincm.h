@@ -344,6 +344,14 @@ int eincm_inv_dist_transform(eincm_ctx* ctx, const uint8_t* edge_img, int n, int
  * (round(8 sigma + 1) | 1 taps), separable, BORDER_REFLECT_101.  src, dst (n, H, W) double; may alias. */
 int eincm_gaussian_blur(eincm_ctx* ctx, const double* src, int n, double sigma, double* dst);
 
+/* image_to_edge (img_utils.py:192-208): cv.Canny(src, threshold1, threshold2, None, aperture_size, l2_gradient) of 8-bit
+ * grayscale images - OpenCV's integer Canny (Sobel with BORDER_REPLICATE, sector NMS, hysteresis over 8-connected survivors;
+ * DESIGN.md section 13), exact.  src, dst (n, H, W) uint8, H x W = the context's sensor; dst is 0 / 255.  The thresholds are
+ * swapped if threshold1 > threshold2; negative or non-finite ones and n < 1 are EINCM_ERR_ARG, aperture_size != 3 is
+ * EINCM_ERR_UNSUPPORTED.  Integer work: fp32 and EINCM_CF_FP64 contexts give the same bytes. */
+int eincm_canny(eincm_ctx* ctx, const uint8_t* src, int n, double threshold1, double threshold2, int aperture_size, int l2_gradient,
+                uint8_t* dst);
+
 /* extract_tiles (img_utils.py:105-120) + compute_adaptive_* (contrast_objectives.py:42-87, correlation_objectives.py:105-130)
  * and their pairwise siblings (correlation_objectives.py:28-102), on the images of the LAST evaluation, per (window, ref):
  * contrast-type objectives on the raw IWE (as losses.py:70 does), pair-type ones on (edges, min-max-normalised IWE)
