@@ -38,6 +38,32 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// A segment list: the binned events of every (window, source tile) cut into segments of at most `seg` events (balanced_seg_len), the
+// event kernels' unit of work; their workgroups take the segments longest first (block_to_work).  Staging builds four lists over the
+// same bins (build_list): the gather's, the splat's, the splat's short one and the 2-DoF gather's.
+struct SegList {
+    int seg = 0;                       // events per segment
+    int n = 0;                         // segments
+    double tspan = 1.0;                // time span (fraction of the window) its LDS windows are sized for (build_list)
+    Item* d_items = nullptr;           // (max_items)
+    int32_t* d_order = nullptr;        // (max_items) the segments by decreasing length
+    std::vector<Item> h_items;         // host sides of the two (kept until the upload has completed); h_items only where the host cuts them
+    std::vector<int32_t> h_order;
+    int32_t* d_win_item0 = nullptr;    // (B + 1) first segment of every window: gather and 2-DoF gather lists
+    std::vector<int32_t> h_win_item0;  // its host copy, where the host cuts the segments
+    Window* d_wins = nullptr;          // (max_items, maxR) destination windows under the current theta: gather and splat lists
+    int32_t* d_itembase = nullptr;     // (B * ntiles) first segment of every (window, tile): gather and splat lists, device binning
+    // blocks of an event kernel: every (segment, reference time) pair, padded to a multiple of 8 segments (block_to_work)
+    unsigned grid(int R) const { return (unsigned)(((n + NXCD - 1) / NXCD) * NXCD * R); }
+};
+
+// LDS destination-window geometry chosen for one list in one evaluation (fit_window)
+struct WinFit {
+    int cap, maxw;                     // capacity (pixels) and largest width
+    bool pal;                          // bank-aligned row pitch (win_pitch)
+    bool fits;                         // the list's windows fit the largest capacity class
+};
+
 }  // namespace
 
 struct eincm_ctx {
@@ -45,50 +71,38 @@ struct eincm_ctx {
     int H = 0, W = 0, maxR = 0, maxB = 0;
     int64_t maxN = 0;
     uint32_t cflags = 0;
-    int seg = 0;                   // events per segment (0 = choose per batch); EINCM_SEG overrides
-    int seg_used = 0;
+    int seg = 0;                   // events per segment of the gather list (0 = choose per batch); EINCM_SEG overrides
+    int seg_s = 0;                 // ... of the splat list; EINCM_SEG_SPLAT overrides
     hipStream_t stream = nullptr;
     std::string err;
 
     // staged batch
     bool staged = false;
     Geom g{};
-    int n_items = 0;
     int64_t n_events = 0;
     std::vector<int64_t> win_events;
 
     // device buffers
     uint32_t* d_xy = nullptr;      // (maxN) x | y<<16, binned by (window, tile); the splat's copy: time order inside a tile, re-dealt in blocks of 256 (k_spread)
     double* d_t = nullptr;         // (maxN)
-    uint32_t* d_xy_g = nullptr;    // (maxN) the gather's copy: the same bins, every segment of d_items sorted by source pixel and dealt to its threads (k_segsort)
+    uint32_t* d_xy_g = nullptr;    // (maxN) the gather's copy: the same bins, every segment of the gather list sorted by source pixel and dealt to its threads (k_segsort)
     double* d_t_g = nullptr;       // (maxN)
-    Item* d_items = nullptr;       // (max_items) segments walked by k_gather / k_count / k_mask
-    Item* d_items_s = nullptr;     // (max_items) shorter segments walked by k_splat
-    int32_t* d_order = nullptr;    // (max_items) d_items by decreasing length: the order the event kernels' workgroups take them in
-    int32_t* d_order_s = nullptr;  // the same for d_items_s
-    std::vector<int32_t> h_order, h_order_s, h_tilecount;   // host sides of the two (kept until the upload has completed)
-    std::vector<int32_t> h_win_item0;                       // host copy of d_win_item0
-    Window* d_wins = nullptr;      // (max_items, maxR) destination windows of the gather segments under the current theta
-    Window* d_wins_s = nullptr;    // (max_items, maxR) ... of the splat segments
-    int n_items_s = 0; int seg_s = 0; int seg_s_used = 0;
-    // third list: the segments the 2-DoF gather walks, on the SPLAT's copy of the events (it has no per-pixel accumulators, so the
-    // time-ordered copy serves it, and it wants shorter segments than the theta-grid gather does: round-2 tuning)
-    Item* d_items_2 = nullptr; int32_t* d_order_2 = nullptr; int32_t* d_win_item0_2 = nullptr;
+    std::vector<int32_t> h_tilecount;   // (B, ntiles) events per (window, tile) of the staged batch: what every segment list is cut from
+    SegList gather;                // walked by k_gather / k_count / k_mask / the fp64 kernels, on the gather's copy of the events
+    SegList splat;                 // shorter segments walked by k_splat
+    SegList splat_sh;              // the splat's SHORT list (8192) beside a 16384-event one: a 2-DoF theta too large for the long segments' windows walks it (launch_forward)
+    // the segments the 2-DoF gather walks, on the SPLAT's copy of the events (it has no per-pixel accumulators, so the time-ordered copy
+    // serves it, and it wants shorter segments than the theta-grid gather does: round-2 tuning)
+    SegList gather_2;
     bool policy_evaluated = false; // an evaluation has chosen capacities since the last staging (eincm_get_launch_policy)
     int pitch_policy = 0;          // the staged batch is in the regime where the bank-aligned LDS pitch pays (set_windows_impl); eval_begin decides per evaluation
-    double tspan_s = 1.0, tspan_sh = 1.0, tspan_a = 1.0, tspan_2 = 1.0;   // time span (fraction of the window) the window capacity is sized for, per segment list (span_quantile)
-    Item* d_items_sh = nullptr; int32_t* d_order_sh = nullptr; int n_items_sh = 0; int seg_sh_used = 0;   // the splat's SHORT list (8192) beside a 16384-event
-                                                                       // one: a 2-DoF theta too large for the long segments' windows walks it (launch_forward)
-    int n_items_2 = 0; int seg_2_used = 0;
-    std::vector<int32_t> h_order_2, h_win_item0_2;
-    int wincap_2 = WIN_CAP_DEFAULT;
     int wincap = WIN_CAP_DEFAULT;
     bool wincap_fixed = false;     // EINCM_WINCAP pins the capacity; otherwise it is chosen per evaluation from max|theta|
     // device-side staging (eincm_binning.hip.h)
     int16_t* d_raw_x = nullptr; int16_t* d_raw_y = nullptr; double* d_raw_t = nullptr;   // (maxN) events as handed over
     BinBlock* d_binblocks = nullptr; int32_t* d_win_blk = nullptr; uint32_t* d_blockhist = nullptr;
-    int32_t* d_tilecount = nullptr; int32_t* d_tilebase = nullptr; int32_t* d_itembase = nullptr; int32_t* d_itembase_s = nullptr; int32_t* d_bin_misc = nullptr;
-    bool itembase_valid = false;   // d_itembase / d_itembase_s hold the first segment of every (window, tile) for the staged batch
+    int32_t* d_tilecount = nullptr; int32_t* d_tilebase = nullptr; int32_t* d_bin_misc = nullptr;
+    bool itembase_valid = false;   // the gather and splat lists' d_itembase hold the first segment of every (window, tile) for the staged batch
     double* d_edges_raw = nullptr; double* d_edge_moments = nullptr;
     int64_t max_binblocks = 0;
     bool host_binning = false;
@@ -103,7 +117,6 @@ struct eincm_ctx {
     double* d_theta_in = nullptr;  // (B,H,W,2) capacity (coarse uses a prefix)
     long long* d_gTheta = nullptr; // (B,H,W,2) i64 fixed point, zero between evaluations (k_project / k_final_dense clear it)
     double* d_g11 = nullptr;       // (max_items, R, 2) 2-DoF theta: per-workgroup partials of dL/dtheta (k_gather -> k_final)
-    int32_t* d_win_item0 = nullptr;// (B) first segment of each window in d_items
     double* d_dtmax = nullptr;     // (B) staging scratch: max |t - tau| per window
     unsigned* d_gmax = nullptr;    // (B,R,nig) per-strip max |dL/dIWE| as float bits (scale of the i64 gradient accumulators)
     unsigned* d_cntmax = nullptr;  // (B) staging scratch: most events on one source pixel
@@ -184,8 +197,8 @@ struct eincm_ctx {
     int last_nparts = 0;           // how many StatParts per image the last evaluation wrote (k_stats vs k_stats_stream)
     // an evaluation split in two halves (eval_begin ... [caller may all-reduce the IWE stack] ... eval_end)
     struct { bool active = false; bool launched = false; EvalParams ep{}; int h = 0, w = 0; bool identity = false, want_grad = false, full_aux = false, div_grad = false;
-             bool pal_2 = false;                    // the 2-DoF gather's windows at the bank-aligned pitch in this evaluation
-             bool splat_short = false;              // this evaluation's k_splat walks the short segment list (d_items_sh)
+             WinFit win_2{};                        // the 2-DoF gather's windows in this evaluation
+             bool splat_short = false;              // this evaluation's k_splat walks the short segment list (splat_sh)
              bool host_asm = false;                 // scalar assembly and the 2-DoF gradient sum on the host (see h_g11)
              bool tv_projected = false;             // k_tv projected its gradient onto the theta cells itself (no k_project for it)
              int copy_mode = 0;                     // 1: the D2H copies of the results are still to be enqueued (device_results)
@@ -317,9 +330,10 @@ void multi_ref_weights(int R, double* w) {
 
 void free_all(eincm_ctx* c) {
     auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->d_xy); F(c->d_t); F(c->d_xy_g); F(c->d_t_g); F(c->d_items); F(c->d_items_s); F(c->d_items_2); F(c->d_order_2); F(c->d_win_item0_2); F(c->d_items_sh); F(c->d_order_sh); F(c->d_order); F(c->d_order_s); F(c->d_wins); F(c->d_wins_s); F(c->d_raw_x); F(c->d_raw_y); F(c->d_raw_t); F(c->d_binblocks); F(c->d_win_blk);
-    F(c->d_blockhist); F(c->d_tilecount); F(c->d_tilebase); F(c->d_itembase); F(c->d_itembase_s); F(c->d_bin_misc); F(c->d_edges_raw); F(c->d_edge_moments); F(c->d_edges); F(c->d_edge_ts); F(c->d_acc); F(c->d_iwe); F(c->d_G); F(c->d_zero_iwe);
-    F(c->d_g11); F(c->d_win_item0); F(c->d_dtmax); F(c->d_gmax); F(c->d_cntmax); F(c->d_gticket);
+    F(c->d_xy); F(c->d_t); F(c->d_xy_g); F(c->d_t_g); F(c->d_raw_x); F(c->d_raw_y); F(c->d_raw_t); F(c->d_binblocks); F(c->d_win_blk);
+    for (SegList* L : {&c->gather, &c->splat, &c->splat_sh, &c->gather_2}) { F(L->d_items); F(L->d_order); F(L->d_win_item0); F(L->d_wins); F(L->d_itembase); }
+    F(c->d_blockhist); F(c->d_tilecount); F(c->d_tilebase); F(c->d_bin_misc); F(c->d_edges_raw); F(c->d_edge_moments); F(c->d_edges); F(c->d_edge_ts); F(c->d_acc); F(c->d_iwe); F(c->d_G); F(c->d_zero_iwe);
+    F(c->d_g11); F(c->d_dtmax); F(c->d_gmax); F(c->d_cntmax); F(c->d_gticket);
     F(c->d_Theta); F(c->d_theta_in); F(c->d_gTheta); F(c->d_tvg); F(c->d_mask); F(c->d_tmm); F(c->d_parts);
     F(c->d_divparts); F(c->d_g2parts); F(c->d_gdiv); F(c->d_dgparts); F(c->d_tvparts); F(c->d_wc); F(c->d_outs); c->d_grad = nullptr; F(c->d_gth); F(c->d_AH); F(c->d_AW);
     F(c->d_rowtap); F(c->d_coltap); F(c->d_tilerng);
@@ -433,47 +447,25 @@ int ensure_resample(eincm_ctx* c, int h, int w, int method) {
 
 constexpr size_t ZERO_COPY_MAX = 65536;   // doubles of theta / gradient that cross PCIe by zero-copy access to pinned host memory (a 64-window batch at 16x16: 32768)
 
-// The event kernels' workgroups take the segments by decreasing length (block_to_work): stable counting sort of the lengths.
-void order_by_length(const std::vector<int32_t>& lens, std::vector<int32_t>& order) {
-    int32_t maxlen = 0;
-    for (int32_t l : lens) maxlen = std::max(maxlen, l);
-    std::vector<int32_t> start((size_t)maxlen + 2, 0);
-    for (int32_t l : lens) ++start[(size_t)(maxlen - l) + 1];
-    for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
-    order.resize(lens.size());
-    for (size_t i = 0; i < lens.size(); ++i) order[(size_t)start[(size_t)(maxlen - lens[i])]++] = (int32_t)i;
-}
-// segment lengths of a (window, tile) population list, in the order k_items emits the segments
-void segment_lengths(const std::vector<int32_t>& tilecount, int seg, std::vector<int32_t>& lens) {
-    lens.clear();
-    for (int32_t cnt : tilecount) {
-        const int len = balanced_seg_len(cnt, seg);
-        for (int s0 = 0; s0 < cnt; s0 += len) lens.push_back(std::min(len, cnt - s0));
-    }
-}
 
-// A segment list from the (window, tile) populations, the way k_items emits it (time ranges left to k_seg_minmax); win_item0: first
-// segment of every window.
-void host_items(const std::vector<int32_t>& tilecount, int ntiles, int seg, std::vector<Item>& items, std::vector<int32_t>& win_item0) {
-    items.clear(); win_item0.clear();
-    int64_t base = 0;
-    for (size_t idx = 0; idx < tilecount.size(); ++idx) {
-        if (idx % (size_t)ntiles == 0) win_item0.push_back((int32_t)items.size());
-        const int cnt = tilecount[idx];
-        const int len = balanced_seg_len(cnt, seg);
-        for (int s0 = 0; s0 < cnt; s0 += len) {
-            Item it;
-            it.win = (int32_t)(idx / (size_t)ntiles); it.tile = (int32_t)(idx % (size_t)ntiles);
-            it.begin = (int32_t)(base + s0); it.count = std::min(len, cnt - s0); it.t_lo = 0.0; it.t_hi = 0.0;
-            items.push_back(it);
-        }
-        base += cnt;
-    }
-}
+// largest width of an LDS destination window of `cap` pixels (Geom.winmaxw)
+int win_maxw(int cap) { return std::max(40, (int)std::lround(std::sqrt((double)cap * 1.4))); }
 
-// blocks of the two event kernels: every (segment, reference time) pair, padded to a multiple of 8 segments (block_to_work)
-unsigned event_grid(const eincm_ctx* c) { return (unsigned)(((c->n_items + NXCD - 1) / NXCD) * NXCD * c->g.R); }
-unsigned splat_grid(const eincm_ctx* c) { return (unsigned)(((c->n_items_s + NXCD - 1) / NXCD) * NXCD * c->g.R); }
+// LDS window capacity for the segments of one list, chosen per evaluation (eval_begin): the host knows theta, hence the largest
+// displacement (vmax * tspan) a segment of the list can see; the window's side is the tile plus that plus the splat's margin.
+// LDS holds pitch x height words per window, the pitch being the width, or the width rounded up to the 32 banks (win_pitch).
+// pitch: 1 takes the aligned pitch where it does not push the window into a larger capacity class (its gain is a few per cent of
+// bank conflicts, a class costs workgroups per CU: 8 windows of 10^6 events whose theta needs 66-pixel windows: 96 x 66 words = the
+// 6912 class, 5 workgroups per CU, 2-DoF gather 62 -> 68 us); 0 keeps pitch = width; -1 too, sized on the unrounded side (the
+// theta-grid gather's rule).  floor_k: the smallest capacity class the list takes.
+WinFit fit_window(double vmax, double tspan, double margin, int floor_k, int pitch) {
+    static const int caps[] = {2304, 3072, 4608, 6912};      // 6912 keeps k_gather's LDS (window + accumulators + Theta tile) under 64 KiB
+    const double side = TS + margin + vmax * tspan, sd = std::ceil(side);
+    const double need = pitch < 0 ? side * side : sd * sd;
+    int cap = caps[3];
+    for (int k = floor_k; k < 4; ++k) if (need <= caps[k]) { cap = caps[k]; break; }
+    return WinFit{cap, win_maxw(cap), pitch > 0 && std::ceil(sd / 32.0) * 32.0 * sd <= (double)cap, need <= (double)caps[3]};
+}
 
 // Every cross-workgroup accumulator (u64 IWE stack, i64 dL/dTheta, i64 coarse cells) is zero between evaluations because its
 // consumer clears it.  If a forward half was launched and never consumed (error between the two halves), clear them here.
@@ -494,8 +486,8 @@ void launch_theta_image(eincm_ctx* c, int h, int w, bool identity, bool use_arg,
     const bool ww = with_windows && c->itembase_valid;
 #define THETA_ARGS(T_) dim3(g.ntiles, g.B), dim3(NT), 0, g, h, w, identity ? 1 : 0, use_arg ? 1 : 0, T_, \
                  theta_dev, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_tilerng, c->d_Theta, c->d_tmm, c->d_edge_ts, \
-                 c->n_items, c->d_items, ww ? c->d_itembase : nullptr, c->d_wins, \
-                 c->n_items_s, c->d_items_s, ww ? c->d_itembase_s : nullptr, c->d_wins_s
+                 c->gather.n, c->gather.d_items, ww ? c->gather.d_itembase : nullptr, c->gather.d_wins, \
+                 c->splat.n, c->splat.d_items, ww ? c->splat.d_itembase : nullptr, c->splat.d_wins
     // the argument block is copied by value into the launch and again into the kernarg buffer: 4 KiB where theta fits (one window at 16x16)
     if (!use_arg || (size_t)g.B * h * w * 2 <= (size_t)THETA_ARG_MID) {
         ThetaArgMid mid;
@@ -550,7 +542,8 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
     }
     {
         StageTimer t(c, EINCM_STAGE_THETA, const_theta ? !need_theta_image : c->itembase_valid);       // one kernel in either case
-        const int nwin_threads = (c->n_items + c->n_items_s) * g.R;
+        const SegList &ga = c->gather, &sp = c->splat;
+        const int nwin_threads = (ga.n + sp.n) * g.R;
         if (const_theta) {
             if (theta_host) c->last_theta11.assign(theta_host, theta_host + (size_t)g.B * 2); else c->last_theta11.clear();
             c->Theta_valid = false;
@@ -559,28 +552,24 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
             // which a host-assembled evaluation does on the host
             if (!host_asm)
                 launch_timed(c, EINCM_STAGE_THETA, k_theta_const, dim3((std::max(g.B * g.ntiles, nwin_threads) + NT - 1) / NT), dim3(NT), 0, g,
-                                   use_arg ? 1 : 0, targ, theta_dev, c->d_tmm, c->d_edge_ts, c->n_items, c->d_items, c->d_wins,
-                                   c->n_items_s, c->d_items_s, c->d_wins_s);
+                                   use_arg ? 1 : 0, targ, theta_dev, c->d_tmm, c->d_edge_ts, ga.n, ga.d_items, ga.d_wins,
+                                   sp.n, sp.d_items, sp.d_wins);
         } else {
             launch_theta_image(c, h, w, identity, use_arg_big, targ_big, theta_dev, true);
             if (nwin_threads > 0 && !c->itembase_valid)
                 hipLaunchKernelGGL(k_windows, dim3((nwin_threads + NT - 1) / NT), dim3(NT), 0, c->stream, g, c->d_tmm, c->d_edge_ts,
-                                   c->n_items, c->d_items, c->d_wins, c->n_items_s, c->d_items_s, c->d_wins_s);
+                                   ga.n, ga.d_items, ga.d_wins, sp.n, sp.d_items, sp.d_wins);
         }
     }
     {
         StageTimer t(c, EINCM_STAGE_SPLAT, true);
         c->acc_dirty = true;
-        if (c->n_items_s > 0) {
+        if (c->splat.n > 0) {
             const int theta_mode = const_theta ? THETA_CONST : THETA_TILE;
             const size_t lds_bytes = (size_t)g.wincap * sizeof(float) + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
-            const bool sshort = c->pend.splat_short && const_theta;
-            const int n_sp = sshort ? c->n_items_sh : c->n_items_s;
-            const Item* items_sp = sshort ? c->d_items_sh : c->d_items_s;
-            const int32_t* order_sp = sshort ? c->d_order_sh : c->d_order_s;
-            const unsigned grid_sp = (unsigned)(((n_sp + NXCD - 1) / NXCD) * NXCD * g.R);
-#define SPLAT_ARGS(NTH) dim3(grid_sp), dim3(NTH), lds_bytes, g, n_sp, \
-                   items_sp, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->d_wins_s, c->d_acc, order_sp, \
+            const SegList& L = c->pend.splat_short && const_theta ? c->splat_sh : c->splat;      // (2-DoF theta derives its windows itself)
+#define SPLAT_ARGS(NTH) dim3(L.grid(g.R)), dim3(NTH), lds_bytes, g, L.n, \
+                   L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, L.d_order, \
                    use_arg ? 1 : 0, theta_dev, targ
             // 512 threads per workgroup in both compile-time modes: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
             // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
@@ -588,10 +577,10 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
                 // another splat window (eincm_splat_window.hip.h): u64 LDS windows, capped so that they fit beside the Theta tile
                 Geom gs = g;
                 gs.wincap = std::min(g.wincap, theta_mode == THETA_TILE ? SW_CAP_TILE : SW_CAP_CONST);
-                gs.winmaxw = std::max(40, (int)std::lround(std::sqrt((double)gs.wincap * 1.4)));
+                gs.winmaxw = win_maxw(gs.wincap);
                 const size_t lds_r = (size_t)gs.wincap * sizeof(unsigned long long) + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
-#define SPLAT_R_ARGS dim3(grid_sp), dim3(NT), lds_r, gs, n_sp, items_sp, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_acc, \
-                     order_sp, use_arg ? 1 : 0, theta_dev, targ
+#define SPLAT_R_ARGS dim3(L.grid(g.R)), dim3(NT), lds_r, gs, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_acc, \
+                     L.d_order, use_arg ? 1 : 0, theta_dev, targ
 #define SPLAT_R(TM_) do { if (c->splat_rad == 0) launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 0>, SPLAT_R_ARGS); \
                           else if (c->splat_rad == 2) launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 2>, SPLAT_R_ARGS); \
                           else launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 3>, SPLAT_R_ARGS); } while (0)
@@ -656,8 +645,9 @@ int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalP
     HIPCHK(c, hipMemsetAsync(c->f64.bad, 0, (size_t)g.B * sizeof(unsigned), c->stream));
     // both event kernels walk the gather's list and copy of the events (sorted by source pixel; the splat's spread copy measured
     // slower with these global atomics: 13.6 vs 10.9 ms of k64_splat on the bench batch, profiles/r04/fp64_mode.txt)
-    if (c->n_items > 0)
-        hipLaunchKernelGGL(k64_splat, dim3(event_grid(c)), dim3(NT), 0, c->stream, g, c->n_items, c->d_items, c->d_xy_g, c->d_t_g, c->d_Theta,
+    const SegList& L = c->gather;
+    if (L.n > 0)
+        hipLaunchKernelGGL(k64_splat, dim3(L.grid(g.R)), dim3(NT), 0, c->stream, g, L.n, L.d_items, c->d_xy_g, c->d_t_g, c->d_Theta,
                            c->d_edge_ts, c->f64.ishift, c->f64.acc);
     const dim3 gimg(c->f64.P, g.R, g.B);
     hipLaunchKernelGGL(k64_img_a, gimg, dim3(NT), 0, c->stream, g, c->f64.ishift, c->f64.acc, c->f64.iwe, c->f64.partA);
@@ -674,8 +664,8 @@ int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalP
                            div_grad ? c->f64.sgn : nullptr, c->f64.G, c->f64.partC);
         hipLaunchKernelGGL(k64_grad2, gimg, dim3(NT), 0, c->stream, g, c->f64.iwe, c->f64.scal, c->f64.partC, c->f64.G, c->f64.gmax,
                            c->f64.bad);
-        if (c->n_items > 0)
-            hipLaunchKernelGGL(k64_gather, dim3(c->n_items), dim3(NT), 0, c->stream, g, c->n_items, c->d_items, c->d_xy_g, c->d_t_g,
+        if (L.n > 0)
+            hipLaunchKernelGGL(k64_gather, dim3(L.n), dim3(NT), 0, c->stream, g, L.n, L.d_items, c->d_xy_g, c->d_t_g,
                                c->d_Theta, c->d_edge_ts, c->f64.G, c->d_wc, c->f64.gmax, c->f64.gacc, c->f64.bad);
         const unsigned nblk = (unsigned)std::min<size_t>((img * 2 + NT - 1) / NT, 512);
         hipLaunchKernelGGL(k64_gfin, dim3(nblk, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, ep.gamma, c->d_tvparts, c->d_tvg, c->d_wc,
@@ -916,7 +906,7 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
     // Small windows give 8 workgroups per CU; windows too small for the flow push taps onto the slow direct-to-HBM path.
     c->policy_evaluated = true;
     c->pend.splat_short = false;
-    c->pend.pal_2 = c->pitch_policy >= 2;            // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
+    c->pend.win_2 = WinFit{c->wincap, win_maxw(c->wincap), c->pitch_policy >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
     c->g.pitch_aligned = c->pitch_policy != 0 ? 1 : 0;
     if (!c->wincap_fixed) {
         double vmax = 0.0;
@@ -925,47 +915,29 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         if (c->theta_dev_in) vmax = (c->vmax_hint >= 0.0 && std::isfinite(c->vmax_hint)) ? c->vmax_hint : 1e9;      // unknown: the largest windows
         else if (stride == 1) { for (size_t i = 0; i < nall; ++i) { const double a = std::fabs(theta_host[i]); vmax = std::max(vmax, a <= 1.7e308 ? a : 0.0); } }   // (vectorises)
         else for (size_t i = 0; i < nall; i += stride) { const double a = std::fabs(theta_host[i]); if (a > vmax && std::isfinite(a)) vmax = a; }
-        // time span the splat's windows are sized for: what all but 3 % of the events' segments stay within (span_quantile; the mean tile
-        // would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
-        const double tspan = c->tspan_s;
-        // LDS holds pitch x height words per window, the pitch being the width, or the width rounded up to the 32 banks (win_pitch).
-        // The aligned pitch is taken where the batch is in its regime (pitch_policy) AND it does not push the window into a larger
-        // capacity class: its gain is a few per cent of bank conflicts, a class costs workgroups per CU (8 windows of 10^6 events whose
-        // theta needs 66-pixel windows: 96 x 66 words = the 6912 class, 5 workgroups per CU, 2-DoF gather 62 -> 68 us).
-        auto lds_words = [](bool pal, double side_px) { const double sd = std::ceil(side_px); return (pal ? std::ceil(sd / 32.0) * 32.0 : sd) * sd; };
-        static const int caps[] = {2304, 3072, 4608, 6912};      // 6912 keeps k_gather's LDS (window + accumulators + Theta tile) under 64 KiB
-        auto cap_of = [&](double need, int floor_k) { for (int k = floor_k; k < 4; ++k) if (need <= caps[k]) return caps[k]; return caps[3]; };
         // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
         const double margin = 2.0 * (c->splat_rad + 1);
-        double side = TS + margin + vmax * tspan;
         const bool two_dof = h == 1 && w == 1 && !identity;
-        // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
-        // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
-        c->pend.splat_short = (two_dof && c->n_items_sh > 0 && lds_words(false, side) > 6912.0);
-        if (c->pend.splat_short) side = TS + margin + vmax * c->tspan_sh;
         // Where a larger window costs no residency it is taken at once (a capacity is an allocation, the windows themselves stay as small
         // as their segments need): the 2-DoF kernels hold nothing but the window in LDS, 4608 words = 18 KiB still gives the 8 workgroups
         // of 4 waves a CU can hold; the theta-grid gather carries 32 KiB beside its window and runs 3 workgroups per CU up to 5461 words.
         // The theta-grid splat (window + 16 KiB Theta tile) pays for capacity with workgroups per CU (6 / 5 / 4 / 3), so it takes what it needs.
-        const int floor_k = two_dof ? 2 : 0;
-        int cap = cap_of(lds_words(false, side), floor_k);
-        const bool pal_s = c->pitch_policy != 0 && lds_words(true, side) <= (double)cap;
-        c->g.wincap = cap;
-        c->g.winmaxw = std::max(40, (int)std::lround(std::sqrt((double)cap * 1.4)));
-        c->g.pitch_aligned = pal_s ? 1 : 0;
+        // Each list's windows are sized for its time span: what all but 3 % of the events' segments stay within (build_list; the mean
+        // tile would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
+        const int floor_s = two_dof ? 2 : 0, pitch_s = c->pitch_policy != 0 ? 1 : 0;
+        WinFit s = fit_window(vmax, c->splat.tspan, margin, floor_s, pitch_s);
+        // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
+        // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
+        c->pend.splat_short = two_dof && c->splat_sh.n > 0 && !s.fits;
+        if (c->pend.splat_short) s = fit_window(vmax, c->splat_sh.tspan, margin, floor_s, pitch_s);
+        c->g.wincap = s.cap; c->g.winmaxw = s.maxw; c->g.pitch_aligned = s.pal ? 1 : 0;
         // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
         // sends taps down the direct path
-        const double side_a = TS + margin + vmax * c->tspan_a;
-        const int cap_a = cap_of(side_a * side_a, 2);          // (the theta-grid gather's windows: pitch = width)
-        c->g.wincap_a = cap_a;
-        c->g.winmaxw_a = std::max(40, (int)std::lround(std::sqrt((double)cap_a * 1.4)));
-        // and the 2-DoF gather's list
-        const double side_2 = TS + margin + vmax * c->tspan_2;
-        const int cap_2 = cap_of(lds_words(false, side_2), 2);
-        // (the 2-DoF gather keeps pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another batch
-        // of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
-        c->pend.pal_2 = c->pitch_policy >= 2 && lds_words(true, side_2) <= (double)cap_2;
-        c->wincap_2 = cap_2;
+        const WinFit a = fit_window(vmax, c->gather.tspan, margin, 2, -1);
+        c->g.wincap_a = a.cap; c->g.winmaxw_a = a.maxw;
+        // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
+        // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
+        c->pend.win_2 = fit_window(vmax, c->gather_2.tspan, margin, 2, c->pitch_policy >= 2 ? 1 : 0);
     }
     // 2-DoF theta with nothing but the contrast and correlation terms (every level above 0 of the reference's pyramid at its first
     // level, and the bench workload): the scalar assembly and the sum of the gather's per-workgroup partials run on the host
@@ -1132,41 +1104,35 @@ int eval_end_launch(eincm_ctx* c) {
             StageTimer t(c, EINCM_STAGE_GATHER, true);
             // 44 KB of LDS (G window + i64 accumulators + Theta tile) fit 3 workgroups per CU: 512 threads each keep 24 waves there
             constexpr int NT_TILE = 512;
-            if (c->n_items > 0) {
-                // Theta grids / dense theta: the gather walks whichever segment list has the longer segments (its per-workgroup
-                // costs - Theta tile, accumulator clear and flush - want them long even for one window, where the 2-DoF gather
-                // wants 4096); nothing downstream depends on the list (the per-segment partials are a 2-DoF matter).
-                // Theta grids / dense theta: the gather walks its own segment list (long segments) on its own copy of the events
-                // (k_segsort); 2-DoF theta: its third list (shorter segments) on the splat's copy
-                const int n_g = direct11 ? c->n_items_2 : c->n_items;
-                const Item* items_g = direct11 ? c->d_items_2 : c->d_items;
-                const Window* wins_g = c->d_wins;                  // (2-DoF theta derives its windows itself)
-                const int32_t* order_g = direct11 ? c->d_order_2 : c->d_order;
+            if (c->gather.n > 0) {
+                // Theta grids / dense theta: the gather walks its own segment list (long segments: its per-workgroup costs - Theta tile,
+                // accumulator clear and flush - want them long even for one window) on its own copy of the events (k_segsort); 2-DoF
+                // theta: the 2-DoF gather list (shorter segments) on the splat's copy, deriving its windows itself (no window table)
+                const SegList& L = direct11 ? c->gather_2 : c->gather;
                 const uint32_t* xy_g = direct11 ? c->d_xy : c->d_xy_g;
                 const double* t_g = direct11 ? c->d_t : c->d_t_g;
                 Geom gg = g;
-                if (direct11) { gg.pitch_aligned = c->pend.pal_2 ? 1 : 0; gg.wincap_a = c->wincap_2; gg.winmaxw_a = std::max(40, (int)std::lround(std::sqrt((double)c->wincap_2 * 1.4))); }
+                if (direct11) { gg.pitch_aligned = c->pend.win_2.pal ? 1 : 0; gg.wincap_a = c->pend.win_2.cap; gg.winmaxw_a = c->pend.win_2.maxw; }
                 // theta grids with the in-gather projection on big launches: one workgroup per segment for all reference times (k_gather, all_r)
                 static const int all_r_env = getenv("EINCM_GATHER_ALL_R") ? atoi(getenv("EINCM_GATHER_ALL_R")) : -1;
                 // (8 windows of 10^6 events at 16x16: 792 workgroups of 5 reference times each instead of 3960: 148 -> 135 us; one window:
                 // 99 workgroups, 29 -> 84 us - so only where the segments alone fill the chip's 768 workgroup slots of this kernel)
-                int all_r = (!direct11 && proj && !identity && n_g >= 700) ? 1 : 0;
+                int all_r = (!direct11 && proj && !identity && L.n >= 700) ? 1 : 0;
                 if (all_r_env >= 0) all_r = (all_r_env && !direct11 && proj && !identity) ? 1 : 0;
-                const unsigned grid_g = (unsigned)(((n_g + NXCD - 1) / NXCD) * NXCD * (all_r ? 1 : g.R));
-#define GATHER_ARGS(NTH) dim3(grid_g), dim3(NTH), \
+#define GATHER_ARGS(NTH) dim3(L.grid(all_r ? 1 : g.R)), dim3(NTH), \
                     gg.wincap_a * sizeof(float) + (direct11 ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2)), \
-                    gg, n_g, items_g, xy_g, t_g, c->d_Theta, c->d_edge_ts, c->d_G, wins_g, c->d_gTheta, \
-                    host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, order_g, \
+                    gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, \
+                    host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, L.d_order, \
                     c->pend.use_arg ? 1 : 0, c->pend.theta_dev, c->pend.targ, \
                     h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth, (int)c->coarse_cap, \
-                    (host_asm && proj) ? 1 : 0, c->d_gticket, c->d_win_item0, c->h_grad, \
+                    (host_asm && proj) ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad, \
                     (host_asm && proj && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap
 #define GATHER_TILE(WIDE_, PROJ_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, PROJ_>, GATHER_ARGS(NT_TILE))
 #define GATHER_ALLR(WIDE_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, 1, 1>, GATHER_ARGS(NT_TILE))
                 if (c->splat_rad != 1) {
                     // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
                     const size_t lds_r = gg.wincap_a * sizeof(float) + (direct11 ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2));
-#define GATHER_R_ARGS dim3((unsigned)(((n_g + NXCD - 1) / NXCD) * NXCD * g.R)), dim3(NT), lds_r, gg, n_g, items_g, xy_g, t_g, c->d_Theta, \
+#define GATHER_R_ARGS dim3(L.grid(g.R)), dim3(NT), lds_r, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, \
                       c->d_tmm, c->d_edge_ts, c->d_G, c->d_gTheta, host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, wide ? 1 : 0, \
                       c->pend.use_arg ? 1 : 0, c->pend.theta_dev, c->pend.targ
 #define GATHER_R(TM_) do { if (c->splat_rad == 0) launch_timed(c, EINCM_STAGE_GATHER, k_gather_r<TM_, 0>, GATHER_R_ARGS); \
@@ -1207,7 +1173,7 @@ int eval_end_launch(eincm_ctx* c) {
         // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
         launch_timed(c, EINCM_STAGE_FINAL, k_final, dim3(g.B), dim3(FT), 0, g, ep, c->d_parts, c->d_divparts, c->d_tvparts,
                            c->d_tmm, c->d_wc, g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
-                           c->d_g11, c->d_win_item0_2, c->n_items_2, c->d_gmax,
+                           c->d_g11, c->gather_2.d_win_item0, c->gather_2.n, c->d_gmax,
                            zero_copy_out ? c->h_outs : c->d_outs, zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
         if (want_grad && identity) {
             hipLaunchKernelGGL(k_final_dense, dim3(256, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, wide ? 1 : 0, c->d_gTheta,
@@ -1271,7 +1237,7 @@ void host_assemble(eincm_ctx* c) {
         o.value = val; o.tv_scale = 0.0;
         o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
         if (c->pend.h == 1 && c->pend.w == 1) {              // 2-DoF: the gather's per-workgroup partials, added in index order
-            const int lo = c->h_win_item0_2[b], hi = c->h_win_item0_2[b + 1];
+            const int lo = c->gather_2.h_win_item0[b], hi = c->gather_2.h_win_item0[b + 1];
             const double* p = c->h_g11 + (size_t)lo * g.R * 2;
             const size_t n = (size_t)(hi - lo) * g.R;
             // four interleaved chains per component (a fixed association, so still a function of the partials alone): one chain is
@@ -1496,18 +1462,16 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     TRY(dalloc(&c->d_t, (size_t)max_events_total));
     TRY(dalloc(&c->d_xy_g, (size_t)max_events_total));
     TRY(dalloc(&c->d_t_g, (size_t)max_events_total));
-    TRY(dalloc(&c->d_items, (size_t)c->max_items));
-    TRY(dalloc(&c->d_items_s, (size_t)c->max_items));
-    TRY(dalloc(&c->d_order, (size_t)c->max_items));
-    TRY(dalloc(&c->d_order_s, (size_t)c->max_items));
-    TRY(dalloc(&c->d_items_2, (size_t)c->max_items));
-    TRY(dalloc(&c->d_items_sh, (size_t)c->max_items));
-    TRY(dalloc(&c->d_order_sh, (size_t)c->max_items));
-    TRY(dalloc(&c->d_order_2, (size_t)c->max_items));
-    TRY(dalloc(&c->d_win_item0_2, B + 1));
-    TRY(dalloc(&c->d_wins, (size_t)c->max_items * max_refs));
-    TRY(dalloc(&c->d_wins_s, (size_t)c->max_items * max_refs));
     c->host_binning = (ntiles > BIN_MAX_TILES) || (getenv("EINCM_HOST_BINNING") != nullptr);
+    for (SegList* L : {&c->gather, &c->splat, &c->splat_sh, &c->gather_2}) {
+        TRY(dalloc(&L->d_items, (size_t)c->max_items));
+        TRY(dalloc(&L->d_order, (size_t)c->max_items));
+    }
+    for (SegList* L : {&c->gather, &c->gather_2}) TRY(dalloc(&L->d_win_item0, B + 1));
+    for (SegList* L : {&c->gather, &c->splat}) {
+        TRY(dalloc(&L->d_wins, (size_t)c->max_items * max_refs));
+        if (!c->host_binning) TRY(dalloc(&L->d_itembase, B * ntiles));
+    }
     TRY(dalloc(&c->d_raw_x, (size_t)max_events_total));          // kept after staging: eincm_get_warped_events walks them
     TRY(dalloc(&c->d_raw_y, (size_t)max_events_total));
     TRY(dalloc(&c->d_raw_t, (size_t)max_events_total));
@@ -1518,8 +1482,6 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
         TRY(dalloc(&c->d_blockhist, (size_t)c->max_binblocks * ntiles));
         TRY(dalloc(&c->d_tilecount, B * ntiles));
         TRY(dalloc(&c->d_tilebase, B * ntiles));
-        TRY(dalloc(&c->d_itembase, B * ntiles));
-        TRY(dalloc(&c->d_itembase_s, B * ntiles));
         TRY(dalloc(&c->d_bin_misc, (size_t)8));
         TRY(dalloc(&c->d_edges_raw, B * R * img));
         TRY(dalloc(&c->d_edge_moments, B * R * EDGE_PARTS * EDGE_MOM));
@@ -1531,7 +1493,6 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     TRY(dalloc(&c->d_iwe, B * R * img));
     TRY(dalloc(&c->d_G, B * R * img));
     TRY(dalloc(&c->d_g11, (size_t)(c->max_items + NXCD) * R * 2));
-    TRY(dalloc(&c->d_win_item0, B + 1));
     TRY(dalloc(&c->d_dtmax, B));
     TRY(dalloc(&c->d_cntmax, B));
     const size_t nig = (size_t)((W + IG_COLS - 1) / IG_COLS) * ((H + IG_ROWS - 1) / IG_ROWS);   // k_imgrad strips per image
@@ -1620,26 +1581,62 @@ void eincm_destroy(eincm_ctx* ctx) {
     delete ctx;
 }
 
-// xs_w / ys_w / ts_w / edges_w: one pointer per window (the caller's own arrays; nothing is concatenated on the host)
-// The fraction of a window's duration the segments of a list span, for the choice of the LDS window capacity (eval_begin): a tile of n events
-// is cut into ceil(n / seg) segments, each spanning about 1 / that of the time.  Not the mean: sparse tiles (sensor noise between the edges)
-// hold one segment that spans the WHOLE window, and their taps go to HBM one by one when the capacity follows the dense tiles (480x640
-// with 10^7 events at 16x16 theta: k_gather 110 -> 90 us with the larger windows).  Returned: the span that all but 3 % of the events stay within.
-static double span_quantile(const std::vector<int32_t>& tilecount, int seg, int64_t N)
+// Segment list L of the staged bins (h_tilecount) at `seg` events per segment, in the order k_items emits the segments.  on_host: the
+// host cuts the segments (with the first one of every window) and uploads them; otherwise k_items has already written the L.n the
+// caller counted.  Then the longest-first order goes up and k_seg_minmax takes every segment's time range from ev_t, the copy of the
+// events the list's walkers read.
+static int build_list(eincm_ctx* c, SegList& L, int seg, bool on_host, int ntiles, const double* ev_t, int64_t N)
 {
+    // L.tspan, for the choice of the LDS window capacity (eval_begin): a tile of n events is cut into ceil(n / seg) segments, each spanning
+    // about 1 / that of the time.  Not the mean: sparse tiles (sensor noise between the edges) hold one segment that spans the WHOLE
+    // window, and their taps go to HBM one by one when the capacity follows the dense tiles (480x640 with 10^7 events at 16x16 theta:
+    // k_gather 110 -> 90 us with the larger windows).  It is the span that all but 3 % of the events stay within.
     constexpr int K = 64;
     int64_t by_nseg[K + 1] = {0};
-    for (const int32_t n : tilecount)
-        if (n > 0) by_nseg[std::min<int64_t>(((int64_t)n + seg - 1) / seg, K)] += n;
+    std::vector<int32_t> lens;
+    L.h_items.clear(); L.h_win_item0.clear();
+    int64_t base = 0;
+    for (size_t idx = 0; idx < c->h_tilecount.size(); ++idx) {
+        if (on_host && idx % (size_t)ntiles == 0) L.h_win_item0.push_back((int32_t)lens.size());
+        const int cnt = c->h_tilecount[idx], len = balanced_seg_len(cnt, seg);
+        if (cnt > 0) by_nseg[std::min<int64_t>(((int64_t)cnt + seg - 1) / seg, K)] += cnt;
+        for (int s0 = 0; s0 < cnt; s0 += len) {
+            lens.push_back(std::min(len, cnt - s0));
+            if (on_host) L.h_items.push_back(Item{(int32_t)(idx / ntiles), (int32_t)(idx % ntiles), (int32_t)(base + s0), lens.back(), 0.0, 0.0});
+        }
+        base += cnt;
+    }
+    if ((int64_t)lens.size() > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %zu segments exceed capacity", lens.size());
+    if (on_host) L.n = (int)lens.size();
+    else if ((int)lens.size() != L.n) return fail(c, EINCM_ERR_ARG, "internal: segment lists disagree (%zu, %d)", lens.size(), L.n);
+    L.seg = seg;
+    L.tspan = 1.0 / K;
     int64_t beyond = 0;
     const int64_t allow = (int64_t)(0.03 * (double)N);
-    for (int k = 1; k <= K; ++k) {              // spans 1, 1/2, 1/3, ...
-        beyond += by_nseg[k];
-        if (beyond > allow) return 1.0 / k;
+    for (int k = 1; k <= K; ++k)                // spans 1, 1/2, 1/3, ...
+        if ((beyond += by_nseg[k]) > allow) { L.tspan = 1.0 / k; break; }
+    // the order the event kernels' workgroups take the segments in (block_to_work): by decreasing length, a stable counting sort
+    int32_t maxlen = 0;
+    for (const int32_t l : lens) maxlen = std::max(maxlen, l);
+    std::vector<int32_t> start((size_t)maxlen + 2, 0);
+    for (const int32_t l : lens) ++start[(size_t)(maxlen - l) + 1];
+    for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
+    L.h_order.resize(lens.size());
+    for (size_t i = 0; i < lens.size(); ++i) L.h_order[(size_t)start[(size_t)(maxlen - lens[i])]++] = (int32_t)i;
+    if (on_host) {
+        L.h_win_item0.push_back(L.n);
+        if (L.d_win_item0)
+            HIPCHK(c, hipMemcpyAsync(L.d_win_item0, L.h_win_item0.data(), L.h_win_item0.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if (L.n > 0) HIPCHK(c, hipMemcpyAsync(L.d_items, L.h_items.data(), (size_t)L.n * sizeof(Item), hipMemcpyHostToDevice, c->stream));
     }
-    return 1.0 / K;
+    if (L.n == 0) return EINCM_OK;
+    HIPCHK(c, hipMemcpyAsync(L.d_order, L.h_order.data(), (size_t)L.n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_seg_minmax, dim3(std::min(L.n, 4096)), dim3(NT), 0, c->stream, L.n, L.d_items, ev_t);
+    HIPCHK(c, hipGetLastError());
+    return EINCM_OK;
 }
 
+// xs_w / ys_w / ts_w / edges_w: one pointer per window (the caller's own arrays; nothing is concatenated on the host)
 static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* const* xs_w,
                             const int16_t* const* ys_w, const double* const* ts_w, const double* const* edges_w,
                             const double* edge_ts, uint32_t sw_flags) {
@@ -1673,8 +1670,8 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     g.igx = (W + IG_COLS - 1) / IG_COLS; g.nig = g.igx * ((H + IG_ROWS - 1) / IG_ROWS);
     g.pstride = std::max(g.ntiles, NSPART);
     g.gmax_n = g.R * g.nig;
-    g.wincap = c->wincap; g.winmaxw = std::max(40, (int)std::lround(std::sqrt((double)c->wincap * 1.4)));
-    g.wincap_a = g.wincap; g.winmaxw_a = g.winmaxw; c->wincap_2 = g.wincap;
+    g.wincap = c->wincap; g.winmaxw = win_maxw(c->wincap);
+    g.wincap_a = g.wincap; g.winmaxw_a = g.winmaxw;
 
     // Segment lengths (events per workgroup and reference time), measured on MI355X with the longest-first order of block_to_work
     // (tools/dev_tune_seg.py, profiles/r02/segment_tuning.txt).  Per-workgroup fixed cost (window clear / flush, G-window load,
@@ -1692,8 +1689,6 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     int seg = c->seg > 0 ? c->seg : 16384;
     int seg_2 = (x_wg >= 4000.0 && (double)N / ((double)n_windows * g.ntiles) < 16384.0) ? 16384 : (x_wg < 1000.0 ? 4096 : 8192);   // (tiles of several segments: as seg_s below; 480x640 with 10^7 events 90 -> 82 us)       // the 2-DoF gather's own list (round-2 tuning)
     if (const char* e = getenv("EINCM_SEG_2DOF")) { const int v = atoi(e); if (v >= 64 && v <= MAX_SEG) seg_2 = v; }
-    c->seg_2_used = seg_2;
-    c->seg_used = seg;
     // (late round 3: k_splat is no longer bound by the LDS atomic unit, so its per-workgroup fixed work - 24 of 90 us on the 8-window
     // batch: window derivation and clear 14, flush 10 - shows: 16384-event segments there, 90.1 -> 85.2 us; 104 -> 100 us at 16x16)
     // ... but only where a tile holds about one such segment: with tiles of several segments (480x640, 10^7 events: 33 000 per tile) the long
@@ -1705,7 +1700,6 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     // window of 10^6 events 72 -> 62 us per evaluation, 2 x 3*10^6 143 -> 128, 480x640 with 5*10^6 173 -> 126, with 10^7 220 -> 184).
     g.pitch_aligned = (x_wg >= 3000.0 && per_tile < 16384.0) ? 1 : 0;
     if (const char* e = getenv("EINCM_PITCH_ALIGNED")) g.pitch_aligned = std::max(0, std::min(2, atoi(e)));      // 0: never, 1: k_splat where it costs no capacity class, 2: the 2-DoF gather too
-    c->seg_s_used = seg_s;
     const bool sort_segments = getenv("EINCM_NO_SEGSORT") == nullptr;
     const size_t img = (size_t)H * W;
     for (int b = 0; b < n_windows; ++b) {
@@ -1714,12 +1708,23 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         for (int r = 0; r < n_refs; ++r)
             if (!std::isfinite(edge_ts[b * n_refs + r])) return fail(c, EINCM_ERR_ARG, "edge_ts[%d,%d] is not finite", b, r);
     }
-    int n_items_total = 0, n_items_s_total = 0;
-    c->h_win_item0.assign((size_t)n_windows + 1, 0);
     std::vector<unsigned> cntmax_h((size_t)n_windows, 0u);
     std::vector<double> dtmax_h((size_t)n_windows, 0.0);
-    std::vector<int32_t> item0_h;                  // host path only
     bool edge_ts_uploaded = false;
+    int rc = EINCM_OK;
+    // the gather's copy of the binned events: every segment of its list sorted by source pixel and dealt to the threads that walk it
+    // (k_segsort, from the binned time order, before the splat's copy is re-dealt in place); EINCM_NO_SEGSORT: a plain copy
+    auto copy_for_gather = [&]() -> int {
+        if (c->gather.n == 0) return EINCM_OK;
+        if (sort_segments) {
+            hipLaunchKernelGGL(k_segsort, dim3(std::min(c->gather.n, 8192)), dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
+                               c->d_xy, c->d_t, c->d_xy_g, c->d_t_g);
+            return EINCM_OK;
+        }
+        HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        return EINCM_OK;
+    };
     if (!c->host_binning) {
         // ---- device path: counting sort by (window, source tile) on the GPU (eincm_binning.hip.h) ----
         std::vector<BinBlock> blks;
@@ -1762,7 +1767,7 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         }
         const int M = n_windows * g.ntiles;
         hipLaunchKernelGGL(k_bin_scan, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, c->d_win_blk, c->d_blockhist, c->d_tilecount);
-        hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, seg, c->d_tilecount, c->d_tilebase, c->d_itembase, c->d_bin_misc);
+        hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase, c->d_bin_misc);
         HIPCHK(c, hipGetLastError());
         int32_t misc[4];
         std::vector<double> mom((size_t)n_windows * n_refs * EDGE_PARTS * EDGE_MOM);
@@ -1784,8 +1789,8 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
             while (b < n_windows - 1 && off >= n_events[b]) { off -= n_events[b]; ++b; }
             return fail(c, EINCM_ERR_ARG, "event %lld of window %d has a non-finite timestamp", (long long)off, b);
         }
-        n_items_total = misc[1];
-        if (n_items_total > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d segments exceed capacity", n_items_total);
+        c->gather.n = misc[1];
+        if (c->gather.n > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d segments exceed capacity", c->gather.n);
         for (int b = 0; b < n_windows; ++b)
             for (int r = 0; r < n_refs; ++r) {          // the blocks' partials, added in index order
                 double sE = 0.0, sEE = 0.0, eabs = 0.0;
@@ -1798,69 +1803,43 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         if (nblk > 0) {
             hipLaunchKernelGGL(k_bin_scatter, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
                                c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t);
-            hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, seg, c->d_tilecount, c->d_tilebase, c->d_itembase, c->d_items);
-            if (n_items_total > 0) {
-                // the gather's copy: every segment of its list sorted by source pixel and dealt to the threads that walk it (from the
-                // binned time order, before the splat's copy is re-dealt in place)
-                if (sort_segments)
-                    hipLaunchKernelGGL(k_segsort, dim3(std::min(n_items_total, 8192)), dim3(SORT_NT), 0, c->stream, n_items_total, c->d_items,
-                                       c->d_xy, c->d_t, c->d_xy_g, c->d_t_g);
-                else {
-                    HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-                }
-                hipLaunchKernelGGL(k_seg_minmax, dim3(std::min(n_items_total, 4096)), dim3(NT), 0, c->stream, n_items_total, c->d_items, c->d_t_g);
-            }
+            hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase,
+                               c->gather.d_items);
+            if ((rc = copy_for_gather())) return rc;
+        }
+        if ((rc = build_list(c, c->gather, seg, false, g.ntiles, c->d_t_g, N))) return rc;
+        c->splat.n = 0;
+        if (nblk > 0) {
             if (!getenv("EINCM_NO_SPREAD"))
                 hipLaunchKernelGGL(k_spread, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t);
             // per window: first segment and max |t - tau| (needs the segment time ranges and the FIRST segmentation's itembase)
             HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, edge_ts, (size_t)n_windows * n_refs * sizeof(double), hipMemcpyHostToDevice, c->stream));
             edge_ts_uploaded = true;
-            hipLaunchKernelGGL(k_win_consts, dim3(n_windows), dim3(NT), 0, c->stream, g, n_items_total, c->d_items, c->d_itembase, c->d_edge_ts,
-                               c->d_win_item0, c->d_dtmax);
+            hipLaunchKernelGGL(k_win_consts, dim3(n_windows), dim3(NT), 0, c->stream, g, c->gather.n, c->gather.d_items, c->gather.d_itembase,
+                               c->d_edge_ts, c->gather.d_win_item0, c->d_dtmax);
             HIPCHK(c, hipMemcpyAsync(dtmax_h.data(), c->d_dtmax, (size_t)n_windows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->h_win_item0.data(), c->d_win_item0, (size_t)n_windows * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            // second segmentation of the same binned events for k_splat
-            hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, seg_s, c->d_tilecount, c->d_tilebase, c->d_itembase_s, c->d_bin_misc);
-            {   // its total is not read back (a synchronisation per staging): the host repeats the arithmetic on the tile populations it holds
-                std::vector<int32_t> lens_s;
-                segment_lengths(c->h_tilecount, seg_s, lens_s);
-                n_items_s_total = (int)lens_s.size();
-            }
-            if (n_items_s_total > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d splat segments exceed capacity", n_items_s_total);
-            hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, seg_s, c->d_tilecount, c->d_tilebase, c->d_itembase_s, c->d_items_s);
-            if (n_items_s_total > 0)
-                hipLaunchKernelGGL(k_seg_minmax, dim3(std::min(n_items_s_total, 4096)), dim3(NT), 0, c->stream, n_items_s_total, c->d_items_s, c->d_t);
-            HIPCHK(c, hipGetLastError());
-            {   // longest-first order of both segment lists, from the tile populations (the host repeats k_items' arithmetic)
-                std::vector<int32_t> lens;
-                segment_lengths(c->h_tilecount, seg, lens);
-                if ((int)lens.size() != n_items_total) return fail(c, EINCM_ERR_ARG, "internal: segment lists disagree (%zu, %d)", lens.size(), n_items_total);
-                order_by_length(lens, c->h_order);
-                segment_lengths(c->h_tilecount, seg_s, lens);
-                if ((int)lens.size() != n_items_s_total) return fail(c, EINCM_ERR_ARG, "internal: splat segment lists disagree (%zu, %d)", lens.size(), n_items_s_total);
-                order_by_length(lens, c->h_order_s);
-                if (n_items_total > 0)
-                    HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), c->h_order.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-                if (n_items_s_total > 0)
-                    HIPCHK(c, hipMemcpyAsync(c->d_order_s, c->h_order_s.data(), c->h_order_s.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            }
+            // second segmentation of the same binned events for k_splat; its total is not read back (a synchronisation per staging):
+            // the host repeats the arithmetic on the tile populations it holds
+            hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, seg_s, c->d_tilecount, c->d_tilebase, c->splat.d_itembase, c->d_bin_misc);
+            for (const int32_t cnt : c->h_tilecount) c->splat.n += (cnt + seg_s - 1) / seg_s;
+            if (c->splat.n > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d splat segments exceed capacity", c->splat.n);
+            hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, seg_s, c->d_tilecount, c->d_tilebase, c->splat.d_itembase,
+                               c->splat.d_items);
         } else {
-            HIPCHK(c, hipMemsetAsync(c->d_win_item0, 0, (size_t)(n_windows + 1) * sizeof(int32_t), c->stream));
+            HIPCHK(c, hipMemsetAsync(c->gather.d_win_item0, 0, (size_t)(n_windows + 1) * sizeof(int32_t), c->stream));
         }
+        if ((rc = build_list(c, c->splat, seg_s, false, g.ntiles, c->d_t, N))) return rc;
     } else {
     // ---- host path (sensors with more tiles than the LDS histogram holds, or EINCM_HOST_BINNING=1): stable counting sort ----
     c->h_tilecount.assign((size_t)n_windows * g.ntiles, 0);
     std::vector<uint32_t> sxy((size_t)std::max<int64_t>(N, 1));
     std::vector<double> st((size_t)std::max<int64_t>(N, 1));
-    std::vector<Item> items, items_s;
     std::vector<int64_t> cnt((size_t)g.ntiles + 1);
     int64_t base = 0;
     for (int b = 0; b < n_windows; ++b) {
         const int64_t n = n_events[b];
         const int16_t* x = xs_w[b]; const int16_t* y = ys_w[b]; const double* t = ts_w[b];
         std::fill(cnt.begin(), cnt.end(), 0);
-        item0_h.push_back((int32_t)items.size());
         for (int64_t i = 0; i < n; ++i) {
             for (int r = 0; r < n_refs; ++r) dtmax_h[b] = std::max(dtmax_h[b], std::fabs(t[i] - edge_ts[b * n_refs + r]));
             if (x[i] < 0 || x[i] >= W || y[i] < 0 || y[i] >= H)
@@ -1882,28 +1861,8 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
             sxy[d] = (uint32_t)(uint16_t)x[i] | ((uint32_t)(uint16_t)y[i] << 16);
             st[d] = t[i];
         }
-        for (int pass = 0; pass < 2; ++pass) {
-            const int sg = pass == 0 ? seg : seg_s;
-            std::vector<Item>& dst = pass == 0 ? items : items_s;
-            for (int k = 0; k < g.ntiles; ++k) {
-                const int len = balanced_seg_len((int)(cnt[k + 1] - cnt[k]), sg);
-                for (int64_t s = cnt[k]; s < cnt[k + 1]; s += len) {
-                    Item it;
-                    it.win = b; it.tile = k; it.begin = (int32_t)(base + s);
-                    it.count = (int32_t)std::min<int64_t>(len, cnt[k + 1] - s);
-                    double lo = st[it.begin], hi = st[it.begin];
-                    for (int q = 1; q < it.count; ++q) { lo = std::min(lo, st[it.begin + q]); hi = std::max(hi, st[it.begin + q]); }
-                    it.t_lo = lo; it.t_hi = hi;
-                    dst.push_back(it);
-                }
-            }
-        }
         base += n;
     }
-    if ((int64_t)items.size() > c->max_items || (int64_t)items_s.size() > c->max_items)
-        return fail(c, EINCM_ERR_ARG, "internal: %zu work items exceed capacity", std::max(items.size(), items_s.size()));
-    n_items_total = (int)items.size();
-    n_items_s_total = (int)items_s.size();
     std::vector<float> ef((size_t)n_windows * n_refs * img);
     for (int b = 0; b < n_windows; ++b) {
         WinConst& wc = c->h_wc[b];
@@ -1929,70 +1888,24 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
             off += (int64_t)nb;
         }
     }
-    if (!items.empty()) {
-        HIPCHK(c, hipMemcpyAsync(c->d_items, items.data(), items.size() * sizeof(Item), hipMemcpyHostToDevice, c->stream));
-        if (sort_segments)      // the gather's copy; a permutation inside the segments: their time ranges (computed above) are unchanged
-            hipLaunchKernelGGL(k_segsort, dim3((unsigned)std::min<size_t>(items.size(), 8192)), dim3(SORT_NT), 0, c->stream, (int)items.size(), c->d_items,
-                               c->d_xy, c->d_t, c->d_xy_g, c->d_t_g);
-        else {
-            HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        }
-    }
-    if (!items_s.empty())
-        HIPCHK(c, hipMemcpyAsync(c->d_items_s, items_s.data(), items_s.size() * sizeof(Item), hipMemcpyHostToDevice, c->stream));
-    {
-        std::vector<int32_t> lens(items.size());
-        for (size_t i = 0; i < items.size(); ++i) lens[i] = items[i].count;
-        order_by_length(lens, c->h_order);
-        lens.resize(items_s.size());
-        for (size_t i = 0; i < items_s.size(); ++i) lens[i] = items_s[i].count;
-        order_by_length(lens, c->h_order_s);
-        if (!items.empty())
-            HIPCHK(c, hipMemcpyAsync(c->d_order, c->h_order.data(), c->h_order.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        if (!items_s.empty())
-            HIPCHK(c, hipMemcpyAsync(c->d_order_s, c->h_order_s.data(), c->h_order_s.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_win_item0, item0_h.data(), item0_h.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    std::copy(item0_h.begin(), item0_h.end(), c->h_win_item0.begin());
+    // the gather's and the splat's lists, cut on the host like the two others (the gather's copy is a permutation inside the gather
+    // list's segments: their time ranges come from either copy)
+    if ((rc = build_list(c, c->gather, seg, true, g.ntiles, c->d_t, N))) return rc;
+    if ((rc = copy_for_gather())) return rc;
+    if ((rc = build_list(c, c->splat, seg_s, true, g.ntiles, c->d_t, N))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_edges, ef.data(), ef.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));     // host vectors go out of scope
     }
     if (!edge_ts_uploaded)
         HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, edge_ts, (size_t)n_windows * n_refs * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_mask, 0, (size_t)n_windows * img, c->stream));
-    std::vector<Item> items_2;
-    {   // the 2-DoF gather's segment list (splat copy of the events): generated on the host from the tile populations
-        host_items(c->h_tilecount, g.ntiles, seg_2, items_2, c->h_win_item0_2);
-        if ((int64_t)items_2.size() > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %zu segments exceed capacity", items_2.size());
-        c->h_win_item0_2.resize((size_t)n_windows + 1, (int32_t)items_2.size());
-        std::vector<int32_t> lens(items_2.size());
-        for (size_t i = 0; i < items_2.size(); ++i) lens[i] = items_2[i].count;
-        order_by_length(lens, c->h_order_2);
-        if (!items_2.empty()) {
-            HIPCHK(c, hipMemcpyAsync(c->d_items_2, items_2.data(), items_2.size() * sizeof(Item), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_order_2, c->h_order_2.data(), c->h_order_2.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_seg_minmax, dim3((unsigned)std::min<size_t>(items_2.size(), 4096)), dim3(NT), 0, c->stream, (int)items_2.size(), c->d_items_2, c->d_t);
-        }
-        HIPCHK(c, hipMemcpyAsync(c->d_win_item0_2, c->h_win_item0_2.data(), (size_t)(n_windows + 1) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    }
-    std::vector<Item> items_sh;
-    std::vector<int32_t> order_sh;
-    c->n_items_sh = 0; c->seg_sh_used = 0;
-    if (seg_s > 8192) {   // the splat's short list: the same events cut into 8192-event segments, for evaluations whose theta is too large for
-        std::vector<int32_t> w0;                    // the windows of the long segments (twice the time span, hence twice the spread)
-        host_items(c->h_tilecount, g.ntiles, 8192, items_sh, w0);
-        if ((int64_t)items_sh.size() <= c->max_items && !items_sh.empty()) {
-            std::vector<int32_t> lens(items_sh.size());
-            for (size_t i = 0; i < items_sh.size(); ++i) lens[i] = items_sh[i].count;
-            order_by_length(lens, order_sh);
-            HIPCHK(c, hipMemcpyAsync(c->d_items_sh, items_sh.data(), items_sh.size() * sizeof(Item), hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(c->d_order_sh, order_sh.data(), order_sh.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_seg_minmax, dim3((unsigned)std::min<size_t>(items_sh.size(), 4096)), dim3(NT), 0, c->stream, (int)items_sh.size(), c->d_items_sh, c->d_t);
-            c->n_items_sh = (int)items_sh.size(); c->seg_sh_used = 8192;
-        }
-    }
-    if (n_items_total > 0 && !c->host_binning) {     // event mask + most events on one source pixel, per tile from its LDS histogram
+    // the 2-DoF gather's list (splat copy of the events), and beside a 16384-event splat list the splat's short one: the same events cut
+    // into 8192-event segments, for evaluations whose theta is too large for the windows of the long segments (twice the time span,
+    // hence twice the spread).  Both cut on the host from the tile populations.
+    if ((rc = build_list(c, c->gather_2, seg_2, true, g.ntiles, c->d_t, N))) return rc;
+    c->splat_sh.n = 0;
+    if (seg_s > 8192 && (rc = build_list(c, c->splat_sh, 8192, true, g.ntiles, c->d_t, N))) return rc;
+    if (c->gather.n > 0 && !c->host_binning) {     // event mask + most events on one source pixel, per tile from its LDS histogram
         HIPCHK(c, hipMemsetAsync(c->d_cntmax, 0, (size_t)n_windows * sizeof(unsigned), c->stream));       // (before the synchronisation below: one per staging fewer)
         hipLaunchKernelGGL(k_tile_counts, dim3(g.ntiles, n_windows), dim3(NT), 0, c->stream, g, c->d_tilebase, c->d_tilecount, c->d_xy,
                            c->d_mask, c->d_cntmax);
@@ -2000,18 +1913,13 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         HIPCHK(c, hipMemcpyAsync(cntmax_h.data(), c->d_cntmax, (size_t)n_windows * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->n_items_2 = (int)items_2.size();
-    c->tspan_s = span_quantile(c->h_tilecount, seg_s, N);
-    c->tspan_sh = span_quantile(c->h_tilecount, 8192, N);
-    c->tspan_a = span_quantile(c->h_tilecount, seg, N);
-    c->tspan_2 = span_quantile(c->h_tilecount, seg_2, N);
     c->pitch_policy = g.pitch_aligned;
     c->policy_evaluated = false;
-    c->g = g; c->n_items = n_items_total; c->n_items_s = n_items_s_total; c->n_events = N;
-    c->itembase_valid = !c->host_binning && n_items_total > 0 && n_items_s_total > 0;      // both tile scans ran on the device
+    c->g = g; c->n_events = N;
+    c->itembase_valid = !c->host_binning && c->gather.n > 0 && c->splat.n > 0;      // both tile scans ran on the device
     c->win_events.assign(n_events, n_events + n_windows);
-    if (c->n_items > 0 && c->host_binning) {
-        hipLaunchKernelGGL(k_mask, dim3(std::min(c->n_items, 2048)), dim3(NT), 0, c->stream, g, c->d_items, c->n_items, c->d_xy, c->d_mask);
+    if (c->gather.n > 0 && c->host_binning) {
+        hipLaunchKernelGGL(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, c->stream, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask);
         HIPCHK(c, hipGetLastError());
     }
 
@@ -2058,7 +1966,7 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         const int rc = evaluate(c, zero.data(), 1, 1, &p, val.data(), nullptr, nullptr, true);
         if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) { c->staged = false; return rc; }
     }
-    const int rc = store_constants(c);
+    rc = store_constants(c);
     c->err.clear();
     return rc;
 }
@@ -2439,8 +2347,9 @@ int eincm_get_count_images(eincm_ctx* c, uint32_t* counts) {
     uint32_t* d = reinterpret_cast<uint32_t*>(c->d_G);
     if (!c->fp64) c->G_valid = false;               // (an fp64 context keeps dL/dIWE in its own buffer)
     HIPCHK(c, hipMemsetAsync(d, 0, n * sizeof(uint32_t), c->stream));
-    if (c->n_items > 0)
-        hipLaunchKernelGGL(k_count, dim3(event_grid(c)), dim3(NT), 0, c->stream, g, c->n_items, c->d_items, c->d_xy, c->d_t, c->d_Theta,
+    const SegList& L = c->gather;
+    if (L.n > 0)
+        hipLaunchKernelGGL(k_count, dim3(L.grid(g.R)), dim3(NT), 0, c->stream, g, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta,
                            c->d_edge_ts, d);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(counts, d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
@@ -2710,13 +2619,13 @@ int eincm_get_host_profile(eincm_ctx* c, double* us, int64_t* n_evals, int reset
 
 int eincm_get_launch_policy(eincm_ctx* c, double* out) {
     if (!c || !out) return EINCM_ERR_ARG;
-    out[EINCM_LP_SEG_GATHER] = c->seg_used; out[EINCM_LP_SEG_SPLAT] = c->seg_s_used; out[EINCM_LP_SEG_GATHER_2DOF] = c->seg_2_used;
-    out[EINCM_LP_SEG_SPLAT_SHORT] = c->seg_sh_used; out[EINCM_LP_PITCH_POLICY] = c->pitch_policy;
-    out[EINCM_LP_SPAN_SPLAT] = c->tspan_s; out[EINCM_LP_SPAN_GATHER] = c->tspan_a; out[EINCM_LP_SPAN_GATHER_2DOF] = c->tspan_2;
+    out[EINCM_LP_SEG_GATHER] = c->gather.seg; out[EINCM_LP_SEG_SPLAT] = c->splat.seg; out[EINCM_LP_SEG_GATHER_2DOF] = c->gather_2.seg;
+    out[EINCM_LP_SEG_SPLAT_SHORT] = c->splat_sh.n > 0 ? c->splat_sh.seg : 0; out[EINCM_LP_PITCH_POLICY] = c->pitch_policy;
+    out[EINCM_LP_SPAN_SPLAT] = c->splat.tspan; out[EINCM_LP_SPAN_GATHER] = c->gather.tspan; out[EINCM_LP_SPAN_GATHER_2DOF] = c->gather_2.tspan;
     const bool evaluated = c->policy_evaluated;
     out[EINCM_LP_CAP_SPLAT] = evaluated ? c->g.wincap : 0; out[EINCM_LP_CAP_GATHER] = evaluated ? c->g.wincap_a : 0;
-    out[EINCM_LP_CAP_GATHER_2DOF] = evaluated ? c->wincap_2 : 0;
-    out[EINCM_LP_PITCH_ALIGNED] = evaluated ? ((c->g.pitch_aligned ? 1 : 0) | (c->pend.pal_2 ? 2 : 0)) : 0;
+    out[EINCM_LP_CAP_GATHER_2DOF] = evaluated ? c->pend.win_2.cap : 0;
+    out[EINCM_LP_PITCH_ALIGNED] = evaluated ? ((c->g.pitch_aligned ? 1 : 0) | (c->pend.win_2.pal ? 2 : 0)) : 0;
     out[EINCM_LP_SPLAT_SHORT] = evaluated && c->pend.splat_short ? 1 : 0;
     return EINCM_OK;
 }
