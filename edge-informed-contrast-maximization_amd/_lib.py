@@ -52,6 +52,19 @@ class ObjectivesOut(C.Structure):
                 ('flow_warp_losses', _A), ('multi_ref_weights', _A), ('variances', _A), ('zero_variance', C.c_double)]
 
 
+PRE_NLMEANS, PRE_CLAHE, PRE_UNSHARP, PRE_BILATERAL = 1, 2, 4, 8      # eincm_preprocess_params.stages (EINCM_PRE_*)
+PRE_ALL = 15
+PRE_STAGES = {'nlmeans': 1, 'clahe': 2, 'unsharp': 4, 'bilateral': 8}
+
+
+class PreprocessParams(C.Structure):
+    _fields_ = [('stages', C.c_int32), ('denoise_h', C.c_double),
+                ('denoise_template_win', C.c_int32), ('denoise_search_win', C.c_int32),
+                ('clahe_clip_limit', C.c_double), ('clahe_tiles_x', C.c_int32), ('clahe_tiles_y', C.c_int32),
+                ('sharpen_sigma', C.c_double), ('sharpen_alpha', C.c_double), ('sharpen_beta', C.c_double),
+                ('bilateral_d', C.c_int32), ('bilateral_sigma_color', C.c_double), ('bilateral_sigma_space', C.c_double)]
+
+
 class TiledOut(C.Structure):
     _fields_ = [('n_refs', C.c_int32), ('n_tiles', C.c_int32),
                 ('adaptive_mean_gradient_magnitude', _A), ('adaptive_variance', _A), ('adaptive_mean_squared_error', _A),
@@ -119,6 +132,7 @@ SIGNATURES = [
                                            C.POINTER(C.c_int32)]),
     ('eincm_gaussian_blur', C.c_int, [_P, _D, C.c_int, C.c_double, _D]),
     ('eincm_canny', C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
+    ('eincm_preprocess_image', C.c_int, [_P, C.POINTER(C.c_uint8), C.c_int, C.POINTER(PreprocessParams), C.POINTER(C.c_uint8)]),
     ('eincm_tiled_objectives', C.c_int, [_P, C.c_int, C.c_int, C.POINTER(TiledOut)]),
     ('eincm_set_objective_tiles', C.c_int, [_P, C.c_int, C.c_int]),
     ('eincm_set_splat_window', C.c_int, [_P, C.c_int]),

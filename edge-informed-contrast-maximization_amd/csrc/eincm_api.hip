@@ -26,6 +26,7 @@
 #include "eincm_objectives.hip.h"
 #include "eincm_splat_window.hip.h"
 #include "eincm_canny.hip.h"
+#include "eincm_preprocess.hip.h"
 
 using namespace eincm;
 
@@ -158,6 +159,12 @@ struct eincm_ctx {
 
     // scratch of the edge-smoothing / Canny / tiled-objective entry points (eincm_edges.hip.h, eincm_canny.hip.h), grown on demand
     DevBuf e_u8, e_g, e_sq, e_misc, e_a, e_b, e_kern, e_out;
+    // scratch of eincm_preprocess_image (eincm_preprocess.hip.h), grown on demand: two uint8 stacks, the blur's row pass, the
+    // per-call tables, the CLAHE LUTs, and the NL-means weight table (kept for the (h, template, search) it was built for)
+    DevBuf p_img[2], p_rows, p_tab, p_lut, p_nlm;
+    std::vector<int32_t> h_pre_tab, h_nlm_tab;
+    float nlm_hh = 0.0f;
+    int nlm_tw = 0, nlm_sw = 0;
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
@@ -341,6 +348,8 @@ void free_all(eincm_ctx* c) {
     F(c->f64.grad); F(c->f64.partA); F(c->f64.partB); F(c->f64.partC); F(c->f64.scal); F(c->f64.gmax); F(c->f64.ishift); F(c->f64.bad);
     F(c->d_objc); F(c->d_oparts); c->oparts_cap = 0;
     for (DevBuf* b : {&c->e_u8, &c->e_g, &c->e_sq, &c->e_misc, &c->e_a, &c->e_b, &c->e_kern, &c->e_out}) { F(b->p); b->bytes = 0; }
+    for (DevBuf* b : {&c->p_img[0], &c->p_img[1], &c->p_rows, &c->p_tab, &c->p_lut, &c->p_nlm}) { F(b->p); b->bytes = 0; }
+    c->nlm_tw = 0;
     auto FH = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
     FH(c->f64.h_scal); FH(c->h_ovals);
     FH(c->h_theta); FH(c->h_outs); c->h_grad = nullptr; FH(c->h_wc); FH(c->h_g11); FH(c->h_g2); FH(c->h_img); FH(c->h_tvparts);
@@ -2504,6 +2513,194 @@ int eincm_canny(eincm_ctx* c, const uint8_t* src, int n, double threshold1, doub
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(dst, d_img, tot, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EINCM_OK;
+}
+
+// preprocess_image (img_utils.py:131-189): host tables of the contract, then the selected stages back to back.
+static int nlm_shift(int tw) { int s = 0; while ((1 << s) < tw * tw) ++s; return s; }
+
+int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_preprocess_params* p, uint8_t* dst) {
+#pragma clang fp contract(off)
+    if (!c) return EINCM_ERR_ARG;
+    if (!src || !dst || !p) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n < 1 || n > 65535) return fail(c, EINCM_ERR_ARG, "n = %d images (1..65535)", n);
+    const int st = p->stages;
+    if (st < 1 || (st & ~EINCM_PRE_ALL)) return fail(c, EINCM_ERR_ARG, "stages = %d: a non-empty set of EINCM_PRE_* bits", st);
+    const int H = c->H, W = c->W;
+    const int tw = p->denoise_template_win, sw = p->denoise_search_win;
+    if (st & EINCM_PRE_NLMEANS) {
+        if (!(p->denoise_h > 0.0) || !std::isfinite(p->denoise_h))
+            return fail(c, EINCM_ERR_ARG, "denoise_h = %g must be positive and finite", p->denoise_h);
+        if (tw < 1 || sw < 1 || !(tw & 1) || !(sw & 1))
+            return fail(c, EINCM_ERR_ARG, "NL-means windows %d, %d must be odd and positive", tw, sw);
+        if (tw > NLM_MAX_TEMPLATE || sw > NLM_MAX_SEARCH)
+            return fail(c, EINCM_ERR_UNSUPPORTED, "NL-means windows %d, %d (template <= %d, search <= %d)", tw, sw, NLM_MAX_TEMPLATE,
+                        NLM_MAX_SEARCH);
+    }
+    const int tx = p->clahe_tiles_x, ty = p->clahe_tiles_y;
+    if (st & EINCM_PRE_CLAHE) {
+        if (tx < 1 || ty < 1 || tx > W || ty > H)
+            return fail(c, EINCM_ERR_ARG, "CLAHE grid %d x %d (x splits the width) does not fit the %d x %d sensor", tx, ty, H, W);
+        if (std::isnan(p->clahe_clip_limit) || std::isinf(p->clahe_clip_limit))
+            return fail(c, EINCM_ERR_ARG, "clahe_clip_limit = %g must be finite", p->clahe_clip_limit);
+    }
+    double taps_d = 0.0;
+    if (st & EINCM_PRE_UNSHARP) {
+        if (!(p->sharpen_sigma > 0.0) || !std::isfinite(p->sharpen_sigma))
+            return fail(c, EINCM_ERR_ARG, "sharpen_sigma = %g must be positive and finite", p->sharpen_sigma);
+        if (!std::isfinite(p->sharpen_alpha) || !std::isfinite(p->sharpen_beta))
+            return fail(c, EINCM_ERR_ARG, "sharpen weights %g, %g must be finite", p->sharpen_alpha, p->sharpen_beta);
+        taps_d = std::nearbyint(p->sharpen_sigma * 3 * 2 + 1);
+        if (taps_d > UNSHARP_MAX_TAPS)
+            return fail(c, EINCM_ERR_UNSUPPORTED, "sharpen_sigma = %g needs %g taps (> %d)", p->sharpen_sigma, taps_d, UNSHARP_MAX_TAPS);
+    }
+    int bil_r = 0;
+    double sc = 1.0, ss = 1.0;
+    if (st & EINCM_PRE_BILATERAL) {
+        if (!std::isfinite(p->bilateral_sigma_color) || !std::isfinite(p->bilateral_sigma_space))
+            return fail(c, EINCM_ERR_ARG, "bilateral sigmas %g, %g must be finite", p->bilateral_sigma_color, p->bilateral_sigma_space);
+        sc = p->bilateral_sigma_color <= 0 ? 1.0 : p->bilateral_sigma_color;
+        ss = p->bilateral_sigma_space <= 0 ? 1.0 : p->bilateral_sigma_space;
+        const double rd = p->bilateral_d > 0 ? (double)(p->bilateral_d / 2) : std::nearbyint(ss * 1.5);
+        if (rd > BIL_MAX_RADIUS) return fail(c, EINCM_ERR_UNSUPPORTED, "bilateral radius %g (> %d)", rd, BIL_MAX_RADIUS);
+        bil_r = std::max((int)rd, 1);
+    }
+
+    // ---- host tables (in h_pre_tab: unsharp taps, then bilateral colour weights, tap offsets and tap weights as float bits)
+    std::vector<int32_t>& T = c->h_pre_tab;
+    T.clear();
+    int un_r = 0, bil_n = 0;
+    size_t off_cw = 0, off_ofs = 0, off_w = 0;
+    if (st & EINCM_PRE_UNSHARP) {
+        // cv::GaussianBlur, 8-bit: getGaussianKernelBitExact (fp64 here) and error-diffusion rounding to 8 fraction bits
+        const double sigma = p->sharpen_sigma;
+        const int taps = (int)taps_d | 1, half = taps / 2;
+        const double scale2 = -0.125 / (sigma * sigma);
+        std::vector<double> v((size_t)half);
+        double sum = 0.0;
+        for (int i = 0, x = 1 - taps; i < half; ++i, x += 2) { v[i] = std::exp((double)(x * x) * scale2); sum += v[i]; }
+        const double mul = 1.0 / (sum * 2.0 + 1.0);
+        T.assign((size_t)taps, 0);
+        double err = 0.0;
+        int acc = 0;
+        for (int i = 0; i < half; ++i) {
+            const double g = v[i] * mul;
+            const double adj = g * 256.0 + err;
+            const double v0 = std::nearbyint(adj);
+            err = adj - v0;
+            T[i] = T[taps - 1 - i] = (int32_t)v0;
+            acc += (int32_t)v0;
+        }
+        T[half] = 256 - 2 * acc;
+        un_r = half;
+    }
+    if (st & EINCM_PRE_BILATERAL) {
+        const double cc = -0.5 / (sc * sc), sc2 = -0.5 / (ss * ss);
+        off_cw = T.size();
+        for (int i = 0; i < 256; ++i) { const float w = (float)std::exp(i * i * cc); int32_t b; std::memcpy(&b, &w, 4); T.push_back(b); }
+        std::vector<int32_t> ofs;
+        std::vector<int32_t> wts;
+        for (int i = -bil_r; i <= bil_r; ++i)
+            for (int j = -bil_r; j <= bil_r; ++j) {
+                const double r = std::sqrt((double)i * i + (double)j * j);
+                if (r > bil_r) continue;
+                const float w = (float)std::exp(r * r * sc2);
+                int32_t b; std::memcpy(&b, &w, 4);
+                ofs.push_back(i); ofs.push_back(j); wts.push_back(b);
+            }
+        bil_n = (int)wts.size();
+        off_ofs = T.size(); T.insert(T.end(), ofs.begin(), ofs.end());
+        off_w = T.size(); T.insert(T.end(), wts.begin(), wts.end());
+    }
+    int clahe_th = 0, clahe_tw = 0, clahe_limit = 0;
+    if (st & EINCM_PRE_CLAHE) {
+        // OpenCV pads bottom and right by a full remainder-to-tile unless both sides divide
+        const bool divides = W % tx == 0 && H % ty == 0;
+        const int Hp = divides ? H : H + ty - H % ty, Wp = divides ? W : W + tx - W % tx;
+        clahe_th = Hp / ty; clahe_tw = Wp / tx;
+        const int total = clahe_th * clahe_tw;
+        if (p->clahe_clip_limit > 0.0) {
+            const double l = p->clahe_clip_limit * total / CLAHE_BINS;
+            clahe_limit = l >= total ? total : std::max((int)l, 1);
+        }
+    }
+
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t npix = (size_t)H * W, tot = npix * n;
+    ENSURE(c, c->p_img[0], tot); ENSURE(c, c->p_img[1], tot);
+    if (!T.empty()) {
+        ENSURE(c, c->p_tab, T.size() * 4);
+        HIPCHK(c, hipMemcpyAsync(c->p_tab.p, T.data(), T.size() * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    if (st & EINCM_PRE_NLMEANS) {
+        const float hf = (float)p->denoise_h;
+        const float hh = hf * hf;
+        if (c->nlm_tw != tw || c->nlm_sw != sw || c->nlm_hh != hh) {
+            // fastNlMeansDenoising's almost_dist2weight: fixed-point weights indexed by the template distance >> shift
+            const int s = nlm_shift(tw);
+            const int fpm = INT32_MAX / (sw * sw * 255);
+            const double mult = (double)(1 << s) / (tw * tw);
+            const int size = (int)(65025 / mult + 1);
+            std::vector<int32_t>& N = c->h_nlm_tab;
+            N.assign((size_t)size, 0);
+            for (int a = 0; a < size; ++a) {
+                const double dist = a * mult;
+                const double w = std::exp(-dist / (double)hh);
+                const double wi = std::nearbyint(fpm * w);
+                N[a] = wi < 0.001 * fpm ? 0 : (int32_t)wi;
+            }
+            c->nlm_tw = 0;                                   // invalid until the upload is queued
+            ENSURE(c, c->p_nlm, N.size() * 4);
+            HIPCHK(c, hipMemcpyAsync(c->p_nlm.p, N.data(), N.size() * 4, hipMemcpyHostToDevice, c->stream));
+            c->nlm_tw = tw; c->nlm_sw = sw; c->nlm_hh = hh;
+        }
+    }
+    if (st & EINCM_PRE_CLAHE) ENSURE(c, c->p_lut, (size_t)n * tx * ty * CLAHE_BINS);
+    if (st & EINCM_PRE_UNSHARP) ENSURE(c, c->p_rows, tot * 2);
+
+    int cur = 0;
+    uint8_t* img[2] = {static_cast<uint8_t*>(c->p_img[0].p), static_cast<uint8_t*>(c->p_img[1].p)};
+    const int32_t* d_tab = static_cast<const int32_t*>(c->p_tab.p);
+    HIPCHK(c, hipMemcpyAsync(img[0], src, tot, hipMemcpyHostToDevice, c->stream));
+    const dim3 rows_grid((W + NT - 1) / NT, H, n);
+    if (st & EINCM_PRE_NLMEANS) {
+        const int b = sw / 2 + tw / 2;
+        const size_t lds = (size_t)(NLM_TH + 2 * b) * (NLM_TW + 2 * b) * 4;
+        const dim3 grid((W + NLM_TW - 1) / NLM_TW, (H + NLM_TH - 1) / NLM_TH, n);
+        const int32_t* tab = static_cast<const int32_t*>(c->p_nlm.p);
+        switch (tw) {
+            case 1: hipLaunchKernelGGL(k_nlm<1>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
+            case 3: hipLaunchKernelGGL(k_nlm<3>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
+            case 5: hipLaunchKernelGGL(k_nlm<5>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
+            default: hipLaunchKernelGGL(k_nlm<7>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
+        }
+        cur ^= 1;
+    }
+    if (st & EINCM_PRE_CLAHE) {
+        uint8_t* lut = static_cast<uint8_t*>(c->p_lut.p);
+        hipLaunchKernelGGL(k_clahe_lut, dim3(tx, ty, n), dim3(NT), 0, c->stream, H, W, clahe_th, clahe_tw, clahe_limit, img[cur], lut);
+        hipLaunchKernelGGL(k_clahe_interp, rows_grid, dim3(NT), 0, c->stream, H, W, clahe_th, clahe_tw, tx, ty, lut, img[cur],
+                           img[cur ^ 1]);
+        cur ^= 1;
+    }
+    if (st & EINCM_PRE_UNSHARP) {
+        uint16_t* rows = static_cast<uint16_t*>(c->p_rows.p);
+        hipLaunchKernelGGL(k_unsharp_rows, rows_grid, dim3(NT), 0, c->stream, H, W, un_r, d_tab, img[cur], rows);
+        hipLaunchKernelGGL(k_unsharp_cols, rows_grid, dim3(NT), 0, c->stream, H, W, un_r, d_tab, (float)p->sharpen_alpha,
+                           (float)p->sharpen_beta, rows, img[cur], img[cur ^ 1]);
+        cur ^= 1;
+    }
+    if (st & EINCM_PRE_BILATERAL) {
+        const size_t lds = (size_t)(BIL_TH + 2 * bil_r) * (BIL_TW + 2 * bil_r) * 4;
+        const dim3 grid((W + BIL_TW - 1) / BIL_TW, (H + BIL_TH - 1) / BIL_TH, n);
+        hipLaunchKernelGGL(k_bilateral, grid, dim3(NT), lds, c->stream, H, W, bil_r, bil_n, d_tab + off_ofs,
+                           reinterpret_cast<const float*>(d_tab + off_w), reinterpret_cast<const float*>(d_tab + off_cw), img[cur],
+                           img[cur ^ 1]);
+        cur ^= 1;
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(dst, img[cur], tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // the host tables stay alive (in the context) until here
     return EINCM_OK;
 }
 

@@ -91,6 +91,91 @@ def check_canny_args(threshold1, threshold2, aperture_size):
     return ths[0], ths[1], 3
 
 
+PREPROCESS_DEFAULTS = dict(denoise_h=4.0, denoise_template_win=3, denoise_search_win=11, clahe_clip_limit=5.0, clahe_tiles=(10, 10),
+                           sharpen_sigma=3.0, sharpen_alpha=1.5, sharpen_beta=-0.5, bilateral_d=5, bilateral_sigma_color=15.0,
+                           bilateral_sigma_space=15.0)
+
+
+def _number(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+        raise ValueError(f'{name} {v!r}: a finite number')
+    return float(v)
+
+
+def _integer(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+        raise ValueError(f'{name} {v!r}: an integer')
+    return int(v)
+
+
+def preprocess_stages(stages):
+    """'all', an EINCM_PRE_* bit mask, a stage name ('nlmeans', 'clahe', 'unsharp', 'bilateral') or an iterable of names."""
+    if isinstance(stages, str):
+        stages = L.PRE_ALL if stages == 'all' else [stages]
+    if isinstance(stages, (int, np.integer)) and not isinstance(stages, bool):
+        mask = int(stages)
+    else:
+        mask = 0
+        for name in stages:
+            if name not in L.PRE_STAGES:
+                raise ValueError(f'stage {name!r}: one of {sorted(L.PRE_STAGES)}')
+            mask |= L.PRE_STAGES[name]
+    if mask < 1 or mask & ~L.PRE_ALL:
+        raise ValueError(f'stages {stages!r}: a non-empty set of the four stages')
+    return mask
+
+
+def make_preprocess_params(shape, stages='all', **kw):
+    """eincm_preprocess_params for a (H, W) sensor, with eincm_preprocess_image's checks made here, before
+    any GPU call.  Keywords and defaults: PREPROCESS_DEFAULTS (the reference's preprocess_image defaults, with sharpen_sigma the
+    sigmaX OpenCV receives); only the selected stages' keywords are checked."""
+    unknown = set(kw) - set(PREPROCESS_DEFAULTS)
+    if unknown:
+        raise TypeError(f'unknown preprocessing arguments {sorted(unknown)}')
+    a = dict(PREPROCESS_DEFAULTS, **kw)
+    H, W = int(shape[0]), int(shape[1])
+    p = L.PreprocessParams()
+    p.stages = mask = preprocess_stages(stages)
+    if mask & L.PRE_NLMEANS:
+        h = _number('denoise_h', a['denoise_h'])
+        tw, sw = _integer('denoise_template_win', a['denoise_template_win']), _integer('denoise_search_win', a['denoise_search_win'])
+        if h <= 0:
+            raise ValueError(f'denoise_h {h!r}: positive')
+        for name, v, top in (('denoise_template_win', tw, 7), ('denoise_search_win', sw, 21)):
+            if v < 1 or v % 2 == 0:
+                raise ValueError(f'{name} {v}: odd and positive')
+            if v > top:
+                raise ValueError(f'{name} {v}: at most {top} is implemented')
+        p.denoise_h, p.denoise_template_win, p.denoise_search_win = h, tw, sw
+    if mask & L.PRE_CLAHE:
+        clip = _number('clahe_clip_limit', a['clahe_clip_limit'])
+        grid = a['clahe_tiles']
+        if not isinstance(grid, (tuple, list)) or len(grid) != 2:
+            raise ValueError(f'clahe_tiles {grid!r}: (tiles_x, tiles_y)')
+        tx, ty = _integer('clahe_tiles', grid[0]), _integer('clahe_tiles', grid[1])
+        if not (1 <= tx <= W and 1 <= ty <= H):
+            raise ValueError(f'clahe_tiles {tx, ty}: (tiles_x, tiles_y) with 1 <= tiles_x <= W = {W}, 1 <= tiles_y <= H = {H}')
+        p.clahe_clip_limit, p.clahe_tiles_x, p.clahe_tiles_y = clip, tx, ty
+    if mask & L.PRE_UNSHARP:
+        sigma = _number('sharpen_sigma', a['sharpen_sigma'])
+        if sigma <= 0:
+            raise ValueError(f'sharpen_sigma {sigma!r}: positive')
+        if round(sigma * 3 * 2 + 1) > 129:
+            raise ValueError(f'sharpen_sigma {sigma!r}: more than 129 blur taps is not implemented')
+        p.sharpen_sigma = sigma
+        p.sharpen_alpha = _number('sharpen_alpha', a['sharpen_alpha'])
+        p.sharpen_beta = _number('sharpen_beta', a['sharpen_beta'])
+    if mask & L.PRE_BILATERAL:
+        d = _integer('bilateral_d', a['bilateral_d'])
+        sc = _number('bilateral_sigma_color', a['bilateral_sigma_color'])
+        ss = _number('bilateral_sigma_space', a['bilateral_sigma_space'])
+        r = d // 2 if d > 0 else round((ss if ss > 0 else 1.0) * 1.5)
+        if r > 32:
+            raise ValueError(f'bilateral_d {d}, sigma_space {ss}: radius {r} > 32 is not implemented')
+        p.bilateral_d, p.bilateral_sigma_color, p.bilateral_sigma_space = d, sc, ss
+    return p
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                 full_aux=False, correlation_kind='mse'):
     """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
@@ -478,6 +563,22 @@ class Engine:
         u8 = C.POINTER(C.c_uint8)
         self._check(self._lib.eincm_canny(self._ctx, a.ctypes.data_as(u8), a.shape[0], th1, th2, ap, 1 if l2_gradient else 0,
                                           out.ctypes.data_as(u8)))
+        return out[0] if single else out
+
+    def preprocess_image(self, imgs, stages='all', **params):
+        """preprocess_image (img_utils.py:131-189): NL-means, CLAHE, unsharp mask, bilateral filter, the stages selected in that
+        order.  imgs: (n,H,W) or (H,W) uint8.  Keywords: PREPROCESS_DEFAULTS.  Returns the same shape."""
+        p = make_preprocess_params((self.H, self.W), stages, **params)
+        a = np.asarray(imgs)
+        if a.dtype != np.uint8:
+            raise ValueError(f'preprocessing input must be uint8, got {a.dtype}')
+        single = a.ndim == 2
+        a = np.ascontiguousarray(a[None] if single else a)
+        if a.ndim != 3 or a.shape[1:] != (self.H, self.W):
+            raise ValueError(f'images must be ({self.H},{self.W}), got {a.shape[1:]}')
+        out = np.empty_like(a)
+        u8 = C.POINTER(C.c_uint8)
+        self._check(self._lib.eincm_preprocess_image(self._ctx, a.ctypes.data_as(u8), a.shape[0], C.byref(p), out.ctypes.data_as(u8)))
         return out[0] if single else out
 
     # -- device images ----------------------------------------------------------------------------

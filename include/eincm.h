@@ -352,6 +352,36 @@ int eincm_gaussian_blur(eincm_ctx* ctx, const double* src, int n, double sigma, 
 int eincm_canny(eincm_ctx* ctx, const uint8_t* src, int n, double threshold1, double threshold2, int aperture_size, int l2_gradient,
                 uint8_t* dst);
 
+/* preprocess_image (img_utils.py:131-189), the clean-up in front of Canny, on 8-bit grayscale images; the stages selected by
+ * `stages` run in this order, each on the previous stage's uint8 output:
+ *   EINCM_PRE_NLMEANS    cv.fastNlMeansDenoising(img, None, denoise_h, denoise_template_win, denoise_search_win), NORM_L2
+ *   EINCM_PRE_CLAHE      cv.createCLAHE(clahe_clip_limit, (clahe_tiles_x, clahe_tiles_y)).apply; tiles_x splits the width
+ *   EINCM_PRE_UNSHARP    cv.addWeighted(img, sharpen_alpha, cv.GaussianBlur(img, None, 0, sharpen_sigma), sharpen_beta, 0): the
+ *                        8-bit fixed-point blur with cvRound(6 sigma + 1) | 1 taps (sharpen_sigma is sigmaX as OpenCV receives it)
+ *   EINCM_PRE_BILATERAL  cv.bilateralFilter(img, bilateral_d, bilateral_sigma_color, bilateral_sigma_space)
+ * Borders are BORDER_REFLECT_101.  src, dst (n, H, W) uint8, H x W = the context's sensor; they may alias.  Only the selected stages'
+ * fields are read.  EINCM_ERR_ARG, before any device work: stages 0 or outside EINCM_PRE_ALL, n < 1, denoise_h <= 0 or
+ * non-finite, even or non-positive window sizes, a tile count below 1 or above its image side, a non-finite clip limit, sharpen_sigma
+ * <= 0 or non-finite, non-finite sharpen weights or bilateral sigmas.  EINCM_ERR_UNSUPPORTED: denoise_template_win > 7,
+ * denoise_search_win > 21, more than 129 blur taps, a bilateral radius above 32.  Integer work and float32 work in a fixed order:
+ * the same bytes on every run and in fp32 and EINCM_CF_FP64 contexts. */
+#define EINCM_PRE_NLMEANS 1
+#define EINCM_PRE_CLAHE 2
+#define EINCM_PRE_UNSHARP 4
+#define EINCM_PRE_BILATERAL 8
+#define EINCM_PRE_ALL 15
+typedef struct eincm_preprocess_params {
+    int32_t stages;                               /* EINCM_PRE_* bits */
+    double denoise_h;                             /* filter strength h */
+    int32_t denoise_template_win, denoise_search_win;   /* odd; <= 7 and <= 21 */
+    double clahe_clip_limit;                      /* <= 0: no clipping */
+    int32_t clahe_tiles_x, clahe_tiles_y;         /* tileGridSize (x splits the width) */
+    double sharpen_sigma, sharpen_alpha, sharpen_beta;
+    int32_t bilateral_d;                          /* <= 0: radius cvRound(1.5 sigma_space) */
+    double bilateral_sigma_color, bilateral_sigma_space;  /* <= 0 becomes 1 */
+} eincm_preprocess_params;
+int eincm_preprocess_image(eincm_ctx* ctx, const uint8_t* src, int n, const eincm_preprocess_params* params, uint8_t* dst);
+
 /* extract_tiles (img_utils.py:105-120) + compute_adaptive_* (contrast_objectives.py:42-87, correlation_objectives.py:105-130)
  * and their pairwise siblings (correlation_objectives.py:28-102), on the images of the LAST evaluation, per (window, ref):
  * contrast-type objectives on the raw IWE (as losses.py:70 does), pair-type ones on (edges, min-max-normalised IWE)
