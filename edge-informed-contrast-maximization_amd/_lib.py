@@ -71,6 +71,9 @@ class TiledOut(C.Structure):
                 ('sum_squared_error', _A), ('mean_hadamard_product', _A), ('sum_hadamard_product', _A), ('joint_contrast', _A)]
 
 
+GTF_DIRECT, GTF_PROPAGATE = 0, 1        # eincm_gt_flow window modes (EINCM_GTF_*)
+GTF_MODES = {'direct': GTF_DIRECT, 'propagate': GTF_PROPAGATE}
+
 EDT_FORMULATIONS = {'exponential': 0, 'linear': 1, 'linear-bound': 2, 'logarithmic': 3}
 
 
@@ -136,6 +139,8 @@ SIGNATURES = [
     ('eincm_tiled_objectives', C.c_int, [_P, C.c_int, C.c_int, C.POINTER(TiledOut)]),
     ('eincm_set_objective_tiles', C.c_int, [_P, C.c_int, C.c_int]),
     ('eincm_set_splat_window', C.c_int, [_P, C.c_int]),
+    ('eincm_gt_flow', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_int32), _D, _D, _D]),
 ]
 
 _lib = None

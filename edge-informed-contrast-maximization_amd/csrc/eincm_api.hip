@@ -27,6 +27,7 @@
 #include "eincm_splat_window.hip.h"
 #include "eincm_canny.hip.h"
 #include "eincm_preprocess.hip.h"
+#include "eincm_gtflow.hip.h"
 
 using namespace eincm;
 
@@ -165,6 +166,8 @@ struct eincm_ctx {
     std::vector<int32_t> h_pre_tab, h_nlm_tab;
     float nlm_hh = 0.0f;
     int nlm_tw = 0, nlm_sw = 0;
+    // scratch of eincm_gt_flow (eincm_gtflow.hip.h), grown on demand: the x and y frame stacks, the step lists, the output
+    DevBuf g_frames, g_tab, g_out;
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
@@ -349,6 +352,7 @@ void free_all(eincm_ctx* c) {
     F(c->d_objc); F(c->d_oparts); c->oparts_cap = 0;
     for (DevBuf* b : {&c->e_u8, &c->e_g, &c->e_sq, &c->e_misc, &c->e_a, &c->e_b, &c->e_kern, &c->e_out}) { F(b->p); b->bytes = 0; }
     for (DevBuf* b : {&c->p_img[0], &c->p_img[1], &c->p_rows, &c->p_tab, &c->p_lut, &c->p_nlm}) { F(b->p); b->bytes = 0; }
+    for (DevBuf* b : {&c->g_frames, &c->g_tab, &c->g_out}) { F(b->p); b->bytes = 0; }
     c->nlm_tw = 0;
     auto FH = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
     FH(c->f64.h_scal); FH(c->h_ovals);
@@ -2701,6 +2705,69 @@ int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(dst, img[cur], tot, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // the host tables stay alive (in the context) until here
+    return EINCM_OK;
+}
+
+// estimate_gt_flow (mvsec_loader.py:322-433) for a batch of windows: the frames and the step lists go up once, k_gt_flow walks every
+// (pixel, window), the (n_windows, H, W, 2) result comes down.
+int eincm_gt_flow(eincm_ctx* c, const void* gt_x, const void* gt_y, int elem_bytes, int n_frames, int n_windows, const int32_t* mode,
+                  const int32_t* step_off, const int32_t* step_frame, const double* step_num, const double* step_den, double* out) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!gt_x || !gt_y || !mode || !step_off || !step_frame || !step_num || !step_den || !out)
+        return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n_frames < 1 || n_windows < 1) return fail(c, EINCM_ERR_ARG, "n_frames = %d, n_windows = %d (both >= 1)", n_frames, n_windows);
+    if (elem_bytes != 4 && elem_bytes != 8) return fail(c, EINCM_ERR_ARG, "elem_bytes = %d (4: float, 8: double)", elem_bytes);
+    if (step_off[0] != 0) return fail(c, EINCM_ERR_ARG, "step_off[0] = %d (must be 0)", step_off[0]);
+    for (int b = 0; b < n_windows; ++b) {
+        const int s0 = step_off[b], s1 = step_off[b + 1];
+        if (mode[b] != EINCM_GTF_DIRECT && mode[b] != EINCM_GTF_PROPAGATE) return fail(c, EINCM_ERR_ARG, "window %d: mode %d unknown", b, mode[b]);
+        if (s1 <= s0) return fail(c, EINCM_ERR_ARG, "window %d has no steps", b);
+        if (mode[b] == EINCM_GTF_DIRECT && s1 - s0 != 1) return fail(c, EINCM_ERR_ARG, "window %d: a direct window has %d steps (1)", b, s1 - s0);
+        for (int k = s0; k < s1; ++k) {
+            if (step_frame[k] < 0 || step_frame[k] >= n_frames)
+                return fail(c, EINCM_ERR_ARG, "window %d step %d: frame %d outside [0, %d)", b, k - s0, step_frame[k], n_frames);
+            if (!std::isfinite(step_num[k])) return fail(c, EINCM_ERR_ARG, "window %d step %d: scale %g is not finite", b, k - s0, step_num[k]);
+            if (mode[b] == EINCM_GTF_DIRECT && (!(step_den[k] != 0.0) || !std::isfinite(step_den[k])))
+                return fail(c, EINCM_ERR_ARG, "window %d: den %g must be finite and non-zero", b, step_den[k]);
+        }
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int H = c->H, W = c->W;
+    const size_t npix = (size_t)H * W, stack = (size_t)n_frames * npix * elem_bytes, n_steps = (size_t)step_off[n_windows];
+    // one upload for the step lists: mode | step_off | step_frame | (8-byte aligned) step_num | step_den
+    const size_t o_off = (size_t)n_windows * 4, o_frame = o_off + ((size_t)n_windows + 1) * 4;
+    const size_t o_num = (o_frame + n_steps * 4 + 7) & ~(size_t)7, o_den = o_num + n_steps * 8, tab_bytes = o_den + n_steps * 8;
+    std::vector<char> tab(tab_bytes, 0);
+    std::memcpy(tab.data(), mode, (size_t)n_windows * 4);
+    std::memcpy(tab.data() + o_off, step_off, ((size_t)n_windows + 1) * 4);
+    std::memcpy(tab.data() + o_frame, step_frame, n_steps * 4);
+    std::memcpy(tab.data() + o_num, step_num, n_steps * 8);
+    std::memcpy(tab.data() + o_den, step_den, n_steps * 8);
+    ENSURE(c, c->g_frames, 2 * stack); ENSURE(c, c->g_tab, tab_bytes); ENSURE(c, c->g_out, (size_t)n_windows * npix * 16);
+    char* d_frames = static_cast<char*>(c->g_frames.p);
+    const char* d_tab = static_cast<const char*>(c->g_tab.p);
+    HIPCHK(c, hipMemcpyAsync(d_frames, gt_x, stack, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_frames + stack, gt_y, stack, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->g_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    const auto* d_mode = reinterpret_cast<const int32_t*>(d_tab);
+    const auto* d_off = reinterpret_cast<const int32_t*>(d_tab + o_off);
+    const auto* d_frame = reinterpret_cast<const int32_t*>(d_tab + o_frame);
+    const auto* d_num = reinterpret_cast<const double*>(d_tab + o_num);
+    const auto* d_den = reinterpret_cast<const double*>(d_tab + o_den);
+    double* d_out = static_cast<double*>(c->g_out.p);
+    const unsigned gx = (unsigned)((npix + NT - 1) / NT);
+    for (int w0 = 0; w0 < n_windows; w0 += GTF_MAX_WINDOWS_PER_LAUNCH) {
+        const dim3 grid(gx, (unsigned)std::min(n_windows - w0, GTF_MAX_WINDOWS_PER_LAUNCH));
+        if (elem_bytes == 4)
+            hipLaunchKernelGGL(k_gt_flow<float>, grid, dim3(NT), 0, c->stream, H, W, w0, reinterpret_cast<const float*>(d_frames),
+                               reinterpret_cast<const float*>(d_frames + stack), d_mode, d_off, d_frame, d_num, d_den, d_out);
+        else
+            hipLaunchKernelGGL(k_gt_flow<double>, grid, dim3(NT), 0, c->stream, H, W, w0, reinterpret_cast<const double*>(d_frames),
+                               reinterpret_cast<const double*>(d_frames + stack), d_mode, d_off, d_frame, d_num, d_den, d_out);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n_windows * npix * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // tab (host vector) stays alive until here
     return EINCM_OK;
 }
 

@@ -1,5 +1,6 @@
 """Python handle on one eincm_ctx (include/eincm.h): a batch of event windows resident on one MI355X."""
 import ctypes as C
+from typing import NamedTuple
 
 import numpy as np
 
@@ -174,6 +175,57 @@ def make_preprocess_params(shape, stages='all', **kw):
             raise ValueError(f'bilateral_d {d}, sigma_space {ss}: radius {r} > 32 is not implemented')
         p.bilateral_d, p.bilateral_sigma_color, p.bilateral_sigma_space = d, sc, ss
     return p
+
+
+class GtFlowPlan(NamedTuple):
+    """One window of eincm_gt_flow, made by evaluation.gt_flow_plan.  mode: 'direct' or 'propagate'; steps: a
+    tuple of (frame, num, den).  A direct window has one step, out = g[frame] * num / den; a propagate window moves every pixel through
+    its steps in order by g[frame] * num (den is 1.0 there and not read)."""
+    mode: str
+    steps: tuple
+
+
+def check_gt_flow_plans(plans, n_frames):
+    """eincm_gt_flow's checks of a list of GtFlowPlan against a stack of n_frames frames, made here before any GPU call.  Returns the
+    (first, last) frame the plans read."""
+    plans = list(plans)
+    if not plans:
+        raise ValueError('no windows')
+    lo, hi = None, None
+    for b, plan in enumerate(plans):
+        mode, steps = plan
+        if mode not in L.GTF_MODES:
+            raise ValueError(f'window {b}: mode {mode!r}, one of {sorted(L.GTF_MODES)}')
+        if len(steps) < 1:
+            raise ValueError(f'window {b} has no steps')
+        if mode == 'direct' and len(steps) != 1:
+            raise ValueError(f'window {b}: a direct window has {len(steps)} steps (1)')
+        for f, num, den in steps:
+            if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or not 0 <= f < n_frames:
+                raise ValueError(f'window {b}: frame {f!r} outside [0, {n_frames})')
+            if not np.isfinite(num):
+                raise ValueError(f'window {b}: scale {num!r} is not finite')
+            if mode == 'direct' and (den == 0 or not np.isfinite(den)):
+                raise ValueError(f'window {b}: den {den!r} must be finite and non-zero')
+            lo = int(f) if lo is None else min(lo, int(f))
+            hi = int(f) if hi is None else max(hi, int(f))
+    return lo, hi
+
+
+def gt_flow_stacks(gt_x, gt_y, sensor_size):
+    """The (n_frames, H, W) x and y flow stacks in the type eincm_gt_flow reads: float32 when both are float32, else float64 (the same
+    output: DESIGN.md section 15)."""
+    gx, gy = np.asarray(gt_x), np.asarray(gt_y)
+    H, W = int(sensor_size[0]), int(sensor_size[1])
+    for name, a in (('gt_x', gx), ('gt_y', gy)):
+        if a.ndim != 3 or a.shape[1:] != (H, W):
+            raise ValueError(f'{name} must be (n_frames, {H}, {W}), got {a.shape}')
+        if a.dtype not in (np.float32, np.float64):
+            raise ValueError(f'{name} must be float32 or float64, got {a.dtype}')
+    if gx.shape != gy.shape:
+        raise ValueError(f'gt_x {gx.shape} and gt_y {gy.shape} differ')
+    dt = np.float32 if gx.dtype == gy.dtype == np.float32 else np.float64
+    return gx.astype(dt, copy=False), gy.astype(dt, copy=False)
 
 
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
@@ -579,6 +631,29 @@ class Engine:
         out = np.empty_like(a)
         u8 = C.POINTER(C.c_uint8)
         self._check(self._lib.eincm_preprocess_image(self._ctx, a.ctypes.data_as(u8), a.shape[0], C.byref(p), out.ctypes.data_as(u8)))
+        return out[0] if single else out
+
+    def gt_flow(self, gt_x, gt_y, plans):
+        """MVSEC's estimate_gt_flow (mvsec_loader.py:322-433) for a batch of windows.  gt_x, gt_y: (n_frames,H,W)
+        float32 or float64 stacks; plans: a list of GtFlowPlan (evaluation.gt_flow_plan), or one.  Only the frames the plans read go
+        to the GPU.  Returns (B,H,W,2) float64, or (H,W,2) for one plan."""
+        single = isinstance(plans, GtFlowPlan)
+        plans = [plans] if single else list(plans)
+        gx, gy = gt_flow_stacks(gt_x, gt_y, (self.H, self.W))
+        f0, f1 = check_gt_flow_plans(plans, gx.shape[0])
+        gx, gy = np.ascontiguousarray(gx[f0:f1 + 1]), np.ascontiguousarray(gy[f0:f1 + 1])
+        mode = np.array([L.GTF_MODES[m] for m, _ in plans], dtype=np.int32)
+        off = np.zeros(len(plans) + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(st) for _, st in plans])
+        steps = [s for _, st in plans for s in st]
+        frame = np.array([int(f) - f0 for f, _, _ in steps], dtype=np.int32)
+        num = np.array([n for _, n, _ in steps], dtype=np.float64)
+        den = np.array([d for _, _, d in steps], dtype=np.float64)
+        out = np.empty((len(plans), self.H, self.W, 2), dtype=np.float64)
+        i32 = C.POINTER(C.c_int32)
+        self._check(self._lib.eincm_gt_flow(self._ctx, gx.ctypes.data, gy.ctypes.data, gx.itemsize, gx.shape[0], len(plans),
+                                            mode.ctypes.data_as(i32), off.ctypes.data_as(i32), frame.ctypes.data_as(i32), _dp(num),
+                                            _dp(den), _dp(out)))
         return out[0] if single else out
 
     # -- device images ----------------------------------------------------------------------------

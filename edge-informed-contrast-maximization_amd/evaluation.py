@@ -5,6 +5,9 @@
                         'counts': n_ee, n_pred, n_gt}
   evaluate_theta_array  mirrors src/evaluations/theta_eval.py:14-95: compute_loss_objectives on the evaluation events
                         (HIP engine, forward only) + flow error + the same ``evals`` keys
+  gt_flow_plan          the index and time arithmetic of MVSECDataLoader.estimate_gt_flow (src/dataloaders/mvsec_loader.py:322-408)
+  estimate_gt_flow      MVSEC's ground-truth flow of evaluation windows: the plans above, walked by one HIP kernel over
+                        (pixel, window)
 The masked reductions are O(H*W), run once per window, and stay on the host; every objective term comes from the GPU.
 """
 import sys
@@ -12,6 +15,7 @@ import sys
 import numpy as np
 
 from . import losses
+from .engine import GtFlowPlan, check_gt_flow_plans
 
 EPSN = sys.float_info.epsilon
 
@@ -77,3 +81,64 @@ def evaluate_theta_array(theta_array, eval_xs, eval_ys, eval_ts, edges, edge_ts,
         'multi_ref_weights': lo['multi_ref_weights'],
     })
     return evals, lo
+
+
+def gt_flow_plan(gt_ts, t_start, t_end):
+    """estimate_gt_flow's index and time arithmetic (mvsec_loader.py:325-400), in float64, as a GtFlowPlan:
+      idx = searchsorted(gt_ts, t_start, 'right') - 1; gt_dt = gt_ts[idx+1] - gt_ts[idx]; dt = t_end - t_start;
+      pre_dt = gt_ts[idx+1] - t_start
+      gt_dt >= dt and pre_dt >= dt:  'direct', one step (idx, dt, gt_dt)
+      otherwise 'propagate':  (idx, pre_dt / gt_dt), then (idx', 1.0) for every idx' = idx+1, ... while gt_ts[idx'+1] < t_end,
+                              then (idx', (t_end - gt_ts[idx']) / (gt_ts[idx'+1] - gt_ts[idx']))   (den 1.0 in every step)
+    Two refusals (ValueError) where the reference misbehaves: t_start before gt_ts[0] (it would read gt[-1], the last frame) and a
+    window that does not end inside the last full GT interval (it raises IndexError).  A non-finite scale or a zero interval in a
+    direct window is a ValueError too."""
+    ts = np.asarray(gt_ts, dtype=np.float64)
+    if ts.ndim != 1 or ts.size < 2:
+        raise ValueError(f'gt_ts must be 1-D with at least two timestamps, got shape {ts.shape}')
+    t_start, t_end = np.float64(t_start), np.float64(t_end)
+    n = ts.size
+    idx = int(np.searchsorted(ts, t_start, side='right')) - 1
+    if idx < 0:
+        raise ValueError(f't_start {t_start!r} precedes the first GT timestamp {ts[0]!r}')
+    past = f'window [{t_start!r}, {t_end!r}] does not end inside the last full GT interval (gt_ts[-1] = {ts[-1]!r})'
+    if idx + 1 >= n:
+        raise ValueError(past)
+    gt_dt = ts[idx + 1] - ts[idx]
+    dt = t_end - t_start
+    pre_dt = ts[idx + 1] - t_start
+    with np.errstate(divide='ignore', invalid='ignore'):
+        if gt_dt >= dt and pre_dt >= dt:
+            plan = GtFlowPlan('direct', ((idx, float(dt), float(gt_dt)),))
+        else:
+            steps = [(idx, float(pre_dt / gt_dt), 1.0)]
+            idx += 1
+            while True:
+                if idx + 1 >= n:
+                    raise ValueError(past)
+                if not ts[idx + 1] < t_end:
+                    break
+                steps.append((idx, 1.0, 1.0))
+                idx += 1
+            steps.append((idx, float((t_end - ts[idx]) / (ts[idx + 1] - ts[idx])), 1.0))
+            plan = GtFlowPlan('propagate', tuple(steps))
+    check_gt_flow_plans([plan], n)
+    return plan
+
+
+def estimate_gt_flow(gt_x, gt_y, gt_ts, t_start, t_end, engine=None):
+    """MVSECDataLoader.estimate_gt_flow (mvsec_loader.py:322-433) on the GPU.  gt_x, gt_y: (n_frames,H,W) float32 or float64 GT flow
+    stacks (already cropped); gt_ts: their (n_frames,) timestamps.  t_start, t_end: scalars, or 1-D arrays of window bounds
+    (broadcast).  One engine call for all windows; engine None: a cached small context per sensor size.  Returns (H,W,2) float64 for
+    scalar bounds, (B,H,W,2) for arrays: the ``flow_gt`` of the reference's datasample."""
+    a, b = np.asarray(t_start, dtype=np.float64), np.asarray(t_end, dtype=np.float64)
+    scalar = a.ndim == 0 and b.ndim == 0
+    a, b = np.broadcast_arrays(np.atleast_1d(a), np.atleast_1d(b))
+    if a.ndim != 1:
+        raise ValueError(f'window bounds must be scalars or 1-D, got shape {a.shape}')
+    plans = [gt_flow_plan(gt_ts, s, e) for s, e in zip(a, b)]
+    if engine is None:
+        from .edges import _engine
+        engine = _engine(np.shape(gt_x)[-2:])
+    out = engine.gt_flow(gt_x, gt_y, plans)
+    return out[0] if scalar else out

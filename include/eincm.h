@@ -414,6 +414,24 @@ int eincm_set_objective_tiles(eincm_ctx* ctx, int tile_h, int tile_w);
 #define EINCM_SPLAT_WINDOW_MAX 7
 int eincm_set_splat_window(eincm_ctx* ctx, int window_size);
 
+/* MVSEC's ground-truth flow of a batch of evaluation windows: estimate_gt_flow / _prop_flow (mvsec_loader.py:322-433) with the index
+ * and time arithmetic done by the caller (evaluation.gt_flow_plan), DESIGN.md section 15.  Window b has mode[b] and the steps
+ * [step_off[b], step_off[b + 1]) of (step_frame, step_num, step_den):
+ *   EINCM_GTF_DIRECT     exactly one step: out = ((double)g[f] * num) / den, x and y (the window fits one GT interval)
+ *   EINCM_GTF_PROPAGATE  each pixel's float32 position walks the steps in order: read the frame's flow at (rintf(cx), rintf(cy)), 0
+ *                        outside the frame or at NaN (cv.remap INTER_NEAREST, constant 0 border); a 0 read clears that component's
+ *                        mask; cx = (float)((double)cx + fx * num), unfused.  out = mask ? (double)(cx - (float)x) : 0, per component.
+ *                        step_den is not read in this mode.
+ * gt_x, gt_y (n_frames, H, W), H x W = the context's sensor, float (elem_bytes 4) or double (elem_bytes 8); a float stack gives the
+ * same output as the same stack widened to double.  out (n_windows, H, W, 2) double.  EINCM_ERR_ARG, before any device work: a null
+ * pointer, n_frames < 1, n_windows < 1, elem_bytes not 4 or 8, an unknown mode, step_off[0] != 0, a window with no steps or a direct
+ * window with more than one, a step_frame outside [0, n_frames), a non-finite step_num, a zero or non-finite step_den.  No reduction
+ * and no atomics: the same bytes on every run and in fp32 and EINCM_CF_FP64 contexts. */
+#define EINCM_GTF_DIRECT 0
+#define EINCM_GTF_PROPAGATE 1
+int eincm_gt_flow(eincm_ctx* ctx, const void* gt_x, const void* gt_y, int elem_bytes, int n_frames, int n_windows, const int32_t* mode,
+                  const int32_t* step_off, const int32_t* step_frame, const double* step_num, const double* step_den, double* out);
+
 #ifdef __cplusplus
 }
 #endif
