@@ -838,6 +838,9 @@ void obj_assemble(eincm_ctx* c) {
 
 int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad, const uint8_t* active = nullptr) {
     HostPhase hp(c, EINCM_HP_BEGIN);
+    // (checked before the mask is touched: the evaluation in flight reads g.wmask again when it is collected)
+    if (c->pend.active && c->pend.launched)
+        return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
     {   // which windows take part (eincm_loss_grad_masked); the others' workgroups leave at once, their outputs are not written
         unsigned long long m = ~0ull;
         if (active) { m = 0ull; for (int b = 0; b < c->g.B && b < 64; ++b) if (active[b]) m |= 1ull << b; }
@@ -849,8 +852,6 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
     const size_t nth = (size_t)h * w * 2;
     const bool full_aux = (p->flags & EINCM_PF_FULL_AUX) != 0;
     const bool div_grad = (p->delta != 0.0 && want_grad);
-    if (c->pend.active && c->pend.launched)
-        return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
     c->pend.active = false; c->pend.launched = false;
     if (div_grad && !c->d_gdiv && !c->fp64) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocate lazily
         HIPCHK(c, dalloc(&c->d_gdiv, (size_t)c->maxB * c->maxR * img));

@@ -396,7 +396,7 @@ class Engine:
             act = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
             if act.shape != (self.B,):
                 raise ValueError(f'active must be ({self.B},), got {act.shape}')
-        self._async = None
+        # (a refused launch - one already in flight - leaves self._async naming that one, so that it can still be collected)
         self._check(self._lib.eincm_loss_grad_masked_async(self._ctx, th.ctypes.data, th.shape[1], th.shape[2], C.byref(params),
                                                            act.ctypes.data if act is not None else None, 1 if want_grad else 0))
         self._async = (th.shape, bool(want_grad))

@@ -49,7 +49,15 @@ def batched_solver(B, H, W, n_lvls, maxiter, hs, n_groups=1):
         B, (H, W), n_lvls, sol.growing_maxiters(n_lvls, maxiter / 5, maxiter), LOSS,
         {'method': 'BFGS', 'options': {'gtol': 1e-7}, 'n_extra_attempts': {'pyr_lvl_0': 1, 'pyr_lvl_1': 1}},
         handover_opt_maxiters=sol.growing_maxiters(n_lvls, 4, 20), handover_opt_solver_params={'method': 'L-BFGS-B', 'options': {'gtol': 1e-6}},
-        handover_settings=hs, pyramid_downscale_method='lanczos3', pyramid_upscale_method='repeat', pyramid_bases=[2] * (n_lvls - 1))
+        handover_settings=hs, pyramid_downscale_method='lanczos3', pyramid_upscale_method='repeat', pyramid_bases=[2] * (n_lvls - 1),
+        n_groups=n_groups)
+
+
+def assert_grouped(bs, B, n_groups):
+    """the solver really runs n_groups contexts, and its groups partition the windows"""
+    assert len(bs.engines) == n_groups, (len(bs.engines), n_groups)
+    assert len(bs.groups) == n_groups
+    assert sorted(int(b) for ix in bs.groups for b in ix) == list(range(B))
 
 
 @pytest.mark.parametrize('n_groups', [1, 2])
@@ -62,6 +70,7 @@ def test_eight_windows_in_lockstep_reach_the_sequential_optima(n_groups):
     args = [(w['xs'], w['ys'], w['ts'], w['edges'], w['edge_ts']) for w in wins]
     bs = batched_solver(B, H, W, n_lvls, 16, None, n_groups)          # n_groups = 2: two contexts, pipelined lockstep
     bs.set_datasamples(args)
+    assert_grouped(bs, B, n_groups)
     out_b = bs.solve()
     N_SEQ_CALLS[0] = 0
     for b in range(B):
@@ -97,6 +106,7 @@ def test_two_sequences_with_handover(n_groups):
     outs = []
     for i in range(2):
         bs.set_datasamples([tup(seqs[b][i]) for b in range(B)])
+        assert_grouped(bs, B, n_groups)
         outs.append(bs.solve())
     bs.close()
     for b in range(B):
