@@ -66,6 +66,28 @@ struct WinFit {
     bool fits;                         // the list's windows fit the largest capacity class
 };
 
+// Every decision of one evaluation, taken once by plan_eval before its first launch; the launch and assembly code only read it.
+struct EvalPlan {
+    enum Shape { IDENTITY, TWO_DOF, GRID } shape = GRID;           // theta (h, w) = the sensor's / (1, 1) / any other grid
+    enum ThetaSrc { THETA_DEVICE, THETA_ARGS, THETA_PINNED, THETA_PIECES } theta_src = THETA_PIECES;   // where k_theta reads theta
+    int h = 0, w = 0; size_t nth = 0;   // nth: doubles of one window's theta
+    bool want_grad = false, full_aux = false, div_grad = false;
+    EvalParams ep{};
+    bool obj = false; ObjGeom og{};     // a contrast / correlation kind other than the defaults (eincm_objectives.hip.h)
+    // LDS windows (fit_window): the splat's and the gather's (into Geom), the 2-DoF gather's, and whether k_splat walks splat_sh
+    int wincap = 0, winmaxw = 0, pitch_aligned = 0, wincap_a = 0, winmaxw_a = 0;
+    WinFit win_2{}; bool splat_short = false;
+    bool use_arg = false, use_arg_big = false;   // theta rides in the arguments of every kernel (ThetaArg) / of k_theta (ThetaArgMid, Big)
+    bool need_theta_image = false;      // k_theta runs (a 2-DoF theta skips it unless somebody reads d_Theta)
+    bool host_asm = false;              // scalar assembly and the 2-DoF gradient sum on the host (see h_g11)
+    bool grid_tail = false;             // host-assembled theta grid: the gather's tail finishes dL/dtheta (and adds the TV term's)
+    bool stream_stats = false, g2_from_imgrad = false;   // k_stats_stream, not k_iwe_finish + k_stats; contrast energy from k_imgrad
+    bool tv_proj = false, proj = false; // k_tv / the theta-grid gather project their tile's gradient onto the theta cells themselves
+    bool all_r = false;                 // ... the gather with one workgroup per segment for all reference times
+    bool events_projected = false; int nsrc = 0;   // k_project's sources: the event term's dL/dTheta image unless projected, the TV term's
+    bool zero_copy_out = false;         // k_final writes the results straight into pinned host memory
+};
+
 }  // namespace
 
 struct eincm_ctx {
@@ -97,6 +119,7 @@ struct eincm_ctx {
     // serves it, and it wants shorter segments than the theta-grid gather does: round-2 tuning)
     SegList gather_2;
     bool policy_evaluated = false; // an evaluation has chosen capacities since the last staging (eincm_get_launch_policy)
+    bool wide = false;             // a window of the staged batch has a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel)
     int pitch_policy = 0;          // the staged batch is in the regime where the bank-aligned LDS pitch pays (set_windows_impl); eval_begin decides per evaluation
     int wincap = WIN_CAP_DEFAULT;
     bool wincap_fixed = false;     // EINCM_WINCAP pins the capacity; otherwise it is chosen per evaluation from max|theta|
@@ -206,16 +229,11 @@ struct eincm_ctx {
     bool G_valid = false;          // d_G holds dL/dIWE of the last evaluation (eincm_get_count_images borrows the buffer)
     int last_nparts = 0;           // how many StatParts per image the last evaluation wrote (k_stats vs k_stats_stream)
     // an evaluation split in two halves (eval_begin ... [caller may all-reduce the IWE stack] ... eval_end)
-    struct { bool active = false; bool launched = false; EvalParams ep{}; int h = 0, w = 0; bool identity = false, want_grad = false, full_aux = false, div_grad = false;
-             WinFit win_2{};                        // the 2-DoF gather's windows in this evaluation
-             bool splat_short = false;              // this evaluation's k_splat walks the short segment list (splat_sh)
-             bool host_asm = false;                 // scalar assembly and the 2-DoF gradient sum on the host (see h_g11)
-             bool tv_projected = false;             // k_tv projected its gradient onto the theta cells itself (no k_project for it)
+    struct { bool active = false, launched = false; EvalPlan plan{};   // (the plan outlives the evaluation: eincm_get_launch_policy)
              int copy_mode = 0;                     // 1: the D2H copies of the results are still to be enqueued (device_results)
-             bool use_arg = false; const double* theta_dev = nullptr; ThetaArg targ{};      // where the event kernels find a 2-DoF theta
-             bool obj = false; ObjGeom og{};        // a contrast / correlation kind other than the defaults (eincm_objectives.hip.h)
+             const double* theta_dev = nullptr; ThetaArg targ{};      // where the event kernels find theta
              } pend;
-    std::vector<uint8_t> theta_nan;    // (B) a NaN / Inf somewhere in window b's theta (host-assembled evaluations)
+    std::vector<uint8_t> theta_nan;    // (B) a NaN / Inf somewhere in window b's theta (host-assembled and float64 evaluations)
     // host-side wall time of the phases of an evaluation (eincm_get_host_profile): a few clock reads per evaluation, always on
     double hp_us[EINCM_N_HOST_PHASES] = {};
     int64_t hp_n = 0;
@@ -497,78 +515,67 @@ void launch_theta_image(eincm_ctx* c, int h, int w, bool identity, bool use_arg,
                         bool with_windows) {
     const Geom& g = c->g;
     const bool ww = with_windows && c->itembase_valid;
-#define THETA_ARGS(T_) dim3(g.ntiles, g.B), dim3(NT), 0, g, h, w, identity ? 1 : 0, use_arg ? 1 : 0, T_, \
-                 theta_dev, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_tilerng, c->d_Theta, c->d_tmm, c->d_edge_ts, \
-                 c->gather.n, c->gather.d_items, ww ? c->gather.d_itembase : nullptr, c->gather.d_wins, \
-                 c->splat.n, c->splat.d_items, ww ? c->splat.d_itembase : nullptr, c->splat.d_wins
+    auto go = [&](auto kernel, const auto& ta) {
+        launch_timed(c, EINCM_STAGE_THETA, kernel, dim3(g.ntiles, g.B), dim3(NT), 0, g, h, w, identity ? 1 : 0, use_arg ? 1 : 0, ta,
+                     theta_dev, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_tilerng, c->d_Theta, c->d_tmm, c->d_edge_ts,
+                     c->gather.n, c->gather.d_items, ww ? c->gather.d_itembase : nullptr, c->gather.d_wins,
+                     c->splat.n, c->splat.d_items, ww ? c->splat.d_itembase : nullptr, c->splat.d_wins);
+    };
     // the argument block is copied by value into the launch and again into the kernarg buffer: 4 KiB where theta fits (one window at 16x16)
     if (!use_arg || (size_t)g.B * h * w * 2 <= (size_t)THETA_ARG_MID) {
         ThetaArgMid mid;
         if (use_arg) memcpy(mid.v, targ.v, (size_t)g.B * h * w * 2 * sizeof(double));
-        launch_timed(c, EINCM_STAGE_THETA, k_theta<ThetaArgMid>, THETA_ARGS(mid));
+        go(k_theta<ThetaArgMid>, mid);
     } else {
-        launch_timed(c, EINCM_STAGE_THETA, k_theta<ThetaArgBig>, THETA_ARGS(targ));
+        go(k_theta<ThetaArgBig>, targ);
     }
-#undef THETA_ARGS
     c->Theta_valid = true;
 }
 
-// Launch the forward half: theta -> Theta -> u64 IWE accumulator.
-// need_theta_image: somebody will read d_Theta (TV term); 2-DoF evaluations otherwise skip the image altogether.
-int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_image, const double* theta_host, bool host_asm) {
+// Launch the forward half of the planned evaluation (pend.plan): theta -> Theta -> u64 IWE accumulator.
+int launch_forward(eincm_ctx* c, const double* theta_host) {
+    const EvalPlan& P = c->pend.plan;
     const Geom& g = c->g;
-    const size_t nth = (size_t)h * w * 2;
-    const bool use_arg = !c->theta_dev_in && !identity && (size_t)g.B * nth <= (size_t)THETA_ARG_MAX;
-    const bool const_theta = !identity && h == 1 && w == 1;
-    const double* theta_dev = c->d_theta_in;
+    const bool two_dof = P.shape == EvalPlan::TWO_DOF;
+    const size_t nall = (size_t)g.B * P.nth;
     ThetaArg targ;
-    // k_theta alone takes a larger theta in its own arguments (a 16x16 grid of one window: 4 KiB); the event kernels read the Theta image
-    static const bool no_big_arg = getenv("EINCM_NO_BIG_THETA_ARG") != nullptr;
-    const bool use_arg_big = !c->theta_dev_in && !identity && (size_t)g.B * nth <= (size_t)THETA_ARG_BIG && !no_big_arg;
     static thread_local ThetaArgBig targ_big;
-    if (use_arg_big) memcpy(targ_big.v, theta_host, (size_t)g.B * nth * sizeof(double));
-    if (c->theta_dev_in) {
-        theta_dev = c->theta_dev_in;                 // device-resident theta: the kernels read the caller's buffer, nothing crosses PCIe
-        if (const_theta) need_theta_image = true;    // (no host copy of theta for ensure_theta_image to rebuild the image from)
-    } else if (use_arg) {
-        memcpy(targ.v, theta_host, (size_t)g.B * nth * sizeof(double));     // theta rides in the kernel arguments
-        if (!use_arg_big) { memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double)); theta_dev = c->h_theta; }   // (k_theta reads memory then)
-    } else if (use_arg_big) {
-        // k_theta has theta in its arguments; a 2-DoF theta is also read by k_theta_const, k_splat and the gather (B * 2 doubles)
-        if (const_theta) memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double));
+    if (P.use_arg_big) memcpy(targ_big.v, theta_host, nall * sizeof(double));
+    if (P.use_arg) memcpy(targ.v, theta_host, nall * sizeof(double));      // theta rides in the kernel arguments
+    const double* theta_dev = P.use_arg ? c->d_theta_in : c->h_theta;      // (not read where every kernel has theta in its arguments)
+    if (P.theta_src == EvalPlan::THETA_DEVICE) {            // the kernels read the caller's buffer, nothing crosses PCIe
+        theta_dev = c->theta_dev_in;
+    } else if (P.theta_src == EvalPlan::THETA_PINNED) {     // read straight from the pinned, GPU-mapped staging buffer (no copy command)
+        memcpy(c->h_theta, theta_host, nall * sizeof(double));
         theta_dev = c->h_theta;
-    } else if ((size_t)g.B * nth <= ZERO_COPY_MAX) {
-        // medium theta (e.g. 16x16): k_theta reads it straight from the pinned, GPU-mapped staging buffer (no copy command)
-        memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double));
-        theta_dev = c->h_theta;
-    } else {
+    } else if (P.theta_src == EvalPlan::THETA_PIECES) {
         // dense theta (4.9 MB at 480x640): staged through pinned memory in a few pieces, so that the DMA of one piece runs while the
         // host copies the next (one memcpy + one DMA back to back: 131 + 187 us)
         StageTimer t(c, EINCM_STAGE_COPY);
-        const size_t total = (size_t)g.B * nth;
-        const size_t piece = std::max<size_t>((total + 5) / 6, (size_t)32768);
-        for (size_t off = 0; off < total; off += piece) {
-            const size_t n = std::min(piece, total - off);
+        const size_t piece = std::max<size_t>((nall + 5) / 6, (size_t)32768);
+        for (size_t off = 0; off < nall; off += piece) {
+            const size_t n = std::min(piece, nall - off);
             memcpy(c->h_theta + off, theta_host + off, n * sizeof(double));
             HIPCHK(c, hipMemcpyAsync(c->d_theta_in + off, c->h_theta + off, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         }
+        theta_dev = c->d_theta_in;
     }
     {
-        StageTimer t(c, EINCM_STAGE_THETA, const_theta ? !need_theta_image : c->itembase_valid);       // one kernel in either case
+        StageTimer t(c, EINCM_STAGE_THETA, two_dof ? !P.need_theta_image : c->itembase_valid);       // one kernel in either case
         const SegList &ga = c->gather, &sp = c->splat;
         const int nwin_threads = (ga.n + sp.n) * g.R;
-        if (const_theta) {
+        if (two_dof) {
             if (theta_host) c->last_theta11.assign(theta_host, theta_host + (size_t)g.B * 2); else c->last_theta11.clear();
             c->Theta_valid = false;
-            if (need_theta_image) launch_theta_image(c, h, w, identity, use_arg_big, targ_big, theta_dev, false);
+            if (P.need_theta_image) launch_theta_image(c, P.h, P.w, false, P.use_arg_big, targ_big, theta_dev, false);
             // the event kernels derive their windows from theta themselves; the velocity bounds (tmm) only feed k_final's NaN scan,
             // which a host-assembled evaluation does on the host
-            if (!host_asm)
+            if (!P.host_asm)
                 launch_timed(c, EINCM_STAGE_THETA, k_theta_const, dim3((std::max(g.B * g.ntiles, nwin_threads) + NT - 1) / NT), dim3(NT), 0, g,
-                                   use_arg ? 1 : 0, targ, theta_dev, c->d_tmm, c->d_edge_ts, ga.n, ga.d_items, ga.d_wins,
+                                   P.use_arg ? 1 : 0, targ, theta_dev, c->d_tmm, c->d_edge_ts, ga.n, ga.d_items, ga.d_wins,
                                    sp.n, sp.d_items, sp.d_wins);
         } else {
-            launch_theta_image(c, h, w, identity, use_arg_big, targ_big, theta_dev, true);
+            launch_theta_image(c, P.h, P.w, P.shape == EvalPlan::IDENTITY, P.use_arg_big, targ_big, theta_dev, true);
             if (nwin_threads > 0 && !c->itembase_valid)
                 hipLaunchKernelGGL(k_windows, dim3((nwin_threads + NT - 1) / NT), dim3(NT), 0, c->stream, g, c->d_tmm, c->d_edge_ts,
                                    ga.n, ga.d_items, ga.d_wins, sp.n, sp.d_items, sp.d_wins);
@@ -578,35 +585,33 @@ int launch_forward(eincm_ctx* c, int h, int w, bool identity, bool need_theta_im
         StageTimer t(c, EINCM_STAGE_SPLAT, true);
         c->acc_dirty = true;
         if (c->splat.n > 0) {
-            const int theta_mode = const_theta ? THETA_CONST : THETA_TILE;
-            const size_t lds_bytes = (size_t)g.wincap * sizeof(float) + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
-            const SegList& L = c->pend.splat_short && const_theta ? c->splat_sh : c->splat;      // (2-DoF theta derives its windows itself)
-#define SPLAT_ARGS(NTH) dim3(L.grid(g.R)), dim3(NTH), lds_bytes, g, L.n, \
-                   L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, L.d_order, \
-                   use_arg ? 1 : 0, theta_dev, targ
-            // 512 threads per workgroup in both compile-time modes: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
-            // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
+            const SegList& L = P.splat_short ? c->splat_sh : c->splat;      // (a 2-DoF theta derives its windows itself)
+            const size_t theta_tile = two_dof ? 0 : TS * TS * sizeof(double2);     // LDS beside the window
+            const int use_arg = P.use_arg ? 1 : 0;
             if (c->splat_rad != 1) {
                 // another splat window (eincm_splat_window.hip.h): u64 LDS windows, capped so that they fit beside the Theta tile
                 Geom gs = g;
-                gs.wincap = std::min(g.wincap, theta_mode == THETA_TILE ? SW_CAP_TILE : SW_CAP_CONST);
+                gs.wincap = std::min(g.wincap, two_dof ? SW_CAP_CONST : SW_CAP_TILE);
                 gs.winmaxw = win_maxw(gs.wincap);
-                const size_t lds_r = (size_t)gs.wincap * sizeof(unsigned long long) + (theta_mode == THETA_TILE ? TS * TS * sizeof(double2) : 0);
-#define SPLAT_R_ARGS dim3(L.grid(g.R)), dim3(NT), lds_r, gs, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_acc, \
-                     L.d_order, use_arg ? 1 : 0, theta_dev, targ
-#define SPLAT_R(TM_) do { if (c->splat_rad == 0) launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 0>, SPLAT_R_ARGS); \
-                          else if (c->splat_rad == 2) launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 2>, SPLAT_R_ARGS); \
-                          else launch_timed(c, EINCM_STAGE_SPLAT, k_splat_r<TM_, 3>, SPLAT_R_ARGS); } while (0)
-                if (theta_mode == THETA_CONST) SPLAT_R(THETA_CONST); else SPLAT_R(THETA_TILE);
-#undef SPLAT_R
-#undef SPLAT_R_ARGS
-            } else if (theta_mode == THETA_CONST) launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_CONST, 512>, SPLAT_ARGS(512));
-            else                           launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_TILE, 512>, SPLAT_ARGS(512));
-#undef SPLAT_ARGS
+                auto go = [&](auto kernel) {
+                    launch_timed(c, EINCM_STAGE_SPLAT, kernel, dim3(L.grid(g.R)), dim3(NT), (size_t)gs.wincap * sizeof(unsigned long long) + theta_tile,
+                                 gs, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_acc, L.d_order, use_arg, theta_dev, targ);
+                };
+                if (two_dof) c->splat_rad == 0 ? go(k_splat_r<THETA_CONST, 0>) : c->splat_rad == 2 ? go(k_splat_r<THETA_CONST, 2>) : go(k_splat_r<THETA_CONST, 3>);
+                else         c->splat_rad == 0 ? go(k_splat_r<THETA_TILE, 0>) : c->splat_rad == 2 ? go(k_splat_r<THETA_TILE, 2>) : go(k_splat_r<THETA_TILE, 3>);
+            } else {
+                // 512 threads per workgroup in both compile-time modes: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
+                // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
+                auto go = [&](auto kernel) {
+                    launch_timed(c, EINCM_STAGE_SPLAT, kernel, dim3(L.grid(g.R)), dim3(512), (size_t)g.wincap * sizeof(float) + theta_tile, g, L.n,
+                                 L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, L.d_order, use_arg, theta_dev, targ);
+                };
+                two_dof ? go(k_splat<THETA_CONST, 512>) : go(k_splat<THETA_TILE, 512>);
+            }
         }
     }
     HIPCHK(c, hipGetLastError());
-    c->pend.use_arg = use_arg; c->pend.theta_dev = theta_dev; c->pend.targ = targ;
+    c->pend.theta_dev = theta_dev; c->pend.targ = targ;
     return EINCM_OK;
 }
 
@@ -639,21 +644,50 @@ int collect_timings(eincm_ctx* c) {
     return (c->ring_size == 1) ? drain_event_ring(c, 0) : EINCM_OK;
 }
 
+// Window b's TV term as the aux reports it (losses.py:171; NAN: not computed): regularizers.py:14-38 from k_tv's partials, in tile order
+double window_tv(const eincm_ctx* c, const EvalParams& ep, int b) {
+    if (!ep.want_tv) return ep.cur_pyr_lvl <= 0 ? NAN : 0.0;
+    const double* q = c->h_tvparts + (size_t)b * c->g.ntiles * 3;
+    double a = 0.0, nz = 0.0;
+    for (int i = 0; i < c->g.ntiles; ++i) { a += q[(size_t)i * 3]; nz += q[(size_t)i * 3 + 1]; }
+    return a / (nz + EPSN);
+}
+
+// One window's value and aux entries (losses.py:176-203) from the sums over reference times of mrw_r * term_r / (zero-warp term + EPSN);
+// mrd, tv: NAN where not computed.  host_assemble (tv_direct) adds gamma * TV straight to the value where the TV was computed, the others
+// add the regularisers' sum: with delta == 0 (every host-assembled evaluation) the two differ in the sign of a zero value only.
+void assemble_window(const EvalParams& ep, int R, double sum_con, double sum_corr, double mrd, double tv, bool theta_bad, bool tv_direct,
+                     OutScal& o) {
+    const double mrc = sum_con / (double)R, mrr = sum_corr / (double)R;
+    double val = ep.alpha * (-mrc) + ep.beta * (-mrr);
+    if (tv_direct) {
+        if (ep.want_tv && ep.gamma != 0.0) val += ep.gamma * tv;
+    } else {
+        double reg = 0.0;
+        if (ep.gamma != 0.0) reg += ep.gamma * ((ep.cur_pyr_lvl <= 0) ? tv : 0.0);
+        if (ep.delta != 0.0) reg += ep.delta * mrd;
+        val += reg;
+    }
+    if (theta_bad) val = NAN;
+    o.mean_rel_contrast = mrc; o.mean_rel_corr = mrr; o.mean_rel_div = mrd; o.tv = tv;
+    o.value = val;
+    o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
+}
+
 // The whole evaluation of a float64 context (EINCM_CF_FP64), enqueued at once: theta -> Theta (k_theta) -> k64_splat -> image passes
 // [-> k_tv] [-> dL/dIWE -> k64_gather -> k64_gfin -> projection] -> results into pinned memory.  eval_end_collect waits and f64_assemble
 // adds the scalars up on the host in index order.  None of the fp32 path's launch policy applies: one segment list, one launch form.
-int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalParams& ep, bool want_grad, bool full_aux, bool div_grad,
-               bool identity) {
+int f64_launch(eincm_ctx* c, const double* theta_host) {
+    const EvalPlan& P = c->pend.plan;
+    const EvalParams& ep = P.ep;
     const Geom& g = c->g;
-    const size_t img = (size_t)g.H * g.W, nth = (size_t)h * w * 2;
-    c->theta_nan.assign((size_t)g.B, 0);
-    for (int b = 0; b < g.B; ++b)
-        for (size_t i = 0; i < nth; ++i) if (!std::isfinite(theta_host[(size_t)b * nth + i])) { c->theta_nan[b] = 1; break; }
+    const int h = P.h, w = P.w;
+    const size_t img = (size_t)g.H * g.W, nth = P.nth;
     memcpy(c->h_theta, theta_host, (size_t)g.B * nth * sizeof(double));
     HIPCHK(c, hipMemcpyAsync(c->d_theta_in, c->h_theta, (size_t)g.B * nth * sizeof(double), hipMemcpyHostToDevice, c->stream));
     static const ThetaArgBig targ{};
-    launch_theta_image(c, h, w, identity, false, targ, c->d_theta_in, false);
-    if (!identity && h == 1 && w == 1) c->last_theta11.assign(theta_host, theta_host + (size_t)g.B * 2);
+    launch_theta_image(c, h, w, P.shape == EvalPlan::IDENTITY, false, targ, c->d_theta_in, false);
+    if (P.shape == EvalPlan::TWO_DOF) c->last_theta11.assign(theta_host, theta_host + (size_t)g.B * 2);
     HIPCHK(c, hipMemsetAsync(c->f64.gmax, 0, (size_t)g.B * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->f64.bad, 0, (size_t)g.B * sizeof(unsigned), c->stream));
     // both event kernels walk the gather's list and copy of the events (sorted by source pixel; the splat's spread copy measured
@@ -665,16 +699,16 @@ int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalP
     const dim3 gimg(c->f64.P, g.R, g.B);
     hipLaunchKernelGGL(k64_img_a, gimg, dim3(NT), 0, c->stream, g, c->f64.ishift, c->f64.acc, c->f64.iwe, c->f64.partA);
     hipLaunchKernelGGL(k64_img_b, gimg, dim3(NT), 0, c->stream, g, c->f64.iwe, c->f64.edges, c->f64.partA, c->f64.partB, ep.want_div,
-                       div_grad ? c->f64.sgn : nullptr);
+                       P.div_grad ? c->f64.sgn : nullptr);
     hipLaunchKernelGGL(k64_scal, dim3(g.R, g.B), dim3(NT), 0, c->stream, g, c->f64.P, c->f64.partA, c->f64.partB, c->f64.scal);
     HIPCHK(c, hipMemcpyAsync(c->f64.h_scal, c->f64.scal, (size_t)g.B * g.R * sizeof(F64Scal), hipMemcpyDeviceToHost, c->stream));
     if (ep.want_tv)            // shared with the fp32 path: k_tv is fp64 throughout; its partials also land in pinned memory for f64_assemble
         hipLaunchKernelGGL(k_tv<0>, dim3(g.ntiles, g.B), dim3(NT), 0, c->stream, g, c->d_Theta, c->d_mask, c->d_tvg, c->d_tvparts,
-                           full_aux ? 1 : 0, h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth + (size_t)c->maxB * c->coarse_cap,
+                           P.full_aux ? 1 : 0, h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth + (size_t)c->maxB * c->coarse_cap,
                            (int)c->coarse_cap, c->h_tvparts);
-    if (want_grad) {
+    if (P.want_grad) {
         hipLaunchKernelGGL(k64_grad1, gimg, dim3(NT), 0, c->stream, g, ep, c->f64.iwe, c->f64.edges, c->f64.scal, c->d_wc,
-                           div_grad ? c->f64.sgn : nullptr, c->f64.G, c->f64.partC);
+                           P.div_grad ? c->f64.sgn : nullptr, c->f64.G, c->f64.partC);
         hipLaunchKernelGGL(k64_grad2, gimg, dim3(NT), 0, c->stream, g, c->f64.iwe, c->f64.scal, c->f64.partC, c->f64.G, c->f64.gmax,
                            c->f64.bad);
         if (L.n > 0)
@@ -684,7 +718,7 @@ int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalP
         hipLaunchKernelGGL(k64_gfin, dim3(nblk, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, ep.gamma, c->d_tvparts, c->d_tvg, c->d_wc,
                            c->f64.gmax, c->f64.gacc, c->f64.bad, c->f64.gTh);
         const double* out = c->f64.gTh;
-        if (!identity) {
+        if (P.shape != EvalPlan::IDENTITY) {
             // the intermediate goes through T, of capacity (B,H,W,2): columns first, (B,H,w,2), unless theta is wider than the sensor;
             // then h < H (h * w <= H * W) and the rows go first, (B,h,W,2)
             const size_t nO = (size_t)g.B * nth;
@@ -707,16 +741,14 @@ int f64_launch(eincm_ctx* c, const double* theta_host, int h, int w, const EvalP
     }
     HIPCHK(c, hipGetLastError());
     c->n_pieces = 0;
-    c->pend.active = true; c->pend.launched = true; c->pend.ep = ep; c->pend.h = h; c->pend.w = w; c->pend.identity = identity;
-    c->pend.want_grad = want_grad; c->pend.full_aux = full_aux; c->pend.div_grad = div_grad; c->pend.host_asm = false;
-    c->pend.copy_mode = 0;
+    c->pend.active = true; c->pend.launched = true; c->pend.copy_mode = 0;
     return EINCM_OK;
 }
 
 // What k_final does, for a float64 evaluation: losses.py:176-203 from the per-image scalars and k_tv's partials, sums in index order.
 void f64_assemble(eincm_ctx* c) {
     const Geom& g = c->g;
-    const EvalParams& ep = c->pend.ep;
+    const EvalParams& ep = c->pend.plan.ep;
     const double Rd = (double)g.R;
     for (int b = 0; b < g.B; ++b) {
         const WinConst& wc = c->h_wc[b];
@@ -734,27 +766,10 @@ void f64_assemble(eincm_ctx* c) {
             srr += wc.mrw[r] * corr / (wc.zc[r] + EPSN);
             srd += wc.mrw[r] * div / (wc.d0 + EPSN);
         }
-        const double mrc = src / Rd, mrr = srr / Rd, mrd = ep.want_div ? srd / Rd : NAN;
-        double val = ep.alpha * (-mrc) + ep.beta * (-mrr);
-        double tv = 0.0;
-        if (ep.want_tv) {
-            double a = 0.0, nz = 0.0;
-            for (int i = 0; i < g.ntiles; ++i) { a += c->h_tvparts[((size_t)b * g.ntiles + i) * 3]; nz += c->h_tvparts[((size_t)b * g.ntiles + i) * 3 + 1]; }
-            tv = a / (nz + EPSN);
-        }
-        double reg = 0.0;
-        if (ep.gamma != 0.0) reg += ep.gamma * ((ep.cur_pyr_lvl <= 0) ? tv : 0.0);
-        if (ep.delta != 0.0) reg += ep.delta * mrd;
-        val += reg;
-        if (c->theta_nan[b]) val = NAN;
-        o.mean_rel_contrast = mrc; o.mean_rel_corr = mrr; o.mean_rel_div = mrd;
-        o.tv = (ep.cur_pyr_lvl <= 0) ? (ep.want_tv ? tv : NAN) : 0.0;
-        o.value = val;
-        o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
+        assemble_window(ep, g.R, src, srr, ep.want_div ? srd / Rd : NAN, window_tv(c, ep, b), c->theta_nan[b] != 0, false, o);
     }
 }
 
-// First half of an evaluation: theta -> Theta -> IWE stack (k_theta, k_splat).  theta_host: (B,h,w,2) doubles.
 // ---- selectable objective kinds (eincm_objectives.hip.h) ----
 ObjGeom obj_geom(const eincm_ctx* c, int ck, int rk, int need) {
     ObjGeom og{};
@@ -808,34 +823,146 @@ int obj_constants(eincm_ctx* c) {
 // per-image values, the zero-warp values), on top of what k_final / host_assemble left for the TV and divergence terms.
 void obj_assemble(eincm_ctx* c) {
     const Geom& g = c->g;
-    const EvalParams& ep = c->pend.ep;
-    const int ck = c->pend.og.ck, rk = c->pend.og.rk;
+    const EvalPlan& P = c->pend.plan;
+    const int ck = P.og.ck, rk = P.og.rk;
     for (int b = 0; b < g.B; ++b) {
         if (b < 64 && !((g.wmask >> b) & 1ull)) continue;
         OutScal& o = c->h_outs[b];
         const ObjConst& oc = c->h_objc[b];
         const WinConst& wc = c->h_wc[b];
         // a NaN theta: host_assemble marks it in theta_nan, k_final in its (default-kind) value
-        const bool bad = c->pend.host_asm ? c->theta_nan[b] != 0 : std::isnan(o.value);
+        const bool bad = P.host_asm ? c->theta_nan[b] != 0 : std::isnan(o.value);
         double sum_rel_con = 0.0, sum_rel_corr = 0.0;
         for (int r = 0; r < g.R; ++r) {
             const double con = c->h_ovals[((size_t)b * g.R + r) * 2], corr = c->h_ovals[((size_t)b * g.R + r) * 2 + 1];
             sum_rel_con += wc.mrw[r] * con / (oc.c0[ck] + EPSN);
             sum_rel_corr += wc.mrw[r] * corr / (oc.zc[rk][r] + EPSN);
         }
-        const double mrc = sum_rel_con / (double)g.R, mrr = sum_rel_corr / (double)g.R;
-        double val = ep.alpha * (-mrc) + ep.beta * (-mrr);
-        double reg = 0.0;
-        if (ep.gamma != 0.0) reg += ep.gamma * ((ep.cur_pyr_lvl <= 0) ? o.tv : 0.0);
-        if (ep.delta != 0.0) reg += ep.delta * o.mean_rel_div;
-        val += reg;
-        if (bad) val = NAN;
-        o.mean_rel_contrast = mrc; o.mean_rel_corr = mrr;
-        o.value = val;
-        o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
+        assemble_window(P.ep, g.R, sum_rel_con, sum_rel_corr, o.mean_rel_div, o.tv, bad, false, o);
     }
 }
 
+// ---- the plan of an evaluation ----
+EvalPlan::Shape theta_shape(const Geom& g, int h, int w) {
+    return (h == g.H && w == g.W) ? EvalPlan::IDENTITY : (h == 1 && w == 1) ? EvalPlan::TWO_DOF : EvalPlan::GRID;
+}
+int correlation_kind(const eincm_params* p) { return (int)((p->flags & EINCM_PF_CORRELATION_MASK) >> 8); }
+bool other_kinds(const eincm_params* p) { return p->contrast_kind > EINCM_CONTRAST_VARIANCE || correlation_kind(p) != EINCM_CORRELATION_MSE; }
+
+// Every decision of one evaluation, from the context's state and the call's checked arguments.  No side effects (eval_begin's).
+EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad) {
+    const Geom& g = c->g;
+    EvalPlan P;
+    P.shape = theta_shape(g, h, w);
+    const bool identity = P.shape == EvalPlan::IDENTITY, two_dof = P.shape == EvalPlan::TWO_DOF;
+    P.h = h; P.w = w; P.nth = (size_t)h * w * 2;
+    P.want_grad = want_grad;
+    P.full_aux = (p->flags & EINCM_PF_FULL_AUX) != 0;
+    P.div_grad = p->delta != 0.0 && want_grad;
+    EvalParams& ep = P.ep;
+    ep.alpha = p->alpha; ep.beta = p->beta; ep.gamma = p->gamma; ep.delta = p->delta;
+    ep.cur_pyr_lvl = p->cur_pyr_lvl; ep.contrast_kind = p->contrast_kind;
+    ep.want_div = (P.full_aux || p->delta != 0.0) ? 1 : 0;
+    ep.want_tv = ((p->cur_pyr_lvl <= 0) && (p->gamma != 0.0 || P.full_aux)) ? 1 : 0;
+    ep.use_tv_grad = (ep.want_tv && p->gamma != 0.0 && want_grad && !(p->flags & EINCM_PF_NO_TV_GRAD)) ? 1 : 0;
+    ep.h = h; ep.w = w; ep.identity = identity ? 1 : 0;
+    P.obj = other_kinds(p);
+    const int ck = p->contrast_kind, rk = correlation_kind(p);
+    if (P.obj) P.og = obj_geom(c, ck, rk, (ck == EINCM_CONTRAST_ADAPTIVE_GRAD_MAG ? OBJ_NEED_TILE_GM : 0) |
+                                          ((ck == EINCM_CONTRAST_GRAD_MAG || rk == EINCM_CORRELATION_JOINT_CONTRAST) ? OBJ_NEED_GM : 0) |
+                                          (rk == EINCM_CORRELATION_JOINT_CONTRAST ? OBJ_NEED_JOINT : 0));
+    if (c->fp64) return P;          // f64_launch: one segment list, one launch form, none of the launch policy below
+    const size_t nall = (size_t)g.B * P.nth;
+
+    // theta in the kernel arguments: up to THETA_ARG_MAX doubles in every kernel's; k_theta alone takes a larger one in its own (a 16x16
+    // grid of one window: 4 KiB), the event kernels then read the Theta image, or a 2-DoF theta from the pinned staging buffer
+    static const bool no_big_arg = getenv("EINCM_NO_BIG_THETA_ARG") != nullptr;
+    P.use_arg = !c->theta_dev_in && !identity && nall <= (size_t)THETA_ARG_MAX;
+    P.use_arg_big = !c->theta_dev_in && !identity && nall <= (size_t)THETA_ARG_BIG && !no_big_arg;
+    P.theta_src = c->theta_dev_in ? EvalPlan::THETA_DEVICE
+                : (P.use_arg_big && (P.use_arg || !two_dof)) ? EvalPlan::THETA_ARGS
+                : nall <= ZERO_COPY_MAX ? EvalPlan::THETA_PINNED : EvalPlan::THETA_PIECES;
+    // (device-resident theta: no host copy for ensure_theta_image to rebuild the image from)
+    P.need_theta_image = !two_dof || ep.want_tv || c->theta_dev_in;
+
+    // LDS window capacity for this evaluation: the host knows theta, hence the largest displacement a segment can see.
+    // Small windows give 8 workgroups per CU; windows too small for the flow push taps onto the slow direct-to-HBM path.
+    P.wincap = g.wincap; P.winmaxw = g.winmaxw; P.wincap_a = g.wincap_a; P.winmaxw_a = g.winmaxw_a;
+    P.pitch_aligned = c->pitch_policy != 0 ? 1 : 0;
+    P.win_2 = WinFit{c->wincap, win_maxw(c->wincap), c->pitch_policy >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
+    if (!c->wincap_fixed) {
+        double vmax = 0.0;
+        const size_t stride = nall > 8192 ? nall / 8192 : 1;            // dense theta: sample (any capacity is correct; 65536 samples cost 90 us)
+        if (c->theta_dev_in) vmax = (c->vmax_hint >= 0.0 && std::isfinite(c->vmax_hint)) ? c->vmax_hint : 1e9;      // unknown: the largest windows
+        else if (stride == 1) { for (size_t i = 0; i < nall; ++i) { const double a = std::fabs(theta_host[i]); vmax = std::max(vmax, a <= 1.7e308 ? a : 0.0); } }   // (vectorises)
+        else for (size_t i = 0; i < nall; i += stride) { const double a = std::fabs(theta_host[i]); if (a > vmax && std::isfinite(a)) vmax = a; }
+        // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
+        const double margin = 2.0 * (c->splat_rad + 1);
+        // Where a larger window costs no residency it is taken at once (a capacity is an allocation, the windows themselves stay as small
+        // as their segments need): the 2-DoF kernels hold nothing but the window in LDS, 4608 words = 18 KiB still gives the 8 workgroups
+        // of 4 waves a CU can hold; the theta-grid gather carries 32 KiB beside its window and runs 3 workgroups per CU up to 5461 words.
+        // The theta-grid splat (window + 16 KiB Theta tile) pays for capacity with workgroups per CU (6 / 5 / 4 / 3), so it takes what it needs.
+        // Each list's windows are sized for its time span: what all but 3 % of the events' segments stay within (build_list; the mean
+        // tile would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
+        const int floor_s = two_dof ? 2 : 0, pitch_s = c->pitch_policy != 0 ? 1 : 0;
+        WinFit s = fit_window(vmax, c->splat.tspan, margin, floor_s, pitch_s);
+        // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
+        // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
+        P.splat_short = two_dof && c->splat_sh.n > 0 && !s.fits;
+        if (P.splat_short) s = fit_window(vmax, c->splat_sh.tspan, margin, floor_s, pitch_s);
+        P.wincap = s.cap; P.winmaxw = s.maxw; P.pitch_aligned = s.pal ? 1 : 0;
+        // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
+        // sends taps down the direct path
+        const WinFit a = fit_window(vmax, c->gather.tspan, margin, 2, -1);
+        P.wincap_a = a.cap; P.winmaxw_a = a.maxw;
+        // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
+        // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
+        P.win_2 = fit_window(vmax, c->gather_2.tspan, margin, 2, c->pitch_policy >= 2 ? 1 : 0);
+    }
+
+    // 2-DoF theta with nothing but the contrast and correlation terms (every level above 0 of the reference's pyramid at its first
+    // level, and the bench workload), or a theta grid whose gather's tail finishes the gradient (not with another splat window), TV
+    // included (k_tv projects its own gradient, the tail combines it; a 2-DoF theta with TV keeps k_final): host assembly
+    static const bool no_host_asm = getenv("EINCM_NO_HOST_ASM") != nullptr;
+    const bool tail_ok = c->splat_rad == 1 && P.shape == EvalPlan::GRID && c->proj_in_gather && c->itembase_valid && nall <= ZERO_COPY_MAX &&
+                         !c->theta_dev_in;
+    P.host_asm = want_grad && ((two_dof && !ep.want_tv) || tail_ok) && !ep.want_div && !P.full_aux && !no_host_asm && !c->device_results &&
+                 !c->theta_dev_in;
+    P.grid_tail = P.host_asm && P.shape == EvalPlan::GRID;
+    // Gradient evaluations with the grad-mag contrast take the contrast energy from k_imgrad (which computes the Scharr images anyway),
+    // so the statistics are a pure streaming reduction.  A new objective kind: k_stats_stream -> k_obj_parts -> k_obj_grad -> gather;
+    // k_final / host_assemble still do the gradient sums and the TV / divergence terms, obj_assemble the contrast and correlation ones.
+    P.g2_from_imgrad = want_grad && ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG && !P.obj;
+    P.stream_stats = P.host_asm || (P.g2_from_imgrad && g.ntiles >= NSPART) || P.obj;
+    // theta grids coarse enough for it: k_tv and k_gather project their tile's gradient onto the theta cells themselves (no k_project)
+    P.tv_proj = ep.use_tv_grad && P.shape == EvalPlan::GRID && c->proj_in_gather;
+    P.proj = want_grad && P.shape == EvalPlan::GRID && c->proj_in_gather && c->splat_rad == 1;
+    // the in-gather projection on big launches: one workgroup per segment for all reference times (8 windows of 10^6 events at 16x16:
+    // 792 workgroups of 5 reference times each instead of 3960: 148 -> 135 us; one window: 99 workgroups, 29 -> 84 us - so only where the
+    // segments alone fill the chip's 768 workgroup slots of this kernel)
+    static const int all_r_env = getenv("EINCM_GATHER_ALL_R") ? atoi(getenv("EINCM_GATHER_ALL_R")) : -1;
+    P.all_r = P.proj && (all_r_env >= 0 ? all_r_env != 0 : c->gather.n >= 700);
+    // k_project's sources: the event term's dL/dTheta image unless a gather projected it (2-DoF: partials), the TV term's unless k_tv did
+    P.events_projected = two_dof || P.proj;
+    P.nsrc = (!want_grad || identity) ? 0 : (P.events_projected ? 0 : 1) + ((ep.use_tv_grad && !P.tv_proj) ? 1 : 0);
+    // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
+    P.zero_copy_out = !c->device_results && !c->theta_dev_in && !identity && nall <= ZERO_COPY_MAX;
+    return P;
+}
+
+// theta_nan[b]: a NaN / Inf somewhere in window b's theta (host-assembled and float64 evaluations)
+void scan_theta(eincm_ctx* c, const double* theta_host, size_t nth) {
+    c->theta_nan.assign((size_t)c->g.B, 0);
+    for (int b = 0; b < c->g.B; ++b) {            // branch-free (vectorises): an OR over the exponent bits, 4096 values at 16x16 x 8 windows
+        const double* __restrict__ tb = theta_host + (size_t)b * nth;
+        uint64_t bad = 0;
+        for (size_t i = 0; i < nth; ++i) { uint64_t u; memcpy(&u, tb + i, sizeof u); bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull); }
+        c->theta_nan[b] = bad != 0;
+    }
+}
+
+// First half of an evaluation: checks, side effects, plan_eval, then theta -> Theta -> IWE stack (launch_forward; a float64 context
+// enqueues the whole evaluation, f64_launch).  theta_host: (B,h,w,2) doubles.
 int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad, const uint8_t* active = nullptr) {
     HostPhase hp(c, EINCM_HP_BEGIN);
     // (checked before the mask is touched: the evaluation in flight reads g.wmask again when it is collected)
@@ -847,35 +974,26 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         c->g.wmask = m;
     }
     const Geom& g = c->g;
-    const bool identity = (h == g.H && w == g.W);
     const size_t img = (size_t)g.H * g.W;
     const size_t nth = (size_t)h * w * 2;
-    const bool full_aux = (p->flags & EINCM_PF_FULL_AUX) != 0;
-    const bool div_grad = (p->delta != 0.0 && want_grad);
     c->pend.active = false; c->pend.launched = false;
-    if (div_grad && !c->d_gdiv && !c->fp64) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocate lazily
+    if (p->delta != 0.0 && want_grad && !c->d_gdiv && !c->fp64) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocate lazily
         HIPCHK(c, dalloc(&c->d_gdiv, (size_t)c->maxB * c->maxR * img));
         HIPCHK(c, dalloc(&c->d_dgparts, (size_t)c->maxB * c->maxR * g.ntiles * 2));
     }
     if (p->contrast_kind < EINCM_CONTRAST_GRAD_MAG || p->contrast_kind > EINCM_CONTRAST_ADAPTIVE_VARIANCE)
         return fail(c, EINCM_ERR_ARG, "contrast_kind %d unknown", p->contrast_kind);
-    const int corr_kind = (int)((p->flags & EINCM_PF_CORRELATION_MASK) >> 8);
+    const int corr_kind = correlation_kind(p);
     if (corr_kind > EINCM_CORRELATION_JOINT_CONTRAST) return fail(c, EINCM_ERR_ARG, "correlation kind %d unknown", corr_kind);
-    const bool obj = p->contrast_kind > EINCM_CONTRAST_VARIANCE || corr_kind != EINCM_CORRELATION_MSE;
-    if (obj && c->fp64)
-        return fail(c, EINCM_ERR_UNSUPPORTED, "contrast kind %d / correlation kind %d: not supported in fp64 mode (EINCM_CF_FP64)",
-                    p->contrast_kind, corr_kind);
-    if (obj) {
+    if (other_kinds(p)) {
+        if (c->fp64)
+            return fail(c, EINCM_ERR_UNSUPPORTED, "contrast kind %d / correlation kind %d: not supported in fp64 mode (EINCM_CF_FP64)",
+                        p->contrast_kind, corr_kind);
         if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
         const int rco = obj_constants(c);
         if (rco) return rco;
-        const int need = (p->contrast_kind == EINCM_CONTRAST_ADAPTIVE_GRAD_MAG ? OBJ_NEED_TILE_GM : 0) |
-                         ((p->contrast_kind == EINCM_CONTRAST_GRAD_MAG || corr_kind == EINCM_CORRELATION_JOINT_CONTRAST) ? OBJ_NEED_GM : 0) |
-                         (corr_kind == EINCM_CORRELATION_JOINT_CONTRAST ? OBJ_NEED_JOINT : 0);
-        c->pend.og = obj_geom(c, p->contrast_kind, corr_kind, need);
     }
-    c->pend.obj = obj;
-    if (!identity) {
+    if (theta_shape(g, h, w) != EvalPlan::IDENTITY) {
         if ((int64_t)h * w > (int64_t)g.H * g.W)
             return fail(c, EINCM_ERR_ARG, "theta (%d,%d,2) has more cells than the %dx%d sensor has pixels: not supported", h, w, g.H, g.W);
         if ((int64_t)nth > c->coarse_cap) {          // unusual (the pyramid tops out at 16x16): grow the coarse accumulators
@@ -888,97 +1006,22 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         int rc = ensure_resample(c, h, w, p->method);
         if (rc) return rc;
     }
-    if (c->fp64) {
-        EvalParams ep{};
-        ep.alpha = p->alpha; ep.beta = p->beta; ep.gamma = p->gamma; ep.delta = p->delta;
-        ep.cur_pyr_lvl = p->cur_pyr_lvl; ep.contrast_kind = p->contrast_kind;
-        ep.want_div = (full_aux || p->delta != 0.0) ? 1 : 0;
-        ep.want_tv = ((p->cur_pyr_lvl <= 0) && (p->gamma != 0.0 || full_aux)) ? 1 : 0;
-        ep.use_tv_grad = (ep.want_tv && p->gamma != 0.0 && want_grad && !(p->flags & EINCM_PF_NO_TV_GRAD)) ? 1 : 0;
-        ep.h = h; ep.w = w; ep.identity = identity ? 1 : 0;
-        return f64_launch(c, theta_host, h, w, ep, want_grad, full_aux, div_grad, identity);
-    }
+    const EvalPlan P = plan_eval(c, theta_host, h, w, p, want_grad);
+    if (c->fp64) { c->pend.plan = P; scan_theta(c, theta_host, nth); return f64_launch(c, theta_host); }
     if (c->acc_dirty) { const int rcd = clear_accumulators(c); if (rcd) return rcd; }
     if (c->cflags & EINCM_CF_TIMING_DOMINANT) c->timed_now = (c->time_counter++ % c->time_period) == 0;
-    const bool timing = timing_on(c);
-    if (timing) {
+    if (timing_on(c)) {
         if (c->ring_n == c->ring_size) { const int rcr = drain_event_ring(c, c->ring_size - 1); if (rcr) return rcr; }   // ring full: read the oldest
         c->ring_cur = (c->ring_lo + c->ring_n) % c->ring_size;
         for (int s = 0; s <= EINCM_N_STAGES; ++s) c->ev_used[c->ring_cur][s] = false;
         if (c->ring_size == 1) (void)hipEventRecord(c->ev[c->ring_cur][EINCM_N_STAGES][0], c->stream);    // EINCM_CF_TIMING only
     }
-
-    EvalParams ep{};
-    ep.alpha = p->alpha; ep.beta = p->beta; ep.gamma = p->gamma; ep.delta = p->delta;
-    ep.cur_pyr_lvl = p->cur_pyr_lvl; ep.contrast_kind = p->contrast_kind;
-    ep.want_div = (full_aux || p->delta != 0.0) ? 1 : 0;
-    ep.want_tv = ((p->cur_pyr_lvl <= 0) && (p->gamma != 0.0 || full_aux)) ? 1 : 0;
-    ep.use_tv_grad = (ep.want_tv && p->gamma != 0.0 && want_grad && !(p->flags & EINCM_PF_NO_TV_GRAD)) ? 1 : 0;
-    ep.h = h; ep.w = w; ep.identity = identity ? 1 : 0;
-
-    // LDS window capacity for this evaluation: the host knows theta, hence the largest displacement a segment can see.
-    // Small windows give 8 workgroups per CU; windows too small for the flow push taps onto the slow direct-to-HBM path.
+    c->pend.plan = P;
     c->policy_evaluated = true;
-    c->pend.splat_short = false;
-    c->pend.win_2 = WinFit{c->wincap, win_maxw(c->wincap), c->pitch_policy >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
-    c->g.pitch_aligned = c->pitch_policy != 0 ? 1 : 0;
-    if (!c->wincap_fixed) {
-        double vmax = 0.0;
-        const size_t nall = (size_t)g.B * nth;
-        const size_t stride = nall > 8192 ? nall / 8192 : 1;            // dense theta: sample (any capacity is correct; 65536 samples cost 90 us)
-        if (c->theta_dev_in) vmax = (c->vmax_hint >= 0.0 && std::isfinite(c->vmax_hint)) ? c->vmax_hint : 1e9;      // unknown: the largest windows
-        else if (stride == 1) { for (size_t i = 0; i < nall; ++i) { const double a = std::fabs(theta_host[i]); vmax = std::max(vmax, a <= 1.7e308 ? a : 0.0); } }   // (vectorises)
-        else for (size_t i = 0; i < nall; i += stride) { const double a = std::fabs(theta_host[i]); if (a > vmax && std::isfinite(a)) vmax = a; }
-        // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
-        const double margin = 2.0 * (c->splat_rad + 1);
-        const bool two_dof = h == 1 && w == 1 && !identity;
-        // Where a larger window costs no residency it is taken at once (a capacity is an allocation, the windows themselves stay as small
-        // as their segments need): the 2-DoF kernels hold nothing but the window in LDS, 4608 words = 18 KiB still gives the 8 workgroups
-        // of 4 waves a CU can hold; the theta-grid gather carries 32 KiB beside its window and runs 3 workgroups per CU up to 5461 words.
-        // The theta-grid splat (window + 16 KiB Theta tile) pays for capacity with workgroups per CU (6 / 5 / 4 / 3), so it takes what it needs.
-        // Each list's windows are sized for its time span: what all but 3 % of the events' segments stay within (build_list; the mean
-        // tile would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
-        const int floor_s = two_dof ? 2 : 0, pitch_s = c->pitch_policy != 0 ? 1 : 0;
-        WinFit s = fit_window(vmax, c->splat.tspan, margin, floor_s, pitch_s);
-        // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
-        // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
-        c->pend.splat_short = two_dof && c->splat_sh.n > 0 && !s.fits;
-        if (c->pend.splat_short) s = fit_window(vmax, c->splat_sh.tspan, margin, floor_s, pitch_s);
-        c->g.wincap = s.cap; c->g.winmaxw = s.maxw; c->g.pitch_aligned = s.pal ? 1 : 0;
-        // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
-        // sends taps down the direct path
-        const WinFit a = fit_window(vmax, c->gather.tspan, margin, 2, -1);
-        c->g.wincap_a = a.cap; c->g.winmaxw_a = a.maxw;
-        // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
-        // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
-        c->pend.win_2 = fit_window(vmax, c->gather_2.tspan, margin, 2, c->pitch_policy >= 2 ? 1 : 0);
-    }
-    // 2-DoF theta with nothing but the contrast and correlation terms (every level above 0 of the reference's pyramid at its first
-    // level, and the bench workload): the scalar assembly and the sum of the gather's per-workgroup partials run on the host
-    static const bool no_host_asm = getenv("EINCM_NO_HOST_ASM") != nullptr;
-    // (another splat window: its gather leaves the theta-grid sums to k_project and k_final, so no tail)
-    const bool grid_tail = c->splat_rad == 1 && !(h == 1 && w == 1) && c->proj_in_gather && c->itembase_valid && (size_t)g.B * nth <= ZERO_COPY_MAX && !c->theta_dev_in;
-    // (the TV term rides along on a theta grid: k_tv projects its own gradient and the gather's tail combines it; a 2-DoF theta with
-    // TV - no level of the reference's pyramid - keeps k_final)
-    const bool host_asm = want_grad && !identity && (((h == 1 && w == 1) && !ep.want_tv) || grid_tail) && !ep.want_div && !full_aux && !no_host_asm &&
-                          !c->device_results && !c->theta_dev_in;
-    if (host_asm) {
-        c->theta_nan.assign((size_t)g.B, 0);
-        for (int b = 0; b < g.B; ++b) {            // branch-free (vectorises): an OR over the exponent bits, 4096 values at 16x16 x 8 windows
-            const double* __restrict__ tb = theta_host + (size_t)b * nth;
-            uint64_t bad = 0;
-            for (size_t i = 0; i < nth; ++i) {
-                uint64_t u;
-                memcpy(&u, tb + i, sizeof u);
-                bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
-            }
-            c->theta_nan[b] = bad != 0;
-        }
-    }
-    int rc = launch_forward(c, h, w, identity, ep.want_tv != 0, theta_host, host_asm);
-    if (rc) return rc;
-    c->pend.active = true; c->pend.ep = ep; c->pend.h = h; c->pend.w = w; c->pend.identity = identity;
-    c->pend.want_grad = want_grad; c->pend.full_aux = full_aux; c->pend.div_grad = div_grad; c->pend.host_asm = host_asm;
+    c->g.wincap = P.wincap; c->g.winmaxw = P.winmaxw; c->g.pitch_aligned = P.pitch_aligned; c->g.wincap_a = P.wincap_a; c->g.winmaxw_a = P.winmaxw_a;
+    if (P.host_asm) scan_theta(c, theta_host, nth);
+    if (const int rc = launch_forward(c, theta_host)) return rc;
+    c->pend.active = true;
     return EINCM_OK;
 }
 
@@ -986,8 +1029,8 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
 // eincm_set_device_results - only by eincm_finish_collect, after the caller has all-reduced the gradient in HBM.
 int enqueue_result_copies(eincm_ctx* c) {
     const Geom& g = c->g;
-    const bool want_grad = c->pend.want_grad;
-    const size_t nth = (size_t)c->pend.h * c->pend.w * 2;
+    const bool want_grad = c->pend.plan.want_grad;
+    const size_t nth = c->pend.plan.nth;
     c->n_pieces = 0;
     if (c->theta_dev_in) {                           // eincm_loss_grad_device: scalars to the host, the gradient device to device
         HIPCHK(c, hipMemcpyAsync(c->h_outs, c->d_outs, (size_t)g.B * sizeof(OutScal), hipMemcpyDeviceToHost, c->stream));
@@ -1030,34 +1073,23 @@ int enqueue_result_copies(eincm_ctx* c) {
 }
 
 // Second half, part 1: enqueue image statistics, dL/dIWE, gather, projection, scalar assembly (on whatever is in the IWE
-// stack now) and the copy back to pinned memory.  Returns without synchronising.
+// stack now) and the copy back to pinned memory, as planned (pend.plan).  Returns without synchronising.
 int eval_end_launch(eincm_ctx* c) {
     if (!c->pend.active) return fail(c, EINCM_ERR_STATE, "no evaluation in flight");
     if (c->pend.launched) return EINCM_OK;
     HostPhase hp(c, EINCM_HP_LAUNCH);
+    const EvalPlan& P = c->pend.plan;
+    const EvalParams& ep = P.ep;
     Geom g = c->g;
-    const EvalParams ep = c->pend.ep;
-    const int h = c->pend.h, w = c->pend.w;
-    const bool identity = c->pend.identity, want_grad = c->pend.want_grad, full_aux = c->pend.full_aux, div_grad = c->pend.div_grad;
-    const size_t nth = (size_t)h * w * 2;
+    const bool identity = P.shape == EvalPlan::IDENTITY, two_dof = P.shape == EvalPlan::TWO_DOF, want_grad = P.want_grad, host_asm = P.host_asm;
     const bool timing = timing_on(c);
-    const bool host_asm = c->pend.host_asm;
-    // The image pass of a gradient evaluation: k_stats_stream -> k_imgrad -> gather.
-    // A new objective kind (pend.obj): k_stats_stream -> k_obj_parts -> k_obj_grad -> gather; k_final / host_assemble still do the
-    // gradient sums and the TV / divergence terms, obj_assemble replaces the contrast and correlation terms of their value.
-    const bool obj = c->pend.obj;
-    const bool g2_from_imgrad = want_grad && ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG && !obj;
-    const bool zero_copy_out = !c->device_results && !c->theta_dev_in && !identity && (size_t)g.B * nth <= ZERO_COPY_MAX;
-    const bool stream_stats = host_asm || (g2_from_imgrad && g.ntiles >= NSPART) || obj;
     const int n_imwg = (g.nig + IG_NT / 64 - 1) / (IG_NT / 64);
     g.gmax_n = g.R * g.nig;
     {
-        StageTimer t(c, EINCM_STAGE_STATS, stream_stats);
+        StageTimer t(c, EINCM_STAGE_STATS, P.stream_stats);
         // Either way the statistics pass is the consumer of the u64 accumulator: it leaves the fp32 IWE stack in d_iwe and clears
         // the accumulator.
-        if (stream_stats) {
-            // gradient evaluations with the grad-mag contrast take the contrast energy from k_imgrad (which computes the Scharr
-            // images anyway), so the statistics are a pure streaming reduction with NSPART fat partials per image
+        if (P.stream_stats) {
             g.nparts = NSPART;
             launch_timed(c, EINCM_STAGE_STATS, k_stats_stream, dim3(NSPART, g.R, g.B), dim3(NT), 0, g, c->d_acc, c->d_iwe, c->d_edges,
                          c->d_parts);
@@ -1067,7 +1099,7 @@ int eval_end_launch(eincm_ctx* c) {
             hipLaunchKernelGGL(k_iwe_finish, dim3((unsigned)std::min<size_t>((ntot + NT - 1) / NT, 2048)), dim3(NT), 0, c->stream, g,
                                c->d_acc, c->d_iwe);
             hipLaunchKernelGGL(k_stats, dim3(g.ntiles, g.R, g.B), dim3(NT), 0, c->stream, g, c->d_iwe, c->d_edges, c->d_parts,
-                               g2_from_imgrad ? 0 : 1);
+                               P.g2_from_imgrad ? 0 : 1);
         }
         c->last_nparts = g.nparts;
     }
@@ -1077,34 +1109,27 @@ int eval_end_launch(eincm_ctx* c) {
     }
     if (ep.want_tv) {
         StageTimer t(c, EINCM_STAGE_TV, true);
-        // theta grids coarse enough for it: k_tv projects its tile's gradient onto the theta cells itself (no image, no k_project)
-        const bool tv_proj = ep.use_tv_grad && !identity && !(h == 1 && w == 1) && c->proj_in_gather;
-#define TV_ARGS dim3(g.ntiles, g.B), dim3(NT), 0, g, c->d_Theta, c->d_mask, c->d_tvg, c->d_tvparts, full_aux ? 1 : 0, \
-                h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap, host_asm ? c->h_tvparts : nullptr
-        if (tv_proj) launch_timed(c, EINCM_STAGE_TV, k_tv<1>, TV_ARGS);
-        else         launch_timed(c, EINCM_STAGE_TV, k_tv<0>, TV_ARGS);
-#undef TV_ARGS
-        c->pend.tv_projected = tv_proj;
+        auto go = [&](auto kernel) {
+            launch_timed(c, EINCM_STAGE_TV, kernel, dim3(g.ntiles, g.B), dim3(NT), 0, g, c->d_Theta, c->d_mask, c->d_tvg, c->d_tvparts,
+                         P.full_aux ? 1 : 0, P.h, P.w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth + (size_t)c->maxB * c->coarse_cap,
+                         (int)c->coarse_cap, host_asm ? c->h_tvparts : nullptr);
+        };
+        P.tv_proj ? go(k_tv<1>) : go(k_tv<0>);
     }
-    if (obj && !want_grad) {          // forward only: the per-image values alone
-        const ObjGeom& og = c->pend.og;
+    if (P.obj && !want_grad) {          // forward only: the per-image values alone
+        const ObjGeom& og = P.og;
         hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts);
         hipLaunchKernelGGL(k_obj_grad, dim3(1, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts,
                            c->d_wc, c->d_objc, c->d_gdiv, c->d_dgparts, c->d_G, c->d_gmax, c->h_ovals, 0);
     }
-    const bool direct11 = want_grad && !identity && h == 1 && w == 1;
-    const bool proj = want_grad && !identity && !direct11 && c->proj_in_gather && c->splat_rad == 1;      // k_gather projects its tile's sums itself
-    // a window with a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel); speed is irrelevant there
-    bool wide = false;
-    for (int b = 0; b < g.B; ++b) wide = wide || (c->win_events[b] * (int64_t)g.R < 4096);
     if (want_grad) {
         {
-            StageTimer t(c, EINCM_STAGE_IMGRAD, !div_grad && !obj);
-            if (div_grad)
+            StageTimer t(c, EINCM_STAGE_IMGRAD, !P.div_grad && !P.obj);
+            if (P.div_grad)
                 hipLaunchKernelGGL(k_divgrad, dim3(g.ntiles, g.R, g.B), dim3(NT), 0, c->stream, g, c->d_iwe, c->d_parts,
                                    c->d_gdiv, c->d_dgparts);
-            if (obj) {
-                const ObjGeom& og = c->pend.og;
+            if (P.obj) {
+                const ObjGeom& og = P.og;
                 hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts);
                 hipLaunchKernelGGL(k_obj_grad, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts,
                                    c->d_wc, c->d_objc, c->d_gdiv, c->d_dgparts, c->d_G, c->d_gmax, c->h_ovals, 1);
@@ -1122,81 +1147,61 @@ int eval_end_launch(eincm_ctx* c) {
                 // Theta grids / dense theta: the gather walks its own segment list (long segments: its per-workgroup costs - Theta tile,
                 // accumulator clear and flush - want them long even for one window) on its own copy of the events (k_segsort); 2-DoF
                 // theta: the 2-DoF gather list (shorter segments) on the splat's copy, deriving its windows itself (no window table)
-                const SegList& L = direct11 ? c->gather_2 : c->gather;
-                const uint32_t* xy_g = direct11 ? c->d_xy : c->d_xy_g;
-                const double* t_g = direct11 ? c->d_t : c->d_t_g;
+                const SegList& L = two_dof ? c->gather_2 : c->gather;
+                const uint32_t* xy_g = two_dof ? c->d_xy : c->d_xy_g;
+                const double* t_g = two_dof ? c->d_t : c->d_t_g;
                 Geom gg = g;
-                if (direct11) { gg.pitch_aligned = c->pend.win_2.pal ? 1 : 0; gg.wincap_a = c->pend.win_2.cap; gg.winmaxw_a = c->pend.win_2.maxw; }
-                // theta grids with the in-gather projection on big launches: one workgroup per segment for all reference times (k_gather, all_r)
-                static const int all_r_env = getenv("EINCM_GATHER_ALL_R") ? atoi(getenv("EINCM_GATHER_ALL_R")) : -1;
-                // (8 windows of 10^6 events at 16x16: 792 workgroups of 5 reference times each instead of 3960: 148 -> 135 us; one window:
-                // 99 workgroups, 29 -> 84 us - so only where the segments alone fill the chip's 768 workgroup slots of this kernel)
-                int all_r = (!direct11 && proj && !identity && L.n >= 700) ? 1 : 0;
-                if (all_r_env >= 0) all_r = (all_r_env && !direct11 && proj && !identity) ? 1 : 0;
-#define GATHER_ARGS(NTH) dim3(L.grid(all_r ? 1 : g.R)), dim3(NTH), \
-                    gg.wincap_a * sizeof(float) + (direct11 ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2)), \
-                    gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, \
-                    host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, L.d_order, \
-                    c->pend.use_arg ? 1 : 0, c->pend.theta_dev, c->pend.targ, \
-                    h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth, (int)c->coarse_cap, \
-                    (host_asm && proj) ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad, \
-                    (host_asm && proj && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap
-#define GATHER_TILE(WIDE_, PROJ_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, PROJ_>, GATHER_ARGS(NT_TILE))
-#define GATHER_ALLR(WIDE_) launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_TILE, WIDE_, NT_TILE, 1, 1>, GATHER_ARGS(NT_TILE))
+                if (two_dof) { gg.pitch_aligned = P.win_2.pal ? 1 : 0; gg.wincap_a = P.win_2.cap; gg.winmaxw_a = P.win_2.maxw; }
+                const dim3 grid(L.grid(P.all_r ? 1 : g.R));
+                const size_t lds = gg.wincap_a * sizeof(float) + (two_dof ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2));
+                double* g11 = host_asm ? c->h_g11 : c->d_g11;
+                const int use_arg = P.use_arg ? 1 : 0;
                 if (c->splat_rad != 1) {
                     // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
-                    const size_t lds_r = gg.wincap_a * sizeof(float) + (direct11 ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2));
-#define GATHER_R_ARGS dim3(L.grid(g.R)), dim3(NT), lds_r, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, \
-                      c->d_tmm, c->d_edge_ts, c->d_G, c->d_gTheta, host_asm ? c->h_g11 : c->d_g11, c->d_wc, c->d_gmax, wide ? 1 : 0, \
-                      c->pend.use_arg ? 1 : 0, c->pend.theta_dev, c->pend.targ
-#define GATHER_R(TM_) do { if (c->splat_rad == 0) launch_timed(c, EINCM_STAGE_GATHER, k_gather_r<TM_, 0>, GATHER_R_ARGS); \
-                           else if (c->splat_rad == 2) launch_timed(c, EINCM_STAGE_GATHER, k_gather_r<TM_, 2>, GATHER_R_ARGS); \
-                           else launch_timed(c, EINCM_STAGE_GATHER, k_gather_r<TM_, 3>, GATHER_R_ARGS); } while (0)
-                    if (direct11) GATHER_R(THETA_CONST); else GATHER_R(THETA_TILE);
-#undef GATHER_R
-#undef GATHER_R_ARGS
-                } else if (direct11) {
-                    launch_timed(c, EINCM_STAGE_GATHER, k_gather<THETA_CONST, 0, NT, 0>, GATHER_ARGS(NT));
-                } else if (all_r) {
-                    if (wide) GATHER_ALLR(1); else GATHER_ALLR(0);
-                } else if (wide) {
-                    if (proj) GATHER_TILE(1, 1); else GATHER_TILE(1, 0);
+                    auto go = [&](auto kernel) {
+                        launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(NT), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, c->d_tmm,
+                                     c->d_edge_ts, c->d_G, c->d_gTheta, g11, c->d_wc, c->d_gmax, c->wide ? 1 : 0, use_arg, c->pend.theta_dev,
+                                     c->pend.targ);
+                    };
+                    if (two_dof) c->splat_rad == 0 ? go(k_gather_r<THETA_CONST, 0>) : c->splat_rad == 2 ? go(k_gather_r<THETA_CONST, 2>) : go(k_gather_r<THETA_CONST, 3>);
+                    else         c->splat_rad == 0 ? go(k_gather_r<THETA_TILE, 0>) : c->splat_rad == 2 ? go(k_gather_r<THETA_TILE, 2>) : go(k_gather_r<THETA_TILE, 3>);
                 } else {
-                    if (proj) GATHER_TILE(0, 1); else GATHER_TILE(0, 0);
+                    auto go = [&](auto kernel, int nthreads) {
+                        launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(nthreads), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta,
+                                     c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, g11, c->d_wc, c->d_gmax, L.d_order, use_arg,
+                                     c->pend.theta_dev, c->pend.targ, P.h, P.w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth, (int)c->coarse_cap,
+                                     P.grid_tail ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad,
+                                     (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap);
+                    };
+                    if (two_dof)      go(k_gather<THETA_CONST, 0, NT, 0>, NT);
+                    else if (P.all_r) c->wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1>, NT_TILE);
+                    else if (c->wide) P.proj ? go(k_gather<THETA_TILE, 1, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 1, NT_TILE, 0>, NT_TILE);
+                    else              P.proj ? go(k_gather<THETA_TILE, 0, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 0>, NT_TILE);
                 }
-#undef GATHER_TILE
-#undef GATHER_ALLR
-#undef GATHER_ARGS
             }
         }
-        // accumulators: two halves (event gradient | TV gradient), each (maxB, coarse_cap) i64, zero on entry (k_final clears them).
-        // 2-DoF theta: k_gather left per-workgroup partials of the event gradient for k_final; only the TV image needs projecting.
-        // (a theta grid coarse enough for k_gather's own projection leaves only the TV image to k_project)
-        const bool events_projected = direct11 || proj;
-        const bool tv_needs_project = ep.use_tv_grad && !(ep.want_tv && c->pend.tv_projected);
-        const int nsrc = (events_projected ? 0 : 1) + (tv_needs_project ? 1 : 0);
-        if (!identity && nsrc > 0) {
+        // accumulators: two halves (event gradient | TV gradient), each (maxB, coarse_cap) i64, zero on entry (k_final clears them)
+        if (P.nsrc > 0) {
             StageTimer t(c, EINCM_STAGE_PROJECT, true);
-            launch_timed(c, EINCM_STAGE_PROJECT, k_project, dim3(g.ntiles, g.B, nsrc), dim3(NT), 0, g, h, w,
-                               (int)c->coarse_cap, events_projected ? 1 : 0, wide ? 1 : 0, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_gTheta, c->d_tvg,
+            launch_timed(c, EINCM_STAGE_PROJECT, k_project, dim3(g.ntiles, g.B, P.nsrc), dim3(NT), 0, g, P.h, P.w,
+                               (int)c->coarse_cap, P.events_projected ? 1 : 0, c->wide ? 1 : 0, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_gTheta, c->d_tvg,
                                c->d_wc, c->d_gmax, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap);
         }
     }
     if (!host_asm) {
         StageTimer t(c, EINCM_STAGE_FINAL, !(want_grad && identity));
-        // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
         launch_timed(c, EINCM_STAGE_FINAL, k_final, dim3(g.B), dim3(FT), 0, g, ep, c->d_parts, c->d_divparts, c->d_tvparts,
-                           c->d_tmm, c->d_wc, g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
+                           c->d_tmm, c->d_wc, P.g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
                            c->d_g11, c->gather_2.d_win_item0, c->gather_2.n, c->d_gmax,
-                           zero_copy_out ? c->h_outs : c->d_outs, zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
+                           P.zero_copy_out ? c->h_outs : c->d_outs, P.zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
         if (want_grad && identity) {
-            hipLaunchKernelGGL(k_final_dense, dim3(256, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, wide ? 1 : 0, c->d_gTheta,
+            hipLaunchKernelGGL(k_final_dense, dim3(256, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, c->wide ? 1 : 0, c->d_gTheta,
                                c->d_tvg, c->d_wc, c->d_gmax, c->d_outs, c->d_grad);
         }
     }
     HIPCHK(c, hipGetLastError());
     c->n_pieces = 0;
-    c->pend.copy_mode = (zero_copy_out || host_asm) ? 0 : 1;
+    c->pend.copy_mode = (P.zero_copy_out || host_asm) ? 0 : 1;
     if (c->pend.copy_mode && !c->device_results) { const int rcc = enqueue_result_copies(c); if (rcc) return rcc; c->pend.copy_mode = 0; }
     if (timing && c->ring_size == 1) { (void)hipEventRecord(c->ev[c->ring_cur][EINCM_N_STAGES][1], c->stream); c->ev_used[c->ring_cur][EINCM_N_STAGES] = true; }
     c->pend.launched = true;
@@ -1204,14 +1209,15 @@ int eval_end_launch(eincm_ctx* c) {
     return EINCM_OK;
 }
 
-// Host-assembled evaluations (pend.host_asm): what k_final does for them, in fp64 on the host from the partials the kernels wrote
+// Host-assembled evaluations (plan.host_asm): what k_final does for them, in fp64 on the host from the partials the kernels wrote
 // into pinned memory - the image scalars of k_imgrad (h_img), its per-strip contrast energies (h_g2) and the per-workgroup partials
 // of the 2-DoF gradient (h_g11) - every sum in index order, so the result is a function of the partials alone (bit-reproducible).
-// losses.py:176-203 without the TV / divergence terms (the caller routed those evaluations to k_final).
+// losses.py:176-203 without the divergence term (the planner routes those evaluations to k_final).
 void host_assemble(eincm_ctx* c) {
     const Geom& g = c->g;
-    const EvalParams& ep = c->pend.ep;
-    const double HW = (double)g.H * (double)g.W, Rd = (double)g.R;
+    const EvalPlan& P = c->pend.plan;
+    const EvalParams& ep = P.ep;
+    const double HW = (double)g.H * (double)g.W;
     for (int b = 0; b < g.B; ++b) {
         const WinConst& wc = c->h_wc[b];
         OutScal& o = c->h_outs[b];
@@ -1236,21 +1242,8 @@ void host_assemble(eincm_ctx* c) {
             sum_rel_con += wc.mrw[r] * con / (c0 + EPSN);
             sum_rel_corr += wc.mrw[r] * (-mse) / (wc.zc[r] + EPSN);
         }
-        const double mrc = sum_rel_con / Rd, mrr = sum_rel_corr / Rd;
-        double val = ep.alpha * (-mrc) + ep.beta * (-mrr);
-        double tv = 0.0;
-        if (ep.want_tv) {                                    // regularizers.py:14-38 from k_tv's per-tile partials, losses.py:171
-            double a = 0.0, nz = 0.0;
-            for (int i = 0; i < g.ntiles; ++i) { a += c->h_tvparts[((size_t)b * g.ntiles + i) * 3]; nz += c->h_tvparts[((size_t)b * g.ntiles + i) * 3 + 1]; }
-            tv = a / (nz + EPSN);
-            if (ep.gamma != 0.0) val += ep.gamma * ((ep.cur_pyr_lvl <= 0) ? tv : 0.0);
-        }
-        if (c->theta_nan[b]) val = NAN;             // a NaN anywhere in theta surfaces as a NaN loss, like in the reference
-        o.mean_rel_contrast = mrc; o.mean_rel_corr = mrr; o.mean_rel_div = NAN;
-        o.tv = (ep.cur_pyr_lvl <= 0) ? (ep.want_tv ? tv : NAN) : 0.0;
-        o.value = val; o.tv_scale = 0.0;
-        o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
-        if (c->pend.h == 1 && c->pend.w == 1) {              // 2-DoF: the gather's per-workgroup partials, added in index order
+        assemble_window(ep, g.R, sum_rel_con, sum_rel_corr, NAN, window_tv(c, ep, b), c->theta_nan[b] != 0, true, o);
+        if (P.shape == EvalPlan::TWO_DOF) {                  // 2-DoF: the gather's per-workgroup partials, added in index order
             const int lo = c->gather_2.h_win_item0[b], hi = c->gather_2.h_win_item0[b + 1];
             const double* p = c->h_g11 + (size_t)lo * g.R * 2;
             const size_t n = (size_t)(hi - lo) * g.R;
@@ -1265,8 +1258,7 @@ void host_assemble(eincm_ctx* c) {
             for (; k < n; ++k) { ax[0] += p[2 * k]; ay[0] += p[2 * k + 1]; }
             c->h_grad[(size_t)b * 2] = (ax[0] + ax[1]) + (ax[2] + ax[3]); c->h_grad[(size_t)b * 2 + 1] = (ay[0] + ay[1]) + (ay[2] + ay[3]);
         } else if (c->win_events[b] == 0) {                  // theta grid: the gather's tail wrote dL/dtheta, unless the window has no workgroup
-            const size_t n = (size_t)c->pend.h * c->pend.w * 2;
-            for (size_t i = 0; i < n; ++i) c->h_grad[(size_t)b * n + i] = 0.0;
+            for (size_t i = 0; i < P.nth; ++i) c->h_grad[(size_t)b * P.nth + i] = 0.0;
         }
     }
 }
@@ -1275,8 +1267,8 @@ void host_assemble(eincm_ctx* c) {
 int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
     if (!c->pend.active || !c->pend.launched) return fail(c, EINCM_ERR_STATE, "no evaluation in flight");
     const Geom& g = c->g;
-    const bool want_grad = c->pend.want_grad;
-    const size_t nth = (size_t)c->pend.h * c->pend.w * 2;
+    const bool want_grad = c->pend.plan.want_grad;
+    const size_t nth = c->pend.plan.nth;
     // The stream is drained before ANY return: the kernels in flight read the pinned theta staging buffer and write the pinned
     // result block, so the context must not look idle (and accept the next theta) while they run.
     if (c->pend.copy_mode) { const int rcc = enqueue_result_copies(c); c->pend.copy_mode = 0; if (rcc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rcc; } }
@@ -1307,9 +1299,9 @@ int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) 
     const bool dev_io = c->theta_dev_in != nullptr;           // the gradient went device to device (enqueue_result_copies)
     if (want_grad && !grad && !dev_io) return fail(c, EINCM_ERR_ARG, "the evaluation was begun with a gradient but grad is NULL");
     HostPhase hp(c, EINCM_HP_COLLECT);
-    if (c->pend.host_asm) host_assemble(c);
+    if (c->pend.plan.host_asm) host_assemble(c);
     else if (c->fp64) f64_assemble(c);
-    if (c->pend.obj) obj_assemble(c);
+    if (c->pend.plan.obj) obj_assemble(c);
     int rc = collect_timings(c);
     if (rc) return rc;
     c->have_eval = true;
@@ -1354,7 +1346,7 @@ int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) 
 }
 
 int eval_end(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
-    if (c->pend.active && c->pend.want_grad && !grad) {
+    if (c->pend.active && c->pend.plan.want_grad && !grad) {
         (void)hipStreamSynchronize(c->stream);       // the forward half is in flight and reads the pinned theta buffer
         c->pend.active = false;
         return fail(c, EINCM_ERR_ARG, "the evaluation was begun with a gradient but grad is NULL");
@@ -1932,6 +1924,7 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     c->g = g; c->n_events = N;
     c->itembase_valid = !c->host_binning && c->gather.n > 0 && c->splat.n > 0;      // both tile scans ran on the device
     c->win_events.assign(n_events, n_events + n_windows);
+    c->wide = std::any_of(n_events, n_events + n_windows, [&](int64_t n) { return n * (int64_t)n_refs < 4096; });
     if (c->gather.n > 0 && c->host_binning) {
         hipLaunchKernelGGL(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, c->stream, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask);
         HIPCHK(c, hipGetLastError());
@@ -2101,8 +2094,8 @@ int eincm_finish_launch(eincm_ctx* c) {
 int eincm_grad_device_ptr(eincm_ctx* c, void** dptr, int64_t* n_doubles) {
     if (!c || !dptr || !n_doubles) return EINCM_ERR_ARG;
     if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_grad_device_ptr is not supported in fp64 mode (EINCM_CF_FP64)");
-    if (!c->pend.active || !c->pend.launched || !c->pend.want_grad) return fail(c, EINCM_ERR_STATE, "no launched gradient evaluation (eincm_finish_launch)");
-    *dptr = c->d_grad; *n_doubles = (int64_t)c->g.B * c->pend.h * c->pend.w * 2;
+    if (!c->pend.active || !c->pend.launched || !c->pend.plan.want_grad) return fail(c, EINCM_ERR_STATE, "no launched gradient evaluation (eincm_finish_launch)");
+    *dptr = c->d_grad; *n_doubles = (int64_t)c->g.B * (int64_t)c->pend.plan.nth;
     return EINCM_OK;
 }
 
@@ -2887,11 +2880,12 @@ int eincm_get_launch_policy(eincm_ctx* c, double* out) {
     out[EINCM_LP_SEG_GATHER] = c->gather.seg; out[EINCM_LP_SEG_SPLAT] = c->splat.seg; out[EINCM_LP_SEG_GATHER_2DOF] = c->gather_2.seg;
     out[EINCM_LP_SEG_SPLAT_SHORT] = c->splat_sh.n > 0 ? c->splat_sh.seg : 0; out[EINCM_LP_PITCH_POLICY] = c->pitch_policy;
     out[EINCM_LP_SPAN_SPLAT] = c->splat.tspan; out[EINCM_LP_SPAN_GATHER] = c->gather.tspan; out[EINCM_LP_SPAN_GATHER_2DOF] = c->gather_2.tspan;
-    const bool evaluated = c->policy_evaluated;
-    out[EINCM_LP_CAP_SPLAT] = evaluated ? c->g.wincap : 0; out[EINCM_LP_CAP_GATHER] = evaluated ? c->g.wincap_a : 0;
-    out[EINCM_LP_CAP_GATHER_2DOF] = evaluated ? c->pend.win_2.cap : 0;
-    out[EINCM_LP_PITCH_ALIGNED] = evaluated ? ((c->g.pitch_aligned ? 1 : 0) | (c->pend.win_2.pal ? 2 : 0)) : 0;
-    out[EINCM_LP_SPLAT_SHORT] = evaluated && c->pend.splat_short ? 1 : 0;
+    const bool evaluated = c->policy_evaluated;         // (never on a float64 context)
+    const EvalPlan& P = c->pend.plan;
+    out[EINCM_LP_CAP_SPLAT] = evaluated ? P.wincap : 0; out[EINCM_LP_CAP_GATHER] = evaluated ? P.wincap_a : 0;
+    out[EINCM_LP_CAP_GATHER_2DOF] = evaluated ? P.win_2.cap : 0;
+    out[EINCM_LP_PITCH_ALIGNED] = evaluated ? ((P.pitch_aligned ? 1 : 0) | (P.win_2.pal ? 2 : 0)) : 0;
+    out[EINCM_LP_SPLAT_SHORT] = evaluated && P.splat_short ? 1 : 0;
     return EINCM_OK;
 }
 
