@@ -7,7 +7,9 @@ GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
 
 
 def golden_names():
-    return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, '*.npz')))
+    """The oracle's own fixtures (make_golden.py); the ref_*.npz recordings of the reference are read by _reference_golden.py."""
+    return sorted(os.path.splitext(os.path.basename(p))[0] for p in glob.glob(os.path.join(GOLDEN_DIR, '*.npz'))
+                  if not os.path.basename(p).startswith('ref_'))
 
 
 def load_golden(name):

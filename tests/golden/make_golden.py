@@ -1,11 +1,11 @@
 """Generate the golden fixtures in this directory.
 
-PROVENANCE: the reference (JAX) cannot be imported or run here (jax/jaxlib/jaxopt absent, no network) and ships no
-golden vectors, so these fixtures are outputs of THIS repo's fp64 oracle (oracle/eincm_oracle.py), each
-cross-checked at generation time against the independent torch-autograd witness (oracle/eincm_torch.py).
-They pin the oracle and the HIP path against regressions; they do NOT pin either to the reference
-("parity unpinned").  Inputs are stored explicitly so the fixtures do not depend on the
-synthetic generator's RNG stream.
+PROVENANCE: these fixtures (every *.npz here except ref_*.npz) are outputs of THIS repo's fp64 oracle
+(oracle/eincm_oracle.py), each cross-checked at generation time against the independent torch-autograd witness
+(oracle/eincm_torch.py).  They pin the oracle and the HIP path against regressions.  The pin to the reference itself
+is ref_*.npz, recorded from the reference's own code by make_reference_golden.py (JAX primitives served by
+oracle/jax_standin.py), which the oracle reproduces to 1e-12 (tests/test_reference_golden.py).
+Inputs are stored explicitly so the fixtures do not depend on the synthetic generator's RNG stream.
 
 Run from the repo root:  python tests/golden/make_golden.py
 """
