@@ -141,6 +141,12 @@ SIGNATURES = [
     ('eincm_set_splat_window', C.c_int, [_P, C.c_int]),
     ('eincm_gt_flow', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                 C.POINTER(C.c_int32), _D, _D, _D]),
+    # the DSEC data path (raw addresses: the arrays are large and typed on the numpy side)
+    ('eincm_rectify_events', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.POINTER(C.c_int64)]),
+    ('eincm_remap_cubic', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('eincm_flow_decode', C.c_int, [_P, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    ('eincm_flow_encode', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
 ]
 
 _lib = None

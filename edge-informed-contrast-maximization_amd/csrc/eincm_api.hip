@@ -28,6 +28,7 @@
 #include "eincm_canny.hip.h"
 #include "eincm_preprocess.hip.h"
 #include "eincm_gtflow.hip.h"
+#include "eincm_dsec.hip.h"
 
 using namespace eincm;
 
@@ -191,6 +192,11 @@ struct eincm_ctx {
     int nlm_tw = 0, nlm_sw = 0;
     // scratch of eincm_gt_flow (eincm_gtflow.hip.h), grown on demand: the x and y frame stacks, the step lists, the output
     DevBuf g_frames, g_tab, g_out;
+    // scratch of the DSEC data path (eincm_dsec.hip.h), grown on demand.  Rectification: the rounded map packed as int16 pairs (kept
+    // from the call that handed a map over), the chunk's coordinates in and out, the keep bytes, the block counts and offsets.  One
+    // input and one output buffer for remap_cubic, flow_decode and flow_encode, their tables, and the counters all four share.
+    DevBuf r_map, r_fmap, r_x, r_y, r_keep, r_rx, r_ry, r_cnt, r_off, d_in, d_out, d_tab, d_cnt;
+    bool rect_map_set = false;
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
@@ -371,6 +377,9 @@ void free_all(eincm_ctx* c) {
     for (DevBuf* b : {&c->e_u8, &c->e_g, &c->e_sq, &c->e_misc, &c->e_a, &c->e_b, &c->e_kern, &c->e_out}) { F(b->p); b->bytes = 0; }
     for (DevBuf* b : {&c->p_img[0], &c->p_img[1], &c->p_rows, &c->p_tab, &c->p_lut, &c->p_nlm}) { F(b->p); b->bytes = 0; }
     for (DevBuf* b : {&c->g_frames, &c->g_tab, &c->g_out}) { F(b->p); b->bytes = 0; }
+    for (DevBuf* b : {&c->r_map, &c->r_fmap, &c->r_x, &c->r_y, &c->r_keep, &c->r_rx, &c->r_ry, &c->r_cnt, &c->r_off, &c->d_in, &c->d_out,
+                      &c->d_tab, &c->d_cnt}) { F(b->p); b->bytes = 0; }
+    c->rect_map_set = false;
     c->nlm_tw = 0;
     auto FH = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
     FH(c->f64.h_scal); FH(c->h_ovals);
@@ -2762,6 +2771,185 @@ int eincm_gt_flow(eincm_ctx* c, const void* gt_x, const void* gt_y, int elem_byt
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n_windows * npix * 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // tab (host vector) stays alive until here
+    return EINCM_OK;
+}
+
+// The non-zero run of every row of a resample matrix A (n_out, n_in): lo, cnt and the weights padded to the longest run.
+static int resample_runs(const std::vector<double>& A, int n_in, int n_out, std::vector<int32_t>& lo, std::vector<int32_t>& cnt,
+                         std::vector<double>& wt) {
+    lo.assign(n_out, 0); cnt.assign(n_out, 0);
+    int stride = 1;
+    for (int o = 0; o < n_out; ++o) {
+        int a = n_in, b = 0;
+        for (int i = 0; i < n_in; ++i) if (A[(size_t)o * n_in + i] != 0.0) { a = std::min(a, i); b = std::max(b, i + 1); }
+        if (a < b) { lo[o] = a; cnt[o] = b - a; stride = std::max(stride, b - a); }
+    }
+    wt.assign((size_t)n_out * stride, 0.0);
+    for (int o = 0; o < n_out; ++o)
+        for (int k = 0; k < cnt[o]; ++k) wt[(size_t)o * stride + k] = A[(size_t)o * n_in + lo[o] + k];
+    return stride;
+}
+
+// DSECDataLoader.rectify_events (dsec_loader.py:145-171) for one chunk of a recording.
+int eincm_rectify_events(eincm_ctx* c, const float* rectify_map, const int16_t* x, const int16_t* y, int64_t n, int16_t* rec_x,
+                         int16_t* rec_y, uint8_t* keep, int64_t* n_kept) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!n_kept) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n < 0 || n > (int64_t)1 << 30) return fail(c, EINCM_ERR_ARG, "n = %lld outside [0, 2^30] (walk a recording in chunks)", (long long)n);
+    if (n > 0 && (!x || !y || !rec_x || !rec_y || !keep)) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (!rectify_map && !c->rect_map_set) return fail(c, EINCM_ERR_STATE, "no rectify map: the first call must hand one over");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int H = c->H, W = c->W;
+    const int64_t npix = (int64_t)H * W;
+    ENSURE(c, c->d_cnt, 4 * sizeof(unsigned long long));
+    auto* d_cnt = static_cast<unsigned long long*>(c->d_cnt.p);       // [0] refused map entries, [1] events outside the sensor, [2] kept
+    HIPCHK(c, hipMemsetAsync(d_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
+    unsigned long long h_cnt[4] = {0, 0, 0, 0};
+    if (rectify_map) {
+        c->rect_map_set = false;
+        ENSURE(c, c->r_fmap, (size_t)npix * 8); ENSURE(c, c->r_map, (size_t)npix * 4);
+        HIPCHK(c, hipMemcpyAsync(c->r_fmap.p, rectify_map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_rect_map, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, c->stream, npix,
+                           static_cast<const float2*>(c->r_fmap.p), static_cast<uint32_t*>(c->r_map.p), d_cnt);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (h_cnt[0]) return fail(c, EINCM_ERR_ARG, "rectify map: %llu of %lld entries are not finite or do not round into int16", h_cnt[0], (long long)npix);
+        c->rect_map_set = true;
+    }
+    *n_kept = 0;
+    if (n == 0) return EINCM_OK;
+    const int64_t nblk = (n + RECT_BLOCK - 1) / RECT_BLOCK;
+    ENSURE(c, c->r_x, (size_t)n * 2); ENSURE(c, c->r_y, (size_t)n * 2); ENSURE(c, c->r_rx, (size_t)n * 2); ENSURE(c, c->r_ry, (size_t)n * 2);
+    ENSURE(c, c->r_keep, (size_t)n); ENSURE(c, c->r_cnt, (size_t)nblk * 4); ENSURE(c, c->r_off, (size_t)nblk * 8);
+    HIPCHK(c, hipMemcpyAsync(c->r_x.p, x, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->r_y.p, y, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
+    const auto* d_x = static_cast<const int16_t*>(c->r_x.p);
+    const auto* d_y = static_cast<const int16_t*>(c->r_y.p);
+    const auto* d_map = static_cast<const uint32_t*>(c->r_map.p);
+    hipLaunchKernelGGL(k_rect_count, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, d_x, d_y, d_map, static_cast<uint8_t*>(c->r_keep.p),
+                       static_cast<uint32_t*>(c->r_cnt.p), d_cnt + 1);
+    hipLaunchKernelGGL(k_rect_scan, dim3(1), dim3(RECT_SCAN_NT), 0, c->stream, (int)nblk, static_cast<const uint32_t*>(c->r_cnt.p),
+                       static_cast<int64_t*>(c->r_off.p), reinterpret_cast<int64_t*>(d_cnt + 2));
+    hipLaunchKernelGGL(k_rect_scatter, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, d_x, d_y, d_map,
+                       static_cast<const int64_t*>(c->r_off.p), static_cast<int16_t*>(c->r_rx.p), static_cast<int16_t*>(c->r_ry.p));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (h_cnt[1]) return fail(c, EINCM_ERR_ARG, "%llu of %lld events have a coordinate outside the %dx%d sensor", h_cnt[1], (long long)n, H, W);
+    const int64_t kept = (int64_t)h_cnt[2];
+    if (kept < 0 || kept > n) return fail(c, EINCM_ERR_HIP, "kept count %lld of %lld events", (long long)kept, (long long)n);
+    HIPCHK(c, hipMemcpyAsync(keep, c->r_keep.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    if (kept) {                                     // only the kept prefix comes back
+        HIPCHK(c, hipMemcpyAsync(rec_x, c->r_rx.p, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rec_y, c->r_ry.p, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_kept = kept;
+    return EINCM_OK;
+}
+
+// cv.remap(img, map, None, INTER_CUBIC) for a stack of 8-bit images under the contract of DESIGN.md section 16.
+int eincm_remap_cubic(eincm_ctx* c, const uint8_t* src, int n, int src_h, int src_w, const float* map, const int32_t* table, uint8_t* dst) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!src || !map || !table || !dst) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n < 1 || src_h < 1 || src_w < 1 || src_h > 32766 || src_w > 32766)
+        return fail(c, EINCM_ERR_ARG, "n = %d images of %dx%d (n >= 1, 1 <= size <= 32766)", n, src_h, src_w);
+    for (int r = 0; r < 1024; ++r) {
+        int64_t s = 0;
+        for (int k = 0; k < 16; ++k) { const int32_t w = table[r * 16 + k]; if (w < -32768 || w > 32768) s = INT64_MIN / 2; s += w; }
+        if (s != 32768) return fail(c, EINCM_ERR_ARG, "weight table row %d: weights within +-32768 that sum to 32768", r);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t npix = (int64_t)c->H * c->W;
+    const size_t sbytes = (size_t)n * src_h * src_w, dbytes = (size_t)n * npix, tbytes = 1024 * 16 * 4;
+    ENSURE(c, c->d_in, sbytes); ENSURE(c, c->d_out, dbytes); ENSURE(c, c->r_fmap, (size_t)npix * 8); ENSURE(c, c->d_tab, tbytes);
+    // (r_fmap is only staging for a float map: the rounded rectify map lives in r_map and stays)
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, src, sbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->r_fmap.p, map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_tab.p, table, tbytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_remap_cubic, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, c->stream, n, src_h, src_w, npix,
+                       static_cast<const uint8_t*>(c->d_in.p), static_cast<const float2*>(c->r_fmap.p),
+                       static_cast<const int32_t*>(c->d_tab.p), static_cast<uint8_t*>(c->d_out.p));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(dst, c->d_out.p, dbytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EINCM_OK;
+}
+
+// DSECDataLoader.flow_16bit_to_float (dsec_loader.py:247-266) for a stack of n flow images.
+int eincm_flow_decode(eincm_ctx* c, const uint16_t* flow16, int n, double* flow, uint8_t* valid, int64_t* n_bad) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!flow16 || !flow || !valid || !n_bad) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n < 1) return fail(c, EINCM_ERR_ARG, "n = %d (>= 1)", n);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t tot = (int64_t)n * c->H * c->W;
+    ENSURE(c, c->d_in, (size_t)tot * 6); ENSURE(c, c->d_out, (size_t)tot * 17); ENSURE(c, c->d_cnt, 4 * sizeof(unsigned long long));
+    auto* d_cnt = static_cast<unsigned long long*>(c->d_cnt.p);
+    double* d_flow = static_cast<double*>(c->d_out.p);
+    uint8_t* d_valid = static_cast<uint8_t*>(c->d_out.p) + (size_t)tot * 16;
+    HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_in.p, flow16, (size_t)tot * 6, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_flow_decode, dim3((unsigned)((tot + NT - 1) / NT)), dim3(NT), 0, c->stream, tot,
+                       static_cast<const uint16_t*>(c->d_in.p), d_flow, d_valid, d_cnt);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(flow, d_flow, (size_t)tot * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(valid, d_valid, (size_t)tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_bad = (int64_t)bad;
+    if (bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a third channel that is neither 0 nor 1", bad);
+    return EINCM_OK;
+}
+
+// dsec_npz_to_png.py:84-96 for a batch of theta: bilinear scale_and_translate to the sensor and the 16-bit code, in one kernel.
+int eincm_flow_encode(eincm_ctx* c, const double* theta, int n, int h, int w, const uint8_t* valid, uint16_t* out, int64_t* n_bad) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!theta || !out || !n_bad) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n < 1 || n > 65535 || h < 1 || w < 1 || h > 32767 || w > 32767) return fail(c, EINCM_ERR_ARG, "n = %d theta of %dx%d (1 <= n <= 65535)", n, h, w);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int H = c->H, W = c->W;
+    const int64_t npix = (int64_t)H * W;
+    std::vector<double> AH, AW, rwt, cwt;
+    std::vector<int32_t> rlo, rcnt, clo, ccnt;
+    resample_matrix(h, H, EINCM_METHOD_BILINEAR, AH);
+    resample_matrix(w, W, EINCM_METHOD_BILINEAR, AW);
+    const int rstride = resample_runs(AH, h, H, rlo, rcnt, rwt), cstride = resample_runs(AW, w, W, clo, ccnt, cwt);
+    // one upload: row weights | column weights | rlo | rcnt | clo | ccnt
+    const size_t o_cw = rwt.size() * 8, o_rlo = o_cw + cwt.size() * 8, o_rcnt = o_rlo + (size_t)H * 4, o_clo = o_rcnt + (size_t)H * 4,
+                 o_ccnt = o_clo + (size_t)W * 4, tbytes = o_ccnt + (size_t)W * 4;
+    std::vector<char> tab(tbytes);
+    std::memcpy(tab.data(), rwt.data(), rwt.size() * 8);
+    std::memcpy(tab.data() + o_cw, cwt.data(), cwt.size() * 8);
+    std::memcpy(tab.data() + o_rlo, rlo.data(), (size_t)H * 4);
+    std::memcpy(tab.data() + o_rcnt, rcnt.data(), (size_t)H * 4);
+    std::memcpy(tab.data() + o_clo, clo.data(), (size_t)W * 4);
+    std::memcpy(tab.data() + o_ccnt, ccnt.data(), (size_t)W * 4);
+    const size_t thbytes = (size_t)n * h * w * 16, vbytes = valid ? (size_t)n * npix : 0, vofs = (thbytes + 15) & ~(size_t)15;
+    ENSURE(c, c->d_in, vofs + vbytes); ENSURE(c, c->d_out, (size_t)n * npix * 6); ENSURE(c, c->d_tab, tbytes);
+    ENSURE(c, c->d_cnt, 4 * sizeof(unsigned long long));
+    auto* d_cnt = static_cast<unsigned long long*>(c->d_cnt.p);
+    char* d_in = static_cast<char*>(c->d_in.p);
+    const char* d_tab = static_cast<const char*>(c->d_tab.p);
+    HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in, theta, thbytes, hipMemcpyHostToDevice, c->stream));
+    if (valid) HIPCHK(c, hipMemcpyAsync(d_in + vofs, valid, vbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_tab.p, tab.data(), tbytes, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_flow_encode, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, H, W, h, w,
+                       reinterpret_cast<const double*>(d_in), reinterpret_cast<const int32_t*>(d_tab + o_rlo),
+                       reinterpret_cast<const int32_t*>(d_tab + o_rcnt), reinterpret_cast<const double*>(d_tab), rstride,
+                       reinterpret_cast<const int32_t*>(d_tab + o_clo), reinterpret_cast<const int32_t*>(d_tab + o_ccnt),
+                       reinterpret_cast<const double*>(d_tab + o_cw), cstride,
+                       valid ? reinterpret_cast<const uint8_t*>(d_in + vofs) : (const uint8_t*)nullptr,
+                       static_cast<uint16_t*>(c->d_out.p), d_cnt);
+    HIPCHK(c, hipGetLastError());
+    unsigned long long bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&bad, d_cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_out.p, (size_t)n * npix * 6, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // tab (host vector) stays alive until here
+    *n_bad = (int64_t)bad;
+    if (bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a flow that is not finite or encodes outside [0, 65536)", bad);
     return EINCM_OK;
 }
 

@@ -228,6 +228,118 @@ def gt_flow_stacks(gt_x, gt_y, sensor_size):
     return gx.astype(dt, copy=False), gy.astype(dt, copy=False)
 
 
+_remap_table = None
+
+
+def remap_cubic_table():
+    """The (32, 32, 16) int32 weight table of the remap contract.  Row (fy, fx), entry ky * 4 + kx.  1-D Keys
+    cubic, A = -0.75, in float32 at f / 32; 2-D weight rint(wy * wx * 32768) (float32 product, half to even); then the row is made to
+    sum to 32768: the difference is added to the largest of the central 2 x 2 weights when the sum is short and taken off the smallest
+    when it is over (first in row-major order on a tie).  int32, so that the single weight 32768 of fraction (0, 0) is held exactly."""
+    global _remap_table
+    if _remap_table is None:
+        f32 = np.float32
+        A = f32(-0.75)
+        x = np.arange(32, dtype=f32) / f32(32)
+        x1, xm = x + f32(1), f32(1) - x
+        c = np.empty((32, 4), dtype=f32)
+        c[:, 0] = ((A * x1 - f32(5) * A) * x1 + f32(8) * A) * x1 - f32(4) * A
+        c[:, 1] = ((A + f32(2)) * x - (A + f32(3))) * x * x + f32(1)
+        c[:, 2] = ((A + f32(2)) * xm - (A + f32(3))) * xm * xm + f32(1)
+        c[:, 3] = f32(1) - c[:, 0] - c[:, 1] - c[:, 2]
+        w = (c[:, None, :, None] * c[None, :, None, :]).astype(f32) * f32(32768)          # (fy, fx, ky, kx)
+        t = np.rint(w).astype(np.int32)
+        for fy in range(32):
+            for fx in range(32):
+                d = int(t[fy, fx].sum()) - 32768
+                if d:
+                    mid = t[fy, fx, 1:3, 1:3].reshape(-1)
+                    k = int(np.argmax(mid)) if d < 0 else int(np.argmin(mid))         # argmax / argmin: the first on a tie
+                    t[fy, fx, 1 + k // 2, 1 + k % 2] -= d
+        _remap_table = np.ascontiguousarray(t.reshape(32, 32, 16))
+        _remap_table.setflags(write=False)
+    return _remap_table
+
+
+def check_rectify_map(rectify_map, sensor_size, what='rectify_map'):
+    """A (H, W, 2) float32 map, C-contiguous.  Shape and type only: the values are checked on the GPU, once per map."""
+    H, W = int(sensor_size[0]), int(sensor_size[1])
+    m = np.asarray(rectify_map)
+    if m.shape != (H, W, 2):
+        raise ValueError(f'{what} must be ({H}, {W}, 2), got {m.shape}')
+    if m.dtype != np.float32:
+        raise ValueError(f'{what} must be float32, got {m.dtype}')
+    return np.ascontiguousarray(m)
+
+
+def check_event_coords(x, y):
+    """The x and y of an event stream as 1-D int16 arrays of one length (integer input only: a raw stream has no fractions)."""
+    x, y = np.asarray(x), np.asarray(y)
+    for name, a in (('x', x), ('y', y)):
+        if a.ndim != 1:
+            raise ValueError(f'event {name} must be 1-D, got shape {a.shape}')
+        if a.dtype.kind not in 'iu':
+            raise ValueError(f'event {name} must be an integer array, got {a.dtype}')
+    if x.shape != y.shape:
+        raise ValueError(f'event x {x.shape} and y {y.shape} differ in length')
+    return np.ascontiguousarray(as_int16_coords(x, 'x')), np.ascontiguousarray(as_int16_coords(y, 'y'))
+
+
+def check_chunk(chunk):
+    if isinstance(chunk, bool) or not isinstance(chunk, (int, np.integer)) or not 1 <= chunk <= 1 << 30:
+        raise ValueError(f'chunk {chunk!r}: an integer number of events in [1, 2^30]')
+    return int(chunk)
+
+
+def check_remap_args(src, mapping):
+    """src (n, Hs, Ws) or (Hs, Ws) uint8 with 1 <= Hs, Ws <= 32766; mapping (H, W, 2) float32.  Returns (src as a stack, mapping, single)."""
+    a = np.asarray(src)
+    if a.dtype != np.uint8:
+        raise ValueError(f'remap input must be uint8, got {a.dtype}')
+    single = a.ndim == 2
+    a = np.ascontiguousarray(a[None] if single else a)
+    if a.ndim != 3 or a.shape[0] < 1 or not (1 <= a.shape[1] <= 32766 and 1 <= a.shape[2] <= 32766):
+        raise ValueError(f'remap input must be (n, Hs, Ws) or (Hs, Ws) with n >= 1 and 1 <= Hs, Ws <= 32766, got {np.shape(src)}')
+    m = np.asarray(mapping)
+    if m.ndim != 3 or m.shape[2] != 2 or m.shape[0] < 1 or m.shape[1] < 1:
+        raise ValueError(f'mapping must be (H, W, 2), got {m.shape}')
+    if m.dtype != np.float32:
+        raise ValueError(f'mapping must be float32, got {m.dtype}')
+    return a, np.ascontiguousarray(m), single
+
+
+def check_flow_16bit(flow_16bit):
+    """(B, H, W, 3) or (H, W, 3) uint16 (dsec_loader.py:249-252).  Returns (stack, single)."""
+    a = np.asarray(flow_16bit)
+    if a.dtype != np.uint16:
+        raise ValueError(f'16-bit flow must be uint16, got {a.dtype}')
+    single = a.ndim == 3
+    a = a[None] if single else a
+    if a.ndim != 4 or a.shape[3] != 3 or a.shape[0] < 1:
+        raise ValueError(f'16-bit flow must be (B, H, W, 3) or (H, W, 3), got {np.shape(flow_16bit)}')
+    return np.ascontiguousarray(a), single
+
+
+def check_theta_batch(theta, valid, sensor_size):
+    """theta (B, h, w, 2) or (h, w, 2) as float64; valid None or (B, H, W) / (H, W).  Returns (theta, valid uint8 or None, single)."""
+    t = np.asarray(theta)
+    if t.dtype.kind not in 'fiu':
+        raise ValueError(f'theta must be numeric, got {t.dtype}')
+    single = t.ndim == 3
+    t = t[None] if single else t
+    if t.ndim != 4 or t.shape[3] != 2 or min(t.shape[:3]) < 1 or t.shape[0] > 65535:
+        raise ValueError(f'theta must be (B, h, w, 2) or (h, w, 2) with 1 <= B <= 65535, got {np.shape(theta)}')
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    v = None
+    if valid is not None:
+        v = np.asarray(valid)
+        v = v[None] if single and v.ndim == 2 else v
+        if v.shape != (t.shape[0], int(sensor_size[0]), int(sensor_size[1])):
+            raise ValueError(f'valid must be {(t.shape[0], int(sensor_size[0]), int(sensor_size[1]))}, got {np.shape(valid)}')
+        v = np.ascontiguousarray(v != 0).astype(np.uint8)
+    return t, v, single
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                 full_aux=False, correlation_kind='mse'):
     """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
@@ -654,6 +766,72 @@ class Engine:
         self._check(self._lib.eincm_gt_flow(self._ctx, gx.ctypes.data, gy.ctypes.data, gx.itemsize, gx.shape[0], len(plans),
                                             mode.ctypes.data_as(i32), off.ctypes.data_as(i32), frame.ctypes.data_as(i32), _dp(num),
                                             _dp(den), _dp(out)))
+        return out[0] if single else out
+
+    # -- the DSEC data path --------------------------------------------------
+    def _check_data(self, rc):
+        """A refusal of the data itself (EINCM_ERR_ARG after the Python side has checked every shape) is a ValueError."""
+        if rc == L.ERR_ARG:
+            raise ValueError(self._lib.eincm_last_error(self._ctx).decode())
+        self._check(rc)
+
+    def rectify_events(self, x, y, rectify_map, chunk=1 << 22):
+        """DSECDataLoader.rectify_events (dsec_loader.py:145-171): (rx, ry) = rectify_map[y, x], rounded half to even to int16; events
+        that leave the sensor are dropped, the others keep their order.  x, y: integer arrays of a whole recording; rectify_map
+        (H, W, 2) float32.  The stream is walked in chunks of ``chunk`` events; the result does not depend on it.  Returns
+        (rec_x, rec_y, keep, n_kept): int16 arrays of the kept events, the bool mask over the input, the kept count.  ValueError: a map
+        entry that is not finite or does not round into int16, an input coordinate outside the sensor."""
+        m = check_rectify_map(rectify_map, (self.H, self.W))
+        xs, ys = check_event_coords(x, y)
+        chunk = check_chunk(chunk)
+        n = xs.shape[0]
+        rec_x, rec_y = np.empty(n, dtype=np.int16), np.empty(n, dtype=np.int16)
+        keep = np.empty(n, dtype=np.uint8)
+        kept, k = 0, C.c_int64(0)
+        # an empty stream still hands the map over, so that it is checked
+        for i0 in ([0] if n == 0 else range(0, n, chunk)):
+            i1 = min(n, i0 + chunk)
+            self._check_data(self._lib.eincm_rectify_events(
+                self._ctx, m.ctypes.data if i0 == 0 else None, xs.ctypes.data + 2 * i0, ys.ctypes.data + 2 * i0, i1 - i0,
+                rec_x.ctypes.data + 2 * kept, rec_y.ctypes.data + 2 * kept, keep.ctypes.data + i0, C.byref(k)))
+            kept += int(k.value)
+        return rec_x[:kept], rec_y[:kept], keep.view(np.bool_), kept
+
+    def remap_cubic(self, src, mapping):
+        """cv.remap(src, mapping, None, INTER_CUBIC) under the contract of DESIGN.md section 16 (map_image_to_rect_event,
+        dsec_loader.py:243-245).  src: (n, Hs, Ws) or (Hs, Ws) uint8, any size up to 32766; mapping (H, W, 2) float32 of the engine's
+        sensor size, one for the stack.  Returns (n, H, W) or (H, W) uint8."""
+        a, m, single = check_remap_args(src, mapping)
+        if m.shape[:2] != (self.H, self.W):
+            raise ValueError(f'mapping must be ({self.H}, {self.W}, 2), got {m.shape}')
+        tab = remap_cubic_table()
+        out = np.empty((a.shape[0], self.H, self.W), dtype=np.uint8)
+        self._check(self._lib.eincm_remap_cubic(self._ctx, a.ctypes.data, a.shape[0], a.shape[1], a.shape[2], m.ctypes.data,
+                                                tab.ctypes.data, out.ctypes.data))
+        return out[0] if single else out
+
+    def flow_decode(self, flow_16bit):
+        """DSECDataLoader.flow_16bit_to_float (dsec_loader.py:247-266) for (B, H, W, 3) or (H, W, 3) uint16: returns (flow float64
+        (..., H, W, 2), valid2D bool (..., H, W)).  ValueError: a pixel whose third channel is neither 0 nor 1 (the reference asserts)."""
+        a, single = check_flow_16bit(flow_16bit)
+        if a.shape[1:3] != (self.H, self.W):
+            raise ValueError(f'16-bit flow must be ({self.H}, {self.W}, 3) per image, got {a.shape[1:]}')
+        flow = np.empty(a.shape[:3] + (2,), dtype=np.float64)
+        valid = np.empty(a.shape[:3], dtype=np.uint8)
+        bad = C.c_int64(0)
+        self._check_data(self._lib.eincm_flow_decode(self._ctx, a.ctypes.data, a.shape[0], flow.ctypes.data, valid.ctypes.data, C.byref(bad)))
+        valid = valid.view(np.bool_)
+        return (flow[0], valid[0]) if single else (flow, valid)
+
+    def flow_encode(self, theta, valid=None):
+        """dsec_npz_to_png.py:84-96: theta (B, h, w, 2) or (h, w, 2), scaled to the sensor with the bilinear scale_and_translate and
+        coded as uint16(trunc(v * 128 + 2^15)), in one kernel.  Channel 2 is 0, or ``valid`` (B, H, W) where given.  Returns
+        (..., H, W, 3) uint16.  ValueError: a value that is not finite or codes outside [0, 65536)."""
+        t, v, single = check_theta_batch(theta, valid, (self.H, self.W))
+        out = np.empty((t.shape[0], self.H, self.W, 3), dtype=np.uint16)
+        bad = C.c_int64(0)
+        self._check_data(self._lib.eincm_flow_encode(self._ctx, t.ctypes.data, t.shape[0], t.shape[1], t.shape[2],
+                                                     None if v is None else v.ctypes.data, out.ctypes.data, C.byref(bad)))
         return out[0] if single else out
 
     # -- device images ----------------------------------------------------------------------------

@@ -8,6 +8,9 @@
   gt_flow_plan          the index and time arithmetic of MVSECDataLoader.estimate_gt_flow (src/dataloaders/mvsec_loader.py:322-408)
   estimate_gt_flow      MVSEC's ground-truth flow of evaluation windows: the plans above, walked by one HIP kernel over
                         (pixel, window)
+  flow_16bit_to_float   DSEC's GT flow format (src/dataloaders/dsec_loader.py:247-266), decoded on the GPU
+  dsec_submission_flow  DSEC's submission format of a solved theta (src/dsec_npz_to_png.py:84-96): up-sampling and 16-bit coding in one
+                        HIP kernel
 The masked reductions are O(H*W), run once per window, and stay on the host; every objective term comes from the GPU.
 """
 import sys
@@ -142,3 +145,33 @@ def estimate_gt_flow(gt_x, gt_y, gt_ts, t_start, t_end, engine=None):
         engine = _engine(np.shape(gt_x)[-2:])
     out = engine.gt_flow(gt_x, gt_y, plans)
     return out[0] if scalar else out
+
+
+def flow_16bit_to_float(flow_16bit, engine=None):
+    """DSECDataLoader.flow_16bit_to_float (dsec_loader.py:247-266) on the GPU.  flow_16bit: (H, W, 3) uint16, or a stack (B, H, W, 3).
+    Returns (flow_map float64 (..., H, W, 2), valid2D bool (..., H, W)): (c - 2^15) / 128 where the third channel is 1, exactly 0
+    elsewhere.  ValueError: not uint16, not (.., 3), or a pixel whose third channel is neither 0 nor 1 (the reference asserts)."""
+    from .engine import check_flow_16bit
+    a, single = check_flow_16bit(flow_16bit)
+    if engine is None:
+        from .edges import _engine
+        engine = _engine(a.shape[1:3])
+    flow, valid = engine.flow_decode(a)
+    return (flow[0], valid[0]) if single else (flow, valid)
+
+
+def dsec_submission_flow(theta, sensor_size=(480, 640), valid=None, engine=None):
+    """The 16-bit flow image dsec_npz_to_png.py:84-96 writes for a solved theta pyramid level.  theta: (h, w, 2) or a batch (B, h, w, 2);
+    it is scaled to sensor_size with the bilinear scale_and_translate and coded as uint16(trunc(v * 128 + 2^15)) into channels 0 and 1,
+    in one kernel.  Channel 2 is 0 as the reference leaves it, or ``valid`` ((H, W) / (B, H, W)) where given.  Returns (..., H, W, 3)
+    uint16.  ValueError: a value that is not finite or codes outside [0, 65536) (the reference's cast is undefined there)."""
+    from .engine import check_theta_batch
+    H, W = int(sensor_size[0]), int(sensor_size[1])
+    t, v, single = check_theta_batch(theta, valid, (H, W))
+    if engine is None:
+        from .edges import _engine
+        engine = _engine((H, W))
+    elif (engine.H, engine.W) != (H, W):
+        raise ValueError(f'sensor_size {(H, W)} is not the engine\'s {(engine.H, engine.W)}')
+    out = engine.flow_encode(t, v)
+    return out[0] if single else out

@@ -11,6 +11,9 @@ the caller passes ``edges``, a stack of smoothed edge images that ``normalize_ed
 
 mvsec_datasamples restates MVSECDataLoader.get_sample_between_two_image_timestamps (mvsec_loader.py:247-320) for arrays in memory,
 its ``flow_gt`` from evaluation.estimate_gt_flow; eval_event_slice is the evaluation-event rule of exp_mgr.py:301-313.
+
+The DSEC data path (DSECDataLoader, src/dataloaders/dsec_loader.py), for arrays in memory as well:
+rectify_events (:145-171), dsec_image_mapping and map_images_to_rect_event (:188-245), dsec_datasamples (:173-186, :285-350).
 """
 import sys
 
@@ -127,4 +130,149 @@ def mvsec_datasamples(events, images, image_ts, gt_x, gt_y, gt_ts, image_indices
             'n_event_deficiency': None if des_n_events is None else deficiency,
             'orig_n_events': orig_n_events,
         })
+    return out
+
+
+def _dsec_engine(engine, sensor_size):
+    if engine is not None:
+        return engine
+    from .edges import _engine
+    return _engine(sensor_size)
+
+
+def rectify_events(events, rectify_map, engine=None, chunk=1 << 22):
+    """DSECDataLoader.rectify_events (dsec_loader.py:145-171).  events: {'x','y','t','p'} arrays of a recording; rectify_map (H, W, 2)
+    float32, channel 0 = x.  x and y go through Engine.rectify_events in chunks of ``chunk`` events (the result does not depend on it);
+    t and p never travel: the keep mask is applied to them here.  Returns the rectified {'x','y','t','p'} (x, y int16).  ValueError:
+    a map that is not (H, W, 2) float32 of the engine's sensor, a map entry that is not finite or does not round into int16, an event
+    coordinate outside the sensor (the reference asserts), arrays of different lengths."""
+    from .engine import check_chunk, check_event_coords, check_rectify_map
+    m = np.asarray(rectify_map)
+    if m.ndim != 3:
+        raise ValueError(f'rectify_map must be (H, W, 2), got {m.shape}')
+    m = check_rectify_map(m, m.shape[:2] if engine is None else (engine.H, engine.W))
+    missing = [k for k in ('x', 'y', 't', 'p') if k not in events]
+    if missing:
+        raise ValueError(f'events lack {missing}')
+    x, y = check_event_coords(events['x'], events['y'])
+    t, p = np.asarray(events['t']), np.asarray(events['p'])
+    if t.shape != x.shape or p.shape != x.shape:
+        raise ValueError(f'events t {t.shape} and p {p.shape} must have the length of x {x.shape}')
+    chunk = check_chunk(chunk)
+    rec_x, rec_y, keep, _ = _dsec_engine(engine, m.shape[:2]).rectify_events(x, y, m, chunk=chunk)
+    return {'x': rec_x, 'y': rec_y, 't': t[keep], 'p': p[keep]}
+
+
+def _k_matrix(cam_to_cam, name):
+    cm = np.asarray(cam_to_cam['intrinsics'][name]['camera_matrix'], dtype=np.float64)
+    if cm.shape != (4,) or not np.all(np.isfinite(cm)):
+        raise ValueError(f'intrinsics.{name}.camera_matrix must be four finite numbers (fx, fy, cx, cy), got {cm!r}')
+    return np.array([[cm[0], 0.0, cm[2]], [0.0, cm[1], cm[3]], [0.0, 0.0, 1.0]])
+
+
+def dsec_image_mapping(cam_to_cam, sensor_size=(480, 640)):
+    """construct_mapping_for_image (dsec_loader.py:188-218) from the dict of a sequence's cam_to_cam.yaml: for every pixel of the
+    rectified event camera, where it lies in the rectified frame camera.  P = K_r1 . R . K_r0^-1 with R the rotation part of
+    T_r1_1 . T_1_0 . T_r0_0^-1, that is R_rect1 . R_10 . R_rect0^T (a rotation's inverse is its transpose); (u, v, s) = P (x, y, 1);
+    map = (u / s, v / s) in float64, cast to float32.  Rotations stay 3 x 3 matrices: the reference's round trip through quaternions
+    (scipy Rotation) is not made, which can move the float64 values by their last bits before the cast.
+    Returns (H, W, 2) float32.  ValueError: a missing key, a matrix of the wrong shape, a non-finite entry."""
+    H, W = int(sensor_size[0]), int(sensor_size[1])
+    if H < 1 or W < 1:
+        raise ValueError(f'sensor_size {sensor_size!r}: positive (H, W)')
+    try:
+        K_r0, K_r1 = _k_matrix(cam_to_cam, 'camRect0'), _k_matrix(cam_to_cam, 'camRect1')
+        ex = cam_to_cam['extrinsics']
+        R_r0_0, R_r1_1 = np.asarray(ex['R_rect0'], dtype=np.float64), np.asarray(ex['R_rect1'], dtype=np.float64)
+        T_10 = np.asarray(ex['T_10'], dtype=np.float64)
+    except (KeyError, TypeError) as e:
+        raise ValueError(f'cam_to_cam lacks {e}: intrinsics.camRect0/camRect1.camera_matrix, extrinsics.R_rect0/R_rect1/T_10') from None
+    if R_r0_0.shape != (3, 3) or R_r1_1.shape != (3, 3) or T_10.shape != (4, 4):
+        raise ValueError(f'R_rect0 {R_r0_0.shape}, R_rect1 {R_r1_1.shape} must be (3, 3) and T_10 {T_10.shape} (4, 4)')
+    if not (np.all(np.isfinite(R_r0_0)) and np.all(np.isfinite(R_r1_1)) and np.all(np.isfinite(T_10))):
+        raise ValueError('non-finite extrinsics')
+    P = K_r1 @ (R_r1_1 @ T_10[:3, :3] @ R_r0_0.T) @ np.linalg.inv(K_r0)
+    xs, ys = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    hom = np.stack([xs, ys, np.ones_like(xs)], axis=-1) @ P.T
+    return np.ascontiguousarray((hom[..., :2] / hom[..., 2:3]).astype(np.float32))
+
+
+def map_images_to_rect_event(images, mapping, engine=None):
+    """map_image_to_rect_event (dsec_loader.py:243-245) for a stack: cv.remap(img, mapping, None, INTER_CUBIC) under the contract of
+    DESIGN.md section 16, one GPU call for the stack.  images (n, Hs, Ws) or (Hs, Ws) uint8; mapping (H, W, 2) float32
+    (dsec_image_mapping).  Returns (n, H, W) or (H, W) uint8, ready for edges.frames_to_edges."""
+    from .engine import check_remap_args
+    a, m, single = check_remap_args(images, mapping)
+    out = _dsec_engine(engine, m.shape[:2]).remap_cubic(a, m)
+    return out[0] if single else out
+
+
+def dsec_datasamples(events, images, image_ts_us, eval_ts_us, t_offset, eval_indices, des_n_events=1_500_000, prefer_latest_events=True,
+                     flow_gt_16bit=None, mapping=None, engine=None):
+    """DSECDataLoader.get_sample (dsec_loader.py:285-350) with precompute_eval_event_indices / precompute_eval_image_indices (:173-186)
+    for each index of eval_indices, on arrays in memory.  events: {'x','y','t','p'}, rectified (rectify_events) and time-sorted, t
+    without the offset; images (n, Hs, Ws) uint8 with image_ts_us (n,); eval_ts_us (n_eval, 3): start, end, file index (the train split's two columns do when flow_gt_16bit is given); t_offset: the
+    recording's offset.  Both ends of a window are searchsorted(..., 'left'): the events on t against eval_ts_us - t_offset, the images
+    on image_ts_us against eval_ts_us, the image slice start : end + 1.  The event window is fitted to des_n_events by
+    fit_event_window; the returned t has t_offset added.  mapping (H, W, 2) float32: the window's images go through one remap_cubic
+    call (map_images_to_rect_event); None: they are handed on as they are.  flow_gt_16bit (len(eval_indices), H, W, 3) uint16, the GT
+    images of the requested windows in order: decoded by one flow_decode call into the keys flow_gt, valid2D; None: the key file_idx
+    instead (the reference's test split).  Keys besides: events, images, image_ts, eval_ts_us, n_event_deficiency, orig_n_events.
+    The reference sets n_event_deficiency only when des_n_events is not None (with None its get_sample fails on the first call);
+    here it is None then.  Each dict goes through stage_datasample as it is."""
+    ev_ts = np.asarray(eval_ts_us)
+    if ev_ts.ndim != 2 or ev_ts.shape[1] < (2 if flow_gt_16bit is not None else 3):
+        raise ValueError(f'eval_ts_us must be (n_eval, 3): start, end, file index (the index may be absent with flow_gt_16bit); got {ev_ts.shape}')
+    image_ts_us = np.asarray(image_ts_us)
+    if image_ts_us.ndim != 1 or len(images) != len(image_ts_us):
+        raise ValueError(f'{len(images)} images and image_ts_us of shape {image_ts_us.shape}')
+    missing = [k for k in ('x', 'y', 't', 'p') if k not in events]
+    if missing:
+        raise ValueError(f'events lack {missing}')
+    ev = {k: np.asarray(events[k]) for k in ('x', 'y', 't', 'p')}
+    n = len(ev['t'])
+    if any(a.shape != (n,) for a in ev.values()):
+        raise ValueError('events x, y, t, p must be 1-D of one length')
+    if des_n_events is not None and (isinstance(des_n_events, bool) or int(des_n_events) != des_n_events or des_n_events < 1):
+        raise ValueError(f'des_n_events {des_n_events!r}: a positive integer or None')
+    idxs = [int(i) for i in np.atleast_1d(eval_indices)]
+    for i in idxs:
+        if not 0 <= i < len(ev_ts):
+            raise ValueError(f'eval index {i} outside the {len(ev_ts)} evaluation windows')
+    flow = valid = None
+    if flow_gt_16bit is not None:
+        from .engine import check_flow_16bit
+        f16, _ = check_flow_16bit(flow_gt_16bit)
+        if np.ndim(flow_gt_16bit) != 4 or f16.shape[0] != len(idxs):
+            raise ValueError(f'flow_gt_16bit must hold one (H, W, 3) image per requested window ({len(idxs)}), got {np.shape(flow_gt_16bit)}')
+    if mapping is not None:
+        from .engine import check_remap_args
+        check_remap_args(np.asarray(images)[:1], mapping)
+    ev_start = np.searchsorted(ev['t'], ev_ts[:, 0] - t_offset, side='left')
+    ev_end = np.searchsorted(ev['t'], ev_ts[:, 1] - t_offset, side='left')
+    im_start = np.searchsorted(image_ts_us, ev_ts[:, 0], side='left')
+    im_end = np.searchsorted(image_ts_us, ev_ts[:, 1], side='left')
+    if flow_gt_16bit is not None and idxs:
+        flow, valid = _dsec_engine(engine, f16.shape[1:3]).flow_decode(f16)
+    out = []
+    for b, i in enumerate(idxs):
+        i0, i1 = int(ev_start[i]), int(ev_end[i])
+        orig_n_events = i1 - i0
+        i0, i1, deficiency = fit_event_window(n, i0, i1, des_n_events, prefer_latest_events)
+        imgs = images[int(im_start[i]):int(im_end[i]) + 1]
+        if mapping is not None and len(imgs):
+            imgs = map_images_to_rect_event(imgs, mapping, engine=engine)
+        d = {
+            'events': {'x': ev['x'][i0:i1], 'y': ev['y'][i0:i1], 't': ev['t'][i0:i1] + t_offset, 'p': ev['p'][i0:i1]},
+            'images': imgs,
+            'image_ts': image_ts_us[int(im_start[i]):int(im_end[i]) + 1],
+            'eval_ts_us': ev_ts[i, :2],
+        }
+        if flow is None:
+            d['file_idx'] = ev_ts[i, 2]
+        else:
+            d['flow_gt'], d['valid2D'] = flow[b], valid[b]
+        d['n_event_deficiency'] = None if des_n_events is None else deficiency
+        d['orig_n_events'] = orig_n_events
+        out.append(d)
     return out

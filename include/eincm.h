@@ -26,7 +26,8 @@ extern "C" {
 #define EINCM_ABI_VERSION 6   /* 2: eincm_iwe_device_ptr hands out the u64 fixed-point accumulator of the IWE stack; 3: eincm_set_timed_kernels, eincm_set_windows_ptrs;
                                 * 4: eincm_loss_grad_masked, eincm_set_device_results / eincm_finish_launch / eincm_grad_device_ptr / eincm_finish_collect, eincm_get_host_profile;
                                * 5: eincm_get_warped_events, eincm_loss_grad_device, eincm_loss_grad_masked_async, eincm_set_timing_period;
-                               * 6: eincm_get_launch_policy */
+                               * 6: eincm_get_launch_policy; added since without a new version: eincm_rectify_events, eincm_remap_cubic, eincm_flow_decode,
+                               *    eincm_flow_encode (the DSEC data path) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -431,6 +432,38 @@ int eincm_set_splat_window(eincm_ctx* ctx, int window_size);
 #define EINCM_GTF_PROPAGATE 1
 int eincm_gt_flow(eincm_ctx* ctx, const void* gt_x, const void* gt_y, int elem_bytes, int n_frames, int n_windows, const int32_t* mode,
                   const int32_t* step_off, const int32_t* step_frame, const double* step_num, const double* step_den, double* out);
+
+/* The DSEC data path.  Arrays in memory only: no file is read or written.
+ *
+ * DSECDataLoader.rectify_events (dsec_loader.py:145-171) for one chunk of n <= 2^30 events.  rectify_map (H, W, 2) float, channel 0 = x,
+ * H x W the context's sensor: (rx, ry) = rectify_map[y][x]; rec = (int16)rint(r), rint in float, half to even; an event is kept iff
+ * 0 <= rec_x < W and 0 <= rec_y < H.  keep (n) gets 1 / 0 per event, rec_x and rec_y (capacity n) the kept events' coordinates in
+ * stream order (a stable compaction; the same bytes on every run), *n_kept their number.  A non-null rectify_map is uploaded, checked and
+ * becomes the context's map; a later chunk of the same recording passes NULL.  EINCM_ERR_ARG: a map entry that is not finite or
+ * whose rounding does not fit int16 (checked once, when the map is handed over; the context then has no map), an event coordinate outside
+ * the sensor (the outputs are not written).  EINCM_ERR_STATE: NULL map and no map in the context. */
+int eincm_rectify_events(eincm_ctx* ctx, const float* rectify_map, const int16_t* x, const int16_t* y, int64_t n, int16_t* rec_x,
+                         int16_t* rec_y, uint8_t* keep, int64_t* n_kept);
+
+/* cv.remap(src, map, None, INTER_CUBIC) of 8-bit single-channel images, constant border 0, as a written contract (DESIGN.md section 16;
+ * parity with OpenCV itself is not pinned).  src (n, src_h, src_w), 1 <= src_h, src_w <= 32766, independent of the sensor; map (H, W, 2)
+ * float, channel 0 = x, one map for the stack; dst (n, H, W).  Per component p = map * 32 in float; NaN: the pixel is 0; p clamped to
+ * +-2^30 and rounded half to even to s; integer part s >> 5 clamped to int16, fraction s & 31.  table (32, 32, 16) int32: row
+ * (fy, fx) holds the 4 x 4 weights (ky major) of that fraction pair, each within +-32768 and each row summing to 32768 (else
+ * EINCM_ERR_ARG; engine.remap_cubic_table builds the contract's).  Taps (iy - 1 .. iy + 2, ix - 1 .. ix + 2), a tap outside the
+ * source adds 0; dst = clamp((sum + 2^14) >> 15, 0, 255). */
+int eincm_remap_cubic(eincm_ctx* ctx, const uint8_t* src, int n, int src_h, int src_w, const float* map, const int32_t* table, uint8_t* dst);
+
+/* DSECDataLoader.flow_16bit_to_float (dsec_loader.py:247-266): flow16 (n, H, W, 3) uint16 -> flow (n, H, W, 2) double,
+ * ((double)c - 32768) / 128 where channel 2 is 1 and 0 elsewhere, and valid (n, H, W) 1 / 0.  *n_bad: pixels whose channel 2 is neither
+ * 0 nor 1 (the reference asserts on them); if any, EINCM_ERR_ARG (the outputs are written all the same). */
+int eincm_flow_decode(eincm_ctx* ctx, const uint16_t* flow16, int n, double* flow, uint8_t* valid, int64_t* n_bad);
+
+/* dsec_npz_to_png.py:84-96: theta (n, h, w, 2) double is scaled to (H, W) with the bilinear scale_and_translate weights of
+ * eincm_resample_matrix and coded as (uint16)trunc(v * 128 + 32768) in double into channels 0 and 1 of out (n, H, W, 3), in one kernel.
+ * Channel 2: 0, or valid[n][H][W] != 0 where valid is not NULL.  *n_bad: pixels with a value that is not finite or codes outside
+ * [0, 65536) (stored as 0); if any, EINCM_ERR_ARG.  1 <= n <= 65535. */
+int eincm_flow_encode(eincm_ctx* ctx, const double* theta, int n, int h, int w, const uint8_t* valid, uint16_t* out, int64_t* n_bad);
 
 #ifdef __cplusplus
 }
