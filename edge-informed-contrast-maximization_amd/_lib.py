@@ -28,6 +28,10 @@ CF_TIMING = 1
 CF_TIMING_DOMINANT = 2
 CF_FP64 = 4                # float64 mode (Engine(..., precision='fp64'))
 PRECISIONS = ('fp32', 'fp64')
+BFGS_MAX_N, BFGS_MAX_WINDOWS = 1024, 64                              # EINCM_BFGS_MAX_N, EINCM_BFGS_MAX_WINDOWS
+BFGS_SKIP, BFGS_UPDATE, BFGS_MOVE, BFGS_INIT = 0, 1, 2, 3            # eincm_bfgs_accept modes (EINCM_BFGS_*)
+BFGS_S_DPHI0, BFGS_S_GMAX, BFGS_S_PNORM, BFGS_S_XMAX, BFGS_S_PMAX, BFGS_S_GNORM, BFGS_S_YS, BFGS_S_YHY = range(8)   # EINCM_BFGS_S_*
+BFGS_NS = 8
 
 
 class Params(C.Structure):
@@ -147,6 +151,16 @@ SIGNATURES = [
     ('eincm_remap_cubic', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('eincm_flow_decode', C.c_int, [_P, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ('eincm_flow_encode', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    # BFGS with its state in HBM (raw addresses: called once per lockstep tick)
+    ('eincm_bfgs_begin', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    ('eincm_bfgs_eval', C.c_int, [_P, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('eincm_bfgs_trial', C.c_int, [_P, C.c_void_p, C.c_void_p]),
+    ('eincm_bfgs_reduce', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('eincm_bfgs_trial_ptrs', C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)]),
+    ('eincm_bfgs_state_ptrs', C.c_int, [_P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                        C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    ('eincm_bfgs_accept', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('eincm_bfgs_fetch', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

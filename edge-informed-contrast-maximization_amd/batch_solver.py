@@ -18,7 +18,7 @@ ready at the same moment can use that.  This module is that caller:
 import numpy as np
 import scipy.optimize as spo
 from scipy.optimize._dcsrch import DCSRCH            # MINPACK-2 dcsrch as SciPy ships it: reverse communication, one step per call
-from scipy.optimize._linesearch import line_search_wolfe2
+from scipy.optimize._linesearch import line_search_wolfe2, scalar_search_wolfe2
 from scipy.linalg.blas import dsymv, dsyr2
 
 if not hasattr(DCSRCH, '_iterate'):                  # private SciPy API (1.12 ... 1.15 have it): fail at import, not mid-solve
@@ -37,6 +37,7 @@ try:                                                 # level-2 BLAS on a 512 x 5
 except ImportError:                                  # without it the update stays in plain numpy
     threadpool_limits = None
 
+from . import _lib as L
 from .engine import Engine, check_precision, check_window_size, make_params
 from .solver import ScipyMinimizeInfo, EmptyCallback, rescale_theta, _canon
 
@@ -426,6 +427,355 @@ class LockstepBFGS:
                 self._start_group(gi)                  # back on the GPU before the next group is collected and fed
         return self._results()
 
+# ---- the same minimisation driven by scalars: x, its gradient, the direction and the inverse Hessian live in a state object --------------
+BFGS_STATES = ('host', 'device')
+
+
+def check_bfgs_state(bfgs_state):
+    """'host' or 'device'; anything else is a ValueError."""
+    if bfgs_state not in BFGS_STATES:
+        raise ValueError(f"bfgs_state {bfgs_state!r}: 'host' or 'device'")
+    return bfgs_state
+
+
+class NumpyBFGSState:
+    """The state interface on the CPU, op for op what ``_WindowBFGS`` does on its rank-two path: the written-down contract of
+    ``DeviceBFGSState``.  A state holds, per window, the point x, its gradient g, the direction p, the inverse Hessian H, the trial
+    point xt = x + a p of the last evaluation and its gradient gt:
+
+    * ``begin(x0, active)``          x = x0, H = I
+    * ``eval(alpha, mask)``          one evaluation at x + alpha[b] p per window of the mask -> (f, phi' = gt . p, max|gt|), each (B,)
+    * ``accept(alpha, modes)``       per window _lib.BFGS_SKIP / UPDATE (the rank-two update with s = alpha p, y = gt - g, then x <- xt,
+                                     g <- gt, p = -H g) / MOVE (x <- xt, g <- gt) / INIT (MOVE and p = -H g) -> scalars (B, _lib.BFGS_NS)
+    * ``fetch(want_hess_inv)``       (x, g, H | None) as arrays (B, n), (B, n), (B, n, n)
+
+    fun_batch(X, mask) -> (values (B,), grads (B, n)) as for ``LockstepBFGS``."""
+
+    def __init__(self, fun_batch):
+        self.fun_batch = fun_batch
+
+    def begin(self, x0, active=None):
+        x0 = np.array(x0, dtype=np.float64)
+        self.B, self.n = x0.shape
+        act = np.ones(self.B, bool) if active is None else np.asarray(active, bool)
+        if not hasattr(self, 'x') or self.x.shape != x0.shape:
+            self.x, self.g, self.p = x0.copy(), np.zeros_like(x0), np.zeros_like(x0)
+            self.xt, self.gt = x0.copy(), np.zeros_like(x0)
+            self.H = [None] * self.B
+            self.scal = np.zeros((self.B, L.BFGS_NS))
+        self.sym = threadpool_limits is not None
+        for b in np.flatnonzero(act):
+            self.x[b] = x0[b]
+            self.g[b] = 0.0
+            self.p[b] = 0.0
+            # sym: the inverse Hessian lives in the UPPER triangle of a Fortran-ordered array (dsymv / dsyr2 touch half the matrix)
+            self.H[b] = np.asfortranarray(np.eye(self.n)) if self.sym else np.eye(self.n)
+
+    def set_state(self, b, x=None, g=None, p=None, H=None):
+        """Overwrite parts of window b's state (H: a full symmetric matrix)."""
+        for dst, src in ((self.x, x), (self.g, g), (self.p, p)):
+            if src is not None:
+                dst[b] = np.asarray(src, dtype=np.float64)
+        if H is not None:
+            H = np.asarray(H, dtype=np.float64)
+            self.H[b] = np.asfortranarray(np.triu(H)) if self.sym else H.copy()
+
+    def eval(self, alpha, mask):
+        for b in np.flatnonzero(mask):
+            self.xt[b] = self.x[b] + alpha[b] * self.p[b]
+        v, g = self.fun_batch(self.xt, mask)
+        f, dphi, gmax = np.full(self.B, np.nan), np.zeros(self.B), np.zeros(self.B)
+        for b in np.flatnonzero(mask):
+            self.gt[b] = np.asarray(g[b], dtype=np.float64).reshape(-1)
+            f[b] = float(v[b])
+            dphi[b] = float(np.dot(self.gt[b], self.p[b]))
+            gmax[b] = np.abs(self.gt[b]).max() if self.n else 0.0
+        return f, dphi, gmax
+
+    def _direction(self, b):
+        return -dsymv(1.0, self.H[b], self.g[b], lower=0) if self.sym else -np.dot(self.H[b], self.g[b])
+
+    def accept(self, alpha, modes):
+        for b in range(self.B):
+            mode = int(modes[b])
+            if mode == L.BFGS_SKIP:
+                continue
+            ys = yhy = 0.0
+            if mode == L.BFGS_UPDATE:
+                sk = alpha[b] * self.p[b]
+                yk = self.gt[b] - self.g[b]
+                rhok_inv = float(np.dot(yk, sk))
+                rhok = 1000.0 if rhok_inv == 0.0 else 1.0 / rhok_inv
+                Hy = dsymv(1.0, self.H[b], yk, lower=0) if self.sym else np.dot(self.H[b], yk)
+                ys, yhy = rhok_inv, float(np.dot(yk, Hy))
+                w = (0.5 * rhok * (1.0 + rhok * yhy)) * sk - rhok * Hy
+                if self.sym:
+                    self.H[b] = dsyr2(1.0, sk, w, a=self.H[b], overwrite_a=1, lower=0)
+                else:
+                    sw = np.outer(sk, w)
+                    self.H[b] = self.H[b] + sw + sw.T
+            self.x[b] = self.xt[b]
+            self.g[b] = self.gt[b]
+            if mode != L.BFGS_MOVE:
+                self.p[b] = self._direction(b)
+            g, p, x = self.g[b], self.p[b], self.x[b]
+            self.scal[b] = (float(np.dot(g, p)), np.abs(g).max(), np.linalg.norm(p), np.abs(x).max(), np.abs(p).max(),
+                            np.linalg.norm(g), ys, yhy)
+        return self.scal.copy()
+
+    def full_hess_inv(self, b):
+        H = self.H[b]
+        if not self.sym:
+            return H.copy()
+        d = H.diagonal().copy()                                    # (the strictly lower triangle is still the identity's: zero)
+        H = H + H.T
+        H[np.diag_indices(self.n)] = d
+        return H
+
+    def fetch(self, want_hess_inv=False):
+        H = np.stack([self.full_hess_inv(b) if self.H[b] is not None else np.zeros((self.n, self.n)) for b in range(self.B)]) \
+            if want_hess_inv else None
+        return self.x.copy(), self.g.copy(), H
+
+
+class DeviceBFGSState:
+    """The state interface on the GPU: the engine's eincm_bfgs_* entry points (csrc/eincm_bfgs.hip.h).  ``shape``: one window's theta
+    (h, w, 2); x0 and the fetched arrays are (B, n) with n = 2 h w.  Nothing but scalars crosses PCIe between begin and fetch."""
+
+    def __init__(self, engine, shape, params):
+        self.engine, self.shape, self.params = engine, tuple(shape), params
+
+    def begin(self, x0, active=None):
+        x0 = np.asarray(x0, dtype=np.float64)
+        self.B, self.n = x0.shape
+        self.engine.bfgs_begin(x0.reshape((self.B,) + self.shape), active)
+
+    def eval(self, alpha, mask):
+        return self.engine.bfgs_eval(self.params, alpha, mask)
+
+    def accept(self, alpha, modes):
+        return self.engine.bfgs_accept(alpha, modes)
+
+    def fetch(self, want_hess_inv=False):
+        x, g, H = self.engine.bfgs_fetch(want_hess_inv)
+        return x.reshape(self.B, self.n), g.reshape(self.B, self.n), H
+
+
+class _ScalarWindowBFGS:
+    """``_WindowBFGS`` with the vectors taken out: the same phases, stopping rules and status codes, fed (phi, phi', max|grad|) at the
+    step it asked for.  ``request`` is that step (a float) or None; after a feed ``pending`` may hold (mode, alpha): what the state has to
+    do with the window before ``accepted`` gets the new iterate's scalars."""
+
+    def __init__(self, maxiter, gtol, n, wolfe2_fallback=True):
+        self.wolfe2_fallback = bool(wolfe2_fallback)
+        self.n = int(n)
+        self.maxiter = int(maxiter) if maxiter is not None else self.n * 200
+        self.gtol = float(gtol)
+        self.phase, self.request = 'init', 0.0          # the first evaluation: at x0 (the state's direction is 0)
+        self.pending = None
+        self.k = self.nfev = self.warnflag = 0
+        self.xnan = False
+        self.done = False
+        self.ls2 = None
+
+    def feed(self, f, dphi, gmax):
+        f, dphi, gmax = float(f), float(dphi), float(gmax)
+        if self.phase == 'init':
+            self.nfev += 1
+            self.old_fval, self.gnorm = f, gmax
+            self._after = 'init'
+            self.pending, self.request = (L.BFGS_INIT, 0.0), None
+        elif self.phase == 'ls':
+            self.nfev += 1
+            self.phi1, self.derphi1, self.gmax_t = f, dphi, gmax
+            self._ls_step()
+        elif self.phase == 'ls2':
+            self.nfev += 1
+            self.gmax_t = gmax
+            self.ls2.answer(f, dphi)
+            self._ls2_advance()
+        elif self.phase == 'reeval':                    # the accepted step was not the last one evaluated: its gradient, not counted
+            self.gmax_t = gmax
+            self._step_taken(self.alpha_k, self.new_fval)
+        else:
+            raise RuntimeError('feed() on a finished window')
+
+    def accepted(self, scal):
+        """The scalars of the iterate the state has just moved to (what ``pending`` asked for)."""
+        self.pending = None
+        self.scal = scal
+        self.xnan = bool(np.isnan(scal[L.BFGS_S_XMAX]))
+        if self._after == 'init':
+            self.old_old_fval = self.old_fval + scal[L.BFGS_S_GNORM] / 2          # initial step guess dx ~ 1
+            self._begin_iteration()
+        elif self._after == 'iterate':
+            self._begin_iteration()
+        else:
+            self._finish()
+
+    def _begin_iteration(self):
+        if not (self.gnorm > self.gtol and self.k < self.maxiter):
+            return self._finish()
+        derphi0 = float(self.scal[L.BFGS_S_DPHI0])
+        self.pnorm = self.scal[L.BFGS_S_PNORM]
+        if self.old_old_fval is not None and derphi0 != 0:
+            alpha1 = min(1.0, 1.01 * 2 * (self.old_fval - self.old_old_fval) / derphi0)
+            if alpha1 < 0:
+                alpha1 = 1.0
+        else:
+            alpha1 = 1.0
+        self.dcsrch = DCSRCH(None, None, _BFGS_C1, _BFGS_C2, _BFGS_XTOL, _BFGS_AMIN, _BFGS_AMAX)
+        self.task, self.alpha1, self.phi1, self.derphi1, self.derphi0 = b'START', alpha1, self.old_fval, derphi0, derphi0
+        self.gmax_t = self.gnorm
+        self.ls_iter = 0
+        self._ls_step()
+
+    def _ls_step(self):
+        if self.ls_iter >= _LS_MAXITER:
+            return self._ls_done(None)
+        self.ls_iter += 1
+        stp, self.phi1, self.derphi1, self.task = self.dcsrch._iterate(self.alpha1, self.phi1, self.derphi1, self.task)
+        if not np.isfinite(stp):
+            return self._ls_done(None)
+        if self.task[:2] == b'FG':
+            self.alpha1 = stp
+            self.phase, self.request = 'ls', float(stp)
+            return
+        if self.task[:5] == b'ERROR' or self.task[:4] == b'WARN':
+            stp = None
+        self._ls_done(stp)
+
+    def _ls_done(self, stp):
+        if stp is not None:
+            return self._step_taken(stp, self.phi1)
+        if not self.wolfe2_fallback:
+            self.warnflag = 2
+            return self._finish()
+        # SciPy's second line search, line_search_wolfe2, is scalar_search_wolfe2 on phi(a) = f(xk + a pk) and derphi(a) = grad . pk with
+        # the gradient of the last derphi call kept for the caller.  The helper thread's f / fprime calls become this window's requests
+        # (_CoroutineCall): the point is the step a, the "gradient" phi'(a); its cache answers derphi(a) after phi(a) without an evaluation.
+        def search(fv, fg):
+            return scalar_search_wolfe2(lambda a: fv(a), lambda a: fg(a)[0], self.old_fval, self.old_old_fval, self.derphi0,
+                                        _BFGS_C1, _BFGS_C2, _BFGS_AMAX, None, maxiter=10)
+        self.ls2 = _CoroutineCall(search)
+        self._ls2_advance()
+
+    def _ls2_advance(self):
+        kind, payload = self.ls2.next()
+        if kind == 'request':
+            self.phase, self.request = 'ls2', float(payload)
+            return
+        alpha_star, phi_star, _, derphi_star = payload
+        if alpha_star is None:
+            self.warnflag = 2                                      # precision loss: no step satisfies the Wolfe conditions
+            return self._finish()
+        if derphi_star is None:                                    # (the search ran out of iterations: its last evaluation was elsewhere)
+            self.alpha_k, self.new_fval = float(alpha_star), phi_star
+            self.phase, self.request = 'reeval', float(alpha_star)
+            return
+        self._step_taken(float(alpha_star), phi_star)
+
+    def _step_taken(self, alpha_k, new_fval):
+        """The state's trial point is x + alpha_k p and its trial gradient the gradient there."""
+        self.old_fval, self.old_old_fval = new_fval, self.old_fval
+        self.k += 1
+        self.gnorm = self.gmax_t
+        self.request = None
+        if self.gnorm <= self.gtol or alpha_k * self.pnorm <= 0.0:      # converged / xrtol = 0: SciPy stops before it updates H
+            self._after, self.pending = 'finish', (L.BFGS_MOVE, alpha_k)
+        elif not np.isfinite(self.old_fval):
+            self.warnflag = 2
+            self._after, self.pending = 'finish', (L.BFGS_MOVE, alpha_k)
+        else:
+            self._after, self.pending = 'iterate', (L.BFGS_UPDATE, alpha_k)
+        self.stepped = True
+
+    def _finish(self):
+        if self.warnflag == 2:
+            pass
+        elif self.k >= self.maxiter:
+            self.warnflag = 1
+        elif np.isnan(self.gnorm) or np.isnan(self.old_fval) or self.xnan:
+            self.warnflag = 3
+        self.phase, self.request, self.done = 'done', None, True
+
+
+class DeviceLockstepBFGS:
+    """``LockstepBFGS`` over a state object (``NumpyBFGSState`` / ``DeviceBFGSState``): B scalar-driven minimisations; every tick is one
+    ``state.eval`` for all the windows that asked and at most one ``state.accept`` for those whose line search ended.  ``callbacks[b]``
+    (or None) gets OptimizeResult(x, fun) per iteration; x crosses to the host before the end only for a callback whose
+    ``callback_needs_x[b]`` is true (the default), the others get x=None."""
+
+    def __init__(self, state, x0, maxiter, gtol, callbacks=None, active=None, wolfe2_fallback=True, want_hess_inv=True,
+                 callback_needs_x=None):
+        x0 = np.asarray(x0, dtype=np.float64)
+        self.B, self.n = x0.shape
+        self.state, self.x0 = state, x0
+        self.active = np.ones(self.B, bool) if active is None else np.asarray(active, bool)
+        maxiters = np.broadcast_to(np.asarray(maxiter), (self.B,))
+        self.callbacks = callbacks if callbacks is not None else [None] * self.B
+        self.needs_x = callback_needs_x if callback_needs_x is not None else [True] * self.B
+        self.windows = [(_ScalarWindowBFGS(maxiters[b], gtol, self.n, wolfe2_fallback) if self.active[b] else None) for b in range(self.B)]
+        self.want_hess_inv = want_hess_inv
+        self.n_batch_evals = 0
+        self.n_window_evals = 0
+        self.n_fetches = 0
+
+    def run(self):
+        """List of scipy OptimizeResult (None for inactive windows)."""
+        try:
+            if threadpool_limits is not None:
+                with threadpool_limits(limits=1, user_api='blas'):
+                    return self._run()
+            return self._run()
+        finally:
+            for w in self.windows:
+                if w is not None and w.ls2 is not None:
+                    w.ls2.abandon()
+
+    def _run(self):
+        B = self.B
+        self.state.begin(self.x0, self.active)
+        while True:
+            req = [(b, w) for b, w in enumerate(self.windows) if w is not None and w.request is not None]
+            if not req:
+                break
+            alpha, m = np.zeros(B), np.zeros(B, bool)
+            for b, w in req:
+                alpha[b], m[b] = w.request, True
+            self.n_batch_evals += 1; self.n_window_evals += len(req)
+            f, dphi, gmax = self.state.eval(alpha, m)
+            for b, w in req:
+                w.stepped = False
+                w.feed(f[b], dphi[b], gmax[b])
+            acc = [(b, w) for b, w in req if w.pending is not None]
+            if not acc:
+                continue
+            modes, alpha = np.zeros(B, np.uint8), np.zeros(B)
+            for b, w in acc:
+                modes[b], alpha[b] = w.pending
+            scal = self.state.accept(alpha, modes)
+            told = [(b, w) for b, w in acc if w.stepped and self.callbacks[b] is not None]
+            if told:
+                x = None
+                if any(self.needs_x[b] for b, _ in told):
+                    self.n_fetches += 1
+                    x = self.state.fetch(False)[0]
+                for b, w in told:
+                    self.callbacks[b](spo.OptimizeResult(x=(x[b].copy() if self.needs_x[b] else None), fun=w.old_fval))
+            for b, w in acc:
+                w.accepted(scal[b])
+        self.n_fetches += 1
+        x, g, H = self.state.fetch(self.want_hess_inv)
+        out = []
+        for b, w in enumerate(self.windows):
+            if w is None:
+                out.append(None)
+                continue
+            out.append(spo.OptimizeResult(fun=w.old_fval, jac=g[b].copy(), hess_inv=(H[b].copy() if H is not None else None), nfev=w.nfev,
+                                          njev=w.nfev, status=w.warnflag, success=(w.warnflag == 0), x=x[b].copy(), nit=w.k))
+        return out
+
 
 def _info(res):
     return ScipyMinimizeInfo(fun_val=float(res.fun), success=bool(res.success), status=int(res.status), iter_num=int(res.nit),
@@ -446,9 +796,19 @@ class BatchedMultipleLevelEINCMSolver:
     def __init__(self, n_windows, sensor_size, n_pyr_lvls, theta_opt_maxiters, loss_kwargs, theta_opt_solver_params,
                  handover_opt_maxiters=None, handover_opt_solver_params=None, handover_settings=None,
                  pyramid_downscale_method='bilinear', pyramid_upscale_method='repeat', pyramid_bases=None, device=0,
-                 theta_solver_callbacks=None, n_groups=1):
+                 theta_solver_callbacks=None, n_groups=1, bfgs_state='host'):
         """n_groups > 1: the windows are split over that many engine contexts (HIP streams) and the lockstep is pipelined - while the
-        host advances one group's line searches the other groups' evaluations run (LockstepBFGS, pipelined form)."""
+        host advances one group's line searches the other groups' evaluations run (LockstepBFGS, pipelined form).
+        bfgs_state: 'host' (default) keeps x, the gradient and the inverse Hessian of every window in numpy; 'device' keeps them in HBM
+        at the levels with more than 64 unknowns (8x8 and finer: DeviceLockstepBFGS on DeviceBFGSState), where only scalars cross PCIe
+        per evaluation; the inverse Hessian of those levels is not downloaded (ScipyMinimizeInfo.hess_inv is None; Engine.bfgs_fetch
+        hands it out).  'device' needs one context (n_groups=1) and the fp32 engine."""
+        check_bfgs_state(bfgs_state)
+        if bfgs_state == 'device' and int(n_groups) > 1:
+            raise ValueError("bfgs_state='device' runs on one engine context: n_groups must be 1 (a pipelined device form does not exist)")
+        if bfgs_state == 'device' and dict(loss_kwargs).get('precision', 'fp32') == 'fp64':
+            raise ValueError("bfgs_state='device' needs precision='fp32': the fp64 engine has no device-resident evaluation")
+        self.bfgs_state = bfgs_state
         hs = handover_settings
         if hs is None:
             hs = {'use_handover': False, 'solve_handover_for_levels': [], 'use_downscaled_finest_priors': False,
@@ -551,14 +911,23 @@ class BatchedMultipleLevelEINCMSolver:
         x = np.stack([np.asarray(s, dtype=np.float64).reshape(-1) for s in starts])
         active = np.ones(self.B, bool)
         states = [None] * self.B
+        on_device = self.bfgs_state == 'device' and x.shape[1] > _EXACT_UPDATE_MAX_N      # below: the host's bit-exact SciPy update
         for attempt in range(1 + extra):
             for b in range(self.B):
                 if active[b]:
                     self.callbacks[b].set_cur_pyr_lvl(k)
                     self.callbacks[b].reset_opt_iter()
-            drv = LockstepBFGS(fun_batch, x, self.theta_opt_maxiters[key], gtol, callbacks=[
-                (lambda r, cb=self.callbacks[b], sh=shape: cb(spo.OptimizeResult(x=np.asarray(r.x).reshape(sh), fun=r.fun)))
-                for b in range(self.B)], active=active, wolfe2_fallback=self.theta_opt_solver_params.get('wolfe2_fallback', True), **pipe)
+            cbs = [(lambda r, cb=self.callbacks[b], sh=shape: cb(spo.OptimizeResult(x=np.asarray(r.x).reshape(sh), fun=r.fun)))
+                   for b in range(self.B)]
+            wolfe2 = self.theta_opt_solver_params.get('wolfe2_fallback', True)
+            if on_device:      # a retry begins again from the last iterate with H = I, as a new LockstepBFGS does
+                # (an EmptyCallback counts iterations and never looks at x: no download for it)
+                plain = [type(self.callbacks[b]) is EmptyCallback for b in range(self.B)]
+                drv = DeviceLockstepBFGS(DeviceBFGSState(self.engine, shape, p), x, self.theta_opt_maxiters[key], gtol, callbacks=[
+                    (self.callbacks[b] if plain[b] else cbs[b]) for b in range(self.B)], callback_needs_x=[not q for q in plain],
+                    active=active, wolfe2_fallback=wolfe2, want_hess_inv=False)      # (H stays in HBM: ScipyMinimizeInfo.hess_inv is None)
+            else:
+                drv = LockstepBFGS(fun_batch, x, self.theta_opt_maxiters[key], gtol, callbacks=cbs, active=active, wolfe2_fallback=wolfe2, **pipe)
             res = drv.run()
             self.n_batch_evals += drv.n_batch_evals; self.n_window_evals += drv.n_window_evals
             for b in range(self.B):

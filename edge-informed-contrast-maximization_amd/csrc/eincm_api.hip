@@ -29,6 +29,7 @@
 #include "eincm_preprocess.hip.h"
 #include "eincm_gtflow.hip.h"
 #include "eincm_dsec.hip.h"
+#include "eincm_bfgs.hip.h"
 
 using namespace eincm;
 
@@ -272,6 +273,18 @@ struct eincm_ctx {
         unsigned* bad = nullptr;             // (B) a non-finite dL/dIWE or event term in this evaluation (gradient -> NaN)
         int P = 0;                           // image-pass workgroups per image
     } f64;
+
+    // BFGS state in HBM (eincm_bfgs.hip.h): allocated at the first eincm_bfgs_begin, grown on demand, nothing per call
+    struct {
+        bool begun = false;                  // eincm_bfgs_begin has run for the staged batch (set_windows clears it)
+        int n = 0, h = 0, w = 0, B = 0;
+        size_t cap_vec = 0, cap_H = 0;       // doubles the vectors / H hold
+        double* vec = nullptr;               // one block: X, G, P, Xt, Gt, S, Y, Hy, each (B, n) at stride cap_vec
+        double *X = nullptr, *G = nullptr, *P = nullptr, *Xt = nullptr, *Gt = nullptr, *S = nullptr, *Y = nullptr, *Hy = nullptr;
+        double* H = nullptr;                 // (B, n, n)
+        double* h_scal = nullptr;            // pinned (maxB, BFGS_NS): k_bfgs_scalars writes it
+        double* h_red = nullptr;             // pinned (maxB, 2): k_bfgs_reduce writes it
+    } bfgs;
 };
 
 namespace {
@@ -374,6 +387,7 @@ void free_all(eincm_ctx* c) {
     F(c->f64.acc); F(c->f64.iwe); F(c->f64.zero_iwe); F(c->f64.edges); F(c->f64.G); F(c->f64.sgn); F(c->f64.gacc); F(c->f64.gTh); F(c->f64.T);
     F(c->f64.grad); F(c->f64.partA); F(c->f64.partB); F(c->f64.partC); F(c->f64.scal); F(c->f64.gmax); F(c->f64.ishift); F(c->f64.bad);
     F(c->d_objc); F(c->d_oparts); c->oparts_cap = 0;
+    F(c->bfgs.vec); F(c->bfgs.H); c->bfgs.cap_vec = c->bfgs.cap_H = 0; c->bfgs.begun = false;
     for (DevBuf* b : {&c->e_u8, &c->e_g, &c->e_sq, &c->e_misc, &c->e_a, &c->e_b, &c->e_kern, &c->e_out}) { F(b->p); b->bytes = 0; }
     for (DevBuf* b : {&c->p_img[0], &c->p_img[1], &c->p_rows, &c->p_tab, &c->p_lut, &c->p_nlm}) { F(b->p); b->bytes = 0; }
     for (DevBuf* b : {&c->g_frames, &c->g_tab, &c->g_out}) { F(b->p); b->bytes = 0; }
@@ -382,7 +396,7 @@ void free_all(eincm_ctx* c) {
     c->rect_map_set = false;
     c->nlm_tw = 0;
     auto FH = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
-    FH(c->f64.h_scal); FH(c->h_ovals);
+    FH(c->f64.h_scal); FH(c->h_ovals); FH(c->bfgs.h_scal); FH(c->bfgs.h_red);
     FH(c->h_theta); FH(c->h_outs); c->h_grad = nullptr; FH(c->h_wc); FH(c->h_g11); FH(c->h_g2); FH(c->h_img); FH(c->h_tvparts);
     if (c->have_events) {
         for (int k = 0; k < eincm_ctx::EV_RING; ++k)
@@ -1675,6 +1689,7 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     if (N > c->maxN) return fail(c, EINCM_ERR_ARG, "total events %lld exceed capacity %lld", (long long)N, (long long)c->maxN);
     c->staged = false;
     c->Theta_valid = false;
+    c->bfgs.begun = false;           // the BFGS state belongs to the batch it was begun for
     // Async copies below read from / write into locals of this function; whatever path leaves it (an error return included), the
     // stream is drained first (safe before only because pageable copies happen to be host-synchronous).
     struct DrainOnExit { hipStream_t s; ~DrainOnExit() { (void)hipStreamSynchronize(s); } } drain_on_exit{c->stream};
@@ -3102,6 +3117,218 @@ int eincm_get_timings(eincm_ctx* c, eincm_timings* t) {
     const int rc = drain_event_ring(c, 0);
     if (rc) return rc;
     *t = c->last_t;
+    return EINCM_OK;
+}
+
+// ---- BFGS with its state in HBM (eincm_bfgs.hip.h) ----
+static int bfgs_ready(eincm_ctx* c, const char* who, bool need_begun) {
+    if (c->fp64)
+        return fail(c, EINCM_ERR_UNSUPPORTED, "%s is not supported in fp64 mode (EINCM_CF_FP64): the device-resident evaluation does not exist there", who);
+    if (!c->staged) return fail(c, EINCM_ERR_STATE, "%s called before eincm_set_windows", who);
+    if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
+    if (c->device_results) return fail(c, EINCM_ERR_STATE, "%s: eincm_set_device_results is on (the split finishing half owns the results)", who);
+    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
+    if (c->g.B > BFGS_MAX_B) return fail(c, EINCM_ERR_ARG, "%s: %d windows exceed EINCM_BFGS_MAX_WINDOWS = %d", who, c->g.B, BFGS_MAX_B);
+    if (need_begun && (!c->bfgs.begun || c->bfgs.B != c->g.B))
+        return fail(c, EINCM_ERR_STATE, "%s called before eincm_bfgs_begin (for the staged windows)", who);
+    return EINCM_OK;
+}
+
+static unsigned long long bfgs_mask(const eincm_ctx* c, const uint8_t* active) {
+    unsigned long long m = 0ull;
+    for (int b = 0; b < c->g.B; ++b) if (!active || active[b]) m |= 1ull << b;
+    return m;
+}
+
+static BfgsAlpha bfgs_alpha(const eincm_ctx* c, unsigned long long m, const double* alpha) {
+    BfgsAlpha al{};
+    for (int b = 0; b < c->g.B; ++b) if ((m >> b) & 1ull) al.a[b] = alpha[b];
+    return al;
+}
+
+static int bfgs_launch_reduce(eincm_ctx* c, unsigned long long m, const double* gsrc) {
+    auto& s = c->bfgs;
+    hipLaunchKernelGGL(k_bfgs_reduce, dim3((unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, m, gsrc, s.Gt, (const double*)s.P, s.h_red);
+    HIPCHK(c, hipGetLastError());
+    return EINCM_OK;
+}
+
+int eincm_bfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const uint8_t* active) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_begin", false)) return rc;
+    if (!x0_host || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_begin: bad argument");
+    const int64_t n64 = (int64_t)2 * h * w;
+    if (n64 > BFGS_MAX_N)
+        return fail(c, EINCM_ERR_ARG, "eincm_bfgs_begin: theta (%d,%d,2) has %lld unknowns, more than EINCM_BFGS_MAX_N = %d", h, w, (long long)n64, BFGS_MAX_N);
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& s = c->bfgs;
+    const int n = (int)n64, B = c->g.B;
+    if (!s.h_scal) {
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.h_scal), (size_t)c->maxB * BFGS_NS * sizeof(double), hipHostMallocDefault));
+        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.h_red), (size_t)c->maxB * 2 * sizeof(double), hipHostMallocDefault));
+        memset(s.h_scal, 0, (size_t)c->maxB * BFGS_NS * sizeof(double));
+        memset(s.h_red, 0, (size_t)c->maxB * 2 * sizeof(double));
+    }
+    const size_t need_vec = (size_t)B * n, need_H = need_vec * n;
+    const bool reshaped = n != s.n || B != s.B;
+    if (need_vec > s.cap_vec) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (s.vec) { (void)hipFree(s.vec); s.vec = nullptr; s.cap_vec = 0; }
+        HIPCHK(c, dalloc(&s.vec, 8 * need_vec));
+        s.cap_vec = need_vec;
+        double** v[8] = {&s.X, &s.G, &s.P, &s.Xt, &s.Gt, &s.S, &s.Y, &s.Hy};
+        for (int k = 0; k < 8; ++k) *v[k] = s.vec + (size_t)k * s.cap_vec;
+    }
+    if (need_H > s.cap_H) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (s.H) { (void)hipFree(s.H); s.H = nullptr; s.cap_H = 0; }
+        HIPCHK(c, dalloc(&s.H, need_H));
+        s.cap_H = need_H;
+    }
+    s.begun = false;
+    if (reshaped) {          // the rows of windows outside this call's mask must hold finite numbers in the new layout
+        HIPCHK(c, hipMemsetAsync(s.vec, 0, 8 * s.cap_vec * sizeof(double), c->stream));
+        HIPCHK(c, hipMemsetAsync(s.H, 0, s.cap_H * sizeof(double), c->stream));
+        memset(s.h_scal, 0, (size_t)c->maxB * BFGS_NS * sizeof(double));
+    }
+    s.n = n; s.h = h; s.w = w; s.B = B;
+    const unsigned long long m = bfgs_mask(c, active);
+    hipLaunchKernelGGL(k_bfgs_begin, dim3((unsigned)((n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)B), dim3(BFGS_NT), 0, c->stream, n, m, s.H, s.P, s.G);
+    HIPCHK(c, hipGetLastError());
+    for (int b = 0; b < B; ) {                        // x0 of the mask's windows, one copy per run of them
+        if (!((m >> b) & 1ull)) { ++b; continue; }
+        int e = b + 1;
+        while (e < B && ((m >> e) & 1ull)) ++e;
+        HIPCHK(c, hipMemcpyAsync(s.X + (size_t)b * n, x0_host + (size_t)b * n, (size_t)(e - b) * n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        for (int k = b; k < e; ++k) {                  // max|x0| bounds |theta| of the first evaluation
+            double xm = 0.0;
+            for (int i = 0; i < n; ++i) { const double a = std::fabs(x0_host[(size_t)k * n + i]); if (a > xm || a != a) xm = a; }
+            double* o = s.h_scal + (size_t)k * BFGS_NS;
+            for (int q = 0; q < BFGS_NS; ++q) o[q] = 0.0;
+            o[EINCM_BFGS_S_XMAX] = xm;
+        }
+        b = e;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s.begun = true;
+    return EINCM_OK;
+}
+
+int eincm_bfgs_trial(eincm_ctx* c, const double* alpha, const uint8_t* active) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_trial", true)) return rc;
+    if (!alpha) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_trial: null pointer argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& s = c->bfgs;
+    const unsigned long long m = bfgs_mask(c, active);
+    hipLaunchKernelGGL(k_bfgs_trial, dim3((unsigned)((s.n + BFGS_NT - 1) / BFGS_NT), (unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, m,
+                       bfgs_alpha(c, m, alpha), (const double*)s.X, (const double*)s.P, s.Xt);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EINCM_OK;
+}
+
+int eincm_bfgs_reduce(eincm_ctx* c, const uint8_t* active, double* dphi, double* gmax) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_reduce", true)) return rc;
+    if (!dphi || !gmax) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_reduce: null pointer argument");
+    HIPCHK(c, hipSetDevice(c->device));
+    const unsigned long long m = bfgs_mask(c, active);
+    if (const int rc = bfgs_launch_reduce(c, m, nullptr)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int b = 0; b < c->bfgs.B; ++b) if ((m >> b) & 1ull) { dphi[b] = c->bfgs.h_red[2 * b]; gmax[b] = c->bfgs.h_red[2 * b + 1]; }
+    return EINCM_OK;
+}
+
+int eincm_bfgs_eval(eincm_ctx* c, const eincm_params* p, const double* alpha, const uint8_t* active, double* value, double* dphi, double* gmax) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_eval", true)) return rc;
+    if (!p || !alpha || !value || !dphi || !gmax) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_eval: null pointer argument");
+    if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& s = c->bfgs;
+    const unsigned long long m = bfgs_mask(c, active);
+    double vmax = 0.0;                             // max|X| + |a| max|P| bounds |theta| at the trial point: selects the LDS window capacity
+    for (int b = 0; b < s.B; ++b) if ((m >> b) & 1ull) {
+        const double* o = s.h_scal + (size_t)b * BFGS_NS;
+        const double v = o[EINCM_BFGS_S_XMAX] + std::fabs(alpha[b]) * o[EINCM_BFGS_S_PMAX];
+        if (!(v <= vmax)) vmax = v;                // (a NaN ends up in vmax: unknown)
+    }
+    hipLaunchKernelGGL(k_bfgs_trial, dim3((unsigned)((s.n + BFGS_NT - 1) / BFGS_NT), (unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, m,
+                       bfgs_alpha(c, m, alpha), (const double*)s.X, (const double*)s.P, s.Xt);
+    HIPCHK(c, hipGetLastError());
+    // the masked evaluation with theta = Xt in HBM; its gradient stays in the engine's block, k_bfgs_reduce moves the mask's rows to Gt
+    struct Reset { eincm_ctx* c; ~Reset() { c->theta_dev_in = nullptr; c->grad_dev_out = nullptr; c->vmax_hint = -1.0; } } reset{c};
+    c->theta_dev_in = s.Xt; c->grad_dev_out = nullptr; c->vmax_hint = std::isfinite(vmax) ? vmax : -1.0;
+    std::vector<uint8_t> act((size_t)s.B);
+    for (int b = 0; b < s.B; ++b) act[b] = (uint8_t)((m >> b) & 1ull);
+    int rc = eval_begin(c, nullptr, s.h, s.w, p, true, act.data());
+    if (!rc) rc = eval_end_launch(c);
+    if (!rc) rc = bfgs_launch_reduce(c, m, c->d_grad);
+    if (rc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rc; }
+    rc = eval_end_collect(c, value, nullptr, nullptr);             // the one synchronisation
+    if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
+    for (int b = 0; b < s.B; ++b) if ((m >> b) & 1ull) { dphi[b] = s.h_red[2 * b]; gmax[b] = s.h_red[2 * b + 1]; }
+    return rc;
+}
+
+int eincm_bfgs_trial_ptrs(eincm_ctx* c, void** xt_dptr, void** gt_dptr, int64_t* n_doubles) {
+    if (!c || !xt_dptr || !gt_dptr || !n_doubles) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_trial_ptrs", true)) return rc;
+    *xt_dptr = c->bfgs.Xt; *gt_dptr = c->bfgs.Gt; *n_doubles = (int64_t)c->bfgs.B * c->bfgs.n;
+    return EINCM_OK;
+}
+
+int eincm_bfgs_state_ptrs(eincm_ctx* c, void** x_dptr, void** g_dptr, void** p_dptr, void** hess_inv_dptr, int* n_windows, int* n) {
+    if (!c || !x_dptr || !g_dptr || !p_dptr || !hess_inv_dptr || !n_windows || !n) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_state_ptrs", true)) return rc;
+    *x_dptr = c->bfgs.X; *g_dptr = c->bfgs.G; *p_dptr = c->bfgs.P; *hess_inv_dptr = c->bfgs.H; *n_windows = c->bfgs.B; *n = c->bfgs.n;
+    return EINCM_OK;
+}
+
+int eincm_bfgs_accept(eincm_ctx* c, const double* alpha, const uint8_t* accept_mode, double* scalars_out) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_accept", true)) return rc;
+    if (!alpha || !accept_mode || !scalars_out) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_accept: null pointer argument");
+    auto& s = c->bfgs;
+    unsigned long long act = 0ull, upd = 0ull, init = 0ull;
+    for (int b = 0; b < s.B; ++b) {
+        const int mode = accept_mode[b];
+        if (mode > EINCM_BFGS_INIT) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_accept: accept_mode[%d] = %d unknown", b, mode);
+        if (mode != EINCM_BFGS_SKIP) act |= 1ull << b;
+        if (mode == EINCM_BFGS_UPDATE) upd |= 1ull << b;
+        if (mode == EINCM_BFGS_INIT) init |= 1ull << b;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (act) {
+        const dim3 grid((unsigned)((s.n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)s.B);
+        if (upd) {
+            hipLaunchKernelGGL(k_bfgs_hy, grid, dim3(BFGS_NT), (size_t)s.n * sizeof(double), c->stream, s.n, upd, bfgs_alpha(c, upd, alpha),
+                               (const double*)s.H, (const double*)s.G, (const double*)s.Gt, (const double*)s.P, s.S, s.Y, s.Hy);
+            HIPCHK(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_bfgs_update, grid, dim3(BFGS_NT), (size_t)3 * s.n * sizeof(double), c->stream, s.n, act, upd, init, s.H,
+                           (const double*)s.S, (const double*)s.Y, (const double*)s.Hy, s.X, (const double*)s.Xt, s.G, (const double*)s.Gt, s.P);
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_bfgs_scalars, dim3((unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, act, (const double*)s.X, (const double*)s.G,
+                           (const double*)s.P, (const double*)s.S, (const double*)s.Y, (const double*)s.Hy, upd, s.h_scal);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    memcpy(scalars_out, s.h_scal, (size_t)s.B * BFGS_NS * sizeof(double));
+    return EINCM_OK;
+}
+
+int eincm_bfgs_fetch(eincm_ctx* c, double* x, double* g, double* hess_inv) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_bfgs_fetch", true)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& s = c->bfgs;
+    const size_t nv = (size_t)s.B * s.n * sizeof(double);
+    if (x) HIPCHK(c, hipMemcpyAsync(x, s.X, nv, hipMemcpyDeviceToHost, c->stream));
+    if (g) HIPCHK(c, hipMemcpyAsync(g, s.G, nv, hipMemcpyDeviceToHost, c->stream));
+    if (hess_inv) HIPCHK(c, hipMemcpyAsync(hess_inv, s.H, nv * s.n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return EINCM_OK;
 }
 

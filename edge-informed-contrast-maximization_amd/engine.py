@@ -596,16 +596,107 @@ class Engine:
         auxl = [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux] if want_aux else None
         return value, grad, auxl
 
+    # -- BFGS with its state in HBM: the host sees scalars, the vectors and the inverse Hessian stay on the GPU ----
+    def _bfgs_mask(self, active):
+        if active is None:
+            return None, None
+        act = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
+        if act.shape != (self.B,):
+            raise ValueError(f'active must be ({self.B},), got {act.shape}')
+        return act, act.ctypes.data
+
+    def _bfgs_alpha(self, alpha):
+        al = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64))
+        if al.shape != (self.B,):
+            raise ValueError(f'alpha must be ({self.B},), got {al.shape}')
+        return al
+
+    def bfgs_begin(self, x0, active=None):
+        """Start B minimisations at x0 (B,h,w,2): X = x0, H = I, for the windows of ``active`` (None = all)."""
+        x = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
+        if x.ndim != 4 or x.shape[0] != self.B or x.shape[3] != 2:
+            raise ValueError(f'x0 must be ({self.B},h,w,2), got {x.shape}')
+        act, p_act = self._bfgs_mask(active)
+        self._check(self._lib.eincm_bfgs_begin(self._ctx, x.ctypes.data, x.shape[1], x.shape[2], p_act))
+        self._bfgs_shape = x.shape
+        out = np.empty(self.B), np.empty(self.B), np.empty(self.B)
+        self._bfgs_out = out + tuple(o.ctypes.data for o in out)
+
+    def bfgs_eval(self, params, alpha, active=None, allow_nonfinite=True):
+        """One evaluation at X + alpha[b] P per window of ``active``: (value, phi' = grad . P, max|grad|), each (B,); the trial point
+        and its gradient stay in HBM.  Entries of the other windows are meaningless."""
+        al = self._bfgs_alpha(alpha)
+        act, p_act = self._bfgs_mask(active)
+        v, d, g, p_v, p_d, p_g = self._bfgs_out
+        rc = self._lib.eincm_bfgs_eval(self._ctx, C.byref(params), al.ctypes.data, p_act, p_v, p_d, p_g)
+        self._check(rc, allow_nonfinite)
+        return v.copy(), d.copy(), g.copy()
+
+    def bfgs_trial(self, alpha, active=None):
+        """Xt = X + alpha[b] P alone (see bfgs_trial_tensors)."""
+        al = self._bfgs_alpha(alpha)
+        act, p_act = self._bfgs_mask(active)
+        self._check(self._lib.eincm_bfgs_trial(self._ctx, al.ctypes.data, p_act))
+
+    def bfgs_reduce(self, active=None):
+        """(phi', max|grad|) of the gradient the caller wrote into the trial gradient's view (torch work on it is synchronised first)."""
+        import torch
+        torch.cuda.current_stream(torch.device('cuda', torch.cuda.current_device())).synchronize()
+        act, p_act = self._bfgs_mask(active)
+        _, d, g, _, p_d, p_g = self._bfgs_out
+        self._check(self._lib.eincm_bfgs_reduce(self._ctx, p_act, p_d, p_g))
+        return d.copy(), g.copy()
+
+    def bfgs_trial_tensors(self):
+        """torch views (B, n) of the trial point Xt and its gradient Gt in HBM: any objective's gradient can be supplied on the device
+        between bfgs_trial and bfgs_reduce."""
+        xt, gt, n = C.c_void_p(), C.c_void_p(), C.c_int64()
+        self._check(self._lib.eincm_bfgs_trial_ptrs(self._ctx, C.byref(xt), C.byref(gt), C.byref(n)))
+        shape = (self.B, int(n.value) // self.B)
+        return self._view_at(xt.value, '<f8', shape), self._view_at(gt.value, '<f8', shape)
+
+    def bfgs_state_tensors(self):
+        """torch views of X, G, P (B, n) and the inverse Hessian H (B, n, n) in HBM."""
+        x, g, p, h, nb, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
+        self._check(self._lib.eincm_bfgs_state_ptrs(self._ctx, C.byref(x), C.byref(g), C.byref(p), C.byref(h), C.byref(nb), C.byref(n)))
+        B, n = int(nb.value), int(n.value)
+        return (self._view_at(x.value, '<f8', (B, n)), self._view_at(g.value, '<f8', (B, n)), self._view_at(p.value, '<f8', (B, n)),
+                self._view_at(h.value, '<f8', (B, n, n)))
+
+    def bfgs_accept(self, alpha, modes):
+        """End of a line search per window: modes[b] in _lib.BFGS_SKIP / UPDATE / MOVE / INIT with the step alpha[b] last evaluated.
+        Returns the scalars (B, _lib.BFGS_NS) of the new iterates (rows of skipped windows: their last values)."""
+        al = self._bfgs_alpha(alpha)
+        md = np.ascontiguousarray(np.asarray(modes).astype(np.uint8))
+        if md.shape != (self.B,):
+            raise ValueError(f'modes must be ({self.B},), got {md.shape}')
+        out = np.empty((self.B, L.BFGS_NS))
+        self._check(self._lib.eincm_bfgs_accept(self._ctx, al.ctypes.data, md.ctypes.data, out.ctypes.data))
+        return out
+
+    def bfgs_fetch(self, want_hess_inv=False):
+        """(x (B,h,w,2), grad (B,h,w,2), inverse Hessian (B,n,n) | None) on the host."""
+        shape = self._bfgs_shape
+        n = int(np.prod(shape[1:]))
+        x, g = np.empty(shape), np.empty(shape)
+        H = np.empty((self.B, n, n)) if want_hess_inv else None
+        self._check(self._lib.eincm_bfgs_fetch(self._ctx, x.ctypes.data, g.ctypes.data, H.ctypes.data if want_hess_inv else None))
+        return x, g, H
+
     def finish_constants(self):
         self._check(self._lib.eincm_finish_constants(self._ctx))
 
     def _device_view(self, getter, typestr, itemsize, shape):
-        import torch
         ptr, n = C.c_void_p(), C.c_int64()
         self._check(getter(self._ctx, C.byref(ptr), C.byref(n)))
+        return self._view_at(ptr.value, typestr, shape)
+
+    @staticmethod
+    def _view_at(address, typestr, shape):
+        import torch
 
         class _View:            # the CUDA array interface: a zero-copy torch tensor over the engine's HBM buffer
-            __cuda_array_interface__ = {'shape': shape, 'typestr': typestr, 'data': (int(ptr.value), False), 'version': 2,
+            __cuda_array_interface__ = {'shape': shape, 'typestr': typestr, 'data': (int(address), False), 'version': 2,
                                         'strides': None}
         return torch.as_tensor(_View(), device=torch.device('cuda', torch.cuda.current_device()))
 

@@ -50,6 +50,9 @@ def main():
                     help='correlation objective of the loss (DESIGN.md section 11); the reference wires mse')
     ap.add_argument('--tile-size', type=int, nargs=2, default=(32, 42), metavar=('TH', 'TW'),
                     help='tile of the adaptive kinds (contrast_objectives.py:56-59)')
+    ap.add_argument('--bfgs-state', choices=('host', 'device'), default='host',
+                    help="with --sequences > 1: 'device' keeps x, the gradient and the inverse Hessian of the 8x8 and 16x16 levels in HBM "
+                         '(DESIGN.md section 17; one engine context, fp32)')
     ap.add_argument('overrides', nargs='*')
     a = ap.parse_args()
     cfg = config.load_config(a.config_dir, 'main', a.overrides) if a.config_dir else config._wrap(DEFAULTS)
@@ -113,7 +116,8 @@ def stage_window(cfg, seed, i, refs, flow_mag, H, W):
 
 def run_batched(a, cfg, H, W, n_lvls):
     """B sequences advance together: window i of every sequence is solved in one lockstep pyramid solve, each sequence handing over
-    from its own previous window (batch_solver.BatchedMultipleLevelEINCMSolver; two engine contexts, pipelined)."""
+    from its own previous window (batch_solver.BatchedMultipleLevelEINCMSolver; two engine contexts, pipelined - or, with
+    --bfgs-state device, one context whose BFGS state stays in HBM at the fine levels)."""
     from eincm_amd import batch_solver as bsol
     B, sp = a.sequences, cfg.solver_params
     loss = dict(alpha=cfg.alpha, beta=cfg.beta, gamma=cfg.gamma, delta=cfg.delta, scale_to_sensor_size_method=cfg.scale_theta_to_sensor_size_method,
@@ -125,7 +129,7 @@ def run_batched(a, cfg, H, W, n_lvls):
         handover_opt_maxiters=sol.growing_maxiters(n_lvls, sp.handover_opt.miniter, sp.handover_opt.maxiter, cfg.maxiters_grow_order, cfg.use_growing_maxiters),
         handover_opt_solver_params=dict(sp.handover_opt), handover_settings=dict(cfg.handover_settings),
         pyramid_downscale_method=cfg.pyramid_downscale_method, pyramid_upscale_method=cfg.pyramid_upscale_method,
-        pyramid_bases=list(cfg.pyramid_bases), n_groups=min(2, B))
+        pyramid_bases=list(cfg.pyramid_bases), n_groups=1 if a.bfgs_state == 'device' else min(2, B), bfgs_state=a.bfgs_state)
     print(f'{B} sequences side by side, sensor {H}x{W}, {cfg.des_n_events} events/window, R={a.refs}')
     scores = []
     for i in range(a.windows):

@@ -27,7 +27,7 @@ extern "C" {
                                 * 4: eincm_loss_grad_masked, eincm_set_device_results / eincm_finish_launch / eincm_grad_device_ptr / eincm_finish_collect, eincm_get_host_profile;
                                * 5: eincm_get_warped_events, eincm_loss_grad_device, eincm_loss_grad_masked_async, eincm_set_timing_period;
                                * 6: eincm_get_launch_policy; added since without a new version: eincm_rectify_events, eincm_remap_cubic, eincm_flow_decode,
-                               *    eincm_flow_encode (the DSEC data path) */
+                               *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -464,6 +464,58 @@ int eincm_flow_decode(eincm_ctx* ctx, const uint16_t* flow16, int n, double* flo
  * Channel 2: 0, or valid[n][H][W] != 0 where valid is not NULL.  *n_bad: pixels with a value that is not finite or codes outside
  * [0, 65536) (stored as 0); if any, EINCM_ERR_ARG.  1 <= n <= 65535. */
 int eincm_flow_encode(eincm_ctx* ctx, const double* theta, int n, int h, int w, const uint8_t* valid, uint16_t* out, int64_t* n_bad);
+
+/* ---- BFGS with its state in HBM --------------------------------------------------------------------------
+ * B = the staged windows (at most EINCM_BFGS_MAX_WINDOWS), each an independent BFGS minimisation (SciPy's _minimize_bfgs) over
+ * n = 2 h w <= EINCM_BFGS_MAX_N unknowns.  The point X, its gradient G, the direction P, the trial point Xt, its gradient Gt (B, n) and
+ * the inverse Hessian H (B, n, n) live in the context's device memory, allocated at the first eincm_bfgs_begin and grown on demand.
+ * The host keeps the line search, which needs phi(a) = f(X + a P) and phi'(a) = Gt . P only, and sees scalars.  Every sum is an
+ * ordered float64 sum in a fixed association: the same bits on every call and in every context.  Masks are (n_windows) bytes, NULL =
+ * every window; the state of a window outside the mask is not touched.  All calls return with the context's stream drained.
+ * Refusals: EINCM_ERR_STATE before eincm_set_windows, before eincm_bfgs_begin (or after a later eincm_set_windows), while an
+ * asynchronous evaluation is in flight, with eincm_set_device_results on; EINCM_ERR_ARG for n above the maximum, more windows than
+ * EINCM_BFGS_MAX_WINDOWS, a null pointer, an unknown accept mode; EINCM_ERR_UNSUPPORTED in an EINCM_CF_FP64 context (the device-resident
+ * evaluation does not exist there). */
+#define EINCM_BFGS_MAX_N 1024
+#define EINCM_BFGS_MAX_WINDOWS 64
+/* eincm_bfgs_accept: what happens to window b */
+#define EINCM_BFGS_SKIP   0   /* nothing */
+#define EINCM_BFGS_UPDATE 1   /* s = a P, y = Gt - G, r = 1 / y.s (1000 where y.s == 0), w = (c / 2) s - r H y with c = r (1 + r y.Hy);
+                                 H += s w^T + w s^T (bit-symmetric), X <- Xt, G <- Gt, P = -H G */
+#define EINCM_BFGS_MOVE   2   /* X <- Xt, G <- Gt only: the step that ends a minimisation (SciPy tests the new gradient before it updates H) */
+#define EINCM_BFGS_INIT   3   /* X <- Xt, G <- Gt, P = -G: after the first evaluation (H = I since eincm_bfgs_begin) */
+/* scalars of a window after eincm_bfgs_accept, EINCM_BFGS_NS doubles */
+#define EINCM_BFGS_S_DPHI0  0   /* G . P: phi'(0) of the next line search */
+#define EINCM_BFGS_S_GMAX   1   /* max |G| */
+#define EINCM_BFGS_S_PNORM  2   /* |P|_2 */
+#define EINCM_BFGS_S_XMAX   3   /* max |X|; with the next one a bound of |theta| at any step: max|X| + |a| max|P| */
+#define EINCM_BFGS_S_PMAX   4   /* max |P| */
+#define EINCM_BFGS_S_GNORM  5   /* |G|_2 (SciPy's first step guess: old_old_fval = f0 + |g0|_2 / 2) */
+#define EINCM_BFGS_S_YS     6   /* y . s and y . H y of an EINCM_BFGS_UPDATE (0 otherwise) */
+#define EINCM_BFGS_S_YHY    7
+#define EINCM_BFGS_NS 8
+/* Start minimisations over theta grids (h, w, 2) at x0_host (n_windows, h, w, 2) for the windows of `active`: X = x0, H = I, P = G = 0. */
+int eincm_bfgs_begin(eincm_ctx* ctx, const double* x0_host, int h, int w, const uint8_t* active);
+/* One function evaluation per window of `active`, on the context's stream with one synchronisation: Xt = X + alpha[b] P, the masked loss
+ * and gradient with theta = Xt and the gradient into Gt (both in HBM), dphi[b] = Gt . P and gmax[b] = max |Gt|.  alpha, value, dphi,
+ * gmax: (n_windows) on the host; entries outside the mask are not written, except value (NaN, as eincm_loss_grad_masked).
+ * EINCM_ERR_NONFINITE as eincm_loss_grad_device (the outputs are written). */
+int eincm_bfgs_eval(eincm_ctx* ctx, const eincm_params* p, const double* alpha, const uint8_t* active, double* value, double* dphi,
+                    double* gmax);
+/* The two steps around the engine on their own, for any objective whose gradient the caller computes on the device: eincm_bfgs_trial
+ * forms Xt; the caller writes the gradient at Xt into Gt (eincm_bfgs_trial_ptrs: n_doubles = n_windows * n each; the writes must be
+ * complete when eincm_bfgs_reduce is called); eincm_bfgs_reduce returns dphi and gmax as eincm_bfgs_eval does. */
+int eincm_bfgs_trial(eincm_ctx* ctx, const double* alpha, const uint8_t* active);
+int eincm_bfgs_reduce(eincm_ctx* ctx, const uint8_t* active, double* dphi, double* gmax);
+int eincm_bfgs_trial_ptrs(eincm_ctx* ctx, void** xt_dptr, void** gt_dptr, int64_t* n_doubles);
+/* Device pointers of X, G, P (n_windows * n doubles each) and H (n_windows * n * n), and the two sizes: the whole state as arrays
+ * (inspection, tests, a caller that seeds H). */
+int eincm_bfgs_state_ptrs(eincm_ctx* ctx, void** x_dptr, void** g_dptr, void** p_dptr, void** hess_inv_dptr, int* n_windows, int* n);
+/* End of a line search: accept_mode[b] (EINCM_BFGS_*) with the step alpha[b] whose evaluation was the window's last one.
+ * scalars_out (n_windows, EINCM_BFGS_NS) on the host: the rows of the windows that took part are new, the others keep their last values. */
+int eincm_bfgs_accept(eincm_ctx* ctx, const double* alpha, const uint8_t* accept_mode, double* scalars_out);
+/* X and G (n_windows, n) and, unless NULL, H (n_windows, n, n) to the host; x or g may be NULL. */
+int eincm_bfgs_fetch(eincm_ctx* ctx, double* x, double* g, double* hess_inv);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,74 @@
+"""The bench's c4_solve workload (8 x [260x346, 1e6 events, R = 5], pyramid 1..16, BFGS budget 40/28/19/11/8 + 1 retry at levels 0 and
+1, n_groups = 1) with the BFGS state on the host or in HBM: whole-solve seconds and, per pyramid level, the seconds per engine call
+(level wall time / lockstep ticks: the evaluation plus the solver's bookkeeping around it).  Whole-solve times swing with which line
+searches fail, so the per-call time at levels 1 and 0 is the figure to compare.
+
+    python3 tools/dev_device_bfgs_timing.py --state host|device [--runs 5] [--root CHECKOUT] [--out FILE.json]
+
+--root: import the package from another checkout (e.g. the parent commit, built there; it needs --state host: the keyword is not
+passed then).  Each invocation is one process: one warm-up solve, then --runs timed ones, each on a fresh solver with staging outside
+the timer (a solve ends in a stream synchronise).  Prints one JSON line."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--state', choices=('host', 'device'), default='device')
+ap.add_argument('--runs', type=int, default=5)
+ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument('--out', default=None)
+ap.add_argument('--events', type=int, default=1_000_000)
+a = ap.parse_args()
+sys.path.insert(0, os.path.abspath(a.root))
+PKG = 'edge-informed-contrast-maximization_amd'
+synth, sol, bsol = (importlib.import_module(f'{PKG}.{m}') for m in ('synth', 'solver', 'batch_solver'))
+
+H, W, R, B, n_lvls = 260, 346, 5, 8, 5
+wins = [synth.make_window(b, (H, W), a.events, R, flow='constant', flow_mag=20.0) for b in range(B)]
+args = [(w['xs'], w['ys'], w['ts'], w['edges'], w['edge_ts']) for w in wins]
+loss = dict(alpha=20.0, beta=35.0, gamma=0.0, delta=0.0, scale_to_sensor_size_method='bilinear')
+maxit = sol.growing_maxiters(n_lvls, 40 / 5, 40)
+sp = {'method': 'BFGS', 'options': {'gtol': 1e-7}, 'n_extra_attempts': {'pyr_lvl_0': 1, 'pyr_lvl_1': 1}}
+kw = {'bfgs_state': 'device'} if a.state == 'device' else {}
+
+
+def one_solve():
+    bs = bsol.BatchedMultipleLevelEINCMSolver(B, (H, W), n_lvls, maxit, loss, sp, pyramid_bases=[2] * (n_lvls - 1), **kw)
+    bs.set_datasamples(args)
+    per_level = {}
+    inner = bs._solve_level
+
+    def timed_level(k, starts):
+        c0, t0 = bs.n_batch_evals, time.perf_counter()
+        out = inner(k, starts)
+        per_level[k] = (time.perf_counter() - t0, bs.n_batch_evals - c0)
+        return out
+    bs._solve_level = timed_level
+    t0 = time.perf_counter()
+    out = bs.solve()
+    t = time.perf_counter() - t0
+    bs.close()
+    fun0 = [float(o['theta_opt_state_pyr']['pyr_lvl_0'].fun_val) for o in out]
+    return t, per_level, fun0, bs.n_batch_evals
+
+
+one_solve()                                        # warm-up: code objects, every theta shape
+runs = [one_solve() for _ in range(a.runs)]
+res = {'state': a.state, 'root': os.path.abspath(a.root), 'runs': a.runs,
+       'solve_s': [r[0] for r in runs], 'engine_calls': runs[0][3], 'level0_fun': runs[0][2],
+       'levels': {str(k): {'seconds': [r[1][k][0] for r in runs], 'engine_calls': runs[0][1][k][1],
+                           'us_per_call': [1e6 * r[1][k][0] / max(r[1][k][1], 1) for r in runs]} for k in sorted(runs[0][1])}}
+for k, v in res['levels'].items():
+    v['us_per_call_median'], v['us_per_call_min'], v['us_per_call_max'] = (float(f(v['us_per_call'])) for f in (np.median, np.min, np.max))
+res['solve_s_median'], res['solve_s_min'], res['solve_s_max'] = (float(f(res['solve_s'])) for f in (np.median, np.min, np.max))
+line = json.dumps(res)
+print(line)
+if a.out:
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)) or '.', exist_ok=True)
+    with open(a.out, 'w') as f:
+        f.write(line + '\n')
