@@ -90,6 +90,41 @@ struct EvalPlan {
     bool zero_copy_out = false;         // k_final writes the results straight into pinned host memory
 };
 
+// Every decision of one staging, taken once by plan_staging before its first HIP call; the phases of stage_windows only read it, and
+// the context keeps the one of the staged batch (plan_eval, eincm_get_launch_policy).
+struct StagePlan {
+    Geom g{};                           // the batch's geometry as staged (an evaluation sets the mask, capacities and pitch of the context's copy)
+    int64_t N = 0;                      // events of the batch
+    int seg = 0, seg_s = 0, seg_2 = 0;  // events per segment of the gather's, the splat's and the 2-DoF gather's list
+    bool splat_short = false;           // the splat gets its short list (8192) beside a longer one
+    int pitch = 0;                      // regime of the bank-aligned LDS pitch (win_pitch): 0 never, 1 k_splat where it costs no capacity class, 2 the 2-DoF gather too; plan_eval decides per evaluation
+    bool sort_segments = true;          // k_segsort deals the gather's copy of the events (EINCM_NO_SEGSORT: a plain copy)
+    bool spread = true;                 // k_spread re-deals the splat's copy (EINCM_NO_SPREAD: time order)
+    bool host_binning = false;          // the host sorts the events by (window, tile), not the kernels of eincm_binning.hip.h
+    bool defer_constants = false;       // EINCM_SW_DEFER_CONSTANTS: the caller sums the shards' IUEs before the window constants are formed
+    bool wide = false;                  // a window has a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel)
+};
+
+constexpr int SEG_SHORT = 8192;         // events per segment of the splat's short list
+constexpr int MIN_SEG = 64;             // the shortest segments EINCM_SEG / EINCM_SEG_SPLAT / EINCM_SEG_2DOF may ask for: what the lists' capacity allows for
+
+// The caller's arrays of one staging: one pointer per window (nothing is concatenated on the host)
+struct StageArgs {
+    int B, R; const int64_t* n_events;
+    const int16_t* const* xs; const int16_t* const* ys; const double* const* ts; const double* const* edges; const double* edge_ts;
+    uint32_t flags;
+};
+
+// All host memory an asynchronous copy of a staging reads or writes.  stage_windows constructs it before the guard that drains the
+// stream, so every way out of a staging drains first and frees afterwards.
+struct StageScratch {
+    std::vector<unsigned> cntmax; std::vector<double> dtmax;       // (B) most events on one source pixel, max |t - tau|
+    bool edge_ts_uploaded = false;
+    std::vector<BinBlock> blks; std::vector<int32_t> win_blk; int32_t misc[4]; std::vector<double> mom;   // device binning
+    std::vector<uint32_t> sxy; std::vector<double> st; std::vector<float> ef;                             // host binning
+    std::vector<int> ishift;                                                                              // float64 mode
+};
+
 }  // namespace
 
 struct eincm_ctx {
@@ -104,8 +139,8 @@ struct eincm_ctx {
 
     // staged batch
     bool staged = false;
+    StagePlan stage;               // the plan the staged batch was staged from (plan_staging)
     Geom g{};
-    int64_t n_events = 0;
     std::vector<int64_t> win_events;
 
     // device buffers
@@ -121,8 +156,6 @@ struct eincm_ctx {
     // serves it, and it wants shorter segments than the theta-grid gather does: round-2 tuning)
     SegList gather_2;
     bool policy_evaluated = false; // an evaluation has chosen capacities since the last staging (eincm_get_launch_policy)
-    bool wide = false;             // a window of the staged batch has a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel)
-    int pitch_policy = 0;          // the staged batch is in the regime where the bank-aligned LDS pitch pays (set_windows_impl); eval_begin decides per evaluation
     int wincap = WIN_CAP_DEFAULT;
     bool wincap_fixed = false;     // EINCM_WINCAP pins the capacity; otherwise it is chosen per evaluation from max|theta|
     // device-side staging (eincm_binning.hip.h)
@@ -911,8 +944,8 @@ EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, c
     // LDS window capacity for this evaluation: the host knows theta, hence the largest displacement a segment can see.
     // Small windows give 8 workgroups per CU; windows too small for the flow push taps onto the slow direct-to-HBM path.
     P.wincap = g.wincap; P.winmaxw = g.winmaxw; P.wincap_a = g.wincap_a; P.winmaxw_a = g.winmaxw_a;
-    P.pitch_aligned = c->pitch_policy != 0 ? 1 : 0;
-    P.win_2 = WinFit{c->wincap, win_maxw(c->wincap), c->pitch_policy >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
+    P.pitch_aligned = c->stage.pitch != 0 ? 1 : 0;
+    P.win_2 = WinFit{c->wincap, win_maxw(c->wincap), c->stage.pitch >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
     if (!c->wincap_fixed) {
         double vmax = 0.0;
         const size_t stride = nall > 8192 ? nall / 8192 : 1;            // dense theta: sample (any capacity is correct; 65536 samples cost 90 us)
@@ -927,7 +960,7 @@ EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, c
         // The theta-grid splat (window + 16 KiB Theta tile) pays for capacity with workgroups per CU (6 / 5 / 4 / 3), so it takes what it needs.
         // Each list's windows are sized for its time span: what all but 3 % of the events' segments stay within (build_list; the mean
         // tile would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
-        const int floor_s = two_dof ? 2 : 0, pitch_s = c->pitch_policy != 0 ? 1 : 0;
+        const int floor_s = two_dof ? 2 : 0, pitch_s = c->stage.pitch != 0 ? 1 : 0;
         WinFit s = fit_window(vmax, c->splat.tspan, margin, floor_s, pitch_s);
         // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
         // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
@@ -940,7 +973,7 @@ EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, c
         P.wincap_a = a.cap; P.winmaxw_a = a.maxw;
         // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
         // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
-        P.win_2 = fit_window(vmax, c->gather_2.tspan, margin, 2, c->pitch_policy >= 2 ? 1 : 0);
+        P.win_2 = fit_window(vmax, c->gather_2.tspan, margin, 2, c->stage.pitch >= 2 ? 1 : 0);
     }
 
     // 2-DoF theta with nothing but the contrast and correlation terms (every level above 0 of the reference's pyramid at its first
@@ -1183,7 +1216,7 @@ int eval_end_launch(eincm_ctx* c) {
                     // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
                     auto go = [&](auto kernel) {
                         launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(NT), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, c->d_tmm,
-                                     c->d_edge_ts, c->d_G, c->d_gTheta, g11, c->d_wc, c->d_gmax, c->wide ? 1 : 0, use_arg, c->pend.theta_dev,
+                                     c->d_edge_ts, c->d_G, c->d_gTheta, g11, c->d_wc, c->d_gmax, c->stage.wide ? 1 : 0, use_arg, c->pend.theta_dev,
                                      c->pend.targ);
                     };
                     if (two_dof) c->splat_rad == 0 ? go(k_gather_r<THETA_CONST, 0>) : c->splat_rad == 2 ? go(k_gather_r<THETA_CONST, 2>) : go(k_gather_r<THETA_CONST, 3>);
@@ -1197,8 +1230,8 @@ int eval_end_launch(eincm_ctx* c) {
                                      (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap);
                     };
                     if (two_dof)      go(k_gather<THETA_CONST, 0, NT, 0>, NT);
-                    else if (P.all_r) c->wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1>, NT_TILE);
-                    else if (c->wide) P.proj ? go(k_gather<THETA_TILE, 1, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 1, NT_TILE, 0>, NT_TILE);
+                    else if (P.all_r) c->stage.wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1>, NT_TILE);
+                    else if (c->stage.wide) P.proj ? go(k_gather<THETA_TILE, 1, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 1, NT_TILE, 0>, NT_TILE);
                     else              P.proj ? go(k_gather<THETA_TILE, 0, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 0>, NT_TILE);
                 }
             }
@@ -1207,7 +1240,7 @@ int eval_end_launch(eincm_ctx* c) {
         if (P.nsrc > 0) {
             StageTimer t(c, EINCM_STAGE_PROJECT, true);
             launch_timed(c, EINCM_STAGE_PROJECT, k_project, dim3(g.ntiles, g.B, P.nsrc), dim3(NT), 0, g, P.h, P.w,
-                               (int)c->coarse_cap, P.events_projected ? 1 : 0, c->wide ? 1 : 0, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_gTheta, c->d_tvg,
+                               (int)c->coarse_cap, P.events_projected ? 1 : 0, c->stage.wide ? 1 : 0, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_gTheta, c->d_tvg,
                                c->d_wc, c->d_gmax, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap);
         }
     }
@@ -1218,7 +1251,7 @@ int eval_end_launch(eincm_ctx* c) {
                            c->d_g11, c->gather_2.d_win_item0, c->gather_2.n, c->d_gmax,
                            P.zero_copy_out ? c->h_outs : c->d_outs, P.zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
         if (want_grad && identity) {
-            hipLaunchKernelGGL(k_final_dense, dim3(256, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, c->wide ? 1 : 0, c->d_gTheta,
+            hipLaunchKernelGGL(k_final_dense, dim3(256, g.B), dim3(NT), 0, c->stream, g, ep.use_tv_grad, c->stage.wide ? 1 : 0, c->d_gTheta,
                                c->d_tvg, c->d_wc, c->d_gmax, c->d_outs, c->d_grad);
         }
     }
@@ -1394,8 +1427,9 @@ eincm_params zero_pass_params() {
     return p;
 }
 
-// After the theta = 0 pass has been finished (eval_end): fill the window constants from its outputs.
-int store_constants(eincm_ctx* c) {
+// After the theta = 0 pass has been finished (rc_pass: what its eval_end returned): fill the window constants from its outputs.
+int store_constants(eincm_ctx* c, int rc_pass) {
+    if (rc_pass != EINCM_OK && rc_pass != EINCM_ERR_NONFINITE) return rc_pass;
     const Geom& g = c->g;
     const size_t img = (size_t)g.H * g.W;
     for (int b = 0; b < g.B; ++b) {
@@ -1417,7 +1451,37 @@ int store_constants(eincm_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->have_eval = false;
     c->constants_pending = false;
+    c->err.clear();
     return EINCM_OK;
+}
+
+// What an evaluation entry point asks of the context first: a staged batch, with its window constants unless the call forms them.
+int eval_ready(eincm_ctx* c, const char* who, bool need_constants = true) {
+    if (!c->staged) return fail(c, EINCM_ERR_STATE, "%s called before eincm_set_windows", who);
+    if (need_constants && c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
+    return EINCM_OK;
+}
+
+// c0, zc[r], d0 are 1 while the theta = 0 pass runs, so that it is well defined; store_constants overwrites them.
+int preset_constants(eincm_ctx* c) {
+    for (int b = 0; b < c->g.B; ++b) {
+        WinConst& wc = c->h_wc[b];
+        wc.c0_gradmag = 1.0; wc.c0_var = 1.0; wc.d0 = 1.0;
+        for (int r = 0; r < c->g.R; ++r) wc.zc[r] = 1.0;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_wc, c->h_wc, (size_t)c->g.B * sizeof(WinConst), hipMemcpyHostToDevice, c->stream));
+    return EINCM_OK;
+}
+
+// The zero-warp constants of the staged windows: one forward pass at theta = 0 (then IWE_r == IUE for every r).
+int window_constants(eincm_ctx* c) {
+    if (const int rc = preset_constants(c)) return rc;
+    const std::vector<double> zero((size_t)c->g.B * 2, 0.0);
+    std::vector<double> val((size_t)c->g.B);
+    const eincm_params p = zero_pass_params();
+    const int rc = evaluate(c, zero.data(), 1, 1, &p, val.data(), nullptr, nullptr, true);
+    if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) c->staged = false;
+    return store_constants(c, rc);
 }
 
 }  // namespace
@@ -1471,9 +1535,6 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     c->fp64 = (flags & EINCM_CF_FP64) != 0;
     c->device = device; c->H = H; c->W = W; c->maxR = max_refs; c->maxB = max_windows; c->maxN = max_events_total;
     c->cflags = flags;
-    if (const char* s = getenv("EINCM_SEG")) { int v = atoi(s); if (v >= 64 && v <= MAX_SEG) c->seg = v; }
-    if (const char* s = getenv("EINCM_SEG_SPLAT")) { int v = atoi(s); if (v >= 64 && v <= MAX_CHUNK) c->seg_s = v; }   // k_splat's u32 sums bound a segment
-    if (const char* s = getenv("EINCM_WINCAP")) { int v = atoi(s); if (v >= 1024 && v <= 6912) { c->wincap = (v / 4) * 4; c->wincap_fixed = true; } }
     auto bail = [&](const char* what, hipError_t err) -> eincm_ctx* {
         fail(nullptr, EINCM_ERR_HIP, "eincm_create: %s failed: %s", what, hipGetErrorString(err));
         free_all(c);
@@ -1485,13 +1546,17 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const int tilesX = (W + TS - 1) / TS, tilesY = (H + TS - 1) / TS, ntiles = tilesX * tilesY;
     const size_t B = max_windows, R = max_refs, img = (size_t)H * W;
-    c->max_items = (int64_t)B * ntiles + max_events_total / 256 + 1;   // segments are never shorter than 256 events unless a tile is
+    // the switches a context reads when it is created, all of them (a staging reads its own in plan_staging)
+    if (const char* s = getenv("EINCM_SEG")) { int v = atoi(s); if (v >= MIN_SEG && v <= MAX_SEG) c->seg = v; }
+    if (const char* s = getenv("EINCM_SEG_SPLAT")) { int v = atoi(s); if (v >= MIN_SEG && v <= MAX_CHUNK) c->seg_s = v; }   // k_splat's u32 sums bound a segment
+    if (const char* s = getenv("EINCM_WINCAP")) { int v = atoi(s); if (v >= 1024 && v <= 6912) { c->wincap = (v / 4) * 4; c->wincap_fixed = true; } }
+    c->host_binning = (ntiles > BIN_MAX_TILES) || (getenv("EINCM_HOST_BINNING") != nullptr);
+    c->max_items = (int64_t)B * ntiles + max_events_total / MIN_SEG + 1;   // a tile of n events is cut into ceil(n / seg) segments, seg >= MIN_SEG
     c->coarse_cap = 64 * 64 * 2;   // coarse theta up to 64x64 (the pyramid tops out at 16x16); grown on demand
     TRY(dalloc(&c->d_xy, (size_t)max_events_total));
     TRY(dalloc(&c->d_t, (size_t)max_events_total));
     TRY(dalloc(&c->d_xy_g, (size_t)max_events_total));
     TRY(dalloc(&c->d_t_g, (size_t)max_events_total));
-    c->host_binning = (ntiles > BIN_MAX_TILES) || (getenv("EINCM_HOST_BINNING") != nullptr);
     for (SegList* L : {&c->gather, &c->splat, &c->splat_sh, &c->gather_2}) {
         TRY(dalloc(&L->d_items, (size_t)c->max_items));
         TRY(dalloc(&L->d_order, (size_t)c->max_items));
@@ -1665,36 +1730,49 @@ static int build_list(eincm_ctx* c, SegList& L, int seg, bool on_host, int ntile
     return EINCM_OK;
 }
 
-// xs_w / ys_w / ts_w / edges_w: one pointer per window (the caller's own arrays; nothing is concatenated on the host)
-static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* const* xs_w,
-                            const int16_t* const* ys_w, const double* const* ts_w, const double* const* edges_w,
-                            const double* edge_ts, uint32_t sw_flags) {
-    if (c && c->pend.active && c->pend.launched)
-        return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
+// ---- staging (eincm_set_windows*): check_staging -> plan_staging -> the phases, each reading the plan ----
+
+// float64 mode: the scale of a window's u64 IWE accumulator.  No pixel can exceed N_b / (2 pi) (one tap per event and pixel), so
+// 2^ishift with N_b / (2 pi) * 2^ishift < 2^62, capped at 2^52
+static int f64_ishift(int64_t n_events) {
+    const double bound = std::max(1.0, (double)n_events * 0.15915494309189535);
+    return std::min(52, 62 - (int)std::ceil(std::log2(bound)));
+}
+
+// Everything a staging refuses from its arguments alone, before it touches the context or enqueues work.
+static int check_staging(eincm_ctx* c, const StageArgs& a) {
     if (!c) return EINCM_ERR_ARG;
-    if (n_windows < 1 || n_windows > c->maxB) return fail(c, EINCM_ERR_ARG, "n_windows %d outside 1..%d", n_windows, c->maxB);
-    if (n_refs < 1 || n_refs > c->maxR) return fail(c, EINCM_ERR_ARG, "n_refs %d outside 1..%d", n_refs, c->maxR);
-    if (!n_events || !xs_w || !ys_w || !ts_w || !edges_w || !edge_ts) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    if (n_windows >= 1 && n_windows <= c->maxB)
-        for (int b = 0; b < n_windows; ++b)
-            if (!edges_w[b] || (n_events[b] > 0 && (!xs_w[b] || !ys_w[b] || !ts_w[b]))) return fail(c, EINCM_ERR_ARG, "null pointer argument (window %d)", b);
-    HIPCHK(c, hipSetDevice(c->device));
-    c->objc_valid = false;         // the zero-warp values of the objective kinds belong to the windows staged before
-    const int H = c->H, W = c->W;
+    if (c->pend.active && c->pend.launched)
+        return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
+    if (a.B < 1 || a.B > c->maxB) return fail(c, EINCM_ERR_ARG, "n_windows %d outside 1..%d", a.B, c->maxB);
+    if (a.R < 1 || a.R > c->maxR) return fail(c, EINCM_ERR_ARG, "n_refs %d outside 1..%d", a.R, c->maxR);
+    if (!a.n_events || !a.xs || !a.ys || !a.ts || !a.edges || !a.edge_ts) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    for (int b = 0; b < a.B; ++b)
+        if (!a.edges[b] || (a.n_events[b] > 0 && (!a.xs[b] || !a.ys[b] || !a.ts[b]))) return fail(c, EINCM_ERR_ARG, "null pointer argument (window %d)", b);
     int64_t N = 0;
-    for (int b = 0; b < n_windows; ++b) {
-        if (n_events[b] < 0) return fail(c, EINCM_ERR_ARG, "n_events[%d] negative", b);
-        N += n_events[b];
+    for (int b = 0; b < a.B; ++b) {
+        if (a.n_events[b] < 0) return fail(c, EINCM_ERR_ARG, "n_events[%d] negative", b);
+        N += a.n_events[b];
     }
     if (N > c->maxN) return fail(c, EINCM_ERR_ARG, "total events %lld exceed capacity %lld", (long long)N, (long long)c->maxN);
-    c->staged = false;
-    c->Theta_valid = false;
-    c->bfgs.begun = false;           // the BFGS state belongs to the batch it was begun for
-    // Async copies below read from / write into locals of this function; whatever path leaves it (an error return included), the
-    // stream is drained first (safe before only because pageable copies happen to be host-synchronous).
-    struct DrainOnExit { hipStream_t s; ~DrainOnExit() { (void)hipStreamSynchronize(s); } } drain_on_exit{c->stream};
-    if (c->acc_dirty) { const int rcd = clear_accumulators(c); if (rcd) return rcd; }
-    Geom g{};
+    for (int b = 0; b < a.B; ++b)
+        for (int r = 0; r < a.R; ++r)
+            if (!std::isfinite(a.edge_ts[b * a.R + r])) return fail(c, EINCM_ERR_ARG, "edge_ts[%d,%d] is not finite", b, r);
+    if (c->fp64) {
+        if (a.flags & EINCM_SW_DEFER_CONSTANTS) return fail(c, EINCM_ERR_UNSUPPORTED, "event-sharded staging is not supported in fp64 mode");
+        for (int b = 0; b < a.B; ++b)
+            if (f64_ishift(a.n_events[b]) < 40)
+                return fail(c, EINCM_ERR_UNSUPPORTED, "window %d: %lld events exceed the fp64 mode's IWE scale (2^-40 per tap)", b, (long long)a.n_events[b]);
+    }
+    return EINCM_OK;
+}
+
+// Every decision of one staging, from the context and the checked arguments.  No HIP calls, no side effects; the one place where a
+// staging reads the environment (EINCM_SEG_2DOF, EINCM_PITCH_ALIGNED, EINCM_NO_SEGSORT, EINCM_NO_SPREAD: at every staging).
+static StagePlan plan_staging(const eincm_ctx* c, const StageArgs& a) {
+    StagePlan P;
+    const int H = c->H, W = c->W, n_windows = a.B, n_refs = a.R;
+    Geom& g = P.g;
     g.H = H; g.W = W; g.R = n_refs; g.B = n_windows;
     g.tilesX = (W + TS - 1) / TS; g.tilesY = (H + TS - 1) / TS; g.ntiles = g.tilesX * g.tilesY;
     g.igx = (W + IG_COLS - 1) / IG_COLS; g.nig = g.igx * ((H + IG_ROWS - 1) / IG_ROWS);
@@ -1702,6 +1780,8 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     g.gmax_n = g.R * g.nig;
     g.wincap = c->wincap; g.winmaxw = win_maxw(c->wincap);
     g.wincap_a = g.wincap; g.winmaxw_a = g.winmaxw;
+    for (int b = 0; b < n_windows; ++b) P.N += a.n_events[b];
+    const int64_t N = P.N;
 
     // Segment lengths (events per workgroup and reference time), measured on MI355X with the longest-first order of block_to_work
     // (tools/dev_tune_seg.py, profiles/r02/segment_tuning.txt).  Per-workgroup fixed cost (window clear / flush, G-window load,
@@ -1714,173 +1794,194 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
     //   theta grids / dense theta: the gather walks the list with the longer segments (one 10^6-event window at 16x16: 35.8 us
     //             with 4096, 30.3 with 8192, 28.6 with 16384; the 8-window batch 157 / 144 / 139 with 8192 / 16384 / 32768).
     const double x_wg = ((double)N / 8192.0 + 0.5 * n_windows * g.ntiles) * n_refs;
+    const double per_tile = (double)N / ((double)n_windows * g.ntiles);
     // Round 3: the gather's list always has long segments (what its theta-grid form wants: thtile, accumulator clear and flush per
-    // workgroup); its 2-DoF form walks a list of its own (seg_2).
-    int seg = c->seg > 0 ? c->seg : 16384;
-    int seg_2 = (x_wg >= 4000.0 && (double)N / ((double)n_windows * g.ntiles) < 16384.0) ? 16384 : (x_wg < 1000.0 ? 4096 : 8192);   // (tiles of several segments: as seg_s below; 480x640 with 10^7 events 90 -> 82 us)       // the 2-DoF gather's own list (round-2 tuning)
-    if (const char* e = getenv("EINCM_SEG_2DOF")) { const int v = atoi(e); if (v >= 64 && v <= MAX_SEG) seg_2 = v; }
+    // workgroup); its 2-DoF form walks a list of its own (seg_2: round-2 tuning; with tiles of several segments as seg_s below:
+    // 480x640 with 10^7 events 90 -> 82 us).
+    P.seg = c->seg > 0 ? c->seg : 16384;
+    P.seg_2 = (x_wg >= 4000.0 && per_tile < 16384.0) ? 16384 : (x_wg < 1000.0 ? 4096 : 8192);
+    if (const char* e = getenv("EINCM_SEG_2DOF")) { const int v = atoi(e); if (v >= MIN_SEG && v <= MAX_SEG) P.seg_2 = v; }
     // (late round 3: k_splat is no longer bound by the LDS atomic unit, so its per-workgroup fixed work - 24 of 90 us on the 8-window
     // batch: window derivation and clear 14, flush 10 - shows: 16384-event segments there, 90.1 -> 85.2 us; 104 -> 100 us at 16x16)
     // ... but only where a tile holds about one such segment: with tiles of several segments (480x640, 10^7 events: 33 000 per tile) the long
     // segments double the duration of EVERY workgroup and the kernel ends in a tail of few resident waves (k_splat 93 -> 137 us there).
-    const double per_tile = (double)N / ((double)n_windows * g.ntiles);
-    int seg_s = c->seg_s > 0 ? c->seg_s : (x_wg >= 3000.0 && per_tile < 16384.0 ? 16384 : (x_wg >= 400.0 ? 8192 : 4096));     // (4 windows of 10^6 events: 52.4 -> 49.7 us; 2 windows: equal; 1: 18.8 vs 19.7 the other way)  one window at R = 1: 4096 (0.066 vs 0.075 ms per evaluation)
+    // (4 windows of 10^6 events: 52.4 -> 49.7 us; 2 windows: equal; 1: 18.8 vs 19.7 the other way; one window at R = 1: 4096, 0.066 vs
+    // 0.075 ms per evaluation)
+    P.seg_s = c->seg_s > 0 ? c->seg_s : (x_wg >= 3000.0 && per_tile < 16384.0 ? 16384 : (x_wg >= 400.0 ? 8192 : 4096));
+    // beside a splat list of longer segments, the short one: the same events cut into 8192-event segments, for evaluations whose theta is
+    // too large for the windows of the long segments (twice the time span, hence twice the spread)
+    P.splat_short = P.seg_s > SEG_SHORT && N > 0;
     // The bank-aligned LDS pitch (win_pitch) goes with the same regime - many resident windows, about one segment per tile: both event
     // kernels 2 % faster on the bench batch; everywhere else pitch = width is the faster layout (profiles/r03/pitch_by_shape.txt: one
     // window of 10^6 events 72 -> 62 us per evaluation, 2 x 3*10^6 143 -> 128, 480x640 with 5*10^6 173 -> 126, with 10^7 220 -> 184).
-    g.pitch_aligned = (x_wg >= 3000.0 && per_tile < 16384.0) ? 1 : 0;
-    if (const char* e = getenv("EINCM_PITCH_ALIGNED")) g.pitch_aligned = std::max(0, std::min(2, atoi(e)));      // 0: never, 1: k_splat where it costs no capacity class, 2: the 2-DoF gather too
-    const bool sort_segments = getenv("EINCM_NO_SEGSORT") == nullptr;
-    const size_t img = (size_t)H * W;
-    for (int b = 0; b < n_windows; ++b) {
-        memset(&c->h_wc[b], 0, sizeof(WinConst));
-        multi_ref_weights(n_refs, c->h_wc[b].mrw);
-        for (int r = 0; r < n_refs; ++r)
-            if (!std::isfinite(edge_ts[b * n_refs + r])) return fail(c, EINCM_ERR_ARG, "edge_ts[%d,%d] is not finite", b, r);
+    P.pitch = (x_wg >= 3000.0 && per_tile < 16384.0) ? 1 : 0;
+    if (const char* e = getenv("EINCM_PITCH_ALIGNED")) P.pitch = std::max(0, std::min(2, atoi(e)));
+    g.pitch_aligned = P.pitch;
+    P.sort_segments = getenv("EINCM_NO_SEGSORT") == nullptr;
+    P.spread = getenv("EINCM_NO_SPREAD") == nullptr;
+    P.host_binning = c->host_binning;
+    P.defer_constants = (a.flags & EINCM_SW_DEFER_CONSTANTS) != 0;
+    P.wide = std::any_of(a.n_events, a.n_events + n_windows, [&](int64_t n) { return n * (int64_t)n_refs < 4096; });
+    return P;
+}
+
+// The refusal of event i of window b: outside the sensor (bad_xy), or with a non-finite timestamp.  refuse_event_at: of the event at
+// index e of the whole batch (what k_bin_hist reports).
+static int refuse_event(eincm_ctx* c, const StageArgs& a, int b, int64_t i, bool bad_xy) {
+    if (!bad_xy) return fail(c, EINCM_ERR_ARG, "event %lld of window %d has a non-finite timestamp", (long long)i, b);
+    return fail(c, EINCM_ERR_ARG, "event %lld of window %d at (x=%d, y=%d) outside the %dx%d sensor", (long long)i, b, (int)a.xs[b][i],
+                (int)a.ys[b][i], c->H, c->W);
+}
+static int refuse_event_at(eincm_ctx* c, const StageArgs& a, int64_t e, bool bad_xy) {
+    int b = 0;
+    while (b < a.B - 1 && e >= a.n_events[b]) { e -= a.n_events[b]; ++b; }
+    return refuse_event(c, a, b, e, bad_xy);
+}
+
+// The events as handed over, window after window: what the device path bins, and what eincm_get_warped_events walks on either path.
+static int upload_raw_events(eincm_ctx* c, const StageArgs& a) {
+    int64_t off = 0;
+    for (int b = 0; b < a.B; ++b) {
+        const size_t nb = (size_t)a.n_events[b];
+        if (nb > 0) {
+            HIPCHK(c, hipMemcpyAsync(c->d_raw_x + off, a.xs[b], nb * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_raw_y + off, a.ys[b], nb * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_raw_t + off, a.ts[b], nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        }
+        off += (int64_t)nb;
     }
-    std::vector<unsigned> cntmax_h((size_t)n_windows, 0u);
-    std::vector<double> dtmax_h((size_t)n_windows, 0.0);
-    bool edge_ts_uploaded = false;
-    int rc = EINCM_OK;
-    // the gather's copy of the binned events: every segment of its list sorted by source pixel and dealt to the threads that walk it
-    // (k_segsort, from the binned time order, before the splat's copy is re-dealt in place); EINCM_NO_SEGSORT: a plain copy
-    auto copy_for_gather = [&]() -> int {
-        if (c->gather.n == 0) return EINCM_OK;
-        if (sort_segments) {
-            hipLaunchKernelGGL(k_segsort, dim3(std::min(c->gather.n, 8192)), dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
-                               c->d_xy, c->d_t, c->d_xy_g, c->d_t_g);
-            return EINCM_OK;
-        }
-        HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return EINCM_OK;
+}
+
+// The gather's copy of the binned events: every segment of its list sorted by source pixel and dealt to the threads that walk it
+// (k_segsort, from the binned time order, before the splat's copy is re-dealt in place); EINCM_NO_SEGSORT: a plain copy.
+static int copy_for_gather(eincm_ctx* c) {
+    if (c->gather.n == 0) return EINCM_OK;
+    if (c->stage.sort_segments) {
+        hipLaunchKernelGGL(k_segsort, dim3(std::min(c->gather.n, 8192)), dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
+                           c->d_xy, c->d_t, c->d_xy_g, c->d_t_g);
         return EINCM_OK;
-    };
-    if (!c->host_binning) {
-        // ---- device path: counting sort by (window, source tile) on the GPU (eincm_binning.hip.h) ----
-        std::vector<BinBlock> blks;
-        std::vector<int32_t> win_blk((size_t)n_windows + 1);
-        int64_t base = 0;
-        for (int b = 0; b < n_windows; ++b) {
-            win_blk[b] = (int32_t)blks.size();
-            for (int64_t s0 = 0; s0 < n_events[b]; s0 += BIN_CHUNK) {
-                BinBlock bb; bb.win = b; bb.start = (int32_t)(base + s0); bb.count = (int32_t)std::min<int64_t>(BIN_CHUNK, n_events[b] - s0);
-                bb.first_blk = win_blk[b];
-                blks.push_back(bb);
-            }
-            base += n_events[b];
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)c->stage.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)c->stage.N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    return EINCM_OK;
+}
+
+// Device binning: counting sort by (window, source tile) on the GPU (eincm_binning.hip.h), the edges to fp32 with their moments, the
+// gather's and the splat's lists cut by k_items.  One synchronisation, for the tile populations and the kernels' verdict on the events.
+static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
+    const StagePlan& P = c->stage;
+    const Geom& g = P.g;
+    const size_t img = (size_t)g.H * g.W;
+    int rc = EINCM_OK;
+    sc.win_blk.resize((size_t)a.B + 1);
+    int64_t base = 0;
+    for (int b = 0; b < a.B; ++b) {
+        sc.win_blk[b] = (int32_t)sc.blks.size();
+        for (int64_t s0 = 0; s0 < a.n_events[b]; s0 += BIN_CHUNK) {
+            BinBlock bb; bb.win = b; bb.start = (int32_t)(base + s0); bb.count = (int32_t)std::min<int64_t>(BIN_CHUNK, a.n_events[b] - s0);
+            bb.first_blk = sc.win_blk[b];
+            sc.blks.push_back(bb);
         }
-        win_blk[n_windows] = (int32_t)blks.size();
-        const int nblk = (int)blks.size();
-        if (nblk > c->max_binblocks) return fail(c, EINCM_ERR_ARG, "internal: %d staging blocks exceed capacity", nblk);
-        int32_t misc_init[4] = {0, 0, 0x7fffffff, 0x7fffffff};                      // totals[2], err[2]
-        HIPCHK(c, hipMemcpyAsync(c->d_bin_misc, misc_init, sizeof misc_init, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_win_blk, win_blk.data(), win_blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        for (int b = 0; b < n_windows; ++b)
-            HIPCHK(c, hipMemcpyAsync(c->d_edges_raw + (size_t)b * n_refs * img, edges_w[b], (size_t)n_refs * img * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_edges, dim3(EDGE_PARTS, n_refs, n_windows), dim3(NT), 0, c->stream, g, c->d_edges_raw, c->d_edges, c->d_edge_moments);
-        if (nblk > 0) {
-            HIPCHK(c, hipMemcpyAsync(c->d_binblocks, blks.data(), blks.size() * sizeof(BinBlock), hipMemcpyHostToDevice, c->stream));
-            int64_t off = 0;
-            for (int b = 0; b < n_windows; ++b) {
-                const size_t nb = (size_t)n_events[b];
-                if (nb > 0) {
-                    HIPCHK(c, hipMemcpyAsync(c->d_raw_x + off, xs_w[b], nb * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->d_raw_y + off, ys_w[b], nb * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-                    HIPCHK(c, hipMemcpyAsync(c->d_raw_t + off, ts_w[b], nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
-                }
-                off += (int64_t)nb;
-            }
-            hipLaunchKernelGGL(k_bin_hist, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
-                               c->d_raw_t, c->d_blockhist, c->d_bin_misc + 2);
-        } else {
-            HIPCHK(c, hipMemsetAsync(c->d_blockhist, 0, sizeof(uint32_t), c->stream));
-        }
-        const int M = n_windows * g.ntiles;
-        hipLaunchKernelGGL(k_bin_scan, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, c->d_win_blk, c->d_blockhist, c->d_tilecount);
-        hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase, c->d_bin_misc);
-        HIPCHK(c, hipGetLastError());
-        int32_t misc[4];
-        std::vector<double> mom((size_t)n_windows * n_refs * EDGE_PARTS * EDGE_MOM);
-        HIPCHK(c, hipMemcpyAsync(misc, c->d_bin_misc, sizeof misc, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(mom.data(), c->d_edge_moments, mom.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        c->h_tilecount.resize((size_t)M);
-        HIPCHK(c, hipMemcpyAsync(c->h_tilecount.data(), c->d_tilecount, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (misc[2] != 0x7fffffff) {
-            const int64_t e = misc[2];
-            int b = 0; int64_t off = e;
-            while (b < n_windows - 1 && off >= n_events[b]) { off -= n_events[b]; ++b; }
-            return fail(c, EINCM_ERR_ARG, "event %lld of window %d at (x=%d, y=%d) outside the %dx%d sensor", (long long)off, b,
-                        (int)xs_w[b][off], (int)ys_w[b][off], H, W);
-        }
-        if (misc[3] != 0x7fffffff) {
-            const int64_t e = misc[3];
-            int b = 0; int64_t off = e;
-            while (b < n_windows - 1 && off >= n_events[b]) { off -= n_events[b]; ++b; }
-            return fail(c, EINCM_ERR_ARG, "event %lld of window %d has a non-finite timestamp", (long long)off, b);
-        }
-        c->gather.n = misc[1];
-        if (c->gather.n > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d segments exceed capacity", c->gather.n);
-        for (int b = 0; b < n_windows; ++b)
-            for (int r = 0; r < n_refs; ++r) {          // the blocks' partials, added in index order
-                double sE = 0.0, sEE = 0.0, eabs = 0.0;
-                for (int k = 0; k < EDGE_PARTS; ++k) {
-                    const double* m = &mom[(((size_t)b * n_refs + r) * EDGE_PARTS + k) * EDGE_MOM];
-                    sE += m[0]; sEE += m[1]; eabs = std::max(eabs, m[2]);
-                }
-                c->h_wc[b].sE[r] = sE; c->h_wc[b].sEE[r] = sEE; c->h_wc[b].eabs[r] = eabs;
-            }
-        if (nblk > 0) {
-            hipLaunchKernelGGL(k_bin_scatter, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
-                               c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t);
-            hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase,
-                               c->gather.d_items);
-            if ((rc = copy_for_gather())) return rc;
-        }
-        if ((rc = build_list(c, c->gather, seg, false, g.ntiles, c->d_t_g, N))) return rc;
-        c->splat.n = 0;
-        if (nblk > 0) {
-            if (!getenv("EINCM_NO_SPREAD"))
-                hipLaunchKernelGGL(k_spread, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t);
-            // per window: first segment and max |t - tau| (needs the segment time ranges and the FIRST segmentation's itembase)
-            HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, edge_ts, (size_t)n_windows * n_refs * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            edge_ts_uploaded = true;
-            hipLaunchKernelGGL(k_win_consts, dim3(n_windows), dim3(NT), 0, c->stream, g, c->gather.n, c->gather.d_items, c->gather.d_itembase,
-                               c->d_edge_ts, c->gather.d_win_item0, c->d_dtmax);
-            HIPCHK(c, hipMemcpyAsync(dtmax_h.data(), c->d_dtmax, (size_t)n_windows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            // second segmentation of the same binned events for k_splat; its total is not read back (a synchronisation per staging):
-            // the host repeats the arithmetic on the tile populations it holds
-            hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, seg_s, c->d_tilecount, c->d_tilebase, c->splat.d_itembase, c->d_bin_misc);
-            for (const int32_t cnt : c->h_tilecount) c->splat.n += (cnt + seg_s - 1) / seg_s;
-            if (c->splat.n > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d splat segments exceed capacity", c->splat.n);
-            hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, seg_s, c->d_tilecount, c->d_tilebase, c->splat.d_itembase,
-                               c->splat.d_items);
-        } else {
-            HIPCHK(c, hipMemsetAsync(c->gather.d_win_item0, 0, (size_t)(n_windows + 1) * sizeof(int32_t), c->stream));
-        }
-        if ((rc = build_list(c, c->splat, seg_s, false, g.ntiles, c->d_t, N))) return rc;
+        base += a.n_events[b];
+    }
+    sc.win_blk[a.B] = (int32_t)sc.blks.size();
+    const int nblk = (int)sc.blks.size();
+    if (nblk > c->max_binblocks) return fail(c, EINCM_ERR_ARG, "internal: %d staging blocks exceed capacity", nblk);
+    static const int32_t misc_init[4] = {0, 0, 0x7fffffff, 0x7fffffff};               // totals[2], err[2]
+    HIPCHK(c, hipMemcpyAsync(c->d_bin_misc, misc_init, sizeof misc_init, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_win_blk, sc.win_blk.data(), sc.win_blk.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    for (int b = 0; b < a.B; ++b)
+        HIPCHK(c, hipMemcpyAsync(c->d_edges_raw + (size_t)b * a.R * img, a.edges[b], (size_t)a.R * img * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_edges, dim3(EDGE_PARTS, a.R, a.B), dim3(NT), 0, c->stream, g, c->d_edges_raw, c->d_edges, c->d_edge_moments);
+    if (nblk > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->d_binblocks, sc.blks.data(), sc.blks.size() * sizeof(BinBlock), hipMemcpyHostToDevice, c->stream));
+        if ((rc = upload_raw_events(c, a))) return rc;
+        hipLaunchKernelGGL(k_bin_hist, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
+                           c->d_raw_t, c->d_blockhist, c->d_bin_misc + 2);
     } else {
-    // ---- host path (sensors with more tiles than the LDS histogram holds, or EINCM_HOST_BINNING=1): stable counting sort ----
-    c->h_tilecount.assign((size_t)n_windows * g.ntiles, 0);
-    std::vector<uint32_t> sxy((size_t)std::max<int64_t>(N, 1));
-    std::vector<double> st((size_t)std::max<int64_t>(N, 1));
+        HIPCHK(c, hipMemsetAsync(c->d_blockhist, 0, sizeof(uint32_t), c->stream));
+    }
+    const int M = a.B * g.ntiles;
+    hipLaunchKernelGGL(k_bin_scan, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, c->d_win_blk, c->d_blockhist, c->d_tilecount);
+    hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, P.seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase, c->d_bin_misc);
+    HIPCHK(c, hipGetLastError());
+    sc.mom.resize((size_t)a.B * a.R * EDGE_PARTS * EDGE_MOM);
+    HIPCHK(c, hipMemcpyAsync(sc.misc, c->d_bin_misc, sizeof sc.misc, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sc.mom.data(), c->d_edge_moments, sc.mom.size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    c->h_tilecount.resize((size_t)M);
+    HIPCHK(c, hipMemcpyAsync(c->h_tilecount.data(), c->d_tilecount, (size_t)M * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (sc.misc[2] != 0x7fffffff) return refuse_event_at(c, a, sc.misc[2], true);
+    if (sc.misc[3] != 0x7fffffff) return refuse_event_at(c, a, sc.misc[3], false);
+    c->gather.n = sc.misc[1];
+    if (c->gather.n > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d segments exceed capacity", c->gather.n);
+    for (int b = 0; b < a.B; ++b)
+        for (int r = 0; r < a.R; ++r) {          // the blocks' partials, added in index order
+            double sE = 0.0, sEE = 0.0, eabs = 0.0;
+            for (int k = 0; k < EDGE_PARTS; ++k) {
+                const double* m = &sc.mom[(((size_t)b * a.R + r) * EDGE_PARTS + k) * EDGE_MOM];
+                sE += m[0]; sEE += m[1]; eabs = std::max(eabs, m[2]);
+            }
+            c->h_wc[b].sE[r] = sE; c->h_wc[b].sEE[r] = sEE; c->h_wc[b].eabs[r] = eabs;
+        }
+    if (nblk > 0) {
+        hipLaunchKernelGGL(k_bin_scatter, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
+                           c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t);
+        hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, P.seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase,
+                           c->gather.d_items);
+        if ((rc = copy_for_gather(c))) return rc;
+    }
+    if ((rc = build_list(c, c->gather, P.seg, false, g.ntiles, c->d_t_g, P.N))) return rc;
+    c->splat.n = 0;
+    if (nblk > 0) {
+        if (P.spread)
+            hipLaunchKernelGGL(k_spread, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t);
+        // per window: first segment and max |t - tau| (needs the segment time ranges and the FIRST segmentation's itembase)
+        HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, a.edge_ts, (size_t)a.B * a.R * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        sc.edge_ts_uploaded = true;
+        hipLaunchKernelGGL(k_win_consts, dim3(a.B), dim3(NT), 0, c->stream, g, c->gather.n, c->gather.d_items, c->gather.d_itembase,
+                           c->d_edge_ts, c->gather.d_win_item0, c->d_dtmax);
+        HIPCHK(c, hipMemcpyAsync(sc.dtmax.data(), c->d_dtmax, (size_t)a.B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        // second segmentation of the same binned events for k_splat; its total is not read back (a synchronisation per staging):
+        // the host repeats the arithmetic on the tile populations it holds
+        hipLaunchKernelGGL(k_bin_tilescan, dim3(1), dim3(1024), 0, c->stream, M, P.seg_s, c->d_tilecount, c->d_tilebase, c->splat.d_itembase, c->d_bin_misc);
+        for (const int32_t cnt : c->h_tilecount) c->splat.n += (cnt + P.seg_s - 1) / P.seg_s;
+        if (c->splat.n > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %d splat segments exceed capacity", c->splat.n);
+        hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, P.seg_s, c->d_tilecount, c->d_tilebase, c->splat.d_itembase,
+                           c->splat.d_items);
+    } else {
+        HIPCHK(c, hipMemsetAsync(c->gather.d_win_item0, 0, (size_t)(a.B + 1) * sizeof(int32_t), c->stream));
+    }
+    return build_list(c, c->splat, P.seg_s, false, g.ntiles, c->d_t, P.N);
+}
+
+// Host binning (sensors with more tiles than the LDS histogram holds, or EINCM_HOST_BINNING=1): a stable counting sort, the edges to
+// fp32 with their moments, the gather's and the splat's lists cut on the host like the two others.
+static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
+    const StagePlan& P = c->stage;
+    const Geom& g = P.g;
+    const int H = g.H, W = g.W;
+    const size_t img = (size_t)H * W;
+    int rc = EINCM_OK;
+    c->h_tilecount.assign((size_t)a.B * g.ntiles, 0);
+    sc.sxy.resize((size_t)std::max<int64_t>(P.N, 1));
+    sc.st.resize((size_t)std::max<int64_t>(P.N, 1));
     std::vector<int64_t> cnt((size_t)g.ntiles + 1);
     int64_t base = 0;
-    for (int b = 0; b < n_windows; ++b) {
-        const int64_t n = n_events[b];
-        const int16_t* x = xs_w[b]; const int16_t* y = ys_w[b]; const double* t = ts_w[b];
+    for (int b = 0; b < a.B; ++b) {
+        const int64_t n = a.n_events[b];
+        const int16_t* x = a.xs[b]; const int16_t* y = a.ys[b]; const double* t = a.ts[b];
         std::fill(cnt.begin(), cnt.end(), 0);
         for (int64_t i = 0; i < n; ++i) {
-            for (int r = 0; r < n_refs; ++r) dtmax_h[b] = std::max(dtmax_h[b], std::fabs(t[i] - edge_ts[b * n_refs + r]));
-            if (x[i] < 0 || x[i] >= W || y[i] < 0 || y[i] >= H)
-                return fail(c, EINCM_ERR_ARG, "event %lld of window %d at (x=%d, y=%d) outside the %dx%d sensor",
-                            (long long)i, b, (int)x[i], (int)y[i], H, W);
-            if (!std::isfinite(t[i])) return fail(c, EINCM_ERR_ARG, "event %lld of window %d has a non-finite timestamp", (long long)i, b);
+            for (int r = 0; r < a.R; ++r) sc.dtmax[b] = std::max(sc.dtmax[b], std::fabs(t[i] - a.edge_ts[b * a.R + r]));
+            if (x[i] < 0 || x[i] >= W || y[i] < 0 || y[i] >= H) return refuse_event(c, a, b, i, true);
+            if (!std::isfinite(t[i])) return refuse_event(c, a, b, i, false);
             ++cnt[(size_t)(y[i] / TS) * g.tilesX + (x[i] / TS) + 1];
         }
         {   // most events on one source pixel
-            std::vector<uint32_t> pc((size_t)H * W, 0u);
-            for (int64_t i = 0; i < n; ++i) cntmax_h[b] = std::max(cntmax_h[b], ++pc[(size_t)y[i] * W + x[i]]);
+            std::vector<uint32_t> pc(img, 0u);
+            for (int64_t i = 0; i < n; ++i) sc.cntmax[b] = std::max(sc.cntmax[b], ++pc[(size_t)y[i] * W + x[i]]);
         }
         for (int k = 0; k < g.ntiles; ++k) c->h_tilecount[(size_t)b * g.ntiles + k] = (int32_t)cnt[k + 1];
         for (int k = 0; k < g.ntiles; ++k) cnt[k + 1] += cnt[k];
@@ -1888,158 +1989,150 @@ static int set_windows_impl(eincm_ctx* c, int n_windows, int n_refs, const int64
         for (int64_t i = 0; i < n; ++i) {
             const int tile = (y[i] / TS) * g.tilesX + (x[i] / TS);
             const int64_t d = base + pos[tile]++;
-            sxy[d] = (uint32_t)(uint16_t)x[i] | ((uint32_t)(uint16_t)y[i] << 16);
-            st[d] = t[i];
+            sc.sxy[d] = (uint32_t)(uint16_t)x[i] | ((uint32_t)(uint16_t)y[i] << 16);
+            sc.st[d] = t[i];
         }
         base += n;
     }
-    std::vector<float> ef((size_t)n_windows * n_refs * img);
-    for (int b = 0; b < n_windows; ++b) {
+    sc.ef.resize((size_t)a.B * a.R * img);
+    for (int b = 0; b < a.B; ++b) {
         WinConst& wc = c->h_wc[b];
-        for (int r = 0; r < n_refs; ++r) {
-            const double* e = edges_w[b] + (size_t)r * img;
-            float* o = ef.data() + ((size_t)b * n_refs + r) * img;
+        for (int r = 0; r < a.R; ++r) {
+            const double* e = a.edges[b] + (size_t)r * img;
+            float* o = sc.ef.data() + ((size_t)b * a.R + r) * img;
             double s = 0.0, ss = 0.0, mx = 0.0;
             for (size_t i = 0; i < img; ++i) { const float f = (float)e[i]; o[i] = f; s += (double)f; ss += (double)f * (double)f; mx = std::max(mx, std::fabs((double)f)); }
             wc.sE[r] = s; wc.sEE[r] = ss; wc.eabs[r] = mx;
         }
     }
-    if (N > 0) {
-        HIPCHK(c, hipMemcpyAsync(c->d_xy, sxy.data(), (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->d_t, st.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        int64_t off = 0;                                   // the events as handed over (eincm_get_warped_events), like the device path keeps them
-        for (int b = 0; b < n_windows; ++b) {
-            const size_t nb = (size_t)n_events[b];
-            if (nb > 0) {
-                HIPCHK(c, hipMemcpyAsync(c->d_raw_x + off, xs_w[b], nb * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->d_raw_y + off, ys_w[b], nb * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
-                HIPCHK(c, hipMemcpyAsync(c->d_raw_t + off, ts_w[b], nb * sizeof(double), hipMemcpyHostToDevice, c->stream));
-            }
-            off += (int64_t)nb;
-        }
+    if (P.N > 0) {
+        HIPCHK(c, hipMemcpyAsync(c->d_xy, sc.sxy.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_t, sc.st.data(), (size_t)P.N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if ((rc = upload_raw_events(c, a))) return rc;
     }
-    // the gather's and the splat's lists, cut on the host like the two others (the gather's copy is a permutation inside the gather
-    // list's segments: their time ranges come from either copy)
-    if ((rc = build_list(c, c->gather, seg, true, g.ntiles, c->d_t, N))) return rc;
-    if ((rc = copy_for_gather())) return rc;
-    if ((rc = build_list(c, c->splat, seg_s, true, g.ntiles, c->d_t, N))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->d_edges, ef.data(), ef.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));     // host vectors go out of scope
-    }
-    if (!edge_ts_uploaded)
-        HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, edge_ts, (size_t)n_windows * n_refs * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_mask, 0, (size_t)n_windows * img, c->stream));
-    // the 2-DoF gather's list (splat copy of the events), and beside a 16384-event splat list the splat's short one: the same events cut
-    // into 8192-event segments, for evaluations whose theta is too large for the windows of the long segments (twice the time span,
-    // hence twice the spread).  Both cut on the host from the tile populations.
-    if ((rc = build_list(c, c->gather_2, seg_2, true, g.ntiles, c->d_t, N))) return rc;
+    // (the gather's copy is a permutation inside the gather list's segments: their time ranges come from either copy)
+    if ((rc = build_list(c, c->gather, P.seg, true, g.ntiles, c->d_t, P.N))) return rc;
+    if ((rc = copy_for_gather(c))) return rc;
+    if ((rc = build_list(c, c->splat, P.seg_s, true, g.ntiles, c->d_t, P.N))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_edges, sc.ef.data(), sc.ef.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    return EINCM_OK;
+}
+
+// What both paths share: the 2-DoF gather's list (on the splat's copy of the events) and the splat's short one, both cut on the host
+// from the tile populations; the event mask and the most events on one source pixel; then the batch becomes the context's.
+static int finish_lists(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
+    const StagePlan& P = c->stage;
+    const Geom& g = P.g;
+    int rc = EINCM_OK;
+    if (!sc.edge_ts_uploaded)
+        HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, a.edge_ts, (size_t)a.B * a.R * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_mask, 0, (size_t)a.B * g.H * g.W, c->stream));
+    if ((rc = build_list(c, c->gather_2, P.seg_2, true, g.ntiles, c->d_t, P.N))) return rc;
     c->splat_sh.n = 0;
-    if (seg_s > 8192 && (rc = build_list(c, c->splat_sh, 8192, true, g.ntiles, c->d_t, N))) return rc;
-    if (c->gather.n > 0 && !c->host_binning) {     // event mask + most events on one source pixel, per tile from its LDS histogram
-        HIPCHK(c, hipMemsetAsync(c->d_cntmax, 0, (size_t)n_windows * sizeof(unsigned), c->stream));       // (before the synchronisation below: one per staging fewer)
-        hipLaunchKernelGGL(k_tile_counts, dim3(g.ntiles, n_windows), dim3(NT), 0, c->stream, g, c->d_tilebase, c->d_tilecount, c->d_xy,
+    if (P.splat_short && (rc = build_list(c, c->splat_sh, SEG_SHORT, true, g.ntiles, c->d_t, P.N))) return rc;
+    if (c->gather.n > 0 && !P.host_binning) {     // event mask + most events on one source pixel, per tile from its LDS histogram
+        HIPCHK(c, hipMemsetAsync(c->d_cntmax, 0, (size_t)a.B * sizeof(unsigned), c->stream));       // (before the synchronisation below: one per staging fewer)
+        hipLaunchKernelGGL(k_tile_counts, dim3(g.ntiles, a.B), dim3(NT), 0, c->stream, g, c->d_tilebase, c->d_tilecount, c->d_xy,
                            c->d_mask, c->d_cntmax);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(cntmax_h.data(), c->d_cntmax, (size_t)n_windows * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(sc.cntmax.data(), c->d_cntmax, (size_t)a.B * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->pitch_policy = g.pitch_aligned;
     c->policy_evaluated = false;
-    c->g = g; c->n_events = N;
-    c->itembase_valid = !c->host_binning && c->gather.n > 0 && c->splat.n > 0;      // both tile scans ran on the device
-    c->win_events.assign(n_events, n_events + n_windows);
-    c->wide = std::any_of(n_events, n_events + n_windows, [&](int64_t n) { return n * (int64_t)n_refs < 4096; });
-    if (c->gather.n > 0 && c->host_binning) {
+    c->g = g;
+    c->itembase_valid = !P.host_binning && c->gather.n > 0 && c->splat.n > 0;      // both tile scans ran on the device
+    c->win_events.assign(a.n_events, a.n_events + a.B);
+    if (c->gather.n > 0 && P.host_binning) {
         hipLaunchKernelGGL(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, c->stream, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask);
         HIPCHK(c, hipGetLastError());
     }
+    return EINCM_OK;
+}
 
-    if (c->fp64) {
-        // float64 mode: the edges as handed over, and the scale of each window's u64 IWE accumulator: no pixel can exceed
-        // N_b / (2 pi) (one tap per event and pixel), so 2^ishift with N_b / (2 pi) * 2^ishift < 2^62, capped at 2^52
-        if (sw_flags & EINCM_SW_DEFER_CONSTANTS) { c->staged = false; return fail(c, EINCM_ERR_UNSUPPORTED, "event-sharded staging is not supported in fp64 mode"); }
-        std::vector<int> ish((size_t)n_windows);
-        for (int b = 0; b < n_windows; ++b) {
-            const double bound = std::max(1.0, (double)n_events[b] * 0.15915494309189535);
-            ish[b] = std::min(52, 62 - (int)std::ceil(std::log2(bound)));
-            if (ish[b] < 40) { c->staged = false; return fail(c, EINCM_ERR_UNSUPPORTED, "window %d: %lld events exceed the fp64 mode's IWE scale (2^-40 per tap)", b, (long long)n_events[b]); }
-        }
-        HIPCHK(c, hipMemcpyAsync(c->f64.ishift, ish.data(), ish.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-        for (int b = 0; b < n_windows; ++b)
-            HIPCHK(c, hipMemcpyAsync(c->f64.edges + (size_t)b * n_refs * img, edges_w[b], (size_t)n_refs * img * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));      // ish goes out of scope; the caller's edges may be freed after return
+// float64 mode: the edges as handed over, and the scale of each window's u64 IWE accumulator
+static int stage_fp64(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
+    const size_t img = (size_t)c->H * c->W;
+    for (int b = 0; b < a.B; ++b) sc.ishift.push_back(f64_ishift(a.n_events[b]));
+    HIPCHK(c, hipMemcpyAsync(c->f64.ishift, sc.ishift.data(), sc.ishift.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    for (int b = 0; b < a.B; ++b)
+        HIPCHK(c, hipMemcpyAsync(c->f64.edges + (size_t)b * a.R * img, a.edges[b], (size_t)a.R * img * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    return EINCM_OK;
+}
+
+// One staging.  The scratch is constructed before the guard, so whatever path leaves this function (an error return included) drains
+// the stream first and frees the host memory its copies read from / write into afterwards; the caller's arrays live longer still.
+static int stage_windows(eincm_ctx* c, const StageArgs& a) {
+    int rc = check_staging(c, a);
+    if (rc) return rc;
+    c->staged = false;
+    c->objc_valid = false;           // the zero-warp values of the objective kinds belong to the windows staged before
+    c->Theta_valid = false;
+    c->bfgs.begun = false;           // the BFGS state belongs to the batch it was begun for
+    c->stage = plan_staging(c, a);
+    const StagePlan& P = c->stage;
+    HIPCHK(c, hipSetDevice(c->device));
+    StageScratch sc;
+    struct DrainOnExit { hipStream_t s; ~DrainOnExit() { (void)hipStreamSynchronize(s); } } drain_on_exit{c->stream};
+    if (c->acc_dirty && (rc = clear_accumulators(c))) return rc;
+    for (int b = 0; b < a.B; ++b) {
+        memset(&c->h_wc[b], 0, sizeof(WinConst));
+        multi_ref_weights(a.R, c->h_wc[b].mrw);
     }
-    // ---- zero-warp constants: one forward pass at theta = 0 (then IWE_r == IUE for every r) ----
-    // c0, zc[r], d0 are temporarily 1 so the pass is well defined; store_constants() overwrites them.
-    for (int b = 0; b < n_windows; ++b) {
+    sc.cntmax.assign((size_t)a.B, 0u);
+    sc.dtmax.assign((size_t)a.B, 0.0);
+    if ((rc = P.host_binning ? bin_on_host(c, a, sc) : bin_on_device(c, a, sc))) return rc;
+    if ((rc = finish_lists(c, a, sc))) return rc;
+    if (c->fp64 && (rc = stage_fp64(c, a, sc))) return rc;
+    for (int b = 0; b < a.B; ++b) {      // bounds behind the scale of the i64 gradient accumulators (grad_shift)
         WinConst& wc = c->h_wc[b];
-        wc.c0_gradmag = 1.0; wc.c0_var = 1.0; wc.d0 = 1.0;
-        for (int r = 0; r < n_refs; ++r) wc.zc[r] = 1.0;
-        // bounds behind the scale of the i64 gradient accumulators (grad_shift)
-        wc.nev = (double)std::max<int64_t>(n_events[b], 1);
-        wc.cntmax = (double)std::max(cntmax_h[b], 1u);
-        wc.dtmax = dtmax_h[b];
+        wc.nev = (double)std::max<int64_t>(a.n_events[b], 1);
+        wc.cntmax = (double)std::max(sc.cntmax[b], 1u);
+        wc.dtmax = sc.dtmax[b];
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_wc, c->h_wc, (size_t)n_windows * sizeof(WinConst), hipMemcpyHostToDevice, c->stream));
     c->staged = true;
     c->have_eval = false;
     c->err.clear();
-    c->sharded_staging = (sw_flags & EINCM_SW_DEFER_CONSTANTS) != 0;
-    if (sw_flags & EINCM_SW_DEFER_CONSTANTS) {       // event-sharded mode: the caller sums the shards' IUEs first
-        c->constants_pending = true;
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        return EINCM_OK;
-    }
-    {
-        std::vector<double> zero((size_t)n_windows * 2, 0.0);
-        std::vector<double> val((size_t)n_windows);
-        const eincm_params p = zero_pass_params();
-        const int rc = evaluate(c, zero.data(), 1, 1, &p, val.data(), nullptr, nullptr, true);
-        if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) { c->staged = false; return rc; }
-    }
-    rc = store_constants(c);
-    c->err.clear();
-    return rc;
+    c->sharded_staging = P.defer_constants;
+    if (!P.defer_constants) return window_constants(c);
+    // event-sharded mode: the caller sums the shards' IUEs first (eincm_forward_iwe(NULL theta), eincm_finish_constants)
+    if ((rc = preset_constants(c))) return rc;
+    c->constants_pending = true;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return EINCM_OK;
 }
 
-// The concatenated forms: per-window pointers into the caller's arrays.
-static int set_windows_concat(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* xs, const int16_t* ys,
-                              const double* ts, const double* edges, const double* edge_ts, uint32_t flags) {
-    if (!c) return EINCM_ERR_ARG;
-    if (!n_events || !xs || !ys || !ts || !edges || !edge_ts) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    if (n_windows < 1 || n_windows > c->maxB) return fail(c, EINCM_ERR_ARG, "n_windows %d outside 1..%d", n_windows, c->maxB);
-    std::vector<const int16_t*> xw((size_t)n_windows), yw((size_t)n_windows);
-    std::vector<const double*> tw((size_t)n_windows), ew((size_t)n_windows);
+// The concatenated forms: per-window pointers into the caller's arrays (arguments stage_windows would refuse go through as they are).
+int eincm_set_windows_ex(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* xs, const int16_t* ys,
+                         const double* ts, const double* edges, const double* edge_ts, uint32_t flags) {
+    const bool sane = c && n_events && xs && ys && ts && edges && n_windows >= 1 && n_windows <= c->maxB;
+    const size_t nb = sane ? (size_t)n_windows : 0, img = c ? (size_t)c->H * c->W : 0;
+    std::vector<const int16_t*> xw(nb), yw(nb);
+    std::vector<const double*> tw(nb), ew(nb);
     int64_t base = 0;
-    const size_t img = (size_t)c->H * c->W;
-    for (int b = 0; b < n_windows; ++b) {
-        xw[b] = xs + base; yw[b] = ys + base; tw[b] = ts + base; ew[b] = edges + (size_t)b * (size_t)std::max(n_refs, 0) * img;
+    for (size_t b = 0; b < nb; ++b) {
+        xw[b] = xs + base; yw[b] = ys + base; tw[b] = ts + base; ew[b] = edges + b * (size_t)std::max(n_refs, 0) * img;
         base += std::max<int64_t>(n_events[b], 0);
     }
-    return set_windows_impl(c, n_windows, n_refs, n_events, xw.data(), yw.data(), tw.data(), ew.data(), edge_ts, flags);
+    return stage_windows(c, StageArgs{n_windows, n_refs, n_events, sane ? xw.data() : nullptr, sane ? yw.data() : nullptr,
+                                      sane ? tw.data() : nullptr, sane ? ew.data() : nullptr, edge_ts, flags});
 }
 
 int eincm_set_windows(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* xs, const int16_t* ys,
                       const double* ts, const double* edges, const double* edge_ts) {
-    return set_windows_concat(c, n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, 0u);
-}
-
-int eincm_set_windows_ex(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* xs, const int16_t* ys,
-                         const double* ts, const double* edges, const double* edge_ts, uint32_t flags) {
-    return set_windows_concat(c, n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, flags);
+    return eincm_set_windows_ex(c, n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, 0u);
 }
 
 int eincm_set_windows_ptrs(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* const* xs,
                            const int16_t* const* ys, const double* const* ts, const double* const* edges, const double* edge_ts,
                            uint32_t flags) {
-    return set_windows_impl(c, n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, flags);
+    return stage_windows(c, StageArgs{n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, flags});
 }
 
 // ---- event-sharded evaluation: forward half / [caller all-reduces the IWE stack] / finishing half ----
 int eincm_forward_iwe(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, int want_grad) {
     if (!c) return EINCM_ERR_ARG;
     if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_forward_iwe (event-sharded mode) is not supported in fp64 mode (EINCM_CF_FP64)");
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_forward_iwe called before eincm_set_windows");
+    if (const int rc = eval_ready(c, "eincm_forward_iwe", false)) return rc;
     if (!p || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "bad argument");
     if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
     HIPCHK(c, hipSetDevice(c->device));
@@ -2071,10 +2164,9 @@ int eincm_loss_grad_device(eincm_ctx* c, const double* theta_dev, int h, int w, 
                            double* value, double* grad_dev, eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
     if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_loss_grad_device is not supported in fp64 mode (EINCM_CF_FP64)");
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_loss_grad_device called before eincm_set_windows");
+    if (const int rc = eval_ready(c, "eincm_loss_grad_device")) return rc;
     if (!theta_dev || !p || !value || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "bad argument");
     if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
-    if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
     if (c->device_results) return fail(c, EINCM_ERR_STATE, "eincm_set_device_results is on: use the split finishing half");
     HIPCHK(c, hipSetDevice(c->device));
     hipPointerAttribute_t at{};
@@ -2138,11 +2230,7 @@ int eincm_finish_constants(eincm_ctx* c) {
     if (!c->constants_pending) return fail(c, EINCM_ERR_STATE, "no deferred window constants");
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<double> val((size_t)c->g.B);
-    const int rc = eval_end(c, val.data(), nullptr, nullptr);
-    if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
-    const int rc2 = store_constants(c);
-    c->err.clear();
-    return rc2;
+    return store_constants(c, eval_end(c, val.data(), nullptr, nullptr));
 }
 
 int eincm_iwe_device_ptr(eincm_ctx* c, void** dptr, int64_t* n_words) {
@@ -2167,8 +2255,7 @@ int eincm_loss_grad_async(eincm_ctx* c, const double* theta, int h, int w, const
 
 int eincm_loss_grad_masked_async(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, const uint8_t* active, int want_grad) {
     if (!c) return EINCM_ERR_ARG;
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_loss_grad_async called before eincm_set_windows");
-    if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants are not finished (eincm_finish_constants)");
+    if (const int rc = eval_ready(c, "eincm_loss_grad_async")) return rc;
     if (!theta || !p) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
     if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
@@ -2189,8 +2276,7 @@ int eincm_loss_grad_wait(eincm_ctx* c, double* value, double* grad, eincm_aux* a
 
 int eincm_loss_grad(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, double* value, double* grad, eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_loss_grad called before eincm_set_windows");
-    if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
+    if (const int rc = eval_ready(c, "eincm_loss_grad")) return rc;
     if (!theta || !p || !value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
     if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
@@ -2201,8 +2287,7 @@ int eincm_loss_grad(eincm_ctx* c, const double* theta, int h, int w, const eincm
 int eincm_loss_grad_masked(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, const uint8_t* active,
                            double* value, double* grad, eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_loss_grad_masked called before eincm_set_windows");
-    if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
+    if (const int rc = eval_ready(c, "eincm_loss_grad_masked")) return rc;
     if (!theta || !p || !value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
     if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
@@ -2213,7 +2298,7 @@ int eincm_loss_grad_masked(eincm_ctx* c, const double* theta, int h, int w, cons
 int eincm_handover_loss_grad(eincm_ctx* c, const double* a, const double* prev_theta, const double* theta, int h, int w,
                              const eincm_params* p, double* value, double* dvalue_da) {
     if (!c) return EINCM_ERR_ARG;
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_handover_loss_grad called before eincm_set_windows");
+    if (const int rc = eval_ready(c, "eincm_handover_loss_grad", false)) return rc;
     if (!a || !prev_theta || !theta || !p || !value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
     HIPCHK(c, hipSetDevice(c->device));
@@ -2237,7 +2322,7 @@ int eincm_handover_loss_grad(eincm_ctx* c, const double* a, const double* prev_t
 
 int eincm_objectives(eincm_ctx* c, const double* Theta, eincm_objectives_out* out) {
     if (!c) return EINCM_ERR_ARG;
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "eincm_objectives called before eincm_set_windows");
+    if (const int rc = eval_ready(c, "eincm_objectives", false)) return rc;
     if (!Theta || !out) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     HIPCHK(c, hipSetDevice(c->device));
     const Geom& g = c->g;
@@ -2993,20 +3078,7 @@ int eincm_set_splat_window(eincm_ctx* c, int window_size) {
     c->splat_rad = window_size / 2;
     c->objc_valid = false;                           // the objective kinds' zero-warp values come from the zero-warp IWE
     if (!c->staged) return EINCM_OK;
-    // the window constants of the staged batch with the new splat: the theta = 0 pass of staging again
-    for (int b = 0; b < c->g.B; ++b) {
-        WinConst& wc = c->h_wc[b];
-        wc.c0_gradmag = 1.0; wc.c0_var = 1.0; wc.d0 = 1.0;
-        for (int r = 0; r < c->g.R; ++r) wc.zc[r] = 1.0;
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_wc, c->h_wc, (size_t)c->g.B * sizeof(WinConst), hipMemcpyHostToDevice, c->stream));
-    std::vector<double> zero((size_t)c->g.B * 2, 0.0), val((size_t)c->g.B);
-    const eincm_params p = zero_pass_params();
-    const int rc = evaluate(c, zero.data(), 1, 1, &p, val.data(), nullptr, nullptr, true);
-    if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) { c->staged = false; return rc; }
-    const int rc2 = store_constants(c);
-    c->err.clear();
-    return rc2;
+    return window_constants(c);      // of the staged batch with the new splat: the theta = 0 pass of staging again
 }
 
 int eincm_tiled_objectives(eincm_ctx* c, int tile_h, int tile_w, eincm_tiled_out* out) {
@@ -3080,8 +3152,9 @@ int eincm_get_host_profile(eincm_ctx* c, double* us, int64_t* n_evals, int reset
 
 int eincm_get_launch_policy(eincm_ctx* c, double* out) {
     if (!c || !out) return EINCM_ERR_ARG;
-    out[EINCM_LP_SEG_GATHER] = c->gather.seg; out[EINCM_LP_SEG_SPLAT] = c->splat.seg; out[EINCM_LP_SEG_GATHER_2DOF] = c->gather_2.seg;
-    out[EINCM_LP_SEG_SPLAT_SHORT] = c->splat_sh.n > 0 ? c->splat_sh.seg : 0; out[EINCM_LP_PITCH_POLICY] = c->pitch_policy;
+    const StagePlan& S = c->stage;                      // the staging half: the plan of the staged batch, and its lists' time spans
+    out[EINCM_LP_SEG_GATHER] = S.seg; out[EINCM_LP_SEG_SPLAT] = S.seg_s; out[EINCM_LP_SEG_GATHER_2DOF] = S.seg_2;
+    out[EINCM_LP_SEG_SPLAT_SHORT] = S.splat_short ? SEG_SHORT : 0; out[EINCM_LP_PITCH_POLICY] = S.pitch;
     out[EINCM_LP_SPAN_SPLAT] = c->splat.tspan; out[EINCM_LP_SPAN_GATHER] = c->gather.tspan; out[EINCM_LP_SPAN_GATHER_2DOF] = c->gather_2.tspan;
     const bool evaluated = c->policy_evaluated;         // (never on a float64 context)
     const EvalPlan& P = c->pend.plan;
@@ -3124,8 +3197,7 @@ int eincm_get_timings(eincm_ctx* c, eincm_timings* t) {
 static int bfgs_ready(eincm_ctx* c, const char* who, bool need_begun) {
     if (c->fp64)
         return fail(c, EINCM_ERR_UNSUPPORTED, "%s is not supported in fp64 mode (EINCM_CF_FP64): the device-resident evaluation does not exist there", who);
-    if (!c->staged) return fail(c, EINCM_ERR_STATE, "%s called before eincm_set_windows", who);
-    if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
+    if (const int rc = eval_ready(c, who)) return rc;
     if (c->device_results) return fail(c, EINCM_ERR_STATE, "%s: eincm_set_device_results is on (the split finishing half owns the results)", who);
     if (c->pend.active) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
     if (c->g.B > BFGS_MAX_B) return fail(c, EINCM_ERR_ARG, "%s: %d windows exceed EINCM_BFGS_MAX_WINDOWS = %d", who, c->g.B, BFGS_MAX_B);

@@ -242,7 +242,7 @@ struct Window { int ox, oy, ww, wh; };
 // its row, and staging deals the events so that the 32 lanes of a half-wave come from 32 different source columns (k_spread): their
 // nine taps fall on 32 different banks.  tools/lds_atomic_bench2.hip: 11.4 ds_add_u32 lane-ops per clock and CU that way, 9.8 with a
 // +-1 column jitter on 30 % of the lanes, 7.2 with random columns (what a pitch equal to the width gives).
-// The aligned pitch is a property of the staged batch (Geom::pitch_aligned, set_windows_impl): it pays where the windows are resident in
+// The aligned pitch is a property of the staged batch (StagePlan::pitch, plan_staging): it pays where the windows are resident in
 // numbers and a tile holds about one segment (the bench batch: both event kernels 2 % faster), and costs where tiles hold several
 // segments' worth of events (480x640 with 10^7 events: k_splat 73 -> 84 us at equal LDS capacity; profiles/r03/pitch_by_shape.txt).
 __device__ __forceinline__ int win_pitch(const Geom& g, int ww) { return g.pitch_aligned ? ((ww + 31) & ~31) : ww; }

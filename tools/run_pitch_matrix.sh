@@ -1,6 +1,6 @@
 #!/bin/bash
 # Developer tool: wall time and event-kernel times of one evaluation per staged shape with the LDS row pitch of the policy
-# (set_windows_impl) and with the other one forced (EINCM_PITCH_ALIGNED).  Output: gpurun_out/pitch/out.txt (profiles/r03/pitch_by_shape.txt).
+# (plan_staging) and with the other one forced (EINCM_PITCH_ALIGNED).  Output: pitch/out.txt in the directory made below (profiles/r03/pitch_by_shape.txt).
 set -e
 mkdir -p gpurun_out/pitch
 : > gpurun_out/pitch/out.txt
