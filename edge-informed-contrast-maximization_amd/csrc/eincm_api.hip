@@ -37,9 +37,59 @@ namespace {
 
 thread_local std::string g_create_error;
 
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
+// The owner of a context's device and pinned host memory: every block is allocated through it and freed by it, one by one (release:
+// a buffer that grows) or all at once (release_all: the context ends, or its creation failed).  DESIGN.md section 5.2.
+struct Mem {
+    struct Block { void* p; size_t bytes; };
+    std::vector<Block> dev, pinned;
+    size_t dev_bytes = 0, pinned_bytes = 0;
+
+    template <typename T> hipError_t alloc_dev(T*& p, size_t n, bool zero = false) {
+        p = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
+        if (e == hipSuccess && p && zero) e = hipMemset(p, 0, n * sizeof(T));
+        return own(dev, dev_bytes, p, n * sizeof(T), e, hipFree);
+    }
+    template <typename T> hipError_t alloc_pinned(T*& p, size_t n, bool zero = false) {
+        p = nullptr;
+        const hipError_t e = hipHostMalloc(reinterpret_cast<void**>(&p), n * sizeof(T), hipHostMallocDefault);
+        if (e == hipSuccess && p && zero) memset(p, 0, n * sizeof(T));
+        return own(pinned, pinned_bytes, p, n * sizeof(T), e, hipHostFree);
+    }
+    void release(void* p) {
+        if (!p) return;
+        if (!drop(dev, dev_bytes, p, hipFree)) drop(pinned, pinned_bytes, p, hipHostFree);
+    }
+    void release_all() {
+        for (const Block& b : dev) (void)hipFree(b.p);
+        for (const Block& b : pinned) (void)hipHostFree(b.p);
+        dev.clear(); pinned.clear();
+        dev_bytes = pinned_bytes = 0;
+    }
+
+private:
+    template <typename T> static hipError_t own(std::vector<Block>& v, size_t& total, T*& p, size_t bytes, hipError_t e, hipError_t (*free_fn)(void*)) {
+        if (e != hipSuccess) { if (p) (void)free_fn(p); p = nullptr; return e; }       // (the block was allocated, zeroing it failed)
+        if (p) { v.push_back(Block{p, bytes}); total += bytes; }
+        return hipSuccess;
+    }
+    static bool drop(std::vector<Block>& v, size_t& total, void* p, hipError_t (*free_fn)(void*)) {
+        for (size_t i = 0; i < v.size(); ++i)
+            if (v[i].p == p) { (void)free_fn(p); total -= v[i].bytes; v.erase(v.begin() + i); return true; }
+        return false;
+    }
+};
+
+// A buffer that is allocated on first use or grows on demand (ensure): n elements at p, in HBM or (PINNED) in pinned host memory.
+template <typename T, bool PINNED = false> struct Grow {
+    T* p = nullptr;
+    size_t n = 0;
+};
+
+// Lays out the pieces of one operator's scratch: add returns the 256-byte-aligned offset of a piece, total is what ensure is asked for.
+struct Carve {
+    size_t total = 0;
+    size_t add(size_t bytes) { const size_t off = total; total += (bytes + 255) & ~(size_t)255; return off; }
 };
 
 // A segment list: the binned events of every (window, source tile) cut into segments of at most `seg` events (balanced_seg_len), the
@@ -136,6 +186,7 @@ struct eincm_ctx {
     int seg_s = 0;                 // ... of the splat list; EINCM_SEG_SPLAT overrides
     hipStream_t stream = nullptr;
     std::string err;
+    Mem mem;                       // owns every device and pinned block below
 
     // staged batch
     bool staged = false;
@@ -187,14 +238,14 @@ struct eincm_ctx {
     StatPart* d_parts = nullptr;   // (B,R,pstride)
     double* d_divparts = nullptr;  // (B,R,ntiles)
     double* d_g2parts = nullptr;   // (B,R,nig) contrast energy partials written by k_imgrad
-    float* d_gdiv = nullptr;       // (B,R,H,W) divergence adjoint image, allocated on first delta != 0 gradient
-    double* d_dgparts = nullptr;   // (B,R,ntiles,2)
+    Grow<float> d_gdiv;            // (B,R,H,W) divergence adjoint image, allocated on the first delta != 0 gradient
+    Grow<double> d_dgparts;        // (B,R,ntiles,2) ... and its per-tile partials
     double* d_tvparts = nullptr;   // (B,ntiles,3)
     WinConst* d_wc = nullptr;      // (B)
-    OutScal* d_outs = nullptr;     // (B)
-    long long* d_gth = nullptr;    // (2,B,maxcoarse) main | tv i64 accumulators for coarse theta, zero between evaluations (k_final clears)
-    double* d_grad = nullptr;      // (B,H,W,2) capacity
-    double* d_AH = nullptr; double* d_AW = nullptr;     // (H,h) (W,w) capacity H*H, W*W? -> sized on demand
+    OutScal* d_outs = nullptr;     // (B) the base of one block [OutScal x B | d_grad]
+    Grow<long long> d_gth;         // (2,B,coarse_cap) main | tv i64 accumulators for coarse theta, zero between evaluations (k_final clears); grown by ensure_coarse
+    double* d_grad = nullptr;      // (B,H,W,2) capacity, inside d_outs' block
+    Grow<double> d_AH, d_AW;       // (H,h) (W,w) for the current theta shape, grown on demand (ensure_resample)
     int2* d_rowtap = nullptr; int2* d_coltap = nullptr;
     TileRange* d_tilerng = nullptr;    // (ntiles) coarse cells under each tile for the current theta shape
     const double* theta_dev_in = nullptr;   // eincm_loss_grad_device: theta of the evaluation being begun lives in HBM (the caller's buffer)
@@ -202,39 +253,34 @@ struct eincm_ctx {
     double* grad_dev_out = nullptr;         // ... and the gradient goes there (device to device)
     bool device_results = false;       // eincm_set_device_results: results stay in HBM until eincm_finish_collect (event-sharded mode over RCCL)
     bool proj_in_gather = false;       // every tile touches <= PG_MAXC x PG_MAXC cells: k_gather projects its tile itself
-    size_t AH_cap = 0, AW_cap = 0;
     int cur_h = -1, cur_w = -1, cur_method = -1;
-    int64_t coarse_cap = 0;        // doubles per window in d_gth halves
+    int64_t coarse_cap = 0;        // cells per window in d_gth's halves: the stride the kernels are given (ensure_coarse)
 
     // selectable objective kinds (eincm_objectives.hip.h): tile size of the adaptive kinds, the zero-warp values of every kind
     // (computed on the first evaluation that needs them, dropped by set_windows and by a tile-size change) and the per-cell partials
     int obj_th = 32, obj_tw = 42;
     bool objc_valid = false;
     std::vector<ObjConst> h_objc;
-    ObjConst* d_objc = nullptr;    // (maxB)
-    double* d_oparts = nullptr;    // (B,R,ncells,OBJ_NP), grown on demand
-    size_t oparts_cap = 0;
-    double* h_ovals = nullptr;     // (maxB,maxR,2) pinned: contrast and signed correlation of every image (k_obj_grad)
+    Grow<ObjConst> d_objc;         // (maxB), allocated on first use
+    Grow<double> d_oparts;         // (B,R,ncells,OBJ_NP), grown on demand
+    Grow<double, true> h_ovals;    // (maxB,maxR,2) pinned: contrast and signed correlation of every image (k_obj_grad), allocated on first use
 
-    // scratch of the edge-smoothing / Canny / tiled-objective entry points (eincm_edges.hip.h, eincm_canny.hip.h), grown on demand
-    DevBuf e_u8, e_g, e_sq, e_misc, e_a, e_b, e_kern, e_out;
-    // scratch of eincm_preprocess_image (eincm_preprocess.hip.h), grown on demand: two uint8 stacks, the blur's row pass, the
-    // per-call tables, the CLAHE LUTs, and the NL-means weight table (kept for the (h, template, search) it was built for)
-    DevBuf p_img[2], p_rows, p_tab, p_lut, p_nlm;
+    // The one scratch block of the one-shot operators (edge smoothing, Canny, preprocessing, ground-truth flow, the DSEC data path,
+    // warped events, tiled objectives).  An operator lays out its pieces (Carve), grows the block once and drains the stream before
+    // it returns, so nothing in here outlives a call.  What a later call reads has a buffer of its own:
+    Grow<char> scratch;
+    // the NL-means weight table of eincm_preprocess_image, kept for the (template, search, h^2) it was built for
+    Grow<int32_t> p_nlm;
     std::vector<int32_t> h_pre_tab, h_nlm_tab;
     float nlm_hh = 0.0f;
     int nlm_tw = 0, nlm_sw = 0;
-    // scratch of eincm_gt_flow (eincm_gtflow.hip.h), grown on demand: the x and y frame stacks, the step lists, the output
-    DevBuf g_frames, g_tab, g_out;
-    // scratch of the DSEC data path (eincm_dsec.hip.h), grown on demand.  Rectification: the rounded map packed as int16 pairs (kept
-    // from the call that handed a map over), the chunk's coordinates in and out, the keep bytes, the block counts and offsets.  One
-    // input and one output buffer for remap_cubic, flow_decode and flow_encode, their tables, and the counters all four share.
-    DevBuf r_map, r_fmap, r_x, r_y, r_keep, r_rx, r_ry, r_cnt, r_off, d_in, d_out, d_tab, d_cnt;
+    // the rounded rectify map of eincm_rectify_events packed as int16 pairs, kept from the call that handed a map over
+    Grow<uint32_t> r_map;
     bool rect_map_set = false;
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
-    double* h_grad = nullptr;
+    double* h_grad = nullptr;      // inside h_outs' block, as d_grad is inside d_outs'
     OutScal* h_outs = nullptr;
     WinConst* h_wc = nullptr;
     // host-assembled evaluations (2-DoF theta, no TV / divergence / full aux): the kernels write their partials straight into these
@@ -311,12 +357,11 @@ struct eincm_ctx {
     struct {
         bool begun = false;                  // eincm_bfgs_begin has run for the staged batch (set_windows clears it)
         int n = 0, h = 0, w = 0, B = 0;
-        size_t cap_vec = 0, cap_H = 0;       // doubles the vectors / H hold
-        double* vec = nullptr;               // one block: X, G, P, Xt, Gt, S, Y, Hy, each (B, n) at stride cap_vec
+        Grow<double> vec;                    // one block: X, G, P, Xt, Gt, S, Y, Hy, each (B, n) at stride vec.n / 8
         double *X = nullptr, *G = nullptr, *P = nullptr, *Xt = nullptr, *Gt = nullptr, *S = nullptr, *Y = nullptr, *Hy = nullptr;
-        double* H = nullptr;                 // (B, n, n)
-        double* h_scal = nullptr;            // pinned (maxB, BFGS_NS): k_bfgs_scalars writes it
-        double* h_red = nullptr;             // pinned (maxB, 2): k_bfgs_reduce writes it
+        Grow<double> H;                      // (B, n, n)
+        Grow<double, true> h_scal;           // pinned (maxB, BFGS_NS): k_bfgs_scalars writes it
+        Grow<double, true> h_red;            // pinned (maxB, 2): k_bfgs_reduce writes it
     } bfgs;
 };
 
@@ -347,7 +392,27 @@ int fail(eincm_ctx* c, int code, const char* fmt, ...) {
                         __FILE__, __LINE__);                                                       \
     } while (0)
 
-template <typename T> hipError_t dalloc(T** p, size_t n) { return hipMalloc(reinterpret_cast<void**>(p), n * sizeof(T)); }
+// g holds at least n elements afterwards.  Growth drains the stream (work in flight may read the old block), frees the old block and
+// allocates the new one, zeroed on request; the old contents are gone.  A failed growth leaves g empty.
+template <typename T, bool PINNED> hipError_t ensure(eincm_ctx* c, Grow<T, PINNED>& g, size_t n, bool zero = false) {
+    if (n <= g.n) return hipSuccess;
+    if (const hipError_t e = hipStreamSynchronize(c->stream)) return e;
+    c->mem.release(g.p);
+    g.p = nullptr; g.n = 0;
+    if (const hipError_t e = PINNED ? c->mem.alloc_pinned(g.p, n, zero) : c->mem.alloc_dev(g.p, n, zero)) return e;
+    g.n = n;
+    return hipSuccess;
+}
+
+// The coarse-theta accumulators for theta of up to `cells` doubles per window, zero as every evaluation expects them.
+hipError_t ensure_coarse(eincm_ctx* c, size_t cells) {
+    if (const hipError_t e = ensure(c, c->d_gth, (size_t)2 * c->maxB * cells, true)) return e;
+    c->coarse_cap = (int64_t)(c->d_gth.n / ((size_t)2 * c->maxB));
+    return hipSuccess;
+}
+
+// One piece of the scratch block (Carve::add gave its offset)
+template <typename T> T* carved(eincm_ctx* c, size_t off) { return reinterpret_cast<T*>(c->scratch.p + off); }
 
 // ---------------------------------------------------------------------------------------------
 // jax.image.scale_and_translate per-axis weight matrix (S7; theta_utils.py:25-35), fp64 on the host.
@@ -409,28 +474,6 @@ void multi_ref_weights(int R, double* w) {
 }
 
 void free_all(eincm_ctx* c) {
-    auto F = [](auto*& p) { if (p) { (void)hipFree(p); p = nullptr; } };
-    F(c->d_xy); F(c->d_t); F(c->d_xy_g); F(c->d_t_g); F(c->d_raw_x); F(c->d_raw_y); F(c->d_raw_t); F(c->d_binblocks); F(c->d_win_blk);
-    for (SegList* L : {&c->gather, &c->splat, &c->splat_sh, &c->gather_2}) { F(L->d_items); F(L->d_order); F(L->d_win_item0); F(L->d_wins); F(L->d_itembase); }
-    F(c->d_blockhist); F(c->d_tilecount); F(c->d_tilebase); F(c->d_bin_misc); F(c->d_edges_raw); F(c->d_edge_moments); F(c->d_edges); F(c->d_edge_ts); F(c->d_acc); F(c->d_iwe); F(c->d_G); F(c->d_zero_iwe);
-    F(c->d_g11); F(c->d_dtmax); F(c->d_gmax); F(c->d_cntmax); F(c->d_gticket);
-    F(c->d_Theta); F(c->d_theta_in); F(c->d_gTheta); F(c->d_tvg); F(c->d_mask); F(c->d_tmm); F(c->d_parts);
-    F(c->d_divparts); F(c->d_g2parts); F(c->d_gdiv); F(c->d_dgparts); F(c->d_tvparts); F(c->d_wc); F(c->d_outs); c->d_grad = nullptr; F(c->d_gth); F(c->d_AH); F(c->d_AW);
-    F(c->d_rowtap); F(c->d_coltap); F(c->d_tilerng);
-    F(c->f64.acc); F(c->f64.iwe); F(c->f64.zero_iwe); F(c->f64.edges); F(c->f64.G); F(c->f64.sgn); F(c->f64.gacc); F(c->f64.gTh); F(c->f64.T);
-    F(c->f64.grad); F(c->f64.partA); F(c->f64.partB); F(c->f64.partC); F(c->f64.scal); F(c->f64.gmax); F(c->f64.ishift); F(c->f64.bad);
-    F(c->d_objc); F(c->d_oparts); c->oparts_cap = 0;
-    F(c->bfgs.vec); F(c->bfgs.H); c->bfgs.cap_vec = c->bfgs.cap_H = 0; c->bfgs.begun = false;
-    for (DevBuf* b : {&c->e_u8, &c->e_g, &c->e_sq, &c->e_misc, &c->e_a, &c->e_b, &c->e_kern, &c->e_out}) { F(b->p); b->bytes = 0; }
-    for (DevBuf* b : {&c->p_img[0], &c->p_img[1], &c->p_rows, &c->p_tab, &c->p_lut, &c->p_nlm}) { F(b->p); b->bytes = 0; }
-    for (DevBuf* b : {&c->g_frames, &c->g_tab, &c->g_out}) { F(b->p); b->bytes = 0; }
-    for (DevBuf* b : {&c->r_map, &c->r_fmap, &c->r_x, &c->r_y, &c->r_keep, &c->r_rx, &c->r_ry, &c->r_cnt, &c->r_off, &c->d_in, &c->d_out,
-                      &c->d_tab, &c->d_cnt}) { F(b->p); b->bytes = 0; }
-    c->rect_map_set = false;
-    c->nlm_tw = 0;
-    auto FH = [](auto*& p) { if (p) { (void)hipHostFree(p); p = nullptr; } };
-    FH(c->f64.h_scal); FH(c->h_ovals); FH(c->bfgs.h_scal); FH(c->bfgs.h_red);
-    FH(c->h_theta); FH(c->h_outs); c->h_grad = nullptr; FH(c->h_wc); FH(c->h_g11); FH(c->h_g2); FH(c->h_img); FH(c->h_tvparts);
     if (c->have_events) {
         for (int k = 0; k < eincm_ctx::EV_RING; ++k)
             for (int i = 0; i <= EINCM_N_STAGES; ++i)
@@ -440,6 +483,7 @@ void free_all(eincm_ctx* c) {
         c->have_events = false;
     }
     if (c->stream) { (void)hipStreamDestroy(c->stream); c->stream = nullptr; }
+    c->mem.release_all();
 }
 
 // EINCM_CF_TIMING: a stage made of ONE kernel launch (single = true) gets its start / stop events attached to that launch
@@ -497,18 +541,10 @@ int ensure_resample(eincm_ctx* c, int h, int w, int method) {
         if (lo >= hi) { lo = 0; hi = 0; }
         ct[x] = make_int2(lo, hi);
     }
-    if (AH.size() > c->AH_cap) {
-        if (c->d_AH) { (void)hipFree(c->d_AH); c->d_AH = nullptr; }
-        HIPCHK(c, dalloc(&c->d_AH, AH.size()));
-        c->AH_cap = AH.size();
-    }
-    if (AW.size() > c->AW_cap) {
-        if (c->d_AW) { (void)hipFree(c->d_AW); c->d_AW = nullptr; }
-        HIPCHK(c, dalloc(&c->d_AW, AW.size()));
-        c->AW_cap = AW.size();
-    }
-    HIPCHK(c, hipMemcpyAsync(c->d_AH, AH.data(), AH.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_AW, AW.data(), AW.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, ensure(c, c->d_AH, AH.size()));
+    HIPCHK(c, ensure(c, c->d_AW, AW.size()));
+    HIPCHK(c, hipMemcpyAsync(c->d_AH.p, AH.data(), AH.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_AW.p, AW.data(), AW.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_rowtap, rt.data(), rt.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_coltap, ct.data(), ct.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
     // the coarse cells under every 32x32 tile (what k_gather's own projection walks)
@@ -560,7 +596,7 @@ int clear_accumulators(eincm_ctx* c) {
     const size_t img = (size_t)c->H * c->W;
     HIPCHK(c, hipMemsetAsync(c->d_acc, 0, (size_t)c->maxB * c->maxR * img * sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_gTheta, 0, (size_t)c->maxB * img * 2 * sizeof(long long), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_gth, 0, (size_t)2 * c->maxB * c->coarse_cap * sizeof(long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_gth.p, 0, (size_t)2 * c->maxB * c->coarse_cap * sizeof(long long), c->stream));
     c->acc_dirty = false;
     return EINCM_OK;
 }
@@ -573,7 +609,7 @@ void launch_theta_image(eincm_ctx* c, int h, int w, bool identity, bool use_arg,
     const bool ww = with_windows && c->itembase_valid;
     auto go = [&](auto kernel, const auto& ta) {
         launch_timed(c, EINCM_STAGE_THETA, kernel, dim3(g.ntiles, g.B), dim3(NT), 0, g, h, w, identity ? 1 : 0, use_arg ? 1 : 0, ta,
-                     theta_dev, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_tilerng, c->d_Theta, c->d_tmm, c->d_edge_ts,
+                     theta_dev, c->d_AH.p, c->d_AW.p, c->d_rowtap, c->d_coltap, c->d_tilerng, c->d_Theta, c->d_tmm, c->d_edge_ts,
                      c->gather.n, c->gather.d_items, ww ? c->gather.d_itembase : nullptr, c->gather.d_wins,
                      c->splat.n, c->splat.d_items, ww ? c->splat.d_itembase : nullptr, c->splat.d_wins);
     };
@@ -760,7 +796,7 @@ int f64_launch(eincm_ctx* c, const double* theta_host) {
     HIPCHK(c, hipMemcpyAsync(c->f64.h_scal, c->f64.scal, (size_t)g.B * g.R * sizeof(F64Scal), hipMemcpyDeviceToHost, c->stream));
     if (ep.want_tv)            // shared with the fp32 path: k_tv is fp64 throughout; its partials also land in pinned memory for f64_assemble
         hipLaunchKernelGGL(k_tv<0>, dim3(g.ntiles, g.B), dim3(NT), 0, c->stream, g, c->d_Theta, c->d_mask, c->d_tvg, c->d_tvparts,
-                           P.full_aux ? 1 : 0, h, w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth + (size_t)c->maxB * c->coarse_cap,
+                           P.full_aux ? 1 : 0, h, w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p + (size_t)c->maxB * c->coarse_cap,
                            (int)c->coarse_cap, c->h_tvparts);
     if (P.want_grad) {
         hipLaunchKernelGGL(k64_grad1, gimg, dim3(NT), 0, c->stream, g, ep, c->f64.iwe, c->f64.edges, c->f64.scal, c->d_wc,
@@ -780,16 +816,16 @@ int f64_launch(eincm_ctx* c, const double* theta_host) {
             const size_t nO = (size_t)g.B * nth;
             if (w <= g.W) {
                 const size_t nT = (size_t)g.B * g.H * w * 2;
-                hipLaunchKernelGGL(k64_proj_w, dim3((unsigned)std::min<size_t>((nT + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, w, c->d_AW,
+                hipLaunchKernelGGL(k64_proj_w, dim3((unsigned)std::min<size_t>((nT + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, w, c->d_AW.p,
                                    c->f64.gTh, c->f64.T);
                 hipLaunchKernelGGL(k64_proj_h, dim3((unsigned)std::min<size_t>((nO + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h, w,
-                                   c->d_AH, c->f64.T, c->f64.grad);
+                                   c->d_AH.p, c->f64.T, c->f64.grad);
             } else {
                 const size_t nT = (size_t)g.B * h * g.W * 2;
                 hipLaunchKernelGGL(k64_proj_h_first, dim3((unsigned)std::min<size_t>((nT + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h,
-                                   c->d_AH, c->f64.gTh, c->f64.T);
+                                   c->d_AH.p, c->f64.gTh, c->f64.T);
                 hipLaunchKernelGGL(k64_proj_w_second, dim3((unsigned)std::min<size_t>((nO + NT - 1) / NT, 4096)), dim3(NT), 0, c->stream, g, h,
-                                   w, c->d_AW, c->f64.T, c->f64.grad);
+                                   w, c->d_AW.p, c->f64.T, c->f64.grad);
             }
             out = c->f64.grad;
         }
@@ -837,14 +873,9 @@ ObjGeom obj_geom(const eincm_ctx* c, int ck, int rk, int need) {
 
 int obj_buffers(eincm_ctx* c, const ObjGeom& og) {
     const size_t n = (size_t)c->g.B * c->g.R * og.ncells * OBJ_NP;
-    if (n > c->oparts_cap) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->d_oparts) { (void)hipFree(c->d_oparts); c->d_oparts = nullptr; c->oparts_cap = 0; }
-        HIPCHK(c, dalloc(&c->d_oparts, n));
-        c->oparts_cap = n;
-    }
-    if (!c->d_objc) HIPCHK(c, dalloc(&c->d_objc, (size_t)c->maxB));
-    if (!c->h_ovals) HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&c->h_ovals), (size_t)c->maxB * c->maxR * 2 * sizeof(double)));
+    HIPCHK(c, ensure(c, c->d_oparts, n));
+    HIPCHK(c, ensure(c, c->d_objc, (size_t)c->maxB));
+    HIPCHK(c, ensure(c, c->h_ovals, (size_t)c->maxB * c->maxR * 2));
     return EINCM_OK;
 }
 
@@ -857,11 +888,11 @@ int obj_constants(eincm_ctx* c) {
     if (rc) return rc;
     Geom g = c->g;
     g.wmask = ~0ull;
-    hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_zero_iwe, 0, c->d_edges, c->d_oparts);
-    hipLaunchKernelGGL(k_obj_const, dim3(g.B), dim3(64), 0, c->stream, g, og, c->d_oparts, c->d_objc);
+    hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_zero_iwe, 0, c->d_edges, c->d_oparts.p);
+    hipLaunchKernelGGL(k_obj_const, dim3(g.B), dim3(64), 0, c->stream, g, og, c->d_oparts.p, c->d_objc.p);
     HIPCHK(c, hipGetLastError());
     c->h_objc.assign((size_t)c->maxB, ObjConst{});
-    HIPCHK(c, hipMemcpyAsync(c->h_objc.data(), c->d_objc, (size_t)g.B * sizeof(ObjConst), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_objc.data(), c->d_objc.p, (size_t)g.B * sizeof(ObjConst), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int b = 0; b < g.B; ++b) {
         ObjConst& o = c->h_objc[b];
@@ -869,7 +900,7 @@ int obj_constants(eincm_ctx* c) {
         o.c0[0] = wc.c0_gradmag; o.c0[1] = wc.c0_var;
         for (int r = 0; r < g.R; ++r) o.zc[0][r] = wc.zc[r];
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_objc, c->h_objc.data(), (size_t)g.B * sizeof(ObjConst), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_objc.p, c->h_objc.data(), (size_t)g.B * sizeof(ObjConst), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->objc_valid = true;
     return EINCM_OK;
@@ -890,7 +921,7 @@ void obj_assemble(eincm_ctx* c) {
         const bool bad = P.host_asm ? c->theta_nan[b] != 0 : std::isnan(o.value);
         double sum_rel_con = 0.0, sum_rel_corr = 0.0;
         for (int r = 0; r < g.R; ++r) {
-            const double con = c->h_ovals[((size_t)b * g.R + r) * 2], corr = c->h_ovals[((size_t)b * g.R + r) * 2 + 1];
+            const double con = c->h_ovals.p[((size_t)b * g.R + r) * 2], corr = c->h_ovals.p[((size_t)b * g.R + r) * 2 + 1];
             sum_rel_con += wc.mrw[r] * con / (oc.c0[ck] + EPSN);
             sum_rel_corr += wc.mrw[r] * corr / (oc.zc[rk][r] + EPSN);
         }
@@ -1033,9 +1064,9 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
     const size_t img = (size_t)g.H * g.W;
     const size_t nth = (size_t)h * w * 2;
     c->pend.active = false; c->pend.launched = false;
-    if (p->delta != 0.0 && want_grad && !c->d_gdiv && !c->fp64) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocate lazily
-        HIPCHK(c, dalloc(&c->d_gdiv, (size_t)c->maxB * c->maxR * img));
-        HIPCHK(c, dalloc(&c->d_dgparts, (size_t)c->maxB * c->maxR * g.ntiles * 2));
+    if (p->delta != 0.0 && want_grad && !c->fp64) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocated on first use
+        HIPCHK(c, ensure(c, c->d_gdiv, (size_t)c->maxB * c->maxR * img));
+        HIPCHK(c, ensure(c, c->d_dgparts, (size_t)c->maxB * c->maxR * g.ntiles * 2));
     }
     if (p->contrast_kind < EINCM_CONTRAST_GRAD_MAG || p->contrast_kind > EINCM_CONTRAST_ADAPTIVE_VARIANCE)
         return fail(c, EINCM_ERR_ARG, "contrast_kind %d unknown", p->contrast_kind);
@@ -1052,13 +1083,7 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
     if (theta_shape(g, h, w) != EvalPlan::IDENTITY) {
         if ((int64_t)h * w > (int64_t)g.H * g.W)
             return fail(c, EINCM_ERR_ARG, "theta (%d,%d,2) has more cells than the %dx%d sensor has pixels: not supported", h, w, g.H, g.W);
-        if ((int64_t)nth > c->coarse_cap) {          // unusual (the pyramid tops out at 16x16): grow the coarse accumulators
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->d_gth) { (void)hipFree(c->d_gth); c->d_gth = nullptr; }
-            HIPCHK(c, dalloc(&c->d_gth, (size_t)2 * c->maxB * nth));
-            HIPCHK(c, hipMemset(c->d_gth, 0, (size_t)2 * c->maxB * nth * sizeof(long long)));
-            c->coarse_cap = (int64_t)nth;
-        }
+        HIPCHK(c, ensure_coarse(c, nth));            // grows for theta beyond 64x64 only (the pyramid tops out at 16x16)
         int rc = ensure_resample(c, h, w, p->method);
         if (rc) return rc;
     }
@@ -1167,31 +1192,31 @@ int eval_end_launch(eincm_ctx* c) {
         StageTimer t(c, EINCM_STAGE_TV, true);
         auto go = [&](auto kernel) {
             launch_timed(c, EINCM_STAGE_TV, kernel, dim3(g.ntiles, g.B), dim3(NT), 0, g, c->d_Theta, c->d_mask, c->d_tvg, c->d_tvparts,
-                         P.full_aux ? 1 : 0, P.h, P.w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth + (size_t)c->maxB * c->coarse_cap,
+                         P.full_aux ? 1 : 0, P.h, P.w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p + (size_t)c->maxB * c->coarse_cap,
                          (int)c->coarse_cap, host_asm ? c->h_tvparts : nullptr);
         };
         P.tv_proj ? go(k_tv<1>) : go(k_tv<0>);
     }
     if (P.obj && !want_grad) {          // forward only: the per-image values alone
         const ObjGeom& og = P.og;
-        hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts);
-        hipLaunchKernelGGL(k_obj_grad, dim3(1, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts,
-                           c->d_wc, c->d_objc, c->d_gdiv, c->d_dgparts, c->d_G, c->d_gmax, c->h_ovals, 0);
+        hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts.p);
+        hipLaunchKernelGGL(k_obj_grad, dim3(1, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts.p,
+                           c->d_wc, c->d_objc.p, c->d_gdiv.p, c->d_dgparts.p, c->d_G, c->d_gmax, c->h_ovals.p, 0);
     }
     if (want_grad) {
         {
             StageTimer t(c, EINCM_STAGE_IMGRAD, !P.div_grad && !P.obj);
             if (P.div_grad)
                 hipLaunchKernelGGL(k_divgrad, dim3(g.ntiles, g.R, g.B), dim3(NT), 0, c->stream, g, c->d_iwe, c->d_parts,
-                                   c->d_gdiv, c->d_dgparts);
+                                   c->d_gdiv.p, c->d_dgparts.p);
             if (P.obj) {
                 const ObjGeom& og = P.og;
-                hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts);
-                hipLaunchKernelGGL(k_obj_grad, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts,
-                                   c->d_wc, c->d_objc, c->d_gdiv, c->d_dgparts, c->d_G, c->d_gmax, c->h_ovals, 1);
+                hipLaunchKernelGGL(k_obj_parts, dim3(og.ncells, g.R, g.B), dim3(NT), 0, c->stream, g, og, c->d_iwe, 1, c->d_edges, c->d_oparts.p);
+                hipLaunchKernelGGL(k_obj_grad, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, c->stream, g, ep, og, c->d_iwe, c->d_edges, c->d_oparts.p,
+                                   c->d_wc, c->d_objc.p, c->d_gdiv.p, c->d_dgparts.p, c->d_G, c->d_gmax, c->h_ovals.p, 1);
             } else {
                 launch_timed(c, EINCM_STAGE_IMGRAD, k_imgrad, dim3(n_imwg, g.R, g.B), dim3(IG_NT), 0, g, ep, c->d_iwe, c->d_edges,
-                                   c->d_parts, c->d_wc, c->d_gdiv, c->d_dgparts, host_asm ? c->h_g2 : c->d_g2parts, c->d_G, c->d_gmax,
+                                   c->d_parts, c->d_wc, c->d_gdiv.p, c->d_dgparts.p, host_asm ? c->h_g2 : c->d_g2parts, c->d_G, c->d_gmax,
                                    host_asm ? c->h_img : nullptr, host_asm ? 1 : 0);
             }
         }
@@ -1225,9 +1250,9 @@ int eval_end_launch(eincm_ctx* c) {
                     auto go = [&](auto kernel, int nthreads) {
                         launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(nthreads), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta,
                                      c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, g11, c->d_wc, c->d_gmax, L.d_order, use_arg,
-                                     c->pend.theta_dev, c->pend.targ, P.h, P.w, c->d_AH, c->d_AW, c->d_tilerng, c->d_gth, (int)c->coarse_cap,
+                                     c->pend.theta_dev, c->pend.targ, P.h, P.w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p, (int)c->coarse_cap,
                                      P.grid_tail ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad,
-                                     (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth + (size_t)c->maxB * c->coarse_cap);
+                                     (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth.p + (size_t)c->maxB * c->coarse_cap);
                     };
                     if (two_dof)      go(k_gather<THETA_CONST, 0, NT, 0>, NT);
                     else if (P.all_r) c->stage.wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1>, NT_TILE);
@@ -1240,14 +1265,14 @@ int eval_end_launch(eincm_ctx* c) {
         if (P.nsrc > 0) {
             StageTimer t(c, EINCM_STAGE_PROJECT, true);
             launch_timed(c, EINCM_STAGE_PROJECT, k_project, dim3(g.ntiles, g.B, P.nsrc), dim3(NT), 0, g, P.h, P.w,
-                               (int)c->coarse_cap, P.events_projected ? 1 : 0, c->stage.wide ? 1 : 0, c->d_AH, c->d_AW, c->d_rowtap, c->d_coltap, c->d_gTheta, c->d_tvg,
-                               c->d_wc, c->d_gmax, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap);
+                               (int)c->coarse_cap, P.events_projected ? 1 : 0, c->stage.wide ? 1 : 0, c->d_AH.p, c->d_AW.p, c->d_rowtap, c->d_coltap, c->d_gTheta, c->d_tvg,
+                               c->d_wc, c->d_gmax, c->d_gth.p, c->d_gth.p + (size_t)c->maxB * c->coarse_cap);
         }
     }
     if (!host_asm) {
         StageTimer t(c, EINCM_STAGE_FINAL, !(want_grad && identity));
         launch_timed(c, EINCM_STAGE_FINAL, k_final, dim3(g.B), dim3(FT), 0, g, ep, c->d_parts, c->d_divparts, c->d_tvparts,
-                           c->d_tmm, c->d_wc, P.g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth, c->d_gth + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
+                           c->d_tmm, c->d_wc, P.g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth.p, c->d_gth.p + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
                            c->d_g11, c->gather_2.d_win_item0, c->gather_2.n, c->d_gmax,
                            P.zero_copy_out ? c->h_outs : c->d_outs, P.zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
         if (want_grad && identity) {
@@ -1552,83 +1577,77 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     if (const char* s = getenv("EINCM_WINCAP")) { int v = atoi(s); if (v >= 1024 && v <= 6912) { c->wincap = (v / 4) * 4; c->wincap_fixed = true; } }
     c->host_binning = (ntiles > BIN_MAX_TILES) || (getenv("EINCM_HOST_BINNING") != nullptr);
     c->max_items = (int64_t)B * ntiles + max_events_total / MIN_SEG + 1;   // a tile of n events is cut into ceil(n / seg) segments, seg >= MIN_SEG
-    c->coarse_cap = 64 * 64 * 2;   // coarse theta up to 64x64 (the pyramid tops out at 16x16); grown on demand
-    TRY(dalloc(&c->d_xy, (size_t)max_events_total));
-    TRY(dalloc(&c->d_t, (size_t)max_events_total));
-    TRY(dalloc(&c->d_xy_g, (size_t)max_events_total));
-    TRY(dalloc(&c->d_t_g, (size_t)max_events_total));
+    TRY(c->mem.alloc_dev(c->d_xy, (size_t)max_events_total));
+    TRY(c->mem.alloc_dev(c->d_t, (size_t)max_events_total));
+    TRY(c->mem.alloc_dev(c->d_xy_g, (size_t)max_events_total));
+    TRY(c->mem.alloc_dev(c->d_t_g, (size_t)max_events_total));
     for (SegList* L : {&c->gather, &c->splat, &c->splat_sh, &c->gather_2}) {
-        TRY(dalloc(&L->d_items, (size_t)c->max_items));
-        TRY(dalloc(&L->d_order, (size_t)c->max_items));
+        TRY(c->mem.alloc_dev(L->d_items, (size_t)c->max_items));
+        TRY(c->mem.alloc_dev(L->d_order, (size_t)c->max_items));
     }
-    for (SegList* L : {&c->gather, &c->gather_2}) TRY(dalloc(&L->d_win_item0, B + 1));
+    for (SegList* L : {&c->gather, &c->gather_2}) TRY(c->mem.alloc_dev(L->d_win_item0, B + 1));
     for (SegList* L : {&c->gather, &c->splat}) {
-        TRY(dalloc(&L->d_wins, (size_t)c->max_items * max_refs));
-        if (!c->host_binning) TRY(dalloc(&L->d_itembase, B * ntiles));
+        TRY(c->mem.alloc_dev(L->d_wins, (size_t)c->max_items * max_refs));
+        if (!c->host_binning) TRY(c->mem.alloc_dev(L->d_itembase, B * ntiles));
     }
-    TRY(dalloc(&c->d_raw_x, (size_t)max_events_total));          // kept after staging: eincm_get_warped_events walks them
-    TRY(dalloc(&c->d_raw_y, (size_t)max_events_total));
-    TRY(dalloc(&c->d_raw_t, (size_t)max_events_total));
+    TRY(c->mem.alloc_dev(c->d_raw_x, (size_t)max_events_total));          // kept after staging: eincm_get_warped_events walks them
+    TRY(c->mem.alloc_dev(c->d_raw_y, (size_t)max_events_total));
+    TRY(c->mem.alloc_dev(c->d_raw_t, (size_t)max_events_total));
     if (!c->host_binning) {
         c->max_binblocks = max_events_total / BIN_CHUNK + (int64_t)B + 1;
-        TRY(dalloc(&c->d_binblocks, (size_t)c->max_binblocks));
-        TRY(dalloc(&c->d_win_blk, B + 1));
-        TRY(dalloc(&c->d_blockhist, (size_t)c->max_binblocks * ntiles));
-        TRY(dalloc(&c->d_tilecount, B * ntiles));
-        TRY(dalloc(&c->d_tilebase, B * ntiles));
-        TRY(dalloc(&c->d_bin_misc, (size_t)8));
-        TRY(dalloc(&c->d_edges_raw, B * R * img));
-        TRY(dalloc(&c->d_edge_moments, B * R * EDGE_PARTS * EDGE_MOM));
+        TRY(c->mem.alloc_dev(c->d_binblocks, (size_t)c->max_binblocks));
+        TRY(c->mem.alloc_dev(c->d_win_blk, B + 1));
+        TRY(c->mem.alloc_dev(c->d_blockhist, (size_t)c->max_binblocks * ntiles));
+        TRY(c->mem.alloc_dev(c->d_tilecount, B * ntiles));
+        TRY(c->mem.alloc_dev(c->d_tilebase, B * ntiles));
+        TRY(c->mem.alloc_dev(c->d_bin_misc, (size_t)8));
+        TRY(c->mem.alloc_dev(c->d_edges_raw, B * R * img));
+        TRY(c->mem.alloc_dev(c->d_edge_moments, B * R * EDGE_PARTS * EDGE_MOM));
     }
-    TRY(dalloc(&c->d_edges, B * R * img));
-    TRY(dalloc(&c->d_edge_ts, B * R));
-    TRY(dalloc(&c->d_acc, B * R * img));
-    TRY(hipMemset(c->d_acc, 0, B * R * img * sizeof(unsigned long long)));
-    TRY(dalloc(&c->d_iwe, B * R * img));
-    TRY(dalloc(&c->d_G, B * R * img));
-    TRY(dalloc(&c->d_g11, (size_t)(c->max_items + NXCD) * R * 2));
-    TRY(dalloc(&c->d_dtmax, B));
-    TRY(dalloc(&c->d_cntmax, B));
+    TRY(c->mem.alloc_dev(c->d_edges, B * R * img));
+    TRY(c->mem.alloc_dev(c->d_edge_ts, B * R));
+    TRY(c->mem.alloc_dev(c->d_acc, B * R * img, true));
+    TRY(c->mem.alloc_dev(c->d_iwe, B * R * img));
+    TRY(c->mem.alloc_dev(c->d_G, B * R * img));
+    TRY(c->mem.alloc_dev(c->d_g11, (size_t)(c->max_items + NXCD) * R * 2));
+    TRY(c->mem.alloc_dev(c->d_dtmax, B));
+    TRY(c->mem.alloc_dev(c->d_cntmax, B));
     const size_t nig = (size_t)((W + IG_COLS - 1) / IG_COLS) * ((H + IG_ROWS - 1) / IG_ROWS);   // k_imgrad strips per image
-    TRY(dalloc(&c->d_gmax, B * R * nig));
-    TRY(hipMemset(c->d_gmax, 0, B * R * nig * sizeof(unsigned)));
-    TRY(dalloc(&c->d_zero_iwe, B * img));
-    TRY(dalloc(&c->d_Theta, B * img * 2));
-    TRY(dalloc(&c->d_theta_in, B * img * 2));
-    TRY(dalloc(&c->d_gTheta, B * img * 2));
-    TRY(hipMemset(c->d_gTheta, 0, B * img * 2 * sizeof(long long)));
-    TRY(dalloc(&c->d_tvg, B * img * 2));
-    TRY(dalloc(&c->d_mask, B * img));
-    TRY(dalloc(&c->d_tmm, B * ntiles * 4));
+    TRY(c->mem.alloc_dev(c->d_gmax, B * R * nig, true));
+    TRY(c->mem.alloc_dev(c->d_zero_iwe, B * img));
+    TRY(c->mem.alloc_dev(c->d_Theta, B * img * 2));
+    TRY(c->mem.alloc_dev(c->d_theta_in, B * img * 2));
+    TRY(c->mem.alloc_dev(c->d_gTheta, B * img * 2, true));
+    TRY(c->mem.alloc_dev(c->d_tvg, B * img * 2));
+    TRY(c->mem.alloc_dev(c->d_mask, B * img));
+    TRY(c->mem.alloc_dev(c->d_tmm, B * ntiles * 4));
     const size_t pstride = (size_t)std::max(ntiles, NSPART);
-    TRY(dalloc(&c->d_parts, B * R * pstride));
-    TRY(dalloc(&c->d_gticket, B));
-    TRY(hipMemset(c->d_gticket, 0, B * sizeof(unsigned)));
-    TRY(dalloc(&c->d_divparts, B * R * ntiles));
-    TRY(dalloc(&c->d_g2parts, B * R * nig));
-    TRY(dalloc(&c->d_tvparts, B * ntiles * 3));
-    TRY(dalloc(&c->d_wc, B));
+    TRY(c->mem.alloc_dev(c->d_parts, B * R * pstride));
+    TRY(c->mem.alloc_dev(c->d_gticket, B, true));
+    TRY(c->mem.alloc_dev(c->d_divparts, B * R * ntiles));
+    TRY(c->mem.alloc_dev(c->d_g2parts, B * R * nig));
+    TRY(c->mem.alloc_dev(c->d_tvparts, B * ntiles * 3));
+    TRY(c->mem.alloc_dev(c->d_wc, B));
     {   // one device block and one pinned block: [OutScal x B | grad (B,H,W,2)] -> a single D2H copy per evaluation
         char* blk = nullptr;
-        TRY(hipMalloc(reinterpret_cast<void**>(&blk), B * sizeof(OutScal) + B * img * 2 * sizeof(double)));
+        TRY(c->mem.alloc_dev(blk, B * sizeof(OutScal) + B * img * 2 * sizeof(double)));
         c->d_outs = reinterpret_cast<OutScal*>(blk);
         c->d_grad = reinterpret_cast<double*>(blk + B * sizeof(OutScal));
         char* hblk = nullptr;
-        TRY(hipHostMalloc(reinterpret_cast<void**>(&hblk), B * sizeof(OutScal) + B * img * 2 * sizeof(double), hipHostMallocDefault));
+        TRY(c->mem.alloc_pinned(hblk, B * sizeof(OutScal) + B * img * 2 * sizeof(double)));
         c->h_outs = reinterpret_cast<OutScal*>(hblk);
         c->h_grad = reinterpret_cast<double*>(hblk + B * sizeof(OutScal));
     }
-    TRY(dalloc(&c->d_gth, 2 * B * (size_t)c->coarse_cap));
-    TRY(hipMemset(c->d_gth, 0, 2 * B * (size_t)c->coarse_cap * sizeof(long long)));
-    TRY(dalloc(&c->d_rowtap, (size_t)H));
-    TRY(dalloc(&c->d_coltap, (size_t)W));
-    TRY(dalloc(&c->d_tilerng, (size_t)ntiles));
-    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_theta), B * img * 2 * sizeof(double), hipHostMallocDefault));
-    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_wc), B * sizeof(WinConst), hipHostMallocDefault));
-    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_g11), (size_t)(c->max_items + NXCD) * R * 2 * sizeof(double), hipHostMallocDefault));
-    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_g2), B * R * nig * sizeof(double), hipHostMallocDefault));
-    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_img), B * R * IMGSCAL_N * sizeof(double), hipHostMallocDefault));
-    TRY(hipHostMalloc(reinterpret_cast<void**>(&c->h_tvparts), B * ntiles * 3 * sizeof(double), hipHostMallocDefault));
+    TRY(ensure_coarse(c, 64 * 64 * 2));   // coarse theta up to 64x64 (the pyramid tops out at 16x16); grown on demand
+    TRY(c->mem.alloc_dev(c->d_rowtap, (size_t)H));
+    TRY(c->mem.alloc_dev(c->d_coltap, (size_t)W));
+    TRY(c->mem.alloc_dev(c->d_tilerng, (size_t)ntiles));
+    TRY(c->mem.alloc_pinned(c->h_theta, B * img * 2));
+    TRY(c->mem.alloc_pinned(c->h_wc, B));
+    TRY(c->mem.alloc_pinned(c->h_g11, (size_t)(c->max_items + NXCD) * R * 2));
+    TRY(c->mem.alloc_pinned(c->h_g2, B * R * nig));
+    TRY(c->mem.alloc_pinned(c->h_img, B * R * IMGSCAL_N));
+    TRY(c->mem.alloc_pinned(c->h_tvparts, B * ntiles * 3));
     c->have_events = true;
     for (int k = 0; k < eincm_ctx::GRAD_PIECES; ++k) TRY(hipEventCreateWithFlags(&c->ev_piece[k], hipEventDisableTiming));
     c->ring_size = (flags & EINCM_CF_TIMING_DOMINANT) && !(flags & EINCM_CF_TIMING) ? eincm_ctx::EV_RING : 1;
@@ -1641,26 +1660,24 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     if (c->fp64) {             // the float64 mode's own buffers (eincm_kernels_f64.hip.h): nothing is allocated per evaluation
         const int P = (int)((img + F64_PIX - 1) / F64_PIX);
         c->f64.P = P;
-        TRY(dalloc(&c->f64.acc, B * R * img));
-        TRY(hipMemset(c->f64.acc, 0, B * R * img * sizeof(unsigned long long)));
-        TRY(dalloc(&c->f64.iwe, B * R * img));
-        TRY(dalloc(&c->f64.zero_iwe, B * img));
-        TRY(dalloc(&c->f64.edges, B * R * img));
-        TRY(dalloc(&c->f64.G, B * R * img));
-        TRY(dalloc(&c->f64.sgn, B * R * img));
-        TRY(dalloc(&c->f64.gacc, B * img * 4));
-        TRY(hipMemset(c->f64.gacc, 0, B * img * 4 * sizeof(unsigned long long)));
-        TRY(dalloc(&c->f64.gTh, B * img * 2));
-        TRY(dalloc(&c->f64.T, B * img * 2));
-        TRY(dalloc(&c->f64.grad, B * img * 2));
-        TRY(dalloc(&c->f64.partA, B * R * P * F64_PA));
-        TRY(dalloc(&c->f64.partB, B * R * P * F64_PB));
-        TRY(dalloc(&c->f64.partC, B * R * P * F64_PC));
-        TRY(dalloc(&c->f64.scal, B * R));
-        TRY(hipHostMalloc(reinterpret_cast<void**>(&c->f64.h_scal), B * R * sizeof(F64Scal), hipHostMallocDefault));
-        TRY(dalloc(&c->f64.gmax, B));
-        TRY(dalloc(&c->f64.ishift, B));
-        TRY(dalloc(&c->f64.bad, B));
+        TRY(c->mem.alloc_dev(c->f64.acc, B * R * img, true));
+        TRY(c->mem.alloc_dev(c->f64.iwe, B * R * img));
+        TRY(c->mem.alloc_dev(c->f64.zero_iwe, B * img));
+        TRY(c->mem.alloc_dev(c->f64.edges, B * R * img));
+        TRY(c->mem.alloc_dev(c->f64.G, B * R * img));
+        TRY(c->mem.alloc_dev(c->f64.sgn, B * R * img));
+        TRY(c->mem.alloc_dev(c->f64.gacc, B * img * 4, true));
+        TRY(c->mem.alloc_dev(c->f64.gTh, B * img * 2));
+        TRY(c->mem.alloc_dev(c->f64.T, B * img * 2));
+        TRY(c->mem.alloc_dev(c->f64.grad, B * img * 2));
+        TRY(c->mem.alloc_dev(c->f64.partA, B * R * P * F64_PA));
+        TRY(c->mem.alloc_dev(c->f64.partB, B * R * P * F64_PB));
+        TRY(c->mem.alloc_dev(c->f64.partC, B * R * P * F64_PC));
+        TRY(c->mem.alloc_dev(c->f64.scal, B * R));
+        TRY(c->mem.alloc_pinned(c->f64.h_scal, B * R));
+        TRY(c->mem.alloc_dev(c->f64.gmax, B));
+        TRY(c->mem.alloc_dev(c->f64.ishift, B));
+        TRY(c->mem.alloc_dev(c->f64.bad, B));
     }
     // both event kernels need > 32 KiB... (<= 64 KiB default limit is fine on gfx950, no attribute needed)
 #undef TRY
@@ -2476,14 +2493,8 @@ int eincm_get_count_images(eincm_ctx* c, uint32_t* counts) {
 // ---------------------------------------------------------------------------------------------
 // SURVEY row f-4 (eincm_edges.hip.h, eincm_canny.hip.h)
 // ---------------------------------------------------------------------------------------------
-static int ensure_buf(eincm_ctx* c, DevBuf& b, size_t bytes) {
-    if (b.bytes >= bytes) return EINCM_OK;
-    if (b.p) { (void)hipFree(b.p); b.p = nullptr; b.bytes = 0; }
-    HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.bytes = bytes;
-    return EINCM_OK;
-}
-#define ENSURE(c, buf, bytes) do { const int rc_ = ensure_buf((c), (buf), (bytes)); if (rc_ != EINCM_OK) return rc_; } while (0)
+// The one-shot operators below share c->scratch: each lays out its pieces (Carve), grows the block once, before its first launch, and
+// drains the stream before it returns, so no call finds another's work on the block still enqueued.
 
 // 'warped_xs' / 'warped_ys' of compute_loss_objectives (losses.py:58,90-91) for one window under the last evaluation's theta
 int eincm_get_warped_events(eincm_ctx* c, int window, double* warped_xs, double* warped_ys) {
@@ -2499,8 +2510,8 @@ int eincm_get_warped_events(eincm_ctx* c, int window, double* warped_xs, double*
     int64_t off = 0;
     for (int b = 0; b < window; ++b) off += c->win_events[b];
     const size_t bytes = (size_t)g.R * (size_t)n * sizeof(double);
-    ENSURE(c, c->e_a, 2 * bytes);                              // scratch of the edge routines: free between calls
-    double* dx = static_cast<double*>(c->e_a.p);
+    HIPCHK(c, ensure(c, c->scratch, 2 * bytes));
+    double* dx = carved<double>(c, 0);
     double* dy = dx + (size_t)g.R * (size_t)n;
     const int grid = (int)std::min<int64_t>((n + NT - 1) / NT, 8192);
     hipLaunchKernelGGL(k_warp_events, dim3(grid), dim3(NT), 0, c->stream, g, window, (long long)n, c->d_raw_x + off, c->d_raw_y + off,
@@ -2525,29 +2536,32 @@ int eincm_inv_dist_transform(eincm_ctx* c, const uint8_t* edge_img, int n, int f
     HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const size_t npix = (size_t)H * W, tot = npix * n;
-    ENSURE(c, c->e_u8, tot); ENSURE(c, c->e_g, tot * 4); ENSURE(c, c->e_sq, tot * 4); ENSURE(c, c->e_misc, (size_t)n * 8);
-    if (out) ENSURE(c, c->e_a, tot * 8);
-    uint32_t* d_misc = static_cast<uint32_t*>(c->e_misc.p);           // [n] edge pixel count | [n] max squared distance
-    HIPCHK(c, hipMemcpyAsync(c->e_u8.p, edge_img, tot, hipMemcpyHostToDevice, c->stream));
+    Carve cv;
+    const size_t o_img = cv.add(tot), o_g = cv.add(tot * 4), o_sq = cv.add(tot * 4), o_misc = cv.add((size_t)n * 8), o_out = out ? cv.add(tot * 8) : 0;
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    uint8_t* d_img = carved<uint8_t>(c, o_img);
+    uint32_t* d_g = carved<uint32_t>(c, o_g);
+    int32_t* d_sq = carved<int32_t>(c, o_sq);
+    uint32_t* d_misc = carved<uint32_t>(c, o_misc);                   // [n] edge pixel count | [n] max squared distance
+    double* d_out = carved<double>(c, o_out);                         // (only where out is asked for)
+    HIPCHK(c, hipMemcpyAsync(d_img, edge_img, tot, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(d_misc, 0, (size_t)n * 8, c->stream));
     const int gx = (W + NT - 1) / NT;
-    hipLaunchKernelGGL(k_edt_cols, dim3(gx, n), dim3(NT), 0, c->stream, H, W, static_cast<const uint8_t*>(c->e_u8.p),
-                       static_cast<uint32_t*>(c->e_g.p), d_misc);
-    hipLaunchKernelGGL(k_edt_rows, dim3(gx, H, n), dim3(NT), 0, c->stream, H, W, static_cast<const uint32_t*>(c->e_g.p),
-                       static_cast<int32_t*>(c->e_sq.p), d_misc + n);
+    hipLaunchKernelGGL(k_edt_cols, dim3(gx, n), dim3(NT), 0, c->stream, H, W, (const uint8_t*)d_img, d_g, d_misc);
+    hipLaunchKernelGGL(k_edt_rows, dim3(gx, H, n), dim3(NT), 0, c->stream, H, W, (const uint32_t*)d_g, d_sq, d_misc + n);
     HIPCHK(c, hipGetLastError());
     std::vector<uint32_t> misc((size_t)n * 2);
     HIPCHK(c, hipMemcpyAsync(misc.data(), d_misc, misc.size() * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; ++i)
         if (misc[i] == 0) return fail(c, EINCM_ERR_ARG, "edge image %d has no edge pixel: its distance transform is undefined", i);
-    if (sqdist) HIPCHK(c, hipMemcpyAsync(sqdist, c->e_sq.p, tot * 4, hipMemcpyDeviceToHost, c->stream));
+    if (sqdist) HIPCHK(c, hipMemcpyAsync(sqdist, d_sq, tot * 4, hipMemcpyDeviceToHost, c->stream));
     if (out) {
         const int nb = (int)std::min<size_t>((npix + NT - 1) / NT, 1024);
-        hipLaunchKernelGGL(k_edt_finish, dim3(nb, n), dim3(NT), 0, c->stream, (int64_t)npix, static_cast<const int32_t*>(c->e_sq.p),
-                           d_misc + n, formulation, alpha, d_sat, static_cast<double*>(c->e_a.p));
+        hipLaunchKernelGGL(k_edt_finish, dim3(nb, n), dim3(NT), 0, c->stream, (int64_t)npix, (const int32_t*)d_sq, d_misc + n, formulation,
+                           alpha, d_sat, d_out);
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out, c->e_a.p, tot * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, d_out, tot * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return EINCM_OK;
@@ -2571,16 +2585,19 @@ int eincm_gaussian_blur(eincm_ctx* c, const double* src, int n, double sigma, do
     HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const size_t tot = (size_t)H * W * n;
-    ENSURE(c, c->e_a, tot * 8); ENSURE(c, c->e_b, tot * 8); ENSURE(c, c->e_kern, (size_t)BLUR_MAX_TAPS * 8);
-    HIPCHK(c, hipMemcpyAsync(c->e_kern.p, k.data(), k.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->e_a.p, src, tot * 8, hipMemcpyHostToDevice, c->stream));
+    Carve cv;
+    const size_t o_a = cv.add(tot * 8), o_b = cv.add(tot * 8), o_kern = cv.add((size_t)BLUR_MAX_TAPS * 8);
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    double* d_a = carved<double>(c, o_a);                  // the source, then the result
+    double* d_b = carved<double>(c, o_b);                  // the row pass
+    double* d_kern = carved<double>(c, o_kern);
+    HIPCHK(c, hipMemcpyAsync(d_kern, k.data(), k.size() * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_a, src, tot * 8, hipMemcpyHostToDevice, c->stream));
     const dim3 grid((W + NT - 1) / NT, H, n);
-    hipLaunchKernelGGL(k_blur, grid, dim3(NT), 0, c->stream, H, W, 0, radius, static_cast<const double*>(c->e_kern.p),
-                       static_cast<const double*>(c->e_a.p), static_cast<double*>(c->e_b.p));
-    hipLaunchKernelGGL(k_blur, grid, dim3(NT), 0, c->stream, H, W, 1, radius, static_cast<const double*>(c->e_kern.p),
-                       static_cast<const double*>(c->e_b.p), static_cast<double*>(c->e_a.p));
+    hipLaunchKernelGGL(k_blur, grid, dim3(NT), 0, c->stream, H, W, 0, radius, (const double*)d_kern, (const double*)d_a, d_b);
+    hipLaunchKernelGGL(k_blur, grid, dim3(NT), 0, c->stream, H, W, 1, radius, (const double*)d_kern, (const double*)d_b, d_a);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, c->e_a.p, tot * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, d_a, tot * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // k (host vector) stays alive until here
     return EINCM_OK;
 }
@@ -2606,10 +2623,12 @@ int eincm_canny(eincm_ctx* c, const uint8_t* src, int n, double threshold1, doub
     HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const size_t npix = (size_t)H * W, tot = npix * n;
-    ENSURE(c, c->e_u8, tot); ENSURE(c, c->e_g, tot * 4); ENSURE(c, c->e_sq, tot);
-    uint8_t* d_img = static_cast<uint8_t*>(c->e_u8.p);             // the source, then the edge image
-    int32_t* d_parent = static_cast<int32_t*>(c->e_g.p);
-    uint8_t* d_state = static_cast<uint8_t*>(c->e_sq.p);
+    Carve cv;
+    const size_t o_img = cv.add(tot), o_parent = cv.add(tot * 4), o_state = cv.add(tot);
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    uint8_t* d_img = carved<uint8_t>(c, o_img);                    // the source, then the edge image
+    int32_t* d_parent = carved<int32_t>(c, o_parent);
+    uint8_t* d_state = carved<uint8_t>(c, o_state);
     HIPCHK(c, hipMemcpyAsync(d_img, src, tot, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_canny_nms, dim3((W + CANNY_TW - 1) / CANNY_TW, (H + CANNY_TH - 1) / CANNY_TH, n), dim3(NT), 0, c->stream,
                        H, W, low, high, l2_gradient ? 1 : 0, d_img, d_state, d_parent);
@@ -2734,11 +2753,14 @@ int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_
 
     HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = (size_t)H * W, tot = npix * n;
-    ENSURE(c, c->p_img[0], tot); ENSURE(c, c->p_img[1], tot);
-    if (!T.empty()) {
-        ENSURE(c, c->p_tab, T.size() * 4);
-        HIPCHK(c, hipMemcpyAsync(c->p_tab.p, T.data(), T.size() * 4, hipMemcpyHostToDevice, c->stream));
-    }
+    // two uint8 stacks, and per stage: the per-call tables, the CLAHE LUTs, the unsharp mask's row pass
+    Carve cv;
+    const size_t o_img[2] = {cv.add(tot), cv.add(tot)}, o_tab = cv.add(T.size() * 4);
+    const size_t o_lut = (st & EINCM_PRE_CLAHE) ? cv.add((size_t)n * tx * ty * CLAHE_BINS) : 0;
+    const size_t o_rows = (st & EINCM_PRE_UNSHARP) ? cv.add(tot * 2) : 0;
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    int32_t* d_tab = carved<int32_t>(c, o_tab);
+    if (!T.empty()) HIPCHK(c, hipMemcpyAsync(d_tab, T.data(), T.size() * 4, hipMemcpyHostToDevice, c->stream));
     if (st & EINCM_PRE_NLMEANS) {
         const float hf = (float)p->denoise_h;
         const float hh = hf * hf;
@@ -2757,24 +2779,21 @@ int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_
                 N[a] = wi < 0.001 * fpm ? 0 : (int32_t)wi;
             }
             c->nlm_tw = 0;                                   // invalid until the upload is queued
-            ENSURE(c, c->p_nlm, N.size() * 4);
+            HIPCHK(c, ensure(c, c->p_nlm, N.size()));
             HIPCHK(c, hipMemcpyAsync(c->p_nlm.p, N.data(), N.size() * 4, hipMemcpyHostToDevice, c->stream));
             c->nlm_tw = tw; c->nlm_sw = sw; c->nlm_hh = hh;
         }
     }
-    if (st & EINCM_PRE_CLAHE) ENSURE(c, c->p_lut, (size_t)n * tx * ty * CLAHE_BINS);
-    if (st & EINCM_PRE_UNSHARP) ENSURE(c, c->p_rows, tot * 2);
 
     int cur = 0;
-    uint8_t* img[2] = {static_cast<uint8_t*>(c->p_img[0].p), static_cast<uint8_t*>(c->p_img[1].p)};
-    const int32_t* d_tab = static_cast<const int32_t*>(c->p_tab.p);
+    uint8_t* img[2] = {carved<uint8_t>(c, o_img[0]), carved<uint8_t>(c, o_img[1])};
     HIPCHK(c, hipMemcpyAsync(img[0], src, tot, hipMemcpyHostToDevice, c->stream));
     const dim3 rows_grid((W + NT - 1) / NT, H, n);
     if (st & EINCM_PRE_NLMEANS) {
         const int b = sw / 2 + tw / 2;
         const size_t lds = (size_t)(NLM_TH + 2 * b) * (NLM_TW + 2 * b) * 4;
         const dim3 grid((W + NLM_TW - 1) / NLM_TW, (H + NLM_TH - 1) / NLM_TH, n);
-        const int32_t* tab = static_cast<const int32_t*>(c->p_nlm.p);
+        const int32_t* tab = c->p_nlm.p;
         switch (tw) {
             case 1: hipLaunchKernelGGL(k_nlm<1>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
             case 3: hipLaunchKernelGGL(k_nlm<3>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
@@ -2784,14 +2803,14 @@ int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_
         cur ^= 1;
     }
     if (st & EINCM_PRE_CLAHE) {
-        uint8_t* lut = static_cast<uint8_t*>(c->p_lut.p);
+        uint8_t* lut = carved<uint8_t>(c, o_lut);
         hipLaunchKernelGGL(k_clahe_lut, dim3(tx, ty, n), dim3(NT), 0, c->stream, H, W, clahe_th, clahe_tw, clahe_limit, img[cur], lut);
         hipLaunchKernelGGL(k_clahe_interp, rows_grid, dim3(NT), 0, c->stream, H, W, clahe_th, clahe_tw, tx, ty, lut, img[cur],
                            img[cur ^ 1]);
         cur ^= 1;
     }
     if (st & EINCM_PRE_UNSHARP) {
-        uint16_t* rows = static_cast<uint16_t*>(c->p_rows.p);
+        uint16_t* rows = carved<uint16_t>(c, o_rows);
         hipLaunchKernelGGL(k_unsharp_rows, rows_grid, dim3(NT), 0, c->stream, H, W, un_r, d_tab, img[cur], rows);
         hipLaunchKernelGGL(k_unsharp_cols, rows_grid, dim3(NT), 0, c->stream, H, W, un_r, d_tab, (float)p->sharpen_alpha,
                            (float)p->sharpen_beta, rows, img[cur], img[cur ^ 1]);
@@ -2846,18 +2865,20 @@ int eincm_gt_flow(eincm_ctx* c, const void* gt_x, const void* gt_y, int elem_byt
     std::memcpy(tab.data() + o_frame, step_frame, n_steps * 4);
     std::memcpy(tab.data() + o_num, step_num, n_steps * 8);
     std::memcpy(tab.data() + o_den, step_den, n_steps * 8);
-    ENSURE(c, c->g_frames, 2 * stack); ENSURE(c, c->g_tab, tab_bytes); ENSURE(c, c->g_out, (size_t)n_windows * npix * 16);
-    char* d_frames = static_cast<char*>(c->g_frames.p);
-    const char* d_tab = static_cast<const char*>(c->g_tab.p);
+    Carve cv;                                             // the x and y frame stacks, the step lists, the output
+    const size_t o_frames = cv.add(2 * stack), o_tab = cv.add(tab_bytes), o_out = cv.add((size_t)n_windows * npix * 16);
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    char* d_frames = carved<char>(c, o_frames);
+    char* d_tab = carved<char>(c, o_tab);
     HIPCHK(c, hipMemcpyAsync(d_frames, gt_x, stack, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(d_frames + stack, gt_y, stack, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->g_tab.p, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
     const auto* d_mode = reinterpret_cast<const int32_t*>(d_tab);
     const auto* d_off = reinterpret_cast<const int32_t*>(d_tab + o_off);
     const auto* d_frame = reinterpret_cast<const int32_t*>(d_tab + o_frame);
     const auto* d_num = reinterpret_cast<const double*>(d_tab + o_num);
     const auto* d_den = reinterpret_cast<const double*>(d_tab + o_den);
-    double* d_out = static_cast<double*>(c->g_out.p);
+    double* d_out = carved<double>(c, o_out);
     const unsigned gx = (unsigned)((npix + NT - 1) / NT);
     for (int w0 = 0; w0 < n_windows; w0 += GTF_MAX_WINDOWS_PER_LAUNCH) {
         const dim3 grid(gx, (unsigned)std::min(n_windows - w0, GTF_MAX_WINDOWS_PER_LAUNCH));
@@ -2901,16 +2922,23 @@ int eincm_rectify_events(eincm_ctx* c, const float* rectify_map, const int16_t* 
     HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const int64_t npix = (int64_t)H * W;
-    ENSURE(c, c->d_cnt, 4 * sizeof(unsigned long long));
-    auto* d_cnt = static_cast<unsigned long long*>(c->d_cnt.p);       // [0] refused map entries, [1] events outside the sensor, [2] kept
+    // both phases are laid out before the block is grown, so it cannot move between them: the counters and, where a map comes along,
+    // its float staging; then the chunk's coordinates in and out, the keep bytes, the block counts and offsets
+    const int64_t nblk = (n + RECT_BLOCK - 1) / RECT_BLOCK;
+    Carve cv;
+    const size_t o_cnt = cv.add(4 * sizeof(unsigned long long)), o_fmap = rectify_map ? cv.add((size_t)npix * 8) : 0;
+    const size_t o_x = cv.add((size_t)n * 2), o_y = cv.add((size_t)n * 2), o_rx = cv.add((size_t)n * 2), o_ry = cv.add((size_t)n * 2);
+    const size_t o_keep = cv.add((size_t)n), o_bcnt = cv.add((size_t)nblk * 4), o_boff = cv.add((size_t)nblk * 8);
+    if (rectify_map) c->rect_map_set = false;
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    auto* d_cnt = carved<unsigned long long>(c, o_cnt);               // [0] refused map entries, [1] events outside the sensor, [2] kept
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
     unsigned long long h_cnt[4] = {0, 0, 0, 0};
     if (rectify_map) {
-        c->rect_map_set = false;
-        ENSURE(c, c->r_fmap, (size_t)npix * 8); ENSURE(c, c->r_map, (size_t)npix * 4);
-        HIPCHK(c, hipMemcpyAsync(c->r_fmap.p, rectify_map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, ensure(c, c->r_map, (size_t)npix));
+        HIPCHK(c, hipMemcpyAsync(carved<float2>(c, o_fmap), rectify_map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_rect_map, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, c->stream, npix,
-                           static_cast<const float2*>(c->r_fmap.p), static_cast<uint32_t*>(c->r_map.p), d_cnt);
+                           (const float2*)carved<float2>(c, o_fmap), c->r_map.p, d_cnt);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2918,31 +2946,33 @@ int eincm_rectify_events(eincm_ctx* c, const float* rectify_map, const int16_t* 
         c->rect_map_set = true;
     }
     *n_kept = 0;
-    if (n == 0) return EINCM_OK;
-    const int64_t nblk = (n + RECT_BLOCK - 1) / RECT_BLOCK;
-    ENSURE(c, c->r_x, (size_t)n * 2); ENSURE(c, c->r_y, (size_t)n * 2); ENSURE(c, c->r_rx, (size_t)n * 2); ENSURE(c, c->r_ry, (size_t)n * 2);
-    ENSURE(c, c->r_keep, (size_t)n); ENSURE(c, c->r_cnt, (size_t)nblk * 4); ENSURE(c, c->r_off, (size_t)nblk * 8);
-    HIPCHK(c, hipMemcpyAsync(c->r_x.p, x, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->r_y.p, y, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
-    const auto* d_x = static_cast<const int16_t*>(c->r_x.p);
-    const auto* d_y = static_cast<const int16_t*>(c->r_y.p);
-    const auto* d_map = static_cast<const uint32_t*>(c->r_map.p);
-    hipLaunchKernelGGL(k_rect_count, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, d_x, d_y, d_map, static_cast<uint8_t*>(c->r_keep.p),
-                       static_cast<uint32_t*>(c->r_cnt.p), d_cnt + 1);
-    hipLaunchKernelGGL(k_rect_scan, dim3(1), dim3(RECT_SCAN_NT), 0, c->stream, (int)nblk, static_cast<const uint32_t*>(c->r_cnt.p),
-                       static_cast<int64_t*>(c->r_off.p), reinterpret_cast<int64_t*>(d_cnt + 2));
-    hipLaunchKernelGGL(k_rect_scatter, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, d_x, d_y, d_map,
-                       static_cast<const int64_t*>(c->r_off.p), static_cast<int16_t*>(c->r_rx.p), static_cast<int16_t*>(c->r_ry.p));
+    if (n == 0) { HIPCHK(c, hipStreamSynchronize(c->stream)); return EINCM_OK; }
+    int16_t* d_x = carved<int16_t>(c, o_x);
+    int16_t* d_y = carved<int16_t>(c, o_y);
+    int16_t* d_rx = carved<int16_t>(c, o_rx);
+    int16_t* d_ry = carved<int16_t>(c, o_ry);
+    uint8_t* d_keep = carved<uint8_t>(c, o_keep);
+    uint32_t* d_bcnt = carved<uint32_t>(c, o_bcnt);
+    int64_t* d_boff = carved<int64_t>(c, o_boff);
+    const uint32_t* d_map = c->r_map.p;
+    HIPCHK(c, hipMemcpyAsync(d_x, x, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_y, y, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_rect_count, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, (const int16_t*)d_x, (const int16_t*)d_y, d_map,
+                       d_keep, d_bcnt, d_cnt + 1);
+    hipLaunchKernelGGL(k_rect_scan, dim3(1), dim3(RECT_SCAN_NT), 0, c->stream, (int)nblk, (const uint32_t*)d_bcnt, d_boff,
+                       reinterpret_cast<int64_t*>(d_cnt + 2));
+    hipLaunchKernelGGL(k_rect_scatter, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, (const int16_t*)d_x, (const int16_t*)d_y, d_map,
+                       (const int64_t*)d_boff, d_rx, d_ry);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (h_cnt[1]) return fail(c, EINCM_ERR_ARG, "%llu of %lld events have a coordinate outside the %dx%d sensor", h_cnt[1], (long long)n, H, W);
     const int64_t kept = (int64_t)h_cnt[2];
     if (kept < 0 || kept > n) return fail(c, EINCM_ERR_HIP, "kept count %lld of %lld events", (long long)kept, (long long)n);
-    HIPCHK(c, hipMemcpyAsync(keep, c->r_keep.p, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     if (kept) {                                     // only the kept prefix comes back
-        HIPCHK(c, hipMemcpyAsync(rec_x, c->r_rx.p, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(rec_y, c->r_ry.p, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rec_x, d_rx, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(rec_y, d_ry, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *n_kept = kept;
@@ -2963,16 +2993,20 @@ int eincm_remap_cubic(eincm_ctx* c, const uint8_t* src, int n, int src_h, int sr
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t npix = (int64_t)c->H * c->W;
     const size_t sbytes = (size_t)n * src_h * src_w, dbytes = (size_t)n * npix, tbytes = 1024 * 16 * 4;
-    ENSURE(c, c->d_in, sbytes); ENSURE(c, c->d_out, dbytes); ENSURE(c, c->r_fmap, (size_t)npix * 8); ENSURE(c, c->d_tab, tbytes);
-    // (r_fmap is only staging for a float map: the rounded rectify map lives in r_map and stays)
-    HIPCHK(c, hipMemcpyAsync(c->d_in.p, src, sbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->r_fmap.p, map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_tab.p, table, tbytes, hipMemcpyHostToDevice, c->stream));
+    Carve cv;                  // (the float map is only staged here: the rounded rectify map lives in r_map and stays)
+    const size_t o_in = cv.add(sbytes), o_out = cv.add(dbytes), o_map = cv.add((size_t)npix * 8), o_tab = cv.add(tbytes);
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    uint8_t* d_in = carved<uint8_t>(c, o_in);
+    uint8_t* d_out = carved<uint8_t>(c, o_out);
+    float2* d_map = carved<float2>(c, o_map);
+    int32_t* d_tab = carved<int32_t>(c, o_tab);
+    HIPCHK(c, hipMemcpyAsync(d_in, src, sbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_map, map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tab, table, tbytes, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_remap_cubic, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, c->stream, n, src_h, src_w, npix,
-                       static_cast<const uint8_t*>(c->d_in.p), static_cast<const float2*>(c->r_fmap.p),
-                       static_cast<const int32_t*>(c->d_tab.p), static_cast<uint8_t*>(c->d_out.p));
+                       (const uint8_t*)d_in, (const float2*)d_map, (const int32_t*)d_tab, d_out);
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, c->d_out.p, dbytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, d_out, dbytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return EINCM_OK;
 }
@@ -2984,14 +3018,17 @@ int eincm_flow_decode(eincm_ctx* c, const uint16_t* flow16, int n, double* flow,
     if (n < 1) return fail(c, EINCM_ERR_ARG, "n = %d (>= 1)", n);
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t tot = (int64_t)n * c->H * c->W;
-    ENSURE(c, c->d_in, (size_t)tot * 6); ENSURE(c, c->d_out, (size_t)tot * 17); ENSURE(c, c->d_cnt, 4 * sizeof(unsigned long long));
-    auto* d_cnt = static_cast<unsigned long long*>(c->d_cnt.p);
-    double* d_flow = static_cast<double*>(c->d_out.p);
-    uint8_t* d_valid = static_cast<uint8_t*>(c->d_out.p) + (size_t)tot * 16;
+    Carve cv;
+    const size_t o_in = cv.add((size_t)tot * 6), o_flow = cv.add((size_t)tot * 16), o_valid = cv.add((size_t)tot), o_cnt = cv.add(sizeof(unsigned long long));
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    uint16_t* d_in = carved<uint16_t>(c, o_in);
+    double* d_flow = carved<double>(c, o_flow);
+    uint8_t* d_valid = carved<uint8_t>(c, o_valid);
+    auto* d_cnt = carved<unsigned long long>(c, o_cnt);
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_in.p, flow16, (size_t)tot * 6, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_flow_decode, dim3((unsigned)((tot + NT - 1) / NT)), dim3(NT), 0, c->stream, tot,
-                       static_cast<const uint16_t*>(c->d_in.p), d_flow, d_valid, d_cnt);
+    HIPCHK(c, hipMemcpyAsync(d_in, flow16, (size_t)tot * 6, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_flow_decode, dim3((unsigned)((tot + NT - 1) / NT)), dim3(NT), 0, c->stream, tot, (const uint16_t*)d_in, d_flow,
+                       d_valid, d_cnt);
     HIPCHK(c, hipGetLastError());
     unsigned long long bad = 0;
     HIPCHK(c, hipMemcpyAsync(&bad, d_cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream));
@@ -3027,26 +3064,28 @@ int eincm_flow_encode(eincm_ctx* c, const double* theta, int n, int h, int w, co
     std::memcpy(tab.data() + o_clo, clo.data(), (size_t)W * 4);
     std::memcpy(tab.data() + o_ccnt, ccnt.data(), (size_t)W * 4);
     const size_t thbytes = (size_t)n * h * w * 16, vbytes = valid ? (size_t)n * npix : 0, vofs = (thbytes + 15) & ~(size_t)15;
-    ENSURE(c, c->d_in, vofs + vbytes); ENSURE(c, c->d_out, (size_t)n * npix * 6); ENSURE(c, c->d_tab, tbytes);
-    ENSURE(c, c->d_cnt, 4 * sizeof(unsigned long long));
-    auto* d_cnt = static_cast<unsigned long long*>(c->d_cnt.p);
-    char* d_in = static_cast<char*>(c->d_in.p);
-    const char* d_tab = static_cast<const char*>(c->d_tab.p);
+    Carve cv;
+    const size_t o_in = cv.add(vofs + vbytes), o_out = cv.add((size_t)n * npix * 6), o_tab = cv.add(tbytes), o_cnt = cv.add(sizeof(unsigned long long));
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    char* d_in = carved<char>(c, o_in);
+    uint16_t* d_out = carved<uint16_t>(c, o_out);
+    char* d_tab = carved<char>(c, o_tab);
+    auto* d_cnt = carved<unsigned long long>(c, o_cnt);
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemcpyAsync(d_in, theta, thbytes, hipMemcpyHostToDevice, c->stream));
     if (valid) HIPCHK(c, hipMemcpyAsync(d_in + vofs, valid, vbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_tab.p, tab.data(), tbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tbytes, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_flow_encode, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, H, W, h, w,
                        reinterpret_cast<const double*>(d_in), reinterpret_cast<const int32_t*>(d_tab + o_rlo),
                        reinterpret_cast<const int32_t*>(d_tab + o_rcnt), reinterpret_cast<const double*>(d_tab), rstride,
                        reinterpret_cast<const int32_t*>(d_tab + o_clo), reinterpret_cast<const int32_t*>(d_tab + o_ccnt),
                        reinterpret_cast<const double*>(d_tab + o_cw), cstride,
                        valid ? reinterpret_cast<const uint8_t*>(d_in + vofs) : (const uint8_t*)nullptr,
-                       static_cast<uint16_t*>(c->d_out.p), d_cnt);
+                       d_out, d_cnt);
     HIPCHK(c, hipGetLastError());
     unsigned long long bad = 0;
     HIPCHK(c, hipMemcpyAsync(&bad, d_cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_out.p, (size_t)n * npix * 6, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n * npix * 6, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));          // tab (host vector) stays alive until here
     *n_bad = (int64_t)bad;
     if (bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a flow that is not finite or encodes outside [0, 65536)", bad);
@@ -3094,8 +3133,8 @@ int eincm_tiled_objectives(eincm_ctx* c, int tile_h, int tile_w, eincm_tiled_out
     const int ntx = g.W / tile_w, nty = g.H / tile_h, ntl = ntx * nty;
     const int nb = std::min((g.H * g.W + NT - 1) / NT, 256);
     const size_t n_t = (size_t)g.B * g.R * ntl * 3, n_p = (size_t)g.B * g.R * nb * 3;
-    ENSURE(c, c->e_out, (n_t + n_p) * 8);
-    double* d_t = static_cast<double*>(c->e_out.p);
+    HIPCHK(c, ensure(c, c->scratch, (n_t + n_p) * 8));
+    double* d_t = carved<double>(c, 0);
     double* d_p = d_t + n_t;
     g.wmask = ~0ull;
     hipLaunchKernelGGL(k_tiled, dim3(ntl, g.R, g.B), dim3(NT), 0, c->stream, g, tile_h, tile_w, ntx, c->d_iwe, c->d_edges, c->d_parts, d_t);
@@ -3147,6 +3186,13 @@ int eincm_get_host_profile(eincm_ctx* c, double* us, int64_t* n_evals, int reset
     for (int i = 0; i < EINCM_N_HOST_PHASES; ++i) us[i] = c->hp_us[i];
     *n_evals = c->hp_n;
     if (reset) { for (double& v : c->hp_us) v = 0.0; c->hp_n = 0; }
+    return EINCM_OK;
+}
+
+int eincm_get_memory(eincm_ctx* c, int64_t out[4]) {
+    if (!c || !out) return EINCM_ERR_ARG;
+    out[0] = (int64_t)c->mem.dev_bytes; out[1] = (int64_t)c->mem.pinned_bytes;
+    out[2] = (int64_t)(c->mem.dev.size() + c->mem.pinned.size()); out[3] = (int64_t)c->scratch.n;
     return EINCM_OK;
 }
 
@@ -3220,7 +3266,7 @@ static BfgsAlpha bfgs_alpha(const eincm_ctx* c, unsigned long long m, const doub
 
 static int bfgs_launch_reduce(eincm_ctx* c, unsigned long long m, const double* gsrc) {
     auto& s = c->bfgs;
-    hipLaunchKernelGGL(k_bfgs_reduce, dim3((unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, m, gsrc, s.Gt, (const double*)s.P, s.h_red);
+    hipLaunchKernelGGL(k_bfgs_reduce, dim3((unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, m, gsrc, s.Gt, (const double*)s.P, s.h_red.p);
     HIPCHK(c, hipGetLastError());
     return EINCM_OK;
 }
@@ -3235,37 +3281,23 @@ int eincm_bfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const ui
     HIPCHK(c, hipSetDevice(c->device));
     auto& s = c->bfgs;
     const int n = (int)n64, B = c->g.B;
-    if (!s.h_scal) {
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.h_scal), (size_t)c->maxB * BFGS_NS * sizeof(double), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc(reinterpret_cast<void**>(&s.h_red), (size_t)c->maxB * 2 * sizeof(double), hipHostMallocDefault));
-        memset(s.h_scal, 0, (size_t)c->maxB * BFGS_NS * sizeof(double));
-        memset(s.h_red, 0, (size_t)c->maxB * 2 * sizeof(double));
-    }
+    s.begun = false;
+    HIPCHK(c, ensure(c, s.h_scal, (size_t)c->maxB * BFGS_NS, true));
+    HIPCHK(c, ensure(c, s.h_red, (size_t)c->maxB * 2, true));
     const size_t need_vec = (size_t)B * n, need_H = need_vec * n;
     const bool reshaped = n != s.n || B != s.B;
-    if (need_vec > s.cap_vec) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (s.vec) { (void)hipFree(s.vec); s.vec = nullptr; s.cap_vec = 0; }
-        HIPCHK(c, dalloc(&s.vec, 8 * need_vec));
-        s.cap_vec = need_vec;
-        double** v[8] = {&s.X, &s.G, &s.P, &s.Xt, &s.Gt, &s.S, &s.Y, &s.Hy};
-        for (int k = 0; k < 8; ++k) *v[k] = s.vec + (size_t)k * s.cap_vec;
-    }
-    if (need_H > s.cap_H) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (s.H) { (void)hipFree(s.H); s.H = nullptr; s.cap_H = 0; }
-        HIPCHK(c, dalloc(&s.H, need_H));
-        s.cap_H = need_H;
-    }
-    s.begun = false;
+    HIPCHK(c, ensure(c, s.vec, 8 * need_vec));
+    HIPCHK(c, ensure(c, s.H, need_H));
+    double** v[8] = {&s.X, &s.G, &s.P, &s.Xt, &s.Gt, &s.S, &s.Y, &s.Hy};
+    for (int k = 0; k < 8; ++k) *v[k] = s.vec.p + (size_t)k * (s.vec.n / 8);
     if (reshaped) {          // the rows of windows outside this call's mask must hold finite numbers in the new layout
-        HIPCHK(c, hipMemsetAsync(s.vec, 0, 8 * s.cap_vec * sizeof(double), c->stream));
-        HIPCHK(c, hipMemsetAsync(s.H, 0, s.cap_H * sizeof(double), c->stream));
-        memset(s.h_scal, 0, (size_t)c->maxB * BFGS_NS * sizeof(double));
+        HIPCHK(c, hipMemsetAsync(s.vec.p, 0, s.vec.n * sizeof(double), c->stream));
+        HIPCHK(c, hipMemsetAsync(s.H.p, 0, s.H.n * sizeof(double), c->stream));
+        memset(s.h_scal.p, 0, s.h_scal.n * sizeof(double));
     }
     s.n = n; s.h = h; s.w = w; s.B = B;
     const unsigned long long m = bfgs_mask(c, active);
-    hipLaunchKernelGGL(k_bfgs_begin, dim3((unsigned)((n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)B), dim3(BFGS_NT), 0, c->stream, n, m, s.H, s.P, s.G);
+    hipLaunchKernelGGL(k_bfgs_begin, dim3((unsigned)((n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)B), dim3(BFGS_NT), 0, c->stream, n, m, s.H.p, s.P, s.G);
     HIPCHK(c, hipGetLastError());
     for (int b = 0; b < B; ) {                        // x0 of the mask's windows, one copy per run of them
         if (!((m >> b) & 1ull)) { ++b; continue; }
@@ -3275,7 +3307,7 @@ int eincm_bfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const ui
         for (int k = b; k < e; ++k) {                  // max|x0| bounds |theta| of the first evaluation
             double xm = 0.0;
             for (int i = 0; i < n; ++i) { const double a = std::fabs(x0_host[(size_t)k * n + i]); if (a > xm || a != a) xm = a; }
-            double* o = s.h_scal + (size_t)k * BFGS_NS;
+            double* o = s.h_scal.p + (size_t)k * BFGS_NS;
             for (int q = 0; q < BFGS_NS; ++q) o[q] = 0.0;
             o[EINCM_BFGS_S_XMAX] = xm;
         }
@@ -3308,7 +3340,7 @@ int eincm_bfgs_reduce(eincm_ctx* c, const uint8_t* active, double* dphi, double*
     const unsigned long long m = bfgs_mask(c, active);
     if (const int rc = bfgs_launch_reduce(c, m, nullptr)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int b = 0; b < c->bfgs.B; ++b) if ((m >> b) & 1ull) { dphi[b] = c->bfgs.h_red[2 * b]; gmax[b] = c->bfgs.h_red[2 * b + 1]; }
+    for (int b = 0; b < c->bfgs.B; ++b) if ((m >> b) & 1ull) { dphi[b] = c->bfgs.h_red.p[2 * b]; gmax[b] = c->bfgs.h_red.p[2 * b + 1]; }
     return EINCM_OK;
 }
 
@@ -3322,7 +3354,7 @@ int eincm_bfgs_eval(eincm_ctx* c, const eincm_params* p, const double* alpha, co
     const unsigned long long m = bfgs_mask(c, active);
     double vmax = 0.0;                             // max|X| + |a| max|P| bounds |theta| at the trial point: selects the LDS window capacity
     for (int b = 0; b < s.B; ++b) if ((m >> b) & 1ull) {
-        const double* o = s.h_scal + (size_t)b * BFGS_NS;
+        const double* o = s.h_scal.p + (size_t)b * BFGS_NS;
         const double v = o[EINCM_BFGS_S_XMAX] + std::fabs(alpha[b]) * o[EINCM_BFGS_S_PMAX];
         if (!(v <= vmax)) vmax = v;                // (a NaN ends up in vmax: unknown)
     }
@@ -3340,7 +3372,7 @@ int eincm_bfgs_eval(eincm_ctx* c, const eincm_params* p, const double* alpha, co
     if (rc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rc; }
     rc = eval_end_collect(c, value, nullptr, nullptr);             // the one synchronisation
     if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
-    for (int b = 0; b < s.B; ++b) if ((m >> b) & 1ull) { dphi[b] = s.h_red[2 * b]; gmax[b] = s.h_red[2 * b + 1]; }
+    for (int b = 0; b < s.B; ++b) if ((m >> b) & 1ull) { dphi[b] = s.h_red.p[2 * b]; gmax[b] = s.h_red.p[2 * b + 1]; }
     return rc;
 }
 
@@ -3354,7 +3386,7 @@ int eincm_bfgs_trial_ptrs(eincm_ctx* c, void** xt_dptr, void** gt_dptr, int64_t*
 int eincm_bfgs_state_ptrs(eincm_ctx* c, void** x_dptr, void** g_dptr, void** p_dptr, void** hess_inv_dptr, int* n_windows, int* n) {
     if (!c || !x_dptr || !g_dptr || !p_dptr || !hess_inv_dptr || !n_windows || !n) return EINCM_ERR_ARG;
     if (const int rc = bfgs_ready(c, "eincm_bfgs_state_ptrs", true)) return rc;
-    *x_dptr = c->bfgs.X; *g_dptr = c->bfgs.G; *p_dptr = c->bfgs.P; *hess_inv_dptr = c->bfgs.H; *n_windows = c->bfgs.B; *n = c->bfgs.n;
+    *x_dptr = c->bfgs.X; *g_dptr = c->bfgs.G; *p_dptr = c->bfgs.P; *hess_inv_dptr = c->bfgs.H.p; *n_windows = c->bfgs.B; *n = c->bfgs.n;
     return EINCM_OK;
 }
 
@@ -3376,18 +3408,18 @@ int eincm_bfgs_accept(eincm_ctx* c, const double* alpha, const uint8_t* accept_m
         const dim3 grid((unsigned)((s.n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)s.B);
         if (upd) {
             hipLaunchKernelGGL(k_bfgs_hy, grid, dim3(BFGS_NT), (size_t)s.n * sizeof(double), c->stream, s.n, upd, bfgs_alpha(c, upd, alpha),
-                               (const double*)s.H, (const double*)s.G, (const double*)s.Gt, (const double*)s.P, s.S, s.Y, s.Hy);
+                               (const double*)s.H.p, (const double*)s.G, (const double*)s.Gt, (const double*)s.P, s.S, s.Y, s.Hy);
             HIPCHK(c, hipGetLastError());
         }
-        hipLaunchKernelGGL(k_bfgs_update, grid, dim3(BFGS_NT), (size_t)3 * s.n * sizeof(double), c->stream, s.n, act, upd, init, s.H,
+        hipLaunchKernelGGL(k_bfgs_update, grid, dim3(BFGS_NT), (size_t)3 * s.n * sizeof(double), c->stream, s.n, act, upd, init, s.H.p,
                            (const double*)s.S, (const double*)s.Y, (const double*)s.Hy, s.X, (const double*)s.Xt, s.G, (const double*)s.Gt, s.P);
         HIPCHK(c, hipGetLastError());
         hipLaunchKernelGGL(k_bfgs_scalars, dim3((unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, act, (const double*)s.X, (const double*)s.G,
-                           (const double*)s.P, (const double*)s.S, (const double*)s.Y, (const double*)s.Hy, upd, s.h_scal);
+                           (const double*)s.P, (const double*)s.S, (const double*)s.Y, (const double*)s.Hy, upd, s.h_scal.p);
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    memcpy(scalars_out, s.h_scal, (size_t)s.B * BFGS_NS * sizeof(double));
+    memcpy(scalars_out, s.h_scal.p, (size_t)s.B * BFGS_NS * sizeof(double));
     return EINCM_OK;
 }
 
@@ -3399,7 +3431,7 @@ int eincm_bfgs_fetch(eincm_ctx* c, double* x, double* g, double* hess_inv) {
     const size_t nv = (size_t)s.B * s.n * sizeof(double);
     if (x) HIPCHK(c, hipMemcpyAsync(x, s.X, nv, hipMemcpyDeviceToHost, c->stream));
     if (g) HIPCHK(c, hipMemcpyAsync(g, s.G, nv, hipMemcpyDeviceToHost, c->stream));
-    if (hess_inv) HIPCHK(c, hipMemcpyAsync(hess_inv, s.H, nv * s.n, hipMemcpyDeviceToHost, c->stream));
+    if (hess_inv) HIPCHK(c, hipMemcpyAsync(hess_inv, s.H.p, nv * s.n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return EINCM_OK;
 }

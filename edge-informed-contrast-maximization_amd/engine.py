@@ -177,6 +177,14 @@ def make_preprocess_params(shape, stages='all', **kw):
     return p
 
 
+class Memory(NamedTuple):
+    """Engine.memory(): what the context holds (eincm_get_memory).  scratch_bytes is part of device_bytes."""
+    device_bytes: int
+    pinned_bytes: int
+    allocations: int
+    scratch_bytes: int
+
+
 class GtFlowPlan(NamedTuple):
     """One window of eincm_gt_flow, made by evaluation.gt_flow_plan.  mode: 'direct' or 'propagate'; steps: a
     tuple of (frame, num, den).  A direct window has one step, out = g[frame] * num / den; a propagate window moves every pixel through
@@ -996,6 +1004,13 @@ class Engine:
         out = (C.c_double * len(self.LAUNCH_POLICY_NAMES))()
         self._check(self._lib.eincm_get_launch_policy(self._ctx, out))
         return dict(zip(self.LAUNCH_POLICY_NAMES, (float(v) for v in out)))
+
+    def memory(self):
+        """Diagnostic (eincm_get_memory): the context's live device and pinned bytes, its allocations and its scratch block.  Equal
+        before and after a call: the call allocated nothing.  No HIP call."""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.eincm_get_memory(self._ctx, out))
+        return Memory(*(int(v) for v in out))
 
     def set_timed_kernels(self, splat=True, gather=True):
         """timing='dominant' contexts: which event kernels carry HIP timing events from the next evaluation on."""

@@ -27,7 +27,7 @@ extern "C" {
                                 * 4: eincm_loss_grad_masked, eincm_set_device_results / eincm_finish_launch / eincm_grad_device_ptr / eincm_finish_collect, eincm_get_host_profile;
                                * 5: eincm_get_warped_events, eincm_loss_grad_device, eincm_loss_grad_masked_async, eincm_set_timing_period;
                                * 6: eincm_get_launch_policy; added since without a new version: eincm_rectify_events, eincm_remap_cubic, eincm_flow_decode,
-                               *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM) */
+                               *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -283,6 +283,11 @@ int eincm_get_host_profile(eincm_ctx* ctx, double* us /* EINCM_N_HOST_PHASES */,
 #define EINCM_LP_SPLAT_SHORT 12      /* last evaluation: k_splat walked its short list */
 #define EINCM_N_LAUNCH_POLICY 13
 int eincm_get_launch_policy(eincm_ctx* ctx, double* out /* EINCM_N_LAUNCH_POLICY */);
+
+/* What the context holds right now: [0] bytes of device memory, [1] bytes of pinned host memory, [2] the number of live allocations
+ * behind the two, [3] bytes of the scratch block the one-shot operators share (part of [0]).  Read from the context's own books: no
+ * HIP call.  Two reads around a call that are equal show that the call allocated nothing. */
+int eincm_get_memory(eincm_ctx* ctx, int64_t out[4]);
 /* sums of the per-evaluation timings since the last reset, and how many evaluations they cover (a bench reads them once after
  * its timed loop instead of calling eincm_get_timings inside it) */
 int eincm_get_timings_total(eincm_ctx* ctx, eincm_timings* sum, int64_t* n_evals, int reset);
