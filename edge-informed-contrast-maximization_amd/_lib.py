@@ -81,6 +81,14 @@ GTF_MODES = {'direct': GTF_DIRECT, 'propagate': GTF_PROPAGATE}
 EDT_FORMULATIONS = {'exponential': 0, 'linear': 1, 'linear-bound': 2, 'logarithmic': 3}
 
 
+FLOW_ERROR_THRESHOLDS = (1, 2, 3, 5, 10, 20)          # the N of A{N}PE (flow_eval.py:67-73)
+
+
+class FlowErrorOut(C.Structure):
+    _fields_ = [('n_ee', C.c_int64), ('n_pred', C.c_int64), ('n_gt', C.c_int64), ('n_over', C.c_int64 * 6),
+                ('sum_ee', C.c_double), ('sum_ree', C.c_double), ('aee', C.c_double), ('aree', C.c_double), ('anpe', C.c_double * 6)]
+
+
 class Timings(C.Structure):
     _fields_ = [('ms', C.c_float * N_STAGES), ('total_ms', C.c_float)]
 
@@ -152,6 +160,9 @@ SIGNATURES = [
     ('eincm_remap_cubic', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('eincm_flow_decode', C.c_int, [_P, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
     ('eincm_flow_encode', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]),
+    # flow errors of a batch of thetas against staged ground truth
+    ('eincm_flow_eval_stage', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ('eincm_flow_errors', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FlowErrorOut), C.c_void_p]),
     # BFGS with its state in HBM (raw addresses: called once per lockstep tick)
     ('eincm_bfgs_begin', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     ('eincm_bfgs_eval', C.c_int, [_P, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -29,6 +29,7 @@
 #include "eincm_preprocess.hip.h"
 #include "eincm_gtflow.hip.h"
 #include "eincm_dsec.hip.h"
+#include "eincm_floweval.hip.h"
 #include "eincm_bfgs.hip.h"
 
 using namespace eincm;
@@ -266,7 +267,7 @@ struct eincm_ctx {
     Grow<double, true> h_ovals;    // (maxB,maxR,2) pinned: contrast and signed correlation of every image (k_obj_grad), allocated on first use
 
     // The one scratch block of the one-shot operators (edge smoothing, Canny, preprocessing, ground-truth flow, the DSEC data path,
-    // warped events, tiled objectives).  An operator lays out its pieces (Carve), grows the block once and drains the stream before
+    // warped events, tiled objectives, the transients of the flow-error evaluation).  An operator lays out its pieces (Carve), grows the block once and drains the stream before
     // it returns, so nothing in here outlives a call.  What a later call reads has a buffer of its own:
     Grow<char> scratch;
     // the NL-means weight table of eincm_preprocess_image, kept for the (template, search, h^2) it was built for
@@ -277,6 +278,11 @@ struct eincm_ctx {
     // the rounded rectify map of eincm_rectify_events packed as int16 pairs, kept from the call that handed a map over
     Grow<uint32_t> r_map;
     bool rect_map_set = false;
+    // the staged flow evaluation of eincm_flow_eval_stage: [GT flow (n, H, W) double2 | flag bytes (n, H, W)],
+    // kept from one staging to the next; every eincm_flow_errors reads it
+    Grow<char> f_eval;
+    int fe_n = 0;                  // windows of the staged flow evaluation (0: none)
+    std::vector<int64_t> fe_ngt;   // (fe_n) GT-valid pixels of every window
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
@@ -409,6 +415,12 @@ hipError_t ensure_coarse(eincm_ctx* c, size_t cells) {
     if (const hipError_t e = ensure(c, c->d_gth, (size_t)2 * c->maxB * cells, true)) return e;
     c->coarse_cap = (int64_t)(c->d_gth.n / ((size_t)2 * c->maxB));
     return hipSuccess;
+}
+
+// The one-shot operators that must not run beside an evaluation begun and not yet collected (its kernels may be on the stream)
+int not_in_flight(eincm_ctx* c, const char* who) {
+    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
+    return EINCM_OK;
 }
 
 // One piece of the scratch block (Carve::add gave its offset)
@@ -3040,6 +3052,34 @@ int eincm_flow_decode(eincm_ctx* c, const uint16_t* flow16, int n, double* flow,
     return EINCM_OK;
 }
 
+// The tap tables of a (h, w) -> (H, W) resampling as k_flow_encode and k_flow_error read them, packed for one upload:
+// row weights | column weights | rlo | rcnt | clo | ccnt
+struct TapTables {
+    std::vector<char> tab;
+    size_t o_cw = 0, o_rlo = 0, o_rcnt = 0, o_clo = 0, o_ccnt = 0;
+    int rstride = 1, cstride = 1;
+    static const int32_t* i32(const char* base, size_t off) { return reinterpret_cast<const int32_t*>(base + off); }
+    static const double* f64(const char* base, size_t off) { return reinterpret_cast<const double*>(base + off); }
+};
+
+static void build_taps(int h, int w, int H, int W, int method, TapTables& t) {
+    std::vector<double> AH, AW, rwt, cwt;
+    std::vector<int32_t> rlo, rcnt, clo, ccnt;
+    resample_matrix(h, H, method, AH);
+    resample_matrix(w, W, method, AW);
+    t.rstride = resample_runs(AH, h, H, rlo, rcnt, rwt);
+    t.cstride = resample_runs(AW, w, W, clo, ccnt, cwt);
+    t.o_cw = rwt.size() * 8; t.o_rlo = t.o_cw + cwt.size() * 8; t.o_rcnt = t.o_rlo + (size_t)H * 4; t.o_clo = t.o_rcnt + (size_t)H * 4;
+    t.o_ccnt = t.o_clo + (size_t)W * 4;
+    t.tab.resize(t.o_ccnt + (size_t)W * 4);
+    std::memcpy(t.tab.data(), rwt.data(), rwt.size() * 8);
+    std::memcpy(t.tab.data() + t.o_cw, cwt.data(), cwt.size() * 8);
+    std::memcpy(t.tab.data() + t.o_rlo, rlo.data(), (size_t)H * 4);
+    std::memcpy(t.tab.data() + t.o_rcnt, rcnt.data(), (size_t)H * 4);
+    std::memcpy(t.tab.data() + t.o_clo, clo.data(), (size_t)W * 4);
+    std::memcpy(t.tab.data() + t.o_ccnt, ccnt.data(), (size_t)W * 4);
+}
+
 // dsec_npz_to_png.py:84-96 for a batch of theta: bilinear scale_and_translate to the sensor and the 16-bit code, in one kernel.
 int eincm_flow_encode(eincm_ctx* c, const double* theta, int n, int h, int w, const uint8_t* valid, uint16_t* out, int64_t* n_bad) {
     if (!c) return EINCM_ERR_ARG;
@@ -3048,21 +3088,9 @@ int eincm_flow_encode(eincm_ctx* c, const double* theta, int n, int h, int w, co
     HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const int64_t npix = (int64_t)H * W;
-    std::vector<double> AH, AW, rwt, cwt;
-    std::vector<int32_t> rlo, rcnt, clo, ccnt;
-    resample_matrix(h, H, EINCM_METHOD_BILINEAR, AH);
-    resample_matrix(w, W, EINCM_METHOD_BILINEAR, AW);
-    const int rstride = resample_runs(AH, h, H, rlo, rcnt, rwt), cstride = resample_runs(AW, w, W, clo, ccnt, cwt);
-    // one upload: row weights | column weights | rlo | rcnt | clo | ccnt
-    const size_t o_cw = rwt.size() * 8, o_rlo = o_cw + cwt.size() * 8, o_rcnt = o_rlo + (size_t)H * 4, o_clo = o_rcnt + (size_t)H * 4,
-                 o_ccnt = o_clo + (size_t)W * 4, tbytes = o_ccnt + (size_t)W * 4;
-    std::vector<char> tab(tbytes);
-    std::memcpy(tab.data(), rwt.data(), rwt.size() * 8);
-    std::memcpy(tab.data() + o_cw, cwt.data(), cwt.size() * 8);
-    std::memcpy(tab.data() + o_rlo, rlo.data(), (size_t)H * 4);
-    std::memcpy(tab.data() + o_rcnt, rcnt.data(), (size_t)H * 4);
-    std::memcpy(tab.data() + o_clo, clo.data(), (size_t)W * 4);
-    std::memcpy(tab.data() + o_ccnt, ccnt.data(), (size_t)W * 4);
+    TapTables T;
+    build_taps(h, w, H, W, EINCM_METHOD_BILINEAR, T);
+    const size_t tbytes = T.tab.size();
     const size_t thbytes = (size_t)n * h * w * 16, vbytes = valid ? (size_t)n * npix : 0, vofs = (thbytes + 15) & ~(size_t)15;
     Carve cv;
     const size_t o_in = cv.add(vofs + vbytes), o_out = cv.add((size_t)n * npix * 6), o_tab = cv.add(tbytes), o_cnt = cv.add(sizeof(unsigned long long));
@@ -3074,21 +3102,129 @@ int eincm_flow_encode(eincm_ctx* c, const double* theta, int n, int h, int w, co
     HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
     HIPCHK(c, hipMemcpyAsync(d_in, theta, thbytes, hipMemcpyHostToDevice, c->stream));
     if (valid) HIPCHK(c, hipMemcpyAsync(d_in + vofs, valid, vbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tbytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_tab, T.tab.data(), tbytes, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_flow_encode, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, H, W, h, w,
-                       reinterpret_cast<const double*>(d_in), reinterpret_cast<const int32_t*>(d_tab + o_rlo),
-                       reinterpret_cast<const int32_t*>(d_tab + o_rcnt), reinterpret_cast<const double*>(d_tab), rstride,
-                       reinterpret_cast<const int32_t*>(d_tab + o_clo), reinterpret_cast<const int32_t*>(d_tab + o_ccnt),
-                       reinterpret_cast<const double*>(d_tab + o_cw), cstride,
+                       reinterpret_cast<const double*>(d_in), T.i32(d_tab, T.o_rlo), T.i32(d_tab, T.o_rcnt),
+                       T.f64(d_tab, 0), T.rstride, T.i32(d_tab, T.o_clo), T.i32(d_tab, T.o_ccnt),
+                       T.f64(d_tab, T.o_cw), T.cstride,
                        valid ? reinterpret_cast<const uint8_t*>(d_in + vofs) : (const uint8_t*)nullptr,
                        d_out, d_cnt);
     HIPCHK(c, hipGetLastError());
     unsigned long long bad = 0;
     HIPCHK(c, hipMemcpyAsync(&bad, d_cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n * npix * 6, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // tab (host vector) stays alive until here
+    HIPCHK(c, hipStreamSynchronize(c->stream));          // T (host vector) stays alive until here
     *n_bad = (int64_t)bad;
     if (bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a flow that is not finite or encodes outside [0, 65536)", bad);
+    return EINCM_OK;
+}
+
+// ---- flow errors of a batch of thetas against staged ground truth (eincm_floweval.hip.h) ----
+// Stage once: the GT flow goes straight into the context's f_eval block, the evaluation events mark their pixels, k_fe_flags folds the
+// event plane, the optional error mask and the GT mask into one flag byte per pixel.  The events, the mask and the counters are
+// transients of the shared scratch.
+int eincm_flow_eval_stage(eincm_ctx* c, int n_windows, const double* gt_flow, const int64_t* n_events, const int16_t* xs, const int16_t* ys,
+                          const uint8_t* eval_mask) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!gt_flow || !n_events || !xs || !ys) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (n_windows < 1 || n_windows > 65535) return fail(c, EINCM_ERR_ARG, "n_windows = %d (1..65535)", n_windows);
+    int64_t tot = 0, most = 0;
+    for (int b = 0; b < n_windows; ++b) {
+        if (n_events[b] < 0 || n_events[b] > (int64_t)1 << 36) return fail(c, EINCM_ERR_ARG, "window %d: n_events = %lld", b, (long long)n_events[b]);
+        tot += n_events[b];
+        most = std::max(most, n_events[b]);
+    }
+    if (const int rc = not_in_flight(c, "eincm_flow_eval_stage")) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int H = c->H, W = c->W, n = n_windows;
+    const size_t npix = (size_t)H * W, plane = (size_t)n * npix;
+    c->fe_n = 0;                                          // whatever was staged is gone from here on
+    std::vector<int64_t> off((size_t)n + 1, 0);
+    for (int b = 0; b < n; ++b) off[b + 1] = off[b] + n_events[b];
+    Carve cv;
+    const size_t o_off = cv.add(off.size() * 8), o_x = cv.add((size_t)tot * 2), o_y = cv.add((size_t)tot * 2);
+    const size_t o_mask = eval_mask ? cv.add(plane) : 0, o_cnt = cv.add(((size_t)n + 1) * 8);
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    HIPCHK(c, ensure(c, c->f_eval, plane * 17));
+    double2* d_gt = reinterpret_cast<double2*>(c->f_eval.p);
+    uint8_t* d_flags = reinterpret_cast<uint8_t*>(c->f_eval.p + plane * 16);
+    int64_t* d_off = carved<int64_t>(c, o_off);
+    int16_t* d_x = carved<int16_t>(c, o_x);
+    int16_t* d_y = carved<int16_t>(c, o_y);
+    const uint8_t* d_mask = eval_mask ? carved<uint8_t>(c, o_mask) : nullptr;
+    auto* d_cnt = carved<unsigned long long>(c, o_cnt);   // [n] GT-valid pixels per window | [1] events outside the sensor
+    HIPCHK(c, hipMemsetAsync(d_cnt, 0, ((size_t)n + 1) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_flags, 0, plane, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_gt, gt_flow, plane * 16, hipMemcpyHostToDevice, c->stream));
+    if (eval_mask) HIPCHK(c, hipMemcpyAsync(carved<uint8_t>(c, o_mask), eval_mask, plane, hipMemcpyHostToDevice, c->stream));
+    if (tot > 0) {
+        HIPCHK(c, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_x, xs, (size_t)tot * 2, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_y, ys, (size_t)tot * 2, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(k_fe_events, dim3((unsigned)((most + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, H, W,
+                           (const int64_t*)d_off, (const int16_t*)d_x, (const int16_t*)d_y, d_flags, d_cnt + n);
+    }
+    hipLaunchKernelGGL(k_fe_flags, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, (int)npix,
+                       (const double2*)d_gt, d_mask, d_flags, d_cnt);
+    HIPCHK(c, hipGetLastError());
+    std::vector<unsigned long long> cnt((size_t)n + 1, 0);
+    HIPCHK(c, hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));           // off (host vector) stays alive until here
+    if (cnt[n]) return fail(c, EINCM_ERR_ARG, "%llu of %lld evaluation events have a coordinate outside the %dx%d sensor", cnt[n], (long long)tot, H, W);
+    c->fe_ngt.assign(cnt.begin(), cnt.begin() + n);
+    c->fe_n = n;
+    return EINCM_OK;
+}
+
+// Evaluate many: only theta goes up.  One launch of k_flow_error, FE_PARTS partials per window come down and are added in index order.
+int eincm_flow_errors(eincm_ctx* c, const double* theta, int h, int w, int method, eincm_flow_error_out* out, double* ee_map) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!theta || !out) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (method < 0 || method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", method);
+    if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
+    if (h > c->H || w > c->W) return fail(c, EINCM_ERR_ARG, "theta (%d,%d,2) is finer than the %dx%d sensor", h, w, c->H, c->W);
+    if (const int rc = not_in_flight(c, "eincm_flow_errors")) return rc;
+    if (c->fe_n < 1) return fail(c, EINCM_ERR_STATE, "eincm_flow_errors called before a successful eincm_flow_eval_stage");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int H = c->H, W = c->W, n = c->fe_n;
+    const size_t npix = (size_t)H * W, plane = (size_t)n * npix;
+    const bool full = h == H && w == W;
+    TapTables T;
+    if (!full) build_taps(h, w, H, W, method, T);
+    const size_t thbytes = (size_t)n * h * w * 16, pbytes = (size_t)n * FE_PARTS * sizeof(FlowErrPart);
+    Carve cv;
+    const size_t o_th = cv.add(thbytes), o_tab = cv.add(T.tab.size()), o_parts = cv.add(pbytes), o_map = ee_map ? cv.add(plane * 8) : 0;
+    HIPCHK(c, ensure(c, c->scratch, cv.total));
+    double2* d_th = carved<double2>(c, o_th);
+    char* d_tab = carved<char>(c, o_tab);
+    FlowErrPart* d_parts = carved<FlowErrPart>(c, o_parts);
+    double* d_map = ee_map ? carved<double>(c, o_map) : nullptr;
+    HIPCHK(c, hipMemcpyAsync(d_th, theta, thbytes, hipMemcpyHostToDevice, c->stream));
+    if (!full) HIPCHK(c, hipMemcpyAsync(d_tab, T.tab.data(), T.tab.size(), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_flow_error, dim3(FE_PARTS, (unsigned)n), dim3(NT), 0, c->stream, H, W, h, w, full ? 1 : 0,
+                       reinterpret_cast<const double2*>(c->f_eval.p), reinterpret_cast<const uint8_t*>(c->f_eval.p + plane * 16),
+                       (const double2*)d_th, T.i32(d_tab, T.o_rlo), T.i32(d_tab, T.o_rcnt), T.f64(d_tab, 0), T.rstride,
+                       T.i32(d_tab, T.o_clo), T.i32(d_tab, T.o_ccnt), T.f64(d_tab, T.o_cw), T.cstride, d_parts, d_map);
+    HIPCHK(c, hipGetLastError());
+    std::vector<FlowErrPart> parts((size_t)n * FE_PARTS);
+    HIPCHK(c, hipMemcpyAsync(parts.data(), d_parts, pbytes, hipMemcpyDeviceToHost, c->stream));
+    if (ee_map) HIPCHK(c, hipMemcpyAsync(ee_map, d_map, plane * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));           // T (host vector) stays alive until here
+    for (int b = 0; b < n; ++b) {
+        eincm_flow_error_out o{};
+        for (int g = 0; g < FE_PARTS; ++g) {              // the partials of a window in index order
+            const FlowErrPart& q = parts[(size_t)b * FE_PARTS + g];
+            o.sum_ee += q.sum_ee; o.sum_ree += q.sum_ree;
+            o.n_ee += q.n_ee; o.n_pred += q.n_pred;
+            for (int k = 0; k < FE_NOVER; ++k) o.n_over[k] += q.n_over[k];
+        }
+        o.n_gt = c->fe_ngt[b];
+        // flow_eval.py:60-76: means over the intersection (NaN where it is empty), percentages over n_ee + eps
+        o.aee = o.n_ee ? o.sum_ee / (double)o.n_ee : std::nan("");
+        o.aree = o.n_ee ? o.sum_ree / (double)o.n_ee : std::nan("");
+        for (int k = 0; k < FE_NOVER; ++k) o.anpe[k] = (double)(o.n_over[k] * 100) / ((double)o.n_ee + EPSN);
+        out[b] = o;
+    }
     return EINCM_OK;
 }
 

@@ -348,6 +348,61 @@ def check_theta_batch(theta, valid, sensor_size):
     return t, v, single
 
 
+def check_flow_eval_batch(gt_flows, events, eval_masks, sensor_size):
+    """The arguments of Engine.flow_eval_stage, checked without a GPU.  gt_flows (n, H, W, 2) float32 or float64 (widened exactly);
+    events: one (xs, ys) per window, any integer or float coordinates as_int16_coords takes; eval_masks None or (n, H, W), non-zero =
+    evaluate.  Returns (gt float64, n_events int64 (n,), xs int16 concatenated, ys, masks uint8 or None)."""
+    H, W = int(sensor_size[0]), int(sensor_size[1])
+    g = np.asarray(gt_flows)
+    if g.dtype not in (np.float32, np.float64):
+        raise ValueError(f'gt_flows must be float32 or float64, got {g.dtype}')
+    if g.ndim != 4 or g.shape[0] < 1 or g.shape[1:] != (H, W, 2):
+        raise ValueError(f'gt_flows must be (n, {H}, {W}, 2) with n >= 1, got {g.shape}')
+    n = g.shape[0]
+    if n > 65535:
+        raise ValueError(f'{n} windows: at most 65535 in one staging')
+    events = list(events)
+    if len(events) != n:
+        raise ValueError(f'{len(events)} event lists for {n} ground-truth flows')
+    xs, ys = [], []
+    for b, e in enumerate(events):
+        if len(e) != 2:
+            raise ValueError(f'window {b}: events must be (xs, ys)')
+        x, y = as_int16_coords(e[0], 'xs'), as_int16_coords(e[1], 'ys')
+        if x.ndim != 1 or x.shape != y.shape:
+            raise ValueError(f'window {b}: xs {x.shape} and ys {y.shape} must be 1-D of one length')
+        xs.append(x)
+        ys.append(y)
+    m = None
+    if eval_masks is not None:
+        m = np.asarray(eval_masks)
+        if m.dtype.kind not in 'biuf':
+            raise ValueError(f'eval_masks must be boolean or numeric, got {m.dtype}')
+        if m.shape != (n, H, W):
+            raise ValueError(f'eval_masks must be {(n, H, W)}, got {m.shape}')
+        m = np.ascontiguousarray(m != 0).astype(np.uint8)
+    n_events = np.array([len(x) for x in xs], dtype=np.int64)
+    cat = lambda a: np.ascontiguousarray(np.concatenate(a)) if n_events.sum() else np.zeros(1, np.int16)      # noqa: E731 (a valid address)
+    return np.ascontiguousarray(g, dtype=np.float64), n_events, cat(xs), cat(ys), m
+
+
+def check_flow_eval_thetas(thetas, n_windows, sensor_size, method):
+    """thetas (n, h, w, 2), or (h, w, 2) for one staged window, no finer than the sensor; method a name of _lib.METHODS.  Returns
+    (thetas float64, method code)."""
+    if not isinstance(method, str) or method not in L.METHODS:
+        raise ValueError(f'method {method!r} not supported; one of {sorted(L.METHODS)}')
+    t = np.asarray(thetas)
+    if t.dtype.kind not in 'fiu':
+        raise ValueError(f'thetas must be numeric, got {t.dtype}')
+    if t.ndim == 3 and n_windows == 1:
+        t = t[None]
+    if t.ndim != 4 or t.shape[3] != 2 or t.shape[0] != n_windows or min(t.shape[1:3]) < 1:
+        raise ValueError(f'thetas must be ({n_windows}, h, w, 2), got {np.shape(thetas)}')
+    if t.shape[1] > int(sensor_size[0]) or t.shape[2] > int(sensor_size[1]):
+        raise ValueError(f'thetas {t.shape[1:3]} are finer than the sensor {tuple(int(v) for v in sensor_size)}')
+    return np.ascontiguousarray(t, dtype=np.float64), L.METHODS[method]
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                 full_aux=False, correlation_kind='mse'):
     """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
@@ -397,6 +452,7 @@ class Engine:
         self.objective_tiles = L.DEFAULT_OBJECTIVE_TILE
         self.splat_window = L.DEFAULT_SPLAT_WINDOW
         self._io = {}                      # (h, w) -> staging buffers of loss_grad with their addresses
+        self.flow_eval_windows = 0         # windows of the staged flow evaluation (flow_eval_stage)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -932,6 +988,40 @@ class Engine:
         self._check_data(self._lib.eincm_flow_encode(self._ctx, t.ctypes.data, t.shape[0], t.shape[1], t.shape[2],
                                                      None if v is None else v.ctypes.data, out.ctypes.data, C.byref(bad)))
         return out[0] if single else out
+
+    # -- flow errors of solved thetas -----------------------------------------
+    def flow_eval_stage(self, gt_flows, events, eval_masks=None):
+        """Stage the ground truth of a batch of evaluation windows once: gt_flows (n, H, W, 2) float32 or float64, events a list of
+        (xs, ys) per window (the evaluation events: per_pix_theta_to_flow's mask), eval_masks None or (n, H, W) (sparse_flow_error's
+        event_mask).  Independent of set_windows; replaced by the next flow_eval_stage.  ValueError: a shape or dtype that does not
+        fit (before the library is touched), an event outside the sensor (the engine then has no staged flow evaluation)."""
+        g, n_events, xs, ys, m = check_flow_eval_batch(gt_flows, events, eval_masks, (self.H, self.W))
+        rc = self._lib.eincm_flow_eval_stage(self._ctx, g.shape[0], g.ctypes.data, n_events.ctypes.data, xs.ctypes.data, ys.ctypes.data,
+                                             None if m is None else m.ctypes.data)
+        if rc != L.ERR_STATE:              # (refused for an evaluation in flight: what was staged is still there)
+            self.flow_eval_windows = g.shape[0] if rc == L.OK else 0
+        self._check_data(rc)
+
+    def flow_errors(self, thetas, method='bilinear', ee_map=False):
+        """sparse_flow_error(per_pix_theta_to_flow(Theta_b, events_b), gt_b, mask_b) of every staged window in one kernel, Theta_b =
+        thetas[b] scaled to the sensor with ``method`` (thetas (n, h, w, 2) at any pyramid level up to the sensor's size).  Returns a
+        list of {'errors': {AEE, AREE, A1PE, ...}, 'counts': {n_ee, n_pred, n_gt}}, sparse_flow_error's keys and types; with
+        ee_map=True also the (n, H, W) float64 map of the endpoint error (NaN outside the intersection of the masks)."""
+        n = self.flow_eval_windows
+        if n < 1:
+            raise EincmError(L.ERR_STATE, 'flow_errors called before flow_eval_stage')
+        t, code = check_flow_eval_thetas(thetas, n, (self.H, self.W), method)
+        out = (L.FlowErrorOut * n)()
+        emap = np.empty((n, self.H, self.W), dtype=np.float64) if ee_map else None
+        self._check(self._lib.eincm_flow_errors(self._ctx, t.ctypes.data, t.shape[1], t.shape[2], code, out,
+                                                None if emap is None else emap.ctypes.data))
+        res = []
+        for o in out:
+            errs = {'AEE': float(o.aee), 'AREE': float(o.aree)}
+            for k, thr in enumerate(L.FLOW_ERROR_THRESHOLDS):
+                errs[f'A{thr}PE'] = float(o.anpe[k])
+            res.append({'errors': errs, 'counts': {'n_ee': int(o.n_ee), 'n_pred': int(o.n_pred), 'n_gt': int(o.n_gt)}})
+        return (res, emap) if ee_map else res
 
     # -- device images ----------------------------------------------------------------------------
     def iwes(self):

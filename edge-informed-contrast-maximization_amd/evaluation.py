@@ -11,14 +11,20 @@
   flow_16bit_to_float   DSEC's GT flow format (src/dataloaders/dsec_loader.py:247-266), decoded on the GPU
   dsec_submission_flow  DSEC's submission format of a solved theta (src/dsec_npz_to_png.py:84-96): up-sampling and 16-bit coding in one
                         HIP kernel
-The masked reductions are O(H*W), run once per window, and stay on the host; every objective term comes from the GPU.
+  BatchThetaEvaluator   the two evaluation functions above for a whole batch of windows: the events, edges and ground truth are staged
+                        once, every later call uploads the thetas only and the masked reductions of all windows run in one HIP kernel
+                        
+The masked reductions of the per-window functions (sparse_flow_error, evaluate_theta_array) are O(H*W) and stay on the host; every
+objective term comes from the GPU.
 """
 import sys
 
 import numpy as np
 
 from . import losses
-from .engine import GtFlowPlan, check_gt_flow_plans
+from . import _lib as L
+from .engine import (Engine, GtFlowPlan, check_flow_eval_batch, check_gt_flow_plans, check_precision, check_window_size,
+                     resample_matrix)
 
 EPSN = sys.float_info.epsilon
 
@@ -84,6 +90,125 @@ def evaluate_theta_array(theta_array, eval_xs, eval_ys, eval_ts, edges, edge_ts,
         'multi_ref_weights': lo['multi_ref_weights'],
     })
     return evals, lo
+
+
+class BatchThetaEvaluator:
+    """evaluate_theta_array / sparse_flow_error for a batch of evaluation windows that is staged once and evaluated many times: what
+    EINCMThetaSolverCallback._evaluate_theta (callbacks.py:131-170) asks for at every iterate of every window of a lockstep batch.
+
+    windows: a list of (eval_xs, eval_ys, eval_ts, edges, edge_ts); gt_flows: (n, H, W, 2) or None (no flow keys, as
+    evaluate_theta_array with gt_flow None); err_eval_event_masks: None or (n, H, W); method: how a theta below the sensor's size is
+    scaled to it.  The evaluator owns an Engine unless one is handed over (which it then stages on and does not close).  Every argument
+    is checked before a GPU context is asked for."""
+
+    def __init__(self, sensor_size, windows, gt_flows, alpha, beta, gamma, delta, err_eval_event_masks=None, method='bilinear',
+                 window_size=3, precision='fp32', engine=None):
+        self.H, self.W = int(sensor_size[0]), int(sensor_size[1])
+        windows = list(windows)
+        if not windows:
+            raise ValueError('no windows')
+        for b, w in enumerate(windows):
+            if len(w) != 5:
+                raise ValueError(f'window {b} must be (eval_xs, eval_ys, eval_ts, edges, edge_ts)')
+        if not isinstance(method, str) or method not in L.METHODS:
+            raise ValueError(f'method {method!r} not supported; one of {sorted(L.METHODS)}')
+        check_precision(precision)
+        window_size = check_window_size(window_size)
+        if gt_flows is None and err_eval_event_masks is not None:
+            raise ValueError('err_eval_event_masks without gt_flows')
+        if gt_flows is not None:
+            if len(gt_flows) != len(windows):
+                raise ValueError(f'{len(gt_flows)} ground-truth flows for {len(windows)} windows')
+            check_flow_eval_batch(gt_flows, [(w[0], w[1]) for w in windows], err_eval_event_masks, (self.H, self.W))
+        self.n = len(windows)
+        self.params = tuple(float(v) for v in (alpha, beta, gamma, delta))
+        self.method = method
+        self.has_gt = gt_flows is not None
+        self._own = engine is None
+        self.engine = None
+        if engine is None:
+            engine = Engine((self.H, self.W), max(sum(len(w[0]) for w in windows), 1),
+                            max_refs=max(len(np.atleast_1d(w[4])) for w in windows), max_windows=self.n, precision=precision)
+        elif (engine.H, engine.W) != (self.H, self.W):
+            raise ValueError(f'sensor_size {(self.H, self.W)} is not the engine\'s {(engine.H, engine.W)}')
+        self.engine = engine
+        try:
+            if engine.splat_window != window_size:
+                engine.set_splat_window(window_size)
+            engine.set_windows(windows)
+            if self.has_gt:
+                engine.flow_eval_stage(gt_flows, [(w[0], w[1]) for w in windows], err_eval_event_masks)
+        except Exception:
+            self.close()
+            raise
+        self._A = {}                       # (h, w) -> the two resample matrices of that theta shape
+
+    def close(self):
+        if self._own and self.engine is not None:
+            self.engine.close()
+        self.engine = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def _thetas(self, thetas):
+        t = np.asarray(thetas, dtype=np.float64)
+        if t.ndim == 3 and self.n == 1:
+            t = t[None]
+        if t.ndim != 4 or t.shape[0] != self.n or t.shape[3] != 2:
+            raise ValueError(f'thetas must be ({self.n}, h, w, 2), got {np.shape(thetas)}')
+        return t
+
+    def flow_errors(self, thetas, ee_map=False):
+        """Engine.flow_errors of the staged batch: a list of sparse_flow_error's dicts (and the error maps with ee_map=True)."""
+        if not self.has_gt:
+            raise ValueError('the evaluator was built without gt_flows')
+        return self.engine.flow_errors(self._thetas(thetas), self.method, ee_map=ee_map)
+
+    def scaled_thetas(self, thetas):
+        """thetas (n, h, w, 2) scaled to the sensor: A_H theta A_W^T with the engine's resample matrices."""
+        t = self._thetas(thetas)
+        h, w = t.shape[1:3]
+        if (h, w) == (self.H, self.W):
+            return t
+        if (h, w) not in self._A:
+            self._A[(h, w)] = (resample_matrix(h, self.H, self.method), resample_matrix(w, self.W, self.method))
+        A_H, A_W = self._A[(h, w)]
+        rows = np.matmul(A_H, t.reshape(self.n, h, w * 2)).reshape(self.n, self.H, w, 2)          # two matrix products, not one 4-index sum
+        return np.ascontiguousarray(np.matmul(rows.transpose(0, 1, 3, 2), A_W.T).transpose(0, 1, 3, 2))
+
+    def evaluate(self, thetas):
+        """evaluate_theta_array for every window: one Engine.objectives call on the scaled thetas and one flow_errors call.  Returns a
+        list of (evals, loss_obj) with evaluate_theta_array's keys (the flow keys only where gt_flows were given)."""
+        t = self._thetas(thetas)
+        los = self.engine.objectives(self.scaled_thetas(t))
+        fes = self.engine.flow_errors(t, self.method) if self.has_gt else [None] * self.n
+        alpha, beta, gamma, delta = self.params
+        res = []
+        for lo, fe in zip(los, fes):
+            mean_rel_contrast = float(lo['rel_contrasts'].mean())
+            mean_rel_corr = float(lo['rel_correlations'].mean())
+            mean_rel_iwe_div = float(lo['rel_iwe_divergences'].mean())
+            tot_var, theta_div = lo['theta_total_variation'], lo['theta_divergence']
+            loss = alpha * (-mean_rel_contrast) + beta * (-mean_rel_corr) + gamma * tot_var + delta * mean_rel_iwe_div
+            evals = {}
+            if fe is not None:
+                evals.update(fe['errors'])
+                evals.update(fe['counts'])
+                evals['n_pixels'] = int(self.H * self.W)
+            evals.update({
+                'loss': loss, 'iwe_var': float(lo['variances'][0]), 'mean_rel_contrast': mean_rel_contrast,
+                'mean_rel_corr': mean_rel_corr, 'theta_tot_var': tot_var, 'theta_div': theta_div,
+                'fwl': float(lo['flow_warp_losses'][0]), 'mean_rel_iwe_div': mean_rel_iwe_div,
+                'rel_iwe_divergences': lo['rel_iwe_divergences'], 'rel_contrasts': lo['rel_contrasts'],
+                'rel_correlations': lo['rel_correlations'], 'flow_warp_losses': lo['flow_warp_losses'],
+                'multi_ref_weights': lo['multi_ref_weights'],
+            })
+            res.append((evals, lo))
+        return res
 
 
 def gt_flow_plan(gt_ts, t_start, t_end):

@@ -27,7 +27,8 @@ extern "C" {
                                 * 4: eincm_loss_grad_masked, eincm_set_device_results / eincm_finish_launch / eincm_grad_device_ptr / eincm_finish_collect, eincm_get_host_profile;
                                * 5: eincm_get_warped_events, eincm_loss_grad_device, eincm_loss_grad_masked_async, eincm_set_timing_period;
                                * 6: eincm_get_launch_policy; added since without a new version: eincm_rectify_events, eincm_remap_cubic, eincm_flow_decode,
-                               *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory */
+                               *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory,
+                               *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -469,6 +470,41 @@ int eincm_flow_decode(eincm_ctx* ctx, const uint16_t* flow16, int n, double* flo
  * Channel 2: 0, or valid[n][H][W] != 0 where valid is not NULL.  *n_bad: pixels with a value that is not finite or codes outside
  * [0, 65536) (stored as 0); if any, EINCM_ERR_ARG.  1 <= n <= 65535. */
 int eincm_flow_encode(eincm_ctx* ctx, const double* theta, int n, int h, int w, const uint8_t* valid, uint16_t* out, int64_t* n_bad);
+
+/* ---- Flow errors of a batch of solved thetas -------------------------------------------------------------
+ * sparse_flow_error (flow_eval.py:14-76) on per_pix_theta_to_flow (theta_utils.py:40-73) of every window of a batch: stage the ground
+ * truth once, evaluate many thetas against it.  "valid" below is the reference's mask: both components are not +-inf and
+ * sqrt(x x + y y) > 0 in double (false for NaN and for a norm that underflows to 0).
+ *
+ * eincm_flow_eval_stage keeps, in device memory of the context that no other call touches, gt_flow (n_windows, H, W, 2) and one flag
+ * byte per pixel: bit 0 = an evaluation event of the window sits on the pixel AND (eval_mask is NULL OR eval_mask[b][y][x] != 0),
+ * bit 1 = the GT flow is valid.  Window b's events are the next n_events[b] entries of xs / ys (the windows' events concatenated);
+ * a window may have none.  eval_mask (n_windows, H, W) or NULL.  It is independent of eincm_set_windows: a staging, an evaluation or
+ * any other operator in between leaves it intact; a later eincm_flow_eval_stage replaces it.
+ * EINCM_ERR_ARG before any device work and without allocating: a null pointer (eval_mask excepted), n_windows outside 1..65535, a
+ * negative n_events.  EINCM_ERR_STATE: an evaluation is in flight.  EINCM_ERR_ARG after the events were looked at: an event outside the
+ * sensor; the context then has NO staged flow evaluation.
+ *
+ * eincm_flow_errors evaluates theta (n_windows, h, w, 2) of the staged batch, h <= H, w <= W.  The predicted flow of a pixel with
+ * bit 0 is theta itself where (h, w) == (H, W), else sum_i a_i (sum_j b_j theta[i0 + i][j0 + j]) over the non-zero runs of the rows of
+ * eincm_resample_matrix(h, H, method) and (w, W, method), j inside i, unfused (eincm_flow_encode's arithmetic, for every method).
+ * Where it is valid the pixel counts in n_pred; where bit 1 is set too it is in the intersection: ee = sqrt(dx dx + dy dy),
+ * ree = ee / (sqrt(gx gx + gy gy) + eps), eps = 2^-52, unfused, IEEE sqrt and division.  out[b]: n_ee (intersection), n_pred, n_gt,
+ * n_over[k] = pixels with ee > N_k strictly (N = 1, 2, 3, 5, 10, 20), sum_ee and sum_ree in the fixed order of DESIGN.md section 18,
+ * aee = sum_ee / n_ee and aree = sum_ree / n_ee (NaN where n_ee == 0), anpe[k] = (double)(n_over[k] * 100) / ((double)n_ee + eps).
+ * ee_map (n_windows, H, W) or NULL: ee in the intersection, NaN elsewhere.  NaN / inf in theta or the GT are data.  The same bytes on
+ * every run and in fp32 and EINCM_CF_FP64 contexts; both calls return with the stream drained.
+ * EINCM_ERR_ARG before any device work: a null pointer (ee_map excepted), an unknown method, h or w < 1, h > H or w > W.
+ * EINCM_ERR_STATE: no staged flow evaluation, an evaluation in flight. */
+typedef struct eincm_flow_error_out {
+    int64_t n_ee, n_pred, n_gt;
+    int64_t n_over[6];                    /* N = 1, 2, 3, 5, 10, 20 */
+    double sum_ee, sum_ree, aee, aree;
+    double anpe[6];
+} eincm_flow_error_out;
+int eincm_flow_eval_stage(eincm_ctx* ctx, int n_windows, const double* gt_flow, const int64_t* n_events, const int16_t* xs,
+                          const int16_t* ys, const uint8_t* eval_mask);
+int eincm_flow_errors(eincm_ctx* ctx, const double* theta, int h, int w, int method, eincm_flow_error_out* out, double* ee_map);
 
 /* ---- BFGS with its state in HBM --------------------------------------------------------------------------
  * B = the staged windows (at most EINCM_BFGS_MAX_WINDOWS), each an independent BFGS minimisation (SciPy's _minimize_bfgs) over
