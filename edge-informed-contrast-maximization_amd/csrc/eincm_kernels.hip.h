@@ -705,7 +705,8 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
     const int n = it.count;
     const int iters = (n + NTH - 1) / NTH;            // uniform over the workgroup
     const int fshift = fix_shift(n);
-    const float FIX_SCALE = ldexpf(1.0f, fshift), FIX_INV = ldexpf(1.0f, -fshift);
+    const float FIX_SCALE = ldexpf(1.0f, fshift);
+    const int up = ACC_SHIFT - fshift;               // >= 0 (fix_shift caps at 30): a segment's integers at the accumulator's scale
 
     // Software pipeline over the segment's events, unrolled x3 with renamed register sets (no rotation moves, so no forced
     // vmcnt(0)): the (xy, t) loads of event j+2 are in flight while event j is splatted.
@@ -758,9 +759,10 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
                         atomicAdd(ldsu + cy * wp + cx, fix_u32(ky[dy], kx[dx]));
                     } else {
                         const int gx = wrap_drop(sx - 1 + dx, g.W), gy = wrap_drop(sy - 1 + dy, g.H);
-                        // straight to HBM in the accumulator's own scale (ky carries 2^fshift; a tap * 2^30 fits 32 bits)
+                        // straight to HBM: the integer the window would have held (the segment's scale 2^fshift), shifted to the
+                        // accumulator's scale like the flush - so the image is the same sum of integers whatever the windows hold
                         if (gx >= 0 && gy >= 0)
-                            atomicAdd(img + (size_t)gy * g.W + gx, (unsigned long long)fix_u32(ky[dy] * FIX_INV * 1073741824.0f, kx[dx]));
+                            atomicAdd(img + (size_t)gy * g.W + gx, (unsigned long long)fix_u32(ky[dy], kx[dx]) << up);
                     }
                 }
             }
@@ -791,7 +793,6 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
     // (scale 2^fshift) are shifted to the accumulator's scale 2^ACC_SHIFT without rounding; integer adds commute, so the image
     // does not depend on the order in which the workgroups arrive.
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int up = ACC_SHIFT - fshift;               // >= 0 (fix_shift caps at 30)
     auto to_acc = [&](int i) -> unsigned long long { return (unsigned long long)ldsu[i] << up; };
     if (wn.ox >= 0 && wn.oy >= 0 && wn.ox + wn.ww <= g.W && wn.oy + wn.wh <= g.H) {
         // the usual case, the window lies inside the image: no index rule per pixel

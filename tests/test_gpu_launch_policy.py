@@ -1,5 +1,5 @@
 """The launch policy of a staged batch (eincm_get_launch_policy; DESIGN.md 4.2 "where those rules hold"): which segment lengths, LDS
-pitch regime and window capacities the library picks is not part of the results - any choice is correct, parity is tested elsewhere -
+pitch regime and window capacities the library picks is not part of the results - any choice is correct, tests/test_gpu_launch_policy_parity.py checks the values cell by cell -
 but it is what the measured configurations rely on, so the rules are pinned here on cheap synthetic batches (uniformly random events)."""
 import importlib
 
