@@ -10,11 +10,18 @@ ready at the same moment can use that.  This module is that caller:
   stopping rules and status codes), restated as a state machine that asks for ONE function evaluation at a time - and answers all
   the requests of a tick with one batched evaluation.  Windows that have converged ride along with their last theta.  Given the
   same (value, grad) a window takes exactly the steps SciPy's BFGS would take.
+* The algorithm is restated once, in ``_BFGSMachine``, which sees scalars only; the vectors of a window are a ``_HostWindow`` (numpy:
+  the three forms of the inverse-Hessian update, each written once) or rows of the GPU's state.  ``LockstepBFGS`` drives the machine
+  through ``_WindowBFGS`` (machine + host window, asks for points), ``DeviceLockstepBFGS`` drives it over a state object
+  (``NumpyBFGSState``: B host windows, the written contract of ``DeviceBFGSState``).  tests/_bfgs_witness.py holds both to a frozen
+  vector form of the algorithm, bit for bit.
 * ``BatchedMultipleLevelEINCMSolver`` drives the theta pyramid of B windows (or of the current windows of B independent sequences)
   level by level with it: same constructor keywords, state and per-window result dict as ``solver.MultipleLevelEINCMSolver``
   (reference solver.py:16-126, :254-267), retries included; a solved handover weight (L-BFGS-B on one scalar, :325-335) is found
   window by window with the other windows riding along.
 """
+import math
+
 import numpy as np
 import scipy.optimize as spo
 from scipy.optimize._dcsrch import DCSRCH            # MINPACK-2 dcsrch as SciPy ships it: reverse communication, one step per call
@@ -147,54 +154,61 @@ class _CoroutineCall:
         self._thread.join(timeout=5.0)
 
 
-class _WindowBFGS:
-    """One window's BFGS, one function evaluation at a time (scipy.optimize._optimize._minimize_bfgs with jac=True)."""
+class _BFGSMachine:
+    """One window's BFGS (scipy.optimize._optimize._minimize_bfgs with jac=True), one function evaluation at a time and with the vectors
+    taken out: the phases, the DCSRCH loop, the fallback to SciPy's second line search, the stopping rules and status codes - the only
+    restatement of the algorithm; both drivers run it.  x, its gradient g, the direction p and the inverse Hessian live in a state
+    (``_HostWindow`` per window, ``NumpyBFGSState``, ``DeviceBFGSState``); the machine is fed (phi, phi' = grad . p, max|grad|) at the step
+    it asked for.  ``request`` is that step along p (a float) or None; after a feed ``pending`` may hold (mode, alpha): what the state has
+    to do with the window (_lib.BFGS_INIT / UPDATE / MOVE) before ``accepted`` gets the new iterate's scalars.  ``phase``:
+    'init' | 'ls' (DCSRCH) | 'ls2' (the fallback, ``ls2`` its helper thread) | 'reeval' | 'done'."""
 
-    def __init__(self, x0, maxiter, gtol, callback=None, wolfe2_fallback=True):
+    def __init__(self, maxiter, gtol, n, wolfe2_fallback=True):
         self.wolfe2_fallback = bool(wolfe2_fallback)
-        self.x0 = np.array(x0, dtype=np.float64).reshape(-1)
-        self.n = self.x0.size
+        self.n = int(n)
         self.maxiter = int(maxiter) if maxiter is not None else self.n * 200
         self.gtol = float(gtol)
-        self.callback = callback
-        self.phase = 'init'
-        self.request = self.x0                  # the point whose (value, grad) this window wants next; None = finished
-        self.k = 0
-        self.nfev = 0
-        self.warnflag = 0
-        self.result = None
+        self.phase, self.request = 'init', 0.0          # the first evaluation: at x0 (the state's direction is 0)
+        self.pending = None
+        self.k = self.nfev = self.warnflag = 0
+        self.ls2 = None
 
-    # -- what the driver calls ----------------------------------------------------------------------------------
-    def feed(self, f, g, single_eval):
-        """(value, grad) at ``self.request``.  single_eval(x) -> (f, g) evaluates this window alone (the rare wolfe2 fallback)."""
-        self.nfev += 1
-        f = float(f)
-        g = np.array(g, dtype=np.float64).reshape(-1)
+    def feed(self, f, dphi, gmax):
+        f, dphi, gmax = float(f), float(dphi), float(gmax)
         if self.phase == 'init':
-            self.xk, self.old_fval, self.gfk = self.x0, f, g
-            self.sym = threadpool_limits is not None and self.n > _EXACT_UPDATE_MAX_N
-            # sym: the inverse Hessian lives in the UPPER triangle of a Fortran-ordered array (dsymv / dsyr2 touch half the matrix)
-            self.Hk = np.asfortranarray(np.eye(self.n)) if self.sym else np.eye(self.n)
-            self.old_old_fval = self.old_fval + np.linalg.norm(self.gfk) / 2          # initial step guess dx ~ 1
-            self.gnorm = np.abs(self.gfk).max() if self.n else 0.0
-            self._begin_iteration(single_eval)
+            self.nfev += 1
+            self.old_fval, self.gnorm = f, gmax
+            self._after = 'init'
+            self.pending, self.request = (L.BFGS_INIT, 0.0), None
         elif self.phase == 'ls':
-            self.phi1, self.gval = f, g
-            self.derphi1 = float(np.dot(g, self.pk))
-            self._ls_step(single_eval)
+            self.nfev += 1
+            self.phi1, self.derphi1, self.gmax_t = f, dphi, gmax
+            self._ls_step()
         elif self.phase == 'ls2':
-            self.ls2.answer(f, g)
-            self._ls2_advance(single_eval)
+            self.nfev += 1
+            self.gmax_t = gmax
+            self.ls2.answer(f, dphi)
+            self._ls2_advance()
+        elif self.phase == 'reeval':                    # the accepted step was not the last one evaluated: its gradient, not counted
+            self.gmax_t = gmax
+            self._step_taken(self.alpha_k, self.new_fval)
         else:
             raise RuntimeError('feed() on a finished window')
 
-    # -- BFGS iteration -------------------------------------------------------------------------------------------
-    def _begin_iteration(self, single_eval):
+    def accepted(self, scal):
+        """The scalars of the iterate the state has just moved to (what ``pending`` asked for)."""
+        self.pending, self.scal = None, scal
+        if self._after == 'init':
+            self.old_old_fval = self.old_fval + scal[L.BFGS_S_GNORM] / 2          # initial step guess dx ~ 1
+        if self._after == 'finish':
+            return self._finish()
+        self._begin_iteration()
+
+    def _begin_iteration(self):
         if not (self.gnorm > self.gtol and self.k < self.maxiter):
             return self._finish()
-        self.pk = -dsymv(1.0, self.Hk, self.gfk, lower=0) if self.sym else -np.dot(self.Hk, self.gfk)
-        derphi0 = float(np.dot(self.gfk, self.pk))
-        # scalar_search_wolfe1: the first trial step
+        derphi0 = float(self.scal[L.BFGS_S_DPHI0])
+        self.pnorm = self.scal[L.BFGS_S_PNORM]
         if self.old_old_fval is not None and derphi0 != 0:
             alpha1 = min(1.0, 1.01 * 2 * (self.old_fval - self.old_old_fval) / derphi0)
             if alpha1 < 0:
@@ -203,107 +217,201 @@ class _WindowBFGS:
             alpha1 = 1.0
         self.dcsrch = DCSRCH(None, None, _BFGS_C1, _BFGS_C2, _BFGS_XTOL, _BFGS_AMIN, _BFGS_AMAX)
         self.task, self.alpha1, self.phi1, self.derphi1, self.derphi0 = b'START', alpha1, self.old_fval, derphi0, derphi0
-        self.gval = self.gfk
+        self.gmax_t = self.gnorm
         self.ls_iter = 0
-        self._ls_step(single_eval)
+        self._ls_step()
 
-    def _ls_step(self, single_eval):
-        """One pass of the loop of DCSRCH.__call__; leaves a request behind, or ends the line search."""
+    def _ls_step(self):
         if self.ls_iter >= _LS_MAXITER:
-            return self._ls_done(None, single_eval)
+            return self._ls_done(None)
         self.ls_iter += 1
         stp, self.phi1, self.derphi1, self.task = self.dcsrch._iterate(self.alpha1, self.phi1, self.derphi1, self.task)
-        if not np.isfinite(stp):
-            return self._ls_done(None, single_eval)
+        if not math.isfinite(stp):
+            return self._ls_done(None)
         if self.task[:2] == b'FG':
             self.alpha1 = stp
-            self.phase, self.request = 'ls', self.xk + stp * self.pk
+            self.phase, self.request = 'ls', float(stp)
             return
         if self.task[:5] == b'ERROR' or self.task[:4] == b'WARN':
             stp = None
-        self._ls_done(stp, single_eval)
+        self._ls_done(stp)
 
-    def _ls_done(self, stp, single_eval):
+    def _ls_done(self, stp):
         if stp is not None:
-            return self._step_taken(stp, self.phi1, self.gval, single_eval)
+            return self._step_taken(stp, self.phi1)
         if not self.wolfe2_fallback:                               # opt-out of SciPy's second line search: precision loss here and now
             self.warnflag = 2
             return self._finish()
-        # _line_search_wolfe12: DCSRCH found no step, SciPy tries its other line search.  That one is not written for reverse
-        # communication, so it runs in a helper thread whose f / fprime calls become this window's requests: the evaluations
-        # stay in lockstep with the other windows (with the engine's fp32-level noise this fallback is the common end of a level)
-        self.ls2 = _CoroutineCall(lambda fv, fg: line_search_wolfe2(fv, fg, self.xk, self.pk, self.gfk, self.old_fval, self.old_old_fval,
-                                                                     c1=_BFGS_C1, c2=_BFGS_C2, amax=_BFGS_AMAX))
-        self._ls2_advance(single_eval)
+        # _line_search_wolfe12: DCSRCH found no step, SciPy tries its other line search (with the engine's fp32-level noise this fallback
+        # is the common end of a level).  That one, line_search_wolfe2, is scalar_search_wolfe2 on phi(a) = f(xk + a pk) and
+        # derphi(a) = grad . pk with the gradient of the last derphi call kept for the caller.  It is not written for reverse
+        # communication, so it runs in a helper thread whose f / fprime calls become this window's requests (_CoroutineCall) and stay in
+        # lockstep with the other windows: the point is the step a, the "gradient" phi'(a); the cache answers derphi(a) after phi(a)
+        # without an evaluation.
+        def search(fv, fg):
+            return scalar_search_wolfe2(lambda a: fv(a), lambda a: fg(a)[0], self.old_fval, self.old_old_fval, self.derphi0,
+                                        _BFGS_C1, _BFGS_C2, _BFGS_AMAX, None, maxiter=10)
+        self.ls2 = _CoroutineCall(search)
+        self._ls2_advance()
 
-    def _ls2_advance(self, single_eval):
+    def _ls2_advance(self):
         kind, payload = self.ls2.next()
         if kind == 'request':
-            self.phase, self.request = 'ls2', payload
+            self.phase, self.request = 'ls2', float(payload)
             return
-        ret = payload
-        if ret[0] is None:
+        alpha_star, phi_star, _, derphi_star = payload
+        if alpha_star is None:
             self.warnflag = 2                                      # precision loss: no step satisfies the Wolfe conditions
             return self._finish()
-        alpha_k, new_fval, gfkp1 = ret[0], ret[3], ret[5]
-        if gfkp1 is None:                                          # (line_search_wolfe2 returns the gradient of its last evaluation)
-            gfkp1 = np.asarray(single_eval(self.xk + alpha_k * self.pk)[1], dtype=np.float64).reshape(-1)
-        self._step_taken(alpha_k, new_fval, gfkp1, single_eval)
+        if derphi_star is None:                                    # (the search ran out of iterations: its last evaluation was elsewhere)
+            self.alpha_k, self.new_fval = float(alpha_star), phi_star
+            self.phase, self.request = 'reeval', float(alpha_star)
+            return
+        self._step_taken(float(alpha_star), phi_star)
 
-    def _step_taken(self, alpha_k, new_fval, gfkp1, single_eval):
+    def _step_taken(self, alpha_k, new_fval):
+        """The state's trial point is x + alpha_k p and its trial gradient the gradient there."""
         self.old_fval, self.old_old_fval = new_fval, self.old_fval
-        sk = alpha_k * self.pk
-        self.xk = self.xk + sk
-        yk = gfkp1 - self.gfk
-        self.gfk = gfkp1
         self.k += 1
-        if self.callback is not None:
-            self.callback(spo.OptimizeResult(x=self.xk, fun=self.old_fval))
-        self.gnorm = np.abs(self.gfk).max()
-        if self.gnorm <= self.gtol:
-            return self._finish()
-        if alpha_k * np.linalg.norm(self.pk) <= 0.0:              # xrtol = 0
-            return self._finish()
-        if not np.isfinite(self.old_fval):
+        self.gnorm = self.gmax_t
+        self.request = None
+        if self.gnorm <= self.gtol or alpha_k * self.pnorm <= 0.0:      # converged / xrtol = 0: SciPy stops before it updates H
+            self._after, self.pending = 'finish', (L.BFGS_MOVE, alpha_k)
+        elif not math.isfinite(self.old_fval):
             self.warnflag = 2
-            return self._finish()
-        rhok_inv = float(np.dot(yk, sk))
-        rhok = 1000.0 if rhok_inv == 0.0 else 1.0 / rhok_inv
-        if self.n <= _EXACT_UPDATE_MAX_N:                          # SciPy's own expression (bit for bit the same inverse Hessian)
-            I = np.eye(self.n, dtype=int)
-            A1 = I - sk[:, np.newaxis] * yk[np.newaxis, :] * rhok
-            A2 = I - yk[:, np.newaxis] * sk[np.newaxis, :] * rhok
-            self.Hk = np.dot(A1, np.dot(self.Hk, A2)) + (rhok * sk[:, np.newaxis] * sk[np.newaxis, :])
+            self._after, self.pending = 'finish', (L.BFGS_MOVE, alpha_k)
         else:
-            # the same update as ONE symmetric rank-two correction, O(n^2) instead of the two n x n products (n = 512 at a 16x16
-            # theta: 10 ms per iteration in SciPy's form, the evaluation itself takes 0.1 ms):
-            #   (I - r s y^T) H (I - r y s^T) + r s s^T = H - r (s (Hy)^T + (Hy) s^T) + r (1 + r y^T H y) s s^T     (H symmetric)
-            #                                         = H + s w^T + w s^T,   w = (c / 2) s - r Hy,  c = r (1 + r y^T H y)
-            Hy = dsymv(1.0, self.Hk, yk, lower=0) if self.sym else np.dot(self.Hk, yk)
-            w = (0.5 * rhok * (1.0 + rhok * float(np.dot(yk, Hy)))) * sk - rhok * Hy
-            if self.sym:
-                self.Hk = dsyr2(1.0, sk, w, a=self.Hk, overwrite_a=1, lower=0)     # in place, upper triangle
-            else:
-                sw = np.outer(sk, w)
-                self.Hk = self.Hk + sw + sw.T
-        self._begin_iteration(single_eval)
+            self._after, self.pending = 'iterate', (L.BFGS_UPDATE, alpha_k)
+        self.stepped = True
 
     def _finish(self):
-        fval = self.old_fval
         if self.warnflag == 2:
             pass
         elif self.k >= self.maxiter:
             self.warnflag = 1
-        elif np.isnan(self.gnorm) or np.isnan(fval) or np.isnan(self.xk).any():
+        elif math.isnan(self.gnorm) or math.isnan(self.old_fval) or math.isnan(self.scal[L.BFGS_S_XMAX]):
             self.warnflag = 3
         self.phase, self.request = 'done', None
-        if getattr(self, 'sym', False):                             # hand out the full matrix
-            d = self.Hk.diagonal().copy()                          # (the strictly lower triangle is still the identity's: zero)
-            self.Hk = self.Hk + self.Hk.T
-            self.Hk[np.diag_indices(self.n)] = d
-            self.sym = False
-        self.result = spo.OptimizeResult(fun=fval, jac=self.gfk, hess_inv=self.Hk, nfev=self.nfev, njev=self.nfev,
-                                         status=self.warnflag, success=(self.warnflag == 0), x=self.xk, nit=self.k)
+
+
+def _max_abs(v):
+    return np.abs(v).max() if v.size else 0.0
+
+
+class _HostWindow:
+    """One window's vectors on the host: the point x, its gradient g, the direction p, the inverse Hessian H, the trial point
+    xt = x + a p of the last evaluation and its gradient gt.  ``form`` is how H is kept and updated:
+
+    * 'exact'  dense, SciPy's own expression (two n x n products): bit for bit SciPy's inverse Hessian
+    * 'rank2'  dense, the same update as ONE symmetric rank-two correction, O(n^2) (n = 512 at a 16x16 theta: 10 ms per iteration in
+               SciPy's form, the evaluation itself takes 0.1 ms):
+                 (I - r s y^T) H (I - r y s^T) + r s s^T = H - r (s (Hy)^T + (Hy) s^T) + r (1 + r y^T H y) s s^T     (H symmetric)
+                                                         = H + s w^T + w s^T,   w = (c / 2) s - r Hy,  c = r (1 + r y^T H y)
+    * 'tri'    that correction on the UPPER triangle of a Fortran-ordered array (dsymv / dsyr2 touch half the matrix)
+    * None     a rider: a point and no H"""
+
+    def __init__(self, x0, form):
+        self.form = form
+        self.x = self.xt = np.array(x0, dtype=np.float64).reshape(-1)      # (every vector is replaced, never written into)
+        self.n = self.x.size
+        self.g = self.gt = self.p = np.zeros(self.n)
+        self.H = None if form is None else np.asfortranarray(np.eye(self.n)) if form == 'tri' else np.eye(self.n)
+        self.I = np.eye(self.n, dtype=int) if form == 'exact' else None      # (SciPy builds it anew in every iteration)
+
+    def trial(self, a):
+        self.xt = self.x + a * self.p
+        return self.xt
+
+    def take(self, g):
+        """The gradient at the trial point -> (gt . p, max|gt|)."""
+        self.gt = np.array(g, dtype=np.float64).reshape(-1)
+        return float(np.dot(self.gt, self.p)), _max_abs(self.gt)
+
+    def _H_times(self, v):
+        return dsymv(1.0, self.H, v, lower=0) if self.form == 'tri' else np.dot(self.H, v)
+
+    def accept(self, alpha, mode, every_scalar=True):
+        """_lib.BFGS_UPDATE (the update with s = alpha p, y = gt - g, then x <- xt, g <- gt, p = -H g) / MOVE (x <- xt, g <- gt) / INIT
+        (MOVE and p = -H g) -> the _lib.BFGS_NS scalars of the new iterate (y . Hy is 0 in SciPy's form, which never has H y).
+        ``every_scalar=False``: only what ``_BFGSMachine.accepted`` reads (g . p, |p|, max|x|, and |g| at INIT), the others 0."""
+        ys = yhy = 0.0
+        if mode == L.BFGS_UPDATE:
+            sk, yk = alpha * self.p, self.gt - self.g
+            ys = float(np.dot(yk, sk))
+            rhok = 1000.0 if ys == 0.0 else 1.0 / ys
+            if self.form == 'exact':
+                I = self.I
+                A1 = I - sk[:, np.newaxis] * yk[np.newaxis, :] * rhok
+                A2 = I - yk[:, np.newaxis] * sk[np.newaxis, :] * rhok
+                self.H = np.dot(A1, np.dot(self.H, A2)) + (rhok * sk[:, np.newaxis] * sk[np.newaxis, :])
+            else:
+                Hy = self._H_times(yk)
+                yhy = float(np.dot(yk, Hy))
+                w = (0.5 * rhok * (1.0 + rhok * yhy)) * sk - rhok * Hy
+                if self.form == 'tri':
+                    self.H = dsyr2(1.0, sk, w, a=self.H, overwrite_a=1, lower=0)     # in place, upper triangle
+                else:
+                    sw = np.outer(sk, w)
+                    self.H = self.H + sw + sw.T
+        self.x, self.g = self.xt, self.gt
+        if mode != L.BFGS_MOVE:
+            self.p = -self._H_times(self.g)
+        g, p, x = self.g, self.p, self.x
+        if every_scalar:
+            return (float(np.dot(g, p)), _max_abs(g), np.linalg.norm(p), _max_abs(x), _max_abs(p), np.linalg.norm(g), ys, yhy)
+        return (float(np.dot(g, p)), 0.0, np.linalg.norm(p), _max_abs(x), 0.0, np.linalg.norm(g) if mode == L.BFGS_INIT else 0.0, ys, yhy)
+
+    def full_hess_inv(self):
+        """The full symmetric matrix, the caller's own."""
+        if self.form is None:
+            return np.zeros((self.n, self.n))
+        if self.form != 'tri':
+            return self.H.copy()
+        d = self.H.diagonal().copy()                               # (the strictly lower triangle is still the identity's: zero)
+        H = self.H + self.H.T
+        H[np.diag_indices(self.n)] = d
+        return H
+
+
+class _WindowBFGS:
+    """The machine and one host state behind what ``LockstepBFGS`` drives: ``request`` is the POINT whose (value, grad) the window wants
+    next (None = finished, ``result`` is there), ``feed`` takes them.  Up to _EXACT_UPDATE_MAX_N unknowns H is updated by SciPy's own
+    expression, above that in the rank-two form - in one triangle where BLAS can be kept on one thread (both read at the first feed)."""
+
+    def __init__(self, x0, maxiter, gtol, callback=None, wolfe2_fallback=True):
+        self.request = np.array(x0, dtype=np.float64).reshape(-1)
+        self.machine = _BFGSMachine(maxiter, gtol, self.request.size, wolfe2_fallback)
+        self.callback = callback
+        self.state = self.result = None
+
+    phase = property(lambda self: self.machine.phase)
+    ls2 = property(lambda self: self.machine.ls2)
+
+    def feed(self, f, g, single_eval):
+        """(value, grad) at ``self.request``.  single_eval(x) -> (f, g) evaluates this window alone (the rare wolfe2 fallback)."""
+        m = self.machine
+        if self.request is None:
+            raise RuntimeError('feed() on a finished window')
+        if self.state is None:
+            n = self.request.size
+            self.state = _HostWindow(self.request, 'exact' if n <= _EXACT_UPDATE_MAX_N else 'tri' if threadpool_limits is not None else 'rank2')
+        st = self.state
+        m.feed(f, *st.take(g))
+        if m.phase == 'reeval':                  # the accepted step's gradient, here and now (its value is known; not counted in nfev)
+            m.feed(np.nan, *st.take(single_eval(st.trial(m.request))[1]))
+        if m.pending is not None:
+            mode, alpha = m.pending
+            scal = st.accept(alpha, mode, every_scalar=False)
+            if mode != L.BFGS_INIT and self.callback is not None:
+                self.callback(spo.OptimizeResult(x=st.x, fun=m.old_fval))
+            m.accepted(scal)
+        if m.request is not None:
+            self.request = st.trial(m.request)
+            return
+        self.request = None
+        self.result = spo.OptimizeResult(fun=m.old_fval, jac=st.g, hess_inv=st.full_hess_inv(), nfev=m.nfev, njev=m.nfev,
+                                         status=m.warnflag, success=(m.warnflag == 0), x=st.x, nit=m.k)
+        self.state = None                                          # (its H is handed out: no second n x n array per finished window)
 
 
 class LockstepBFGS:
@@ -427,7 +535,7 @@ class LockstepBFGS:
                 self._start_group(gi)                  # back on the GPU before the next group is collected and fed
         return self._results()
 
-# ---- the same minimisation driven by scalars: x, its gradient, the direction and the inverse Hessian live in a state object --------------
+# ---- the machine driven over a state object: x, its gradient, the direction and the inverse Hessian of all windows live there --------------
 BFGS_STATES = ('host', 'device')
 
 
@@ -439,9 +547,9 @@ def check_bfgs_state(bfgs_state):
 
 
 class NumpyBFGSState:
-    """The state interface on the CPU, op for op what ``_WindowBFGS`` does on its rank-two path: the written-down contract of
-    ``DeviceBFGSState``.  A state holds, per window, the point x, its gradient g, the direction p, the inverse Hessian H, the trial
-    point xt = x + a p of the last evaluation and its gradient gt:
+    """The state interface on the CPU: B ``_HostWindow`` in the rank-two form (in the triangle wherever BLAS can be kept on one thread) -
+    the written-down contract of ``DeviceBFGSState``, op for op what the GPU does.  A state holds, per window, the point x, its gradient
+    g, the direction p, the inverse Hessian H, the trial point xt = x + a p of the last evaluation and its gradient gt:
 
     * ``begin(x0, active)``          x = x0, H = I
     * ``eval(alpha, mask)``          one evaluation at x + alpha[b] p per window of the mask -> (f, phi' = gt . p, max|gt|), each (B,)
@@ -453,89 +561,58 @@ class NumpyBFGSState:
 
     def __init__(self, fun_batch):
         self.fun_batch = fun_batch
+        self.windows = []
 
     def begin(self, x0, active=None):
         x0 = np.array(x0, dtype=np.float64)
         self.B, self.n = x0.shape
         act = np.ones(self.B, bool) if active is None else np.asarray(active, bool)
-        if not hasattr(self, 'x') or self.x.shape != x0.shape:
-            self.x, self.g, self.p = x0.copy(), np.zeros_like(x0), np.zeros_like(x0)
-            self.xt, self.gt = x0.copy(), np.zeros_like(x0)
-            self.H = [None] * self.B
+        if not self.windows or (len(self.windows), self.windows[0].n) != x0.shape:
+            self.windows = [_HostWindow(x0[b], None) for b in range(self.B)]
+            self.xt = x0.copy()                          # the batch's trial points as fun_batch takes them
             self.scal = np.zeros((self.B, L.BFGS_NS))
-        self.sym = threadpool_limits is not None
         for b in np.flatnonzero(act):
-            self.x[b] = x0[b]
-            self.g[b] = 0.0
-            self.p[b] = 0.0
-            # sym: the inverse Hessian lives in the UPPER triangle of a Fortran-ordered array (dsymv / dsyr2 touch half the matrix)
-            self.H[b] = np.asfortranarray(np.eye(self.n)) if self.sym else np.eye(self.n)
+            self.windows[b] = _HostWindow(x0[b], 'tri' if threadpool_limits is not None else 'rank2')
+
+    def _rows(self, name):
+        return np.stack([getattr(w, name) for w in self.windows])
+
+    # (B, n) copies of the windows' vectors, for reading: ``set_state`` is the way to write
+    x = property(lambda self: self._rows('x'))
+    g = property(lambda self: self._rows('g'))
+    p = property(lambda self: self._rows('p'))
 
     def set_state(self, b, x=None, g=None, p=None, H=None):
         """Overwrite parts of window b's state (H: a full symmetric matrix)."""
-        for dst, src in ((self.x, x), (self.g, g), (self.p, p)):
+        w = self.windows[b]
+        for name, src in (('x', x), ('g', g), ('p', p)):
             if src is not None:
-                dst[b] = np.asarray(src, dtype=np.float64)
+                setattr(w, name, np.array(src, dtype=np.float64))
         if H is not None:
-            H = np.asarray(H, dtype=np.float64)
-            self.H[b] = np.asfortranarray(np.triu(H)) if self.sym else H.copy()
+            H = np.array(H, dtype=np.float64)
+            w.H = np.asfortranarray(np.triu(H)) if w.form == 'tri' else H
 
     def eval(self, alpha, mask):
         for b in np.flatnonzero(mask):
-            self.xt[b] = self.x[b] + alpha[b] * self.p[b]
+            self.xt[b] = self.windows[b].trial(alpha[b])
         v, g = self.fun_batch(self.xt, mask)
         f, dphi, gmax = np.full(self.B, np.nan), np.zeros(self.B), np.zeros(self.B)
         for b in np.flatnonzero(mask):
-            self.gt[b] = np.asarray(g[b], dtype=np.float64).reshape(-1)
             f[b] = float(v[b])
-            dphi[b] = float(np.dot(self.gt[b], self.p[b]))
-            gmax[b] = np.abs(self.gt[b]).max() if self.n else 0.0
+            dphi[b], gmax[b] = self.windows[b].take(g[b])
         return f, dphi, gmax
-
-    def _direction(self, b):
-        return -dsymv(1.0, self.H[b], self.g[b], lower=0) if self.sym else -np.dot(self.H[b], self.g[b])
 
     def accept(self, alpha, modes):
         for b in range(self.B):
-            mode = int(modes[b])
-            if mode == L.BFGS_SKIP:
-                continue
-            ys = yhy = 0.0
-            if mode == L.BFGS_UPDATE:
-                sk = alpha[b] * self.p[b]
-                yk = self.gt[b] - self.g[b]
-                rhok_inv = float(np.dot(yk, sk))
-                rhok = 1000.0 if rhok_inv == 0.0 else 1.0 / rhok_inv
-                Hy = dsymv(1.0, self.H[b], yk, lower=0) if self.sym else np.dot(self.H[b], yk)
-                ys, yhy = rhok_inv, float(np.dot(yk, Hy))
-                w = (0.5 * rhok * (1.0 + rhok * yhy)) * sk - rhok * Hy
-                if self.sym:
-                    self.H[b] = dsyr2(1.0, sk, w, a=self.H[b], overwrite_a=1, lower=0)
-                else:
-                    sw = np.outer(sk, w)
-                    self.H[b] = self.H[b] + sw + sw.T
-            self.x[b] = self.xt[b]
-            self.g[b] = self.gt[b]
-            if mode != L.BFGS_MOVE:
-                self.p[b] = self._direction(b)
-            g, p, x = self.g[b], self.p[b], self.x[b]
-            self.scal[b] = (float(np.dot(g, p)), np.abs(g).max(), np.linalg.norm(p), np.abs(x).max(), np.abs(p).max(),
-                            np.linalg.norm(g), ys, yhy)
+            if int(modes[b]) != L.BFGS_SKIP:
+                self.scal[b] = self.windows[b].accept(alpha[b], int(modes[b]))
         return self.scal.copy()
 
     def full_hess_inv(self, b):
-        H = self.H[b]
-        if not self.sym:
-            return H.copy()
-        d = H.diagonal().copy()                                    # (the strictly lower triangle is still the identity's: zero)
-        H = H + H.T
-        H[np.diag_indices(self.n)] = d
-        return H
+        return self.windows[b].full_hess_inv()
 
     def fetch(self, want_hess_inv=False):
-        H = np.stack([self.full_hess_inv(b) if self.H[b] is not None else np.zeros((self.n, self.n)) for b in range(self.B)]) \
-            if want_hess_inv else None
-        return self.x.copy(), self.g.copy(), H
+        return self.x, self.g, (np.stack([w.full_hess_inv() for w in self.windows]) if want_hess_inv else None)
 
 
 class DeviceBFGSState:
@@ -561,145 +638,6 @@ class DeviceBFGSState:
         return x.reshape(self.B, self.n), g.reshape(self.B, self.n), H
 
 
-class _ScalarWindowBFGS:
-    """``_WindowBFGS`` with the vectors taken out: the same phases, stopping rules and status codes, fed (phi, phi', max|grad|) at the
-    step it asked for.  ``request`` is that step (a float) or None; after a feed ``pending`` may hold (mode, alpha): what the state has to
-    do with the window before ``accepted`` gets the new iterate's scalars."""
-
-    def __init__(self, maxiter, gtol, n, wolfe2_fallback=True):
-        self.wolfe2_fallback = bool(wolfe2_fallback)
-        self.n = int(n)
-        self.maxiter = int(maxiter) if maxiter is not None else self.n * 200
-        self.gtol = float(gtol)
-        self.phase, self.request = 'init', 0.0          # the first evaluation: at x0 (the state's direction is 0)
-        self.pending = None
-        self.k = self.nfev = self.warnflag = 0
-        self.xnan = False
-        self.done = False
-        self.ls2 = None
-
-    def feed(self, f, dphi, gmax):
-        f, dphi, gmax = float(f), float(dphi), float(gmax)
-        if self.phase == 'init':
-            self.nfev += 1
-            self.old_fval, self.gnorm = f, gmax
-            self._after = 'init'
-            self.pending, self.request = (L.BFGS_INIT, 0.0), None
-        elif self.phase == 'ls':
-            self.nfev += 1
-            self.phi1, self.derphi1, self.gmax_t = f, dphi, gmax
-            self._ls_step()
-        elif self.phase == 'ls2':
-            self.nfev += 1
-            self.gmax_t = gmax
-            self.ls2.answer(f, dphi)
-            self._ls2_advance()
-        elif self.phase == 'reeval':                    # the accepted step was not the last one evaluated: its gradient, not counted
-            self.gmax_t = gmax
-            self._step_taken(self.alpha_k, self.new_fval)
-        else:
-            raise RuntimeError('feed() on a finished window')
-
-    def accepted(self, scal):
-        """The scalars of the iterate the state has just moved to (what ``pending`` asked for)."""
-        self.pending = None
-        self.scal = scal
-        self.xnan = bool(np.isnan(scal[L.BFGS_S_XMAX]))
-        if self._after == 'init':
-            self.old_old_fval = self.old_fval + scal[L.BFGS_S_GNORM] / 2          # initial step guess dx ~ 1
-            self._begin_iteration()
-        elif self._after == 'iterate':
-            self._begin_iteration()
-        else:
-            self._finish()
-
-    def _begin_iteration(self):
-        if not (self.gnorm > self.gtol and self.k < self.maxiter):
-            return self._finish()
-        derphi0 = float(self.scal[L.BFGS_S_DPHI0])
-        self.pnorm = self.scal[L.BFGS_S_PNORM]
-        if self.old_old_fval is not None and derphi0 != 0:
-            alpha1 = min(1.0, 1.01 * 2 * (self.old_fval - self.old_old_fval) / derphi0)
-            if alpha1 < 0:
-                alpha1 = 1.0
-        else:
-            alpha1 = 1.0
-        self.dcsrch = DCSRCH(None, None, _BFGS_C1, _BFGS_C2, _BFGS_XTOL, _BFGS_AMIN, _BFGS_AMAX)
-        self.task, self.alpha1, self.phi1, self.derphi1, self.derphi0 = b'START', alpha1, self.old_fval, derphi0, derphi0
-        self.gmax_t = self.gnorm
-        self.ls_iter = 0
-        self._ls_step()
-
-    def _ls_step(self):
-        if self.ls_iter >= _LS_MAXITER:
-            return self._ls_done(None)
-        self.ls_iter += 1
-        stp, self.phi1, self.derphi1, self.task = self.dcsrch._iterate(self.alpha1, self.phi1, self.derphi1, self.task)
-        if not np.isfinite(stp):
-            return self._ls_done(None)
-        if self.task[:2] == b'FG':
-            self.alpha1 = stp
-            self.phase, self.request = 'ls', float(stp)
-            return
-        if self.task[:5] == b'ERROR' or self.task[:4] == b'WARN':
-            stp = None
-        self._ls_done(stp)
-
-    def _ls_done(self, stp):
-        if stp is not None:
-            return self._step_taken(stp, self.phi1)
-        if not self.wolfe2_fallback:
-            self.warnflag = 2
-            return self._finish()
-        # SciPy's second line search, line_search_wolfe2, is scalar_search_wolfe2 on phi(a) = f(xk + a pk) and derphi(a) = grad . pk with
-        # the gradient of the last derphi call kept for the caller.  The helper thread's f / fprime calls become this window's requests
-        # (_CoroutineCall): the point is the step a, the "gradient" phi'(a); its cache answers derphi(a) after phi(a) without an evaluation.
-        def search(fv, fg):
-            return scalar_search_wolfe2(lambda a: fv(a), lambda a: fg(a)[0], self.old_fval, self.old_old_fval, self.derphi0,
-                                        _BFGS_C1, _BFGS_C2, _BFGS_AMAX, None, maxiter=10)
-        self.ls2 = _CoroutineCall(search)
-        self._ls2_advance()
-
-    def _ls2_advance(self):
-        kind, payload = self.ls2.next()
-        if kind == 'request':
-            self.phase, self.request = 'ls2', float(payload)
-            return
-        alpha_star, phi_star, _, derphi_star = payload
-        if alpha_star is None:
-            self.warnflag = 2                                      # precision loss: no step satisfies the Wolfe conditions
-            return self._finish()
-        if derphi_star is None:                                    # (the search ran out of iterations: its last evaluation was elsewhere)
-            self.alpha_k, self.new_fval = float(alpha_star), phi_star
-            self.phase, self.request = 'reeval', float(alpha_star)
-            return
-        self._step_taken(float(alpha_star), phi_star)
-
-    def _step_taken(self, alpha_k, new_fval):
-        """The state's trial point is x + alpha_k p and its trial gradient the gradient there."""
-        self.old_fval, self.old_old_fval = new_fval, self.old_fval
-        self.k += 1
-        self.gnorm = self.gmax_t
-        self.request = None
-        if self.gnorm <= self.gtol or alpha_k * self.pnorm <= 0.0:      # converged / xrtol = 0: SciPy stops before it updates H
-            self._after, self.pending = 'finish', (L.BFGS_MOVE, alpha_k)
-        elif not np.isfinite(self.old_fval):
-            self.warnflag = 2
-            self._after, self.pending = 'finish', (L.BFGS_MOVE, alpha_k)
-        else:
-            self._after, self.pending = 'iterate', (L.BFGS_UPDATE, alpha_k)
-        self.stepped = True
-
-    def _finish(self):
-        if self.warnflag == 2:
-            pass
-        elif self.k >= self.maxiter:
-            self.warnflag = 1
-        elif np.isnan(self.gnorm) or np.isnan(self.old_fval) or self.xnan:
-            self.warnflag = 3
-        self.phase, self.request, self.done = 'done', None, True
-
-
 class DeviceLockstepBFGS:
     """``LockstepBFGS`` over a state object (``NumpyBFGSState`` / ``DeviceBFGSState``): B scalar-driven minimisations; every tick is one
     ``state.eval`` for all the windows that asked and at most one ``state.accept`` for those whose line search ended.  ``callbacks[b]``
@@ -715,7 +653,7 @@ class DeviceLockstepBFGS:
         maxiters = np.broadcast_to(np.asarray(maxiter), (self.B,))
         self.callbacks = callbacks if callbacks is not None else [None] * self.B
         self.needs_x = callback_needs_x if callback_needs_x is not None else [True] * self.B
-        self.windows = [(_ScalarWindowBFGS(maxiters[b], gtol, self.n, wolfe2_fallback) if self.active[b] else None) for b in range(self.B)]
+        self.windows = [(_BFGSMachine(maxiters[b], gtol, self.n, wolfe2_fallback) if self.active[b] else None) for b in range(self.B)]
         self.want_hess_inv = want_hess_inv
         self.n_batch_evals = 0
         self.n_window_evals = 0

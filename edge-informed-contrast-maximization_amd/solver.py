@@ -30,10 +30,10 @@ class ScipyMinimize:
 
     def __init__(self, fun, method=None, maxiter=500, jit=True, has_aux=False, options=None, callback=None, tol=None,
                  dtype=np.float64, value_and_grad=True, bfgs_update='scipy', wolfe2_fallback=True):
-        """bfgs_update (method 'BFGS' only): 'scipy' = scipy.optimize.minimize itself; 'rank2' = the same algorithm restated in
-        batch_solver.LockstepBFGS, whose inverse-Hessian update costs O(n^2) instead of SciPy's two n x n products - identical iterates
-        up to 64 unknowns, equal to rounding beyond (at a 16x16 theta, n = 512, SciPy's update takes 10 ms per iteration, the
-        evaluation 0.1 ms)."""
+        """bfgs_update (method 'BFGS' only): 'scipy' = scipy.optimize.minimize itself; 'rank2' = the same algorithm as batch_solver
+        restates it (LockstepBFGS with one window, over its one state machine), whose inverse-Hessian update costs O(n^2) instead of
+        SciPy's two n x n products - identical iterates up to 64 unknowns, equal to rounding beyond (at a 16x16 theta, n = 512,
+        SciPy's update takes 10 ms per iteration, the evaluation 0.1 ms)."""
         if not value_and_grad:
             raise ValueError('this wrapper needs fun to return (value, grad): the HIP engine cannot be differentiated by tracing')
         if bfgs_update not in ('scipy', 'rank2'):

@@ -1,11 +1,11 @@
 """The bench's c4_solve workload (8 x [260x346, 1e6 events, R = 5], pyramid 1..16, BFGS budget 40/28/19/11/8 + 1 retry at levels 0 and
-1, n_groups = 1) with the BFGS state on the host or in HBM: whole-solve seconds and, per pyramid level, the seconds per engine call
+1) with the BFGS state on the host or in HBM: whole-solve seconds and, per pyramid level, the seconds per engine call
 (level wall time / lockstep ticks: the evaluation plus the solver's bookkeeping around it).  Whole-solve times swing with which line
 searches fail, so the per-call time at levels 1 and 0 is the figure to compare.
 
-    python3 tools/dev_device_bfgs_timing.py --state host|device [--runs 5] [--root CHECKOUT] [--out FILE.json]
+    python3 tools/dev_device_bfgs_timing.py --state host|device [--groups 1] [--runs 5] [--root CHECKOUT] [--out FILE.json]
 
---root: import the package from another checkout (e.g. the parent commit, built there; it needs --state host: the keyword is not
+--groups: engine contexts the windows are spread over (the pipelined lockstep; 'device' takes 1 only).  --root: import the package from another checkout (e.g. the parent commit, built there; it needs --state host: the keyword is not
 passed then).  Each invocation is one process: one warm-up solve, then --runs timed ones, each on a fresh solver with staging outside
 the timer (a solve ends in a stream synchronise).  Prints one JSON line."""
 import argparse
@@ -20,6 +20,7 @@ import numpy as np
 ap = argparse.ArgumentParser()
 ap.add_argument('--state', choices=('host', 'device'), default='device')
 ap.add_argument('--runs', type=int, default=5)
+ap.add_argument('--groups', type=int, default=1)
 ap.add_argument('--root', default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument('--out', default=None)
 ap.add_argument('--events', type=int, default=1_000_000)
@@ -35,6 +36,8 @@ loss = dict(alpha=20.0, beta=35.0, gamma=0.0, delta=0.0, scale_to_sensor_size_me
 maxit = sol.growing_maxiters(n_lvls, 40 / 5, 40)
 sp = {'method': 'BFGS', 'options': {'gtol': 1e-7}, 'n_extra_attempts': {'pyr_lvl_0': 1, 'pyr_lvl_1': 1}}
 kw = {'bfgs_state': 'device'} if a.state == 'device' else {}
+if a.groups != 1:
+    kw['n_groups'] = a.groups
 
 
 def one_solve():
@@ -59,7 +62,7 @@ def one_solve():
 
 one_solve()                                        # warm-up: code objects, every theta shape
 runs = [one_solve() for _ in range(a.runs)]
-res = {'state': a.state, 'root': os.path.abspath(a.root), 'runs': a.runs,
+res = {'state': a.state, 'n_groups': a.groups, 'root': os.path.abspath(a.root), 'runs': a.runs,
        'solve_s': [r[0] for r in runs], 'engine_calls': runs[0][3], 'level0_fun': runs[0][2],
        'levels': {str(k): {'seconds': [r[1][k][0] for r in runs], 'engine_calls': runs[0][1][k][1],
                            'us_per_call': [1e6 * r[1][k][0] / max(r[1][k][1], 1) for r in runs]} for k in sorted(runs[0][1])}}
