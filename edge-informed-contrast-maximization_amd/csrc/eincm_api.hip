@@ -87,10 +87,18 @@ template <typename T, bool PINNED = false> struct Grow {
     size_t n = 0;
 };
 
-// Lays out the pieces of one operator's scratch: add returns the 256-byte-aligned offset of a piece, total is what ensure is asked for.
-struct Carve {
-    size_t total = 0;
-    size_t add(size_t bytes) { const size_t off = total; total += (bytes + 255) & ~(size_t)255; return off; }
+// Packs host arrays into one block for a single upload: add appends `bytes` at the next multiple of `align` (zero padding) and returns
+// their offset; i32 / f64 form a typed pointer into a copy of the block.
+struct Packer {
+    std::vector<char> buf;
+    size_t add(const void* p, size_t bytes, size_t align = 1) {
+        const size_t off = (buf.size() + align - 1) / align * align;
+        buf.resize(off + bytes, 0);
+        if (bytes) std::memcpy(buf.data() + off, p, bytes);
+        return off;
+    }
+    static const int32_t* i32(const char* base, size_t off) { return reinterpret_cast<const int32_t*>(base + off); }
+    static const double* f64(const char* base, size_t off) { return reinterpret_cast<const double*>(base + off); }
 };
 
 // A segment list: the binned events of every (window, source tile) cut into segments of at most `seg` events (balanced_seg_len), the
@@ -267,22 +275,27 @@ struct eincm_ctx {
     Grow<double, true> h_ovals;    // (maxB,maxR,2) pinned: contrast and signed correlation of every image (k_obj_grad), allocated on first use
 
     // The one scratch block of the one-shot operators (edge smoothing, Canny, preprocessing, ground-truth flow, the DSEC data path,
-    // warped events, tiled objectives, the transients of the flow-error evaluation).  An operator lays out its pieces (Carve), grows the block once and drains the stream before
-    // it returns, so nothing in here outlives a call.  What a later call reads has a buffer of its own:
+    // warped events, tiled objectives, the transients of the flow-error evaluation).  An operator takes its pieces of it through its call
+    // frame (OneShot), which grows the block once and drains the stream on every exit, so nothing in here outlives a call.  What a later
+    // call reads has a buffer of its own:
     Grow<char> scratch;
-    // the NL-means weight table of eincm_preprocess_image, kept for the (template, search, h^2) it was built for
-    Grow<int32_t> p_nlm;
-    std::vector<int32_t> h_pre_tab, h_nlm_tab;
-    float nlm_hh = 0.0f;
-    int nlm_tw = 0, nlm_sw = 0;
-    // the rounded rectify map of eincm_rectify_events packed as int16 pairs, kept from the call that handed a map over
-    Grow<uint32_t> r_map;
-    bool rect_map_set = false;
+    struct {                           // eincm_preprocess_image
+        Grow<int32_t> p_nlm;           // the NL-means weight table, kept for the (template, search, h^2) it was built for
+        std::vector<int32_t> h_pre_tab, h_nlm_tab;   // host sides of the per-call tables and of p_nlm (uploads read them)
+        float nlm_hh = 0.0f;
+        int nlm_tw = 0, nlm_sw = 0;
+    } pre;
+    struct {                           // eincm_rectify_events
+        Grow<uint32_t> r_map;          // the rounded rectify map packed as int16 pairs, kept from the call that handed a map over
+        bool rect_map_set = false;
+    } rect;
     // the staged flow evaluation of eincm_flow_eval_stage: [GT flow (n, H, W) double2 | flag bytes (n, H, W)],
     // kept from one staging to the next; every eincm_flow_errors reads it
-    Grow<char> f_eval;
-    int fe_n = 0;                  // windows of the staged flow evaluation (0: none)
-    std::vector<int64_t> fe_ngt;   // (fe_n) GT-valid pixels of every window
+    struct {
+        Grow<char> f_eval;
+        int fe_n = 0;                  // windows of the staged flow evaluation (0: none)
+        std::vector<int64_t> fe_ngt;   // (fe_n) GT-valid pixels of every window
+    } fe;
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
@@ -423,8 +436,41 @@ int not_in_flight(eincm_ctx* c, const char* who) {
     return EINCM_OK;
 }
 
-// One piece of the scratch block (Carve::add gave its offset)
-template <typename T> T* carved(eincm_ctx* c, size_t off) { return reinterpret_cast<T*>(c->scratch.p + off); }
+// The call frame of a one-shot operator.  After its argument checks an operator declares the pieces of c->scratch
+// it needs (piece) and the host memory its downloads land in (host_buf), grows the block once (begin), and puts every command on the
+// stream through the frame.  The destructor drains the stream on every exit that sync() has not drained already, and the members are
+// freed after it: no exit leaves work on the block, or a copy in flight on host memory of the call.  Host memory an asynchronous copy
+// touches is therefore the caller's, the context's, a host_buf, or (upload sources only) a local declared before the frame.
+struct OneShot {
+    eincm_ctx* c; size_t total = 0; bool pending = false;
+    std::vector<std::vector<char>> host;
+    explicit OneShot(eincm_ctx* c_) : c(c_) {}
+    OneShot(const OneShot&) = delete;
+    ~OneShot() { if (pending) (void)hipStreamSynchronize(c->stream); }
+    // A piece resolves its pointer when it is used, so the block cannot be read before begin() has grown it
+    template <typename T> struct Piece {
+        const OneShot* op; size_t off; bool on;
+        operator T*() const { return on ? reinterpret_cast<T*>(op->c->scratch.p + off) : nullptr; }
+    };
+    // n elements at the next 256-byte-aligned offset; a piece that is not wanted takes no bytes and is null
+    template <typename T> Piece<T> piece(size_t n, bool wanted = true) {
+        const size_t off = total;
+        if (wanted) total += (n * sizeof(T) + 255) & ~(size_t)255;
+        return {this, off, wanted};
+    }
+    template <typename T> T* host_buf(size_t n) { host.emplace_back(n * sizeof(T), 0); return reinterpret_cast<T*>(host.back().data()); }
+    hipError_t begin() { if (const hipError_t e = hipSetDevice(c->device)) return e; return ensure(c, c->scratch, total); }
+    hipError_t up(void* dst, const void* src, size_t bytes) { pending = true; return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream); }
+    hipError_t down(void* dst, const void* src, size_t bytes) { pending = true; return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream); }
+    hipError_t zero(void* dst, size_t bytes) { pending = true; return hipMemsetAsync(dst, 0, bytes, c->stream); }
+    // every argument is cast to the kernel's own parameter type (a Piece<T> to T* or const T*, a void* to any object pointer)
+    template <typename... P, typename... A> hipError_t launch(void (*k)(P...), dim3 grid, dim3 block, size_t lds, A&&... a) {
+        pending = true;
+        hipLaunchKernelGGL(k, grid, block, lds, c->stream, static_cast<P>(a)...);
+        return hipGetLastError();
+    }
+    hipError_t sync() { pending = false; return hipStreamSynchronize(c->stream); }
+};
 
 // ---------------------------------------------------------------------------------------------
 // jax.image.scale_and_translate per-axis weight matrix (S7; theta_utils.py:25-35), fp64 on the host.
@@ -2484,29 +2530,30 @@ int eincm_get_count_images(eincm_ctx* c, uint32_t* counts) {
     if (!c) return EINCM_ERR_ARG;
     if (!counts) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (!c->staged || !c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
-    HIPCHK(c, hipSetDevice(c->device));
     { const int rc = ensure_theta_image(c); if (rc) return rc; }
     const Geom& g = c->g;
     const size_t n = (size_t)g.B * g.R * g.H * g.W;
     // the dL/dIWE buffer is free between evaluations and has exactly this many 4-byte cells
     uint32_t* d = reinterpret_cast<uint32_t*>(c->d_G);
+    OneShot op(c);                                  // no piece of the scratch: the frame is here for its drain
+    HIPCHK(c, op.begin());
     if (!c->fp64) c->G_valid = false;               // (an fp64 context keeps dL/dIWE in its own buffer)
-    HIPCHK(c, hipMemsetAsync(d, 0, n * sizeof(uint32_t), c->stream));
+    HIPCHK(c, op.zero(d, n * sizeof(uint32_t)));
     const SegList& L = c->gather;
     if (L.n > 0)
-        hipLaunchKernelGGL(k_count, dim3(L.grid(g.R)), dim3(NT), 0, c->stream, g, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta,
-                           c->d_edge_ts, d);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(counts, d, n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, op.launch(k_count, dim3(L.grid(g.R)), dim3(NT), 0, g, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, d));
+    HIPCHK(c, op.down(counts, d, n * sizeof(uint32_t)));          // (host memory: the caller's)
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // SURVEY row f-4 (eincm_edges.hip.h, eincm_canny.hip.h)
 // ---------------------------------------------------------------------------------------------
-// The one-shot operators below share c->scratch: each lays out its pieces (Carve), grows the block once, before its first launch, and
-// drains the stream before it returns, so no call finds another's work on the block still enqueued.
+// The one-shot operators below share c->scratch through one call frame each (OneShot): state and argument checks first; then the frame,
+// its pieces and host buffers; begin() grows the block once, before the first command; every command goes onto the stream through the
+// frame, which drains it on every way out, failures included, so no call finds another's work on the block still enqueued.  Before the
+// frame only a return that had reached its last synchronisation drained.  Each copy says whose host memory it touches.
 
 // 'warped_xs' / 'warped_ys' of compute_loss_objectives (losses.py:58,90-91) for one window under the last evaluation's theta
 int eincm_get_warped_events(eincm_ctx* c, int window, double* warped_xs, double* warped_ys) {
@@ -2515,23 +2562,21 @@ int eincm_get_warped_events(eincm_ctx* c, int window, double* warped_xs, double*
     if (!c->staged || !c->have_eval) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
     const Geom& g = c->g;
     if (window < 0 || window >= g.B) return fail(c, EINCM_ERR_ARG, "window %d of %d", window, g.B);
-    HIPCHK(c, hipSetDevice(c->device));
     { const int rc = ensure_theta_image(c); if (rc) return rc; }
     const int64_t n = c->win_events[window];
     if (n == 0) return EINCM_OK;
     int64_t off = 0;
     for (int b = 0; b < window; ++b) off += c->win_events[b];
-    const size_t bytes = (size_t)g.R * (size_t)n * sizeof(double);
-    HIPCHK(c, ensure(c, c->scratch, 2 * bytes));
-    double* dx = carved<double>(c, 0);
-    double* dy = dx + (size_t)g.R * (size_t)n;
+    const size_t cells = (size_t)g.R * (size_t)n;
+    OneShot op(c);
+    const auto dx = op.piece<double>(cells), dy = op.piece<double>(cells);
+    HIPCHK(c, op.begin());
     const int grid = (int)std::min<int64_t>((n + NT - 1) / NT, 8192);
-    hipLaunchKernelGGL(k_warp_events, dim3(grid), dim3(NT), 0, c->stream, g, window, (long long)n, c->d_raw_x + off, c->d_raw_y + off,
-                       c->d_raw_t + off, c->d_Theta, c->d_edge_ts, dx, dy);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(warped_xs, dx, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(warped_ys, dy, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, op.launch(k_warp_events, dim3(grid), dim3(NT), 0, g, window, n, c->d_raw_x + off, c->d_raw_y + off, c->d_raw_t + off,
+                        c->d_Theta, c->d_edge_ts, dx, dy));
+    HIPCHK(c, op.down(warped_xs, dx, cells * sizeof(double)));    // (host memory: the caller's, both)
+    HIPCHK(c, op.down(warped_ys, dy, cells * sizeof(double)));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
@@ -2545,37 +2590,32 @@ int eincm_inv_dist_transform(eincm_ctx* c, const uint8_t* edge_img, int n, int f
         return fail(c, EINCM_ERR_ARG, "unknown formulation %d", formulation);
     if (out && formulation == EINCM_EDT_EXPONENTIAL && !(alpha > 0.0)) return fail(c, EINCM_ERR_ARG, "alpha = %g must be positive", alpha);
     if (out && formulation == EINCM_EDT_LINEAR_BOUND && !(d_sat > 0.0)) return fail(c, EINCM_ERR_ARG, "d_sat = %g must be positive", d_sat);
-    HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const size_t npix = (size_t)H * W, tot = npix * n;
-    Carve cv;
-    const size_t o_img = cv.add(tot), o_g = cv.add(tot * 4), o_sq = cv.add(tot * 4), o_misc = cv.add((size_t)n * 8), o_out = out ? cv.add(tot * 8) : 0;
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    uint8_t* d_img = carved<uint8_t>(c, o_img);
-    uint32_t* d_g = carved<uint32_t>(c, o_g);
-    int32_t* d_sq = carved<int32_t>(c, o_sq);
-    uint32_t* d_misc = carved<uint32_t>(c, o_misc);                   // [n] edge pixel count | [n] max squared distance
-    double* d_out = carved<double>(c, o_out);                         // (only where out is asked for)
-    HIPCHK(c, hipMemcpyAsync(d_img, edge_img, tot, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_misc, 0, (size_t)n * 8, c->stream));
+    OneShot op(c);
+    const auto d_img = op.piece<uint8_t>(tot);
+    const auto d_g = op.piece<uint32_t>(tot);
+    const auto d_sq = op.piece<int32_t>(tot);
+    const auto d_misc = op.piece<uint32_t>((size_t)n * 2);            // [n] edge pixel count | [n] max squared distance
+    const auto d_out = op.piece<double>(tot, out != nullptr);         // (only where out is asked for)
+    uint32_t* misc = op.host_buf<uint32_t>((size_t)n * 2);            // d_misc comes down here
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_img, edge_img, tot));                           // (host memory: the caller's, as sqdist and out below)
+    HIPCHK(c, op.zero(d_misc, (size_t)n * 8));
     const int gx = (W + NT - 1) / NT;
-    hipLaunchKernelGGL(k_edt_cols, dim3(gx, n), dim3(NT), 0, c->stream, H, W, (const uint8_t*)d_img, d_g, d_misc);
-    hipLaunchKernelGGL(k_edt_rows, dim3(gx, H, n), dim3(NT), 0, c->stream, H, W, (const uint32_t*)d_g, d_sq, d_misc + n);
-    HIPCHK(c, hipGetLastError());
-    std::vector<uint32_t> misc((size_t)n * 2);
-    HIPCHK(c, hipMemcpyAsync(misc.data(), d_misc, misc.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, op.launch(k_edt_cols, dim3(gx, n), dim3(NT), 0, H, W, d_img, d_g, d_misc));
+    HIPCHK(c, op.launch(k_edt_rows, dim3(gx, H, n), dim3(NT), 0, H, W, d_g, d_sq, d_misc + n));
+    HIPCHK(c, op.down(misc, d_misc, (size_t)n * 8));
+    HIPCHK(c, op.sync());
     for (int i = 0; i < n; ++i)
         if (misc[i] == 0) return fail(c, EINCM_ERR_ARG, "edge image %d has no edge pixel: its distance transform is undefined", i);
-    if (sqdist) HIPCHK(c, hipMemcpyAsync(sqdist, d_sq, tot * 4, hipMemcpyDeviceToHost, c->stream));
+    if (sqdist) HIPCHK(c, op.down(sqdist, d_sq, tot * 4));
     if (out) {
         const int nb = (int)std::min<size_t>((npix + NT - 1) / NT, 1024);
-        hipLaunchKernelGGL(k_edt_finish, dim3(nb, n), dim3(NT), 0, c->stream, (int64_t)npix, (const int32_t*)d_sq, d_misc + n, formulation,
-                           alpha, d_sat, d_out);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(out, d_out, tot * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, op.launch(k_edt_finish, dim3(nb, n), dim3(NT), 0, npix, d_sq, d_misc + n, formulation, alpha, d_sat, d_out));
+        HIPCHK(c, op.down(out, d_out, tot * 8));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
@@ -2594,23 +2634,20 @@ int eincm_gaussian_blur(eincm_ctx* c, const double* src, int n, double sigma, do
     double sum = 0.0;
     for (int i = 0; i < taps; ++i) { const double x = i - (taps - 1) * 0.5; k[i] = std::exp(-0.5 / (sigma * sigma) * x * x); sum += k[i]; }
     for (double& v : k) v /= sum;
-    HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const size_t tot = (size_t)H * W * n;
-    Carve cv;
-    const size_t o_a = cv.add(tot * 8), o_b = cv.add(tot * 8), o_kern = cv.add((size_t)BLUR_MAX_TAPS * 8);
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    double* d_a = carved<double>(c, o_a);                  // the source, then the result
-    double* d_b = carved<double>(c, o_b);                  // the row pass
-    double* d_kern = carved<double>(c, o_kern);
-    HIPCHK(c, hipMemcpyAsync(d_kern, k.data(), k.size() * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_a, src, tot * 8, hipMemcpyHostToDevice, c->stream));
+    OneShot op(c);
+    const auto d_a = op.piece<double>(tot);                // the source, then the result
+    const auto d_b = op.piece<double>(tot);                // the row pass
+    const auto d_kern = op.piece<double>(BLUR_MAX_TAPS);
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_kern, k.data(), k.size() * 8));      // (host memory: k, a local older than the frame)
+    HIPCHK(c, op.up(d_a, src, tot * 8));                   // (the caller's, as dst)
     const dim3 grid((W + NT - 1) / NT, H, n);
-    hipLaunchKernelGGL(k_blur, grid, dim3(NT), 0, c->stream, H, W, 0, radius, (const double*)d_kern, (const double*)d_a, d_b);
-    hipLaunchKernelGGL(k_blur, grid, dim3(NT), 0, c->stream, H, W, 1, radius, (const double*)d_kern, (const double*)d_b, d_a);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, d_a, tot * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // k (host vector) stays alive until here
+    HIPCHK(c, op.launch(k_blur, grid, dim3(NT), 0, H, W, 0, radius, d_kern, d_a, d_b));
+    HIPCHK(c, op.launch(k_blur, grid, dim3(NT), 0, H, W, 1, radius, d_kern, d_b, d_a));
+    HIPCHK(c, op.down(dst, d_a, tot * 8));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
@@ -2632,25 +2669,22 @@ int eincm_canny(eincm_ctx* c, const uint8_t* src, int n, double threshold1, doub
         if (threshold2 > 0) threshold2 *= threshold2;
     }
     const int low = (int)std::floor(threshold1), high = (int)std::floor(threshold2);
-    HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const size_t npix = (size_t)H * W, tot = npix * n;
-    Carve cv;
-    const size_t o_img = cv.add(tot), o_parent = cv.add(tot * 4), o_state = cv.add(tot);
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    uint8_t* d_img = carved<uint8_t>(c, o_img);                    // the source, then the edge image
-    int32_t* d_parent = carved<int32_t>(c, o_parent);
-    uint8_t* d_state = carved<uint8_t>(c, o_state);
-    HIPCHK(c, hipMemcpyAsync(d_img, src, tot, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_canny_nms, dim3((W + CANNY_TW - 1) / CANNY_TW, (H + CANNY_TH - 1) / CANNY_TH, n), dim3(NT), 0, c->stream,
-                       H, W, low, high, l2_gradient ? 1 : 0, d_img, d_state, d_parent);
+    OneShot op(c);
+    const auto d_img = op.piece<uint8_t>(tot);                     // the source, then the edge image
+    const auto d_parent = op.piece<int32_t>(tot);
+    const auto d_state = op.piece<uint8_t>(tot);
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_img, src, tot));                             // (host memory: the caller's, as dst)
+    HIPCHK(c, op.launch(k_canny_nms, dim3((W + CANNY_TW - 1) / CANNY_TW, (H + CANNY_TH - 1) / CANNY_TH, n), dim3(NT), 0, H, W, low, high,
+                        l2_gradient ? 1 : 0, d_img, d_state, d_parent));
     const dim3 grid((unsigned)std::min<size_t>((npix + NT - 1) / NT, 1024), n);
-    hipLaunchKernelGGL(k_canny_merge, grid, dim3(NT), 0, c->stream, H, W, d_state, d_parent);
-    hipLaunchKernelGGL(k_canny_resolve, grid, dim3(NT), 0, c->stream, H, W, d_state, d_parent);
-    hipLaunchKernelGGL(k_canny_output, grid, dim3(NT), 0, c->stream, H, W, d_state, d_parent, d_img);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, d_img, tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, op.launch(k_canny_merge, grid, dim3(NT), 0, H, W, d_state, d_parent));
+    HIPCHK(c, op.launch(k_canny_resolve, grid, dim3(NT), 0, H, W, d_state, d_parent));
+    HIPCHK(c, op.launch(k_canny_output, grid, dim3(NT), 0, H, W, d_state, d_parent, d_img));
+    HIPCHK(c, op.down(dst, d_img, tot));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
@@ -2705,7 +2739,7 @@ int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_
     }
 
     // ---- host tables (in h_pre_tab: unsharp taps, then bilateral colour weights, tap offsets and tap weights as float bits)
-    std::vector<int32_t>& T = c->h_pre_tab;
+    std::vector<int32_t>& T = c->pre.h_pre_tab;
     T.clear();
     int un_r = 0, bil_n = 0;
     size_t off_cw = 0, off_ofs = 0, off_w = 0;
@@ -2763,26 +2797,25 @@ int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_
         }
     }
 
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t npix = (size_t)H * W, tot = npix * n;
     // two uint8 stacks, and per stage: the per-call tables, the CLAHE LUTs, the unsharp mask's row pass
-    Carve cv;
-    const size_t o_img[2] = {cv.add(tot), cv.add(tot)}, o_tab = cv.add(T.size() * 4);
-    const size_t o_lut = (st & EINCM_PRE_CLAHE) ? cv.add((size_t)n * tx * ty * CLAHE_BINS) : 0;
-    const size_t o_rows = (st & EINCM_PRE_UNSHARP) ? cv.add(tot * 2) : 0;
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    int32_t* d_tab = carved<int32_t>(c, o_tab);
-    if (!T.empty()) HIPCHK(c, hipMemcpyAsync(d_tab, T.data(), T.size() * 4, hipMemcpyHostToDevice, c->stream));
+    OneShot op(c);
+    const OneShot::Piece<uint8_t> img[2] = {op.piece<uint8_t>(tot), op.piece<uint8_t>(tot)};
+    const auto d_tab = op.piece<int32_t>(T.size());
+    const auto lut = op.piece<uint8_t>((size_t)n * tx * ty * CLAHE_BINS, (st & EINCM_PRE_CLAHE) != 0);
+    const auto rows = op.piece<uint16_t>(tot, (st & EINCM_PRE_UNSHARP) != 0);
+    HIPCHK(c, op.begin());
+    if (!T.empty()) HIPCHK(c, op.up(d_tab, T.data(), T.size() * 4));        // (host memory: the context's, as the NL-means table)
     if (st & EINCM_PRE_NLMEANS) {
         const float hf = (float)p->denoise_h;
         const float hh = hf * hf;
-        if (c->nlm_tw != tw || c->nlm_sw != sw || c->nlm_hh != hh) {
+        if (c->pre.nlm_tw != tw || c->pre.nlm_sw != sw || c->pre.nlm_hh != hh) {
             // fastNlMeansDenoising's almost_dist2weight: fixed-point weights indexed by the template distance >> shift
             const int s = nlm_shift(tw);
             const int fpm = INT32_MAX / (sw * sw * 255);
             const double mult = (double)(1 << s) / (tw * tw);
             const int size = (int)(65025 / mult + 1);
-            std::vector<int32_t>& N = c->h_nlm_tab;
+            std::vector<int32_t>& N = c->pre.h_nlm_tab;
             N.assign((size_t)size, 0);
             for (int a = 0; a < size; ++a) {
                 const double dist = a * mult;
@@ -2790,55 +2823,46 @@ int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_
                 const double wi = std::nearbyint(fpm * w);
                 N[a] = wi < 0.001 * fpm ? 0 : (int32_t)wi;
             }
-            c->nlm_tw = 0;                                   // invalid until the upload is queued
-            HIPCHK(c, ensure(c, c->p_nlm, N.size()));
-            HIPCHK(c, hipMemcpyAsync(c->p_nlm.p, N.data(), N.size() * 4, hipMemcpyHostToDevice, c->stream));
-            c->nlm_tw = tw; c->nlm_sw = sw; c->nlm_hh = hh;
+            c->pre.nlm_tw = 0;                               // invalid until the upload is queued
+            HIPCHK(c, ensure(c, c->pre.p_nlm, N.size()));
+            HIPCHK(c, op.up(c->pre.p_nlm.p, N.data(), N.size() * 4));
+            c->pre.nlm_tw = tw; c->pre.nlm_sw = sw; c->pre.nlm_hh = hh;
         }
     }
 
     int cur = 0;
-    uint8_t* img[2] = {carved<uint8_t>(c, o_img[0]), carved<uint8_t>(c, o_img[1])};
-    HIPCHK(c, hipMemcpyAsync(img[0], src, tot, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, op.up(img[0], src, tot));                                      // (the caller's, as dst)
     const dim3 rows_grid((W + NT - 1) / NT, H, n);
     if (st & EINCM_PRE_NLMEANS) {
         const int b = sw / 2 + tw / 2;
         const size_t lds = (size_t)(NLM_TH + 2 * b) * (NLM_TW + 2 * b) * 4;
         const dim3 grid((W + NLM_TW - 1) / NLM_TW, (H + NLM_TH - 1) / NLM_TH, n);
-        const int32_t* tab = c->p_nlm.p;
-        switch (tw) {
-            case 1: hipLaunchKernelGGL(k_nlm<1>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
-            case 3: hipLaunchKernelGGL(k_nlm<3>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
-            case 5: hipLaunchKernelGGL(k_nlm<5>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
-            default: hipLaunchKernelGGL(k_nlm<7>, grid, dim3(NT), lds, c->stream, H, W, sw / 2, tab, img[cur], img[cur ^ 1]); break;
-        }
+        static_assert(NLM_MAX_TEMPLATE == 7, "one k_nlm per odd template window");
+        decltype(&k_nlm<1>) const k[] = {k_nlm<1>, k_nlm<3>, k_nlm<5>, k_nlm<7>};
+        HIPCHK(c, op.launch(k[tw / 2], grid, dim3(NT), lds, H, W, sw / 2, c->pre.p_nlm.p, img[cur], img[cur ^ 1]));
         cur ^= 1;
     }
     if (st & EINCM_PRE_CLAHE) {
-        uint8_t* lut = carved<uint8_t>(c, o_lut);
-        hipLaunchKernelGGL(k_clahe_lut, dim3(tx, ty, n), dim3(NT), 0, c->stream, H, W, clahe_th, clahe_tw, clahe_limit, img[cur], lut);
-        hipLaunchKernelGGL(k_clahe_interp, rows_grid, dim3(NT), 0, c->stream, H, W, clahe_th, clahe_tw, tx, ty, lut, img[cur],
-                           img[cur ^ 1]);
+        HIPCHK(c, op.launch(k_clahe_lut, dim3(tx, ty, n), dim3(NT), 0, H, W, clahe_th, clahe_tw, clahe_limit, img[cur], lut));
+        HIPCHK(c, op.launch(k_clahe_interp, rows_grid, dim3(NT), 0, H, W, clahe_th, clahe_tw, tx, ty, lut, img[cur], img[cur ^ 1]));
         cur ^= 1;
     }
     if (st & EINCM_PRE_UNSHARP) {
-        uint16_t* rows = carved<uint16_t>(c, o_rows);
-        hipLaunchKernelGGL(k_unsharp_rows, rows_grid, dim3(NT), 0, c->stream, H, W, un_r, d_tab, img[cur], rows);
-        hipLaunchKernelGGL(k_unsharp_cols, rows_grid, dim3(NT), 0, c->stream, H, W, un_r, d_tab, (float)p->sharpen_alpha,
-                           (float)p->sharpen_beta, rows, img[cur], img[cur ^ 1]);
+        HIPCHK(c, op.launch(k_unsharp_rows, rows_grid, dim3(NT), 0, H, W, un_r, d_tab, img[cur], rows));
+        HIPCHK(c, op.launch(k_unsharp_cols, rows_grid, dim3(NT), 0, H, W, un_r, d_tab, p->sharpen_alpha, p->sharpen_beta, rows, img[cur],
+                            img[cur ^ 1]));
         cur ^= 1;
     }
     if (st & EINCM_PRE_BILATERAL) {
         const size_t lds = (size_t)(BIL_TH + 2 * bil_r) * (BIL_TW + 2 * bil_r) * 4;
         const dim3 grid((W + BIL_TW - 1) / BIL_TW, (H + BIL_TH - 1) / BIL_TH, n);
-        hipLaunchKernelGGL(k_bilateral, grid, dim3(NT), lds, c->stream, H, W, bil_r, bil_n, d_tab + off_ofs,
-                           reinterpret_cast<const float*>(d_tab + off_w), reinterpret_cast<const float*>(d_tab + off_cw), img[cur],
-                           img[cur ^ 1]);
+        HIPCHK(c, op.launch(k_bilateral, grid, dim3(NT), lds, H, W, bil_r, bil_n, d_tab + off_ofs,
+                            reinterpret_cast<const float*>(d_tab + off_w), reinterpret_cast<const float*>(d_tab + off_cw), img[cur],
+                            img[cur ^ 1]));
         cur ^= 1;
     }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, img[cur], tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // the host tables stay alive (in the context) until here
+    HIPCHK(c, op.down(dst, img[cur], tot));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
@@ -2865,45 +2889,33 @@ int eincm_gt_flow(eincm_ctx* c, const void* gt_x, const void* gt_y, int elem_byt
                 return fail(c, EINCM_ERR_ARG, "window %d: den %g must be finite and non-zero", b, step_den[k]);
         }
     }
-    HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const size_t npix = (size_t)H * W, stack = (size_t)n_frames * npix * elem_bytes, n_steps = (size_t)step_off[n_windows];
-    // one upload for the step lists: mode | step_off | step_frame | (8-byte aligned) step_num | step_den
-    const size_t o_off = (size_t)n_windows * 4, o_frame = o_off + ((size_t)n_windows + 1) * 4;
-    const size_t o_num = (o_frame + n_steps * 4 + 7) & ~(size_t)7, o_den = o_num + n_steps * 8, tab_bytes = o_den + n_steps * 8;
-    std::vector<char> tab(tab_bytes, 0);
-    std::memcpy(tab.data(), mode, (size_t)n_windows * 4);
-    std::memcpy(tab.data() + o_off, step_off, ((size_t)n_windows + 1) * 4);
-    std::memcpy(tab.data() + o_frame, step_frame, n_steps * 4);
-    std::memcpy(tab.data() + o_num, step_num, n_steps * 8);
-    std::memcpy(tab.data() + o_den, step_den, n_steps * 8);
-    Carve cv;                                             // the x and y frame stacks, the step lists, the output
-    const size_t o_frames = cv.add(2 * stack), o_tab = cv.add(tab_bytes), o_out = cv.add((size_t)n_windows * npix * 16);
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    char* d_frames = carved<char>(c, o_frames);
-    char* d_tab = carved<char>(c, o_tab);
-    HIPCHK(c, hipMemcpyAsync(d_frames, gt_x, stack, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_frames + stack, gt_y, stack, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_tab, tab.data(), tab_bytes, hipMemcpyHostToDevice, c->stream));
-    const auto* d_mode = reinterpret_cast<const int32_t*>(d_tab);
-    const auto* d_off = reinterpret_cast<const int32_t*>(d_tab + o_off);
-    const auto* d_frame = reinterpret_cast<const int32_t*>(d_tab + o_frame);
-    const auto* d_num = reinterpret_cast<const double*>(d_tab + o_num);
-    const auto* d_den = reinterpret_cast<const double*>(d_tab + o_den);
-    double* d_out = carved<double>(c, o_out);
+    Packer tab;      // one upload for the step lists: mode | step_off | step_frame | (8-byte aligned) step_num | step_den
+    tab.add(mode, (size_t)n_windows * 4);
+    const size_t o_off = tab.add(step_off, ((size_t)n_windows + 1) * 4), o_frame = tab.add(step_frame, n_steps * 4);
+    const size_t o_num = tab.add(step_num, n_steps * 8, 8), o_den = tab.add(step_den, n_steps * 8);
+    OneShot op(c);                                        // the x and y frame stacks, the step lists, the output
+    const auto d_frames = op.piece<char>(2 * stack), d_tab = op.piece<char>(tab.buf.size());
+    const auto d_out = op.piece<double>((size_t)n_windows * npix * 2);
+    HIPCHK(c, op.begin());
+    const void* const d_x = d_frames;                     // (launch casts them to the kernel's element type)
+    const void* const d_y = d_frames + stack;
+    HIPCHK(c, op.up(d_frames, gt_x, stack));              // (host memory: the caller's, as out)
+    HIPCHK(c, op.up(d_frames + stack, gt_y, stack));
+    HIPCHK(c, op.up(d_tab, tab.buf.data(), tab.buf.size()));     // (tab, a local older than the frame)
     const unsigned gx = (unsigned)((npix + NT - 1) / NT);
     for (int w0 = 0; w0 < n_windows; w0 += GTF_MAX_WINDOWS_PER_LAUNCH) {
         const dim3 grid(gx, (unsigned)std::min(n_windows - w0, GTF_MAX_WINDOWS_PER_LAUNCH));
         if (elem_bytes == 4)
-            hipLaunchKernelGGL(k_gt_flow<float>, grid, dim3(NT), 0, c->stream, H, W, w0, reinterpret_cast<const float*>(d_frames),
-                               reinterpret_cast<const float*>(d_frames + stack), d_mode, d_off, d_frame, d_num, d_den, d_out);
+            HIPCHK(c, op.launch(k_gt_flow<float>, grid, dim3(NT), 0, H, W, w0, d_x, d_y, tab.i32(d_tab, 0), tab.i32(d_tab, o_off),
+                                tab.i32(d_tab, o_frame), tab.f64(d_tab, o_num), tab.f64(d_tab, o_den), d_out));
         else
-            hipLaunchKernelGGL(k_gt_flow<double>, grid, dim3(NT), 0, c->stream, H, W, w0, reinterpret_cast<const double*>(d_frames),
-                               reinterpret_cast<const double*>(d_frames + stack), d_mode, d_off, d_frame, d_num, d_den, d_out);
+            HIPCHK(c, op.launch(k_gt_flow<double>, grid, dim3(NT), 0, H, W, w0, d_x, d_y, tab.i32(d_tab, 0), tab.i32(d_tab, o_off),
+                                tab.i32(d_tab, o_frame), tab.f64(d_tab, o_num), tab.f64(d_tab, o_den), d_out));
     }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n_windows * npix * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // tab (host vector) stays alive until here
+    HIPCHK(c, op.down(out, d_out, (size_t)n_windows * npix * 16));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
@@ -2930,63 +2942,52 @@ int eincm_rectify_events(eincm_ctx* c, const float* rectify_map, const int16_t* 
     if (!n_kept) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (n < 0 || n > (int64_t)1 << 30) return fail(c, EINCM_ERR_ARG, "n = %lld outside [0, 2^30] (walk a recording in chunks)", (long long)n);
     if (n > 0 && (!x || !y || !rec_x || !rec_y || !keep)) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    if (!rectify_map && !c->rect_map_set) return fail(c, EINCM_ERR_STATE, "no rectify map: the first call must hand one over");
-    HIPCHK(c, hipSetDevice(c->device));
+    if (!rectify_map && !c->rect.rect_map_set) return fail(c, EINCM_ERR_STATE, "no rectify map: the first call must hand one over");
     const int H = c->H, W = c->W;
     const int64_t npix = (int64_t)H * W;
     // both phases are laid out before the block is grown, so it cannot move between them: the counters and, where a map comes along,
     // its float staging; then the chunk's coordinates in and out, the keep bytes, the block counts and offsets
     const int64_t nblk = (n + RECT_BLOCK - 1) / RECT_BLOCK;
-    Carve cv;
-    const size_t o_cnt = cv.add(4 * sizeof(unsigned long long)), o_fmap = rectify_map ? cv.add((size_t)npix * 8) : 0;
-    const size_t o_x = cv.add((size_t)n * 2), o_y = cv.add((size_t)n * 2), o_rx = cv.add((size_t)n * 2), o_ry = cv.add((size_t)n * 2);
-    const size_t o_keep = cv.add((size_t)n), o_bcnt = cv.add((size_t)nblk * 4), o_boff = cv.add((size_t)nblk * 8);
-    if (rectify_map) c->rect_map_set = false;
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    auto* d_cnt = carved<unsigned long long>(c, o_cnt);               // [0] refused map entries, [1] events outside the sensor, [2] kept
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, 4 * sizeof(unsigned long long), c->stream));
-    unsigned long long h_cnt[4] = {0, 0, 0, 0};
+    OneShot op(c);
+    const auto d_cnt = op.piece<unsigned long long>(4);               // [0] refused map entries, [1] events outside the sensor, [2] kept
+    const auto d_fmap = op.piece<float2>((size_t)npix, rectify_map != nullptr);
+    const auto d_x = op.piece<int16_t>((size_t)n), d_y = op.piece<int16_t>((size_t)n);
+    const auto d_rx = op.piece<int16_t>((size_t)n), d_ry = op.piece<int16_t>((size_t)n);
+    const auto d_keep = op.piece<uint8_t>((size_t)n);
+    const auto d_bcnt = op.piece<uint32_t>((size_t)nblk);
+    const auto d_boff = op.piece<int64_t>((size_t)nblk);
+    unsigned long long* h_cnt = op.host_buf<unsigned long long>(4);   // d_cnt comes down here, in either phase
+    if (rectify_map) c->rect.rect_map_set = false;
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.zero(d_cnt, 4 * sizeof(unsigned long long)));
     if (rectify_map) {
-        HIPCHK(c, ensure(c, c->r_map, (size_t)npix));
-        HIPCHK(c, hipMemcpyAsync(carved<float2>(c, o_fmap), rectify_map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_rect_map, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, c->stream, npix,
-                           (const float2*)carved<float2>(c, o_fmap), c->r_map.p, d_cnt);
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, ensure(c, c->rect.r_map, (size_t)npix));
+        HIPCHK(c, op.up(d_fmap, rectify_map, (size_t)npix * 8));      // (host memory: the caller's, as every copy below but h_cnt's)
+        HIPCHK(c, op.launch(k_rect_map, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, npix, d_fmap, c->rect.r_map.p, d_cnt));
+        HIPCHK(c, op.down(h_cnt, d_cnt, sizeof(unsigned long long)));
+        HIPCHK(c, op.sync());
         if (h_cnt[0]) return fail(c, EINCM_ERR_ARG, "rectify map: %llu of %lld entries are not finite or do not round into int16", h_cnt[0], (long long)npix);
-        c->rect_map_set = true;
+        c->rect.rect_map_set = true;
     }
     *n_kept = 0;
-    if (n == 0) { HIPCHK(c, hipStreamSynchronize(c->stream)); return EINCM_OK; }
-    int16_t* d_x = carved<int16_t>(c, o_x);
-    int16_t* d_y = carved<int16_t>(c, o_y);
-    int16_t* d_rx = carved<int16_t>(c, o_rx);
-    int16_t* d_ry = carved<int16_t>(c, o_ry);
-    uint8_t* d_keep = carved<uint8_t>(c, o_keep);
-    uint32_t* d_bcnt = carved<uint32_t>(c, o_bcnt);
-    int64_t* d_boff = carved<int64_t>(c, o_boff);
-    const uint32_t* d_map = c->r_map.p;
-    HIPCHK(c, hipMemcpyAsync(d_x, x, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_y, y, (size_t)n * 2, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_rect_count, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, (const int16_t*)d_x, (const int16_t*)d_y, d_map,
-                       d_keep, d_bcnt, d_cnt + 1);
-    hipLaunchKernelGGL(k_rect_scan, dim3(1), dim3(RECT_SCAN_NT), 0, c->stream, (int)nblk, (const uint32_t*)d_bcnt, d_boff,
-                       reinterpret_cast<int64_t*>(d_cnt + 2));
-    hipLaunchKernelGGL(k_rect_scatter, dim3((unsigned)nblk), dim3(NT), 0, c->stream, H, W, n, (const int16_t*)d_x, (const int16_t*)d_y, d_map,
-                       (const int64_t*)d_boff, d_rx, d_ry);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(h_cnt, d_cnt, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n == 0) { HIPCHK(c, op.sync()); return EINCM_OK; }
+    const uint32_t* d_map = c->rect.r_map.p;
+    HIPCHK(c, op.up(d_x, x, (size_t)n * 2));
+    HIPCHK(c, op.up(d_y, y, (size_t)n * 2));
+    HIPCHK(c, op.launch(k_rect_count, dim3((unsigned)nblk), dim3(NT), 0, H, W, n, d_x, d_y, d_map, d_keep, d_bcnt, d_cnt + 1));
+    HIPCHK(c, op.launch(k_rect_scan, dim3(1), dim3(RECT_SCAN_NT), 0, nblk, d_bcnt, d_boff, reinterpret_cast<int64_t*>(d_cnt + 2)));
+    HIPCHK(c, op.launch(k_rect_scatter, dim3((unsigned)nblk), dim3(NT), 0, H, W, n, d_x, d_y, d_map, d_boff, d_rx, d_ry));
+    HIPCHK(c, op.down(h_cnt, d_cnt, 4 * sizeof(unsigned long long)));
+    HIPCHK(c, op.sync());
     if (h_cnt[1]) return fail(c, EINCM_ERR_ARG, "%llu of %lld events have a coordinate outside the %dx%d sensor", h_cnt[1], (long long)n, H, W);
     const int64_t kept = (int64_t)h_cnt[2];
     if (kept < 0 || kept > n) return fail(c, EINCM_ERR_HIP, "kept count %lld of %lld events", (long long)kept, (long long)n);
-    HIPCHK(c, hipMemcpyAsync(keep, d_keep, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, op.down(keep, d_keep, (size_t)n));
     if (kept) {                                     // only the kept prefix comes back
-        HIPCHK(c, hipMemcpyAsync(rec_x, d_rx, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(rec_y, d_ry, (size_t)kept * 2, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, op.down(rec_x, d_rx, (size_t)kept * 2));
+        HIPCHK(c, op.down(rec_y, d_ry, (size_t)kept * 2));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, op.sync());
     *n_kept = kept;
     return EINCM_OK;
 }
@@ -3002,24 +3003,19 @@ int eincm_remap_cubic(eincm_ctx* c, const uint8_t* src, int n, int src_h, int sr
         for (int k = 0; k < 16; ++k) { const int32_t w = table[r * 16 + k]; if (w < -32768 || w > 32768) s = INT64_MIN / 2; s += w; }
         if (s != 32768) return fail(c, EINCM_ERR_ARG, "weight table row %d: weights within +-32768 that sum to 32768", r);
     }
-    HIPCHK(c, hipSetDevice(c->device));
     const int64_t npix = (int64_t)c->H * c->W;
-    const size_t sbytes = (size_t)n * src_h * src_w, dbytes = (size_t)n * npix, tbytes = 1024 * 16 * 4;
-    Carve cv;                  // (the float map is only staged here: the rounded rectify map lives in r_map and stays)
-    const size_t o_in = cv.add(sbytes), o_out = cv.add(dbytes), o_map = cv.add((size_t)npix * 8), o_tab = cv.add(tbytes);
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    uint8_t* d_in = carved<uint8_t>(c, o_in);
-    uint8_t* d_out = carved<uint8_t>(c, o_out);
-    float2* d_map = carved<float2>(c, o_map);
-    int32_t* d_tab = carved<int32_t>(c, o_tab);
-    HIPCHK(c, hipMemcpyAsync(d_in, src, sbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_map, map, (size_t)npix * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_tab, table, tbytes, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_remap_cubic, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, c->stream, n, src_h, src_w, npix,
-                       (const uint8_t*)d_in, (const float2*)d_map, (const int32_t*)d_tab, d_out);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(dst, d_out, dbytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const size_t sbytes = (size_t)n * src_h * src_w, dbytes = (size_t)n * npix;
+    OneShot op(c);             // (the float map is only staged here: the rounded rectify map lives in r_map and stays)
+    const auto d_in = op.piece<uint8_t>(sbytes), d_out = op.piece<uint8_t>(dbytes);
+    const auto d_map = op.piece<float2>((size_t)npix);
+    const auto d_tab = op.piece<int32_t>(1024 * 16);
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_in, src, sbytes));                              // (host memory: the caller's, all four)
+    HIPCHK(c, op.up(d_map, map, (size_t)npix * 8));
+    HIPCHK(c, op.up(d_tab, table, 1024 * 16 * 4));
+    HIPCHK(c, op.launch(k_remap_cubic, dim3((unsigned)((npix + NT - 1) / NT)), dim3(NT), 0, n, src_h, src_w, npix, d_in, d_map, d_tab, d_out));
+    HIPCHK(c, op.down(dst, d_out, dbytes));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 
@@ -3028,38 +3024,32 @@ int eincm_flow_decode(eincm_ctx* c, const uint16_t* flow16, int n, double* flow,
     if (!c) return EINCM_ERR_ARG;
     if (!flow16 || !flow || !valid || !n_bad) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (n < 1) return fail(c, EINCM_ERR_ARG, "n = %d (>= 1)", n);
-    HIPCHK(c, hipSetDevice(c->device));
     const int64_t tot = (int64_t)n * c->H * c->W;
-    Carve cv;
-    const size_t o_in = cv.add((size_t)tot * 6), o_flow = cv.add((size_t)tot * 16), o_valid = cv.add((size_t)tot), o_cnt = cv.add(sizeof(unsigned long long));
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    uint16_t* d_in = carved<uint16_t>(c, o_in);
-    double* d_flow = carved<double>(c, o_flow);
-    uint8_t* d_valid = carved<uint8_t>(c, o_valid);
-    auto* d_cnt = carved<unsigned long long>(c, o_cnt);
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in, flow16, (size_t)tot * 6, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_flow_decode, dim3((unsigned)((tot + NT - 1) / NT)), dim3(NT), 0, c->stream, tot, (const uint16_t*)d_in, d_flow,
-                       d_valid, d_cnt);
-    HIPCHK(c, hipGetLastError());
-    unsigned long long bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(flow, d_flow, (size_t)tot * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(valid, d_valid, (size_t)tot, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    *n_bad = (int64_t)bad;
-    if (bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a third channel that is neither 0 nor 1", bad);
+    OneShot op(c);
+    const auto d_in = op.piece<uint16_t>((size_t)tot * 3);
+    const auto d_flow = op.piece<double>((size_t)tot * 2);
+    const auto d_valid = op.piece<uint8_t>((size_t)tot);
+    const auto d_cnt = op.piece<unsigned long long>(1);
+    unsigned long long* bad = op.host_buf<unsigned long long>(1);     // d_cnt comes down here
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.zero(d_cnt, sizeof(unsigned long long)));
+    HIPCHK(c, op.up(d_in, flow16, (size_t)tot * 6));                  // (host memory: the caller's, as flow and valid)
+    HIPCHK(c, op.launch(k_flow_decode, dim3((unsigned)((tot + NT - 1) / NT)), dim3(NT), 0, tot, d_in, d_flow, d_valid, d_cnt));
+    HIPCHK(c, op.down(bad, d_cnt, sizeof *bad));
+    HIPCHK(c, op.down(flow, d_flow, (size_t)tot * 16));
+    HIPCHK(c, op.down(valid, d_valid, (size_t)tot));
+    HIPCHK(c, op.sync());
+    *n_bad = (int64_t)*bad;
+    if (*bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a third channel that is neither 0 nor 1", *bad);
     return EINCM_OK;
 }
 
 // The tap tables of a (h, w) -> (H, W) resampling as k_flow_encode and k_flow_error read them, packed for one upload:
 // row weights | column weights | rlo | rcnt | clo | ccnt
 struct TapTables {
-    std::vector<char> tab;
+    Packer tab;
     size_t o_cw = 0, o_rlo = 0, o_rcnt = 0, o_clo = 0, o_ccnt = 0;
     int rstride = 1, cstride = 1;
-    static const int32_t* i32(const char* base, size_t off) { return reinterpret_cast<const int32_t*>(base + off); }
-    static const double* f64(const char* base, size_t off) { return reinterpret_cast<const double*>(base + off); }
 };
 
 static void build_taps(int h, int w, int H, int W, int method, TapTables& t) {
@@ -3069,15 +3059,10 @@ static void build_taps(int h, int w, int H, int W, int method, TapTables& t) {
     resample_matrix(w, W, method, AW);
     t.rstride = resample_runs(AH, h, H, rlo, rcnt, rwt);
     t.cstride = resample_runs(AW, w, W, clo, ccnt, cwt);
-    t.o_cw = rwt.size() * 8; t.o_rlo = t.o_cw + cwt.size() * 8; t.o_rcnt = t.o_rlo + (size_t)H * 4; t.o_clo = t.o_rcnt + (size_t)H * 4;
-    t.o_ccnt = t.o_clo + (size_t)W * 4;
-    t.tab.resize(t.o_ccnt + (size_t)W * 4);
-    std::memcpy(t.tab.data(), rwt.data(), rwt.size() * 8);
-    std::memcpy(t.tab.data() + t.o_cw, cwt.data(), cwt.size() * 8);
-    std::memcpy(t.tab.data() + t.o_rlo, rlo.data(), (size_t)H * 4);
-    std::memcpy(t.tab.data() + t.o_rcnt, rcnt.data(), (size_t)H * 4);
-    std::memcpy(t.tab.data() + t.o_clo, clo.data(), (size_t)W * 4);
-    std::memcpy(t.tab.data() + t.o_ccnt, ccnt.data(), (size_t)W * 4);
+    t.tab.add(rwt.data(), rwt.size() * 8);
+    t.o_cw = t.tab.add(cwt.data(), cwt.size() * 8);
+    t.o_rlo = t.tab.add(rlo.data(), (size_t)H * 4); t.o_rcnt = t.tab.add(rcnt.data(), (size_t)H * 4);
+    t.o_clo = t.tab.add(clo.data(), (size_t)W * 4); t.o_ccnt = t.tab.add(ccnt.data(), (size_t)W * 4);
 }
 
 // dsec_npz_to_png.py:84-96 for a batch of theta: bilinear scale_and_translate to the sensor and the 16-bit code, in one kernel.
@@ -3085,37 +3070,33 @@ int eincm_flow_encode(eincm_ctx* c, const double* theta, int n, int h, int w, co
     if (!c) return EINCM_ERR_ARG;
     if (!theta || !out || !n_bad) return fail(c, EINCM_ERR_ARG, "null pointer argument");
     if (n < 1 || n > 65535 || h < 1 || w < 1 || h > 32767 || w > 32767) return fail(c, EINCM_ERR_ARG, "n = %d theta of %dx%d (1 <= n <= 65535)", n, h, w);
-    HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W;
     const int64_t npix = (int64_t)H * W;
     TapTables T;
     build_taps(h, w, H, W, EINCM_METHOD_BILINEAR, T);
-    const size_t tbytes = T.tab.size();
+    const Packer& tab = T.tab;
     const size_t thbytes = (size_t)n * h * w * 16, vbytes = valid ? (size_t)n * npix : 0, vofs = (thbytes + 15) & ~(size_t)15;
-    Carve cv;
-    const size_t o_in = cv.add(vofs + vbytes), o_out = cv.add((size_t)n * npix * 6), o_tab = cv.add(tbytes), o_cnt = cv.add(sizeof(unsigned long long));
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    char* d_in = carved<char>(c, o_in);
-    uint16_t* d_out = carved<uint16_t>(c, o_out);
-    char* d_tab = carved<char>(c, o_tab);
-    auto* d_cnt = carved<unsigned long long>(c, o_cnt);
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_in, theta, thbytes, hipMemcpyHostToDevice, c->stream));
-    if (valid) HIPCHK(c, hipMemcpyAsync(d_in + vofs, valid, vbytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_tab, T.tab.data(), tbytes, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_flow_encode, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, H, W, h, w,
-                       reinterpret_cast<const double*>(d_in), T.i32(d_tab, T.o_rlo), T.i32(d_tab, T.o_rcnt),
-                       T.f64(d_tab, 0), T.rstride, T.i32(d_tab, T.o_clo), T.i32(d_tab, T.o_ccnt),
-                       T.f64(d_tab, T.o_cw), T.cstride,
-                       valid ? reinterpret_cast<const uint8_t*>(d_in + vofs) : (const uint8_t*)nullptr,
-                       d_out, d_cnt);
-    HIPCHK(c, hipGetLastError());
-    unsigned long long bad = 0;
-    HIPCHK(c, hipMemcpyAsync(&bad, d_cnt, sizeof bad, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, d_out, (size_t)n * npix * 6, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));          // T (host vector) stays alive until here
-    *n_bad = (int64_t)bad;
-    if (bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a flow that is not finite or encodes outside [0, 65536)", bad);
+    OneShot op(c);
+    const auto d_in = op.piece<char>(vofs + vbytes);                  // theta | (16-byte aligned) valid
+    const auto d_out = op.piece<uint16_t>((size_t)n * npix * 3);
+    const auto d_tab = op.piece<char>(tab.buf.size());
+    const auto d_cnt = op.piece<unsigned long long>(1);
+    unsigned long long* bad = op.host_buf<unsigned long long>(1);     // d_cnt comes down here
+    HIPCHK(c, op.begin());
+    const void* const d_theta = d_in;                                 // (launch casts them to the kernel's types)
+    const void* const d_valid = valid ? d_in + vofs : nullptr;
+    HIPCHK(c, op.zero(d_cnt, sizeof(unsigned long long)));
+    HIPCHK(c, op.up(d_in, theta, thbytes));                           // (host memory: the caller's, as valid and out)
+    if (valid) HIPCHK(c, op.up(d_in + vofs, valid, vbytes));
+    HIPCHK(c, op.up(d_tab, tab.buf.data(), tab.buf.size()));          // (T, a local older than the frame)
+    HIPCHK(c, op.launch(k_flow_encode, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, H, W, h, w, d_theta,
+                        tab.i32(d_tab, T.o_rlo), tab.i32(d_tab, T.o_rcnt), tab.f64(d_tab, 0), T.rstride, tab.i32(d_tab, T.o_clo),
+                        tab.i32(d_tab, T.o_ccnt), tab.f64(d_tab, T.o_cw), T.cstride, d_valid, d_out, d_cnt));
+    HIPCHK(c, op.down(bad, d_cnt, sizeof *bad));
+    HIPCHK(c, op.down(out, d_out, (size_t)n * npix * 6));
+    HIPCHK(c, op.sync());
+    *n_bad = (int64_t)*bad;
+    if (*bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a flow that is not finite or encodes outside [0, 65536)", *bad);
     return EINCM_OK;
 }
 
@@ -3135,44 +3116,38 @@ int eincm_flow_eval_stage(eincm_ctx* c, int n_windows, const double* gt_flow, co
         most = std::max(most, n_events[b]);
     }
     if (const int rc = not_in_flight(c, "eincm_flow_eval_stage")) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     const int H = c->H, W = c->W, n = n_windows;
     const size_t npix = (size_t)H * W, plane = (size_t)n * npix;
-    c->fe_n = 0;                                          // whatever was staged is gone from here on
+    c->fe.fe_n = 0;                                       // whatever was staged is gone from here on
     std::vector<int64_t> off((size_t)n + 1, 0);
     for (int b = 0; b < n; ++b) off[b + 1] = off[b] + n_events[b];
-    Carve cv;
-    const size_t o_off = cv.add(off.size() * 8), o_x = cv.add((size_t)tot * 2), o_y = cv.add((size_t)tot * 2);
-    const size_t o_mask = eval_mask ? cv.add(plane) : 0, o_cnt = cv.add(((size_t)n + 1) * 8);
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    HIPCHK(c, ensure(c, c->f_eval, plane * 17));
-    double2* d_gt = reinterpret_cast<double2*>(c->f_eval.p);
-    uint8_t* d_flags = reinterpret_cast<uint8_t*>(c->f_eval.p + plane * 16);
-    int64_t* d_off = carved<int64_t>(c, o_off);
-    int16_t* d_x = carved<int16_t>(c, o_x);
-    int16_t* d_y = carved<int16_t>(c, o_y);
-    const uint8_t* d_mask = eval_mask ? carved<uint8_t>(c, o_mask) : nullptr;
-    auto* d_cnt = carved<unsigned long long>(c, o_cnt);   // [n] GT-valid pixels per window | [1] events outside the sensor
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, ((size_t)n + 1) * 8, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_flags, 0, plane, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_gt, gt_flow, plane * 16, hipMemcpyHostToDevice, c->stream));
-    if (eval_mask) HIPCHK(c, hipMemcpyAsync(carved<uint8_t>(c, o_mask), eval_mask, plane, hipMemcpyHostToDevice, c->stream));
+    OneShot op(c);
+    const auto d_off = op.piece<int64_t>(off.size());
+    const auto d_x = op.piece<int16_t>((size_t)tot), d_y = op.piece<int16_t>((size_t)tot);
+    const auto d_mask = op.piece<uint8_t>(plane, eval_mask != nullptr);
+    const auto d_cnt = op.piece<unsigned long long>((size_t)n + 1);   // [n] GT-valid pixels per window | [1] events outside the sensor
+    unsigned long long* cnt = op.host_buf<unsigned long long>((size_t)n + 1);   // d_cnt comes down here
+    HIPCHK(c, op.begin());
+    HIPCHK(c, ensure(c, c->fe.f_eval, plane * 17));
+    double2* d_gt = reinterpret_cast<double2*>(c->fe.f_eval.p);
+    uint8_t* d_flags = reinterpret_cast<uint8_t*>(c->fe.f_eval.p + plane * 16);
+    HIPCHK(c, op.zero(d_cnt, ((size_t)n + 1) * 8));
+    HIPCHK(c, op.zero(d_flags, plane));
+    HIPCHK(c, op.up(d_gt, gt_flow, plane * 16));          // (host memory: the caller's, as eval_mask, xs and ys)
+    if (eval_mask) HIPCHK(c, op.up(d_mask, eval_mask, plane));
     if (tot > 0) {
-        HIPCHK(c, hipMemcpyAsync(d_off, off.data(), off.size() * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_x, xs, (size_t)tot * 2, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(d_y, ys, (size_t)tot * 2, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_fe_events, dim3((unsigned)((most + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, H, W,
-                           (const int64_t*)d_off, (const int16_t*)d_x, (const int16_t*)d_y, d_flags, d_cnt + n);
+        HIPCHK(c, op.up(d_off, off.data(), off.size() * 8));          // (off, a local older than the frame)
+        HIPCHK(c, op.up(d_x, xs, (size_t)tot * 2));
+        HIPCHK(c, op.up(d_y, ys, (size_t)tot * 2));
+        HIPCHK(c, op.launch(k_fe_events, dim3((unsigned)((most + NT - 1) / NT), (unsigned)n), dim3(NT), 0, H, W, d_off, d_x, d_y, d_flags,
+                            d_cnt + n));
     }
-    hipLaunchKernelGGL(k_fe_flags, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, c->stream, (int)npix,
-                       (const double2*)d_gt, d_mask, d_flags, d_cnt);
-    HIPCHK(c, hipGetLastError());
-    std::vector<unsigned long long> cnt((size_t)n + 1, 0);
-    HIPCHK(c, hipMemcpyAsync(cnt.data(), d_cnt, cnt.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));           // off (host vector) stays alive until here
+    HIPCHK(c, op.launch(k_fe_flags, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)n), dim3(NT), 0, npix, d_gt, d_mask, d_flags, d_cnt));
+    HIPCHK(c, op.down(cnt, d_cnt, ((size_t)n + 1) * 8));
+    HIPCHK(c, op.sync());
     if (cnt[n]) return fail(c, EINCM_ERR_ARG, "%llu of %lld evaluation events have a coordinate outside the %dx%d sensor", cnt[n], (long long)tot, H, W);
-    c->fe_ngt.assign(cnt.begin(), cnt.begin() + n);
-    c->fe_n = n;
+    c->fe.fe_ngt.assign(cnt, cnt + n);
+    c->fe.fe_n = n;
     return EINCM_OK;
 }
 
@@ -3184,32 +3159,31 @@ int eincm_flow_errors(eincm_ctx* c, const double* theta, int h, int w, int metho
     if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
     if (h > c->H || w > c->W) return fail(c, EINCM_ERR_ARG, "theta (%d,%d,2) is finer than the %dx%d sensor", h, w, c->H, c->W);
     if (const int rc = not_in_flight(c, "eincm_flow_errors")) return rc;
-    if (c->fe_n < 1) return fail(c, EINCM_ERR_STATE, "eincm_flow_errors called before a successful eincm_flow_eval_stage");
-    HIPCHK(c, hipSetDevice(c->device));
-    const int H = c->H, W = c->W, n = c->fe_n;
+    if (c->fe.fe_n < 1) return fail(c, EINCM_ERR_STATE, "eincm_flow_errors called before a successful eincm_flow_eval_stage");
+    const int H = c->H, W = c->W, n = c->fe.fe_n;
     const size_t npix = (size_t)H * W, plane = (size_t)n * npix;
     const bool full = h == H && w == W;
     TapTables T;
     if (!full) build_taps(h, w, H, W, method, T);
+    const Packer& tab = T.tab;
     const size_t thbytes = (size_t)n * h * w * 16, pbytes = (size_t)n * FE_PARTS * sizeof(FlowErrPart);
-    Carve cv;
-    const size_t o_th = cv.add(thbytes), o_tab = cv.add(T.tab.size()), o_parts = cv.add(pbytes), o_map = ee_map ? cv.add(plane * 8) : 0;
-    HIPCHK(c, ensure(c, c->scratch, cv.total));
-    double2* d_th = carved<double2>(c, o_th);
-    char* d_tab = carved<char>(c, o_tab);
-    FlowErrPart* d_parts = carved<FlowErrPart>(c, o_parts);
-    double* d_map = ee_map ? carved<double>(c, o_map) : nullptr;
-    HIPCHK(c, hipMemcpyAsync(d_th, theta, thbytes, hipMemcpyHostToDevice, c->stream));
-    if (!full) HIPCHK(c, hipMemcpyAsync(d_tab, T.tab.data(), T.tab.size(), hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_flow_error, dim3(FE_PARTS, (unsigned)n), dim3(NT), 0, c->stream, H, W, h, w, full ? 1 : 0,
-                       reinterpret_cast<const double2*>(c->f_eval.p), reinterpret_cast<const uint8_t*>(c->f_eval.p + plane * 16),
-                       (const double2*)d_th, T.i32(d_tab, T.o_rlo), T.i32(d_tab, T.o_rcnt), T.f64(d_tab, 0), T.rstride,
-                       T.i32(d_tab, T.o_clo), T.i32(d_tab, T.o_ccnt), T.f64(d_tab, T.o_cw), T.cstride, d_parts, d_map);
-    HIPCHK(c, hipGetLastError());
-    std::vector<FlowErrPart> parts((size_t)n * FE_PARTS);
-    HIPCHK(c, hipMemcpyAsync(parts.data(), d_parts, pbytes, hipMemcpyDeviceToHost, c->stream));
-    if (ee_map) HIPCHK(c, hipMemcpyAsync(ee_map, d_map, plane * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));           // T (host vector) stays alive until here
+    OneShot op(c);
+    const auto d_th = op.piece<double2>((size_t)n * h * w);
+    const auto d_tab = op.piece<char>(tab.buf.size());
+    const auto d_parts = op.piece<FlowErrPart>((size_t)n * FE_PARTS);
+    const auto d_map = op.piece<double>(plane, ee_map != nullptr);
+    FlowErrPart* parts = op.host_buf<FlowErrPart>((size_t)n * FE_PARTS);   // d_parts comes down here
+    HIPCHK(c, op.begin());
+    const void* const d_gt = c->fe.f_eval.p;              // (launch casts them to the kernel's types)
+    const void* const d_flags = c->fe.f_eval.p + plane * 16;
+    HIPCHK(c, op.up(d_th, theta, thbytes));               // (host memory: the caller's, as ee_map)
+    if (!full) HIPCHK(c, op.up(d_tab, tab.buf.data(), tab.buf.size()));           // (T, a local older than the frame)
+    HIPCHK(c, op.launch(k_flow_error, dim3(FE_PARTS, (unsigned)n), dim3(NT), 0, H, W, h, w, full ? 1 : 0, d_gt, d_flags, d_th,
+                        tab.i32(d_tab, T.o_rlo), tab.i32(d_tab, T.o_rcnt), tab.f64(d_tab, 0), T.rstride, tab.i32(d_tab, T.o_clo),
+                        tab.i32(d_tab, T.o_ccnt), tab.f64(d_tab, T.o_cw), T.cstride, d_parts, d_map));
+    HIPCHK(c, op.down(parts, d_parts, pbytes));
+    if (ee_map) HIPCHK(c, op.down(ee_map, d_map, plane * 8));
+    HIPCHK(c, op.sync());
     for (int b = 0; b < n; ++b) {
         eincm_flow_error_out o{};
         for (int g = 0; g < FE_PARTS; ++g) {              // the partials of a window in index order
@@ -3218,7 +3192,7 @@ int eincm_flow_errors(eincm_ctx* c, const double* theta, int h, int w, int metho
             o.n_ee += q.n_ee; o.n_pred += q.n_pred;
             for (int k = 0; k < FE_NOVER; ++k) o.n_over[k] += q.n_over[k];
         }
-        o.n_gt = c->fe_ngt[b];
+        o.n_gt = c->fe.fe_ngt[b];
         // flow_eval.py:60-76: means over the intersection (NaN where it is empty), percentages over n_ee + eps
         o.aee = o.n_ee ? o.sum_ee / (double)o.n_ee : std::nan("");
         o.aree = o.n_ee ? o.sum_ree / (double)o.n_ee : std::nan("");
@@ -3265,27 +3239,25 @@ int eincm_tiled_objectives(eincm_ctx* c, int tile_h, int tile_w, eincm_tiled_out
     g.nparts = c->last_nparts;
     if (tile_h < 1 || tile_w < 1 || tile_h > g.H || tile_w > g.W)
         return fail(c, EINCM_ERR_ARG, "tile %d x %d does not fit the %d x %d sensor", tile_h, tile_w, g.H, g.W);
-    HIPCHK(c, hipSetDevice(c->device));
     const int ntx = g.W / tile_w, nty = g.H / tile_h, ntl = ntx * nty;
     const int nb = std::min((g.H * g.W + NT - 1) / NT, 256);
     const size_t n_t = (size_t)g.B * g.R * ntl * 3, n_p = (size_t)g.B * g.R * nb * 3;
-    HIPCHK(c, ensure(c, c->scratch, (n_t + n_p) * 8));
-    double* d_t = carved<double>(c, 0);
-    double* d_p = d_t + n_t;
+    OneShot op(c);
+    const auto d_v = op.piece<double>(n_t + n_p);         // the tiles' values | the workgroups' partials: one piece, one download
+    double* hv = op.host_buf<double>(n_t + n_p);          // ... which lands here
+    HIPCHK(c, op.begin());
     g.wmask = ~0ull;
-    hipLaunchKernelGGL(k_tiled, dim3(ntl, g.R, g.B), dim3(NT), 0, c->stream, g, tile_h, tile_w, ntx, c->d_iwe, c->d_edges, c->d_parts, d_t);
-    hipLaunchKernelGGL(k_pair_objectives, dim3(nb, g.R, g.B), dim3(NT), 0, c->stream, g, c->d_iwe, c->d_edges, c->d_parts, d_p);
-    HIPCHK(c, hipGetLastError());
-    std::vector<double> hv(n_t + n_p);
-    HIPCHK(c, hipMemcpyAsync(hv.data(), d_t, hv.size() * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, op.launch(k_tiled, dim3(ntl, g.R, g.B), dim3(NT), 0, g, tile_h, tile_w, ntx, c->d_iwe, c->d_edges, c->d_parts, d_v));
+    HIPCHK(c, op.launch(k_pair_objectives, dim3(nb, g.R, g.B), dim3(NT), 0, g, c->d_iwe, c->d_edges, c->d_parts, d_v + n_t));
+    HIPCHK(c, op.down(hv, d_v, (n_t + n_p) * 8));
+    HIPCHK(c, op.sync());
     const double HW = (double)g.H * g.W;
     for (int b = 0; b < g.B; ++b) {
         eincm_tiled_out& o = out[b];
         memset(&o, 0, sizeof o);
         o.n_refs = g.R; o.n_tiles = ntl;
         for (int r = 0; r < g.R; ++r) {
-            const double* t = hv.data() + ((size_t)b * g.R + r) * ntl * 3;
+            const double* t = hv + ((size_t)b * g.R + r) * ntl * 3;
             for (int k = 0; k < ntl; ++k) {
                 o.adaptive_mean_gradient_magnitude[r] += t[k * 3];
                 o.adaptive_variance[r] += t[k * 3 + 1];
@@ -3293,7 +3265,7 @@ int eincm_tiled_objectives(eincm_ctx* c, int tile_h, int tile_w, eincm_tiled_out
             }
             double q[3] = {0.0, 0.0, 0.0};                       // the workgroups' partials, added in index order
             for (int k = 0; k < nb; ++k) {
-                const double* pk = hv.data() + n_t + (((size_t)b * g.R + r) * nb + k) * 3;
+                const double* pk = hv + n_t + (((size_t)b * g.R + r) * nb + k) * 3;
                 q[0] += pk[0]; q[1] += pk[1]; q[2] += pk[2];
             }
             o.sum_squared_error[r] = q[0];

@@ -290,3 +290,71 @@ def test_refused_calls_allocate_nothing():
         after = eng.memory()
     assert refused == [L.ERR_ARG, L.ERR_UNSUPPORTED] + [L.ERR_ARG] * 7 + [L.ERR_STATE]
     assert after == before and before.scratch_bytes == 0
+
+
+# -- 6. a call refused after work has run on the GPU leaves the context as an accepted call of the same sizes does ---------------------
+def _changed(a, index, value):
+    a = a.copy()
+    a[index] = value
+    return a
+
+
+def _rectify(e, x, y, m):
+    return e.rectify_events(x, y, m)[:3]
+
+
+def _fe_stage(e, x_outside=None):
+    d = _inputs()
+    x, y = d['xy'] if x_outside is None else (_changed(d['xy'][0], x_outside, W), d['xy'][1])
+    gt = np.random.default_rng(33).normal(0.0, 2.0, (N_MAX, H, W, 2))
+    e.flow_eval_stage(gt, [(x[b * 1000:(b + 1) * 1000], y[b * 1000:(b + 1) * 1000]) for b in range(N_MAX)], d['valid'])
+
+
+def _fe_read(e):
+    res, emap = e.flow_errors(_inputs()['theta'], ee_map=True)
+    return tuple(np.array(list(r['errors'].values()) + list(r['counts'].values())) for r in res) + (emap,)
+
+
+# name: (the refused call, a piece of its message, the accepted call of the same sizes, how that one's results are read if it returns none)
+LATE_REFUSALS = {
+    'inv_dist_transform_empty_image': (lambda e: e.inv_dist_transform(_changed(_inputs()['edge'][:2], 1, 0)), 'has no edge pixel',
+                                       lambda e: e.inv_dist_transform(_inputs()['edge'][:2]), None),
+    'rectify_events_nan_in_map': (lambda e: _rectify(e, *_inputs()['xy'], _changed(_inputs()['map'], (7, 9, 1), np.nan)), 'rectify map',
+                                  lambda e: _rectify(e, *_inputs()['xy'], _inputs()['map']), None),
+    'rectify_events_x_equals_W': (lambda e: _rectify(e, _changed(_inputs()['xy'][0], 1234, W), _inputs()['xy'][1], _inputs()['map']),
+                                  'events have a coordinate outside', lambda e: _rectify(e, *_inputs()['xy'], _inputs()['map']), None),
+    'flow_decode_third_channel_2': (lambda e: e.flow_decode(_changed(_inputs()['f16'], (1, 5, 6, 2), 2)), 'third channel',
+                                    lambda e: e.flow_decode(_inputs()['f16']), None),
+    'flow_encode_nonfinite_theta': (lambda e: e.flow_encode(_changed(_inputs()['theta'], (1, 2, 3, 0), np.inf), _inputs()['valid']),
+                                    'not finite', lambda e: e.flow_encode(_inputs()['theta'], _inputs()['valid']), None),
+    'flow_eval_stage_event_outside': (lambda e: _fe_stage(e, x_outside=1017), 'evaluation events have a coordinate outside',
+                                      _fe_stage, _fe_read),
+}
+
+
+@pytest.mark.parametrize('name', list(LATE_REFUSALS))
+def test_a_late_refusal_leaves_the_context_as_an_accepted_call_does(name):
+    refuse, message, accept, read = LATE_REFUSALS[name]
+    with E.Engine(SENSOR, 1, max_refs=1) as twin:              # never sees the refusal
+        want = accept(twin)
+        m_want = twin.memory()
+        want = read(twin) if read else want
+    with E.Engine(SENSOR, 1, max_refs=1) as eng:
+        with pytest.raises((ValueError, E.EincmError), match=message):
+            refuse(eng)
+        m_got = eng.memory()
+        if read is _fe_read:                                   # nothing is staged now: the library says so, and so does the wrapper
+            th = _inputs()['theta']
+            out = (L.FlowErrorOut * N_MAX)()
+            assert L.load().eincm_flow_errors(eng._ctx, th.ctypes.data, th.shape[1], th.shape[2], L.METHODS['bilinear'], out,
+                                              None) == L.ERR_STATE
+            with pytest.raises(E.EincmError):
+                eng.flow_errors(th)
+            assert eng.memory() == m_got
+        got = accept(eng)
+        m_after = eng.memory()
+        got = read(eng) if read else got
+    print(name, m_want, m_got, m_after)
+    assert m_got._asdict() == m_want._asdict()                 # field by field
+    assert m_after == m_want
+    assert _same(got, want)
