@@ -648,6 +648,57 @@ template <int NTH> struct SegWalk {
     }
 };
 
+// The event loop of both event kernels.  A thread walks the events trip * STRIDE + off of its segment, trip = 0 .. nfull - 1 (every
+// thread of the workgroup has an event in those) and, where `tail`, one event of the partial trip nfull - in that order, which
+// the 2-DoF gradient's per-thread fp32 sums depend on.  load(ev, trip) reads the thread's event of a trip and is called with a
+// UNIFORM trip, so the addresses are a scalar base advanced per trip plus the thread's fixed 32-bit offset (ev_load): a full trip
+// costs no VALU for addressing, no bound test and no zero fill.  Only the partial trip is predicated; its load is issued first.
+// PIPE: the loads of trip j + 2 are in flight while trip j is worked on - three register sets renamed by a x3 unroll, no
+// rotation moves.  Every load of the pipeline is unconditional (past the last full trip the scalar index is clamped: the last
+// trip is read again and dropped), so the compiler can count them and waits with vmcnt(n), the later trips' loads outstanding;
+// loads behind a test it cannot count, and it waited for all of them.  Without PIPE (k_gather, which needs its registers for
+// occupancy): load, then use, two trips per turn of the loop.
+template <bool PIPE, typename Load, typename Body>
+__device__ __forceinline__ void event_trips(int nfull, bool tail, const Load& load, const Body& body) {
+    EvReg T; T.xy = 0u; T.t = 0.0;
+    if (tail) load(T, nfull);
+    if (PIPE) {
+        if (nfull > 0) {
+            const int last = nfull - 1;
+            EvReg A, B, C;
+            load(A, 0); load(B, min(1, last));
+            int j = 0;
+            for (; j + 3 <= nfull; j += 3) {
+                load(C, min(j + 2, last)); body(A);
+                load(A, min(j + 3, last)); body(B);
+                load(B, min(j + 4, last)); body(C);
+            }
+            if (j < nfull) body(A);
+            if (j + 1 < nfull) body(B);
+        }
+    } else {
+#pragma unroll 2
+        for (int j = 0; j < nfull; ++j) { EvReg ev; load(ev, j); body(ev); }
+    }
+    if (tail) body(T);
+}
+// A segment's events as two buffer resources, and one event of them at a uniform element index `base` plus the thread's byte offsets
+// off4 = 4 * off, off8 = 8 * off: buffer loads take the trip as their scalar offset and the thread's share as their vector offset.
+// (With plain pointers the compiler folds the thread's offset into a 64-bit vector base outside the loop and adds the trip to it with
+// two v_lshl_add_u64 per event.)  The resources span exactly the segment's n events; a load past them would return zero.
+struct EvBuf { __amdgpu_buffer_rsrc_t xy, t; };
+__device__ __forceinline__ EvBuf ev_buf(const uint32_t* __restrict__ xy, const double* __restrict__ t, int n) {
+    constexpr int RSRC_WORD3 = 0x00020000;          // raw buffer of dwords on gfx90a / gfx94x / gfx950
+    EvBuf b;
+    b.xy = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(xy), 0, n * 4, RSRC_WORD3);
+    b.t = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(t), 0, n * 8, RSRC_WORD3);
+    return b;
+}
+__device__ __forceinline__ void ev_load(EvReg& r, const EvBuf& b, int base, uint32_t off4, uint32_t off8) {
+    r.xy = __builtin_amdgcn_raw_buffer_load_b32(b.xy, off4, base * 4, 0);
+    r.t = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(b.t, off8, base * 8, 0));
+}
+
 // ------------------------------------------------------------------------------------------------
 // k_splat: the dominant kernel.  grid ceil(n_items/8)*8*R blocks (block_to_work), LDS wincap*4 bytes (+ the Theta tile).
 // A segment (<= MAX_CHUNK events) is accumulated in its u32 fixed-point window in LDS (exact integer ds_add_u32, scale
@@ -703,20 +754,21 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
     const uint32_t* __restrict__ exy = ev_xy + it.begin;
     const double* __restrict__ et = ev_t + it.begin;
     const int n = it.count;
-    const int iters = (n + NTH - 1) / NTH;            // uniform over the workgroup
     const int fshift = fix_shift(n);
     const float FIX_SCALE = ldexpf(1.0f, fshift);
     const int up = ACC_SHIFT - fshift;               // >= 0 (fix_shift caps at 30): a segment's integers at the accumulator's scale
 
-    // Software pipeline over the segment's events, unrolled x3 with renamed register sets (no rotation moves, so no forced
-    // vmcnt(0)): the (xy, t) loads of event j+2 are in flight while event j is splatted.
+    // The segment's events by the event loop of both kernels (event_trips): trip j holds the events j * NTH + tid.
     const int tid = threadIdx.x;
+    const int nfull = n / NTH;                        // uniform over the workgroup: only trip nfull can be partial
+    const uint32_t off4 = (uint32_t)tid * 4u, off8 = (uint32_t)tid * 8u;
 #if defined(EINCM_ABL_S_NOLOADT)                  // timing-only: no 8-byte timestamp load (what the event traffic from L2 costs)
-    auto load_ev = [&](EvReg& r, int e) { if (e < n) { r.xy = exy[e]; r.t = it.t_lo + 1e-9 * (double)e; } else { r.xy = 0u; r.t = 0.0; } };
+    auto load_ev = [&](EvReg& r, int j) { const int e = j * NTH + tid; r.xy = exy[e]; r.t = it.t_lo + 1e-9 * (double)e; };
 #elif defined(EINCM_ABL_S_NOLOAD)                 // timing-only: no event loads at all
-    auto load_ev = [&](EvReg& r, int e) { r.xy = ((uint32_t)(ty0 + ((e * 7) & 31)) << 16) | (uint32_t)(tx0 + (e & 31)); r.t = it.t_lo + 1e-9 * (double)e; };
+    auto load_ev = [&](EvReg& r, int j) { const int e = j * NTH + tid; r.xy = ((uint32_t)(ty0 + ((e * 7) & 31)) << 16) | (uint32_t)(tx0 + (e & 31)); r.t = it.t_lo + 1e-9 * (double)e; };
 #else
-    auto load_ev = [&](EvReg& r, int e) { if (e < n) { r.xy = exy[e]; r.t = et[e]; } else { r.xy = 0u; r.t = 0.0; } };
+    const EvBuf evb = ev_buf(exy, et, n);
+    auto load_ev = [&](EvReg& r, int j) { ev_load(r, evb, j * NTH, off4, off8); };
 #endif
     const float scy = INV_2PI * FIX_SCALE;          // one fixed-point scale per segment
     auto splat_ev = [&](const EvReg& ev) {
@@ -768,22 +820,8 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
             }
         }
     };
-    // one pipeline step: cur is splatted, nxt gets its (xy, t); j = iteration index of cur
-    auto step = [&](EvReg& cur, EvReg& mid, EvReg& nxt, int j) {
-        const int e = j * NTH + tid;
-        load_ev(nxt, e + 2 * NTH);
-        if (e < n) splat_ev(cur);
-    };
-    EvReg A, B, C;
-    load_ev(A, tid);
-    load_ev(B, tid + NTH);
-    C.xy = 0u; C.t = 0.0;
 #ifndef EINCM_ABL_S_NOEVENTS           // EINCM_ABL_*: timing-only ablation builds (tools/build_variant.sh); results are wrong by design
-    for (int j = 0; j < iters; j += 3) {
-        step(A, B, C, j);
-        if (j + 1 < iters) step(B, C, A, j + 1);
-        if (j + 2 < iters) step(C, A, B, j + 2);
-    }
+    event_trips<true>(nfull, nfull * NTH + tid < n, load_ev, splat_ev);
 #endif
     __syncthreads();
 #ifdef EINCM_ABL_S_NOFLUSH
@@ -1569,24 +1607,24 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     };
     // the staged layout (SegWalk): a half of the segment is K coalesced steps of 256 threads, the last one a prefix
     const SegWalk<NTH> walk(n, tid);
-    auto walk_half = [&](int c) {                 // steps [0, K) of half c
+    const EvBuf evb = ev_buf(exy, et, n);
+    // Steps [0, K) of half c by the event loop of both kernels (event_trips): the K - 1 full steps, then the prefix.  The half's
+    // start rides in the thread's fixed offset (a 512-thread workgroup walks both halves at once), the step in the scalar base.
+    auto walk_half = [&](int c) {
         const int K = c ? walk.K1 : walk.K0, rem = c ? walk.rem1 : walk.rem0;
-        const uint32_t* __restrict__ px = exy + (c ? walk.n0 : 0) + walk.tt;
-        const double* __restrict__ pt = et + (c ? walk.n0 : 0) + walk.tt;
-#pragma unroll 2
-        for (int j = 0; j < K - 1; ++j) {
-            EvReg ev; ev.xy = px[j * 256]; ev.t = pt[j * 256];
-            gather_ev(ev);
-        }
-        if (K > 0 && walk.tt < rem) {
-            EvReg ev; ev.xy = px[(K - 1) * 256]; ev.t = pt[(K - 1) * 256];
-            gather_ev(ev);
-        }
+        const uint32_t off = (uint32_t)((c ? walk.n0 : 0) + walk.tt), off4 = off * 4u, off8 = off * 8u;
+        // no pipeline here, 2-DoF theta included: three events in flight take the 2-DoF gather from 68 to 92 VGPRs, 7 to 5 waves per
+        // SIMD, and the kernel from 82 to 88 us (profiles/event_loop_trim.md) - its latency is covered by occupancy
+        event_trips<false>(max(K - 1, 0), K > 0 && walk.tt < rem,
+                              [&](EvReg& ev, int j) { ev_load(ev, evb, j * 256, off4, off8); }, gather_ev);
     };
     for (int rr = r; ; ) {                        // one reference time, or all of them (all_r)
 #ifndef EINCM_ABL_G_NOEVENTS
     if (NTH == 512) walk_half(walk.half);
-    else { walk_half(0); walk_half(1); }
+    else {
+#pragma unroll 1                                  // (one copy of the loop's code for both halves)
+        for (int c = 0; c < 2; ++c) walk_half(c);
+    }
     if (!direct11) { flush_run(); cur_key = 0xffffffffu; run_x = 0.0; run_y = 0.0; }
 #endif
     if (!all_r || ++rr >= g.R) break;

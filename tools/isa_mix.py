@@ -3,8 +3,9 @@
 usage: python tools/isa_mix.py <file.s> > profiles/rNN/isa_instruction_mix.md
 
 For each kernel the event loop is located (the innermost loop that contains v_exp_f32), its basic blocks are listed, and the
-blocks of the common case - every tap inside the LDS window - are summed per instruction class.  One trip of the loop handles
-one event per lane (k_splat's loop is unrolled x3 by the source; the per-event figure divides by the events per trip)."""
+blocks of the common case - every tap inside the LDS window - are summed per instruction class.  The loops are unrolled by the
+source (x3, or x2), and the compiler may gather the tap arithmetic of all events of a trip in one block: the per-event figure is
+the trip's sum divided by the events per trip."""
 import re
 import sys
 from collections import Counter, OrderedDict
@@ -38,9 +39,17 @@ def blocks(body):
     cur, name, out = [], 'entry', []
     for line in body.splitlines():
         line = line.strip()
-        m = re.match(r'^(\.LBB\d+_\d+):', line)
+        m = re.match(r'^(\.LBB\d+_\d+):(.*)', line)
         if m:
             out.append((name, cur)); name, cur = m.group(1), []
+            LOOP[name] = None
+            line = m.group(2).strip()
+        if line.startswith(';') and not cur and not name.endswith('+'):       # the compiler's own loop annotation of the label (one or two lines)
+            h = re.search(r'in Loop: Header=(BB\d+_\d+)', line)
+            if h:
+                LOOP[name] = '.L' + h.group(1)
+            elif 'Inner Loop Header' in line:
+                LOOP[name] = name
             continue
         if not line or line.startswith(';') or line.startswith('.') or line.startswith('//'):
             continue
@@ -52,12 +61,25 @@ def blocks(body):
     return out
 
 
+LOOP = {}           # label -> header label of the innermost loop it belongs to (labels are unique over the file)
+
+
+def event_loop(bl):
+    """The blocks of the first innermost loop that holds the tap arithmetic (>= 3 v_exp_f32), in layout order."""
+    for n, _ in bl:
+        if LOOP.get(n) == n:
+            body = [(m, ops) for m, ops in bl if LOOP.get(m.rstrip('+')) == n]
+            if sum(o == 'v_exp_f32_e32' for _, ops in body for o in ops) >= 3:
+                return body
+    return []
+
+
 def main():
     text = open(sys.argv[1]).read()
     want = [('k_splat<THETA_CONST>  (2-DoF theta, the bench configuration)', 'k_splatILi1E', 'ds_add_u32', 3),
-            ('k_gather<THETA_CONST, 0>  (2-DoF theta)', 'k_gatherILi1ELi0E', 'ds_read_b32', 1),
+            ('k_gather<THETA_CONST, 0>  (2-DoF theta)', 'k_gatherILi1ELi0E', 'ds_read', 1),
             ('k_splat<THETA_TILE>  (pyramid levels >= 1, dense)', 'k_splatILi2E', 'ds_add_u32', 3),
-            ('k_gather<THETA_TILE, 0>', 'k_gatherILi2ELi0E', 'ds_read_b32', 1)]
+            ('k_gather<THETA_TILE, 0>', 'k_gatherILi2ELi0E', 'ds_read', 1)]
     print('# Instruction mix of the event kernels\' inner loops (gfx950 ISA, hipcc -O3, `tools/isa_mix.py`)\n')
     print('Counted from the disassembly: the basic blocks of the event loop that run in the common case (every tap of the event inside the LDS\n'
           'window).  "per event" = per lane-event and reference time, i.e. per warped event.  The out-of-window path (taps sent straight to HBM with\n'
@@ -70,32 +92,20 @@ def main():
 
         def has(ops, prefix, n):
             return sum(o.startswith(prefix) for o in ops) >= n
-        # The source unrolls the event loop x3 (k_splat: renamed-register pipeline; k_gather: #pragma unroll 2 + remainder), so the
-        # common-case blocks come in repeating groups; the MIDDLE group is the steady state.
-        #   k_splat : [loads + fp64 warp + tap math (4 v_exp_f32)] [9 products + 9 ds_add_u32]
-        #   k_gather: [loads + fp64 warp (>= 3 global_load)] [window reads (>= 6 ds_read)] [tap math + combination (3 v_exp_f32 + 2 v_rcp_f32)]
-        if key.startswith('k_splat'):
-            groups, cur = [], []
-            for n, ops in bl:
-                if has(ops, 'v_exp_f32', 4):
-                    cur = [(n, ops)]
-                elif cur and has(ops, 'ds_add_u32', 9):
-                    groups.append(cur + [(n, ops)]); cur = []
-        else:
-            # k_gather's loop is not unrolled: [event loads + fp64 warp + window test] [9 window reads] [tap math + combination]
-            # (+ for 2-DoF theta the fp32 accumulation, for the tile form the two i64 conversions and ds_add_u64)
-            groups, cur, stage = [], [], 0
-            for n, ops in bl:
-                if stage == 0 and has(ops, 'global_load', 2) and sum('_f64' in o for o in ops) >= 8:
-                    cur, stage = [(n, ops)], 1
-                elif stage == 1 and has(ops, 'ds_read', 6):
-                    cur.append((n, ops)); stage = 2
-                elif stage == 2 and has(ops, 'v_exp_f32', 3):
-                    cur.append((n, ops)); stage = 3
-                elif stage == 3:
-                    cur.append((n, ops)); groups.append(cur); cur, stage = [], 0
-        fast = groups[len(groups) // 2] if groups else []
-        events_per_trip = 1
+        # The common case inside the event loop (event_trips: unrolled x3 with renamed registers, or #pragma unroll 2): every block
+        # but the out-of-window path, which runs from the block that warps an event and tests its taps against the window (fp64
+        # arithmetic, closed by s_cbranch_execz) to the block with the nine LDS operations of that event.  One such block = one event.
+        marker_n = 9 if marker == 'ds_add_u32' else 6
+        fast, slow, events_per_trip = [], False, 0
+        for n, ops in event_loop(bl):
+            if slow and not has(ops, marker, marker_n):
+                continue
+            slow = False
+            fast.append((n, ops))
+            events_per_trip += has(ops, marker, marker_n)
+            if ops and ops[-1] == 's_cbranch_execz' and sum('_f64' in o for o in ops) >= 8:
+                slow = True
+        events_per_trip = max(events_per_trip, 1)
         tot = Counter()
         for n, ops in fast:
             for o in ops:
