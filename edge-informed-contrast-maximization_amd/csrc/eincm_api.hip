@@ -184,6 +184,35 @@ struct StageScratch {
     std::vector<int> ishift;                                                                              // float64 mode
 };
 
+// theta and gradient of an evaluation whose caller keeps them in HBM (eincm_loss_grad_device, eincm_bfgs_eval)
+struct DevIo {
+    const double* theta = nullptr;      // (B,h,w,2) in the caller's device buffer; nullptr: theta comes from the host
+    double* grad = nullptr;             // the gradient goes there, device to device (nullptr: it stays in the engine's block)
+    double vmax = -1.0;                 // bounds |theta| for the window-capacity choice (< 0: unknown, largest windows)
+};
+
+// The evaluation in flight: eval_begin enqueues its forward half (FORWARD; the caller may all-reduce the IWE
+// stack; a float64 context goes to LAUNCHED at once), eval_end_launch the rest (LAUNCHED), eval_end_collect waits and hands over (IDLE).
+// All of it belongs to that one evaluation, as does the window mask, which is g.wmask because the kernels take it from the Geom.
+struct Flight {
+    enum State { IDLE, FORWARD, LAUNCHED } state = IDLE;
+    EvalPlan plan{};                    // (outlives the evaluation: eincm_get_launch_policy)
+    DevIo io{};                         // the call's device-resident theta and gradient, if any
+    const double* theta_dev = nullptr; ThetaArg targ{};      // where the event kernels find theta
+    int copy_mode = 0;                  // 1: the D2H copies of the results are still to be enqueued (device_results)
+    int n_pieces = 0;                   // pieces of the gradient download (0: it came with the results / in one copy)
+    size_t piece_len = 0;
+    std::vector<uint8_t> theta_nan;     // (B) a NaN / Inf somewhere in window b's theta (host-assembled and float64 evaluations)
+    bool timed_now = true;              // EINCM_CF_TIMING_DOMINANT: this evaluation carries events (eincm_set_timing_period)
+    int ring_cur = 0;                   // ... in this slot of the ring
+    bool idle() const { return state == IDLE; }
+    bool launched() const { return state == LAUNCHED; }
+    void land() { state = IDLE; io = DevIo{}; }          // (the caller's device pointers end with the evaluation)
+    // Give the evaluation up: what it enqueued reads the pinned theta buffer and writes the pinned result block, so the stream drains
+    // before the context looks idle.  (acc_dirty, set when the forward half starts, already says what the kernels left behind.)
+    void abandon(hipStream_t stream) { (void)hipStreamSynchronize(stream); land(); }
+};
+
 }  // namespace
 
 struct eincm_ctx {
@@ -257,9 +286,6 @@ struct eincm_ctx {
     Grow<double> d_AH, d_AW;       // (H,h) (W,w) for the current theta shape, grown on demand (ensure_resample)
     int2* d_rowtap = nullptr; int2* d_coltap = nullptr;
     TileRange* d_tilerng = nullptr;    // (ntiles) coarse cells under each tile for the current theta shape
-    const double* theta_dev_in = nullptr;   // eincm_loss_grad_device: theta of the evaluation being begun lives in HBM (the caller's buffer)
-    double vmax_hint = -1.0;                // ... and this bounds |theta| for the window-capacity choice (< 0: unknown, largest windows)
-    double* grad_dev_out = nullptr;         // ... and the gradient goes there (device to device)
     bool device_results = false;       // eincm_set_device_results: results stay in HBM until eincm_finish_collect (event-sharded mode over RCCL)
     bool proj_in_gather = false;       // every tile touches <= PG_MAXC x PG_MAXC cells: k_gather projects its tile itself
     int cur_h = -1, cur_w = -1, cur_method = -1;
@@ -316,13 +342,10 @@ struct eincm_ctx {
     bool ev_used[EV_RING][EINCM_N_STAGES + 1] = {};
     int ring_size = 1;             // EV_RING in the dominant mode, 1 otherwise (read out at once)
     int ring_lo = 0, ring_n = 0;   // finished evaluations whose events have not been read yet: slots ring_lo .. ring_lo + ring_n - 1
-    int ring_cur = 0;              // slot of the evaluation in flight
     static constexpr int GRAD_PIECES = 4;
     hipEvent_t ev_piece[GRAD_PIECES] = {};   // dense gradients come back in pieces; the host scans piece k while piece k + 1 crosses PCIe
-    int n_pieces = 0;              // pieces of the evaluation in flight (0: the gradient came with the results / in one copy)
-    size_t piece_len = 0;
     int attach_stage = -1;         // EINCM_CF_TIMING: the single-kernel stage whose launch takes its events along (StageTimer)
-    int time_period = 1; int64_t time_counter = 0; bool timed_now = true;   // EINCM_CF_TIMING_DOMINANT: events on every time_period-th evaluation only (eincm_set_timing_period)
+    int time_period = 1; int64_t time_counter = 0;   // EINCM_CF_TIMING_DOMINANT: events on every time_period-th evaluation only (eincm_set_timing_period)
     bool time_splat = true, time_gather = true;   // EINCM_CF_TIMING_DOMINANT: which event kernels carry start / stop events (eincm_set_timed_kernels)
     bool have_events = false;
     eincm_timings last_t{};
@@ -333,12 +356,7 @@ struct eincm_ctx {
     bool have_eval = false;
     bool G_valid = false;          // d_G holds dL/dIWE of the last evaluation (eincm_get_count_images borrows the buffer)
     int last_nparts = 0;           // how many StatParts per image the last evaluation wrote (k_stats vs k_stats_stream)
-    // an evaluation split in two halves (eval_begin ... [caller may all-reduce the IWE stack] ... eval_end)
-    struct { bool active = false, launched = false; EvalPlan plan{};   // (the plan outlives the evaluation: eincm_get_launch_policy)
-             int copy_mode = 0;                     // 1: the D2H copies of the results are still to be enqueued (device_results)
-             const double* theta_dev = nullptr; ThetaArg targ{};      // where the event kernels find theta
-             } pend;
-    std::vector<uint8_t> theta_nan;    // (B) a NaN / Inf somewhere in window b's theta (host-assembled and float64 evaluations)
+    Flight fl;                     // the evaluation in flight
     // host-side wall time of the phases of an evaluation (eincm_get_host_profile): a few clock reads per evaluation, always on
     double hp_us[EINCM_N_HOST_PHASES] = {};
     int64_t hp_n = 0;
@@ -432,8 +450,31 @@ hipError_t ensure_coarse(eincm_ctx* c, size_t cells) {
 
 // The one-shot operators that must not run beside an evaluation begun and not yet collected (its kernels may be on the stream)
 int not_in_flight(eincm_ctx* c, const char* who) {
-    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
     return EINCM_OK;
+}
+
+// Abandons the evaluation in flight (Flight::abandon: drain, IDLE) on every exit of its scope but the hand-over: keep() says the state
+// the flight is left in is meant - FORWARD or LAUNCHED for the next call, IDLE after a collect (who arms one).
+struct FlightGuard {
+    eincm_ctx* c; bool armed = true;
+    explicit FlightGuard(eincm_ctx* c_) : c(c_) {}
+    FlightGuard(const FlightGuard&) = delete;
+    ~FlightGuard() { if (armed) c->fl.abandon(c->stream); }
+    int keep(int rc = EINCM_OK) { armed = false; return rc; }
+};
+
+// Window b sits the evaluation out (eincm_loss_grad_masked): the host's form of the kernels' !win_active(g, b)
+inline bool window_sat_out(const Geom& g, int b) { return b < 64 && !((g.wmask >> b) & 1ull); }
+
+// Is a NaN / Inf among src[0..n)?  Copies src to dst on the way unless dst is null.  Branch-free, so that it vectorises: an OR over the
+// exponent bits (an early-exit std::isfinite loop does not: 0.6 ms of a 1.8 ms dense-theta evaluation at 480x640).  No __restrict__:
+// with it the compiler splits the copying loop into a memcpy and a second pass over the source (+0.1 ms on that evaluation).
+inline bool copy_scan_finite(double* dst, const double* src, size_t n) {
+    uint64_t bad = 0;
+    if (dst) for (size_t i = 0; i < n; ++i) { uint64_t u; memcpy(&u, src + i, sizeof u); dst[i] = src[i]; bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull); }
+    else     for (size_t i = 0; i < n; ++i) { uint64_t u; memcpy(&u, src + i, sizeof u); bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull); }
+    return bad != 0;
 }
 
 // The call frame of a one-shot operator.  After its argument checks an operator declares the pieces of c->scratch
@@ -551,11 +592,11 @@ struct StageTimer {
     eincm_ctx* c; int stage; bool on, single;
     StageTimer(eincm_ctx* c_, int s, bool single_ = false) : c(c_), stage(s), on((c_->cflags & EINCM_CF_TIMING) != 0), single(single_) {
         if (on && single) c->attach_stage = stage;
-        else if (on) { (void)hipEventRecord(c->ev[c->ring_cur][stage][0], c->stream); }
+        else if (on) { (void)hipEventRecord(c->ev[c->fl.ring_cur][stage][0], c->stream); }
     }
     ~StageTimer() {
         if (on && single) c->attach_stage = -1;
-        else if (on) { (void)hipEventRecord(c->ev[c->ring_cur][stage][1], c->stream); c->ev_used[c->ring_cur][stage] = true; }
+        else if (on) { (void)hipEventRecord(c->ev[c->fl.ring_cur][stage][1], c->stream); c->ev_used[c->fl.ring_cur][stage] = true; }
     }
 };
 
@@ -563,18 +604,18 @@ struct StageTimer {
 // dispatch's completion signal carries the timestamps).  Marker events around them (hipEventRecord) cost 25 us per evaluation in
 // barrier packets and lost launch overlap; attached events cost ~6 us per timed kernel.
 static inline bool timing_on(const eincm_ctx* c) {
-    return (c->cflags & EINCM_CF_TIMING) != 0 || ((c->cflags & EINCM_CF_TIMING_DOMINANT) != 0 && c->timed_now);
+    return (c->cflags & EINCM_CF_TIMING) != 0 || ((c->cflags & EINCM_CF_TIMING_DOMINANT) != 0 && c->fl.timed_now);
 }
 
 template <typename K, typename... Args>
 void launch_timed(eincm_ctx* c, int stage, K kernel, dim3 grid, dim3 block, size_t lds, Args... args) {
     const bool attach = (c->cflags & EINCM_CF_TIMING) ? c->attach_stage == stage
-                      : ((c->cflags & EINCM_CF_TIMING_DOMINANT) && c->timed_now) ? (stage == EINCM_STAGE_SPLAT ? c->time_splat : stage == EINCM_STAGE_GATHER && c->time_gather)
+                      : ((c->cflags & EINCM_CF_TIMING_DOMINANT) && c->fl.timed_now) ? (stage == EINCM_STAGE_SPLAT ? c->time_splat : stage == EINCM_STAGE_GATHER && c->time_gather)
                       : false;
     if (attach) {
-        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, c->stream, c->ev[c->ring_cur][stage][0], c->ev[c->ring_cur][stage][1], 0,
+        hipExtLaunchKernelGGL(kernel, grid, block, (uint32_t)lds, c->stream, c->ev[c->fl.ring_cur][stage][0], c->ev[c->fl.ring_cur][stage][1], 0,
                               args...);
-        c->ev_used[c->ring_cur][stage] = true;
+        c->ev_used[c->fl.ring_cur][stage] = true;
     } else {
         hipLaunchKernelGGL(kernel, grid, block, lds, c->stream, args...);
     }
@@ -682,19 +723,20 @@ void launch_theta_image(eincm_ctx* c, int h, int w, bool identity, bool use_arg,
     c->Theta_valid = true;
 }
 
-// Launch the forward half of the planned evaluation (pend.plan): theta -> Theta -> u64 IWE accumulator.
+// Launch the forward half of the planned evaluation (fl.plan): theta -> Theta -> u64 IWE accumulator.
 int launch_forward(eincm_ctx* c, const double* theta_host) {
-    const EvalPlan& P = c->pend.plan;
+    const EvalPlan& P = c->fl.plan;
     const Geom& g = c->g;
     const bool two_dof = P.shape == EvalPlan::TWO_DOF;
     const size_t nall = (size_t)g.B * P.nth;
+    c->acc_dirty = true;               // from the first command on: an exit below leaves accumulators half-written
     ThetaArg targ;
     static thread_local ThetaArgBig targ_big;
     if (P.use_arg_big) memcpy(targ_big.v, theta_host, nall * sizeof(double));
     if (P.use_arg) memcpy(targ.v, theta_host, nall * sizeof(double));      // theta rides in the kernel arguments
     const double* theta_dev = P.use_arg ? c->d_theta_in : c->h_theta;      // (not read where every kernel has theta in its arguments)
     if (P.theta_src == EvalPlan::THETA_DEVICE) {            // the kernels read the caller's buffer, nothing crosses PCIe
-        theta_dev = c->theta_dev_in;
+        theta_dev = c->fl.io.theta;
     } else if (P.theta_src == EvalPlan::THETA_PINNED) {     // read straight from the pinned, GPU-mapped staging buffer (no copy command)
         memcpy(c->h_theta, theta_host, nall * sizeof(double));
         theta_dev = c->h_theta;
@@ -733,7 +775,6 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
     }
     {
         StageTimer t(c, EINCM_STAGE_SPLAT, true);
-        c->acc_dirty = true;
         if (c->splat.n > 0) {
             const SegList& L = P.splat_short ? c->splat_sh : c->splat;      // (a 2-DoF theta derives its windows itself)
             const size_t theta_tile = two_dof ? 0 : TS * TS * sizeof(double2);     // LDS beside the window
@@ -761,7 +802,7 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
         }
     }
     HIPCHK(c, hipGetLastError());
-    c->pend.theta_dev = theta_dev; c->pend.targ = targ;
+    c->fl.theta_dev = theta_dev; c->fl.targ = targ;
     return EINCM_OK;
 }
 
@@ -828,7 +869,7 @@ void assemble_window(const EvalParams& ep, int R, double sum_con, double sum_cor
 // [-> k_tv] [-> dL/dIWE -> k64_gather -> k64_gfin -> projection] -> results into pinned memory.  eval_end_collect waits and f64_assemble
 // adds the scalars up on the host in index order.  None of the fp32 path's launch policy applies: one segment list, one launch form.
 int f64_launch(eincm_ctx* c, const double* theta_host) {
-    const EvalPlan& P = c->pend.plan;
+    const EvalPlan& P = c->fl.plan;
     const EvalParams& ep = P.ep;
     const Geom& g = c->g;
     const int h = P.h, w = P.w;
@@ -890,21 +931,20 @@ int f64_launch(eincm_ctx* c, const double* theta_host) {
         HIPCHK(c, hipMemcpyAsync(c->h_grad, out, (size_t)g.B * nth * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipGetLastError());
-    c->n_pieces = 0;
-    c->pend.active = true; c->pend.launched = true; c->pend.copy_mode = 0;
+    c->fl.n_pieces = 0; c->fl.copy_mode = 0;
     return EINCM_OK;
 }
 
 // What k_final does, for a float64 evaluation: losses.py:176-203 from the per-image scalars and k_tv's partials, sums in index order.
 void f64_assemble(eincm_ctx* c) {
     const Geom& g = c->g;
-    const EvalParams& ep = c->pend.plan.ep;
+    const EvalParams& ep = c->fl.plan.ep;
     const double Rd = (double)g.R;
     for (int b = 0; b < g.B; ++b) {
         const WinConst& wc = c->h_wc[b];
         OutScal& o = c->h_outs[b];
         memset(&o, 0, sizeof o);
-        if (b < 64 && !((g.wmask >> b) & 1ull)) continue;
+        if (window_sat_out(g, b)) continue;
         double src = 0.0, srr = 0.0, srd = 0.0;
         for (int r = 0; r < g.R; ++r) {
             const F64Scal& s = c->f64.h_scal[(size_t)b * g.R + r];
@@ -916,7 +956,7 @@ void f64_assemble(eincm_ctx* c) {
             srr += wc.mrw[r] * corr / (wc.zc[r] + EPSN);
             srd += wc.mrw[r] * div / (wc.d0 + EPSN);
         }
-        assemble_window(ep, g.R, src, srr, ep.want_div ? srd / Rd : NAN, window_tv(c, ep, b), c->theta_nan[b] != 0, false, o);
+        assemble_window(ep, g.R, src, srr, ep.want_div ? srd / Rd : NAN, window_tv(c, ep, b), c->fl.theta_nan[b] != 0, false, o);
     }
 }
 
@@ -968,15 +1008,15 @@ int obj_constants(eincm_ctx* c) {
 // per-image values, the zero-warp values), on top of what k_final / host_assemble left for the TV and divergence terms.
 void obj_assemble(eincm_ctx* c) {
     const Geom& g = c->g;
-    const EvalPlan& P = c->pend.plan;
+    const EvalPlan& P = c->fl.plan;
     const int ck = P.og.ck, rk = P.og.rk;
     for (int b = 0; b < g.B; ++b) {
-        if (b < 64 && !((g.wmask >> b) & 1ull)) continue;
+        if (window_sat_out(g, b)) continue;
         OutScal& o = c->h_outs[b];
         const ObjConst& oc = c->h_objc[b];
         const WinConst& wc = c->h_wc[b];
         // a NaN theta: host_assemble marks it in theta_nan, k_final in its (default-kind) value
-        const bool bad = P.host_asm ? c->theta_nan[b] != 0 : std::isnan(o.value);
+        const bool bad = P.host_asm ? c->fl.theta_nan[b] != 0 : std::isnan(o.value);
         double sum_rel_con = 0.0, sum_rel_corr = 0.0;
         for (int r = 0; r < g.R; ++r) {
             const double con = c->h_ovals.p[((size_t)b * g.R + r) * 2], corr = c->h_ovals.p[((size_t)b * g.R + r) * 2 + 1];
@@ -1022,13 +1062,13 @@ EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, c
     // theta in the kernel arguments: up to THETA_ARG_MAX doubles in every kernel's; k_theta alone takes a larger one in its own (a 16x16
     // grid of one window: 4 KiB), the event kernels then read the Theta image, or a 2-DoF theta from the pinned staging buffer
     static const bool no_big_arg = getenv("EINCM_NO_BIG_THETA_ARG") != nullptr;
-    P.use_arg = !c->theta_dev_in && !identity && nall <= (size_t)THETA_ARG_MAX;
-    P.use_arg_big = !c->theta_dev_in && !identity && nall <= (size_t)THETA_ARG_BIG && !no_big_arg;
-    P.theta_src = c->theta_dev_in ? EvalPlan::THETA_DEVICE
+    P.use_arg = !c->fl.io.theta && !identity && nall <= (size_t)THETA_ARG_MAX;
+    P.use_arg_big = !c->fl.io.theta && !identity && nall <= (size_t)THETA_ARG_BIG && !no_big_arg;
+    P.theta_src = c->fl.io.theta ? EvalPlan::THETA_DEVICE
                 : (P.use_arg_big && (P.use_arg || !two_dof)) ? EvalPlan::THETA_ARGS
                 : nall <= ZERO_COPY_MAX ? EvalPlan::THETA_PINNED : EvalPlan::THETA_PIECES;
     // (device-resident theta: no host copy for ensure_theta_image to rebuild the image from)
-    P.need_theta_image = !two_dof || ep.want_tv || c->theta_dev_in;
+    P.need_theta_image = !two_dof || ep.want_tv || c->fl.io.theta;
 
     // LDS window capacity for this evaluation: the host knows theta, hence the largest displacement a segment can see.
     // Small windows give 8 workgroups per CU; windows too small for the flow push taps onto the slow direct-to-HBM path.
@@ -1038,7 +1078,7 @@ EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, c
     if (!c->wincap_fixed) {
         double vmax = 0.0;
         const size_t stride = nall > 8192 ? nall / 8192 : 1;            // dense theta: sample (any capacity is correct; 65536 samples cost 90 us)
-        if (c->theta_dev_in) vmax = (c->vmax_hint >= 0.0 && std::isfinite(c->vmax_hint)) ? c->vmax_hint : 1e9;      // unknown: the largest windows
+        if (c->fl.io.theta) vmax = (c->fl.io.vmax >= 0.0 && std::isfinite(c->fl.io.vmax)) ? c->fl.io.vmax : 1e9;      // unknown: the largest windows
         else if (stride == 1) { for (size_t i = 0; i < nall; ++i) { const double a = std::fabs(theta_host[i]); vmax = std::max(vmax, a <= 1.7e308 ? a : 0.0); } }   // (vectorises)
         else for (size_t i = 0; i < nall; i += stride) { const double a = std::fabs(theta_host[i]); if (a > vmax && std::isfinite(a)) vmax = a; }
         // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
@@ -1070,9 +1110,9 @@ EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, c
     // included (k_tv projects its own gradient, the tail combines it; a 2-DoF theta with TV keeps k_final): host assembly
     static const bool no_host_asm = getenv("EINCM_NO_HOST_ASM") != nullptr;
     const bool tail_ok = c->splat_rad == 1 && P.shape == EvalPlan::GRID && c->proj_in_gather && c->itembase_valid && nall <= ZERO_COPY_MAX &&
-                         !c->theta_dev_in;
+                         !c->fl.io.theta;
     P.host_asm = want_grad && ((two_dof && !ep.want_tv) || tail_ok) && !ep.want_div && !P.full_aux && !no_host_asm && !c->device_results &&
-                 !c->theta_dev_in;
+                 !c->fl.io.theta;
     P.grid_tail = P.host_asm && P.shape == EvalPlan::GRID;
     // Gradient evaluations with the grad-mag contrast take the contrast energy from k_imgrad (which computes the Scharr images anyway),
     // so the statistics are a pure streaming reduction.  A new objective kind: k_stats_stream -> k_obj_parts -> k_obj_grad -> gather;
@@ -1091,28 +1131,27 @@ EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, c
     P.events_projected = two_dof || P.proj;
     P.nsrc = (!want_grad || identity) ? 0 : (P.events_projected ? 0 : 1) + ((ep.use_tv_grad && !P.tv_proj) ? 1 : 0);
     // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
-    P.zero_copy_out = !c->device_results && !c->theta_dev_in && !identity && nall <= ZERO_COPY_MAX;
+    P.zero_copy_out = !c->device_results && !c->fl.io.theta && !identity && nall <= ZERO_COPY_MAX;
     return P;
 }
 
 // theta_nan[b]: a NaN / Inf somewhere in window b's theta (host-assembled and float64 evaluations)
 void scan_theta(eincm_ctx* c, const double* theta_host, size_t nth) {
-    c->theta_nan.assign((size_t)c->g.B, 0);
-    for (int b = 0; b < c->g.B; ++b) {            // branch-free (vectorises): an OR over the exponent bits, 4096 values at 16x16 x 8 windows
-        const double* __restrict__ tb = theta_host + (size_t)b * nth;
-        uint64_t bad = 0;
-        for (size_t i = 0; i < nth; ++i) { uint64_t u; memcpy(&u, tb + i, sizeof u); bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull); }
-        c->theta_nan[b] = bad != 0;
-    }
+    c->fl.theta_nan.assign((size_t)c->g.B, 0);
+    for (int b = 0; b < c->g.B; ++b) c->fl.theta_nan[b] = copy_scan_finite(nullptr, theta_host + (size_t)b * nth, nth);   // (4096 values at 16x16 x 8 windows)
 }
 
 // First half of an evaluation: checks, side effects, plan_eval, then theta -> Theta -> IWE stack (launch_forward; a float64 context
-// enqueues the whole evaluation, f64_launch).  theta_host: (B,h,w,2) doubles.
-int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad, const uint8_t* active = nullptr) {
+// enqueues the whole evaluation, f64_launch).  theta_host: (B,h,w,2) doubles, or io.theta in HBM.  Leaves the flight FORWARD (float64:
+// LAUNCHED); any other exit abandons it.  A forward half that was never finished is discarded.
+int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad, const uint8_t* active = nullptr,
+               const DevIo& io = DevIo{}) {
     HostPhase hp(c, EINCM_HP_BEGIN);
-    // (checked before the mask is touched: the evaluation in flight reads g.wmask again when it is collected)
-    if (c->pend.active && c->pend.launched)
+    // (checked before the flight is touched: the evaluation in flight reads the mask and its plan again when it is collected)
+    if (c->fl.launched())
         return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
+    FlightGuard guard(c);
+    c->fl.land(); c->fl.io = io;
     {   // which windows take part (eincm_loss_grad_masked); the others' workgroups leave at once, their outputs are not written
         unsigned long long m = ~0ull;
         if (active) { m = 0ull; for (int b = 0; b < c->g.B && b < 64; ++b) if (active[b]) m |= 1ull << b; }
@@ -1121,7 +1160,6 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
     const Geom& g = c->g;
     const size_t img = (size_t)g.H * g.W;
     const size_t nth = (size_t)h * w * 2;
-    c->pend.active = false; c->pend.launched = false;
     if (p->delta != 0.0 && want_grad && !c->fp64) {      // rare path (the reference keeps delta = 0, configs/main.yaml:19): allocated on first use
         HIPCHK(c, ensure(c, c->d_gdiv, (size_t)c->maxB * c->maxR * img));
         HIPCHK(c, ensure(c, c->d_dgparts, (size_t)c->maxB * c->maxR * g.ntiles * 2));
@@ -1146,35 +1184,40 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         if (rc) return rc;
     }
     const EvalPlan P = plan_eval(c, theta_host, h, w, p, want_grad);
-    if (c->fp64) { c->pend.plan = P; scan_theta(c, theta_host, nth); return f64_launch(c, theta_host); }
+    if (c->fp64) {
+        c->fl.plan = P; scan_theta(c, theta_host, nth);
+        if (const int rc = f64_launch(c, theta_host)) return rc;
+        c->fl.state = Flight::LAUNCHED;
+        return guard.keep();
+    }
     if (c->acc_dirty) { const int rcd = clear_accumulators(c); if (rcd) return rcd; }
-    if (c->cflags & EINCM_CF_TIMING_DOMINANT) c->timed_now = (c->time_counter++ % c->time_period) == 0;
+    if (c->cflags & EINCM_CF_TIMING_DOMINANT) c->fl.timed_now = (c->time_counter++ % c->time_period) == 0;
     if (timing_on(c)) {
         if (c->ring_n == c->ring_size) { const int rcr = drain_event_ring(c, c->ring_size - 1); if (rcr) return rcr; }   // ring full: read the oldest
-        c->ring_cur = (c->ring_lo + c->ring_n) % c->ring_size;
-        for (int s = 0; s <= EINCM_N_STAGES; ++s) c->ev_used[c->ring_cur][s] = false;
-        if (c->ring_size == 1) (void)hipEventRecord(c->ev[c->ring_cur][EINCM_N_STAGES][0], c->stream);    // EINCM_CF_TIMING only
+        c->fl.ring_cur = (c->ring_lo + c->ring_n) % c->ring_size;
+        for (int s = 0; s <= EINCM_N_STAGES; ++s) c->ev_used[c->fl.ring_cur][s] = false;
+        if (c->ring_size == 1) (void)hipEventRecord(c->ev[c->fl.ring_cur][EINCM_N_STAGES][0], c->stream);    // EINCM_CF_TIMING only
     }
-    c->pend.plan = P;
+    c->fl.plan = P;
     c->policy_evaluated = true;
     c->g.wincap = P.wincap; c->g.winmaxw = P.winmaxw; c->g.pitch_aligned = P.pitch_aligned; c->g.wincap_a = P.wincap_a; c->g.winmaxw_a = P.winmaxw_a;
     if (P.host_asm) scan_theta(c, theta_host, nth);
     if (const int rc = launch_forward(c, theta_host)) return rc;
-    c->pend.active = true;
-    return EINCM_OK;
+    c->fl.state = Flight::FORWARD;
+    return guard.keep();
 }
 
 // The D2H copies of an evaluation whose results k_final left in HBM (d_outs, d_grad).  Enqueued right behind the kernels, or - with
 // eincm_set_device_results - only by eincm_finish_collect, after the caller has all-reduced the gradient in HBM.
 int enqueue_result_copies(eincm_ctx* c) {
     const Geom& g = c->g;
-    const bool want_grad = c->pend.plan.want_grad;
-    const size_t nth = c->pend.plan.nth;
-    c->n_pieces = 0;
-    if (c->theta_dev_in) {                           // eincm_loss_grad_device: scalars to the host, the gradient device to device
+    const bool want_grad = c->fl.plan.want_grad;
+    const size_t nth = c->fl.plan.nth;
+    c->fl.n_pieces = 0;
+    if (c->fl.io.theta) {                           // eincm_loss_grad_device: scalars to the host, the gradient device to device
         HIPCHK(c, hipMemcpyAsync(c->h_outs, c->d_outs, (size_t)g.B * sizeof(OutScal), hipMemcpyDeviceToHost, c->stream));
-        if (want_grad && c->grad_dev_out)
-            HIPCHK(c, hipMemcpyAsync(c->grad_dev_out, c->d_grad, (size_t)g.B * nth * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        if (want_grad && c->fl.io.grad)
+            HIPCHK(c, hipMemcpyAsync(c->fl.io.grad, c->d_grad, (size_t)g.B * nth * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         return EINCM_OK;
     }
     if (want_grad && (size_t)g.B * nth >= ((size_t)1 << 17)) {
@@ -1183,22 +1226,22 @@ int enqueue_result_copies(eincm_ctx* c) {
         HIPCHK(c, hipMemcpyAsync(c->h_outs, c->d_outs, (size_t)g.B * sizeof(OutScal), hipMemcpyDeviceToHost, c->stream));
         // the rows of windows that sat this evaluation out were not written: clear them, so that they come back as 0 and pass the
         // host's finite scan (eval_end_collect zeroes them on the host only when the gradient comes in one piece)
-        for (int b = 0; b < g.B && b < 64; ) {
-            if ((g.wmask >> b) & 1ull) { ++b; continue; }
+        for (int b = 0; b < g.B; ) {
+            if (!window_sat_out(g, b)) { ++b; continue; }
             int e = b + 1;
-            while (e < g.B && e < 64 && !((g.wmask >> e) & 1ull)) ++e;
+            while (e < g.B && window_sat_out(g, e)) ++e;
             HIPCHK(c, hipMemsetAsync(c->d_grad + (size_t)b * nth, 0, (size_t)(e - b) * nth * sizeof(double), c->stream));
             b = e;
         }
         const size_t total = (size_t)g.B * nth;
-        c->piece_len = (total + eincm_ctx::GRAD_PIECES - 1) / eincm_ctx::GRAD_PIECES;
+        c->fl.piece_len = (total + eincm_ctx::GRAD_PIECES - 1) / eincm_ctx::GRAD_PIECES;
         for (int k = 0; k < eincm_ctx::GRAD_PIECES; ++k) {
-            const size_t off = (size_t)k * c->piece_len;
+            const size_t off = (size_t)k * c->fl.piece_len;
             if (off >= total) break;
-            const size_t n = std::min(c->piece_len, total - off);
+            const size_t n = std::min(c->fl.piece_len, total - off);
             HIPCHK(c, hipMemcpyAsync(c->h_grad + off, c->d_grad + off, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipEventRecord(c->ev_piece[k], c->stream));
-            c->n_pieces = k + 1;
+            c->fl.n_pieces = k + 1;
         }
     } else if (want_grad && g.B == c->maxB) {      // outs and grad are contiguous: one copy
         HIPCHK(c, hipMemcpyAsync(c->h_outs, c->d_outs, (size_t)g.B * sizeof(OutScal) + (size_t)g.B * nth * sizeof(double),
@@ -1212,12 +1255,14 @@ int enqueue_result_copies(eincm_ctx* c) {
 }
 
 // Second half, part 1: enqueue image statistics, dL/dIWE, gather, projection, scalar assembly (on whatever is in the IWE
-// stack now) and the copy back to pinned memory, as planned (pend.plan).  Returns without synchronising.
+// stack now) and the copy back to pinned memory, as planned (fl.plan).  Returns without synchronising: FORWARD -> LAUNCHED; any
+// other exit abandons the flight.
 int eval_end_launch(eincm_ctx* c) {
-    if (!c->pend.active) return fail(c, EINCM_ERR_STATE, "no evaluation in flight");
-    if (c->pend.launched) return EINCM_OK;
+    if (c->fl.idle()) return fail(c, EINCM_ERR_STATE, "no evaluation in flight");
+    if (c->fl.launched()) return EINCM_OK;
+    FlightGuard guard(c);
     HostPhase hp(c, EINCM_HP_LAUNCH);
-    const EvalPlan& P = c->pend.plan;
+    const EvalPlan& P = c->fl.plan;
     const EvalParams& ep = P.ep;
     Geom g = c->g;
     const bool identity = P.shape == EvalPlan::IDENTITY, two_dof = P.shape == EvalPlan::TWO_DOF, want_grad = P.want_grad, host_asm = P.host_asm;
@@ -1299,8 +1344,8 @@ int eval_end_launch(eincm_ctx* c) {
                     // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
                     auto go = [&](auto kernel) {
                         launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(NT), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, c->d_tmm,
-                                     c->d_edge_ts, c->d_G, c->d_gTheta, g11, c->d_wc, c->d_gmax, c->stage.wide ? 1 : 0, use_arg, c->pend.theta_dev,
-                                     c->pend.targ);
+                                     c->d_edge_ts, c->d_G, c->d_gTheta, g11, c->d_wc, c->d_gmax, c->stage.wide ? 1 : 0, use_arg, c->fl.theta_dev,
+                                     c->fl.targ);
                     };
                     if (two_dof) c->splat_rad == 0 ? go(k_gather_r<THETA_CONST, 0>) : c->splat_rad == 2 ? go(k_gather_r<THETA_CONST, 2>) : go(k_gather_r<THETA_CONST, 3>);
                     else         c->splat_rad == 0 ? go(k_gather_r<THETA_TILE, 0>) : c->splat_rad == 2 ? go(k_gather_r<THETA_TILE, 2>) : go(k_gather_r<THETA_TILE, 3>);
@@ -1308,7 +1353,7 @@ int eval_end_launch(eincm_ctx* c) {
                     auto go = [&](auto kernel, int nthreads) {
                         launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(nthreads), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta,
                                      c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, g11, c->d_wc, c->d_gmax, L.d_order, use_arg,
-                                     c->pend.theta_dev, c->pend.targ, P.h, P.w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p, (int)c->coarse_cap,
+                                     c->fl.theta_dev, c->fl.targ, P.h, P.w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p, (int)c->coarse_cap,
                                      P.grid_tail ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad,
                                      (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth.p + (size_t)c->maxB * c->coarse_cap);
                     };
@@ -1339,13 +1384,13 @@ int eval_end_launch(eincm_ctx* c) {
         }
     }
     HIPCHK(c, hipGetLastError());
-    c->n_pieces = 0;
-    c->pend.copy_mode = (P.zero_copy_out || host_asm) ? 0 : 1;
-    if (c->pend.copy_mode && !c->device_results) { const int rcc = enqueue_result_copies(c); if (rcc) return rcc; c->pend.copy_mode = 0; }
-    if (timing && c->ring_size == 1) { (void)hipEventRecord(c->ev[c->ring_cur][EINCM_N_STAGES][1], c->stream); c->ev_used[c->ring_cur][EINCM_N_STAGES] = true; }
-    c->pend.launched = true;
+    c->fl.n_pieces = 0;
+    c->fl.copy_mode = (P.zero_copy_out || host_asm) ? 0 : 1;
+    if (c->fl.copy_mode && !c->device_results) { const int rcc = enqueue_result_copies(c); if (rcc) return rcc; c->fl.copy_mode = 0; }
+    if (timing && c->ring_size == 1) { (void)hipEventRecord(c->ev[c->fl.ring_cur][EINCM_N_STAGES][1], c->stream); c->ev_used[c->fl.ring_cur][EINCM_N_STAGES] = true; }
+    c->fl.state = Flight::LAUNCHED;
     c->acc_dirty = false;          // every accumulator this evaluation touched has been consumed (and cleared) by the kernels above
-    return EINCM_OK;
+    return guard.keep();
 }
 
 // Host-assembled evaluations (plan.host_asm): what k_final does for them, in fp64 on the host from the partials the kernels wrote
@@ -1354,14 +1399,14 @@ int eval_end_launch(eincm_ctx* c) {
 // losses.py:176-203 without the divergence term (the planner routes those evaluations to k_final).
 void host_assemble(eincm_ctx* c) {
     const Geom& g = c->g;
-    const EvalPlan& P = c->pend.plan;
+    const EvalPlan& P = c->fl.plan;
     const EvalParams& ep = P.ep;
     const double HW = (double)g.H * (double)g.W;
     for (int b = 0; b < g.B; ++b) {
         const WinConst& wc = c->h_wc[b];
         OutScal& o = c->h_outs[b];
         memset(&o, 0, sizeof o);
-        if (b < 64 && !((g.wmask >> b) & 1ull)) continue;       // sat this evaluation out (eval_end_collect marks its outputs)
+        if (window_sat_out(g, b)) continue;       // sat this evaluation out (eval_end_collect marks its outputs)
         double sum_rel_con = 0.0, sum_rel_corr = 0.0;
         for (int r = 0; r < g.R; ++r) {
             const double* q = c->h_img + ((size_t)b * g.R + r) * IMGSCAL_N;
@@ -1381,7 +1426,7 @@ void host_assemble(eincm_ctx* c) {
             sum_rel_con += wc.mrw[r] * con / (c0 + EPSN);
             sum_rel_corr += wc.mrw[r] * (-mse) / (wc.zc[r] + EPSN);
         }
-        assemble_window(ep, g.R, sum_rel_con, sum_rel_corr, NAN, window_tv(c, ep, b), c->theta_nan[b] != 0, true, o);
+        assemble_window(ep, g.R, sum_rel_con, sum_rel_corr, NAN, window_tv(c, ep, b), c->fl.theta_nan[b] != 0, true, o);
         if (P.shape == EvalPlan::TWO_DOF) {                  // 2-DoF: the gather's per-workgroup partials, added in index order
             const int lo = c->gather_2.h_win_item0[b], hi = c->gather_2.h_win_item0[b + 1];
             const double* p = c->h_g11 + (size_t)lo * g.R * 2;
@@ -1402,59 +1447,49 @@ void host_assemble(eincm_ctx* c) {
     }
 }
 
-// Second half, part 2: wait for the stream and hand the results over.
+// Second half, part 2: wait for the stream and hand the results over.  LAUNCHED -> IDLE once the stream has drained; an exit before
+// that abandons the flight (the kernels in flight read the pinned theta staging buffer and write the pinned result block, so the
+// context must not look idle, and accept the next theta, while they run).
 int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
-    if (!c->pend.active || !c->pend.launched) return fail(c, EINCM_ERR_STATE, "no evaluation in flight");
+    if (!c->fl.launched()) return fail(c, EINCM_ERR_STATE, "no evaluation in flight");
+    FlightGuard guard(c);
+    Flight& fl = c->fl;
     const Geom& g = c->g;
-    const bool want_grad = c->pend.plan.want_grad;
-    const size_t nth = c->pend.plan.nth;
-    // The stream is drained before ANY return: the kernels in flight read the pinned theta staging buffer and write the pinned
-    // result block, so the context must not look idle (and accept the next theta) while they run.
-    if (c->pend.copy_mode) { const int rcc = enqueue_result_copies(c); c->pend.copy_mode = 0; if (rcc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rcc; } }
-    bool piece_bad = false;
-    if (c->n_pieces > 0 && want_grad && grad) {
-        const size_t total = (size_t)g.B * nth;
-        for (int k = 0; k < c->n_pieces; ++k) {
+    const bool want_grad = fl.plan.want_grad;
+    const size_t nth = fl.plan.nth, total = (size_t)g.B * nth;
+    if (fl.copy_mode) { fl.copy_mode = 0; if (const int rcc = enqueue_result_copies(c)) return rcc; }
+    bool nonfinite = false;
+    if (fl.n_pieces > 0 && want_grad && grad) {
+        for (int k = 0; k < fl.n_pieces; ++k) {
             if (hipEventSynchronize(c->ev_piece[k]) != hipSuccess) break;      // the stream sync below reports the error
-            const size_t off = (size_t)k * c->piece_len, n = std::min(c->piece_len, total - off);
-            const double* __restrict__ src = c->h_grad + off;
-            double* __restrict__ dst = grad + off;
-            uint64_t bad = 0;
-            for (size_t i = 0; i < n; ++i) {
-                uint64_t u;
-                memcpy(&u, src + i, sizeof u);
-                dst[i] = src[i];
-                bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
-            }
-            piece_bad = piece_bad || bad != 0;
+            const size_t off = (size_t)k * fl.piece_len;
+            if (copy_scan_finite(grad + off, c->h_grad + off, std::min(fl.piece_len, total - off))) nonfinite = true;
         }
     }
     {
         HostPhase hp(c, EINCM_HP_WAIT);
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    c->pend.active = false; c->pend.launched = false;
+    const bool dev_io = fl.io.theta != nullptr;      // the gradient went device to device (enqueue_result_copies)
+    fl.land();
+    guard.keep();
     ++c->hp_n;
-    const bool dev_io = c->theta_dev_in != nullptr;           // the gradient went device to device (enqueue_result_copies)
+    const bool whole_grad = want_grad && fl.n_pieces == 0 && !dev_io;        // in pinned memory, in one piece
     if (want_grad && !grad && !dev_io) return fail(c, EINCM_ERR_ARG, "the evaluation was begun with a gradient but grad is NULL");
     HostPhase hp(c, EINCM_HP_COLLECT);
-    if (c->pend.plan.host_asm) host_assemble(c);
+    if (fl.plan.host_asm) host_assemble(c);
     else if (c->fp64) f64_assemble(c);
-    if (c->pend.plan.obj) obj_assemble(c);
-    int rc = collect_timings(c);
-    if (rc) return rc;
+    if (fl.plan.obj) obj_assemble(c);
+    if (const int rc = collect_timings(c)) return rc;
     c->have_eval = true;
     c->G_valid = want_grad;
 
-    bool nonfinite = false;
+    OutScal sat_out{};                               // a window that was not evaluated: NaN value, zero gradient, no verdict
+    sat_out.value = sat_out.mean_rel_corr = sat_out.mean_rel_contrast = sat_out.mean_rel_div = sat_out.tv = NAN;
     for (int b = 0; b < g.B; ++b) {
-        if (b < 64 && !((g.wmask >> b) & 1ull)) {               // not evaluated: NaN value, zero gradient, no verdict
-            if (value) value[b] = NAN;
-            if (aux) { aux[b].final_loss = NAN; aux[b].mean_rel_corr = NAN; aux[b].mean_rel_contrast = NAN; aux[b].mean_rel_iwe_divergence = NAN; aux[b].theta_total_variation = NAN; }
-            if (want_grad && c->n_pieces == 0 && !dev_io) for (size_t i = 0; i < nth; ++i) c->h_grad[(size_t)b * nth + i] = 0.0;
-            continue;
-        }
-        const OutScal& o = c->h_outs[b];
+        const bool out = window_sat_out(g, b);
+        if (out && whole_grad) for (size_t i = 0; i < nth; ++i) c->h_grad[(size_t)b * nth + i] = 0.0;
+        const OutScal& o = out ? sat_out : c->h_outs[b];
         if (value) value[b] = o.value;
         if (aux) {
             aux[b].final_loss = o.value;
@@ -1465,41 +1500,24 @@ int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) 
         }
         if (o.nonfinite != 0.0) nonfinite = true;
     }
-    if (piece_bad) nonfinite = true;
-    if (want_grad && c->n_pieces == 0 && !dev_io) {
-        // copy out and look for NaN/Inf in the same pass; an integer OR-reduction over the exponent bits vectorises, an
-        // early-exit std::isfinite loop does not (0.6 ms of a 1.8 ms dense-theta evaluation at 480x640)
-        const size_t n = (size_t)g.B * nth;
-        const double* __restrict__ src = c->h_grad;
-        uint64_t bad = 0;
-        for (size_t i = 0; i < n; ++i) {
-            uint64_t u;
-            memcpy(&u, src + i, sizeof u);
-            grad[i] = src[i];
-            bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull);
-        }
-        if (bad) nonfinite = true;
-    }
+    if (whole_grad && copy_scan_finite(grad, c->h_grad, total)) nonfinite = true;      // copy out and look for NaN / Inf in the same pass
     if (nonfinite) return fail(c, EINCM_ERR_NONFINITE, "loss or gradient is not finite");
     return EINCM_OK;
 }
 
 int eval_end(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
-    if (c->pend.active && c->pend.plan.want_grad && !grad) {
-        (void)hipStreamSynchronize(c->stream);       // the forward half is in flight and reads the pinned theta buffer
-        c->pend.active = false;
+    if (!c->fl.idle() && c->fl.plan.want_grad && !grad) {
+        c->fl.abandon(c->stream);                    // the forward half is in flight and reads the pinned theta buffer
         return fail(c, EINCM_ERR_ARG, "the evaluation was begun with a gradient but grad is NULL");
     }
-    const int rc = eval_end_launch(c);
-    if (rc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rc; }
+    if (const int rc = eval_end_launch(c)) return rc;
     return eval_end_collect(c, value, grad, aux);
 }
 
 // The whole evaluation.  theta_host: (B,h,w,2) doubles (already validated).
 int evaluate(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p,
-             double* value, double* grad, eincm_aux* aux, bool /*for_constants*/, const uint8_t* active = nullptr) {
-    int rc = eval_begin(c, theta_host, h, w, p, grad != nullptr, active);
-    if (rc) return rc;
+             double* value, double* grad, eincm_aux* aux, const uint8_t* active = nullptr) {
+    if (const int rc = eval_begin(c, theta_host, h, w, p, grad != nullptr, active)) return rc;
     return eval_end(c, value, grad, aux);
 }
 
@@ -1545,6 +1563,19 @@ int eval_ready(eincm_ctx* c, const char* who, bool need_constants = true) {
     return EINCM_OK;
 }
 
+// The argument checks of an evaluation entry point; the call names what differs from eincm_loss_grad's
+enum : unsigned { THETA_MAY_BE_NULL = 1, NO_VALUE = 2, CONSTANTS_MAY_PEND = 4, NOT_IN_FP64 = 8 };
+int eval_entry(eincm_ctx* c, const char* who, const void* theta, int h, int w, const eincm_params* p, const void* value, unsigned except = 0) {
+    if (!c) return EINCM_ERR_ARG;
+    if (c->fp64 && (except & NOT_IN_FP64)) return fail(c, EINCM_ERR_UNSUPPORTED, "%s is not supported in fp64 mode (EINCM_CF_FP64)", who);
+    if (const int rc = eval_ready(c, who, !(except & CONSTANTS_MAY_PEND))) return rc;
+    if ((!theta && !(except & THETA_MAY_BE_NULL)) || !p || (!value && !(except & NO_VALUE))) return fail(c, EINCM_ERR_ARG, "%s: null pointer argument", who);
+    if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "%s: theta shape (%d,%d,2) invalid", who, h, w);
+    if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "%s: method %d unknown", who, p->method);
+    HIPCHK(c, hipSetDevice(c->device));
+    return EINCM_OK;
+}
+
 // c0, zc[r], d0 are 1 while the theta = 0 pass runs, so that it is well defined; store_constants overwrites them.
 int preset_constants(eincm_ctx* c) {
     for (int b = 0; b < c->g.B; ++b) {
@@ -1562,7 +1593,7 @@ int window_constants(eincm_ctx* c) {
     const std::vector<double> zero((size_t)c->g.B * 2, 0.0);
     std::vector<double> val((size_t)c->g.B);
     const eincm_params p = zero_pass_params();
-    const int rc = evaluate(c, zero.data(), 1, 1, &p, val.data(), nullptr, nullptr, true);
+    const int rc = evaluate(c, zero.data(), 1, 1, &p, val.data(), nullptr, nullptr);
     if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) c->staged = false;
     return store_constants(c, rc);
 }
@@ -1817,7 +1848,7 @@ static int f64_ishift(int64_t n_events) {
 // Everything a staging refuses from its arguments alone, before it touches the context or enqueues work.
 static int check_staging(eincm_ctx* c, const StageArgs& a) {
     if (!c) return EINCM_ERR_ARG;
-    if (c->pend.active && c->pend.launched)
+    if (c->fl.launched())
         return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
     if (a.B < 1 || a.B > c->maxB) return fail(c, EINCM_ERR_ARG, "n_windows %d outside 1..%d", a.B, c->maxB);
     if (a.R < 1 || a.R > c->maxR) return fail(c, EINCM_ERR_ARG, "n_refs %d outside 1..%d", a.R, c->maxR);
@@ -2205,12 +2236,8 @@ int eincm_set_windows_ptrs(eincm_ctx* c, int n_windows, int n_refs, const int64_
 
 // ---- event-sharded evaluation: forward half / [caller all-reduces the IWE stack] / finishing half ----
 int eincm_forward_iwe(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, int want_grad) {
-    if (!c) return EINCM_ERR_ARG;
-    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_forward_iwe (event-sharded mode) is not supported in fp64 mode (EINCM_CF_FP64)");
-    if (const int rc = eval_ready(c, "eincm_forward_iwe", false)) return rc;
-    if (!p || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "bad argument");
-    if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
-    HIPCHK(c, hipSetDevice(c->device));
+    if (const int rc = eval_entry(c, "eincm_forward_iwe", theta, h, w, p, nullptr,
+                                  THETA_MAY_BE_NULL | NO_VALUE | CONSTANTS_MAY_PEND | NOT_IN_FP64)) return rc;
     std::vector<double> zero;
     eincm_params pz;
     if (!theta) {                                    // NULL theta = the theta = 0 pass that yields the window constants
@@ -2219,10 +2246,10 @@ int eincm_forward_iwe(eincm_ctx* c, const double* theta, int h, int w, const ein
     } else if (c->constants_pending) {
         return fail(c, EINCM_ERR_STATE, "window constants pending: run eincm_forward_iwe(NULL theta), sum the IWE stacks, eincm_finish_constants");
     }
-    int rc = eval_begin(c, theta, h, w, p, want_grad != 0);
-    if (rc) return rc;
+    if (const int rc = eval_begin(c, theta, h, w, p, want_grad != 0)) return rc;
+    FlightGuard guard(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));     // the IWE stack is complete: safe to reduce on any stream
-    return EINCM_OK;
+    return guard.keep();
 }
 
 int eincm_finish_loss_grad(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
@@ -2237,13 +2264,8 @@ int eincm_finish_loss_grad(eincm_ctx* c, double* value, double* grad, eincm_aux*
 // theta and gradient resident in HBM (a caller whose optimiser lives on the GPU): nothing but the scalars crosses PCIe.
 int eincm_loss_grad_device(eincm_ctx* c, const double* theta_dev, int h, int w, const eincm_params* p, double theta_abs_max,
                            double* value, double* grad_dev, eincm_aux* aux) {
-    if (!c) return EINCM_ERR_ARG;
-    if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_loss_grad_device is not supported in fp64 mode (EINCM_CF_FP64)");
-    if (const int rc = eval_ready(c, "eincm_loss_grad_device")) return rc;
-    if (!theta_dev || !p || !value || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "bad argument");
-    if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
+    if (const int rc = eval_entry(c, "eincm_loss_grad_device", theta_dev, h, w, p, value, NOT_IN_FP64)) return rc;
     if (c->device_results) return fail(c, EINCM_ERR_STATE, "eincm_set_device_results is on: use the split finishing half");
-    HIPCHK(c, hipSetDevice(c->device));
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, theta_dev) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
         (void)hipGetLastError();
@@ -2253,19 +2275,15 @@ int eincm_loss_grad_device(eincm_ctx* c, const double* theta_dev, int h, int w, 
         (void)hipGetLastError();
         return fail(c, EINCM_ERR_ARG, "grad_dev is not memory of device %d", c->device);
     }
-    struct Reset { eincm_ctx* c; ~Reset() { c->theta_dev_in = nullptr; c->grad_dev_out = nullptr; c->vmax_hint = -1.0; } } reset{c};
-    c->theta_dev_in = theta_dev; c->grad_dev_out = grad_dev; c->vmax_hint = theta_abs_max;
-    int rc = eval_begin(c, nullptr, h, w, p, grad_dev != nullptr);
-    if (rc) return rc;
-    rc = eval_end_launch(c);
-    if (rc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rc; }
+    if (const int rc = eval_begin(c, nullptr, h, w, p, grad_dev != nullptr, nullptr, DevIo{theta_dev, grad_dev, theta_abs_max})) return rc;
+    if (const int rc = eval_end_launch(c)) return rc;
     return eval_end_collect(c, value, nullptr, aux);
 }
 
 int eincm_set_device_results(eincm_ctx* c, int on) {
     if (!c) return EINCM_ERR_ARG;
     if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_set_device_results is not supported in fp64 mode (EINCM_CF_FP64)");
-    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
     c->device_results = on != 0;
     return EINCM_OK;
 }
@@ -2276,17 +2294,17 @@ int eincm_finish_launch(eincm_ctx* c) {
     if (!c->device_results) return fail(c, EINCM_ERR_STATE, "eincm_finish_launch needs eincm_set_device_results(ctx, 1)");
     if (c->constants_pending) return fail(c, EINCM_ERR_STATE, "window constants pending (eincm_finish_constants)");
     HIPCHK(c, hipSetDevice(c->device));
-    const int rc = eval_end_launch(c);
-    if (rc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rc; }
+    if (const int rc = eval_end_launch(c)) return rc;
+    FlightGuard guard(c);
     HIPCHK(c, hipStreamSynchronize(c->stream));     // the gradient is complete in HBM: safe to reduce on any stream
-    return EINCM_OK;
+    return guard.keep();
 }
 
 int eincm_grad_device_ptr(eincm_ctx* c, void** dptr, int64_t* n_doubles) {
     if (!c || !dptr || !n_doubles) return EINCM_ERR_ARG;
     if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_grad_device_ptr is not supported in fp64 mode (EINCM_CF_FP64)");
-    if (!c->pend.active || !c->pend.launched || !c->pend.plan.want_grad) return fail(c, EINCM_ERR_STATE, "no launched gradient evaluation (eincm_finish_launch)");
-    *dptr = c->d_grad; *n_doubles = (int64_t)c->g.B * (int64_t)c->pend.plan.nth;
+    if (!c->fl.launched() || !c->fl.plan.want_grad) return fail(c, EINCM_ERR_STATE, "no launched gradient evaluation (eincm_finish_launch)");
+    *dptr = c->d_grad; *n_doubles = (int64_t)c->g.B * (int64_t)c->fl.plan.nth;
     return EINCM_OK;
 }
 
@@ -2294,7 +2312,7 @@ int eincm_finish_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* a
     if (!c) return EINCM_ERR_ARG;
     if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "eincm_finish_collect is not supported in fp64 mode (EINCM_CF_FP64)");
     if (!value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    if (!c->pend.active || !c->pend.launched) return fail(c, EINCM_ERR_STATE, "eincm_finish_collect without eincm_finish_launch");
+    if (!c->fl.launched()) return fail(c, EINCM_ERR_STATE, "eincm_finish_collect without eincm_finish_launch");
     HIPCHK(c, hipSetDevice(c->device));
     return eval_end_collect(c, value, grad, aux);
 }
@@ -2329,45 +2347,27 @@ int eincm_loss_grad_async(eincm_ctx* c, const double* theta, int h, int w, const
 }
 
 int eincm_loss_grad_masked_async(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, const uint8_t* active, int want_grad) {
-    if (!c) return EINCM_ERR_ARG;
-    if (const int rc = eval_ready(c, "eincm_loss_grad_async")) return rc;
-    if (!theta || !p) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
-    if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
-    HIPCHK(c, hipSetDevice(c->device));
-    int rc = eval_begin(c, theta, h, w, p, want_grad != 0, active);
-    if (rc) return rc;
-    rc = eval_end_launch(c);
-    if (rc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; }
-    return rc;
+    if (const int rc = eval_entry(c, "eincm_loss_grad_async", theta, h, w, p, nullptr, NO_VALUE)) return rc;
+    if (const int rc = eval_begin(c, theta, h, w, p, want_grad != 0, active)) return rc;
+    return eval_end_launch(c);
 }
 
 int eincm_loss_grad_wait(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
-    if (!c->pend.active || !c->pend.launched) return fail(c, EINCM_ERR_STATE, "eincm_loss_grad_wait without eincm_loss_grad_async");
+    if (!c->fl.launched()) return fail(c, EINCM_ERR_STATE, "eincm_loss_grad_wait without eincm_loss_grad_async");
     HIPCHK(c, hipSetDevice(c->device));
     return eval_end_collect(c, value, grad, aux);      // drains the stream and clears the pending state on every path
 }
 
 int eincm_loss_grad(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, double* value, double* grad, eincm_aux* aux) {
-    if (!c) return EINCM_ERR_ARG;
-    if (const int rc = eval_ready(c, "eincm_loss_grad")) return rc;
-    if (!theta || !p || !value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
-    if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
-    HIPCHK(c, hipSetDevice(c->device));
-    return evaluate(c, theta, h, w, p, value, grad, aux, false);
+    if (const int rc = eval_entry(c, "eincm_loss_grad", theta, h, w, p, value)) return rc;
+    return evaluate(c, theta, h, w, p, value, grad, aux);
 }
 
 int eincm_loss_grad_masked(eincm_ctx* c, const double* theta, int h, int w, const eincm_params* p, const uint8_t* active,
                            double* value, double* grad, eincm_aux* aux) {
-    if (!c) return EINCM_ERR_ARG;
-    if (const int rc = eval_ready(c, "eincm_loss_grad_masked")) return rc;
-    if (!theta || !p || !value) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    if (h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "theta shape (%d,%d,2) invalid", h, w);
-    if (p->method < 0 || p->method > EINCM_METHOD_CUBIC) return fail(c, EINCM_ERR_ARG, "method %d unknown", p->method);
-    HIPCHK(c, hipSetDevice(c->device));
-    return evaluate(c, theta, h, w, p, value, grad, aux, false, active);
+    if (const int rc = eval_entry(c, "eincm_loss_grad_masked", theta, h, w, p, value)) return rc;
+    return evaluate(c, theta, h, w, p, value, grad, aux, active);
 }
 
 int eincm_handover_loss_grad(eincm_ctx* c, const double* a, const double* prev_theta, const double* theta, int h, int w,
@@ -2383,7 +2383,7 @@ int eincm_handover_loss_grad(eincm_ctx* c, const double* a, const double* prev_t
         for (size_t i = 0; i < nth; ++i)   // losses.py:269
             tho[b * nth + i] = a[b] * prev_theta[b * nth + i] + (1.0 - a[b]) * theta[b * nth + i];
     if (dvalue_da) grad.resize(B * nth);
-    const int rc = evaluate(c, tho.data(), h, w, p, value, dvalue_da ? grad.data() : nullptr, nullptr, false);
+    const int rc = evaluate(c, tho.data(), h, w, p, value, dvalue_da ? grad.data() : nullptr, nullptr);
     if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
     if (dvalue_da) {
         for (size_t b = 0; b < B; ++b) {
@@ -2405,7 +2405,7 @@ int eincm_objectives(eincm_ctx* c, const double* Theta, eincm_objectives_out* ou
     p.alpha = 1.0; p.beta = 1.0; p.gamma = 0.0; p.delta = 0.0; p.cur_pyr_lvl = 0; p.method = EINCM_METHOD_BILINEAR;
     p.flags = EINCM_PF_FULL_AUX;
     std::vector<double> val((size_t)g.B);
-    const int rc = evaluate(c, Theta, g.H, g.W, &p, val.data(), nullptr, nullptr, false);
+    const int rc = evaluate(c, Theta, g.H, g.W, &p, val.data(), nullptr, nullptr);
     if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
     std::vector<double> tvp((size_t)g.B * g.ntiles * 3);
     HIPCHK(c, hipMemcpy(tvp.data(), c->d_tvparts, tvp.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -3206,7 +3206,7 @@ int eincm_set_objective_tiles(eincm_ctx* c, int tile_h, int tile_w) {
     if (!c) return EINCM_ERR_ARG;
     if (tile_h < 1 || tile_w < 1 || tile_h > c->H || tile_w > c->W)
         return fail(c, EINCM_ERR_ARG, "objective tile %dx%d outside 1x1 .. %dx%d (the sensor)", tile_h, tile_w, c->H, c->W);
-    if (c->pend.active && c->pend.launched) return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
+    if (c->fl.launched()) return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
     if (tile_h != c->obj_th || tile_w != c->obj_tw) { c->obj_th = tile_h; c->obj_tw = tile_w; c->objc_valid = false; }
     return EINCM_OK;
 }
@@ -3215,7 +3215,7 @@ int eincm_set_splat_window(eincm_ctx* c, int window_size) {
     if (!c) return EINCM_ERR_ARG;
     if (window_size < 1 || window_size > EINCM_SPLAT_WINDOW_MAX)
         return fail(c, EINCM_ERR_ARG, "splat window size %d outside 1..%d", window_size, EINCM_SPLAT_WINDOW_MAX);
-    if (c->pend.active && c->pend.launched) return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
+    if (c->fl.launched()) return fail(c, EINCM_ERR_STATE, "an asynchronous evaluation is in flight: call eincm_loss_grad_wait first");
     if (c->fp64 && window_size != 3)
         return fail(c, EINCM_ERR_UNSUPPORTED, "splat window size %d: fp64 mode (EINCM_CF_FP64) supports size 3 only", window_size);
     if (window_size == c->splat_size) return EINCM_OK;
@@ -3281,7 +3281,7 @@ int eincm_get_timings_total(eincm_ctx* c, eincm_timings* t, int64_t* n_evals, in
     if (!c || !t || !n_evals) return EINCM_ERR_ARG;
     if (!(c->cflags & (EINCM_CF_TIMING | EINCM_CF_TIMING_DOMINANT)))
         return fail(c, EINCM_ERR_STATE, "context was created without EINCM_CF_TIMING / EINCM_CF_TIMING_DOMINANT");
-    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
     const int rc = drain_event_ring(c, 0);
     if (rc) return rc;
     *t = c->sum_t; *n_evals = c->sum_n;
@@ -3311,7 +3311,7 @@ int eincm_get_launch_policy(eincm_ctx* c, double* out) {
     out[EINCM_LP_SEG_SPLAT_SHORT] = S.splat_short ? SEG_SHORT : 0; out[EINCM_LP_PITCH_POLICY] = S.pitch;
     out[EINCM_LP_SPAN_SPLAT] = c->splat.tspan; out[EINCM_LP_SPAN_GATHER] = c->gather.tspan; out[EINCM_LP_SPAN_GATHER_2DOF] = c->gather_2.tspan;
     const bool evaluated = c->policy_evaluated;         // (never on a float64 context)
-    const EvalPlan& P = c->pend.plan;
+    const EvalPlan& P = c->fl.plan;
     out[EINCM_LP_CAP_SPLAT] = evaluated ? P.wincap : 0; out[EINCM_LP_CAP_GATHER] = evaluated ? P.wincap_a : 0;
     out[EINCM_LP_CAP_GATHER_2DOF] = evaluated ? P.win_2.cap : 0;
     out[EINCM_LP_PITCH_ALIGNED] = evaluated ? ((P.pitch_aligned ? 1 : 0) | (P.win_2.pal ? 2 : 0)) : 0;
@@ -3322,7 +3322,7 @@ int eincm_get_launch_policy(eincm_ctx* c, double* out) {
 int eincm_set_timed_kernels(eincm_ctx* c, int splat, int gather) {
     if (!c) return EINCM_ERR_ARG;
     if (!(c->cflags & EINCM_CF_TIMING_DOMINANT)) return fail(c, EINCM_ERR_STATE, "context was created without EINCM_CF_TIMING_DOMINANT");
-    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
     c->time_splat = splat != 0; c->time_gather = gather != 0;
     return EINCM_OK;
 }
@@ -3330,7 +3330,7 @@ int eincm_set_timed_kernels(eincm_ctx* c, int splat, int gather) {
 int eincm_set_timing_period(eincm_ctx* c, int period) {
     if (!c) return EINCM_ERR_ARG;
     if (!(c->cflags & EINCM_CF_TIMING_DOMINANT)) return fail(c, EINCM_ERR_STATE, "context was created without EINCM_CF_TIMING_DOMINANT");
-    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
     if (period < 1) return fail(c, EINCM_ERR_ARG, "period %d", period);
     c->time_period = period; c->time_counter = 0;
     return EINCM_OK;
@@ -3340,7 +3340,7 @@ int eincm_get_timings(eincm_ctx* c, eincm_timings* t) {
     if (!c || !t) return EINCM_ERR_ARG;
     if (!(c->cflags & (EINCM_CF_TIMING | EINCM_CF_TIMING_DOMINANT)))
         return fail(c, EINCM_ERR_STATE, "context was created without EINCM_CF_TIMING / EINCM_CF_TIMING_DOMINANT");
-    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "an evaluation is in flight");
     const int rc = drain_event_ring(c, 0);
     if (rc) return rc;
     *t = c->last_t;
@@ -3353,7 +3353,7 @@ static int bfgs_ready(eincm_ctx* c, const char* who, bool need_begun) {
         return fail(c, EINCM_ERR_UNSUPPORTED, "%s is not supported in fp64 mode (EINCM_CF_FP64): the device-resident evaluation does not exist there", who);
     if (const int rc = eval_ready(c, who)) return rc;
     if (c->device_results) return fail(c, EINCM_ERR_STATE, "%s: eincm_set_device_results is on (the split finishing half owns the results)", who);
-    if (c->pend.active) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
     if (c->g.B > BFGS_MAX_B) return fail(c, EINCM_ERR_ARG, "%s: %d windows exceed EINCM_BFGS_MAX_WINDOWS = %d", who, c->g.B, BFGS_MAX_B);
     if (need_begun && (!c->bfgs.begun || c->bfgs.B != c->g.B))
         return fail(c, EINCM_ERR_STATE, "%s called before eincm_bfgs_begin (for the staged windows)", who);
@@ -3470,15 +3470,14 @@ int eincm_bfgs_eval(eincm_ctx* c, const eincm_params* p, const double* alpha, co
                        bfgs_alpha(c, m, alpha), (const double*)s.X, (const double*)s.P, s.Xt);
     HIPCHK(c, hipGetLastError());
     // the masked evaluation with theta = Xt in HBM; its gradient stays in the engine's block, k_bfgs_reduce moves the mask's rows to Gt
-    struct Reset { eincm_ctx* c; ~Reset() { c->theta_dev_in = nullptr; c->grad_dev_out = nullptr; c->vmax_hint = -1.0; } } reset{c};
-    c->theta_dev_in = s.Xt; c->grad_dev_out = nullptr; c->vmax_hint = std::isfinite(vmax) ? vmax : -1.0;
     std::vector<uint8_t> act((size_t)s.B);
     for (int b = 0; b < s.B; ++b) act[b] = (uint8_t)((m >> b) & 1ull);
-    int rc = eval_begin(c, nullptr, s.h, s.w, p, true, act.data());
+    int rc = eval_begin(c, nullptr, s.h, s.w, p, true, act.data(), DevIo{s.Xt, nullptr, std::isfinite(vmax) ? vmax : -1.0});
     if (!rc) rc = eval_end_launch(c);
-    if (!rc) rc = bfgs_launch_reduce(c, m, c->d_grad);
-    if (rc) { (void)hipStreamSynchronize(c->stream); c->pend.active = false; c->pend.launched = false; return rc; }
-    rc = eval_end_collect(c, value, nullptr, nullptr);             // the one synchronisation
+    if (rc) return rc;
+    FlightGuard guard(c);
+    if ((rc = bfgs_launch_reduce(c, m, c->d_grad))) return rc;
+    rc = guard.keep(eval_end_collect(c, value, nullptr, nullptr));             // the one synchronisation
     if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
     for (int b = 0; b < s.B; ++b) if ((m >> b) & 1ull) { dphi[b] = s.h_red.p[2 * b]; gmax[b] = s.h_red.p[2 * b + 1]; }
     return rc;

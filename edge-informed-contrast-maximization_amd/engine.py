@@ -482,6 +482,32 @@ class Engine:
             raise NonFiniteLoss(rc, msg)
         raise EincmError(rc, msg)
 
+    def _theta_batch(self, theta, what='theta'):
+        """theta (an ndarray or a torch tensor) as the batch (B,h,w,2); (h,w,2) stands for it when B == 1."""
+        th = theta[None] if theta.ndim == 3 else theta
+        if th.ndim != 4 or th.shape[0] != self.B or th.shape[3] != 2:
+            raise ValueError(f'{what} must be ({self.B},h,w,2), got {tuple(theta.shape)}')
+        return th
+
+    def _active_ptr(self, active):
+        """(mask array | None, its address | None) of an ``active`` argument; the array keeps the address alive."""
+        if active is None:
+            return None, None
+        act = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
+        if act.shape != (self.B,):
+            raise ValueError(f'active must be ({self.B},), got {act.shape}')
+        return act, act.ctypes.data
+
+    def _outputs(self, shape, want_grad, want_aux):
+        """Fresh (value (B,), grad of ``shape`` | None, aux block | None) for one evaluation call to fill."""
+        return (np.empty(self.B, dtype=np.float64), np.empty(shape, dtype=np.float64) if want_grad else None,
+                (L.Aux * self.B)() if want_aux else None)
+
+    def _collect(self, rc, value, grad, aux, allow_nonfinite):
+        """The tail of every evaluation call: the return code's verdict, the aux block as a list of dicts."""
+        self._check(rc, allow_nonfinite)
+        return value, grad, None if aux is None else [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux]
+
     # -- staging ----------------------------------------------------------------------------------
     def set_windows(self, windows, defer_constants=False):
         """windows: list of (xs, ys, ts, edges, edge_ts) tuples (the reference's datasample tuple).
@@ -522,11 +548,7 @@ class Engine:
     def loss_grad(self, theta, params, want_grad=True, want_aux=False, allow_nonfinite=True, active=None):
         """theta: (B,h,w,2) or (h,w,2) when B == 1.  Returns (value (B,), grad (B,h,w,2) | None, aux list | None).
         active: optional (B,) mask - only those windows are evaluated (the others: value NaN, gradient 0), at about their share of the cost."""
-        th = theta if isinstance(theta, np.ndarray) else np.asarray(theta, dtype=np.float64)
-        if th.ndim == 3:
-            th = th[None]
-        if th.ndim != 4 or th.shape[0] != self.B or th.shape[3] != 2:
-            raise ValueError(f'theta must be ({self.B},h,w,2), got {th.shape}')
+        th = self._theta_batch(theta if isinstance(theta, np.ndarray) else np.asarray(theta, dtype=np.float64))
         _, h, w, _ = th.shape
         # Staging buffers per theta shape with their addresses cached: `ndarray.ctypes.data` costs ~1 us per use, three of them per
         # call were 3 of the ~5 us this wrapper added to a 70 us evaluation.  The caller gets copies (a few hundred bytes at the
@@ -539,42 +561,29 @@ class Engine:
                 bufs = self._io[(h, w)] = (tb, vb, gb, tb.ctypes.data, vb.ctypes.data, gb.ctypes.data)
             tb, vb, gb, p_th, p_v, p_g = bufs
             np.copyto(tb, th)
+            aux = (L.Aux * self.B)() if want_aux else None
         else:
             th = np.ascontiguousarray(th, dtype=np.float64)
-            vb, gb = np.empty(self.B, dtype=np.float64), (np.empty_like(th) if want_grad else None)
+            vb, gb, aux = self._outputs(th.shape, want_grad, want_aux)
             p_th, p_v, p_g = th.ctypes.data, vb.ctypes.data, (gb.ctypes.data if want_grad else None)
-        aux = (L.Aux * self.B)() if want_aux else None
         if active is not None:
-            act = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
-            if act.shape != (self.B,):
-                raise ValueError(f'active must be ({self.B},), got {act.shape}')
-            rc = self._lib.eincm_loss_grad_masked(self._ctx, p_th, h, w, C.byref(params), act.ctypes.data, p_v, p_g if want_grad else None, aux)
+            act, p_act = self._active_ptr(active)
+            rc = self._lib.eincm_loss_grad_masked(self._ctx, p_th, h, w, C.byref(params), p_act, p_v, p_g if want_grad else None, aux)
         else:
             rc = self._lib.eincm_loss_grad(self._ctx, p_th, h, w, C.byref(params), p_v, p_g if want_grad else None, aux)
+        if not small:
+            return self._collect(rc, vb, gb, aux, allow_nonfinite)
         self._check(rc, allow_nonfinite)
-        value = vb.copy() if small else vb
-        grad = (gb.copy() if small else gb) if want_grad else None
-        auxl = None
-        if want_aux:
-            auxl = [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux]
-        return value, grad, auxl
+        return vb.copy(), gb.copy() if want_grad else None, [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux] if want_aux else None
 
     # -- asynchronous evaluation: enqueue now, collect later (several contexts in flight, see EngineGroup) ----
     def loss_grad_async(self, theta, params, want_grad=True, active=None):
         """Enqueue an evaluation and return at once (theta is copied before the call returns); ``active`` as in loss_grad."""
-        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64))
-        if th.ndim == 3:
-            th = th[None]
-        if th.ndim != 4 or th.shape[0] != self.B or th.shape[3] != 2:
-            raise ValueError(f'theta must be ({self.B},h,w,2), got {th.shape}')
-        act = None
-        if active is not None:
-            act = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
-            if act.shape != (self.B,):
-                raise ValueError(f'active must be ({self.B},), got {act.shape}')
+        th = self._theta_batch(np.ascontiguousarray(np.asarray(theta, dtype=np.float64)))
+        act, p_act = self._active_ptr(active)
         # (a refused launch - one already in flight - leaves self._async naming that one, so that it can still be collected)
         self._check(self._lib.eincm_loss_grad_masked_async(self._ctx, th.ctypes.data, th.shape[1], th.shape[2], C.byref(params),
-                                                           act.ctypes.data if act is not None else None, 1 if want_grad else 0))
+                                                           p_act, 1 if want_grad else 0))
         self._async = (th.shape, bool(want_grad))
 
     def loss_grad_wait(self, want_aux=False, allow_nonfinite=True):
@@ -582,13 +591,9 @@ class Engine:
             raise EincmError(L.ERR_STATE, 'eincm_loss_grad_wait without eincm_loss_grad_async')
         shape, want_grad = self._async
         self._async = None
-        value = np.empty(self.B, dtype=np.float64)
-        grad = np.empty(shape, dtype=np.float64) if want_grad else None
-        aux = (L.Aux * self.B)() if want_aux else None
+        value, grad, aux = self._outputs(shape, want_grad, want_aux)
         rc = self._lib.eincm_loss_grad_wait(self._ctx, value.ctypes.data, grad.ctypes.data if want_grad else None, aux)
-        self._check(rc, allow_nonfinite)
-        auxl = [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux] if want_aux else None
-        return value, grad, auxl
+        return self._collect(rc, value, grad, aux, allow_nonfinite)
 
     # -- the two halves of an evaluation (event-sharded mode) ------------------------------------------
     def forward_iwe(self, theta, params, want_grad=True):
@@ -597,22 +602,14 @@ class Engine:
             rc = self._lib.eincm_forward_iwe(self._ctx, None, 1, 1, C.byref(make_params(1, 1, 0, 0, 1)), 0)
             self._check(rc)
             return None
-        th = np.ascontiguousarray(np.asarray(theta, dtype=np.float64))
-        if th.ndim == 3:
-            th = th[None]
-        if th.ndim != 4 or th.shape[0] != self.B or th.shape[3] != 2:
-            raise ValueError(f'theta must be ({self.B},h,w,2), got {th.shape}')
+        th = self._theta_batch(np.ascontiguousarray(np.asarray(theta, dtype=np.float64)))
         self._check(self._lib.eincm_forward_iwe(self._ctx, _dp(th), th.shape[1], th.shape[2], C.byref(params), 1 if want_grad else 0))
         return th.shape
 
     def finish_loss_grad(self, theta_shape, want_grad=True, want_aux=False, allow_nonfinite=True):
-        value = np.empty(self.B, dtype=np.float64)
-        grad = np.empty(theta_shape, dtype=np.float64) if want_grad else None
-        aux = (L.Aux * self.B)() if want_aux else None
+        value, grad, aux = self._outputs(theta_shape, want_grad, want_aux)
         rc = self._lib.eincm_finish_loss_grad(self._ctx, _dp(value), _dp(grad) if want_grad else None, aux)
-        self._check(rc, allow_nonfinite)
-        auxl = [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux] if want_aux else None
-        return value, grad, auxl
+        return self._collect(rc, value, grad, aux, allow_nonfinite)
 
     # -- the finishing half with the results kept in HBM (event-sharded mode over a GPU collective) ------------------
     def set_device_results(self, on=True):
@@ -626,13 +623,9 @@ class Engine:
         return self._device_view(self._lib.eincm_grad_device_ptr, '<f8', 8, tuple(theta_shape))
 
     def finish_collect(self, theta_shape, want_grad=True, want_aux=False, allow_nonfinite=True):
-        value = np.empty(self.B, dtype=np.float64)
-        grad = np.empty(theta_shape, dtype=np.float64) if want_grad else None
-        aux = (L.Aux * self.B)() if want_aux else None
+        value, grad, aux = self._outputs(theta_shape, want_grad, want_aux)
         rc = self._lib.eincm_finish_collect(self._ctx, _dp(value), _dp(grad) if want_grad else None, aux)
-        self._check(rc, allow_nonfinite)
-        auxl = [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux] if want_aux else None
-        return value, grad, auxl
+        return self._collect(rc, value, grad, aux, allow_nonfinite)
 
     # -- theta and gradient resident in HBM (an optimiser that lives on the GPU) -------------------------------------------
     def loss_grad_device(self, theta, params, theta_abs_max=None, want_grad=True, want_aux=False, allow_nonfinite=True):
@@ -642,33 +635,16 @@ class Engine:
         import torch
         if not (isinstance(theta, torch.Tensor) and theta.is_cuda and theta.dtype == torch.float64):
             raise TypeError('theta must be a float64 CUDA tensor')
-        th = theta.contiguous()
-        if th.dim() == 3:
-            th = th[None]
-        if th.dim() != 4 or th.shape[0] != self.B or th.shape[3] != 2:
-            raise ValueError(f'theta must be ({self.B},h,w,2), got {tuple(theta.shape)}')
+        th = self._theta_batch(theta.contiguous())
         grad = torch.empty_like(th) if want_grad else None
         torch.cuda.current_stream(th.device).synchronize()              # the engine's kernels run on its own stream
-        value = np.empty(self.B, dtype=np.float64)
-        aux = (L.Aux * self.B)() if want_aux else None
+        value, _, aux = self._outputs(None, False, want_aux)
         rc = self._lib.eincm_loss_grad_device(self._ctx, C.c_void_p(th.data_ptr()), int(th.shape[1]), int(th.shape[2]), C.byref(params),
                                               -1.0 if theta_abs_max is None else float(theta_abs_max), _dp(value),
                                               C.c_void_p(grad.data_ptr()) if want_grad else None, aux)
-        self._check(rc, allow_nonfinite)
-        if want_grad and theta.dim() == 3:
-            grad = grad[0]
-        auxl = [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux] if want_aux else None
-        return value, grad, auxl
+        return self._collect(rc, value, grad[0] if want_grad and theta.dim() == 3 else grad, aux, allow_nonfinite)
 
     # -- BFGS with its state in HBM: the host sees scalars, the vectors and the inverse Hessian stay on the GPU ----
-    def _bfgs_mask(self, active):
-        if active is None:
-            return None, None
-        act = np.ascontiguousarray(np.asarray(active).astype(np.uint8))
-        if act.shape != (self.B,):
-            raise ValueError(f'active must be ({self.B},), got {act.shape}')
-        return act, act.ctypes.data
-
     def _bfgs_alpha(self, alpha):
         al = np.ascontiguousarray(np.asarray(alpha, dtype=np.float64))
         if al.shape != (self.B,):
@@ -680,7 +656,7 @@ class Engine:
         x = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
         if x.ndim != 4 or x.shape[0] != self.B or x.shape[3] != 2:
             raise ValueError(f'x0 must be ({self.B},h,w,2), got {x.shape}')
-        act, p_act = self._bfgs_mask(active)
+        act, p_act = self._active_ptr(active)
         self._check(self._lib.eincm_bfgs_begin(self._ctx, x.ctypes.data, x.shape[1], x.shape[2], p_act))
         self._bfgs_shape = x.shape
         out = np.empty(self.B), np.empty(self.B), np.empty(self.B)
@@ -690,7 +666,7 @@ class Engine:
         """One evaluation at X + alpha[b] P per window of ``active``: (value, phi' = grad . P, max|grad|), each (B,); the trial point
         and its gradient stay in HBM.  Entries of the other windows are meaningless."""
         al = self._bfgs_alpha(alpha)
-        act, p_act = self._bfgs_mask(active)
+        act, p_act = self._active_ptr(active)
         v, d, g, p_v, p_d, p_g = self._bfgs_out
         rc = self._lib.eincm_bfgs_eval(self._ctx, C.byref(params), al.ctypes.data, p_act, p_v, p_d, p_g)
         self._check(rc, allow_nonfinite)
@@ -699,14 +675,14 @@ class Engine:
     def bfgs_trial(self, alpha, active=None):
         """Xt = X + alpha[b] P alone (see bfgs_trial_tensors)."""
         al = self._bfgs_alpha(alpha)
-        act, p_act = self._bfgs_mask(active)
+        act, p_act = self._active_ptr(active)
         self._check(self._lib.eincm_bfgs_trial(self._ctx, al.ctypes.data, p_act))
 
     def bfgs_reduce(self, active=None):
         """(phi', max|grad|) of the gradient the caller wrote into the trial gradient's view (torch work on it is synchronised first)."""
         import torch
         torch.cuda.current_stream(torch.device('cuda', torch.cuda.current_device())).synchronize()
-        act, p_act = self._bfgs_mask(active)
+        act, p_act = self._active_ptr(active)
         _, d, g, _, p_d, p_g = self._bfgs_out
         self._check(self._lib.eincm_bfgs_reduce(self._ctx, p_act, p_d, p_g))
         return d.copy(), g.copy()
