@@ -32,6 +32,8 @@ BFGS_MAX_N, BFGS_MAX_WINDOWS = 1024, 64                              # EINCM_BFG
 BFGS_SKIP, BFGS_UPDATE, BFGS_MOVE, BFGS_INIT = 0, 1, 2, 3            # eincm_bfgs_accept modes (EINCM_BFGS_*)
 BFGS_S_DPHI0, BFGS_S_GMAX, BFGS_S_PNORM, BFGS_S_XMAX, BFGS_S_PMAX, BFGS_S_GNORM, BFGS_S_YS, BFGS_S_YHY = range(8)   # EINCM_BFGS_S_*
 BFGS_NS = 8
+LBFGS_MAX_HISTORY = 16                                               # EINCM_LBFGS_MAX_HISTORY
+LBFGS_SCALES = {'identity': 0, 'last_pair': 1}                       # EINCM_LBFGS_SCALE_*
 
 
 class Params(C.Structure):
@@ -173,6 +175,9 @@ SIGNATURES = [
                                         C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     ('eincm_bfgs_accept', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('eincm_bfgs_fetch', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # ... in the limited-memory form
+    ('eincm_lbfgs_begin', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    ('eincm_lbfgs_history_ptrs', C.c_int, [_P] + [C.POINTER(C.c_void_p)] * 6 + [C.POINTER(C.c_int)]),
 ]
 
 _lib = None

@@ -45,7 +45,7 @@ except ImportError:                                  # without it the update sta
     threadpool_limits = None
 
 from . import _lib as L
-from .engine import Engine, check_precision, check_window_size, make_params
+from .engine import Engine, check_history, check_initial_scale, check_precision, check_window_size, make_params
 from .solver import ScipyMinimizeInfo, EmptyCallback, rescale_theta, _canon
 
 _BFGS_C1, _BFGS_C2, _BFGS_XTOL, _BFGS_AMIN, _BFGS_AMAX, _LS_MAXITER = 1e-4, 0.9, 1e-14, 1e-100, 1e100, 100
@@ -563,6 +563,9 @@ class NumpyBFGSState:
         self.fun_batch = fun_batch
         self.windows = []
 
+    def _new_window(self, x0):
+        return _HostWindow(x0, 'tri' if threadpool_limits is not None else 'rank2')
+
     def begin(self, x0, active=None):
         x0 = np.array(x0, dtype=np.float64)
         self.B, self.n = x0.shape
@@ -572,7 +575,7 @@ class NumpyBFGSState:
             self.xt = x0.copy()                          # the batch's trial points as fun_batch takes them
             self.scal = np.zeros((self.B, L.BFGS_NS))
         for b in np.flatnonzero(act):
-            self.windows[b] = _HostWindow(x0[b], 'tri' if threadpool_limits is not None else 'rank2')
+            self.windows[b] = self._new_window(x0[b])
 
     def _rows(self, name):
         return np.stack([getattr(w, name) for w in self.windows])
@@ -636,6 +639,159 @@ class DeviceBFGSState:
     def fetch(self, want_hess_inv=False):
         x, g, H = self.engine.bfgs_fetch(want_hess_inv)
         return x.reshape(self.B, self.n), g.reshape(self.B, self.n), H
+
+
+# ---- the limited-memory form of the state: a ring of pairs (s, y) per window instead of the matrix ------------------
+LBFGS_EPS = 2.220446049250313e-16          # a pair is kept iff y.s > LBFGS_EPS * y.y (the skip rule of SciPy's L-BFGS-B)
+HESSIANS = ('dense', 'limited', 'auto')
+
+
+def check_hessian(hessian):
+    """'dense', 'limited' or 'auto'; anything else is a ValueError."""
+    if not isinstance(hessian, str) or hessian not in HESSIANS:
+        raise ValueError(f"hessian {hessian!r}: 'dense', 'limited' or 'auto'")
+    return hessian
+
+
+def lbfgs_basis(head, count, m):
+    """(ring slots of the pairs, oldest first; indices into D and delta of the basis [s_0 .. s_{c-1}, y_0 .. y_{c-1}, g] in its order):
+    s of slot k sits at k, y of slot k at m + k, g at 2 m."""
+    slots = [(int(head) + i) % m for i in range(int(count))]
+    return slots, slots + [m + k for k in slots] + [2 * m]
+
+
+def lbfgs_delta(D, head, count, m, initial_scale):
+    """The two-loop recursion in its dot-matrix form: D (2m+1, 2m+1) with D[u, v] = b_u . b_v -> the coefficients delta (2m+1) of
+    p = sum_j delta_j b_j.  Plain float arithmetic, one operation at a time: every sum runs over the basis in its order, one rounded
+    product added after the other, exactly what the GPU's coefficient kernel does (its delta equals this bit for bit on the same D)."""
+    slots, order = lbfgs_basis(head, count, m)
+    c = len(slots)
+    Dl = np.asarray(D, dtype=np.float64)[np.ix_(order, order)].tolist()      # the basis' block, in basis order: s at i, y at c + i, g at 2c
+    d = [0.0] * (2 * c + 1)
+    d[2 * c] = -1.0
+    a = [0.0] * c
+    for i in reversed(range(c)):
+        acc = 0.0
+        for u in range(2 * c + 1):
+            acc += d[u] * Dl[u][i]
+        a[i] = acc / Dl[i][c + i]
+        d[c + i] -= a[i]
+    if initial_scale == 'last_pair' and c:
+        gamma = Dl[c - 1][2 * c - 1] / Dl[2 * c - 1][2 * c - 1]
+        for u in range(2 * c + 1):
+            d[u] *= gamma
+    for i in range(c):
+        acc = 0.0
+        for u in range(2 * c + 1):
+            acc += d[u] * Dl[u][c + i]
+        beta = acc / Dl[i][c + i]
+        d[i] += a[i] - beta
+    delta = np.zeros(2 * m + 1)
+    delta[order] = d
+    return delta
+
+
+def lbfgs_combine(delta, S, Y, g, head, count, m):
+    """p = sum_j delta_j b_j per element over the basis in its order: the first product as it is, every later one rounded, then added."""
+    slots, _ = lbfgs_basis(head, count, m)
+    terms = [delta[k] * S[k] for k in slots] + [delta[m + k] * Y[k] for k in slots] + [delta[2 * m] * np.asarray(g)]
+    p = terms[0]
+    for v in terms[1:]:
+        p = p + v
+    return p
+
+
+class _LimitedWindow(_HostWindow):
+    """One window's vectors on the host with the inverse Hessian kept as at most m pairs: the rings S, Y (m, n) by ring slot, ``head``
+    (the oldest pair's slot), ``count``, the dot matrix D and the coefficients delta (``lbfgs_delta``)."""
+
+    def __init__(self, x0, history, initial_scale):
+        super().__init__(x0, None)
+        self.form, self.m, self.initial_scale = 'limited', int(history), initial_scale
+        m = self.m
+        self.S, self.Y = np.zeros((m, self.n)), np.zeros((m, self.n))
+        self.D, self.delta = np.zeros((2 * m + 1, 2 * m + 1)), np.zeros(2 * m + 1)
+        self.head = self.count = 0
+
+    def _vector(self, u):
+        m = self.m
+        return self.g if u == 2 * m else self.Y[u - m] if u >= m else self.S[u]
+
+    def _row(self, u):
+        """Row (and column) u of D as direct dot products against the whole basis."""
+        v = self._vector(u)
+        for w in lbfgs_basis(self.head, self.count, self.m)[1]:
+            self.D[u, w] = self.D[w, u] = float(np.dot(v, self._vector(w)))
+
+    def accept(self, alpha, mode, every_scalar=True):
+        """_lib.BFGS_UPDATE (s = alpha p with the product rounded, y = gt - g; the pair enters the ring iff y.s > LBFGS_EPS y.y, the
+        oldest one leaving a full ring; x <- xt, g <- gt; the rows of D of the new s, y and g; delta; p) / MOVE (x <- xt, g <- gt) / INIT
+        (MOVE, the ring emptied, p = -g) -> the _lib.BFGS_NS scalars of the new iterate; slot BFGS_S_YHY holds y . y."""
+        m = self.m
+        ys = yy = 0.0
+        kept = None
+        if mode == L.BFGS_UPDATE:
+            sk, yk = alpha * self.p, self.gt - self.g
+            ys, yy = float(np.dot(yk, sk)), float(np.dot(yk, yk))
+            if ys > LBFGS_EPS * yy:
+                kept = (self.head + self.count) % m
+                if self.count == m:
+                    self.head = (self.head + 1) % m
+                else:
+                    self.count += 1
+                self.S[kept], self.Y[kept] = sk, yk
+        elif mode == L.BFGS_INIT:
+            self.head = self.count = 0
+            self.D[:] = 0.0
+        self.x, self.g = self.xt, self.gt
+        if mode != L.BFGS_MOVE:
+            if kept is not None:
+                self._row(kept)
+                self._row(m + kept)
+            self._row(2 * m)
+            self.delta = lbfgs_delta(self.D, self.head, self.count, m, self.initial_scale)
+            self.p = lbfgs_combine(self.delta, self.S, self.Y, self.g, self.head, self.count, m)
+        g, p, x = self.g, self.p, self.x
+        return (float(np.dot(g, p)), _max_abs(g), np.linalg.norm(p), _max_abs(x), _max_abs(p), np.linalg.norm(g), ys, yy)
+
+    def full_hess_inv(self):
+        return None
+
+
+class NumpyLBFGSState(NumpyBFGSState):
+    """``NumpyBFGSState`` with the inverse Hessian of every window kept as a ring of at most ``history`` pairs (s, y): the written-down
+    contract of ``DeviceLBFGSState`` (csrc/eincm_lbfgs.hip.h), op for op what the GPU does up to the association of the dot products.
+    ``initial_scale``: 'last_pair' starts the recursion from (y.s / y.y) I of the newest pair, 'identity' from I.  There is no inverse
+    Hessian to fetch: ``fetch`` returns None for it."""
+
+    def __init__(self, fun_batch, history=10, initial_scale='last_pair'):
+        super().__init__(fun_batch)
+        self.history, self.initial_scale = check_history(history, None), check_initial_scale(initial_scale)      # (no bound on the host)
+
+    def _new_window(self, x0):
+        return _LimitedWindow(x0, self.history, self.initial_scale)
+
+    def full_hess_inv(self, b):
+        return None
+
+    def fetch(self, want_hess_inv=False):
+        return self.x, self.g, None
+
+
+class DeviceLBFGSState(DeviceBFGSState):
+    """``DeviceBFGSState`` in the limited form (Engine.lbfgs_begin): any theta shape, the dense one included."""
+
+    def __init__(self, engine, shape, params, history=10, initial_scale='last_pair'):
+        super().__init__(engine, shape, params)
+        self.history, self.initial_scale = check_history(history), check_initial_scale(initial_scale)
+
+    def begin(self, x0, active=None):
+        x0 = np.asarray(x0, dtype=np.float64)
+        self.B, self.n = x0.shape
+        self.engine.lbfgs_begin(x0.reshape((self.B,) + self.shape), active, self.history, self.initial_scale)
+
+    def fetch(self, want_hess_inv=False):
+        return super().fetch(False)
 
 
 class DeviceLockstepBFGS:
@@ -715,6 +871,47 @@ class DeviceLockstepBFGS:
         return out
 
 
+def minimize_thetas(engine, theta0, params, maxiter, gtol, hessian='auto', history=10, bfgs_state='device', callbacks=None, active=None,
+                    initial_scale='last_pair', wolfe2_fallback=True, callback_needs_x=None, fun_batch=None, pipeline=None, stats=None):
+    """One level of B lockstep BFGS minimisations of the engine's objective over thetas of any shape, the dense one included.
+
+    theta0: (B, h, w, 2).  ``hessian``: 'dense' keeps the n x n inverse Hessian (the device form refuses more than EINCM_BFGS_MAX_N
+    unknowns), 'limited' a ring of ``history`` pairs above _EXACT_UPDATE_MAX_N unknowns, 'auto' the matrix up to EINCM_BFGS_MAX_N unknowns
+    and the ring above.  ``bfgs_state``: 'device' keeps the vectors in HBM above _EXACT_UPDATE_MAX_N unknowns (DeviceBFGSState /
+    DeviceLBFGSState), 'host' in numpy over ``engine.loss_grad`` (LockstepBFGS / NumpyLBFGSState).  ``callbacks[b]`` gets
+    OptimizeResult(x (n,), fun) per iteration (x=None where ``callback_needs_x[b]`` is false, device forms only).  ``fun_batch`` /
+    ``pipeline`` replace the host forms' evaluation (the multi-context solver's).  ``stats``: a dict whose 'n_batch_evals' and
+    'n_window_evals' are advanced.  Returns a list of scipy OptimizeResult (None for inactive windows), x flat."""
+    check_hessian(hessian)
+    check_bfgs_state(bfgs_state)
+    history, initial_scale = check_history(history, L.LBFGS_MAX_HISTORY if bfgs_state == 'device' else None), check_initial_scale(initial_scale)
+    theta0 = np.asarray(theta0, dtype=np.float64)
+    if theta0.ndim != 4 or theta0.shape[3] != 2:
+        raise ValueError(f'theta0 must be (B,h,w,2), got {theta0.shape}')
+    B, shape = theta0.shape[0], theta0.shape[1:]
+    x = theta0.reshape(B, -1)
+    n = x.shape[1]
+    limited = n > (_EXACT_UPDATE_MAX_N if hessian == 'limited' else L.BFGS_MAX_N if hessian == 'auto' else n)
+    if fun_batch is None:
+        def fun_batch(X, mask):
+            v, g, _ = engine.loss_grad(X.reshape((B,) + shape), params, active=mask)
+            return v, g.reshape(B, -1)
+    if bfgs_state == 'device' and n > _EXACT_UPDATE_MAX_N:          # below: the host's bit-exact SciPy update
+        state = DeviceLBFGSState(engine, shape, params, history, initial_scale) if limited else DeviceBFGSState(engine, shape, params)
+        drv = DeviceLockstepBFGS(state, x, maxiter, gtol, callbacks=callbacks, callback_needs_x=callback_needs_x, active=active,
+                                 wolfe2_fallback=wolfe2_fallback, want_hess_inv=False)      # (H stays in HBM: hess_inv is None)
+    elif limited:
+        drv = DeviceLockstepBFGS(NumpyLBFGSState(fun_batch, history, initial_scale), x, maxiter, gtol, callbacks=callbacks, active=active,
+                                 wolfe2_fallback=wolfe2_fallback, want_hess_inv=False)
+    else:
+        drv = LockstepBFGS(fun_batch, x, maxiter, gtol, callbacks=callbacks, active=active, wolfe2_fallback=wolfe2_fallback, **(pipeline or {}))
+    res = drv.run()
+    if stats is not None:
+        stats['n_batch_evals'] = stats.get('n_batch_evals', 0) + drv.n_batch_evals
+        stats['n_window_evals'] = stats.get('n_window_evals', 0) + drv.n_window_evals
+    return res
+
+
 def _info(res):
     return ScipyMinimizeInfo(fun_val=float(res.fun), success=bool(res.success), status=int(res.status), iter_num=int(res.nit),
                              hess_inv=getattr(res, 'hess_inv', None), num_fun_eval=int(res.nfev), num_jac_eval=int(res.njev),
@@ -734,14 +931,20 @@ class BatchedMultipleLevelEINCMSolver:
     def __init__(self, n_windows, sensor_size, n_pyr_lvls, theta_opt_maxiters, loss_kwargs, theta_opt_solver_params,
                  handover_opt_maxiters=None, handover_opt_solver_params=None, handover_settings=None,
                  pyramid_downscale_method='bilinear', pyramid_upscale_method='repeat', pyramid_bases=None, device=0,
-                 theta_solver_callbacks=None, n_groups=1, bfgs_state='host'):
+                 theta_solver_callbacks=None, n_groups=1, bfgs_state='host', hessian='dense', history=10, initial_scale='last_pair'):
         """n_groups > 1: the windows are split over that many engine contexts (HIP streams) and the lockstep is pipelined - while the
         host advances one group's line searches the other groups' evaluations run (LockstepBFGS, pipelined form).
         bfgs_state: 'host' (default) keeps x, the gradient and the inverse Hessian of every window in numpy; 'device' keeps them in HBM
         at the levels with more than 64 unknowns (8x8 and finer: DeviceLockstepBFGS on DeviceBFGSState), where only scalars cross PCIe
         per evaluation; the inverse Hessian of those levels is not downloaded (ScipyMinimizeInfo.hess_inv is None; Engine.bfgs_fetch
-        hands it out).  'device' needs one context (n_groups=1) and the fp32 engine."""
+        hands it out).  'device' needs one context (n_groups=1) and the fp32 engine.
+        hessian: 'dense' (default) keeps the n x n inverse Hessian at every level, so bfgs_state='device' stops at EINCM_BFGS_MAX_N
+        unknowns; 'limited' keeps the newest ``history`` pairs (s, y) instead at every level above 64 unknowns (NumpyLBFGSState /
+        DeviceLBFGSState; ``initial_scale``: 'last_pair' or 'identity'), which has no bound on the theta shape; 'auto' is dense up to
+        EINCM_BFGS_MAX_N unknowns and limited above.  It is the same BFGS machine either way (theta_opt.method stays 'BFGS')."""
         check_bfgs_state(bfgs_state)
+        self.hessian, self.initial_scale = check_hessian(hessian), check_initial_scale(initial_scale)
+        self.history = check_history(history, L.LBFGS_MAX_HISTORY if bfgs_state == 'device' else None)
         if bfgs_state == 'device' and int(n_groups) > 1:
             raise ValueError("bfgs_state='device' runs on one engine context: n_groups must be 1 (a pipelined device form does not exist)")
         if bfgs_state == 'device' and dict(loss_kwargs).get('precision', 'fp32') == 'fp64':
@@ -850,6 +1053,16 @@ class BatchedMultipleLevelEINCMSolver:
         active = np.ones(self.B, bool)
         states = [None] * self.B
         on_device = self.bfgs_state == 'device' and x.shape[1] > _EXACT_UPDATE_MAX_N      # below: the host's bit-exact SciPy update
+        if self.n_groups > 1:
+            def fun_batch_groups(X, mask):              # (the limited host form over several contexts: every group launched, then collected)
+                for gi in range(self.n_groups):
+                    launch(gi, X, mask)
+                vg = [collect(gi) for gi in range(self.n_groups)]
+                v, g = np.empty(self.B), np.empty((self.B, X.shape[1]))
+                for ix, (vi, gi_) in zip(self.groups, vg):
+                    v[ix], g[ix] = vi, gi_
+                return v, g
+        stats = {}
         for attempt in range(1 + extra):
             for b in range(self.B):
                 if active[b]:
@@ -858,16 +1071,16 @@ class BatchedMultipleLevelEINCMSolver:
             cbs = [(lambda r, cb=self.callbacks[b], sh=shape: cb(spo.OptimizeResult(x=np.asarray(r.x).reshape(sh), fun=r.fun)))
                    for b in range(self.B)]
             wolfe2 = self.theta_opt_solver_params.get('wolfe2_fallback', True)
+            needs_x = None
             if on_device:      # a retry begins again from the last iterate with H = I, as a new LockstepBFGS does
                 # (an EmptyCallback counts iterations and never looks at x: no download for it)
                 plain = [type(self.callbacks[b]) is EmptyCallback for b in range(self.B)]
-                drv = DeviceLockstepBFGS(DeviceBFGSState(self.engine, shape, p), x, self.theta_opt_maxiters[key], gtol, callbacks=[
-                    (self.callbacks[b] if plain[b] else cbs[b]) for b in range(self.B)], callback_needs_x=[not q for q in plain],
-                    active=active, wolfe2_fallback=wolfe2, want_hess_inv=False)      # (H stays in HBM: ScipyMinimizeInfo.hess_inv is None)
-            else:
-                drv = LockstepBFGS(fun_batch, x, self.theta_opt_maxiters[key], gtol, callbacks=cbs, active=active, wolfe2_fallback=wolfe2, **pipe)
-            res = drv.run()
-            self.n_batch_evals += drv.n_batch_evals; self.n_window_evals += drv.n_window_evals
+                cbs = [(self.callbacks[b] if plain[b] else cbs[b]) for b in range(self.B)]
+                needs_x = [not q for q in plain]
+            res = minimize_thetas(self.engine, x.reshape((self.B,) + shape), p, self.theta_opt_maxiters[key], gtol, hessian=self.hessian,
+                                  history=self.history, bfgs_state=self.bfgs_state, callbacks=cbs, active=active,
+                                  initial_scale=self.initial_scale, wolfe2_fallback=wolfe2, callback_needs_x=needs_x,
+                                  fun_batch=fun_batch_groups if self.n_groups > 1 else fun_batch, pipeline=pipe, stats=stats)
             for b in range(self.B):
                 if active[b]:
                     x[b], states[b] = res[b].x, _info(res[b])
@@ -875,6 +1088,7 @@ class BatchedMultipleLevelEINCMSolver:
             active = np.array([active[b] and (not states[b].success) and states[b].iter_num > 0 for b in range(self.B)])
             if not active.any():
                 break
+        self.n_batch_evals += stats['n_batch_evals']; self.n_window_evals += stats['n_window_evals']
         return [x[b].reshape(shape) for b in range(self.B)], states
 
     # -- handover (solver.py:302-347) ----------------------------------------------------------------------------------------

@@ -31,6 +31,7 @@
 #include "eincm_dsec.hip.h"
 #include "eincm_floweval.hip.h"
 #include "eincm_bfgs.hip.h"
+#include "eincm_lbfgs.hip.h"
 
 using namespace eincm;
 
@@ -399,6 +400,24 @@ struct eincm_ctx {
         Grow<double> H;                      // (B, n, n)
         Grow<double, true> h_scal;           // pinned (maxB, BFGS_NS): k_bfgs_scalars writes it
         Grow<double, true> h_red;            // pinned (maxB, 2): k_bfgs_reduce writes it
+        // the limited-memory form (eincm_lbfgs.hip.h, eincm_lbfgs_begin): no H; S and Y above are the staging rows of the newest pair
+        int m = 0;                           // pairs kept per window; 0: the dense form
+        int scale = 0;                       // EINCM_LBFGS_SCALE_*
+        Grow<double> hist;                   // the rings S | Y, each (B, m, n) by ring slot
+        Grow<double> dmat;                   // D (B, 2m+1, 2m+1) | delta (B, 2m+1) | y.s, y.y (B, 2)
+        Grow<int> ring;                      // head (B) | count (B) | the last accept kept its pair (B)
+        Grow<double> part;                   // per-chunk partials: dots (B, chunks, 6m+6) | direction (B, chunks, 6) | reduce (B, chunks, 2)
+        double* lS() const { return hist.p; }
+        double* lY() const { return hist.p + (size_t)B * m * n; }
+        double* lD() const { return dmat.p; }
+        double* ldelta() const { return dmat.p + (size_t)B * (2 * m + 1) * (2 * m + 1); }
+        double* lysyy() const { return ldelta() + (size_t)B * (2 * m + 1); }
+        int* head() const { return ring.p; }
+        int* count() const { return ring.p + B; }
+        int* stored() const { return ring.p + 2 * B; }
+        double* part_dots() const { return part.p; }
+        double* part_dir() const { return part.p + (size_t)B * lbfgs_chunks(n) * lbfgs_nq(m); }
+        double* part_red() const { return part_dir() + (size_t)B * lbfgs_chunks(n) * LBFGS_NP; }
     } bfgs;
 };
 
@@ -3374,18 +3393,28 @@ static BfgsAlpha bfgs_alpha(const eincm_ctx* c, unsigned long long m, const doub
 
 static int bfgs_launch_reduce(eincm_ctx* c, unsigned long long m, const double* gsrc) {
     auto& s = c->bfgs;
+    if (s.m) {          // the limited form has no bound on n: per-chunk partials, then one wave per window in chunk order
+        const int chunks = lbfgs_chunks(s.n);
+        hipLaunchKernelGGL(k_lbfgs_reduce, dim3((unsigned)chunks, (unsigned)s.B), dim3(LBFGS_NT), 0, c->stream, s.n, m, gsrc, s.Gt,
+                           (const double*)s.P, s.part_red());
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_lbfgs_reduce_fin, dim3((unsigned)s.B), dim3(64), 0, c->stream, chunks, m, (const double*)s.part_red(), s.h_red.p);
+        HIPCHK(c, hipGetLastError());
+        return EINCM_OK;
+    }
     hipLaunchKernelGGL(k_bfgs_reduce, dim3((unsigned)s.B), dim3(BFGS_NT), 0, c->stream, s.n, m, gsrc, s.Gt, (const double*)s.P, s.h_red.p);
     HIPCHK(c, hipGetLastError());
     return EINCM_OK;
 }
 
-int eincm_bfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const uint8_t* active) {
-    if (!c) return EINCM_ERR_ARG;
-    if (const int rc = bfgs_ready(c, "eincm_bfgs_begin", false)) return rc;
-    if (!x0_host || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_begin: bad argument");
+// Both forms' begin: history = 0 is the dense form (H = I), history = m > 0 the limited one (an empty ring of m slots)
+static int bfgs_begin_form(eincm_ctx* c, const char* who, const double* x0_host, int h, int w, const uint8_t* active, int history, int scale) {
+    if (const int rc = bfgs_ready(c, who, false)) return rc;
+    if (!x0_host || h < 1 || w < 1) return fail(c, EINCM_ERR_ARG, "%s: bad argument", who);
     const int64_t n64 = (int64_t)2 * h * w;
-    if (n64 > BFGS_MAX_N)
+    if (!history && n64 > BFGS_MAX_N)
         return fail(c, EINCM_ERR_ARG, "eincm_bfgs_begin: theta (%d,%d,2) has %lld unknowns, more than EINCM_BFGS_MAX_N = %d", h, w, (long long)n64, BFGS_MAX_N);
+    if (n64 > (int64_t)1 << 30) return fail(c, EINCM_ERR_ARG, "%s: theta (%d,%d,2) has %lld unknowns, more than 2^30", who, h, w, (long long)n64);
     HIPCHK(c, hipSetDevice(c->device));
     auto& s = c->bfgs;
     const int n = (int)n64, B = c->g.B;
@@ -3393,19 +3422,32 @@ int eincm_bfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const ui
     HIPCHK(c, ensure(c, s.h_scal, (size_t)c->maxB * BFGS_NS, true));
     HIPCHK(c, ensure(c, s.h_red, (size_t)c->maxB * 2, true));
     const size_t need_vec = (size_t)B * n, need_H = need_vec * n;
-    const bool reshaped = n != s.n || B != s.B;
+    const bool reshaped = n != s.n || B != s.B || history != s.m;
     HIPCHK(c, ensure(c, s.vec, 8 * need_vec));
-    HIPCHK(c, ensure(c, s.H, need_H));
     double** v[8] = {&s.X, &s.G, &s.P, &s.Xt, &s.Gt, &s.S, &s.Y, &s.Hy};
     for (int k = 0; k < 8; ++k) *v[k] = s.vec.p + (size_t)k * (s.vec.n / 8);
+    const int nd = 2 * history + 1, chunks = lbfgs_chunks(n);
+    if (history) {
+        HIPCHK(c, ensure(c, s.hist, 2 * need_vec * history));
+        HIPCHK(c, ensure(c, s.dmat, (size_t)B * (nd * nd + nd + 2)));
+        HIPCHK(c, ensure(c, s.ring, (size_t)3 * B));
+        HIPCHK(c, ensure(c, s.part, (size_t)B * chunks * (lbfgs_nq(history) + LBFGS_NP + 2)));
+    } else HIPCHK(c, ensure(c, s.H, need_H));
     if (reshaped) {          // the rows of windows outside this call's mask must hold finite numbers in the new layout
         HIPCHK(c, hipMemsetAsync(s.vec.p, 0, s.vec.n * sizeof(double), c->stream));
-        HIPCHK(c, hipMemsetAsync(s.H.p, 0, s.H.n * sizeof(double), c->stream));
+        if (history) {
+            HIPCHK(c, hipMemsetAsync(s.hist.p, 0, s.hist.n * sizeof(double), c->stream));
+            HIPCHK(c, hipMemsetAsync(s.dmat.p, 0, s.dmat.n * sizeof(double), c->stream));
+            HIPCHK(c, hipMemsetAsync(s.ring.p, 0, s.ring.n * sizeof(int), c->stream));
+        } else HIPCHK(c, hipMemsetAsync(s.H.p, 0, s.H.n * sizeof(double), c->stream));
         memset(s.h_scal.p, 0, s.h_scal.n * sizeof(double));
     }
-    s.n = n; s.h = h; s.w = w; s.B = B;
+    s.n = n; s.h = h; s.w = w; s.B = B; s.m = history; s.scale = scale;
     const unsigned long long m = bfgs_mask(c, active);
-    hipLaunchKernelGGL(k_bfgs_begin, dim3((unsigned)((n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)B), dim3(BFGS_NT), 0, c->stream, n, m, s.H.p, s.P, s.G);
+    if (history)
+        hipLaunchKernelGGL(k_lbfgs_begin, dim3((unsigned)chunks, (unsigned)B), dim3(LBFGS_NT), 0, c->stream, n, m, s.P, s.G, s.head(), s.count(), s.stored());
+    else
+        hipLaunchKernelGGL(k_bfgs_begin, dim3((unsigned)((n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)B), dim3(BFGS_NT), 0, c->stream, n, m, s.H.p, s.P, s.G);
     HIPCHK(c, hipGetLastError());
     for (int b = 0; b < B; ) {                        // x0 of the mask's windows, one copy per run of them
         if (!((m >> b) & 1ull)) { ++b; continue; }
@@ -3423,6 +3465,31 @@ int eincm_bfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const ui
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     s.begun = true;
+    return EINCM_OK;
+}
+
+int eincm_bfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const uint8_t* active) {
+    if (!c) return EINCM_ERR_ARG;
+    return bfgs_begin_form(c, "eincm_bfgs_begin", x0_host, h, w, active, 0, 0);
+}
+
+int eincm_lbfgs_begin(eincm_ctx* c, const double* x0_host, int h, int w, const uint8_t* active, int history, int initial_scale) {
+    if (!c) return EINCM_ERR_ARG;
+    if (history < 1 || history > LBFGS_MAX_M)
+        return fail(c, EINCM_ERR_ARG, "eincm_lbfgs_begin: history %d outside 1 .. EINCM_LBFGS_MAX_HISTORY = %d", history, LBFGS_MAX_M);
+    if (initial_scale != EINCM_LBFGS_SCALE_IDENTITY && initial_scale != EINCM_LBFGS_SCALE_LAST_PAIR)
+        return fail(c, EINCM_ERR_ARG, "eincm_lbfgs_begin: initial_scale %d unknown", initial_scale);
+    return bfgs_begin_form(c, "eincm_lbfgs_begin", x0_host, h, w, active, history, initial_scale);
+}
+
+int eincm_lbfgs_history_ptrs(eincm_ctx* c, void** s_dptr, void** y_dptr, void** d_dptr, void** delta_dptr, void** head_dptr, void** count_dptr,
+                             int* history) {
+    if (!c || !s_dptr || !y_dptr || !d_dptr || !delta_dptr || !head_dptr || !count_dptr || !history) return EINCM_ERR_ARG;
+    if (const int rc = bfgs_ready(c, "eincm_lbfgs_history_ptrs", true)) return rc;
+    auto& s = c->bfgs;
+    if (!s.m) return fail(c, EINCM_ERR_STATE, "eincm_lbfgs_history_ptrs: the state is in the dense form (eincm_bfgs_begin)");
+    *s_dptr = s.lS(); *y_dptr = s.lY(); *d_dptr = s.lD(); *delta_dptr = s.ldelta(); *head_dptr = s.head(); *count_dptr = s.count();
+    *history = s.m;
     return EINCM_OK;
 }
 
@@ -3493,7 +3560,7 @@ int eincm_bfgs_trial_ptrs(eincm_ctx* c, void** xt_dptr, void** gt_dptr, int64_t*
 int eincm_bfgs_state_ptrs(eincm_ctx* c, void** x_dptr, void** g_dptr, void** p_dptr, void** hess_inv_dptr, int* n_windows, int* n) {
     if (!c || !x_dptr || !g_dptr || !p_dptr || !hess_inv_dptr || !n_windows || !n) return EINCM_ERR_ARG;
     if (const int rc = bfgs_ready(c, "eincm_bfgs_state_ptrs", true)) return rc;
-    *x_dptr = c->bfgs.X; *g_dptr = c->bfgs.G; *p_dptr = c->bfgs.P; *hess_inv_dptr = c->bfgs.H.p; *n_windows = c->bfgs.B; *n = c->bfgs.n;
+    *x_dptr = c->bfgs.X; *g_dptr = c->bfgs.G; *p_dptr = c->bfgs.P; *hess_inv_dptr = c->bfgs.m ? nullptr : c->bfgs.H.p; *n_windows = c->bfgs.B; *n = c->bfgs.n;
     return EINCM_OK;
 }
 
@@ -3511,7 +3578,27 @@ int eincm_bfgs_accept(eincm_ctx* c, const double* alpha, const uint8_t* accept_m
         if (mode == EINCM_BFGS_INIT) init |= 1ull << b;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    if (act) {
+    if (act && s.m) {
+        const int chunks = lbfgs_chunks(s.n);
+        const dim3 grid((unsigned)chunks, (unsigned)s.B);
+        if (upd | init) {
+            hipLaunchKernelGGL(k_lbfgs_dots, grid, dim3(LBFGS_NT), 0, c->stream, s.n, s.m, upd, init, bfgs_alpha(c, upd, alpha), (const double*)s.G,
+                               (const double*)s.Gt, (const double*)s.P, (const double*)s.lS(), (const double*)s.lY(), (const int*)s.head(),
+                               (const int*)s.count(), s.S, s.Y, s.part_dots());
+            HIPCHK(c, hipGetLastError());
+            hipLaunchKernelGGL(k_lbfgs_coef, dim3((unsigned)s.B), dim3(64), 0, c->stream, chunks, s.m, s.scale, upd, init, (const double*)s.part_dots(),
+                               s.lD(), s.ldelta(), s.head(), s.count(), s.stored(), s.lysyy());
+            HIPCHK(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_lbfgs_dir, grid, dim3(LBFGS_NT), 0, c->stream, s.n, s.m, act, upd, init, s.X, (const double*)s.Xt, s.G, (const double*)s.Gt,
+                           s.P, s.lS(), s.lY(), (const double*)s.S, (const double*)s.Y, (const double*)s.ldelta(), (const int*)s.head(),
+                           (const int*)s.count(), (const int*)s.stored(), s.part_dir());
+        HIPCHK(c, hipGetLastError());
+        hipLaunchKernelGGL(k_lbfgs_finish, dim3((unsigned)s.B), dim3(64), 0, c->stream, chunks, act, upd, (const double*)s.part_dir(),
+                           (const double*)s.lysyy(), s.h_scal.p);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    } else if (act) {
         const dim3 grid((unsigned)((s.n + BFGS_ROWS - 1) / BFGS_ROWS), (unsigned)s.B);
         if (upd) {
             hipLaunchKernelGGL(k_bfgs_hy, grid, dim3(BFGS_NT), (size_t)s.n * sizeof(double), c->stream, s.n, upd, bfgs_alpha(c, upd, alpha),
@@ -3533,8 +3620,9 @@ int eincm_bfgs_accept(eincm_ctx* c, const double* alpha, const uint8_t* accept_m
 int eincm_bfgs_fetch(eincm_ctx* c, double* x, double* g, double* hess_inv) {
     if (!c) return EINCM_ERR_ARG;
     if (const int rc = bfgs_ready(c, "eincm_bfgs_fetch", true)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
     auto& s = c->bfgs;
+    if (s.m && hess_inv) return fail(c, EINCM_ERR_ARG, "eincm_bfgs_fetch: the limited form (eincm_lbfgs_begin) keeps no inverse Hessian: hess_inv must be NULL");
+    HIPCHK(c, hipSetDevice(c->device));
     const size_t nv = (size_t)s.B * s.n * sizeof(double);
     if (x) HIPCHK(c, hipMemcpyAsync(x, s.X, nv, hipMemcpyDeviceToHost, c->stream));
     if (g) HIPCHK(c, hipMemcpyAsync(g, s.G, nv, hipMemcpyDeviceToHost, c->stream));

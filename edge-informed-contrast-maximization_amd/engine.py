@@ -79,6 +79,21 @@ def check_window_size(window_size):
     return int(window_size)
 
 
+def check_history(history, limit=L.LBFGS_MAX_HISTORY):
+    """Pairs (s, y) the limited-memory BFGS state keeps per window: an int in 1..EINCM_LBFGS_MAX_HISTORY on the device (bool and float
+    are refused); ``limit=None``: any positive int (the host state has no bound)."""
+    if isinstance(history, bool) or not isinstance(history, (int, np.integer)) or int(history) < 1 or (limit is not None and int(history) > limit):
+        raise ValueError(f'history {history!r}: an integer in 1..{limit}' if limit is not None else f'history {history!r}: a positive integer')
+    return int(history)
+
+
+def check_initial_scale(initial_scale):
+    """'last_pair' (H0 = y.s / y.y of the newest pair) or 'identity' (H0 = I)."""
+    if not isinstance(initial_scale, str) or initial_scale not in L.LBFGS_SCALES:
+        raise ValueError(f"initial_scale {initial_scale!r}: 'last_pair' or 'identity'")
+    return initial_scale
+
+
 def check_canny_args(threshold1, threshold2, aperture_size):
     """cv.Canny's arguments as eincm_canny takes them: finite, non-negative thresholds and aperture 3 (5, 7 and Scharr are not
     implemented).  Checked before any GPU call."""
@@ -662,6 +677,29 @@ class Engine:
         out = np.empty(self.B), np.empty(self.B), np.empty(self.B)
         self._bfgs_out = out + tuple(o.ctypes.data for o in out)
 
+    def lbfgs_begin(self, x0, active=None, history=10, initial_scale='last_pair'):
+        """``bfgs_begin`` with the inverse Hessian kept as a ring of ``history`` pairs (s, y) per window: any theta
+        shape, the dense one included.  The other ``bfgs_*`` calls then operate on that form (no inverse Hessian to fetch)."""
+        history, scale = check_history(history), L.LBFGS_SCALES[check_initial_scale(initial_scale)]
+        x = np.ascontiguousarray(np.asarray(x0, dtype=np.float64))
+        if x.ndim != 4 or x.shape[0] != self.B or x.shape[3] != 2:
+            raise ValueError(f'x0 must be ({self.B},h,w,2), got {x.shape}')
+        act, p_act = self._active_ptr(active)
+        self._check(self._lib.eincm_lbfgs_begin(self._ctx, x.ctypes.data, x.shape[1], x.shape[2], p_act, history, scale))
+        self._bfgs_shape = x.shape
+        out = np.empty(self.B), np.empty(self.B), np.empty(self.B)
+        self._bfgs_out = out + tuple(o.ctypes.data for o in out)
+
+    def lbfgs_history_tensors(self):
+        """torch views of the limited form's history in HBM: the rings S, Y (B, m, n) by ring slot, D (B, 2m+1, 2m+1) and delta (B, 2m+1)
+        (s of slot k at k, y of slot k at m + k, g at 2m), the int32 ring head and count (B,), and m."""
+        ptr = [C.c_void_p() for _ in range(6)]
+        m = C.c_int()
+        self._check(self._lib.eincm_lbfgs_history_ptrs(self._ctx, *(C.byref(q) for q in ptr), C.byref(m)))
+        B, n, m = self.B, int(np.prod(self._bfgs_shape[1:])), int(m.value)
+        shapes = ((B, m, n), (B, m, n), (B, 2 * m + 1, 2 * m + 1), (B, 2 * m + 1), (B,), (B,))
+        return tuple(self._view_at(q.value, '<f8' if i < 4 else '<i4', sh) for i, (q, sh) in enumerate(zip(ptr, shapes))) + (m,)
+
     def bfgs_eval(self, params, alpha, active=None, allow_nonfinite=True):
         """One evaluation at X + alpha[b] P per window of ``active``: (value, phi' = grad . P, max|grad|), each (B,); the trial point
         and its gradient stay in HBM.  Entries of the other windows are meaningless."""
@@ -696,12 +734,12 @@ class Engine:
         return self._view_at(xt.value, '<f8', shape), self._view_at(gt.value, '<f8', shape)
 
     def bfgs_state_tensors(self):
-        """torch views of X, G, P (B, n) and the inverse Hessian H (B, n, n) in HBM."""
+        """torch views of X, G, P (B, n) and the inverse Hessian H (B, n, n) in HBM (None in the limited form, which keeps none)."""
         x, g, p, h, nb, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(), C.c_int()
         self._check(self._lib.eincm_bfgs_state_ptrs(self._ctx, C.byref(x), C.byref(g), C.byref(p), C.byref(h), C.byref(nb), C.byref(n)))
         B, n = int(nb.value), int(n.value)
         return (self._view_at(x.value, '<f8', (B, n)), self._view_at(g.value, '<f8', (B, n)), self._view_at(p.value, '<f8', (B, n)),
-                self._view_at(h.value, '<f8', (B, n, n)))
+                self._view_at(h.value, '<f8', (B, n, n)) if h.value else None)
 
     def bfgs_accept(self, alpha, modes):
         """End of a line search per window: modes[b] in _lib.BFGS_SKIP / UPDATE / MOVE / INIT with the step alpha[b] last evaluated.

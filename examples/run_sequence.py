@@ -53,6 +53,10 @@ def main():
     ap.add_argument('--bfgs-state', choices=('host', 'device'), default='host',
                     help="with --sequences > 1: 'device' keeps x, the gradient and the inverse Hessian of the 8x8 and 16x16 levels in HBM "
                          '(DESIGN.md section 17; one engine context, fp32)')
+    ap.add_argument('--hessian', choices=('dense', 'limited', 'auto'), default='dense',
+                    help="with --sequences > 1: 'limited' keeps the newest --history pairs (s, y) instead of the inverse Hessian above 64 "
+                         "unknowns, 'auto' above 1024 unknowns only: pyramids deeper than 16x16 (DESIGN.md section 19)")
+    ap.add_argument('--history', type=int, default=10, help='pairs kept by --hessian limited / auto (at most 16 with --bfgs-state device)')
     ap.add_argument('overrides', nargs='*')
     a = ap.parse_args()
     cfg = config.load_config(a.config_dir, 'main', a.overrides) if a.config_dir else config._wrap(DEFAULTS)
@@ -129,7 +133,8 @@ def run_batched(a, cfg, H, W, n_lvls):
         handover_opt_maxiters=sol.growing_maxiters(n_lvls, sp.handover_opt.miniter, sp.handover_opt.maxiter, cfg.maxiters_grow_order, cfg.use_growing_maxiters),
         handover_opt_solver_params=dict(sp.handover_opt), handover_settings=dict(cfg.handover_settings),
         pyramid_downscale_method=cfg.pyramid_downscale_method, pyramid_upscale_method=cfg.pyramid_upscale_method,
-        pyramid_bases=list(cfg.pyramid_bases), n_groups=1 if a.bfgs_state == 'device' else min(2, B), bfgs_state=a.bfgs_state)
+        pyramid_bases=list(cfg.pyramid_bases), n_groups=1 if a.bfgs_state == 'device' else min(2, B), bfgs_state=a.bfgs_state,
+        hessian=a.hessian, history=a.history)
     print(f'{B} sequences side by side, sensor {H}x{W}, {cfg.des_n_events} events/window, R={a.refs}')
     scores = []
     for i in range(a.windows):

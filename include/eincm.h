@@ -28,7 +28,8 @@ extern "C" {
                                * 5: eincm_get_warped_events, eincm_loss_grad_device, eincm_loss_grad_masked_async, eincm_set_timing_period;
                                * 6: eincm_get_launch_policy; added since without a new version: eincm_rectify_events, eincm_remap_cubic, eincm_flow_decode,
                                *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory,
-                               *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas) */
+                               *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas), eincm_lbfgs_* (that BFGS with a limited-memory
+                               *    inverse Hessian) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -557,6 +558,26 @@ int eincm_bfgs_state_ptrs(eincm_ctx* ctx, void** x_dptr, void** g_dptr, void** p
 int eincm_bfgs_accept(eincm_ctx* ctx, const double* alpha, const uint8_t* accept_mode, double* scalars_out);
 /* X and G (n_windows, n) and, unless NULL, H (n_windows, n, n) to the host; x or g may be NULL. */
 int eincm_bfgs_fetch(eincm_ctx* ctx, double* x, double* g, double* hess_inv);
+
+/* ---- The limited-memory form of that state ------------------------------------------------------------------
+ * The same minimisations with the inverse Hessian kept as a ring of at most `history` pairs (s, y) per window instead of a matrix, so n
+ * is bounded by memory alone: theta grids beyond EINCM_BFGS_MAX_N unknowns and the dense per-pixel theta.  eincm_lbfgs_begin puts the
+ * context's optimiser state into this form; eincm_bfgs_eval / _trial / _reduce / _trial_ptrs / _accept / _fetch then operate on it
+ * (eincm_bfgs_fetch requires hess_inv == NULL, eincm_bfgs_state_ptrs returns NULL for H), with the accept modes and scalars above and
+ * two differences: an EINCM_BFGS_UPDATE stores the pair s = a P, y = Gt - G only if y.s > 2.220446049250313e-16 y.y (the oldest pair
+ * leaves a full ring) and takes P = sum_j delta_j b_j from the dot-matrix form of the two-loop recursion over the basis b = [s.., y.., G];
+ * and slot EINCM_BFGS_S_YHY holds y.y.  EINCM_BFGS_INIT empties the ring.  eincm_bfgs_begin switches the state back to the dense form.
+ * Refusals: those of eincm_bfgs_begin except its bound on n; EINCM_ERR_ARG for a history outside 1 .. EINCM_LBFGS_MAX_HISTORY or an
+ * unknown initial_scale. */
+#define EINCM_LBFGS_MAX_HISTORY 16
+#define EINCM_LBFGS_SCALE_IDENTITY  0   /* the recursion starts from H0 = I */
+#define EINCM_LBFGS_SCALE_LAST_PAIR 1   /* ... from H0 = (y.s / y.y) I of the newest pair (I while the ring is empty) */
+int eincm_lbfgs_begin(eincm_ctx* ctx, const double* x0_host, int h, int w, const uint8_t* active, int history, int initial_scale);
+/* Device pointers of the rings S and Y (n_windows, history, n) by ring slot, the dot matrix D (n_windows, 2 history + 1, 2 history + 1)
+ * and the coefficients delta (n_windows, 2 history + 1), both indexed s of slot k at k, y of slot k at history + k, G at 2 history, and of
+ * the int32 ring head (the oldest pair's slot) and count (n_windows each): inspection and tests. */
+int eincm_lbfgs_history_ptrs(eincm_ctx* ctx, void** s_dptr, void** y_dptr, void** d_dptr, void** delta_dptr, void** head_dptr,
+                             void** count_dptr, int* history);
 
 #ifdef __cplusplus
 }
