@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "eincm.h"
+#include "eincm_plan.h"
 #include "eincm_kernels.hip.h"
 #include "eincm_kernels_f64.hip.h"
 #include "eincm_binning.hip.h"
@@ -88,86 +89,6 @@ template <typename T, bool PINNED = false> struct Grow {
     size_t n = 0;
 };
 
-// Packs host arrays into one block for a single upload: add appends `bytes` at the next multiple of `align` (zero padding) and returns
-// their offset; i32 / f64 form a typed pointer into a copy of the block.
-struct Packer {
-    std::vector<char> buf;
-    size_t add(const void* p, size_t bytes, size_t align = 1) {
-        const size_t off = (buf.size() + align - 1) / align * align;
-        buf.resize(off + bytes, 0);
-        if (bytes) std::memcpy(buf.data() + off, p, bytes);
-        return off;
-    }
-    static const int32_t* i32(const char* base, size_t off) { return reinterpret_cast<const int32_t*>(base + off); }
-    static const double* f64(const char* base, size_t off) { return reinterpret_cast<const double*>(base + off); }
-};
-
-// A segment list: the binned events of every (window, source tile) cut into segments of at most `seg` events (balanced_seg_len), the
-// event kernels' unit of work; their workgroups take the segments longest first (block_to_work).  Staging builds four lists over the
-// same bins (build_list): the gather's, the splat's, the splat's short one and the 2-DoF gather's.
-struct SegList {
-    int seg = 0;                       // events per segment
-    int n = 0;                         // segments
-    double tspan = 1.0;                // time span (fraction of the window) its LDS windows are sized for (build_list)
-    Item* d_items = nullptr;           // (max_items)
-    int32_t* d_order = nullptr;        // (max_items) the segments by decreasing length
-    std::vector<Item> h_items;         // host sides of the two (kept until the upload has completed); h_items only where the host cuts them
-    std::vector<int32_t> h_order;
-    int32_t* d_win_item0 = nullptr;    // (B + 1) first segment of every window: gather and 2-DoF gather lists
-    std::vector<int32_t> h_win_item0;  // its host copy, where the host cuts the segments
-    Window* d_wins = nullptr;          // (max_items, maxR) destination windows under the current theta: gather and splat lists
-    int32_t* d_itembase = nullptr;     // (B * ntiles) first segment of every (window, tile): gather and splat lists, device binning
-    // blocks of an event kernel: every (segment, reference time) pair, padded to a multiple of 8 segments (block_to_work)
-    unsigned grid(int R) const { return (unsigned)(((n + NXCD - 1) / NXCD) * NXCD * R); }
-};
-
-// LDS destination-window geometry chosen for one list in one evaluation (fit_window)
-struct WinFit {
-    int cap, maxw;                     // capacity (pixels) and largest width
-    bool pal;                          // bank-aligned row pitch (win_pitch)
-    bool fits;                         // the list's windows fit the largest capacity class
-};
-
-// Every decision of one evaluation, taken once by plan_eval before its first launch; the launch and assembly code only read it.
-struct EvalPlan {
-    enum Shape { IDENTITY, TWO_DOF, GRID } shape = GRID;           // theta (h, w) = the sensor's / (1, 1) / any other grid
-    enum ThetaSrc { THETA_DEVICE, THETA_ARGS, THETA_PINNED, THETA_PIECES } theta_src = THETA_PIECES;   // where k_theta reads theta
-    int h = 0, w = 0; size_t nth = 0;   // nth: doubles of one window's theta
-    bool want_grad = false, full_aux = false, div_grad = false;
-    EvalParams ep{};
-    bool obj = false; ObjGeom og{};     // a contrast / correlation kind other than the defaults (eincm_objectives.hip.h)
-    // LDS windows (fit_window): the splat's and the gather's (into Geom), the 2-DoF gather's, and whether k_splat walks splat_sh
-    int wincap = 0, winmaxw = 0, pitch_aligned = 0, wincap_a = 0, winmaxw_a = 0;
-    WinFit win_2{}; bool splat_short = false;
-    bool use_arg = false, use_arg_big = false;   // theta rides in the arguments of every kernel (ThetaArg) / of k_theta (ThetaArgMid, Big)
-    bool need_theta_image = false;      // k_theta runs (a 2-DoF theta skips it unless somebody reads d_Theta)
-    bool host_asm = false;              // scalar assembly and the 2-DoF gradient sum on the host (see h_g11)
-    bool grid_tail = false;             // host-assembled theta grid: the gather's tail finishes dL/dtheta (and adds the TV term's)
-    bool stream_stats = false, g2_from_imgrad = false;   // k_stats_stream, not k_iwe_finish + k_stats; contrast energy from k_imgrad
-    bool tv_proj = false, proj = false; // k_tv / the theta-grid gather project their tile's gradient onto the theta cells themselves
-    bool all_r = false;                 // ... the gather with one workgroup per segment for all reference times
-    bool events_projected = false; int nsrc = 0;   // k_project's sources: the event term's dL/dTheta image unless projected, the TV term's
-    bool zero_copy_out = false;         // k_final writes the results straight into pinned host memory
-};
-
-// Every decision of one staging, taken once by plan_staging before its first HIP call; the phases of stage_windows only read it, and
-// the context keeps the one of the staged batch (plan_eval, eincm_get_launch_policy).
-struct StagePlan {
-    Geom g{};                           // the batch's geometry as staged (an evaluation sets the mask, capacities and pitch of the context's copy)
-    int64_t N = 0;                      // events of the batch
-    int seg = 0, seg_s = 0, seg_2 = 0;  // events per segment of the gather's, the splat's and the 2-DoF gather's list
-    bool splat_short = false;           // the splat gets its short list (8192) beside a longer one
-    int pitch = 0;                      // regime of the bank-aligned LDS pitch (win_pitch): 0 never, 1 k_splat where it costs no capacity class, 2 the 2-DoF gather too; plan_eval decides per evaluation
-    bool sort_segments = true;          // k_segsort deals the gather's copy of the events (EINCM_NO_SEGSORT: a plain copy)
-    bool spread = true;                 // k_spread re-deals the splat's copy (EINCM_NO_SPREAD: time order)
-    bool host_binning = false;          // the host sorts the events by (window, tile), not the kernels of eincm_binning.hip.h
-    bool defer_constants = false;       // EINCM_SW_DEFER_CONSTANTS: the caller sums the shards' IUEs before the window constants are formed
-    bool wide = false;                  // a window has a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel)
-};
-
-constexpr int SEG_SHORT = 8192;         // events per segment of the splat's short list
-constexpr int MIN_SEG = 64;             // the shortest segments EINCM_SEG / EINCM_SEG_SPLAT / EINCM_SEG_2DOF may ask for: what the lists' capacity allows for
-
 // The caller's arrays of one staging: one pointer per window (nothing is concatenated on the host)
 struct StageArgs {
     int B, R; const int64_t* n_events;
@@ -183,13 +104,6 @@ struct StageScratch {
     std::vector<BinBlock> blks; std::vector<int32_t> win_blk; int32_t misc[4]; std::vector<double> mom;   // device binning
     std::vector<uint32_t> sxy; std::vector<double> st; std::vector<float> ef;                             // host binning
     std::vector<int> ishift;                                                                              // float64 mode
-};
-
-// theta and gradient of an evaluation whose caller keeps them in HBM (eincm_loss_grad_device, eincm_bfgs_eval)
-struct DevIo {
-    const double* theta = nullptr;      // (B,h,w,2) in the caller's device buffer; nullptr: theta comes from the host
-    double* grad = nullptr;             // the gradient goes there, device to device (nullptr: it stays in the engine's block)
-    double vmax = -1.0;                 // bounds |theta| for the window-capacity choice (< 0: unknown, largest windows)
 };
 
 // The evaluation in flight: eval_begin enqueues its forward half (FORWARD; the caller may all-reduce the IWE
@@ -216,21 +130,18 @@ struct Flight {
 
 }  // namespace
 
-struct eincm_ctx {
+// (PlanCtx, eincm_plan.h: the sensor size, the staged batch's geometry, plan and segment lists, and the settings both plans read)
+struct eincm_ctx : PlanCtx {
     int device = 0;
-    int H = 0, W = 0, maxR = 0, maxB = 0;
+    int maxR = 0, maxB = 0;
     int64_t maxN = 0;
     uint32_t cflags = 0;
-    int seg = 0;                   // events per segment of the gather list (0 = choose per batch); EINCM_SEG overrides
-    int seg_s = 0;                 // ... of the splat list; EINCM_SEG_SPLAT overrides
     hipStream_t stream = nullptr;
     std::string err;
     Mem mem;                       // owns every device and pinned block below
 
     // staged batch
     bool staged = false;
-    StagePlan stage;               // the plan the staged batch was staged from (plan_staging)
-    Geom g{};
     std::vector<int64_t> win_events;
 
     // device buffers
@@ -239,23 +150,13 @@ struct eincm_ctx {
     uint32_t* d_xy_g = nullptr;    // (maxN) the gather's copy: the same bins, every segment of the gather list sorted by source pixel and dealt to its threads (k_segsort)
     double* d_t_g = nullptr;       // (maxN)
     std::vector<int32_t> h_tilecount;   // (B, ntiles) events per (window, tile) of the staged batch: what every segment list is cut from
-    SegList gather;                // walked by k_gather / k_count / k_mask / the fp64 kernels, on the gather's copy of the events
-    SegList splat;                 // shorter segments walked by k_splat
-    SegList splat_sh;              // the splat's SHORT list (8192) beside a 16384-event one: a 2-DoF theta too large for the long segments' windows walks it (launch_forward)
-    // the segments the 2-DoF gather walks, on the SPLAT's copy of the events (it has no per-pixel accumulators, so the time-ordered copy
-    // serves it, and it wants shorter segments than the theta-grid gather does: round-2 tuning)
-    SegList gather_2;
     bool policy_evaluated = false; // an evaluation has chosen capacities since the last staging (eincm_get_launch_policy)
-    int wincap = WIN_CAP_DEFAULT;
-    bool wincap_fixed = false;     // EINCM_WINCAP pins the capacity; otherwise it is chosen per evaluation from max|theta|
     // device-side staging (eincm_binning.hip.h)
     int16_t* d_raw_x = nullptr; int16_t* d_raw_y = nullptr; double* d_raw_t = nullptr;   // (maxN) events as handed over
     BinBlock* d_binblocks = nullptr; int32_t* d_win_blk = nullptr; uint32_t* d_blockhist = nullptr;
     int32_t* d_tilecount = nullptr; int32_t* d_tilebase = nullptr; int32_t* d_bin_misc = nullptr;
-    bool itembase_valid = false;   // the gather and splat lists' d_itembase hold the first segment of every (window, tile) for the staged batch
     double* d_edges_raw = nullptr; double* d_edge_moments = nullptr;
     int64_t max_binblocks = 0;
-    bool host_binning = false;
     int64_t max_items = 0;
     float* d_edges = nullptr;      // (B,R,H,W)
     double* d_edge_ts = nullptr;   // (B,R)
@@ -287,14 +188,11 @@ struct eincm_ctx {
     Grow<double> d_AH, d_AW;       // (H,h) (W,w) for the current theta shape, grown on demand (ensure_resample)
     int2* d_rowtap = nullptr; int2* d_coltap = nullptr;
     TileRange* d_tilerng = nullptr;    // (ntiles) coarse cells under each tile for the current theta shape
-    bool device_results = false;       // eincm_set_device_results: results stay in HBM until eincm_finish_collect (event-sharded mode over RCCL)
-    bool proj_in_gather = false;       // every tile touches <= PG_MAXC x PG_MAXC cells: k_gather projects its tile itself
     int cur_h = -1, cur_w = -1, cur_method = -1;
     int64_t coarse_cap = 0;        // cells per window in d_gth's halves: the stride the kernels are given (ensure_coarse)
 
-    // selectable objective kinds (eincm_objectives.hip.h): tile size of the adaptive kinds, the zero-warp values of every kind
+    // selectable objective kinds (eincm_objectives.hip.h): the zero-warp values of every kind
     // (computed on the first evaluation that needs them, dropped by set_windows and by a tile-size change) and the per-cell partials
-    int obj_th = 32, obj_tw = 42;
     bool objc_valid = false;
     std::vector<ObjConst> h_objc;
     Grow<ObjConst> d_objc;         // (maxB), allocated on first use
@@ -363,14 +261,12 @@ struct eincm_ctx {
     int64_t hp_n = 0;
     bool constants_pending = false;   // staged with EINCM_SW_DEFER_CONSTANTS and not finished yet
     bool sharded_staging = false;     // the staged batch's constants came from EINCM_SW_DEFER_CONSTANTS (summed IUEs of all shards)
-    int splat_size = 3;               // eincm_set_splat_window: events_to_pdf_frame's window_size
-    int splat_rad = 1;                // its radius splat_size / 2: 1 runs k_splat / k_gather, any other k_splat_r / k_gather_r
+    int splat_size = 3;               // eincm_set_splat_window: events_to_pdf_frame's window_size (splat_rad: its radius splat_size / 2)
     bool acc_dirty = false;        // a forward half was launched and its consumers were not: accumulators must be memset before reuse
     bool Theta_valid = false;      // d_Theta holds the upsampled theta of the last evaluation (2-DoF evaluations skip the image)
     std::vector<double> last_theta11;   // (B,2) theta of the last 2-DoF evaluation (to build d_Theta on demand)
 
     // float64 mode (EINCM_CF_FP64, eincm_kernels_f64.hip.h): its own images and accumulators, sized at create
-    bool fp64 = false;
     struct {
         unsigned long long* acc = nullptr;   // (B,R,H,W) u64 IWE accumulator at 2^ishift[b], zero between evaluations (k64_img_a clears)
         double* iwe = nullptr;               // (B,R,H,W)
@@ -532,63 +428,30 @@ struct OneShot {
     hipError_t sync() { pending = false; return hipStreamSynchronize(c->stream); }
 };
 
-// ---------------------------------------------------------------------------------------------
-// jax.image.scale_and_translate per-axis weight matrix (S7; theta_utils.py:25-35), fp64 on the host.
-// A is (n_out, n_in): out = A @ in.
-// ---------------------------------------------------------------------------------------------
-double kern_eval(int method, double x) {
-    switch (method) {
-        case EINCM_METHOD_BILINEAR: return std::max(0.0, 1.0 - std::fabs(x));
-        case EINCM_METHOD_LANCZOS3:
-        case EINCM_METHOD_LANCZOS5: {
-            const double radius = (method == EINCM_METHOD_LANCZOS3) ? 3.0 : 5.0;
-            if (x > radius) return 0.0;
-            if (!(x > 1e-3)) return 1.0;
-            const double y = radius * std::sin(M_PI * x) * std::sin(M_PI * x / radius);
-            return y / (M_PI * M_PI * x * x);
-        }
-        case EINCM_METHOD_CUBIC: {
-            if (x >= 2.0) return 0.0;
-            if (x >= 1.0) return ((-0.5 * x + 2.5) * x - 4.0) * x + 2.0;
-            return ((1.5 * x - 2.5) * x) * x + 1.0;
-        }
-    }
-    return 0.0;
+// ---- the environment: every read, one function per lifetime ----
+const EvalKnobs& process_knobs() {     // once per process, at the first evaluation of a context that is not float64
+    static const EvalKnobs k{getenv("EINCM_NO_BIG_THETA_ARG") != nullptr, getenv("EINCM_NO_HOST_ASM") != nullptr,
+                             getenv("EINCM_GATHER_ALL_R") ? atoi(getenv("EINCM_GATHER_ALL_R")) : -1};
+    return k;
 }
-
-void resample_matrix(int n_in, int n_out, int method, std::vector<double>& A) {
-    A.assign((size_t)n_out * n_in, 0.0);
-    const double scale = (double)n_out / (double)n_in;
-    const double inv_scale = 1.0 / scale;
-    const double kernel_scale = std::max(inv_scale, 1.0);
-    const double thresh = 1000.0 * 1.1920928955078125e-07;   // 1000 * float32 eps
-    for (int o = 0; o < n_out; ++o) {
-        const double sample_f = ((double)o + 0.5) * inv_scale - 0.5;
-        double total = 0.0;
-        for (int i = 0; i < n_in; ++i) {
-            const double x = std::fabs(sample_f - (double)i) / kernel_scale;
-            const double wgt = kern_eval(method, x);
-            A[(size_t)o * n_in + i] = wgt;
-            total += wgt;
-        }
-        const bool inside = (sample_f >= -0.5) && (sample_f <= (double)n_in - 0.5);
-        for (int i = 0; i < n_in; ++i) {
-            double& a = A[(size_t)o * n_in + i];
-            a = (std::fabs(total) > thresh) ? a / (total != 0.0 ? total : 1.0) : 0.0;
-            if (!inside) a = 0.0;
-        }
-    }
+struct CreateKnobs { int seg = 0, seg_s = 0, wincap = 0; bool host_binning = false; };      // (0: not set)
+CreateKnobs create_knobs() {           // when a context is created
+    CreateKnobs k;
+    if (const char* s = getenv("EINCM_SEG")) k.seg = atoi(s);
+    if (const char* s = getenv("EINCM_SEG_SPLAT")) k.seg_s = atoi(s);
+    if (const char* s = getenv("EINCM_WINCAP")) k.wincap = atoi(s);
+    k.host_binning = getenv("EINCM_HOST_BINNING") != nullptr;
+    return k;
 }
-
-void multi_ref_weights(int R, double* w) {
-    double s = 0.0;
-    for (int r = 0; r < R; ++r) {
-        // np.linspace(-1.5, 1.5, R): start + r*step with step = 3/(R-1); R == 1 -> [-1.5]
-        const double x = (R > 1) ? (-1.5 + (double)r * (3.0 / (double)(R - 1))) : -1.5;
-        w[r] = std::exp(-0.5 * x * x) / std::sqrt(2.0 * M_PI);
-        s += w[r];
-    }
-    for (int r = 0; r < R; ++r) w[r] /= s;
+struct LiveKnobs { StageKnobs stage; bool no_proj_in_gather = false; };
+LiveKnobs live_knobs() {               // where they are used: `stage` at every staging, the other whenever the resample tables are rebuilt
+    LiveKnobs k;
+    if (const char* e = getenv("EINCM_SEG_2DOF")) k.stage.seg_2 = atoi(e);
+    if (const char* e = getenv("EINCM_PITCH_ALIGNED")) { k.stage.has_pitch = true; k.stage.pitch = atoi(e); }
+    k.stage.no_segsort = getenv("EINCM_NO_SEGSORT") != nullptr;
+    k.stage.no_spread = getenv("EINCM_NO_SPREAD") != nullptr;
+    k.no_proj_in_gather = getenv("EINCM_NO_PROJ_IN_GATHER") != nullptr;
+    return k;
 }
 
 void free_all(eincm_ctx* c) {
@@ -642,70 +505,20 @@ void launch_timed(eincm_ctx* c, int stage, K kernel, dim3 grid, dim3 block, size
 
 int ensure_resample(eincm_ctx* c, int h, int w, int method) {
     if (c->cur_h == h && c->cur_w == w && c->cur_method == method) return EINCM_OK;
-    const int H = c->H, W = c->W;
-    std::vector<double> AH, AW;
-    resample_matrix(h, H, method, AH);
-    resample_matrix(w, W, method, AW);
-    std::vector<int2> rt(H), ct(W);
-    for (int y = 0; y < H; ++y) {
-        int lo = h, hi = 0;
-        for (int i = 0; i < h; ++i) if (AH[(size_t)y * h + i] != 0.0) { lo = std::min(lo, i); hi = std::max(hi, i + 1); }
-        if (lo >= hi) { lo = 0; hi = 0; }
-        rt[y] = make_int2(lo, hi);
-    }
-    for (int x = 0; x < W; ++x) {
-        int lo = w, hi = 0;
-        for (int j = 0; j < w; ++j) if (AW[(size_t)x * w + j] != 0.0) { lo = std::min(lo, j); hi = std::max(hi, j + 1); }
-        if (lo >= hi) { lo = 0; hi = 0; }
-        ct[x] = make_int2(lo, hi);
-    }
-    HIPCHK(c, ensure(c, c->d_AH, AH.size()));
-    HIPCHK(c, ensure(c, c->d_AW, AW.size()));
-    HIPCHK(c, hipMemcpyAsync(c->d_AH.p, AH.data(), AH.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_AW.p, AW.data(), AW.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_rowtap, rt.data(), rt.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_coltap, ct.data(), ct.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
-    // the coarse cells under every 32x32 tile (what k_gather's own projection walks)
-    const int tilesX = (W + TS - 1) / TS, tilesY = (H + TS - 1) / TS;
-    std::vector<TileRange> tr((size_t)tilesX * tilesY);
-    bool fits = true;
-    for (int ty = 0; ty < tilesY; ++ty)
-        for (int tx = 0; tx < tilesX; ++tx) {
-            int ilo = h, ihi = 0, jlo = w, jhi = 0;
-            for (int y = ty * TS; y < std::min(ty * TS + TS, H); ++y) if (rt[y].y > rt[y].x) { ilo = std::min(ilo, rt[y].x); ihi = std::max(ihi, rt[y].y); }
-            for (int x = tx * TS; x < std::min(tx * TS + TS, W); ++x) if (ct[x].y > ct[x].x) { jlo = std::min(jlo, ct[x].x); jhi = std::max(jhi, ct[x].y); }
-            TileRange q;
-            q.ilo = ilo < ihi ? ilo : 0; q.ni = std::max(ihi - ilo, 0); q.jlo = jlo < jhi ? jlo : 0; q.nj = std::max(jhi - jlo, 0);
-            fits = fits && q.ni <= PG_MAXC && q.nj <= PG_MAXC;
-            tr[(size_t)ty * tilesX + tx] = q;
-        }
-    HIPCHK(c, hipMemcpyAsync(c->d_tilerng, tr.data(), tr.size() * sizeof(TileRange), hipMemcpyHostToDevice, c->stream));
-    c->proj_in_gather = fits && !getenv("EINCM_NO_PROJ_IN_GATHER");
+    static_assert(sizeof(Int2) == sizeof(int2) && sizeof(TileRange) == 4 * sizeof(int), "the tap tables go up as they are");
+    ResampleTables t;
+    build_resample(h, w, c->H, c->W, method, t);
+    HIPCHK(c, ensure(c, c->d_AH, t.AH.size()));
+    HIPCHK(c, ensure(c, c->d_AW, t.AW.size()));
+    HIPCHK(c, hipMemcpyAsync(c->d_AH.p, t.AH.data(), t.AH.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_AW.p, t.AW.data(), t.AW.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_rowtap, t.rowtap.data(), t.rowtap.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_coltap, t.coltap.data(), t.coltap.size() * sizeof(int2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_tilerng, t.tilerng.data(), t.tilerng.size() * sizeof(TileRange), hipMemcpyHostToDevice, c->stream));
+    c->proj_in_gather = t.fits && !live_knobs().no_proj_in_gather;
     HIPCHK(c, hipStreamSynchronize(c->stream));     // host vectors go out of scope
     c->cur_h = h; c->cur_w = w; c->cur_method = method;
     return EINCM_OK;
-}
-
-constexpr size_t ZERO_COPY_MAX = 65536;   // doubles of theta / gradient that cross PCIe by zero-copy access to pinned host memory (a 64-window batch at 16x16: 32768)
-
-
-// largest width of an LDS destination window of `cap` pixels (Geom.winmaxw)
-int win_maxw(int cap) { return std::max(40, (int)std::lround(std::sqrt((double)cap * 1.4))); }
-
-// LDS window capacity for the segments of one list, chosen per evaluation (eval_begin): the host knows theta, hence the largest
-// displacement (vmax * tspan) a segment of the list can see; the window's side is the tile plus that plus the splat's margin.
-// LDS holds pitch x height words per window, the pitch being the width, or the width rounded up to the 32 banks (win_pitch).
-// pitch: 1 takes the aligned pitch where it does not push the window into a larger capacity class (its gain is a few per cent of
-// bank conflicts, a class costs workgroups per CU: 8 windows of 10^6 events whose theta needs 66-pixel windows: 96 x 66 words = the
-// 6912 class, 5 workgroups per CU, 2-DoF gather 62 -> 68 us); 0 keeps pitch = width; -1 too, sized on the unrounded side (the
-// theta-grid gather's rule).  floor_k: the smallest capacity class the list takes.
-WinFit fit_window(double vmax, double tspan, double margin, int floor_k, int pitch) {
-    static const int caps[] = {2304, 3072, 4608, 6912};      // 6912 keeps k_gather's LDS (window + accumulators + Theta tile) under 64 KiB
-    const double side = TS + margin + vmax * tspan, sd = std::ceil(side);
-    const double need = pitch < 0 ? side * side : sd * sd;
-    int cap = caps[3];
-    for (int k = floor_k; k < 4; ++k) if (need <= caps[k]) { cap = caps[k]; break; }
-    return WinFit{cap, win_maxw(cap), pitch > 0 && std::ceil(sd / 32.0) * 32.0 * sd <= (double)cap, need <= (double)caps[3]};
 }
 
 // Every cross-workgroup accumulator (u64 IWE stack, i64 dL/dTheta, i64 coarse cells) is zero between evaluations because its
@@ -980,14 +793,6 @@ void f64_assemble(eincm_ctx* c) {
 }
 
 // ---- selectable objective kinds (eincm_objectives.hip.h) ----
-ObjGeom obj_geom(const eincm_ctx* c, int ck, int rk, int need) {
-    ObjGeom og{};
-    og.th = c->obj_th; og.tw = c->obj_tw;
-    og.nty = c->g.H / og.th; og.ntx = c->g.W / og.tw; og.ncells = og.nty * og.ntx;
-    og.ck = ck; og.rk = rk; og.need = need;
-    return og;
-}
-
 int obj_buffers(eincm_ctx* c, const ObjGeom& og) {
     const size_t n = (size_t)c->g.B * c->g.R * og.ncells * OBJ_NP;
     HIPCHK(c, ensure(c, c->d_oparts, n));
@@ -1000,7 +805,7 @@ int obj_buffers(eincm_ctx* c, const ObjGeom& og) {
 // k_obj_const; the default kinds' values come from the window constants of staging.  Synchronous (once per staging / tile size).
 int obj_constants(eincm_ctx* c) {
     if (c->objc_valid) return EINCM_OK;
-    const ObjGeom og = obj_geom(c, 0, 0, OBJ_NEED_TILE_GM | OBJ_NEED_GM | OBJ_NEED_JOINT);
+    const ObjGeom og = obj_geom(*c, 0, 0, OBJ_NEED_TILE_GM | OBJ_NEED_GM | OBJ_NEED_JOINT);
     int rc = obj_buffers(c, og);
     if (rc) return rc;
     Geom g = c->g;
@@ -1044,114 +849,6 @@ void obj_assemble(eincm_ctx* c) {
         }
         assemble_window(P.ep, g.R, sum_rel_con, sum_rel_corr, o.mean_rel_div, o.tv, bad, false, o);
     }
-}
-
-// ---- the plan of an evaluation ----
-EvalPlan::Shape theta_shape(const Geom& g, int h, int w) {
-    return (h == g.H && w == g.W) ? EvalPlan::IDENTITY : (h == 1 && w == 1) ? EvalPlan::TWO_DOF : EvalPlan::GRID;
-}
-int correlation_kind(const eincm_params* p) { return (int)((p->flags & EINCM_PF_CORRELATION_MASK) >> 8); }
-bool other_kinds(const eincm_params* p) { return p->contrast_kind > EINCM_CONTRAST_VARIANCE || correlation_kind(p) != EINCM_CORRELATION_MSE; }
-
-// Every decision of one evaluation, from the context's state and the call's checked arguments.  No side effects (eval_begin's).
-EvalPlan plan_eval(const eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad) {
-    const Geom& g = c->g;
-    EvalPlan P;
-    P.shape = theta_shape(g, h, w);
-    const bool identity = P.shape == EvalPlan::IDENTITY, two_dof = P.shape == EvalPlan::TWO_DOF;
-    P.h = h; P.w = w; P.nth = (size_t)h * w * 2;
-    P.want_grad = want_grad;
-    P.full_aux = (p->flags & EINCM_PF_FULL_AUX) != 0;
-    P.div_grad = p->delta != 0.0 && want_grad;
-    EvalParams& ep = P.ep;
-    ep.alpha = p->alpha; ep.beta = p->beta; ep.gamma = p->gamma; ep.delta = p->delta;
-    ep.cur_pyr_lvl = p->cur_pyr_lvl; ep.contrast_kind = p->contrast_kind;
-    ep.want_div = (P.full_aux || p->delta != 0.0) ? 1 : 0;
-    ep.want_tv = ((p->cur_pyr_lvl <= 0) && (p->gamma != 0.0 || P.full_aux)) ? 1 : 0;
-    ep.use_tv_grad = (ep.want_tv && p->gamma != 0.0 && want_grad && !(p->flags & EINCM_PF_NO_TV_GRAD)) ? 1 : 0;
-    ep.h = h; ep.w = w; ep.identity = identity ? 1 : 0;
-    P.obj = other_kinds(p);
-    const int ck = p->contrast_kind, rk = correlation_kind(p);
-    if (P.obj) P.og = obj_geom(c, ck, rk, (ck == EINCM_CONTRAST_ADAPTIVE_GRAD_MAG ? OBJ_NEED_TILE_GM : 0) |
-                                          ((ck == EINCM_CONTRAST_GRAD_MAG || rk == EINCM_CORRELATION_JOINT_CONTRAST) ? OBJ_NEED_GM : 0) |
-                                          (rk == EINCM_CORRELATION_JOINT_CONTRAST ? OBJ_NEED_JOINT : 0));
-    if (c->fp64) return P;          // f64_launch: one segment list, one launch form, none of the launch policy below
-    const size_t nall = (size_t)g.B * P.nth;
-
-    // theta in the kernel arguments: up to THETA_ARG_MAX doubles in every kernel's; k_theta alone takes a larger one in its own (a 16x16
-    // grid of one window: 4 KiB), the event kernels then read the Theta image, or a 2-DoF theta from the pinned staging buffer
-    static const bool no_big_arg = getenv("EINCM_NO_BIG_THETA_ARG") != nullptr;
-    P.use_arg = !c->fl.io.theta && !identity && nall <= (size_t)THETA_ARG_MAX;
-    P.use_arg_big = !c->fl.io.theta && !identity && nall <= (size_t)THETA_ARG_BIG && !no_big_arg;
-    P.theta_src = c->fl.io.theta ? EvalPlan::THETA_DEVICE
-                : (P.use_arg_big && (P.use_arg || !two_dof)) ? EvalPlan::THETA_ARGS
-                : nall <= ZERO_COPY_MAX ? EvalPlan::THETA_PINNED : EvalPlan::THETA_PIECES;
-    // (device-resident theta: no host copy for ensure_theta_image to rebuild the image from)
-    P.need_theta_image = !two_dof || ep.want_tv || c->fl.io.theta;
-
-    // LDS window capacity for this evaluation: the host knows theta, hence the largest displacement a segment can see.
-    // Small windows give 8 workgroups per CU; windows too small for the flow push taps onto the slow direct-to-HBM path.
-    P.wincap = g.wincap; P.winmaxw = g.winmaxw; P.wincap_a = g.wincap_a; P.winmaxw_a = g.winmaxw_a;
-    P.pitch_aligned = c->stage.pitch != 0 ? 1 : 0;
-    P.win_2 = WinFit{c->wincap, win_maxw(c->wincap), c->stage.pitch >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
-    if (!c->wincap_fixed) {
-        double vmax = 0.0;
-        const size_t stride = nall > 8192 ? nall / 8192 : 1;            // dense theta: sample (any capacity is correct; 65536 samples cost 90 us)
-        if (c->fl.io.theta) vmax = (c->fl.io.vmax >= 0.0 && std::isfinite(c->fl.io.vmax)) ? c->fl.io.vmax : 1e9;      // unknown: the largest windows
-        else if (stride == 1) { for (size_t i = 0; i < nall; ++i) { const double a = std::fabs(theta_host[i]); vmax = std::max(vmax, a <= 1.7e308 ? a : 0.0); } }   // (vectorises)
-        else for (size_t i = 0; i < nall; i += stride) { const double a = std::fabs(theta_host[i]); if (a > vmax && std::isfinite(a)) vmax = a; }
-        // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
-        const double margin = 2.0 * (c->splat_rad + 1);
-        // Where a larger window costs no residency it is taken at once (a capacity is an allocation, the windows themselves stay as small
-        // as their segments need): the 2-DoF kernels hold nothing but the window in LDS, 4608 words = 18 KiB still gives the 8 workgroups
-        // of 4 waves a CU can hold; the theta-grid gather carries 32 KiB beside its window and runs 3 workgroups per CU up to 5461 words.
-        // The theta-grid splat (window + 16 KiB Theta tile) pays for capacity with workgroups per CU (6 / 5 / 4 / 3), so it takes what it needs.
-        // Each list's windows are sized for its time span: what all but 3 % of the events' segments stay within (build_list; the mean
-        // tile would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
-        const int floor_s = two_dof ? 2 : 0, pitch_s = c->stage.pitch != 0 ? 1 : 0;
-        WinFit s = fit_window(vmax, c->splat.tspan, margin, floor_s, pitch_s);
-        // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
-        // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
-        P.splat_short = two_dof && c->splat_sh.n > 0 && !s.fits;
-        if (P.splat_short) s = fit_window(vmax, c->splat_sh.tspan, margin, floor_s, pitch_s);
-        P.wincap = s.cap; P.winmaxw = s.maxw; P.pitch_aligned = s.pal ? 1 : 0;
-        // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
-        // sends taps down the direct path
-        const WinFit a = fit_window(vmax, c->gather.tspan, margin, 2, -1);
-        P.wincap_a = a.cap; P.winmaxw_a = a.maxw;
-        // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
-        // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
-        P.win_2 = fit_window(vmax, c->gather_2.tspan, margin, 2, c->stage.pitch >= 2 ? 1 : 0);
-    }
-
-    // 2-DoF theta with nothing but the contrast and correlation terms (every level above 0 of the reference's pyramid at its first
-    // level, and the bench workload), or a theta grid whose gather's tail finishes the gradient (not with another splat window), TV
-    // included (k_tv projects its own gradient, the tail combines it; a 2-DoF theta with TV keeps k_final): host assembly
-    static const bool no_host_asm = getenv("EINCM_NO_HOST_ASM") != nullptr;
-    const bool tail_ok = c->splat_rad == 1 && P.shape == EvalPlan::GRID && c->proj_in_gather && c->itembase_valid && nall <= ZERO_COPY_MAX &&
-                         !c->fl.io.theta;
-    P.host_asm = want_grad && ((two_dof && !ep.want_tv) || tail_ok) && !ep.want_div && !P.full_aux && !no_host_asm && !c->device_results &&
-                 !c->fl.io.theta;
-    P.grid_tail = P.host_asm && P.shape == EvalPlan::GRID;
-    // Gradient evaluations with the grad-mag contrast take the contrast energy from k_imgrad (which computes the Scharr images anyway),
-    // so the statistics are a pure streaming reduction.  A new objective kind: k_stats_stream -> k_obj_parts -> k_obj_grad -> gather;
-    // k_final / host_assemble still do the gradient sums and the TV / divergence terms, obj_assemble the contrast and correlation ones.
-    P.g2_from_imgrad = want_grad && ep.contrast_kind == EINCM_CONTRAST_GRAD_MAG && !P.obj;
-    P.stream_stats = P.host_asm || (P.g2_from_imgrad && g.ntiles >= NSPART) || P.obj;
-    // theta grids coarse enough for it: k_tv and k_gather project their tile's gradient onto the theta cells themselves (no k_project)
-    P.tv_proj = ep.use_tv_grad && P.shape == EvalPlan::GRID && c->proj_in_gather;
-    P.proj = want_grad && P.shape == EvalPlan::GRID && c->proj_in_gather && c->splat_rad == 1;
-    // the in-gather projection on big launches: one workgroup per segment for all reference times (8 windows of 10^6 events at 16x16:
-    // 792 workgroups of 5 reference times each instead of 3960: 148 -> 135 us; one window: 99 workgroups, 29 -> 84 us - so only where the
-    // segments alone fill the chip's 768 workgroup slots of this kernel)
-    static const int all_r_env = getenv("EINCM_GATHER_ALL_R") ? atoi(getenv("EINCM_GATHER_ALL_R")) : -1;
-    P.all_r = P.proj && (all_r_env >= 0 ? all_r_env != 0 : c->gather.n >= 700);
-    // k_project's sources: the event term's dL/dTheta image unless a gather projected it (2-DoF: partials), the TV term's unless k_tv did
-    P.events_projected = two_dof || P.proj;
-    P.nsrc = (!want_grad || identity) ? 0 : (P.events_projected ? 0 : 1) + ((ep.use_tv_grad && !P.tv_proj) ? 1 : 0);
-    // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
-    P.zero_copy_out = !c->device_results && !c->fl.io.theta && !identity && nall <= ZERO_COPY_MAX;
-    return P;
 }
 
 // theta_nan[b]: a NaN / Inf somewhere in window b's theta (host-assembled and float64 evaluations)
@@ -1202,7 +899,8 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         int rc = ensure_resample(c, h, w, p->method);
         if (rc) return rc;
     }
-    const EvalPlan P = plan_eval(c, theta_host, h, w, p, want_grad);
+    static const EvalKnobs no_knobs;               // (a float64 evaluation has no launch policy and reads none)
+    const EvalPlan P = plan_eval(*c, c->fl.io, c->fp64 ? no_knobs : process_knobs(), theta_host, h, w, p, want_grad);
     if (c->fp64) {
         c->fl.plan = P; scan_theta(c, theta_host, nth);
         if (const int rc = f64_launch(c, theta_host)) return rc;
@@ -1679,11 +1377,12 @@ eincm_ctx* eincm_create(int device, int H, int W, int max_refs, int max_windows,
     TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
     const int tilesX = (W + TS - 1) / TS, tilesY = (H + TS - 1) / TS, ntiles = tilesX * tilesY;
     const size_t B = max_windows, R = max_refs, img = (size_t)H * W;
-    // the switches a context reads when it is created, all of them (a staging reads its own in plan_staging)
-    if (const char* s = getenv("EINCM_SEG")) { int v = atoi(s); if (v >= MIN_SEG && v <= MAX_SEG) c->seg = v; }
-    if (const char* s = getenv("EINCM_SEG_SPLAT")) { int v = atoi(s); if (v >= MIN_SEG && v <= MAX_CHUNK) c->seg_s = v; }   // k_splat's u32 sums bound a segment
-    if (const char* s = getenv("EINCM_WINCAP")) { int v = atoi(s); if (v >= 1024 && v <= 6912) { c->wincap = (v / 4) * 4; c->wincap_fixed = true; } }
-    c->host_binning = (ntiles > BIN_MAX_TILES) || (getenv("EINCM_HOST_BINNING") != nullptr);
+    // the switches a context reads when it is created, all of them (a staging reads its own: live_knobs)
+    const CreateKnobs k = create_knobs();
+    if (k.seg >= MIN_SEG && k.seg <= MAX_SEG) c->seg = k.seg;
+    if (k.seg_s >= MIN_SEG && k.seg_s <= MAX_CHUNK) c->seg_s = k.seg_s;   // k_splat's u32 sums bound a segment
+    if (k.wincap >= 1024 && k.wincap <= 6912) { c->wincap = (k.wincap / 4) * 4; c->wincap_fixed = true; }
+    c->host_binning = (ntiles > BIN_MAX_TILES) || k.host_binning;
     c->max_items = (int64_t)B * ntiles + max_events_total / MIN_SEG + 1;   // a tile of n events is cut into ceil(n / seg) segments, seg >= MIN_SEG
     TRY(c->mem.alloc_dev(c->d_xy, (size_t)max_events_total));
     TRY(c->mem.alloc_dev(c->d_t, (size_t)max_events_total));
@@ -1800,50 +1499,18 @@ void eincm_destroy(eincm_ctx* ctx) {
     delete ctx;
 }
 
-// Segment list L of the staged bins (h_tilecount) at `seg` events per segment, in the order k_items emits the segments.  on_host: the
-// host cuts the segments (with the first one of every window) and uploads them; otherwise k_items has already written the L.n the
-// caller counted.  Then the longest-first order goes up and k_seg_minmax takes every segment's time range from ev_t, the copy of the
-// events the list's walkers read.
+// Segment list L of the staged bins (h_tilecount) at `seg` events per segment (cut_segments).  on_host: the host cuts the segments
+// (with the first one of every window) and uploads them; otherwise k_items has already written the L.n the caller counted.  Then
+// the longest-first order goes up and k_seg_minmax takes every segment's time range from ev_t, the copy of the events the list's
+// walkers read.
 static int build_list(eincm_ctx* c, SegList& L, int seg, bool on_host, int ntiles, const double* ev_t, int64_t N)
 {
-    // L.tspan, for the choice of the LDS window capacity (eval_begin): a tile of n events is cut into ceil(n / seg) segments, each spanning
-    // about 1 / that of the time.  Not the mean: sparse tiles (sensor noise between the edges) hold one segment that spans the WHOLE
-    // window, and their taps go to HBM one by one when the capacity follows the dense tiles (480x640 with 10^7 events at 16x16 theta:
-    // k_gather 110 -> 90 us with the larger windows).  It is the span that all but 3 % of the events stay within.
-    constexpr int K = 64;
-    int64_t by_nseg[K + 1] = {0};
     std::vector<int32_t> lens;
-    L.h_items.clear(); L.h_win_item0.clear();
-    int64_t base = 0;
-    for (size_t idx = 0; idx < c->h_tilecount.size(); ++idx) {
-        if (on_host && idx % (size_t)ntiles == 0) L.h_win_item0.push_back((int32_t)lens.size());
-        const int cnt = c->h_tilecount[idx], len = balanced_seg_len(cnt, seg);
-        if (cnt > 0) by_nseg[std::min<int64_t>(((int64_t)cnt + seg - 1) / seg, K)] += cnt;
-        for (int s0 = 0; s0 < cnt; s0 += len) {
-            lens.push_back(std::min(len, cnt - s0));
-            if (on_host) L.h_items.push_back(Item{(int32_t)(idx / ntiles), (int32_t)(idx % ntiles), (int32_t)(base + s0), lens.back(), 0.0, 0.0});
-        }
-        base += cnt;
-    }
+    cut_segments(c->h_tilecount.data(), c->h_tilecount.size(), ntiles, seg, N, on_host, L, lens);
     if ((int64_t)lens.size() > c->max_items) return fail(c, EINCM_ERR_ARG, "internal: %zu segments exceed capacity", lens.size());
     if (on_host) L.n = (int)lens.size();
     else if ((int)lens.size() != L.n) return fail(c, EINCM_ERR_ARG, "internal: segment lists disagree (%zu, %d)", lens.size(), L.n);
-    L.seg = seg;
-    L.tspan = 1.0 / K;
-    int64_t beyond = 0;
-    const int64_t allow = (int64_t)(0.03 * (double)N);
-    for (int k = 1; k <= K; ++k)                // spans 1, 1/2, 1/3, ...
-        if ((beyond += by_nseg[k]) > allow) { L.tspan = 1.0 / k; break; }
-    // the order the event kernels' workgroups take the segments in (block_to_work): by decreasing length, a stable counting sort
-    int32_t maxlen = 0;
-    for (const int32_t l : lens) maxlen = std::max(maxlen, l);
-    std::vector<int32_t> start((size_t)maxlen + 2, 0);
-    for (const int32_t l : lens) ++start[(size_t)(maxlen - l) + 1];
-    for (size_t k = 1; k < start.size(); ++k) start[k] += start[k - 1];
-    L.h_order.resize(lens.size());
-    for (size_t i = 0; i < lens.size(); ++i) L.h_order[(size_t)start[(size_t)(maxlen - lens[i])]++] = (int32_t)i;
     if (on_host) {
-        L.h_win_item0.push_back(L.n);
         if (L.d_win_item0)
             HIPCHK(c, hipMemcpyAsync(L.d_win_item0, L.h_win_item0.data(), L.h_win_item0.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         if (L.n > 0) HIPCHK(c, hipMemcpyAsync(L.d_items, L.h_items.data(), (size_t)L.n * sizeof(Item), hipMemcpyHostToDevice, c->stream));
@@ -1856,13 +1523,6 @@ static int build_list(eincm_ctx* c, SegList& L, int seg, bool on_host, int ntile
 }
 
 // ---- staging (eincm_set_windows*): check_staging -> plan_staging -> the phases, each reading the plan ----
-
-// float64 mode: the scale of a window's u64 IWE accumulator.  No pixel can exceed N_b / (2 pi) (one tap per event and pixel), so
-// 2^ishift with N_b / (2 pi) * 2^ishift < 2^62, capped at 2^52
-static int f64_ishift(int64_t n_events) {
-    const double bound = std::max(1.0, (double)n_events * 0.15915494309189535);
-    return std::min(52, 62 - (int)std::ceil(std::log2(bound)));
-}
 
 // Everything a staging refuses from its arguments alone, before it touches the context or enqueues work.
 static int check_staging(eincm_ctx* c, const StageArgs& a) {
@@ -1890,64 +1550,6 @@ static int check_staging(eincm_ctx* c, const StageArgs& a) {
                 return fail(c, EINCM_ERR_UNSUPPORTED, "window %d: %lld events exceed the fp64 mode's IWE scale (2^-40 per tap)", b, (long long)a.n_events[b]);
     }
     return EINCM_OK;
-}
-
-// Every decision of one staging, from the context and the checked arguments.  No HIP calls, no side effects; the one place where a
-// staging reads the environment (EINCM_SEG_2DOF, EINCM_PITCH_ALIGNED, EINCM_NO_SEGSORT, EINCM_NO_SPREAD: at every staging).
-static StagePlan plan_staging(const eincm_ctx* c, const StageArgs& a) {
-    StagePlan P;
-    const int H = c->H, W = c->W, n_windows = a.B, n_refs = a.R;
-    Geom& g = P.g;
-    g.H = H; g.W = W; g.R = n_refs; g.B = n_windows;
-    g.tilesX = (W + TS - 1) / TS; g.tilesY = (H + TS - 1) / TS; g.ntiles = g.tilesX * g.tilesY;
-    g.igx = (W + IG_COLS - 1) / IG_COLS; g.nig = g.igx * ((H + IG_ROWS - 1) / IG_ROWS);
-    g.pstride = std::max(g.ntiles, NSPART);
-    g.gmax_n = g.R * g.nig;
-    g.wincap = c->wincap; g.winmaxw = win_maxw(c->wincap);
-    g.wincap_a = g.wincap; g.winmaxw_a = g.winmaxw;
-    for (int b = 0; b < n_windows; ++b) P.N += a.n_events[b];
-    const int64_t N = P.N;
-
-    // Segment lengths (events per workgroup and reference time), measured on MI355X with the longest-first order of block_to_work
-    // (tools/dev_tune_seg.py, profiles/r02/segment_tuning.txt).  Per-workgroup fixed cost (window clear / flush, G-window load,
-    // reductions) favours long segments, the end of the launch (the last workgroups run on a mostly idle chip) short ones; x
-    // estimates the workgroups of a launch at 8192-event segments against the 2048 the chip holds at once.
-    //   k_gather: x >= 4000 (8 windows x 10^6 events, one window of 10^7): 16384 (96.9 -> 91.7 us, 167 -> 140 us);
-    //             x < 1000 (one 10^6-event window): 4096 (22.8 us against 25.5 with 8192 and 41 with 16384); else 8192.
-    //   k_splat:  bound by LDS atomics, it gains nothing beyond 8192 (108 us at 8192 and 16384, 122 at 4096, 186 at 2048 on the
-    //             8-window batch) and loses nothing with it on a single window (22.7 vs 23.5 us; theta grids 22.3 vs 24.5).
-    //   theta grids / dense theta: the gather walks the list with the longer segments (one 10^6-event window at 16x16: 35.8 us
-    //             with 4096, 30.3 with 8192, 28.6 with 16384; the 8-window batch 157 / 144 / 139 with 8192 / 16384 / 32768).
-    const double x_wg = ((double)N / 8192.0 + 0.5 * n_windows * g.ntiles) * n_refs;
-    const double per_tile = (double)N / ((double)n_windows * g.ntiles);
-    // Round 3: the gather's list always has long segments (what its theta-grid form wants: thtile, accumulator clear and flush per
-    // workgroup); its 2-DoF form walks a list of its own (seg_2: round-2 tuning; with tiles of several segments as seg_s below:
-    // 480x640 with 10^7 events 90 -> 82 us).
-    P.seg = c->seg > 0 ? c->seg : 16384;
-    P.seg_2 = (x_wg >= 4000.0 && per_tile < 16384.0) ? 16384 : (x_wg < 1000.0 ? 4096 : 8192);
-    if (const char* e = getenv("EINCM_SEG_2DOF")) { const int v = atoi(e); if (v >= MIN_SEG && v <= MAX_SEG) P.seg_2 = v; }
-    // (late round 3: k_splat is no longer bound by the LDS atomic unit, so its per-workgroup fixed work - 24 of 90 us on the 8-window
-    // batch: window derivation and clear 14, flush 10 - shows: 16384-event segments there, 90.1 -> 85.2 us; 104 -> 100 us at 16x16)
-    // ... but only where a tile holds about one such segment: with tiles of several segments (480x640, 10^7 events: 33 000 per tile) the long
-    // segments double the duration of EVERY workgroup and the kernel ends in a tail of few resident waves (k_splat 93 -> 137 us there).
-    // (4 windows of 10^6 events: 52.4 -> 49.7 us; 2 windows: equal; 1: 18.8 vs 19.7 the other way; one window at R = 1: 4096, 0.066 vs
-    // 0.075 ms per evaluation)
-    P.seg_s = c->seg_s > 0 ? c->seg_s : (x_wg >= 3000.0 && per_tile < 16384.0 ? 16384 : (x_wg >= 400.0 ? 8192 : 4096));
-    // beside a splat list of longer segments, the short one: the same events cut into 8192-event segments, for evaluations whose theta is
-    // too large for the windows of the long segments (twice the time span, hence twice the spread)
-    P.splat_short = P.seg_s > SEG_SHORT && N > 0;
-    // The bank-aligned LDS pitch (win_pitch) goes with the same regime - many resident windows, about one segment per tile: both event
-    // kernels 2 % faster on the bench batch; everywhere else pitch = width is the faster layout (profiles/r03/pitch_by_shape.txt: one
-    // window of 10^6 events 72 -> 62 us per evaluation, 2 x 3*10^6 143 -> 128, 480x640 with 5*10^6 173 -> 126, with 10^7 220 -> 184).
-    P.pitch = (x_wg >= 3000.0 && per_tile < 16384.0) ? 1 : 0;
-    if (const char* e = getenv("EINCM_PITCH_ALIGNED")) P.pitch = std::max(0, std::min(2, atoi(e)));
-    g.pitch_aligned = P.pitch;
-    P.sort_segments = getenv("EINCM_NO_SEGSORT") == nullptr;
-    P.spread = getenv("EINCM_NO_SPREAD") == nullptr;
-    P.host_binning = c->host_binning;
-    P.defer_constants = (a.flags & EINCM_SW_DEFER_CONSTANTS) != 0;
-    P.wide = std::any_of(a.n_events, a.n_events + n_windows, [&](int64_t n) { return n * (int64_t)n_refs < 4096; });
-    return P;
 }
 
 // The refusal of event i of window b: outside the sensor (bad_xy), or with a non-finite timestamp.  refuse_event_at: of the event at
@@ -2086,49 +1688,15 @@ static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
 static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     const StagePlan& P = c->stage;
     const Geom& g = P.g;
-    const int H = g.H, W = g.W;
-    const size_t img = (size_t)H * W;
+    const size_t img = (size_t)g.H * g.W;
     int rc = EINCM_OK;
-    c->h_tilecount.assign((size_t)a.B * g.ntiles, 0);
-    sc.sxy.resize((size_t)std::max<int64_t>(P.N, 1));
-    sc.st.resize((size_t)std::max<int64_t>(P.N, 1));
-    std::vector<int64_t> cnt((size_t)g.ntiles + 1);
-    int64_t base = 0;
-    for (int b = 0; b < a.B; ++b) {
-        const int64_t n = a.n_events[b];
-        const int16_t* x = a.xs[b]; const int16_t* y = a.ys[b]; const double* t = a.ts[b];
-        std::fill(cnt.begin(), cnt.end(), 0);
-        for (int64_t i = 0; i < n; ++i) {
-            for (int r = 0; r < a.R; ++r) sc.dtmax[b] = std::max(sc.dtmax[b], std::fabs(t[i] - a.edge_ts[b * a.R + r]));
-            if (x[i] < 0 || x[i] >= W || y[i] < 0 || y[i] >= H) return refuse_event(c, a, b, i, true);
-            if (!std::isfinite(t[i])) return refuse_event(c, a, b, i, false);
-            ++cnt[(size_t)(y[i] / TS) * g.tilesX + (x[i] / TS) + 1];
-        }
-        {   // most events on one source pixel
-            std::vector<uint32_t> pc(img, 0u);
-            for (int64_t i = 0; i < n; ++i) sc.cntmax[b] = std::max(sc.cntmax[b], ++pc[(size_t)y[i] * W + x[i]]);
-        }
-        for (int k = 0; k < g.ntiles; ++k) c->h_tilecount[(size_t)b * g.ntiles + k] = (int32_t)cnt[k + 1];
-        for (int k = 0; k < g.ntiles; ++k) cnt[k + 1] += cnt[k];
-        std::vector<int64_t> pos(cnt.begin(), cnt.end() - 1);
-        for (int64_t i = 0; i < n; ++i) {
-            const int tile = (y[i] / TS) * g.tilesX + (x[i] / TS);
-            const int64_t d = base + pos[tile]++;
-            sc.sxy[d] = (uint32_t)(uint16_t)x[i] | ((uint32_t)(uint16_t)y[i] << 16);
-            sc.st[d] = t[i];
-        }
-        base += n;
-    }
+    if (const EventRefusal r = bin_events(g, a.n_events, a.xs, a.ys, a.ts, a.edge_ts, P.N, c->h_tilecount, sc.sxy, sc.st, sc.cntmax, sc.dtmax))
+        return refuse_event(c, a, r.win, r.index, r.bad_xy);
     sc.ef.resize((size_t)a.B * a.R * img);
     for (int b = 0; b < a.B; ++b) {
         WinConst& wc = c->h_wc[b];
-        for (int r = 0; r < a.R; ++r) {
-            const double* e = a.edges[b] + (size_t)r * img;
-            float* o = sc.ef.data() + ((size_t)b * a.R + r) * img;
-            double s = 0.0, ss = 0.0, mx = 0.0;
-            for (size_t i = 0; i < img; ++i) { const float f = (float)e[i]; o[i] = f; s += (double)f; ss += (double)f * (double)f; mx = std::max(mx, std::fabs((double)f)); }
-            wc.sE[r] = s; wc.sEE[r] = ss; wc.eabs[r] = mx;
-        }
+        for (int r = 0; r < a.R; ++r)
+            edge_moments(a.edges[b] + (size_t)r * img, img, sc.ef.data() + ((size_t)b * a.R + r) * img, wc.sE[r], wc.sEE[r], wc.eabs[r]);
     }
     if (P.N > 0) {
         HIPCHK(c, hipMemcpyAsync(c->d_xy, sc.sxy.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
@@ -2193,7 +1761,7 @@ static int stage_windows(eincm_ctx* c, const StageArgs& a) {
     c->objc_valid = false;           // the zero-warp values of the objective kinds belong to the windows staged before
     c->Theta_valid = false;
     c->bfgs.begun = false;           // the BFGS state belongs to the batch it was begun for
-    c->stage = plan_staging(c, a);
+    c->stage = plan_staging(*c, a.B, a.R, a.n_events, a.flags, live_knobs().stage);
     const StagePlan& P = c->stage;
     HIPCHK(c, hipSetDevice(c->device));
     StageScratch sc;
@@ -2708,7 +2276,6 @@ int eincm_canny(eincm_ctx* c, const uint8_t* src, int n, double threshold1, doub
 }
 
 // preprocess_image (img_utils.py:131-189): host tables of the contract, then the selected stages back to back.
-static int nlm_shift(int tw) { int s = 0; while ((1 << s) < tw * tw) ++s; return s; }
 
 int eincm_preprocess_image(eincm_ctx* c, const uint8_t* src, int n, const eincm_preprocess_params* p, uint8_t* dst) {
 #pragma clang fp contract(off)
@@ -2938,22 +2505,6 @@ int eincm_gt_flow(eincm_ctx* c, const void* gt_x, const void* gt_y, int elem_byt
     return EINCM_OK;
 }
 
-// The non-zero run of every row of a resample matrix A (n_out, n_in): lo, cnt and the weights padded to the longest run.
-static int resample_runs(const std::vector<double>& A, int n_in, int n_out, std::vector<int32_t>& lo, std::vector<int32_t>& cnt,
-                         std::vector<double>& wt) {
-    lo.assign(n_out, 0); cnt.assign(n_out, 0);
-    int stride = 1;
-    for (int o = 0; o < n_out; ++o) {
-        int a = n_in, b = 0;
-        for (int i = 0; i < n_in; ++i) if (A[(size_t)o * n_in + i] != 0.0) { a = std::min(a, i); b = std::max(b, i + 1); }
-        if (a < b) { lo[o] = a; cnt[o] = b - a; stride = std::max(stride, b - a); }
-    }
-    wt.assign((size_t)n_out * stride, 0.0);
-    for (int o = 0; o < n_out; ++o)
-        for (int k = 0; k < cnt[o]; ++k) wt[(size_t)o * stride + k] = A[(size_t)o * n_in + lo[o] + k];
-    return stride;
-}
-
 // DSECDataLoader.rectify_events (dsec_loader.py:145-171) for one chunk of a recording.
 int eincm_rectify_events(eincm_ctx* c, const float* rectify_map, const int16_t* x, const int16_t* y, int64_t n, int16_t* rec_x,
                          int16_t* rec_y, uint8_t* keep, int64_t* n_kept) {
@@ -3061,27 +2612,6 @@ int eincm_flow_decode(eincm_ctx* c, const uint16_t* flow16, int n, double* flow,
     *n_bad = (int64_t)*bad;
     if (*bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a third channel that is neither 0 nor 1", *bad);
     return EINCM_OK;
-}
-
-// The tap tables of a (h, w) -> (H, W) resampling as k_flow_encode and k_flow_error read them, packed for one upload:
-// row weights | column weights | rlo | rcnt | clo | ccnt
-struct TapTables {
-    Packer tab;
-    size_t o_cw = 0, o_rlo = 0, o_rcnt = 0, o_clo = 0, o_ccnt = 0;
-    int rstride = 1, cstride = 1;
-};
-
-static void build_taps(int h, int w, int H, int W, int method, TapTables& t) {
-    std::vector<double> AH, AW, rwt, cwt;
-    std::vector<int32_t> rlo, rcnt, clo, ccnt;
-    resample_matrix(h, H, method, AH);
-    resample_matrix(w, W, method, AW);
-    t.rstride = resample_runs(AH, h, H, rlo, rcnt, rwt);
-    t.cstride = resample_runs(AW, w, W, clo, ccnt, cwt);
-    t.tab.add(rwt.data(), rwt.size() * 8);
-    t.o_cw = t.tab.add(cwt.data(), cwt.size() * 8);
-    t.o_rlo = t.tab.add(rlo.data(), (size_t)H * 4); t.o_rcnt = t.tab.add(rcnt.data(), (size_t)H * 4);
-    t.o_clo = t.tab.add(clo.data(), (size_t)W * 4); t.o_ccnt = t.tab.add(ccnt.data(), (size_t)W * 4);
 }
 
 // dsec_npz_to_png.py:84-96 for a batch of theta: bilinear scale_and_translate to the sensor and the 16-bit code, in one kernel.
@@ -3325,16 +2855,7 @@ int eincm_get_memory(eincm_ctx* c, int64_t out[4]) {
 
 int eincm_get_launch_policy(eincm_ctx* c, double* out) {
     if (!c || !out) return EINCM_ERR_ARG;
-    const StagePlan& S = c->stage;                      // the staging half: the plan of the staged batch, and its lists' time spans
-    out[EINCM_LP_SEG_GATHER] = S.seg; out[EINCM_LP_SEG_SPLAT] = S.seg_s; out[EINCM_LP_SEG_GATHER_2DOF] = S.seg_2;
-    out[EINCM_LP_SEG_SPLAT_SHORT] = S.splat_short ? SEG_SHORT : 0; out[EINCM_LP_PITCH_POLICY] = S.pitch;
-    out[EINCM_LP_SPAN_SPLAT] = c->splat.tspan; out[EINCM_LP_SPAN_GATHER] = c->gather.tspan; out[EINCM_LP_SPAN_GATHER_2DOF] = c->gather_2.tspan;
-    const bool evaluated = c->policy_evaluated;         // (never on a float64 context)
-    const EvalPlan& P = c->fl.plan;
-    out[EINCM_LP_CAP_SPLAT] = evaluated ? P.wincap : 0; out[EINCM_LP_CAP_GATHER] = evaluated ? P.wincap_a : 0;
-    out[EINCM_LP_CAP_GATHER_2DOF] = evaluated ? P.win_2.cap : 0;
-    out[EINCM_LP_PITCH_ALIGNED] = evaluated ? ((P.pitch_aligned ? 1 : 0) | (P.win_2.pal ? 2 : 0)) : 0;
-    out[EINCM_LP_SPLAT_SHORT] = evaluated && P.splat_short ? 1 : 0;
+    launch_policy(*c, c->fl.plan, c->policy_evaluated, out);
     return EINCM_OK;
 }
 

@@ -25,14 +25,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "eincm_types.h"
+
 namespace eincm {
 
-constexpr int TS = 32;            // source tile edge (pixels)
 constexpr int NT = 256;           // threads per workgroup = 4 waves of 64
 constexpr int NWAVE = NT / 64;
-constexpr int WIN_CAP_DEFAULT = 2304;   // pixels of LDS for a segment's destination window
 constexpr int WIN_CAP_MAX = 9216;
-constexpr int NXCD = 8;           // XCDs: blocks b and b+8 share an L2 (round-robin dispatch; speed only, never correctness)
 constexpr double EPSN = 2.220446049250313e-16;   // sys.float_info.epsilon (losses.py:24)
 constexpr float INV_2PI = 0.15915494309189535f;
 // LDS accumulation of the splat is u32 fixed point: on gfx950 ds_add_f32 retires ~1 lane per 3 clocks whatever the
@@ -41,7 +40,6 @@ constexpr float INV_2PI = 0.15915494309189535f;
 // with count * 0.16 * 2^k <= 2^32: k = 21 at 8192 events, 22 at 4096) the integer sum of a window pixel cannot overflow.
 // Resolution 2^-k (round to nearest, unbiased): 4.8e-7 absolute per tap at 8192 events.
 constexpr int MAX_CHUNK = 16384;   // events per splat segment (bounds the u32 sums; the fixed-point scale follows the count, fix_shift)
-constexpr int MAX_SEG = 1 << 20;   // events per segment (one window flush per segment and reference time)
 // Per-item scale 2^k, the largest power of two with count * 0.16 * 2^k <= 2^32 (k capped at 30, where the smallest
 // tap 0.0137 still keeps its full fp32 mantissa): k = 23 for 2048 events, 22 for 4096, 30 for <= 25 events — sparse
 // items are accumulated essentially exactly, dense ones with an absolute step (6e-8) below the fp32 ulp of their sums.
@@ -50,36 +48,9 @@ __device__ __forceinline__ int fix_shift(int count) {
     const int ceillog2 = (c <= 1u) ? 0 : (32 - __clz(c - 1u));
     return min(30, 32 - ceillog2);
 }
-// A tile's c events are cut into ceil(c/seg) segments of EQUAL length (rounded up to whole workgroup trips), not into
-// seg, seg, ..., remainder: the event kernels' workgroups then finish together instead of leaving a tail of short ones.
-__host__ __device__ __forceinline__ int balanced_seg_len(int c, int seg) {
-    const int nseg = (c + seg - 1) / seg;
-    if (nseg <= 1) return seg;
-    const int len = (((c + nseg - 1) / nseg + 255) / 256) * 256;
-    return len < seg ? len : seg;
-}
 constexpr float EXP_M05 = 0.6065306597126334f;   // exp(-1/2)
 
-struct Geom {
-    int H, W, R, B;
-    int tilesX, tilesY, ntiles;
-    int wincap, winmaxw;      // LDS destination-window capacity (pixels) and maximum width: the splat's segment list (items_s, "list b")
-    int wincap_a, winmaxw_a;  // the same for the gather's own list (items, "list a"): its segments are longer, so they span more time and move further
-    int nparts;               // StatParts per image written by the statistics kernel of this evaluation (ntiles or NSPART)
-    int pstride;              // StatPart slots per image: max(ntiles, NSPART)
-    int gmax_n;               // words of `gmax` per window: R * nig per-strip maxima of k_imgrad
-    unsigned long long wmask; // bit b: window b takes part in this evaluation (eincm_loss_grad_masked: a lockstep solver's converged windows
-                              // sit out; their workgroups leave at once and their outputs are not written).  Windows >= 64 always take part.
-    int igx, nig;             // k_imgrad strips per image row / per image (IG_COLS x IG_ROWS pixels each): slots of g2parts and gmax
-    int pitch_aligned;        // LDS windows of the splat's event copy at a row pitch rounded up to the 32 banks (win_pitch)
-};
-
 __device__ __forceinline__ bool win_active(const Geom& g, int b) { return b >= 64 || ((g.wmask >> b) & 1ull) != 0ull; }
-
-struct Item {                     // one segment of event work: <= seg events of one source tile of one window
-    int32_t win, tile, begin, count;
-    double t_lo, t_hi;            // time range of its events
-};
 
 struct StatPart {                 // per (window, ref, tile) partial of the image reductions
     double mn, mx, cmn, cmx;      // min, max and how many pixels attain them inside the tile
@@ -171,18 +142,8 @@ __device__ __forceinline__ int grad_shift(const WinConst& c, double gm, int R) {
     return fix64_wide_shift(2.15 * gm * c.dtmax * fmax(c.nev, 1.0) * (double)R * 4.0);
 }
 
-struct EvalParams {
-    double alpha, beta, gamma, delta;
-    int cur_pyr_lvl, contrast_kind;
-    int want_div, want_tv, use_tv_grad;
-    int h, w, identity;
-};
-
-constexpr int THETA_ARG_MAX = 128;    // doubles of theta that ride in the kernel arguments instead of an H2D copy
 struct ThetaArg { double v[THETA_ARG_MAX]; };
-constexpr int THETA_ARG_BIG = 4096;   // k_theta alone takes up to 32 KiB of theta (16x16 grids of 8 windows) in its arguments: no read of pinned host memory
 struct ThetaArgBig { double v[THETA_ARG_BIG]; };
-constexpr int THETA_ARG_MID = 512;    // ... and a 4 KiB form for one window's 16x16 grid: the launch copies its arguments twice on the host (k_theta<TA>)
 struct ThetaArgMid { double v[THETA_ARG_MID]; };
 
 struct OutScal {                  // per-window result block written by k_final
@@ -232,8 +193,6 @@ __device__ __forceinline__ double block_sum(double v, double* scratch) {
     }
     return r;
 }
-
-struct Window { int ox, oy, ww, wh; };
 
 // Destination bounding box of an item at reference time tau: source tile shifted by -v*dt for
 // v in the tile's velocity bounds and dt in the item's time range, +1 for the 3x3 taps, +1 for rounding.
@@ -341,7 +300,6 @@ __device__ __forceinline__ uint32_t fix_u32(float a, float b) { return cvt_rpi(a
 // of k_project were that latency.  A tile touches the coarse rows [ilo, ilo + ni) and columns [jlo, jlo + nj); staged when both
 // fit RS_MAXC (theta grids up to ~100 cells per axis at the usual sensors; anything else keeps the direct path).
 constexpr int RS_MAXC = 24;
-struct TileRange { int ilo, ni, jlo, nj; };     // the coarse cells a tile's pixels have weight on (host: ensure_resample)
 struct ResampleTile {
     int ilo, ni, jlo, nj;
     bool staged;
@@ -956,7 +914,6 @@ __global__ __launch_bounds__(NT) void k_iwe_finish(Geom g, unsigned long long* _
 // no per-tile meaning (they are only ever reduced over the whole image), so NSPART fat blocks per image read the image with
 // coalesced grid-stride loads and pay the fp64 cross-lane reduction once each.  grid (NSPART, R, B).
 // It is also the consumer of the u64 accumulator: converts it to the fp32 IWE stack (what every later kernel reads) and clears it.
-constexpr int NSPART = 32;
 __global__ __launch_bounds__(NT) void k_stats_stream(Geom g, unsigned long long* __restrict__ acc, float* __restrict__ iwe,
                                                       const float* __restrict__ edges, StatPart* __restrict__ parts)
 {
@@ -1055,7 +1012,6 @@ __host__ __device__ __forceinline__ double mse_from_moments(const ImgScal& s, do
 // horizontal neighbours come from the adjacent lanes by DPP wave shifts (no LDS), its vertical neighbours from the
 // previous iterations.  Lanes 0,1,62,63 and rows -2,-1,+1,+2 of a strip are halo (5x5 support of the stacked stencils).
 // ------------------------------------------------------------------------------------------------
-constexpr int IG_ROWS = 12, IG_COLS = 60, IG_NT = 256;      // rows: 16.5 / 15.7 / 16.0 us with 16 / 12 / 8 on the 8-window batch, 8.2 / 7.2 / 6.7 on one window (k_final pays for more strips)
 
 template <int CTRL> __device__ __forceinline__ float dpp_lane(float v) {       // zero where the source lane does not exist
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
@@ -1420,7 +1376,6 @@ __host__ __device__ __forceinline__ int tv_shift(int H, int W) {
     while ((double)(1ull << e) <= 256.0 * (double)H * (double)W) ++e;
     return 61 - e;
 }
-constexpr int PG_MAXC = 6;        // coarse rows / columns under one 32x32 tile that k_gather's own projection handles (16x16 theta on 260x346: 4)
 
 // One 32x32 tile of a (H,W,2) image projected onto the theta cells, cells[i,j] += sum_{y,x} AH[y,i] AW[x,j] vals[y,x]  (the adjoint of
 // theta_utils.py:25-35 restricted to the tile), by the whole workgroup.  vals: the tile as double2 in LDS, already at the cells'

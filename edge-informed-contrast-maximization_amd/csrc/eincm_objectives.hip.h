@@ -20,17 +20,6 @@
 
 namespace eincm {
 
-struct ObjGeom {
-    int th, tw;          // tile size
-    int nty, ntx;        // whole tiles per column / row (>= 1)
-    int ncells;          // nty * ntx
-    int ck, rk;          // contrast kind (0..3), correlation kind (0..3)
-    int need;            // OBJ_NEED_* bits: which stencil sums k_obj_parts forms
-};
-constexpr int OBJ_NEED_TILE_GM = 1;     // tile-local Scharr energy          (adaptive_grad_mag)
-constexpr int OBJ_NEED_GM = 2;          // whole-image Scharr energy of I    (grad_mag, joint_contrast)
-constexpr int OBJ_NEED_JOINT = 4;       // cross terms with S E and S 1      (joint_contrast)
-
 // per-cell partials: [0..3] min, #min, max, #max; [4..7] sum I, I^2, E I, E; [8..12] over the whole tile: sum I, I^2, E I, E, E^2;
 // [13] tile-local sum |S_t I|^2; [14] sum |S I|^2; [15] sum S I . S E; [16] sum S I . S 1; [17] sum |S E|^2; [18] sum S E . S 1;
 // [19] sum |S 1|^2; [20] sum E^2

@@ -1,0 +1,79 @@
+// eincm_types.h — the plain types and constants the kernels (eincm_kernels.hip.h, eincm_objectives.hip.h) share with the host's
+// planning (eincm_plan.h).  Plain C++17: no HIP header and no device code, so a compiler that knows no HIP can build what the host
+// decides with them.  Layouts, field order and values are the kernels' argument layouts: they do not change here.
+#pragma once
+#include <stdint.h>
+
+// The one function both sides run: __host__ __device__ under hipcc, a plain inline function anywhere else.
+#if defined(__HIPCC__)
+#define EINCM_HD __host__ __device__ inline __attribute__((always_inline))
+#else
+#define EINCM_HD inline
+#endif
+
+namespace eincm {
+
+constexpr int TS = 32;            // source tile edge (pixels)
+constexpr int WIN_CAP_DEFAULT = 2304;   // pixels of LDS for a segment's destination window
+constexpr int NXCD = 8;           // XCDs: blocks b and b+8 share an L2 (round-robin dispatch; speed only, never correctness)
+constexpr int MAX_SEG = 1 << 20;   // events per segment (one window flush per segment and reference time)
+// A tile's c events are cut into ceil(c/seg) segments of EQUAL length (rounded up to whole workgroup trips), not into
+// seg, seg, ..., remainder: the event kernels' workgroups then finish together instead of leaving a tail of short ones.
+EINCM_HD int balanced_seg_len(int c, int seg) {
+    const int nseg = (c + seg - 1) / seg;
+    if (nseg <= 1) return seg;
+    const int len = (((c + nseg - 1) / nseg + 255) / 256) * 256;
+    return len < seg ? len : seg;
+}
+
+struct Geom {
+    int H, W, R, B;
+    int tilesX, tilesY, ntiles;
+    int wincap, winmaxw;      // LDS destination-window capacity (pixels) and maximum width: the splat's segment list (items_s, "list b")
+    int wincap_a, winmaxw_a;  // the same for the gather's own list (items, "list a"): its segments are longer, so they span more time and move further
+    int nparts;               // StatParts per image written by the statistics kernel of this evaluation (ntiles or NSPART)
+    int pstride;              // StatPart slots per image: max(ntiles, NSPART)
+    int gmax_n;               // words of `gmax` per window: R * nig per-strip maxima of k_imgrad
+    unsigned long long wmask; // bit b: window b takes part in this evaluation (eincm_loss_grad_masked: a lockstep solver's converged windows
+                              // sit out; their workgroups leave at once and their outputs are not written).  Windows >= 64 always take part.
+    int igx, nig;             // k_imgrad strips per image row / per image (IG_COLS x IG_ROWS pixels each): slots of g2parts and gmax
+    int pitch_aligned;        // LDS windows of the splat's event copy at a row pitch rounded up to the 32 banks (win_pitch)
+};
+
+struct Item {                     // one segment of event work: <= seg events of one source tile of one window
+    int32_t win, tile, begin, count;
+    double t_lo, t_hi;            // time range of its events
+};
+
+struct EvalParams {
+    double alpha, beta, gamma, delta;
+    int cur_pyr_lvl, contrast_kind;
+    int want_div, want_tv, use_tv_grad;
+    int h, w, identity;
+};
+
+constexpr int THETA_ARG_MAX = 128;    // doubles of theta that ride in the kernel arguments instead of an H2D copy
+constexpr int THETA_ARG_BIG = 4096;   // k_theta alone takes up to 32 KiB of theta (16x16 grids of 8 windows) in its arguments: no read of pinned host memory
+constexpr int THETA_ARG_MID = 512;    // ... and a 4 KiB form for one window's 16x16 grid: the launch copies its arguments twice on the host (k_theta<TA>)
+
+struct Window { int ox, oy, ww, wh; };
+
+struct TileRange { int ilo, ni, jlo, nj; };     // the coarse cells a tile's pixels have weight on (host: build_resample)
+
+constexpr int NSPART = 32;        // blocks per image of k_stats_stream
+constexpr int IG_ROWS = 12, IG_COLS = 60, IG_NT = 256;      // rows: 16.5 / 15.7 / 16.0 us with 16 / 12 / 8 on the 8-window batch, 8.2 / 7.2 / 6.7 on one window (k_final pays for more strips)
+constexpr int PG_MAXC = 6;        // coarse rows / columns under one 32x32 tile that k_gather's own projection handles (16x16 theta on 260x346: 4)
+
+// the selectable objective kinds (eincm_objectives.hip.h)
+struct ObjGeom {
+    int th, tw;          // tile size
+    int nty, ntx;        // whole tiles per column / row (>= 1)
+    int ncells;          // nty * ntx
+    int ck, rk;          // contrast kind (0..3), correlation kind (0..3)
+    int need;            // OBJ_NEED_* bits: which stencil sums k_obj_parts forms
+};
+constexpr int OBJ_NEED_TILE_GM = 1;     // tile-local Scharr energy          (adaptive_grad_mag)
+constexpr int OBJ_NEED_GM = 2;          // whole-image Scharr energy of I    (grad_mag, joint_contrast)
+constexpr int OBJ_NEED_JOINT = 4;       // cross terms with S E and S 1      (joint_contrast)
+
+}  // namespace eincm

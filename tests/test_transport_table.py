@@ -22,10 +22,11 @@ def _const(src, name):
 
 
 def limits():
-    kern = _read('csrc', 'eincm_kernels.hip.h')
+    types = _read('csrc', 'eincm_types.h')           # the argument blocks' sizes, shared by the kernels and the planning
+    plan = _read('csrc', 'eincm_plan.h')             # plan_eval decides where theta rides
     api = _read('csrc', 'eincm_api.hip')
-    lim = {n: _const(kern, n) for n in ('THETA_ARG_MAX', 'THETA_ARG_MID', 'THETA_ARG_BIG')}
-    lim['ZERO_COPY_MAX'] = _const(api, 'ZERO_COPY_MAX')
+    lim = {n: _const(types, n) for n in ('THETA_ARG_MAX', 'THETA_ARG_MID', 'THETA_ARG_BIG')}
+    lim['ZERO_COPY_MAX'] = _const(plan, 'ZERO_COPY_MAX')
     # enqueue_result_copies: the gradient comes back in pieces from nd >= 1 << k, so the last nd of one copy is (1 << k) - 1
     pieces = set(re.findall(r'want_grad && \(size_t\)g\.B \* nth >= \(\(size_t\)1 << (\d+)\)', api))
     assert len(pieces) == 1, f'the piece threshold of enqueue_result_copies not found (or ambiguous): {pieces}'
