@@ -34,6 +34,7 @@ BFGS_S_DPHI0, BFGS_S_GMAX, BFGS_S_PNORM, BFGS_S_XMAX, BFGS_S_PMAX, BFGS_S_GNORM,
 BFGS_NS = 8
 LBFGS_MAX_HISTORY = 16                                               # EINCM_LBFGS_MAX_HISTORY
 LBFGS_SCALES = {'identity': 0, 'last_pair': 1}                       # EINCM_LBFGS_SCALE_*
+MOTION_MAX_COEFFS, MOTION_NQ = 12, 12                                # EINCM_MOTION_MAX_COEFFS, EINCM_MOTION_NQ
 
 
 class Params(C.Structure):
@@ -89,6 +90,11 @@ FLOW_ERROR_THRESHOLDS = (1, 2, 3, 5, 10, 20)          # the N of A{N}PE (flow_ev
 class FlowErrorOut(C.Structure):
     _fields_ = [('n_ee', C.c_int64), ('n_pred', C.c_int64), ('n_gt', C.c_int64), ('n_over', C.c_int64 * 6),
                 ('sum_ee', C.c_double), ('sum_ree', C.c_double), ('aee', C.c_double), ('aree', C.c_double), ('anpe', C.c_double * 6)]
+
+
+class MotionModel(C.Structure):            # eincm_motion_model: M is (12, K) row major in its first 12 K entries
+    _fields_ = [('n_coeffs', C.c_int32), ('cx', C.c_double), ('cy', C.c_double), ('scale', C.c_double),
+                ('M', C.c_double * (MOTION_NQ * MOTION_MAX_COEFFS))]
 
 
 class Timings(C.Structure):
@@ -178,6 +184,10 @@ SIGNATURES = [
     # ... in the limited-memory form
     ('eincm_lbfgs_begin', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     ('eincm_lbfgs_history_ptrs', C.c_int, [_P] + [C.POINTER(C.c_void_p)] * 6 + [C.POINTER(C.c_int)]),
+    # parametric motion-field models
+    ('eincm_set_motion_model', C.c_int, [_P, C.POINTER(MotionModel)]),
+    ('eincm_loss_grad_motion', C.c_int, [_P, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Aux)]),
+    ('eincm_motion_field', C.c_int, [_P, C.c_void_p, C.c_void_p]),
 ]
 
 _lib = None

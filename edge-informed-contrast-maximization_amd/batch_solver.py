@@ -912,6 +912,28 @@ def minimize_thetas(engine, theta0, params, maxiter, gtol, hessian='auto', histo
     return res
 
 
+def minimize_motion(engine, model, coeffs0, params, maxiter, gtol, callbacks=None, active=None, wolfe2_fallback=True, stats=None):
+    """B lockstep BFGS minimisations of the engine's objective over the coefficients of a parametric motion-field model
+    (motion.MotionModel).  coeffs0: (B, K); K <= 12, so every window takes the host's bit-exact SciPy update
+    (LockstepBFGS) over ``engine.loss_grad_motion``.  ``callbacks``, ``active``, ``wolfe2_fallback`` and ``stats`` as in minimize_thetas.
+    Returns a list of scipy OptimizeResult (None for inactive windows), x the coefficients (K,)."""
+    coeffs0 = np.asarray(coeffs0, dtype=np.float64)
+    if coeffs0.ndim != 2 or coeffs0.shape[1] != model.n_coeffs:
+        raise ValueError(f'coeffs0 must be (B,{model.n_coeffs}), got {coeffs0.shape}')
+    if engine.motion_model is not model:
+        engine.set_motion_model(model)
+
+    def fun_batch(X, mask):
+        v, g, _ = engine.loss_grad_motion(X, params, active=mask)
+        return v, g
+    drv = LockstepBFGS(fun_batch, coeffs0, maxiter, gtol, callbacks=callbacks, active=active, wolfe2_fallback=wolfe2_fallback)
+    res = drv.run()
+    if stats is not None:
+        stats['n_batch_evals'] = stats.get('n_batch_evals', 0) + drv.n_batch_evals
+        stats['n_window_evals'] = stats.get('n_window_evals', 0) + drv.n_window_evals
+    return res
+
+
 def _info(res):
     return ScipyMinimizeInfo(fun_val=float(res.fun), success=bool(res.success), status=int(res.status), iter_num=int(res.nit),
                              hess_inv=getattr(res, 'hess_inv', None), num_fun_eval=int(res.nfev), num_jac_eval=int(res.njev),

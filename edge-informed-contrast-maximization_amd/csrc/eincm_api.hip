@@ -33,6 +33,7 @@
 #include "eincm_floweval.hip.h"
 #include "eincm_bfgs.hip.h"
 #include "eincm_lbfgs.hip.h"
+#include "eincm_motion.hip.h"
 
 using namespace eincm;
 
@@ -315,6 +316,15 @@ struct eincm_ctx : PlanCtx {
         double* part_dir() const { return part.p + (size_t)B * lbfgs_chunks(n) * lbfgs_nq(m); }
         double* part_red() const { return part_dir() + (size_t)B * lbfgs_chunks(n) * LBFGS_NP; }
     } bfgs;
+
+    // parametric motion-field models (eincm_motion.hip.h): nothing is allocated before the first call that needs it
+    struct {
+        bool set = false;                    // eincm_set_motion_model handed a model over
+        eincm_motion_model model{};
+        Grow<double> Theta;                  // (maxB, H, W, 2) the expanded field: the device-resident theta of the evaluation
+        Grow<double, true> h_part;           // pinned: the moment partials (maxB, MOTION_PARTS, 12) | q of every window (maxB, 12)
+        double* h_q(int maxB) const { return h_part.p + (size_t)maxB * MOTION_PARTS * MOTION_NQ; }
+    } motion;
 };
 
 namespace {
@@ -3150,6 +3160,113 @@ int eincm_bfgs_fetch(eincm_ctx* c, double* x, double* g, double* hess_inv) {
     if (hess_inv) HIPCHK(c, hipMemcpyAsync(hess_inv, s.H.p, nv * s.n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return EINCM_OK;
+}
+
+// ---- parametric motion-field models ----
+static int motion_ready(eincm_ctx* c, const char* who, const double* coeffs) {
+    if (c->fp64)
+        return fail(c, EINCM_ERR_UNSUPPORTED, "%s is not supported in fp64 mode (EINCM_CF_FP64): the device-resident evaluation does not exist there", who);
+    if (!c->motion.set) return fail(c, EINCM_ERR_STATE, "%s: no motion model set (eincm_set_motion_model)", who);
+    if (const int rc = eval_ready(c, who)) return rc;
+    if (c->device_results) return fail(c, EINCM_ERR_STATE, "%s: eincm_set_device_results is on (the split finishing half owns the results)", who);
+    if (!c->fl.idle()) return fail(c, EINCM_ERR_STATE, "%s: an evaluation is in flight", who);
+    if (!coeffs) return fail(c, EINCM_ERR_ARG, "%s: null pointer argument", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, ensure(c, c->motion.Theta, (size_t)c->maxB * c->H * c->W * 2));
+    HIPCHK(c, ensure(c, c->motion.h_part, (size_t)c->maxB * (MOTION_PARTS + 1) * MOTION_NQ, true));
+    return EINCM_OK;
+}
+
+// q = M c of the mask's windows and the launch of k_motion_expand; returns the bound of |Theta| over those windows (NaN: unknown).
+// The caller's frame drains the stream: with more than MOTION_ARG_WINDOWS windows the kernel reads q from the pinned block.
+static double motion_expand(eincm_ctx* c, const double* coeffs, unsigned long long wmask, MotionGeom& mg) {
+    auto& mo = c->motion;
+    const Geom& g = c->g;
+    const int K = mo.model.n_coeffs;
+    mg = MotionGeom{g.H, g.W, g.B, wmask, mo.model.cx, mo.model.cy, mo.model.scale};
+    double mm[MOTION_NM];
+    motion_monomial_bounds(mo.model, g.H, g.W, mm);
+    const bool use_arg = g.B <= MOTION_ARG_WINDOWS;
+    static thread_local MotionQArg qarg;
+    double* qs = use_arg ? qarg.q : mo.h_q(c->maxB);
+    double vmax = 0.0;
+    for (int b = 0; b < g.B; ++b) {
+        double* q = qs + (size_t)b * MOTION_NQ;
+        if (b < 64 && !((wmask >> b) & 1ull)) { for (int j = 0; j < MOTION_NQ; ++j) q[j] = 0.0; continue; }
+        motion_q(mo.model, coeffs + (size_t)b * K, q);
+        const double v = motion_abs_bound(q, mm);
+        if (!(v <= vmax)) vmax = v;                // (a NaN ends up in vmax: unknown)
+    }
+    const int npix = g.H * g.W;
+    hipLaunchKernelGGL(k_motion_expand, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)g.B), dim3(NT), 0, c->stream, mg, use_arg ? 1 : 0, qarg,
+                       (const double*)mo.h_q(c->maxB), reinterpret_cast<double2*>(mo.Theta.p));
+    return vmax;
+}
+
+int eincm_set_motion_model(eincm_ctx* c, const eincm_motion_model* model) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!model) { c->motion.set = false; return EINCM_OK; }
+    if (const char* what = motion_model_error(*model)) return fail(c, EINCM_ERR_ARG, "eincm_set_motion_model: %s", what);
+    c->motion.model = *model;
+    c->motion.set = true;
+    return EINCM_OK;
+}
+
+int eincm_motion_field(eincm_ctx* c, const double* coeffs, double* Theta) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = motion_ready(c, "eincm_motion_field", coeffs)) return rc;
+    if (!Theta) return fail(c, EINCM_ERR_ARG, "eincm_motion_field: null pointer argument");
+    OneShot op(c);
+    op.pending = true;                             // (motion_expand launches on the stream itself)
+    MotionGeom mg;
+    (void)motion_expand(c, coeffs, ~0ull, mg);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, op.down(Theta, c->motion.Theta.p, (size_t)c->g.B * c->g.H * c->g.W * 2 * sizeof(double)));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+int eincm_loss_grad_motion(eincm_ctx* c, const double* coeffs, const eincm_params* p, const uint8_t* active, double* value, double* grad,
+                           eincm_aux* aux) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = motion_ready(c, "eincm_loss_grad_motion", coeffs)) return rc;
+    if (!p || !value) return fail(c, EINCM_ERR_ARG, "eincm_loss_grad_motion: null pointer argument");
+    auto& mo = c->motion;
+    const Geom& g = c->g;
+    const int K = mo.model.n_coeffs;
+    unsigned long long wmask = ~0ull;
+    if (active) { wmask = 0ull; for (int b = 0; b < g.B && b < 64; ++b) if (active[b]) wmask |= 1ull << b; }
+    // the dense evaluation needs no resampling method: the field is at sensor size
+    eincm_params pe = *p;
+    pe.method = EINCM_METHOD_BILINEAR;
+    FlightGuard guard(c);                          // from the first launch on, every exit drains the stream
+    MotionGeom mg;
+    const double vmax = motion_expand(c, coeffs, wmask, mg);
+    HIPCHK(c, hipGetLastError());
+    // the masked dense evaluation with theta = the field in HBM; its gradient stays in the engine's block for k_motion_moments
+    int rc = eval_begin(c, nullptr, g.H, g.W, &pe, grad != nullptr, active, DevIo{mo.Theta.p, nullptr, std::isfinite(vmax) ? vmax : -1.0});
+    if (!rc) rc = eval_end_launch(c);
+    if (rc) return rc;
+    if (grad) {
+        hipLaunchKernelGGL(k_motion_moments, dim3((unsigned)MOTION_PARTS, (unsigned)g.B), dim3(NT), 0, c->stream, mg,
+                           reinterpret_cast<const double2*>(c->d_grad), mo.h_part.p);
+        HIPCHK(c, hipGetLastError());
+    }
+    rc = guard.keep(eval_end_collect(c, value, nullptr, aux));                 // the one synchronisation
+    if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
+    if (grad) {
+        bool nonfinite = false;
+        for (int b = 0; b < g.B; ++b) {
+            double* gb = grad + (size_t)b * K;
+            if (window_sat_out(g, b)) { for (int k = 0; k < K; ++k) gb[k] = 0.0; continue; }
+            double mu[MOTION_NQ];
+            motion_sum_partials(mo.h_part.p + (size_t)b * MOTION_PARTS * MOTION_NQ, MOTION_PARTS, mu);
+            motion_project(mo.model, mu, gb);
+            if (copy_scan_finite(nullptr, gb, (size_t)K)) nonfinite = true;
+        }
+        if (nonfinite && rc == EINCM_OK) rc = fail(c, EINCM_ERR_NONFINITE, "loss or gradient is not finite");
+    }
+    return rc;
 }
 
 }  // extern "C"

@@ -418,6 +418,33 @@ def check_flow_eval_thetas(thetas, n_windows, sensor_size, method):
     return np.ascontiguousarray(t, dtype=np.float64), L.METHODS[method]
 
 
+def check_motion_model(model, sensor_size):
+    """A motion.MotionModel for this sensor (or None, which clears the engine's model); anything else is a ValueError."""
+    if model is None:
+        return None
+    from .motion import MotionModel
+    if not isinstance(model, MotionModel):
+        raise ValueError(f'model must be a motion.MotionModel or None, got {type(model).__name__}')
+    if tuple(model.sensor_size) != tuple(int(s) for s in sensor_size):
+        raise ValueError(f'the model was built for sensor size {model.sensor_size}, the engine has {tuple(sensor_size)}')
+    return model
+
+
+def check_motion_coeffs(coeffs, n_windows, model):
+    """coeffs as a C-contiguous float64 (B, K) array; (K,) stands for it when B == 1."""
+    if model is None:
+        raise ValueError('no motion model set (Engine.set_motion_model)')
+    c = np.asarray(coeffs)
+    if c.dtype.kind not in 'fiu':
+        raise ValueError(f'coeffs must be numeric, got dtype {c.dtype}')
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if c.ndim == 1 and n_windows == 1:
+        c = c[None]
+    if c.shape != (n_windows, model.n_coeffs):
+        raise ValueError(f'coeffs must be ({n_windows},{model.n_coeffs}), got {np.shape(coeffs)}')
+    return c
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                 full_aux=False, correlation_kind='mse'):
     """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
@@ -468,6 +495,7 @@ class Engine:
         self.splat_window = L.DEFAULT_SPLAT_WINDOW
         self._io = {}                      # (h, w) -> staging buffers of loss_grad with their addresses
         self.flow_eval_windows = 0         # windows of the staged flow evaluation (flow_eval_stage)
+        self.motion_model = None           # the motion.MotionModel of loss_grad_motion / motion_field (set_motion_model)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -658,6 +686,30 @@ class Engine:
                                               -1.0 if theta_abs_max is None else float(theta_abs_max), _dp(value),
                                               C.c_void_p(grad.data_ptr()) if want_grad else None, aux)
         return self._collect(rc, value, grad[0] if want_grad and theta.dim() == 3 else grad, aux, allow_nonfinite)
+
+    # -- parametric motion-field models: the unknowns are K coefficients per window --------------------------
+    def set_motion_model(self, model):
+        """model: a motion.MotionModel built for this sensor size, or None to clear it."""
+        model = check_motion_model(model, (self.H, self.W))
+        self._check(self._lib.eincm_set_motion_model(self._ctx, None if model is None else C.byref(model.as_struct())))
+        self.motion_model = model
+
+    def loss_grad_motion(self, coeffs, params, want_grad=True, want_aux=False, allow_nonfinite=True, active=None):
+        """coeffs: (B,K), or (K,) when B == 1.  Returns (value (B,), grad (B,K) | None, aux list | None): the loss of the field
+        model.field(coeffs) and its gradient with respect to the coefficients, the TV term's share included.  ``active`` as in loss_grad."""
+        c = check_motion_coeffs(coeffs, self.B, self.motion_model)
+        act, p_act = self._active_ptr(active)
+        value, grad, aux = self._outputs(c.shape, want_grad, want_aux)
+        rc = self._lib.eincm_loss_grad_motion(self._ctx, c.ctypes.data, C.byref(params), p_act, value.ctypes.data,
+                                              grad.ctypes.data if want_grad else None, aux)
+        return self._collect(rc, value, grad, aux, allow_nonfinite)
+
+    def motion_field(self, coeffs):
+        """Theta (B,H,W,2) of coeffs (B,K), expanded on the GPU: array_equal to model.field(coeffs)."""
+        c = check_motion_coeffs(coeffs, self.B, self.motion_model)
+        out = np.empty((self.B, self.H, self.W, 2), dtype=np.float64)
+        self._check(self._lib.eincm_motion_field(self._ctx, c.ctypes.data, out.ctypes.data))
+        return out
 
     # -- BFGS with its state in HBM (DESIGN.md section 17): the host sees scalars, the vectors and the inverse Hessian stay on the GPU ----
     def _bfgs_alpha(self, alpha):

@@ -9,7 +9,8 @@ so the hydra plugin point (configs/theta_loss_func/default.yaml:1-2, ``_target_:
 can name this module instead.  The reference differentiates ``loss_func`` with JAX inside jaxopt; a HIP
 engine cannot be traced, so the gradient is exposed explicitly as ``value_and_grad_loss_func`` /
 ``value_and_grad_handover_loss_func`` (what jax.value_and_grad would return) and consumed by
-``solver.ScipyMinimize``.
+``solver.ScipyMinimize``.  ``motion_loss_func`` / ``value_and_grad_motion_loss_func`` are the same callables over the coefficients of
+a parametric motion-field model (``motion.MotionModel``, passed as ``model=``) in place of theta.
 
 The event window is staged on the GPU once and reused for every evaluation, like the reference's closed-over
 device-resident ``*args``: engines are cached by the identity of the (xs, ys, ts, edges, edge_ts) arrays.  JAX arrays are
@@ -122,6 +123,35 @@ def loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
     eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
     v, _, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=False, want_aux=True)
+    return float(v[0]), _aux_dict(eng, aux[0], True)
+
+
+def _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size):
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
+    if eng.motion_model is not model:
+        eng.set_motion_model(model)
+    return eng
+
+
+def value_and_grad_motion_loss_func(coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
+                                    scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, full_aux=False,
+                                    aux_arrays=False, correlation_kind='mse', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW,
+                                    precision='fp32', *, model):
+    """((final_loss, aux_info), grad (K,)) of loss_func on the field model.field(coeffs) of a motion.MotionModel, differentiated
+    with respect to the coefficients.  The field is at sensor size: the scaling method is not read."""
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux, correlation_kind)
+    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size)
+    v, g, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=True, want_aux=True)
+    return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
+
+
+def motion_loss_func(coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
+                     scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse',
+                     tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32', *, model):
+    """(final_loss, aux_info) of loss_func on model.field(coeffs); forward only, every aux entry evaluated."""
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
+    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size)
+    v, _, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=False, want_aux=True)
     return float(v[0]), _aux_dict(eng, aux[0], True)
 
 

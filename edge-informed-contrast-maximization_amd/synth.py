@@ -50,16 +50,21 @@ def _bilinear_field(grid, H, W):
 def make_window(seed, sensor_size, n_events, n_refs, flow='constant', flow_mag=20.0, noise_frac=0.10,
                 jitter_px=0.5, n_segments=64, n_circles=16):
     """Return a dict with xs, ys (int16), ts (float64, sorted), edges (R,H,W) float64 in [0,1],
-    edge_ts (R,) float64 and flow_gt (H,W,2) float64 (displacement over the unit window)."""
+    edge_ts (R,) float64 and flow_gt (H,W,2) float64 (displacement over the unit window).  flow: 'constant', 'smooth', 'zero'
+    or an (H,W,2) array that is taken as the ground-truth flow itself (flow_mag is not read then)."""
     H, W = sensor_size
     rng = np.random.default_rng(seed)
-    if flow == 'constant':
+    if isinstance(flow, str) and flow == 'constant':
         v = rng.uniform(-flow_mag, flow_mag, 2)
         flow_gt = np.broadcast_to(v, (H, W, 2)).copy()
-    elif flow == 'smooth':
+    elif isinstance(flow, str) and flow == 'smooth':
         flow_gt = _bilinear_field(rng.uniform(-flow_mag, flow_mag, (16, 16, 2)), H, W)
-    elif flow == 'zero':
+    elif isinstance(flow, str) and flow == 'zero':
         flow_gt = np.zeros((H, W, 2))
+    elif isinstance(flow, np.ndarray):                 # the caller's field, e.g. motion.MotionModel.field(c)
+        if flow.shape != (H, W, 2) or not np.isfinite(flow).all():
+            raise ValueError(f'a flow array must be a finite ({H}, {W}, 2) field, got {flow.shape}')
+        flow_gt = np.array(flow, dtype=np.float64)
     else:
         raise ValueError(f'unknown flow kind {flow!r}')
 

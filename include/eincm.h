@@ -29,7 +29,7 @@ extern "C" {
                                * 6: eincm_get_launch_policy; added since without a new version: eincm_rectify_events, eincm_remap_cubic, eincm_flow_decode,
                                *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory,
                                *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas), eincm_lbfgs_* (that BFGS with a limited-memory
-                               *    inverse Hessian) */
+                               *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -578,6 +578,35 @@ int eincm_lbfgs_begin(eincm_ctx* ctx, const double* x0_host, int h, int w, const
  * the int32 ring head (the oldest pair's slot) and count (n_windows each): inspection and tests. */
 int eincm_lbfgs_history_ptrs(eincm_ctx* ctx, void** s_dptr, void** y_dptr, void** d_dptr, void** delta_dptr, void** head_dptr,
                              void** count_dptr, int* history);
+
+/* ---- Parametric motion-field models as a theta mode --------------------------------------------------------
+ * The unknowns of a window are K <= 12 coefficients c of a polynomial motion field of degree <= 2 instead of a theta grid.  With the
+ * normalised coordinates u = (x - cx) / scale, v = (y - cy) / scale and the monomials m = [1, u, v, u u, u v, v v], q = M c (M row
+ * major (12, K), a left-to-right sum over k) gives
+ *     Theta_x(x, y) = ((((q0 m0 + q1 m1) + q2 m2) + q3 m3) + q4 m4) + q5 m5,     Theta_y likewise from q6 .. q11,
+ * in px per unit time: every product rounded, the sums left to right, u u, u v, v v rounded once each.  The evaluation is the dense
+ * device-resident one (eincm_loss_grad_device) on that field; the gradient is M^T mu with the moments mu_j = sum_pix m_j dL/dTheta_x
+ * (j < 6) or m_(j-6) dL/dTheta_y, ordered float64 sums: the same bits on every call and in every context.
+ * Refusals: EINCM_ERR_ARG for n_coeffs outside 1 .. EINCM_MOTION_MAX_COEFFS, a non-finite M, cx or cy, a scale that is not a positive
+ * finite number, a null pointer; EINCM_ERR_STATE with no model set, no staged windows, an evaluation in flight or
+ * eincm_set_device_results on; EINCM_ERR_UNSUPPORTED in an EINCM_CF_FP64 context (it has no device-resident evaluation). */
+#define EINCM_MOTION_MAX_COEFFS 12
+#define EINCM_MOTION_NQ 12              /* polynomial coefficients q of the two components */
+typedef struct eincm_motion_model {
+    int32_t n_coeffs;                   /* K */
+    double cx, cy, scale;               /* the centre (principal point) in px and the normalising length (focal length) in px */
+    double M[EINCM_MOTION_NQ * EINCM_MOTION_MAX_COEFFS];   /* (12, K) row major: the first 12 K entries are read */
+} eincm_motion_model;
+/* The model of every later eincm_loss_grad_motion / eincm_motion_field (copied); NULL clears it. */
+int eincm_set_motion_model(eincm_ctx* ctx, const eincm_motion_model* model);
+/* Loss and gradient with respect to the coefficients.  coeffs (n_windows, K) and grad (n_windows, K) or NULL on the host; active
+ * (n_windows) bytes or NULL: windows outside it get value NaN and gradient 0, as eincm_loss_grad_masked gives.  p->method is not read
+ * (the field is at sensor size); the TV term's share is in the gradient.  EINCM_ERR_NONFINITE as eincm_loss_grad_device (the outputs
+ * are written).  eincm_get_scaled_theta afterwards returns the field. */
+int eincm_loss_grad_motion(eincm_ctx* ctx, const double* coeffs, const eincm_params* p, const uint8_t* active, double* value, double* grad,
+                           eincm_aux* aux);
+/* The field alone: Theta (n_windows, H, W, 2) on the host. */
+int eincm_motion_field(eincm_ctx* ctx, const double* coeffs, double* Theta);
 
 #ifdef __cplusplus
 }

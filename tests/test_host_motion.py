@@ -1,0 +1,177 @@
+"""The host's rules of the parametric motion-field models (csrc/eincm_motion.h: validation, q = M c, the bound of |Theta|, the order
+of the partial sums, M^T mu) on the CPU.
+
+tests/host/motion_check.cpp is built once per session with the address and undefined-behaviour sanitizers, exactly as
+tests/test_host_plan.py builds plan_check, and run once, as a child process, over every case of this module; nothing is preloaded.
+Its outputs equal the numpy witness (motion.MotionModel) bit for bit, and its refusals are those of include/eincm.h."""
+import importlib
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import _motion_cases as MC
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, 'edge-informed-contrast-maximization_amd', 'csrc')
+SANITIZE = ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all']
+motion = importlib.import_module('edge-informed-contrast-maximization_amd.motion')
+
+KINDS = ('translation', 'similarity', 'affine', 'quadratic', 'rotation', 'polynomial2', 'zoom')
+SHAPES = ((5, 7), (37, 53), (480, 640))
+PARTS = 64
+
+
+def _compiler():
+    rocm = os.environ.get('ROCM_PATH', '/opt/rocm')
+    for cxx in ('g++', os.path.join(rocm, 'llvm', 'bin', 'clang++'), os.path.join(rocm, 'lib', 'llvm', 'bin', 'clang++')):
+        if shutil.which(cxx):
+            return shutil.which(cxx)
+    raise AssertionError('neither g++ nor the ROCm clang++ found')
+
+
+@pytest.fixture(scope='session')
+def motion_check(tmp_path_factory):
+    """Path of the sanitized checker."""
+    exe = str(tmp_path_factory.mktemp('motion_check') / 'motion_check')
+    cxx = _compiler()
+    # (g++ links the sanitizers' runtimes into the program, as clang++ does by default: the program needs nothing preloaded)
+    static = ['-static-libasan', '-static-libubsan'] if os.path.basename(cxx) == 'g++' else []
+    cmd = [cxx, '-std=c++17', '-Wall', '-Wextra', '-Werror'] + SANITIZE + static + [
+        '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-o', exe, os.path.join(ROOT, 'tests', 'host', 'motion_check.cpp')]
+    print(' '.join(cmd))
+    assert '-fsanitize=address,undefined' in cmd and '-fno-sanitize-recover=all' in cmd
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
+
+
+# ---- the cases: name -> input line, collected when the module is imported; one run of the checker answers all of them ----
+CASES = {}
+
+
+def _case(name, *tokens):
+    assert name not in CASES, name
+    CASES[name] = ' '.join(str(int(t)) if isinstance(t, (bool, int, np.integer)) else repr(float(t)) for t in tokens[1:])
+    CASES[name] = tokens[0] + ' ' + CASES[name]
+    return name
+
+
+def _model_tokens(m):
+    return (m.n_coeffs, m.cx, m.cy, m.scale, *m.matrix.reshape(-1).tolist())
+
+
+@pytest.fixture(scope='module')
+def out(motion_check, tmp_path_factory):
+    """name -> the checker's line for that case, split at ' |' into lists of words."""
+    path = tmp_path_factory.mktemp('motion_cases') / 'cases.txt'
+    path.write_text('\n'.join(CASES.values()) + '\n')
+    r = subprocess.run([motion_check, str(path)], capture_output=True, text=True)
+    assert r.returncode == 0 and not r.stderr, f'the sanitized checker failed (exit {r.returncode}):\n{r.stderr[-4000:]}'
+    lines = r.stdout.splitlines()
+    assert len(lines) == len(CASES)
+    res = {}
+    for (name, inp), line in zip(CASES.items(), lines):
+        word, _, rest = line.partition(' ')
+        assert word == inp.split()[0]
+        res[name] = [part.split() for part in rest.split('|')]
+    return res
+
+
+def _f(tokens):
+    return np.array([float(t) for t in tokens], dtype=np.float64)
+
+
+def _models():
+    for kind in KINDS:
+        for shape in SHAPES:
+            yield f'{kind}-{shape[0]}x{shape[1]}', MC.make_model(kind, shape)
+    yield 'rotation-calibrated', motion.MotionModel('rotation', (260, 346), centre=(171.3, 128.9), scale=226.4)
+    rng = np.random.default_rng(11)
+    yield 'custom-dense-K5', motion.MotionModel('custom', (37, 53), matrix=rng.normal(size=(12, 5)))
+
+
+RNG = np.random.default_rng(7)
+MODELS = dict(_models())
+COEFFS = {n: RNG.normal(size=m.n_coeffs) * 10.0 ** RNG.integers(-3, 3) for n, m in MODELS.items()}
+MUS = {n: RNG.normal(size=12) * 10.0 ** RNG.integers(-6, 6, size=12) for n in MODELS}
+for _n, _m in MODELS.items():
+    _case('q-' + _n, 'q', *_model_tokens(_m), *COEFFS[_n])
+    _case('vmax-' + _n, 'vmax', *_model_tokens(_m), *_m.sensor_size, *COEFFS[_n])
+    _case('project-' + _n, 'project', *_model_tokens(_m), *MUS[_n])
+_case('vmax-nan', 'vmax', *_model_tokens(MODELS['affine-37x53']), 37, 53, 1.0, np.nan, 0.0, 0.0, 0.0, 0.0)
+_case('vmax-inf', 'vmax', *_model_tokens(MODELS['affine-37x53']), 37, 53, 1.0, np.inf, 0.0, 0.0, 0.0, 0.0)
+
+SUMS = {'sum-random': RNG.normal(size=(PARTS, 12)) * 10.0 ** RNG.integers(-8, 8, size=(PARTS, 12)),
+        'sum-mostly-empty': np.concatenate([RNG.normal(size=(1, 12)), np.zeros((PARTS - 1, 12))]),
+        'sum-cancelling': np.concatenate([RNG.normal(size=(PARTS // 2, 12)) * 1e9, RNG.normal(size=(PARTS // 2, 12))]),
+        'sum-one': RNG.normal(size=(1, 12))}
+for _n, _p in SUMS.items():
+    _case(_n, 'sum', _p.shape[0], *_p.reshape(-1).tolist())
+
+_OK = MODELS['affine-5x7']
+REFUSALS = {
+    'model-ok': (_model_tokens(_OK), None),
+    'model-K1': (_model_tokens(MODELS['zoom-5x7']), None),
+    'model-K12': (_model_tokens(MODELS['polynomial2-5x7']), None),
+    'model-K0': ((0, 3.0, 2.0, 3.5), 'n_coeffs'),
+    'model-K13': ((13, 3.0, 2.0, 3.5), 'n_coeffs'),
+    'model-K-neg': ((-1, 3.0, 2.0, 3.5), 'n_coeffs'),
+    'model-cx-nan': ((6, np.nan, 2.0, 3.5, *_OK.matrix.reshape(-1).tolist()), 'centre'),
+    'model-cy-inf': ((6, 3.0, -np.inf, 3.5, *_OK.matrix.reshape(-1).tolist()), 'centre'),
+    'model-scale-0': ((6, 3.0, 2.0, 0.0, *_OK.matrix.reshape(-1).tolist()), 'scale'),
+    'model-scale-neg': ((6, 3.0, 2.0, -2.0, *_OK.matrix.reshape(-1).tolist()), 'scale'),
+    'model-scale-nan': ((6, 3.0, 2.0, np.nan, *_OK.matrix.reshape(-1).tolist()), 'scale'),
+    'model-scale-inf': ((6, 3.0, 2.0, np.inf, *_OK.matrix.reshape(-1).tolist()), 'scale'),
+    'model-M-nan': ((6, 3.0, 2.0, 3.5, *([0.0] * 71 + [np.nan])), 'M holds'),
+    'model-M-inf': ((6, 3.0, 2.0, 3.5, *([np.inf] + [0.0] * 71)), 'M holds'),
+}
+for _n, (_tok, _) in REFUSALS.items():
+    _case(_n, 'model', *_tok)
+_case('consts', 'consts')
+
+
+
+@pytest.mark.parametrize('name', sorted(MODELS))
+def test_q_vmax_and_projection_equal_numpy_bit_for_bit(out, name):
+    m, c, mu = MODELS[name], COEFFS[name], MUS[name]
+    assert np.array_equal(_f(out['q-' + name][0]), m.poly(c))
+    mm, bound = out['vmax-' + name]
+    assert np.array_equal(_f(mm), m.monomial_bounds())
+    assert float(bound[0]) == m.abs_bound(c)
+    assert np.abs(m.field(c)).max() <= float(bound[0])
+    assert np.array_equal(_f(out['project-' + name][0]), m.project_moments(mu))
+
+
+def test_a_nonfinite_coefficient_makes_the_bound_unknown(out):
+    assert np.isnan(float(out['vmax-nan'][1][0]))
+    assert not np.isfinite(float(out['vmax-inf'][1][0]))           # (the entry point passes "unknown" for anything not finite)
+
+
+@pytest.mark.parametrize('name', sorted(SUMS))
+def test_partials_are_added_in_index_order(out, name):
+    parts = SUMS[name]
+    s = parts[0].copy()
+    for g in range(1, parts.shape[0]):
+        s = s + parts[g]
+    assert np.array_equal(_f(out[name][0]), s)
+    if name == 'sum-cancelling':
+        assert not np.array_equal(s, parts[::-1].cumsum(axis=0)[-1])   # the order matters on this input: the check can see it
+
+
+@pytest.mark.parametrize('name', sorted(REFUSALS))
+def test_refusals(out, name):
+    words = out[name][0]
+    want = REFUSALS[name][1]
+    if want is None:
+        assert words == ['0', 'ok']
+    else:
+        assert words[0] == '1' and want in ' '.join(words[1:])
+
+
+def test_shared_sizes(out):
+    nq, nm, max_k, parts, arg_windows, arg_bytes = (int(w) for w in out['consts'][0])
+    assert (nq, nm, max_k) == (12, 6, 12) and parts == PARTS
+    assert arg_windows == 64 and arg_bytes == 64 * 12 * 8          # q of up to 64 windows rides in the kernel arguments
