@@ -389,19 +389,6 @@ struct FlightGuard {
     int keep(int rc = EINCM_OK) { armed = false; return rc; }
 };
 
-// Window b sits the evaluation out (eincm_loss_grad_masked): the host's form of the kernels' !win_active(g, b)
-inline bool window_sat_out(const Geom& g, int b) { return b < 64 && !((g.wmask >> b) & 1ull); }
-
-// Is a NaN / Inf among src[0..n)?  Copies src to dst on the way unless dst is null.  Branch-free, so that it vectorises: an OR over the
-// exponent bits (an early-exit std::isfinite loop does not: 0.6 ms of a 1.8 ms dense-theta evaluation at 480x640).  No __restrict__:
-// with it the compiler splits the copying loop into a memcpy and a second pass over the source (+0.1 ms on that evaluation).
-inline bool copy_scan_finite(double* dst, const double* src, size_t n) {
-    uint64_t bad = 0;
-    if (dst) for (size_t i = 0; i < n; ++i) { uint64_t u; memcpy(&u, src + i, sizeof u); dst[i] = src[i]; bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull); }
-    else     for (size_t i = 0; i < n; ++i) { uint64_t u; memcpy(&u, src + i, sizeof u); bad |= (uint64_t)((u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull); }
-    return bad != 0;
-}
-
 // The call frame of a one-shot operator.  After its argument checks an operator declares the pieces of c->scratch
 // it needs (piece) and the host memory its downloads land in (host_buf), grows the block once (begin), and puts every command on the
 // stream through the frame.  The destructor drains the stream on every exit that sync() has not drained already, and the members are
@@ -677,34 +664,12 @@ int collect_timings(eincm_ctx* c) {
     return (c->ring_size == 1) ? drain_event_ring(c, 0) : EINCM_OK;
 }
 
-// Window b's TV term as the aux reports it (losses.py:171; NAN: not computed): regularizers.py:14-38 from k_tv's partials, in tile order
-double window_tv(const eincm_ctx* c, const EvalParams& ep, int b) {
-    if (!ep.want_tv) return ep.cur_pyr_lvl <= 0 ? NAN : 0.0;
-    const double* q = c->h_tvparts + (size_t)b * c->g.ntiles * 3;
-    double a = 0.0, nz = 0.0;
-    for (int i = 0; i < c->g.ntiles; ++i) { a += q[(size_t)i * 3]; nz += q[(size_t)i * 3 + 1]; }
-    return a / (nz + EPSN);
-}
-
-// One window's value and aux entries (losses.py:176-203) from the sums over reference times of mrw_r * term_r / (zero-warp term + EPSN);
-// mrd, tv: NAN where not computed.  host_assemble (tv_direct) adds gamma * TV straight to the value where the TV was computed, the others
-// add the regularisers' sum: with delta == 0 (every host-assembled evaluation) the two differ in the sign of a zero value only.
-void assemble_window(const EvalParams& ep, int R, double sum_con, double sum_corr, double mrd, double tv, bool theta_bad, bool tv_direct,
-                     OutScal& o) {
-    const double mrc = sum_con / (double)R, mrr = sum_corr / (double)R;
-    double val = ep.alpha * (-mrc) + ep.beta * (-mrr);
-    if (tv_direct) {
-        if (ep.want_tv && ep.gamma != 0.0) val += ep.gamma * tv;
-    } else {
-        double reg = 0.0;
-        if (ep.gamma != 0.0) reg += ep.gamma * ((ep.cur_pyr_lvl <= 0) ? tv : 0.0);
-        if (ep.delta != 0.0) reg += ep.delta * mrd;
-        val += reg;
-    }
-    if (theta_bad) val = NAN;
-    o.mean_rel_contrast = mrc; o.mean_rel_corr = mrr; o.mean_rel_div = mrd; o.tv = tv;
-    o.value = val;
-    o.nonfinite = std::isfinite(val) ? 0.0 : 1.0;
+// The view eincm_loss.h's assemblies take of the evaluation that has landed: the plan's parameters and the pinned memory its kernels wrote
+LossView loss_view(eincm_ctx* c) {
+    const EvalPlan& P = c->fl.plan;
+    return LossView{&c->g, &P.ep, P.shape == EvalPlan::TWO_DOF, P.nth, c->h_wc, c->h_outs, c->h_grad, c->fl.theta_nan.data(), c->h_tvparts,
+                    c->h_img, c->h_g2, c->h_g11, c->gather_2.h_win_item0.data(), c->win_events.data(), c->f64.h_scal,
+                    c->h_objc.data(), c->h_ovals.p, P.og.ck, P.og.rk, P.host_asm};
 }
 
 // The whole evaluation of a float64 context (EINCM_CF_FP64), enqueued at once: theta -> Theta (k_theta) -> k64_splat -> image passes
@@ -777,31 +742,6 @@ int f64_launch(eincm_ctx* c, const double* theta_host) {
     return EINCM_OK;
 }
 
-// What k_final does, for a float64 evaluation: losses.py:176-203 from the per-image scalars and k_tv's partials, sums in index order.
-void f64_assemble(eincm_ctx* c) {
-    const Geom& g = c->g;
-    const EvalParams& ep = c->fl.plan.ep;
-    const double Rd = (double)g.R;
-    for (int b = 0; b < g.B; ++b) {
-        const WinConst& wc = c->h_wc[b];
-        OutScal& o = c->h_outs[b];
-        memset(&o, 0, sizeof o);
-        if (window_sat_out(g, b)) continue;
-        double src = 0.0, srr = 0.0, srd = 0.0;
-        for (int r = 0; r < g.R; ++r) {
-            const F64Scal& s = c->f64.h_scal[(size_t)b * g.R + r];
-            const double corr = -s.mse, div = ep.want_div ? s.div : NAN;
-            o.corr[r] = corr; o.contrast_gm[r] = s.g2; o.var[r] = s.var; o.div[r] = div;
-            const double con = (ep.contrast_kind == EINCM_CONTRAST_VARIANCE) ? s.var : s.g2;
-            const double c0 = (ep.contrast_kind == EINCM_CONTRAST_VARIANCE) ? wc.c0_var : wc.c0_gradmag;
-            src += wc.mrw[r] * con / (c0 + EPSN);
-            srr += wc.mrw[r] * corr / (wc.zc[r] + EPSN);
-            srd += wc.mrw[r] * div / (wc.d0 + EPSN);
-        }
-        assemble_window(ep, g.R, src, srr, ep.want_div ? srd / Rd : NAN, window_tv(c, ep, b), c->fl.theta_nan[b] != 0, false, o);
-    }
-}
-
 // ---- selectable objective kinds (eincm_objectives.hip.h) ----
 int obj_buffers(eincm_ctx* c, const ObjGeom& og) {
     const size_t n = (size_t)c->g.B * c->g.R * og.ncells * OBJ_NP;
@@ -838,33 +778,9 @@ int obj_constants(eincm_ctx* c) {
     return EINCM_OK;
 }
 
-// After the kernels of an evaluation with a new kind: the scalar assembly of losses.py:176-193 with the kinds' values (k_obj_grad's
-// per-image values, the zero-warp values), on top of what k_final / host_assemble left for the TV and divergence terms.
-void obj_assemble(eincm_ctx* c) {
-    const Geom& g = c->g;
-    const EvalPlan& P = c->fl.plan;
-    const int ck = P.og.ck, rk = P.og.rk;
-    for (int b = 0; b < g.B; ++b) {
-        if (window_sat_out(g, b)) continue;
-        OutScal& o = c->h_outs[b];
-        const ObjConst& oc = c->h_objc[b];
-        const WinConst& wc = c->h_wc[b];
-        // a NaN theta: host_assemble marks it in theta_nan, k_final in its (default-kind) value
-        const bool bad = P.host_asm ? c->fl.theta_nan[b] != 0 : std::isnan(o.value);
-        double sum_rel_con = 0.0, sum_rel_corr = 0.0;
-        for (int r = 0; r < g.R; ++r) {
-            const double con = c->h_ovals.p[((size_t)b * g.R + r) * 2], corr = c->h_ovals.p[((size_t)b * g.R + r) * 2 + 1];
-            sum_rel_con += wc.mrw[r] * con / (oc.c0[ck] + EPSN);
-            sum_rel_corr += wc.mrw[r] * corr / (oc.zc[rk][r] + EPSN);
-        }
-        assemble_window(P.ep, g.R, sum_rel_con, sum_rel_corr, o.mean_rel_div, o.tv, bad, false, o);
-    }
-}
-
-// theta_nan[b]: a NaN / Inf somewhere in window b's theta (host-assembled and float64 evaluations)
 void scan_theta(eincm_ctx* c, const double* theta_host, size_t nth) {
     c->fl.theta_nan.assign((size_t)c->g.B, 0);
-    for (int b = 0; b < c->g.B; ++b) c->fl.theta_nan[b] = copy_scan_finite(nullptr, theta_host + (size_t)b * nth, nth);   // (4096 values at 16x16 x 8 windows)
+    eincm::scan_theta(theta_host, c->g.B, nth, c->fl.theta_nan.data());
 }
 
 // First half of an evaluation: checks, side effects, plan_eval, then theta -> Theta -> IWE stack (launch_forward; a float64 context
@@ -1120,60 +1036,6 @@ int eval_end_launch(eincm_ctx* c) {
     return guard.keep();
 }
 
-// Host-assembled evaluations (plan.host_asm): what k_final does for them, in fp64 on the host from the partials the kernels wrote
-// into pinned memory - the image scalars of k_imgrad (h_img), its per-strip contrast energies (h_g2) and the per-workgroup partials
-// of the 2-DoF gradient (h_g11) - every sum in index order, so the result is a function of the partials alone (bit-reproducible).
-// losses.py:176-203 without the divergence term (the planner routes those evaluations to k_final).
-void host_assemble(eincm_ctx* c) {
-    const Geom& g = c->g;
-    const EvalPlan& P = c->fl.plan;
-    const EvalParams& ep = P.ep;
-    const double HW = (double)g.H * (double)g.W;
-    for (int b = 0; b < g.B; ++b) {
-        const WinConst& wc = c->h_wc[b];
-        OutScal& o = c->h_outs[b];
-        memset(&o, 0, sizeof o);
-        if (window_sat_out(g, b)) continue;       // sat this evaluation out (eval_end_collect marks its outputs)
-        double sum_rel_con = 0.0, sum_rel_corr = 0.0;
-        for (int r = 0; r < g.R; ++r) {
-            const double* q = c->h_img + ((size_t)b * g.R + r) * IMGSCAL_N;
-            ImgScal s{};
-            s.m = q[0]; s.M = q[1]; s.D = q[2]; s.cm = q[3]; s.cM = q[4]; s.sI = q[5]; s.sII = q[6]; s.sEI = q[7];
-            double g2 = 0.0;
-            const int nwg = (g.nig + IG_NT / 64 - 1) / (IG_NT / 64);          // one partial per k_imgrad workgroup
-            const double* g2p = c->h_g2 + ((size_t)b * g.R + r) * nwg;
-            for (int i = 0; i < nwg; ++i) g2 += g2p[i];
-            const double mse = mse_from_moments(s, wc.sE[r], wc.sEE[r], HW);
-            const double mean = s.sI / HW;
-            const double var = s.sII / HW - mean * mean;
-            const double cgm = g2 / HW;
-            const double con = (ep.contrast_kind == 1) ? var : cgm;
-            const double c0 = (ep.contrast_kind == 1) ? wc.c0_var : wc.c0_gradmag;
-            o.corr[r] = -mse; o.contrast_gm[r] = cgm; o.var[r] = var; o.div[r] = NAN;
-            sum_rel_con += wc.mrw[r] * con / (c0 + EPSN);
-            sum_rel_corr += wc.mrw[r] * (-mse) / (wc.zc[r] + EPSN);
-        }
-        assemble_window(ep, g.R, sum_rel_con, sum_rel_corr, NAN, window_tv(c, ep, b), c->fl.theta_nan[b] != 0, true, o);
-        if (P.shape == EvalPlan::TWO_DOF) {                  // 2-DoF: the gather's per-workgroup partials, added in index order
-            const int lo = c->gather_2.h_win_item0[b], hi = c->gather_2.h_win_item0[b + 1];
-            const double* p = c->h_g11 + (size_t)lo * g.R * 2;
-            const size_t n = (size_t)(hi - lo) * g.R;
-            // four interleaved chains per component (a fixed association, so still a function of the partials alone): one chain is
-            // bound by the latency of the add, 4000 partials of the 8-window batch took 6 us
-            double ax[4] = {0.0, 0.0, 0.0, 0.0}, ay[4] = {0.0, 0.0, 0.0, 0.0};
-            size_t k = 0;
-            for (; k + 4 <= n; k += 4) {
-                ax[0] += p[2 * k]; ay[0] += p[2 * k + 1]; ax[1] += p[2 * k + 2]; ay[1] += p[2 * k + 3];
-                ax[2] += p[2 * k + 4]; ay[2] += p[2 * k + 5]; ax[3] += p[2 * k + 6]; ay[3] += p[2 * k + 7];
-            }
-            for (; k < n; ++k) { ax[0] += p[2 * k]; ay[0] += p[2 * k + 1]; }
-            c->h_grad[(size_t)b * 2] = (ax[0] + ax[1]) + (ax[2] + ax[3]); c->h_grad[(size_t)b * 2 + 1] = (ay[0] + ay[1]) + (ay[2] + ay[3]);
-        } else if (c->win_events[b] == 0) {                  // theta grid: the gather's tail wrote dL/dtheta, unless the window has no workgroup
-            for (size_t i = 0; i < P.nth; ++i) c->h_grad[(size_t)b * P.nth + i] = 0.0;
-        }
-    }
-}
-
 // Second half, part 2: wait for the stream and hand the results over.  LAUNCHED -> IDLE once the stream has drained; an exit before
 // that abandons the flight (the kernels in flight read the pinned theta staging buffer and write the pinned result block, so the
 // context must not look idle, and accept the next theta, while they run).
@@ -1204,29 +1066,15 @@ int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) 
     const bool whole_grad = want_grad && fl.n_pieces == 0 && !dev_io;        // in pinned memory, in one piece
     if (want_grad && !grad && !dev_io) return fail(c, EINCM_ERR_ARG, "the evaluation was begun with a gradient but grad is NULL");
     HostPhase hp(c, EINCM_HP_COLLECT);
-    if (fl.plan.host_asm) host_assemble(c);
-    else if (c->fp64) f64_assemble(c);
-    if (fl.plan.obj) obj_assemble(c);
+    const LossView v = loss_view(c);
+    if (fl.plan.host_asm) host_assemble(v);
+    else if (c->fp64) f64_assemble(v);
+    if (fl.plan.obj) obj_assemble(v);
     if (const int rc = collect_timings(c)) return rc;
     c->have_eval = true;
     c->G_valid = want_grad;
 
-    OutScal sat_out{};                               // a window that was not evaluated: NaN value, zero gradient, no verdict
-    sat_out.value = sat_out.mean_rel_corr = sat_out.mean_rel_contrast = sat_out.mean_rel_div = sat_out.tv = NAN;
-    for (int b = 0; b < g.B; ++b) {
-        const bool out = window_sat_out(g, b);
-        if (out && whole_grad) for (size_t i = 0; i < nth; ++i) c->h_grad[(size_t)b * nth + i] = 0.0;
-        const OutScal& o = out ? sat_out : c->h_outs[b];
-        if (value) value[b] = o.value;
-        if (aux) {
-            aux[b].final_loss = o.value;
-            aux[b].mean_rel_corr = o.mean_rel_corr;
-            aux[b].mean_rel_contrast = o.mean_rel_contrast;
-            aux[b].mean_rel_iwe_divergence = o.mean_rel_div;
-            aux[b].theta_total_variation = o.tv;
-        }
-        if (o.nonfinite != 0.0) nonfinite = true;
-    }
+    if (hand_over(v, whole_grad, value, aux)) nonfinite = true;
     if (whole_grad && copy_scan_finite(grad, c->h_grad, total)) nonfinite = true;      // copy out and look for NaN / Inf in the same pass
     if (nonfinite) return fail(c, EINCM_ERR_NONFINITE, "loss or gradient is not finite");
     return EINCM_OK;
@@ -1260,15 +1108,7 @@ int store_constants(eincm_ctx* c, int rc_pass) {
     if (rc_pass != EINCM_OK && rc_pass != EINCM_ERR_NONFINITE) return rc_pass;
     const Geom& g = c->g;
     const size_t img = (size_t)g.H * g.W;
-    for (int b = 0; b < g.B; ++b) {
-        WinConst& wc = c->h_wc[b];
-        const OutScal& o = c->h_outs[b];
-        wc.c0_gradmag = o.contrast_gm[0];
-        wc.c0_var = o.var[0];
-        wc.d0 = o.div[0];
-        for (int r = 0; r < g.R; ++r) { wc.zc[r] = o.corr[r]; wc.inv_zc[r] = 1.0 / (wc.zc[r] + EPSN); }     // -MSE(E_r, n0)
-        wc.inv_c0_gradmag = 1.0 / (wc.c0_gradmag + EPSN); wc.inv_c0_var = 1.0 / (wc.c0_var + EPSN);
-    }
+    for (int b = 0; b < g.B; ++b) constants_from_zero_pass(c->h_outs[b], g.R, c->h_wc[b]);
     HIPCHK(c, hipMemcpyAsync(c->d_wc, c->h_wc, (size_t)g.B * sizeof(WinConst), hipMemcpyHostToDevice, c->stream));
     for (int b = 0; b < g.B && c->fp64; ++b)
         HIPCHK(c, hipMemcpyAsync(c->f64.zero_iwe + (size_t)b * img, c->f64.iwe + (size_t)b * g.R * img, img * sizeof(double),
@@ -1976,19 +1816,11 @@ int eincm_handover_loss_grad(eincm_ctx* c, const double* a, const double* prev_t
     HIPCHK(c, hipSetDevice(c->device));
     const size_t nth = (size_t)h * w * 2, B = c->g.B;
     std::vector<double> tho(B * nth), grad;
-    for (size_t b = 0; b < B; ++b)
-        for (size_t i = 0; i < nth; ++i)   // losses.py:269
-            tho[b * nth + i] = a[b] * prev_theta[b * nth + i] + (1.0 - a[b]) * theta[b * nth + i];
+    handover_blend(a, prev_theta, theta, B, nth, tho.data());
     if (dvalue_da) grad.resize(B * nth);
     const int rc = evaluate(c, tho.data(), h, w, p, value, dvalue_da ? grad.data() : nullptr, nullptr);
     if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
-    if (dvalue_da) {
-        for (size_t b = 0; b < B; ++b) {
-            double s = 0.0;
-            for (size_t i = 0; i < nth; ++i) s += grad[b * nth + i] * (prev_theta[b * nth + i] - theta[b * nth + i]);
-            dvalue_da[b] = s;
-        }
-    }
+    if (dvalue_da) handover_chain(grad.data(), prev_theta, theta, B, nth, dvalue_da);
     return rc;
 }
 
@@ -2006,31 +1838,7 @@ int eincm_objectives(eincm_ctx* c, const double* Theta, eincm_objectives_out* ou
     if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
     std::vector<double> tvp((size_t)g.B * g.ntiles * 3);
     HIPCHK(c, hipMemcpy(tvp.data(), c->d_tvparts, tvp.size() * sizeof(double), hipMemcpyDeviceToHost));
-    const double HW = (double)g.H * g.W;
-    for (int b = 0; b < g.B; ++b) {
-        eincm_objectives_out& o = out[b];
-        memset(&o, 0, sizeof o);
-        const OutScal& s = c->h_outs[b];
-        const WinConst& wc = c->h_wc[b];
-        o.n_refs = g.R;
-        o.zero_contrast = wc.c0_gradmag; o.zero_variance = wc.c0_var; o.zero_iwe_divergence = wc.d0;
-        for (int r = 0; r < g.R; ++r) {
-            o.correlations[r] = s.corr[r];
-            o.zero_correlations[r] = wc.zc[r];
-            o.rel_correlations[r] = s.corr[r] / (wc.zc[r] + EPSN);
-            o.contrasts[r] = s.contrast_gm[r];
-            o.rel_contrasts[r] = s.contrast_gm[r] / (wc.c0_gradmag + EPSN);
-            o.iwe_divergences[r] = s.div[r];
-            o.rel_iwe_divergences[r] = s.div[r] / (wc.d0 + EPSN);
-            o.variances[r] = s.var[r];
-            o.flow_warp_losses[r] = s.var[r] / wc.c0_var;          // contrast_metrics.py:17
-            o.multi_ref_weights[r] = wc.mrw[r];
-        }
-        o.theta_total_variation = s.tv;
-        double td = 0.0;
-        for (int k = 0; k < g.ntiles; ++k) td += tvp[((size_t)b * g.ntiles + k) * 3 + 2];
-        o.theta_divergence = td / HW;
-    }
+    for (int b = 0; b < g.B; ++b) fill_objectives(g, c->h_outs[b], c->h_wc[b], tvp.data() + (size_t)b * g.ntiles * 3, out[b]);
     return rc;
 }
 

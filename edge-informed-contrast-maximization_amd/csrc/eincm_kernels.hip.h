@@ -26,13 +26,13 @@
 #include <stdint.h>
 
 #include "eincm_types.h"
+#include "eincm_loss.h"
 
 namespace eincm {
 
 constexpr int NT = 256;           // threads per workgroup = 4 waves of 64
 constexpr int NWAVE = NT / 64;
 constexpr int WIN_CAP_MAX = 9216;
-constexpr double EPSN = 2.220446049250313e-16;   // sys.float_info.epsilon (losses.py:24)
 constexpr float INV_2PI = 0.15915494309189535f;
 // LDS accumulation of the splat is u32 fixed point: on gfx950 ds_add_f32 retires ~1 lane per 3 clocks whatever the
 // address pattern (0.33 lane-ops/clk/CU measured, tools/lds_atomic_bench.hip) while ds_add_u32 sustains 5-7.4.
@@ -51,29 +51,6 @@ __device__ __forceinline__ int fix_shift(int count) {
 constexpr float EXP_M05 = 0.6065306597126334f;   // exp(-1/2)
 
 __device__ __forceinline__ bool win_active(const Geom& g, int b) { return b >= 64 || ((g.wmask >> b) & 1ull) != 0ull; }
-
-struct StatPart {                 // per (window, ref, tile) partial of the image reductions
-    double mn, mx, cmn, cmx;      // min, max and how many pixels attain them inside the tile
-    double sI, sII, sEI, sG2;     // sum I, sum I^2, sum E*I, sum (gx^2+gy^2)
-};
-
-struct ImgScal {                  // per (window, ref) reduced scalars
-    double m, M, D, cm, cM, sI, sII, sEI, sG2;
-};
-constexpr int IMGSCAL_N = 9;      // doubles per image handed to the host: m, M, D, cm, cM, sI, sII, sEI, sG2
-
-struct WinConst {                 // theta-independent constants of a window (losses.py:54-55,66,71,80,84)
-    double c0_gradmag, c0_var, d0;
-    double zc[16];                // zero_corrs[r] = -MSE(E_r, n0)
-    double sE[16], sEE[16];       // sum E_r, sum E_r^2
-    double eabs[16];              // max |E_r|
-    double inv_c0_gradmag, inv_c0_var, inv_zc[16];   // 1 / (c0 + eps), 1 / (zc[r] + eps)
-    // (no kernel reads eabs or inv_*: they stay so that the layout, and with it every kernel's code, does not move)
-    double mrw[16];               // multi-reference weights (losses.py:39-46)
-    double dtmax;                 // max |t_e - tau_r| over the window's events and reference times (bounds a gradient term)
-    double nev;                   // events staged in this window of this context
-    double cntmax;                // most events on one source pixel (bounds a per-pixel gradient sum)
-};
 
 // The IWE accumulator holds pixel * 2^ACC_SHIFT as u64.  A segment's u32 LDS sums have scale 2^fshift with fshift <= 30 = ACC_SHIFT,
 // so the flush is an exact left shift: the accumulated image is the exact sum of the per-tap fixed-point values, whatever the order.
@@ -145,11 +122,6 @@ __device__ __forceinline__ int grad_shift(const WinConst& c, double gm, int R) {
 struct ThetaArg { double v[THETA_ARG_MAX]; };
 struct ThetaArgBig { double v[THETA_ARG_BIG]; };
 struct ThetaArgMid { double v[THETA_ARG_MID]; };
-
-struct OutScal {                  // per-window result block written by k_final
-    double value, mean_rel_corr, mean_rel_contrast, mean_rel_div, tv, tv_scale, nonfinite, _pad;
-    double corr[16], contrast_gm[16], var[16], div[16];
-};
 
 // ------------------------------------------------------------------------------------------------
 // helpers
@@ -997,12 +969,6 @@ __device__ __forceinline__ ImgScal reduce_parts(const StatPart* __restrict__ par
     return s;
 }
 
-// mean((E - n)^2) with n = (I - m)/D from the moments (correlation_objectives.py:25-26 on img_utils.py:24-25)
-__host__ __device__ __forceinline__ double mse_from_moments(const ImgScal& s, double sE, double sEE, double HW) {
-    const double a = s.m / s.D;
-    return (sEE + HW * a * a + s.sII / (s.D * s.D) + 2.0 * a * sE - 2.0 * s.sEI / s.D - 2.0 * a * s.sI / s.D) / HW;
-}
-
 // ------------------------------------------------------------------------------------------------
 // k_imgrad: G = dL/dIWE.  grid (ceil(nig / 4), R, B), 4 waves per workgroup, one strip of IG_COLS x IG_ROWS pixels per wave.
 //   contrast (grad-mag): a_r * (2/HW) * (adj_Sx(gx) + adj_Sy(gy)),  adj_S(c) = -conv_same(c, S) for Scharr
@@ -1062,11 +1028,11 @@ __global__ __launch_bounds__(IG_NT) void k_imgrad(Geom g, EvalParams ep,
             dAn = __shfl(wave_sum(dAn), 0, 64); dA = __shfl(wave_sum(dA), 0, 64);
         }
         if (threadIdx.x == 0 && blockIdx.x == 0 && imgscal_out) {
-            double* o = imgscal_out + ((size_t)b * g.R + r) * IMGSCAL_N;
-            o[0] = s.m; o[1] = s.M; o[2] = s.D; o[3] = s.cm; o[4] = s.cM; o[5] = s.sI; o[6] = s.sII; o[7] = s.sEI;
+            pack(s, imgscal_out + ((size_t)b * g.R + r) * IMGSCAL_N);
         }
         if (threadIdx.x == 0) {
             const double c0 = (ep.contrast_kind == 1) ? c.c0_var : c.c0_gradmag;
+            // loss_weights (eincm_loss.h), written out: this kernel's instructions move with the call, and it is one of the hot ones
             const double a_r = -ep.alpha * c.mrw[r] / ((double)g.R * (c0 + EPSN));
             const double b_r = -ep.beta * c.mrw[r] / ((double)g.R * (c.zc[r] + EPSN));
             const double a = s.m / s.D;
@@ -1644,7 +1610,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
             __shared__ double tvred[NTH / 64];
             nz = block_sum<NTH / 64>(nz, tvred);
             __shared__ double s_stv;
-            if (threadIdx.x == 0) s_stv = tv_gamma * 0.25 / (nz + EPSN) * ldexp(1.0, -tv_shift(g.H, g.W));
+            if (threadIdx.x == 0) s_stv = tv_grad_scale(tv_gamma, nz) * ldexp(1.0, -tv_shift(g.H, g.W));
             __syncthreads();
             stv = s_stv;
         }
@@ -2140,17 +2106,9 @@ __global__ __launch_bounds__(FT) void k_final(Geom g, EvalParams ep,
             }
             const ImgScal s = reduce_parts(parts + ((size_t)b * g.R + r) * g.pstride, g.nparts);
             if (lane == 0) {
-                const double mse = mse_from_moments(s, c.sE[r], c.sEE[r], HW);
-                const double mean = s.sI / HW;
-                const double var = s.sII / HW - mean * mean;
-                const double cgm = (g2parts ? g2sum : s.sG2) / HW;
-                const double con = (ep.contrast_kind == 1) ? var : cgm;
-                const double c0 = (ep.contrast_kind == 1) ? c.c0_var : c.c0_gradmag;
-                const double dv = ep.want_div ? dsum / HW : NAN;
-                o->corr[r] = -mse; o->contrast_gm[r] = cgm; o->var[r] = var; o->div[r] = dv;
-                sh_rel[0][r] = c.mrw[r] * con / (c0 + EPSN);
-                sh_rel[1][r] = c.mrw[r] * (-mse) / (c.zc[r] + EPSN);
-                sh_rel[2][r] = ep.want_div ? c.mrw[r] * dv / (c.d0 + EPSN) : 0.0;
+                const ImageTerms t = image_terms(ep, c, r, s, g2parts ? g2sum : s.sG2, dsum, HW);
+                store_terms(*o, r, t);
+                sh_rel[0][r] = t.rel_con; sh_rel[1][r] = t.rel_corr; sh_rel[2][r] = t.rel_div;
             }
         }
     }
@@ -2167,26 +2125,13 @@ __global__ __launch_bounds__(FT) void k_final(Geom g, EvalParams ep,
         }
         a = block_sum<FW>(a, scratch);
         n = block_sum<FW>(n, scratch);
-        if (threadIdx.x == 0) { tv = a / (n + EPSN); tvscale = ep.gamma * 0.25 / (n + EPSN); }
+        if (threadIdx.x == 0) { tv = tv_value(a, n); tvscale = tv_grad_scale(ep.gamma, n); }
     }
     // a NaN anywhere in theta must surface as a NaN loss (the reference propagates it through the warp)
     bad = block_sum<FW>(bad, scratch);
     if (threadIdx.x == 0) {
-        const double R = (double)g.R;
-        const double mrc = sum_rel_con / R, mrr = sum_rel_corr / R;
-        const double mrd = ep.want_div ? sum_rel_div / R : NAN;
-        const double tv_in_loss = (ep.cur_pyr_lvl <= 0) ? tv : 0.0;
-        double val = (ep.alpha * (-mrc) + ep.beta * (-mrr));
-        double reg = 0.0;
-        if (ep.gamma != 0.0) reg += ep.gamma * tv_in_loss;
-        if (ep.delta != 0.0) reg += ep.delta * mrd;
-        val += reg;
-        if (bad > 0.0) val = NAN;
-        o->mean_rel_contrast = mrc; o->mean_rel_corr = mrr; o->mean_rel_div = mrd;
-        o->tv = (ep.cur_pyr_lvl <= 0) ? (ep.want_tv ? tv : NAN) : 0.0;
-        o->value = val;
+        assemble_window(ep, g.R, sum_rel_con, sum_rel_corr, ep.want_div ? sum_rel_div / (double)g.R : NAN, tv_reported(ep, tv), bad > 0.0, false, *o);
         o->tv_scale = ep.use_tv_grad ? tvscale : 0.0;
-        o->nonfinite = (val - val == 0.0) ? 0.0 : 1.0;
         o->_pad = 0.0;
         sh_tvscale = ep.use_tv_grad ? tvscale : 0.0;
     }

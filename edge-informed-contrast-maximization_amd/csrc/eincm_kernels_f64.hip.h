@@ -31,10 +31,6 @@ constexpr int F64_PC = 2;              // partials of k64_grad1: sum Gn (n - 1),
 constexpr double INV_2PI_D = 0.15915494309189535;    // exp(-log(2 pi)) (event_utils.py:56)
 constexpr double EXP_M1_D = 0.36787944117144233;
 
-struct F64Scal {                       // per (window, ref) image scalars of the fp64 mode
-    double m, M, D, cm, cM, mean, var, g2, mse, div;   // g2 = mean(gx^2 + gy^2), mse = mean((E - n)^2), div = mean |div n|
-};
-
 // fixed-order block reduction (waves, then the waves in index order); the result is returned to every thread
 template <typename Op>
 __device__ __forceinline__ double block_reduce64(double v, double* scratch, Op op) {
@@ -314,9 +310,8 @@ __global__ __launch_bounds__(NT) void k64_grad1(Geom g, EvalParams ep, const dou
     const WinConst& wc = wcs[b];
     const bool var_kind = ep.contrast_kind == 1;
     const double c0 = var_kind ? wc.c0_var : wc.c0_gradmag;
-    const double a_r = -ep.alpha * wc.mrw[r] / (Rd * (c0 + EPSN));
-    const double b_r = -ep.beta * wc.mrw[r] / (Rd * (wc.zc[r] + EPSN));
-    const double e_r = ep.delta * wc.mrw[r] / (Rd * (wc.d0 + EPSN));
+    const LossWeights lw = loss_weights(ep, wc.mrw[r], Rd, c0, wc.zc[r], wc.d0, 1.0);
+    const double a_r = lw.a, b_r = lw.b, e_r = lw.e;
     const double* __restrict__ I = iwe + base;
     const double* __restrict__ E = edges + base;
     const double* __restrict__ S = sgn ? sgn + base : nullptr;
@@ -529,7 +524,7 @@ __global__ __launch_bounds__(NT) void k64_gfin(Geom g, int use_tv, double gamma,
         double nz = 0.0;
         for (int k = threadIdx.x; k < g.ntiles; k += NT) nz += tvparts[((size_t)b * g.ntiles + k) * 3 + 1];
         nz = block_reduce64(nz, scratch, OpSum());
-        tvs = gamma * 0.25 / (nz + EPSN);
+        tvs = tv_grad_scale(gamma, nz);
     }
     const double inv = ldexp(1.0, -gshift64(wcs[b], gmax[b], g.R));
     const bool nonfinite = bad[b] != 0u;           // a NaN / Inf the integer accumulator could not carry: the whole window's gradient is NaN

@@ -25,11 +25,6 @@ namespace eincm {
 // [19] sum |S 1|^2; [20] sum E^2
 constexpr int OBJ_NP = 21;
 
-struct ObjConst {                  // zero-warp values per window, indexed by kind: [0] / [1] from WinConst (host), [2] / [3] here
-    double c0[4];                  // contrast of the zero-warp IWE
-    double zc[4][16];              // correlation (signed) of (E_r, n0)
-};
-
 // Scharr of an accessor u(y, x) at (y, x): the convention of scharr_at
 template <typename U> __device__ __forceinline__ void obj_scharr(const U& u, int y, int x, double& gx, double& gy) {
     scharr_at(u, y, x, gx, gy);
@@ -246,9 +241,8 @@ __global__ __launch_bounds__(IG_NT) void k_obj_grad(Geom g, EvalParams ep, ObjGe
             const WinConst& c = wc[b];
             if (blockIdx.x == 0) { vals_out[((size_t)b * g.R + r) * 2] = q.con; vals_out[((size_t)b * g.R + r) * 2 + 1] = q.corr; }
             const double c0 = oc[b].c0[ck], zc = oc[b].zc[rk][r];
-            const double a_r = -ep.alpha * c.mrw[r] / ((double)g.R * (c0 + EPSN));
-            const double b_r = -ep.beta * c.mrw[r] / ((double)g.R * (zc + EPSN));
-            const double e_hw = use_div ? ep.delta * c.mrw[r] / ((double)g.R * (c.d0 + EPSN) * HW) : 0.0;
+            const LossWeights lw = loss_weights(ep, c.mrw[r], (double)g.R, c0, zc, c.d0, HW);
+            const double a_r = lw.a, b_r = lw.b, e_hw = use_div ? lw.e : 0.0;
             const double sGn_n = b_r * q.sdnn + e_hw * dAn;          // sum Gn * n   (Gn = dL/dn)
             const double sGn = b_r * q.sdn + e_hw * dA;              // sum Gn
             sc[0] = q.m; sc[1] = q.M; sc[2] = 1.0 / q.D;

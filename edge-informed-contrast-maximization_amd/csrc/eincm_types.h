@@ -2,6 +2,7 @@
 // planning (eincm_plan.h).  Plain C++17: no HIP header and no device code, so a compiler that knows no HIP can build what the host
 // decides with them.  Layouts, field order and values are the kernels' argument layouts: they do not change here.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 // The one function both sides run: __host__ __device__ under hipcc, a plain inline function anywhere else.
@@ -75,5 +76,52 @@ struct ObjGeom {
 constexpr int OBJ_NEED_TILE_GM = 1;     // tile-local Scharr energy          (adaptive_grad_mag)
 constexpr int OBJ_NEED_GM = 2;          // whole-image Scharr energy of I    (grad_mag, joint_contrast)
 constexpr int OBJ_NEED_JOINT = 4;       // cross terms with S E and S 1      (joint_contrast)
+
+constexpr double EPSN = 2.220446049250313e-16;   // sys.float_info.epsilon (losses.py:24)
+
+struct StatPart {                 // per (window, ref, tile) partial of the image reductions
+    double mn, mx, cmn, cmx;      // min, max and how many pixels attain them inside the tile
+    double sI, sII, sEI, sG2;     // sum I, sum I^2, sum E*I, sum (gx^2+gy^2)
+};
+
+struct ImgScal {                  // per (window, ref) reduced scalars
+    double m, M, D, cm, cM, sI, sII, sEI, sG2;
+};
+constexpr int IMGSCAL_N = 9;      // doubles per image handed to the host: m, M, D, cm, cM, sI, sII, sEI, sG2
+
+struct WinConst {                 // theta-independent constants of a window (losses.py:54-55,66,71,80,84)
+    double c0_gradmag, c0_var, d0;
+    double zc[16];                // zero_corrs[r] = -MSE(E_r, n0)
+    double sE[16], sEE[16];       // sum E_r, sum E_r^2
+    double eabs[16];              // max |E_r|
+    double inv_c0_gradmag, inv_c0_var, inv_zc[16];   // 1 / (c0 + eps), 1 / (zc[r] + eps)
+    // (no kernel reads eabs or inv_*: they stay so that the layout, and with it every kernel's code, does not move)
+    double mrw[16];               // multi-reference weights (losses.py:39-46)
+    double dtmax;                 // max |t_e - tau_r| over the window's events and reference times (bounds a gradient term)
+    double nev;                   // events staged in this window of this context
+    double cntmax;                // most events on one source pixel (bounds a per-pixel gradient sum)
+};
+
+struct OutScal {                  // per-window result block written by k_final
+    double value, mean_rel_corr, mean_rel_contrast, mean_rel_div, tv, tv_scale, nonfinite, _pad;
+    double corr[16], contrast_gm[16], var[16], div[16];
+};
+
+struct F64Scal {                       // per (window, ref) image scalars of the fp64 mode
+    double m, M, D, cm, cM, mean, var, g2, mse, div;   // g2 = mean(gx^2 + gy^2), mse = mean((E - n)^2), div = mean |div n|
+};
+
+struct ObjConst {                  // zero-warp values per window, indexed by kind: [0] / [1] from WinConst (host), [2] / [3] here
+    double c0[4];                  // contrast of the zero-warp IWE
+    double zc[4][16];              // correlation (signed) of (E_r, n0)
+};
+
+// the kernels' argument and result layouts: a move of one cannot go unnoticed
+static_assert(sizeof(StatPart) == 64 && offsetof(StatPart, mn) == 0 && offsetof(StatPart, sG2) == 56, "StatPart layout");
+static_assert(sizeof(ImgScal) == IMGSCAL_N * 8 && offsetof(ImgScal, m) == 0 && offsetof(ImgScal, sG2) == 64, "ImgScal layout");
+static_assert(sizeof(WinConst) == 104 * 8 && offsetof(WinConst, c0_gradmag) == 0 && offsetof(WinConst, cntmax) == 103 * 8, "WinConst layout");
+static_assert(sizeof(OutScal) == 72 * 8 && offsetof(OutScal, value) == 0 && offsetof(OutScal, div) == 56 * 8, "OutScal layout");
+static_assert(sizeof(F64Scal) == 80 && offsetof(F64Scal, m) == 0 && offsetof(F64Scal, div) == 72, "F64Scal layout");
+static_assert(sizeof(ObjConst) == 68 * 8 && offsetof(ObjConst, c0) == 0 && offsetof(ObjConst, zc) == 32, "ObjConst layout");
 
 }  // namespace eincm

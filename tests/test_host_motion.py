@@ -5,18 +5,13 @@ tests/host/motion_check.cpp is built once per session with the address and undef
 tests/test_host_plan.py builds plan_check, and run once, as a child process, over every case of this module; nothing is preloaded.
 Its outputs equal the numpy witness (motion.MotionModel) bit for bit, and its refusals are those of include/eincm.h."""
 import importlib
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import _host_check as HC
 import _motion_cases as MC
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'edge-informed-contrast-maximization_amd', 'csrc')
-SANITIZE = ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all']
 motion = importlib.import_module('edge-informed-contrast-maximization_amd.motion')
 
 KINDS = ('translation', 'similarity', 'affine', 'quadratic', 'rotation', 'polynomial2', 'zoom')
@@ -24,28 +19,10 @@ SHAPES = ((5, 7), (37, 53), (480, 640))
 PARTS = 64
 
 
-def _compiler():
-    rocm = os.environ.get('ROCM_PATH', '/opt/rocm')
-    for cxx in ('g++', os.path.join(rocm, 'llvm', 'bin', 'clang++'), os.path.join(rocm, 'lib', 'llvm', 'bin', 'clang++')):
-        if shutil.which(cxx):
-            return shutil.which(cxx)
-    raise AssertionError('neither g++ nor the ROCm clang++ found')
-
-
 @pytest.fixture(scope='session')
 def motion_check(tmp_path_factory):
     """Path of the sanitized checker."""
-    exe = str(tmp_path_factory.mktemp('motion_check') / 'motion_check')
-    cxx = _compiler()
-    # (g++ links the sanitizers' runtimes into the program, as clang++ does by default: the program needs nothing preloaded)
-    static = ['-static-libasan', '-static-libubsan'] if os.path.basename(cxx) == 'g++' else []
-    cmd = [cxx, '-std=c++17', '-Wall', '-Wextra', '-Werror'] + SANITIZE + static + [
-        '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-o', exe, os.path.join(ROOT, 'tests', 'host', 'motion_check.cpp')]
-    print(' '.join(cmd))
-    assert '-fsanitize=address,undefined' in cmd and '-fno-sanitize-recover=all' in cmd
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return HC.build(tmp_path_factory, 'motion_check')
 
 
 # ---- the cases: name -> input line, collected when the module is imported; one run of the checker answers all of them ----
@@ -53,35 +30,20 @@ CASES = {}
 
 
 def _case(name, *tokens):
-    assert name not in CASES, name
-    CASES[name] = ' '.join(str(int(t)) if isinstance(t, (bool, int, np.integer)) else repr(float(t)) for t in tokens[1:])
-    CASES[name] = tokens[0] + ' ' + CASES[name]
-    return name
-
-
-def _model_tokens(m):
-    return (m.n_coeffs, m.cx, m.cy, m.scale, *m.matrix.reshape(-1).tolist())
+    return HC.add_case(CASES, name, *tokens)
 
 
 @pytest.fixture(scope='module')
 def out(motion_check, tmp_path_factory):
     """name -> the checker's line for that case, split at ' |' into lists of words."""
-    path = tmp_path_factory.mktemp('motion_cases') / 'cases.txt'
-    path.write_text('\n'.join(CASES.values()) + '\n')
-    r = subprocess.run([motion_check, str(path)], capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr, f'the sanitized checker failed (exit {r.returncode}):\n{r.stderr[-4000:]}'
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(CASES)
-    res = {}
-    for (name, inp), line in zip(CASES.items(), lines):
-        word, _, rest = line.partition(' ')
-        assert word == inp.split()[0]
-        res[name] = [part.split() for part in rest.split('|')]
-    return res
+    return HC.run(motion_check, CASES, tmp_path_factory, 'motion_cases')
 
 
-def _f(tokens):
-    return np.array([float(t) for t in tokens], dtype=np.float64)
+_f, _i = HC.f, HC.i
+
+
+def _model_tokens(m):
+    return (m.n_coeffs, m.cx, m.cy, m.scale, *m.matrix.reshape(-1).tolist())
 
 
 def _models():

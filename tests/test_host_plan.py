@@ -4,46 +4,23 @@ tests/host/plan_check.cpp is built once per session with the address and undefin
 process, over every case of this module; the tests compare what it printed with numpy, the oracle and the launch-policy witness
 (tests/_launch_policy_witness.py).  The GPU modules (test_gpu_launch_policy*.py) guard the wiring of the same rules into the library."""
 import math
-import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
+import _host_check as HC
 import _launch_policy_cases as C
 import _launch_policy_witness as LP
 from oracle import eincm_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, 'edge-informed-contrast-maximization_amd', 'csrc')
-SANITIZE = ['-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all']
 METHODS = {'bilinear': 0, 'lanczos3': 1, 'lanczos5': 2, 'cubic': 3}
 PG_MAXC = 6                            # cells per axis under a tile that k_gather's own projection handles
-
-
-def _compiler():
-    rocm = os.environ.get('ROCM_PATH', '/opt/rocm')
-    for cxx in ('g++', os.path.join(rocm, 'llvm', 'bin', 'clang++'), os.path.join(rocm, 'lib', 'llvm', 'bin', 'clang++')):
-        if shutil.which(cxx):
-            return shutil.which(cxx)
-    raise AssertionError('neither g++ nor the ROCm clang++ found')
 
 
 @pytest.fixture(scope='session')
 def plan_check(tmp_path_factory):
     """Path of the sanitized checker."""
-    exe = str(tmp_path_factory.mktemp('plan_check') / 'plan_check')
-    cxx = _compiler()
-    # (g++ links the sanitizers' runtimes into the program, as clang++ does by default: the program needs nothing preloaded)
-    static = ['-static-libasan', '-static-libubsan'] if os.path.basename(cxx) == 'g++' else []
-    cmd = [cxx, '-std=c++17', '-Wall', '-Wextra', '-Werror'] + SANITIZE + static + [
-        '-I', os.path.join(ROOT, 'include'), '-I', CSRC, '-o', exe, os.path.join(ROOT, 'tests', 'host', 'plan_check.cpp')]
-    print(' '.join(cmd))
-    assert '-fsanitize=address,undefined' in cmd and '-fno-sanitize-recover=all' in cmd
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
+    return HC.build(tmp_path_factory, 'plan_check')
 
 
 # ---- the cases: name -> input line, collected when the module is imported; one run of the checker answers all of them ----
@@ -51,35 +28,16 @@ CASES = {}
 
 
 def _case(name, *tokens):
-    assert name not in CASES, name
-    CASES[name] = ' '.join(str(int(t)) if isinstance(t, (bool, np.integer)) else repr(float(t)) if isinstance(t, (float, np.floating)) else str(t)
-                           for t in tokens)
-    return name
+    return HC.add_case(CASES, name, *tokens)
 
 
 @pytest.fixture(scope='module')
 def out(plan_check, tmp_path_factory):
-    """name -> the checker's line for that case, split at ' |' into lists of numbers."""
-    path = tmp_path_factory.mktemp('plan_cases') / 'cases.txt'
-    path.write_text('\n'.join(CASES.values()) + '\n')
-    r = subprocess.run([plan_check, str(path)], capture_output=True, text=True)
-    assert r.returncode == 0 and not r.stderr, f'the sanitized checker failed (exit {r.returncode}):\n{r.stderr[-4000:]}'
-    lines = r.stdout.splitlines()
-    assert len(lines) == len(CASES)
-    res = {}
-    for (name, inp), line in zip(CASES.items(), lines):
-        word, _, rest = line.partition(' ')
-        assert word == inp.split()[0]
-        res[name] = [part.split() for part in rest.split('|')]
-    return res
+    """name -> the checker's line for that case, split at ' |' into lists of words."""
+    return HC.run(plan_check, CASES, tmp_path_factory, 'plan_cases')
 
 
-def _f(tokens):
-    return np.array([float(t) for t in tokens], dtype=np.float64)
-
-
-def _i(tokens):
-    return np.array([int(t) for t in tokens], dtype=np.int64)
+_f, _i = HC.f, HC.i
 
 
 # ================================================================================================
