@@ -188,6 +188,7 @@ SIGNATURES = [
     ('eincm_set_motion_model', C.c_int, [_P, C.POINTER(MotionModel)]),
     ('eincm_loss_grad_motion', C.c_int, [_P, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Aux)]),
     ('eincm_motion_field', C.c_int, [_P, C.c_void_p, C.c_void_p]),
+    ('eincm_loss_grad_motion_fused', C.c_int, [_P, C.c_void_p, C.POINTER(Params), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Aux)]),
 ]
 
 _lib = None

@@ -916,6 +916,7 @@ def minimize_motion(engine, model, coeffs0, params, maxiter, gtol, callbacks=Non
     """B lockstep BFGS minimisations of the engine's objective over the coefficients of a parametric motion-field model
     (motion.MotionModel).  coeffs0: (B, K); K <= 12, so every window takes the host's bit-exact SciPy update
     (LockstepBFGS) over ``engine.loss_grad_motion``.  ``callbacks``, ``active``, ``wolfe2_fallback`` and ``stats`` as in minimize_thetas.
+    Every step is evaluated by the engine's motion path (Engine.set_motion_path: 'expanded' | 'fused' | 'auto').
     Returns a list of scipy OptimizeResult (None for inactive windows), x the coefficients (K,)."""
     coeffs0 = np.asarray(coeffs0, dtype=np.float64)
     if coeffs0.ndim != 2 or coeffs0.shape[1] != model.n_coeffs:

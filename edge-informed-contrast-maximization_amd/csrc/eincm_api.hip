@@ -324,6 +324,11 @@ struct eincm_ctx : PlanCtx {
         Grow<double> Theta;                  // (maxB, H, W, 2) the expanded field: the device-resident theta of the evaluation
         Grow<double, true> h_part;           // pinned: the moment partials (maxB, MOTION_PARTS, 12) | q of every window (maxB, 12)
         double* h_q(int maxB) const { return h_part.p + (size_t)maxB * MOTION_PARTS * MOTION_NQ; }
+        // the fused evaluation
+        Grow<double, true> h_fpart;          // pinned: the gather's moment partials, one slot of 12 per (segment, reference time) or per segment
+        Grow<double> tmm_zero;               // (maxB, ntiles, 4) zeros: k_final's NaN scan of the velocity bounds (the host has looked at q)
+        std::vector<double> last_q;          // (B, 12) q of the last fused evaluation (to build d_Theta on demand, as last_theta11)
+        std::vector<int64_t> seg0;           // (B + 1) first segment of every window in the gather's list (motion_slot_offsets); empty: not formed for this staging
     } motion;
 };
 
@@ -559,6 +564,30 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
     const bool two_dof = P.shape == EvalPlan::TWO_DOF;
     const size_t nall = (size_t)g.B * P.nth;
     c->acc_dirty = true;               // from the first command on: an exit below leaves accumulators half-written
+    if (P.shape == EvalPlan::MOTION) {
+        // theta_host is q (B, 12): it rides in the event kernels' arguments behind (cx, cy, s), or is read from the pinned block; the
+        // splat forms its tiles and derives its windows itself, so nothing runs in front of it
+        auto& mo = c->motion;
+        ThetaArg ta{};
+        ta.v[0] = mo.model.cx; ta.v[1] = mo.model.cy; ta.v[2] = mo.model.scale;
+        const size_t nq = (size_t)g.B * MOTION_NQ;
+        if (P.use_arg) memcpy(ta.v + POLY_ARG_Q0, theta_host, nq * sizeof(double));
+        else memcpy(mo.h_q(c->maxB), theta_host, nq * sizeof(double));
+        mo.last_q.assign(theta_host, theta_host + nq);
+        c->last_theta11.clear();
+        c->Theta_valid = false;
+        {
+            StageTimer t(c, EINCM_STAGE_SPLAT, true);
+            if (c->splat.n > 0)
+                launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_POLY, 512>, dim3(c->splat.grid(g.R)), dim3(512),
+                             (size_t)g.wincap * sizeof(float) + TS * TS * sizeof(double2) + POLY_SCRATCH_BYTES, g, c->splat.n, c->splat.d_items,
+                             c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, c->splat.d_order, P.use_arg ? 1 : 0,
+                             (const double*)mo.h_q(c->maxB), ta);
+        }
+        HIPCHK(c, hipGetLastError());
+        c->fl.theta_dev = mo.h_q(c->maxB); c->fl.targ = ta;
+        return EINCM_OK;
+    }
     ThetaArg targ;
     static thread_local ThetaArgBig targ_big;
     if (P.use_arg_big) memcpy(targ_big.v, theta_host, nall * sizeof(double));
@@ -587,6 +616,7 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
         const int nwin_threads = (ga.n + sp.n) * g.R;
         if (two_dof) {
             if (theta_host) c->last_theta11.assign(theta_host, theta_host + (size_t)g.B * 2); else c->last_theta11.clear();
+            c->motion.last_q.clear();
             c->Theta_valid = false;
             if (P.need_theta_image) launch_theta_image(c, P.h, P.w, false, P.use_arg_big, targ_big, theta_dev, false);
             // the event kernels derive their windows from theta themselves; the velocity bounds (tmm) only feed k_final's NaN scan,
@@ -786,8 +816,9 @@ void scan_theta(eincm_ctx* c, const double* theta_host, size_t nth) {
 // First half of an evaluation: checks, side effects, plan_eval, then theta -> Theta -> IWE stack (launch_forward; a float64 context
 // enqueues the whole evaluation, f64_launch).  theta_host: (B,h,w,2) doubles, or io.theta in HBM.  Leaves the flight FORWARD (float64:
 // LAUNCHED); any other exit abandons it.  A forward half that was never finished is discarded.
+// motion: the fused evaluation of a motion model (plan_motion): theta_host is q (B, 12) and io carries the bound of the field alone.
 int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm_params* p, bool want_grad, const uint8_t* active = nullptr,
-               const DevIo& io = DevIo{}) {
+               const DevIo& io = DevIo{}, bool motion = false) {
     HostPhase hp(c, EINCM_HP_BEGIN);
     // (checked before the flight is touched: the evaluation in flight reads the mask and its plan again when it is collected)
     if (c->fl.launched())
@@ -826,7 +857,8 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         if (rc) return rc;
     }
     static const EvalKnobs no_knobs;               // (a float64 evaluation has no launch policy and reads none)
-    const EvalPlan P = plan_eval(*c, c->fl.io, c->fp64 ? no_knobs : process_knobs(), theta_host, h, w, p, want_grad);
+    const EvalPlan P = motion ? plan_motion(*c, process_knobs(), io.vmax, p, want_grad)
+                              : plan_eval(*c, c->fl.io, c->fp64 ? no_knobs : process_knobs(), theta_host, h, w, p, want_grad);
     if (c->fp64) {
         c->fl.plan = P; scan_theta(c, theta_host, nth);
         if (const int rc = f64_launch(c, theta_host)) return rc;
@@ -980,8 +1012,10 @@ int eval_end_launch(eincm_ctx* c) {
                 Geom gg = g;
                 if (two_dof) { gg.pitch_aligned = P.win_2.pal ? 1 : 0; gg.wincap_a = P.win_2.cap; gg.winmaxw_a = P.win_2.maxw; }
                 const dim3 grid(L.grid(P.all_r ? 1 : g.R));
-                const size_t lds = gg.wincap_a * sizeof(float) + (two_dof ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2));
-                double* g11 = host_asm ? c->h_g11 : c->d_g11;
+                const bool fused = P.shape == EvalPlan::MOTION;       // the polynomial mode: the moments go to their pinned slots
+                const size_t lds = gg.wincap_a * sizeof(float) + (two_dof ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2)) +
+                                   (fused ? POLY_SCRATCH_BYTES : 0);
+                double* g11 = fused ? c->motion.h_fpart.p : host_asm ? c->h_g11 : c->d_g11;
                 const int use_arg = P.use_arg ? 1 : 0;
                 if (c->splat_rad != 1) {
                     // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
@@ -1000,7 +1034,11 @@ int eval_end_launch(eincm_ctx* c) {
                                      P.grid_tail ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad,
                                      (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth.p + (size_t)c->maxB * c->coarse_cap);
                     };
-                    if (two_dof)      go(k_gather<THETA_CONST, 0, NT, 0>, NT);
+                    if (fused) {
+                        if (P.all_r) c->stage.wide ? go(k_gather<THETA_POLY, 1, NT_TILE, 0, 1>, NT_TILE) : go(k_gather<THETA_POLY, 0, NT_TILE, 0, 1>, NT_TILE);
+                        else         c->stage.wide ? go(k_gather<THETA_POLY, 1, NT_TILE, 0>, NT_TILE) : go(k_gather<THETA_POLY, 0, NT_TILE, 0>, NT_TILE);
+                    }
+                    else if (two_dof) go(k_gather<THETA_CONST, 0, NT, 0>, NT);
                     else if (P.all_r) c->stage.wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1>, NT_TILE);
                     else if (c->stage.wide) P.proj ? go(k_gather<THETA_TILE, 1, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 1, NT_TILE, 0>, NT_TILE);
                     else              P.proj ? go(k_gather<THETA_TILE, 0, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 0>, NT_TILE);
@@ -1018,7 +1056,7 @@ int eval_end_launch(eincm_ctx* c) {
     if (!host_asm) {
         StageTimer t(c, EINCM_STAGE_FINAL, !(want_grad && identity));
         launch_timed(c, EINCM_STAGE_FINAL, k_final, dim3(g.B), dim3(FT), 0, g, ep, c->d_parts, c->d_divparts, c->d_tvparts,
-                           c->d_tmm, c->d_wc, P.g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth.p, c->d_gth.p + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
+                           P.shape == EvalPlan::MOTION ? c->motion.tmm_zero.p : c->d_tmm, c->d_wc, P.g2_from_imgrad ? c->d_g2parts : nullptr, c->d_gth.p, c->d_gth.p + (size_t)c->maxB * c->coarse_cap, (int)c->coarse_cap,
                            c->d_g11, c->gather_2.d_win_item0, c->gather_2.n, c->d_gmax,
                            P.zero_copy_out ? c->h_outs : c->d_outs, P.zero_copy_out ? c->h_grad : c->d_grad, want_grad ? 1 : 0);
         if (want_grad && identity) {
@@ -1059,7 +1097,8 @@ int eval_end_collect(eincm_ctx* c, double* value, double* grad, eincm_aux* aux) 
         HostPhase hp(c, EINCM_HP_WAIT);
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
-    const bool dev_io = fl.io.theta != nullptr;      // the gradient went device to device (enqueue_result_copies)
+    // the gradient went device to device (enqueue_result_copies), or as the moments of a motion model (eincm_loss_grad_motion_fused)
+    const bool dev_io = fl.io.theta != nullptr || fl.plan.shape == EvalPlan::MOTION;
     fl.land();
     guard.keep();
     ++c->hp_n;
@@ -1610,6 +1649,7 @@ static int stage_windows(eincm_ctx* c, const StageArgs& a) {
     c->staged = false;
     c->objc_valid = false;           // the zero-warp values of the objective kinds belong to the windows staged before
     c->Theta_valid = false;
+    c->motion.last_q.clear(); c->motion.seg0.clear();      // ... as do a fused evaluation's q and the windows' segment ranges
     c->bfgs.begun = false;           // the BFGS state belongs to the batch it was begun for
     c->stage = plan_staging(*c, a.B, a.R, a.n_events, a.flags, live_knobs().stage);
     const StagePlan& P = c->stage;
@@ -1909,9 +1949,11 @@ int eincm_get_image_grad(eincm_ctx* c, float* G) {
     if (c && c->fp64) return copy_image(c, nullptr, c->f64.G, (size_t)c->g.B * c->g.R * c->g.H * c->g.W, G, nullptr);
     return copy_out(c, G, c ? c->d_G : nullptr, c ? (size_t)c->g.B * c->g.R * c->g.H * c->g.W * sizeof(float) : 0);
 }
-// 2-DoF evaluations skip the Theta image; build it when somebody asks for it
+static int motion_theta_image(eincm_ctx* c);
+// 2-DoF evaluations and fused motion-model evaluations skip the Theta image; build it when somebody asks for it
 static int ensure_theta_image(eincm_ctx* c) {
     if (c->Theta_valid) return EINCM_OK;
+    if (c->motion.last_q.size() == (size_t)c->g.B * MOTION_NQ && c->motion.set) return motion_theta_image(c);
     if (c->last_theta11.size() != (size_t)c->g.B * 2) return fail(c, EINCM_ERR_STATE, "no evaluation yet");
     HIPCHK(c, hipSetDevice(c->device));
     const int rc = ensure_resample(c, 1, 1, EINCM_METHOD_BILINEAR);      // a (1,1,2) theta upsamples to a constant with every method
@@ -3013,10 +3055,11 @@ static double motion_expand(eincm_ctx* c, const double* coeffs, unsigned long lo
 
 int eincm_set_motion_model(eincm_ctx* c, const eincm_motion_model* model) {
     if (!c) return EINCM_ERR_ARG;
-    if (!model) { c->motion.set = false; return EINCM_OK; }
+    if (!model) { c->motion.set = false; c->motion.last_q.clear(); return EINCM_OK; }
     if (const char* what = motion_model_error(*model)) return fail(c, EINCM_ERR_ARG, "eincm_set_motion_model: %s", what);
     c->motion.model = *model;
     c->motion.set = true;
+    c->motion.last_q.clear();                       // (a fused evaluation's q belongs to the model it was formed with)
     return EINCM_OK;
 }
 
@@ -3074,6 +3117,95 @@ int eincm_loss_grad_motion(eincm_ctx* c, const double* coeffs, const eincm_param
         }
         if (nonfinite && rc == EINCM_OK) rc = fail(c, EINCM_ERR_NONFINITE, "loss or gradient is not finite");
     }
+    return rc;
+}
+
+// The field of the last fused evaluation's q into d_Theta, for the accessors that read the image (ensure_theta_image): every window,
+// whatever the evaluation masked (a window that sat out has q = 0).
+static int motion_theta_image(eincm_ctx* c) {
+    auto& mo = c->motion;
+    const Geom& g = c->g;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, ensure(c, mo.h_part, (size_t)c->maxB * (MOTION_PARTS + 1) * MOTION_NQ, true));
+    OneShot op(c);                                  // (the frame is here for its drain: the kernel reads the pinned q)
+    op.pending = true;
+    memcpy(mo.h_q(c->maxB), mo.last_q.data(), mo.last_q.size() * sizeof(double));
+    const MotionGeom mg{g.H, g.W, g.B, ~0ull, mo.model.cx, mo.model.cy, mo.model.scale};
+    static const MotionQArg none{};
+    const int npix = g.H * g.W;
+    hipLaunchKernelGGL(k_motion_expand, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)g.B), dim3(NT), 0, c->stream, mg, 0, none,
+                       (const double*)mo.h_q(c->maxB), reinterpret_cast<double2*>(c->d_Theta));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, op.sync());
+    c->Theta_valid = true;
+    return EINCM_OK;
+}
+
+int eincm_loss_grad_motion_fused(eincm_ctx* c, const double* coeffs, const eincm_params* p, const uint8_t* active, double* value, double* grad,
+                                 eincm_aux* aux) {
+    if (!c) return EINCM_ERR_ARG;
+    static const char* who = "eincm_loss_grad_motion_fused";
+    const MotionCtxState st{c->fp64, c->motion.set, c->staged, c->constants_pending, c->device_results, !c->fl.idle(), c->splat_size};
+    if (const MotionRefusal r = motion_fused_supported(st, p)) return fail(c, r.code, "%s: %s", who, r.why);
+    if (!coeffs || !p || !value) return fail(c, EINCM_ERR_ARG, "%s: null pointer argument", who);
+    HIPCHK(c, hipSetDevice(c->device));
+    auto& mo = c->motion;
+    const Geom& g = c->g;
+    const int K = mo.model.n_coeffs;
+    // q = M c and the bound of the field per window, before any launch: a window whose q (or bound) is not finite sits the launch out
+    double mm[MOTION_NM];
+    motion_monomial_bounds(mo.model, g.H, g.W, mm);
+    std::vector<double> q((size_t)g.B * MOTION_NQ, 0.0);
+    std::vector<uint8_t> act((size_t)g.B, 1), bad((size_t)g.B, 0);
+    double vmax = 0.0;
+    bool any_bad = false;
+    for (int b = 0; b < g.B; ++b) {
+        if (active && b < 64 && !active[b]) { act[b] = 0; continue; }        // (windows >= 64 always take part, as in every masked evaluation)
+        double* qb = q.data() + (size_t)b * MOTION_NQ;
+        motion_q(mo.model, coeffs + (size_t)b * K, qb);
+        const double v = motion_abs_bound(qb, mm);
+        if (!motion_q_usable(qb, v)) {
+            for (int j = 0; j < MOTION_NQ; ++j) qb[j] = 0.0;
+            act[b] = 0; bad[b] = 1; any_bad = true;
+            continue;
+        }
+        vmax = std::max(vmax, v);
+    }
+    HIPCHK(c, ensure(c, mo.h_part, (size_t)c->maxB * (MOTION_PARTS + 1) * MOTION_NQ, true));
+    HIPCHK(c, ensure(c, mo.tmm_zero, (size_t)c->maxB * g.ntiles * 4, true));
+    if (grad) HIPCHK(c, ensure(c, mo.h_fpart, (size_t)std::max(c->gather.n, 1) * g.R * MOTION_NQ));
+    if (grad && mo.seg0.empty()) {
+        mo.seg0.resize((size_t)g.B + 1);
+        const int64_t n = motion_slot_offsets(c->h_tilecount.data(), g.B, g.ntiles, c->stage.seg, 1, mo.seg0.data());
+        if (n != c->gather.n) { mo.seg0.clear(); return fail(c, EINCM_ERR_STATE, "%s: internal: %lld segments counted, the gather's list has %d", who, (long long)n, c->gather.n); }
+    }
+    eincm_params pe = *p;
+    pe.method = EINCM_METHOD_BILINEAR;             // (no resampling: the field is at sensor size)
+    FlightGuard guard(c);                          // from the first launch on, every exit drains the stream
+    int rc = eval_begin(c, q.data(), g.H, g.W, &pe, grad != nullptr, act.data(), DevIo{nullptr, nullptr, vmax}, true);
+    if (!rc) rc = eval_end_launch(c);
+    if (rc) return rc;
+    const int sps = c->fl.plan.all_r ? 1 : g.R;    // slots per segment
+    rc = guard.keep(eval_end_collect(c, value, nullptr, aux));                 // the one synchronisation
+    if (rc != EINCM_OK && rc != EINCM_ERR_NONFINITE) return rc;
+    bool nonfinite = any_bad;
+    HostPhase hp(c, EINCM_HP_COLLECT);             // the host's share of the gradient: the slots in index order, then M^T mu
+    for (int b = 0; b < g.B; ++b) {
+        double* gb = grad ? grad + (size_t)b * K : nullptr;
+        if (bad[b]) {
+            value[b] = NAN;
+            if (aux) aux[b].final_loss = aux[b].mean_rel_corr = aux[b].mean_rel_contrast = aux[b].mean_rel_iwe_divergence = aux[b].theta_total_variation = NAN;
+            for (int k = 0; gb && k < K; ++k) gb[k] = NAN;
+            continue;
+        }
+        if (!gb) continue;
+        if (window_sat_out(g, b)) { for (int k = 0; k < K; ++k) gb[k] = 0.0; continue; }
+        double mu[MOTION_NQ];
+        motion_sum_slots(mo.h_fpart.p + (size_t)mo.seg0[b] * sps * MOTION_NQ, (mo.seg0[b + 1] - mo.seg0[b]) * sps, mu);
+        motion_project(mo.model, mu, gb);
+        if (copy_scan_finite(nullptr, gb, (size_t)K)) nonfinite = true;
+    }
+    if (nonfinite && rc == EINCM_OK) rc = fail(c, EINCM_ERR_NONFINITE, "loss or gradient is not finite");
     return rc;
 }
 

@@ -260,6 +260,122 @@ struct EvReg { uint32_t xy; double t; };   // one event in flight through the so
 // wave-instruction (64 lanes, 64 different cache lines) and was 2/3 of k_splat's time; every workgroup works on ONE source tile, so:
 constexpr int THETA_CONST = 1;   // theta (1,1,2): Theta is one constant per window (read from the tile bounds, min == max)
 constexpr int THETA_TILE = 2;    // otherwise: the tile's 32x32 double2 velocities are staged in LDS once per segment (16 KiB)
+constexpr int THETA_POLY = 3;    // a motion model: the tile is formed in LDS from the window's polynomial, no Theta image
+
+// ---- the polynomial of a motion model (DESIGN.md sections 20 and 21): one statement for k_motion_expand, k_motion_moments and the
+// THETA_POLY mode of the event kernels, so that their bits cannot drift apart.  No FMA contraction anywhere in it. ----
+// normalised coordinate of column x (c = cx) or row y (c = cy): a correctly rounded division
+__device__ __forceinline__ double motion_coord(int x, double c, double s) {
+#pragma clang fp contract(off)
+    return __ddiv_rn((double)x - c, s);
+}
+// the three products of the monomials m = [1, u, v, u u, u v, v v], rounded once each
+__device__ __forceinline__ void motion_products(double u, double v, double& uu, double& uv, double& vv) {
+#pragma clang fp contract(off)
+    uu = u * u; uv = u * v; vv = v * v;
+}
+// Theta_x = ((((q0 + q1 u) + q2 v) + q3 uu) + q4 uv) + q5 vv, Theta_y likewise from q6..q11: every product rounded, sums left to right
+__device__ __forceinline__ double2 motion_poly(const double* q, double u, double v, double uu, double uv, double vv) {
+#pragma clang fp contract(off)
+    double2 t;
+    t.x = ((((q[0] + q[1] * u) + q[2] * v) + q[3] * uu) + q[4] * uv) + q[5] * vv;
+    t.y = ((((q[6] + q[7] * u) + q[8] * v) + q[9] * uu) + q[10] * uv) + q[11] * vv;
+    return t;
+}
+
+// THETA_POLY: how the event kernels' existing theta parameters carry a motion model.  targ.v[0..2] = (cx, cy, s) always; q (12 doubles
+// per window) rides in targ.v[POLY_ARG_Q0 ..] for up to POLY_ARG_WINDOWS windows (use_arg), beyond that it is read behind theta_c.
+constexpr int POLY_NQ = 12;
+constexpr int POLY_ARG_Q0 = 4;
+constexpr int POLY_ARG_WINDOWS = (THETA_ARG_MAX - POLY_ARG_Q0) / POLY_NQ;
+// LDS beside the Theta tile: u of the tile's 32 columns | v of its 32 rows | 4 bounds of each of up to 8 waves
+constexpr int POLY_SCRATCH = 2 * TS + 4 * 8;
+constexpr size_t POLY_SCRATCH_BYTES = POLY_SCRATCH * sizeof(double);
+
+// the tile's velocity bounds from the per-wave bounds poly_fill_tile left behind u and v (every thread; after its last barrier)
+template <int NTH>
+__device__ __forceinline__ void poly_tile_bounds(const double* uv, double* mm4) {
+    const double* red = uv + 2 * TS;
+    mm4[0] = red[0]; mm4[1] = red[1]; mm4[2] = red[2]; mm4[3] = red[3];
+    for (int i = 1; i < NTH / 64; ++i) {
+        mm4[0] = fmin(mm4[0], red[4 * i]); mm4[1] = fmax(mm4[1], red[4 * i + 1]);
+        mm4[2] = fmin(mm4[2], red[4 * i + 2]); mm4[3] = fmax(mm4[3], red[4 * i + 3]);
+    }
+}
+
+// The Theta tile of source tile (tx0, ty0) of window `win`, formed by the whole workgroup: 32 + 32 divisions by one wave, then the
+// polynomial at the tile's pixels (0 outside the sensor, as the staged tile of THETA_TILE has).  mm4: the tile's velocity bounds over
+// its pixels inside the sensor, in every thread (what k_theta leaves in tmm: item_window takes them).  uv keeps u and v for the
+// backward's moments.  Two barriers; the caller synchronises before the tile is read.
+template <int NTH>
+__device__ __forceinline__ void poly_fill_tile(const Geom& g, int win, int tx0, int ty0, int use_arg, const double* __restrict__ theta_c,
+                                               const ThetaArg& targ, double2* thtile, double* uv, double* mm4) {
+#pragma clang fp contract(off)
+    static_assert(NTH <= 512 && TS == 32, "the bounds' scratch holds 8 waves; one wave divides for 2 x 32 coordinates");
+    const int tid = threadIdx.x;
+    if (tid < 2 * TS) {
+        const bool row = tid >= TS;
+        uv[tid] = motion_coord((row ? ty0 : tx0) + (tid & (TS - 1)), row ? targ.v[1] : targ.v[0], targ.v[2]);
+    }
+    double q[POLY_NQ];
+#pragma unroll
+    for (int j = 0; j < POLY_NQ; ++j) q[j] = use_arg ? targ.v[POLY_ARG_Q0 + POLY_NQ * win + j] : theta_c[(size_t)POLY_NQ * win + j];
+    __syncthreads();
+    double mnx = INFINITY, mxx = -INFINITY, mny = INFINITY, mxy = -INFINITY;
+    for (int p = tid; p < TS * TS; p += NTH) {
+        const int ly = p / TS, lx = p % TS;
+        double2 t = make_double2(0.0, 0.0);
+        if (ty0 + ly < g.H && tx0 + lx < g.W) {
+            const double u = uv[lx], v = uv[TS + ly];
+            double uu, uvp, vv;
+            motion_products(u, v, uu, uvp, vv);
+            t = motion_poly(q, u, v, uu, uvp, vv);
+            mnx = fmin(mnx, t.x); mxx = fmax(mxx, t.x); mny = fmin(mny, t.y); mxy = fmax(mxy, t.y);
+        }
+        thtile[p] = t;
+    }
+    mnx = wave_min(mnx); mxx = wave_max(mxx); mny = wave_min(mny); mxy = wave_max(mxy);
+    double* red = uv + 2 * TS;
+    if ((tid & 63) == 0) { double* o = red + 4 * (tid >> 6); o[0] = mnx; o[1] = mxx; o[2] = mny; o[3] = mxy; }
+    __syncthreads();
+    poly_tile_bounds<NTH>(uv, mm4);
+}
+
+// The twelve moments of a tile's gradient sums, mu_j = sum_pix m_j dL/dTheta_x (j < 6) and the same with dL/dTheta_y: the adjoint of
+// poly_fill_tile.  accum: the tile's i64 sums (x, y interleaved) at scale 2^shift; every sum is converted to fp64 once, multiplied by
+// the monomials of the pixel (each product rounded) and added to the thread's chain, pixels p = tid, tid + NTH, ...; the chains are
+// reduced in block_sum's order (lanes by the wave tree, then the waves in index order; `red`: 12 doubles per wave of dead LDS) and
+// thread 0 STORES the twelve results in out[0..12).  Pixels outside the sensor hold zero sums.  The caller has synchronised.
+template <int NTH>
+__device__ __forceinline__ void poly_project_moments(const unsigned long long* accum, const double* uv, int shift, double* red,
+                                                     double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const double inv = ldexp(1.0, -shift);
+    double a[POLY_NQ];
+#pragma unroll
+    for (int j = 0; j < POLY_NQ; ++j) a[j] = 0.0;
+    for (int p = threadIdx.x; p < TS * TS; p += NTH) {
+        const double dx = (double)(long long)accum[2 * p] * inv, dy = (double)(long long)accum[2 * p + 1] * inv;
+        const double u = uv[p % TS], v = uv[TS + p / TS];
+        double uu, uvp, vv;
+        motion_products(u, v, uu, uvp, vv);
+        a[0] += dx; a[1] += u * dx; a[2] += v * dx; a[3] += uu * dx; a[4] += uvp * dx; a[5] += vv * dx;
+        a[6] += dy; a[7] += u * dy; a[8] += v * dy; a[9] += uu * dy; a[10] += uvp * dy; a[11] += vv * dy;
+    }
+#pragma unroll
+    for (int j = 0; j < POLY_NQ; ++j) a[j] = wave_sum(a[j]);
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < POLY_NQ; ++j) red[wv * POLY_NQ + j] = a[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < POLY_NQ) {
+        double r = 0.0;
+        for (int i = 0; i < NTH / 64; ++i) r += red[i * POLY_NQ + threadIdx.x];
+        out[threadIdx.x] = r;
+    }
+}
 
 // round-to-nearest fixed-point conversion of a positive product < 2^31: v_mul_f32 + v_cvt_rpi_i32_f32 (floor(x + 0.5) in the converter itself;
 // the compiler has no builtin for it).  Where b is the constant 1 (the centre column of the normalised taps) the multiply folds away: one
@@ -634,7 +750,7 @@ __device__ __forceinline__ void ev_load(EvReg& r, const EvBuf& b, int base, uint
 // A segment (<= MAX_CHUNK events) is accumulated in its u32 fixed-point window in LDS (exact integer ds_add_u32, scale
 // fix_shift(count)); the window is flushed to HBM once per segment.
 // ------------------------------------------------------------------------------------------------
-template <int TM, int NTH>   // TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE)
+template <int TM, int NTH>   // TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE / THETA_POLY)
 __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
         const Item* __restrict__ items,
         const uint32_t* __restrict__ ev_xy,    // x | y << 16, binned by (window, tile)
@@ -648,7 +764,7 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
 {
     constexpr int theta_mode = TM;                // every branch on it below folds away: 8 % on both event kernels
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsu[];
-    double2* thtile = reinterpret_cast<double2*>(ldsu + g.wincap);                 // present only for THETA_TILE
+    double2* thtile = reinterpret_cast<double2*>(ldsu + g.wincap);                 // present only for THETA_TILE / THETA_POLY (which keeps POLY_SCRATCH doubles behind it)
     int item, r;
     if (!block_to_work(n_items, g.R, order, item, r)) return;
     const Item it = items[item];
@@ -662,6 +778,12 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
         // launch in front of the splat, no table): ~150 uniform instructions against a dependent kernel boundary per evaluation
         vconst = use_arg ? make_double2(targ.v[2 * it.win], targ.v[2 * it.win + 1]) : make_double2(theta_c[2 * it.win], theta_c[2 * it.win + 1]);
         const double mm4[4] = {vconst.x, vconst.x, vconst.y, vconst.y};
+        wn = item_window(g, it, mm4, tau, g.wincap, g.winmaxw);
+    } else if (theta_mode == THETA_POLY) {
+        // a motion model: the workgroup forms its tile from the window's polynomial and derives its window from the tile's bounds, as
+        // the 2-DoF form does from its constant - no Theta image, no window table, no kernel in front of the splat
+        double mm4[4];
+        poly_fill_tile<NTH>(g, it.win, tx0, ty0, use_arg, theta_c, targ, thtile, reinterpret_cast<double*>(thtile + TS * TS), mm4);
         wn = item_window(g, it, mm4, tau, g.wincap, g.winmaxw);
     } else {
         const double* __restrict__ ThW = Theta + (size_t)it.win * g.H * g.W * 2;
@@ -1395,14 +1517,14 @@ __device__ __forceinline__ void project_tile_to_cells(const Geom& g, int h, int 
         if (ay != 0.0) atomicAdd(o + 1, (unsigned long long)fix64_wide(ay));
     }
 }
-template <int TM, int WIDE, int NTH, int PROJ, int ALLR = 0>      // NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE)
+template <int TM, int WIDE, int NTH, int PROJ, int ALLR = 0>      // NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE / THETA_POLY)
 __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_items,      // WIDE: 61-bit fixed point per event (tiny windows, see grad_shift_pixel)
         const Item* __restrict__ items, const uint32_t* __restrict__ ev_xy, const double* __restrict__ ev_t,
         const double* __restrict__ Theta, const double* __restrict__ edge_ts,
         const float* __restrict__ G,           // (B,R,H,W) dL/dIWE written by k_imgrad
         const Window* __restrict__ wins,       // (n_items, R) windows of this evaluation
         long long* __restrict__ gTheta,        // (B,H,W,2) i64 fixed point, zero on entry (cleared by its consumer)
-        double* __restrict__ g11,              // 2-DoF theta: (n_items, R, 2) per-workgroup partials of dL/dtheta
+        double* __restrict__ g11,              // 2-DoF theta: (n_items, R, 2) per-workgroup partials of dL/dtheta; THETA_POLY: (n_items, R | 1, 12) the moments
         const WinConst* __restrict__ wc, const unsigned* __restrict__ gmax,   // scale of the i64 accumulators (grad_shift)
         const int32_t* __restrict__ order,
         int use_arg, const double* __restrict__ theta_c, ThetaArg targ,   // 2-DoF theta (B,2): in the kernel arguments, or behind theta_c
@@ -1422,7 +1544,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     constexpr bool direct11 = TM == THETA_CONST;  // 2-DoF theta <=> per-workgroup partials
     // the segments walked are the gather's own lists (window capacity wincap_a), not the splat's
     const int wincap = g.wincap_a, winmaxw = g.winmaxw_a;
-    // LDS: [G window: wincap floats][accum: TS*TS*2 doubles unless direct11][Theta tile: TS*TS double2 if THETA_TILE]
+    // LDS: [G window: wincap floats][accum: TS*TS*2 doubles unless direct11][Theta tile: TS*TS double2 if THETA_TILE / THETA_POLY][POLY_SCRATCH doubles if THETA_POLY]
     extern __shared__ __attribute__((aligned(16))) float lds[];
     __shared__ double red11[NTH / 64];
     unsigned long long* accum = reinterpret_cast<unsigned long long*>(lds + wincap);   // i64 fixed point: ds_add_u64 (3.7 lane-ops/clk/CU; ds_add_f32: 0.33)
@@ -1441,6 +1563,11 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         vconst = use_arg ? make_double2(targ.v[2 * it.win], targ.v[2 * it.win + 1]) : make_double2(theta_c[2 * it.win], theta_c[2 * it.win + 1]);
         const double mm4[4] = {vconst.x, vconst.x, vconst.y, vconst.y};
         wn = item_window(g, it, mm4, tau, wincap, winmaxw);
+    } else if (theta_mode == THETA_POLY) {        // the tile from the window's polynomial, the window from its bounds (see k_splat)
+        double mm4[4];
+        poly_fill_tile<NTH>(g, it.win, (it.tile % g.tilesX) * TS, (it.tile / g.tilesX) * TS, use_arg, theta_c, targ, thtile,
+                            reinterpret_cast<double*>(thtile + TS * TS), mm4);
+        wn = item_window(g, it, mm4, tau, wincap, winmaxw, false);
     } else {
         wn = wins[(size_t)item * g.R + r];
     }
@@ -1449,7 +1576,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     const float* __restrict__ Gi = G + img;
     const int tx = it.tile % g.tilesX, ty = it.tile / g.tilesX;
     const int x0 = tx * TS, y0 = ty * TS;
-    if (theta_mode != THETA_CONST) {
+    if (theta_mode == THETA_TILE) {
         const double* __restrict__ ThW = Theta + (size_t)it.win * g.H * g.W * 2;
         for (int p = threadIdx.x; p < TS * TS; p += NTH) {
             const int y = y0 + p / TS, x = x0 + p % TS;
@@ -1475,10 +1602,12 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     load_window();
     double gscale = 0.0;                          // 2^eg of this window's gradient accumulators
     double gm_used = 0.0;                         // max |G| the scales derive from
+    int gshift = 0;                               // eg (THETA_POLY converts its sums back itself)
     if (!direct11) {
         __shared__ unsigned gms[NTH / 64];
         const double gm = gmax_of(gmax + (size_t)it.win * g.gmax_n, g.gmax_n, gms);
-        gscale = ldexp(1.0, grad_shift_pixel(wc[it.win], gm, g.R, WIDE != 0));
+        gshift = grad_shift_pixel(wc[it.win], gm, g.R, WIDE != 0);
+        gscale = ldexp(1.0, gshift);
         gm_used = gm;
     }
     __syncthreads();
@@ -1551,7 +1680,13 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     if (!all_r || ++rr >= g.R) break;
     __syncthreads();                              // every lane is done with the G window of the previous reference time
     tau = edge_ts[it.win * g.R + rr];
-    wn = wins[(size_t)item * g.R + rr];
+    if (theta_mode == THETA_POLY) {
+        double mm4[4];
+        poly_tile_bounds<NTH>(reinterpret_cast<const double*>(thtile + TS * TS), mm4);
+        wn = item_window(g, it, mm4, tau, wincap, winmaxw, false);
+    } else {
+        wn = wins[(size_t)item * g.R + rr];
+    }
     wp = wn.ww;
     img = ((size_t)it.win * g.R + rr) * g.H * g.W;
     Gi = G + img;
@@ -1571,6 +1706,14 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
 #ifdef EINCM_ABL_G_NOFLUSH
     return;
 #endif
+    if (theta_mode == THETA_POLY) {
+        // The tile's sums projected onto the twelve moments of the motion model, stored in the workgroup's own slot: nothing is flushed
+        // to the dL/dTheta image, nothing is left to clear.  The G window is dead by now: its LDS holds the waves' partial sums.
+        static_assert((NTH / 64) * POLY_NQ * 8 <= WIN_CAP_DEFAULT * 4, "the waves' sums fit the smallest G window");
+        poly_project_moments<NTH>(accum, reinterpret_cast<const double*>(thtile + TS * TS), gshift, reinterpret_cast<double*>(lds),
+                                  g11 + ((size_t)item * (all_r ? 1 : g.R) + (all_r ? 0 : r)) * POLY_NQ);
+        return;
+    }
     if (PROJ) {
         // The tile's sums projected onto the theta cells (project_tile_to_cells); the G window is dead by now: its LDS holds the weights.
         const TileRange tr = tilerng[it.tile];

@@ -28,13 +28,13 @@ struct MotionGeom {
 
 __device__ __forceinline__ bool motion_active(const MotionGeom& g, int b) { return b >= 64 || ((g.wmask >> b) & 1ull) != 0ull; }
 
-// the monomials of pixel p (m[0] = 1 is implied)
+// the monomials of pixel p (m[0] = 1 is implied), by the helpers the event kernels' THETA_POLY mode shares (eincm_kernels.hip.h)
 __device__ __forceinline__ void motion_monomials(const MotionGeom& g, int p, double& u, double& v, double& uu, double& uv, double& vv) {
 #pragma clang fp contract(off)
     const int y = p / g.W, x = p - y * g.W;
-    u = __ddiv_rn((double)x - g.cx, g.s);
-    v = __ddiv_rn((double)y - g.cy, g.s);
-    uu = u * u; uv = u * v; vv = v * v;
+    u = motion_coord(x, g.cx, g.s);
+    v = motion_coord(y, g.cy, g.s);
+    motion_products(u, v, uu, uv, vv);
 }
 
 // Theta (B, H, W) double2.  use_arg: q of window b is qarg.q[12 b ..], else q_mem[12 b ..].
@@ -51,10 +51,7 @@ __global__ __launch_bounds__(NT) void k_motion_expand(MotionGeom g, int use_arg,
     for (int j = 0; j < MOTION_NQ; ++j) q[j] = use_arg ? qarg.q[b * MOTION_NQ + j] : q_mem[(int64_t)b * MOTION_NQ + j];
     double u, v, uu, uv, vv;
     motion_monomials(g, p, u, v, uu, uv, vv);
-    double2 t;
-    t.x = ((((q[0] + q[1] * u) + q[2] * v) + q[3] * uu) + q[4] * uv) + q[5] * vv;
-    t.y = ((((q[6] + q[7] * u) + q[8] * v) + q[9] * uu) + q[10] * uv) + q[11] * vv;
-    Theta[(int64_t)b * npix + p] = t;
+    Theta[(int64_t)b * npix + p] = motion_poly(q, u, v, uu, uv, vv);       // (the expression the event kernels' THETA_POLY mode evaluates)
 }
 
 // grad (B, H, W) double2: the dense dL/dTheta of the evaluation.  parts (B, MOTION_PARTS, 12) in pinned host memory.

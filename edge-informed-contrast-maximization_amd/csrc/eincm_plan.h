@@ -437,7 +437,7 @@ struct DevIo {
 
 // Every decision of one evaluation, taken once by plan_eval before its first launch; the launch and assembly code only read it.
 struct EvalPlan {
-    enum Shape { IDENTITY, TWO_DOF, GRID } shape = GRID;           // theta (h, w) = the sensor's / (1, 1) / any other grid
+    enum Shape { IDENTITY, TWO_DOF, GRID, MOTION } shape = GRID;   // theta (h, w) = the sensor's / (1, 1) / any other grid / a motion model's polynomial inside the event kernels (plan_motion)
     enum ThetaSrc { THETA_DEVICE, THETA_ARGS, THETA_PINNED, THETA_PIECES } theta_src = THETA_PIECES;   // where k_theta reads theta
     int h = 0, w = 0; size_t nth = 0;   // nth: doubles of one window's theta
     bool want_grad = false, full_aux = false, div_grad = false;
@@ -457,6 +457,7 @@ struct EvalPlan {
     bool zero_copy_out = false;         // k_final writes the results straight into pinned host memory
 };
 
+constexpr int MOTION_PLAN_ARG_WINDOWS = (THETA_ARG_MAX - 4) / 12;   // windows whose q rides in the event kernels' arguments beside (cx, cy, s) (POLY_ARG_WINDOWS)
 constexpr size_t ZERO_COPY_MAX = 65536;   // doubles of theta / gradient that cross PCIe by zero-copy access to pinned host memory (a 64-window batch at 16x16: 32768)
 
 inline EvalPlan::Shape theta_shape(const Geom& g, int h, int w) {
@@ -480,6 +481,39 @@ struct EvalKnobs {
     bool no_host_asm = false;           // EINCM_NO_HOST_ASM
     int all_r = -1;                     // EINCM_GATHER_ALL_R (-1: not set)
 };
+
+// The LDS window capacities of an evaluation as staged (a pinned capacity, EINCM_WINCAP), and - plan_windows - chosen from vmax, a
+// bound of |theta| over the evaluation's windows.  Shared by plan_eval and plan_motion.
+inline void plan_windows_preset(const PlanCtx& c, EvalPlan& P) {
+    const Geom& g = c.g;
+    P.wincap = g.wincap; P.winmaxw = g.winmaxw; P.wincap_a = g.wincap_a; P.winmaxw_a = g.winmaxw_a;
+    P.pitch_aligned = c.stage.pitch != 0 ? 1 : 0;
+    P.win_2 = WinFit{c.wincap, win_maxw(c.wincap), c.stage.pitch >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
+}
+inline void plan_windows(const PlanCtx& c, EvalPlan& P, double vmax, bool two_dof) {
+    // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
+    const double margin = 2.0 * (c.splat_rad + 1);
+    // Where a larger window costs no residency it is taken at once (a capacity is an allocation, the windows themselves stay as small
+    // as their segments need): the 2-DoF kernels hold nothing but the window in LDS, 4608 words = 18 KiB still gives the 8 workgroups
+    // of 4 waves a CU can hold; the theta-grid gather carries 32 KiB beside its window and runs 3 workgroups per CU up to 5461 words.
+    // The theta-grid splat (window + 16 KiB Theta tile) pays for capacity with workgroups per CU (6 / 5 / 4 / 3), so it takes what it needs.
+    // Each list's windows are sized for its time span: what all but 3 % of the events' segments stay within (cut_segments; the mean
+    // tile would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
+    const int floor_s = two_dof ? 2 : 0, pitch_s = c.stage.pitch != 0 ? 1 : 0;
+    WinFit s = fit_window(vmax, c.splat.tspan, margin, floor_s, pitch_s);
+    // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
+    // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
+    P.splat_short = two_dof && c.splat_sh.n > 0 && !s.fits;
+    if (P.splat_short) s = fit_window(vmax, c.splat_sh.tspan, margin, floor_s, pitch_s);
+    P.wincap = s.cap; P.winmaxw = s.maxw; P.pitch_aligned = s.pal ? 1 : 0;
+    // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
+    // sends taps down the direct path
+    const WinFit a = fit_window(vmax, c.gather.tspan, margin, 2, -1);
+    P.wincap_a = a.cap; P.winmaxw_a = a.maxw;
+    // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
+    // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
+    P.win_2 = fit_window(vmax, c.gather_2.tspan, margin, 2, c.stage.pitch >= 2 ? 1 : 0);
+}
 
 // Every decision of one evaluation, from the context's state, the call's device-resident theta (io) and its checked arguments.
 // No HIP calls, no side effects (eval_begin's).
@@ -520,37 +554,14 @@ inline EvalPlan plan_eval(const PlanCtx& c, const DevIo& io, const EvalKnobs& kn
 
     // LDS window capacity for this evaluation: the host knows theta, hence the largest displacement a segment can see.
     // Small windows give 8 workgroups per CU; windows too small for the flow push taps onto the slow direct-to-HBM path.
-    P.wincap = g.wincap; P.winmaxw = g.winmaxw; P.wincap_a = g.wincap_a; P.winmaxw_a = g.winmaxw_a;
-    P.pitch_aligned = c.stage.pitch != 0 ? 1 : 0;
-    P.win_2 = WinFit{c.wincap, win_maxw(c.wincap), c.stage.pitch >= 2, true};   // (a pinned capacity, EINCM_WINCAP: the pitch as staged)
+    plan_windows_preset(c, P);
     if (!c.wincap_fixed) {
         double vmax = 0.0;
         const size_t stride = nall > 8192 ? nall / 8192 : 1;            // dense theta: sample (any capacity is correct; 65536 samples cost 90 us)
         if (io.theta) vmax = (io.vmax >= 0.0 && std::isfinite(io.vmax)) ? io.vmax : 1e9;      // unknown: the largest windows
         else if (stride == 1) { for (size_t i = 0; i < nall; ++i) { const double a = std::fabs(theta_host[i]); vmax = std::max(vmax, a <= 1.7e308 ? a : 0.0); } }   // (vectorises)
         else for (size_t i = 0; i < nall; i += stride) { const double a = std::fabs(theta_host[i]); if (a > vmax && std::isfinite(a)) vmax = a; }
-        // the window's margin: +-(radius + 1) pixels (the taps and the rounding); 4 for the default 3x3 splat
-        const double margin = 2.0 * (c.splat_rad + 1);
-        // Where a larger window costs no residency it is taken at once (a capacity is an allocation, the windows themselves stay as small
-        // as their segments need): the 2-DoF kernels hold nothing but the window in LDS, 4608 words = 18 KiB still gives the 8 workgroups
-        // of 4 waves a CU can hold; the theta-grid gather carries 32 KiB beside its window and runs 3 workgroups per CU up to 5461 words.
-        // The theta-grid splat (window + 16 KiB Theta tile) pays for capacity with workgroups per CU (6 / 5 / 4 / 3), so it takes what it needs.
-        // Each list's windows are sized for its time span: what all but 3 % of the events' segments stay within (cut_segments; the mean
-        // tile would size them for the dense tiles alone and send the taps of the sparse ones, whose single segment spans the whole window, to HBM)
-        const int floor_s = two_dof ? 2 : 0, pitch_s = c.stage.pitch != 0 ? 1 : 0;
-        WinFit s = fit_window(vmax, c.splat.tspan, margin, floor_s, pitch_s);
-        // a 2-DoF theta whose spread over a long splat segment outgrows the largest window: the short list (half the time span); the taps
-        // of a window that is too small go to HBM one by one (117 px per window: 1220 us on the long list, 544 us on the short one)
-        P.splat_short = two_dof && c.splat_sh.n > 0 && !s.fits;
-        if (P.splat_short) s = fit_window(vmax, c.splat_sh.tspan, margin, floor_s, pitch_s);
-        P.wincap = s.cap; P.winmaxw = s.maxw; P.pitch_aligned = s.pal ? 1 : 0;
-        // the gather's own list: longer segments see a longer time span, hence a larger displacement spread; a window too small for it
-        // sends taps down the direct path
-        const WinFit a = fit_window(vmax, c.gather.tspan, margin, 2, -1);
-        P.wincap_a = a.cap; P.winmaxw_a = a.maxw;
-        // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
-        // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
-        P.win_2 = fit_window(vmax, c.gather_2.tspan, margin, 2, c.stage.pitch >= 2 ? 1 : 0);
+        plan_windows(c, P, vmax, two_dof);
     }
 
     // 2-DoF theta with nothing but the contrast and correlation terms (every level above 0 of the reference's pyramid at its first
@@ -578,6 +589,29 @@ inline EvalPlan plan_eval(const PlanCtx& c, const DevIo& io, const EvalKnobs& kn
     P.nsrc = (!want_grad || identity) ? 0 : (P.events_projected ? 0 : 1) + ((ep.use_tv_grad && !P.tv_proj) ? 1 : 0);
     // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
     P.zero_copy_out = !c.device_results && !io.theta && !identity && nall <= ZERO_COPY_MAX;
+    return P;
+}
+
+// The fused evaluation of a motion model (shape MOTION): the event kernels form the tile's Theta from the
+// window's polynomial themselves and the gather reduces its tile to the twelve moments, so there is no theta image, no window table
+// and no dense gradient.  Planned like the 2-DoF shape where that fits - the kernels derive their windows, the capacities come from
+// the host's bound of the field (vmax; not finite: unknown, the largest windows), theta rides in the event kernels' arguments, the
+// results land in pinned memory without a copy command - and like the dense shape where the outputs must be the expanded path's
+// bits: the image passes and k_final are the ones plan_eval gives a device-resident dense theta (no host assembly: the host's sums
+// of the contrast energy are in another order than k_final's).  all_r: one gather workgroup per segment walks all reference times,
+// by the theta-grid rule (the segments alone fill the chip's workgroup slots).  The caller has refused what motion_fused_supported refuses.
+inline EvalPlan plan_motion(const PlanCtx& c, const EvalKnobs& knobs, double vmax, const eincm_params* p, bool want_grad) {
+    static const double no_theta = 0.0;               // (plan_eval reads no theta of a device-resident one)
+    DevIo io;
+    io.theta = &no_theta; io.vmax = vmax;
+    EvalPlan P = plan_eval(c, io, knobs, nullptr, c.g.H, c.g.W, p, want_grad);
+    P.shape = EvalPlan::MOTION;
+    P.theta_src = EvalPlan::THETA_ARGS;
+    P.use_arg = c.g.B <= MOTION_PLAN_ARG_WINDOWS;
+    P.need_theta_image = false;
+    P.all_r = want_grad && c.g.R > 1 && (knobs.all_r >= 0 ? knobs.all_r != 0 : c.gather.n >= 700);
+    P.events_projected = true;                        // (by the gather itself, onto the moments)
+    P.zero_copy_out = true;
     return P;
 }
 

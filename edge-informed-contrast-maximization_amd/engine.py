@@ -445,6 +445,38 @@ def check_motion_coeffs(coeffs, n_windows, model):
     return c
 
 
+MOTION_PATHS = ('expanded', 'fused', 'auto')
+
+
+def check_motion_path(path):
+    """'expanded' (the Theta image and the dense gradient), 'fused' (the polynomial inside the event kernels,
+    section 21) or 'auto' (fused where it applies and is the faster one); anything else is a ValueError."""
+    if path not in MOTION_PATHS:
+        raise ValueError(f"path {path!r}: one of 'expanded', 'fused', 'auto'")
+    return path
+
+
+def motion_fused_refusal(precision, splat_window, params):
+    """Why the fused path does not apply to this engine and these parameters (csrc/eincm_motion.h: motion_fused_supported, the part of
+    it that Python can see before a GPU call), or None."""
+    if precision == 'fp64':
+        return 'the fused motion path is not supported in fp64 mode'
+    if int(splat_window) != 3:
+        return f'the fused motion path has the 3x3 splat window only, the engine has {int(splat_window)}'
+    if params.flags & L.PF_FULL_AUX:
+        return 'the fused motion path cannot serve full_aux: it needs the Theta image during the evaluation'
+    if params.cur_pyr_lvl <= 0 and params.gamma != 0.0:
+        return 'the fused motion path cannot serve the TV term (level 0, gamma != 0): it needs the Theta image during the evaluation'
+    return None
+
+
+def motion_auto_takes_fused(n_windows, n_events, n_refs):
+    """The rule of the path 'auto' where the fused path applies (csrc/eincm_motion.h: motion_auto_takes_fused): the fused path was the faster
+    one in every cell of profiles/motion_fused.md (8 windows of 1e6 events, one 480x640 window, 64 windows of 3e4 events), so it is
+    taken wherever it applies."""
+    return True
+
+
 def make_params(alpha, beta, gamma, delta, cur_pyr_lvl, method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                 full_aux=False, correlation_kind='mse'):
     """eincm_params.  contrast_kind / correlation_kind: a name or an integer code; the correlation kind rides in
@@ -496,6 +528,7 @@ class Engine:
         self._io = {}                      # (h, w) -> staging buffers of loss_grad with their addresses
         self.flow_eval_windows = 0         # windows of the staged flow evaluation (flow_eval_stage)
         self.motion_model = None           # the motion.MotionModel of loss_grad_motion / motion_field (set_motion_model)
+        self.motion_path = 'expanded'      # how loss_grad_motion evaluates (set_motion_path): 'expanded' | 'fused' | 'auto'
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -694,14 +727,30 @@ class Engine:
         self._check(self._lib.eincm_set_motion_model(self._ctx, None if model is None else C.byref(model.as_struct())))
         self.motion_model = model
 
+    def set_motion_path(self, path):
+        """How loss_grad_motion (and with it minimize_motion) evaluates from here on: 'expanded' (the default: the field as an image,
+        the dense gradient reduced to the moments), 'fused' (the polynomial inside the event kernels, DESIGN.md section 21: the same
+        value bit for bit, the gradient the same sum in another order; a ValueError from loss_grad_motion where it does not apply) or
+        'auto' (fused where it applies and profiles/motion_fused.md found it the faster one, else expanded).  A setting of the engine,
+        not a keyword of loss_grad_motion: the signatures of section 20's callables stay as they are."""
+        self.motion_path = check_motion_path(path)
+
     def loss_grad_motion(self, coeffs, params, want_grad=True, want_aux=False, allow_nonfinite=True, active=None):
         """coeffs: (B,K), or (K,) when B == 1.  Returns (value (B,), grad (B,K) | None, aux list | None): the loss of the field
-        model.field(coeffs) and its gradient with respect to the coefficients, the TV term's share included.  ``active`` as in loss_grad."""
+        model.field(coeffs) and its gradient with respect to the coefficients, the TV term's share included.  ``active`` as in loss_grad.
+        The evaluation path is the engine's ``motion_path`` (set_motion_path; 'expanded' unless set)."""
+        path = check_motion_path(self.motion_path)
         c = check_motion_coeffs(coeffs, self.B, self.motion_model)
+        fused = False
+        if path != 'expanded':
+            why = motion_fused_refusal(self.precision, self.splat_window, params)
+            if why is not None and path == 'fused':
+                raise ValueError(why)
+            fused = why is None and (path == 'fused' or motion_auto_takes_fused(self.B, int(np.sum(self.n_events)), self.R))
+        call = self._lib.eincm_loss_grad_motion_fused if fused else self._lib.eincm_loss_grad_motion
         act, p_act = self._active_ptr(active)
         value, grad, aux = self._outputs(c.shape, want_grad, want_aux)
-        rc = self._lib.eincm_loss_grad_motion(self._ctx, c.ctypes.data, C.byref(params), p_act, value.ctypes.data,
-                                              grad.ctypes.data if want_grad else None, aux)
+        rc = call(self._ctx, c.ctypes.data, C.byref(params), p_act, value.ctypes.data, grad.ctypes.data if want_grad else None, aux)
         return self._collect(rc, value, grad, aux, allow_nonfinite)
 
     def motion_field(self, coeffs):

@@ -18,12 +18,13 @@ immutable, numpy arrays are not: a cheap content fingerprint (<= 256 strided sam
 is a BEST-EFFORT check for in-place edits - an edit of a few elements between two calls can go unnoticed, and the stale
 staged window would then be evaluated.  Code that edits a cached array in place calls ``clear_engine_cache()``.
 """
+import functools
 import weakref
 
 import numpy as np
 
 from . import _lib as L
-from .engine import Engine, check_precision, check_tile_size, check_window_size, make_params
+from .engine import Engine, check_motion_path, check_precision, check_tile_size, check_window_size, make_params
 
 _CACHE = []            # [(refs tuple, key, Engine)] most-recent first
 _CACHE_SIZE = 2
@@ -126,11 +127,30 @@ def loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_
     return float(v[0]), _aux_dict(eng, aux[0], True)
 
 
-def _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size):
+def _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path='expanded'):
     eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
     if eng.motion_model is not model:
         eng.set_motion_model(model)
+    eng.set_motion_path(path)              # (every call: the engine is shared with the callables of the other paths)
     return eng
+
+
+def _value_and_grad_motion(path, coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
+                           scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, full_aux=False, aux_arrays=False,
+                           correlation_kind='mse', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32', *, model):
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux, correlation_kind)
+    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path)
+    v, g, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=True, want_aux=True)
+    return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
+
+
+def _motion_loss(path, coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
+                 scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None,
+                 window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32', *, model):
+    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
+    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path)
+    v, _, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=False, want_aux=True)
+    return float(v[0]), _aux_dict(eng, aux[0], True)
 
 
 def value_and_grad_motion_loss_func(coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
@@ -138,21 +158,28 @@ def value_and_grad_motion_loss_func(coeffs, xs, ys, ts, edges, edge_ts, alpha, b
                                     aux_arrays=False, correlation_kind='mse', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW,
                                     precision='fp32', *, model):
     """((final_loss, aux_info), grad (K,)) of loss_func on the field model.field(coeffs) of a motion.MotionModel, differentiated
-    with respect to the coefficients.  The field is at sensor size: the scaling method is not read."""
-    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux, correlation_kind)
-    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size)
-    v, g, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=True, want_aux=True)
-    return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
+    with respect to the coefficients.  The field is at sensor size: the scaling method is not read.
+    By the expanded path; motion_loss_funcs(path) gives the same callable on another."""
+    return _value_and_grad_motion('expanded', coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls,
+                                  sensor_size, scale_to_sensor_size_method, contrast_kind, full_aux, aux_arrays, correlation_kind, tile_size,
+                                  window_size, precision, model=model)
 
 
 def motion_loss_func(coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
                      scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse',
                      tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32', *, model):
     """(final_loss, aux_info) of loss_func on model.field(coeffs); forward only, every aux entry evaluated."""
-    p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
-    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size)
-    v, _, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=False, want_aux=True)
-    return float(v[0]), _aux_dict(eng, aux[0], True)
+    return _motion_loss('expanded', coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
+                        scale_to_sensor_size_method, contrast_kind, correlation_kind, tile_size, window_size, precision, model=model)
+
+
+def motion_loss_funcs(path='expanded'):
+    """(motion_loss_func, value_and_grad_motion_loss_func) evaluating by ``path``: 'expanded' | 'fused' | 'auto' as
+    Engine.set_motion_path takes it; the module's own pair is motion_loss_funcs('expanded').  The callables take
+    the arguments of that pair.  path is validated here, before any engine exists.  The forward-only callable evaluates every aux
+    entry, which needs the Theta image: with 'fused' it raises, with 'auto' it takes the expanded path."""
+    path = check_motion_path(path)
+    return functools.partial(_motion_loss, path), functools.partial(_value_and_grad_motion, path)
 
 
 def value_and_grad_handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma,

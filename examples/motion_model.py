@@ -1,7 +1,7 @@
 """Solve a parametric motion-field model instead of a theta grid: stage a batch of windows, minimise the
 objective over the six coefficients of an affine field per window in lockstep, and score the solved fields against the ground truth.
 
-    python3 examples/motion_model.py [--windows 3] [--events 20000] [--kind affine]
+    python3 examples/motion_model.py [--windows 3] [--events 20000] [--kind affine] [--path expanded|fused|auto]
 
 The scenes are synthetic (synth.make_window with the model's own field as ground-truth flow); with real data the windows come from
 staging.mvsec_datasamples / dsec_datasamples and the model of a calibrated camera is
@@ -21,6 +21,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--windows', type=int, default=3)
 ap.add_argument('--events', type=int, default=20000)
 ap.add_argument('--kind', default='affine', choices=['translation', 'similarity', 'affine', 'quadratic'])
+ap.add_argument('--path', default='expanded', choices=['expanded', 'fused', 'auto'],
+                help='how every step is evaluated: the field as an image, or the polynomial inside the event kernels (DESIGN.md section 21)')
 a = ap.parse_args()
 
 H, W, R = 96, 128, 3
@@ -37,6 +39,7 @@ params = engine.make_params(ALPHA, BETA, GAMMA, DELTA, 1)
 with engine.Engine((H, W), a.windows * a.events, max_refs=R, max_windows=a.windows) as eng:
     eng.set_windows(windows)
     eng.set_motion_model(model)
+    eng.set_motion_path(a.path)
     stats = {}
     results = bsol.minimize_motion(eng, model, np.zeros((a.windows, K)), params, maxiter=40, gtol=1e-6, stats=stats)
 c = np.stack([r.x for r in results])

@@ -29,7 +29,8 @@ extern "C" {
                                * 6: eincm_get_launch_policy; added since without a new version: eincm_rectify_events, eincm_remap_cubic, eincm_flow_decode,
                                *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory,
                                *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas), eincm_lbfgs_* (that BFGS with a limited-memory
-                               *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models) */
+                               *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models),
+                               *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -607,6 +608,17 @@ int eincm_loss_grad_motion(eincm_ctx* ctx, const double* coeffs, const eincm_par
                            eincm_aux* aux);
 /* The field alone: Theta (n_windows, H, W, 2) on the host. */
 int eincm_motion_field(eincm_ctx* ctx, const double* coeffs, double* Theta);
+/* eincm_loss_grad_motion by the fused path: the event kernels form the field of their source tile from the
+ * window's polynomial and reduce the tile's gradient to the twelve moments themselves; no Theta image and no dense gradient exist
+ * during the evaluation.  Same arguments and the same masked-window contract (value NaN, gradient 0, coefficients not read).  The
+ * value, the IWE stack and every image pass are the bits eincm_loss_grad_motion gives; the gradient is the same sum in another order.
+ * A window whose q = M c (or the bound of its field) is not finite sits the launch out: its value and gradient are NaN and the call
+ * returns EINCM_ERR_NONFINITE with the other windows' outputs written.  EINCM_ERR_UNSUPPORTED, with the reason in eincm_last_error,
+ * where the path does not apply: the TV term active (level <= 0 and gamma != 0), EINCM_PF_FULL_AUX, a splat window other than 3, an
+ * EINCM_CF_FP64 context; EINCM_ERR_STATE as eincm_loss_grad_motion.  eincm_get_scaled_theta, eincm_get_count_images and
+ * eincm_get_warped_events afterwards build the field from the evaluation's q. */
+int eincm_loss_grad_motion_fused(eincm_ctx* ctx, const double* coeffs, const eincm_params* p, const uint8_t* active, double* value, double* grad,
+                                 eincm_aux* aux);
 
 #ifdef __cplusplus
 }
