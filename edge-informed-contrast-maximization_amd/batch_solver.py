@@ -1023,7 +1023,8 @@ class BatchedMultipleLevelEINCMSolver:
 
     # -- staging -------------------------------------------------------------------------------------------------------
     def set_datasamples(self, windows):
-        """windows: B tuples (xs, ys, ts, edges, edge_ts)."""
+        """windows: B tuples (xs, ys, ts, edges, edge_ts), or (xs, ys, ts, edges, edge_ts, weights) with per-event weights or None
+        (Engine.set_windows): the tuples go to the engines as they are."""
         assert len(windows) == self.B
         n_tot = max(sum(len(windows[b][0]) for b in ix) for ix in self.groups)
         R = len(np.atleast_1d(windows[0][4]))

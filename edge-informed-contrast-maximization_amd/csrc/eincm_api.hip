@@ -95,6 +95,7 @@ struct StageArgs {
     int B, R; const int64_t* n_events;
     const int16_t* const* xs; const int16_t* const* ys; const double* const* ts; const double* const* edges; const double* edge_ts;
     uint32_t flags;
+    const float* const* weights = nullptr;      // eincm_set_windows_weighted: NULL, or per window its events' weights (NULL: ones)
 };
 
 // All host memory an asynchronous copy of a staging reads or writes.  stage_windows constructs it before the guard that drains the
@@ -103,7 +104,7 @@ struct StageScratch {
     std::vector<unsigned> cntmax; std::vector<double> dtmax;       // (B) most events on one source pixel, max |t - tau|
     bool edge_ts_uploaded = false;
     std::vector<BinBlock> blks; std::vector<int32_t> win_blk; int32_t misc[4]; std::vector<double> mom;   // device binning
-    std::vector<uint32_t> sxy; std::vector<double> st; std::vector<float> ef;                             // host binning
+    std::vector<uint32_t> sxy; std::vector<double> st; std::vector<float> ef; std::vector<float> sw;      // host binning
     std::vector<int> ishift;                                                                              // float64 mode
 };
 
@@ -150,6 +151,10 @@ struct eincm_ctx : PlanCtx {
     double* d_t = nullptr;         // (maxN)
     uint32_t* d_xy_g = nullptr;    // (maxN) the gather's copy: the same bins, every segment of the gather list sorted by source pixel and dealt to its threads (k_segsort)
     double* d_t_g = nullptr;       // (maxN)
+    // per-event weights of a weighted batch (stage.weighted), one copy per event layout: allocated by the first
+    // weighted staging of the context (ensure_weights), not read by an unweighted batch
+    float* d_w = nullptr;          // (maxN) in the order of d_xy
+    float* d_w_g = nullptr;        // (maxN) in the order of d_xy_g; during a device binning it first holds the weights as handed over
     std::vector<int32_t> h_tilecount;   // (B, ntiles) events per (window, tile) of the staged batch: what every segment list is cut from
     bool policy_evaluated = false; // an evaluation has chosen capacities since the last staging (eincm_get_launch_policy)
     // device-side staging (eincm_binning.hip.h)
@@ -582,7 +587,7 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
                 launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_POLY, 512>, dim3(c->splat.grid(g.R)), dim3(512),
                              (size_t)g.wincap * sizeof(float) + TS * TS * sizeof(double2) + POLY_SCRATCH_BYTES, g, c->splat.n, c->splat.d_items,
                              c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, c->splat.d_order, P.use_arg ? 1 : 0,
-                             (const double*)mo.h_q(c->maxB), ta);
+                             (const double*)mo.h_q(c->maxB), ta, (const float*)nullptr);
         }
         HIPCHK(c, hipGetLastError());
         c->fl.theta_dev = mo.h_q(c->maxB); c->fl.targ = ta;
@@ -654,9 +659,12 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
                 // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
                 auto go = [&](auto kernel) {
                     launch_timed(c, EINCM_STAGE_SPLAT, kernel, dim3(L.grid(g.R)), dim3(512), (size_t)g.wincap * sizeof(float) + theta_tile, g, L.n,
-                                 L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, L.d_order, use_arg, theta_dev, targ);
+                                 L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, L.d_order, use_arg, theta_dev, targ,
+                                 (const float*)(c->stage.weighted ? c->d_w : nullptr));
                 };
-                two_dof ? go(k_splat<THETA_CONST, 512>) : go(k_splat<THETA_TILE, 512>);
+                // a weighted batch (stage.weighted) runs the weighted instantiation; an unweighted one the code it always ran
+                if (c->stage.weighted) two_dof ? go(k_splat<THETA_CONST, 512, 1>) : go(k_splat<THETA_TILE, 512, 1>);
+                else                   two_dof ? go(k_splat<THETA_CONST, 512>) : go(k_splat<THETA_TILE, 512>);
             }
         }
     }
@@ -1032,9 +1040,16 @@ int eval_end_launch(eincm_ctx* c) {
                                      c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, g11, c->d_wc, c->d_gmax, L.d_order, use_arg,
                                      c->fl.theta_dev, c->fl.targ, P.h, P.w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p, (int)c->coarse_cap,
                                      P.grid_tail ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad,
-                                     (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth.p + (size_t)c->maxB * c->coarse_cap);
+                                     (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth.p + (size_t)c->maxB * c->coarse_cap,
+                                     (const float*)(c->stage.weighted ? (two_dof ? c->d_w : c->d_w_g) : nullptr));
                     };
-                    if (fused) {
+                    if (c->stage.weighted && !fused) {      // the weighted instantiations, cell for cell the unweighted choice below
+                        if (two_dof) go(k_gather<THETA_CONST, 0, NT, 0, 0, 1>, NT);
+                        else if (P.all_r) c->stage.wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1, 1>, NT_TILE);
+                        else if (c->stage.wide) P.proj ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 0, 1>, NT_TILE) : go(k_gather<THETA_TILE, 1, NT_TILE, 0, 0, 1>, NT_TILE);
+                        else              P.proj ? go(k_gather<THETA_TILE, 0, NT_TILE, 1, 0, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 0, 0, 1>, NT_TILE);
+                    }
+                    else if (fused) {
                         if (P.all_r) c->stage.wide ? go(k_gather<THETA_POLY, 1, NT_TILE, 0, 1>, NT_TILE) : go(k_gather<THETA_POLY, 0, NT_TILE, 0, 1>, NT_TILE);
                         else         c->stage.wide ? go(k_gather<THETA_POLY, 1, NT_TILE, 0>, NT_TILE) : go(k_gather<THETA_POLY, 0, NT_TILE, 0>, NT_TILE);
                     }
@@ -1438,6 +1453,22 @@ static int check_staging(eincm_ctx* c, const StageArgs& a) {
             if (f64_ishift(a.n_events[b]) < 40)
                 return fail(c, EINCM_ERR_UNSUPPORTED, "window %d: %lld events exceed the fp64 mode's IWE scale (2^-40 per tap)", b, (long long)a.n_events[b]);
     }
+    // per-event weights: the values first, on the host arrays; then what has no weighted form
+    if (const WeightRefusal r = check_weights(a.B, a.n_events, a.weights))
+        return fail(c, EINCM_ERR_ARG, "weight %lld of window %d is %g: weights are finite and within [0, 1]", (long long)r.index, r.win, (double)r.value);
+    if (batch_weighted(a.B, a.n_events, a.weights)) {
+        if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "per-event weights are not supported in fp64 mode (EINCM_CF_FP64)");
+        if (c->splat_size != 3)
+            return fail(c, EINCM_ERR_UNSUPPORTED, "per-event weights have the 3x3 splat window only, the context has %d (eincm_set_splat_window)", c->splat_size);
+        if (a.flags & EINCM_SW_DEFER_CONSTANTS) return fail(c, EINCM_ERR_UNSUPPORTED, "per-event weights are not supported in an event-sharded staging");
+    }
+    return EINCM_OK;
+}
+
+// The two weight buffers of a weighted batch, allocated by the first weighted staging of the context and kept from then on
+static int ensure_weights(eincm_ctx* c) {
+    if (!c->d_w) HIPCHK(c, c->mem.alloc_dev(c->d_w, (size_t)c->maxN));
+    if (!c->d_w_g) HIPCHK(c, c->mem.alloc_dev(c->d_w_g, (size_t)c->maxN));
     return EINCM_OK;
 }
 
@@ -1469,15 +1500,33 @@ static int upload_raw_events(eincm_ctx* c, const StageArgs& a) {
     return EINCM_OK;
 }
 
+// A weighted batch on the device path: the weights as handed over, window after window like the events, ones for a window without.
+// They go into d_w_g, which k_bin_scatter reads and k_segsort overwrites afterwards with the gather's order.
+static int upload_raw_weights(eincm_ctx* c, const StageArgs& a) {
+    int64_t off = 0;
+    for (int b = 0; b < a.B; ++b) {
+        const size_t nb = (size_t)a.n_events[b];
+        if (nb > 0 && a.weights[b]) HIPCHK(c, hipMemcpyAsync(c->d_w_g + off, a.weights[b], nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        else if (nb > 0) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_w_g + off), 0x3f800000 /* 1.0f */, nb, c->stream));
+        off += (int64_t)nb;
+    }
+    return EINCM_OK;
+}
+
 // The gather's copy of the binned events: every segment of its list sorted by source pixel and dealt to the threads that walk it
 // (k_segsort, from the binned time order, before the splat's copy is re-dealt in place); EINCM_NO_SEGSORT: a plain copy.
 static int copy_for_gather(eincm_ctx* c) {
     if (c->gather.n == 0) return EINCM_OK;
+    const bool wt = c->stage.weighted;        // the weights take the same way as the events
     if (c->stage.sort_segments) {
-        hipLaunchKernelGGL(k_segsort, dim3(std::min(c->gather.n, 8192)), dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
-                           c->d_xy, c->d_t, c->d_xy_g, c->d_t_g);
+        const dim3 grid(std::min(c->gather.n, 8192));
+        if (wt) hipLaunchKernelGGL(k_segsort<1>, grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
+                                   c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)c->d_w, c->d_w_g);
+        else hipLaunchKernelGGL(k_segsort<0>, grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
+                                c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)nullptr, (float*)nullptr);
         return EINCM_OK;
     }
+    if (wt) HIPCHK(c, hipMemcpyAsync(c->d_w_g, c->d_w, (size_t)c->stage.N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)c->stage.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)c->stage.N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return EINCM_OK;
@@ -1542,8 +1591,13 @@ static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
             c->h_wc[b].sE[r] = sE; c->h_wc[b].sEE[r] = sEE; c->h_wc[b].eabs[r] = eabs;
         }
     if (nblk > 0) {
-        hipLaunchKernelGGL(k_bin_scatter, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
-                           c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t);
+        if (P.weighted) {
+            if ((rc = upload_raw_weights(c, a))) return rc;
+            hipLaunchKernelGGL(k_bin_scatter<1>, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x,
+                               c->d_raw_y, c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)c->d_w_g, c->d_w);
+        } else
+        hipLaunchKernelGGL(k_bin_scatter<0>, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
+                           c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)nullptr, (float*)nullptr);
         hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, P.seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase,
                            c->gather.d_items);
         if ((rc = copy_for_gather(c))) return rc;
@@ -1551,8 +1605,10 @@ static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     if ((rc = build_list(c, c->gather, P.seg, false, g.ntiles, c->d_t_g, P.N))) return rc;
     c->splat.n = 0;
     if (nblk > 0) {
-        if (P.spread)
-            hipLaunchKernelGGL(k_spread, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t);
+        if (P.spread && P.weighted)
+            hipLaunchKernelGGL(k_spread<1>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, c->d_w);
+        else if (P.spread)
+            hipLaunchKernelGGL(k_spread<0>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, (float*)nullptr);
         // per window: first segment and max |t - tau| (needs the segment time ranges and the FIRST segmentation's itembase)
         HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, a.edge_ts, (size_t)a.B * a.R * sizeof(double), hipMemcpyHostToDevice, c->stream));
         sc.edge_ts_uploaded = true;
@@ -1579,7 +1635,8 @@ static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     const Geom& g = P.g;
     const size_t img = (size_t)g.H * g.W;
     int rc = EINCM_OK;
-    if (const EventRefusal r = bin_events(g, a.n_events, a.xs, a.ys, a.ts, a.edge_ts, P.N, c->h_tilecount, sc.sxy, sc.st, sc.cntmax, sc.dtmax))
+    if (const EventRefusal r = bin_events(g, a.n_events, a.xs, a.ys, a.ts, a.edge_ts, P.N, c->h_tilecount, sc.sxy, sc.st, sc.cntmax, sc.dtmax,
+                                          a.weights, P.weighted ? &sc.sw : nullptr))
         return refuse_event(c, a, r.win, r.index, r.bad_xy);
     sc.ef.resize((size_t)a.B * a.R * img);
     for (int b = 0; b < a.B; ++b) {
@@ -1590,6 +1647,7 @@ static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     if (P.N > 0) {
         HIPCHK(c, hipMemcpyAsync(c->d_xy, sc.sxy.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_t, sc.st.data(), (size_t)P.N * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        if (P.weighted) HIPCHK(c, hipMemcpyAsync(c->d_w, sc.sw.data(), (size_t)P.N * sizeof(float), hipMemcpyHostToDevice, c->stream));
         if ((rc = upload_raw_events(c, a))) return rc;
     }
     // (the gather's copy is a permutation inside the gather list's segments: their time ranges come from either copy)
@@ -1615,7 +1673,7 @@ static int finish_lists(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     if (c->gather.n > 0 && !P.host_binning) {     // event mask + most events on one source pixel, per tile from its LDS histogram
         HIPCHK(c, hipMemsetAsync(c->d_cntmax, 0, (size_t)a.B * sizeof(unsigned), c->stream));       // (before the synchronisation below: one per staging fewer)
         hipLaunchKernelGGL(k_tile_counts, dim3(g.ntiles, a.B), dim3(NT), 0, c->stream, g, c->d_tilebase, c->d_tilecount, c->d_xy,
-                           c->d_mask, c->d_cntmax);
+                           c->d_mask, c->d_cntmax, (const float*)(P.weighted ? c->d_w : nullptr));
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(sc.cntmax.data(), c->d_cntmax, (size_t)a.B * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     }
@@ -1625,7 +1683,8 @@ static int finish_lists(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     c->itembase_valid = !P.host_binning && c->gather.n > 0 && c->splat.n > 0;      // both tile scans ran on the device
     c->win_events.assign(a.n_events, a.n_events + a.B);
     if (c->gather.n > 0 && P.host_binning) {
-        hipLaunchKernelGGL(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, c->stream, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask);
+        hipLaunchKernelGGL(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, c->stream, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask,
+                           (const float*)(P.weighted ? c->d_w : nullptr));
         HIPCHK(c, hipGetLastError());
     }
     return EINCM_OK;
@@ -1651,9 +1710,10 @@ static int stage_windows(eincm_ctx* c, const StageArgs& a) {
     c->Theta_valid = false;
     c->motion.last_q.clear(); c->motion.seg0.clear();      // ... as do a fused evaluation's q and the windows' segment ranges
     c->bfgs.begun = false;           // the BFGS state belongs to the batch it was begun for
-    c->stage = plan_staging(*c, a.B, a.R, a.n_events, a.flags, live_knobs().stage);
+    c->stage = plan_staging(*c, a.B, a.R, a.n_events, a.flags, live_knobs().stage, a.weights);    // (an unweighted staging drops the weighted state with the plan)
     const StagePlan& P = c->stage;
     HIPCHK(c, hipSetDevice(c->device));
+    if (P.weighted && (rc = ensure_weights(c))) return rc;
     StageScratch sc;
     struct DrainOnExit { hipStream_t s; ~DrainOnExit() { (void)hipStreamSynchronize(s); } } drain_on_exit{c->stream};
     if (c->acc_dirty && (rc = clear_accumulators(c))) return rc;
@@ -1709,6 +1769,12 @@ int eincm_set_windows_ptrs(eincm_ctx* c, int n_windows, int n_refs, const int64_
                            const int16_t* const* ys, const double* const* ts, const double* const* edges, const double* edge_ts,
                            uint32_t flags) {
     return stage_windows(c, StageArgs{n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, flags});
+}
+
+int eincm_set_windows_weighted(eincm_ctx* c, int n_windows, int n_refs, const int64_t* n_events, const int16_t* const* xs,
+                               const int16_t* const* ys, const double* const* ts, const double* const* edges, const double* edge_ts,
+                               const float* const* weights, uint32_t flags) {
+    return stage_windows(c, StageArgs{n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, flags, weights});
 }
 
 // ---- event-sharded evaluation: forward half / [caller all-reduces the IWE stack] / finishing half ----
@@ -1988,7 +2054,8 @@ int eincm_get_count_images(eincm_ctx* c, uint32_t* counts) {
     HIPCHK(c, op.zero(d, n * sizeof(uint32_t)));
     const SegList& L = c->gather;
     if (L.n > 0)
-        HIPCHK(c, op.launch(k_count, dim3(L.grid(g.R)), dim3(NT), 0, g, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, d));
+        HIPCHK(c, op.launch(k_count, dim3(L.grid(g.R)), dim3(NT), 0, g, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, d,
+                             (const float*)(c->stage.weighted ? c->d_w : nullptr)));
     HIPCHK(c, op.down(counts, d, n * sizeof(uint32_t)));          // (host memory: the caller's)
     HIPCHK(c, op.sync());
     return EINCM_OK;
@@ -2628,6 +2695,9 @@ int eincm_set_splat_window(eincm_ctx* c, int window_size) {
     if (c->fp64 && window_size != 3)
         return fail(c, EINCM_ERR_UNSUPPORTED, "splat window size %d: fp64 mode (EINCM_CF_FP64) supports size 3 only", window_size);
     if (window_size == c->splat_size) return EINCM_OK;
+    if (c->staged && c->stage.weighted && window_size != 3)
+        return fail(c, EINCM_ERR_UNSUPPORTED, "splat window size %d: the staged batch carries per-event weights, which have the 3x3 splat window only",
+                    window_size);
     if (c->staged && (c->sharded_staging || c->constants_pending))
         return fail(c, EINCM_ERR_STATE, "the staged batch's window constants come from an event-sharded staging: set the splat window "
                                         "before eincm_set_windows");
@@ -3145,7 +3215,8 @@ int eincm_loss_grad_motion_fused(eincm_ctx* c, const double* coeffs, const eincm
                                  eincm_aux* aux) {
     if (!c) return EINCM_ERR_ARG;
     static const char* who = "eincm_loss_grad_motion_fused";
-    const MotionCtxState st{c->fp64, c->motion.set, c->staged, c->constants_pending, c->device_results, !c->fl.idle(), c->splat_size};
+    const MotionCtxState st{c->fp64, c->motion.set, c->staged, c->constants_pending, c->device_results, !c->fl.idle(), c->splat_size,
+                            c->staged && c->stage.weighted};
     if (const MotionRefusal r = motion_fused_supported(st, p)) return fail(c, r.code, "%s: %s", who, r.why);
     if (!coeffs || !p || !value) return fail(c, EINCM_ERR_ARG, "%s: null pointer argument", who);
     HIPCHK(c, hipSetDevice(c->device));

@@ -254,7 +254,7 @@ __device__ __forceinline__ void taps3x2(float fx, float fy, float scale_y, f2v& 
     kp.x = bx; kp.y = s * by;                    // d = +1
 }
 
-struct EvReg { uint32_t xy; double t; };   // one event in flight through the software pipeline of the event kernels
+struct EvReg { uint32_t xy; double t; float w; };   // one event in flight through the software pipeline of the event kernels (w: its weight, loaded and read by the weighted forms only)
 
 // Where an event's velocity Theta[y,x] comes from inside the event kernels.  A per-event global gather costs ~64 L1 cycles per
 // wave-instruction (64 lanes, 64 different cache lines) and was 2/3 of k_splat's time; every workgroup works on ONE source tile, so:
@@ -706,7 +706,7 @@ template <int NTH> struct SegWalk {
 // occupancy): load, then use, two trips per turn of the loop.
 template <bool PIPE, typename Load, typename Body>
 __device__ __forceinline__ void event_trips(int nfull, bool tail, const Load& load, const Body& body) {
-    EvReg T; T.xy = 0u; T.t = 0.0;
+    EvReg T; T.xy = 0u; T.t = 0.0; T.w = 0.0f;
     if (tail) load(T, nfull);
     if (PIPE) {
         if (nfull > 0) {
@@ -732,7 +732,7 @@ __device__ __forceinline__ void event_trips(int nfull, bool tail, const Load& lo
 // off4 = 4 * off, off8 = 8 * off: buffer loads take the trip as their scalar offset and the thread's share as their vector offset.
 // (With plain pointers the compiler folds the thread's offset into a 64-bit vector base outside the loop and adds the trip to it with
 // two v_lshl_add_u64 per event.)  The resources span exactly the segment's n events; a load past them would return zero.
-struct EvBuf { __amdgpu_buffer_rsrc_t xy, t; };
+struct EvBuf { __amdgpu_buffer_rsrc_t xy, t, w; };   // w: the events' weights, set and read by the weighted forms only (ev_buf_weights)
 __device__ __forceinline__ EvBuf ev_buf(const uint32_t* __restrict__ xy, const double* __restrict__ t, int n) {
     constexpr int RSRC_WORD3 = 0x00020000;          // raw buffer of dwords on gfx90a / gfx94x / gfx950
     EvBuf b;
@@ -740,9 +740,15 @@ __device__ __forceinline__ EvBuf ev_buf(const uint32_t* __restrict__ xy, const d
     b.t = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(t), 0, n * 8, RSRC_WORD3);
     return b;
 }
+__device__ __forceinline__ void ev_buf_weights(EvBuf& b, const float* __restrict__ w, int n) {
+    b.w = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(w), 0, n * 4, 0x00020000);
+}
+// WT: the weighted form - one more 4-byte load per event, at the offsets of xy
+template <int WT = 0>
 __device__ __forceinline__ void ev_load(EvReg& r, const EvBuf& b, int base, uint32_t off4, uint32_t off8) {
     r.xy = __builtin_amdgcn_raw_buffer_load_b32(b.xy, off4, base * 4, 0);
     r.t = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(b.t, off8, base * 8, 0));
+    if (WT) r.w = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b.w, off4, base * 4, 0));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -750,7 +756,9 @@ __device__ __forceinline__ void ev_load(EvReg& r, const EvBuf& b, int base, uint
 // A segment (<= MAX_CHUNK events) is accumulated in its u32 fixed-point window in LDS (exact integer ds_add_u32, scale
 // fix_shift(count)); the window is flushed to HBM once per segment.
 // ------------------------------------------------------------------------------------------------
-template <int TM, int NTH>   // TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE / THETA_POLY)
+// WT = 1: the weighted form, I_r[p] = sum_e w_e k_e(p): the weight (0 <= w <= 1, so the bound behind fix_shift
+// holds) enters the per-event tap scale in front of taps3x2, on every path the taps take.  WT = 0 reads neither ev_w nor EvReg.w.
+template <int TM, int NTH, int WT = 0>   // TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE / THETA_POLY)
 __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
         const Item* __restrict__ items,
         const uint32_t* __restrict__ ev_xy,    // x | y << 16, binned by (window, tile)
@@ -760,7 +768,8 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
         const Window* __restrict__ wins,       // (n_items, R) destination windows of this evaluation (k_theta / k_windows); unused for 2-DoF theta
         unsigned long long* __restrict__ acc,  // (B,R,H,W) u64 fixed point at 2^ACC_SHIFT, zero on entry (cleared by its consumer)
         const int32_t* __restrict__ order,     // (n_items) segments by decreasing length (block_to_work)
-        int use_arg, const double* __restrict__ theta_c, ThetaArg targ)   // 2-DoF theta (B,2): in the kernel arguments, or behind theta_c
+        int use_arg, const double* __restrict__ theta_c, ThetaArg targ,   // 2-DoF theta (B,2): in the kernel arguments, or behind theta_c
+        const float* __restrict__ ev_w = nullptr)   // WT: the events' weights, in the order of ev_xy
 {
     constexpr int theta_mode = TM;                // every branch on it below folds away: 8 % on both event kernels
     extern __shared__ __attribute__((aligned(16))) uint32_t ldsu[];
@@ -819,8 +828,9 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
 #elif defined(EINCM_ABL_S_NOLOAD)                 // timing-only: no event loads at all
     auto load_ev = [&](EvReg& r, int j) { const int e = j * NTH + tid; r.xy = ((uint32_t)(ty0 + ((e * 7) & 31)) << 16) | (uint32_t)(tx0 + (e & 31)); r.t = it.t_lo + 1e-9 * (double)e; };
 #else
-    const EvBuf evb = ev_buf(exy, et, n);
-    auto load_ev = [&](EvReg& r, int j) { ev_load(r, evb, j * NTH, off4, off8); };
+    EvBuf evb = ev_buf(exy, et, n);
+    if (WT) ev_buf_weights(evb, ev_w + it.begin, n);
+    auto load_ev = [&](EvReg& r, int j) { ev_load<WT>(r, evb, j * NTH, off4, off8); };
 #endif
     const float scy = INV_2PI * FIX_SCALE;          // one fixed-point scale per segment
     auto splat_ev = [&](const EvReg& ev) {
@@ -835,7 +845,7 @@ __global__ __launch_bounds__(NTH) void k_splat(Geom g, int n_items,
 #ifdef EINCM_ABL_S_NOMATH                            // timing-only: the atomics at their real addresses, no tap arithmetic
         km.x = km.y = k0.x = k0.y = kp.x = kp.y = 3.0f;
 #else
-        taps3x2(fx, fy, scy, km, k0, kp);
+        taps3x2(fx, fy, WT ? scy * ev.w : scy, km, k0, kp);
 #endif
         const int lx = irx - 1 - wn.ox, ly = iry - 1 - wn.oy;        // window coords of the top-left tap
         if ((unsigned)lx < (unsigned)(wn.ww - 2) && (unsigned)ly < (unsigned)(wn.wh - 2)) {
@@ -1517,7 +1527,7 @@ __device__ __forceinline__ void project_tile_to_cells(const Geom& g, int h, int 
         if (ay != 0.0) atomicAdd(o + 1, (unsigned long long)fix64_wide(ay));
     }
 }
-template <int TM, int WIDE, int NTH, int PROJ, int ALLR = 0>      // NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE / THETA_POLY)
+template <int TM, int WIDE, int NTH, int PROJ, int ALLR = 0, int WT = 0>      // WT = 1: the weighted form, dL/dw_e times w_e (see k_splat); NTH threads per workgroup: 256, or 512 where the LDS footprint allows only 3 workgroups per CU (THETA_TILE); TM: the theta mode as a compile-time constant (THETA_CONST / THETA_TILE / THETA_POLY)
 __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_items,      // WIDE: 61-bit fixed point per event (tiny windows, see grad_shift_pixel)
         const Item* __restrict__ items, const uint32_t* __restrict__ ev_xy, const double* __restrict__ ev_t,
         const double* __restrict__ Theta, const double* __restrict__ edge_ts,
@@ -1536,7 +1546,8 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         // tail (PROJ only, tail != 0): the workgroup of a window that finishes LAST turns the window's i64 cell sums into dL/dtheta and
         // writes it where the host reads it - what k_final did in a launch of its own (7-8 us of a 65 us evaluation)
         int tail, unsigned* __restrict__ ticket, const int32_t* __restrict__ win_item0, double* __restrict__ grad_out,
-        double tv_gamma, const double* __restrict__ tvparts, long long* __restrict__ gth_tv)   // tail with the TV term (gamma != 0 at level 0)
+        double tv_gamma, const double* __restrict__ tvparts, long long* __restrict__ gth_tv,   // tail with the TV term (gamma != 0 at level 0)
+        const float* __restrict__ ev_w = nullptr)   // WT: the events' weights, in the order of ev_xy
 {
     // (ALLR = 1, theta grids on big batches: ONE workgroup per segment walks all R reference times - grid = segments, not
     // segments x R -, so that the Theta tile, the accumulator clear, the projection and the ticket are paid once per segment)
@@ -1645,6 +1656,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         }
         float gwx, gwy;
         event_dLdw(g, wn, wp, lds, G_at, x, y, vcur, dt, gwx, gwy);
+        if (WT) { gwx *= ev.w; gwy *= ev.w; }     // w <= 1: the bound behind grad_shift_pixel holds
         if (direct11) {          // theta (1,1,2): Theta is constant, dL/dtheta = sum over all events; no per-pixel image needed.
             // fp32 over the thread's own <= 64 terms (their rounding errors are independent across 10^6 threads and average out:
             // measured 1e-9 relative on the gradient), fp64 from there on
@@ -1657,7 +1669,8 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
     };
     // the staged layout (SegWalk): a half of the segment is K coalesced steps of 256 threads, the last one a prefix
     const SegWalk<NTH> walk(n, tid);
-    const EvBuf evb = ev_buf(exy, et, n);
+    EvBuf evb = ev_buf(exy, et, n);
+    if (WT) ev_buf_weights(evb, ev_w + it.begin, n);
     // Steps [0, K) of half c by the event loop of both kernels (event_trips): the K - 1 full steps, then the prefix.  The half's
     // start rides in the thread's fixed offset (a 512-thread workgroup walks both halves at once), the step in the scalar base.
     auto walk_half = [&](int c) {
@@ -1666,7 +1679,7 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
         // no pipeline here, 2-DoF theta included: three events in flight take the 2-DoF gather from 68 to 92 VGPRs, 7 to 5 waves per
         // SIMD, and the kernel from 82 to 88 us (profiles/event_loop_trim.md) - its latency is covered by occupancy
         event_trips<false>(max(K - 1, 0), K > 0 && walk.tt < rem,
-                              [&](EvReg& ev, int j) { ev_load(ev, evb, j * 256, off4, off8); }, gather_ev);
+                              [&](EvReg& ev, int j) { ev_load<WT>(ev, evb, j * 256, off4, off8); }, gather_ev);
     };
     for (int rr = r; ; ) {                        // one reference time, or all of them (all_r)
 #ifndef EINCM_ABL_G_NOEVENTS
@@ -1780,9 +1793,11 @@ __global__ __launch_bounds__(NTH, (ALLR ? 6 : 1)) void k_gather(Geom g, int n_it
 // events_to_pdf_frame, event_utils.py:32-33,59).  Not on the evaluation path: it exposes the fp64 warp + half-to-even
 // rounding decisions as an integer image that must equal the oracle's bit for bit.  grid as k_splat (block_to_work).
 // ------------------------------------------------------------------------------------------------
+// ev_w (or nullptr: an unweighted batch): an event of weight 0 is not counted.
 __global__ __launch_bounds__(NT) void k_count(Geom g, int n_items, const Item* __restrict__ items, const uint32_t* __restrict__ ev_xy,
                                                const double* __restrict__ ev_t, const double* __restrict__ Theta,
-                                               const double* __restrict__ edge_ts, uint32_t* __restrict__ counts)
+                                               const double* __restrict__ edge_ts, uint32_t* __restrict__ counts,
+                                               const float* __restrict__ ev_w = nullptr)
 {
     int item, r;
     if (!block_to_work(n_items, g.R, nullptr, item, r)) return;
@@ -1791,6 +1806,7 @@ __global__ __launch_bounds__(NT) void k_count(Geom g, int n_items, const Item* _
     const double* __restrict__ Th = Theta + (size_t)it.win * g.H * g.W * 2;
     uint32_t* __restrict__ img = counts + ((size_t)it.win * g.R + r) * g.H * g.W;
     for (int i = threadIdx.x; i < it.count; i += NT) {
+        if (ev_w && !(ev_w[it.begin + i] > 0.0f)) continue;
         const uint32_t xy = ev_xy[it.begin + i];
         const double dt = ev_t[it.begin + i] - tau;
         const int x = xy & 0xffff, y = xy >> 16;
@@ -1829,13 +1845,15 @@ __global__ __launch_bounds__(NT) void k_warp_events(Geom g, int win, long long n
 // ------------------------------------------------------------------------------------------------
 // k_mask: event-presence mask (event_utils.py:64-76 / theta_utils.py:59-71).  grid-stride over events.
 // ------------------------------------------------------------------------------------------------
+// ev_w (or nullptr: an unweighted batch): an event of weight 0 is not in the mask.
 __global__ void k_mask(Geom g, const Item* __restrict__ items, int n_items, const uint32_t* __restrict__ ev_xy,
-                       uint8_t* __restrict__ mask)
+                       uint8_t* __restrict__ mask, const float* __restrict__ ev_w = nullptr)
 {
     for (int it = blockIdx.x; it < n_items; it += gridDim.x) {
         const Item I = items[it];
         uint8_t* m = mask + (size_t)I.win * g.H * g.W;
         for (int i = threadIdx.x; i < I.count; i += blockDim.x) {
+            if (ev_w && !(ev_w[I.begin + i] > 0.0f)) continue;
             const uint32_t xy = ev_xy[I.begin + i];
             m[(size_t)(xy >> 16) * g.W + (xy & 0xffff)] = 1;
         }
@@ -1845,7 +1863,8 @@ __global__ void k_mask(Geom g, const Item* __restrict__ items, int n_items, cons
 // k_tile_counts: the same mask, plus the largest number of events on one source pixel (WinConst.cntmax), per (tile, window):
 // LDS histogram of the tile's events.  grid (ntiles, B).  cntmax (B) zeroed beforehand (atomicMax: order-independent).
 __global__ __launch_bounds__(NT) void k_tile_counts(Geom g, const int32_t* __restrict__ tilebase, const int32_t* __restrict__ tilecount,
-                                                     const uint32_t* __restrict__ ev_xy, uint8_t* __restrict__ mask, unsigned* __restrict__ cntmax)
+                                                     const uint32_t* __restrict__ ev_xy, uint8_t* __restrict__ mask, unsigned* __restrict__ cntmax,
+                                                     const float* __restrict__ ev_w = nullptr)   // (or nullptr: an unweighted batch) events of weight 0 are left out of both
 {
     __shared__ unsigned hist[TS * TS];
     __shared__ unsigned wmax[NWAVE];
@@ -1855,6 +1874,7 @@ __global__ __launch_bounds__(NT) void k_tile_counts(Geom g, const int32_t* __res
     __syncthreads();
     const int base = tilebase[(size_t)b * g.ntiles + tile], cnt = tilecount[(size_t)b * g.ntiles + tile];
     for (int i = threadIdx.x; i < cnt; i += NT) {
+        if (ev_w && !(ev_w[base + i] > 0.0f)) continue;
         const uint32_t xy = ev_xy[base + i];
         atomicAdd(&hist[((xy >> 11) & (31u << 5)) | (xy & 31u)], 1u);
     }

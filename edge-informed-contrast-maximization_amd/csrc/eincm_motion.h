@@ -101,6 +101,7 @@ inline void motion_project(const eincm_motion_model& m, const double* mu, double
 struct MotionCtxState {
     bool fp64, model_set, staged, constants_pending, device_results, in_flight;
     int splat_size;                                 // eincm_set_splat_window's window_size
+    bool weighted = false;                          // the staged batch carries per-event weights
 };
 struct MotionRefusal {
     int code;                                       // EINCM_OK: the fused path applies
@@ -121,6 +122,7 @@ inline MotionRefusal motion_fused_supported(const MotionCtxState& s, const eincm
     if (p && (p->flags & EINCM_PF_FULL_AUX)) return {EINCM_ERR_UNSUPPORTED, "EINCM_PF_FULL_AUX needs the Theta image during the evaluation: use eincm_loss_grad_motion"};
     if (p && p->cur_pyr_lvl <= 0 && p->gamma != 0.0)
         return {EINCM_ERR_UNSUPPORTED, "the TV term (level 0, gamma != 0) needs the Theta image during the evaluation: use eincm_loss_grad_motion"};
+    if (s.weighted) return {EINCM_ERR_UNSUPPORTED, "the fused path has no weighted form (the staged batch carries per-event weights): use eincm_loss_grad_motion"};
     return {EINCM_OK, nullptr};
 }
 

@@ -253,8 +253,11 @@ struct EventRefusal {
 inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int16_t* const* xs, const int16_t* const* ys,
                                const double* const* ts, const double* edge_ts, int64_t N, std::vector<int32_t>& tilecount,
                                std::vector<uint32_t>& sxy, std::vector<double>& st, std::vector<unsigned>& cntmax,
-                               std::vector<double>& dtmax) {
+                               std::vector<double>& dtmax, const float* const* weights = nullptr, std::vector<float>* sw = nullptr) {
+    // sw (a weighted batch): the weights in the order of sxy, ones for a window without (weights[b] NULL); events of weight 0 are
+    // not counted into cntmax
     const int H = g.H, W = g.W;
+    if (sw) sw->resize((size_t)std::max<int64_t>(N, 1));
     tilecount.assign((size_t)g.B * g.ntiles, 0);
     sxy.resize((size_t)std::max<int64_t>(N, 1));
     st.resize((size_t)std::max<int64_t>(N, 1));
@@ -263,6 +266,7 @@ inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int
     for (int b = 0; b < g.B; ++b) {
         const int64_t n = n_events[b];
         const int16_t* x = xs[b]; const int16_t* y = ys[b]; const double* t = ts[b];
+        const float* wb = (sw && weights) ? weights[b] : nullptr;
         std::fill(cnt.begin(), cnt.end(), 0);
         for (int64_t i = 0; i < n; ++i) {
             for (int r = 0; r < g.R; ++r) dtmax[b] = std::max(dtmax[b], std::fabs(t[i] - edge_ts[b * g.R + r]));
@@ -272,7 +276,8 @@ inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int
         }
         {   // most events on one source pixel
             std::vector<uint32_t> pc((size_t)H * W, 0u);
-            for (int64_t i = 0; i < n; ++i) cntmax[b] = std::max(cntmax[b], ++pc[(size_t)y[i] * W + x[i]]);
+            for (int64_t i = 0; i < n; ++i)
+                if (!wb || wb[i] > 0.0f) cntmax[b] = std::max(cntmax[b], ++pc[(size_t)y[i] * W + x[i]]);
         }
         for (int k = 0; k < g.ntiles; ++k) tilecount[(size_t)b * g.ntiles + k] = (int32_t)cnt[k + 1];
         for (int k = 0; k < g.ntiles; ++k) cnt[k + 1] += cnt[k];
@@ -282,6 +287,7 @@ inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int
             const int64_t d = base + pos[tile]++;
             sxy[d] = (uint32_t)(uint16_t)x[i] | ((uint32_t)(uint16_t)y[i] << 16);
             st[d] = t[i];
+            if (sw) (*sw)[d] = wb ? wb[i] : 1.0f;
         }
         base += n;
     }
@@ -338,7 +344,33 @@ struct StagePlan {
     bool host_binning = false;          // the host sorts the events by (window, tile), not the kernels of eincm_binning.hip.h
     bool defer_constants = false;       // EINCM_SW_DEFER_CONSTANTS: the caller sums the shards' IUEs before the window constants are formed
     bool wide = false;                  // a window has a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel)
+    bool weighted = false;              // a window with events carries per-event weights: the payload ev_w rides beside ev_xy / ev_t and the event kernels run their weighted forms
 };
+
+// Does a staging carry per-event weights?  weights: NULL, or one pointer per window, NULL where a window's weights are all ones.
+// Weights of a window without events change nothing, so they do not make the batch a weighted one.
+inline bool batch_weighted(int n_windows, const int64_t* n_events, const float* const* weights) {
+    if (!weights) return false;
+    for (int b = 0; b < n_windows; ++b) if (weights[b] && n_events[b] > 0) return true;
+    return false;
+}
+
+// The first weight a staging refuses: not finite, or outside [0, 1] (the bounds behind both fixed-point scales assume w <= 1, and
+// neither accumulator is signed)
+struct WeightRefusal {
+    int win = -1; int64_t index = 0; float value = 0.0f;
+    explicit operator bool() const { return win >= 0; }
+};
+inline WeightRefusal check_weights(int n_windows, const int64_t* n_events, const float* const* weights) {
+    if (!weights) return WeightRefusal{};
+    for (int b = 0; b < n_windows; ++b) {
+        const float* w = weights[b];
+        if (!w) continue;
+        for (int64_t i = 0; i < n_events[b]; ++i)
+            if (!(w[i] >= 0.0f && w[i] <= 1.0f)) return WeightRefusal{b, i, w[i]};     // (a NaN fails both comparisons)
+    }
+    return WeightRefusal{};
+}
 
 // What the planning reads of a context; eincm_ctx derives from it, so both plans take the context by const reference.
 struct PlanCtx {
@@ -372,8 +404,10 @@ struct StageKnobs {
 };
 
 // Every decision of one staging, from the context and the checked arguments.  No HIP calls, no side effects.
-inline StagePlan plan_staging(const PlanCtx& c, int n_windows, int n_refs, const int64_t* n_events, uint32_t flags, const StageKnobs& k) {
+inline StagePlan plan_staging(const PlanCtx& c, int n_windows, int n_refs, const int64_t* n_events, uint32_t flags, const StageKnobs& k,
+                              const float* const* weights = nullptr) {
     StagePlan P;
+    P.weighted = batch_weighted(n_windows, n_events, weights);
     const int H = c.H, W = c.W;
     Geom& g = P.g;
     g.H = H; g.W = W; g.R = n_refs; g.B = n_windows;

@@ -456,9 +456,43 @@ def check_motion_path(path):
     return path
 
 
-def motion_fused_refusal(precision, splat_window, params):
+def check_event_weights(weights, n):
+    """Per-event weights of one window as the contiguous float32 array staging hands over: ``n`` values, finite and
+    within [0, 1], rounded to float32 once, here.  Anything else is a ValueError, raised before any library call."""
+    w = np.asarray(weights)
+    if w.dtype.kind not in 'fiub':
+        raise ValueError(f'weights must be numbers, got dtype {w.dtype}')
+    if w.shape != (int(n),):
+        raise ValueError(f'weights must be ({int(n)},), one per event, got {w.shape}')
+    if w.size:
+        # two passes and no copy of a float32 array (a batch of 8 x 10^6 weights is staged in milliseconds); a NaN anywhere makes both NaN,
+        # and the range is checked on the values as given, before the rounding
+        lo, hi = float(w.min()), float(w.max())
+        if not (np.isfinite(lo) and np.isfinite(hi)):
+            raise ValueError('weights must be finite')
+        if lo < 0.0 or hi > 1.0:
+            raise ValueError(f'weights must lie within [0, 1], got {lo if lo < 0.0 else hi!r} (signed weights are out of scope; larger '
+                             'ones would break the fixed-point bounds: scale them down)')
+    return np.ascontiguousarray(w, dtype=np.float32)
+
+
+def event_weights_refusal(precision, splat_window, sharded=False):
+    """Why a weighted batch cannot be staged on an engine of this precision and splat window (not built), or
+    None.  csrc/eincm_api.hip (check_staging) refuses the same."""
+    if precision == 'fp64':
+        return 'per-event weights are not supported in fp64 mode'
+    if int(splat_window) != 3:
+        return f'per-event weights have the 3x3 splat window only, the engine has {int(splat_window)}'
+    if sharded:
+        return 'per-event weights are not supported by the event-sharded engine'
+    return None
+
+
+def motion_fused_refusal(precision, splat_window, params, weighted=False):
     """Why the fused path does not apply to this engine and these parameters (csrc/eincm_motion.h: motion_fused_supported, the part of
-    it that Python can see before a GPU call), or None."""
+    it that Python can see before a GPU call), or None.  weighted: the staged batch carries per-event weights."""
+    if weighted:
+        return 'the fused motion path has no weighted form: the staged batch carries per-event weights'
     if precision == 'fp64':
         return 'the fused motion path is not supported in fp64 mode'
     if int(splat_window) != 3:
@@ -529,6 +563,7 @@ class Engine:
         self.flow_eval_windows = 0         # windows of the staged flow evaluation (flow_eval_stage)
         self.motion_model = None           # the motion.MotionModel of loss_grad_motion / motion_field (set_motion_model)
         self.motion_path = 'expanded'      # how loss_grad_motion evaluates (set_motion_path): 'expanded' | 'fused' | 'auto'
+        self._weighted = False             # the staged batch carries per-event weights (set_windows; the property `weighted`)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -586,9 +621,19 @@ class Engine:
 
     # -- staging ----------------------------------------------------------------------------------
     def set_windows(self, windows, defer_constants=False):
-        """windows: list of (xs, ys, ts, edges, edge_ts) tuples (the reference's datasample tuple).
+        """windows: list of (xs, ys, ts, edges, edge_ts) tuples (the reference's datasample tuple), or of 6-tuples whose last element
+        is the window's per-event weights (check_event_weights) or None for ones - the two may be mixed.
         defer_constants: event-sharded mode (see sharding.ShardedEngine): stage only, finish with finish_constants()."""
         B = len(windows)
+        for b, w in enumerate(windows):
+            if len(w) not in (5, 6):
+                raise ValueError(f'window {b}: a (xs, ys, ts, edges, edge_ts) or (xs, ys, ts, edges, edge_ts, weights) tuple, got {len(w)} elements')
+        ws = [None if len(w) == 5 or w[5] is None else check_event_weights(w[5], len(w[0])) for w in windows]
+        weighted = any(w is not None and w.size > 0 for w in ws)      # (weights of a window without events change nothing)
+        if weighted:
+            why = event_weights_refusal(self.precision, self.splat_window, sharded=defer_constants)
+            if why is not None:
+                raise ValueError(why)
         R = len(np.atleast_1d(windows[0][4]))
         n = np.array([len(w[0]) for w in windows], dtype=np.int64)
         # every window's arrays go over as they are (one pointer per window): no host-side concatenation of the batch
@@ -608,17 +653,31 @@ class Engine:
         one = np.zeros(1, np.int16), np.zeros(1, np.float64)           # a valid address for empty windows
         def ptrs(arrs, dummy):
             return (C.c_void_p * B)(*[(a if a.size else dummy).ctypes.data for a in arrs])
-        rc = self._lib.eincm_set_windows_ptrs(self._ctx, B, R, n.ctypes.data_as(C.POINTER(C.c_int64)),
-                                              ptrs(xs, one[0]), ptrs(ys, one[0]), ptrs(ts, one[1]), ptrs(edges, one[1]),
-                                              _dp(edge_ts), L.SW_DEFER_CONSTANTS if defer_constants else 0)
+        flags = L.SW_DEFER_CONSTANTS if defer_constants else 0
+        if weighted:        # one float pointer per window, NULL where a window has none
+            wp = (C.c_void_p * B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
+            rc = self._lib.eincm_set_windows_weighted(self._ctx, B, R, n.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                      ptrs(xs, one[0]), ptrs(ys, one[0]), ptrs(ts, one[1]), ptrs(edges, one[1]),
+                                                      _dp(edge_ts), wp, flags)
+        else:
+            rc = self._lib.eincm_set_windows_ptrs(self._ctx, B, R, n.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                  ptrs(xs, one[0]), ptrs(ys, one[0]), ptrs(ts, one[1]), ptrs(edges, one[1]),
+                                                  _dp(edge_ts), flags)
+        self._weighted = False          # (a refused staging leaves nothing staged)
         self._check(rc)
         if B != self.B:
             self._io = {}
         self.B, self.R = B, R
         self.n_events = n
+        self._weighted = weighted
 
-    def set_window(self, xs, ys, ts, edges, edge_ts):
-        self.set_windows([(xs, ys, ts, edges, edge_ts)])
+    def set_window(self, xs, ys, ts, edges, edge_ts, weights=None):
+        self.set_windows([(xs, ys, ts, edges, edge_ts, weights)])
+
+    @property
+    def weighted(self):
+        """The staged batch carries per-event weights (some window was handed weights; all-ones weights count)."""
+        return getattr(self, '_weighted', False)
 
     # -- evaluation -------------------------------------------------------------------------------
     def loss_grad(self, theta, params, want_grad=True, want_aux=False, allow_nonfinite=True, active=None):
@@ -743,7 +802,7 @@ class Engine:
         c = check_motion_coeffs(coeffs, self.B, self.motion_model)
         fused = False
         if path != 'expanded':
-            why = motion_fused_refusal(self.precision, self.splat_window, params)
+            why = motion_fused_refusal(self.precision, self.splat_window, params, self.weighted)
             if why is not None and path == 'fused':
                 raise ValueError(why)
             fused = why is None and (path == 'fused' or motion_auto_takes_fused(self.B, int(np.sum(self.n_events)), self.R))
@@ -931,8 +990,10 @@ class Engine:
 
     def set_splat_window(self, window_size):
         """Splat window size of every IWE of this context (events_to_pdf_frame's window_size, default 3).  On a
-        staged batch the window constants are formed again.  fp64 engines accept 3 only."""
+        staged batch the window constants are formed again.  fp64 engines accept 3 only, and so does a staged weighted batch."""
         s = check_window_size(window_size)
+        if self.weighted and s != 3:
+            raise ValueError(event_weights_refusal(self.precision, s))
         self._check(self._lib.eincm_set_splat_window(self._ctx, s))
         self.splat_window = s
 

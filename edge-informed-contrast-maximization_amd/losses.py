@@ -17,6 +17,10 @@ device-resident ``*args``: engines are cached by the identity of the (xs, ys, ts
 immutable, numpy arrays are not: a cheap content fingerprint (<= 256 strided samples of every array plus its last element)
 is a BEST-EFFORT check for in-place edits - an edit of a few elements between two calls can go unnoticed, and the stale
 staged window would then be evaluated.  Code that edits a cached array in place calls ``clear_engine_cache()``.
+
+``event_weights=`` (every callable; None by default) hands the window's per-event weights to the staging; the
+array joins the five others in the cache's identity and fingerprint.  It stands in front of ``precision``, which stays the last
+parameter of the reference-shaped callables.
 """
 import functools
 import weakref
@@ -48,15 +52,17 @@ def _fingerprint(arrs):
     return hash(tuple(parts))
 
 
-def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp32', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW):
+def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp32', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW,
+               event_weights=None):
     """Engine holding this window (staged on first use; reused while the same, unmodified array objects are passed).  One engine per
     precision: 'fp64' is the float64 mode (Engine(..., precision='fp64')).  tile_size: (tile_h, tile_w) of the adaptive objective
     kinds, set on the engine (None: the default 32 x 42).  window_size: the splat window of every IWE (events_to_pdf_frame's
-    window_size, 1..7, default 3), set on the engine."""
+    window_size, 1..7, default 3), set on the engine.  event_weights: per-event weights of the window (engine.check_event_weights; DESIGN.md
+    section 22) or None; the array is part of the cache's identity and fingerprint like the five others."""
     check_precision(precision)
     tiles = L.DEFAULT_OBJECTIVE_TILE if tile_size is None else check_tile_size(tile_size, sensor_size)
     window = check_window_size(window_size)
-    eng = _engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device, precision)
+    eng = _engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device, precision, event_weights)
     if eng.objective_tiles != tiles:
         eng.set_objective_tiles(tiles)
     if eng.splat_window != window:
@@ -64,8 +70,10 @@ def engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device=0, precision='fp3
     return eng
 
 
-def _engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device, precision):
+def _engine_for(xs, ys, ts, edges, edge_ts, sensor_size, device, precision, event_weights=None):
     arrs = tuple(_as_np(a) for a in (xs, ys, ts, edges, edge_ts))
+    if event_weights is not None:          # a sixth array of the key, the identity check and the fingerprint; staged by set_window
+        arrs += (_as_np(event_weights),)
     fp = _fingerprint(arrs)
     key = (tuple(int(s) for s in sensor_size), device, precision) + tuple((a.shape, a.dtype.str) for a in arrs)
     for i, (refs, k, eng) in enumerate(_CACHE):
@@ -108,27 +116,30 @@ def _aux_dict(eng, a, with_arrays):
 def value_and_grad_loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls,
                              sensor_size, scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG,
                              full_aux=False, aux_arrays=False, correlation_kind='mse', tile_size=None,
-                             window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
+                             window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32'):
     """((final_loss, aux_info), grad) — the shape jax.value_and_grad(loss_func, has_aux=True) returns.  precision='fp64': the engine's
     float64 mode (what the reference computes with jax_enable_x64: true)."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size,
+                     event_weights=event_weights)
     v, g, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=True, want_aux=True)
     return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
 
 
 def loss_func(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
               scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse',
-              tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
+              tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32'):
     """(final_loss, aux_info) as losses.py:108-205; forward only, every aux entry evaluated."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size,
+                     event_weights=event_weights)
     v, _, aux = eng.loss_grad(np.asarray(theta, dtype=np.float64), p, want_grad=False, want_aux=True)
     return float(v[0]), _aux_dict(eng, aux[0], True)
 
 
-def _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path='expanded'):
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
+def _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path='expanded', event_weights=None):
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size,
+                     event_weights=event_weights)
     if eng.motion_model is not model:
         eng.set_motion_model(model)
     eng.set_motion_path(path)              # (every call: the engine is shared with the callables of the other paths)
@@ -137,18 +148,18 @@ def _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, ti
 
 def _value_and_grad_motion(path, coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
                            scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, full_aux=False, aux_arrays=False,
-                           correlation_kind='mse', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32', *, model):
+                           correlation_kind='mse', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32', *, model):
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, full_aux, correlation_kind)
-    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path)
+    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path, event_weights)
     v, g, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=True, want_aux=True)
     return (float(v[0]), _aux_dict(eng, aux[0], aux_arrays)), g[0]
 
 
 def _motion_loss(path, coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
                  scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None,
-                 window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32', *, model):
+                 window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32', *, model):
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, True, correlation_kind)
-    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path)
+    eng = _motion_engine(model, xs, ys, ts, edges, edge_ts, sensor_size, precision, tile_size, window_size, path, event_weights)
     v, _, aux = eng.loss_grad_motion(np.asarray(coeffs, dtype=np.float64), p, want_grad=False, want_aux=True)
     return float(v[0]), _aux_dict(eng, aux[0], True)
 
@@ -156,21 +167,21 @@ def _motion_loss(path, coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, d
 def value_and_grad_motion_loss_func(coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
                                     scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, full_aux=False,
                                     aux_arrays=False, correlation_kind='mse', tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW,
-                                    precision='fp32', *, model):
+                                    event_weights=None, precision='fp32', *, model):
     """((final_loss, aux_info), grad (K,)) of loss_func on the field model.field(coeffs) of a motion.MotionModel, differentiated
     with respect to the coefficients.  The field is at sensor size: the scaling method is not read.
     By the expanded path; motion_loss_funcs(path) gives the same callable on another."""
     return _value_and_grad_motion('expanded', coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls,
                                   sensor_size, scale_to_sensor_size_method, contrast_kind, full_aux, aux_arrays, correlation_kind, tile_size,
-                                  window_size, precision, model=model)
+                                  window_size, event_weights, precision, model=model)
 
 
 def motion_loss_func(coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
                      scale_to_sensor_size_method='bilinear', contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse',
-                     tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32', *, model):
+                     tile_size=None, window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32', *, model):
     """(final_loss, aux_info) of loss_func on model.field(coeffs); forward only, every aux entry evaluated."""
     return _motion_loss('expanded', coeffs, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, n_pyr_lvls, sensor_size,
-                        scale_to_sensor_size_method, contrast_kind, correlation_kind, tile_size, window_size, precision, model=model)
+                        scale_to_sensor_size_method, contrast_kind, correlation_kind, tile_size, window_size, event_weights, precision, model=model)
 
 
 def motion_loss_funcs(path='expanded'):
@@ -185,10 +196,11 @@ def motion_loss_funcs(path='expanded'):
 def value_and_grad_handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma,
                                       delta, cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
                                       contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None,
-                                      window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
+                                      window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32'):
     """(loss, d loss / d alpha_handover) of losses.py:269-276."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size,
+                     event_weights=event_weights)
     v, dv = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=True)
     return float(v[0]), float(dv[0])
 
@@ -196,19 +208,20 @@ def value_and_grad_handover_loss_func(alpha_handover, prev_theta, theta, xs, ys,
 def handover_loss_func(alpha_handover, prev_theta, theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta,
                        cur_pyr_lvl, n_pyr_lvls, sensor_size, scale_to_sensor_size_method='bilinear',
                        contrast_kind=L.CONTRAST_GRAD_MAG, correlation_kind='mse', tile_size=None,
-                       window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
+                       window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32'):
     """loss only, as losses.py:208-276."""
     p = make_params(alpha, beta, gamma, delta, cur_pyr_lvl, scale_to_sensor_size_method, contrast_kind, False, correlation_kind)
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, tile_size=tile_size, window_size=window_size,
+                     event_weights=event_weights)
     v, _ = eng.handover_loss_grad(float(np.asarray(alpha_handover).reshape(-1)[0]), prev_theta, theta, p, want_grad=False)
     return float(v[0])
 
 
 def compute_loss_objectives(theta, xs, ys, ts, edges, edge_ts, sensor_size, warped_events=True,
-                            window_size=L.DEFAULT_SPLAT_WINDOW, precision='fp32'):
+                            window_size=L.DEFAULT_SPLAT_WINDOW, event_weights=None, precision='fp32'):
     """losses.py:49-105 on a full-resolution theta (H,W,2): every key of the reference dict.  The per-event ``warped_xs`` /
     ``warped_ys`` ((R, n_events) float64, read by plotters only) cost a 2*R*n_events*8-byte copy: ``warped_events=False`` skips them."""
-    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, window_size=window_size)
+    eng = engine_for(xs, ys, ts, edges, edge_ts, sensor_size, precision=precision, window_size=window_size, event_weights=event_weights)
     d = eng.objectives(np.asarray(theta, dtype=np.float64))[0]
     if warped_events:
         d['warped_xs'], d['warped_ys'] = eng.warped_events(0)

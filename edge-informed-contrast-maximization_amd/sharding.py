@@ -79,6 +79,14 @@ def rs_ag_sum_(dist, t, world):
         flat.copy_(buf[:n])
 
 
+def check_unweighted(windows):
+    """ShardedEngine.set_windows' refusal of per-event weights (a window tuple whose sixth element is not None), as a ValueError
+    before anything is staged: the shards' window constants come from summed IWE stacks, and no weighted form of that exchange is built."""
+    for b, w in enumerate(windows):
+        if len(w) > 5 and w[5] is not None:
+            raise ValueError(f'window {b} carries per-event weights: the event-sharded engine does not support them')
+
+
 class ShardedEngine:
     """Event-sharded evaluation: every rank stages ITS slice of each window's events (edges replicated) in its own Engine.
     The IWE is additive over events (src/utils/event_utils.py:59 is a pure sum), so one exchange step suffices per
@@ -144,7 +152,9 @@ class ShardedEngine:
             torch.cuda.current_stream().synchronize()
 
     def set_windows(self, local_windows):
-        """local_windows: this rank's (xs, ys, ts, edges, edge_ts) per window — its slice of the events, the full edges."""
+        """local_windows: this rank's (xs, ys, ts, edges, edge_ts) per window — its slice of the events, the full edges.
+        Per-event weights (a sixth element that is not None) are refused: the sharded engine has no weighted form."""
+        check_unweighted(local_windows)
         D = self.dist
         self.eng.set_windows(local_windows, defer_constants=True)
         self._allreduce_(self.eng.mask_tensor(), D.ReduceOp.MAX)          # TV needs the global event mask

@@ -64,13 +64,23 @@ def normalize_edges(edge_images):
     return np.stack(out)
 
 
-def stage_datasample(datasample, edges=None, **edge_kw):
+def stage_datasample(datasample, edges=None, event_weights=None, **edge_kw):
     """The part of EINCMExperiment.stage_datasample (exp_mgr.py:278-376) that feeds the loss: returns
     (xs:int16, ys:int16, ts:float64, edges:(R,H,W) float64, edge_ts:float64) ready for solver.set_datasample.
     edges None: built from datasample['images'] by edges.frames_to_edges(images, **edge_kw) (Canny and smoothing on the GPU).
-    Otherwise each given edge image is min-max normalised (normalize_edges), and edge_kw must be empty."""
+    Otherwise each given edge image is min-max normalised (normalize_edges), and edge_kw must be empty.
+    event_weights: one weight per event of the sample (engine.check_event_weights: finite, within [0, 1]; DESIGN.md section 22);
+    the tuple then carries them as float32 in a sixth place, as Engine.set_windows takes it.  None: the 5-tuple, as ever."""
     if edges is not None and edge_kw:
         raise TypeError(f'edge extraction arguments {sorted(edge_kw)} given with ready edges')
+    tup = _stage_datasample(datasample, edges, edge_kw)
+    if event_weights is None:
+        return tup
+    from .engine import check_event_weights
+    return tup + (check_event_weights(event_weights, len(tup[0])),)
+
+
+def _stage_datasample(datasample, edges, edge_kw):
     ev = datasample['events']
     start_time, end_time = datasample['eval_ts_us'] if 'eval_ts_us' in datasample else datasample['eval_ts']
     ts, image_ts = normalize_times(ev['t'], datasample['image_ts'], float(start_time), float(end_time))

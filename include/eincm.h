@@ -30,7 +30,7 @@ extern "C" {
                                *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory,
                                *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas), eincm_lbfgs_* (that BFGS with a limited-memory
                                *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models),
-                               *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels) */
+                               *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels), eincm_set_windows_weighted (per-event weights) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -181,6 +181,16 @@ int eincm_set_windows_ex(eincm_ctx* ctx, int n_windows, int n_refs, const int64_
 int eincm_set_windows_ptrs(eincm_ctx* ctx, int n_windows, int n_refs, const int64_t* n_events,
                            const int16_t* const* xs, const int16_t* const* ys, const double* const* ts,
                            const double* const* edges, const double* edge_ts, uint32_t flags);
+/* The same with per-event weights: weights[b] holds n_events[b] floats, finite and within [0, 1]; weights == NULL,
+ * or weights[b] == NULL, stands for ones.  I_r[p] = sum_e w_e k_e(p) in every IWE (the zero-warp one included) and dL/dw_e carries the
+ * same factor; an event of weight 0 behaves as an absent one in the loss, the gradient, the TV event mask and the count images, and
+ * stays in n_events and in eincm_get_warped_events.  The weights are data: there is no dL/dw.  Refused with EINCM_ERR_ARG: a weight
+ * out of range or not finite (checked on the host arrays, before the GPU is touched); with EINCM_ERR_UNSUPPORTED: a weighted batch on
+ * a float64 context, with a splat window other than 3, or with EINCM_SW_DEFER_CONSTANTS.  eincm_loss_grad_motion_fused refuses a
+ * weighted batch (eincm_loss_grad_motion serves it).  A later staging without weights drops the weighted state. */
+int eincm_set_windows_weighted(eincm_ctx* ctx, int n_windows, int n_refs, const int64_t* n_events,
+                               const int16_t* const* xs, const int16_t* const* ys, const double* const* ts,
+                               const double* const* edges, const double* edge_ts, const float* const* weights, uint32_t flags);
 
 /* value_and_grad(loss_func) for every staged window (losses.py:108-205 + its reverse pass).
  *   theta  (n_windows, h, w, 2)     value (n_windows)     grad (n_windows, h, w, 2) or NULL (forward only)
