@@ -74,10 +74,12 @@ def mixed_windows(n):
     return [w0 + (draw_weights(n, 900 + n),), w1 + (None,)]
 
 
-def stage(wins, seg=None, B=None):
+def stage(wins, seg=None, B=None, binning='device'):
     with pytest.MonkeyPatch.context() as mp:
         for k in EC.ENV:
             mp.delenv(k, raising=False)
+        if binning == 'host':           # (read when the context is created)
+            mp.setenv('EINCM_HOST_BINNING', '1')
         if seg is not None:
             for k in ('EINCM_SEG', 'EINCM_SEG_SPLAT', 'EINCM_SEG_2DOF'):
                 mp.setenv(k, str(seg))
@@ -173,8 +175,8 @@ def test_all_ones_dense_bit_for_bit():
 
 
 # ---- 3. weight 0 is absence --------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize('hw', [(1, 1), (4, 4)])
-def test_weight_zero_is_absence(hw):
+def weight_zero_batch(hw):
+    """(full, cut, ws, theta, params): two weighted windows, the same without their weight-0 events, the weights, a theta near the truth."""
     H, W, N, R = EC.H, EC.W, 1500, 2
     wins = [synth.make_window(60 + b, (H, W), N, R, flow='smooth', flow_mag=5.0) for b in range(2)]
     ws = [draw_weights(N, 70 + b) for b in range(2)]
@@ -186,8 +188,15 @@ def test_weight_zero_is_absence(hw):
         on[v['ys'][k], v['xs'][k]] = True
         assert (~on[v['ys'][~k], v['xs'][~k]]).any()
     th = np.stack([synth.theta_near_truth(60 + b, v, hw) for b, v in enumerate(wins)])
-    p = engine.make_params(20.0, 35.0, 2.5e-4, 0.0, 0)
-    a, b = stage(full), stage(cut)
+    return full, cut, ws, th, engine.make_params(20.0, 35.0, 2.5e-4, 0.0, 0)
+
+
+def check_weight_zero_is_absence(hw, binning='device'):
+    """The body of test_weight_zero_is_absence on either binning path (tests/test_gpu_event_weights_cells.py runs it on the host's);
+    returns the weighted batch's value and gradient."""
+    H, W, N = EC.H, EC.W, 1500
+    full, cut, ws, th, p = weight_zero_batch(hw)
+    a, b = stage(full, binning=binning), stage(cut, binning=binning)
     try:
         va, ga, xa = a.loss_grad(th, p, want_aux=True)
         vb, gb, xb = b.loss_grad(th, p, want_aux=True)
@@ -208,6 +217,12 @@ def test_weight_zero_is_absence(hw):
     finally:
         a.close()
         b.close()
+    return va, ga
+
+
+@pytest.mark.parametrize('hw', [(1, 1), (4, 4)])
+def test_weight_zero_is_absence(hw):
+    check_weight_zero_is_absence(hw)
 
 
 # ---- 4. dense theta and the device path -------------------------------------------------------------------------------------------
