@@ -34,6 +34,7 @@
 #include "eincm_bfgs.hip.h"
 #include "eincm_lbfgs.hip.h"
 #include "eincm_motion.hip.h"
+#include "eincm_event_support.hip.h"
 
 using namespace eincm;
 
@@ -220,6 +221,10 @@ struct eincm_ctx : PlanCtx {
         Grow<uint32_t> r_map;          // the rounded rectify map packed as int16 pairs, kept from the call that handed a map over
         bool rect_map_set = false;
     } rect;
+    struct {                           // eincm_event_support: what one chunk of a stream hands to the next
+        Grow<double> last_t;           // (H, W) the time of every pixel's last event so far, -inf: none; allocated by the first call
+        double last_time = es_no_event();   // the time of the last event of the previous chunk
+    } es;
     // the staged flow evaluation of eincm_flow_eval_stage: [GT flow (n, H, W) double2 | flag bytes (n, H, W)],
     // kept from one staging to the next; every eincm_flow_errors reads it
     struct {
@@ -2486,6 +2491,95 @@ int eincm_rectify_events(eincm_ctx* c, const float* rectify_map, const int16_t* 
     }
     HIPCHK(c, op.sync());
     *n_kept = kept;
+    return EINCM_OK;
+}
+
+// The spatiotemporal support filter for one chunk of a stream (eincm_event_support.hip.h): validate, sort the
+// event indices by pixel, search every neighbour's run, update the carried map.  A refused chunk leaves the carried state as it was.
+int eincm_event_support(eincm_ctx* c, const int16_t* x, const int16_t* y, const double* t, int64_t n, double tau, int radius,
+                        int full_support, const uint8_t* pixel_mask, int reset, float* weights, uint8_t* support) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = not_in_flight(c, "eincm_event_support")) return rc;
+    switch (es_check_args(n, tau, radius, full_support)) {
+        case ES_ARG_N: return fail(c, EINCM_ERR_ARG, "n = %lld outside [0, 2^30] (walk a recording in chunks)", (long long)n);
+        case ES_ARG_TAU: return fail(c, EINCM_ERR_ARG, "tau = %g (finite and >= 0)", tau);
+        case ES_ARG_RADIUS: return fail(c, EINCM_ERR_ARG, "radius = %d outside [1, %d]", radius, ES_MAX_RADIUS);
+        case ES_ARG_FULL_SUPPORT:
+            return fail(c, EINCM_ERR_ARG, "full_support = %d outside [1, %d] for radius %d", full_support, es_max_support(radius), radius);
+        case ES_ARG_OK: break;
+    }
+    if (n > 0 && (!x || !y || !t || !weights)) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    const int H = c->H, W = c->W;
+    const int64_t npix = (int64_t)H * W;
+    const double carried = reset ? es_no_event() : c->es.last_time;
+    const int nblk = (int)((n + ES_SORT_BLOCK - 1) / ES_SORT_BLOCK);
+    const size_t nhist = (size_t)ES_RADIX * (size_t)nblk;
+    const unsigned gn = (unsigned)((n + NT - 1) / NT), gp = (unsigned)((npix + NT - 1) / NT);
+    OneShot op(c);
+    const auto d_x = op.piece<int16_t>((size_t)n), d_y = op.piece<int16_t>((size_t)n);
+    const auto d_t = op.piece<double>((size_t)n);
+    const OneShot::Piece<uint32_t> d_key[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
+    const OneShot::Piece<uint32_t> d_val[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
+    const auto d_hist = op.piece<uint32_t>(nhist);
+    const size_t ntiles = (nhist + ES_SCAN_TILE - 1) / ES_SCAN_TILE;
+    const auto d_tiles = op.piece<uint32_t>(ntiles);
+    const auto d_lohi = op.piece<uint32_t>((size_t)npix * 2);            // lo | hi
+    const auto d_mask = op.piece<uint8_t>((size_t)npix, pixel_mask != nullptr);
+    const auto d_w = op.piece<float>((size_t)n);
+    const auto d_s = op.piece<uint8_t>((size_t)n);
+    const auto d_err = op.piece<uint32_t>(1);
+    uint32_t* h_err = op.host_buf<uint32_t>(1);                          // d_err comes down here
+    HIPCHK(c, op.begin());
+    if (n > 0) {
+        HIPCHK(c, op.up(d_x, x, (size_t)n * 2));                         // (host memory: the caller's, as every copy below but h_err's)
+        HIPCHK(c, op.up(d_y, y, (size_t)n * 2));
+        HIPCHK(c, op.up(d_t, t, (size_t)n * 8));
+        HIPCHK(c, op.zero(d_err, sizeof(uint32_t)));
+        HIPCHK(c, op.launch(k_es_validate, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, carried, d_key[0], d_err));
+        HIPCHK(c, op.down(h_err, d_err, sizeof(uint32_t)));
+        HIPCHK(c, op.sync());
+        if (*h_err) {
+            const int64_t e = n - (int64_t)*h_err;
+            if (e < 0 || e >= n) return fail(c, EINCM_ERR_HIP, "first refused event %lld of %lld", (long long)e, (long long)n);
+            switch (es_event_fault(H, W, x[e], y[e], t[e], e > 0 ? t[e - 1] : carried)) {
+                case ES_EV_COORD: return fail(c, EINCM_ERR_ARG, "event %lld: (%d, %d) outside the %dx%d sensor", (long long)e, x[e], y[e], H, W);
+                case ES_EV_TIME: return fail(c, EINCM_ERR_ARG, "event %lld: time %g is not finite", (long long)e, t[e]);
+                default:
+                    return fail(c, EINCM_ERR_ARG, "event %lld: time %.17g is smaller than %.17g, %s", (long long)e, t[e],
+                                e > 0 ? t[e - 1] : carried, e > 0 ? "its predecessor's" : "the last time of the previous chunk");
+            }
+        }
+    }
+    const bool fresh = c->es.last_t.n < (size_t)npix;
+    HIPCHK(c, ensure(c, c->es.last_t, (size_t)npix));
+    if (fresh || reset) {
+        HIPCHK(c, op.launch(k_es_fill, dim3(gp), dim3(NT), 0, npix, c->es.last_t.p, es_no_event()));
+        c->es.last_time = es_no_event();
+    }
+    if (n == 0) { HIPCHK(c, op.sync()); return EINCM_OK; }
+    uint32_t* const d_lo = d_lohi;
+    uint32_t* const d_hi = d_lo + npix;
+    if (pixel_mask) HIPCHK(c, op.up(d_mask, pixel_mask, (size_t)npix));
+    HIPCHK(c, op.zero(d_lo, (size_t)npix * 2 * sizeof(uint32_t)));
+    const int passes = es_sort_passes(npix);
+    int cur = 0;                                                         // the sorted (key, index) arrays so far: d_key[cur], d_val[cur]
+    for (int pass = 0; pass < passes; ++pass, cur ^= 1) {
+        const int shift = pass * ES_RADIX_BITS;
+        const uint32_t* const vin = pass ? (const uint32_t*)d_val[cur] : nullptr;      // (pass 0: the indices themselves)
+        HIPCHK(c, op.launch(k_es_hist, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], d_hist));
+        HIPCHK(c, op.launch(k_es_scan_tiles, dim3((unsigned)ntiles), dim3(ES_SCAN_NT), 0, (int64_t)nhist, d_hist, d_tiles));
+        HIPCHK(c, op.launch(k_es_scan, dim3(1), dim3(ES_SCAN_NT), 0, (int64_t)ntiles, d_tiles));
+        HIPCHK(c, op.launch(k_es_scatter, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], vin, d_hist, d_tiles,
+                            d_key[cur ^ 1], d_val[cur ^ 1]));
+    }
+    HIPCHK(c, op.launch(k_es_bounds, dim3(gn), dim3(NT), 0, n, npix, d_key[cur], d_lo, d_hi));
+    HIPCHK(c, op.launch(k_es_support, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, tau, radius, full_support, d_mask, d_lo, d_hi,
+                        d_val[cur], c->es.last_t.p, d_w, d_s));
+    HIPCHK(c, op.launch(k_es_map, dim3(gp), dim3(NT), 0, npix, n, d_lo, d_hi, d_val[cur], d_t, c->es.last_t.p));
+    HIPCHK(c, op.down(weights, d_w, (size_t)n * sizeof(float)));
+    if (support) HIPCHK(c, op.down(support, d_s, (size_t)n));
+    HIPCHK(c, op.sync());
+    c->es.last_time = t[n - 1];
     return EINCM_OK;
 }
 

@@ -314,6 +314,80 @@ def check_chunk(chunk):
     return int(chunk)
 
 
+EVENT_SUPPORT_MAX_RADIUS = 3      # ES_MAX_RADIUS (csrc/eincm_event_support.h)
+
+
+def check_event_times(t, n):
+    """The times of a raw stream as a 1-D float64 array of n elements.  Floating input is widened; integer input (microsecond ticks)
+    goes to float64 only if every value has magnitude <= 2^53, where the conversion is exact."""
+    a = np.asarray(t)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(f'event t must be 1-D with {n} elements, got shape {a.shape}')
+    if a.dtype.kind == 'b' or a.dtype.kind not in 'iuf':
+        raise ValueError(f'event t must be floating or integer, got {a.dtype}')
+    if a.dtype.kind in 'iu' and a.size and (int(a.max()) > 1 << 53 or int(a.min()) < -(1 << 53)):
+        raise ValueError('integer event times beyond 2^53 do not convert to float64 exactly')
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def check_event_support_args(tau, radius, full_support):
+    """(tau, radius, full_support) of the event-support filter as (float, int, int); ValueError as eincm_event_support refuses them."""
+    try:
+        tau = float(tau)
+    except (TypeError, ValueError):
+        raise ValueError(f'tau {tau!r}: a finite number >= 0') from None
+    if not np.isfinite(tau) or tau < 0.0:
+        raise ValueError(f'tau = {tau!r} (finite and >= 0)')
+    for name, v in (('radius', radius), ('full_support', full_support)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f'{name} {v!r}: an integer')
+    if not 1 <= radius <= EVENT_SUPPORT_MAX_RADIUS:
+        raise ValueError(f'radius = {radius} outside [1, {EVENT_SUPPORT_MAX_RADIUS}]')
+    most = (2 * int(radius) + 1) ** 2 - 1
+    if not 1 <= full_support <= most:
+        raise ValueError(f'full_support = {full_support} outside [1, {most}] for radius {radius}')
+    return tau, int(radius), int(full_support)
+
+
+def check_pixel_mask(pixel_mask, shape):
+    """None, or the (H, W) mask as uint8 with 1 where the input is non-zero."""
+    if pixel_mask is None:
+        return None
+    m = np.asarray(pixel_mask)
+    if m.shape != tuple(shape) or m.dtype.kind not in 'biu':
+        raise ValueError(f'pixel_mask must be a bool or integer array of shape {tuple(shape)}, got {m.dtype} {m.shape}')
+    return np.ascontiguousarray(m != 0, dtype=np.uint8)
+
+
+def event_support_first_offender(xs, ys, ts, shape, carried=-np.inf):
+    """The first event eincm_event_support refuses, as (index, why), or None: a coordinate outside the sensor, a non-finite time, a
+    time smaller than its predecessor's (``carried`` for event 0).  An event's refusal depends on itself and on its predecessor's
+    time alone, so the first of the stream is the smallest index of the vectorised test."""
+    H, W = shape
+    n = xs.shape[0]
+    if n == 0:
+        return None
+    # a good stream, in a few reductions: every coordinate inside, and times that never step back between two finite ends are all
+    # finite (a NaN fails both comparisons it takes part in; an infinity cannot lie between finite neighbours of a sorted run)
+    if (xs.min() >= 0 and xs.max() < W and ys.min() >= 0 and ys.max() < H and np.isfinite(ts[0]) and np.isfinite(ts[-1])
+            and not ts[0] < carried and bool(np.all(ts[1:] >= ts[:-1]))):
+        return None
+    prev = np.concatenate(([carried], ts[:-1]))
+    coord = (xs < 0) | (xs >= W) | (ys < 0) | (ys >= H)
+    time = ~np.isfinite(ts)
+    with np.errstate(invalid='ignore'):
+        order = ts < prev
+    bad = coord | time | order
+    if not bad.any():
+        return None
+    e = int(np.argmax(bad))
+    if coord[e]:
+        return e, f'event {e}: ({int(xs[e])}, {int(ys[e])}) outside the {H}x{W} sensor'
+    if time[e]:
+        return e, f'event {e}: time {ts[e]!r} is not finite'
+    return e, f'event {e}: time {ts[e]!r} is smaller than its predecessor\'s {prev[e]!r}'
+
+
 def check_remap_args(src, mapping):
     """src (n, Hs, Ws) or (Hs, Ws) uint8 with 1 <= Hs, Ws <= 32766; mapping (H, W, 2) float32.  Returns (src as a stack, mapping, single)."""
     a = np.asarray(src)
@@ -1127,6 +1201,33 @@ class Engine:
                 rec_x.ctypes.data + 2 * kept, rec_y.ctypes.data + 2 * kept, keep.ctypes.data + i0, C.byref(k)))
             kept += int(k.value)
         return rec_x[:kept], rec_y[:kept], keep.view(np.bool_), kept
+
+    def event_support(self, xs, ys, ts, tau, radius=1, full_support=1, pixel_mask=None, chunk=1 << 22, return_support=False):
+        """The spatiotemporal support filter (background-activity filter) of a raw stream: per event, the
+        number of neighbouring pixels (Chebyshev distance <= radius, inside the sensor, not masked, never the event's own pixel)
+        whose most recent earlier event lies at most ``tau`` back, and the weight min(support, full_support) / full_support as
+        float32: what ``set_windows``, ``stage_datasample(event_weights=)`` and the ``losses`` callables take.  xs, ys: integer
+        arrays in stream order; ts: finite, non-decreasing, floating or integer (integers of magnitude <= 2^53), ``tau`` in their
+        unit.  pixel_mask (H, W), non-zero = masked: events there get weight 0 and support nobody.  The stream is walked in chunks
+        of ``chunk`` events; the result does not depend on it.  Returns the weights (n,), and the uint8 support too when asked.
+        ValueError, before the library is reached: every refusal of the C contract, with the index of the first offending event."""
+        x, y = check_event_coords(xs, ys)
+        n = x.shape[0]
+        t = check_event_times(ts, n)
+        tau, radius, full_support = check_event_support_args(tau, radius, full_support)
+        mask = check_pixel_mask(pixel_mask, (self.H, self.W))
+        chunk = check_chunk(chunk)
+        bad = event_support_first_offender(x, y, t, (self.H, self.W))
+        if bad is not None:
+            raise ValueError(bad[1])
+        weights, support = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.uint8)
+        # an empty stream still reaches the library: it clears the carried state
+        for i0 in ([0] if n == 0 else range(0, n, chunk)):
+            i1 = min(n, i0 + chunk)
+            self._check_data(self._lib.eincm_event_support(
+                self._ctx, x.ctypes.data + 2 * i0, y.ctypes.data + 2 * i0, t.ctypes.data + 8 * i0, i1 - i0, tau, radius, full_support,
+                None if mask is None else mask.ctypes.data, int(i0 == 0), weights.ctypes.data + 4 * i0, support.ctypes.data + i0))
+        return (weights, support) if return_support else weights
 
     def remap_cubic(self, src, mapping):
         """cv.remap(src, mapping, None, INTER_CUBIC) under the contract of DESIGN.md section 16 (map_image_to_rect_event,

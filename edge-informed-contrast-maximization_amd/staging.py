@@ -173,6 +173,45 @@ def rectify_events(events, rectify_map, engine=None, chunk=1 << 22):
     return {'x': rec_x, 'y': rec_y, 't': t[keep], 'p': p[keep]}
 
 
+def event_support_weights(events, sensor_size, tau, radius=1, full_support=1, pixel_mask=None, chunk=1 << 22, return_support=False,
+                          engine=None):
+    """Per-event weights of a raw stream from the spatiotemporal support filter (Engine.event_support).
+    events: {'x','y','t',...} arrays in stream order; ``tau`` in the unit of events['t'] (the raw times, not the normalised ones of
+    stage_datasample, whose ``event_weights=`` takes the result).  engine None: the cached small context of edges._engine.  The
+    arguments are checked here, before a context is made.  Returns float32 weights (n,), and the uint8 support too when asked."""
+    from .engine import (check_chunk, check_event_coords, check_event_support_args, check_event_times, check_pixel_mask,
+                         event_support_first_offender)
+    missing = [k for k in ('x', 'y', 't') if k not in events]
+    if missing:
+        raise ValueError(f'events lack {missing}')
+    H, W = (int(sensor_size[0]), int(sensor_size[1])) if engine is None else (engine.H, engine.W)
+    if (H, W) != (int(sensor_size[0]), int(sensor_size[1])):
+        raise ValueError(f'sensor_size {tuple(sensor_size)} is not the engine\'s ({H}, {W})')
+    x, y = check_event_coords(events['x'], events['y'])
+    t = check_event_times(events['t'], x.shape[0])
+    tau, radius, full_support = check_event_support_args(tau, radius, full_support)
+    mask = check_pixel_mask(pixel_mask, (H, W))
+    chunk = check_chunk(chunk)
+    bad = event_support_first_offender(x, y, t, (H, W)) if engine is None else None      # (an engine handed over looks itself)
+    if bad is not None:
+        raise ValueError(bad[1])
+    return _dsec_engine(engine, (H, W)).event_support(x, y, t, tau, radius=radius, full_support=full_support, pixel_mask=mask, chunk=chunk,
+                                                      return_support=return_support)
+
+
+def hot_pixel_mask(xs, ys, sensor_size, max_count):
+    """(H, W) uint8, 1 at the pixels with more than ``max_count`` events: ready for ``pixel_mask=``.  Plain numpy."""
+    from .engine import check_event_coords
+    H, W = int(sensor_size[0]), int(sensor_size[1])
+    x, y = check_event_coords(xs, ys)
+    if x.size and (x.min() < 0 or x.max() >= W or y.min() < 0 or y.max() >= H):
+        raise ValueError(f'event coordinates outside the {H}x{W} sensor')
+    if isinstance(max_count, bool) or not isinstance(max_count, (int, np.integer)) or max_count < 0:
+        raise ValueError(f'max_count {max_count!r}: an integer >= 0')
+    counts = np.bincount(y.astype(np.int64) * W + x.astype(np.int64), minlength=H * W)
+    return (counts.reshape(H, W) > max_count).astype(np.uint8)
+
+
 def _k_matrix(cam_to_cam, name):
     cm = np.asarray(cam_to_cam['intrinsics'][name]['camera_matrix'], dtype=np.float64)
     if cm.shape != (4,) or not np.all(np.isfinite(cm)):

@@ -30,7 +30,8 @@ extern "C" {
                                *    eincm_flow_encode (the DSEC data path), eincm_bfgs_* (BFGS with its state in HBM), eincm_get_memory,
                                *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas), eincm_lbfgs_* (that BFGS with a limited-memory
                                *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models),
-                               *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels), eincm_set_windows_weighted (per-event weights) */
+                               *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels), eincm_set_windows_weighted (per-event weights),
+                               *    eincm_event_support (the event-support filter) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -462,6 +463,23 @@ int eincm_gt_flow(eincm_ctx* ctx, const void* gt_x, const void* gt_y, int elem_b
  * the sensor (the outputs are not written).  EINCM_ERR_STATE: NULL map and no map in the context. */
 int eincm_rectify_events(eincm_ctx* ctx, const float* rectify_map, const int16_t* x, const int16_t* y, int64_t n, int16_t* rec_x,
                          int16_t* rec_y, uint8_t* keep, int64_t* n_kept);
+
+/* The spatiotemporal support filter (background-activity filter) of a raw event stream, one chunk of n <= 2^30 events per call
+ * (DESIGN.md section 23).  Stream order is the order handed over; times are finite and non-decreasing.  The neighbours of pixel p are
+ * the pixels q != p within Chebyshev distance radius (1..3) of p, inside the sensor and not masked.  For event e at p, neighbour q is
+ * supported iff q's most recent event j < e in stream order has t[e] - t[j] <= tau (one double subtraction, one compare; no earlier
+ * event: not supported; equal times support the later index only).  support[e] = the number of supported neighbours (uint8, may be
+ * NULL), weights[e] = (float)min(support, full_support) / (float)full_support, 1 <= full_support <= (2 radius + 1)^2 - 1.  An event's
+ * own pixel never supports it.  pixel_mask (H, W) uint8 or NULL, non-zero = masked: events there get support 0 and weight 0 and give
+ * no support.  The context carries, from chunk to chunk, the time of every pixel's last event (allocated by the first call) and the
+ * time of the last event handed over; reset != 0 clears both before the chunk, so any split of a stream into consecutive chunks
+ * gives the bytes of the unsplit call.  n == 0 is valid and writes nothing.  EINCM_ERR_ARG, before any output is written and with
+ * the carried state unchanged, naming the first offender's index: a coordinate outside the sensor, a non-finite time, a time smaller
+ * than its predecessor's (or than the carried last time when reset == 0); also tau not finite or negative, radius or full_support
+ * out of range, n outside [0, 2^30], a null x, y, t or weights with n > 0.  EINCM_ERR_STATE: an evaluation is in flight.  Integer
+ * counts and no floating-point sums: the same bytes on every run, in fp32 and EINCM_CF_FP64 contexts. */
+int eincm_event_support(eincm_ctx* ctx, const int16_t* x, const int16_t* y, const double* t, int64_t n, double tau, int radius,
+                        int full_support, const uint8_t* pixel_mask, int reset, float* weights, uint8_t* support);
 
 /* cv.remap(src, map, None, INTER_CUBIC) of 8-bit single-channel images, constant border 0, as a written contract (DESIGN.md section 16;
  * parity with OpenCV itself is not pinned).  src (n, src_h, src_w), 1 <= src_h, src_w <= 32766, independent of the sensor; map (H, W, 2)
