@@ -9,6 +9,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdarg>
@@ -16,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "eincm.h"
@@ -567,6 +569,66 @@ void launch_theta_image(eincm_ctx* c, int h, int w, bool identity, bool use_arg,
     c->Theta_valid = true;
 }
 
+// The event kernels the library contains: every row of eincm_plan.h's four form lists bound to its instantiation, in the lists' order,
+// so a plan's row (SplatForm.row, GatherForm.row) is the kernel to launch.  No other place names an instantiation of the four.
+template <size_t... I> constexpr auto bind_splat(std::index_sequence<I...>) {
+    return std::array{&k_splat<SPLAT_FORMS[I].mode, SPLAT_FORMS[I].threads, SPLAT_FORMS[I].weighted>...};
+}
+template <size_t... I> constexpr auto bind_splat_r(std::index_sequence<I...>) {
+    return std::array{&k_splat_r<SPLAT_R_FORMS[I].mode, SPLAT_R_FORMS[I].rad>...};
+}
+template <size_t... I> constexpr auto bind_gather(std::index_sequence<I...>) {
+    return std::array{&k_gather<GATHER_FORMS[I].mode, GATHER_FORMS[I].wide, GATHER_FORMS[I].threads, GATHER_FORMS[I].proj, GATHER_FORMS[I].all_r,
+                                GATHER_FORMS[I].weighted>...};
+}
+template <size_t... I> constexpr auto bind_gather_r(std::index_sequence<I...>) {
+    return std::array{&k_gather_r<GATHER_R_FORMS[I].mode, GATHER_R_FORMS[I].rad>...};
+}
+const auto SPLAT_KERNELS = bind_splat(std::make_index_sequence<std::size(SPLAT_FORMS)>{});
+const auto SPLAT_R_KERNELS = bind_splat_r(std::make_index_sequence<std::size(SPLAT_R_FORMS)>{});
+const auto GATHER_KERNELS = bind_gather(std::make_index_sequence<std::size(GATHER_FORMS)>{});
+const auto GATHER_R_KERNELS = bind_gather_r(std::make_index_sequence<std::size(GATHER_R_FORMS)>{});
+// k_splat_r and k_gather_r take the mode and the radius alone: their rows hold what the kernels are written for in every other field
+constexpr bool other_window_rows_plain() {
+    for (const SplatKey& k : SPLAT_R_FORMS) if (k.threads != NT || k.weighted) return false;
+    for (const GatherKey& k : GATHER_R_FORMS) if (k.threads != NT || k.wide || k.proj || k.all_r || k.weighted) return false;
+    return true;
+}
+static_assert(other_window_rows_plain(), "a row of SPLAT_R_FORMS / GATHER_R_FORMS names a kernel that k_splat_r / k_gather_r are not");
+
+// a plan whose form is no row: what the entry points refuse (plan_forms), had it come this far
+int no_such_form(eincm_ctx* c, const char* kernel, const GatherKey& k) {
+    return fail(c, EINCM_ERR_UNSUPPORTED, "internal: the library holds no %s kernel for theta mode %d, splat radius %d, wide %d, %d threads, "
+                "proj %d, all_r %d, weighted %d (eincm_plan.h)", kernel, k.mode, k.rad, k.wide, k.threads, k.proj, k.all_r, k.weighted);
+}
+
+// The splat of the planned evaluation as its form says (fl.plan.splat), and with it the end of the forward half
+int launch_splat(eincm_ctx* c, const double* theta_dev, const ThetaArg& targ) {
+    const EvalPlan& P = c->fl.plan;
+    const SplatForm& F = P.splat;
+    {
+        StageTimer t(c, EINCM_STAGE_SPLAT, true);
+        if (c->splat.n > 0) {
+            if (F.row < 0) return no_such_form(c, "splat", GatherKey{F.key.mode, F.key.rad, 0, F.key.threads, 0, 0, F.key.weighted});
+            const SegList& L = seg_list(*c, F.list);
+            Geom gs = c->g;
+            gs.wincap = F.wincap; gs.winmaxw = F.winmaxw;
+            const dim3 grid(L.grid(gs.R)), block(F.key.threads);
+            const int use_arg = P.use_arg ? 1 : 0;
+            if (F.key.rad == 1)
+                launch_timed(c, EINCM_STAGE_SPLAT, SPLAT_KERNELS[F.row], grid, block, F.lds, gs, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta,
+                             c->d_edge_ts, c->splat.d_wins, c->d_acc, L.d_order, use_arg, theta_dev, targ,
+                             (const float*)(F.key.weighted ? c->d_w : nullptr));
+            else
+                launch_timed(c, EINCM_STAGE_SPLAT, SPLAT_R_KERNELS[F.row], grid, block, F.lds, gs, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta,
+                             c->d_tmm, c->d_edge_ts, c->d_acc, L.d_order, use_arg, theta_dev, targ);
+        }
+    }
+    HIPCHK(c, hipGetLastError());
+    c->fl.theta_dev = theta_dev; c->fl.targ = targ;
+    return EINCM_OK;
+}
+
 // Launch the forward half of the planned evaluation (fl.plan): theta -> Theta -> u64 IWE accumulator.
 int launch_forward(eincm_ctx* c, const double* theta_host) {
     const EvalPlan& P = c->fl.plan;
@@ -586,17 +648,7 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
         mo.last_q.assign(theta_host, theta_host + nq);
         c->last_theta11.clear();
         c->Theta_valid = false;
-        {
-            StageTimer t(c, EINCM_STAGE_SPLAT, true);
-            if (c->splat.n > 0)
-                launch_timed(c, EINCM_STAGE_SPLAT, k_splat<THETA_POLY, 512>, dim3(c->splat.grid(g.R)), dim3(512),
-                             (size_t)g.wincap * sizeof(float) + TS * TS * sizeof(double2) + POLY_SCRATCH_BYTES, g, c->splat.n, c->splat.d_items,
-                             c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, c->splat.d_order, P.use_arg ? 1 : 0,
-                             (const double*)mo.h_q(c->maxB), ta, (const float*)nullptr);
-        }
-        HIPCHK(c, hipGetLastError());
-        c->fl.theta_dev = mo.h_q(c->maxB); c->fl.targ = ta;
-        return EINCM_OK;
+        return launch_splat(c, mo.h_q(c->maxB), ta);
     }
     ThetaArg targ;
     static thread_local ThetaArgBig targ_big;
@@ -642,40 +694,7 @@ int launch_forward(eincm_ctx* c, const double* theta_host) {
                                    ga.n, ga.d_items, ga.d_wins, sp.n, sp.d_items, sp.d_wins);
         }
     }
-    {
-        StageTimer t(c, EINCM_STAGE_SPLAT, true);
-        if (c->splat.n > 0) {
-            const SegList& L = P.splat_short ? c->splat_sh : c->splat;      // (a 2-DoF theta derives its windows itself)
-            const size_t theta_tile = two_dof ? 0 : TS * TS * sizeof(double2);     // LDS beside the window
-            const int use_arg = P.use_arg ? 1 : 0;
-            if (c->splat_rad != 1) {
-                // another splat window (eincm_splat_window.hip.h): u64 LDS windows, capped so that they fit beside the Theta tile
-                Geom gs = g;
-                gs.wincap = std::min(g.wincap, two_dof ? SW_CAP_CONST : SW_CAP_TILE);
-                gs.winmaxw = win_maxw(gs.wincap);
-                auto go = [&](auto kernel) {
-                    launch_timed(c, EINCM_STAGE_SPLAT, kernel, dim3(L.grid(g.R)), dim3(NT), (size_t)gs.wincap * sizeof(unsigned long long) + theta_tile,
-                                 gs, L.n, L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_tmm, c->d_edge_ts, c->d_acc, L.d_order, use_arg, theta_dev, targ);
-                };
-                if (two_dof) c->splat_rad == 0 ? go(k_splat_r<THETA_CONST, 0>) : c->splat_rad == 2 ? go(k_splat_r<THETA_CONST, 2>) : go(k_splat_r<THETA_CONST, 3>);
-                else         c->splat_rad == 0 ? go(k_splat_r<THETA_TILE, 0>) : c->splat_rad == 2 ? go(k_splat_r<THETA_TILE, 2>) : go(k_splat_r<THETA_TILE, 3>);
-            } else {
-                // 512 threads per workgroup in both compile-time modes: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
-                // (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us)
-                auto go = [&](auto kernel) {
-                    launch_timed(c, EINCM_STAGE_SPLAT, kernel, dim3(L.grid(g.R)), dim3(512), (size_t)g.wincap * sizeof(float) + theta_tile, g, L.n,
-                                 L.d_items, c->d_xy, c->d_t, c->d_Theta, c->d_edge_ts, c->splat.d_wins, c->d_acc, L.d_order, use_arg, theta_dev, targ,
-                                 (const float*)(c->stage.weighted ? c->d_w : nullptr));
-                };
-                // a weighted batch (stage.weighted) runs the weighted instantiation; an unweighted one the code it always ran
-                if (c->stage.weighted) two_dof ? go(k_splat<THETA_CONST, 512, 1>) : go(k_splat<THETA_TILE, 512, 1>);
-                else                   two_dof ? go(k_splat<THETA_CONST, 512>) : go(k_splat<THETA_TILE, 512>);
-            }
-        }
-    }
-    HIPCHK(c, hipGetLastError());
-    c->fl.theta_dev = theta_dev; c->fl.targ = targ;
-    return EINCM_OK;
+    return launch_splat(c, theta_dev, targ);
 }
 
 // Read one finished evaluation's events (its stream work has been waited for) into last_t and the running sums.
@@ -953,7 +972,7 @@ int eval_end_launch(eincm_ctx* c) {
     const EvalPlan& P = c->fl.plan;
     const EvalParams& ep = P.ep;
     Geom g = c->g;
-    const bool identity = P.shape == EvalPlan::IDENTITY, two_dof = P.shape == EvalPlan::TWO_DOF, want_grad = P.want_grad, host_asm = P.host_asm;
+    const bool identity = P.shape == EvalPlan::IDENTITY, want_grad = P.want_grad, host_asm = P.host_asm;
     const bool timing = timing_on(c);
     const int n_imwg = (g.nig + IG_NT / 64 - 1) / (IG_NT / 64);
     g.gmax_n = g.R * g.nig;
@@ -1013,56 +1032,31 @@ int eval_end_launch(eincm_ctx* c) {
         }
         {
             StageTimer t(c, EINCM_STAGE_GATHER, true);
-            // 44 KB of LDS (G window + i64 accumulators + Theta tile) fit 3 workgroups per CU: 512 threads each keep 24 waves there
-            constexpr int NT_TILE = 512;
             if (c->gather.n > 0) {
-                // Theta grids / dense theta: the gather walks its own segment list (long segments: its per-workgroup costs - Theta tile,
-                // accumulator clear and flush - want them long even for one window) on its own copy of the events (k_segsort); 2-DoF
-                // theta: the 2-DoF gather list (shorter segments) on the splat's copy, deriving its windows itself (no window table)
-                const SegList& L = two_dof ? c->gather_2 : c->gather;
-                const uint32_t* xy_g = two_dof ? c->d_xy : c->d_xy_g;
-                const double* t_g = two_dof ? c->d_t : c->d_t_g;
+                // as the plan's form says (P.gather): the list, the copy of the events and weights, the window geometry, the kernel
+                const GatherForm& F = P.gather;
+                if (F.row < 0) return no_such_form(c, "gather", F.key);
+                const SegList& L = seg_list(*c, F.list);
+                const bool own_copy = F.copy == EventCopy::GATHER;
+                const uint32_t* xy_g = own_copy ? c->d_xy_g : c->d_xy;
+                const double* t_g = own_copy ? c->d_t_g : c->d_t;
                 Geom gg = g;
-                if (two_dof) { gg.pitch_aligned = P.win_2.pal ? 1 : 0; gg.wincap_a = P.win_2.cap; gg.winmaxw_a = P.win_2.maxw; }
-                const dim3 grid(L.grid(P.all_r ? 1 : g.R));
-                const bool fused = P.shape == EvalPlan::MOTION;       // the polynomial mode: the moments go to their pinned slots
-                const size_t lds = gg.wincap_a * sizeof(float) + (two_dof ? 0 : TS * TS * 2 * sizeof(double) + TS * TS * sizeof(double2)) +
-                                   (fused ? POLY_SCRATCH_BYTES : 0);
-                double* g11 = fused ? c->motion.h_fpart.p : host_asm ? c->h_g11 : c->d_g11;
+                gg.pitch_aligned = F.pitch_aligned; gg.wincap_a = F.wincap; gg.winmaxw_a = F.winmaxw;
+                const dim3 grid(L.grid(F.wg_per_seg)), block(F.key.threads);
+                // the polynomial mode: the moments go to their pinned slots
+                double* g11 = P.shape == EvalPlan::MOTION ? c->motion.h_fpart.p : host_asm ? c->h_g11 : c->d_g11;
                 const int use_arg = P.use_arg ? 1 : 0;
-                if (c->splat_rad != 1) {
-                    // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
-                    auto go = [&](auto kernel) {
-                        launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(NT), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta, c->d_tmm,
-                                     c->d_edge_ts, c->d_G, c->d_gTheta, g11, c->d_wc, c->d_gmax, c->stage.wide ? 1 : 0, use_arg, c->fl.theta_dev,
-                                     c->fl.targ);
-                    };
-                    if (two_dof) c->splat_rad == 0 ? go(k_gather_r<THETA_CONST, 0>) : c->splat_rad == 2 ? go(k_gather_r<THETA_CONST, 2>) : go(k_gather_r<THETA_CONST, 3>);
-                    else         c->splat_rad == 0 ? go(k_gather_r<THETA_TILE, 0>) : c->splat_rad == 2 ? go(k_gather_r<THETA_TILE, 2>) : go(k_gather_r<THETA_TILE, 3>);
-                } else {
-                    auto go = [&](auto kernel, int nthreads) {
-                        launch_timed(c, EINCM_STAGE_GATHER, kernel, grid, dim3(nthreads), lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta,
-                                     c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, g11, c->d_wc, c->d_gmax, L.d_order, use_arg,
-                                     c->fl.theta_dev, c->fl.targ, P.h, P.w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p, (int)c->coarse_cap,
-                                     P.grid_tail ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad,
-                                     (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth.p + (size_t)c->maxB * c->coarse_cap,
-                                     (const float*)(c->stage.weighted ? (two_dof ? c->d_w : c->d_w_g) : nullptr));
-                    };
-                    if (c->stage.weighted && !fused) {      // the weighted instantiations, cell for cell the unweighted choice below
-                        if (two_dof) go(k_gather<THETA_CONST, 0, NT, 0, 0, 1>, NT);
-                        else if (P.all_r) c->stage.wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1, 1>, NT_TILE);
-                        else if (c->stage.wide) P.proj ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 0, 1>, NT_TILE) : go(k_gather<THETA_TILE, 1, NT_TILE, 0, 0, 1>, NT_TILE);
-                        else              P.proj ? go(k_gather<THETA_TILE, 0, NT_TILE, 1, 0, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 0, 0, 1>, NT_TILE);
-                    }
-                    else if (fused) {
-                        if (P.all_r) c->stage.wide ? go(k_gather<THETA_POLY, 1, NT_TILE, 0, 1>, NT_TILE) : go(k_gather<THETA_POLY, 0, NT_TILE, 0, 1>, NT_TILE);
-                        else         c->stage.wide ? go(k_gather<THETA_POLY, 1, NT_TILE, 0>, NT_TILE) : go(k_gather<THETA_POLY, 0, NT_TILE, 0>, NT_TILE);
-                    }
-                    else if (two_dof) go(k_gather<THETA_CONST, 0, NT, 0>, NT);
-                    else if (P.all_r) c->stage.wide ? go(k_gather<THETA_TILE, 1, NT_TILE, 1, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 1, 1>, NT_TILE);
-                    else if (c->stage.wide) P.proj ? go(k_gather<THETA_TILE, 1, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 1, NT_TILE, 0>, NT_TILE);
-                    else              P.proj ? go(k_gather<THETA_TILE, 0, NT_TILE, 1>, NT_TILE) : go(k_gather<THETA_TILE, 0, NT_TILE, 0>, NT_TILE);
-                }
+                if (F.key.rad == 1)
+                    launch_timed(c, EINCM_STAGE_GATHER, GATHER_KERNELS[F.row], grid, block, F.lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta,
+                                 c->d_edge_ts, c->d_G, c->gather.d_wins, c->d_gTheta, g11, c->d_wc, c->d_gmax, L.d_order, use_arg,
+                                 c->fl.theta_dev, c->fl.targ, P.h, P.w, c->d_AH.p, c->d_AW.p, c->d_tilerng, c->d_gth.p, (int)c->coarse_cap,
+                                 P.grid_tail ? 1 : 0, c->d_gticket, c->gather.d_win_item0, c->h_grad,
+                                 (P.grid_tail && ep.use_tv_grad) ? ep.gamma : 0.0, c->d_tvparts, c->d_gth.p + (size_t)c->maxB * c->coarse_cap,
+                                 (const float*)(F.key.weighted ? (own_copy ? c->d_w_g : c->d_w) : nullptr));
+                else    // another splat window (eincm_splat_window.hip.h): per-workgroup partials (2-DoF) or the dL/dTheta image for k_project
+                    launch_timed(c, EINCM_STAGE_GATHER, GATHER_R_KERNELS[F.row], grid, block, F.lds, gg, L.n, L.d_items, xy_g, t_g, c->d_Theta,
+                                 c->d_tmm, c->d_edge_ts, c->d_G, c->d_gTheta, g11, c->d_wc, c->d_gmax, c->stage.wide ? 1 : 0, use_arg,
+                                 c->fl.theta_dev, c->fl.targ);
             }
         }
         // accumulators: two halves (event gradient | TV gradient), each (maxB, coarse_cap) i64, zero on entry (k_final clears them)

@@ -30,7 +30,6 @@
 
 namespace eincm {
 
-constexpr int NT = 256;           // threads per workgroup = 4 waves of 64
 constexpr int NWAVE = NT / 64;
 constexpr int WIN_CAP_MAX = 9216;
 constexpr float INV_2PI = 0.15915494309189535f;
@@ -256,12 +255,6 @@ __device__ __forceinline__ void taps3x2(float fx, float fy, float scale_y, f2v& 
 
 struct EvReg { uint32_t xy; double t; float w; };   // one event in flight through the software pipeline of the event kernels (w: its weight, loaded and read by the weighted forms only)
 
-// Where an event's velocity Theta[y,x] comes from inside the event kernels.  A per-event global gather costs ~64 L1 cycles per
-// wave-instruction (64 lanes, 64 different cache lines) and was 2/3 of k_splat's time; every workgroup works on ONE source tile, so:
-constexpr int THETA_CONST = 1;   // theta (1,1,2): Theta is one constant per window (read from the tile bounds, min == max)
-constexpr int THETA_TILE = 2;    // otherwise: the tile's 32x32 double2 velocities are staged in LDS once per segment (16 KiB)
-constexpr int THETA_POLY = 3;    // a motion model: the tile is formed in LDS from the window's polynomial, no Theta image
-
 // ---- the polynomial of a motion model (DESIGN.md sections 20 and 21): one statement for k_motion_expand, k_motion_moments and the
 // THETA_POLY mode of the event kernels, so that their bits cannot drift apart.  No FMA contraction anywhere in it. ----
 // normalised coordinate of column x (c = cx) or row y (c = cy): a correctly rounded division
@@ -288,9 +281,6 @@ __device__ __forceinline__ double2 motion_poly(const double* q, double u, double
 constexpr int POLY_NQ = 12;
 constexpr int POLY_ARG_Q0 = 4;
 constexpr int POLY_ARG_WINDOWS = (THETA_ARG_MAX - POLY_ARG_Q0) / POLY_NQ;
-// LDS beside the Theta tile: u of the tile's 32 columns | v of its 32 rows | 4 bounds of each of up to 8 waves
-constexpr int POLY_SCRATCH = 2 * TS + 4 * 8;
-constexpr size_t POLY_SCRATCH_BYTES = POLY_SCRATCH * sizeof(double);
 
 // the tile's velocity bounds from the per-wave bounds poly_fill_tile left behind u and v (every thread; after its last barrier)
 template <int NTH>

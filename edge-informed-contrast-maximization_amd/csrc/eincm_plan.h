@@ -469,6 +469,86 @@ struct DevIo {
     double vmax = -1.0;                 // bounds |theta| for the window-capacity choice (< 0: unknown, largest windows)
 };
 
+// ---- the event kernels' launch forms ----
+
+// The instantiations of the four event kernels the library contains, as data: eincm_api.hip binds every row to its kernel, in this
+// order, and launches nothing else, so a row here is a kernel that exists and the other way round.  plan_forms names the row an
+// evaluation runs; tests/test_host_plan.py asserts it cell by cell and that the rows are exactly what the plans can reach.
+struct SplatKey {
+    int mode;                           // THETA_CONST / THETA_TILE / THETA_POLY
+    int rad;                            // radius of the splat window: 1 is k_splat, 0 / 2 / 3 k_splat_r
+    int threads;                        // per workgroup
+    int weighted;                       // the weighted form
+};
+struct GatherKey {
+    int mode, rad;                      // as the splat's: radius 1 is k_gather, 0 / 2 / 3 k_gather_r
+    int wide;                           // 61-bit per-pixel sums (StagePlan.wide) as a template argument: k_gather's grid and motion forms (k_gather_r takes it at run time)
+    int threads;
+    int proj, all_r;                    // the tile's gradient projected onto the theta cells in the gather; one workgroup per segment for all reference times
+    int weighted;
+};
+constexpr bool operator==(const SplatKey& a, const SplatKey& b) {
+    return a.mode == b.mode && a.rad == b.rad && a.threads == b.threads && a.weighted == b.weighted;
+}
+constexpr bool operator==(const GatherKey& a, const GatherKey& b) {
+    return a.mode == b.mode && a.rad == b.rad && a.wide == b.wide && a.threads == b.threads && a.proj == b.proj && a.all_r == b.all_r &&
+           a.weighted == b.weighted;
+}
+// k_splat: 512 threads per workgroup in every compile-time mode: 93 vs 94 us on the 8-window batch, 18.8 vs 23.2 us on one window
+// (1024: 102 us; the gather is slower with 512: 93.5 vs 81.7 us).  The gather of a grid or a motion model: 44 KB of LDS (G window +
+// i64 accumulators + Theta tile) fit 3 workgroups per CU: 512 threads each keep 24 waves there.
+constexpr int NT_TILE = 512;
+// k_splat<mode, threads, weighted>
+inline constexpr SplatKey SPLAT_FORMS[] = {
+    {THETA_CONST, 1, NT_TILE, 0}, {THETA_CONST, 1, NT_TILE, 1}, {THETA_TILE, 1, NT_TILE, 0}, {THETA_TILE, 1, NT_TILE, 1},
+    {THETA_POLY, 1, NT_TILE, 0},
+};
+// k_splat_r<mode, rad>
+inline constexpr SplatKey SPLAT_R_FORMS[] = {
+    {THETA_CONST, 0, NT, 0}, {THETA_CONST, 2, NT, 0}, {THETA_CONST, 3, NT, 0}, {THETA_TILE, 0, NT, 0}, {THETA_TILE, 2, NT, 0}, {THETA_TILE, 3, NT, 0},
+};
+// k_gather<mode, wide, threads, proj, all_r, weighted>
+inline constexpr GatherKey GATHER_FORMS[] = {
+    {THETA_CONST, 1, 0, NT, 0, 0, 0},      {THETA_CONST, 1, 0, NT, 0, 0, 1},
+    {THETA_TILE, 1, 0, NT_TILE, 0, 0, 0},  {THETA_TILE, 1, 0, NT_TILE, 0, 0, 1},  {THETA_TILE, 1, 1, NT_TILE, 0, 0, 0},  {THETA_TILE, 1, 1, NT_TILE, 0, 0, 1},
+    {THETA_TILE, 1, 0, NT_TILE, 1, 0, 0},  {THETA_TILE, 1, 0, NT_TILE, 1, 0, 1},  {THETA_TILE, 1, 1, NT_TILE, 1, 0, 0},  {THETA_TILE, 1, 1, NT_TILE, 1, 0, 1},
+    {THETA_TILE, 1, 0, NT_TILE, 1, 1, 0},  {THETA_TILE, 1, 0, NT_TILE, 1, 1, 1},  {THETA_TILE, 1, 1, NT_TILE, 1, 1, 0},  {THETA_TILE, 1, 1, NT_TILE, 1, 1, 1},
+    {THETA_POLY, 1, 0, NT_TILE, 0, 0, 0},  {THETA_POLY, 1, 1, NT_TILE, 0, 0, 0},  {THETA_POLY, 1, 0, NT_TILE, 0, 1, 0},  {THETA_POLY, 1, 1, NT_TILE, 0, 1, 0},
+};
+// k_gather_r<mode, rad>
+inline constexpr GatherKey GATHER_R_FORMS[] = {
+    {THETA_CONST, 0, 0, NT, 0, 0, 0}, {THETA_CONST, 2, 0, NT, 0, 0, 0}, {THETA_CONST, 3, 0, NT, 0, 0, 0},
+    {THETA_TILE, 0, 0, NT, 0, 0, 0},  {THETA_TILE, 2, 0, NT, 0, 0, 0},  {THETA_TILE, 3, 0, NT, 0, 0, 0},
+};
+// the row of `rows` that equals k; -1: the library holds no such kernel
+template <typename K, size_t N> constexpr int form_row(const K (&rows)[N], const K& k) {
+    for (size_t i = 0; i < N; ++i) if (rows[i] == k) return (int)i;
+    return -1;
+}
+
+enum class ListId { GATHER, SPLAT, SPLAT_SHORT, GATHER_2DOF };   // PlanCtx's gather / splat / splat_sh / gather_2 (seg_list)
+enum class EventCopy { SPLAT, GATHER };                          // the splat's copy of the events and weights (time order, k_spread), or the gather's (k_segsort)
+
+// How an evaluation launches its splat: the kernel (key; row: its place in SPLAT_FORMS, or in SPLAT_R_FORMS where the radius is not 1)
+// and what must agree with it.
+struct SplatForm {
+    SplatKey key{};
+    int row = -1;
+    size_t lds = 0;                     // dynamic LDS bytes: the window, the Theta tile, the polynomial's scratch
+    ListId list = ListId::SPLAT;        // the list it walks
+    int wincap = 0, winmaxw = 0;        // the window capacity and largest width of its Geom: the plan's, capped for k_splat_r's u64 windows
+};
+// ... and its gather (filled for a gradient evaluation only)
+struct GatherForm {
+    GatherKey key{};
+    int row = -1;                       // in GATHER_FORMS, or in GATHER_R_FORMS where the radius is not 1
+    size_t lds = 0;                     // the G window, the accumulators and the Theta tile of a grid, the polynomial's scratch
+    ListId list = ListId::GATHER;
+    EventCopy copy = EventCopy::GATHER; // the events and weights it reads
+    int wg_per_seg = 0;                 // workgroups per segment: one per reference time, or 1 (all_r)
+    int wincap = 0, winmaxw = 0, pitch_aligned = 0;   // wincap_a, winmaxw_a and pitch_aligned of its Geom (the 2-DoF gather: its own list's, win_2)
+};
+
 // Every decision of one evaluation, taken once by plan_eval before its first launch; the launch and assembly code only read it.
 struct EvalPlan {
     enum Shape { IDENTITY, TWO_DOF, GRID, MOTION } shape = GRID;   // theta (h, w) = the sensor's / (1, 1) / any other grid / a motion model's polynomial inside the event kernels (plan_motion)
@@ -489,6 +569,7 @@ struct EvalPlan {
     bool all_r = false;                 // ... the gather with one workgroup per segment for all reference times
     bool events_projected = false; int nsrc = 0;   // k_project's sources: the event term's dL/dTheta image unless projected, the TV term's
     bool zero_copy_out = false;         // k_final writes the results straight into pinned host memory
+    SplatForm splat; GatherForm gather; // the event kernels' launches (plan_forms); gather: of a gradient evaluation
 };
 
 constexpr int MOTION_PLAN_ARG_WINDOWS = (THETA_ARG_MAX - 4) / 12;   // windows whose q rides in the event kernels' arguments beside (cx, cy, s) (POLY_ARG_WINDOWS)
@@ -547,6 +628,48 @@ inline void plan_windows(const PlanCtx& c, EvalPlan& P, double vmax, bool two_do
     // and the 2-DoF gather's list (pitch = width: at the aligned pitch it measured equal on the bench batch and 63 -> 68 us on another
     // batch of the same shape, profiles/r03/pitch_by_shape.txt; EINCM_PITCH_ALIGNED=2 aligns it too)
     P.win_2 = fit_window(vmax, c.gather_2.tspan, margin, 2, c.stage.pitch >= 2 ? 1 : 0);
+}
+
+inline const SegList& seg_list(const PlanCtx& c, ListId id) {
+    return id == ListId::GATHER ? c.gather : id == ListId::SPLAT ? c.splat : id == ListId::SPLAT_SHORT ? c.splat_sh : c.gather_2;
+}
+
+// The event kernels' launch forms of a planned evaluation (its shape, windows, proj and all_r are set): which instantiation runs, and
+// the threads, LDS bytes, list, event copy and window geometry that must agree with its template arguments.  A combination the entry
+// points refuse (weights or a motion model with another splat window, weights with a motion model) has no row: the launch reports it.
+inline void plan_forms(const PlanCtx& c, EvalPlan& P) {
+    const bool two_dof = P.shape == EvalPlan::TWO_DOF, fused = P.shape == EvalPlan::MOTION;
+    const int mode = two_dof ? THETA_CONST : fused ? THETA_POLY : THETA_TILE, rad = c.splat_rad, wt = c.stage.weighted ? 1 : 0;
+    const size_t theta_tile = two_dof ? 0 : TS * TS * 2 * sizeof(double);      // LDS beside the window: the tile's double2 velocities
+    const size_t scratch = fused ? POLY_SCRATCH_BYTES : 0;
+    SplatForm& s = P.splat;
+    s.list = P.splat_short ? ListId::SPLAT_SHORT : ListId::SPLAT;              // (a 2-DoF theta derives its windows itself)
+    if (rad == 1) {
+        s.key = SplatKey{mode, rad, NT_TILE, wt};
+        s.row = form_row(SPLAT_FORMS, s.key);
+        s.wincap = P.wincap; s.winmaxw = P.winmaxw;
+        s.lds = (size_t)s.wincap * sizeof(float) + theta_tile + scratch;
+    } else {
+        // another splat window (eincm_splat_window.hip.h): u64 LDS windows, capped so that they fit beside the Theta tile
+        s.key = SplatKey{mode, rad, NT, wt};
+        s.row = form_row(SPLAT_R_FORMS, s.key);
+        s.wincap = std::min(P.wincap, two_dof ? SW_CAP_CONST : SW_CAP_TILE); s.winmaxw = win_maxw(s.wincap);
+        s.lds = (size_t)s.wincap * sizeof(unsigned long long) + theta_tile + scratch;
+    }
+    if (!P.want_grad) return;
+    // Theta grids / dense theta / motion models: the gather walks its own segment list (long segments: its per-workgroup costs - Theta
+    // tile, accumulator clear and flush - want them long even for one window) on its own copy of the events (k_segsort); 2-DoF theta:
+    // the 2-DoF gather list (shorter segments) on the splat's copy, deriving its windows itself (no window table)
+    GatherForm& a = P.gather;
+    a.list = two_dof ? ListId::GATHER_2DOF : ListId::GATHER;
+    a.copy = two_dof ? EventCopy::SPLAT : EventCopy::GATHER;
+    a.wg_per_seg = P.all_r ? 1 : c.g.R;
+    a.wincap = two_dof ? P.win_2.cap : P.wincap_a; a.winmaxw = two_dof ? P.win_2.maxw : P.winmaxw_a;
+    a.pitch_aligned = two_dof ? (P.win_2.pal ? 1 : 0) : P.pitch_aligned;
+    a.lds = (size_t)a.wincap * sizeof(float) + (two_dof ? 0 : TS * TS * 2 * sizeof(double) + theta_tile) + scratch;
+    const bool templated = rad == 1 && !two_dof;        // the grid and motion forms of k_gather: 512 threads, `wide` a template argument
+    a.key = GatherKey{mode, rad, templated && c.stage.wide ? 1 : 0, templated ? NT_TILE : NT, P.proj ? 1 : 0, P.all_r ? 1 : 0, wt};
+    a.row = rad == 1 ? form_row(GATHER_FORMS, a.key) : form_row(GATHER_R_FORMS, a.key);
 }
 
 // Every decision of one evaluation, from the context's state, the call's device-resident theta (io) and its checked arguments.
@@ -623,6 +746,7 @@ inline EvalPlan plan_eval(const PlanCtx& c, const DevIo& io, const EvalKnobs& kn
     P.nsrc = (!want_grad || identity) ? 0 : (P.events_projected ? 0 : 1) + ((ep.use_tv_grad && !P.tv_proj) ? 1 : 0);
     // small results (everything but a dense gradient) are written by k_final straight into pinned host memory: no D2H copy command
     P.zero_copy_out = !c.device_results && !io.theta && !identity && nall <= ZERO_COPY_MAX;
+    plan_forms(c, P);
     return P;
 }
 
@@ -646,6 +770,7 @@ inline EvalPlan plan_motion(const PlanCtx& c, const EvalKnobs& knobs, double vma
     P.all_r = want_grad && c.g.R > 1 && (knobs.all_r >= 0 ? knobs.all_r != 0 : c.gather.n >= 700);
     P.events_projected = true;                        // (by the gather itself, onto the moments)
     P.zero_copy_out = true;
+    plan_forms(c, P);                                 // (again: the shape and all_r are the motion model's now)
     return P;
 }
 

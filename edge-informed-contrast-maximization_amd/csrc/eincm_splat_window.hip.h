@@ -27,8 +27,6 @@
 namespace eincm {
 
 constexpr int SPLAT_RADIUS_MAX = 3;          // window size 7
-constexpr int SW_CAP_TILE = 4608;            // u64 words of k_splat_r's window beside the 16 KiB Theta tile (36 + 16 KiB of LDS)
-constexpr int SW_CAP_CONST = 6912;           // ... with nothing beside it (54 KiB)
 
 // item_window with the margin of radius `rad` (+rad for the taps, +1 for the rounding) and the row pitch equal to the width
 __device__ __forceinline__ Window item_window_r(const Geom& g, const Item& it, const double* mm4, double tau, int wincap, int winmaxw, int rad) {

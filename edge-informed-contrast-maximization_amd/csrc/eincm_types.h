@@ -57,6 +57,21 @@ constexpr int THETA_ARG_MAX = 128;    // doubles of theta that ride in the kerne
 constexpr int THETA_ARG_BIG = 4096;   // k_theta alone takes up to 32 KiB of theta (16x16 grids of 8 windows) in its arguments: no read of pinned host memory
 constexpr int THETA_ARG_MID = 512;    // ... and a 4 KiB form for one window's 16x16 grid: the launch copies its arguments twice on the host (k_theta<TA>)
 
+// ---- what the event kernels' launch forms are made of (eincm_plan.h: SplatForm, GatherForm) ----
+constexpr int NT = 256;           // threads per workgroup = 4 waves of 64
+
+// Where an event's velocity Theta[y,x] comes from inside the event kernels.  A per-event global gather costs ~64 L1 cycles per
+// wave-instruction (64 lanes, 64 different cache lines) and was 2/3 of k_splat's time; every workgroup works on ONE source tile, so:
+constexpr int THETA_CONST = 1;   // theta (1,1,2): Theta is one constant per window (read from the tile bounds, min == max)
+constexpr int THETA_TILE = 2;    // otherwise: the tile's 32x32 double2 velocities are staged in LDS once per segment (16 KiB)
+constexpr int THETA_POLY = 3;    // a motion model: the tile is formed in LDS from the window's polynomial, no Theta image
+// THETA_POLY: LDS beside the Theta tile: u of the tile's 32 columns | v of its 32 rows | 4 bounds of each of up to 8 waves
+constexpr int POLY_SCRATCH = 2 * TS + 4 * 8;
+constexpr size_t POLY_SCRATCH_BYTES = POLY_SCRATCH * sizeof(double);
+// another splat window (eincm_splat_window.hip.h):
+constexpr int SW_CAP_TILE = 4608;            // u64 words of k_splat_r's window beside the 16 KiB Theta tile (36 + 16 KiB of LDS)
+constexpr int SW_CAP_CONST = 6912;           // ... with nothing beside it (54 KiB)
+
 struct Window { int ox, oy, ww, wh; };
 
 struct TileRange { int ilo, ni, jlo, nj; };     // the coarse cells a tile's pixels have weight on (host: build_resample)

@@ -11,23 +11,24 @@ sys.path.insert(0, ROOT)
 
 H, W, R, B = 120, 160, 3, 2
 N = (40000, 26000)
+N_WIDE = (1200, 26000, 9000)            # window 0 with n * R < 4096: the staging is `wide` (plan_staging in csrc/eincm_plan.h)
 CASES = [((1, 1), 0.0, 4), ((4, 4), 2.5e-4, 0), ((16, 16), 0.0, 1), ((8, 8), 2.5e-4, 0)]
 
 
-def inputs():
+def inputs(n=N):
     synth = importlib.import_module('edge-informed-contrast-maximization_amd.synth')
-    wins = [synth.make_window(120 + b, (H, W), N[b], R, flow='smooth', flow_mag=9.0) for b in range(B)]
+    wins = [synth.make_window(120 + b, (H, W), n[b], R, flow='smooth', flow_mag=9.0) for b in range(len(n))]
     thetas = [np.stack([synth.theta_near_truth(120 + b, w, hw) for b, w in enumerate(wins)]) for hw, _, _ in CASES]
     return wins, thetas
 
 
-def main(out_path):
+def main(out_path, n=N):
     import __graft_entry__ as ge
     ge.build()
     engine = importlib.import_module('edge-informed-contrast-maximization_amd.engine')
-    wins, thetas = inputs()
+    wins, thetas = inputs(n)
     res = {}
-    with engine.Engine((H, W), sum(N), max_refs=R, max_windows=B) as eng:
+    with engine.Engine((H, W), sum(n), max_refs=R, max_windows=len(n)) as eng:
         eng.set_windows([(w['xs'], w['ys'], w['ts'], w['edges'], w['edge_ts']) for w in wins])
         for i, (th, (hw, gamma, lvl)) in enumerate(zip(thetas, CASES)):
             v, g, _ = eng.loss_grad(th, engine.make_params(20.0, 35.0, gamma, 0.0, lvl))
@@ -38,4 +39,4 @@ def main(out_path):
 
 
 if __name__ == '__main__':
-    main(sys.argv[1])
+    main(sys.argv[1], N_WIDE if sys.argv[2:] == ['wide'] else N)

@@ -25,6 +25,36 @@ void put(double v) { std::printf(" %.17g", v); }
 void put_i(int64_t v) { std::printf(" %lld", (long long)v); }
 template <typename T> void put_all(const std::vector<T>& v) { std::printf(" |"); for (const T& x : v) put_i((int64_t)x); }
 
+// The context of a staged batch of these tile populations (counts: B * ntiles): plan_staging, and the four lists as stage_windows cuts them
+void stage_counts(PlanCtx& c, int R, int B, const std::vector<int32_t>& counts, const StageKnobs& sk, const char* who) {
+    const int ntiles = ((c.W + TS - 1) / TS) * ((c.H + TS - 1) / TS);
+    if (counts.size() != (size_t)B * ntiles) { std::fprintf(stderr, "plan_check: %s wants %d x %d counts\n", who, B, ntiles); std::exit(2); }
+    std::vector<int64_t> n_events((size_t)B, 0);
+    for (int b = 0; b < B; ++b) for (int t = 0; t < ntiles; ++t) n_events[b] += counts[(size_t)b * ntiles + t];
+    c.stage = plan_staging(c, B, R, n_events.data(), 0u, sk);
+    c.g = c.stage.g;
+    std::vector<int32_t> lens;
+    const StagePlan& S = c.stage;
+    cut_segments(counts.data(), counts.size(), ntiles, S.seg, S.N, false, c.gather, lens); c.gather.n = (int)lens.size();
+    cut_segments(counts.data(), counts.size(), ntiles, S.seg_s, S.N, false, c.splat, lens); c.splat.n = (int)lens.size();
+    cut_segments(counts.data(), counts.size(), ntiles, S.seg_2, S.N, true, c.gather_2, lens); c.gather_2.n = (int)lens.size();
+    if (S.splat_short) { cut_segments(counts.data(), counts.size(), ntiles, SEG_SHORT, S.N, true, c.splat_sh, lens); c.splat_sh.n = (int)lens.size(); }
+}
+
+// a (B, h, w, 2) theta whose largest magnitude is vmax
+std::vector<double> theta_of(int B, int h, int w, double vmax) {
+    std::vector<double> theta((size_t)B * h * w * 2);
+    for (size_t i = 0; i < theta.size(); ++i) theta[i] = (i % 3 == 0 ? -0.5 : 0.75) * vmax;
+    theta[theta.size() / 2] = -vmax;
+    return theta;
+}
+
+eincm_params level2_params() {
+    eincm_params p{};
+    p.alpha = 20.0; p.beta = 35.0; p.cur_pyr_lvl = 2; p.contrast_kind = EINCM_CONTRAST_GRAD_MAG;
+    return p;
+}
+
 // policy H W R B rad pitch_env(-1: unset) vmax(< 0: staged only) h w counts[B * ntiles]: the thirteen fields of
 // eincm_get_launch_policy for a context that staged these tile populations and evaluated a (h, w) theta of that maximum
 void policy(Args& a) {
@@ -39,30 +69,84 @@ void policy(Args& a) {
     const int h = (int)a.i(), w = (int)a.i();
     std::vector<int32_t> counts;
     while (a.more()) counts.push_back((int32_t)a.i());
-    const int ntiles = ((c.W + TS - 1) / TS) * ((c.H + TS - 1) / TS);
-    if (counts.size() != (size_t)B * ntiles) { std::fprintf(stderr, "plan_check: policy wants %d x %d counts\n", B, ntiles); std::exit(2); }
-    std::vector<int64_t> n_events((size_t)B, 0);
-    for (int b = 0; b < B; ++b) for (int t = 0; t < ntiles; ++t) n_events[b] += counts[(size_t)b * ntiles + t];
-    c.stage = plan_staging(c, B, R, n_events.data(), 0u, sk);
-    c.g = c.stage.g;
-    std::vector<int32_t> lens;
-    const StagePlan& S = c.stage;                                      // the four lists, as stage_windows cuts them
-    cut_segments(counts.data(), counts.size(), ntiles, S.seg, S.N, false, c.gather, lens); c.gather.n = (int)lens.size();
-    cut_segments(counts.data(), counts.size(), ntiles, S.seg_s, S.N, false, c.splat, lens); c.splat.n = (int)lens.size();
-    cut_segments(counts.data(), counts.size(), ntiles, S.seg_2, S.N, true, c.gather_2, lens); c.gather_2.n = (int)lens.size();
-    if (S.splat_short) { cut_segments(counts.data(), counts.size(), ntiles, SEG_SHORT, S.N, true, c.splat_sh, lens); c.splat_sh.n = (int)lens.size(); }
+    stage_counts(c, R, B, counts, sk, "policy");
     EvalPlan P;
     if (vmax >= 0.0) {
-        std::vector<double> theta((size_t)B * h * w * 2);
-        for (size_t i = 0; i < theta.size(); ++i) theta[i] = (i % 3 == 0 ? -0.5 : 0.75) * vmax;
-        theta[theta.size() / 2] = -vmax;
-        eincm_params p{};
-        p.alpha = 20.0; p.beta = 35.0; p.cur_pyr_lvl = 2; p.contrast_kind = EINCM_CONTRAST_GRAD_MAG;
+        const std::vector<double> theta = theta_of(B, h, w, vmax);
+        const eincm_params p = level2_params();
         P = plan_eval(c, DevIo{}, EvalKnobs{}, theta.data(), h, w, &p, true);
     }
     double out[EINCM_LP_SPLAT_SHORT + 1] = {};
     launch_policy(c, P, vmax >= 0.0, out);
     for (const double v : out) put(v);
+}
+
+// forms H W R B rad weighted wide(-1: as staged) proj_in_gather itembase_valid n_gather n_splat n_splat_sh n_gather_2 all_r(-1: unset)
+// no_host_asm motion h w vmax want_grad [counts[B * ntiles]]: the launch forms of the event kernels (plan_forms) for a context in that
+// state - the four lists hold that many segments, or, with counts, the staged batch of these tile populations (the four n_ are then
+// not read) - that evaluates a (h, w) theta of that maximum, or (motion) a motion model whose field has that bound.
+//   splat: mode rad threads weighted row lds list wincap winmaxw
+// | gather: mode rad wide threads proj all_r weighted row lds list copy wg_per_seg wincap winmaxw pitch_aligned (row -1: none planned)
+// | plan: wincap winmaxw wincap_a winmaxw_a pitch_aligned win_2.cap win_2.maxw win_2.pal splat_short proj all_r host_asm
+void forms(Args& a) {
+    PlanCtx c;
+    c.H = (int)a.i(); c.W = (int)a.i();
+    const int R = (int)a.i(), B = (int)a.i();
+    c.splat_rad = (int)a.i();
+    const bool weighted = a.i() != 0;
+    const int wide = (int)a.i();
+    c.proj_in_gather = a.i() != 0; c.itembase_valid = a.i() != 0;
+    const int n_list[4] = {(int)a.i(), (int)a.i(), (int)a.i(), (int)a.i()};
+    EvalKnobs knobs;
+    knobs.all_r = (int)a.i(); knobs.no_host_asm = a.i() != 0;
+    const bool motion = a.i() != 0;
+    const int h = (int)a.i(), w = (int)a.i();
+    const double vmax = a.f();
+    const bool want_grad = a.i() != 0;
+    std::vector<int32_t> counts;
+    while (a.more()) counts.push_back((int32_t)a.i());
+    if (!counts.empty()) {
+        stage_counts(c, R, B, counts, StageKnobs{}, "forms");
+    } else {
+        const std::vector<int64_t> n_events((size_t)B, 100000);
+        c.stage = plan_staging(c, B, R, n_events.data(), 0u, StageKnobs{});
+        c.g = c.stage.g;
+        c.gather.n = n_list[0]; c.splat.n = n_list[1]; c.splat_sh.n = n_list[2]; c.gather_2.n = n_list[3];
+    }
+    c.stage.weighted = weighted;
+    if (wide >= 0) c.stage.wide = wide != 0;
+    const eincm_params p = level2_params();
+    EvalPlan P;
+    if (motion) {
+        P = plan_motion(c, knobs, vmax, &p, want_grad);
+    } else {
+        const std::vector<double> theta = theta_of(B, h, w, vmax);
+        P = plan_eval(c, DevIo{}, knobs, theta.data(), h, w, &p, want_grad);
+    }
+    const SplatForm& s = P.splat;
+    for (const int64_t v : {(int64_t)s.key.mode, (int64_t)s.key.rad, (int64_t)s.key.threads, (int64_t)s.key.weighted, (int64_t)s.row, (int64_t)s.lds,
+                            (int64_t)s.list, (int64_t)s.wincap, (int64_t)s.winmaxw}) put_i(v);
+    std::printf(" |");
+    const GatherForm& g = P.gather;
+    for (const int64_t v : {(int64_t)g.key.mode, (int64_t)g.key.rad, (int64_t)g.key.wide, (int64_t)g.key.threads, (int64_t)g.key.proj,
+                            (int64_t)g.key.all_r, (int64_t)g.key.weighted, (int64_t)g.row, (int64_t)g.lds, (int64_t)g.list, (int64_t)g.copy,
+                            (int64_t)g.wg_per_seg, (int64_t)g.wincap, (int64_t)g.winmaxw, (int64_t)g.pitch_aligned}) put_i(v);
+    std::printf(" |");
+    for (const int64_t v : {(int64_t)P.wincap, (int64_t)P.winmaxw, (int64_t)P.wincap_a, (int64_t)P.winmaxw_a, (int64_t)P.pitch_aligned,
+                            (int64_t)P.win_2.cap, (int64_t)P.win_2.maxw, (int64_t)P.win_2.pal, (int64_t)P.splat_short, (int64_t)P.proj,
+                            (int64_t)P.all_r, (int64_t)P.host_asm}) put_i(v);
+}
+
+// formrows: the rows of the four form lists, k_splat's (mode rad threads weighted) | k_splat_r's | k_gather's (mode rad wide threads
+// proj all_r weighted) | k_gather_r's
+void formrows() {
+    for (const SplatKey& k : SPLAT_FORMS) { put_i(k.mode); put_i(k.rad); put_i(k.threads); put_i(k.weighted); }
+    std::printf(" |");
+    for (const SplatKey& k : SPLAT_R_FORMS) { put_i(k.mode); put_i(k.rad); put_i(k.threads); put_i(k.weighted); }
+    std::printf(" |");
+    for (const GatherKey& k : GATHER_FORMS) { put_i(k.mode); put_i(k.rad); put_i(k.wide); put_i(k.threads); put_i(k.proj); put_i(k.all_r); put_i(k.weighted); }
+    std::printf(" |");
+    for (const GatherKey& k : GATHER_R_FORMS) { put_i(k.mode); put_i(k.rad); put_i(k.wide); put_i(k.threads); put_i(k.proj); put_i(k.all_r); put_i(k.weighted); }
 }
 
 // cut seg ntiles N want_items counts[]: n, tspan | lens | order | win_item0 | items (win, tile, begin, count)
@@ -175,6 +259,8 @@ int main(int argc, char** argv) {
         const std::string& what = a.tok[0];
         std::printf("%s", what.c_str());
         if (what == "policy") policy(a);
+        else if (what == "forms") forms(a);
+        else if (what == "formrows") formrows();
         else if (what == "cut") cut(a);
         else if (what == "resample") resample(a);
         else if (what == "taps") taps(a);

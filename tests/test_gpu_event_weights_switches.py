@@ -7,31 +7,15 @@ tests/_event_weights_witness.py at 1e-5 (value and gradient of every window, the
 once, in the parent), and every switched run to the default run at the bars of tests/test_gpu_switches.py between two configurations
 of the library: 2e-6 for the value, 2e-5 for the gradient and dL/dIWE, 1e-6 for the IWE stack.
 
-Which weighted code each run reaches.  Nothing outside the library can observe which instantiation ran, so the table is derived from
-the dispatch in csrc/eincm_api.hip (the weighted branch of the gather launch, bin_on_device / bin_on_host / copy_for_gather /
-finish_lists) and the predicates of csrc/eincm_plan.h (plan_staging: wide = some window with n * R < 4096; plan_eval: proj = theta
-grid whose tiles touch at most 6 x 6 cells and no EINCM_NO_PROJ_IN_GATHER, all_r = proj and (EINCM_GATHER_ALL_R or >= 700 segments));
-the test asserts the table's inputs: n * R on either side of 4096, the cells a tile touches, and the environment each child saw.
-k_gather<TM, WIDE, NTH, PROJ, ALLR, WT>, k_splat<TM, NTH, WT>:
+Which weighted code each run reaches is asserted, not derived by eye: the launch form of an evaluation (the instantiation of k_splat and
+k_gather with its threads, LDS bytes and lists) is a value of the plan (plan_forms in csrc/eincm_plan.h), and
+tests/test_host_plan.py::test_named_cells_take_their_forms asserts on the CPU which form each run of this module plans - the cases
+forms-2dof-, forms-grid*-, forms-noproj- and forms-allr- at -w1-wide0 (narrow batch) and -w1-wide1 (wide batch); DESIGN.md section 22
+has the table, staging kernels included.  This module asserts the inputs those cases assume: n * R on either side of 4096 (plan_staging:
+wide), the cells a tile touches (plan_eval: proj), and the environment each child saw.
 
-    kernel                                    run                          batch    theta shapes
-    k_splat<THETA_CONST, 512, 1>              every run                    both     (1, 1)
-    k_splat<THETA_TILE, 512, 1>               every run                    both     (4, 4), (16, 16), (8, 8)
-    k_gather<THETA_CONST, 0, 256, 0, 0, 1>    every run                    both     (1, 1)
-    k_gather<THETA_TILE, 0, 512, 1, 0, 1>     default                      narrow   the three grids
-    k_gather<THETA_TILE, 1, 512, 1, 0, 1>     default                      wide     the three grids
-    k_gather<THETA_TILE, 0, 512, 0, 0, 1>     EINCM_NO_PROJ_IN_GATHER      narrow   the three grids
-    k_gather<THETA_TILE, 1, 512, 0, 0, 1>     EINCM_NO_PROJ_IN_GATHER      wide     the three grids
-    k_gather<THETA_TILE, 0, 512, 1, 1, 1>     EINCM_GATHER_ALL_R=1         narrow   the three grids
-    k_gather<THETA_TILE, 1, 512, 1, 1, 1>     EINCM_GATHER_ALL_R=1         wide     the three grids (the one kernel that spills: 12 bytes of scratch per lane)
-    k_bin_scatter<1>, k_spread<1>, k_segsort<1>   default                  both     (staging)
-    d_w as scattered, d_w_g its plain copy    EINCM_NO_SEGSORT + EINCM_NO_SPREAD   both   (staging)
-    sorted weights uploaded, k_segsort<1>,
-    k_mask with weights, cntmax of bin_events EINCM_HOST_BINNING           both     (4, 4) and (8, 8): gamma != 0 at level 0 reads the mask
-    k_tile_counts with weights                every other run              both     (4, 4) and (8, 8)
-
-The same two all-reference-times gathers run without a switch on the 16-window batches of
-tests/test_gpu_event_weights_cells.py (1500 segments and more; WIDE = 0), and the weighted k_mask in its
+The all-reference-times gather also runs without a switch, on the 16-window batches of
+tests/test_gpu_event_weights_cells.py (1500 segments and more; WIDE = 0: forms-cell-*-w1), and the weighted k_mask in its
 test_weight_zero_is_absence_on_host_binning, where pixels that hold nothing but weight-0 events decide the TV term.
 """
 import importlib.util

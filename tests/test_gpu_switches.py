@@ -28,11 +28,11 @@ SWITCHES = [
 ]
 
 
-def run_probe(tmp_path, tag, env_extra):
+def run_probe(tmp_path, tag, env_extra, batch=()):
     out = os.path.join(tmp_path, f'{tag}.npz')
     env = {k: v for k, v in os.environ.items() if not k.startswith('EINCM_') or k == 'EINCM_LIB'}
     env.update(env_extra)
-    r = subprocess.run([sys.executable, os.path.join(HERE, '_switch_probe.py'), out], env=env, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([sys.executable, os.path.join(HERE, '_switch_probe.py'), out, *batch], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (tag, r.stdout[-2000:], r.stderr[-2000:])
     return dict(np.load(out))
 
@@ -59,3 +59,27 @@ def test_switches_reproduce_the_default_and_the_oracle(built_lib, tmp_path):
             assert rel(got[f'g{i}'], base[f'g{i}']) <= 2e-5, (what, hw, rel(got[f'g{i}'], base[f'g{i}']))
             assert rel(got[f'iwe{i}'], base[f'iwe{i}']) <= 1e-6, (what, hw)
             assert rel(got[f'G{i}'], base[f'G{i}']) <= 2e-5, (what, hw)
+
+
+@pytest.mark.timeout(900)
+def test_wide_batch_with_the_all_reference_times_gather(built_lib, tmp_path):
+    """The unweighted k_gather<THETA_TILE, 1, 512, 1, 1> (tests/test_host_plan.py: forms-allr-w0-wide1), which no batch above reaches:
+    three windows, window 0 with n * R < 4096, so the staging is `wide` (61-bit per-pixel sums), and EINCM_GATHER_ALL_R=1, so one
+    workgroup per segment walks all reference times.  The default run (k_gather<THETA_TILE, 1, 512, 1, 0>) against the oracle, the
+    switched run against the default one, at the bars of the test above."""
+    from oracle import eincm_oracle as O
+    assert probe.N_WIDE[0] * probe.R < 4096 <= min(probe.N_WIDE[1:]) * probe.R
+    base = run_probe(str(tmp_path), 'wide-default', {}, ['wide'])
+    wins, thetas = probe.inputs(probe.N_WIDE)
+    for i, (th, (hw, gamma, lvl)) in enumerate(zip(thetas, probe.CASES)):
+        for b, w in enumerate(wins):
+            a = (w['xs'], w['ys'], w['ts'], w['edges'], w['edge_ts'])
+            v_o, g_o, _ = O.loss_and_grad(th[b], *a, 20.0, 35.0, gamma, 0.0, lvl, 5, (probe.H, probe.W))
+            assert abs(base[f'v{i}'][b] - v_o) <= 1e-5 * abs(v_o), (hw, b)
+            assert rel(base[f'g{i}'][b], g_o) <= 1e-5, (hw, b)
+    got = run_probe(str(tmp_path), 'wide-all-r', {'EINCM_GATHER_ALL_R': '1'}, ['wide'])
+    for i, (hw, _, _) in enumerate(probe.CASES):
+        assert rel(got[f'v{i}'], base[f'v{i}']) <= 2e-6, (hw, rel(got[f'v{i}'], base[f'v{i}']))
+        assert rel(got[f'g{i}'], base[f'g{i}']) <= 2e-5, (hw, rel(got[f'g{i}'], base[f'g{i}']))
+        assert rel(got[f'iwe{i}'], base[f'iwe{i}']) <= 1e-6, hw
+        assert rel(got[f'G{i}'], base[f'G{i}']) <= 2e-5, hw

@@ -121,6 +121,232 @@ def test_pinned_batches_keep_their_numbers(out):
 
 
 # ================================================================================================
+# launch forms of the event kernels: plan_forms, the one decision that selects the machine code (DESIGN.md sections 5 and 22)
+# ================================================================================================
+CONST, TILE, POLY = 1, 2, 3                                  # THETA_CONST / THETA_TILE / THETA_POLY (csrc/eincm_types.h)
+L_GATHER, L_SPLAT, L_SPLAT_SHORT, L_GATHER_2DOF = range(4)   # ListId
+COPY_SPLAT, COPY_GATHER = range(2)                           # EventCopy
+SW_CAP = {CONST: 6912, TILE: 4608}                           # SW_CAP_CONST / SW_CAP_TILE
+THETA_TILE_BYTES, ACCUM_BYTES, POLY_SCRATCH_BYTES = 32 * 32 * 16, 32 * 32 * 2 * 8, (2 * 32 + 4 * 8) * 8
+PH, PW, PR, PB = 120, 160, 3, 3                              # the batches of tests/_switch_probe.py and tests/_weighted_switch_probe.py
+
+
+def _forms_case(name, *, H=PH, W=PW, R=PR, B=PB, rad=1, weighted=0, wide=0, proj=1, itembase=1, n=(100, 100, 0, 100), all_r=None,
+                no_host_asm=0, motion=0, hw=(4, 4), vmax=9.0, want_grad=1, counts=()):
+    """n: segments of the gather's, the splat's, the splat's short and the 2-DoF gather's list; counts: the staged tile populations
+    instead (wide = -1: as staged)."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    return _case(name, 'forms', H, W, R, B, rad, weighted, wide, proj, itembase, *n, -1 if all_r is None else all_r, no_host_asm, motion,
+                 hw[0], hw[1], float(vmax), want_grad, *counts.tolist())
+
+
+def S(mode, rad=1, threads=512, wt=0, lst=L_SPLAT):
+    """What a test expects of a SplatForm: the key (mode, rad, threads, weighted) and the list."""
+    return (mode, rad, threads, wt), lst
+
+
+def G(mode, rad=1, wide=0, threads=512, proj=0, all_r=0, wt=0, lst=L_GATHER, copy=COPY_GATHER, wg=PR):
+    """... of a GatherForm: the key (mode, rad, wide, threads, proj, all_r, weighted), the list, the event copy, workgroups per segment."""
+    return (mode, rad, wide, threads, proj, all_r, wt), lst, copy, wg
+
+
+def G2(rad=1, wt=0, wg=PR):
+    """The 2-DoF gather: 256 threads, its own list on the splat's copy of the events."""
+    return G(CONST, rad, 0, 256, 0, 0, wt, L_GATHER_2DOF, COPY_SPLAT, wg)
+
+
+_case('formrows', 'formrows')
+NAMED = {}                             # case name -> (expected SplatForm, expected GatherForm), literals read off the parent's ladders
+
+
+def _named(name, want_s, want_g, **kw):
+    NAMED[_forms_case(name, **kw)] = (want_s, want_g)
+
+
+# DESIGN.md section 22's table (weighted: wt = 1) with its unweighted twin, on the context of the switch probes: narrow and wide batch
+for _wt in (0, 1):
+    for _wide in (0, 1):
+        _t, _k = f'w{_wt}-wide{_wide}', dict(weighted=_wt, wide=_wide)
+        _named(f'forms-2dof-{_t}', S(CONST, wt=_wt), G2(wt=_wt), hw=(1, 1), **_k)
+        for _hw in ((4, 4), (16, 16), (8, 8)):         # default run: the in-gather projection
+            _named(f'forms-grid{_hw[0]}-{_t}', S(TILE, wt=_wt), G(TILE, wide=_wide, proj=1, wt=_wt), hw=_hw, **_k)
+        _named(f'forms-noproj-{_t}', S(TILE, wt=_wt), G(TILE, wide=_wide, wt=_wt), proj=0, **_k)                 # EINCM_NO_PROJ_IN_GATHER
+        _named(f'forms-allr-{_t}', S(TILE, wt=_wt), G(TILE, wide=_wide, proj=1, all_r=1, wt=_wt, wg=1), all_r=1, **_k)   # EINCM_GATHER_ALL_R=1
+        _named(f'forms-allr-noproj-{_t}', S(TILE, wt=_wt), G(TILE, wide=_wide, wt=_wt), all_r=1, proj=0, **_k)   # (all_r goes with proj)
+        _named(f'forms-allr0-800-{_t}', S(TILE, wt=_wt), G(TILE, wide=_wide, proj=1, wt=_wt), all_r=0, n=(800, 800, 0, 800), **_k)
+        _named(f'forms-800-{_t}', S(TILE, wt=_wt), G(TILE, wide=_wide, proj=1, all_r=1, wt=_wt, wg=1), n=(800, 800, 0, 800), **_k)
+        _named(f'forms-dense-{_t}', S(TILE, wt=_wt), G(TILE, wide=_wide, wt=_wt), hw=(PH, PW), n=(800, 800, 0, 800), **_k)
+        _named(f'forms-forward-{_t}', S(TILE, wt=_wt), None, want_grad=0, **_k)
+# the fused motion forms (DESIGN.md section 21): narrow and wide, all reference times on and off
+for _wide in (0, 1):
+    _k = dict(motion=1, wide=_wide, hw=(0, 0))
+    _named(f'forms-motion-wide{_wide}', S(POLY), G(POLY, wide=_wide), **_k)
+    _named(f'forms-motion-800-wide{_wide}', S(POLY), G(POLY, wide=_wide, all_r=1, wg=1), n=(800, 800, 0, 800), **_k)
+    _named(f'forms-motion-allr-wide{_wide}', S(POLY), G(POLY, wide=_wide, all_r=1, wg=1), all_r=1, **_k)
+    _named(f'forms-motion-allr0-wide{_wide}', S(POLY), G(POLY, wide=_wide), all_r=0, n=(800, 800, 0, 800), **_k)
+    _named(f'forms-motion-R1-wide{_wide}', S(POLY), G(POLY, wide=_wide, wg=1), R=1, n=(800, 800, 0, 800), **_k)   # (one reference time: nothing to fold)
+    _named(f'forms-motion-forward-wide{_wide}', S(POLY), None, want_grad=0, **_k)
+# the three other splat windows, at 2-DoF and at a grid: k_splat_r / k_gather_r take neither `wide` nor the projection nor all_r
+for _rad in (0, 2, 3):
+    _named(f'forms-rad{_rad}-2dof', S(CONST, _rad, 256), G2(_rad), rad=_rad, hw=(1, 1), vmax=150.0)
+    _named(f'forms-rad{_rad}-grid', S(TILE, _rad, 256), G(TILE, _rad, 0, 256), rad=_rad, vmax=150.0)
+    _named(f'forms-rad{_rad}-grid-wide-allr', S(TILE, _rad, 256), G(TILE, _rad, 0, 256), rad=_rad, wide=1, all_r=1, n=(800, 800, 0, 800))
+    _named(f'forms-rad{_rad}-dense', S(TILE, _rad, 256), G(TILE, _rad, 0, 256), rad=_rad, hw=(PH, PW))
+# the cells of tests/_launch_policy_cases.py, unweighted and weighted (tests/test_gpu_launch_policy_parity.py,
+# tests/test_gpu_event_weights_cells.py): 2-DoF on the long and on the short list; every grid has 700 gather segments and more
+for _c in C.CASES:
+    for _wt in (0, 1):
+        _k = dict(H=C.H, W=C.W, R=C.R, B=C.B, weighted=_wt, wide=-1, hw=_c.hw, vmax=_c.v, counts=C.counts(_c.batch))
+        if _c.two_dof:
+            _named(f'forms-cell-{_c.id}-w{_wt}', S(CONST, wt=_wt, lst=L_SPLAT_SHORT if _c.list == 'short' else L_SPLAT), G2(wt=_wt, wg=C.R), **_k)
+        else:
+            _named(f'forms-cell-{_c.id}-w{_wt}', S(TILE, wt=_wt), G(TILE, proj=1, all_r=1, wt=_wt, wg=1), **_k)
+
+# closure: everything the entry points accept, on a small sensor
+SWEEP = []
+_E = None
+
+
+def _refused(shape, weighted, rad):
+    """What check_staging / eincm_set_splat_window (engine.event_weights_refusal) and motion_fused_supported (engine.motion_fused_refusal) refuse."""
+    global _E
+    if _E is None:
+        import importlib
+        _E = importlib.import_module('edge-informed-contrast-maximization_amd.engine')
+    size = 2 * rad + 1
+    if weighted and _E.event_weights_refusal('fp32', size) is not None:
+        return True
+    return shape == 'motion' and _E.motion_fused_refusal('fp32', size, _E.make_params(20.0, 35.0, 0.0, 0.0, 2), bool(weighted)) is not None
+
+
+SWEEP_HW = {'identity': (40, 48), '2dof': (1, 1), 'grid': (2, 2), 'motion': (0, 0)}
+for _shape, _hw in SWEEP_HW.items():
+    for _wt in (0, 1):
+        for _rad in (0, 1, 2, 3):
+            if _refused(_shape, _wt, _rad):
+                continue
+            for _wide in (0, 1):
+                for _proj in (0, 1):
+                    for _allr in (None, 0, 1):
+                        for _n in (699, 700, 701):
+                            for _wg in (0, 1):
+                                for _v in (3.0, 200.0):
+                                    SWEEP.append(_forms_case(
+                                        f'sweep-{_shape}-w{_wt}-r{_rad}-wide{_wide}-p{_proj}-a{_allr}-n{_n}-g{_wg}-v{_v:g}', H=40, W=48, R=3, B=2,
+                                        rad=_rad, weighted=_wt, wide=_wide, proj=_proj, n=(_n, 50, 50, 50), all_r=_allr,
+                                        motion=int(_shape == 'motion'), hw=_hw, vmax=_v, want_grad=_wg))
+
+
+def _form(parts):
+    """The checker's line as (splat, gather, plan) dicts; gather None where none was planned."""
+    s = dict(zip(('mode', 'rad', 'threads', 'weighted', 'row', 'lds', 'list', 'wincap', 'winmaxw'), _i(parts[0]).tolist()))
+    g = dict(zip(('mode', 'rad', 'wide', 'threads', 'proj', 'all_r', 'weighted', 'row', 'lds', 'list', 'copy', 'wg', 'wincap', 'winmaxw', 'pal'),
+                 _i(parts[1]).tolist()))
+    p = dict(zip(('wincap', 'winmaxw', 'wincap_a', 'winmaxw_a', 'pal', 'cap_2', 'maxw_2', 'pal_2', 'splat_short', 'proj', 'all_r', 'host_asm'),
+                 _i(parts[2]).tolist()))
+    s['key'] = tuple(s[k] for k in ('mode', 'rad', 'threads', 'weighted'))
+    g['key'] = tuple(g[k] for k in ('mode', 'rad', 'wide', 'threads', 'proj', 'all_r', 'weighted'))
+    return s, (g if g['row'] >= 0 or any(g['key']) else None), p
+
+
+def _rows(out):
+    """The four form lists as lists of key tuples: k_splat's, k_splat_r's, k_gather's, k_gather_r's."""
+    sp, spr, ga, gar = out['formrows']
+    return [[tuple(r) for r in _i(part).reshape(-1, n).tolist()] for part, n in ((sp, 4), (spr, 4), (ga, 7), (gar, 7))]
+
+
+def _check_form(name, s, g, p, rows):
+    """What must hold of every planned form: it is a row of its family's list, at that row; its threads, LDS bytes and window
+    geometry are the ones the parent's launch code computed beside its ladders."""
+    sp, spr, ga, gar = rows
+    fam = sp if s['rad'] == 1 else spr
+    assert 0 <= s['row'] < len(fam) and fam[s['row']] == s['key'], (name, s)
+    tile = 0 if s['mode'] == CONST else THETA_TILE_BYTES
+    scratch = POLY_SCRATCH_BYTES if s['mode'] == POLY else 0
+    if s['rad'] == 1:
+        assert s['threads'] == 512 and (s['wincap'], s['winmaxw']) == (p['wincap'], p['winmaxw']), (name, s, p)
+        assert s['lds'] == s['wincap'] * 4 + tile + scratch, (name, s)
+    else:                              # u64 windows, capped to fit beside the Theta tile; the plan keeps the uncapped capacity
+        assert s['threads'] == 256 and s['wincap'] == min(p['wincap'], SW_CAP[s['mode']]), (name, s, p)
+        assert s['winmaxw'] == max(40, round(math.sqrt(s['wincap'] * 1.4))) and s['lds'] == s['wincap'] * 8 + tile, (name, s)
+    assert s['lds'] <= 65536 and s['list'] == (L_SPLAT_SHORT if p['splat_short'] else L_SPLAT), (name, s, p)
+    if g is None:
+        return
+    fam = ga if g['rad'] == 1 else gar
+    assert 0 <= g['row'] < len(fam) and fam[g['row']] == g['key'], (name, g)
+    two_dof = g['mode'] == CONST
+    assert g['threads'] == (256 if two_dof or g['rad'] != 1 else 512), (name, g)
+    want_geom = (p['cap_2'], p['maxw_2'], p['pal_2']) if two_dof else (p['wincap_a'], p['winmaxw_a'], p['pal'])
+    assert (g['wincap'], g['winmaxw'], g['pal']) == want_geom, (name, g, p)
+    assert g['lds'] == g['wincap'] * 4 + (0 if two_dof else ACCUM_BYTES + THETA_TILE_BYTES) + scratch and g['lds'] <= 65536, (name, g)
+    assert (g['list'], g['copy']) == ((L_GATHER_2DOF, COPY_SPLAT) if two_dof else (L_GATHER, COPY_GATHER)), (name, g)
+    assert g['proj'] == p['proj'] and g['all_r'] == p['all_r'], (name, g, p)
+
+
+def test_the_form_lists_are_the_instantiations_of_the_library(out):
+    """5 k_splat, 6 k_splat_r, 18 k_gather and 6 k_gather_r kernels, as the parent's code object holds them (profiles/launch_forms.md)."""
+    sp, spr, ga, gar = _rows(out)
+    assert sorted(sp) == sorted([(m, 1, 512, wt) for m in (CONST, TILE) for wt in (0, 1)] + [(POLY, 1, 512, 0)])
+    assert sorted(spr) == sorted((m, r, 256, 0) for m in (CONST, TILE) for r in (0, 2, 3))
+    assert sorted(ga) == sorted([(CONST, 1, 0, 256, 0, 0, wt) for wt in (0, 1)] +
+                                [(TILE, 1, wide, 512, pr, ar, wt) for wide in (0, 1) for pr, ar in ((0, 0), (1, 0), (1, 1)) for wt in (0, 1)] +
+                                [(POLY, 1, wide, 512, 0, ar, 0) for wide in (0, 1) for ar in (0, 1)])
+    assert sorted(gar) == sorted((m, r, 0, 256, 0, 0, 0) for m in (CONST, TILE) for r in (0, 2, 3))
+    for fam in (sp, spr, ga, gar):
+        assert len(set(fam)) == len(fam)
+
+
+def test_named_cells_take_their_forms(out):
+    rows = _rows(out)
+    for name, (want_s, want_g) in NAMED.items():
+        s, g, p = _form(out[name])
+        assert (s['key'], s['list']) == want_s, (name, s, want_s)
+        if want_g is None:
+            assert g is None, (name, g)
+        else:
+            assert g is not None and (g['key'], g['list'], g['copy'], g['wg']) == want_g, (name, g, want_g)
+        _check_form(name, s, g, p, rows)
+    # the capped window of k_splat_r lives in the form alone
+    for rad in (0, 2, 3):
+        s, _, p = _form(out[f'forms-rad{rad}-grid'])
+        assert p['wincap'] == 6912 and s['wincap'] == 4608
+        s, _, p = _form(out[f'forms-rad{rad}-2dof'])
+        assert p['wincap'] == s['wincap'] == 6912
+    # the launch-policy cells: the splat's capacity class and pitch are the case's
+    for c in C.CASES:
+        s, g, p = _form(out[f'forms-cell-{c.id}-w0'])
+        assert s['wincap'] == c.cap and p['pal'] == int(c.aligned), (c.id, s, p)
+
+
+def test_every_reachable_form_is_a_row_and_every_row_is_reached(out):
+    rows = _rows(out)
+    reached = [set(), set(), set(), set()]
+    assert len(SWEEP) > 2000
+    for name in SWEEP:
+        s, g, p = _form(out[name])
+        _check_form(name, s, g, p, rows)
+        assert (g is not None) == name.split('-')[8].endswith('1'), name       # a gather form exactly for a gradient evaluation
+        reached[0 if s['rad'] == 1 else 1].add(s['key'])
+        if g is not None:
+            reached[2 if g['rad'] == 1 else 3].add(g['key'])
+    for fam, got in zip(rows, reached):
+        assert got == set(fam), (sorted(set(fam) - got), sorted(got - set(fam)))
+
+
+def test_a_refused_combination_has_no_row(out):
+    """Weights or a motion model with another splat window, weights with a motion model: the entry points refuse them, and the plan
+    names no kernel for them (row -1: the launch reports it instead of running some kernel)."""
+    for name in ('refused-weighted-rad2', 'refused-motion-rad2', 'refused-weighted-motion'):
+        s, g, _ = _form(out[name])
+        assert s['row'] == -1 and g is not None and g['row'] == -1, (name, s, g)
+
+
+_forms_case('refused-weighted-rad2', weighted=1, rad=2)
+_forms_case('refused-motion-rad2', motion=1, rad=2, hw=(0, 0))
+_forms_case('refused-weighted-motion', weighted=1, motion=1, hw=(0, 0))
+
+
+# ================================================================================================
 # segment cut
 # ================================================================================================
 CUTS = {}                              # name -> (counts (nbins,), ntiles, seg)

@@ -6,7 +6,10 @@ Build each with the hipcc line of build() plus `--cuda-device-only -S -o X.s`, t
     python tools/kernel_diff.py PARENT.s NEW.s
 
 It lists every kernel whose instruction text differs (or that only one file has), with its instruction counts and the .amdhsa
-register, LDS and scratch lines of both.  It compares text only.  Exit status 0; the list is the result.
+register, LDS and scratch lines of both.  It compares text only, with one allowance: the compiler numbers a function's local labels
+(.LBB<f>_<n>, .LJTI<f>_<n>) by the function's place <f> in the module, which moves when other kernels are instantiated in another
+order, so <f> is dropped before the comparison.  A kernel whose instructions agree and whose resource lines do not is listed too.
+Exit status 0; the list is the result.
 """
 import re
 import sys
@@ -24,7 +27,7 @@ def kernels(path):
         for ln in m.group(2).splitlines():
             ln = ln.split(';')[0].strip()
             if ln and not ln.startswith('.') and not ln.endswith(':'):
-                lines.append(re.sub(r'\s+', ' ', ln))
+                lines.append(re.sub(r'\.(LBB|LJTI)\d+_', r'.\1_', re.sub(r'\s+', ' ', ln)))
         body[name] = lines
     for m in re.finditer(r'^\s*\.amdhsa_kernel\s+(\w+)\n(.*?)^\s*\.end_amdhsa_kernel', text, re.S | re.M):
         res[m.group(1)] = {k: v for k, v in re.findall(r'^\s*(\.amdhsa_\w+)\s+(\S+)', m.group(2), re.M) if k in RESOURCES}
@@ -37,7 +40,7 @@ def main():
     for name in sorted(set(a) | set(b)):
         if name not in a or name not in b:
             print(f'{name}: only in {sys.argv[1] if name in a else sys.argv[2]}')
-        elif a[name][0] == b[name][0]:
+        elif a[name] == b[name]:
             same += 1
         else:
             print(f'{name}: instructions {len(a[name][0])} -> {len(b[name][0])}')
