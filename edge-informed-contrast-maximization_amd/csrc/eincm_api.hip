@@ -37,6 +37,7 @@
 #include "eincm_lbfgs.hip.h"
 #include "eincm_motion.hip.h"
 #include "eincm_event_support.hip.h"
+#include "eincm_event_filter.hip.h"
 
 using namespace eincm;
 
@@ -227,6 +228,10 @@ struct eincm_ctx : PlanCtx {
         Grow<double> last_t;           // (H, W) the time of every pixel's last event so far, -inf: none; allocated by the first call
         double last_time = es_no_event();   // the time of the last event of the previous chunk
     } es;
+    struct {                           // eincm_event_filter: its own carried state, apart from es
+        Grow<double> maps;             // 3 (H, W): last_any | last_kept[0] | last_kept[1], -inf: none; allocated by the first call
+        double last_time = es_no_event();   // the time of the last event of the previous chunk
+    } ef;
     // the staged flow evaluation of eincm_flow_eval_stage: [GT flow (n, H, W) double2 | flag bytes (n, H, W)],
     // kept from one staging to the next; every eincm_flow_errors reads it
     struct {
@@ -2574,6 +2579,116 @@ int eincm_event_support(eincm_ctx* c, const int16_t* x, const int16_t* y, const 
     if (support) HIPCHK(c, op.down(support, d_s, (size_t)n));
     HIPCHK(c, op.sync());
     c->es.last_time = t[n - 1];
+    return EINCM_OK;
+}
+
+// The refractory and polarity-aware filter for one chunk of a stream (eincm_event_filter.hip.h): validate, sort
+// and bound as eincm_event_support does, decide per sorted position which events survive, max-scan the survivors' positions, count
+// every kept event's neighbours from kept events alone, update the three carried maps.  A refused chunk leaves the carried state as
+// it was.
+int eincm_event_filter(eincm_ctx* c, const int16_t* x, const int16_t* y, const double* t, const int8_t* p, int64_t n, double refractory,
+                       double tau, int radius, int full_support, int flags, const uint8_t* pixel_mask, int reset, uint8_t* keep,
+                       float* weights, uint8_t* support) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = not_in_flight(c, "eincm_event_filter")) return rc;
+    switch (ef_check_args(n, refractory, tau, radius, full_support, flags, p != nullptr)) {
+        case EF_ARG_N: return fail(c, EINCM_ERR_ARG, "n = %lld outside [0, 2^30] (walk a recording in chunks)", (long long)n);
+        case EF_ARG_REFRACTORY: return fail(c, EINCM_ERR_ARG, "refractory = %g (finite and >= 0)", refractory);
+        case EF_ARG_TAU: return fail(c, EINCM_ERR_ARG, "tau = %g (finite and >= 0)", tau);
+        case EF_ARG_RADIUS: return fail(c, EINCM_ERR_ARG, "radius = %d outside [0, %d]", radius, ES_MAX_RADIUS);
+        case EF_ARG_FULL_SUPPORT:
+            return fail(c, EINCM_ERR_ARG, "full_support = %d outside [1, %d] for radius %d", full_support,
+                        radius == 0 ? 1 : es_max_support(radius), radius);
+        case EF_ARG_FLAGS:
+            return fail(c, EINCM_ERR_ARG, "flags = %d (%s)", flags,
+                        (flags & ~EF_KNOWN_FLAGS) ? "EINCM_EF_POLARITY is the only flag" : "EINCM_EF_POLARITY needs p");
+        case EF_ARG_OK: break;
+    }
+    if (n > 0 && (!x || !y || !t || !keep || !weights)) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    const int H = c->H, W = c->W;
+    const int64_t npix = (int64_t)H * W;
+    const double carried = reset ? es_no_event() : c->ef.last_time;
+    const int nblk = (int)((n + ES_SORT_BLOCK - 1) / ES_SORT_BLOCK);
+    const size_t nhist = (size_t)ES_RADIX * (size_t)nblk;
+    const unsigned gn = (unsigned)((n + NT - 1) / NT), gp = (unsigned)((npix + NT - 1) / NT);
+    OneShot op(c);
+    const auto d_x = op.piece<int16_t>((size_t)n), d_y = op.piece<int16_t>((size_t)n);
+    const auto d_t = op.piece<double>((size_t)n);
+    const auto d_p = op.piece<int8_t>((size_t)n, p != nullptr);
+    const OneShot::Piece<uint32_t> d_key[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
+    const OneShot::Piece<uint32_t> d_val[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
+    const auto d_hist = op.piece<uint32_t>(nhist);
+    const size_t ntiles = (nhist + ES_SCAN_TILE - 1) / ES_SCAN_TILE;
+    const auto d_tiles = op.piece<uint32_t>(ntiles);
+    const auto d_lohi = op.piece<uint32_t>((size_t)npix * 2);            // lo | hi
+    const auto d_mask = op.piece<uint8_t>((size_t)npix, pixel_mask != nullptr);
+    const auto d_m = op.piece<uint2>((size_t)n);                         // the scan seeds, then the scan
+    const size_t nmt = ((size_t)n + EF_SCAN_TILE - 1) / EF_SCAN_TILE;
+    const auto d_mt = op.piece<uint2>(nmt);
+    const auto d_k = op.piece<uint8_t>((size_t)n);
+    const auto d_w = op.piece<float>((size_t)n);
+    const auto d_s = op.piece<uint8_t>((size_t)n);
+    const auto d_err = op.piece<uint32_t>(1);
+    uint32_t* h_err = op.host_buf<uint32_t>(1);                          // d_err comes down here
+    HIPCHK(c, op.begin());
+    if (n > 0) {
+        HIPCHK(c, op.up(d_x, x, (size_t)n * 2));                         // (host memory: the caller's, as every copy below but h_err's)
+        HIPCHK(c, op.up(d_y, y, (size_t)n * 2));
+        HIPCHK(c, op.up(d_t, t, (size_t)n * 8));
+        HIPCHK(c, op.zero(d_err, sizeof(uint32_t)));
+        HIPCHK(c, op.launch(k_es_validate, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, carried, d_key[0], d_err));
+        HIPCHK(c, op.down(h_err, d_err, sizeof(uint32_t)));
+        HIPCHK(c, op.sync());
+        if (*h_err) {
+            const int64_t e = n - (int64_t)*h_err;
+            if (e < 0 || e >= n) return fail(c, EINCM_ERR_HIP, "first refused event %lld of %lld", (long long)e, (long long)n);
+            switch (es_event_fault(H, W, x[e], y[e], t[e], e > 0 ? t[e - 1] : carried)) {
+                case ES_EV_COORD: return fail(c, EINCM_ERR_ARG, "event %lld: (%d, %d) outside the %dx%d sensor", (long long)e, x[e], y[e], H, W);
+                case ES_EV_TIME: return fail(c, EINCM_ERR_ARG, "event %lld: time %g is not finite", (long long)e, t[e]);
+                default:
+                    return fail(c, EINCM_ERR_ARG, "event %lld: time %.17g is smaller than %.17g, %s", (long long)e, t[e],
+                                e > 0 ? t[e - 1] : carried, e > 0 ? "its predecessor's" : "the last time of the previous chunk");
+            }
+        }
+    }
+    const bool fresh = c->ef.maps.n < (size_t)npix * 3;
+    HIPCHK(c, ensure(c, c->ef.maps, (size_t)npix * 3));
+    if (fresh || reset) {
+        HIPCHK(c, op.launch(k_es_fill, dim3((unsigned)((npix * 3 + NT - 1) / NT)), dim3(NT), 0, npix * 3, c->ef.maps.p, es_no_event()));
+        c->ef.last_time = es_no_event();
+    }
+    if (n == 0) { HIPCHK(c, op.sync()); return EINCM_OK; }
+    double* const last_any = c->ef.maps.p;
+    double* const kept0 = last_any + npix;
+    double* const kept1 = kept0 + npix;
+    uint32_t* const d_lo = d_lohi;
+    uint32_t* const d_hi = d_lo + npix;
+    if (pixel_mask) HIPCHK(c, op.up(d_mask, pixel_mask, (size_t)npix));
+    if (p) HIPCHK(c, op.up(d_p, p, (size_t)n));
+    HIPCHK(c, op.zero(d_lo, (size_t)npix * 2 * sizeof(uint32_t)));
+    const int passes = es_sort_passes(npix);
+    int cur = 0;                                                         // the sorted (key, index) arrays so far: d_key[cur], d_val[cur]
+    for (int pass = 0; pass < passes; ++pass, cur ^= 1) {
+        const int shift = pass * ES_RADIX_BITS;
+        const uint32_t* const vin = pass ? (const uint32_t*)d_val[cur] : nullptr;      // (pass 0: the indices themselves)
+        HIPCHK(c, op.launch(k_es_hist, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], d_hist));
+        HIPCHK(c, op.launch(k_es_scan_tiles, dim3((unsigned)ntiles), dim3(ES_SCAN_NT), 0, (int64_t)nhist, d_hist, d_tiles));
+        HIPCHK(c, op.launch(k_es_scan, dim3(1), dim3(ES_SCAN_NT), 0, (int64_t)ntiles, d_tiles));
+        HIPCHK(c, op.launch(k_es_scatter, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], vin, d_hist, d_tiles,
+                            d_key[cur ^ 1], d_val[cur ^ 1]));
+    }
+    HIPCHK(c, op.launch(k_es_bounds, dim3(gn), dim3(NT), 0, n, npix, d_key[cur], d_lo, d_hi));
+    HIPCHK(c, op.launch(k_ef_keep, dim3(gn), dim3(NT), 0, n, d_key[cur], d_val[cur], d_lo, d_t, d_p, refractory, d_mask, last_any, d_k, d_m));
+    HIPCHK(c, op.launch(k_ef_scan_tiles, dim3((unsigned)nmt), dim3(EF_SCAN_NT), 0, n, d_m, d_mt));
+    HIPCHK(c, op.launch(k_ef_scan, dim3(1), dim3(EF_SCAN_NT), 0, (int64_t)nmt, d_mt));
+    HIPCHK(c, op.launch(k_ef_support, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, d_p, tau, radius, full_support,
+                        (flags & EF_POLARITY) ? 1 : 0, d_mask, d_lo, d_hi, d_val[cur], d_m, d_mt, d_k, kept0, kept1, d_w, d_s));
+    HIPCHK(c, op.launch(k_ef_map, dim3(gp), dim3(NT), 0, npix, n, d_lo, d_hi, d_val[cur], d_m, d_mt, d_t, last_any, kept0, kept1));
+    HIPCHK(c, op.down(keep, d_k, (size_t)n));
+    HIPCHK(c, op.down(weights, d_w, (size_t)n * sizeof(float)));
+    if (support) HIPCHK(c, op.down(support, d_s, (size_t)n));
+    HIPCHK(c, op.sync());
+    c->ef.last_time = t[n - 1];
     return EINCM_OK;
 }
 

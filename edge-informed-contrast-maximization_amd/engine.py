@@ -349,6 +349,43 @@ def check_event_support_args(tau, radius, full_support):
     return tau, int(radius), int(full_support)
 
 
+EVENT_FILTER_POLARITY = 1         # EINCM_EF_POLARITY (include/eincm.h)
+
+
+def check_event_filter_args(refractory, tau, radius, full_support, polarity):
+    """(refractory, tau, radius, full_support, flags) of the event filter; ValueError as eincm_event_filter refuses them.  radius 0
+    switches the support stage off and leaves full_support one value."""
+    try:
+        refractory = float(refractory)
+    except (TypeError, ValueError):
+        raise ValueError(f'refractory {refractory!r}: a finite number >= 0') from None
+    if not np.isfinite(refractory) or refractory < 0.0:
+        raise ValueError(f'refractory = {refractory!r} (finite and >= 0)')
+    if isinstance(radius, (int, np.integer)) and not isinstance(radius, bool) and radius == 0:
+        tau, _, _ = check_event_support_args(tau, 1, 1)
+        if isinstance(full_support, bool) or not isinstance(full_support, (int, np.integer)) or full_support != 1:
+            raise ValueError(f'full_support = {full_support!r} with radius 0 (the support stage is off: 1)')
+    else:
+        tau, radius, full_support = check_event_support_args(tau, radius, full_support)
+    if not isinstance(polarity, (bool, np.bool_)):
+        raise ValueError(f'polarity {polarity!r}: True or False')
+    return refractory, tau, int(radius), int(full_support), EVENT_FILTER_POLARITY if polarity else 0
+
+
+def check_event_polarity(ps, n, polarity):
+    """None, or the polarity classes of a raw stream as int8 (1 where the input is > 0: {0, 1} and {-1, +1} recordings alike)."""
+    if ps is None:
+        if polarity:
+            raise ValueError('polarity=True needs the events\' polarities')
+        return None
+    a = np.asarray(ps)
+    if a.ndim != 1 or a.shape[0] != n:
+        raise ValueError(f'event p must be 1-D with {n} elements, got shape {a.shape}')
+    if a.dtype.kind not in 'biu':
+        raise ValueError(f'event p must be a boolean or integer array, got {a.dtype}')
+    return np.ascontiguousarray(a > 0, dtype=np.int8)
+
+
 def check_pixel_mask(pixel_mask, shape):
     """None, or the (H, W) mask as uint8 with 1 where the input is non-zero."""
     if pixel_mask is None:
@@ -1228,6 +1265,36 @@ class Engine:
                 self._ctx, x.ctypes.data + 2 * i0, y.ctypes.data + 2 * i0, t.ctypes.data + 8 * i0, i1 - i0, tau, radius, full_support,
                 None if mask is None else mask.ctypes.data, int(i0 == 0), weights.ctypes.data + 4 * i0, support.ctypes.data + i0))
         return (weights, support) if return_support else weights
+
+    def event_filter(self, xs, ys, ts, ps=None, refractory=0.0, tau=0.0, radius=1, full_support=1, polarity=False, pixel_mask=None,
+                     chunk=1 << 22, return_support=False):
+        """The refractory and polarity-aware filter of a raw stream, beside ``event_support``.  An event is
+        dropped when it follows its own pixel's previous event, kept or not, by less than ``refractory`` (or lies on a masked
+        pixel); a kept event's support counts the neighbours whose last KEPT event lies at most ``tau`` back, of the event's own
+        polarity class with ``polarity=True``.  ps: boolean or integer array (class 1 where > 0), needed only with
+        ``polarity=True``.  ``radius=0`` switches the support stage off: the weights are then 1 for kept events.  Everything else
+        (stream order, times, mask, chunking, refusals) is ``event_support``'s.  Returns (keep bool (n,), weights float32 (n,)), and
+        the uint8 support too when asked; the staged lists are not shortened, callers index with ``keep``."""
+        x, y = check_event_coords(xs, ys)
+        n = x.shape[0]
+        t = check_event_times(ts, n)
+        refractory, tau, radius, full_support, flags = check_event_filter_args(refractory, tau, radius, full_support, polarity)
+        p = check_event_polarity(ps, n, polarity)
+        mask = check_pixel_mask(pixel_mask, (self.H, self.W))
+        chunk = check_chunk(chunk)
+        bad = event_support_first_offender(x, y, t, (self.H, self.W))
+        if bad is not None:
+            raise ValueError(bad[1])
+        keep, weights, support = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.float32), np.empty(n, dtype=np.uint8)
+        # an empty stream still reaches the library: it clears the carried state
+        for i0 in ([0] if n == 0 else range(0, n, chunk)):
+            i1 = min(n, i0 + chunk)
+            self._check_data(self._lib.eincm_event_filter(
+                self._ctx, x.ctypes.data + 2 * i0, y.ctypes.data + 2 * i0, t.ctypes.data + 8 * i0, None if p is None else p.ctypes.data + i0,
+                i1 - i0, refractory, tau, radius, full_support, flags, None if mask is None else mask.ctypes.data, int(i0 == 0),
+                keep.ctypes.data + i0, weights.ctypes.data + 4 * i0, support.ctypes.data + i0))
+        keep = keep.view(np.bool_)
+        return (keep, weights, support) if return_support else (keep, weights)
 
     def remap_cubic(self, src, mapping):
         """cv.remap(src, mapping, None, INTER_CUBIC) under the contract of DESIGN.md section 16 (map_image_to_rect_event,

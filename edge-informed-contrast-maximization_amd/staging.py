@@ -199,6 +199,34 @@ def event_support_weights(events, sensor_size, tau, radius=1, full_support=1, pi
                                                       return_support=return_support)
 
 
+def event_filter_weights(events, sensor_size, refractory=0.0, tau=0.0, radius=1, full_support=1, polarity=False, pixel_mask=None,
+                         chunk=1 << 22, return_support=False, engine=None):
+    """The keep mask and per-event weights of a raw stream from the refractory and polarity-aware filter (Engine.event_filter,
+    DESIGN.md section 24).  events: {'x','y','t',...} arrays in stream order, with 'p' where ``polarity=True`` asks for it (it is
+    handed over whenever it is there); ``refractory`` and ``tau`` in the unit of events['t'].  engine None: the cached small context
+    of edges._engine.  The arguments are checked here, before a context is made.  Returns (keep bool (n,), weights float32 (n,)),
+    and the uint8 support too when asked: ``stage_datasample(event_weights=)`` takes the weights, dropped events weigh 0."""
+    from .engine import (check_chunk, check_event_coords, check_event_filter_args, check_event_polarity, check_event_times,
+                         check_pixel_mask, event_support_first_offender)
+    missing = [k for k in ('x', 'y', 't') if k not in events]
+    if missing:
+        raise ValueError(f'events lack {missing}')
+    H, W = (int(sensor_size[0]), int(sensor_size[1])) if engine is None else (engine.H, engine.W)
+    if (H, W) != (int(sensor_size[0]), int(sensor_size[1])):
+        raise ValueError(f'sensor_size {tuple(sensor_size)} is not the engine\'s ({H}, {W})')
+    x, y = check_event_coords(events['x'], events['y'])
+    t = check_event_times(events['t'], x.shape[0])
+    refractory, tau, radius, full_support, _ = check_event_filter_args(refractory, tau, radius, full_support, polarity)
+    p = check_event_polarity(events.get('p'), x.shape[0], polarity)
+    mask = check_pixel_mask(pixel_mask, (H, W))
+    chunk = check_chunk(chunk)
+    bad = event_support_first_offender(x, y, t, (H, W)) if engine is None else None      # (an engine handed over looks itself)
+    if bad is not None:
+        raise ValueError(bad[1])
+    return _dsec_engine(engine, (H, W)).event_filter(x, y, t, p, refractory=refractory, tau=tau, radius=radius, full_support=full_support,
+                                                     polarity=bool(polarity), pixel_mask=mask, chunk=chunk, return_support=return_support)
+
+
 def hot_pixel_mask(xs, ys, sensor_size, max_count):
     """(H, W) uint8, 1 at the pixels with more than ``max_count`` events: ready for ``pixel_mask=``.  Plain numpy."""
     from .engine import check_event_coords

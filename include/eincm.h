@@ -31,7 +31,8 @@ extern "C" {
                                *    eincm_flow_eval_stage, eincm_flow_errors (batched flow errors of solved thetas), eincm_lbfgs_* (that BFGS with a limited-memory
                                *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models),
                                *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels), eincm_set_windows_weighted (per-event weights),
-                               *    eincm_event_support (the event-support filter) */
+                               *    eincm_event_support (the event-support filter), eincm_event_filter (the refractory and polarity-aware
+                               *    filter) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -480,6 +481,31 @@ int eincm_rectify_events(eincm_ctx* ctx, const float* rectify_map, const int16_t
  * counts and no floating-point sums: the same bytes on every run, in fp32 and EINCM_CF_FP64 contexts. */
 int eincm_event_support(eincm_ctx* ctx, const int16_t* x, const int16_t* y, const double* t, int64_t n, double tau, int radius,
                         int full_support, const uint8_t* pixel_mask, int reset, float* weights, uint8_t* support);
+
+/* The refractory and polarity-aware filter of a raw event stream, one chunk of n <= 2^30 events per call.
+ * An operator beside eincm_event_support: stream order, finite non-decreasing times, the neighbour window, the mask, the refusals
+ * and the chunking are that operator's, and the carried state is its own (eincm_event_support's is not touched).  p (n) int8 or
+ * NULL: the polarity class of event e is p[e] > 0, NULL puts every event in class 0.  Per event e at pixel P, in stream order:
+ *   kept = P not masked and not (t[e] - last_any[P] < refractory), last_any[P] being the time of P's previous event whatever
+ *          became of it (none: kept; refractory == 0 keeps every unmasked event; equal times on one pixel with refractory > 0 drop
+ *          the later index); then last_any[P] = t[e], for masked events too;
+ *   a kept event with radius > 0 counts the neighbours q (as eincm_event_support) with t[e] - L(q) <= tau, where L(q) is the time
+ *          of q's last KEPT event: of class c_e under EINCM_EF_POLARITY, of either class without; then last_kept[c_e][P] = t[e].
+ *          radius == 0 switches the support stage off (full_support must be 1); a kept event still updates last_kept.
+ * keep[e] = kept (uint8); support[e] (uint8, may be NULL) is 0 for dropped events and for radius == 0; weights[e] =
+ * (float)min(support, full_support) / (float)full_support with radius > 0, kept ? 1 : 0 with radius == 0.  The context carries the
+ * three (H, W) maps last_any, last_kept[0], last_kept[1] (allocated by the first call) and the time of the last event handed over;
+ * reset != 0 clears them before the chunk, so any split of a stream into consecutive chunks gives the bytes of the unsplit call.
+ * With refractory == 0 and flags == 0, weights and support are the bytes of eincm_event_support.  n == 0 is valid and writes
+ * nothing.  EINCM_ERR_ARG, before any output is written and with the carried state unchanged: an event refused as
+ * eincm_event_support refuses it (naming the first offender's index); n, refractory, tau, radius, full_support or flags out of
+ * range (the first of that order); a flag other than EINCM_EF_POLARITY, EINCM_EF_POLARITY with p == NULL; a null x, y, t, keep or
+ * weights with n > 0.  EINCM_ERR_STATE: an evaluation is in flight.  Integer maxima and counts, no floating-point sums: the same
+ * bytes on every run, in fp32 and EINCM_CF_FP64 contexts. */
+#define EINCM_EF_POLARITY 1   /* flags: support counts only neighbours' kept events of the event's own polarity class */
+int eincm_event_filter(eincm_ctx* ctx, const int16_t* x, const int16_t* y, const double* t, const int8_t* p, int64_t n,
+                       double refractory, double tau, int radius, int full_support, int flags,
+                       const uint8_t* pixel_mask, int reset, uint8_t* keep, float* weights, uint8_t* support);
 
 /* cv.remap(src, map, None, INTER_CUBIC) of 8-bit single-channel images, constant border 0, as a written contract (DESIGN.md section 16;
  * parity with OpenCV itself is not pinned).  src (n, src_h, src_w), 1 <= src_h, src_w <= 32766, independent of the sensor; map (H, W, 2)

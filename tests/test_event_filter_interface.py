@@ -1,0 +1,339 @@
+"""The refractory and polarity-aware event filter without a GPU: the entry point in header, binding and
+cross-compiled library, the refusals that Python raises before a library call, the properties of the sequential witness
+(tests/_event_filter_witness.py) that the contract lists as consequences, and the conditions that keep
+tests/test_gpu_event_filter.py honest.  From the witness alone, every generated case with radius > 0 has at least 25 % of its events
+dropped by the refractory rule, 20 % kept with weight 0, 8 % kept with weight > 0, 5 % strictly between 0 and 1 (full_support > 1)
+or at weight 1 (full_support 1); the polarity flag changes the support of at least 3 % of the events, and a filter whose last_kept
+maps every unmasked event updates differs in at least 2 %."""
+import ctypes as C
+import importlib
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+import _event_filter_witness as EF
+import _event_support_witness as ES
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+L = importlib.import_module('edge-informed-contrast-maximization_amd._lib')
+E = importlib.import_module('edge-informed-contrast-maximization_amd.engine')
+staging = importlib.import_module('edge-informed-contrast-maximization_amd.staging')
+
+NAME = 'eincm_event_filter'
+# the two Python entry points: a tree without them has nothing that this module could test
+event_filter, event_filter_weights = E.Engine.event_filter, staging.event_filter_weights
+EF_SCAN_TILE = 4096        # the scan's tile (csrc/eincm_event_filter.hip.h), which the GPU module's sizes are built around
+
+
+# ---- the entry point ---------------------------------------------------------------------------------------------------------
+def test_entry_point_in_header_binding_and_library(built_lib):
+    hdr = open(os.path.join(ROOT, 'include', 'eincm.h')).read()
+    m = re.search(r'int\s+' + NAME + r'\s*\(([^)]*)\)', hdr)
+    assert m, 'not declared'
+    args = [' '.join(a.split()) for a in m.group(1).split(',')]
+    assert args == ['eincm_ctx* ctx', 'const int16_t* x', 'const int16_t* y', 'const double* t', 'const int8_t* p', 'int64_t n',
+                    'double refractory', 'double tau', 'int radius', 'int full_support', 'int flags', 'const uint8_t* pixel_mask',
+                    'int reset', 'uint8_t* keep', 'float* weights', 'uint8_t* support']
+    defines = dict(re.findall(r'#define\s+(EINCM_[A-Z0-9_]+)\s+(\d+)\b', hdr))
+    assert int(defines['EINCM_ABI_VERSION']) == 6 and int(defines['EINCM_EF_POLARITY']) == 1 == E.EVENT_FILTER_POLARITY
+    assert NAME in hdr.split('#define EINCM_ABI_VERSION')[1].split('*/')[0], 'not in the name list after EINCM_ABI_VERSION'
+    assert [n for n, _, _ in L.SIGNATURES].count(NAME) == 1
+    res, a = {n: (r, a) for n, r, a in L.SIGNATURES}[NAME]
+    assert res is C.c_int and a == [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int,
+                                    C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    fn = getattr(built_lib, NAME)
+    assert fn.restype is C.c_int and list(fn.argtypes) == a
+    assert built_lib.eincm_abi_version() == 6
+    assert hasattr(C.CDLL(os.path.join(ROOT, 'edge-informed-contrast-maximization_amd', 'libeincm_hip.so')), NAME)
+    assert fn(None, None, None, None, None, 0, 0.0, 1.0, 1, 1, 0, None, 0, None, None, None) == L.ERR_ARG      # no context: refused without a GPU
+
+
+def test_kernels_live_in_their_own_header_and_the_rules_in_a_hip_free_one():
+    csrc = os.path.join(ROOT, 'edge-informed-contrast-maximization_amd', 'csrc')
+    rules = open(os.path.join(csrc, 'eincm_event_filter.h')).read()
+    includes = re.findall(r'#include\s+[<"]([^>"]+)[>"]', rules)
+    assert 'hip' not in ''.join(includes).lower() and 'eincm_event_support.h' in includes
+    for fn in ('ef_check_args', 'ef_class', 'ef_kept', 'ef_last_kept', 'ef_weight'):
+        assert re.search(r'\b' + fn + r'\(', rules), fn
+    for fn in ('es_event_fault', 'es_window', 'es_supported', 'es_no_event'):     # stated once, in the support filter's rules
+        assert not re.search(r'(EINCM_HD|inline)[^;{]*\b' + fn + r'\(', rules), fn
+    kern = open(os.path.join(csrc, 'eincm_event_filter.hip.h')).read()
+    for k in ('k_ef_keep', 'k_ef_scan_tiles', 'k_ef_scan', 'k_ef_support', 'k_ef_map'):
+        assert re.search(r'__global__[^;{]*\b' + k + r'\(', kern), k
+    for fn in ('ef_kept(', 'ef_class(', 'ef_last_kept(', 'ef_weight(', 'es_window(', 'es_supported('):
+        assert fn in kern, fn
+    assert int(re.search(r'constexpr int EF_SCAN_NT = (\d+);', kern).group(1)) * 4 == EF_SCAN_TILE
+    assert 'constexpr int EF_SCAN_TILE = EF_SCAN_NT * 4;' in kern and 'atomic' not in kern
+    api = open(os.path.join(csrc, 'eincm_api.hip')).read()
+    body = api.split('int eincm_event_filter(')[1].split('\n}\n')[0]
+    assert 'not_in_flight(c, "eincm_event_filter")' in body and 'OneShot op(c);' in body
+    assert 'c->es.' not in body                                          # the carried state is its own
+    for k in ('k_es_validate', 'k_es_hist', 'k_es_scan_tiles', 'k_es_scan', 'k_es_scatter', 'k_es_bounds', 'k_es_fill', 'k_ef_keep',
+              'k_ef_scan_tiles', 'k_ef_scan', 'k_ef_support', 'k_ef_map'):
+        assert re.search(r'op\.launch\(' + k + r'\b', body), k
+
+
+# ---- the refusals, with a stub in the library's place ---------------------------------------------------------------------------
+class NoGpu:
+    """Stands where the library is: any call through it fails the test."""
+    def __getattr__(self, name):
+        raise AssertionError(f'{name} was reached: a library call')
+
+
+def stub_engine(H=5, W=7):
+    eng = E.Engine.__new__(E.Engine)
+    eng._ctx, eng._lib = None, NoGpu()
+    eng.precision, eng.splat_window, eng.B, eng.R, eng.H, eng.W = 'fp32', 3, 0, 0, H, W
+    eng._io = {}
+    return eng
+
+
+def _ok(n=6):
+    return np.arange(n) % 7, np.arange(n) % 5, np.arange(n, dtype=np.float64)
+
+
+P = np.array([1, -1, 1, 1, -1, 0])
+
+
+def test_a_good_call_reaches_the_library():
+    reached = pytest.raises(AssertionError, match=NAME + ' was reached')
+    with reached:
+        stub_engine().event_filter(*_ok())
+    with reached:
+        stub_engine().event_filter(*_ok(), P, refractory=0.5, tau=0.0, radius=3, full_support=48, polarity=True,
+                                   pixel_mask=np.zeros((5, 7), bool), chunk=1, return_support=True)
+    with reached:
+        stub_engine().event_filter(*_ok(), P > 0, refractory=2, tau=1, radius=0, full_support=1)
+    with reached:
+        stub_engine().event_filter(*_ok(), P.astype(np.uint8), polarity=True)
+    with reached:
+        staging.event_filter_weights(dict(zip('xyt', _ok())), (5, 7), 0.5, 1.0, engine=stub_engine())
+    with reached:
+        staging.event_filter_weights(dict(zip('xytp', _ok() + (P,))), (5, 7), refractory=0.5, tau=1.0, polarity=True, engine=stub_engine())
+
+
+def _set(arr, at, v, dtype=None):
+    a = np.array(arr, dtype=dtype)
+    a[at] = v
+    return a
+
+
+X, Y, T = _ok()
+BAD_EVENTS = [
+    ('x-negative', (_set(X, 3, -1), Y, T), 'event 3'), ('x-at-W', (_set(X, 2, 7), Y, T), 'event 2'),
+    ('y-negative', (X, _set(Y, 0, -1), T), 'event 0'), ('y-at-H', (X, _set(Y, 5, 5), T), 'event 5'),
+    ('nan', (X, Y, _set(T, 4, np.nan)), 'event 4'), ('inf', (X, Y, _set(T, 1, np.inf)), 'event 1'),
+    ('minus-inf', (X, Y, _set(T, 0, -np.inf)), 'event 0'), ('order', (X, Y, _set(T, 3, 1.5)), 'event 3'),
+    ('the-first-of-two', (_set(X, 4, 99), Y, _set(T, 2, 0.0)), 'event 2'),
+]
+
+
+@pytest.mark.parametrize('name,args,match', BAD_EVENTS, ids=[b[0] for b in BAD_EVENTS])
+def test_bad_events_are_value_errors_with_the_first_index_before_any_library_call(name, args, match):
+    with pytest.raises(ValueError, match=match + r'\b'):
+        stub_engine().event_filter(*args, P, refractory=0.5, tau=1.0)
+    with pytest.raises(ValueError, match=match + r'\b'):
+        staging.event_filter_weights(dict(x=args[0], y=args[1], t=args[2], p=P), (5, 7), 0.5, 1.0)
+
+
+BAD_ARGS = [dict(refractory=-1.0), dict(refractory=-1e-300), dict(refractory=np.nan), dict(refractory=np.inf), dict(refractory='a'),
+            dict(refractory=None), dict(tau=-1.0), dict(tau=np.nan), dict(tau=np.inf), dict(tau='a'), dict(radius=-1), dict(radius=4),
+            dict(radius=1.0), dict(radius=True), dict(radius=0, full_support=2), dict(radius=0, full_support=0), dict(full_support=0),
+            dict(full_support=9), dict(radius=2, full_support=25), dict(radius=3, full_support=49), dict(full_support=1.0),
+            dict(polarity=1), dict(polarity='yes'), dict(chunk=0), dict(chunk=(1 << 30) + 1), dict(chunk=1.5),
+            dict(pixel_mask=np.zeros((7, 5), np.uint8)), dict(pixel_mask=np.zeros((5, 7)))]
+
+
+@pytest.mark.parametrize('kw', BAD_ARGS, ids=lambda kw: '-'.join(f'{k}={v if np.ndim(v) == 0 else np.shape(v)}' for k, v in kw.items()))
+def test_bad_arguments_are_value_errors_before_any_library_call(kw):
+    kw = dict(dict(refractory=0.5, tau=1.0), **kw)
+    with pytest.raises(ValueError):
+        stub_engine().event_filter(*_ok(), P, **kw)
+    with pytest.raises(ValueError):
+        staging.event_filter_weights(dict(zip('xytp', _ok() + (P,))), (5, 7), engine=stub_engine(), **kw)
+
+
+def test_bad_polarities_are_value_errors_before_any_library_call():
+    x, y, t = _ok()
+    for ps in (P.astype(np.float64), P.astype(str), P[:-1], P[:, None], np.array(1)):
+        with pytest.raises(ValueError, match='event p'):
+            stub_engine().event_filter(x, y, t, ps)
+        with pytest.raises(ValueError, match='event p'):
+            staging.event_filter_weights(dict(x=x, y=y, t=t, p=ps), (5, 7), engine=stub_engine())
+    with pytest.raises(ValueError, match='polarity=True'):
+        stub_engine().event_filter(x, y, t, polarity=True)
+    with pytest.raises(ValueError, match='polarity=True'):
+        staging.event_filter_weights(dict(x=x, y=y, t=t), (5, 7), polarity=True, engine=stub_engine())
+    # {0, 1}, {-1, +1} and booleans give one class array
+    for ps in (P, P > 0, (P > 0).astype(np.uint8), P.astype(np.int64) * 1000):
+        got = E.check_event_polarity(ps, 6, True)
+        assert got.dtype == np.int8 and got.tolist() == [1, 0, 1, 1, 0, 0]
+    assert E.check_event_polarity(None, 6, False) is None
+
+
+def test_bad_arrays_are_value_errors_before_any_library_call():
+    x, y, t = _ok()
+    for args in ((x[:-1], y, t), (x, y, t[:-1]), (x, y, t[:, None]), (x.astype(np.float64), y, t), (x, y, t.astype(str)),
+                 (x, y, t.astype(bool)), (x, y, _set(t.astype(np.int64), 5, (1 << 53) + 2))):
+        with pytest.raises(ValueError):
+            stub_engine().event_filter(*args)
+    with pytest.raises(ValueError, match='lack'):
+        staging.event_filter_weights(dict(x=x, y=y), (5, 7), engine=stub_engine())
+    with pytest.raises(ValueError, match='sensor_size'):
+        staging.event_filter_weights(dict(x=x, y=y, t=t), (7, 5), engine=stub_engine())
+
+
+def test_signatures_of_the_python_layer():
+    p = inspect.signature(event_filter).parameters
+    assert list(p) == ['self', 'xs', 'ys', 'ts', 'ps', 'refractory', 'tau', 'radius', 'full_support', 'polarity', 'pixel_mask', 'chunk',
+                       'return_support']
+    assert [p[k].default for k in list(p)[4:]] == [None, 0.0, 0.0, 1, 1, False, None, 1 << 22, False]
+    p = inspect.signature(event_filter_weights).parameters
+    assert list(p) == ['events', 'sensor_size', 'refractory', 'tau', 'radius', 'full_support', 'polarity', 'pixel_mask', 'chunk',
+                       'return_support', 'engine']
+    assert [p[k].default for k in list(p)[2:]] == [0.0, 0.0, 1, 1, False, None, 1 << 22, False, None]
+    assert 'event_filter' not in inspect.getsource(staging.stage_datasample)         # stage_datasample is not changed
+    # the operator beside it keeps its signatures
+    assert list(inspect.signature(E.Engine.event_support).parameters)[1:5] == ['xs', 'ys', 'ts', 'tau']
+
+
+# ---- the consequences of the contract, on the witness ------------------------------------------------------------------------------
+def _bytes(res):
+    return tuple(a.tobytes() for a in res)
+
+
+def _tail(name, n=200):
+    xs, ys, ts, ps, mask, s = EF.generated(name)
+    return xs[-n:], ys[-n:], ts[-n:], ps[-n:], mask, s
+
+
+@pytest.mark.parametrize('polarity', [False, True])
+@pytest.mark.parametrize('name', ['3x3-r3-k8', '5x7-r2-k3-ties', '5x7-r1-k4-mask', '5x7-r1-k1-tau0', '5x7-r0'])
+def test_witness_split_at_any_index_gives_the_unsplit_result(name, polarity):
+    xs, ys, ts, ps, mask, s = _tail(name)
+    n = len(xs)
+    a = (s['shape'], s['refractory'], s['tau'], s['radius'], s['full_support'], polarity, mask)
+    whole = EF.event_filter(xs, ys, ts, ps, *a)
+    assert 0 < whole[0].sum() < n
+    for cut in range(n + 1):
+        h = EF.event_filter(xs[:cut], ys[:cut], ts[:cut], ps[:cut], *a)
+        g = EF.event_filter(xs[cut:], ys[cut:], ts[cut:], ps[cut:], *a, state=h[3])
+        assert _bytes([np.concatenate([h[i], g[i]]) for i in range(3)] + [g[3]]) == _bytes(whole), cut
+
+
+@pytest.mark.parametrize('name', sorted(n for n, s in EF.GENERATED.items() if s['radius'] > 0))
+def test_witness_without_refractory_and_flag_is_the_support_filter(name):
+    xs, ys, ts, ps, mask, s = EF.generated(name)
+    keep, w, sup, st = EF.event_filter(xs, ys, ts, ps, s['shape'], 0.0, s['tau'], s['radius'], s['full_support'], False, mask)
+    w_es, sup_es, last = ES.support_filter(xs, ys, ts, s['shape'], s['tau'], s['radius'], s['full_support'], mask)
+    assert w.tobytes() == w_es.tobytes() and sup.tobytes() == sup_es.tobytes() and st.last_any.tobytes() == last.tobytes()
+    masked = np.zeros(len(xs), bool) if mask is None else mask[ys, xs] != 0
+    assert np.array_equal(keep != 0, ~masked)                             # rho = 0 keeps every unmasked event
+
+
+@pytest.mark.parametrize('name', ['5x7-r2-k5', '33x65-r2-k4-mask', '5x7-r1-k1-tau0'])
+def test_witness_constant_polarity_makes_the_flag_void(name):
+    xs, ys, ts, ps, mask, s = EF.generated(name)
+    a = (s['shape'], s['refractory'], s['tau'], s['radius'], s['full_support'])
+    for const in (np.ones_like(ps), -np.ones_like(ps), None):
+        off = EF.event_filter(xs, ys, ts, const, *a, False, mask)
+        if const is not None:
+            assert _bytes(EF.event_filter(xs, ys, ts, const, *a, True, mask)[:3]) == _bytes(off[:3])
+        assert _bytes(off[:3]) == _bytes(EF.event_filter(xs, ys, ts, ps, *a, False, mask)[:3])      # without the flag p is not read
+
+
+def test_witness_keep_depends_on_the_refractory_rule_alone():
+    xs, ys, ts, ps, mask, s = EF.generated('5x7-r1-k4-mask')
+    ref = EF.event_filter(xs, ys, ts, ps, s['shape'], s['refractory'], s['tau'], 1, 4, False, mask)[0]
+    for tau, r, k, pol in ((0.0, 1, 1, False), (7.0, 3, 48, True), (s['tau'], 0, 1, False), (s['tau'], 2, 24, True)):
+        assert EF.event_filter(xs, ys, ts, ps, s['shape'], s['refractory'], tau, r, k, pol, mask)[0].tobytes() == ref.tobytes()
+    assert EF.event_filter(xs, ys, ts, ps, s['shape'], 2 * s['refractory'], s['tau'], 1, 4, False, mask)[0].tobytes() != ref.tobytes()
+
+
+def test_witness_is_invariant_under_an_exact_translation_of_the_times():
+    xs, ys, ts, ps, mask, s = EF.generated('33x65-r2-k12')
+    ts = np.round(ts * 1024.0) / 1024.0                                      # multiples of 2^-10 below 2^20: adding 2^30 is exact
+    assert ts.max() < 2.0 ** 20
+    shifted = ts + 2.0 ** 30
+    assert np.array_equal(shifted - 2.0 ** 30, ts)
+    for pol in (False, True):
+        a = EF.event_filter(xs, ys, ts, ps, s['shape'], 0.25, 0.5, s['radius'], s['full_support'], pol)
+        b = EF.event_filter(xs, ys, shifted, ps, s['shape'], 0.25, 0.5, s['radius'], s['full_support'], pol)
+        assert _bytes(a[:3]) == _bytes(b[:3])
+        assert 0.0 < a[0].mean() < 1.0 and 0.0 < a[1].mean() < 1.0
+
+
+def test_witness_chattering_pixel_keeps_its_first_event_and_vouches_once():
+    # pixel a chatters faster than rho; its neighbour b fires late: only a's first event is kept, and it is too old to support b
+    n = 50
+    xs, ys, ts = np.array([2] * n + [3]), np.full(n + 1, 2), np.arange(n + 1) * 0.1
+    keep, w, sup, st = EF.event_filter(xs, ys, ts, None, (5, 7), 0.5, 1.0)
+    assert keep.tolist() == [1] + [0] * (n - 1) + [1] and sup[-1] == 0
+    assert st.last_any[2, 2] == ts[n - 1] and st.last_kept[0, 2, 2] == ts[0] and st.last_kept[1, 2, 2] == -np.inf
+    assert ES.support_filter(xs, ys, ts, (5, 7), 1.0)[1][-1] == 1           # the support filter lets the chatter vouch
+    # equal times on one pixel with rho > 0 drop the later index; t - prev == rho keeps
+    keep = EF.event_filter([1, 1, 1, 1], [1, 1, 1, 1], [1.0, 1.0, 1.5, 1.75], None, (3, 3), 0.5, 1.0)[0]
+    assert keep.tolist() == [1, 0, 1, 0]
+    # masked events are dropped but still happened: the next event of the pixel is measured from them... on a masked pixel that
+    # changes nothing it can show, so show the map
+    mask = np.zeros((3, 3), np.uint8)
+    mask[1, 1] = 1
+    keep, w, sup, st = EF.event_filter([1, 1], [1, 1], [1.0, 9.0], None, (3, 3), 0.5, 1.0, pixel_mask=mask)
+    assert not keep.any() and st.last_any[1, 1] == 9.0 and np.isneginf(st.last_kept).all()
+
+
+# ---- the conditions that keep the GPU tests honest --------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', sorted(EF.GENERATED))
+def test_every_generated_case_meets_the_conditions(name):
+    xs, ys, ts, ps, mask, s = EF.generated(name)
+    n = s['n']
+    assert len(xs) == len(ps) == n and np.all(np.diff(ts) >= 0) and np.isfinite(ts).all() and s['refractory'] > 0
+    assert set(np.unique(ps).tolist()) == {-1, 1}
+    keep, w, sup, _ = EF.run(name)
+    kept = keep != 0
+    masked = np.zeros(n, bool) if mask is None else mask[ys, xs] != 0
+    assert (~kept & ~masked).mean() >= 0.25, 'dropped by the refractory rule'
+    if s['radius'] == 0:
+        assert kept.mean() >= 0.25 and np.array_equal(w, kept.astype(np.float32)) and not sup.any()
+        return
+    assert (kept & (w == 0)).mean() >= 0.20, 'kept with weight 0'
+    assert (kept & (w > 0)).mean() >= 0.08, 'kept with weight > 0'
+    if s['full_support'] > 1:
+        assert ((w > 0) & (w < 1)).mean() >= 0.05, 'strictly between 0 and 1'
+    else:
+        assert (w == 1).mean() >= 0.05, 'at weight 1'
+    keep_p, _, sup_p, _ = EF.run(name, polarity=True)
+    assert keep_p.tobytes() == keep.tobytes()
+    assert (sup_p != sup).mean() >= 0.03, 'support with the polarity flag differs from without it'
+    sup_all = EF.run(name, kept_only=False)[2]
+    assert (sup_all != sup).mean() >= 0.02, 'support differs from a filter whose last_kept maps every unmasked event updates'
+
+
+def test_generated_cases_cover_the_shapes_and_parameters():
+    specs = list(EF.GENERATED.values())
+    assert {s['shape'] for s in specs} == {(3, 3), (5, 7), (33, 65), (260, 346)}
+    assert {s['radius'] for s in specs} == {0, 1, 2, 3} and [s['shape'] for s in specs if s['radius'] == 0] == [(5, 7)]
+    for r in (1, 2, 3):
+        ks = {s['full_support'] for s in specs if s['radius'] == r}
+        assert 1 in ks or r > 1
+        assert ES.max_support(r) in ks and any(1 < k < ES.max_support(r) for k in ks), (r, ks)
+    assert any(s['mask'] is not None for s in specs) and any(s['tau'] == 0.0 for s in specs) and any(s['tie_run'] > 64 for s in specs)
+
+
+def test_long_chatter_and_two_pixel_streams_say_what_their_tests_need():
+    nb = 3 * EF_SCAN_TILE + 5
+    xs, ys, ts, ps, burst, gap = EF.long_chatter_stream(nb)
+    assert gap < burst and len(xs) == nb + 1
+    for pol in (False, True):
+        keep, _, sup, _ = EF.event_filter(xs, ys, ts, ps, (3, 3), 1.0, 2.0 * burst, polarity=pol)
+        assert keep.sum() == 2 and keep[0] and keep[-1]
+        assert sup[-1] == (1 if not pol or (ps[0] > 0) == (ps[-1] > 0) else 0)
+        assert EF.event_filter(xs, ys, ts, ps, (3, 3), 1.0, 2.0 * gap, polarity=pol)[2][-1] == 0
+    assert EF.event_filter(xs, ys, ts, ps, (3, 3), 1.0, 2.0 * gap, kept_only=False)[2][-1] == 1
+    xs, ys, ts, ps = EF.two_pixel_stream(4000)
+    keep, w, sup, _ = EF.event_filter(xs, ys, ts, ps, (3, 3), 1.0, 1.0)
+    assert 0.2 <= keep.mean() <= 0.8 and (w[keep != 0] == 0).any() and (w == 1).mean() >= 0.2
+    assert set(zip(ys.tolist(), xs.tolist())) == {(1, 0), (1, 1)}

@@ -1,0 +1,366 @@
+"""The refractory and polarity-aware event filter on the GPU against the sequential numpy witness
+tests/_event_filter_witness.py, byte for byte, keep, weights and support alike: the arithmetic is integer maxima and counts, exact
+compares and one correctly rounded division, so no tolerance applies.  tests/test_event_filter_interface.py asserts on the CPU that
+every generated case has dropped events, kept ones without and with support, and events whose support the polarity flag and the
+kept-only rule change, so a kernel that ignores any of them fails here.  Every test runs under its own time limit."""
+import importlib
+import signal
+
+import numpy as np
+import pytest
+
+import _event_filter_witness as EF
+
+pytestmark = pytest.mark.gpu
+
+pkg = 'edge-informed-contrast-maximization_amd'
+E = importlib.import_module(pkg + '.engine')
+L = importlib.import_module(pkg + '._lib')
+edges_mod = importlib.import_module(pkg + '.edges')
+staging = importlib.import_module(pkg + '.staging')
+synth = importlib.import_module(pkg + '.synth')
+
+TIME_LIMIT_S = 60
+EF_SCAN_TILE = 4096        # csrc/eincm_event_filter.hip.h (tests/test_event_filter_interface.py reads it there)
+_engines = {}
+
+
+def _eng(shape, precision='fp32'):
+    key = (tuple(shape), precision)
+    if key not in _engines:
+        _engines[key] = E.Engine(tuple(shape), max_events_total=1, max_refs=1, precision=precision)
+    return _engines[key]
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _close_engines(built_lib):
+    yield
+    for e in _engines.values():
+        e.close()
+    _engines.clear()
+    edges_mod.clear_engines()
+
+
+@pytest.fixture(autouse=True)
+def _time_limit():
+    def stop(signum, frame):
+        raise TimeoutError(f'test exceeded {TIME_LIMIT_S} s')
+    old = signal.signal(signal.SIGALRM, stop)
+    signal.alarm(TIME_LIMIT_S)
+    yield
+    signal.alarm(0)
+    signal.signal(signal.SIGALRM, old)
+
+
+_witness = {}
+
+
+def _case(name, polarity=False):
+    """(xs, ys, ts, ps, mask, spec, witness keep, weights, support) of a generated case, computed once"""
+    if (name, polarity) not in _witness:
+        xs, ys, ts, ps, mask, s = EF.generated(name)
+        k, w, sup, _ = EF.event_filter(xs, ys, ts, ps, s['shape'], s['refractory'], s['tau'], s['radius'], s['full_support'], polarity, mask)
+        for a in (xs, ys, ts, ps, k, w, sup):
+            a.setflags(write=False)
+        _witness[(name, polarity)] = (xs, ys, ts, ps, mask, s, k, w, sup)
+    return _witness[(name, polarity)]
+
+
+def _equal(got, k, w, sup):
+    gk, gw, gs = got
+    assert gk.dtype == np.bool_ and gw.dtype == np.float32 and gs.dtype == np.uint8
+    assert gk.shape == k.shape and gw.shape == w.shape and gs.shape == sup.shape
+    bad = np.nonzero(gk.view(np.uint8) != k)[0]
+    assert bad.size == 0, f'{bad.size} of {len(k)} keeps differ, first at {bad[0]}: {gk[bad[0]]} for {k[bad[0]]}'
+    bad = np.nonzero(gs != sup)[0]
+    assert bad.size == 0, f'{bad.size} of {len(sup)} supports differ, first at {bad[0]}: {gs[bad[0]]} for {sup[bad[0]]}'
+    assert gk.tobytes() == k.tobytes() and gw.tobytes() == w.tobytes()
+
+
+def _run(eng, xs, ys, ts, ps, s, polarity=False, mask=None, **kw):
+    return eng.event_filter(xs, ys, ts, ps, refractory=s['refractory'], tau=s['tau'], radius=s['radius'], full_support=s['full_support'],
+                            polarity=polarity, pixel_mask=mask, return_support=True, **kw)
+
+
+def _check(eng, xs, ys, ts, ps, shape, rho, tau, radius=1, k=1, polarity=False, mask=None, **kw):
+    ref = EF.event_filter(xs, ys, ts, ps, shape, rho, tau, radius, k, polarity, mask)
+    got = eng.event_filter(xs, ys, ts, ps, refractory=rho, tau=tau, radius=radius, full_support=k, polarity=polarity, pixel_mask=mask,
+                           return_support=True, **kw)
+    _equal(got, *ref[:3])
+    return ref
+
+
+# ---- every generated case, the polarity flag off and on; a call repeated ------------------------------------------------------------
+@pytest.mark.parametrize('polarity', [False, True], ids=['any-polarity', 'same-polarity'])
+@pytest.mark.parametrize('name', sorted(EF.GENERATED))
+def test_generated_case_equals_the_witness_and_repeats(name, polarity):
+    xs, ys, ts, ps, mask, s, k, w, sup = _case(name, polarity)
+    eng = _eng(s['shape'])
+    first = _run(eng, xs, ys, ts, ps, s, polarity, mask)
+    _equal(first, k, w, sup)
+    again = _run(eng, xs, ys, ts, ps, s, polarity, mask)
+    assert all(a.tobytes() == b.tobytes() for a, b in zip(again, first))
+    pair = eng.event_filter(xs, ys, ts, ps, refractory=s['refractory'], tau=s['tau'], radius=s['radius'], full_support=s['full_support'],
+                            polarity=polarity, pixel_mask=mask)
+    assert len(pair) == 2 and pair[0].tobytes() == k.tobytes() and pair[1].tobytes() == w.tobytes()
+    if not polarity:                                          # without the flag p is not needed, and not read
+        _equal(_run(eng, xs, ys, ts, None, s, False, mask), k, w, sup)
+
+
+@pytest.mark.parametrize('name', ['5x7-r2-k5', '33x65-r3-kmax', '33x65-r2-k4-mask', '5x7-r1-k1-tau0', '5x7-r0'])
+def test_fp64_context_gives_the_same_bytes(name):
+    xs, ys, ts, ps, mask, s, k, w, sup = _case(name, True)
+    _equal(_run(_eng(s['shape'], 'fp64'), xs, ys, ts, ps, s, True, mask), k, w, sup)
+
+
+# ---- n = 0, 1 and both sides of the wave, the workgroup, the sort's block, the scan's tile and twice it -------------------------------
+def test_no_event_and_one_event():
+    eng = _eng((5, 7))
+    k, w, sup = eng.event_filter(np.zeros(0, np.int16), np.zeros(0, np.int16), np.zeros(0), return_support=True)
+    assert (k.shape, k.dtype, w.shape, w.dtype, sup.shape, sup.dtype) == ((0,), np.bool_, (0,), np.float32, (0,), np.uint8)
+    for x, y in ((0, 0), (6, 4), (3, 2)):
+        k, w, sup = eng.event_filter([x], [y], [3.5], [1], refractory=9.0, tau=1.0, radius=3, full_support=7, polarity=True, return_support=True)
+        assert k.tolist() == [True] and w.tolist() == [0.0] and sup.tolist() == [0]
+        k, w = eng.event_filter([x], [y], [3.5], refractory=9.0, radius=0)
+        assert k.tolist() == [True] and w.tolist() == [1.0]
+
+
+_sizes = {}
+
+
+def _sized(n):
+    """The first n events of one long stream on 5x7 that begins with its first chatter phase, so that the smallest sizes have
+    dropped events too"""
+    if not _sizes:
+        total = 2 * EF_SCAN_TILE + 2 + 1200
+        xs, ys, ts, ps = (a[EF.first_chatter(total):] for a in EF.make_stream(77, (5, 7), total, 1, 2, 1.0, 0.25))
+        assert len(xs) > 2 * EF_SCAN_TILE
+        _sizes['stream'] = (xs, ys, ts, ps)
+        _sizes['ref'] = {pol: EF.event_filter(xs, ys, ts, ps, (5, 7), 0.25, 1.0, 1, 2, pol) for pol in (False, True)}
+    xs, ys, ts, ps = _sizes['stream']
+    return (xs[:n], ys[:n], ts[:n], ps[:n]), {pol: tuple(a[:n] for a in r[:3]) for pol, r in _sizes['ref'].items()}
+
+
+@pytest.mark.parametrize('n', [2, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, EF_SCAN_TILE - 1, EF_SCAN_TILE,
+                               EF_SCAN_TILE + 1, 2 * EF_SCAN_TILE - 1, 2 * EF_SCAN_TILE, 2 * EF_SCAN_TILE + 1])
+def test_sizes_around_the_kernels_steps(n):
+    (xs, ys, ts, ps), ref = _sized(n)                        # (a prefix of a stream has the whole stream's results for its events)
+    for pol in (False, True):
+        got = _eng((5, 7)).event_filter(xs, ys, ts, ps, refractory=0.25, tau=1.0, radius=1, full_support=2, polarity=pol, return_support=True)
+        _equal(got, *ref[pol])
+    k, w, _ = ref[False]
+    assert n < 63 or (0.1 < k.mean() < 0.9 and (w[k != 0] == 0).any())
+    assert n < 1500 or (w > 0).any()
+
+
+# ---- the scan across tile sums: a burst of more than three tiles on one pixel, all dropped but the first ------------------------------
+@pytest.mark.parametrize('polarity', [False, True])
+def test_long_chatter_is_one_kept_event_however_long_the_burst(polarity):
+    nb = 3 * EF_SCAN_TILE + 5
+    xs, ys, ts, ps, burst, gap = EF.long_chatter_stream(nb)
+    ps = ps.copy()
+    ps[-1] = ps[0]                                           # the neighbour has the class of the burst's one kept event
+    eng = _eng((3, 3))
+    ref = _check(eng, xs, ys, ts, ps, (3, 3), 1.0, 2.0 * burst, polarity=polarity)
+    assert ref[0].sum() == 2 and ref[2][-1] == 1             # tau longer than the burst: the first event, three tiles back, supports
+    ref = _check(eng, xs, ys, ts, ps, (3, 3), 1.0, 2.0 * gap, polarity=polarity)
+    assert ref[2][-1] == 0                                   # tau shorter than the burst, longer than the last gap: nobody kept supports
+    # ... in chunks that cut the burst, the kept event is carried by the map while the run's own events are all dropped
+    _check(eng, xs, ys, ts, ps, (3, 3), 1.0, 2.0 * burst, polarity=polarity, chunk=EF_SCAN_TILE + 3)
+    _check(eng, xs, ys, ts, ps, (3, 3), 1.0, 2.0 * gap, polarity=polarity, chunk=EF_SCAN_TILE + 3)
+
+
+def test_two_hot_pixels_with_2e5_events_finish_in_normal_time():
+    """Alternating on two adjacent pixels, ~10^5 positions in each of two runs, phases faster and slower than the refractory period:
+    only a search and a scan that are not linear in the run finish inside the time limit of a test."""
+    xs, ys, ts, ps = EF.two_pixel_stream(200000)
+    for pol in (False, True):
+        k, w, sup, _ = _check(_eng((3, 3)), xs, ys, ts, ps, (3, 3), 1.0, 1.0, polarity=pol)
+        assert 0.2 <= k.mean() <= 0.8 and (w == 1).mean() >= 0.1 and (w[k != 0] == 0).any()
+
+
+# ---- chunking and the carried state ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['5x7-r2-k3-ties', '33x65-r2-k4-mask', '5x7-r0'])
+def test_result_does_not_depend_on_chunk(name):
+    xs, ys, ts, ps, mask, s, k, w, sup = _case(name, True)
+    n = min(1500, len(xs))
+    xs, ys, ts, ps = xs[:n], ys[:n], ts[:n], ps[:n]
+    for chunk in (1, 7, 1024, 1025, n):
+        _equal(_run(_eng(s['shape']), xs, ys, ts, ps, s, True, mask, chunk=chunk), k[:n], w[:n], sup[:n])
+
+
+def _raw(eng, xs, ys, ts, ps, rho, tau, radius, k, flags, mask, reset, keep, w, sup):
+    xs, ys, ts = np.ascontiguousarray(xs, np.int16), np.ascontiguousarray(ys, np.int16), np.ascontiguousarray(ts, np.float64)
+    ps = None if ps is None else np.ascontiguousarray(ps, np.int8)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    return eng._lib.eincm_event_filter(eng._ctx, ptr(xs), ptr(ys), ptr(ts), ptr(ps), len(xs), rho, tau, radius, k, flags, ptr(mask), reset,
+                                       ptr(keep), ptr(w), ptr(sup))
+
+
+def _outputs(n):
+    return np.empty(n, np.uint8), np.empty(n, np.float32), np.empty(n, np.uint8)
+
+
+def test_split_inside_a_chatter_phase_carries_an_old_last_kept_beside_a_young_last_any():
+    xs, ys, ts, ps, mask, s, k, w, sup = _case('5x7-r2-k5', True)
+    n = len(xs)                                              # one cycle: the chatter phases are its last 30 %
+    assert n == 900
+    state = EF.event_filter(xs[:700], ys[:700], ts[:700], ps[:700], (5, 7), s['refractory'], s['tau'], 2, 5, True)[3]
+    young = np.isfinite(state.last_any) & (state.last_any - state.last_kept.max(axis=0) > 2 * s['refractory'])
+    assert young.any()                                       # a pixel whose last event is much younger than its last kept one
+    eng = _eng((5, 7))
+    gk, gw, gs = _outputs(n)
+    a = (s['refractory'], s['tau'], 2, 5, 1, None)
+    for i0, i1 in ((0, 700), (700, 701), (701, n)):
+        assert _raw(eng, xs[i0:i1], ys[i0:i1], ts[i0:i1], ps[i0:i1], *a, int(i0 == 0), gk[i0:i1], gw[i0:i1], gs[i0:i1]) == L.OK
+    _equal((gk.view(np.bool_), gw, gs), k, w, sup)
+
+
+def test_reset_in_mid_stream_forgets_the_maps_and_the_carried_time():
+    xs, ys, ts, ps, mask, s, k, w, sup = _case('5x7-r2-k5', True)
+    eng, n, cut = _eng((5, 7)), len(xs), 650
+    a = (s['refractory'], s['tau'], 2, 5, 1, None)
+    gk, gw, gs = _outputs(n)
+    assert _raw(eng, xs[:cut], ys[:cut], ts[:cut], ps[:cut], *a, 1, gk[:cut], gw[:cut], gs[:cut]) == L.OK
+    assert _raw(eng, xs[cut:], ys[cut:], ts[cut:], ps[cut:], *a, 1, gk[cut:], gw[cut:], gs[cut:]) == L.OK       # a reset in mid-stream
+    tail = EF.event_filter(xs[cut:], ys[cut:], ts[cut:], ps[cut:], (5, 7), *a[:4], True)
+    _equal((gk[cut:].view(np.bool_), gw[cut:], gs[cut:]), *tail[:3])
+    assert gk[cut:].tobytes() != k[cut:].tobytes() or gs[cut:].tobytes() != sup[cut:].tobytes()                 # ... which the stream notices
+    # without a reset the stream's start is older than the carried time: refused, naming event 0, outputs untouched
+    gw[:] = -1.0
+    assert _raw(eng, xs, ys, ts, ps, *a, 0, gk, gw, gs) == L.ERR_ARG
+    assert 'event 0' in eng._lib.eincm_last_error(eng._ctx).decode() and np.all(gw == -1.0)
+    assert _raw(eng, xs, ys, ts, ps, *a, 1, gk, gw, None) == L.OK                                               # (support may be NULL)
+    assert gk.tobytes() == k.tobytes() and gw.tobytes() == w.tobytes()
+
+
+def test_refused_chunk_in_mid_stream_leaves_the_state_and_the_good_rest_completes_the_unsplit_bytes():
+    xs, ys, ts, ps, mask, s, k, w, sup = _case('5x7-r1-k1', True)
+    eng, n = _eng((5, 7)), len(xs)
+    a = (s['refractory'], s['tau'], 1, 1, 1, None)
+    gk, gw, gs = _outputs(n)
+    half = n // 2
+    assert _raw(eng, xs[:half], ys[:half], ts[:half], ps[:half], *a, 1, gk[:half], gw[:half], gs[:half]) == L.OK
+    for which, at, value in ((0, 301, 7), (0, 5, -1), (1, 64, 5), (2, 200, np.nan), (2, 255, np.inf), (2, 300, ts[half + 299] - 1e-9)):
+        b = [xs[half:].copy(), ys[half:].copy(), ts[half:].copy()]
+        b[which][at] = value
+        b[0][340] = 99                                                   # a later offender never wins
+        out_k, out_w = np.full(n - half, 7, np.uint8), np.full(n - half, -1.0, np.float32)
+        assert _raw(eng, *b, ps[half:], *a, 0, out_k, out_w, None) == L.ERR_ARG
+        assert f'event {at}:' in eng._lib.eincm_last_error(eng._ctx).decode() and np.all(out_w == -1.0) and np.all(out_k == 7)
+    rest = (xs[half:], ys[half:], ts[half:], ps[half:])
+    for bad in (dict(rho=-1.0), dict(rho=np.nan), dict(tau=-1.0), dict(tau=np.inf), dict(radius=-1), dict(radius=4), dict(k=0), dict(k=9),
+                dict(radius=0, k=2), dict(flags=2), dict(flags=3)):
+        kw = dict(dict(rho=0.25, tau=1.0, radius=1, k=1, flags=1), **bad)
+        assert _raw(eng, *rest, kw['rho'], kw['tau'], kw['radius'], kw['k'], kw['flags'], None, 0, gk[half:], gw[half:], None) == L.ERR_ARG
+    assert _raw(eng, *rest[:3], None, *a, 0, gk[half:], gw[half:], None) == L.ERR_ARG                           # the flag without p
+    assert 'EINCM_EF_POLARITY' in eng._lib.eincm_last_error(eng._ctx).decode()
+    assert _raw(eng, *rest, *a, 0, None, gw[half:], None) == L.ERR_ARG and _raw(eng, *rest, *a, 0, gk[half:], None, None) == L.ERR_ARG
+    assert eng._lib.eincm_event_filter(eng._ctx, None, None, None, None, -1, 0.0, 1.0, 1, 1, 0, None, 0, None, None, None) == L.ERR_ARG
+    # the carried state is what the first half left: the second half completes the unsplit result
+    assert _raw(eng, *rest, *a, 0, gk[half:], gw[half:], gs[half:]) == L.OK
+    _equal((gk.view(np.bool_), gw, gs), k, w, sup)
+
+
+# ---- beside the event-support filter: the same bytes at rho = 0 without the flag, and two carried states that do not touch ------------
+@pytest.mark.parametrize('name', ['33x65-r2-k4-mask', '5x7-r1-k1-tau0', '260x346-r1-k3'])
+def test_without_refractory_and_flag_the_bytes_are_event_supports(name):
+    xs, ys, ts, ps, mask, s, _, _, _ = _case(name)
+    eng = _eng(s['shape'])
+    kw = dict(radius=s['radius'], full_support=s['full_support'], pixel_mask=mask, return_support=True)
+    half = len(xs) // 2
+    w_es, sup_es = eng.event_support(xs, ys, ts, s['tau'], **kw)
+    k, w, sup = eng.event_filter(xs, ys, ts, ps, refractory=0.0, tau=s['tau'], **kw)
+    assert w.tobytes() == w_es.tobytes() and sup.tobytes() == sup_es.tobytes()
+    masked = np.zeros(len(xs), bool) if mask is None else mask[ys, xs] != 0
+    assert np.array_equal(k, ~masked)
+    # each operator's second half follows its own first half, whatever the other did in between
+    raw_s = lambda i0, i1, reset, w_, s_: eng._lib.eincm_event_support(
+        eng._ctx, xs[i0:i1].ctypes.data, ys[i0:i1].ctypes.data, ts[i0:i1].ctypes.data, i1 - i0, s['tau'], s['radius'], s['full_support'],
+        None if mask is None else mask.ctypes.data, reset, w_.ctypes.data, s_.ctypes.data)
+    n = len(xs)
+    ws, ss = np.empty(n, np.float32), np.empty(n, np.uint8)
+    gk, gw, gs = _outputs(n)
+    a = (s['refractory'], s['tau'], s['radius'], s['full_support'], 0, mask)
+    assert raw_s(0, half, 1, ws[:half], ss[:half]) == L.OK
+    assert _raw(eng, xs[:half], ys[:half], ts[:half], ps[:half], *a, 1, gk[:half], gw[:half], gs[:half]) == L.OK
+    assert raw_s(half, n, 0, ws[half:], ss[half:]) == L.OK
+    assert _raw(eng, xs[half:], ys[half:], ts[half:], ps[half:], *a, 0, gk[half:], gw[half:], gs[half:]) == L.OK
+    assert ws.tobytes() == w_es.tobytes() and ss.tobytes() == sup_es.tobytes()
+    _equal((gk.view(np.bool_), gw, gs), *_case(name)[6:])
+    again = eng.event_support(xs, ys, ts, s['tau'], **kw)
+    assert again[0].tobytes() == w_es.tobytes() and again[1].tobytes() == sup_es.tobytes()
+
+
+# ---- masks ---------------------------------------------------------------------------------------------------------------------------
+def test_masked_pixel_is_dropped_gives_no_support_and_still_ages():
+    n = 300
+    i = np.arange(n)
+    xs, ys, ts = np.where(i % 2 == 0, 30, 31).astype(np.int16), np.full(n, 16, np.int16), i * 0.125    # across the 32-pixel tile edge
+    ps = (i % 4 < 2).astype(np.int8)
+    eng = _eng((33, 65))
+    k, w = eng.event_filter(xs, ys, ts, refractory=0.25, tau=1.0)       # each pixel fires every 0.25: t - prev == rho keeps
+    assert k.all() and w[0] == 0 and np.all(w[1:] == 1)
+    mask = np.zeros((33, 65), np.uint8)
+    mask[16, 31] = 255
+    ref = _check(eng, xs, ys, ts, ps, (33, 65), 0.25, 1.0, polarity=True, mask=mask)
+    assert ref[0].tolist() == [1, 0] * (n // 2) and not ref[1].any() and not ref[2].any()
+
+
+# ---- beside the evaluation ---------------------------------------------------------------------------------------------------------------
+def _window(n=3000, shape=(33, 65)):
+    return synth.make_window(4, shape, n, 2, flow='smooth', flow_mag=3.0)
+
+
+def test_operator_between_two_evaluations_leaves_value_and_gradient_bits():
+    shape = (33, 65)
+    win = _window()
+    xs, ys, ts, ps, mask, s, k, w, sup = _case('33x65-r2-k12', True)
+    theta = synth.theta_near_truth(1, win, (4, 4))
+    p = E.make_params(20.0, 35.0, 2.5e-4, 0.0, 0)
+    with E.Engine(shape, len(win['xs']), max_refs=2) as eng:
+        eng.set_window(win['xs'], win['ys'], win['ts'], win['edges'], win['edge_ts'])
+        v0, g0, _ = eng.loss_grad(theta, p)
+        _equal(_run(eng, xs, ys, ts, ps, s, True), k, w, sup)
+        v1, g1, _ = eng.loss_grad(theta, p)
+        assert v0.tobytes() == v1.tobytes() and g0.tobytes() == g1.tobytes()
+        # an evaluation in flight: refused as the other one-shot operators refuse it, and the evaluation is untouched
+        eng.loss_grad_async(theta, p)
+        with pytest.raises(E.EincmError, match='in flight') as ei:
+            _run(eng, xs, ys, ts, ps, s, True)
+        assert ei.value.code == L.ERR_STATE
+        v2, g2, _ = eng.loss_grad_wait()
+        assert v0.tobytes() == v2.tobytes() and g0.tobytes() == g2.tobytes()
+        _equal(_run(eng, xs, ys, ts, ps, s, True), k, w, sup)
+
+
+def test_weights_end_to_end_through_staging_into_one_loss_grad():
+    shape = (33, 65)
+    win = _window()
+    n = len(win['xs'])
+    raw_t = 1.0e6 + win['ts'] * 5.0e4                                      # raw times in "microseconds"; tau and rho in their unit
+    order = np.argsort(raw_t, kind='stable')
+    rng = np.random.default_rng(5)
+    ev = dict(x=win['xs'][order], y=win['ys'][order], t=raw_t[order], p=rng.integers(0, 2, n).astype(np.int8))
+    mask = staging.hot_pixel_mask(ev['x'], ev['y'], shape, 6)
+    rho, tau, r, k = 1500.0, 6000.0, 2, 3
+    k_ref, w_ref, sup_ref, _ = EF.event_filter(ev['x'], ev['y'], ev['t'], ev['p'], shape, rho, tau, r, k, True, mask)
+    assert 0.05 <= 1 - k_ref.mean() and (w_ref == 0).mean() >= 0.2 and (w_ref > 0).mean() >= 0.2
+    got = staging.event_filter_weights(ev, shape, rho, tau, radius=r, full_support=k, polarity=True, pixel_mask=mask, return_support=True)
+    _equal(got, k_ref, w_ref, sup_ref)
+    w_gpu = got[1]
+    ds = dict(events=ev, image_ts=np.array([raw_t.min(), raw_t.max()]), eval_ts=(raw_t.min(), raw_t.max()))
+    theta = synth.theta_near_truth(1, win, (1, 1))
+    p = E.make_params(20.0, 35.0, 0.0, 0.0, 0)
+    res = []
+    with E.Engine(shape, n, max_refs=2) as eng:
+        for wts in (w_gpu, w_ref):
+            tup = staging.stage_datasample(ds, edges=win['edges'], event_weights=wts)
+            eng.set_windows([tup])
+            assert eng.weighted
+            v, g, _ = eng.loss_grad(theta, p)
+            res.append((v.tobytes(), g.tobytes()))
+        eng.set_windows([staging.stage_datasample(ds, edges=win['edges'])])
+        v_plain, _, _ = eng.loss_grad(theta, p)
+    assert res[0] == res[1] and np.isfinite(np.frombuffer(res[0][0])).all()
+    assert v_plain.tobytes() != res[0][0]                                  # the weights did reach the loss
