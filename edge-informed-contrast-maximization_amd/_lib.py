@@ -178,6 +178,8 @@ SIGNATURES = [
     # the refractory and polarity-aware event filter (raw addresses, as above)
     ('eincm_event_filter', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_int,
                                      C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # per-event scores: an image stack sampled at the warped events (raw addresses, as above)
+    ('eincm_event_scores', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # flow errors of a batch of thetas against staged ground truth
     ('eincm_flow_eval_stage', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('eincm_flow_errors', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FlowErrorOut), C.c_void_p]),

@@ -38,6 +38,8 @@
 #include "eincm_motion.hip.h"
 #include "eincm_event_support.hip.h"
 #include "eincm_event_filter.hip.h"
+#include "eincm_event_scores.h"
+#include "eincm_event_scores.hip.h"
 
 using namespace eincm;
 
@@ -271,6 +273,7 @@ struct eincm_ctx : PlanCtx {
 
     // last eval bookkeeping
     bool have_eval = false;
+    unsigned long long eval_wmask = ~0ull;   // the window mask the last evaluation was begun with (g.wmask is rewritten by ensure_theta_image)
     bool G_valid = false;          // d_G holds dL/dIWE of the last evaluation (eincm_get_count_images borrows the buffer)
     int last_nparts = 0;           // how many StatParts per image the last evaluation wrote (k_stats vs k_stats_stream)
     Flight fl;                     // the evaluation in flight
@@ -866,6 +869,7 @@ int eval_begin(eincm_ctx* c, const double* theta_host, int h, int w, const eincm
         unsigned long long m = ~0ull;
         if (active) { m = 0ull; for (int b = 0; b < c->g.B && b < 64; ++b) if (active[b]) m |= 1ull << b; }
         c->g.wmask = m;
+        c->eval_wmask = m;
     }
     const Geom& g = c->g;
     const size_t img = (size_t)g.H * g.W;
@@ -2094,6 +2098,50 @@ int eincm_get_warped_events(eincm_ctx* c, int window, double* warped_xs, double*
                         c->d_Theta, c->d_edge_ts, dx, dy));
     HIPCHK(c, op.down(warped_xs, dx, cells * sizeof(double)));    // (host memory: the caller's, both)
     HIPCHK(c, op.down(warped_ys, dy, cells * sizeof(double)));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+
+// Per-event scores of the whole staged batch under the last evaluation's Theta (eincm_event_scores.hip.h): the
+// checks and the layout are eincm_event_scores.h's.  images == NULL reads the IWE stack where the evaluation left it.
+int eincm_event_scores(eincm_ctx* c, const float* images, const double* ref_weights, float* scores, float* selfs) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    bool masked = false;
+    for (int b = 0; c->staged && b < g.B && b < 64; ++b) masked = masked || !((c->eval_wmask >> b) & 1ull);
+    const ScState st{!c->fl.idle(), scores != nullptr, c->staged, c->have_eval, c->fp64, c->splat_size,
+                     c->sharded_staging || c->constants_pending, images != nullptr, masked};
+    if (const ScFault f = sc_check(st, ref_weights, g.R)) return fail(c, sc_code(f), "eincm_event_scores: %s", sc_why(f));
+    { const int rc = ensure_theta_image(c); if (rc) return rc; }
+    const int B = g.B, R = g.R;
+    const bool combined = ref_weights != nullptr;
+    const int64_t* ne = c->win_events.data();
+    const int64_t n_events = sc_total(ne, B, 1, true), n_out = sc_total(ne, B, R, combined);
+    if (n_events == 0) return EINCM_OK;
+    const size_t stack = (size_t)B * R * g.H * g.W;
+    OneShot op(c);
+    const auto d_off = op.piece<int64_t>((size_t)B + 1);
+    const auto d_img = op.piece<float>(stack, images != nullptr);
+    const auto d_rw = op.piece<float>((size_t)R, combined);
+    const auto d_s = op.piece<float>((size_t)n_out);
+    const auto d_q = op.piece<float>((size_t)n_out, selfs != nullptr);
+    int64_t* h_off = op.host_buf<int64_t>((size_t)B + 1);                // d_off goes up from here, d_rw from h_rw
+    float* h_rw = op.host_buf<float>((size_t)R);
+    int64_t n_max = 0;
+    for (int b = 0; b <= B; ++b) h_off[b] = sc_block_offset(ne, b, 1, true);
+    for (int b = 0; b < B; ++b) n_max = std::max(n_max, ne[b]);
+    for (int r = 0; combined && r < R; ++r) h_rw[r] = (float)ref_weights[r];
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)));
+    if (images) HIPCHK(c, op.up(d_img, images, stack * sizeof(float)));  // (host memory: the caller's, as scores and selfs)
+    if (combined) HIPCHK(c, op.up(d_rw, h_rw, (size_t)R * sizeof(float)));
+    const float* F = images ? (const float*)d_img : (const float*)c->d_iwe;
+    const dim3 grid((unsigned)((n_max + NT - 1) / NT), (unsigned)B);
+    HIPCHK(c, op.launch(k_event_scores, grid, dim3(NT), 0, g, d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F, d_rw,
+                        d_s, d_q));
+    HIPCHK(c, op.down(scores, d_s, (size_t)n_out * sizeof(float)));
+    if (selfs) HIPCHK(c, op.down(selfs, d_q, (size_t)n_out * sizeof(float)));
     HIPCHK(c, op.sync());
     return EINCM_OK;
 }

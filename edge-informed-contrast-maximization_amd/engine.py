@@ -587,6 +587,45 @@ def check_event_weights(weights, n):
     return np.ascontiguousarray(w, dtype=np.float32)
 
 
+def event_scores_layout(n_events, n_refs, combined):
+    """(offsets (B,), lengths (B,), total) of the windows' blocks in the ``scores`` / ``selfs`` arrays of eincm_event_scores, in floats
+    (csrc/eincm_event_scores.h: sc_block_offset, sc_block_len, sc_total, restated; tests/test_event_scores_interface.py compares the
+    two): (n_refs, n_events[b]) per window, or (n_events[b]) in the combined form, one block after the other."""
+    n = np.asarray(n_events, dtype=np.int64).reshape(-1)
+    lengths = n if combined else n * int(n_refs)
+    offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64) if n.size else np.zeros(0, np.int64)
+    return offsets, lengths.astype(np.int64), int(lengths.sum())
+
+
+def check_score_images(images, n_windows, n_refs, sensor_size):
+    """The caller's image stack of Engine.event_scores as contiguous float32 (B,R,H,W); (R,H,W) stands for it when B == 1.  None stays
+    None (the IWEs of the last evaluation).  Anything else is a ValueError, raised before any library call."""
+    if images is None:
+        return None
+    a = np.asarray(images)
+    if a.dtype.kind not in 'fiub':
+        raise ValueError(f'images must be numbers, got dtype {a.dtype}')
+    shape = (int(n_windows), int(n_refs), int(sensor_size[0]), int(sensor_size[1]))
+    if a.ndim == 3 and shape[0] == 1:
+        a = a[None]
+    if a.shape != shape:
+        raise ValueError(f'images must be {shape}' + (f' or {shape[1:]}' if shape[0] == 1 else '') + f', got {np.shape(images)}')
+    return np.ascontiguousarray(a, dtype=np.float32)
+
+
+def check_ref_weights(ref_weights, n_refs):
+    """The reference-time weights of Engine.event_scores as (R,) float64, finite; None stays None (the per-reference form)."""
+    if ref_weights is None:
+        return None
+    w = np.asarray(ref_weights)
+    if w.dtype.kind not in 'fiub' or w.shape != (int(n_refs),):
+        raise ValueError(f'ref_weights must be ({int(n_refs)},) numbers, got {w.dtype} {w.shape}')
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if not np.isfinite(w).all():
+        raise ValueError('ref_weights must be finite')
+    return w
+
+
 def event_weights_refusal(precision, splat_window, sharded=False):
     """Why a weighted batch cannot be staged on an engine of this precision and splat window (not built), or
     None.  csrc/eincm_api.hip (check_staging) refuses the same."""
@@ -775,12 +814,14 @@ class Engine:
                                                   ptrs(xs, one[0]), ptrs(ys, one[0]), ptrs(ts, one[1]), ptrs(edges, one[1]),
                                                   _dp(edge_ts), flags)
         self._weighted = False          # (a refused staging leaves nothing staged)
+        self._staged_weights = None
         self._check(rc)
         if B != self.B:
             self._io = {}
         self.B, self.R = B, R
         self.n_events = n
         self._weighted = weighted
+        self._staged_weights = ws       # what the windows were handed (None: ones), for event_scores(exclude_self=True)
 
     def set_window(self, xs, ys, ts, edges, edge_ts, weights=None):
         self.set_windows([(xs, ys, ts, edges, edge_ts, weights)])
@@ -1409,6 +1450,39 @@ class Engine:
         wy = np.empty((self.R, n), dtype=np.float64)
         self._check(self._lib.eincm_get_warped_events(self._ctx, int(window), _dp(wx), _dp(wy)))
         return wx, wy
+
+    def event_scores(self, images=None, ref_weights=None, exclude_self=False, theta=None, params=None):
+        """Per-event scores: an image stack sampled at every staged event's warped position under the last
+        evaluation's Theta, with the splat's nine tap weights - how much image lies under the event once it is warped.
+        images: (B,R,H,W), or (R,H,W) when B == 1; None takes the IWEs of the last evaluation (read on the device).
+        ref_weights: None gives one (R, n_b) float32 array per window; (R,) finite numbers give (n_b,), the weighted sum over the
+        reference times.  exclude_self: subtract the event's own share w_e * sum_d k(d)^2, the leave-one-out score against the IWE;
+        w is what ``set_windows`` was handed, or ones.  theta with params: ``loss_grad(theta, params, want_grad=False)`` runs first.
+        Returns the list of the B arrays, events in the order they were staged."""
+        if (theta is None) != (params is None):
+            raise ValueError('theta and params go together: both, or neither (the last evaluation)')
+        imgs = check_score_images(images, self.B, self.R, (self.H, self.W))
+        rw = check_ref_weights(ref_weights, self.R)
+        ws = getattr(self, '_staged_weights', None)
+        if exclude_self and (ws is None or len(ws) != self.B):
+            raise ValueError('exclude_self needs the weights the batch was staged with, and this engine does not hold them: stage with set_windows')
+        if theta is not None:
+            self.loss_grad(theta, params, want_grad=False)
+        off, length, total = event_scores_layout(self.n_events if self.B else [], self.R, rw is not None)
+        scores = np.empty(total, dtype=np.float32)
+        selfs = np.empty(total, dtype=np.float32) if exclude_self else None
+        self._check(self._lib.eincm_event_scores(self._ctx, None if imgs is None else imgs.ctypes.data, None if rw is None else rw.ctypes.data,
+                                                 scores.ctypes.data, None if selfs is None else selfs.ctypes.data))
+        out = []
+        for b in range(self.B):
+            n = int(self.n_events[b])
+            shape = (n,) if rw is not None else (self.R, n)
+            s = scores[off[b]:off[b] + length[b]].reshape(shape)
+            if exclude_self:
+                q = selfs[off[b]:off[b] + length[b]].reshape(shape)
+                s = s - q if ws[b] is None else s - ws[b] * q
+            out.append(np.ascontiguousarray(s, dtype=np.float32))
+        return out
 
     def scaled_theta(self):
         a = np.empty((self.B, self.H, self.W, 2), dtype=np.float64)

@@ -92,6 +92,47 @@ def evaluate_theta_array(theta_array, eval_xs, eval_ys, eval_ts, edges, edge_ts,
     return evals, lo
 
 
+SCORE_SOURCES = ('iwe', 'edges')
+
+
+def event_scores(theta, xs, ys, ts, edges, edge_ts, source='iwe', sensor_size=None, ref_weights=None, exclude_self=False,
+                 event_weights=None, method='bilinear', engine=None):
+    """Per-event scores of one window under ``theta`` (Engine.event_scores), in the argument shape of
+    evaluate_theta_array: how much image lies under each event once it is warped.  source 'iwe': the window's own IWEs at theta
+    (exclude_self=True gives the leave-one-out score); 'edges': the edge stack, min-max normalised per image (staging.normalize_edges)
+    - the edge map under each warped event.  theta: (h,w,2) of any pyramid size, scaled to the sensor with ``method``.
+    ref_weights None: (R, n) float32; (R,) numbers: (n,), combined over the reference times.  engine None: the cached engine of
+    losses.engine_for; an engine handed over is staged with the window and left open.  Arguments are checked before a GPU context is
+    asked for."""
+    from .engine import check_ref_weights, check_event_weights, make_params
+    if source not in SCORE_SOURCES:
+        raise ValueError(f'source {source!r}: one of {SCORE_SOURCES}')
+    if exclude_self and source != 'iwe':
+        raise ValueError("exclude_self subtracts the event's share of the IWE: it goes with source='iwe'")
+    e = np.asarray(edges, dtype=np.float64)
+    R = len(np.atleast_1d(edge_ts))
+    H, W = (int(sensor_size[0]), int(sensor_size[1])) if sensor_size is not None else tuple(int(v) for v in e.shape[-2:])
+    if e.shape != (R, H, W):
+        raise ValueError(f'edges must be ({R},{H},{W}), got {e.shape}')
+    th = np.asarray(theta, dtype=np.float64)
+    if th.ndim != 3 or th.shape[2] != 2:
+        raise ValueError(f'theta must be (h,w,2), got {th.shape}')
+    rw = check_ref_weights(ref_weights, R)
+    if event_weights is not None:
+        event_weights = check_event_weights(event_weights, len(xs))
+    p = make_params(1.0, 0.0, 0.0, 0.0, 1, method)
+    if engine is None:
+        eng = losses.engine_for(xs, ys, ts, edges, edge_ts, (H, W), event_weights=event_weights)
+    else:
+        eng = engine
+        eng.set_window(xs, ys, ts, edges, edge_ts, event_weights)
+    images = None
+    if source == 'edges':
+        from .staging import normalize_edges
+        images = normalize_edges(e).astype(np.float32)
+    return eng.event_scores(images=images, ref_weights=rw, exclude_self=exclude_self, theta=th, params=p)[0]
+
+
 class BatchThetaEvaluator:
     """evaluate_theta_array / sparse_flow_error for a batch of evaluation windows that is staged once and evaluated many times: what
     EINCMThetaSolverCallback._evaluate_theta (callbacks.py:131-170) asks for at every iterate of every window of a lockstep batch.

@@ -227,6 +227,37 @@ def event_filter_weights(events, sensor_size, refractory=0.0, tau=0.0, radius=1,
                                                      polarity=bool(polarity), pixel_mask=mask, chunk=chunk, return_support=return_support)
 
 
+def weights_from_scores(scores, ref_weights=None, full_score=None):
+    """Per-event weights from per-event scores (Engine.event_scores): an event that lands on nothing after motion
+    compensation weighs little.  scores: (R, n) per reference time, or (n,) already combined.  (R, n) scores are combined over r with
+    ``ref_weights`` ((R,); None: the loss's own compute_weights_for_multi_reference(R), losses.py:39-46), divided by ``full_score``
+    (a positive number; None: the median of the positive combined scores, so that half of the events that hit anything weigh 1), and
+    clipped to [0, 1].  Plain numpy; the float32 result is what ``stage_datasample(event_weights=)`` takes."""
+    s = np.asarray(scores, dtype=np.float64)
+    if s.ndim not in (1, 2) or not np.isfinite(s).all():
+        raise ValueError(f'scores must be finite, (R, n) or (n,), got shape {s.shape}')
+    if s.ndim == 2:
+        R = s.shape[0]
+        if ref_weights is None:
+            x = np.linspace(-1.5, 1.5, R)
+            w = np.exp(-0.5 * x * x)
+            w = w / w.sum()
+        else:
+            w = np.asarray(ref_weights, dtype=np.float64)
+            if w.shape != (R,) or not np.isfinite(w).all():
+                raise ValueError(f'ref_weights must be ({R},) finite numbers, got shape {w.shape}')
+        s = w @ s
+    elif ref_weights is not None:
+        raise ValueError('ref_weights given with scores that are already combined')
+    if full_score is None:
+        pos = s[s > 0.0]
+        full_score = float(np.median(pos)) if pos.size else 1.0
+    full_score = float(full_score)
+    if not (np.isfinite(full_score) and full_score > 0.0):
+        raise ValueError(f'full_score {full_score!r}: a positive number')
+    return np.clip(s / full_score, 0.0, 1.0).astype(np.float32)
+
+
 def hot_pixel_mask(xs, ys, sensor_size, max_count):
     """(H, W) uint8, 1 at the pixels with more than ``max_count`` events: ready for ``pixel_mask=``.  Plain numpy."""
     from .engine import check_event_coords

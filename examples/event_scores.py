@@ -1,0 +1,58 @@
+"""Per-event scores closing the loop from a solved motion back to the events: a synthetic window of moving edges
+plus a known set of uniform noise events is solved, every event is scored by how much of the OTHER events' IWE lies under it once it
+is warped (the leave-one-out score), the scores become per-event weights, and the window is staged with them and solved again.
+
+    python3 examples/event_scores.py [--events 30000] [--noise 10000]
+
+The two stream filters (examples/event_denoise.py, examples/event_filter.py) judge an event by its neighbours in the raw stream; they
+never see theta.  This one judges it by where the motion takes it: events that land on nothing after motion compensation are noise.
+The mean score of the signal events and of the noise events, and the flow error of both solves, are printed."""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+PKG = 'edge-informed-contrast-maximization_amd'
+synth, engine, bsol, staging = (importlib.import_module(f'{PKG}.{m}') for m in ('synth', 'engine', 'batch_solver', 'staging'))
+
+ap = argparse.ArgumentParser()
+ap.add_argument('--events', type=int, default=30000, help='events of the moving edges')
+ap.add_argument('--noise', type=int, default=10000, help='uniform noise events')
+a = ap.parse_args()
+
+H, W, R = 96, 128, 3
+rng = np.random.default_rng(0)
+win = synth.make_window(0, (H, W), a.events, R, flow='constant', flow_mag=8.0, noise_frac=0, n_segments=12, n_circles=2)
+ts = np.concatenate([win['ts'], rng.random(a.noise)])
+order = np.argsort(ts, kind='stable')                                          # the noise merged in by time
+n = len(order)
+xs = np.concatenate([win['xs'], rng.integers(0, W, a.noise)])[order].astype(np.int16)
+ys = np.concatenate([win['ys'], rng.integers(0, H, a.noise)])[order].astype(np.int16)
+ts = ts[order]
+is_noise = order >= a.events
+
+ds = dict(events=dict(x=xs, y=ys, t=ts), image_ts=win['edge_ts'], eval_ts=(0.0, 1.0))
+params = engine.make_params(20.0, 35.0, 0.0, 0.0, 1)
+truth = win['flow_gt'][0, 0]
+with engine.Engine((H, W), n, max_refs=R) as eng:
+    eng.set_windows([staging.stage_datasample(ds, edges=win['edges'])])
+    first = bsol.minimize_thetas(eng, np.zeros((1, 1, 1, 2)), params, maxiter=60, gtol=1e-6)[0]
+    th1 = np.asarray(first.x).reshape(1, 1, 1, 2)
+    # (R, n): the IWE of the solved theta under each warped event, the event's own share taken out
+    scores = eng.event_scores(exclude_self=True, theta=th1, params=params)[0]
+    weights = staging.weights_from_scores(scores)
+    eng.set_windows([staging.stage_datasample(ds, edges=win['edges'], event_weights=weights)])
+    second = bsol.minimize_thetas(eng, np.zeros((1, 1, 1, 2)), params, maxiter=60, gtol=1e-6)[0]
+
+mean = scores.mean(axis=0)
+s_sig, s_noise = float(mean[~is_noise].mean()), float(mean[is_noise].mean())
+print(f'{n} events: {a.events} on the edges, {a.noise} noise; true flow ({truth[0]:+.2f}, {truth[1]:+.2f}) px per window')
+print(f'mean leave-one-out score: signal events {s_sig:.3f}, noise events {s_noise:.3f}')
+print(f'mean weight: signal events {weights[~is_noise].mean():.3f}, noise events {weights[is_noise].mean():.3f}')
+for name, r in zip(('as staged', 'with the scores\' weights'), (first, second)):
+    th = np.asarray(r.x).reshape(2)
+    print(f'{name}: theta ({th[0]:+.2f}, {th[1]:+.2f}), flow error {np.linalg.norm(th - truth):.3f} px after {r.nit} iterations')
+assert s_sig > s_noise, 'signal events must outscore noise events'

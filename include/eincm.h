@@ -32,7 +32,7 @@ extern "C" {
                                *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models),
                                *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels), eincm_set_windows_weighted (per-event weights),
                                *    eincm_event_support (the event-support filter), eincm_event_filter (the refractory and polarity-aware
-                               *    filter) */
+                               *    filter), eincm_event_scores (an image stack sampled at the warped events) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -254,6 +254,32 @@ int eincm_get_count_images(eincm_ctx* ctx, uint32_t* counts);
  * compute_loss_objectives (src/eincm/losses.py:58,90-91; per_pix_warp, src/eincm/event_warpers.py:28-37), read only by plotters.
  * warped_xs, warped_ys: (n_refs, n_events[window]) float64 each.  Same operations as the evaluation's warp (product rounded first). */
 int eincm_get_warped_events(eincm_ctx* ctx, int window, double* warped_xs, double* warped_ys);
+
+/* Per-event scores: an image stack sampled at the warped events, the adjoint of the splat without the derivative,
+ *     s[r, e] = sum over d in {-1,0,1}^2 of  k_{e,r}(d) * F_r[ wrap_drop(round(x'_{e,r}) + d) ]
+ * for EVERY event of the staged batch in one call, under the Theta of the last evaluation (the one eincm_get_warped_events uses, also
+ * after a 2-DoF, motion-model or fused evaluation).  The warp is the evaluation's, the tap weights k are the splat's for the 3x3 window
+ * with the 1/(2 pi), the index rule is the splat's (negative indices wrap once, anything still outside is dropped); a dropped tap
+ * contributes 0.  Events are taken in the order they were handed to eincm_set_windows*, window after window.
+ *   images       (n_windows, n_refs, H, W) float on the host, or NULL: the IWEs of the last evaluation as eincm_get_iwes returns them,
+ *                read on the device without a trip through the host
+ *   ref_weights  NULL: window b's block of `scores` is (n_refs, n_events[b]) floats; or n_refs finite doubles omega: the block is
+ *                (n_events[b]) floats, sum_r (float)omega_r * s[r, e], summed in fp32 in ascending r.  The blocks follow one another.
+ *   selfs        NULL, or laid out as `scores`: sum over the undropped taps of k_{e,r}(d)^2 (combined: sum_r (float)omega_r * self[r, e]),
+ *                the event's own unit-weight share of an IWE at its own taps.  A caller forms the leave-one-out score against the IWE as
+ *                scores - w_e * selfs with the weight w_e the event was staged with (1 without weights); the kernel never reads the
+ *                staged weights.  With H, W >= 3 the three taps of an axis are distinct pixels after the wrap, so the event met each
+ *                of its pixels once and the subtraction removes exactly its own share.
+ * Arithmetic: fp32 after the fp64 warp.  k(d) = ky * kx is one rounded product; the nine taps are added in one fixed order, rows
+ * dy = -1, 0, +1 and within a row dx = -1, 0, +1, by one fused multiply-add each onto a sum that starts at +0, skipping dropped taps.
+ * No atomics and no reduction across threads: every run gives the same bytes.  An event whose taps are all dropped (Theta far out of
+ * frame) scores exactly 0.
+ * Refused before anything is written, in this order: EINCM_ERR_STATE an evaluation in flight; EINCM_ERR_ARG scores == NULL;
+ * EINCM_ERR_STATE nothing staged or no evaluation yet; EINCM_ERR_UNSUPPORTED an EINCM_CF_FP64 context, a splat window other than 3
+ * (as a weighted batch), an event-sharded staging (EINCM_SW_DEFER_CONSTANTS); EINCM_ERR_ARG a ref_weights entry that is not finite;
+ * EINCM_ERR_STATE images == NULL after an evaluation that left windows out (eincm_loss_grad_masked: their IWEs are not current).  A
+ * batch with no events at all is valid and writes nothing; a window without events has an empty block. */
+int eincm_event_scores(eincm_ctx* ctx, const float* images, const double* ref_weights, float* scores, float* selfs);
 
 /* compute_weights_for_multi_reference (losses.py:39-46) */
 int eincm_multi_ref_weights(int n_refs, double* w);
