@@ -450,6 +450,93 @@ struct OneShot {
     hipError_t sync() { pending = false; return hipStreamSynchronize(c->stream); }
 };
 
+// The front end of the operators on one chunk of a raw event stream (eincm_event_support, eincm_event_filter; DESIGN.md
+// sections 5.2 and 23): what they share before their own kernels.  Constructed on the call's OneShot before begin(), it declares the shared pieces;
+// then, in the operator's order of calls, validate() refuses a bad chunk, carried_maps() readies the operator's own carried state,
+// and sort_and_bound() leaves every pixel's events as one ascending run [lo()[pixel], hi()[pixel]) of key() (sorted pixel keys) and
+// idx() (the event indices in that order).  It touches no carried state but what carried_maps() is handed.
+struct StreamChunk {
+    eincm_ctx* const c; OneShot& op;
+    const int16_t* const x; const int16_t* const y; const double* const t; const int64_t n; const uint8_t* const pixel_mask;
+    const int H, W; const int64_t npix; const EsSortPlan plan;
+    const unsigned gn, gp;                                               // grids of NT threads over the events, over the pixels
+    const OneShot::Piece<int16_t> d_x, d_y; const OneShot::Piece<double> d_t;
+    const OneShot::Piece<uint32_t> d_key[2], d_val[2], d_hist, d_tiles, d_lohi;      // (lo | hi)
+    const OneShot::Piece<uint8_t> d_mask; const OneShot::Piece<uint32_t> d_err;
+    uint32_t* const h_err;                                               // d_err comes down here
+    int cur = 0;                                                         // the sorted (key, index) arrays so far: d_key[cur], d_val[cur]
+    StreamChunk(OneShot& op_, const int16_t* x_, const int16_t* y_, const double* t_, int64_t n_, const uint8_t* pixel_mask_)
+        : c(op_.c), op(op_), x(x_), y(y_), t(t_), n(n_), pixel_mask(pixel_mask_), H(c->H), W(c->W), npix((int64_t)H * W),
+          plan(es_sort_plan(n, npix)), gn((unsigned)((n + NT - 1) / NT)), gp((unsigned)((npix + NT - 1) / NT)),
+          d_x(op.piece<int16_t>((size_t)n)), d_y(op.piece<int16_t>((size_t)n)), d_t(op.piece<double>((size_t)n)),
+          d_key{op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)},
+          d_val{op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)}, d_hist(op.piece<uint32_t>((size_t)plan.nhist)),
+          d_tiles(op.piece<uint32_t>((size_t)plan.ntiles)), d_lohi(op.piece<uint32_t>((size_t)npix * 2)),
+          d_mask(op.piece<uint8_t>((size_t)npix, pixel_mask != nullptr)), d_err(op.piece<uint32_t>(1)), h_err(op.host_buf<uint32_t>(1)) {}
+
+    // The argument faults that every stream operator words alike
+    static int bad_n(eincm_ctx* c, int64_t n) {
+        return fail(c, EINCM_ERR_ARG, "n = %lld outside [0, 2^30] (walk a recording in chunks)", (long long)n);
+    }
+    static int bad_tau(eincm_ctx* c, double tau) { return fail(c, EINCM_ERR_ARG, "tau = %g (finite and >= 0)", tau); }
+
+    // x, y, t go up and are checked against `carried`, the time of the last event before the chunk; the pixel keys are left in key().
+    // A refusal names the first offender.
+    int validate(double carried) {
+        if (n == 0) return EINCM_OK;
+        HIPCHK(c, op.up(d_x, x, (size_t)n * 2));                         // (host memory: the caller's, as every copy below but h_err's)
+        HIPCHK(c, op.up(d_y, y, (size_t)n * 2));
+        HIPCHK(c, op.up(d_t, t, (size_t)n * 8));
+        HIPCHK(c, op.zero(d_err, sizeof(uint32_t)));
+        HIPCHK(c, op.launch(k_es_validate, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, carried, d_key[0], d_err));
+        HIPCHK(c, op.down(h_err, d_err, sizeof(uint32_t)));
+        HIPCHK(c, op.sync());
+        if (!*h_err) return EINCM_OK;
+        const int64_t e = n - (int64_t)*h_err;
+        if (e < 0 || e >= n) return fail(c, EINCM_ERR_HIP, "first refused event %lld of %lld", (long long)e, (long long)n);
+        switch (es_event_fault(H, W, x[e], y[e], t[e], e > 0 ? t[e - 1] : carried)) {
+            case ES_EV_COORD: return fail(c, EINCM_ERR_ARG, "event %lld: (%d, %d) outside the %dx%d sensor", (long long)e, x[e], y[e], H, W);
+            case ES_EV_TIME: return fail(c, EINCM_ERR_ARG, "event %lld: time %g is not finite", (long long)e, t[e]);
+            default:
+                return fail(c, EINCM_ERR_ARG, "event %lld: time %.17g is smaller than %.17g, %s", (long long)e, t[e],
+                            e > 0 ? t[e - 1] : carried, e > 0 ? "its predecessor's" : "the last time of the previous chunk");
+        }
+    }
+
+    // An operator's carried maps (count doubles) exist afterwards; on the first call and on a reset they, and last_time, say "no event"
+    int carried_maps(Grow<double>& maps, size_t count, int reset, double& last_time) {
+        const bool fresh = maps.n < count;
+        HIPCHK(c, ensure(c, maps, count));
+        if (fresh || reset) {
+            HIPCHK(c, op.launch(k_es_fill, dim3((unsigned)((count + NT - 1) / NT)), dim3(NT), 0, (int64_t)count, maps.p, es_no_event()));
+            last_time = es_no_event();
+        }
+        return EINCM_OK;
+    }
+
+    // n > 0, after validate(): the mask goes up, (key, index) are sorted by key and every pixel's run is bounded
+    int sort_and_bound() {
+        if (pixel_mask) HIPCHK(c, op.up(d_mask, pixel_mask, (size_t)npix));
+        HIPCHK(c, op.zero(d_lohi, (size_t)npix * 2 * sizeof(uint32_t)));
+        const unsigned nblk = (unsigned)plan.nblk, ntiles = (unsigned)plan.ntiles;
+        for (int pass = 0; pass < plan.passes; ++pass, cur ^= 1) {
+            const int shift = pass * ES_RADIX_BITS;
+            const uint32_t* const vin = pass ? (const uint32_t*)d_val[cur] : nullptr;      // (pass 0: the indices themselves)
+            HIPCHK(c, op.launch(k_es_hist, dim3(nblk), dim3(64), 0, n, plan.nblk, shift, d_key[cur], d_hist));
+            HIPCHK(c, op.launch(k_es_scan_tiles, dim3(ntiles), dim3(ES_SCAN_NT), 0, plan.nhist, d_hist, d_tiles));
+            HIPCHK(c, op.launch(k_es_scan, dim3(1), dim3(ES_SCAN_NT), 0, plan.ntiles, d_tiles));
+            HIPCHK(c, op.launch(k_es_scatter, dim3(nblk), dim3(64), 0, n, plan.nblk, shift, d_key[cur], vin, d_hist, d_tiles,
+                                d_key[cur ^ 1], d_val[cur ^ 1]));
+        }
+        HIPCHK(c, op.launch(k_es_bounds, dim3(gn), dim3(NT), 0, n, npix, d_key[cur], lo(), hi()));
+        return EINCM_OK;
+    }
+    uint32_t* lo() const { return d_lohi; }
+    uint32_t* hi() const { return lo() + npix; }
+    const uint32_t* key() const { return d_key[cur]; }
+    const uint32_t* idx() const { return d_val[cur]; }
+};
+
 // ---- the environment: every read, one function per lifetime ----
 const EvalKnobs& process_knobs() {     // once per process, at the first evaluation of a context that is not float64
     static const EvalKnobs k{getenv("EINCM_NO_BIG_THETA_ARG") != nullptr, getenv("EINCM_NO_HOST_ASM") != nullptr,
@@ -2541,88 +2628,34 @@ int eincm_rectify_events(eincm_ctx* c, const float* rectify_map, const int16_t* 
     return EINCM_OK;
 }
 
-// The spatiotemporal support filter for one chunk of a stream (eincm_event_support.hip.h): validate, sort the
-// event indices by pixel, search every neighbour's run, update the carried map.  A refused chunk leaves the carried state as it was.
+// The spatiotemporal support filter for one chunk of a stream (eincm_event_support.hip.h): the front end
+// validates, sorts the event indices by pixel and bounds the runs; then search every neighbour's run, update the carried map.  A
+// refused chunk leaves the carried state as it was: validate() returns before carried_maps() is reached.
 int eincm_event_support(eincm_ctx* c, const int16_t* x, const int16_t* y, const double* t, int64_t n, double tau, int radius,
                         int full_support, const uint8_t* pixel_mask, int reset, float* weights, uint8_t* support) {
     if (!c) return EINCM_ERR_ARG;
     if (const int rc = not_in_flight(c, "eincm_event_support")) return rc;
     switch (es_check_args(n, tau, radius, full_support)) {
-        case ES_ARG_N: return fail(c, EINCM_ERR_ARG, "n = %lld outside [0, 2^30] (walk a recording in chunks)", (long long)n);
-        case ES_ARG_TAU: return fail(c, EINCM_ERR_ARG, "tau = %g (finite and >= 0)", tau);
+        case ES_ARG_N: return StreamChunk::bad_n(c, n);
+        case ES_ARG_TAU: return StreamChunk::bad_tau(c, tau);
         case ES_ARG_RADIUS: return fail(c, EINCM_ERR_ARG, "radius = %d outside [1, %d]", radius, ES_MAX_RADIUS);
         case ES_ARG_FULL_SUPPORT:
             return fail(c, EINCM_ERR_ARG, "full_support = %d outside [1, %d] for radius %d", full_support, es_max_support(radius), radius);
         case ES_ARG_OK: break;
     }
     if (n > 0 && (!x || !y || !t || !weights)) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    const int H = c->H, W = c->W;
-    const int64_t npix = (int64_t)H * W;
-    const double carried = reset ? es_no_event() : c->es.last_time;
-    const int nblk = (int)((n + ES_SORT_BLOCK - 1) / ES_SORT_BLOCK);
-    const size_t nhist = (size_t)ES_RADIX * (size_t)nblk;
-    const unsigned gn = (unsigned)((n + NT - 1) / NT), gp = (unsigned)((npix + NT - 1) / NT);
     OneShot op(c);
-    const auto d_x = op.piece<int16_t>((size_t)n), d_y = op.piece<int16_t>((size_t)n);
-    const auto d_t = op.piece<double>((size_t)n);
-    const OneShot::Piece<uint32_t> d_key[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
-    const OneShot::Piece<uint32_t> d_val[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
-    const auto d_hist = op.piece<uint32_t>(nhist);
-    const size_t ntiles = (nhist + ES_SCAN_TILE - 1) / ES_SCAN_TILE;
-    const auto d_tiles = op.piece<uint32_t>(ntiles);
-    const auto d_lohi = op.piece<uint32_t>((size_t)npix * 2);            // lo | hi
-    const auto d_mask = op.piece<uint8_t>((size_t)npix, pixel_mask != nullptr);
+    StreamChunk sc(op, x, y, t, n, pixel_mask);
     const auto d_w = op.piece<float>((size_t)n);
     const auto d_s = op.piece<uint8_t>((size_t)n);
-    const auto d_err = op.piece<uint32_t>(1);
-    uint32_t* h_err = op.host_buf<uint32_t>(1);                          // d_err comes down here
     HIPCHK(c, op.begin());
-    if (n > 0) {
-        HIPCHK(c, op.up(d_x, x, (size_t)n * 2));                         // (host memory: the caller's, as every copy below but h_err's)
-        HIPCHK(c, op.up(d_y, y, (size_t)n * 2));
-        HIPCHK(c, op.up(d_t, t, (size_t)n * 8));
-        HIPCHK(c, op.zero(d_err, sizeof(uint32_t)));
-        HIPCHK(c, op.launch(k_es_validate, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, carried, d_key[0], d_err));
-        HIPCHK(c, op.down(h_err, d_err, sizeof(uint32_t)));
-        HIPCHK(c, op.sync());
-        if (*h_err) {
-            const int64_t e = n - (int64_t)*h_err;
-            if (e < 0 || e >= n) return fail(c, EINCM_ERR_HIP, "first refused event %lld of %lld", (long long)e, (long long)n);
-            switch (es_event_fault(H, W, x[e], y[e], t[e], e > 0 ? t[e - 1] : carried)) {
-                case ES_EV_COORD: return fail(c, EINCM_ERR_ARG, "event %lld: (%d, %d) outside the %dx%d sensor", (long long)e, x[e], y[e], H, W);
-                case ES_EV_TIME: return fail(c, EINCM_ERR_ARG, "event %lld: time %g is not finite", (long long)e, t[e]);
-                default:
-                    return fail(c, EINCM_ERR_ARG, "event %lld: time %.17g is smaller than %.17g, %s", (long long)e, t[e],
-                                e > 0 ? t[e - 1] : carried, e > 0 ? "its predecessor's" : "the last time of the previous chunk");
-            }
-        }
-    }
-    const bool fresh = c->es.last_t.n < (size_t)npix;
-    HIPCHK(c, ensure(c, c->es.last_t, (size_t)npix));
-    if (fresh || reset) {
-        HIPCHK(c, op.launch(k_es_fill, dim3(gp), dim3(NT), 0, npix, c->es.last_t.p, es_no_event()));
-        c->es.last_time = es_no_event();
-    }
+    if (const int rc = sc.validate(reset ? es_no_event() : c->es.last_time)) return rc;
+    if (const int rc = sc.carried_maps(c->es.last_t, (size_t)sc.npix, reset, c->es.last_time)) return rc;
     if (n == 0) { HIPCHK(c, op.sync()); return EINCM_OK; }
-    uint32_t* const d_lo = d_lohi;
-    uint32_t* const d_hi = d_lo + npix;
-    if (pixel_mask) HIPCHK(c, op.up(d_mask, pixel_mask, (size_t)npix));
-    HIPCHK(c, op.zero(d_lo, (size_t)npix * 2 * sizeof(uint32_t)));
-    const int passes = es_sort_passes(npix);
-    int cur = 0;                                                         // the sorted (key, index) arrays so far: d_key[cur], d_val[cur]
-    for (int pass = 0; pass < passes; ++pass, cur ^= 1) {
-        const int shift = pass * ES_RADIX_BITS;
-        const uint32_t* const vin = pass ? (const uint32_t*)d_val[cur] : nullptr;      // (pass 0: the indices themselves)
-        HIPCHK(c, op.launch(k_es_hist, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], d_hist));
-        HIPCHK(c, op.launch(k_es_scan_tiles, dim3((unsigned)ntiles), dim3(ES_SCAN_NT), 0, (int64_t)nhist, d_hist, d_tiles));
-        HIPCHK(c, op.launch(k_es_scan, dim3(1), dim3(ES_SCAN_NT), 0, (int64_t)ntiles, d_tiles));
-        HIPCHK(c, op.launch(k_es_scatter, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], vin, d_hist, d_tiles,
-                            d_key[cur ^ 1], d_val[cur ^ 1]));
-    }
-    HIPCHK(c, op.launch(k_es_bounds, dim3(gn), dim3(NT), 0, n, npix, d_key[cur], d_lo, d_hi));
-    HIPCHK(c, op.launch(k_es_support, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, tau, radius, full_support, d_mask, d_lo, d_hi,
-                        d_val[cur], c->es.last_t.p, d_w, d_s));
-    HIPCHK(c, op.launch(k_es_map, dim3(gp), dim3(NT), 0, npix, n, d_lo, d_hi, d_val[cur], d_t, c->es.last_t.p));
+    if (const int rc = sc.sort_and_bound()) return rc;
+    HIPCHK(c, op.launch(k_es_support, dim3(sc.gn), dim3(NT), 0, sc.H, sc.W, n, sc.d_x, sc.d_y, sc.d_t, tau, radius, full_support, sc.d_mask,
+                        sc.lo(), sc.hi(), sc.idx(), c->es.last_t.p, d_w, d_s));
+    HIPCHK(c, op.launch(k_es_map, dim3(sc.gp), dim3(NT), 0, sc.npix, n, sc.lo(), sc.hi(), sc.idx(), sc.d_t, c->es.last_t.p));
     HIPCHK(c, op.down(weights, d_w, (size_t)n * sizeof(float)));
     if (support) HIPCHK(c, op.down(support, d_s, (size_t)n));
     HIPCHK(c, op.sync());
@@ -2630,19 +2663,18 @@ int eincm_event_support(eincm_ctx* c, const int16_t* x, const int16_t* y, const 
     return EINCM_OK;
 }
 
-// The refractory and polarity-aware filter for one chunk of a stream (eincm_event_filter.hip.h): validate, sort
-// and bound as eincm_event_support does, decide per sorted position which events survive, max-scan the survivors' positions, count
-// every kept event's neighbours from kept events alone, update the three carried maps.  A refused chunk leaves the carried state as
-// it was.
+// The refractory and polarity-aware filter for one chunk of a stream (eincm_event_filter.hip.h): the same
+// front end; then decide per sorted position which events survive, max-scan the survivors' positions, count every kept event's
+// neighbours from kept events alone, update the three carried maps.  A refused chunk leaves the carried state as it was.
 int eincm_event_filter(eincm_ctx* c, const int16_t* x, const int16_t* y, const double* t, const int8_t* p, int64_t n, double refractory,
                        double tau, int radius, int full_support, int flags, const uint8_t* pixel_mask, int reset, uint8_t* keep,
                        float* weights, uint8_t* support) {
     if (!c) return EINCM_ERR_ARG;
     if (const int rc = not_in_flight(c, "eincm_event_filter")) return rc;
     switch (ef_check_args(n, refractory, tau, radius, full_support, flags, p != nullptr)) {
-        case EF_ARG_N: return fail(c, EINCM_ERR_ARG, "n = %lld outside [0, 2^30] (walk a recording in chunks)", (long long)n);
+        case EF_ARG_N: return StreamChunk::bad_n(c, n);
         case EF_ARG_REFRACTORY: return fail(c, EINCM_ERR_ARG, "refractory = %g (finite and >= 0)", refractory);
-        case EF_ARG_TAU: return fail(c, EINCM_ERR_ARG, "tau = %g (finite and >= 0)", tau);
+        case EF_ARG_TAU: return StreamChunk::bad_tau(c, tau);
         case EF_ARG_RADIUS: return fail(c, EINCM_ERR_ARG, "radius = %d outside [0, %d]", radius, ES_MAX_RADIUS);
         case EF_ARG_FULL_SUPPORT:
             return fail(c, EINCM_ERR_ARG, "full_support = %d outside [1, %d] for radius %d", full_support,
@@ -2653,85 +2685,31 @@ int eincm_event_filter(eincm_ctx* c, const int16_t* x, const int16_t* y, const d
         case EF_ARG_OK: break;
     }
     if (n > 0 && (!x || !y || !t || !keep || !weights)) return fail(c, EINCM_ERR_ARG, "null pointer argument");
-    const int H = c->H, W = c->W;
-    const int64_t npix = (int64_t)H * W;
-    const double carried = reset ? es_no_event() : c->ef.last_time;
-    const int nblk = (int)((n + ES_SORT_BLOCK - 1) / ES_SORT_BLOCK);
-    const size_t nhist = (size_t)ES_RADIX * (size_t)nblk;
-    const unsigned gn = (unsigned)((n + NT - 1) / NT), gp = (unsigned)((npix + NT - 1) / NT);
     OneShot op(c);
-    const auto d_x = op.piece<int16_t>((size_t)n), d_y = op.piece<int16_t>((size_t)n);
-    const auto d_t = op.piece<double>((size_t)n);
+    StreamChunk sc(op, x, y, t, n, pixel_mask);
     const auto d_p = op.piece<int8_t>((size_t)n, p != nullptr);
-    const OneShot::Piece<uint32_t> d_key[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
-    const OneShot::Piece<uint32_t> d_val[2] = {op.piece<uint32_t>((size_t)n), op.piece<uint32_t>((size_t)n)};
-    const auto d_hist = op.piece<uint32_t>(nhist);
-    const size_t ntiles = (nhist + ES_SCAN_TILE - 1) / ES_SCAN_TILE;
-    const auto d_tiles = op.piece<uint32_t>(ntiles);
-    const auto d_lohi = op.piece<uint32_t>((size_t)npix * 2);            // lo | hi
-    const auto d_mask = op.piece<uint8_t>((size_t)npix, pixel_mask != nullptr);
     const auto d_m = op.piece<uint2>((size_t)n);                         // the scan seeds, then the scan
     const size_t nmt = ((size_t)n + EF_SCAN_TILE - 1) / EF_SCAN_TILE;
     const auto d_mt = op.piece<uint2>(nmt);
     const auto d_k = op.piece<uint8_t>((size_t)n);
     const auto d_w = op.piece<float>((size_t)n);
     const auto d_s = op.piece<uint8_t>((size_t)n);
-    const auto d_err = op.piece<uint32_t>(1);
-    uint32_t* h_err = op.host_buf<uint32_t>(1);                          // d_err comes down here
     HIPCHK(c, op.begin());
-    if (n > 0) {
-        HIPCHK(c, op.up(d_x, x, (size_t)n * 2));                         // (host memory: the caller's, as every copy below but h_err's)
-        HIPCHK(c, op.up(d_y, y, (size_t)n * 2));
-        HIPCHK(c, op.up(d_t, t, (size_t)n * 8));
-        HIPCHK(c, op.zero(d_err, sizeof(uint32_t)));
-        HIPCHK(c, op.launch(k_es_validate, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, carried, d_key[0], d_err));
-        HIPCHK(c, op.down(h_err, d_err, sizeof(uint32_t)));
-        HIPCHK(c, op.sync());
-        if (*h_err) {
-            const int64_t e = n - (int64_t)*h_err;
-            if (e < 0 || e >= n) return fail(c, EINCM_ERR_HIP, "first refused event %lld of %lld", (long long)e, (long long)n);
-            switch (es_event_fault(H, W, x[e], y[e], t[e], e > 0 ? t[e - 1] : carried)) {
-                case ES_EV_COORD: return fail(c, EINCM_ERR_ARG, "event %lld: (%d, %d) outside the %dx%d sensor", (long long)e, x[e], y[e], H, W);
-                case ES_EV_TIME: return fail(c, EINCM_ERR_ARG, "event %lld: time %g is not finite", (long long)e, t[e]);
-                default:
-                    return fail(c, EINCM_ERR_ARG, "event %lld: time %.17g is smaller than %.17g, %s", (long long)e, t[e],
-                                e > 0 ? t[e - 1] : carried, e > 0 ? "its predecessor's" : "the last time of the previous chunk");
-            }
-        }
-    }
-    const bool fresh = c->ef.maps.n < (size_t)npix * 3;
-    HIPCHK(c, ensure(c, c->ef.maps, (size_t)npix * 3));
-    if (fresh || reset) {
-        HIPCHK(c, op.launch(k_es_fill, dim3((unsigned)((npix * 3 + NT - 1) / NT)), dim3(NT), 0, npix * 3, c->ef.maps.p, es_no_event()));
-        c->ef.last_time = es_no_event();
-    }
+    if (const int rc = sc.validate(reset ? es_no_event() : c->ef.last_time)) return rc;
+    if (const int rc = sc.carried_maps(c->ef.maps, (size_t)sc.npix * 3, reset, c->ef.last_time)) return rc;
     if (n == 0) { HIPCHK(c, op.sync()); return EINCM_OK; }
     double* const last_any = c->ef.maps.p;
-    double* const kept0 = last_any + npix;
-    double* const kept1 = kept0 + npix;
-    uint32_t* const d_lo = d_lohi;
-    uint32_t* const d_hi = d_lo + npix;
-    if (pixel_mask) HIPCHK(c, op.up(d_mask, pixel_mask, (size_t)npix));
+    double* const kept0 = last_any + sc.npix;
+    double* const kept1 = kept0 + sc.npix;
     if (p) HIPCHK(c, op.up(d_p, p, (size_t)n));
-    HIPCHK(c, op.zero(d_lo, (size_t)npix * 2 * sizeof(uint32_t)));
-    const int passes = es_sort_passes(npix);
-    int cur = 0;                                                         // the sorted (key, index) arrays so far: d_key[cur], d_val[cur]
-    for (int pass = 0; pass < passes; ++pass, cur ^= 1) {
-        const int shift = pass * ES_RADIX_BITS;
-        const uint32_t* const vin = pass ? (const uint32_t*)d_val[cur] : nullptr;      // (pass 0: the indices themselves)
-        HIPCHK(c, op.launch(k_es_hist, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], d_hist));
-        HIPCHK(c, op.launch(k_es_scan_tiles, dim3((unsigned)ntiles), dim3(ES_SCAN_NT), 0, (int64_t)nhist, d_hist, d_tiles));
-        HIPCHK(c, op.launch(k_es_scan, dim3(1), dim3(ES_SCAN_NT), 0, (int64_t)ntiles, d_tiles));
-        HIPCHK(c, op.launch(k_es_scatter, dim3((unsigned)nblk), dim3(64), 0, n, nblk, shift, d_key[cur], vin, d_hist, d_tiles,
-                            d_key[cur ^ 1], d_val[cur ^ 1]));
-    }
-    HIPCHK(c, op.launch(k_es_bounds, dim3(gn), dim3(NT), 0, n, npix, d_key[cur], d_lo, d_hi));
-    HIPCHK(c, op.launch(k_ef_keep, dim3(gn), dim3(NT), 0, n, d_key[cur], d_val[cur], d_lo, d_t, d_p, refractory, d_mask, last_any, d_k, d_m));
+    if (const int rc = sc.sort_and_bound()) return rc;
+    HIPCHK(c, op.launch(k_ef_keep, dim3(sc.gn), dim3(NT), 0, n, sc.key(), sc.idx(), sc.lo(), sc.d_t, d_p, refractory, sc.d_mask, last_any,
+                        d_k, d_m));
     HIPCHK(c, op.launch(k_ef_scan_tiles, dim3((unsigned)nmt), dim3(EF_SCAN_NT), 0, n, d_m, d_mt));
     HIPCHK(c, op.launch(k_ef_scan, dim3(1), dim3(EF_SCAN_NT), 0, (int64_t)nmt, d_mt));
-    HIPCHK(c, op.launch(k_ef_support, dim3(gn), dim3(NT), 0, H, W, n, d_x, d_y, d_t, d_p, tau, radius, full_support,
-                        (flags & EF_POLARITY) ? 1 : 0, d_mask, d_lo, d_hi, d_val[cur], d_m, d_mt, d_k, kept0, kept1, d_w, d_s));
-    HIPCHK(c, op.launch(k_ef_map, dim3(gp), dim3(NT), 0, npix, n, d_lo, d_hi, d_val[cur], d_m, d_mt, d_t, last_any, kept0, kept1));
+    HIPCHK(c, op.launch(k_ef_support, dim3(sc.gn), dim3(NT), 0, sc.H, sc.W, n, sc.d_x, sc.d_y, sc.d_t, d_p, tau, radius, full_support,
+                        (flags & EF_POLARITY) ? 1 : 0, sc.d_mask, sc.lo(), sc.hi(), sc.idx(), d_m, d_mt, d_k, kept0, kept1, d_w, d_s));
+    HIPCHK(c, op.launch(k_ef_map, dim3(sc.gp), dim3(NT), 0, sc.npix, n, sc.lo(), sc.hi(), sc.idx(), d_m, d_mt, sc.d_t, last_any, kept0, kept1));
     HIPCHK(c, op.down(keep, d_k, (size_t)n));
     HIPCHK(c, op.down(weights, d_w, (size_t)n * sizeof(float)));
     if (support) HIPCHK(c, op.down(support, d_s, (size_t)n));

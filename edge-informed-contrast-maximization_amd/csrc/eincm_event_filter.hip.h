@@ -1,7 +1,9 @@
 // eincm_event_filter.hip.h — the refractory and polarity-aware event filter of a raw event stream, one chunk per call (DESIGN.md
-// section 24; the rules themselves are in eincm_event_filter.h).  The chunk is validated, sorted by pixel and bounded by the
-// event-support filter's own kernels (k_es_validate, k_es_hist, k_es_scan_tiles, k_es_scan, k_es_scatter, k_es_bounds of
-// eincm_event_support.hip.h), after which every pixel's events are one ascending run of the sorted positions.  What is new:
+// section 24; the rules themselves are in eincm_event_filter.h).  The chunk front end of eincm_api.hip (StreamChunk) validates the
+// chunk, sorts it by pixel and bounds the runs with the event-support filter's kernels (k_es_validate, k_es_hist, k_es_scan_tiles,
+// k_es_scan, k_es_scatter, k_es_bounds of eincm_event_support.hip.h), after which every pixel's events are one ascending run of the
+// sorted positions.  The scans below are that header's block_scan and block_exclusive_prefix under EfMax, the search its
+// es_run_lower_bound.  What is new:
 //
 //   k_ef_keep        per sorted position s: the event's predecessor on its pixel is position s - 1 (the carried last_any map for
 //                    the first of a run), whatever became of it, so the refractory rule is one subtraction and one compare;
@@ -28,6 +30,7 @@ constexpr int EF_SCAN_NT = 1024;
 constexpr int EF_SCAN_TILE = EF_SCAN_NT * 4;       // sorted positions per workgroup of the tile scan (the tests name this size)
 
 __device__ __forceinline__ uint2 ef_max(uint2 a, uint2 b) { return make_uint2(a.x > b.x ? a.x : b.x, a.y > b.y ? a.y : b.y); }
+struct EfMax { __device__ uint2 operator()(uint2 a, uint2 b) const { return ef_max(a, b); } };
 
 // The scanned pair at position j: the tile's own scan joined to the maximum of every tile before it
 __device__ __forceinline__ uint2 ef_scanned(const uint2* __restrict__ m, const uint2* __restrict__ tilepre, uint32_t j) {
@@ -51,20 +54,6 @@ __global__ __launch_bounds__(NT) void k_ef_keep(int64_t n, const uint32_t* __res
     m[s] = make_uint2(cls == 0 ? seed : 0u, cls == 1 ? seed : 0u);
 }
 
-// The workgroup's EF_SCAN_NT pairs become their inclusive prefix maxima in part (Hillis-Steele in LDS; integer maxima: the shape of
-// the scan does not show in the result).  part is complete and no longer written when the function returns.
-__device__ __forceinline__ void ef_block_scan(uint2* part, uint2 own) {
-    const int tid = threadIdx.x;
-    part[tid] = own;
-    __syncthreads();
-    for (int d = 1; d < EF_SCAN_NT; d <<= 1) {
-        const uint2 v = tid >= d ? part[tid - d] : make_uint2(0u, 0u);
-        __syncthreads();
-        part[tid] = ef_max(part[tid], v);
-        __syncthreads();
-    }
-}
-
 // grid ceil(n / EF_SCAN_TILE).  Every tile of m (n) becomes its own inclusive prefix maximum, in place, and tilemax[tile] its
 // maximum.  A thread owns four consecutive pairs: two 16-byte loads and stores (m is 16-byte aligned, a thread starts at a multiple
 // of four pairs).
@@ -80,7 +69,7 @@ __global__ __launch_bounds__(EF_SCAN_NT) void k_ef_scan_tiles(int64_t n, uint2* 
 #pragma unroll
         for (int k = 0; k < 4; ++k) if (i0 + k < n) v[k] = m[i0 + k];
     }
-    ef_block_scan(part, ef_max(ef_max(v[0], v[1]), ef_max(v[2], v[3])));
+    block_scan<EF_SCAN_NT>(part, ef_max(ef_max(v[0], v[1]), ef_max(v[2], v[3])), EfMax{});
     if (threadIdx.x == EF_SCAN_NT - 1) tilemax[blockIdx.x] = part[EF_SCAN_NT - 1];
     uint2 r = threadIdx.x > 0 ? part[threadIdx.x - 1] : make_uint2(0u, 0u);
 #pragma unroll
@@ -94,18 +83,10 @@ __global__ __launch_bounds__(EF_SCAN_NT) void k_ef_scan_tiles(int64_t n, uint2* 
     }
 }
 
-// One workgroup: data (len, the tile maxima) becomes its exclusive prefix maximum, in place.  A thread owns a contiguous piece; the
-// pieces' maxima are scanned in LDS.
+// One workgroup: data (len, the tile maxima) becomes its exclusive prefix maximum, in place.
 __global__ __launch_bounds__(EF_SCAN_NT) void k_ef_scan(int64_t len, uint2* data) {
     __shared__ uint2 part[EF_SCAN_NT];
-    const int tid = threadIdx.x;
-    const int64_t per = (len + EF_SCAN_NT - 1) / EF_SCAN_NT;
-    const int64_t i0 = (int64_t)tid * per < len ? (int64_t)tid * per : len, i1 = i0 + per < len ? i0 + per : len;
-    uint2 own = make_uint2(0u, 0u);
-    for (int64_t i = i0; i < i1; ++i) own = ef_max(own, data[i]);
-    ef_block_scan(part, own);
-    uint2 run = tid > 0 ? part[tid - 1] : make_uint2(0u, 0u);
-    for (int64_t i = i0; i < i1; ++i) { const uint2 v = data[i]; data[i] = run; run = ef_max(run, v); }
+    block_exclusive_prefix<EF_SCAN_NT>(part, len, data, EfMax{});
 }
 
 // grid ceil(n / NT).  idx: the sorted event indices (every pixel's run ascending); m, tilepre: the scan as k_ef_scan_tiles and
@@ -134,11 +115,7 @@ __global__ __launch_bounds__(NT) void k_ef_support(int H, int W, int64_t n, cons
                 const int q = qy * W + qx;
                 if (q == p || (mask && mask[q])) continue;
                 const uint32_t first = lo[q];
-                uint32_t a = first, b = hi[q];                // the first position of the run whose index is not below e
-                while (a < b) {
-                    const uint32_t mid = a + ((b - a) >> 1);
-                    if (idx[mid] < (uint32_t)e) a = mid + 1u; else b = mid;
-                }
+                const uint32_t a = es_run_lower_bound(idx, first, hi[q], (uint32_t)e);
                 uint32_t last = 0u;                           // one past the position of q's last kept event below e that counts
                 if (a > first) {
                     const uint2 sc = ef_scanned(m, tilepre, a - 1u);

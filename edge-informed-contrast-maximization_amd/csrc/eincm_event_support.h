@@ -1,6 +1,7 @@
 // eincm_event_support.h — the rules of the event-support filter that need no GPU: the argument checks, the
-// per-event refusals and their first offender, the neighbour window clipped to the sensor, the carried-time rule and the weight.
-// The kernels of eincm_event_support.hip.h run the EINCM_HD functions below per event; eincm_api.hip runs the argument checks.
+// per-event refusals and their first offender, the neighbour window clipped to the sensor, the carried-time rule, the weight, and
+// the geometry of the sort by pixel.  The kernels of eincm_event_support.hip.h run the EINCM_HD functions below per event;
+// eincm_api.hip runs the argument checks and launches the sort from es_sort_plan.
 //
 // As eincm_plan.h: no HIP, no environment.  Plain C++17, so tests/host/event_support_check.cpp runs all of it on the CPU under the
 // sanitizers (tests/test_host_event_support.py).
@@ -83,6 +84,33 @@ EINCM_HD bool es_supported(double t_e, double t_prev, double tau) { return t_e -
 // One float32 division
 EINCM_HD float es_weight(int support, int full_support) {
     return (float)(support < full_support ? support : full_support) / (float)full_support;
+}
+
+// ---- the geometry of the sort by pixel (the kernels: eincm_event_support.hip.h) ----
+constexpr int ES_RADIX_BITS = 8;
+constexpr int ES_RADIX = 1 << ES_RADIX_BITS;       // 256 digits: 4 per lane
+constexpr int ES_SORT_BLOCK = 1024;                // events per wave of the sort: 16 trips of 64
+constexpr int ES_SCAN_NT = 1024;
+constexpr int ES_SCAN_TILE = ES_SCAN_NT * 4;       // histogram entries per workgroup of the tile scan
+
+// Passes of ES_RADIX_BITS bits that cover every pixel key below npix
+inline int es_sort_passes(int64_t npix) {
+    int bits = 1;
+    while (((int64_t)1 << bits) < npix) ++bits;
+    return (bits + ES_RADIX_BITS - 1) / ES_RADIX_BITS;
+}
+
+// What the host launches the sort of n events (0 <= n <= ES_MAX_N) over npix pixels with: nblk waves of ES_SORT_BLOCK events, the
+// digit-major histogram of nhist = ES_RADIX nblk entries (at most 2^28: an int, and every entry and every sum of entries counts
+// events, so stays <= 2^30 in a uint32_t), its ntiles tiles of ES_SCAN_TILE entries, and the passes.
+struct EsSortPlan { int nblk; int64_t nhist, ntiles; int passes; };
+inline EsSortPlan es_sort_plan(int64_t n, int64_t npix) {
+    EsSortPlan p;
+    p.nblk = (int)((n + ES_SORT_BLOCK - 1) / ES_SORT_BLOCK);
+    p.nhist = (int64_t)ES_RADIX * p.nblk;
+    p.ntiles = (p.nhist + ES_SCAN_TILE - 1) / ES_SCAN_TILE;
+    p.passes = es_sort_passes(npix);
+    return p;
 }
 
 }   // namespace eincm

@@ -18,6 +18,12 @@
 //   k_es_map        per pixel with a list: last_t[pixel] = the time of the list's last element
 //   k_es_fill       the carried map to "no event" (first call, reset)
 // Integer counts, one exact compare and one correctly rounded division: the outputs are the same bytes on every run.
+//
+// k_es_validate to k_es_bounds and k_es_fill are launched by the chunk front end of eincm_api.hip (StreamChunk, DESIGN.md section
+// 23), which the refractory filter of eincm_event_filter.hip.h uses too; the sort's geometry (ES_RADIX_BITS, ES_SORT_BLOCK,
+// ES_SCAN_TILE, es_sort_plan) is host arithmetic and lives in eincm_event_support.h.  Three pieces are written once for both
+// filters' kernels: block_scan (a workgroup's inclusive scan under any operator), block_exclusive_prefix (the body of k_es_scan
+// and k_ef_scan) and es_run_lower_bound (the search of k_es_support and k_ef_support).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -26,18 +32,6 @@
 #include "eincm_kernels.hip.h"
 
 namespace eincm {
-
-constexpr int ES_RADIX_BITS = 8;
-constexpr int ES_RADIX = 1 << ES_RADIX_BITS;       // 256 digits: 4 per lane
-constexpr int ES_SORT_BLOCK = 1024;                // events per wave of the sort: 16 trips of 64
-constexpr int ES_SCAN_NT = 1024;
-constexpr int ES_SCAN_TILE = ES_SCAN_NT * 4;       // histogram entries per workgroup of the tile scan
-
-inline int es_sort_passes(int64_t npix) {
-    int bits = 1;
-    while (((int64_t)1 << bits) < npix) ++bits;
-    return (bits + ES_RADIX_BITS - 1) / ES_RADIX_BITS;
-}
 
 // grid ceil(n / NT).  err[0] = max(n - e) over the refused events e (zero before the launch: none), key[e] = y W + x.
 __global__ __launch_bounds__(NT) void k_es_validate(int H, int W, int64_t n, const int16_t* __restrict__ xs, const int16_t* __restrict__ ys,
@@ -68,20 +62,36 @@ __global__ __launch_bounds__(64) void k_es_hist(int64_t n, int nblk, int shift, 
     for (int k = 0; k < ES_RADIX / 64; ++k) hist[(int64_t)(lane + 64 * k) * nblk + blockIdx.x] = h[lane + 64 * k];
 }
 
-// The workgroup's ES_SCAN_NT values become their inclusive prefix sums (Hillis-Steele in LDS; integer sums: the shape of the scan does
-// not show in the result).  Returns the calling thread's.
-__device__ __forceinline__ uint32_t es_block_scan(uint32_t* part, uint32_t own) {
+// The workgroup's NTH values become their inclusive prefixes under op in part (Hillis-Steele in LDS); returns the calling thread's.
+// T{} is op's identity (zero: sums and maxima of unsigned integers).  part is complete and no longer written when the function
+// returns.  Every use is an integer sum, an integer maximum or feeds an exact compare: the shape of the scan does not show in a result.
+template <int NTH, typename T, typename Op> __device__ __forceinline__ T block_scan(T* part, T own, Op op) {
     const int tid = threadIdx.x;
     part[tid] = own;
     __syncthreads();
-    for (int d = 1; d < ES_SCAN_NT; d <<= 1) {
-        const uint32_t v = tid >= d ? part[tid - d] : 0u;
+    for (int d = 1; d < NTH; d <<= 1) {
+        const T v = tid >= d ? part[tid - d] : T{};
         __syncthreads();
-        part[tid] += v;
+        part[tid] = op(part[tid], v);
         __syncthreads();
     }
     return part[tid];
 }
+
+// One workgroup of NTH threads: data (len) becomes its exclusive prefix under op, in place.  A thread owns a contiguous piece; the
+// pieces' totals are scanned in part (NTH elements of LDS).
+template <int NTH, typename T, typename Op> __device__ __forceinline__ void block_exclusive_prefix(T* part, int64_t len, T* data, Op op) {
+    const int tid = threadIdx.x;
+    const int64_t per = (len + NTH - 1) / NTH;
+    const int64_t i0 = (int64_t)tid * per < len ? (int64_t)tid * per : len, i1 = i0 + per < len ? i0 + per : len;
+    T own{};
+    for (int64_t i = i0; i < i1; ++i) own = op(own, data[i]);
+    block_scan<NTH>(part, own, op);
+    T run = tid > 0 ? part[tid - 1] : T{};
+    for (int64_t i = i0; i < i1; ++i) { const T v = data[i]; data[i] = run; run = op(run, v); }
+}
+
+struct EsSum { __device__ uint32_t operator()(uint32_t a, uint32_t b) const { return a + b; } };
 
 // grid ceil(len / ES_SCAN_TILE).  Every tile of data (len) becomes its own exclusive prefix sum, in place, and tilesum[tile] its total:
 // the exclusive prefix sum of data is then data[i] + (the exclusive prefix sum of tilesum)[i / ES_SCAN_TILE], which k_es_scatter adds
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(ES_SCAN_NT) void k_es_scan_tiles(int64_t len, uint3
         for (int k = 0; k < 4; ++k) if (i0 + k < len) v[k] = data[i0 + k];
     }
     const uint32_t own = v[0] + v[1] + v[2] + v[3];
-    const uint32_t incl = es_block_scan(part, own);
+    const uint32_t incl = block_scan<ES_SCAN_NT>(part, own, EsSum{});
     if (threadIdx.x == ES_SCAN_NT - 1) tilesum[blockIdx.x] = incl;
     const uint32_t run = incl - own;
     if (full) {
@@ -113,16 +123,10 @@ __global__ __launch_bounds__(ES_SCAN_NT) void k_es_scan_tiles(int64_t len, uint3
 }
 
 // One workgroup: data (len) becomes its exclusive prefix sum, in place (the tile sums of k_es_scan_tiles: len / 4096 of the
-// histogram).  A thread owns a contiguous piece; the pieces' sums are scanned in LDS.
+// histogram).
 __global__ __launch_bounds__(ES_SCAN_NT) void k_es_scan(int64_t len, uint32_t* data) {
     __shared__ uint32_t part[ES_SCAN_NT];
-    const int tid = threadIdx.x;
-    const int64_t per = (len + ES_SCAN_NT - 1) / ES_SCAN_NT;
-    const int64_t i0 = (int64_t)tid * per < len ? (int64_t)tid * per : len, i1 = i0 + per < len ? i0 + per : len;
-    uint32_t own = 0u;
-    for (int64_t i = i0; i < i1; ++i) own += data[i];
-    uint32_t run = es_block_scan(part, own) - own;
-    for (int64_t i = i0; i < i1; ++i) { const uint32_t v = data[i]; data[i] = run; run += v; }
+    block_exclusive_prefix<ES_SCAN_NT>(part, len, data, EsSum{});
 }
 
 // grid nblk, one wave each.  base, tilebase: the scanned histogram as k_es_scan_tiles and k_es_scan leave it.  The block's events go
@@ -176,6 +180,15 @@ __global__ __launch_bounds__(NT) void k_es_bounds(int64_t n, int64_t npix, const
     if (i == n - 1 || key[i + 1] != k) hi[k] = (uint32_t)(i + 1);
 }
 
+// The first position of the run [lo, hi) of idx whose index is not below e (hi: none); the run ascends.  log2(hi - lo) + 1 probes
+__device__ __forceinline__ uint32_t es_run_lower_bound(const uint32_t* __restrict__ idx, uint32_t lo, uint32_t hi, uint32_t e) {
+    while (lo < hi) {
+        const uint32_t m = lo + ((hi - lo) >> 1);
+        if (idx[m] < e) lo = m + 1u; else hi = m;
+    }
+    return lo;
+}
+
 // grid ceil(n / NT).  idx: the sorted event indices (every pixel's run ascending); last_t (npix) the carried map; mask (npix) or NULL.
 __global__ __launch_bounds__(NT) void k_es_support(int H, int W, int64_t n, const int16_t* __restrict__ xs, const int16_t* __restrict__ ys,
                                                    const double* __restrict__ ts, double tau, int radius, int full_support,
@@ -196,11 +209,7 @@ __global__ __launch_bounds__(NT) void k_es_support(int H, int W, int64_t n, cons
                 const int q = qy * W + qx;
                 if (q == p || (mask && mask[q])) continue;
                 const uint32_t first = lo[q];
-                uint32_t a = first, b = hi[q];                // the first position of the run whose index is not below e
-                while (a < b) {
-                    const uint32_t m = a + ((b - a) >> 1);
-                    if (idx[m] < (uint32_t)e) a = m + 1u; else b = m;
-                }
+                const uint32_t a = es_run_lower_bound(idx, first, hi[q], (uint32_t)e);
                 const uint32_t j = a > first ? idx[a - 1u] : (uint32_t)e;
                 const bool in_chunk = j < (uint32_t)e;        // (an index of the run below e: never read past the chunk)
                 const double tp = in_chunk ? es_prev_time(true, ts[j], 0.0) : es_prev_time(false, 0.0, last_t[q]);

@@ -314,6 +314,13 @@ def check_chunk(chunk):
     return int(chunk)
 
 
+def chunk_walk(n, chunk):
+    """The [i0, i1) pieces of a stream of n events, ``chunk`` at a time.  An empty stream is one empty piece: it still reaches the
+    library once (a map handed over is checked, a carried state is cleared)."""
+    for i0 in ([0] if n == 0 else range(0, n, chunk)):
+        yield i0, min(n, i0 + chunk)
+
+
 EVENT_SUPPORT_MAX_RADIUS = 3      # ES_MAX_RADIUS (csrc/eincm_event_support.h)
 
 
@@ -423,6 +430,19 @@ def event_support_first_offender(xs, ys, ts, shape, carried=-np.inf):
     if time[e]:
         return e, f'event {e}: time {ts[e]!r} is not finite'
     return e, f'event {e}: time {ts[e]!r} is smaller than its predecessor\'s {prev[e]!r}'
+
+
+def check_raw_stream(xs, ys, ts, pixel_mask, chunk, shape):
+    """What the operators on a raw stream take before their own arguments: (x, y int16, t float64, mask uint8 or None, chunk) of a
+    stream on a sensor of ``shape``.  ValueError: every refusal of the arrays, and the first event the C contract refuses."""
+    x, y = check_event_coords(xs, ys)
+    t = check_event_times(ts, x.shape[0])
+    mask = check_pixel_mask(pixel_mask, shape)
+    chunk = check_chunk(chunk)
+    bad = event_support_first_offender(x, y, t, shape)
+    if bad is not None:
+        raise ValueError(bad[1])
+    return x, y, t, mask, chunk
 
 
 def check_remap_args(src, mapping):
@@ -1271,9 +1291,7 @@ class Engine:
         rec_x, rec_y = np.empty(n, dtype=np.int16), np.empty(n, dtype=np.int16)
         keep = np.empty(n, dtype=np.uint8)
         kept, k = 0, C.c_int64(0)
-        # an empty stream still hands the map over, so that it is checked
-        for i0 in ([0] if n == 0 else range(0, n, chunk)):
-            i1 = min(n, i0 + chunk)
+        for i0, i1 in chunk_walk(n, chunk):
             self._check_data(self._lib.eincm_rectify_events(
                 self._ctx, m.ctypes.data if i0 == 0 else None, xs.ctypes.data + 2 * i0, ys.ctypes.data + 2 * i0, i1 - i0,
                 rec_x.ctypes.data + 2 * kept, rec_y.ctypes.data + 2 * kept, keep.ctypes.data + i0, C.byref(k)))
@@ -1289,19 +1307,11 @@ class Engine:
         unit.  pixel_mask (H, W), non-zero = masked: events there get weight 0 and support nobody.  The stream is walked in chunks
         of ``chunk`` events; the result does not depend on it.  Returns the weights (n,), and the uint8 support too when asked.
         ValueError, before the library is reached: every refusal of the C contract, with the index of the first offending event."""
-        x, y = check_event_coords(xs, ys)
-        n = x.shape[0]
-        t = check_event_times(ts, n)
         tau, radius, full_support = check_event_support_args(tau, radius, full_support)
-        mask = check_pixel_mask(pixel_mask, (self.H, self.W))
-        chunk = check_chunk(chunk)
-        bad = event_support_first_offender(x, y, t, (self.H, self.W))
-        if bad is not None:
-            raise ValueError(bad[1])
+        x, y, t, mask, chunk = check_raw_stream(xs, ys, ts, pixel_mask, chunk, (self.H, self.W))
+        n = x.shape[0]
         weights, support = np.empty(n, dtype=np.float32), np.empty(n, dtype=np.uint8)
-        # an empty stream still reaches the library: it clears the carried state
-        for i0 in ([0] if n == 0 else range(0, n, chunk)):
-            i1 = min(n, i0 + chunk)
+        for i0, i1 in chunk_walk(n, chunk):
             self._check_data(self._lib.eincm_event_support(
                 self._ctx, x.ctypes.data + 2 * i0, y.ctypes.data + 2 * i0, t.ctypes.data + 8 * i0, i1 - i0, tau, radius, full_support,
                 None if mask is None else mask.ctypes.data, int(i0 == 0), weights.ctypes.data + 4 * i0, support.ctypes.data + i0))
@@ -1316,20 +1326,12 @@ class Engine:
         ``polarity=True``.  ``radius=0`` switches the support stage off: the weights are then 1 for kept events.  Everything else
         (stream order, times, mask, chunking, refusals) is ``event_support``'s.  Returns (keep bool (n,), weights float32 (n,)), and
         the uint8 support too when asked; the staged lists are not shortened, callers index with ``keep``."""
-        x, y = check_event_coords(xs, ys)
-        n = x.shape[0]
-        t = check_event_times(ts, n)
         refractory, tau, radius, full_support, flags = check_event_filter_args(refractory, tau, radius, full_support, polarity)
+        x, y, t, mask, chunk = check_raw_stream(xs, ys, ts, pixel_mask, chunk, (self.H, self.W))
+        n = x.shape[0]
         p = check_event_polarity(ps, n, polarity)
-        mask = check_pixel_mask(pixel_mask, (self.H, self.W))
-        chunk = check_chunk(chunk)
-        bad = event_support_first_offender(x, y, t, (self.H, self.W))
-        if bad is not None:
-            raise ValueError(bad[1])
         keep, weights, support = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.float32), np.empty(n, dtype=np.uint8)
-        # an empty stream still reaches the library: it clears the carried state
-        for i0 in ([0] if n == 0 else range(0, n, chunk)):
-            i1 = min(n, i0 + chunk)
+        for i0, i1 in chunk_walk(n, chunk):
             self._check_data(self._lib.eincm_event_filter(
                 self._ctx, x.ctypes.data + 2 * i0, y.ctypes.data + 2 * i0, t.ctypes.data + 8 * i0, None if p is None else p.ctypes.data + i0,
                 i1 - i0, refractory, tau, radius, full_support, flags, None if mask is None else mask.ctypes.data, int(i0 == 0),

@@ -1,9 +1,11 @@
 // event_support_check.cpp — the HIP-free rules of the event-support filter (csrc/eincm_event_support.h) as a
-// program of its own: the argument checks, the first refused event, the neighbour window clipped to the sensor, and the carried-time
-// rule walked chunk by chunk.  tests/test_host_event_support.py builds it with the sanitizers and compares its lines with numpy.
+// program of its own: the argument checks, the geometry of the sort by pixel (es_sort_plan; fits: every number on the way fits the
+// type it is used in), the first refused event, the neighbour window clipped to the sensor, and the carried-time rule walked chunk by
+// chunk.  tests/test_host_event_support.py builds it with the sanitizers and compares its lines with numpy.
 //
 // One case per input line:
 //   args n tau radius full_support                                   ->  args fault |
+//   plan n npix                                                      ->  plan nblk nhist ntiles passes fits |
 //   first H W carried n  x[n] y[n] t[n]                              ->  first index fault |
 //   window H W r npts  x[npts] y[npts]                               ->  window | x0 x1 y0 y1 neighbours  (per point)
 //   filter H W tau r k has_mask nchunks len[nchunks] n  x[n] y[n] t[n] mask[H W]?
@@ -39,6 +41,21 @@ int main(int argc, char** argv) {
             const double tau = num();
             const int radius = (int)num(), fs = (int)num();
             std::printf("args %d |\n", (int)es_check_args(n, tau, radius, fs));
+        } else if (tok[0] == "plan") {
+            const int64_t n = (int64_t)num(), npix = (int64_t)num();
+            const EsSortPlan p = es_sort_plan(n, npix);
+            // the same numbers in 64-bit unsigned arithmetic that cannot wrap at these sizes, and whether each fits where it is used:
+            // nblk an int and a grid, nhist the int64_t length of the histogram whose uint32_t entries sum to n, ntiles a grid, the
+            // key bits covered by the passes' shifts inside a uint32_t
+            const uint64_t un = (uint64_t)n, nblk = (un + (uint64_t)ES_SORT_BLOCK - 1) / (uint64_t)ES_SORT_BLOCK;
+            const uint64_t nhist = (uint64_t)ES_RADIX * nblk, ntiles = (nhist + (uint64_t)ES_SCAN_TILE - 1) / (uint64_t)ES_SCAN_TILE;
+            const uint64_t hist_bytes = nhist * sizeof(uint32_t);
+            const bool same = (uint64_t)p.nblk == nblk && (uint64_t)p.nhist == nhist && (uint64_t)p.ntiles == ntiles && p.nblk >= 0;
+            const bool fits = nblk <= (uint64_t)INT32_MAX && nhist <= (uint64_t)INT32_MAX && ntiles <= (uint64_t)INT32_MAX &&
+                              hist_bytes <= (uint64_t)INT64_MAX && un <= (uint64_t)UINT32_MAX && p.passes * ES_RADIX_BITS <= 32 &&
+                              (npix <= 1 || ((uint64_t)(npix - 1) >> (p.passes * ES_RADIX_BITS - 1)) <= 1u) &&
+                              nblk * (uint64_t)ES_SORT_BLOCK >= un && ntiles * (uint64_t)ES_SCAN_TILE >= nhist;
+            std::printf("plan %d %lld %lld %d %d |\n", p.nblk, (long long)p.nhist, (long long)p.ntiles, p.passes, (int)(same && fits));
         } else if (tok[0] == "first") {
             const int H = (int)num(), W = (int)num();
             const double carried = num();

@@ -71,9 +71,21 @@ def test_kernels_live_in_their_own_header_and_the_rules_in_a_hip_free_one():
     body = api.split('int eincm_event_filter(')[1].split('\n}\n')[0]
     assert 'not_in_flight(c, "eincm_event_filter")' in body and 'OneShot op(c);' in body
     assert 'c->es.' not in body                                          # the carried state is its own
-    for k in ('k_es_validate', 'k_es_hist', 'k_es_scan_tiles', 'k_es_scan', 'k_es_scatter', 'k_es_bounds', 'k_es_fill', 'k_ef_keep',
-              'k_ef_scan_tiles', 'k_ef_scan', 'k_ef_support', 'k_ef_map'):
+    for k in ('k_ef_keep', 'k_ef_scan_tiles', 'k_ef_scan', 'k_ef_support', 'k_ef_map'):
         assert re.search(r'op\.launch\(' + k + r'\b', body), k
+    # validation, the carried maps, the sort and the bounds are launched by the front end that both operators use, and only there
+    front = api.split('\nstruct StreamChunk {')[1].split('\n};\n')[0]
+    assert len(api.split('\nstruct StreamChunk {')) == 2
+    shared = ('k_es_validate', 'k_es_hist', 'k_es_scan_tiles', 'k_es_scan', 'k_es_scatter', 'k_es_bounds', 'k_es_fill')
+    for k in shared:
+        assert len(re.findall(r'op\.launch\(' + k + r'\b', front)) == 1, k
+    for entry in ('eincm_event_support', 'eincm_event_filter'):
+        b = api.split('int ' + entry + '(')[1].split('\n}\n')[0]
+        assert 'StreamChunk sc(op, ' in b and 'sc.validate(' in b and 'sc.carried_maps(' in b and 'sc.sort_and_bound()' in b, entry
+        assert b.index('OneShot op(c);') < b.index('StreamChunk sc(op, ') < b.index('op.begin()') < b.index('sc.validate(') \
+            < b.index('sc.carried_maps(') < b.index('sc.sort_and_bound()'), entry         # a refused chunk moves no carried state
+        for k in shared:
+            assert k not in b, (entry, k)
 
 
 # ---- the refusals, with a stub in the library's place ---------------------------------------------------------------------------

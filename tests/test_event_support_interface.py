@@ -51,6 +51,21 @@ def test_kernels_live_in_their_own_header_and_the_rules_in_a_hip_free_one():
     api = open(os.path.join(csrc, 'eincm_api.hip')).read()
     body = api.split('int eincm_event_support(')[1].split('\n}\n')[0]
     assert 'not_in_flight(c, "eincm_event_support")' in body and 'OneShot op(c);' in body
+    assert 'c->ef.' not in body                                          # the carried state is its own
+    # the geometry of the sort is host arithmetic: stated in the HIP-free header (where tests/host/event_support_check.cpp reaches
+    # it) and in no kernel header
+    hip_headers = [f for f in os.listdir(csrc) if f.endswith('.hip.h')]
+    assert 'eincm_event_support.hip.h' in hip_headers and 'eincm_event_filter.hip.h' in hip_headers
+    for name in ('ES_RADIX_BITS', 'ES_RADIX', 'ES_SORT_BLOCK', 'ES_SCAN_NT', 'ES_SCAN_TILE'):
+        define = r'constexpr\s+int\s+' + name + r'\s*='
+        assert len(re.findall(define, rules)) == 1, name
+        for f in hip_headers:
+            assert not re.search(define, open(os.path.join(csrc, f)).read()), (name, f)
+    for fn in ('es_sort_passes', 'es_sort_plan'):
+        define = r'inline\s+\w+\s+' + fn + r'\s*\('
+        assert len(re.findall(define, rules)) == 1, fn
+        for f in hip_headers:
+            assert not re.search(define, open(os.path.join(csrc, f)).read()), (fn, f)
 
 
 # ---- the refusals, with a stub in the library's place ---------------------------------------------------------------------------

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import _event_filter_witness as EF
+import _event_support_witness as ES
 
 pytestmark = pytest.mark.gpu
 
@@ -260,6 +261,83 @@ def test_refused_chunk_in_mid_stream_leaves_the_state_and_the_good_rest_complete
     # the carried state is what the first half left: the second half completes the unsplit result
     assert _raw(eng, *rest, *a, 0, gk[half:], gw[half:], gs[half:]) == L.OK
     _equal((gk.view(np.bool_), gw, gs), k, w, sup)
+
+
+# ---- the refusals of the chunk front end that both operators share -----------------------------------------------------------------------
+def _raw_support(eng, xs, ys, ts, tau, radius, k, mask, reset, w, sup):
+    xs, ys, ts = np.ascontiguousarray(xs, np.int16), np.ascontiguousarray(ys, np.int16), np.ascontiguousarray(ts, np.float64)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    return eng._lib.eincm_event_support(eng._ctx, ptr(xs), ptr(ys), ptr(ts), len(xs), tau, radius, k, ptr(mask), reset, ptr(w), ptr(sup))
+
+
+def _two_chunks():
+    """140 good events on 5x7 in two chunks of 70 (a chunk crosses a wave): times of step 0.25, two consecutive events per pixel (the
+    second falls inside the refractory period 0.6), pixels that move on to a neighbour.  (xs, ys, ts, both witnesses' outputs)"""
+    i = np.arange(140)
+    xs, ys, ts = ((i // 2) % 7).astype(np.int16), ((i // 14) % 5).astype(np.int16), i * 0.25
+    es = ES.support_filter(xs, ys, ts, (5, 7), 1.0, 1, 2)[:2]
+    ef = EF.event_filter(xs, ys, ts, None, (5, 7), 0.6, 1.0, 1, 2, False)[:3]
+    assert 0 < ef[0].mean() < 1 and 0 < (ef[2] > 0).mean() < 1 and 0 < (es[1] > 0).mean() < 1
+    return xs, ys, ts, es, ef
+
+
+# (which array, the event of the second chunk, the value, eincm_last_error: the format strings of eincm_api.hip's front end filled in)
+REFUSALS = {
+    'coordinate-outside': (0, 65, 7, 'event 65: (7, 4) outside the 5x7 sensor'),
+    'time-not-finite': (2, 65, np.inf, 'event 65: time inf is not finite'),
+    'time-below-predecessor': (2, 65, 33.25, 'event 65: time 33.25 is smaller than 33.5, its predecessor\'s'),
+    'time-below-carried': (2, 0, 17.0, 'event 0: time 17 is smaller than 17.25, the last time of the previous chunk'),
+}
+
+
+@pytest.mark.parametrize('fault', sorted(REFUSALS))
+def test_both_operators_refuse_a_chunk_in_the_same_words_and_keep_their_states(fault):
+    xs, ys, ts, es, ef = _two_chunks()
+    which, at, value, text = REFUSALS[fault]
+    eng, n, cut = _eng((5, 7)), 140, 70
+    sw, ss = np.empty(n, np.float32), np.empty(n, np.uint8)
+    gk, gw, gs = _outputs(n)
+    a_s, a_f = (1.0, 1, 2, None), (0.6, 1.0, 1, 2, 0, None)
+    assert _raw_support(eng, xs[:cut], ys[:cut], ts[:cut], *a_s, 1, sw[:cut], ss[:cut]) == L.OK
+    assert _raw(eng, xs[:cut], ys[:cut], ts[:cut], None, *a_f, 1, gk[:cut], gw[:cut], gs[:cut]) == L.OK
+    bad = [xs[cut:].copy(), ys[cut:].copy(), ts[cut:].copy()]
+    bad[which][at] = value
+    out_w, out_k = np.full(n - cut, -1.0, np.float32), np.full(n - cut, 7, np.uint8)
+    assert _raw_support(eng, *bad, *a_s, 0, out_w, None) == L.ERR_ARG
+    said = eng._lib.eincm_last_error(eng._ctx).decode()
+    assert _raw(eng, *bad, None, *a_f, 0, out_k, out_w, None) == L.ERR_ARG
+    assert eng._lib.eincm_last_error(eng._ctx).decode() == said == text
+    assert np.all(out_w == -1.0) and np.all(out_k == 7)
+    # neither carried state moved: the good second chunk completes the unsplit stream's bytes
+    assert _raw_support(eng, xs[cut:], ys[cut:], ts[cut:], *a_s, 0, sw[cut:], ss[cut:]) == L.OK
+    assert _raw(eng, xs[cut:], ys[cut:], ts[cut:], None, *a_f, 0, gk[cut:], gw[cut:], gs[cut:]) == L.OK
+    assert sw.tobytes() == es[0].tobytes() and ss.tobytes() == es[1].tobytes()
+    _equal((gk.view(np.bool_), gw, gs), *ef)
+
+
+# ---- the scan of the tile maxima with more than one tile per thread ----------------------------------------------------------------------
+@pytest.mark.parametrize('polarity', [False, True])
+def test_burst_of_more_than_1024_tiles_reaches_the_neighbour_through_the_scan_of_tile_maxima(polarity):
+    """One call of 1024 EF_SCAN_TILE + EF_SCAN_TILE + 5 burst events and their neighbour's one: 1026 tile maxima, so every thread of
+    k_ef_scan owns two (any shorter call leaves a thread at most one).  The burst's one kept event, at sorted position 0, reaches the
+    neighbour's search at tile 1025 only through that scan.  The expected outputs are written in closed form (the witness is a Python
+    loop per event): the burst keeps its first event, the neighbour is kept; tau twice the burst's duration: supported by the first
+    event, support 1, weight 1; tau twice the last gap: not supported.  k_es_scan instantiates the same template for uint32_t sums
+    and takes this path only from n > 2^24 events: it has no test of its own."""
+    nb = 1024 * EF_SCAN_TILE + EF_SCAN_TILE + 5
+    xs, ys, ts, ps, burst, gap = EF.long_chatter_stream(nb)
+    ps = ps.copy()
+    ps[-1] = ps[0]                                           # the neighbour has the class of the burst's one kept event
+    n = nb + 1
+    assert len(xs) == n and -(-n // EF_SCAN_TILE) == 1026
+    keep = np.zeros(n, np.uint8)
+    keep[0] = keep[-1] = 1
+    for tau, last in ((2.0 * burst, 1), (2.0 * gap, 0)):
+        sup, w = np.zeros(n, np.uint8), np.zeros(n, np.float32)
+        sup[-1], w[-1] = last, float(last)
+        got = _eng((3, 3)).event_filter(xs, ys, ts, ps, refractory=1.0, tau=tau, radius=1, full_support=1, polarity=polarity, chunk=n,
+                                        return_support=True)
+        _equal(got, keep, w, sup)
 
 
 # ---- beside the event-support filter: the same bytes at rho = 0 without the flag, and two carried states that do not touch ------------

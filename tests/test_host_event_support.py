@@ -1,6 +1,7 @@
 """The HIP-free rules of the event-support filter (csrc/eincm_event_support.h) on the CPU: the argument checks,
-the first refused event of a chunk, the neighbour window at corners, edges and inside for r = 1, 2, 3, and the carried-time rule
-walked chunk by chunk (the previous event of a neighbour: its last one in the chunk, else the carried map's).
+the geometry of the sort by pixel (es_sort_plan) up to 2^30 events and 2^24 pixels, the first refused event of a chunk, the
+neighbour window at corners, edges and inside for r = 1, 2, 3, and the carried-time rule walked chunk by chunk (the previous event of
+a neighbour: its last one in the chunk, else the carried map's).
 
 tests/host/event_support_check.cpp is built once per session with the address and undefined-behaviour sanitizers, as
 tests/test_host_plan.py builds plan_check, and run once, as a child process, over every case of this module; nothing is preloaded.
@@ -40,6 +41,23 @@ ARGS = [_args('ok', 10, 1.0, 1, 1, ARG_OK), _args('n0', 0, 0.0, 3, 48, ARG_OK), 
         _args('k0', 5, 1.0, 1, 0, ARG_FULL), _args('k9-r1', 5, 1.0, 1, 9, ARG_FULL), _args('k24-r2', 5, 1.0, 2, 24, ARG_OK),
         _args('k25-r2', 5, 1.0, 2, 25, ARG_FULL), _args('k48-r3', 5, 1.0, 3, 48, ARG_OK), _args('k49-r3', 5, 1.0, 3, 49, ARG_FULL),
         _args('n-before-tau', -1, np.nan, 0, 0, ARG_N)]
+
+
+# ---- the geometry of the sort by pixel ---------------------------------------------------------------------------------------------
+SORT_BLOCK, RADIX_BITS, SCAN_TILE = 1024, 8, 4096      # ES_SORT_BLOCK, ES_RADIX_BITS, ES_SCAN_TILE (csrc/eincm_event_support.h)
+
+
+def _plan(n, npix):
+    name = f'plan-n{n}-npix{npix}'
+    HC.add_case(CASES, name, 'plan', n, npix)
+    nblk = -(-n // SORT_BLOCK)
+    nhist = (1 << RADIX_BITS) * nblk
+    passes = next(k for k in range(1, 5) if npix <= 1 << (RADIX_BITS * k))     # the fewest 8-bit digits that tell npix keys apart
+    EXPECT[name] = (nblk, nhist, -(-nhist // SCAN_TILE), passes, 1)
+    return name
+
+
+PLANS = [_plan(n, npix) for npix in (1, 2, 256, 257, 65536, 65537, 1 << 24) for n in (0, 1, 1024, 1025, 16384, 16385, 1 << 30)]
 
 
 # ---- first offender ------------------------------------------------------------------------------------------------------------
@@ -139,6 +157,11 @@ def out(event_support_check, tmp_path_factory):
 @pytest.mark.parametrize('name', ARGS)
 def test_argument_checks(out, name):
     assert int(out[name][0][0]) == EXPECT[name]
+
+
+@pytest.mark.parametrize('name', PLANS)
+def test_sort_plan_and_that_its_numbers_fit_their_types(out, name):
+    assert tuple(int(v) for v in out[name][0]) == EXPECT[name]
 
 
 @pytest.mark.parametrize('name', FIRST)
