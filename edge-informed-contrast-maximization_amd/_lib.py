@@ -35,6 +35,8 @@ BFGS_NS = 8
 LBFGS_MAX_HISTORY = 16                                               # EINCM_LBFGS_MAX_HISTORY
 LBFGS_SCALES = {'identity': 0, 'last_pair': 1}                       # EINCM_LBFGS_SCALE_*
 MOTION_MAX_COEFFS, MOTION_NQ = 12, 12                                # EINCM_MOTION_MAX_COEFFS, EINCM_MOTION_NQ
+TA_FILL_SOURCE, TA_FILL_ZERO = 0, 1                                  # EINCM_TA_FILL_*
+TA_FILLS = {'source': TA_FILL_SOURCE, 'zero': TA_FILL_ZERO}
 
 
 class Params(C.Structure):
@@ -180,6 +182,9 @@ SIGNATURES = [
                                      C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # per-event scores: an image stack sampled at the warped events (raw addresses, as above)
     ('eincm_event_scores', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # a solved theta carried along its own flow to the next window (raw addresses, as above)
+    ('eincm_theta_advect', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                     C.c_void_p, C.c_void_p, C.c_void_p]),
     # flow errors of a batch of thetas against staged ground truth
     ('eincm_flow_eval_stage', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ('eincm_flow_errors', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(FlowErrorOut), C.c_void_p]),

@@ -46,7 +46,7 @@ except ImportError:                                  # without it the update sta
 
 from . import _lib as L
 from .engine import Engine, check_history, check_initial_scale, check_precision, check_window_size, make_params
-from .solver import ScipyMinimizeInfo, EmptyCallback, rescale_theta, _canon
+from .solver import ScipyMinimizeInfo, EmptyCallback, rescale_theta, _canon, advect_theta_pyramids, prior_transport_settings
 
 _BFGS_C1, _BFGS_C2, _BFGS_XTOL, _BFGS_AMIN, _BFGS_AMAX, _LS_MAXITER = 1e-4, 0.9, 1e-14, 1e-100, 1e100, 100
 _EXACT_UPDATE_MAX_N = 64          # up to this many unknowns the inverse-Hessian update is SciPy's own expression (two n x n products)
@@ -1003,6 +1003,16 @@ class BatchedMultipleLevelEINCMSolver:
         self.prior = [self._pyramid_from_top(top) for _ in range(self.B)]        # prior_theta_pyr per window
         self.n_batch_evals = 0
         self.n_window_evals = 0
+        # carrying the priors to the next window: off unless handover_settings asks for it
+        self.prior_transport, self._transport_kw = prior_transport_settings(hs)
+        self._untransported = None              # the handed-over thetas the held priors were carried from
+
+    def _transported(self, pyrs, **override):
+        """The B pyramids carried to the next window, one engine call per level: handover_settings' prior_* values, or
+        set_datasamples' (scalars or one per window)."""
+        kw = dict(self._transport_kw, **{k: v for k, v in override.items() if v is not None})
+        return advect_theta_pyramids(pyrs, self.sensor_size, method=self.loss_kwargs.get('scale_to_sensor_size_method', 'bilinear'),
+                                     engine=self.engine, **kw)
 
     # -- pyramids (solver.py:132-151, :350-377) ---------------------------------------------------------------------
     def _upscale(self, theta, base):
@@ -1022,10 +1032,14 @@ class BatchedMultipleLevelEINCMSolver:
         return pyr
 
     # -- staging -------------------------------------------------------------------------------------------------------
-    def set_datasamples(self, windows):
+    def set_datasamples(self, windows, prior_tau=None, prior_gain=None):
         """windows: B tuples (xs, ys, ts, edges, edge_ts), or (xs, ys, ts, edges, edge_ts, weights) with per-event weights or None
-        (Engine.set_windows): the tuples go to the engines as they are."""
+        (Engine.set_windows): the tuples go to the engines as they are.  prior_tau / prior_gain
+        (prior_transport='advect' only; scalars or one per window): tau and gain of the step that led to THESE windows, for sequences
+        with uneven spacing; the priors are carried again from the previous windows' handed-over thetas with them."""
         assert len(windows) == self.B
+        if (prior_tau is not None or prior_gain is not None) and self.prior_transport != 'advect':
+            raise ValueError("prior_tau / prior_gain need handover_settings['prior_transport'] = 'advect'")
         n_tot = max(sum(len(windows[b][0]) for b in ix) for ix in self.groups)
         R = len(np.atleast_1d(windows[0][4]))
         if not self.engines or n_tot > self._cap or R > self._cap_r:
@@ -1042,6 +1056,8 @@ class BatchedMultipleLevelEINCMSolver:
             if window is not None and eng.splat_window != window:
                 eng.set_splat_window(window)
             eng.set_windows([windows[b] for b in ix])
+        if (prior_tau is not None or prior_gain is not None) and self._untransported is not None:
+            self.prior = self._transported(self._untransported, tau=prior_tau, gain=prior_gain)
 
     def close(self):
         for eng in self.engines:
@@ -1191,5 +1207,8 @@ class BatchedMultipleLevelEINCMSolver:
                             'pre_handover_theta_pyr': opt[b], 'ho_opt_state_pyr': ho_states[b],
                             'final_handover_weight_pyr': ho_weights[b], 'final_theta_pyr': ho_opt[b]})
             self.prior[b] = dict(ho_opt[b])
+        if self.prior_transport == 'advect':
+            self._untransported = [dict(p) for p in ho_opt]
+            self.prior = self._transported(self._untransported)
         self._first = False
         return results

@@ -40,6 +40,8 @@
 #include "eincm_event_filter.hip.h"
 #include "eincm_event_scores.h"
 #include "eincm_event_scores.hip.h"
+#include "eincm_theta_advect.h"
+#include "eincm_theta_advect.hip.h"
 
 using namespace eincm;
 
@@ -2802,6 +2804,69 @@ int eincm_flow_encode(eincm_ctx* c, const double* theta, int n, int h, int w, co
     HIPCHK(c, op.sync());
     *n_bad = (int64_t)*bad;
     if (*bad) return fail(c, EINCM_ERR_ARG, "%llu pixels have a flow that is not finite or encodes outside [0, 65536)", *bad);
+    return EINCM_OK;
+}
+
+// ---- a solved theta carried along its own flow to the next window (eincm_theta_advect.hip.h) ----
+// The checks, their order and the fixed-point scales are eincm_theta_advect.h's.  Everything is a piece of the shared scratch; a piece
+// that is not wanted (the difference image and the column sums for a dense theta, the dense field, the coverage) takes none of it.
+int eincm_theta_advect(eincm_ctx* c, const double* theta, int n, int h, int w, int method, const double* tau, const double* gain, int fill,
+                       double min_coverage, double* out_theta, double* out_dense, float* out_coverage) {
+    if (!c) return EINCM_ERR_ARG;
+    const int H = c->H, W = c->W;
+    const TaArgs args{theta != nullptr, tau != nullptr, gain != nullptr, out_theta != nullptr, n, h, w, H, W, method, fill, tau, gain, min_coverage};
+    if (const TaFault f = ta_check(args))
+        return fail(c, ta_code(f), "eincm_theta_advect: %s (n = %d, theta %dx%d, sensor %dx%d, method %d, fill %d, min_coverage %g)", ta_why(f), n, h,
+                    w, H, W, method, fill, min_coverage);
+    if (const int rc = not_in_flight(c, "eincm_theta_advect")) return rc;
+    const bool full = h == H && w == W;
+    TapTables up, dn;                                     // (h, w) -> (H, W) of the expansion; (H, W) -> (h, w) of the reduction
+    if (!full) { build_taps(h, w, H, W, method, up); build_taps(H, W, h, w, method, dn); }
+    if (!ta_range_ok(theta, (size_t)n * h * w * 2, full ? 1.0 : ta_tap_gain(up, H, W)))
+        return fail(c, ta_code(TA_RANGE), "eincm_theta_advect: %s", ta_why(TA_RANGE));
+    const size_t npix = (size_t)H * W, plane = (size_t)n * npix, cells = (size_t)n * h * w;
+    std::vector<double> tg((size_t)2 * n);                // tau | gain: one upload
+    std::copy(tau, tau + n, tg.begin());
+    std::copy(gain, gain + n, tg.begin() + n);
+    OneShot op(c);
+    const auto d_th = op.piece<double2>(cells);
+    const auto d_tg = op.piece<double>(tg.size());
+    const auto d_up = op.piece<char>(up.tab.buf.size(), !full), d_dn = op.piece<char>(dn.tab.buf.size(), !full);
+    const auto d_acc = op.piece<int64_t>(plane * 3);
+    const auto d_D = op.piece<double2>(plane, !full);
+    const auto d_S = op.piece<double2>((size_t)n * H * w, !full);
+    const auto d_dense = op.piece<double2>(plane, out_dense != nullptr);
+    const auto d_cov = op.piece<float>(plane, out_coverage != nullptr);
+    const auto d_out = op.piece<double2>(cells);
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.zero(d_acc, plane * 3 * sizeof(int64_t)));
+    HIPCHK(c, op.up(d_th, theta, cells * 16));            // (host memory: the caller's, as the three outputs)
+    HIPCHK(c, op.up(d_tg, tg.data(), tg.size() * 8));     // (tg, up and dn: locals older than the frame)
+    TaTaps taps{};
+    if (!full) {
+        HIPCHK(c, op.up(d_up, up.tab.buf.data(), up.tab.buf.size()));
+        HIPCHK(c, op.up(d_dn, dn.tab.buf.data(), dn.tab.buf.size()));
+        const char* const t = d_up;
+        taps = TaTaps{Packer::i32(t, up.o_rlo), Packer::i32(t, up.o_rcnt), Packer::f64(t, 0), up.rstride,
+                      Packer::i32(t, up.o_clo), Packer::i32(t, up.o_ccnt), Packer::f64(t, up.o_cw), up.cstride};
+    }
+    const double* const d_tau = d_tg;
+    const double* const d_gain = d_tau + n;
+    const dim3 pix((unsigned)((npix + NT - 1) / NT), (unsigned)n);
+    HIPCHK(c, op.launch(k_ta_splat, pix, dim3(NT), 0, H, W, h, w, full ? 1 : 0, d_th, taps, d_tau, d_acc));
+    HIPCHK(c, op.launch(k_ta_resolve, pix, dim3(NT), 0, H, W, h, w, full ? 1 : 0, d_th, taps, d_gain, d_acc, fill == EINCM_TA_FILL_ZERO ? 1 : 0,
+                        min_coverage, d_D, d_dense, d_cov, full ? (double2*)d_out : nullptr));
+    if (!full) {
+        const char* const t = d_dn;
+        HIPCHK(c, op.launch(k_ta_reduce_cols, dim3((unsigned)(((size_t)H * w + NT - 1) / NT), (unsigned)n), dim3(NT), 0, H, W, w, d_D,
+                            Packer::i32(t, dn.o_clo), Packer::i32(t, dn.o_ccnt), Packer::f64(t, dn.o_cw), dn.cstride, d_S));
+        HIPCHK(c, op.launch(k_ta_reduce_rows, dim3((unsigned)(((size_t)h * w + NT - 1) / NT), (unsigned)n), dim3(NT), 0, H, h, w, d_S,
+                            Packer::i32(t, dn.o_rlo), Packer::i32(t, dn.o_rcnt), Packer::f64(t, 0), dn.rstride, d_th, d_gain, d_out));
+    }
+    HIPCHK(c, op.down(out_theta, d_out, cells * 16));
+    if (out_dense) HIPCHK(c, op.down(out_dense, d_dense, plane * 16));
+    if (out_coverage) HIPCHK(c, op.down(out_coverage, d_cov, plane * 4));
+    HIPCHK(c, op.sync());
     return EINCM_OK;
 }
 

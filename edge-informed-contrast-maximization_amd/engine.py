@@ -646,6 +646,41 @@ def check_ref_weights(ref_weights, n_refs):
     return w
 
 
+def check_theta_advect_args(thetas, tau, gain, method, fill, min_coverage, sensor_size):
+    """The arguments of Engine.advect_theta, checked without a GPU (csrc/eincm_theta_advect.h refuses the same).  thetas (n, h, w, 2)
+    or (h, w, 2), no finer than the sensor; tau and gain scalars or (n,), finite; method a name of _lib.METHODS; fill 'source' or
+    'zero'; min_coverage in (0, 1].  The value range of thetas is the library's check (it depends on the method's taps).  Returns
+    (thetas float64, tau (n,), gain (n,), method code, fill code, min_coverage, single)."""
+    if not isinstance(method, str) or method not in L.METHODS:
+        raise ValueError(f'method {method!r} not supported; one of {sorted(L.METHODS)}')
+    if not isinstance(fill, str) or fill not in L.TA_FILLS:
+        raise ValueError(f'fill {fill!r} not supported; one of {sorted(L.TA_FILLS)}')
+    t = np.asarray(thetas)
+    if t.dtype.kind not in 'fiu':
+        raise ValueError(f'thetas must be numeric, got {t.dtype}')
+    single = t.ndim == 3
+    t = t[None] if single else t
+    if t.ndim != 4 or t.shape[3] != 2 or min(t.shape[:3]) < 1 or t.shape[0] > 65535:
+        raise ValueError(f'thetas must be (n, h, w, 2) or (h, w, 2) with 1 <= n <= 65535, got {np.shape(thetas)}')
+    if t.shape[1] > int(sensor_size[0]) or t.shape[2] > int(sensor_size[1]):
+        raise ValueError(f'thetas {t.shape[1:3]} are finer than the sensor {tuple(int(v) for v in sensor_size)}')
+    n = t.shape[0]
+
+    def per_field(name, v):
+        a = np.asarray(v)
+        if a.dtype.kind not in 'fiu' or a.shape not in ((), (n,)):
+            raise ValueError(f'{name} must be a number or ({n},) numbers, got {a.dtype} {a.shape}')
+        a = np.ascontiguousarray(np.broadcast_to(a.astype(np.float64), (n,)))
+        if not np.isfinite(a).all():
+            raise ValueError(f'{name} must be finite')
+        return a
+    tau, gain = per_field('tau', tau), per_field('gain', gain)
+    mc = _number('min_coverage', min_coverage)
+    if not (0.0 < mc <= 1.0):
+        raise ValueError(f'min_coverage must lie in (0, 1], got {min_coverage!r}')
+    return np.ascontiguousarray(t, dtype=np.float64), tau, gain, L.METHODS[method], L.TA_FILLS[fill], mc, single
+
+
 def event_weights_refusal(precision, splat_window, sharded=False):
     """Why a weighted batch cannot be staged on an engine of this precision and splat window (not built), or
     None.  csrc/eincm_api.hip (check_staging) refuses the same."""
@@ -1409,6 +1444,31 @@ class Engine:
                 errs[f'A{thr}PE'] = float(o.anpe[k])
             res.append({'errors': errs, 'counts': {'n_ee': int(o.n_ee), 'n_pred': int(o.n_pred), 'n_gt': int(o.n_gt)}})
         return (res, emap) if ee_map else res
+
+    # -- a solved theta carried to the next window -----------------------------
+    def advect_theta(self, thetas, tau=1.0, gain=1.0, method='bilinear', fill='source', min_coverage=0.5, return_dense=False,
+                     return_coverage=False):
+        """The prior of the next window from a solved theta: every field (thetas (n, h, w, 2) or (h, w, 2), any pyramid level up to the
+        sensor's size) is scaled to the sensor with ``method``, forward-splatted along itself over ``tau`` (the time to the next
+        window's start in units of this window's normalised duration) with integer bilinear weights, resolved per pixel (a pixel with
+        coverage below ``min_coverage`` keeps its own value with fill='source', or gets 0 with fill='zero'), and the DIFFERENCE to the
+        source field is resampled back to (h, w) and added: returns gain * (theta + R(D)), so tau=0 returns gain * theta exactly.
+        ``gain``: the ratio of the two windows' durations.  tau and gain are scalars or (n,).  With return_dense / return_coverage
+        also the (n, H, W, 2) float64 dense field and the (n, H, W) float32 coverage, in that order.  The same bytes on every run
+        and in both precisions; the staged batch and its last evaluation are not touched.  ValueError: an argument that does not
+        fit, a theta value that is not finite or beyond the fixed-point range (511 px at the sensor)."""
+        t, tau, gain, mcode, fcode, mc, single = check_theta_advect_args(thetas, tau, gain, method, fill, min_coverage, (self.H, self.W))
+        n = t.shape[0]
+        out = np.empty_like(t)
+        dense = np.empty((n, self.H, self.W, 2), dtype=np.float64) if return_dense else None
+        cov = np.empty((n, self.H, self.W), dtype=np.float32) if return_coverage else None
+        self._check_data(self._lib.eincm_theta_advect(self._ctx, t.ctypes.data, n, t.shape[1], t.shape[2], mcode, tau.ctypes.data,
+                                                      gain.ctypes.data, fcode, mc, out.ctypes.data,
+                                                      None if dense is None else dense.ctypes.data,
+                                                      None if cov is None else cov.ctypes.data))
+        res = [out] + [a for a in (dense, cov) if a is not None]
+        res = [a[0] for a in res] if single else res
+        return res[0] if len(res) == 1 else tuple(res)
 
     # -- device images ----------------------------------------------------------------------------
     def iwes(self):

@@ -125,6 +125,68 @@ def rescale_theta(theta, out_hw, method):
     return np.einsum('yi,xj,dc,ijc->yxd', A_H, A_W, A_C, theta)
 
 
+PRIOR_TRANSPORTS = ('none', 'advect')
+
+
+def _transport_engine(sensor_size, engine):
+    H, W = int(sensor_size[0]), int(sensor_size[1])
+    if engine is None:
+        from .edges import _engine
+        return _engine((H, W))
+    if (engine.H, engine.W) != (H, W):
+        raise ValueError(f'sensor_size {(H, W)} is not the engine\'s {(engine.H, engine.W)}')
+    return engine
+
+
+def advect_theta(theta, sensor_size, tau=1.0, gain=1.0, method='bilinear', fill='source', min_coverage=0.5, engine=None):
+    """A solved theta ((h, w, 2), or a batch (n, h, w, 2) with scalar or per-field tau and gain) carried along its own flow to the
+    next window (Engine.advect_theta): the prior that belongs at a pixel of the next window is the flow of
+    whatever moved into it.  tau: the time from this window's start to the next one's in units of this window's normalised duration;
+    gain: the ratio of the two durations; both 1.0 for back-to-back equal windows.  engine None: the cached small context of
+    edges._engine (the operator needs only a stream and scratch)."""
+    return _transport_engine(sensor_size, engine).advect_theta(theta, tau=tau, gain=gain, method=_canon(method), fill=fill,
+                                                               min_coverage=min_coverage)
+
+
+def advect_theta_pyramids(pyrs, sensor_size, tau=1.0, gain=1.0, method='bilinear', fill='source', min_coverage=0.5, engine=None):
+    """advect_theta for every level of every pyramid of ``pyrs`` (a list of {'pyr_lvl_k': (h, w, 2)} dicts; tau and gain scalars or
+    one per pyramid): the levels of one shape travel as one batch, so a list of B like pyramids costs one engine call per level.
+    Every level is carried on its own, from its own expansion.  Returns new dicts; the arrays of ``pyrs`` are not written."""
+    eng = _transport_engine(sensor_size, engine)
+    n = len(pyrs)
+    tau = np.broadcast_to(np.asarray(tau, dtype=np.float64), (n,))
+    gain = np.broadcast_to(np.asarray(gain, dtype=np.float64), (n,))
+    by_shape = {}
+    for b, pyr in enumerate(pyrs):
+        for key, th in pyr.items():
+            by_shape.setdefault(np.shape(th), []).append((b, key))
+    out = [dict() for _ in range(n)]
+    for shape, where in by_shape.items():
+        stack = np.stack([np.asarray(pyrs[b][key], dtype=np.float64) for b, key in where])
+        moved = eng.advect_theta(stack, tau=tau[[b for b, _ in where]], gain=gain[[b for b, _ in where]], method=_canon(method), fill=fill,
+                                 min_coverage=min_coverage)
+        for (b, key), th in zip(where, moved):
+            out[b][key] = th
+    return [{key: o[key] for key in pyr} for o, pyr in zip(out, pyrs)]
+
+
+def advect_theta_pyramid(pyr, sensor_size, tau=1.0, gain=1.0, method='bilinear', fill='source', min_coverage=0.5, engine=None):
+    """advect_theta_pyramids for one pyramid: one engine call per distinct level shape."""
+    return advect_theta_pyramids([pyr], sensor_size, tau, gain, method, fill, min_coverage, engine)[0]
+
+
+def prior_transport_settings(handover_settings):
+    """What handover_settings says about carrying the prior to the next window: (transport, {tau, gain, fill, min_coverage}).  Every
+    key is optional; 'prior_transport' absent is 'none' (the prior is the handed-over theta, copied).  Motion-model coefficients
+    (minimize_motion) are not transported."""
+    hs = handover_settings or {}
+    transport = hs.get('prior_transport', 'none')
+    if transport not in PRIOR_TRANSPORTS:
+        raise ValueError(f'prior_transport {transport!r}: one of {PRIOR_TRANSPORTS}')
+    return transport, {'tau': hs.get('prior_tau', 1.0), 'gain': hs.get('prior_gain', 1.0), 'fill': hs.get('prior_fill', 'source'),
+                       'min_coverage': hs.get('prior_min_coverage', 0.5)}
+
+
 class EmptyCallback:
     """Bookkeeping interface the solver drives (callbacks.py:8-96): no collection."""
 
@@ -228,6 +290,19 @@ class MultipleLevelEINCMSolver:
         self.datasample = {}
         self._IS_FIRST_SAMPLE = True
         self.theta_opt_state_pyr, self.ho_opt_state_pyr = {}, {}
+        # carrying the prior to the next window: off unless handover_settings asks for it
+        self.prior_transport, self._transport_kw = prior_transport_settings(hs)
+        self._untransported_pyr = None      # the handed-over theta the held prior was carried from
+
+    def _transported(self, pyr, **override):
+        """``pyr`` carried to the next window with handover_settings' prior_* values (``override``: set_datasample's)."""
+        kw = dict(self._transport_kw, **{k: v for k, v in override.items() if v is not None})
+        bound = getattr(self.theta_loss_pfunc, 'keywords', None) or {}
+        sensor = self.handover_settings.get('prior_sensor_size', bound.get('sensor_size'))
+        if sensor is None:
+            raise ValueError("prior_transport='advect' needs the sensor size: bind sensor_size in theta_loss_pfunc, or set "
+                             "handover_settings['prior_sensor_size']")
+        return advect_theta_pyramid(pyr, sensor, method=bound.get('scale_to_sensor_size_method', 'bilinear'), **kw)
 
     def not_first_sample(self):
         self._IS_FIRST_SAMPLE = False
@@ -265,8 +340,16 @@ class MultipleLevelEINCMSolver:
                     options={'gtol': self.handover_opt_solver_params['options']['gtol']},
                     callback=self.handover_solver_callback)
 
-    def set_datasample(self, xs, ys, ts, edges, edge_ts):
+    def set_datasample(self, xs, ys, ts, edges, edge_ts, prior_tau=None, prior_gain=None):
+        """prior_tau / prior_gain (prior_transport='advect' only): tau and gain of the step that led to THIS window, for sequences
+        with uneven spacing; the prior is carried again from the previous window's handed-over theta with them."""
         self.datasample = {'events': {'x': xs, 'y': ys, 't': ts}, 'edges': edges, 'edge_ts': edge_ts}
+        if prior_tau is None and prior_gain is None:
+            return
+        if self.prior_transport != 'advect':
+            raise ValueError("prior_tau / prior_gain need handover_settings['prior_transport'] = 'advect'")
+        if self._untransported_pyr is not None:
+            self.prior_theta_pyr = self._transported(self._untransported_pyr, tau=prior_tau, gain=prior_gain)
 
     def _args(self):
         d = self.datasample
@@ -294,6 +377,9 @@ class MultipleLevelEINCMSolver:
                 print(f'{key} done | loss={st.fun_val:8.4f} status={st.status} n_iters={st.iter_num}')
         old_prior = dict(self.prior_theta_pyr)
         self.prior_theta_pyr = dict(self.handover_opt_theta_pyr)
+        if self.prior_transport == 'advect':
+            self._untransported_pyr = dict(self.handover_opt_theta_pyr)
+            self.prior_theta_pyr = self._transported(self._untransported_pyr)
         self._IS_FIRST_SAMPLE = False
         return {
             'prior_theta_pyr': old_prior,

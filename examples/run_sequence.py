@@ -57,9 +57,16 @@ def main():
                     help="with --sequences > 1: 'limited' keeps the newest --history pairs (s, y) instead of the inverse Hessian above 64 "
                          "unknowns, 'auto' above 1024 unknowns only: pyramids deeper than 16x16 (DESIGN.md section 19)")
     ap.add_argument('--history', type=int, default=10, help='pairs kept by --hessian limited / auto (at most 16 with --bfgs-state device)')
+    ap.add_argument('--prior-transport', choices=('none', 'advect'), default='none',
+                    help="'advect': the prior of the next window is the handed-over theta carried along its own flow "
+                         "(handover_settings['prior_transport'], DESIGN.md section 26); 'none' copies it in place, as the reference does")
+    ap.add_argument('--scene', choices=('constant', 'two-region'), default='constant',
+                    help="'two-region': a band moving at --flow-mag px per window over a background moving the other way at a quarter "
+                         'of it; the band, and so the motion boundary, is --flow-mag px further on in every window')
     ap.add_argument('overrides', nargs='*')
     a = ap.parse_args()
     cfg = config.load_config(a.config_dir, 'main', a.overrides) if a.config_dir else config._wrap(DEFAULTS)
+    cfg.handover_settings['prior_transport'] = a.prior_transport
     H, W = cfg.dataset.sensor_size
     n_lvls = cfg.n_pyr_lvls
     kw = dict(alpha=cfg.alpha, beta=cfg.beta, gamma=cfg.gamma, delta=cfg.delta, n_pyr_lvls=n_lvls, sensor_size=(H, W),
@@ -84,7 +91,8 @@ def main():
     scores = []
     for i in range(a.windows):
         # a "loader" sample: a time-sorted stream in microseconds around the evaluation window, fitted to des_n_events
-        win = synth.make_window(900 + i, (H, W), int(cfg.des_n_events * 1.3), a.refs, flow='constant', flow_mag=a.flow_mag)
+        win = synth.make_window(900 + i, (H, W), int(cfg.des_n_events * 1.3), a.refs, flow=scene_flow(a.scene, i, a.flow_mag, H, W),
+                                flow_mag=a.flow_mag)
         t_us = 1_000_000.0 * (i + win['ts'])
         sl, deficiency = staging.select_events(t_us, 1_000_000.0 * i, 1_000_000.0 * (i + 1), cfg.des_n_events, True)
         sample = {'events': {'x': win['xs'][sl], 'y': win['ys'][sl], 't': t_us[sl]},
@@ -99,8 +107,9 @@ def main():
         ev, _ = evaluation.evaluate_theta_array(Theta, xs, ys, ts, edges, edge_ts, win['flow_gt'], cfg.alpha, cfg.beta, cfg.gamma, cfg.delta,
                                                 (H, W), evaluation.make_event_mask(xs, ys, (H, W)), precision=a.precision)
         n_it = sum(st.iter_num for st in out['theta_opt_state_pyr'].values())
+        n_ev = sum(st.num_fun_eval for st in out['theta_opt_state_pyr'].values())
         ho = {k: round(float(v), 3) for k, v in out['final_handover_weight_pyr'].items() if k in out['ho_opt_state_pyr']}
-        print(f'window {i}: {n_it} BFGS iterations in {t_solve*1e3:.1f} ms | loss {ev["loss"]:.4f} FWL {ev["fwl"]:.4f} AEE {ev["AEE"]:.3f} '
+        print(f'window {i}: {n_it} BFGS iterations, {n_ev} evaluations in {t_solve*1e3:.1f} ms | loss {ev["loss"]:.4f} FWL {ev["fwl"]:.4f} AEE {ev["AEE"]:.3f} '
               f'A3PE {ev["A3PE"]:.1f}% | solved handover weights {ho}')
         scores.append((ev['fwl'], ev['AEE'], t_solve))
     s = np.array(scores)
@@ -108,9 +117,21 @@ def main():
     losses.clear_engine_cache()
 
 
-def stage_window(cfg, seed, i, refs, flow_mag, H, W):
+def scene_flow(scene, i, flow_mag, H, W):
+    """make_window's ``flow`` for window i of a sequence: 'constant', or the two-region field whose band has moved on by i windows."""
+    if scene == 'constant':
+        return 'constant'
+    left = 0.15 * W + i * flow_mag                                      # the band is a quarter of the sensor wide
+    xs = np.arange(W)
+    band = (xs >= left) & (xs < left + 0.25 * W)
+    flow = np.zeros((H, W, 2))
+    flow[..., 0] = np.where(band, flow_mag, -0.25 * flow_mag)[None, :]
+    return flow
+
+
+def stage_window(cfg, seed, i, refs, flow_mag, H, W, scene='constant'):
     """One "loader" sample of a sequence, staged like exp_mgr does (time-normalised, fitted to des_n_events)."""
-    win = synth.make_window(seed, (H, W), int(cfg.des_n_events * 1.3), refs, flow='constant', flow_mag=flow_mag)
+    win = synth.make_window(seed, (H, W), int(cfg.des_n_events * 1.3), refs, flow=scene_flow(scene, i, flow_mag, H, W), flow_mag=flow_mag)
     t_us = 1_000_000.0 * (i + win['ts'])
     sl, _ = staging.select_events(t_us, 1_000_000.0 * i, 1_000_000.0 * (i + 1), cfg.des_n_events, True)
     sample = {'events': {'x': win['xs'][sl], 'y': win['ys'][sl], 't': t_us[sl]},
@@ -138,7 +159,7 @@ def run_batched(a, cfg, H, W, n_lvls):
     print(f'{B} sequences side by side, sensor {H}x{W}, {cfg.des_n_events} events/window, R={a.refs}')
     scores = []
     for i in range(a.windows):
-        staged = [stage_window(cfg, 900 + 100 * b + i, i, a.refs, a.flow_mag + 0.5 * b, H, W) for b in range(B)]
+        staged = [stage_window(cfg, 900 + 100 * b + i, i, a.refs, a.flow_mag + 0.5 * b, H, W, a.scene) for b in range(B)]
         bs.set_datasamples([st for st, _ in staged])
         t0 = time.perf_counter()
         outs = bs.solve()

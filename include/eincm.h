@@ -32,7 +32,8 @@ extern "C" {
                                *    inverse Hessian), eincm_set_motion_model, eincm_loss_grad_motion, eincm_motion_field (parametric motion-field models),
                                *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels), eincm_set_windows_weighted (per-event weights),
                                *    eincm_event_support (the event-support filter), eincm_event_filter (the refractory and polarity-aware
-                               *    filter), eincm_event_scores (an image stack sampled at the warped events) */
+                               *    filter), eincm_event_scores (an image stack sampled at the warped events), eincm_theta_advect (a solved theta
+                               *    carried along its own flow to the next window) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -552,6 +553,27 @@ int eincm_flow_decode(eincm_ctx* ctx, const uint16_t* flow16, int n, double* flo
  * Channel 2: 0, or valid[n][H][W] != 0 where valid is not NULL.  *n_bad: pixels with a value that is not finite or codes outside
  * [0, 65536) (stored as 0); if any, EINCM_ERR_ARG.  1 <= n <= 65535. */
 int eincm_flow_encode(eincm_ctx* ctx, const double* theta, int n, int h, int w, const uint8_t* valid, uint16_t* out, int64_t* n_bad);
+
+/* ---- A solved theta carried along its own flow to the next window ------------------------------------------
+ * theta (n, h, w, 2) double, h <= H, w <= W, with tau[n] and gain[n].  Per field: Theta = theta scaled to the sensor (theta itself
+ * where (h, w) == (H, W), else eincm_flow_errors' tap sums for `method`); source pixel p lands at q = p + Theta(p) tau and deposits
+ * Q = llrint(Theta 2^13) into the four pixels around q with integer bilinear weights (two 10-bit fractions; the four sum to 2^20) by
+ * 64-bit integer atomics: taps outside the sensor are dropped, a source whose q is not finite or outside (-1, W) x (-1, H) deposits
+ * nothing.  Coverage c = sum of weights 2^-20.  Where c >= min_coverage the difference D = (sum w Q / sum w) 2^-13 - Q(Theta(p)) 2^-13;
+ * elsewhere D = 0 (EINCM_TA_FILL_SOURCE) or -Theta(p) (EINCM_TA_FILL_ZERO).  out_theta (n, h, w, 2) = gain (theta + R(D)), R the
+ * separable resampling (H, W) -> (h, w) with eincm_resample_matrix's weights for `method`, columns then rows, as ordered float64 sums
+ * (the identity for a dense theta).  So tau = 0 returns gain theta and a uniform field returns gain times itself, exactly.
+ * out_dense (n, H, W, 2) double = Theta + D and out_coverage (n, H, W) float = c are optional (NULL: not computed, no scratch).
+ * Float64 and integer arithmetic of its own: the same bytes on every run and in fp32 and EINCM_CF_FP64 contexts; nothing staged or
+ * evaluated is touched.  EINCM_ERR_ARG, in this order: a NULL theta, tau, gain or out_theta; n outside 1..65535; h or w outside
+ * 1..H / 1..W; a sensor of more than 2^21 pixels; an unknown method; an unknown fill; a tau or gain that is not finite; min_coverage
+ * outside (0, 1]; a theta value that is not finite or with |theta| L > 511, L = the largest product of the absolute row and column
+ * tap sums (1 for bilinear and for a dense theta).  EINCM_ERR_STATE (after the cheap checks, before the value range): an evaluation
+ * is in flight. */
+#define EINCM_TA_FILL_SOURCE 0
+#define EINCM_TA_FILL_ZERO   1
+int eincm_theta_advect(eincm_ctx* ctx, const double* theta, int n, int h, int w, int method, const double* tau, const double* gain, int fill,
+                       double min_coverage, double* out_theta, double* out_dense, float* out_coverage);
 
 /* ---- Flow errors of a batch of solved thetas -------------------------------------------------------------
  * sparse_flow_error (flow_eval.py:14-76) on per_pix_theta_to_flow (theta_utils.py:40-73) of every window of a batch: stage the ground
