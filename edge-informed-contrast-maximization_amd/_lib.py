@@ -37,6 +37,7 @@ LBFGS_SCALES = {'identity': 0, 'last_pair': 1}                       # EINCM_LBF
 MOTION_MAX_COEFFS, MOTION_NQ = 12, 12                                # EINCM_MOTION_MAX_COEFFS, EINCM_MOTION_NQ
 TA_FILL_SOURCE, TA_FILL_ZERO = 0, 1                                  # EINCM_TA_FILL_*
 TA_FILLS = {'source': TA_FILL_SOURCE, 'zero': TA_FILL_ZERO}
+RS_MAX_MODELS, RS_EXCLUDE_SELF = 8, 1                                # EINCM_RS_MAX_MODELS, EINCM_RS_EXCLUDE_SELF
 
 
 class Params(C.Structure):
@@ -182,6 +183,9 @@ SIGNATURES = [
                                      C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # per-event scores: an image stack sampled at the warped events (raw addresses, as above)
     ('eincm_event_scores', C.c_int, [_P, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the E-step of a motion segmentation: those scores normalised over the models of a group (raw addresses)
+    ('eincm_event_responsibilities', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     # a solved theta carried along its own flow to the next window (raw addresses, as above)
     ('eincm_theta_advect', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

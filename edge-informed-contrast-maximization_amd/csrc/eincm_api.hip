@@ -40,6 +40,8 @@
 #include "eincm_event_filter.hip.h"
 #include "eincm_event_scores.h"
 #include "eincm_event_scores.hip.h"
+#include "eincm_responsibilities.h"
+#include "eincm_responsibilities.hip.h"
 #include "eincm_theta_advect.h"
 #include "eincm_theta_advect.hip.h"
 
@@ -2231,6 +2233,77 @@ int eincm_event_scores(eincm_ctx* c, const float* images, const double* ref_weig
                         d_s, d_q));
     HIPCHK(c, op.down(scores, d_s, (size_t)n_out * sizeof(float)));
     if (selfs) HIPCHK(c, op.down(selfs, d_q, (size_t)n_out * sizeof(float)));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+// The E-step of a segmentation into n_models motions (eincm_responsibilities.hip.h): the scores of
+// eincm_event_scores' combined form, normalised over the models of a group on the device.  The checks and the layout are
+// eincm_responsibilities.h's.
+int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images, const double* ref_weights, const float* const* weights_in,
+                                 const double* prior, uint32_t flags, float* weights_out, uint8_t* labels, double* mass,
+                                 int64_t* n_unsupported) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    bool masked = false;
+    for (int b = 0; c->staged && b < g.B && b < 64; ++b) masked = masked || !((c->eval_wmask >> b) & 1ull);
+    const RsState st{{!c->fl.idle(), weights_out || labels || mass || n_unsupported, c->staged, c->have_eval, c->fp64, c->splat_size,
+                      c->sharded_staging || c->constants_pending, images != nullptr, masked},
+                     c->staged ? g.B : 0, c->win_events.data()};
+    if (const RsFault f = rs_check(st, n_models, ref_weights, g.R, prior))
+        return fail(c, rs_code(f), "eincm_event_responsibilities: %s", rs_why(f));
+    { const int rc = ensure_theta_image(c); if (rc) return rc; }
+    const int B = g.B, R = g.R, K = n_models, G = B / K;
+    const int64_t* ne = c->win_events.data();
+    const int64_t n_events = rs_weights_total(ne, B), n_labels = rs_labels_total(ne, B, K);
+    if (n_events == 0) return EINCM_OK;
+    int64_t n_max = 0;
+    for (int b = 0; b < B; ++b) n_max = std::max(n_max, ne[b]);
+    const size_t n_blk = (size_t)((n_max + NT - 1) / NT), stack = (size_t)B * R * g.H * g.W;
+    bool any_w = false;
+    for (int b = 0; (flags & EINCM_RS_EXCLUDE_SELF) && weights_in && b < B; ++b) any_w = any_w || (weights_in[b] && ne[b] > 0);
+    OneShot op(c);
+    const auto d_off = op.piece<int64_t>((size_t)B + 1);
+    const auto d_img = op.piece<float>(stack, images != nullptr);
+    const auto d_rw = op.piece<float>((size_t)R);
+    const auto d_pi = op.piece<float>((size_t)B);
+    const auto d_win = op.piece<float>((size_t)n_events, any_w);
+    const auto d_has = op.piece<uint8_t>((size_t)B, any_w);
+    const auto d_wout = op.piece<float>((size_t)n_events, weights_out != nullptr);
+    const auto d_lab = op.piece<uint8_t>((size_t)n_labels, labels != nullptr);
+    const auto d_part = op.piece<double>((size_t)B * n_blk, mass != nullptr);
+    const auto d_mass = op.piece<double>((size_t)B, mass != nullptr);
+    const auto d_uns = op.piece<unsigned long long>((size_t)G, n_unsupported != nullptr);
+    int64_t* h_off = op.host_buf<int64_t>((size_t)B + 1);                // d_off, d_rw, d_pi and d_has go up from these
+    float* h_rw = op.host_buf<float>((size_t)R);
+    float* h_pi = op.host_buf<float>((size_t)B);
+    uint8_t* h_has = op.host_buf<uint8_t>((size_t)B);
+    for (int b = 0; b <= B; ++b) h_off[b] = rs_weights_offset(ne, b);
+    for (int r = 0; r < R; ++r) h_rw[r] = (float)ref_weights[r];
+    for (int b = 0; b < B; ++b) h_pi[b] = prior ? (float)prior[b] : 1.0f;
+    for (int b = 0; b < B; ++b) h_has[b] = any_w && weights_in[b] && ne[b] > 0;
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)));
+    if (images) HIPCHK(c, op.up(d_img, images, stack * sizeof(float)));  // (host memory: the caller's, as weights_in and the outputs)
+    HIPCHK(c, op.up(d_rw, h_rw, (size_t)R * sizeof(float)));
+    HIPCHK(c, op.up(d_pi, h_pi, (size_t)B * sizeof(float)));
+    if (any_w) {
+        HIPCHK(c, op.up(d_has, h_has, (size_t)B));
+        for (int b = 0; b < B; ++b)
+            if (h_has[b]) HIPCHK(c, op.up((float*)d_win + h_off[b], weights_in[b], (size_t)ne[b] * sizeof(float)));
+    }
+    if (n_unsupported) HIPCHK(c, op.zero(d_uns, (size_t)G * sizeof(unsigned long long)));
+    const float* F = images ? (const float*)d_img : (const float*)c->d_iwe;
+    const dim3 grid((unsigned)n_blk, (unsigned)G);
+    HIPCHK(c, op.launch(rs_kernel(K), grid, dim3(NT), 0, g, d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F, d_rw,
+                        d_win, d_has, d_pi, flags, d_wout, d_lab, d_part, d_uns));
+    if (mass) {
+        HIPCHK(c, op.launch(k_rs_mass, dim3((unsigned)((B + NT - 1) / NT)), dim3(NT), 0, B, d_off, d_part, (int64_t)n_blk, d_mass));
+        HIPCHK(c, op.down(mass, d_mass, (size_t)B * sizeof(double)));
+    }
+    if (weights_out) HIPCHK(c, op.down(weights_out, d_wout, (size_t)n_events * sizeof(float)));
+    if (labels) HIPCHK(c, op.down(labels, d_lab, (size_t)n_labels));
+    if (n_unsupported) HIPCHK(c, op.down(n_unsupported, d_uns, (size_t)G * sizeof(int64_t)));
     HIPCHK(c, op.sync());
     return EINCM_OK;
 }

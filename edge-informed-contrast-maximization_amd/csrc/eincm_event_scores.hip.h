@@ -16,6 +16,37 @@
 
 namespace eincm {
 
+// One (event, reference time) cell: the warp, the nine tap weights and the two sums s and self in the order stated above, both from +0.
+// F is the image of that (window, r).  Shared by k_event_scores and k_responsibilities (eincm_responsibilities.hip.h), so that both
+// have the same operations in the same order: the same bits.
+__device__ __forceinline__ void sc_event_ref(const Geom& g, int x, int y, double2 v, double dt, const float* __restrict__ F, float& s_out,
+                                             float& q_out)
+{
+#pragma clang fp contract(off)
+    int irx, iry; float fx, fy;
+    warp_axis(x, v.x, dt, irx, fx);
+    warp_axis(y, v.y, dt, iry, fy);
+    f2v km, k0, kp;                                  // .x = x-axis weight, .y = y-axis weight (carries the 1/(2 pi))
+    taps3x2(fx, fy, INV_2PI, km, k0, kp);
+    const float kx[3] = {km.x, k0.x, kp.x}, ky[3] = {km.y, k0.y, kp.y};
+    const int sx = clamp_far(irx), sy = clamp_far(iry);
+    float s = 0.0f, q = 0.0f;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy) {
+        const int gy = wrap_drop(sy - 1 + dy, g.H);
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int gx = wrap_drop(sx - 1 + dx, g.W);
+            if (gx >= 0 && gy >= 0) {
+                const float k = ky[dy] * kx[dx];
+                s = fmaf(k, F[(size_t)gy * g.W + gx], s);
+                q = fmaf(k, k, q);
+            }
+        }
+    }
+    s_out = s; q_out = q;
+}
+
 // One thread per event, the Theta pair loaded once (as k_warp_events), a loop over the reference times in the thread.  grid
 // (ceil(max_b n_b / NT), B): blockIdx.y is the window.  (One grid row per reference time, so that a workgroup stays inside one image,
 // was measured and not kept: 2 to 7 % slower on every batch of profiles/event_scores.md; the combined output
@@ -40,29 +71,8 @@ __global__ __launch_bounds__(NT) void k_event_scores(Geom g, const int64_t* __re
     const int64_t base = e0 * (rw ? 1 : g.R);
     float S = 0.0f, Q = 0.0f;                        // the combined form's sums over r
     for (int r = 0; r < g.R; ++r) {
-        const double dt = t - edge_ts[win * g.R + r];
-        int irx, iry; float fx, fy;
-        warp_axis(x, v.x, dt, irx, fx);
-        warp_axis(y, v.y, dt, iry, fy);
-        f2v km, k0, kp;                              // .x = x-axis weight, .y = y-axis weight (carries the 1/(2 pi))
-        taps3x2(fx, fy, INV_2PI, km, k0, kp);
-        const float kx[3] = {km.x, k0.x, kp.x}, ky[3] = {km.y, k0.y, kp.y};
-        const int sx = clamp_far(irx), sy = clamp_far(iry);
-        const float* __restrict__ F = images + ((size_t)win * g.R + r) * npix;
-        float s = 0.0f, q = 0.0f;
-#pragma unroll
-        for (int dy = 0; dy < 3; ++dy) {
-            const int gy = wrap_drop(sy - 1 + dy, g.H);
-#pragma unroll
-            for (int dx = 0; dx < 3; ++dx) {
-                const int gx = wrap_drop(sx - 1 + dx, g.W);
-                if (gx >= 0 && gy >= 0) {
-                    const float k = ky[dy] * kx[dx];
-                    s = fmaf(k, F[(size_t)gy * g.W + gx], s);
-                    q = fmaf(k, k, q);
-                }
-            }
-        }
+        float s, q;
+        sc_event_ref(g, x, y, v, t - edge_ts[win * g.R + r], images + ((size_t)win * g.R + r) * npix, s, q);
         if (rw) {
             const float w = rw[r];
             S = S + w * s;

@@ -617,6 +617,52 @@ def event_scores_layout(n_events, n_refs, combined):
     return offsets, lengths.astype(np.int64), int(lengths.sum())
 
 
+def event_responsibilities_layout(n_events, n_models):
+    """(weight offsets (B,), weight total, label offsets (G,), label lengths (G,), label total) of eincm_event_responsibilities
+    (csrc/eincm_responsibilities.h: rs_weights_offset, rs_weights_total, rs_labels_offset, rs_group_events, rs_labels_total, restated;
+    tests/test_responsibilities_interface.py compares the two): window b's block of ``weights_out`` is n_events[b] floats, group g's
+    block of ``labels`` one byte per event of its first window, each kind one block after the other."""
+    n = np.asarray(n_events, dtype=np.int64).reshape(-1)
+    K = int(n_models)
+    w_off = np.concatenate([[0], np.cumsum(n)[:-1]]).astype(np.int64) if n.size else np.zeros(0, np.int64)
+    lab_len = n[:(n.size // K) * K:K].astype(np.int64)
+    lab_off = np.concatenate([[0], np.cumsum(lab_len)[:-1]]).astype(np.int64) if lab_len.size else np.zeros(0, np.int64)
+    return w_off, int(n.sum()), lab_off, lab_len, int(lab_len.sum())
+
+
+RS_OUTPUTS = ('weights', 'labels', 'mass', 'n_unsupported')
+
+
+def check_responsibility_args(n_models, n_events, prior, want):
+    """The arguments of Engine.event_responsibilities that csrc/eincm_responsibilities.h refuses too, checked without a GPU: n_models
+    within 1 .. RS_MAX_MODELS and dividing the batch, equal event counts inside a group, prior None or (B,) finite and >= 0 as float32
+    with a positive sum in every group, want a non-empty subset of RS_OUTPUTS.  Returns (n_models, prior float64 or None, want)."""
+    if isinstance(n_models, bool) or not isinstance(n_models, (int, np.integer)) or not 1 <= int(n_models) <= L.RS_MAX_MODELS:
+        raise ValueError(f'n_models must be an integer within 1 .. {L.RS_MAX_MODELS}, got {n_models!r}')
+    K = int(n_models)
+    n = np.asarray(n_events, dtype=np.int64).reshape(-1)
+    if n.size % K:
+        raise ValueError(f'the {n.size} staged windows are not a whole number of groups of {K} models')
+    if n.size and (n.reshape(-1, K) != n.reshape(-1, K)[:, :1]).any():
+        raise ValueError('the windows of a group must have equal numbers of events (they are one event list under several motions)')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in RS_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a non-empty choice of {RS_OUTPUTS} without repeats, got {want!r}')
+    if prior is not None:
+        p = np.asarray(prior)
+        if p.dtype.kind not in 'fiub' or p.shape != (n.size,):
+            raise ValueError(f'prior must be ({n.size},) numbers, one per staged window, got {p.dtype} {p.shape}')
+        prior = np.ascontiguousarray(p, dtype=np.float64)
+        with np.errstate(over='ignore'):
+            p32 = prior.astype(np.float32)
+        if not (np.isfinite(prior).all() and np.isfinite(p32).all()) or (prior < 0).any():
+            raise ValueError('prior must be finite and >= 0')
+        s = p32.reshape(-1, K).sum(axis=1, dtype=np.float32) if n.size else np.ones(0, np.float32)
+        if not (np.isfinite(s).all() and (s > 0).all()):
+            raise ValueError("every group's prior must have a positive (finite) sum")
+    return K, prior, want
+
+
 def check_score_images(images, n_windows, n_refs, sensor_size):
     """The caller's image stack of Engine.event_scores as contiguous float32 (B,R,H,W); (R,H,W) stands for it when B == 1.  None stays
     None (the IWEs of the last evaluation).  Anything else is a ValueError, raised before any library call."""
@@ -1544,6 +1590,46 @@ class Engine:
                 q = selfs[off[b]:off[b] + length[b]].reshape(shape)
                 s = s - q if ws[b] is None else s - ws[b] * q
             out.append(np.ascontiguousarray(s, dtype=np.float32))
+        return out
+
+    def event_responsibilities(self, n_models, images=None, ref_weights=None, prior=None, exclude_self=True,
+                               want=('weights', 'labels', 'mass')):
+        """The E-step of a segmentation into ``n_models`` motions, one device operation: the staged batch is
+        G = B / n_models groups of n_models consecutive windows that hold the same events under different motions (and complementary
+        weights); every event's combined scores (event_scores with ref_weights) under the last evaluation are normalised over the
+        models of its group.  images as event_scores.  ref_weights: (R,) finite, default multi_ref_weights(R).  prior: None (ones) or
+        (B,) numbers >= 0, positive in sum per group.  exclude_self: the leave-one-out score, with the weights ``set_windows`` was
+        handed.  want: which of RS_OUTPUTS to fetch.  Returns a dict of those: 'weights' a list of B float32 (n_b,) arrays, what
+        set_windows takes back; 'labels' a list of G uint8 (n_g,) arrays, the lowest model with the largest share; 'mass' (G,
+        n_models) float64, each window's sum of weights; 'n_unsupported' (G,) int64, the events no model supports (they get the
+        prior's shares)."""
+        K, pi, want = check_responsibility_args(n_models, self.n_events if self.B else [], prior, want)
+        imgs = check_score_images(images, self.B, self.R, (self.H, self.W))
+        rw = check_ref_weights(multi_ref_weights(self.R) if ref_weights is None else ref_weights, self.R)
+        ws = getattr(self, '_staged_weights', None)
+        if exclude_self and (ws is None or len(ws) != self.B):
+            raise ValueError('exclude_self needs the weights the batch was staged with, and this engine does not hold them: stage with set_windows')
+        B, G = self.B, self.B // K
+        w_off, w_total, lab_off, lab_len, lab_total = event_responsibilities_layout(self.n_events if B else [], K)
+        weights = np.empty(w_total, dtype=np.float32) if 'weights' in want else None
+        labels = np.empty(lab_total, dtype=np.uint8) if 'labels' in want else None
+        mass = np.zeros(B, dtype=np.float64) if 'mass' in want else None                # (a batch without events writes nothing)
+        n_uns = np.zeros(G, dtype=np.int64) if 'n_unsupported' in want else None
+        wp = None
+        if exclude_self and any(w is not None and w.size for w in ws):
+            wp = (C.c_void_p * B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
+        addr = lambda a: None if a is None else a.ctypes.data
+        self._check(self._lib.eincm_event_responsibilities(self._ctx, K, addr(imgs), addr(rw), wp, addr(pi), L.RS_EXCLUDE_SELF if exclude_self else 0,
+                                                           addr(weights), addr(labels), addr(mass), addr(n_uns)))
+        out = {}
+        if weights is not None:
+            out['weights'] = [weights[w_off[b]:w_off[b] + int(self.n_events[b])] for b in range(B)]
+        if labels is not None:
+            out['labels'] = [labels[lab_off[g]:lab_off[g] + lab_len[g]] for g in range(G)]
+        if mass is not None:
+            out['mass'] = mass.reshape(G, K)
+        if n_uns is not None:
+            out['n_unsupported'] = n_uns
         return out
 
     def scaled_theta(self):

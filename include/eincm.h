@@ -33,7 +33,8 @@ extern "C" {
                                *    eincm_loss_grad_motion_fused (the model evaluated inside the event kernels), eincm_set_windows_weighted (per-event weights),
                                *    eincm_event_support (the event-support filter), eincm_event_filter (the refractory and polarity-aware
                                *    filter), eincm_event_scores (an image stack sampled at the warped events), eincm_theta_advect (a solved theta
-                               *    carried along its own flow to the next window) */
+                               *    carried along its own flow to the next window), eincm_event_responsibilities (those scores normalised over
+                               *    the models of a group: the E-step of a motion segmentation) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -281,6 +282,41 @@ int eincm_get_warped_events(eincm_ctx* ctx, int window, double* warped_xs, doubl
  * EINCM_ERR_STATE images == NULL after an evaluation that left windows out (eincm_loss_grad_masked: their IWEs are not current).  A
  * batch with no events at all is valid and writes nothing; a window without events has an empty block. */
 int eincm_event_scores(eincm_ctx* ctx, const float* images, const double* ref_weights, float* scores, float* selfs);
+
+/* The E-step of a segmentation into several motions.  The staged batch of B windows is G = B / n_models groups
+ * of K = n_models consecutive windows; window b = g * K + l is model l of group g.  The windows of a group have equal n_events and
+ * event i of each of them is one event seen under K motions (each window's own staged events are read: nothing else is assumed about
+ * them being shared).  Under the last evaluation's Theta, as eincm_event_scores, and for event i of group g:
+ *     s_l, q_l  the combined score and self of eincm_event_scores for window g * K + l with omega = ref_weights: the same operations
+ *               in the same order, the same bits
+ *     a_l  = s_l - w_l * q_l with EINCM_RS_EXCLUDE_SELF (w_l = weights_in[b][i]; a NULL entry or a NULL array is ones), else s_l
+ *     a_l  = a_l > 0 ? a_l : +0          (a NaN becomes +0)
+ *     p_l  = (float)prior[b] * a_l,      T = sum_l p_l in ascending l from +0
+ *     T not > 0 or not finite: the event is unsupported, p_l = (float)prior[b] and T is summed again
+ *     w'_l = p_l / T
+ * in fp32 without contraction, every operation rounded once; the division is correctly rounded (the plain `/` of a build without
+ * fast-math flags, which emits v_div_scale / v_div_fmas / v_div_fixup).
+ *   images        as eincm_event_scores: (B, n_refs, H, W) floats, or NULL for the IWEs of the last evaluation
+ *   ref_weights   n_refs finite doubles (required)
+ *   weights_in    NULL, or B host pointers, each NULL or n_events[b] floats: what the windows were staged with
+ *   prior         NULL (ones) or B doubles pi, each finite and >= 0 as a float, every group's float sum positive and finite
+ *   flags         EINCM_RS_EXCLUDE_SELF or 0; other bits are reserved
+ *   weights_out   NULL, or window b's block of n_events[b] floats w', the blocks one after another: what
+ *                 eincm_set_windows_weighted takes back
+ *   labels        NULL, or one byte per event of a group, group after group: the lowest l with the largest p_l
+ *   mass          NULL, or B doubles: sum_i w' in fp64 in one fixed order (64 events of a wave by halving, the four waves of a
+ *                 256-event block in ascending order, the blocks in ascending order from +0); no float atomics, the same bytes on every run
+ *   n_unsupported NULL, or G exact counts
+ * Refused before anything is written, in this order: EINCM_ERR_STATE an evaluation in flight; EINCM_ERR_ARG all four outputs NULL;
+ * EINCM_ERR_STATE nothing staged or no evaluation yet; EINCM_ERR_UNSUPPORTED an EINCM_CF_FP64 context, a splat window other than 3,
+ * an event-sharded staging; EINCM_ERR_ARG n_models outside 1 .. EINCM_RS_MAX_MODELS, B not a multiple of n_models, unequal n_events
+ * inside a group, ref_weights NULL or not finite, a bad prior; EINCM_ERR_STATE images == NULL after an evaluation that left windows
+ * out.  A batch with no events at all is valid and writes nothing. */
+#define EINCM_RS_MAX_MODELS   8
+#define EINCM_RS_EXCLUDE_SELF 1u   /* flags: leave the event's own share out of its score (the leave-one-out score against the IWE) */
+int eincm_event_responsibilities(eincm_ctx* ctx, int n_models, const float* images, const double* ref_weights,
+                                 const float* const* weights_in, const double* prior, uint32_t flags,
+                                 float* weights_out, uint8_t* labels, double* mass, int64_t* n_unsupported);
 
 /* compute_weights_for_multi_reference (losses.py:39-46) */
 int eincm_multi_ref_weights(int n_refs, double* w);
