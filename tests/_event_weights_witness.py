@@ -129,12 +129,19 @@ def loss_and_grad(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, 
     return float(val.detach()), th.grad.numpy().copy(), G, I, terms
 
 
-def loss_and_grad_Theta(Theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, weights=None):
-    """(value, dL/dTheta (H,W,2)) on a full-resolution Theta: what a motion model's gradient is projected from."""
+def loss_and_grad_Theta(Theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, weights=None, contrast_kind=0,
+                        correlation_kind=0, tile=WIT.DEFAULT_TILE, full=False):
+    """(value, dL/dTheta (H,W,2)) on a full-resolution Theta: what a motion model's gradient is projected from.
+    full: (value, dL/dTheta, dL/dIWE (R,H,W), IWEs (R,H,W), terms), as loss_and_grad returns them."""
     Th = torch.tensor(np.asarray(Theta, dtype=np.float64), requires_grad=True)
-    val = loss_from_Theta(Th, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, weights)
+    imgs, terms = [], {}
+    val = loss_from_Theta(Th, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, weights, contrast_kind, correlation_kind,
+                          tile, imgs, terms)
     val.backward()
-    return float(val.detach()), Th.grad.numpy().copy()
+    if not full:
+        return float(val.detach()), Th.grad.numpy().copy()
+    return (float(val.detach()), Th.grad.numpy().copy(), np.stack([i.grad.numpy() for i in imgs]),
+            np.stack([i.detach().numpy() for i in imgs]), terms)
 
 
 def loss_value(theta, xs, ys, ts, edges, edge_ts, alpha, beta, gamma, delta, cur_pyr_lvl, A_H, A_W, weights=None, **kw):

@@ -9,7 +9,6 @@ the other theta modes, the accessors, every refusal and a lockstep solve.  Batch
 a test says otherwise; scenes and coefficients: tests/_motion_cases.py."""
 import ctypes as C
 import importlib
-import math
 
 import numpy as np
 import pytest
@@ -17,8 +16,8 @@ import torch
 from scipy.optimize import minimize
 
 from oracle import eincm_oracle as O
-import _launch_policy_witness as LP
 import _motion_cases as MC
+from _motion_bounds import moment_bound, slots_per_window
 import _splat_window_witness as SW
 
 pytestmark = pytest.mark.gpu
@@ -31,7 +30,6 @@ synth = importlib.import_module(pkg + '.synth')
 L = importlib.import_module(pkg + '._lib')
 
 A, B_ = 20.0, 35.0
-U = 2.0 ** -53
 MASK = np.array([1, 0, 1], dtype=np.uint8)
 ON = [0, 2]
 # sensor size -> events per window: one partial tile (wide) / four tiles, three partial / six full tiles / a tile of two gather segments
@@ -68,37 +66,7 @@ def params(gamma=0.0, delta=0.0, lvl=1, ck=0, rk=0, full_aux=False):
     return engine.make_params(A, B_, gamma, delta, lvl, 'bilinear', ck, full_aux=full_aux, correlation_kind=rk)
 
 
-# ---- the bound of the fused gradient ----
-def slots_per_window(wins, shape, R):
-    """(slots of every window's moment partials, all_r): a slot per (segment of the gather's list, reference time), or per segment where
-    one workgroup walks all reference times (700 segments and more: csrc/eincm_plan.h, plan_motion)."""
-    H, W = shape
-    segs = np.array([len(LP.segment_lengths(LP.tile_counts(w['xs'], w['ys'], H, W), LP.SEG_LONG)) for w in wins])
-    all_r = R > 1 and segs.sum() >= 700
-    return segs * (1 if all_r else R), all_r
-
-
-def exact_moments(model, dense_grad):
-    """(mu (B, 12), sum|m_j g| (B, 12)): the moments of a dense gradient, every sum exact (math.fsum) and rounded once."""
-    H, W = model.sensor_size
-    mono = [np.broadcast_to(m, (H, W)) for m in (np.ones((1, 1)),) + model.monomials()]
-    G = np.asarray(dense_grad, dtype=np.float64)
-    mu = np.array([[math.fsum((m * G[b, :, :, a]).ravel().tolist()) for a in range(2) for m in mono] for b in range(G.shape[0])])
-    mu_abs = np.array([[math.fsum((np.abs(m) * np.abs(G[b, :, :, a])).ravel().tolist()) for a in range(2) for m in mono] for b in range(G.shape[0])])
-    return mu, mu_abs
-
-
-def moment_bound(model, dense_grad, slots):
-    """|fused gradient - (exact moments) M| is at most this.  A moment is an ordered float64 sum of rounded products m_j(p) g: a thread
-    adds its 2 pixels (512 threads, 1024 pixels), the wave tree has 6 levels, the 8 waves are added in index order, and the host adds
-    the window's `slots` partials in index order - the longest chain of additions an addend goes through is n = 2 + 6 + 8 + slots; the
-    rounding of the product and of the i64 -> fp64 conversion of a 61-bit sum make it n + 2.  Such a sum is within n 2^-53 sum|m_j g|
-    of the exact one to first order; the bound has the form of sections 17 and 20, 2 n 2^-53 sum|m_j g|, carried through |M|, plus the
-    2 * 12 * 2^-53 sum_j |M_jk mu_j| of the two 12-term sums M^T mu (the fused one and this reference's).  Nothing is fitted."""
-    mu, mu_abs = exact_moments(model, dense_grad)
-    n = 2 + 6 + 8 + np.asarray(slots, dtype=np.float64) + 2
-    absM = np.abs(model.matrix)
-    return mu @ model.matrix, (2.0 * n[:, None] * U * mu_abs) @ absM + 2.0 * 12 * U * (np.abs(mu) @ absM)
+# ---- the bound of the fused gradient: tests/_motion_bounds.py (shared with the motion sweep of tests/dev/fuzz_gpu.py) ----
 
 
 # ---- 1. against the expanded path and the dense path of the same build ----
