@@ -38,6 +38,8 @@ MOTION_MAX_COEFFS, MOTION_NQ = 12, 12                                # EINCM_MOT
 TA_FILL_SOURCE, TA_FILL_ZERO = 0, 1                                  # EINCM_TA_FILL_*
 TA_FILLS = {'source': TA_FILL_SOURCE, 'zero': TA_FILL_ZERO}
 RS_MAX_MODELS, RS_EXCLUDE_SELF = 8, 1                                # EINCM_RS_MAX_MODELS, EINCM_RS_EXCLUDE_SELF
+CL_MAX_CANDIDATES = 4096                                             # EINCM_CL_MAX_CANDIDATES
+CL_CELLS = (1, 2, 4, 8)                                              # the cell sizes of eincm_contrast_landscape
 
 
 class Params(C.Structure):
@@ -186,6 +188,8 @@ SIGNATURES = [
     # the E-step of a motion segmentation: those scores normalised over the models of a group (raw addresses)
     ('eincm_event_responsibilities', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the contrast landscape over motion coefficients (raw addresses, as above)
+    ('eincm_contrast_landscape', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # a solved theta carried along its own flow to the next window (raw addresses, as above)
     ('eincm_theta_advect', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

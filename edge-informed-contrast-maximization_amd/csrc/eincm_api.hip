@@ -44,6 +44,8 @@
 #include "eincm_responsibilities.hip.h"
 #include "eincm_theta_advect.h"
 #include "eincm_theta_advect.hip.h"
+#include "eincm_contrast_landscape.h"
+#include "eincm_contrast_landscape.hip.h"
 
 using namespace eincm;
 
@@ -2308,6 +2310,68 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
     return EINCM_OK;
 }
 
+
+// The contrast landscape over motion coefficients (eincm_contrast_landscape.hip.h): per window and candidate the
+// integer sum of squared cell counts of the warped events, and how many events stayed inside the sensor.  The checks, their order and
+// the band plan are eincm_contrast_landscape.h's; q = M c is motion_q, as eincm_loss_grad_motion forms it.
+int eincm_contrast_landscape(eincm_ctx* c, int n_candidates, const double* coeffs, const double* t_ref, int cell, const uint8_t* const* keep,
+                             uint64_t* sumsq, uint32_t* n_in) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    const auto& mo = c->motion;
+    const ClState st{!c->fl.idle(), sumsq || n_in, c->staged, mo.set, c->sharded_staging || c->constants_pending, c->staged ? g.B : 0,
+                     mo.set ? mo.model.n_coeffs : 0};
+    int bad_b = 0; int64_t bad_i = 0;
+    if (const ClFault f = cl_check(st, n_candidates, cell, coeffs, t_ref, &bad_b, &bad_i)) {
+        if (f == CL_NONFINITE && bad_i < 0) return fail(c, cl_code(f), "eincm_contrast_landscape: %s: t_ref of window %d", cl_why(f), bad_b);
+        if (f == CL_NONFINITE)
+            return fail(c, cl_code(f), "eincm_contrast_landscape: %s: window %d, candidate %lld, coefficient %d", cl_why(f), bad_b,
+                        (long long)(bad_i / mo.model.n_coeffs), (int)(bad_i % mo.model.n_coeffs));
+        return fail(c, cl_code(f), "eincm_contrast_landscape: %s", cl_why(f));
+    }
+    const int B = g.B, V = n_candidates, K = mo.model.n_coeffs;
+    const int64_t* ne = c->win_events.data();
+    const ClBands plan = cl_bands(g.H, g.W, cell);
+    const size_t BV = (size_t)B * V, n_bands = (size_t)plan.n_bands();
+    bool any_keep = false;
+    for (int b = 0; keep && b < B; ++b) any_keep = any_keep || (keep[b] && ne[b] > 0);
+    int64_t n_events = 0;
+    for (int b = 0; b < B; ++b) n_events += ne[b];
+    OneShot op(c);
+    const auto d_off = op.piece<int64_t>((size_t)B + 1);
+    const auto d_q = op.piece<double>(BV * MOTION_NQ);
+    const auto d_tref = op.piece<double>((size_t)B);
+    const auto d_keep = op.piece<uint8_t>((size_t)n_events, any_keep);
+    const auto d_has = op.piece<uint8_t>((size_t)B, any_keep);
+    const auto d_part = op.piece<unsigned long long>(BV * n_bands * 2);
+    const auto d_sumsq = op.piece<unsigned long long>(BV, sumsq != nullptr);
+    const auto d_nin = op.piece<uint32_t>(BV, n_in != nullptr);
+    int64_t* h_off = op.host_buf<int64_t>((size_t)B + 1);                // d_off, d_q and d_has go up from these; d_tref from the caller's
+    double* h_q = op.host_buf<double>(BV * MOTION_NQ);
+    uint8_t* h_has = op.host_buf<uint8_t>((size_t)B);
+    h_off[0] = 0;
+    for (int b = 0; b < B; ++b) h_off[b + 1] = h_off[b] + ne[b];
+    for (size_t i = 0; i < BV; ++i) motion_q(mo.model, coeffs + i * K, h_q + i * MOTION_NQ);
+    for (int b = 0; b < B; ++b) h_has[b] = any_keep && keep[b] && ne[b] > 0;
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)));
+    HIPCHK(c, op.up(d_q, h_q, BV * MOTION_NQ * sizeof(double)));
+    HIPCHK(c, op.up(d_tref, t_ref, (size_t)B * sizeof(double)));         // (host memory: the caller's, as keep and the outputs)
+    if (any_keep) {
+        HIPCHK(c, op.up(d_has, h_has, (size_t)B));
+        for (int b = 0; b < B; ++b)
+            if (h_has[b]) HIPCHK(c, op.up((uint8_t*)d_keep + h_off[b], keep[b], (size_t)ne[b]));
+    }
+    const ClGeom cg{g.H, g.W, V, cl_log2_cell(cell), plan.rows, plan.cols, plan.n_col_bands, plan.Hc, plan.Wc, plan.table,
+                    mo.model.cx, mo.model.cy, mo.model.scale};
+    HIPCHK(c, op.launch(k_contrast_landscape, dim3((unsigned)n_bands, (unsigned)V, (unsigned)B), dim3(CL_NT), (size_t)plan.lds_bytes(), cg, d_off,
+                        c->d_raw_x, c->d_raw_y, c->d_raw_t, d_q, d_tref, d_keep, d_has, d_part));
+    HIPCHK(c, op.launch(k_cl_sum_bands, dim3((unsigned)((BV + NT - 1) / NT)), dim3(NT), 0, (int)BV, (int)n_bands, d_part, d_sumsq, d_nin));
+    if (sumsq) HIPCHK(c, op.down(sumsq, d_sumsq, BV * sizeof(uint64_t)));
+    if (n_in) HIPCHK(c, op.down(n_in, d_nin, BV * sizeof(uint32_t)));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
 
 int eincm_inv_dist_transform(eincm_ctx* c, const uint8_t* edge_img, int n, int formulation, double alpha, double d_sat,
                              double* out, int32_t* sqdist) {

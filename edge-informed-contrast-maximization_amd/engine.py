@@ -663,6 +663,63 @@ def check_responsibility_args(n_models, n_events, prior, want):
     return K, prior, want
 
 
+CL_OUTPUTS = ('sumsq', 'n_in')
+
+
+def check_contrast_landscape_args(coeffs, n_events, n_coeffs, t_ref, cell, keep, want):
+    """The arguments of Engine.contrast_landscape that csrc/eincm_contrast_landscape.h refuses too, and every shape, checked without a
+    GPU.  n_events: the staged windows' event counts (B,); n_coeffs: K of the engine's motion model, None when none is set.  coeffs
+    (B, V, K), or (V, K) when B == 1, finite, 1 <= V <= CL_MAX_CANDIDATES; t_ref None (0.5 for every window), a number or (B,), finite;
+    cell one of CL_CELLS; keep None or B entries, each None or (n_events[b],) of booleans or integers; want a non-empty choice of
+    CL_OUTPUTS.  Returns (coeffs (B, V, K) float64, t_ref (B,) float64, cell, keep as None or a list of None / uint8 arrays, want)."""
+    n = np.asarray(n_events, dtype=np.int64).reshape(-1)
+    B = n.size
+    if B < 1:
+        raise ValueError('no windows staged (Engine.set_windows)')
+    if n_coeffs is None:
+        raise ValueError('no motion model set (Engine.set_motion_model)')
+    K = int(n_coeffs)
+    c = np.asarray(coeffs)
+    if c.dtype.kind not in 'fiu':
+        raise ValueError(f'coeffs must be numeric, got dtype {c.dtype}')
+    if c.ndim == 2 and B == 1:
+        c = c[None]
+    if c.ndim != 3 or c.shape[0] != B or c.shape[2] != K:
+        raise ValueError(f'coeffs must be ({B}, V, {K})' + (f' or (V, {K})' if B == 1 else '') + f', got {np.shape(coeffs)}')
+    if not 1 <= c.shape[1] <= L.CL_MAX_CANDIDATES:
+        raise ValueError(f'the number of candidates must lie within 1 .. {L.CL_MAX_CANDIDATES}, got {c.shape[1]}')
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if not np.isfinite(c).all():
+        raise ValueError('coeffs must be finite')
+    t = np.asarray(0.5 if t_ref is None else t_ref)
+    if t.dtype.kind not in 'fiu' or t.shape not in ((), (B,)):
+        raise ValueError(f't_ref must be a number or ({B},) numbers, got {t.dtype} {t.shape}')
+    t = np.ascontiguousarray(np.broadcast_to(t.astype(np.float64), (B,)))
+    if not np.isfinite(t).all():
+        raise ValueError('t_ref must be finite')
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or int(cell) not in L.CL_CELLS:
+        raise ValueError(f'cell must be one of {L.CL_CELLS}, got {cell!r}')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in CL_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a non-empty choice of {CL_OUTPUTS} without repeats, got {want!r}')
+    if keep is not None:
+        if isinstance(keep, np.ndarray) and keep.ndim == 1 and B == 1:
+            keep = [keep]
+        if len(keep) != B:
+            raise ValueError(f'keep must hold {B} entries, one per staged window, got {len(keep)}')
+        masks = []
+        for b, k in enumerate(keep):
+            if k is None:
+                masks.append(None)
+                continue
+            k = np.asarray(k)
+            if k.dtype.kind not in 'biu' or k.shape != (int(n[b]),):
+                raise ValueError(f'keep[{b}] must be ({int(n[b])},) booleans or integers, got {k.dtype} {k.shape}')
+            masks.append(np.ascontiguousarray(k != 0, dtype=np.uint8))
+        keep = masks
+    return c, t, int(cell), keep, want
+
+
 def check_score_images(images, n_windows, n_refs, sensor_size):
     """The caller's image stack of Engine.event_scores as contiguous float32 (B,R,H,W); (R,H,W) stands for it when B == 1.  None stays
     None (the IWEs of the last evaluation).  Anything else is a ValueError, raised before any library call."""
@@ -1630,6 +1687,32 @@ class Engine:
             out['mass'] = mass.reshape(G, K)
         if n_uns is not None:
             out['n_unsupported'] = n_uns
+        return out
+
+    def contrast_landscape(self, coeffs, t_ref=None, cell=1, keep=None, want=('sumsq', 'n_in')):
+        """The contrast landscape over motion coefficients, one device operation: every staged window's raw
+        events are warped to ``t_ref`` by the engine's motion model at each of V candidate coefficient vectors, dropped where they leave
+        the sensor, and counted in cells of ``cell`` x ``cell`` pixels.  coeffs: (B, V, K), or (V, K) when B == 1.  t_ref: None (0.5), a
+        number or (B,).  keep: None, or B entries, each None or a mask over the window's events as they were staged: only those take
+        part.  Returns a dict of ``want``: 'sumsq' (B, V) uint64, the sum of squared cell counts - the integer the search ranks by;
+        'n_in' (B, V) uint32, the events inside the sensor.  Staged weights are ignored.  Exact: equal to
+        tests/_contrast_landscape_witness.py integer for integer, and the same bytes on every run."""
+        c, t, cell, masks, want = check_contrast_landscape_args(coeffs, self.n_events if self.B else [],
+                                                                None if self.motion_model is None else self.motion_model.n_coeffs,
+                                                                t_ref, cell, keep, want)
+        B, V = c.shape[:2]
+        sumsq = np.zeros((B, V), dtype=np.uint64) if 'sumsq' in want else None
+        n_in = np.zeros((B, V), dtype=np.uint32) if 'n_in' in want else None
+        kp = None
+        if masks is not None and any(m is not None and m.size for m in masks):
+            kp = (C.c_void_p * B)(*[None if (m is None or not m.size) else m.ctypes.data for m in masks])
+        addr = lambda a: None if a is None else a.ctypes.data
+        self._check(self._lib.eincm_contrast_landscape(self._ctx, V, c.ctypes.data, t.ctypes.data, cell, kp, addr(sumsq), addr(n_in)))
+        out = {}
+        if sumsq is not None:
+            out['sumsq'] = sumsq
+        if n_in is not None:
+            out['n_in'] = n_in
         return out
 
     def scaled_theta(self):

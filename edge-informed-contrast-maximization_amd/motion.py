@@ -163,3 +163,53 @@ class MotionModel:
         for j in range(1, NM):
             s = s + q[:, :, j] * mm[j]
         return float(s.max())
+
+
+# -- the contrast landscape over coefficients -------------------------------------------------------------------
+def coefficient_grid(model, centre, axes, span, n):
+    """The (n ** len(axes), K) candidates of a regular grid through ``centre`` (K,): along every one of the 1 to 3 distinct coefficient
+    indices ``axes`` the coefficient takes the n values centre[a] + (i - (n - 1) / 2) * (2 * span / (n - 1)), i = 0 .. n - 1; the others
+    stay at the centre.  span: the half-range, a positive number or one per axis.  n: odd and >= 3, so the centre is a candidate.
+    axes[0] varies fastest: candidate j has i_k = (j // n ** k) % n along axes[k]."""
+    K = model.n_coeffs
+    c = np.asarray(centre, dtype=np.float64)
+    if c.shape != (K,) or not np.isfinite(c).all():
+        raise ValueError(f'centre must be ({K},) finite numbers, got {np.shape(centre)}')
+    ax = [a for a in np.atleast_1d(np.asarray(axes)).tolist()]
+    if not 1 <= len(ax) <= 3 or any(isinstance(a, bool) or not isinstance(a, int) or not 0 <= a < K for a in ax) or len(set(ax)) != len(ax):
+        raise ValueError(f'axes must hold 1 to 3 distinct coefficient indices within 0 .. {K - 1}, got {axes!r}')
+    sp = np.asarray(span, dtype=np.float64)
+    if sp.shape not in ((), (len(ax),)) or not (np.isfinite(sp).all() and (sp > 0).all()):
+        raise ValueError(f'span must be a positive finite number or one per axis, got {span!r}')
+    sp = np.broadcast_to(sp, (len(ax),))
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 3 or n % 2 == 0:
+        raise ValueError(f'n must be an odd integer >= 3, got {n!r}')
+    n = int(n)
+    out = np.tile(c, (n ** len(ax), 1))
+    j = np.arange(n ** len(ax))
+    for k, a in enumerate(ax):
+        i = (j // n ** k) % n
+        out[:, a] = c[a] + (i - (n - 1) / 2) * (2 * sp[k] / (n - 1))
+    return out
+
+
+def landscape_variance(sumsq, n_in, n_cells):
+    """The variance of the image of cell counts, sumsq / P - (n_in / P) ** 2 with P = n_cells, in float64: for display.  The search
+    itself ranks by the integer ``sumsq``."""
+    P = float(n_cells)
+    return np.asarray(sumsq, dtype=np.float64) / P - (np.asarray(n_in, dtype=np.float64) / P) ** 2
+
+
+def warped_pixels(model, coeffs, xs, ys, ts, t_ref):
+    """Where the contrast landscape counts one window's events under coeffs (K,): (r_x, r_y, inside) with r = rint(x - Theta * dt) as
+    float64, Theta = field(coeffs) at the event's own pixel, dt = ts - t_ref, the product rounded before the subtraction; inside is the
+    in-sensor test 0 <= r_x < W and 0 <= r_y < H on the floats (false for a NaN).  The host half of segmentation.seed_motions."""
+    H, W = model.sensor_size
+    x, y = np.asarray(xs).astype(np.int64), np.asarray(ys).astype(np.int64)
+    with np.errstate(over='ignore', invalid='ignore'):
+        th = model.field(coeffs)[y, x]
+        dt = np.asarray(ts, dtype=np.float64) - float(t_ref)
+        rx = np.rint(x.astype(np.float64) - th[:, 0] * dt)
+        ry = np.rint(y.astype(np.float64) - th[:, 1] * dt)
+        inside = (rx >= 0.0) & (rx < float(W)) & (ry >= 0.0) & (ry < float(H))
+    return rx, ry, inside

@@ -4,10 +4,16 @@ K motion models on one event list are K windows of a batch that share the events
 (section 22).  The M-step solves every model on its weighted events (batch_solver.minimize_motion, section 20); the E-step scores every
 event under every model, leave-one-out against that model's image of warped events, and normalises over the models
 (Engine.event_responsibilities, one device operation).  Staging keeps no index back to the caller's order, so every iteration stages
-the batch again with the new weights."""
+the batch again with the new weights.
+
+The EM is local and needs starting coefficients.  seed_motions finds them without a gradient: a coarse-to-fine
+grid search on the contrast landscape (Engine.contrast_landscape), one motion after the other, each on the events that the motions
+found before it do not explain."""
 import numpy as np
 
+from . import _lib as L
 from . import batch_solver as bsol
+from . import motion
 
 PRIORS = ('mass', 'uniform')
 
@@ -107,3 +113,112 @@ def segment_motions(engine, windows, model, coeffs0, params, n_iters=5, maxiter=
             callback(it, record)
         active = active & (r['mass'] >= min_mass)
     return history
+
+
+# ---- seeds for the models: a peeling search on the contrast landscape -------------------------------------------
+def landscape_cell(step):
+    """The cell size a grid of this step is evaluated at: the smallest of CL_CELLS that is >= the step, 8 beyond."""
+    for cell in L.CL_CELLS:
+        if cell >= step:
+            return cell
+    return L.CL_CELLS[-1]
+
+
+def peel_explained(model, coeffs, xs, ys, ts, t_ref, keep, peel_min_count):
+    """The events of one window that the motion ``coeffs`` explains: kept, inside the sensor after the warp, and sharing their pixel of
+    the count image of the kept in-sensor events with at least peel_min_count others.  (n,) bool."""
+    H, W = model.sensor_size
+    rx, ry, inside = motion.warped_pixels(model, coeffs, xs, ys, ts, t_ref)
+    part = inside & keep
+    pix = ry[part].astype(np.int64) * W + rx[part].astype(np.int64)
+    count = np.bincount(pix, minlength=H * W)
+    explained = np.zeros(len(keep), dtype=bool)
+    explained[part] = count[pix] - 1 >= peel_min_count
+    return explained
+
+
+def check_seed_args(windows, model, n_models, span, axes, base, n, refine_levels, refine_n, t_ref, peel_min_count, min_events):
+    """The arguments of seed_motions, checked without a GPU.  Returns (base (G, K) float64, span (len(axes),) float64, t_ref (G,))."""
+    G, K = len(windows), model.n_coeffs
+    if G < 1:
+        raise ValueError('windows must hold at least one (xs, ys, ts, edges, edge_ts) tuple')
+    for g, w in enumerate(windows):
+        if len(w) != 5:
+            raise ValueError(f'window {g}: a (xs, ys, ts, edges, edge_ts) tuple, got {len(w)} elements (the landscape ignores weights)')
+    if isinstance(n_models, bool) or not isinstance(n_models, (int, np.integer)) or n_models < 1:
+        raise ValueError(f'n_models must be a positive integer, got {n_models!r}')
+    b = np.zeros((G, K)) if base is None else np.asarray(base, dtype=np.float64)
+    if b.shape == (K,):
+        b = np.broadcast_to(b, (G, K))
+    if b.shape != (G, K) or not np.isfinite(b).all():
+        raise ValueError(f'base must be ({K},) or ({G}, {K}) finite numbers, got {np.shape(base)}')
+    for name, v, lo in (('refine_levels', refine_levels, 0), ('peel_min_count', peel_min_count, 0), ('min_events', min_events, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
+            raise ValueError(f'{name} must be an integer >= {lo}, got {v!r}')
+    motion.coefficient_grid(model, b[0], axes, span, n)                                # (raises for bad axes, span and n)
+    motion.coefficient_grid(model, b[0], axes, 1.0, refine_n)
+    n_axes = len(np.atleast_1d(np.asarray(axes)))
+    t = np.asarray(t_ref, dtype=np.float64)
+    if t.shape not in ((), (G,)) or not np.isfinite(t).all():
+        raise ValueError(f't_ref must be a finite number or ({G},) of them, got {t_ref!r}')
+    return np.array(b), np.array(np.broadcast_to(np.asarray(span, dtype=np.float64), (n_axes,))), np.array(np.broadcast_to(t, (G,)))
+
+
+def seed_motions(engine, windows, model, n_models, span, axes=(0, 1), base=None, n=17, refine_levels=2, refine_n=9, t_ref=0.5,
+                 peel_min_count=2, min_events=16, landscape=None):
+    """Starting coefficients for segment_motions, found without a gradient: per window, n_models motions one after the other, each the
+    best candidate of a coarse-to-fine grid search on the contrast landscape (Engine.contrast_landscape: the integer sum of squared
+    cell counts of the warped events) over the events that the motions found before it do not explain.
+
+    windows: G (xs, ys, ts, edges, edge_ts) tuples.  model: a motion.MotionModel.  The grids run over the coefficient indices ``axes``
+    (1 to 3), the other coefficients stay at ``base`` ((K,) or (G, K), zeros by default).  Level 0 is coefficient_grid(base, axes, span,
+    n); each of the refine_levels that follow is centred on the level's winner (the largest sumsq, the lowest index on a tie) with the
+    previous level's step as its half-range and refine_n values per axis.  A level is evaluated at landscape_cell(its largest step).
+    All windows' candidates of a level go into one call, cut into pieces of at most CL_MAX_CANDIDATES.  After a motion is found, the
+    events it explains (peel_explained) leave the window's ``keep``; when fewer than min_events remain the window stops, its remaining
+    rows NaN.
+
+    landscape: the callable (coeffs (G, V, K), t_ref (G,), cell, keep: G bool arrays) -> sumsq (G, V) that evaluates candidates; None
+    stages the windows on ``engine``, sets the model and takes the engine's operator.  With a callable the engine is not touched.
+
+    Returns a dict: 'coeffs0' (G, n_models, K) float64; 'sumsq' (G, n_models) uint64, each winner's sumsq at the last level's cell;
+    'n_kept' (G, n_models) int64, the events that took part in each search; 'n_found' (G,) int64, the valid rows."""
+    base, span, t_ref = check_seed_args(windows, model, n_models, span, axes, base, n, refine_levels, refine_n, t_ref, peel_min_count,
+                                        min_events)
+    G, K, M = len(windows), model.n_coeffs, int(n_models)
+    if landscape is None:
+        engine.set_windows([tuple(w) for w in windows])
+        engine.set_motion_model(model)
+
+        def landscape(coeffs, t_ref, cell, keep):
+            return engine.contrast_landscape(coeffs, t_ref=t_ref, cell=cell, keep=keep, want='sumsq')['sumsq']
+
+    def best(cands, cell, keep):
+        """(winner index (G,), its sumsq (G,)) over the (G, V, K) candidates"""
+        V = cands.shape[1]
+        s = np.concatenate([np.asarray(landscape(np.ascontiguousarray(cands[:, v:v + L.CL_MAX_CANDIDATES]), t_ref, cell, keep))
+                            for v in range(0, V, L.CL_MAX_CANDIDATES)], axis=1)
+        j = np.argmax(s, axis=1)                                                       # (the first of equal maxima: the lowest index)
+        return j, s[np.arange(G), j]
+
+    keep = [np.ones(len(w[0]), dtype=bool) for w in windows]
+    out = dict(coeffs0=np.full((G, M, K), np.nan), sumsq=np.zeros((G, M), dtype=np.uint64), n_kept=np.zeros((G, M), dtype=np.int64),
+               n_found=np.zeros(G, dtype=np.int64))
+    live = np.ones(G, dtype=bool)
+    for m in range(M):
+        live &= np.array([int(k.sum()) >= min_events for k in keep])
+        if not live.any():
+            break
+        centre, half, count = base.copy(), span, int(n)
+        for level in range(1 + int(refine_levels)):
+            step = 2.0 * half / (count - 1)
+            cands = np.stack([motion.coefficient_grid(model, centre[g], axes, half, count) for g in range(G)])
+            j, s = best(cands, landscape_cell(float(step.max())), keep)
+            centre = cands[np.arange(G), j]
+            half, count = step, int(refine_n)
+        for g in np.flatnonzero(live):
+            out['coeffs0'][g, m], out['sumsq'][g, m], out['n_kept'][g, m] = centre[g], s[g], int(keep[g].sum())
+            out['n_found'][g] = m + 1
+            xs, ys, ts = windows[g][:3]
+            keep[g] = keep[g] & ~peel_explained(model, centre[g], xs, ys, ts, t_ref[g], keep[g], int(peel_min_count))
+    return out

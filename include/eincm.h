@@ -34,7 +34,8 @@ extern "C" {
                                *    eincm_event_support (the event-support filter), eincm_event_filter (the refractory and polarity-aware
                                *    filter), eincm_event_scores (an image stack sampled at the warped events), eincm_theta_advect (a solved theta
                                *    carried along its own flow to the next window), eincm_event_responsibilities (those scores normalised over
-                               *    the models of a group: the E-step of a motion segmentation) */
+                               *    the models of a group: the E-step of a motion segmentation), eincm_contrast_landscape (the integer contrast of
+                               *    the warped events on a grid of candidate motion coefficients) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -317,6 +318,36 @@ int eincm_event_scores(eincm_ctx* ctx, const float* images, const double* ref_we
 int eincm_event_responsibilities(eincm_ctx* ctx, int n_models, const float* images, const double* ref_weights,
                                  const float* const* weights_in, const double* prior, uint32_t flags,
                                  float* weights_out, uint8_t* labels, double* mass, int64_t* n_unsupported);
+
+/* The contrast landscape over motion coefficients: a global, derivative-free look at the objective that seeds
+ * the motion models.  For every window b of the staged batch and every candidate j of n_candidates, the events of the window are
+ * warped by the context's motion model (eincm_set_motion_model) at the candidate's coefficients and counted per cell.  The raw events
+ * are read as they were staged; staged weights are ignored.  For an event e (x_e, y_e, t_e) that takes part:
+ *     q      = M c, formed as eincm_loss_grad_motion forms it (every product rounded, the sum left to right)
+ *     Theta  = the model's field at the event's own pixel (y_e, x_e): the bits of eincm_motion_field there
+ *     dt     = t_e - t_ref[b]
+ *     w      = (double)x_e - Theta_x * dt, and the same in y: the product rounded before the subtraction, no fused multiply-add
+ *     r      = rint(w), half to even
+ *     the event is in the sensor iff 0 <= r_x < W and 0 <= r_y < H, tested on the doubles (false for a NaN)
+ *     outside the sensor the event is DROPPED: the reference's wrap of negative indices to the far side of the image does not apply
+ *     an in-sensor event adds 1 to cell (r_y >> log2 cell, r_x >> log2 cell) of a ceil(H / cell) x ceil(W / cell) image of counts
+ *   n_candidates  V, 1 .. EINCM_CL_MAX_CANDIDATES
+ *   coeffs        (B, V, K) doubles, all finite; K the model's n_coeffs
+ *   t_ref         (B) finite doubles
+ *   cell          1, 2, 4 or 8
+ *   keep          NULL, or B host pointers, each NULL (all events) or n_events[b] bytes: non-zero means the event takes part
+ *   sumsq         NULL, or (B, V): the sum over the cells of count^2
+ *   n_in          NULL, or (B, V): the number of in-sensor events
+ * Every result is an integer: counts by integer atomics in LDS, the squares summed in 64-bit integers, no float accumulated anywhere
+ * and nothing accumulated across workgroups, so every run gives the same bytes.  A window without events gives zeros.  Allowed on
+ * EINCM_CF_FP64 contexts and with any splat window: it uses neither.
+ * Refused before anything is written, in this order: EINCM_ERR_STATE an evaluation in flight; EINCM_ERR_ARG sumsq and n_in both NULL;
+ * EINCM_ERR_STATE nothing staged; EINCM_ERR_STATE no motion model set; EINCM_ERR_UNSUPPORTED an event-sharded staging; EINCM_ERR_ARG
+ * n_candidates out of range or cell not one of the four; EINCM_ERR_ARG coeffs or t_ref NULL; EINCM_ERR_ARG a coefficient or a t_ref
+ * that is not finite (the message names its window and index). */
+#define EINCM_CL_MAX_CANDIDATES 4096
+int eincm_contrast_landscape(eincm_ctx* ctx, int n_candidates, const double* coeffs, const double* t_ref, int cell,
+                             const uint8_t* const* keep, uint64_t* sumsq, uint32_t* n_in);
 
 /* compute_weights_for_multi_reference (losses.py:39-46) */
 int eincm_multi_ref_weights(int n_refs, double* w);
