@@ -24,6 +24,7 @@ METHODS = {'linear': 0, 'bilinear': 0, 'triangle': 0, 'lanczos3': 1, 'lanczos5':
 PF_FULL_AUX = 1
 PF_NO_TV_GRAD = 2
 SW_DEFER_CONSTANTS = 1
+SW_KEEP_ORDER = 2           # EINCM_SW_KEEP_ORDER: staging keeps its event order (Engine.set_windows(..., keep_order=True))
 CF_TIMING = 1
 CF_TIMING_DOMINANT = 2
 CF_FP64 = 4                # float64 mode (Engine(..., precision='fp64'))
@@ -38,6 +39,7 @@ MOTION_MAX_COEFFS, MOTION_NQ = 12, 12                                # EINCM_MOT
 TA_FILL_SOURCE, TA_FILL_ZERO = 0, 1                                  # EINCM_TA_FILL_*
 TA_FILLS = {'source': TA_FILL_SOURCE, 'zero': TA_FILL_ZERO}
 RS_MAX_MODELS, RS_EXCLUDE_SELF = 8, 1                                # EINCM_RS_MAX_MODELS, EINCM_RS_EXCLUDE_SELF
+RS_STAGED_WEIGHTS, RS_APPLY = 2, 4                                   # EINCM_RS_STAGED_WEIGHTS, EINCM_RS_APPLY (a keep-order batch)
 CL_MAX_CANDIDATES = 4096                                             # EINCM_CL_MAX_CANDIDATES
 CL_CELLS = (1, 2, 4, 8)                                              # the cell sizes of eincm_contrast_landscape
 
@@ -188,6 +190,10 @@ SIGNATURES = [
     # the E-step of a motion segmentation: those scores normalised over the models of a group (raw addresses)
     ('eincm_event_responsibilities', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    # a keep-order batch takes new weights in place (raw addresses, as above)
+    ('eincm_set_weights', C.c_int, [_P, C.c_void_p]),
+    ('eincm_get_stage_order', C.c_int, [_P, C.c_void_p, C.c_void_p]),
+    ('eincm_get_staged_weights', C.c_int, [_P, C.c_void_p]),
     # the contrast landscape over motion coefficients (raw addresses, as above)
     ('eincm_contrast_landscape', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # a solved theta carried along its own flow to the next window (raw addresses, as above)

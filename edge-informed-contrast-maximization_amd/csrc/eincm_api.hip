@@ -116,7 +116,7 @@ struct StageScratch {
     std::vector<unsigned> cntmax; std::vector<double> dtmax;       // (B) most events on one source pixel, max |t - tau|
     bool edge_ts_uploaded = false;
     std::vector<BinBlock> blks; std::vector<int32_t> win_blk; int32_t misc[4]; std::vector<double> mom;   // device binning
-    std::vector<uint32_t> sxy; std::vector<double> st; std::vector<float> ef; std::vector<float> sw;      // host binning
+    std::vector<uint32_t> sxy; std::vector<double> st; std::vector<float> ef; std::vector<float> sw; std::vector<uint32_t> sidx;   // host binning
     std::vector<int> ishift;                                                                              // float64 mode
 };
 
@@ -167,6 +167,14 @@ struct eincm_ctx : PlanCtx {
     // weighted staging of the context (ensure_weights), not read by an unweighted batch
     float* d_w = nullptr;          // (maxN) in the order of d_xy
     float* d_w_g = nullptr;        // (maxN) in the order of d_xy_g; during a device binning it first holds the weights as handed over
+    // a keep-order batch (EINCM_SW_KEEP_ORDER; stage.keep_order): allocated by the first staging that asks for it
+    // (ensure_order), not touched by any other
+    struct {
+        uint32_t* splat = nullptr;     // (maxN) for every slot of d_xy: where its event stood in the batch as handed over (the index into d_raw_*)
+        uint32_t* gather = nullptr;    // (maxN) the same for d_xy_g
+        float* stream = nullptr;       // (maxN) the staged weights in the order of d_raw_*: what k_bin_scatter and k_reweight read, ones where a window was handed none
+        std::vector<uint32_t> h_xy;    // host binning only: the events as handed over, x | y << 16 (the host counts the most events on one pixel)
+    } ord;
     std::vector<int32_t> h_tilecount;   // (B, ntiles) events per (window, tile) of the staged batch: what every segment list is cut from
     bool policy_evaluated = false; // an evaluation has chosen capacities since the last staging (eincm_get_launch_policy)
     // device-side staging (eincm_binning.hip.h)
@@ -1563,6 +1571,13 @@ static int check_staging(eincm_ctx* c, const StageArgs& a) {
             return fail(c, EINCM_ERR_UNSUPPORTED, "per-event weights have the 3x3 splat window only, the context has %d (eincm_set_splat_window)", c->splat_size);
         if (a.flags & EINCM_SW_DEFER_CONSTANTS) return fail(c, EINCM_ERR_UNSUPPORTED, "per-event weights are not supported in an event-sharded staging");
     }
+    // a keep-order batch is a weighted one whatever it was handed: the same three, in its own words
+    if (a.flags & EINCM_SW_KEEP_ORDER) {
+        if (c->fp64) return fail(c, EINCM_ERR_UNSUPPORTED, "EINCM_SW_KEEP_ORDER is not supported in fp64 mode (EINCM_CF_FP64)");
+        if (c->splat_size != 3)
+            return fail(c, EINCM_ERR_UNSUPPORTED, "EINCM_SW_KEEP_ORDER has the 3x3 splat window only, the context has %d (eincm_set_splat_window)", c->splat_size);
+        if (a.flags & EINCM_SW_DEFER_CONSTANTS) return fail(c, EINCM_ERR_UNSUPPORTED, "EINCM_SW_KEEP_ORDER is not supported in an event-sharded staging");
+    }
     return EINCM_OK;
 }
 
@@ -1570,6 +1585,14 @@ static int check_staging(eincm_ctx* c, const StageArgs& a) {
 static int ensure_weights(eincm_ctx* c) {
     if (!c->d_w) HIPCHK(c, c->mem.alloc_dev(c->d_w, (size_t)c->maxN));
     if (!c->d_w_g) HIPCHK(c, c->mem.alloc_dev(c->d_w_g, (size_t)c->maxN));
+    return EINCM_OK;
+}
+
+// The two indices and the stream-order weights of a keep-order batch, allocated by the first such staging of the context and kept
+static int ensure_order(eincm_ctx* c) {
+    if (!c->ord.splat) HIPCHK(c, c->mem.alloc_dev(c->ord.splat, (size_t)c->maxN));
+    if (!c->ord.gather) HIPCHK(c, c->mem.alloc_dev(c->ord.gather, (size_t)c->maxN));
+    if (!c->ord.stream) HIPCHK(c, c->mem.alloc_dev(c->ord.stream, (size_t)c->maxN));
     return EINCM_OK;
 }
 
@@ -1601,14 +1624,15 @@ static int upload_raw_events(eincm_ctx* c, const StageArgs& a) {
     return EINCM_OK;
 }
 
-// A weighted batch on the device path: the weights as handed over, window after window like the events, ones for a window without.
-// They go into d_w_g, which k_bin_scatter reads and k_segsort overwrites afterwards with the gather's order.
-static int upload_raw_weights(eincm_ctx* c, const StageArgs& a) {
+// The weights as handed over, window after window like the events, ones for a window without (weights NULL: for every window), into
+// dst.  A weighted batch on the device path sends them to d_w_g, which k_bin_scatter reads and k_segsort overwrites afterwards with the
+// gather's order; a keep-order batch, and eincm_set_weights, to ord.stream, where they stay.
+static int upload_raw_weights(eincm_ctx* c, int B, const int64_t* n_events, const float* const* weights, float* dst) {
     int64_t off = 0;
-    for (int b = 0; b < a.B; ++b) {
-        const size_t nb = (size_t)a.n_events[b];
-        if (nb > 0 && a.weights[b]) HIPCHK(c, hipMemcpyAsync(c->d_w_g + off, a.weights[b], nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        else if (nb > 0) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c->d_w_g + off), 0x3f800000 /* 1.0f */, nb, c->stream));
+    for (int b = 0; b < B; ++b) {
+        const size_t nb = (size_t)n_events[b];
+        if (nb > 0 && weights && weights[b]) HIPCHK(c, hipMemcpyAsync(dst + off, weights[b], nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        else if (nb > 0) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + off), 0x3f800000 /* 1.0f */, nb, c->stream));
         off += (int64_t)nb;
     }
     return EINCM_OK;
@@ -1618,15 +1642,18 @@ static int upload_raw_weights(eincm_ctx* c, const StageArgs& a) {
 // (k_segsort, from the binned time order, before the splat's copy is re-dealt in place); EINCM_NO_SEGSORT: a plain copy.
 static int copy_for_gather(eincm_ctx* c) {
     if (c->gather.n == 0) return EINCM_OK;
-    const bool wt = c->stage.weighted;        // the weights take the same way as the events
+    const bool wt = c->stage.weighted, ix = c->stage.keep_order;        // the weights, and a keep-order batch's index, take the same way as the events
     if (c->stage.sort_segments) {
         const dim3 grid(std::min(c->gather.n, 8192));
-        if (wt) hipLaunchKernelGGL(k_segsort<1>, grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
-                                   c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)c->d_w, c->d_w_g);
+        if (ix) hipLaunchKernelGGL((k_segsort<1, 1>), grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
+                                   c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)c->d_w, c->d_w_g, (const uint32_t*)c->ord.splat, c->ord.gather);
+        else if (wt) hipLaunchKernelGGL(k_segsort<1>, grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
+                                   c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)c->d_w, c->d_w_g, (const uint32_t*)nullptr, (uint32_t*)nullptr);
         else hipLaunchKernelGGL(k_segsort<0>, grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
-                                c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)nullptr, (float*)nullptr);
+                                c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)nullptr, (float*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
         return EINCM_OK;
     }
+    if (ix) HIPCHK(c, hipMemcpyAsync(c->ord.gather, c->ord.splat, (size_t)c->stage.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     if (wt) HIPCHK(c, hipMemcpyAsync(c->d_w_g, c->d_w, (size_t)c->stage.N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)c->stage.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)c->stage.N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -1692,13 +1719,17 @@ static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
             c->h_wc[b].sE[r] = sE; c->h_wc[b].sEE[r] = sEE; c->h_wc[b].eabs[r] = eabs;
         }
     if (nblk > 0) {
-        if (P.weighted) {
-            if ((rc = upload_raw_weights(c, a))) return rc;
+        if (P.keep_order) {
+            if ((rc = upload_raw_weights(c, a.B, a.n_events, a.weights, c->ord.stream))) return rc;
+            hipLaunchKernelGGL((k_bin_scatter<1, 1>), dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x,
+                               c->d_raw_y, c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)c->ord.stream, c->d_w, c->ord.splat);
+        } else if (P.weighted) {
+            if ((rc = upload_raw_weights(c, a.B, a.n_events, a.weights, c->d_w_g))) return rc;
             hipLaunchKernelGGL(k_bin_scatter<1>, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x,
-                               c->d_raw_y, c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)c->d_w_g, c->d_w);
+                               c->d_raw_y, c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)c->d_w_g, c->d_w, (uint32_t*)nullptr);
         } else
         hipLaunchKernelGGL(k_bin_scatter<0>, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
-                           c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)nullptr, (float*)nullptr);
+                           c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)nullptr, (float*)nullptr, (uint32_t*)nullptr);
         hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, P.seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase,
                            c->gather.d_items);
         if ((rc = copy_for_gather(c))) return rc;
@@ -1706,10 +1737,15 @@ static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     if ((rc = build_list(c, c->gather, P.seg, false, g.ntiles, c->d_t_g, P.N))) return rc;
     c->splat.n = 0;
     if (nblk > 0) {
-        if (P.spread && P.weighted)
-            hipLaunchKernelGGL(k_spread<1>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, c->d_w);
+        if (P.spread && P.keep_order)
+            hipLaunchKernelGGL((k_spread<1, 1>), dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, c->d_w,
+                               c->ord.splat);
+        else if (P.spread && P.weighted)
+            hipLaunchKernelGGL(k_spread<1>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, c->d_w,
+                               (uint32_t*)nullptr);
         else if (P.spread)
-            hipLaunchKernelGGL(k_spread<0>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, (float*)nullptr);
+            hipLaunchKernelGGL(k_spread<0>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, (float*)nullptr,
+                               (uint32_t*)nullptr);
         // per window: first segment and max |t - tau| (needs the segment time ranges and the FIRST segmentation's itembase)
         HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, a.edge_ts, (size_t)a.B * a.R * sizeof(double), hipMemcpyHostToDevice, c->stream));
         sc.edge_ts_uploaded = true;
@@ -1737,7 +1773,7 @@ static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     const size_t img = (size_t)g.H * g.W;
     int rc = EINCM_OK;
     if (const EventRefusal r = bin_events(g, a.n_events, a.xs, a.ys, a.ts, a.edge_ts, P.N, c->h_tilecount, sc.sxy, sc.st, sc.cntmax, sc.dtmax,
-                                          a.weights, P.weighted ? &sc.sw : nullptr))
+                                          a.weights, P.weighted ? &sc.sw : nullptr, P.keep_order ? &sc.sidx : nullptr))
         return refuse_event(c, a, r.win, r.index, r.bad_xy);
     sc.ef.resize((size_t)a.B * a.R * img);
     for (int b = 0; b < a.B; ++b) {
@@ -1749,6 +1785,14 @@ static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
         HIPCHK(c, hipMemcpyAsync(c->d_xy, sc.sxy.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_t, sc.st.data(), (size_t)P.N * sizeof(double), hipMemcpyHostToDevice, c->stream));
         if (P.weighted) HIPCHK(c, hipMemcpyAsync(c->d_w, sc.sw.data(), (size_t)P.N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (P.keep_order) {      // the index beside the splat's copy, the weights in stream order, and the host's copy of the pixels (reweight_staged counts on them)
+            HIPCHK(c, hipMemcpyAsync(c->ord.splat, sc.sidx.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            if ((rc = upload_raw_weights(c, a.B, a.n_events, a.weights, c->ord.stream))) return rc;
+            c->ord.h_xy.resize((size_t)P.N);
+            size_t e = 0;
+            for (int b = 0; b < a.B; ++b)
+                for (int64_t i = 0; i < a.n_events[b]; ++i) c->ord.h_xy[e++] = (uint32_t)(uint16_t)a.xs[b][i] | ((uint32_t)(uint16_t)a.ys[b][i] << 16);
+        }
         if ((rc = upload_raw_events(c, a))) return rc;
     }
     // (the gather's copy is a permutation inside the gather list's segments: their time ranges come from either copy)
@@ -1815,6 +1859,7 @@ static int stage_windows(eincm_ctx* c, const StageArgs& a) {
     const StagePlan& P = c->stage;
     HIPCHK(c, hipSetDevice(c->device));
     if (P.weighted && (rc = ensure_weights(c))) return rc;
+    if (P.keep_order && (rc = ensure_order(c))) return rc;
     StageScratch sc;
     struct DrainOnExit { hipStream_t s; ~DrainOnExit() { (void)hipStreamSynchronize(s); } } drain_on_exit{c->stream};
     if (c->acc_dirty && (rc = clear_accumulators(c))) return rc;
@@ -1876,6 +1921,99 @@ int eincm_set_windows_weighted(eincm_ctx* c, int n_windows, int n_refs, const in
                                const int16_t* const* ys, const double* const* ts, const double* const* edges, const double* edge_ts,
                                const float* const* weights, uint32_t flags) {
     return stage_windows(c, StageArgs{n_windows, n_refs, n_events, xs, ys, ts, edges, edge_ts, flags, weights});
+}
+
+// ---- a keep-order batch takes new weights in place ----
+
+// Why a call that needs the indices of a keep-order staging cannot run, or EINCM_OK
+static int keep_order_ready(eincm_ctx* c, const char* who) {
+    if (!c->staged) return fail(c, EINCM_ERR_STATE, "%s called before eincm_set_windows", who);
+    if (!c->stage.keep_order)
+        return fail(c, EINCM_ERR_STATE, "%s: the batch was staged without EINCM_SW_KEEP_ORDER (keep_order=True), so staging kept no index back to "
+                    "the order of its events", who);
+    return EINCM_OK;
+}
+
+// The weights in ord.stream (enqueued on the stream by the caller, through its frame) become the staged batch's: the gather through the
+// two indices into both layouts, then everything a staging derives from the weights, by the kernels staging runs - the event mask and
+// the most events on one pixel (finish_lists), the bound behind the gradient scale, the zero-warp constants - and what a staging
+// invalidates.  The edges and their moments, the four lists, dtmax and the raw events do not depend on the weights and stay.
+static int reweight_staged(eincm_ctx* c, OneShot& op) {
+    const StagePlan& P = c->stage;
+    const Geom& g = c->g;
+    const int B = g.B;
+    const size_t N = (size_t)P.N;
+    unsigned* h_cnt = op.host_buf<unsigned>((size_t)B);                  // d_cntmax comes down here (zeros: a window without events)
+    float* h_w = op.host_buf<float>(P.host_binning ? N : 0);             // host binning: ord.stream comes down here
+    if (N > 0)
+        HIPCHK(c, op.launch(k_reweight, dim3((unsigned)((N + NT - 1) / NT)), dim3(NT), 0, (int64_t)N, c->ord.stream, c->ord.splat, c->ord.gather,
+                            c->d_w, c->d_w_g));
+    HIPCHK(c, op.zero(c->d_mask, (size_t)B * g.H * g.W));
+    if (c->gather.n > 0 && !P.host_binning) {
+        HIPCHK(c, op.zero(c->d_cntmax, (size_t)B * sizeof(unsigned)));
+        HIPCHK(c, op.launch(k_tile_counts, dim3(g.ntiles, B), dim3(NT), 0, g, c->d_tilebase, c->d_tilecount, c->d_xy, c->d_mask, c->d_cntmax,
+                            c->d_w));
+        HIPCHK(c, op.down(h_cnt, c->d_cntmax, (size_t)B * sizeof(unsigned)));
+    } else if (c->gather.n > 0) {
+        HIPCHK(c, op.launch(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask, c->d_w));
+        HIPCHK(c, op.down(h_w, c->ord.stream, N * sizeof(float)));
+    }
+    HIPCHK(c, op.sync());
+    size_t off = 0;
+    for (int b = 0; b < B; ++b) {
+        const int64_t nb = c->win_events[b];
+        if (P.host_binning && nb > 0) h_cnt[b] = most_on_one_pixel(g.H, g.W, nb, c->ord.h_xy.data() + off, h_w + off);
+        c->h_wc[b].cntmax = (double)std::max(h_cnt[b], 1u);
+        off += (size_t)nb;
+    }
+    c->objc_valid = false;
+    c->Theta_valid = false;
+    c->motion.last_q.clear(); c->motion.seg0.clear();
+    c->bfgs.begun = false;
+    c->policy_evaluated = false;
+    c->have_eval = false;
+    c->err.clear();
+    return window_constants(c);
+}
+
+int eincm_set_weights(eincm_ctx* c, const float* const* weights) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = keep_order_ready(c, "eincm_set_weights")) return rc;
+    if (const int rc = not_in_flight(c, "eincm_set_weights")) return rc;
+    const int B = c->g.B;
+    const int64_t* ne = c->win_events.data();
+    if (const WeightRefusal r = check_weights(B, ne, weights))
+        return fail(c, EINCM_ERR_ARG, "weight %lld of window %d is %g: weights are finite and within [0, 1]", (long long)r.index, r.win, (double)r.value);
+    OneShot op(c);                                  // no piece of the scratch: the frame is here for its drain
+    HIPCHK(c, op.begin());
+    op.pending = true;                              // staging's own upload enqueues below, not through the frame: the frame drains it all the same
+    if (const int rc = upload_raw_weights(c, B, ne, weights, c->ord.stream)) return rc;       // (host memory: the caller's)
+    return reweight_staged(c, op);
+}
+
+int eincm_get_stage_order(eincm_ctx* c, uint32_t* order_splat, uint32_t* order_gather) {
+    if (!c) return EINCM_ERR_ARG;
+    if (const int rc = keep_order_ready(c, "eincm_get_stage_order")) return rc;
+    const size_t bytes = (size_t)c->stage.N * sizeof(uint32_t);
+    if (bytes == 0) return EINCM_OK;
+    OneShot op(c);
+    HIPCHK(c, op.begin());
+    if (order_splat) HIPCHK(c, op.down(order_splat, c->ord.splat, bytes));       // (host memory: the caller's, both)
+    if (order_gather) HIPCHK(c, op.down(order_gather, c->ord.gather, bytes));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+int eincm_get_staged_weights(eincm_ctx* c, float* weights) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!weights) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (const int rc = keep_order_ready(c, "eincm_get_staged_weights")) return rc;
+    if (c->stage.N == 0) return EINCM_OK;
+    OneShot op(c);
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.down(weights, c->ord.stream, (size_t)c->stage.N * sizeof(float)));      // (host memory: the caller's)
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
 }
 
 // ---- event-sharded evaluation: forward half / [caller all-reduces the IWE stack] / finishing half ----
@@ -2249,11 +2387,16 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
     const Geom& g = c->g;
     bool masked = false;
     for (int b = 0; c->staged && b < g.B && b < 64; ++b) masked = masked || !((c->eval_wmask >> b) & 1ull);
-    const RsState st{{!c->fl.idle(), weights_out || labels || mass || n_unsupported, c->staged, c->have_eval, c->fp64, c->splat_size,
+    const bool apply = (flags & EINCM_RS_APPLY) != 0, own_w = (flags & EINCM_RS_STAGED_WEIGHTS) != 0;    // a keep-order batch's two
+    const RsState st{{!c->fl.idle(), weights_out || labels || mass || n_unsupported || apply, c->staged, c->have_eval, c->fp64, c->splat_size,
                       c->sharded_staging || c->constants_pending, images != nullptr, masked},
                      c->staged ? g.B : 0, c->win_events.data()};
     if (const RsFault f = rs_check(st, n_models, ref_weights, g.R, prior))
         return fail(c, rs_code(f), "eincm_event_responsibilities: %s", rs_why(f));
+    if (apply || own_w) {
+        if (const int rc = keep_order_ready(c, apply ? "eincm_event_responsibilities (EINCM_RS_APPLY)" : "eincm_event_responsibilities (EINCM_RS_STAGED_WEIGHTS)")) return rc;
+        if (own_w && weights_in) return fail(c, EINCM_ERR_ARG, "eincm_event_responsibilities: weights_in must be NULL with EINCM_RS_STAGED_WEIGHTS");
+    }
     { const int rc = ensure_theta_image(c); if (rc) return rc; }
     const int B = g.B, R = g.R, K = n_models, G = B / K;
     const int64_t* ne = c->win_events.data();
@@ -2264,14 +2407,15 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
     const size_t n_blk = (size_t)((n_max + NT - 1) / NT), stack = (size_t)B * R * g.H * g.W;
     bool any_w = false;
     for (int b = 0; (flags & EINCM_RS_EXCLUDE_SELF) && weights_in && b < B; ++b) any_w = any_w || (weights_in[b] && ne[b] > 0);
+    const bool self_own = own_w && (flags & EINCM_RS_EXCLUDE_SELF);       // w_l is read where staging left it: every window has its weights there
     OneShot op(c);
     const auto d_off = op.piece<int64_t>((size_t)B + 1);
     const auto d_img = op.piece<float>(stack, images != nullptr);
     const auto d_rw = op.piece<float>((size_t)R);
     const auto d_pi = op.piece<float>((size_t)B);
     const auto d_win = op.piece<float>((size_t)n_events, any_w);
-    const auto d_has = op.piece<uint8_t>((size_t)B, any_w);
-    const auto d_wout = op.piece<float>((size_t)n_events, weights_out != nullptr);
+    const auto d_has = op.piece<uint8_t>((size_t)B, any_w || self_own);
+    const auto d_wout = op.piece<float>((size_t)n_events, weights_out != nullptr || apply);
     const auto d_lab = op.piece<uint8_t>((size_t)n_labels, labels != nullptr);
     const auto d_part = op.piece<double>((size_t)B * n_blk, mass != nullptr);
     const auto d_mass = op.piece<double>((size_t)B, mass != nullptr);
@@ -2283,7 +2427,7 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
     for (int b = 0; b <= B; ++b) h_off[b] = rs_weights_offset(ne, b);
     for (int r = 0; r < R; ++r) h_rw[r] = (float)ref_weights[r];
     for (int b = 0; b < B; ++b) h_pi[b] = prior ? (float)prior[b] : 1.0f;
-    for (int b = 0; b < B; ++b) h_has[b] = any_w && weights_in[b] && ne[b] > 0;
+    for (int b = 0; b < B; ++b) h_has[b] = self_own || (any_w && weights_in[b] && ne[b] > 0);
     HIPCHK(c, op.begin());
     HIPCHK(c, op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)));
     if (images) HIPCHK(c, op.up(d_img, images, stack * sizeof(float)));  // (host memory: the caller's, as weights_in and the outputs)
@@ -2294,11 +2438,13 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
         for (int b = 0; b < B; ++b)
             if (h_has[b]) HIPCHK(c, op.up((float*)d_win + h_off[b], weights_in[b], (size_t)ne[b] * sizeof(float)));
     }
+    if (self_own) HIPCHK(c, op.up(d_has, h_has, (size_t)B));
+    const float* w_self = self_own ? (const float*)c->ord.stream : (const float*)d_win;     // (the stream order is the layout of weights_in)
     if (n_unsupported) HIPCHK(c, op.zero(d_uns, (size_t)G * sizeof(unsigned long long)));
     const float* F = images ? (const float*)d_img : (const float*)c->d_iwe;
     const dim3 grid((unsigned)n_blk, (unsigned)G);
     HIPCHK(c, op.launch(rs_kernel(K), grid, dim3(NT), 0, g, d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F, d_rw,
-                        d_win, d_has, d_pi, flags, d_wout, d_lab, d_part, d_uns));
+                        w_self, d_has, d_pi, flags, d_wout, d_lab, d_part, d_uns));
     if (mass) {
         HIPCHK(c, op.launch(k_rs_mass, dim3((unsigned)((B + NT - 1) / NT)), dim3(NT), 0, B, d_off, d_part, (int64_t)n_blk, d_mass));
         HIPCHK(c, op.down(mass, d_mass, (size_t)B * sizeof(double)));
@@ -2306,6 +2452,10 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
     if (weights_out) HIPCHK(c, op.down(weights_out, d_wout, (size_t)n_events * sizeof(float)));
     if (labels) HIPCHK(c, op.down(labels, d_lab, (size_t)n_labels));
     if (n_unsupported) HIPCHK(c, op.down(n_unsupported, d_uns, (size_t)G * sizeof(int64_t)));
+    if (apply) {                                    // w' is in the stream order already: it becomes the staged weights without leaving the device
+        HIPCHK(c, hipMemcpyAsync(c->ord.stream, (const float*)d_wout, (size_t)n_events * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        return reweight_staged(c, op);
+    }
     HIPCHK(c, op.sync());
     return EINCM_OK;
 }

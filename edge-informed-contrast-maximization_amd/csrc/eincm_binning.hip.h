@@ -9,6 +9,8 @@
 //   k_items / k_seg_minmax                                                                -> segments with their time range
 //   k_segsort                                                                             -> the order inside a segment (see there)
 // A weighted batch carries ev_w, one float per event, beside ev_xy and ev_t through the three kernels that move events.
+// A keep-order batch (section 29) also carries ev_i, the event's position in the batch as handed over; k_reweight then fetches new
+// weights for the staged events through it, without another sort.
 // The sort is STABLE: a block is one wave walking its 1024 events in input order, and events of a wave-step that share a tile are
 // ranked by lane (k_bin_scatter), so a tile's events keep the order they were handed over in; k_segsort is a stable sort of a
 // segment's events by source pixel.  Staging the same window twice therefore gives the same arrays bit for bit.  The per-thread sums
@@ -115,12 +117,16 @@ __global__ __launch_bounds__(1024) void k_bin_tilescan(int M, int seg, const int
 // WT (k_bin_scatter, k_spread, k_segsort): a weighted batch - the float payload ev_w rides beside ev_xy and ev_t
 // through every permutation, so each of the two event layouts carries its own copy of the weights.  The permutations themselves read
 // xy alone: a weighted batch is laid out exactly as the same events without weights.  WT = 0 touches neither pointer.
-template <int WT>
+// IX (the same three kernels): a keep-order batch - a second payload, the event's position in the batch as it was
+// handed over (the index into the raw events), rides the same way into ev_i, so each layout knows where its slots came from.  A pure
+// move like the weight: no arithmetic on it, and IX = 0 touches none of its pointers.
+template <int WT, int IX = 0>
 __global__ __launch_bounds__(BIN_NT) void k_bin_scatter(Geom g, const BinBlock* __restrict__ blks, const int16_t* __restrict__ xs,
                                                          const int16_t* __restrict__ ys, const double* __restrict__ ts,
                                                          const uint32_t* __restrict__ blockoff, const int32_t* __restrict__ tilebase,
                                                          uint32_t* __restrict__ ev_xy, double* __restrict__ ev_t,
-                                                         const float* __restrict__ ws, float* __restrict__ ev_w)   // ws: the weights as handed over, one per event of the batch
+                                                         const float* __restrict__ ws, float* __restrict__ ev_w,   // ws: the weights as handed over, one per event of the batch
+                                                         uint32_t* __restrict__ ev_i = nullptr)                    // IX: where the event stood in the batch (bb.start + i: nothing to load)
 {
     extern __shared__ uint32_t cnt[];            // where this block's next event of each tile goes: tile base + block offset + placed so far
     const BinBlock bb = blks[blockIdx.x];
@@ -171,6 +177,7 @@ __global__ __launch_bounds__(BIN_NT) void k_bin_scatter(Geom g, const BinBlock* 
             ev_xy[pos] = (uint32_t)(uint16_t)x | ((uint32_t)(uint16_t)y << 16);
             ev_t[pos] = t;
             if (WT) ev_w[pos] = wt[WT ? k : 0];
+            if (IX) ev_i[pos] = (uint32_t)(bb.start + i);
         }
     }
 }
@@ -183,9 +190,10 @@ __global__ __launch_bounds__(BIN_NT) void k_bin_scatter(Geom g, const BinBlock* 
 // segments are multiples of 256 events from the tile's start, so no event changes segment.  A trailing partial block keeps its order.
 // grid (B * ntiles, SPREAD_Y) workgroups of 256 threads: the blocks of a tile are dealt round-robin to SPREAD_Y workgroups.
 constexpr int SPREAD_Y = 16;
-template <int WT>
+template <int WT, int IX = 0>
 __global__ __launch_bounds__(256) void k_spread(Geom g, const int32_t* __restrict__ tilecount, const int32_t* __restrict__ tilebase,
-                                                uint32_t* __restrict__ ev_xy, double* __restrict__ ev_t, float* __restrict__ ev_w)
+                                                uint32_t* __restrict__ ev_xy, double* __restrict__ ev_t, float* __restrict__ ev_w,
+                                                uint32_t* __restrict__ ev_i = nullptr)
 {
     __shared__ __attribute__((aligned(16))) uint32_t keys[256];
     const int idx = blockIdx.x;
@@ -196,6 +204,8 @@ __global__ __launch_bounds__(256) void k_spread(Geom g, const int32_t* __restric
         const double tm = ev_t[base + b0 + t];
         float wgt = 0.0f;
         if (WT) wgt = ev_w[base + b0 + t];
+        uint32_t src = 0u;
+        if (IX) src = ev_i[base + b0 + t];
         // pixel inside the 32x32 tile (10 bits) above the position in the block (8 bits)
         // pixel inside the 32x32 tile, COLUMN-major (10 bits: x, then y), above the position in the block (8 bits)
         const uint32_t key = (((xy & 31u) << 5) | ((xy >> 16) & 31u)) << 8 | (uint32_t)t;
@@ -216,6 +226,7 @@ __global__ __launch_bounds__(256) void k_spread(Geom g, const int32_t* __restric
         ev_xy[base + b0 + pos] = xy;                      // every thread has read its event: the block-local permutation is safe in place
         ev_t[base + b0 + pos] = tm;
         if (WT) ev_w[base + b0 + pos] = wgt;
+        if (IX) ev_i[base + b0 + pos] = src;
     }
 }
 
@@ -256,11 +267,12 @@ struct SegLayout {                 // where the sorted event of rank s (0 <= s <
 constexpr int SORT_NT = 256, SORT_NW = SORT_NT / 64, SORT_KEYS = TS * TS, SORT_KEY_BITS = 10;
 static_assert(SORT_KEYS == 1 << SORT_KEY_BITS, "pixkey has SORT_KEY_BITS bits");
 __device__ __forceinline__ uint32_t pixkey(uint32_t xy) { return ((xy >> 11) & (31u << 5)) | (xy & 31u); }     // pixel inside the 32x32 tile (raster order)
-template <int WT>
+template <int WT, int IX = 0>
 __global__ __launch_bounds__(SORT_NT) void k_segsort(int n_items, const Item* __restrict__ items,
                                                       const uint32_t* __restrict__ src_xy, const double* __restrict__ src_t,
                                                       uint32_t* __restrict__ dst_xy, double* __restrict__ dst_t,
-                                                      const float* __restrict__ src_w, float* __restrict__ dst_w)
+                                                      const float* __restrict__ src_w, float* __restrict__ dst_w,
+                                                      const uint32_t* __restrict__ src_i = nullptr, uint32_t* __restrict__ dst_i = nullptr)
 {
     __shared__ uint32_t cnt[SORT_NW][SORT_KEYS];        // per (wave, key): count, then the running output rank
     __shared__ uint32_t wsum[SORT_NT];
@@ -298,13 +310,21 @@ __global__ __launch_bounds__(SORT_NT) void k_segsort(int n_items, const Item* __
         // placement: a wave walks its quarter in input order; lanes of a step that share a key are ranked by lane
         const SegLayout L(n);
         // (the next step's events are fetched before this step is ranked: the steps of a wave depend on each other through LDS only)
-        uint32_t nxy = 0u; double nt = 0.0; float nw = 0.0f;
-        if (lo + lane < hi) { nxy = src_xy[begin + lo + lane]; nt = src_t[begin + lo + lane]; if (WT) nw = src_w[begin + lo + lane]; }
+        uint32_t nxy = 0u; double nt = 0.0; float nw = 0.0f; uint32_t ni = 0u;
+        if (lo + lane < hi) {
+            nxy = src_xy[begin + lo + lane]; nt = src_t[begin + lo + lane];
+            if (WT) nw = src_w[begin + lo + lane];
+            if (IX) ni = src_i[begin + lo + lane];
+        }
         for (int i0 = lo; i0 < hi; i0 += 64) {                  // wave-uniform trip count
             const int i = i0 + lane;
             const bool valid = i < hi;
-            const uint32_t xy = nxy; const double t = nt; const float wgt = nw;
-            if (i + 64 < hi) { nxy = src_xy[begin + i + 64]; nt = src_t[begin + i + 64]; if (WT) nw = src_w[begin + i + 64]; }
+            const uint32_t xy = nxy; const double t = nt; const float wgt = nw; const uint32_t src = ni;
+            if (i + 64 < hi) {
+                nxy = src_xy[begin + i + 64]; nt = src_t[begin + i + 64];
+                if (WT) nw = src_w[begin + i + 64];
+                if (IX) ni = src_i[begin + i + 64];
+            }
             const int key = valid ? (int)pixkey(xy) : -1;
             // the lanes that share a key, found bit by bit (SORT_KEYS = 2^10: ten ballots instead of one LDS round per distinct key of the step)
             unsigned long long grp = __ballot(valid);
@@ -324,10 +344,24 @@ __global__ __launch_bounds__(SORT_NT) void k_segsort(int n_items, const Item* __
                 dst_xy[begin + pos] = xy;
                 dst_t[begin + pos] = t;
                 if (WT) dst_w[begin + pos] = wgt;
+                if (IX) dst_i[begin + pos] = src;
             }
         }
         __syncthreads();                                        // cnt is reused by the next segment of this workgroup
     }
+}
+
+// k_reweight: new weights for the staged events of a keep-order batch (eincm_set_weights).  w_raw holds one
+// weight per event in the order the batch was handed over; every staged slot of the two layouts fetches its own through the index that
+// staging kept.  One thread per slot: the index reads and both stores are coalesced, the gather of w_raw is the only scattered access.
+// Every idx value lies in [0, n): staging wrote each slot of [0, n) from an event of the batch.
+__global__ __launch_bounds__(NT) void k_reweight(int64_t n, const float* __restrict__ w_raw, const uint32_t* __restrict__ idx,
+                                                 const uint32_t* __restrict__ idx_g, float* __restrict__ ev_w, float* __restrict__ ev_w_g)
+{
+    const int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x;
+    if (i >= n) return;
+    ev_w[i] = w_raw[idx[i]];
+    ev_w_g[i] = w_raw[idx_g[i]];
 }
 
 // thread per (window, tile): emit its segments

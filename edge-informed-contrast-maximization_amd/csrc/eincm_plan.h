@@ -253,11 +253,14 @@ struct EventRefusal {
 inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int16_t* const* xs, const int16_t* const* ys,
                                const double* const* ts, const double* edge_ts, int64_t N, std::vector<int32_t>& tilecount,
                                std::vector<uint32_t>& sxy, std::vector<double>& st, std::vector<unsigned>& cntmax,
-                               std::vector<double>& dtmax, const float* const* weights = nullptr, std::vector<float>* sw = nullptr) {
+                               std::vector<double>& dtmax, const float* const* weights = nullptr, std::vector<float>* sw = nullptr,
+                               std::vector<uint32_t>* sidx = nullptr) {
     // sw (a weighted batch): the weights in the order of sxy, ones for a window without (weights[b] NULL); events of weight 0 are
-    // not counted into cntmax
+    // not counted into cntmax.  sidx (a keep-order batch): where the event of every slot of sxy stood in the batch
+    // as it was handed over, window after window
     const int H = g.H, W = g.W;
     if (sw) sw->resize((size_t)std::max<int64_t>(N, 1));
+    if (sidx) sidx->resize((size_t)std::max<int64_t>(N, 1));
     tilecount.assign((size_t)g.B * g.ntiles, 0);
     sxy.resize((size_t)std::max<int64_t>(N, 1));
     st.resize((size_t)std::max<int64_t>(N, 1));
@@ -288,10 +291,21 @@ inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int
             sxy[d] = (uint32_t)(uint16_t)x[i] | ((uint32_t)(uint16_t)y[i] << 16);
             st[d] = t[i];
             if (sw) (*sw)[d] = wb ? wb[i] : 1.0f;
+            if (sidx) (*sidx)[d] = (uint32_t)(base + i);
         }
         base += n;
     }
     return EventRefusal{};
+}
+
+// The most events of weight > 0 on one source pixel of a window (WinConst.cntmax before its floor of 1), as bin_events counts it: xy
+// are the window's n events as x | y << 16, w their weights (NULL: ones).  What a re-weighting of a host-binned batch recomputes.
+inline unsigned most_on_one_pixel(int H, int W, int64_t n, const uint32_t* xy, const float* w) {
+    std::vector<uint32_t> pc((size_t)H * W, 0u);
+    unsigned m = 0u;
+    for (int64_t i = 0; i < n; ++i)
+        if (!w || w[i] > 0.0f) m = std::max(m, ++pc[(size_t)(xy[i] >> 16) * W + (xy[i] & 0xffffu)]);
+    return m;
 }
 
 // One edge image to fp32 with its moments: the sum, the sum of squares and the largest magnitude of the fp32 values
@@ -345,6 +359,7 @@ struct StagePlan {
     bool defer_constants = false;       // EINCM_SW_DEFER_CONSTANTS: the caller sums the shards' IUEs before the window constants are formed
     bool wide = false;                  // a window has a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel)
     bool weighted = false;              // a window with events carries per-event weights: the payload ev_w rides beside ev_xy / ev_t and the event kernels run their weighted forms
+    bool keep_order = false;            // EINCM_SW_KEEP_ORDER: both layouts keep the index of every slot into the batch as handed over, and the batch is a weighted one whatever it was handed, so a later eincm_set_weights changes no plan
 };
 
 // Does a staging carry per-event weights?  weights: NULL, or one pointer per window, NULL where a window's weights are all ones.
@@ -407,7 +422,8 @@ struct StageKnobs {
 inline StagePlan plan_staging(const PlanCtx& c, int n_windows, int n_refs, const int64_t* n_events, uint32_t flags, const StageKnobs& k,
                               const float* const* weights = nullptr) {
     StagePlan P;
-    P.weighted = batch_weighted(n_windows, n_events, weights);
+    P.keep_order = (flags & EINCM_SW_KEEP_ORDER) != 0;
+    P.weighted = P.keep_order || batch_weighted(n_windows, n_events, weights);
     const int H = c.H, W = c.W;
     Geom& g = P.g;
     g.H = H; g.W = W; g.R = n_refs; g.B = n_windows;

@@ -796,6 +796,28 @@ def event_weights_refusal(precision, splat_window, sharded=False):
     return None
 
 
+def keep_order_refusal(precision, splat_window, sharded=False):
+    """Why a batch cannot be staged with keep_order=True on an engine of this precision and splat window (a
+    keep-order batch is a weighted one whatever it is handed, so it is refused where weights are, in its own words), or None.
+    csrc/eincm_api.hip (check_staging) refuses the same."""
+    if precision == 'fp64':
+        return 'keep_order is not supported in fp64 mode'
+    if int(splat_window) != 3:
+        return f'keep_order has the 3x3 splat window only, the engine has {int(splat_window)}'
+    if sharded:
+        return 'keep_order is not supported by the event-sharded engine (defer_constants)'
+    return None
+
+
+def check_weight_list(weights, n_events):
+    """The argument of Engine.set_weights, checked without a GPU: a list of one entry per staged window, each None (ones) or the
+    window's weights as check_event_weights takes them.  Returns the list of float32 arrays and Nones."""
+    n = np.asarray(n_events, dtype=np.int64).reshape(-1)
+    if weights is None or isinstance(weights, np.ndarray) or not hasattr(weights, '__len__') or len(weights) != n.size:
+        raise ValueError(f'weights must be a list of {n.size} entries, one per staged window (an array, or None for ones)')
+    return [None if w is None else check_event_weights(w, int(n[b])) for b, w in enumerate(weights)]
+
+
 def motion_fused_refusal(precision, splat_window, params, weighted=False):
     """Why the fused path does not apply to this engine and these parameters (csrc/eincm_motion.h: motion_fused_supported, the part of
     it that Python can see before a GPU call), or None.  weighted: the staged batch carries per-event weights."""
@@ -872,6 +894,7 @@ class Engine:
         self.motion_model = None           # the motion.MotionModel of loss_grad_motion / motion_field (set_motion_model)
         self.motion_path = 'expanded'      # how loss_grad_motion evaluates (set_motion_path): 'expanded' | 'fused' | 'auto'
         self._weighted = False             # the staged batch carries per-event weights (set_windows; the property `weighted`)
+        self._keep_order = False           # the staged batch kept its event order (set_windows(..., keep_order=True); the property `keep_order`)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -928,11 +951,19 @@ class Engine:
         return value, grad, None if aux is None else [{k: getattr(a, k) for k, _ in L.Aux._fields_} for a in aux]
 
     # -- staging ----------------------------------------------------------------------------------
-    def set_windows(self, windows, defer_constants=False):
+    def set_windows(self, windows, defer_constants=False, keep_order=False):
         """windows: list of (xs, ys, ts, edges, edge_ts) tuples (the reference's datasample tuple), or of 6-tuples whose last element
         is the window's per-event weights (check_event_weights) or None for ones - the two may be mixed.
-        defer_constants: event-sharded mode (see sharding.ShardedEngine): stage only, finish with finish_constants()."""
+        defer_constants: event-sharded mode (see sharding.ShardedEngine): stage only, finish with finish_constants().
+        keep_order: staging keeps the index from its sorted copies of the events back to the order handed over (DESIGN.md section
+        29), so the batch takes new weights in place: set_weights, apply_responsibilities.  Such a batch is a weighted one whatever
+        it was handed (all-ones weights give the unweighted batch's bits)."""
         B = len(windows)
+        keep_order = bool(keep_order)
+        if keep_order:
+            why = keep_order_refusal(self.precision, self.splat_window, sharded=defer_constants)
+            if why is not None:
+                raise ValueError(why)
         for b, w in enumerate(windows):
             if len(w) not in (5, 6):
                 raise ValueError(f'window {b}: a (xs, ys, ts, edges, edge_ts) or (xs, ys, ts, edges, edge_ts, weights) tuple, got {len(w)} elements')
@@ -961,9 +992,9 @@ class Engine:
         one = np.zeros(1, np.int16), np.zeros(1, np.float64)           # a valid address for empty windows
         def ptrs(arrs, dummy):
             return (C.c_void_p * B)(*[(a if a.size else dummy).ctypes.data for a in arrs])
-        flags = L.SW_DEFER_CONSTANTS if defer_constants else 0
-        if weighted:        # one float pointer per window, NULL where a window has none
-            wp = (C.c_void_p * B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
+        flags = (L.SW_DEFER_CONSTANTS if defer_constants else 0) | (L.SW_KEEP_ORDER if keep_order else 0)
+        if weighted or keep_order:        # one float pointer per window, NULL where a window has none (or for all of them)
+            wp = None if not weighted else (C.c_void_p * B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
             rc = self._lib.eincm_set_windows_weighted(self._ctx, B, R, n.ctypes.data_as(C.POINTER(C.c_int64)),
                                                       ptrs(xs, one[0]), ptrs(ys, one[0]), ptrs(ts, one[1]), ptrs(edges, one[1]),
                                                       _dp(edge_ts), wp, flags)
@@ -972,17 +1003,71 @@ class Engine:
                                                   ptrs(xs, one[0]), ptrs(ys, one[0]), ptrs(ts, one[1]), ptrs(edges, one[1]),
                                                   _dp(edge_ts), flags)
         self._weighted = False          # (a refused staging leaves nothing staged)
+        self._keep_order = False
         self._staged_weights = None
         self._check(rc)
         if B != self.B:
             self._io = {}
         self.B, self.R = B, R
         self.n_events = n
-        self._weighted = weighted
+        self._weighted = weighted or keep_order
+        self._keep_order = keep_order
         self._staged_weights = ws       # what the windows were handed (None: ones), for event_scores(exclude_self=True)
 
-    def set_window(self, xs, ys, ts, edges, edge_ts, weights=None):
-        self.set_windows([(xs, ys, ts, edges, edge_ts, weights)])
+    def set_window(self, xs, ys, ts, edges, edge_ts, weights=None, keep_order=False):
+        self.set_windows([(xs, ys, ts, edges, edge_ts, weights)], keep_order=keep_order)
+
+    @property
+    def keep_order(self):
+        """The staged batch kept its event order (set_windows(..., keep_order=True)): set_weights and apply_responsibilities serve it."""
+        return getattr(self, '_keep_order', False)
+
+    def _need_keep_order(self, who):
+        if not self.keep_order:
+            raise ValueError(f'{who} needs a batch staged with keep_order=True (set_windows): without it staging keeps no index back to '
+                             'the order of its events')
+
+    def set_weights(self, weights):
+        """New per-event weights for the staged events, in place: a list of B entries, each None (ones) or the
+        window's weights as check_event_weights takes them.  The batch must have been staged with keep_order=True.  Everything is
+        checked before anything is touched: a refused call leaves the staged batch and its last evaluation as they were.  Afterwards
+        the engine answers as after a fresh set_windows of the same windows with these weights and keep_order=True, byte for byte; the
+        last evaluation is gone, as after a staging."""
+        ws = check_weight_list(weights, self.n_events if self.B else [])
+        self._need_keep_order('set_weights')
+        wp = None
+        if any(w is not None and w.size for w in ws):
+            wp = (C.c_void_p * self.B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
+        self._check(self._lib.eincm_set_weights(self._ctx, wp))
+        self._staged_weights = ws
+
+    def staged_weights(self):
+        """The staged weights of a keep-order batch, downloaded: a list of B float32 (n_b,) arrays in the order the events were handed
+        over, ones where a window was handed none - what the last set_windows, set_weights or apply_responsibilities left."""
+        self._need_keep_order('staged_weights')
+        w = np.empty(int(self.n_events.sum()), dtype=np.float32)
+        self._check(self._lib.eincm_get_staged_weights(self._ctx, w.ctypes.data))
+        off = np.concatenate([[0], np.cumsum(self.n_events)]).astype(np.int64)
+        return [w[off[b]:off[b + 1]] for b in range(self.B)]
+
+    def staged_order(self):
+        """(order_splat, order_gather) of a keep-order batch, (N,) uint32 each: for every slot of the splat's and of the gather's copy of
+        the events, the position of its event in the batch as handed over, window after window.  For tests and tools."""
+        self._need_keep_order('staged_order')
+        n = int(self.n_events.sum())
+        a, b = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        self._check(self._lib.eincm_get_stage_order(self._ctx, a.ctypes.data, b.ctypes.data))
+        return a, b
+
+    def _self_weights(self):
+        """The weights exclude_self subtracts the events' own shares with: a keep-order batch's come from the device (they may have
+        been set there), any other's are what set_windows was handed."""
+        if self.keep_order:
+            return self.staged_weights()
+        ws = getattr(self, '_staged_weights', None)
+        if ws is None or len(ws) != self.B:
+            raise ValueError('exclude_self needs the weights the batch was staged with, and this engine does not hold them: stage with set_windows')
+        return ws
 
     @property
     def weighted(self):
@@ -1622,15 +1707,13 @@ class Engine:
         images: (B,R,H,W), or (R,H,W) when B == 1; None takes the IWEs of the last evaluation (read on the device).
         ref_weights: None gives one (R, n_b) float32 array per window; (R,) finite numbers give (n_b,), the weighted sum over the
         reference times.  exclude_self: subtract the event's own share w_e * sum_d k(d)^2, the leave-one-out score against the IWE;
-        w is what ``set_windows`` was handed, or ones.  theta with params: ``loss_grad(theta, params, want_grad=False)`` runs first.
+        w is what ``set_windows`` was handed, or ones (a keep-order batch: ``staged_weights()``).  theta with params: ``loss_grad(theta, params, want_grad=False)`` runs first.
         Returns the list of the B arrays, events in the order they were staged."""
         if (theta is None) != (params is None):
             raise ValueError('theta and params go together: both, or neither (the last evaluation)')
         imgs = check_score_images(images, self.B, self.R, (self.H, self.W))
         rw = check_ref_weights(ref_weights, self.R)
-        ws = getattr(self, '_staged_weights', None)
-        if exclude_self and (ws is None or len(ws) != self.B):
-            raise ValueError('exclude_self needs the weights the batch was staged with, and this engine does not hold them: stage with set_windows')
+        ws = self._self_weights() if exclude_self else None
         if theta is not None:
             self.loss_grad(theta, params, want_grad=False)
         off, length, total = event_scores_layout(self.n_events if self.B else [], self.R, rw is not None)
@@ -1659,13 +1742,30 @@ class Engine:
         handed.  want: which of RS_OUTPUTS to fetch.  Returns a dict of those: 'weights' a list of B float32 (n_b,) arrays, what
         set_windows takes back; 'labels' a list of G uint8 (n_g,) arrays, the lowest model with the largest share; 'mass' (G,
         n_models) float64, each window's sum of weights; 'n_unsupported' (G,) int64, the events no model supports (they get the
-        prior's shares)."""
-        K, pi, want = check_responsibility_args(n_models, self.n_events if self.B else [], prior, want)
+        prior's shares).  A keep-order batch's leave-one-out score reads the staged weights on the device (EINCM_RS_STAGED_WEIGHTS)."""
+        return self._responsibilities(n_models, images, ref_weights, prior, exclude_self, want, False)
+
+    def apply_responsibilities(self, n_models, images=None, ref_weights=None, prior=None, exclude_self=True, want=('labels', 'mass')):
+        """event_responsibilities whose result becomes the staged weights of all B windows, in place (EINCM_RS_APPLY, DESIGN.md section
+        29): after the responsibilities are formed on the device they are gathered into the staged layouts as set_weights would, with
+        no host round trip in between.  The batch must have been staged with keep_order=True.  ``want`` may leave 'weights' out, so that
+        nothing per-event is downloaded, or be empty; what it names are the bytes event_responsibilities returns, and the engine is
+        left as event_responsibilities followed by a set_windows with its 'weights' would leave it.  Returns the dict of ``want``."""
+        self._need_keep_order('apply_responsibilities')
+        return self._responsibilities(n_models, images, ref_weights, prior, exclude_self, want, True)
+
+    def _responsibilities(self, n_models, images, ref_weights, prior, exclude_self, want, apply):
+        if apply and isinstance(want, (tuple, list)) and len(want) == 0:
+            K, pi, _ = check_responsibility_args(n_models, self.n_events if self.B else [], prior, RS_OUTPUTS)
+            want = ()
+        else:
+            K, pi, want = check_responsibility_args(n_models, self.n_events if self.B else [], prior, want)
         imgs = check_score_images(images, self.B, self.R, (self.H, self.W))
         rw = check_ref_weights(multi_ref_weights(self.R) if ref_weights is None else ref_weights, self.R)
-        ws = getattr(self, '_staged_weights', None)
-        if exclude_self and (ws is None or len(ws) != self.B):
-            raise ValueError('exclude_self needs the weights the batch was staged with, and this engine does not hold them: stage with set_windows')
+        ws = None if (self.keep_order or not exclude_self) else self._self_weights()
+        flags = (L.RS_EXCLUDE_SELF if exclude_self else 0) | (L.RS_APPLY if apply else 0)
+        if self.keep_order and exclude_self:
+            flags |= L.RS_STAGED_WEIGHTS
         B, G = self.B, self.B // K
         w_off, w_total, lab_off, lab_len, lab_total = event_responsibilities_layout(self.n_events if B else [], K)
         weights = np.empty(w_total, dtype=np.float32) if 'weights' in want else None
@@ -1673,11 +1773,13 @@ class Engine:
         mass = np.zeros(B, dtype=np.float64) if 'mass' in want else None                # (a batch without events writes nothing)
         n_uns = np.zeros(G, dtype=np.int64) if 'n_unsupported' in want else None
         wp = None
-        if exclude_self and any(w is not None and w.size for w in ws):
+        if ws is not None and any(w is not None and w.size for w in ws):
             wp = (C.c_void_p * B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
         addr = lambda a: None if a is None else a.ctypes.data
-        self._check(self._lib.eincm_event_responsibilities(self._ctx, K, addr(imgs), addr(rw), wp, addr(pi), L.RS_EXCLUDE_SELF if exclude_self else 0,
+        self._check(self._lib.eincm_event_responsibilities(self._ctx, K, addr(imgs), addr(rw), wp, addr(pi), flags,
                                                            addr(weights), addr(labels), addr(mass), addr(n_uns)))
+        if apply:
+            self._staged_weights = None     # (they are the device's now: staged_weights())
         out = {}
         if weights is not None:
             out['weights'] = [weights[w_off[b]:w_off[b] + int(self.n_events[b])] for b in range(B)]

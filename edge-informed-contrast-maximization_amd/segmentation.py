@@ -3,8 +3,9 @@
 K motion models on one event list are K windows of a batch that share the events and carry complementary per-event weights
 (section 22).  The M-step solves every model on its weighted events (batch_solver.minimize_motion, section 20); the E-step scores every
 event under every model, leave-one-out against that model's image of warped events, and normalises over the models
-(Engine.event_responsibilities, one device operation).  Staging keeps no index back to the caller's order, so every iteration stages
-the batch again with the new weights.
+(Engine.event_responsibilities, one device operation).  segment_motions stages the batch again with the new weights in every
+iteration; segment_motions_in_place stages it once with keep_order=True and lets every E-step write its result
+straight into the staged layouts (Engine.apply_responsibilities).  The two return the same bytes.
 
 The EM is local and needs starting coefficients.  seed_motions finds them without a gradient: a coarse-to-fine
 grid search on the contrast landscape (Engine.contrast_landscape), one motion after the other, each on the events that the motions
@@ -18,9 +19,13 @@ from . import motion
 PRIORS = ('mass', 'uniform')
 
 
-def check_segment_args(windows, model, coeffs0, n_iters, weights0, prior, min_mass):
-    """The arguments of segment_motions, checked without a GPU.  Returns (coeffs0 (G,K,n_coeffs) float64, weights0 as G lists of K
-    float32 arrays or None)."""
+def check_segment_args(windows, model, coeffs0, n_iters, weights0, prior, min_mass, in_place=False, record_weights=True):
+    """The arguments of segment_motions and segment_motions_in_place, checked without a GPU.  Returns (coeffs0 (G,K,n_coeffs) float64,
+    weights0 as G lists of K float32 arrays or None)."""
+    if not isinstance(in_place, (bool, np.bool_)) or not isinstance(record_weights, (bool, np.bool_)):
+        raise ValueError(f'in_place and record_weights must be True or False, got {in_place!r} and {record_weights!r}')
+    if not in_place and not record_weights:
+        raise ValueError('record_weights=False goes with in_place=True: the restaging route holds the weights on the host anyway')
     G = len(windows)
     if G < 1:
         raise ValueError('windows must hold at least one (xs, ys, ts, edges, edge_ts) tuple')
@@ -69,19 +74,45 @@ def segment_motions(engine, windows, model, coeffs0, params, n_iters=5, maxiter=
     solved coefficients so that every IWE is current, and takes the responsibilities as the next weights.  Returns a list of n_iters
     dicts: 'coeffs' (G,K,n_coeffs), 'weights' (G lists of K float32 arrays), 'labels' (G uint8 arrays), 'mass' (G,K),
     'n_unsupported' (G,), 'results' (G lists of K OptimizeResult, None for a frozen model), 'active' (G,K) bool."""
-    c, weights = check_segment_args(windows, model, coeffs0, n_iters, weights0, prior, min_mass)
+    return _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, False, True)
+
+
+def segment_motions_in_place(engine, windows, model, coeffs0, params, n_iters=5, maxiter=25, gtol=1e-6, weights0=None, prior='mass',
+                             min_mass=1.0, callback=None, record_weights=True):
+    """segment_motions with in_place=True: the G*K windows are staged once with keep_order=True, weights0 goes in
+    through Engine.set_weights, and every E-step applies its own result on the device (Engine.apply_responsibilities) - no per-event
+    download, no restaging.  The history is byte-equal to segment_motions' in 'coeffs', 'weights', 'labels', 'mass', 'n_unsupported' and
+    'active': the engine is bit-reproducible and the staged layouts are the same.  A record's 'weights' are fetched by
+    Engine.staged_weights(); record_weights=False leaves them out (None), and nothing per-event crosses to the host but the labels."""
+    return _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, True, record_weights)
+
+
+def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, in_place, record_weights):
+    c, weights = check_segment_args(windows, model, coeffs0, n_iters, weights0, prior, min_mass, in_place, record_weights)
     G, K = c.shape[:2]
     want = ('weights', 'labels', 'mass', 'n_unsupported')
     engine.set_motion_model(model)
     engine.set_motion_path('expanded')
+    staged_once = []
 
     def stage(wts):
-        engine.set_windows([tuple(windows[g]) + (None if wts is None else wts[g][l],) for g in range(G) for l in range(K)])
+        if not in_place:
+            engine.set_windows([tuple(windows[g]) + (None if wts is None else wts[g][l],) for g in range(G) for l in range(K)])
+        elif not staged_once:           # the one staging: the windows as they are; the weights go in like every later set
+            engine.set_windows([tuple(windows[g]) for g in range(G) for l in range(K)], keep_order=True)
+            staged_once.append(True)
+            if wts is not None:
+                engine.set_weights([wts[g][l] for g in range(G) for l in range(K)])
+        elif wts is not None:           # (None: the E-step has applied its own result)
+            engine.set_weights([wts[g][l] for g in range(G) for l in range(K)])
 
     def e_step(coeffs, pi):
         engine.loss_grad_motion(coeffs.reshape(G * K, -1), params, want_grad=False, allow_nonfinite=True)
-        r = engine.event_responsibilities(K, prior=pi, exclude_self=True, want=want)
-        return [[np.array(r['weights'][g * K + l]) for l in range(K)] for g in range(G)], r
+        if not in_place:
+            r = engine.event_responsibilities(K, prior=pi, exclude_self=True, want=want)
+            return [[np.array(r['weights'][g * K + l]) for l in range(K)] for g in range(G)], r
+        r = engine.apply_responsibilities(K, prior=pi, exclude_self=True, want=want[1:])
+        return None, r
 
     def mixing(mass):
         if prior == 'uniform':
@@ -106,7 +137,11 @@ def segment_motions(engine, windows, model, coeffs0, params, n_iters=5, maxiter=
                       for b in range(G * K)]).reshape(G, K, -1)
         weights, r = e_step(c, pi)
         pi = mixing(r['mass'])
-        record = dict(coeffs=c.copy(), weights=weights, labels=[np.array(a) for a in r['labels']], mass=r['mass'].copy(),
+        recorded = weights              # (in place: None, the weights are the device's and the next stage() has nothing to hand over)
+        if in_place and record_weights:
+            w = engine.staged_weights()
+            recorded = [[np.array(w[g * K + l]) for l in range(K)] for g in range(G)]
+        record = dict(coeffs=c.copy(), weights=recorded, labels=[np.array(a) for a in r['labels']], mass=r['mass'].copy(),
                       n_unsupported=r['n_unsupported'].copy(), results=[results[g * K:(g + 1) * K] for g in range(G)], active=active.copy())
         history.append(record)
         if callback is not None:

@@ -1,6 +1,7 @@
 """Per-event scores closing the loop from a solved motion back to the events: a synthetic window of moving edges
 plus a known set of uniform noise events is solved, every event is scored by how much of the OTHER events' IWE lies under it once it
-is warped (the leave-one-out score), the scores become per-event weights, and the window is staged with them and solved again.
+is warped (the leave-one-out score), the scores become per-event weights, and the window, staged with keep_order=True, takes them in
+place (Engine.set_weights) and is solved again.
 
     python3 examples/event_scores.py [--events 30000] [--noise 10000]
 
@@ -38,13 +39,13 @@ ds = dict(events=dict(x=xs, y=ys, t=ts), image_ts=win['edge_ts'], eval_ts=(0.0, 
 params = engine.make_params(20.0, 35.0, 0.0, 0.0, 1)
 truth = win['flow_gt'][0, 0]
 with engine.Engine((H, W), n, max_refs=R) as eng:
-    eng.set_windows([staging.stage_datasample(ds, edges=win['edges'])])
+    eng.set_windows([staging.stage_datasample(ds, edges=win['edges'])], keep_order=True)
     first = bsol.minimize_thetas(eng, np.zeros((1, 1, 1, 2)), params, maxiter=60, gtol=1e-6)[0]
     th1 = np.asarray(first.x).reshape(1, 1, 1, 2)
     # (R, n): the IWE of the solved theta under each warped event, the event's own share taken out
     scores = eng.event_scores(exclude_self=True, theta=th1, params=params)[0]
     weights = staging.weights_from_scores(scores)
-    eng.set_windows([staging.stage_datasample(ds, edges=win['edges'], event_weights=weights)])
+    eng.set_weights([weights])                                                 # the staged events stay where they are
     second = bsol.minimize_thetas(eng, np.zeros((1, 1, 1, 2)), params, maxiter=60, gtol=1e-6)[0]
 
 mean = scores.mean(axis=0)

@@ -35,7 +35,8 @@ extern "C" {
                                *    filter), eincm_event_scores (an image stack sampled at the warped events), eincm_theta_advect (a solved theta
                                *    carried along its own flow to the next window), eincm_event_responsibilities (those scores normalised over
                                *    the models of a group: the E-step of a motion segmentation), eincm_contrast_landscape (the integer contrast of
-                               *    the warped events on a grid of candidate motion coefficients) */
+                               *    the warped events on a grid of candidate motion coefficients), eincm_set_weights, eincm_get_stage_order,
+                               *    eincm_get_staged_weights (a batch staged with EINCM_SW_KEEP_ORDER takes new weights in place) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -177,6 +178,13 @@ int eincm_set_windows(eincm_ctx* ctx, int n_windows, int n_refs, const int64_t* 
 /* eincm_set_windows with flags.  EINCM_SW_DEFER_CONSTANTS: stage only; the zero-warp constants are finished later by
  * eincm_forward_iwe(theta = NULL) -> [sum the IWE stacks of all shards] -> eincm_finish_constants (event-sharded mode). */
 #define EINCM_SW_DEFER_CONSTANTS 1u
+/* EINCM_SW_KEEP_ORDER (eincm_set_windows_ex, _ptrs, _weighted): staging keeps, beside each of its two sorted copies
+ * of the events, the position of every slot's event in the batch as it was handed over (4 B per event and copy), and the weights in
+ * that order (4 B per event; ones where a window was handed none).  Such a batch is a weighted batch whatever it was handed (all-ones
+ * weights give the unweighted batch's bits), with the refusals of one: EINCM_ERR_UNSUPPORTED on a float64 context, with a splat window
+ * other than 3, with EINCM_SW_DEFER_CONSTANTS.  It takes new weights without being staged again: eincm_set_weights, and
+ * eincm_event_responsibilities with EINCM_RS_APPLY.  The three buffers are allocated by the first staging that asks for them. */
+#define EINCM_SW_KEEP_ORDER      2u
 int eincm_set_windows_ex(eincm_ctx* ctx, int n_windows, int n_refs, const int64_t* n_events,
                          const int16_t* xs, const int16_t* ys, const double* ts,
                          const double* edges, const double* edge_ts, uint32_t flags);
@@ -196,6 +204,23 @@ int eincm_set_windows_ptrs(eincm_ctx* ctx, int n_windows, int n_refs, const int6
 int eincm_set_windows_weighted(eincm_ctx* ctx, int n_windows, int n_refs, const int64_t* n_events,
                                const int16_t* const* xs, const int16_t* const* ys, const double* const* ts,
                                const double* const* edges, const double* edge_ts, const float* const* weights, uint32_t flags);
+
+/* New weights for the staged events, in place.  weights: NULL, or one host pointer per staged window, each NULL
+ * (ones) or n_events[b] floats, finite and within [0, 1], in the order the window's events were handed over.  One upload, one gather
+ * through the indices that EINCM_SW_KEEP_ORDER kept, and what staging derives from the weights is formed again: the event mask, the
+ * most events on one pixel, the zero-warp constants.  Edges, segment lists and the events themselves are left alone.  Afterwards the
+ * context answers every call with the bytes of a fresh eincm_set_windows_weighted(..., weights, EINCM_SW_KEEP_ORDER) of the same
+ * windows; the last evaluation, a BFGS begun and the launch policy's evaluation are gone, as after a staging.  Refused before anything
+ * is touched (the staged batch and its last evaluation stay): EINCM_ERR_STATE nothing staged, an evaluation in flight, or a batch
+ * staged without EINCM_SW_KEEP_ORDER; EINCM_ERR_ARG a weight out of range or not finite. */
+int eincm_set_weights(eincm_ctx* ctx, const float* const* weights);
+/* The indices a keep-order staging kept: for every slot of the splat's copy of the events (order_splat) and of the gather's
+ * (order_gather), sum(n_events) values each, the position of its event in the batch as handed over.  Either may be NULL.  For tests and
+ * tools.  EINCM_ERR_STATE without a batch staged with EINCM_SW_KEEP_ORDER. */
+int eincm_get_stage_order(eincm_ctx* ctx, uint32_t* order_splat, uint32_t* order_gather);
+/* The staged weights of a keep-order batch in the order the events were handed over, window after window: sum(n_events) floats, what
+ * the last staging, eincm_set_weights or EINCM_RS_APPLY left.  EINCM_ERR_STATE without a batch staged with EINCM_SW_KEEP_ORDER. */
+int eincm_get_staged_weights(eincm_ctx* ctx, float* weights);
 
 /* value_and_grad(loss_func) for every staged window (losses.py:108-205 + its reverse pass).
  *   theta  (n_windows, h, w, 2)     value (n_windows)     grad (n_windows, h, w, 2) or NULL (forward only)
@@ -301,7 +326,7 @@ int eincm_event_scores(eincm_ctx* ctx, const float* images, const double* ref_we
  *   ref_weights   n_refs finite doubles (required)
  *   weights_in    NULL, or B host pointers, each NULL or n_events[b] floats: what the windows were staged with
  *   prior         NULL (ones) or B doubles pi, each finite and >= 0 as a float, every group's float sum positive and finite
- *   flags         EINCM_RS_EXCLUDE_SELF or 0; other bits are reserved
+ *   flags         0 or any of EINCM_RS_EXCLUDE_SELF, EINCM_RS_STAGED_WEIGHTS, EINCM_RS_APPLY (the last two: below); other bits are reserved
  *   weights_out   NULL, or window b's block of n_events[b] floats w', the blocks one after another: what
  *                 eincm_set_windows_weighted takes back
  *   labels        NULL, or one byte per event of a group, group after group: the lowest l with the largest p_l
@@ -312,9 +337,15 @@ int eincm_event_scores(eincm_ctx* ctx, const float* images, const double* ref_we
  * EINCM_ERR_STATE nothing staged or no evaluation yet; EINCM_ERR_UNSUPPORTED an EINCM_CF_FP64 context, a splat window other than 3,
  * an event-sharded staging; EINCM_ERR_ARG n_models outside 1 .. EINCM_RS_MAX_MODELS, B not a multiple of n_models, unequal n_events
  * inside a group, ref_weights NULL or not finite, a bad prior; EINCM_ERR_STATE images == NULL after an evaluation that left windows
- * out.  A batch with no events at all is valid and writes nothing. */
+ * out.  A batch with no events at all is valid and writes nothing.
+ * A batch staged with EINCM_SW_KEEP_ORDER has two more flags (without such a batch either is EINCM_ERR_STATE,
+ * checked after the refusals above).  EINCM_RS_STAGED_WEIGHTS: w_l is the context's own copy of the staged weights and weights_in must
+ * be NULL (EINCM_ERR_ARG otherwise).  EINCM_RS_APPLY: the w' become the staged weights of all B windows as eincm_set_weights would set
+ * them, without leaving the device; the four outputs may then all be NULL, and those given are the same bytes as without the flag. */
 #define EINCM_RS_MAX_MODELS   8
 #define EINCM_RS_EXCLUDE_SELF 1u   /* flags: leave the event's own share out of its score (the leave-one-out score against the IWE) */
+#define EINCM_RS_STAGED_WEIGHTS 2u /* flags: w_l comes from the keep-order batch's staged weights, not from weights_in */
+#define EINCM_RS_APPLY        4u   /* flags: the responsibilities become the staged weights, in place */
 int eincm_event_responsibilities(eincm_ctx* ctx, int n_models, const float* images, const double* ref_weights,
                                  const float* const* weights_in, const double* prior, uint32_t flags,
                                  float* weights_out, uint8_t* labels, double* mass, int64_t* n_unsupported);

@@ -1,0 +1,105 @@
+"""The inputs of tests/test_gpu_reweight.py and of its child process tests/_reweight_probe.py.  Not a test module.
+
+batch(): a 64 x 96 sensor (2 x 3 tiles of 32 x 32), R = 2, B = 4 -
+  window 0: 3000 events, 1500 of them in tile 1 (several 1024-event bin blocks, several 256-event blocks of k_spread and a trailing
+            partial one, a k_segsort segment with many equal keys), 300 of those on one pixel;
+  window 1: 300 events;  window 2: empty;  window 3: 700 events, handed no weights in either set.
+Two weight sets with exact zeros, exact ones and values between; the second puts its zeros on other pixels than the first, whole
+pixels among them, so the event mask differs between the two.
+
+e_step_batch(): two groups of two models - a two-layer scene of 2000 events and one of 300 - for the applying E-step.
+two_layer(): the small two-layer scene of the EM drivers, about 2000 events."""
+import numpy as np
+
+H, W, R, B = 64, 96, 2, 4
+N = (3000, 300, 0, 700)
+CROWD = (40, 9)                     # (x, y) of the pixel that holds 300 events of window 0, in tile 1
+ALPHA, BETA, GAMMA = 20.0, 35.0, 2.5e-4
+
+_cache = {}
+
+
+def _events(rng, n, x0=0, x1=W, y0=0, y1=H):
+    return rng.integers(x0, x1, n).astype(np.int16), rng.integers(y0, y1, n).astype(np.int16)
+
+
+def _weights(rng, xs, ys, zero_pixels):
+    """{0} u (0, 1) u {1}: every event on a pixel of zero_pixels (y * W + x values) gets exact 0, a fifth of the rest exact 1."""
+    n = len(xs)
+    w = rng.uniform(0.05, 0.95, n)
+    w[rng.random(n) < 0.2] = 1.0
+    w[np.isin(ys.astype(np.int64) * W + xs, zero_pixels)] = 0.0
+    return w.astype(np.float32)
+
+
+def batch(synth):
+    """dict(windows: B (xs, ys, ts, edges, edge_ts) tuples, w1, w2: B entries (float32 array or None), theta8 (B,8,8,2), dense
+    (B,H,W,2), coeffs (B,6) of an affine model)"""
+    if 'batch' not in _cache:
+        rng = np.random.default_rng(2901)
+        wins, w1, w2 = [], [], []
+        for b, n in enumerate(N):
+            base = synth.make_window(2900 + b, (H, W), max(n, 50), R, flow='smooth', flow_mag=6.0)        # the edges and their times
+            if b == 0:
+                xa, ya = _events(rng, 1200, 32, 64, 0, 32)                                               # tile 1
+                xc, yc = np.full(300, CROWD[0], np.int16), np.full(300, CROWD[1], np.int16)              # ... and one pixel of it
+                xb, yb = _events(rng, 1500)
+                xs, ys = np.concatenate([xa, xc, xb]), np.concatenate([ya, yc, yb])
+                p = rng.permutation(n)
+                xs, ys = xs[p], ys[p]
+            else:
+                xs, ys = _events(rng, n)
+            ts = np.sort(rng.uniform(0.0, 1.0, n))
+            wins.append((xs, ys, ts, base['edges'], base['edge_ts']))
+            if b == 3 or n == 0:
+                w1.append(None); w2.append(None)
+                continue
+            pix = np.unique(ys.astype(np.int64) * W + xs)
+            z1 = rng.choice(pix, len(pix) // 6, replace=False)
+            z2 = rng.choice(np.setdiff1d(pix, z1), len(pix) // 6, replace=False)                         # other pixels: the mask must change
+            if b == 0:
+                z2 = np.append(z2, CROWD[1] * W + CROWD[0])                                              # cntmax changes too
+                z1 = z1[z1 != CROWD[1] * W + CROWD[0]]
+            w1.append(_weights(rng, xs, ys, z1)); w2.append(_weights(rng, xs, ys, z2))
+        theta8 = rng.uniform(-6.0, 6.0, (B, 8, 8, 2))
+        dense = rng.uniform(-6.0, 6.0, (B, H, W, 2))
+        coeffs = np.concatenate([rng.uniform(-6.0, 6.0, (B, 2)), rng.uniform(-2.0, 2.0, (B, 4))], axis=1)
+        _cache['batch'] = dict(windows=wins, w1=w1, w2=w2, theta8=theta8, dense=dense, coeffs=coeffs)
+    return _cache['batch']
+
+
+def staged(c, weights):
+    """The window tuples of batch() with a weight set (or None: 5-tuples)"""
+    return [w if weights is None else w + (weights[b],) for b, w in enumerate(c['windows'])]
+
+
+def two_layer(synth, n_layer=1000, seeds=(1, 2), flows=((12.0, 3.0), (-6.0, -9.0)), start=(0.6, 1.4)):
+    """dict(window, coeffs0 (1,2,2)): two transparent layers of constant flow merged by time (tests/_responsibilities_witness.py's
+    driver case at a third of its size)"""
+    key = ('two_layer', n_layer, seeds)
+    if key not in _cache:
+        layers = [synth.make_window(seed, (H, W), n_layer, R, flow=np.broadcast_to(np.array(v), (H, W, 2)).copy(), n_segments=8, n_circles=2,
+                                    jitter_px=0.3, noise_frac=0) for seed, v in zip(seeds, flows)]
+        ts = np.concatenate([l['ts'] for l in layers])
+        order = np.argsort(ts, kind='stable')
+        xs = np.concatenate([l['xs'] for l in layers])[order]
+        ys = np.concatenate([l['ys'] for l in layers])[order]
+        edges = np.maximum(layers[0]['edges'], layers[1]['edges'])
+        f = np.array(flows)
+        _cache[key] = dict(window=(xs, ys, ts[order], edges, layers[0]['edge_ts']), coeffs0=(f * np.array(start)[:, None])[None], flows=f)
+    return _cache[key]
+
+
+def e_step_batch(synth):
+    """dict(windows: 4 tuples (two groups of two models: 2000 and 300 events), w0: 4 weight arrays, coeffs (4, 2) translations)"""
+    if 'e_step' not in _cache:
+        rng = np.random.default_rng(2902)
+        big, small = two_layer(synth), two_layer(synth, n_layer=150, seeds=(3, 4))
+        wins = [big['window'], big['window'], small['window'], small['window']]
+        w0 = []
+        for g in (big, small):
+            a = np.where(rng.random(len(g['window'][0])) < 0.1, 0.0, rng.uniform(0.0, 1.0, len(g['window'][0]))).astype(np.float32)
+            w0 += [a, (np.float32(1.0) - a).astype(np.float32)]
+        coeffs = np.concatenate([big['flows'] * 0.9, small['flows'] * 1.1])
+        _cache['e_step'] = dict(windows=wins, w0=w0, coeffs=coeffs)
+    return _cache['e_step']
