@@ -551,6 +551,44 @@ struct StreamChunk {
     const uint32_t* idx() const { return d_val[cur]; }
 };
 
+// Where window b's events start in the stream order (the batch as handed over: d_raw_*, ord.stream, every per-event array of an operator)
+inline int64_t stream_offset(const int64_t* n_events, int b) { return sc_block_offset(n_events, b, 1, true); }
+
+// The front of the per-event operators on the staged raw events (eincm_event_scores, eincm_event_responsibilities,
+// eincm_contrast_landscape).  Constructed on the call's OneShot after the operator's checks and before begin(), it declares the (B + 1)
+// offset table of the kernels, the frame's first piece, and fills it by the layout function of the operator's contract (the stream order).
+struct RawEvents {
+    OneShot& op; const int B; const int64_t* const ne;                   // the staged windows' event counts
+    const OneShot::Piece<int64_t> d_off; int64_t* const h_off;           // d_off goes up from h_off (upload)
+    int64_t n_max = 0;                                                   // the most events of one window
+    explicit RawEvents(OneShot& op_, int64_t (*offset)(const int64_t* n_events, int b) = stream_offset)
+        : op(op_), B(op.c->g.B), ne(op.c->win_events.data()), d_off(op.piece<int64_t>((size_t)B + 1)), h_off(op.host_buf<int64_t>((size_t)B + 1)) {
+        for (int b = 0; b <= B; ++b) h_off[b] = offset(ne, b);
+        for (int b = 0; b < B; ++b) n_max = std::max(n_max, ne[b]);
+    }
+    int64_t total() const { return h_off[B]; }
+    // Did the last evaluation leave a window of the staged batch out (eincm_loss_grad_masked)?  Its Theta and IWEs are not that window's.
+    static bool masked(const eincm_ctx* c) {
+        for (int b = 0; c->staged && b < c->g.B && b < 64; ++b) if (!((c->eval_wmask >> b) & 1ull)) return true;
+        return false;
+    }
+    hipError_t upload() { return op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)); }
+    // One optional host array per window (the caller's: NULL, or per window NULL or its events' values) as one packed device array in
+    // the stream order plus a `has` byte per window.  any(): some window with events has one - what the two pieces are wanted for.
+    template <typename T> bool any(const T* const* arrays) const {
+        for (int b = 0; arrays && b < B; ++b) if (arrays[b] && ne[b] > 0) return true;
+        return false;
+    }
+    template <typename T> hipError_t upload_per_window(const T* const* arrays, T* piece, uint8_t* has_piece) {
+        uint8_t* h_has = op.host_buf<uint8_t>((size_t)B);
+        for (int b = 0; b < B; ++b) h_has[b] = arrays[b] && ne[b] > 0;
+        if (const hipError_t e = op.up(has_piece, h_has, (size_t)B)) return e;
+        for (int b = 0; b < B; ++b)
+            if (h_has[b]) if (const hipError_t e = op.up(piece + h_off[b], arrays[b], (size_t)ne[b] * sizeof(T))) return e;
+        return hipSuccess;
+    }
+};
+
 // ---- the environment: every read, one function per lifetime ----
 const EvalKnobs& process_knobs() {     // once per process, at the first evaluation of a context that is not float64
     static const EvalKnobs k{getenv("EINCM_NO_BIG_THETA_ARG") != nullptr, getenv("EINCM_NO_HOST_ASM") != nullptr,
@@ -1628,33 +1666,44 @@ static int upload_raw_events(eincm_ctx* c, const StageArgs& a) {
 // dst.  A weighted batch on the device path sends them to d_w_g, which k_bin_scatter reads and k_segsort overwrites afterwards with the
 // gather's order; a keep-order batch, and eincm_set_weights, to ord.stream, where they stay.
 static int upload_raw_weights(eincm_ctx* c, int B, const int64_t* n_events, const float* const* weights, float* dst) {
-    int64_t off = 0;
     for (int b = 0; b < B; ++b) {
         const size_t nb = (size_t)n_events[b];
-        if (nb > 0 && weights && weights[b]) HIPCHK(c, hipMemcpyAsync(dst + off, weights[b], nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        else if (nb > 0) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dst + off), 0x3f800000 /* 1.0f */, nb, c->stream));
-        off += (int64_t)nb;
+        float* const d = dst + stream_offset(n_events, b);
+        if (nb > 0 && weights && weights[b]) HIPCHK(c, hipMemcpyAsync(d, weights[b], nb * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        else if (nb > 0) HIPCHK(c, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d), 0x3f800000 /* 1.0f */, nb, c->stream));
     }
     return EINCM_OK;
 }
+
+// The staged batch's payload beside one event layout (StagePlan.payload): its device arrays, null where the payload has none.  raw: where
+// k_bin_scatter reads the weights as handed over - ord.stream, where a keep-order batch keeps them, or d_w_g, which k_segsort overwrites.
+struct Payload { float* w = nullptr; uint32_t* idx = nullptr; float* raw = nullptr; };
+enum Layout { SPLAT_LAYOUT, GATHER_LAYOUT };
+static Payload payload(const eincm_ctx* c, Layout l) {
+    Payload p;
+    if (c->stage.payload != PAYLOAD_NONE) { p.w = l == SPLAT_LAYOUT ? c->d_w : c->d_w_g; p.raw = c->d_w_g; }
+    if (c->stage.payload == PAYLOAD_WEIGHTS_ORDER) { p.idx = l == SPLAT_LAYOUT ? c->ord.splat : c->ord.gather; p.raw = c->ord.stream; }
+    return p;
+}
+
+// Staging's three kernels that carry the payload, every StagePayload state (in the enum's order) bound to its instantiation:
+// StagePlan.payload is the kernel to launch.  No other place names an instantiation of the three.
+const std::array BIN_SCATTER_KERNELS{&k_bin_scatter<0>, &k_bin_scatter<1>, &k_bin_scatter<1, 1>};
+const std::array SPREAD_KERNELS{&k_spread<0>, &k_spread<1>, &k_spread<1, 1>};
+const std::array SEGSORT_KERNELS{&k_segsort<0>, &k_segsort<1>, &k_segsort<1, 1>};
 
 // The gather's copy of the binned events: every segment of its list sorted by source pixel and dealt to the threads that walk it
 // (k_segsort, from the binned time order, before the splat's copy is re-dealt in place); EINCM_NO_SEGSORT: a plain copy.
 static int copy_for_gather(eincm_ctx* c) {
     if (c->gather.n == 0) return EINCM_OK;
-    const bool wt = c->stage.weighted, ix = c->stage.keep_order;        // the weights, and a keep-order batch's index, take the same way as the events
+    const Payload src = payload(c, SPLAT_LAYOUT), dst = payload(c, GATHER_LAYOUT);      // the payload takes the same way as the events
     if (c->stage.sort_segments) {
-        const dim3 grid(std::min(c->gather.n, 8192));
-        if (ix) hipLaunchKernelGGL((k_segsort<1, 1>), grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
-                                   c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)c->d_w, c->d_w_g, (const uint32_t*)c->ord.splat, c->ord.gather);
-        else if (wt) hipLaunchKernelGGL(k_segsort<1>, grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
-                                   c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)c->d_w, c->d_w_g, (const uint32_t*)nullptr, (uint32_t*)nullptr);
-        else hipLaunchKernelGGL(k_segsort<0>, grid, dim3(SORT_NT), 0, c->stream, c->gather.n, c->gather.d_items,
-                                c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)nullptr, (float*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr);
+        hipLaunchKernelGGL(SEGSORT_KERNELS[c->stage.payload], dim3(std::min(c->gather.n, 8192)), dim3(SORT_NT), 0, c->stream, c->gather.n,
+                           c->gather.d_items, c->d_xy, c->d_t, c->d_xy_g, c->d_t_g, (const float*)src.w, dst.w, (const uint32_t*)src.idx, dst.idx);
         return EINCM_OK;
     }
-    if (ix) HIPCHK(c, hipMemcpyAsync(c->ord.gather, c->ord.splat, (size_t)c->stage.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
-    if (wt) HIPCHK(c, hipMemcpyAsync(c->d_w_g, c->d_w, (size_t)c->stage.N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    if (src.idx) HIPCHK(c, hipMemcpyAsync(dst.idx, src.idx, (size_t)c->stage.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
+    if (src.w) HIPCHK(c, hipMemcpyAsync(dst.w, src.w, (size_t)c->stage.N * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_xy_g, c->d_xy, (size_t)c->stage.N * sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_t_g, c->d_t, (size_t)c->stage.N * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
     return EINCM_OK;
@@ -1718,18 +1767,11 @@ static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
             }
             c->h_wc[b].sE[r] = sE; c->h_wc[b].sEE[r] = sEE; c->h_wc[b].eabs[r] = eabs;
         }
+    const Payload pl = payload(c, SPLAT_LAYOUT);
     if (nblk > 0) {
-        if (P.keep_order) {
-            if ((rc = upload_raw_weights(c, a.B, a.n_events, a.weights, c->ord.stream))) return rc;
-            hipLaunchKernelGGL((k_bin_scatter<1, 1>), dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x,
-                               c->d_raw_y, c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)c->ord.stream, c->d_w, c->ord.splat);
-        } else if (P.weighted) {
-            if ((rc = upload_raw_weights(c, a.B, a.n_events, a.weights, c->d_w_g))) return rc;
-            hipLaunchKernelGGL(k_bin_scatter<1>, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x,
-                               c->d_raw_y, c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)c->d_w_g, c->d_w, (uint32_t*)nullptr);
-        } else
-        hipLaunchKernelGGL(k_bin_scatter<0>, dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks, c->d_raw_x, c->d_raw_y,
-                           c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)nullptr, (float*)nullptr, (uint32_t*)nullptr);
+        if (pl.raw && (rc = upload_raw_weights(c, a.B, a.n_events, a.weights, pl.raw))) return rc;
+        hipLaunchKernelGGL(BIN_SCATTER_KERNELS[P.payload], dim3(nblk), dim3(BIN_NT), g.ntiles * sizeof(uint32_t), c->stream, g, c->d_binblocks,
+                           c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_blockhist, c->d_tilebase, c->d_xy, c->d_t, (const float*)pl.raw, pl.w, pl.idx);
         hipLaunchKernelGGL(k_items, dim3((M + 255) / 256), dim3(256), 0, c->stream, g, P.seg, c->d_tilecount, c->d_tilebase, c->gather.d_itembase,
                            c->gather.d_items);
         if ((rc = copy_for_gather(c))) return rc;
@@ -1737,15 +1779,9 @@ static int bin_on_device(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     if ((rc = build_list(c, c->gather, P.seg, false, g.ntiles, c->d_t_g, P.N))) return rc;
     c->splat.n = 0;
     if (nblk > 0) {
-        if (P.spread && P.keep_order)
-            hipLaunchKernelGGL((k_spread<1, 1>), dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, c->d_w,
-                               c->ord.splat);
-        else if (P.spread && P.weighted)
-            hipLaunchKernelGGL(k_spread<1>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, c->d_w,
-                               (uint32_t*)nullptr);
-        else if (P.spread)
-            hipLaunchKernelGGL(k_spread<0>, dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t, (float*)nullptr,
-                               (uint32_t*)nullptr);
+        if (P.spread)
+            hipLaunchKernelGGL(SPREAD_KERNELS[P.payload], dim3(M, SPREAD_Y), dim3(256), 0, c->stream, g, c->d_tilecount, c->d_tilebase, c->d_xy, c->d_t,
+                               pl.w, pl.idx);
         // per window: first segment and max |t - tau| (needs the segment time ranges and the FIRST segmentation's itembase)
         HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, a.edge_ts, (size_t)a.B * a.R * sizeof(double), hipMemcpyHostToDevice, c->stream));
         sc.edge_ts_uploaded = true;
@@ -1772,8 +1808,9 @@ static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     const Geom& g = P.g;
     const size_t img = (size_t)g.H * g.W;
     int rc = EINCM_OK;
+    const Payload pl = payload(c, SPLAT_LAYOUT);
     if (const EventRefusal r = bin_events(g, a.n_events, a.xs, a.ys, a.ts, a.edge_ts, P.N, c->h_tilecount, sc.sxy, sc.st, sc.cntmax, sc.dtmax,
-                                          a.weights, P.weighted ? &sc.sw : nullptr, P.keep_order ? &sc.sidx : nullptr))
+                                          a.weights, pl.w ? &sc.sw : nullptr, pl.idx ? &sc.sidx : nullptr))
         return refuse_event(c, a, r.win, r.index, r.bad_xy);
     sc.ef.resize((size_t)a.B * a.R * img);
     for (int b = 0; b < a.B; ++b) {
@@ -1784,10 +1821,10 @@ static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     if (P.N > 0) {
         HIPCHK(c, hipMemcpyAsync(c->d_xy, sc.sxy.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_t, sc.st.data(), (size_t)P.N * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        if (P.weighted) HIPCHK(c, hipMemcpyAsync(c->d_w, sc.sw.data(), (size_t)P.N * sizeof(float), hipMemcpyHostToDevice, c->stream));
-        if (P.keep_order) {      // the index beside the splat's copy, the weights in stream order, and the host's copy of the pixels (reweight_staged counts on them)
-            HIPCHK(c, hipMemcpyAsync(c->ord.splat, sc.sidx.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            if ((rc = upload_raw_weights(c, a.B, a.n_events, a.weights, c->ord.stream))) return rc;
+        if (pl.w) HIPCHK(c, hipMemcpyAsync(pl.w, sc.sw.data(), (size_t)P.N * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        if (pl.idx) {            // the index beside the splat's copy, the weights in stream order, and the host's copy of the pixels (weight_state counts on them)
+            HIPCHK(c, hipMemcpyAsync(pl.idx, sc.sidx.data(), (size_t)P.N * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+            if ((rc = upload_raw_weights(c, a.B, a.n_events, a.weights, pl.raw))) return rc;
             c->ord.h_xy.resize((size_t)P.N);
             size_t e = 0;
             for (int b = 0; b < a.B; ++b)
@@ -1803,35 +1840,59 @@ static int bin_on_host(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     return EINCM_OK;
 }
 
+// What depends on the weights of the batch in c->stage, once its lists exist and both layouts hold their weights: the event mask, and
+// per window the most events of weight > 0 on one source pixel into h_cnt (B) and, with its floor of 1, into WinConst.cntmax.  The
+// device path takes both from k_tile_counts, per tile from its LDS histogram; a host-binned batch takes the mask from k_mask and the
+// count from the host: h_cnt as bin_events filled it, or, with h_w (N floats: a re-weighting), counted here on ord.stream.  One
+// synchronisation, which whatever the caller enqueued before rides on; the call ends on it.
+static int weight_state(eincm_ctx* c, unsigned* h_cnt, float* h_w = nullptr) {
+    const StagePlan& P = c->stage;
+    const Geom& g = P.g;
+    const float* const w = payload(c, SPLAT_LAYOUT).w;
+    HIPCHK(c, hipMemsetAsync(c->d_mask, 0, (size_t)g.B * g.H * g.W, c->stream));
+    if (c->gather.n > 0 && !P.host_binning) {
+        HIPCHK(c, hipMemsetAsync(c->d_cntmax, 0, (size_t)g.B * sizeof(unsigned), c->stream));
+        hipLaunchKernelGGL(k_tile_counts, dim3(g.ntiles, g.B), dim3(NT), 0, c->stream, g, c->d_tilebase, c->d_tilecount, c->d_xy, c->d_mask, c->d_cntmax, w);
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(h_cnt, c->d_cntmax, (size_t)g.B * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    } else if (c->gather.n > 0) {
+        hipLaunchKernelGGL(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, c->stream, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask, w);
+        HIPCHK(c, hipGetLastError());
+        if (h_w) HIPCHK(c, hipMemcpyAsync(h_w, c->ord.stream, (size_t)P.N * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int b = 0; b < g.B; ++b) {
+        const int64_t off = stream_offset(c->win_events.data(), b), nb = c->win_events[b];
+        if (h_w && nb > 0) h_cnt[b] = most_on_one_pixel(g.H, g.W, nb, c->ord.h_xy.data() + off, h_w + off);
+        c->h_wc[b].cntmax = (double)std::max(h_cnt[b], 1u);     // a bound behind the scale of the i64 gradient accumulators (grad_shift)
+    }
+    return EINCM_OK;
+}
+
+// What a new batch, and new weights for the staged one, drop: the objective kinds' zero-warp values, the Theta image, a fused evaluation's q
+// and segment ranges, the BFGS state, the chosen capacities, the last evaluation and error.  A cache tied to the staged batch goes here.
+static void drop_batch_state(eincm_ctx* c) {
+    c->objc_valid = false; c->Theta_valid = false;
+    c->motion.last_q.clear(); c->motion.seg0.clear();
+    c->bfgs.begun = false; c->policy_evaluated = false;
+    c->have_eval = false; c->err.clear();
+}
+
 // What both paths share: the 2-DoF gather's list (on the splat's copy of the events) and the splat's short one, both cut on the host
-// from the tile populations; the event mask and the most events on one source pixel; then the batch becomes the context's.
+// from the tile populations; what depends on the weights (weight_state, with this phase's one synchronisation); then the batch is the context's.
 static int finish_lists(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
     const StagePlan& P = c->stage;
     const Geom& g = P.g;
     int rc = EINCM_OK;
     if (!sc.edge_ts_uploaded)
         HIPCHK(c, hipMemcpyAsync(c->d_edge_ts, a.edge_ts, (size_t)a.B * a.R * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_mask, 0, (size_t)a.B * g.H * g.W, c->stream));
     if ((rc = build_list(c, c->gather_2, P.seg_2, true, g.ntiles, c->d_t, P.N))) return rc;
     c->splat_sh.n = 0;
     if (P.splat_short && (rc = build_list(c, c->splat_sh, SEG_SHORT, true, g.ntiles, c->d_t, P.N))) return rc;
-    if (c->gather.n > 0 && !P.host_binning) {     // event mask + most events on one source pixel, per tile from its LDS histogram
-        HIPCHK(c, hipMemsetAsync(c->d_cntmax, 0, (size_t)a.B * sizeof(unsigned), c->stream));       // (before the synchronisation below: one per staging fewer)
-        hipLaunchKernelGGL(k_tile_counts, dim3(g.ntiles, a.B), dim3(NT), 0, c->stream, g, c->d_tilebase, c->d_tilecount, c->d_xy,
-                           c->d_mask, c->d_cntmax, (const float*)(P.weighted ? c->d_w : nullptr));
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(sc.cntmax.data(), c->d_cntmax, (size_t)a.B * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->policy_evaluated = false;
+    c->win_events.assign(a.n_events, a.n_events + a.B);
+    if ((rc = weight_state(c, sc.cntmax.data()))) return rc;
     c->g = g;
     c->itembase_valid = !P.host_binning && c->gather.n > 0 && c->splat.n > 0;      // both tile scans ran on the device
-    c->win_events.assign(a.n_events, a.n_events + a.B);
-    if (c->gather.n > 0 && P.host_binning) {
-        hipLaunchKernelGGL(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, c->stream, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask,
-                           (const float*)(P.weighted ? c->d_w : nullptr));
-        HIPCHK(c, hipGetLastError());
-    }
     return EINCM_OK;
 }
 
@@ -1850,11 +1911,7 @@ static int stage_fp64(eincm_ctx* c, const StageArgs& a, StageScratch& sc) {
 static int stage_windows(eincm_ctx* c, const StageArgs& a) {
     int rc = check_staging(c, a);
     if (rc) return rc;
-    c->staged = false;
-    c->objc_valid = false;           // the zero-warp values of the objective kinds belong to the windows staged before
-    c->Theta_valid = false;
-    c->motion.last_q.clear(); c->motion.seg0.clear();      // ... as do a fused evaluation's q and the windows' segment ranges
-    c->bfgs.begun = false;           // the BFGS state belongs to the batch it was begun for
+    c->staged = false;               // (every reader of what drop_batch_state drops asks for a staged batch first)
     c->stage = plan_staging(*c, a.B, a.R, a.n_events, a.flags, live_knobs().stage, a.weights);    // (an unweighted staging drops the weighted state with the plan)
     const StagePlan& P = c->stage;
     HIPCHK(c, hipSetDevice(c->device));
@@ -1872,15 +1929,13 @@ static int stage_windows(eincm_ctx* c, const StageArgs& a) {
     if ((rc = P.host_binning ? bin_on_host(c, a, sc) : bin_on_device(c, a, sc))) return rc;
     if ((rc = finish_lists(c, a, sc))) return rc;
     if (c->fp64 && (rc = stage_fp64(c, a, sc))) return rc;
-    for (int b = 0; b < a.B; ++b) {      // bounds behind the scale of the i64 gradient accumulators (grad_shift)
+    for (int b = 0; b < a.B; ++b) {      // bounds behind the scale of the i64 gradient accumulators (grad_shift), beside weight_state's cntmax
         WinConst& wc = c->h_wc[b];
         wc.nev = (double)std::max<int64_t>(a.n_events[b], 1);
-        wc.cntmax = (double)std::max(sc.cntmax[b], 1u);
         wc.dtmax = sc.dtmax[b];
     }
+    drop_batch_state(c);
     c->staged = true;
-    c->have_eval = false;
-    c->err.clear();
     c->sharded_staging = P.defer_constants;
     if (!P.defer_constants) return window_constants(c);
     // event-sharded mode: the caller sums the shards' IUEs first (eincm_forward_iwe(NULL theta), eincm_finish_constants)
@@ -1935,44 +1990,20 @@ static int keep_order_ready(eincm_ctx* c, const char* who) {
 }
 
 // The weights in ord.stream (enqueued on the stream by the caller, through its frame) become the staged batch's: the gather through the
-// two indices into both layouts, then everything a staging derives from the weights, by the kernels staging runs - the event mask and
-// the most events on one pixel (finish_lists), the bound behind the gradient scale, the zero-warp constants - and what a staging
-// invalidates.  The edges and their moments, the four lists, dtmax and the raw events do not depend on the weights and stay.
+// two indices into both layouts, then what a staging derives from the weights (weight_state), what it drops (drop_batch_state) and the
+// zero-warp constants.  The edges and their moments, the four lists, dtmax and the raw events do not depend on the weights and stay.
 static int reweight_staged(eincm_ctx* c, OneShot& op) {
     const StagePlan& P = c->stage;
-    const Geom& g = c->g;
-    const int B = g.B;
     const size_t N = (size_t)P.N;
-    unsigned* h_cnt = op.host_buf<unsigned>((size_t)B);                  // d_cntmax comes down here (zeros: a window without events)
-    float* h_w = op.host_buf<float>(P.host_binning ? N : 0);             // host binning: ord.stream comes down here
+    unsigned* h_cnt = op.host_buf<unsigned>((size_t)P.g.B);              // d_cntmax comes down here (zeros: a window without events)
+    float* h_w = P.host_binning ? op.host_buf<float>(N) : nullptr;       // host binning: ord.stream comes down here
     if (N > 0)
         HIPCHK(c, op.launch(k_reweight, dim3((unsigned)((N + NT - 1) / NT)), dim3(NT), 0, (int64_t)N, c->ord.stream, c->ord.splat, c->ord.gather,
                             c->d_w, c->d_w_g));
-    HIPCHK(c, op.zero(c->d_mask, (size_t)B * g.H * g.W));
-    if (c->gather.n > 0 && !P.host_binning) {
-        HIPCHK(c, op.zero(c->d_cntmax, (size_t)B * sizeof(unsigned)));
-        HIPCHK(c, op.launch(k_tile_counts, dim3(g.ntiles, B), dim3(NT), 0, g, c->d_tilebase, c->d_tilecount, c->d_xy, c->d_mask, c->d_cntmax,
-                            c->d_w));
-        HIPCHK(c, op.down(h_cnt, c->d_cntmax, (size_t)B * sizeof(unsigned)));
-    } else if (c->gather.n > 0) {
-        HIPCHK(c, op.launch(k_mask, dim3(std::min(c->gather.n, 2048)), dim3(NT), 0, g, c->gather.d_items, c->gather.n, c->d_xy, c->d_mask, c->d_w));
-        HIPCHK(c, op.down(h_w, c->ord.stream, N * sizeof(float)));
-    }
-    HIPCHK(c, op.sync());
-    size_t off = 0;
-    for (int b = 0; b < B; ++b) {
-        const int64_t nb = c->win_events[b];
-        if (P.host_binning && nb > 0) h_cnt[b] = most_on_one_pixel(g.H, g.W, nb, c->ord.h_xy.data() + off, h_w + off);
-        c->h_wc[b].cntmax = (double)std::max(h_cnt[b], 1u);
-        off += (size_t)nb;
-    }
-    c->objc_valid = false;
-    c->Theta_valid = false;
-    c->motion.last_q.clear(); c->motion.seg0.clear();
-    c->bfgs.begun = false;
-    c->policy_evaluated = false;
-    c->have_eval = false;
-    c->err.clear();
+    op.pending = true;                              // weight_state enqueues on the stream itself: the frame drains that too, until ...
+    if (const int rc = weight_state(c, h_cnt, h_w)) return rc;
+    op.pending = false;                             // ... the call has ended on its synchronisation
+    drop_batch_state(c);
     return window_constants(c);
 }
 
@@ -2318,8 +2349,7 @@ int eincm_get_warped_events(eincm_ctx* c, int window, double* warped_xs, double*
     { const int rc = ensure_theta_image(c); if (rc) return rc; }
     const int64_t n = c->win_events[window];
     if (n == 0) return EINCM_OK;
-    int64_t off = 0;
-    for (int b = 0; b < window; ++b) off += c->win_events[b];
+    const int64_t off = stream_offset(c->win_events.data(), window);
     const size_t cells = (size_t)g.R * (size_t)n;
     OneShot op(c);
     const auto dx = op.piece<double>(cells), dy = op.piece<double>(cells);
@@ -2339,37 +2369,30 @@ int eincm_get_warped_events(eincm_ctx* c, int window, double* warped_xs, double*
 int eincm_event_scores(eincm_ctx* c, const float* images, const double* ref_weights, float* scores, float* selfs) {
     if (!c) return EINCM_ERR_ARG;
     const Geom& g = c->g;
-    bool masked = false;
-    for (int b = 0; c->staged && b < g.B && b < 64; ++b) masked = masked || !((c->eval_wmask >> b) & 1ull);
     const ScState st{!c->fl.idle(), scores != nullptr, c->staged, c->have_eval, c->fp64, c->splat_size,
-                     c->sharded_staging || c->constants_pending, images != nullptr, masked};
+                     c->sharded_staging || c->constants_pending, images != nullptr, RawEvents::masked(c)};
     if (const ScFault f = sc_check(st, ref_weights, g.R)) return fail(c, sc_code(f), "eincm_event_scores: %s", sc_why(f));
     { const int rc = ensure_theta_image(c); if (rc) return rc; }
     const int B = g.B, R = g.R;
     const bool combined = ref_weights != nullptr;
-    const int64_t* ne = c->win_events.data();
-    const int64_t n_events = sc_total(ne, B, 1, true), n_out = sc_total(ne, B, R, combined);
-    if (n_events == 0) return EINCM_OK;
-    const size_t stack = (size_t)B * R * g.H * g.W;
     OneShot op(c);
-    const auto d_off = op.piece<int64_t>((size_t)B + 1);
+    RawEvents ev(op, [](const int64_t* n, int b) { return sc_block_offset(n, b, 1, true); });
+    const int64_t n_out = sc_total(ev.ne, B, R, combined);
+    if (ev.total() == 0) return EINCM_OK;
+    const size_t stack = (size_t)B * R * g.H * g.W;
     const auto d_img = op.piece<float>(stack, images != nullptr);
     const auto d_rw = op.piece<float>((size_t)R, combined);
     const auto d_s = op.piece<float>((size_t)n_out);
     const auto d_q = op.piece<float>((size_t)n_out, selfs != nullptr);
-    int64_t* h_off = op.host_buf<int64_t>((size_t)B + 1);                // d_off goes up from here, d_rw from h_rw
-    float* h_rw = op.host_buf<float>((size_t)R);
-    int64_t n_max = 0;
-    for (int b = 0; b <= B; ++b) h_off[b] = sc_block_offset(ne, b, 1, true);
-    for (int b = 0; b < B; ++b) n_max = std::max(n_max, ne[b]);
+    float* h_rw = op.host_buf<float>((size_t)R);                         // d_rw goes up from here
     for (int r = 0; combined && r < R; ++r) h_rw[r] = (float)ref_weights[r];
     HIPCHK(c, op.begin());
-    HIPCHK(c, op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)));
+    HIPCHK(c, ev.upload());
     if (images) HIPCHK(c, op.up(d_img, images, stack * sizeof(float)));  // (host memory: the caller's, as scores and selfs)
     if (combined) HIPCHK(c, op.up(d_rw, h_rw, (size_t)R * sizeof(float)));
     const float* F = images ? (const float*)d_img : (const float*)c->d_iwe;
-    const dim3 grid((unsigned)((n_max + NT - 1) / NT), (unsigned)B);
-    HIPCHK(c, op.launch(k_event_scores, grid, dim3(NT), 0, g, d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F, d_rw,
+    const dim3 grid((unsigned)((ev.n_max + NT - 1) / NT), (unsigned)B);
+    HIPCHK(c, op.launch(k_event_scores, grid, dim3(NT), 0, g, ev.d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F, d_rw,
                         d_s, d_q));
     HIPCHK(c, op.down(scores, d_s, (size_t)n_out * sizeof(float)));
     if (selfs) HIPCHK(c, op.down(selfs, d_q, (size_t)n_out * sizeof(float)));
@@ -2385,11 +2408,9 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
                                  int64_t* n_unsupported) {
     if (!c) return EINCM_ERR_ARG;
     const Geom& g = c->g;
-    bool masked = false;
-    for (int b = 0; c->staged && b < g.B && b < 64; ++b) masked = masked || !((c->eval_wmask >> b) & 1ull);
     const bool apply = (flags & EINCM_RS_APPLY) != 0, own_w = (flags & EINCM_RS_STAGED_WEIGHTS) != 0;    // a keep-order batch's two
     const RsState st{{!c->fl.idle(), weights_out || labels || mass || n_unsupported || apply, c->staged, c->have_eval, c->fp64, c->splat_size,
-                      c->sharded_staging || c->constants_pending, images != nullptr, masked},
+                      c->sharded_staging || c->constants_pending, images != nullptr, RawEvents::masked(c)},
                      c->staged ? g.B : 0, c->win_events.data()};
     if (const RsFault f = rs_check(st, n_models, ref_weights, g.R, prior))
         return fail(c, rs_code(f), "eincm_event_responsibilities: %s", rs_why(f));
@@ -2399,17 +2420,13 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
     }
     { const int rc = ensure_theta_image(c); if (rc) return rc; }
     const int B = g.B, R = g.R, K = n_models, G = B / K;
-    const int64_t* ne = c->win_events.data();
-    const int64_t n_events = rs_weights_total(ne, B), n_labels = rs_labels_total(ne, B, K);
-    if (n_events == 0) return EINCM_OK;
-    int64_t n_max = 0;
-    for (int b = 0; b < B; ++b) n_max = std::max(n_max, ne[b]);
-    const size_t n_blk = (size_t)((n_max + NT - 1) / NT), stack = (size_t)B * R * g.H * g.W;
-    bool any_w = false;
-    for (int b = 0; (flags & EINCM_RS_EXCLUDE_SELF) && weights_in && b < B; ++b) any_w = any_w || (weights_in[b] && ne[b] > 0);
-    const bool self_own = own_w && (flags & EINCM_RS_EXCLUDE_SELF);       // w_l is read where staging left it: every window has its weights there
     OneShot op(c);
-    const auto d_off = op.piece<int64_t>((size_t)B + 1);
+    RawEvents ev(op, [](const int64_t* n, int b) { return rs_weights_offset(n, b); });
+    const int64_t n_events = rs_weights_total(ev.ne, B), n_labels = rs_labels_total(ev.ne, B, K);
+    if (n_events == 0) return EINCM_OK;
+    const size_t n_blk = (size_t)((ev.n_max + NT - 1) / NT), stack = (size_t)B * R * g.H * g.W;
+    const bool any_w = (flags & EINCM_RS_EXCLUDE_SELF) && ev.any(weights_in);
+    const bool self_own = own_w && (flags & EINCM_RS_EXCLUDE_SELF);       // w_l is read where staging left it: every window has its weights there
     const auto d_img = op.piece<float>(stack, images != nullptr);
     const auto d_rw = op.piece<float>((size_t)R);
     const auto d_pi = op.piece<float>((size_t)B);
@@ -2420,33 +2437,27 @@ int eincm_event_responsibilities(eincm_ctx* c, int n_models, const float* images
     const auto d_part = op.piece<double>((size_t)B * n_blk, mass != nullptr);
     const auto d_mass = op.piece<double>((size_t)B, mass != nullptr);
     const auto d_uns = op.piece<unsigned long long>((size_t)G, n_unsupported != nullptr);
-    int64_t* h_off = op.host_buf<int64_t>((size_t)B + 1);                // d_off, d_rw, d_pi and d_has go up from these
-    float* h_rw = op.host_buf<float>((size_t)R);
+    float* h_rw = op.host_buf<float>((size_t)R);                         // d_rw, d_pi and (self_own) d_has go up from these
     float* h_pi = op.host_buf<float>((size_t)B);
-    uint8_t* h_has = op.host_buf<uint8_t>((size_t)B);
-    for (int b = 0; b <= B; ++b) h_off[b] = rs_weights_offset(ne, b);
+    uint8_t* h_all = op.host_buf<uint8_t>((size_t)B);
     for (int r = 0; r < R; ++r) h_rw[r] = (float)ref_weights[r];
     for (int b = 0; b < B; ++b) h_pi[b] = prior ? (float)prior[b] : 1.0f;
-    for (int b = 0; b < B; ++b) h_has[b] = self_own || (any_w && weights_in[b] && ne[b] > 0);
+    for (int b = 0; b < B; ++b) h_all[b] = 1;
     HIPCHK(c, op.begin());
-    HIPCHK(c, op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)));
+    HIPCHK(c, ev.upload());
     if (images) HIPCHK(c, op.up(d_img, images, stack * sizeof(float)));  // (host memory: the caller's, as weights_in and the outputs)
     HIPCHK(c, op.up(d_rw, h_rw, (size_t)R * sizeof(float)));
     HIPCHK(c, op.up(d_pi, h_pi, (size_t)B * sizeof(float)));
-    if (any_w) {
-        HIPCHK(c, op.up(d_has, h_has, (size_t)B));
-        for (int b = 0; b < B; ++b)
-            if (h_has[b]) HIPCHK(c, op.up((float*)d_win + h_off[b], weights_in[b], (size_t)ne[b] * sizeof(float)));
-    }
-    if (self_own) HIPCHK(c, op.up(d_has, h_has, (size_t)B));
+    if (any_w) HIPCHK(c, ev.upload_per_window(weights_in, (float*)d_win, d_has));
+    if (self_own) HIPCHK(c, op.up(d_has, h_all, (size_t)B));
     const float* w_self = self_own ? (const float*)c->ord.stream : (const float*)d_win;     // (the stream order is the layout of weights_in)
     if (n_unsupported) HIPCHK(c, op.zero(d_uns, (size_t)G * sizeof(unsigned long long)));
     const float* F = images ? (const float*)d_img : (const float*)c->d_iwe;
     const dim3 grid((unsigned)n_blk, (unsigned)G);
-    HIPCHK(c, op.launch(rs_kernel(K), grid, dim3(NT), 0, g, d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F, d_rw,
+    HIPCHK(c, op.launch(rs_kernel(K), grid, dim3(NT), 0, g, ev.d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F, d_rw,
                         w_self, d_has, d_pi, flags, d_wout, d_lab, d_part, d_uns));
     if (mass) {
-        HIPCHK(c, op.launch(k_rs_mass, dim3((unsigned)((B + NT - 1) / NT)), dim3(NT), 0, B, d_off, d_part, (int64_t)n_blk, d_mass));
+        HIPCHK(c, op.launch(k_rs_mass, dim3((unsigned)((B + NT - 1) / NT)), dim3(NT), 0, B, ev.d_off, d_part, (int64_t)n_blk, d_mass));
         HIPCHK(c, op.down(mass, d_mass, (size_t)B * sizeof(double)));
     }
     if (weights_out) HIPCHK(c, op.down(weights_out, d_wout, (size_t)n_events * sizeof(float)));
@@ -2480,41 +2491,28 @@ int eincm_contrast_landscape(eincm_ctx* c, int n_candidates, const double* coeff
         return fail(c, cl_code(f), "eincm_contrast_landscape: %s", cl_why(f));
     }
     const int B = g.B, V = n_candidates, K = mo.model.n_coeffs;
-    const int64_t* ne = c->win_events.data();
     const ClBands plan = cl_bands(g.H, g.W, cell);
     const size_t BV = (size_t)B * V, n_bands = (size_t)plan.n_bands();
-    bool any_keep = false;
-    for (int b = 0; keep && b < B; ++b) any_keep = any_keep || (keep[b] && ne[b] > 0);
-    int64_t n_events = 0;
-    for (int b = 0; b < B; ++b) n_events += ne[b];
     OneShot op(c);
-    const auto d_off = op.piece<int64_t>((size_t)B + 1);
+    RawEvents ev(op);
+    const bool any_keep = ev.any(keep);
     const auto d_q = op.piece<double>(BV * MOTION_NQ);
     const auto d_tref = op.piece<double>((size_t)B);
-    const auto d_keep = op.piece<uint8_t>((size_t)n_events, any_keep);
+    const auto d_keep = op.piece<uint8_t>((size_t)ev.total(), any_keep);
     const auto d_has = op.piece<uint8_t>((size_t)B, any_keep);
     const auto d_part = op.piece<unsigned long long>(BV * n_bands * 2);
     const auto d_sumsq = op.piece<unsigned long long>(BV, sumsq != nullptr);
     const auto d_nin = op.piece<uint32_t>(BV, n_in != nullptr);
-    int64_t* h_off = op.host_buf<int64_t>((size_t)B + 1);                // d_off, d_q and d_has go up from these; d_tref from the caller's
-    double* h_q = op.host_buf<double>(BV * MOTION_NQ);
-    uint8_t* h_has = op.host_buf<uint8_t>((size_t)B);
-    h_off[0] = 0;
-    for (int b = 0; b < B; ++b) h_off[b + 1] = h_off[b] + ne[b];
+    double* h_q = op.host_buf<double>(BV * MOTION_NQ);                   // d_q goes up from here; d_tref from the caller's
     for (size_t i = 0; i < BV; ++i) motion_q(mo.model, coeffs + i * K, h_q + i * MOTION_NQ);
-    for (int b = 0; b < B; ++b) h_has[b] = any_keep && keep[b] && ne[b] > 0;
     HIPCHK(c, op.begin());
-    HIPCHK(c, op.up(d_off, h_off, ((size_t)B + 1) * sizeof(int64_t)));
+    HIPCHK(c, ev.upload());
     HIPCHK(c, op.up(d_q, h_q, BV * MOTION_NQ * sizeof(double)));
     HIPCHK(c, op.up(d_tref, t_ref, (size_t)B * sizeof(double)));         // (host memory: the caller's, as keep and the outputs)
-    if (any_keep) {
-        HIPCHK(c, op.up(d_has, h_has, (size_t)B));
-        for (int b = 0; b < B; ++b)
-            if (h_has[b]) HIPCHK(c, op.up((uint8_t*)d_keep + h_off[b], keep[b], (size_t)ne[b]));
-    }
+    if (any_keep) HIPCHK(c, ev.upload_per_window(keep, (uint8_t*)d_keep, d_has));
     const ClGeom cg{g.H, g.W, V, cl_log2_cell(cell), plan.rows, plan.cols, plan.n_col_bands, plan.Hc, plan.Wc, plan.table,
                     mo.model.cx, mo.model.cy, mo.model.scale};
-    HIPCHK(c, op.launch(k_contrast_landscape, dim3((unsigned)n_bands, (unsigned)V, (unsigned)B), dim3(CL_NT), (size_t)plan.lds_bytes(), cg, d_off,
+    HIPCHK(c, op.launch(k_contrast_landscape, dim3((unsigned)n_bands, (unsigned)V, (unsigned)B), dim3(CL_NT), (size_t)plan.lds_bytes(), cg, ev.d_off,
                         c->d_raw_x, c->d_raw_y, c->d_raw_t, d_q, d_tref, d_keep, d_has, d_part));
     HIPCHK(c, op.launch(k_cl_sum_bands, dim3((unsigned)((BV + NT - 1) / NT)), dim3(NT), 0, (int)BV, (int)n_bands, d_part, d_sumsq, d_nin));
     if (sumsq) HIPCHK(c, op.down(sumsq, d_sumsq, BV * sizeof(uint64_t)));

@@ -247,6 +247,17 @@ struct EventRefusal {
     explicit operator bool() const { return win >= 0; }
 };
 
+// The most events of weight > 0 on one source pixel of a window (WinConst.cntmax before its floor of 1); events of weight 0 are not
+// counted.  xy are the window's n events as x | y << 16, in any order, w their weights (NULL: ones).  bin_events counts with it, and
+// so does a re-weighting of a host-binned batch.
+inline unsigned most_on_one_pixel(int H, int W, int64_t n, const uint32_t* xy, const float* w) {
+    std::vector<uint32_t> pc((size_t)H * W, 0u);
+    unsigned m = 0u;
+    for (int64_t i = 0; i < n; ++i)
+        if (!w || w[i] > 0.0f) m = std::max(m, ++pc[(size_t)(xy[i] >> 16) * W + (xy[i] & 0xffffu)]);
+    return m;
+}
+
 // A stable counting sort of the batch's events by (window, tile) into sxy (x | y << 16) and st (both max(N, 1) long), the events per
 // (window, tile) into tilecount, and per window the running maxima cntmax (most events on one source pixel) and dtmax (max |t - tau|;
 // both B long, as the caller initialised them).  Stops at the first event it refuses.
@@ -255,9 +266,8 @@ inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int
                                std::vector<uint32_t>& sxy, std::vector<double>& st, std::vector<unsigned>& cntmax,
                                std::vector<double>& dtmax, const float* const* weights = nullptr, std::vector<float>* sw = nullptr,
                                std::vector<uint32_t>* sidx = nullptr) {
-    // sw (a weighted batch): the weights in the order of sxy, ones for a window without (weights[b] NULL); events of weight 0 are
-    // not counted into cntmax.  sidx (a keep-order batch): where the event of every slot of sxy stood in the batch
-    // as it was handed over, window after window
+    // sw (a weighted batch): the weights in the order of sxy, ones for a window without (weights[b] NULL).  sidx (a keep-order batch,
+    // DESIGN.md section 29): where the event of every slot of sxy stood in the batch as it was handed over, window after window
     const int H = g.H, W = g.W;
     if (sw) sw->resize((size_t)std::max<int64_t>(N, 1));
     if (sidx) sidx->resize((size_t)std::max<int64_t>(N, 1));
@@ -277,11 +287,6 @@ inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int
             if (!std::isfinite(t[i])) return EventRefusal{b, i, false};
             ++cnt[(size_t)(y[i] / TS) * g.tilesX + (x[i] / TS) + 1];
         }
-        {   // most events on one source pixel
-            std::vector<uint32_t> pc((size_t)H * W, 0u);
-            for (int64_t i = 0; i < n; ++i)
-                if (!wb || wb[i] > 0.0f) cntmax[b] = std::max(cntmax[b], ++pc[(size_t)y[i] * W + x[i]]);
-        }
         for (int k = 0; k < g.ntiles; ++k) tilecount[(size_t)b * g.ntiles + k] = (int32_t)cnt[k + 1];
         for (int k = 0; k < g.ntiles; ++k) cnt[k + 1] += cnt[k];
         std::vector<int64_t> pos(cnt.begin(), cnt.end() - 1);
@@ -293,19 +298,11 @@ inline EventRefusal bin_events(const Geom& g, const int64_t* n_events, const int
             if (sw) (*sw)[d] = wb ? wb[i] : 1.0f;
             if (sidx) (*sidx)[d] = (uint32_t)(base + i);
         }
+        // (the sorted slots hold the window's events as x | y << 16 beside their weights: any order counts the same)
+        cntmax[b] = std::max(cntmax[b], most_on_one_pixel(H, W, n, sxy.data() + base, wb ? sw->data() + base : nullptr));
         base += n;
     }
     return EventRefusal{};
-}
-
-// The most events of weight > 0 on one source pixel of a window (WinConst.cntmax before its floor of 1), as bin_events counts it: xy
-// are the window's n events as x | y << 16, w their weights (NULL: ones).  What a re-weighting of a host-binned batch recomputes.
-inline unsigned most_on_one_pixel(int H, int W, int64_t n, const uint32_t* xy, const float* w) {
-    std::vector<uint32_t> pc((size_t)H * W, 0u);
-    unsigned m = 0u;
-    for (int64_t i = 0; i < n; ++i)
-        if (!w || w[i] > 0.0f) m = std::max(m, ++pc[(size_t)(xy[i] >> 16) * W + (xy[i] & 0xffffu)]);
-    return m;
 }
 
 // One edge image to fp32 with its moments: the sum, the sum of squares and the largest magnitude of the fp32 values
@@ -345,6 +342,10 @@ inline WinFit fit_window(double vmax, double tspan, double margin, int floor_k, 
 
 // ---- the plans ----
 
+// What rides beside ev_xy / ev_t through staging's kernels: nothing, the per-event weights, the weights and the index back into the
+// batch as handed over.  The value indexes the instantiations of k_bin_scatter, k_spread and k_segsort.
+enum StagePayload { PAYLOAD_NONE, PAYLOAD_WEIGHTS, PAYLOAD_WEIGHTS_ORDER };
+
 // Every decision of one staging, taken once by plan_staging before its first HIP call; the phases of stage_windows only read it, and
 // the context keeps the one of the staged batch (plan_eval, eincm_get_launch_policy).
 struct StagePlan {
@@ -358,6 +359,7 @@ struct StagePlan {
     bool host_binning = false;          // the host sorts the events by (window, tile), not the kernels of eincm_binning.hip.h
     bool defer_constants = false;       // EINCM_SW_DEFER_CONSTANTS: the caller sums the shards' IUEs before the window constants are formed
     bool wide = false;                  // a window has a handful of events: 61-bit fixed point in the per-pixel gradient sums (grad_shift_pixel)
+    StagePayload payload = PAYLOAD_NONE;     // the batch's payload state: the two flags below as one value (plan_staging)
     bool weighted = false;              // a window with events carries per-event weights: the payload ev_w rides beside ev_xy / ev_t and the event kernels run their weighted forms
     bool keep_order = false;            // EINCM_SW_KEEP_ORDER: both layouts keep the index of every slot into the batch as handed over, and the batch is a weighted one whatever it was handed, so a later eincm_set_weights changes no plan
 };
@@ -424,6 +426,7 @@ inline StagePlan plan_staging(const PlanCtx& c, int n_windows, int n_refs, const
     StagePlan P;
     P.keep_order = (flags & EINCM_SW_KEEP_ORDER) != 0;
     P.weighted = P.keep_order || batch_weighted(n_windows, n_events, weights);
+    P.payload = P.keep_order ? PAYLOAD_WEIGHTS_ORDER : P.weighted ? PAYLOAD_WEIGHTS : PAYLOAD_NONE;
     const int H = c.H, W = c.W;
     Geom& g = P.g;
     g.H = H; g.W = W; g.R = n_refs; g.B = n_windows;

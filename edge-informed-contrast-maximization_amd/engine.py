@@ -994,7 +994,7 @@ class Engine:
             return (C.c_void_p * B)(*[(a if a.size else dummy).ctypes.data for a in arrs])
         flags = (L.SW_DEFER_CONSTANTS if defer_constants else 0) | (L.SW_KEEP_ORDER if keep_order else 0)
         if weighted or keep_order:        # one float pointer per window, NULL where a window has none (or for all of them)
-            wp = None if not weighted else (C.c_void_p * B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
+            wp = per_window_ptrs(ws)
             rc = self._lib.eincm_set_windows_weighted(self._ctx, B, R, n.ctypes.data_as(C.POINTER(C.c_int64)),
                                                       ptrs(xs, one[0]), ptrs(ys, one[0]), ptrs(ts, one[1]), ptrs(edges, one[1]),
                                                       _dp(edge_ts), wp, flags)
@@ -1035,10 +1035,7 @@ class Engine:
         last evaluation is gone, as after a staging."""
         ws = check_weight_list(weights, self.n_events if self.B else [])
         self._need_keep_order('set_weights')
-        wp = None
-        if any(w is not None and w.size for w in ws):
-            wp = (C.c_void_p * self.B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
-        self._check(self._lib.eincm_set_weights(self._ctx, wp))
+        self._check(self._lib.eincm_set_weights(self._ctx, per_window_ptrs(ws)))
         self._staged_weights = ws
 
     def staged_weights(self):
@@ -1772,11 +1769,8 @@ class Engine:
         labels = np.empty(lab_total, dtype=np.uint8) if 'labels' in want else None
         mass = np.zeros(B, dtype=np.float64) if 'mass' in want else None                # (a batch without events writes nothing)
         n_uns = np.zeros(G, dtype=np.int64) if 'n_unsupported' in want else None
-        wp = None
-        if ws is not None and any(w is not None and w.size for w in ws):
-            wp = (C.c_void_p * B)(*[None if (w is None or not w.size) else w.ctypes.data for w in ws])
         addr = lambda a: None if a is None else a.ctypes.data
-        self._check(self._lib.eincm_event_responsibilities(self._ctx, K, addr(imgs), addr(rw), wp, addr(pi), flags,
+        self._check(self._lib.eincm_event_responsibilities(self._ctx, K, addr(imgs), addr(rw), per_window_ptrs(ws), addr(pi), flags,
                                                            addr(weights), addr(labels), addr(mass), addr(n_uns)))
         if apply:
             self._staged_weights = None     # (they are the device's now: staged_weights())
@@ -1805,11 +1799,8 @@ class Engine:
         B, V = c.shape[:2]
         sumsq = np.zeros((B, V), dtype=np.uint64) if 'sumsq' in want else None
         n_in = np.zeros((B, V), dtype=np.uint32) if 'n_in' in want else None
-        kp = None
-        if masks is not None and any(m is not None and m.size for m in masks):
-            kp = (C.c_void_p * B)(*[None if (m is None or not m.size) else m.ctypes.data for m in masks])
         addr = lambda a: None if a is None else a.ctypes.data
-        self._check(self._lib.eincm_contrast_landscape(self._ctx, V, c.ctypes.data, t.ctypes.data, cell, kp, addr(sumsq), addr(n_in)))
+        self._check(self._lib.eincm_contrast_landscape(self._ctx, V, c.ctypes.data, t.ctypes.data, cell, per_window_ptrs(masks), addr(sumsq), addr(n_in)))
         out = {}
         if sumsq is not None:
             out['sumsq'] = sumsq
@@ -1867,6 +1858,14 @@ class Engine:
         d = {n: float(t.ms[i]) for i, n in enumerate(L.STAGE_NAMES)}
         d['total'] = float(t.total_ms)
         return d
+
+
+def per_window_ptrs(arrays):
+    """The C form of one optional host array per window: a (void* x B) list with NULL for a missing or empty entry, or None for the
+    whole list when no entry has data (or ``arrays`` is None).  The arrays must outlive the call that takes the list."""
+    if arrays is None or not any(a is not None and a.size for a in arrays):
+        return None
+    return (C.c_void_p * len(arrays))(*[None if (a is None or not a.size) else a.ctypes.data for a in arrays])
 
 
 def multi_ref_weights(n_refs):

@@ -8,6 +8,9 @@
 // ->  order plan_keep plan_weighted plan_weighted_without_the_flag
 //       | not_a_permutation leaves_its_window xy_differs t_differs w_differs descends_inside_a_tile cntmax_differs    (counts: all 0)
 //       | idx ..
+//
+//   payload B  n_0 .. n_{B-1}  has_0 .. has_{B-1}  keep
+// ->  payload state weighted keep_order      (StagePlan.payload as a number: 0 none, 1 weights, 2 weights and order; the two flags set from it)
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -28,9 +31,26 @@ int main(int argc, char** argv) {
         std::istringstream s(line);
         std::vector<std::string> tok;
         for (std::string t; s >> t;) tok.push_back(t);
-        if (tok.empty() || tok[0] != "order") return 3;
+        if (tok.empty() || (tok[0] != "order" && tok[0] != "payload")) return 3;
         size_t k = 1;
         auto num = [&]() { return std::strtod(tok.at(k++).c_str(), nullptr); };
+        if (tok[0] == "payload") {
+            const int B = (int)num();
+            std::vector<int64_t> n((size_t)B);
+            std::vector<const float*> wp((size_t)B, nullptr);
+            static const float some = 0.5f;               // the plan reads which windows have weights, never the values
+            for (auto& v : n) v = (int64_t)num();
+            bool any = false;
+            for (auto& w : wp) if ((int)num()) { w = &some; any = true; }
+            const uint32_t flags = (int)num() ? EINCM_SW_KEEP_ORDER : 0u;
+            if (k != tok.size()) return 4;
+            PlanCtx c;
+            c.H = 70; c.W = 100;
+            const StagePlan P = plan_staging(c, B, 2, n.data(), flags, StageKnobs{}, any ? wp.data() : nullptr);
+            static_assert(PAYLOAD_NONE == 0 && PAYLOAD_WEIGHTS == 1 && PAYLOAD_WEIGHTS_ORDER == 2, "the payload state indexes the staging kernels");
+            std::printf("payload %d %d %d\n", (int)P.payload, P.weighted ? 1 : 0, P.keep_order ? 1 : 0);
+            continue;
+        }
         const int H = (int)num(), W = (int)num(), B = (int)num();
         std::vector<int64_t> n((size_t)B);
         std::vector<int> has((size_t)B);

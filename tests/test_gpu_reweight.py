@@ -42,41 +42,7 @@ def _engine(n=sum(RS.N), B=RS.B):
     return E.Engine((RS.H, RS.W), max(n, 1), max_refs=RS.R, max_windows=B)
 
 
-def _bytes(x):
-    if isinstance(x, dict):
-        return {k: _bytes(v) for k, v in sorted(x.items())}
-    if isinstance(x, (list, tuple)):
-        return [_bytes(v) for v in x]
-    return None if x is None else (np.asarray(x).dtype.str, np.asarray(x).shape, np.asarray(x).tobytes())
-
-
-def answers(eng, c):
-    """Everything the contract names, in one fixed order of calls, as bytes"""
-    out = {}
-    eng.set_motion_model(motion.MotionModel('affine', (RS.H, RS.W)))
-    eng.set_motion_path('expanded')
-    out['policy_staged'] = eng.launch_policy()
-    out['zero_iwe'] = eng.zero_iwe()
-    out['mask'] = eng.mask_tensor().cpu().numpy()
-    for name in ('theta8', 'dense'):
-        out['loss_grad_' + name] = eng.loss_grad(c[name], P0, want_aux=True)
-        out['iwes_' + name] = eng.iwes()
-        out['policy_' + name] = eng.launch_policy()
-    out['count_images'] = eng.count_images()
-    out['event_scores'] = eng.event_scores(exclude_self=True)
-    out['event_scores_per_ref'] = eng.event_scores(ref_weights=None)
-    out['responsibilities_1'] = eng.event_responsibilities(1, want=E.RS_OUTPUTS)
-    out['loss_grad_motion'] = eng.loss_grad_motion(c['coeffs'], P1, want_aux=True)
-    out['iwes_motion'] = eng.iwes()
-    out['loss_grad_device'] = _device(eng, c['theta8'])
-    return _bytes(out)
-
-
-def _device(eng, theta):
-    import torch
-    th = torch.as_tensor(theta, dtype=torch.float64, device='cuda')
-    v, g, aux = eng.loss_grad_device(th, P1, theta_abs_max=float(np.abs(theta).max()), want_aux=True)
-    return v, g.cpu().numpy() if hasattr(g, 'cpu') else g, aux
+_bytes, answers = RS.as_bytes, RS.answers
 
 
 def _same(got, want, what):

@@ -71,3 +71,29 @@ def test_the_host_sort_keeps_the_index_of_every_slot(out, name):
     names = ('not a permutation', 'leaves its window', 'xy differs', 't differs', 'w differs', 'descends inside a tile', 'cntmax differs')
     assert dict(zip(names, (int(v) for v in faults))) == dict.fromkeys(names, 0)
     assert np.array_equal(HC.i(idx), np.array(EXPECT[name], dtype=np.int64))
+
+
+# ---- the payload state of a staging (StagePlan.payload): what (weights, EINCM_SW_KEEP_ORDER) make of a batch ---------------------------
+NONE, WEIGHTS, WEIGHTS_ORDER = 0, 1, 2
+PAYLOADS = {    # name: (events per window, which windows were handed weights, the flag) -> the state
+    'no-weights-no-flag': ((700, 0, 300), (0, 0, 0), 0, NONE),
+    'weights-on-one-window': ((700, 0, 300), (0, 0, 1), 0, WEIGHTS),
+    'weights-on-every-window': ((700, 5, 300), (1, 1, 1), 0, WEIGHTS),
+    'weights-only-on-an-empty-window': ((700, 0, 300), (0, 1, 0), 0, NONE),
+    'no-events-at-all-with-weights': ((0, 0), (1, 1), 0, NONE),
+    'the-flag-alone': ((700, 0, 300), (0, 0, 0), 1, WEIGHTS_ORDER),
+    'the-flag-and-weights': ((700, 0, 300), (1, 0, 1), 1, WEIGHTS_ORDER),
+    'the-flag-and-weights-only-on-an-empty-window': ((700, 0, 300), (0, 1, 0), 1, WEIGHTS_ORDER),
+    'the-flag-without-events': ((0,), (0,), 1, WEIGHTS_ORDER),
+}
+PAYLOAD_CASES = {}
+for _name, (_n, _has, _keep, _) in PAYLOADS.items():
+    HC.add_case(PAYLOAD_CASES, _name, 'payload', len(_n), *_n, *_has, _keep)
+
+
+def test_the_plan_names_one_payload_state_and_sets_both_flags_from_it(reweight_check, tmp_path_factory):
+    out = HC.run(reweight_check, PAYLOAD_CASES, tmp_path_factory, 'payload_cases')
+    for name, (_n, _has, _keep, want) in PAYLOADS.items():
+        state, weighted, keep_order = (int(v) for v in out[name][0])
+        assert state == want, name
+        assert (weighted, keep_order) == (int(want != NONE), int(want == WEIGHTS_ORDER)), name

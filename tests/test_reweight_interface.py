@@ -79,12 +79,22 @@ def test_the_index_rides_through_the_three_permutation_kernels_and_the_host_sort
     body = api.split('int eincm_set_weights(')[1].split('\n}\n')[0]
     assert body.index('keep_order_ready(') < body.index('check_weights(') < body.index('OneShot op(c);') < body.index('upload_raw_weights(')
     assert 'hipMalloc' not in body and 'alloc_dev' not in body
-    body = api.split('static int reweight_staged(')[1].split('\n}\n')[0]
+    # reweight_staged and the two functions it shares with a staging - what depends on the weights, what a new batch drops - hold the steps
+    fn = {name: api.split(f'static {ret} {name}(')[1].split('\n}\n')[0]
+          for ret, name in (('int', 'reweight_staged'), ('int', 'weight_state'), ('void', 'drop_batch_state'))}
+    assert fn['reweight_staged'].index('k_reweight') < fn['reweight_staged'].index('weight_state(c') \
+        < fn['reweight_staged'].index('drop_batch_state(c)') < fn['reweight_staged'].index('window_constants(c)')
+    body = '\n'.join(fn.values())
     for step in ('k_reweight', 'k_tile_counts', 'k_mask', 'most_on_one_pixel', 'window_constants(c)', 'have_eval = false', 'objc_valid = false',
                  'bfgs.begun = false', 'last_q.clear()', 'seg0.clear()', 'policy_evaluated = false'):
         assert step in body, step
     for untouched in ('k_edges', 'build_list', 'k_segsort', 'k_spread', 'k_bin_', 'upload_raw_events', 'alloc_dev'):
         assert untouched not in body, untouched
+    # one owner each: a staging calls the same two and states neither list itself
+    staging = api.split('static int finish_lists(')[1].split('\nint eincm_set_windows_ex(')[0]
+    assert 'weight_state(c' in staging and 'drop_batch_state(c)' in staging
+    for once in ('k_tile_counts', 'k_mask', 'objc_valid = false', 'bfgs.begun = false', 'have_eval = false', 'policy_evaluated = false'):
+        assert once not in staging, once
 
 
 def test_c_side_states_the_refusals_in_their_own_words():
