@@ -42,6 +42,11 @@ RS_MAX_MODELS, RS_EXCLUDE_SELF = 8, 1                                # EINCM_RS_
 RS_STAGED_WEIGHTS, RS_APPLY = 2, 4                                   # EINCM_RS_STAGED_WEIGHTS, EINCM_RS_APPLY (a keep-order batch)
 CL_MAX_CANDIDATES = 4096                                             # EINCM_CL_MAX_CANDIDATES
 CL_CELLS = (1, 2, 4, 8)                                              # the cell sizes of eincm_contrast_landscape
+ML_HARD, ML_SOFT, ML_FILL_ZERO, ML_FILL_DOMINANT = 0, 1, 0, 2        # EINCM_ML_* flags of eincm_compose_motions
+ML_MODES = {'hard': ML_HARD, 'soft': ML_SOFT}
+ML_FILLS = {'zero': ML_FILL_ZERO, 'dominant': ML_FILL_DOMINANT}
+ML_NO_LABEL = 255                                                    # EINCM_ML_NO_LABEL
+ML_Q_ONE = 4096                                                      # the quantised weight of 1 (csrc/eincm_motion_layers.h)
 
 
 class Params(C.Structure):
@@ -196,6 +201,8 @@ SIGNATURES = [
     ('eincm_get_staged_weights', C.c_int, [_P, C.c_void_p]),
     # the contrast landscape over motion coefficients (raw addresses, as above)
     ('eincm_contrast_landscape', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # a motion segmentation composed into one flow field and a label image (raw addresses, as above)
+    ('eincm_compose_motions', C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # a solved theta carried along its own flow to the next window (raw addresses, as above)
     ('eincm_theta_advect', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

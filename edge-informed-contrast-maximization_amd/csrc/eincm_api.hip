@@ -42,6 +42,8 @@
 #include "eincm_event_scores.hip.h"
 #include "eincm_responsibilities.h"
 #include "eincm_responsibilities.hip.h"
+#include "eincm_motion_layers.h"
+#include "eincm_motion_layers.hip.h"
 #include "eincm_theta_advect.h"
 #include "eincm_theta_advect.hip.h"
 #include "eincm_contrast_landscape.h"
@@ -2517,6 +2519,64 @@ int eincm_contrast_landscape(eincm_ctx* c, int n_candidates, const double* coeff
     HIPCHK(c, op.launch(k_cl_sum_bands, dim3((unsigned)((BV + NT - 1) / NT)), dim3(NT), 0, (int)BV, (int)n_bands, d_part, d_sumsq, d_nin));
     if (sumsq) HIPCHK(c, op.down(sumsq, d_sumsq, BV * sizeof(uint64_t)));
     if (n_in) HIPCHK(c, op.down(n_in, d_nin, BV * sizeof(uint32_t)));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+// A motion segmentation composed into one flow field and a label image (eincm_motion_layers.hip.h): per pixel the
+// quantised staged weights of the events that fired there, summed per model; the label is the model of the largest sum and Theta that
+// model's field, or the blend.  The checks, their order and the layout are eincm_motion_layers.h's; q = M c is motion_q.  Only the
+// gather's copy of the staged events and its weights are read; the mass images, the largest piece, live in the call frame's scratch,
+// which grows on the first call.
+int eincm_compose_motions(eincm_ctx* c, int n_models, const double* coeffs, unsigned flags, double* theta, uint8_t* labels, uint32_t* mass,
+                          uint64_t* total) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    const auto& mo = c->motion;
+    const MlState st{!c->fl.idle(), theta || labels || mass || total, c->staged, mo.set, c->fp64, c->sharded_staging || c->constants_pending,
+                     c->staged ? g.B : 0, c->win_events.data(), mo.set ? mo.model.n_coeffs : 0, c->h_tilecount.data(),
+                     c->staged ? (int64_t)c->h_tilecount.size() : 0};
+    int bad_b = 0; int64_t bad_i = 0;
+    if (const MlFault f = ml_check(st, n_models, coeffs, flags, &bad_b, &bad_i)) {
+        if (f == ML_COEFFS && bad_b >= 0)
+            return fail(c, ml_code(f), "eincm_compose_motions: %s: window %d, coefficient %d", ml_why(f), bad_b, (int)bad_i);
+        if (f == ML_CROWDED)
+            return fail(c, ml_code(f), "eincm_compose_motions: %s: window %d, tile %lld holds %d", ml_why(f), bad_b, (long long)bad_i,
+                        (int)c->h_tilecount[(size_t)bad_b * g.ntiles + (size_t)bad_i]);
+        return fail(c, ml_code(f), "eincm_compose_motions: %s", ml_why(f));
+    }
+    const int B = g.B, K = n_models, G = B / K, Kc = mo.model.n_coeffs;
+    const size_t npix = (size_t)g.H * g.W, bins = (size_t)B * g.ntiles, GK = (size_t)G * K;
+    OneShot op(c);
+    const auto d_off = op.piece<int32_t>(bins + 1);
+    const auto d_q = op.piece<double>((size_t)B * MOTION_NQ);
+    const auto d_mass = op.piece<uint32_t>(GK * npix);
+    const auto d_part = op.piece<unsigned long long>(GK * g.ntiles);
+    const auto d_total = op.piece<unsigned long long>(GK);
+    const auto d_theta = op.piece<double2>((size_t)G * npix, theta != nullptr);
+    const auto d_lab = op.piece<uint8_t>((size_t)G * npix, labels != nullptr);
+    int32_t* h_off = op.host_buf<int32_t>(bins + 1);                     // d_off and d_q go up from these
+    double* h_q = op.host_buf<double>((size_t)B * MOTION_NQ);
+    int64_t run = 0;                                                     // (the bins lie one after another in (window, tile) order: eincm_binning.hip.h)
+    for (size_t i = 0; i < bins; ++i) { h_off[i] = (int32_t)run; run += c->h_tilecount[i]; }
+    h_off[bins] = (int32_t)run;
+    if (run != c->stage.N) return fail(c, EINCM_ERR_STATE, "eincm_compose_motions: internal: the tile populations do not add up to the staged events");
+    for (int b = 0; b < B; ++b) motion_q(mo.model, coeffs + (size_t)b * Kc, h_q + (size_t)b * MOTION_NQ);
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_off, h_off, (bins + 1) * sizeof(int32_t)));
+    HIPCHK(c, op.up(d_q, h_q, (size_t)B * MOTION_NQ * sizeof(double)));
+    const MlGeom mg{g.H, g.W, g.tilesX, g.ntiles, K, flags, mo.model.cx, mo.model.cy, mo.model.scale};
+    const float* w = c->stage.weighted ? (const float*)c->d_w_g : nullptr;          // (an unweighted batch has no ev_w: q = 4096)
+    HIPCHK(c, op.launch(k_ml_mass, dim3((unsigned)g.ntiles, (unsigned)G), dim3(ML_NT), (size_t)K * ML_TILE_PIX * sizeof(uint32_t), mg, d_off,
+                        c->d_xy_g, w, d_mass, d_part));
+    HIPCHK(c, op.launch(k_ml_total, dim3((unsigned)GK), dim3(64), 0, g.ntiles, d_part, d_total));
+    if (theta || labels)
+        HIPCHK(c, op.launch(k_ml_compose, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)G), dim3(NT), 0, mg, d_mass, d_total, d_q, d_theta,
+                            d_lab));
+    if (theta) HIPCHK(c, op.down(theta, d_theta, (size_t)G * npix * sizeof(double2)));   // (host memory: the caller's, all four)
+    if (labels) HIPCHK(c, op.down(labels, d_lab, (size_t)G * npix));
+    if (mass) HIPCHK(c, op.down(mass, d_mass, GK * npix * sizeof(uint32_t)));
+    if (total) HIPCHK(c, op.down(total, d_total, GK * sizeof(uint64_t)));
     HIPCHK(c, op.sync());
     return EINCM_OK;
 }

@@ -720,6 +720,46 @@ def check_contrast_landscape_args(coeffs, n_events, n_coeffs, t_ref, cell, keep,
     return c, t, int(cell), keep, want
 
 
+ML_OUTPUTS = ('theta', 'labels', 'mass', 'total')
+
+
+def compose_motions_layout(n_groups, n_models, sensor_size):
+    """The shapes of eincm_compose_motions' four outputs and where a group's block starts in each, in elements of the output's own type
+    (csrc/eincm_motion_layers.h: ml_theta_offset, ml_labels_offset, ml_mass_offset, ml_total_offset, restated;
+    tests/test_motion_layers_interface.py compares the two): a dict name -> (shape, dtype, offsets (G,) int64)."""
+    G, K, H, W = int(n_groups), int(n_models), int(sensor_size[0]), int(sensor_size[1])
+    g = np.arange(G, dtype=np.int64)
+    return {'theta': ((G, H, W, 2), np.float64, g * (H * W * 2)), 'labels': ((G, H, W), np.uint8, g * (H * W)),
+            'mass': ((G, K, H, W), np.uint32, g * (K * H * W)), 'total': ((G, K), np.uint64, g * K)}
+
+
+def check_compose_args(n_models, coeffs, n_windows, n_coeffs, mode, fill, want):
+    """The arguments of Engine.compose_motions, checked without a GPU: n_models an integer within 1 .. RS_MAX_MODELS; mode one of
+    ML_MODES and fill one of ML_FILLS; want a non-empty choice of ML_OUTPUTS without repeats; coeffs a numeric (B, K_c) array, B the
+    staged windows and K_c the model's coefficients where the engine knows them (n_windows 0: nothing staged, n_coeffs None: no model
+    - the library refuses those itself).  What depends on the staged batch or on the values - nothing staged, no model, the context's
+    precision, B not a multiple of n_models, unequal groups, a coefficient that is not finite, a crowded tile - is left to the library,
+    so that those refusals carry the codes and the sentences of csrc/eincm_motion_layers.h.  Returns (n_models, coeffs float64
+    C-contiguous, flags, want)."""
+    if isinstance(n_models, bool) or not isinstance(n_models, (int, np.integer)) or not 1 <= int(n_models) <= L.RS_MAX_MODELS:
+        raise ValueError(f'n_models must be an integer within 1 .. {L.RS_MAX_MODELS}, got {n_models!r}')
+    if mode not in L.ML_MODES:
+        raise ValueError(f'mode {mode!r} unknown; one of {tuple(L.ML_MODES)}')
+    if fill not in L.ML_FILLS:
+        raise ValueError(f'fill {fill!r} unknown; one of {tuple(L.ML_FILLS)}')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in ML_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a non-empty choice of {ML_OUTPUTS} without repeats, got {want!r}')
+    c = np.asarray(coeffs)
+    if c.dtype.kind not in 'fiu':
+        raise ValueError(f'coeffs must be numeric, got dtype {c.dtype}')
+    rows = 'B' if not n_windows else str(int(n_windows))
+    cols = 'K_c' if n_coeffs is None else str(int(n_coeffs))
+    if c.ndim != 2 or (n_windows and c.shape[0] != n_windows) or (n_coeffs is not None and c.shape[1] != n_coeffs):
+        raise ValueError(f'coeffs must be ({rows}, {cols}): one row of model coefficients per staged window, got {np.shape(coeffs)}')
+    return int(n_models), np.ascontiguousarray(c, dtype=np.float64), L.ML_MODES[mode] | L.ML_FILLS[fill], want
+
+
 def check_score_images(images, n_windows, n_refs, sensor_size):
     """The caller's image stack of Engine.event_scores as contiguous float32 (B,R,H,W); (R,H,W) stands for it when B == 1.  None stays
     None (the IWEs of the last evaluation).  Anything else is a ValueError, raised before any library call."""
@@ -1806,6 +1846,25 @@ class Engine:
             out['sumsq'] = sumsq
         if n_in is not None:
             out['n_in'] = n_in
+        return out
+
+    def compose_motions(self, n_models, coeffs, mode='hard', fill='zero', want=('theta', 'labels')):
+        """A motion segmentation composed into one flow field and a label image, one device operation.  The
+        staged batch is G = B / n_models groups of n_models consecutive windows that hold the same events with complementary
+        weights, as event_responsibilities reads it; coeffs (B, K_c) are the models' coefficients, window g * n_models + l model l of
+        group g.  Per sensor pixel the staged weights of the events that fired there are quantised to 1/4096 and summed per model.
+        Returns a dict of ``want``: 'mass' (G, n_models, H, W) uint32, those sums; 'total' (G, n_models) uint64, their sums over the
+        pixels; 'labels' (G, H, W) uint8, the lowest model with the largest mass, ML_NO_LABEL (255) where no mass lies; 'theta'
+        (G, H, W, 2) float64, what flow_errors, advect_theta and loss_grad take: mode 'hard' writes the label's field
+        (model.field(coeffs) there, bit for bit), 'soft' the mass-weighted blend of the models' fields; a pixel without mass takes
+        fill 'zero', (0, 0), or 'dominant', the field of the group's model of the largest total.  Needs staged windows and a motion
+        model, no evaluation.  Exact: equal to tests/_motion_layers_witness.py byte for byte, and the same bytes on every run."""
+        K, c, flags, want = check_compose_args(n_models, coeffs, self.B, None if self.motion_model is None else self.motion_model.n_coeffs,
+                                               mode, fill, want)
+        lay = compose_motions_layout(self.B // K, K, (self.H, self.W))
+        out = {name: np.zeros(lay[name][0], dtype=lay[name][1]) for name in want}
+        addr = lambda name: out[name].ctypes.data if name in out else None
+        self._check(self._lib.eincm_compose_motions(self._ctx, K, c.ctypes.data, flags, addr('theta'), addr('labels'), addr('mass'), addr('total')))
         return out
 
     def scaled_theta(self):

@@ -9,7 +9,10 @@ straight into the staged layouts (Engine.apply_responsibilities).  The two retur
 
 The EM is local and needs starting coefficients.  seed_motions finds them without a gradient: a coarse-to-fine
 grid search on the contrast landscape (Engine.contrast_landscape), one motion after the other, each on the events that the motions
-found before it do not explain."""
+found before it do not explain.
+
+What the EM ends in - K coefficient vectors and one weight per event and model - becomes one flow field and a label image through
+segmented_flow (Engine.compose_motions): the form that flow_errors, advect_theta and a submission take."""
 import numpy as np
 
 from . import _lib as L
@@ -148,6 +151,52 @@ def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, we
             callback(it, record)
         active = active & (r['mass'] >= min_mass)
     return history
+
+
+# ---- the segmentation as one flow field and a label image ---------------------------------------------------------
+def check_segmented_flow_args(windows, model, record):
+    """The arguments of segmented_flow, checked without a GPU.  Returns (coeffs (G, K, n_coeffs) float64, weights as G lists of K
+    float32 arrays)."""
+    G = len(windows)
+    if G < 1:
+        raise ValueError('windows must hold at least one (xs, ys, ts, edges, edge_ts) tuple')
+    for g, w in enumerate(windows):
+        if len(w) != 5:
+            raise ValueError(f'window {g}: a (xs, ys, ts, edges, edge_ts) tuple, got {len(w)} elements (the weights are the record\'s)')
+    if not isinstance(record, dict) or 'coeffs' not in record or 'weights' not in record:
+        raise ValueError("record must be a history record of segment_motions: a dict with 'coeffs' and 'weights'")
+    c = np.asarray(record['coeffs'], dtype=np.float64)
+    if c.ndim != 3 or c.shape[0] != G or c.shape[1] < 1 or c.shape[2] != model.n_coeffs:
+        raise ValueError(f"record['coeffs'] must be ({G}, K, {model.n_coeffs}), got {c.shape}")
+    K = c.shape[1]
+    weights = record['weights']
+    if weights is None:
+        raise ValueError("record['weights'] is None (segment_motions_in_place with record_weights=False): the engine still holds the "
+                         "weights, call engine.compose_motions")
+    if len(weights) != G or any(len(wg) != K for wg in weights):
+        raise ValueError(f"record['weights'] must be {G} lists of {K} weight arrays")
+    weights = [[np.ascontiguousarray(w, dtype=np.float32) for w in wg] for wg in weights]
+    for g, wg in enumerate(weights):
+        n = len(windows[g][0])
+        if any(w.shape != (n,) for w in wg):
+            raise ValueError(f"window {g}: every array of record['weights'] must be ({n},)")
+    return c, weights
+
+
+def segmented_flow(engine, windows, model, record, mode='hard', fill='dominant'):
+    """The flow field and the label image of a segmentation (Engine.compose_motions).  windows: the G
+    (xs, ys, ts, edges, edge_ts) tuples that were segmented; record: one record of segment_motions' history (its 'coeffs' (G, K,
+    n_coeffs) and 'weights').  Stages the G*K windows with the record's weights, sets the model and returns compose_motions' dict
+    with all four outputs: 'theta' (G, H, W, 2) is what flow_errors, advect_theta, a dense loss_grad and
+    evaluation.dsec_submission_flow take.
+
+    After segment_motions_in_place the engine already holds the final weights in its staged layouts, so
+    ``engine.compose_motions(K, record['coeffs'].reshape(G * K, -1))`` gives the last record's result with no staging at all."""
+    c, weights = check_segmented_flow_args(windows, model, record)
+    G, K = c.shape[:2]
+    engine.set_motion_model(model)
+    engine.set_windows([tuple(windows[g]) + (weights[g][l],) for g in range(G) for l in range(K)])
+    return engine.compose_motions(K, c.reshape(G * K, -1), mode=mode, fill=fill, want=('theta', 'labels', 'mass', 'total'))
 
 
 # ---- seeds for the models: a peeling search on the contrast landscape (DESIGN.md section 28) -------------------------------------------

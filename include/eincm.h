@@ -36,7 +36,8 @@ extern "C" {
                                *    carried along its own flow to the next window), eincm_event_responsibilities (those scores normalised over
                                *    the models of a group: the E-step of a motion segmentation), eincm_contrast_landscape (the integer contrast of
                                *    the warped events on a grid of candidate motion coefficients), eincm_set_weights, eincm_get_stage_order,
-                               *    eincm_get_staged_weights (a batch staged with EINCM_SW_KEEP_ORDER takes new weights in place) */
+                               *    eincm_get_staged_weights (a batch staged with EINCM_SW_KEEP_ORDER takes new weights in place), eincm_compose_motions
+                               *    (a motion segmentation composed into one flow field and a label image) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -379,6 +380,42 @@ int eincm_event_responsibilities(eincm_ctx* ctx, int n_models, const float* imag
 #define EINCM_CL_MAX_CANDIDATES 4096
 int eincm_contrast_landscape(eincm_ctx* ctx, int n_candidates, const double* coeffs, const double* t_ref, int cell,
                              const uint8_t* const* keep, uint64_t* sumsq, uint32_t* n_in);
+
+/* A motion segmentation composed into one flow field and a label image.  The staged batch of B windows is read
+ * as G = B / n_models groups of K = n_models consecutive windows that hold the same events, as eincm_event_responsibilities reads it;
+ * l is a model of a group, p a sensor pixel, e an event of the group at its raw integer pixel (x_e, y_e).  With w the staged weight of
+ * event e in window g * K + l (what eincm_set_windows_weighted, eincm_set_weights or EINCM_RS_APPLY left; 1 in an unweighted batch):
+ *     q(w)          = (uint32) rintf(w * 4096.0f): the scaling is exact, the rounding half to even; q <= 4096 as w lies in [0, 1]
+ *     mass[g, l, p] = sum of q(w) over the events of window g * K + l with (y_e, x_e) = p, as uint32
+ *     total[g, l]   = sum_p mass[g, l, p], as uint64
+ *     label[g, p]   = the lowest l with the largest mass[g, l, p] if that mass is > 0, else EINCM_ML_NO_LABEL
+ *     f_l(p)        = the motion model's field at p for coeffs[g * K + l]: the bits of eincm_motion_field there
+ *     EINCM_ML_HARD:  Theta[g, p] = f_label(p)
+ *     EINCM_ML_SOFT:  S = sum_l mass[g, l, p] as uint64, a_l = (double)mass_l / (double)S; Theta = a_0 * f_0, then Theta = Theta + a_l * f_l
+ *                     for l = 1 .. K - 1 in order, per component: every division, product and sum rounded on its own, no contraction
+ *     a pixel with S = 0 (no event, or every weight quantised to 0) keeps the label EINCM_ML_NO_LABEL and takes the fill:
+ *     EINCM_ML_FILL_ZERO: Theta = (0, 0);  EINCM_ML_FILL_DOMINANT: Theta = f_d(p), d the lowest l with the largest total[g, l], or
+ *     (0, 0) if that total is 0
+ *   n_models  K, 1 .. EINCM_RS_MAX_MODELS
+ *   coeffs    (B, K_c) finite doubles, K_c the n_coeffs of the context's motion model (eincm_set_motion_model)
+ *   flags     one of EINCM_ML_HARD, EINCM_ML_SOFT | one of EINCM_ML_FILL_ZERO, EINCM_ML_FILL_DOMINANT; other bits are reserved
+ *   theta     NULL, or (G, H, W, 2) doubles          labels  NULL, or (G, H, W) bytes
+ *   mass      NULL, or (G, n_models, H, W) uint32    total   NULL, or (G, n_models) uint64
+ * Integer up to one thread's fp64 blend: no float is accumulated across threads and nothing is accumulated by global atomics, so every
+ * run gives the same bytes.  It reads no IWE, so it needs no evaluation, and the splat window does not matter to it.  A batch with no
+ * events is valid: its masses and totals are 0, its labels EINCM_ML_NO_LABEL, its Theta all fill.
+ * Refused before anything is written, in this order: EINCM_ERR_STATE an evaluation in flight; EINCM_ERR_ARG all four outputs NULL;
+ * EINCM_ERR_STATE nothing staged or no motion model set; EINCM_ERR_UNSUPPORTED an EINCM_CF_FP64 context, an event-sharded staging
+ * (EINCM_SW_DEFER_CONSTANTS); EINCM_ERR_ARG n_models outside 1 .. EINCM_RS_MAX_MODELS, B not a multiple of n_models, unequal n_events
+ * inside a group, coeffs NULL or not finite (the message names window and index), unknown flag bits; EINCM_ERR_UNSUPPORTED a 32x32
+ * source tile of one window with 2^20 events or more (then no pixel's sum can reach 2^32: (2^20 - 1) * 4096 < 2^32). */
+#define EINCM_ML_HARD          0u   /* flags: every labelled pixel takes the flow of its label */
+#define EINCM_ML_SOFT          1u   /* flags: every labelled pixel takes the mass-weighted blend of the models' flows */
+#define EINCM_ML_FILL_ZERO     0u   /* flags: a pixel without mass takes (0, 0) */
+#define EINCM_ML_FILL_DOMINANT 2u   /* flags: a pixel without mass takes the flow of the group's model of the largest total mass */
+#define EINCM_ML_NO_LABEL      255  /* labels: no event with a weight that quantises above 0 fired here */
+int eincm_compose_motions(eincm_ctx* ctx, int n_models, const double* coeffs, unsigned flags, double* theta, uint8_t* labels,
+                          uint32_t* mass, uint64_t* total);
 
 /* compute_weights_for_multi_reference (losses.py:39-46) */
 int eincm_multi_ref_weights(int n_refs, double* w);
