@@ -47,6 +47,7 @@ ML_MODES = {'hard': ML_HARD, 'soft': ML_SOFT}
 ML_FILLS = {'zero': ML_FILL_ZERO, 'dominant': ML_FILL_DOMINANT}
 ML_NO_LABEL = 255                                                    # EINCM_ML_NO_LABEL
 ML_Q_ONE = 4096                                                      # the quantised weight of 1 (csrc/eincm_motion_layers.h)
+MD_NONE, MD_UNBOUNDED = 0xFFFFFFFF, 0xFFFFFFFF                       # EINCM_MD_NONE (dist2), EINCM_MD_UNBOUNDED (max_dist2) of eincm_densify_motions
 
 
 class Params(C.Structure):
@@ -203,6 +204,9 @@ SIGNATURES = [
     ('eincm_contrast_landscape', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     # a motion segmentation composed into one flow field and a label image (raw addresses, as above)
     ('eincm_compose_motions', C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # that composition made dense: every pixel takes the label of its nearest labelled pixel (raw addresses, as above)
+    ('eincm_densify_motions', C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     # a solved theta carried along its own flow to the next window (raw addresses, as above)
     ('eincm_theta_advect', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

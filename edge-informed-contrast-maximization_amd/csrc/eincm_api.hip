@@ -44,6 +44,8 @@
 #include "eincm_responsibilities.hip.h"
 #include "eincm_motion_layers.h"
 #include "eincm_motion_layers.hip.h"
+#include "eincm_motion_fill.h"
+#include "eincm_motion_fill.hip.h"
 #include "eincm_theta_advect.h"
 #include "eincm_theta_advect.hip.h"
 #include "eincm_contrast_landscape.h"
@@ -2577,6 +2579,76 @@ int eincm_compose_motions(eincm_ctx* c, int n_models, const double* coeffs, unsi
     if (labels) HIPCHK(c, op.down(labels, d_lab, (size_t)G * npix));
     if (mass) HIPCHK(c, op.down(mass, d_mass, GK * npix * sizeof(uint32_t)));
     if (total) HIPCHK(c, op.down(total, d_total, GK * sizeof(uint64_t)));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+// That composition made dense (eincm_motion_fill.hip.h): the masses and totals by the same two kernels, then the
+// sites, the feature transform (columns, rows) and the composition at every pixel's nearest site.  The checks, their order and the
+// layout are eincm_motion_fill.h's.  Only what an output asked for needs is allocated, launched and downloaded.
+int eincm_densify_motions(eincm_ctx* c, int n_models, const double* coeffs, unsigned flags, uint32_t min_site_mass, uint32_t max_dist2,
+                          double* theta, uint8_t* labels, uint32_t* dist2, int32_t* nearest, uint32_t* n_sites) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    const auto& mo = c->motion;
+    const MlState st{!c->fl.idle(), theta || labels || dist2 || nearest || n_sites, c->staged, mo.set, c->fp64,
+                     c->sharded_staging || c->constants_pending, c->staged ? g.B : 0, c->win_events.data(), mo.set ? mo.model.n_coeffs : 0,
+                     c->h_tilecount.data(), c->staged ? (int64_t)c->h_tilecount.size() : 0};
+    int bad_b = 0; int64_t bad_i = 0;
+    if (const int f = mf_check(st, g.W, n_models, coeffs, flags, min_site_mass, &bad_b, &bad_i)) {
+        if (f == ML_COEFFS && bad_b >= 0)
+            return fail(c, mf_code(f), "eincm_densify_motions: %s: window %d, coefficient %d", mf_why(f), bad_b, (int)bad_i);
+        if (f == ML_CROWDED)
+            return fail(c, mf_code(f), "eincm_densify_motions: %s: window %d, tile %lld holds %d", mf_why(f), bad_b, (long long)bad_i,
+                        (int)c->h_tilecount[(size_t)bad_b * g.ntiles + (size_t)bad_i]);
+        return fail(c, mf_code(f), "eincm_densify_motions: %s", mf_why(f));
+    }
+    const int B = g.B, K = n_models, G = B / K, Kc = mo.model.n_coeffs;
+    const size_t npix = (size_t)g.H * g.W, bins = (size_t)B * g.ntiles, GK = (size_t)G * K, nblk = (npix + NT - 1) / NT;
+    const bool composed = theta || labels, transformed = composed || dist2 || nearest;
+    OneShot op(c);
+    const auto d_off = op.piece<int32_t>(bins + 1);
+    const auto d_q = op.piece<double>((size_t)B * MOTION_NQ, composed);
+    const auto d_mass = op.piece<uint32_t>(GK * npix);
+    const auto d_part = op.piece<unsigned long long>(GK * g.ntiles);
+    const auto d_total = op.piece<unsigned long long>(GK);
+    const auto d_site = op.piece<uint8_t>((size_t)G * npix);
+    const auto d_cnt = op.piece<uint32_t>((size_t)G * nblk);
+    const auto d_nsites = op.piece<uint32_t>((size_t)G, n_sites != nullptr);
+    const auto d_rec = op.piece<uint32_t>((size_t)G * npix, transformed);
+    const auto d_near = op.piece<int32_t>((size_t)G * npix, composed || nearest);
+    const auto d_d2 = op.piece<uint32_t>((size_t)G * npix, composed || dist2);
+    const auto d_theta = op.piece<double2>((size_t)G * npix, theta != nullptr);
+    const auto d_lab = op.piece<uint8_t>((size_t)G * npix, labels != nullptr);
+    int32_t* h_off = op.host_buf<int32_t>(bins + 1);                     // d_off and d_q go up from these
+    double* h_q = op.host_buf<double>((size_t)B * MOTION_NQ);
+    int64_t run = 0;                                                     // (as eincm_compose_motions: the bins lie in (window, tile) order)
+    for (size_t i = 0; i < bins; ++i) { h_off[i] = (int32_t)run; run += c->h_tilecount[i]; }
+    h_off[bins] = (int32_t)run;
+    if (run != c->stage.N) return fail(c, EINCM_ERR_STATE, "eincm_densify_motions: internal: the tile populations do not add up to the staged events");
+    for (int b = 0; b < B; ++b) motion_q(mo.model, coeffs + (size_t)b * Kc, h_q + (size_t)b * MOTION_NQ);
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_off, h_off, (bins + 1) * sizeof(int32_t)));
+    if (composed) HIPCHK(c, op.up(d_q, h_q, (size_t)B * MOTION_NQ * sizeof(double)));
+    const MlGeom mg{g.H, g.W, g.tilesX, g.ntiles, K, flags, mo.model.cx, mo.model.cy, mo.model.scale};
+    const float* w = c->stage.weighted ? (const float*)c->d_w_g : nullptr;          // (an unweighted batch has no ev_w: q = 4096)
+    HIPCHK(c, op.launch(k_ml_mass, dim3((unsigned)g.ntiles, (unsigned)G), dim3(ML_NT), (size_t)K * ML_TILE_PIX * sizeof(uint32_t), mg, d_off,
+                        c->d_xy_g, w, d_mass, d_part));
+    if (composed) HIPCHK(c, op.launch(k_ml_total, dim3((unsigned)GK), dim3(64), 0, g.ntiles, d_part, d_total));
+    HIPCHK(c, op.launch(k_mf_sites, dim3((unsigned)nblk, (unsigned)G), dim3(NT), 0, (int)npix, K, min_site_mass, d_mass, d_site, d_cnt));
+    if (n_sites) HIPCHK(c, op.launch(k_mf_count, dim3((unsigned)G), dim3(64), 0, (int)nblk, d_cnt, d_nsites));
+    if (transformed) {
+        HIPCHK(c, op.launch(k_mf_cols, dim3((unsigned)((g.W + NT - 1) / NT), (unsigned)G), dim3(NT), 0, g.H, g.W, d_site, d_rec));
+        HIPCHK(c, op.launch(k_mf_rows, dim3((unsigned)g.H, (unsigned)G), dim3(NT), (size_t)g.W * sizeof(uint32_t), g.H, g.W, d_rec, d_near, d_d2));
+    }
+    if (composed)
+        HIPCHK(c, op.launch(k_mf_compose, dim3((unsigned)nblk, (unsigned)G), dim3(NT), 0, mg, max_dist2, d_mass, d_total, d_q, d_near, d_d2,
+                            d_theta, d_lab));
+    if (theta) HIPCHK(c, op.down(theta, d_theta, (size_t)G * npix * sizeof(double2)));   // (host memory: the caller's, all five)
+    if (labels) HIPCHK(c, op.down(labels, d_lab, (size_t)G * npix));
+    if (dist2) HIPCHK(c, op.down(dist2, d_d2, (size_t)G * npix * sizeof(uint32_t)));
+    if (nearest) HIPCHK(c, op.down(nearest, d_near, (size_t)G * npix * sizeof(int32_t)));
+    if (n_sites) HIPCHK(c, op.down(n_sites, d_nsites, (size_t)G * sizeof(uint32_t)));
     HIPCHK(c, op.sync());
     return EINCM_OK;
 }

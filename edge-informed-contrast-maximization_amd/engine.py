@@ -760,6 +760,47 @@ def check_compose_args(n_models, coeffs, n_windows, n_coeffs, mode, fill, want):
     return int(n_models), np.ascontiguousarray(c, dtype=np.float64), L.ML_MODES[mode] | L.ML_FILLS[fill], want
 
 
+MF_OUTPUTS = ('theta', 'labels', 'dist2', 'nearest', 'n_sites')
+
+
+def densify_motions_layout(n_groups, sensor_size):
+    """The shapes of eincm_densify_motions' five outputs and where a group's block starts in each, in elements of the output's own
+    type (csrc/eincm_motion_fill.h: mf_theta_offset ... mf_nsites_offset, restated; tests/test_host_motion_fill.py compares the two):
+    a dict name -> (shape, dtype, offsets (G,) int64)."""
+    G, H, W = int(n_groups), int(sensor_size[0]), int(sensor_size[1])
+    g = np.arange(G, dtype=np.int64)
+    return {'theta': ((G, H, W, 2), np.float64, g * (H * W * 2)), 'labels': ((G, H, W), np.uint8, g * (H * W)),
+            'dist2': ((G, H, W), np.uint32, g * (H * W)), 'nearest': ((G, H, W), np.int32, g * (H * W)), 'n_sites': ((G,), np.uint32, g)}
+
+
+def check_densify_args(n_models, coeffs, n_windows, n_coeffs, mode, fallback, min_site_mass, max_distance, want):
+    """The arguments of Engine.densify_motions, checked without a GPU.  n_models, coeffs and mode as check_compose_args takes them;
+    fallback one of ML_FILLS (what a pixel that no site reaches takes); min_site_mass an integer within 1 .. 2^32 - 1; max_distance
+    None (no bound) or a finite number >= 0 in pixels, which becomes max_dist2 = floor(float64(max_distance)^2), at most 0xFFFFFFFE;
+    want a non-empty choice of MF_OUTPUTS without repeats.  What depends on the staged batch or on the values is left to the library,
+    as there.  Returns (n_models, coeffs float64 C-contiguous, flags, min_site_mass, max_dist2, want)."""
+    if mode not in L.ML_MODES:
+        raise ValueError(f'mode {mode!r} unknown; one of {tuple(L.ML_MODES)}')
+    if fallback not in L.ML_FILLS:
+        raise ValueError(f'fallback {fallback!r} unknown; one of {tuple(L.ML_FILLS)}')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in MF_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a non-empty choice of {MF_OUTPUTS} without repeats, got {want!r}')
+    if isinstance(min_site_mass, bool) or not isinstance(min_site_mass, (int, np.integer)) or not 1 <= int(min_site_mass) <= 0xFFFFFFFF:
+        raise ValueError(f'min_site_mass must be an integer within 1 .. 2^32 - 1 (4096 is one event of weight 1), got {min_site_mass!r}')
+    if max_distance is None:
+        max_dist2 = L.MD_UNBOUNDED
+    else:
+        if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float, np.integer, np.floating)) \
+                or not np.isfinite(max_distance) or max_distance < 0:
+            raise ValueError(f'max_distance must be None or a finite number >= 0, got {max_distance!r}')
+        d = np.float64(max_distance)
+        with np.errstate(over='ignore'):
+            max_dist2 = int(min(np.floor(d * d), np.float64(0xFFFFFFFE)))
+    K, c, flags, _ = check_compose_args(n_models, coeffs, n_windows, n_coeffs, mode, fallback, ('theta',))
+    return K, c, flags, int(min_site_mass), max_dist2, want
+
+
 def check_score_images(images, n_windows, n_refs, sensor_size):
     """The caller's image stack of Engine.event_scores as contiguous float32 (B,R,H,W); (R,H,W) stands for it when B == 1.  None stays
     None (the IWEs of the last evaluation).  Anything else is a ValueError, raised before any library call."""
@@ -1865,6 +1906,27 @@ class Engine:
         out = {name: np.zeros(lay[name][0], dtype=lay[name][1]) for name in want}
         addr = lambda name: out[name].ctypes.data if name in out else None
         self._check(self._lib.eincm_compose_motions(self._ctx, K, c.ctypes.data, flags, addr('theta'), addr('labels'), addr('mass'), addr('total')))
+        return out
+
+    def densify_motions(self, n_models, coeffs, mode='hard', fallback='dominant', min_site_mass=1, max_distance=None,
+                        want=('theta', 'labels')):
+        """compose_motions made dense, one device operation: a pixel is a site if its summed mass reaches
+        min_site_mass (4096 is one event of weight 1), and every pixel within max_distance pixels of a site (None: any distance) takes
+        the label of its nearest site - equal distances go to the lowest row, then the lowest column - and is composed from that
+        site's masses and the models' fields at the pixel itself.  A pixel no site reaches keeps ML_NO_LABEL and takes fallback
+        'zero' or 'dominant', compose_motions' fill.  The staged batch, n_models, coeffs and mode are compose_motions'.  Returns a
+        dict of ``want``: 'theta' (G, H, W, 2) float64, 'labels' (G, H, W) uint8, 'dist2' (G, H, W) uint32, the squared distance to
+        the nearest site (MD_NONE in a group without one), 'nearest' (G, H, W) int32, that site as y * W + x (-1), 'n_sites' (G,)
+        uint32.  With min_site_mass=1 and max_distance=0 'theta' and 'labels' are compose_motions' bytes.  Exact: equal to
+        tests/_motion_fill_witness.py byte for byte, and the same bytes on every run."""
+        K, c, flags, site_mass, max_dist2, want = check_densify_args(
+            n_models, coeffs, self.B, None if self.motion_model is None else self.motion_model.n_coeffs, mode, fallback, min_site_mass,
+            max_distance, want)
+        lay = densify_motions_layout(self.B // K, (self.H, self.W))
+        out = {name: np.zeros(lay[name][0], dtype=lay[name][1]) for name in want}
+        addr = lambda name: out[name].ctypes.data if name in out else None
+        self._check(self._lib.eincm_densify_motions(self._ctx, K, c.ctypes.data, flags, site_mass, max_dist2, addr('theta'), addr('labels'),
+                                                    addr('dist2'), addr('nearest'), addr('n_sites')))
         return out
 
     def scaled_theta(self):

@@ -199,6 +199,22 @@ def segmented_flow(engine, windows, model, record, mode='hard', fill='dominant')
     return engine.compose_motions(K, c.reshape(G * K, -1), mode=mode, fill=fill, want=('theta', 'labels', 'mass', 'total'))
 
 
+def segmented_flow_dense(engine, windows, model, record, mode='hard', fallback='dominant', min_site_mass=1, max_distance=None):
+    """segmented_flow with the pixels that hold no event filled from the nearest one that does (Engine.densify_motions, DESIGN.md
+    section 31).  windows, model and record as segmented_flow takes them.  Stages the G*K windows with the record's weights, sets the
+    model and returns densify_motions' dict with all five outputs: 'theta' (G, H, W, 2) is dense, so the inside of an object takes
+    the object's motion and not the background's.
+
+    After segment_motions_in_place the engine already holds the final weights in its staged layouts, so a bare
+    ``engine.densify_motions(K, record['coeffs'].reshape(G * K, -1))`` gives the last record's result with no staging at all."""
+    c, weights = check_segmented_flow_args(windows, model, record)
+    G, K = c.shape[:2]
+    engine.set_motion_model(model)
+    engine.set_windows([tuple(windows[g]) + (weights[g][l],) for g in range(G) for l in range(K)])
+    return engine.densify_motions(K, c.reshape(G * K, -1), mode=mode, fallback=fallback, min_site_mass=min_site_mass,
+                                  max_distance=max_distance, want=('theta', 'labels', 'dist2', 'nearest', 'n_sites'))
+
+
 # ---- seeds for the models: a peeling search on the contrast landscape (DESIGN.md section 28) -------------------------------------------
 def landscape_cell(step):
     """The cell size a grid of this step is evaluated at: the smallest of CL_CELLS that is >= the step, 8 beyond."""

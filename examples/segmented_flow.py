@@ -5,7 +5,11 @@ composed into one (H, W, 2) flow field and a label image (Engine.compose_motions
 per-event download.  The composed field is what the rest of the engine takes: it is scored against the scene's true flow
 (Engine.flow_eval_stage / flow_errors) and carried to the next window as its prior (Engine.advect_theta).
 
+With --fill nearest the pixels that hold no event take the label of the nearest one that does (Engine.densify_motions, section 31)
+instead of the window's dominant motion, and the dense error over ALL pixels of the true flow is printed for both fills.
+
     python3 examples/segmented_flow.py [--events 6000] [--iters 3] [--span 16] [--mode hard|soft]
+                                       [--fill dominant|nearest] [--max-distance PX] [--min-site-mass Q]
 """
 import argparse
 import importlib
@@ -23,6 +27,10 @@ ap.add_argument('--events', type=int, default=6000, help='events of the window')
 ap.add_argument('--iters', type=int, default=3, help='EM iterations')
 ap.add_argument('--span', type=float, default=16.0, help='half-range of the seed search in px per window')
 ap.add_argument('--mode', choices=('hard', 'soft'), default='hard', help="every pixel takes its label's flow, or the mass-weighted blend")
+ap.add_argument('--fill', choices=('dominant', 'nearest'), default='dominant',
+                help="what a pixel without events takes: the window's dominant motion, or the label of the nearest pixel that has one")
+ap.add_argument('--max-distance', type=float, default=None, help='--fill nearest: reach of a labelled pixel in px (default: unbounded)')
+ap.add_argument('--min-site-mass', type=int, default=1, help='--fill nearest: summed mass a pixel needs to be a site (4096 = one whole event)')
 a = ap.parse_args()
 
 H, W, R = 64, 96, 2
@@ -60,6 +68,18 @@ with engine.Engine((H, W), 2 * K * a.events, max_refs=R, max_windows=K) as eng:
     print(f'composed ({a.mode}): {int(seen.sum())} of {H * W} pixels labelled, {int((labels == 0).sum())} / {int((labels == 1).sum())} per model; '
           f'total mass {[int(t) / 4096 for t in out["total"][0]]} events')
     print(f'pixel label accuracy on the labelled pixels {float((((labels ^ swap) == (~left).astype(np.uint8)) & seen).sum() / max(int(seen.sum()), 1)):.3f}')
+
+    if a.fill == 'nearest':
+        # the same staged weights once more: every pixel from its nearest labelled one, and the dense error over all pixels of the true flow
+        dense = eng.densify_motions(K, rec['coeffs'].reshape(K, -1), mode=a.mode, fallback='dominant', min_site_mass=a.min_site_mass,
+                                    max_distance=a.max_distance, want=('theta', 'labels', 'dist2', 'n_sites'))
+        reached = dense['labels'][0] != 255
+        print(f'filled from the nearest of {int(dense["n_sites"][0])} sites: {int(reached.sum())} of {H * W} pixels reached, '
+              f'farthest {float(np.sqrt(dense["dist2"][0][reached].max())) if reached.any() else 0.0:.1f} px; '
+              f'pixel label accuracy {float((((dense["labels"][0] ^ swap) == (~left).astype(np.uint8)) & reached).sum() / max(int(reached.sum()), 1)):.3f}')
+        for name, th in (('dominant', theta), ('nearest', dense['theta'])):
+            print(f'dense AEE over all {H * W} pixels, fill {name}: {float(np.linalg.norm(th[0] - flow_gt, axis=-1).mean()):.3f} px')
+        theta = dense['theta']
 
     eng.flow_eval_stage(flow_gt[None], [(win['xs'], win['ys'])])
     res = eng.flow_errors(theta)[0]

@@ -37,7 +37,8 @@ extern "C" {
                                *    the models of a group: the E-step of a motion segmentation), eincm_contrast_landscape (the integer contrast of
                                *    the warped events on a grid of candidate motion coefficients), eincm_set_weights, eincm_get_stage_order,
                                *    eincm_get_staged_weights (a batch staged with EINCM_SW_KEEP_ORDER takes new weights in place), eincm_compose_motions
-                               *    (a motion segmentation composed into one flow field and a label image) */
+                               *    (a motion segmentation composed into one flow field and a label image), eincm_densify_motions (that
+                               *    composition made dense: every pixel takes the label of its nearest labelled pixel) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -416,6 +417,31 @@ int eincm_contrast_landscape(eincm_ctx* ctx, int n_candidates, const double* coe
 #define EINCM_ML_NO_LABEL      255  /* labels: no event with a weight that quantises above 0 fired here */
 int eincm_compose_motions(eincm_ctx* ctx, int n_models, const double* coeffs, unsigned flags, double* theta, uint8_t* labels,
                           uint32_t* mass, uint64_t* total);
+
+/* The composition of eincm_compose_motions made dense: a pixel without events takes the label of the nearest
+ * pixel that has one, by an exact Euclidean feature transform with a fixed tie rule.  The staged batch, n_models, coeffs, q(w),
+ * mass[g, l, p], total[g, l], f_l(p), the label rule, the soft blend and the two flags are eincm_compose_motions'.  Per group g:
+ *     site        pixel s is a site iff S(s) = sum_l mass[g, l, s] (as uint64) >= min_site_mass; n_sites[g] counts the sites
+ *     nearest     the nearest site of p = (x, y) is the site (x', y') that minimises the key (d2, y', x') lexicographically,
+ *                 d2 = (x - x')^2 + (y - y')^2: equal distances go to the lowest row, then to the lowest column.  A site's nearest
+ *                 site is itself.  nearest[g, p] = y' * W + x', dist2[g, p] = d2; a group without a site has nearest = -1 and
+ *                 dist2 = EINCM_MD_NONE everywhere.  Both are reported whatever max_dist2 is
+ *     reached     p is reached iff it has a nearest site and d2 <= max_dist2 (EINCM_MD_UNBOUNDED: no bound)
+ *     labels      a reached pixel takes the label of mass[g, :, nearest]; any other pixel EINCM_ML_NO_LABEL
+ *     Theta       a reached pixel is composed from the mass vector of its nearest site and the models' fields AT p:
+ *                 EINCM_ML_HARD f_label(p), EINCM_ML_SOFT the blend of eincm_compose_motions with the site's masses and f_l(p).
+ *                 Any other pixel takes the fill of eincm_compose_motions: EINCM_ML_FILL_ZERO or EINCM_ML_FILL_DOMINANT
+ *   min_site_mass  >= 1; 4096 is one event of weight 1, so 2 * 4096 keeps a lone event from owning a cell
+ *   theta     NULL, or (G, H, W, 2) doubles     labels  NULL, or (G, H, W) bytes     dist2  NULL, or (G, H, W) uint32
+ *   nearest   NULL, or (G, H, W) int32          n_sites NULL, or (G) uint32
+ * With min_site_mass = 1 and max_dist2 = 0 theta and labels are the bytes of eincm_compose_motions with the same flags.  Integer up
+ * to one thread's fp64 blend, no global atomics: every run gives the same bytes.
+ * Refused before anything is written, in the order and with the codes of eincm_compose_motions (EINCM_ERR_ARG all five outputs
+ * NULL), then: EINCM_ERR_ARG min_site_mass = 0; EINCM_ERR_UNSUPPORTED a sensor wider than 16384 pixels. */
+#define EINCM_MD_NONE      0xFFFFFFFFu   /* dist2: the group has no site */
+#define EINCM_MD_UNBOUNDED 0xFFFFFFFFu   /* max_dist2: every pixel of a group with a site is reached */
+int eincm_densify_motions(eincm_ctx* ctx, int n_models, const double* coeffs, unsigned flags, uint32_t min_site_mass, uint32_t max_dist2,
+                          double* theta, uint8_t* labels, uint32_t* dist2, int32_t* nearest, uint32_t* n_sites);
 
 /* compute_weights_for_multi_reference (losses.py:39-46) */
 int eincm_multi_ref_weights(int n_refs, double* w);
