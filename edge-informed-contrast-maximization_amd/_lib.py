@@ -40,6 +40,8 @@ TA_FILL_SOURCE, TA_FILL_ZERO = 0, 1                                  # EINCM_TA_
 TA_FILLS = {'source': TA_FILL_SOURCE, 'zero': TA_FILL_ZERO}
 RS_MAX_MODELS, RS_EXCLUDE_SELF = 8, 1                                # EINCM_RS_MAX_MODELS, EINCM_RS_EXCLUDE_SELF
 RS_STAGED_WEIGHTS, RS_APPLY = 2, 4                                   # EINCM_RS_STAGED_WEIGHTS, EINCM_RS_APPLY (a keep-order batch)
+RS_PRIOR_STAGED = 8                                                  # EINCM_RS_PRIOR_STAGED (eincm_event_responsibilities_spatial)
+LP_MAX_RADIUS = 8                                                    # EINCM_LP_MAX_RADIUS (eincm_label_prior)
 CL_MAX_CANDIDATES = 4096                                             # EINCM_CL_MAX_CANDIDATES
 CL_CELLS = (1, 2, 4, 8)                                              # the cell sizes of eincm_contrast_landscape
 ML_HARD, ML_SOFT, ML_FILL_ZERO, ML_FILL_DOMINANT = 0, 1, 0, 2        # EINCM_ML_* flags of eincm_compose_motions
@@ -207,6 +209,11 @@ SIGNATURES = [
     # that composition made dense: every pixel takes the label of its nearest labelled pixel (raw addresses, as above)
     ('eincm_densify_motions', C.c_int, [_P, C.c_int, C.c_void_p, C.c_uint, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    # the per-pixel label prior, and the E-step that reads a prior image stack (raw addresses, as above)
+    ('eincm_label_prior', C.c_int, [_P, C.c_int, C.c_int, C.c_uint32, C.c_uint, C.c_void_p, C.c_void_p]),
+    ('eincm_get_staged_prior', C.c_int, [_P, C.c_void_p]),
+    ('eincm_event_responsibilities_spatial', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # a solved theta carried along its own flow to the next window (raw addresses, as above)
     ('eincm_theta_advect', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

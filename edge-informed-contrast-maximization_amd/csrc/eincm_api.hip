@@ -46,6 +46,8 @@
 #include "eincm_motion_layers.hip.h"
 #include "eincm_motion_fill.h"
 #include "eincm_motion_fill.hip.h"
+#include "eincm_label_prior.h"
+#include "eincm_label_prior.hip.h"
 #include "eincm_theta_advect.h"
 #include "eincm_theta_advect.hip.h"
 #include "eincm_contrast_landscape.h"
@@ -259,6 +261,11 @@ struct eincm_ctx : PlanCtx {
         int fe_n = 0;                  // windows of the staged flow evaluation (0: none)
         std::vector<int64_t> fe_ngt;   // (fe_n) GT-valid pixels of every window
     } fe;
+
+    struct {                           // eincm_label_prior: the staged prior, read in place by the spatial E-step
+        Grow<float> prior;             // (B, H, W), allocated by the first call
+        bool staged = false;           // it belongs to the staged batch: dropped by the next staging, kept across a re-weighting
+    } lp;
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
@@ -1916,6 +1923,7 @@ static int stage_windows(eincm_ctx* c, const StageArgs& a) {
     int rc = check_staging(c, a);
     if (rc) return rc;
     c->staged = false;               // (every reader of what drop_batch_state drops asks for a staged batch first)
+    c->lp.staged = false;            // the staged prior belonged to the batch that goes (a re-weighting keeps it: it is not a staging)
     c->stage = plan_staging(*c, a.B, a.R, a.n_events, a.flags, live_knobs().stage, a.weights);    // (an unweighted staging drops the weighted state with the plan)
     const StagePlan& P = c->stage;
     HIPCHK(c, hipSetDevice(c->device));
@@ -2649,6 +2657,148 @@ int eincm_densify_motions(eincm_ctx* c, int n_models, const double* coeffs, unsi
     if (dist2) HIPCHK(c, op.down(dist2, d_d2, (size_t)G * npix * sizeof(uint32_t)));
     if (nearest) HIPCHK(c, op.down(nearest, d_near, (size_t)G * npix * sizeof(int32_t)));
     if (n_sites) HIPCHK(c, op.down(n_sites, d_nsites, (size_t)G * sizeof(uint32_t)));
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+// The per-pixel label prior (eincm_label_prior.hip.h): the mass images by k_ml_mass, as eincm_compose_motions
+// forms them, then every (tile, group)'s box sums and shares by one workgroup.  The checks, their order and the layout are
+// eincm_label_prior.h's.  The prior stack is written where it stays, c->lp.prior (grown before the frame begins: a growth drains the
+// stream and nothing of this call is on it yet), and marked staged once the call has ended on its synchronisation.
+int eincm_label_prior(eincm_ctx* c, int n_models, int radius, uint32_t floor_mass, unsigned flags, float* prior, uint64_t* smoothed) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    const LpState st{!c->fl.idle(), c->staged, c->fp64, c->sharded_staging || c->constants_pending, c->staged ? g.B : 0, c->win_events.data(),
+                     c->h_tilecount.data(), c->staged ? (int64_t)c->h_tilecount.size() : 0};
+    int bad_b = 0; int64_t bad_i = 0;
+    if (const LpFault f = lp_check(st, n_models, radius, flags, &bad_b, &bad_i)) {
+        if (f == LP_CROWDED)
+            return fail(c, lp_code(f), "eincm_label_prior: %s: window %d, tile %lld holds %d", lp_why(f), bad_b, (long long)bad_i,
+                        (int)c->h_tilecount[(size_t)bad_b * g.ntiles + (size_t)bad_i]);
+        return fail(c, lp_code(f), "eincm_label_prior: %s", lp_why(f));
+    }
+    const int B = g.B, K = n_models, G = B / K;
+    const size_t npix = (size_t)g.H * g.W, bins = (size_t)B * g.ntiles, GK = (size_t)G * K;
+    OneShot op(c);
+    const auto d_off = op.piece<int32_t>(bins + 1);
+    const auto d_mass = op.piece<uint32_t>(GK * npix);
+    const auto d_part = op.piece<unsigned long long>(GK * g.ntiles);
+    const auto d_smooth = op.piece<unsigned long long>(GK * npix, smoothed != nullptr);
+    int32_t* h_off = op.host_buf<int32_t>(bins + 1);                     // d_off goes up from here
+    int64_t run = 0;                                                     // (as eincm_compose_motions: the bins lie in (window, tile) order)
+    for (size_t i = 0; i < bins; ++i) { h_off[i] = (int32_t)run; run += c->h_tilecount[i]; }
+    h_off[bins] = (int32_t)run;
+    if (run != c->stage.N) return fail(c, EINCM_ERR_STATE, "eincm_label_prior: internal: the tile populations do not add up to the staged events");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, ensure(c, c->lp.prior, (size_t)B * npix));
+    c->lp.staged = false;                                                // (until this call's prior is whole)
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.up(d_off, h_off, (bins + 1) * sizeof(int32_t)));
+    const MlGeom mg{g.H, g.W, g.tilesX, g.ntiles, K, 0u, 0.0, 0.0, 1.0};                   // (k_ml_mass reads no flag and no model)
+    const float* w = c->stage.weighted ? (const float*)c->d_w_g : nullptr;          // (an unweighted batch has no ev_w: q = 4096)
+    HIPCHK(c, op.launch(k_ml_mass, dim3((unsigned)g.ntiles, (unsigned)G), dim3(ML_NT), (size_t)K * ML_TILE_PIX * sizeof(uint32_t), mg, d_off,
+                        c->d_xy_g, w, d_mass, d_part));
+    const LpGeom lg{g.H, g.W, g.tilesX, radius, floor_mass};
+    HIPCHK(c, op.launch(lp_kernel(K), dim3((unsigned)g.ntiles, (unsigned)G), dim3(LP_NT), 0, lg, d_mass, c->lp.prior.p, d_smooth));
+    if (prior) HIPCHK(c, op.down(prior, c->lp.prior.p, (size_t)B * npix * sizeof(float)));       // (host memory: the caller's, both)
+    if (smoothed) HIPCHK(c, op.down(smoothed, d_smooth, GK * npix * sizeof(uint64_t)));
+    HIPCHK(c, op.sync());
+    c->lp.staged = true;
+    return EINCM_OK;
+}
+
+int eincm_get_staged_prior(eincm_ctx* c, float* prior) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!prior) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (const int rc = not_in_flight(c, "eincm_get_staged_prior")) return rc;
+    if (!c->staged || !c->lp.staged)
+        return fail(c, EINCM_ERR_STATE, "eincm_get_staged_prior: no staged prior (eincm_label_prior since the last eincm_set_windows)");
+    OneShot op(c);                                  // no piece of the scratch: the frame is here for its drain
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.down(prior, c->lp.prior.p, (size_t)c->g.B * c->g.H * c->g.W * sizeof(float)));          // (host memory: the caller's)
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+// The E-step with a prior image.  eincm_event_responsibilities' body is pinned by its tests, so this one follows
+// it line by line instead of sharing it: the same checks first (rs_check, then the keep-order flags), then rs_spatial_check; the same
+// frame with one piece more, the prior stack, uploaded or (EINCM_RS_PRIOR_STAGED) read where eincm_label_prior left it; the SP = 1
+// instantiation of the same kernel; k_rs_mass, the downloads and EINCM_RS_APPLY as there.
+int eincm_event_responsibilities_spatial(eincm_ctx* c, int n_models, const float* images, const double* ref_weights,
+                                         const float* const* weights_in, const double* prior, const float* prior_images, uint32_t flags,
+                                         float* weights_out, uint8_t* labels, double* mass, int64_t* n_unsupported) {
+    if (!c) return EINCM_ERR_ARG;
+    static const char who[] = "eincm_event_responsibilities_spatial";
+    const Geom& g = c->g;
+    const bool apply = (flags & EINCM_RS_APPLY) != 0, own_w = (flags & EINCM_RS_STAGED_WEIGHTS) != 0;
+    const RsState st{{!c->fl.idle(), weights_out || labels || mass || n_unsupported || apply, c->staged, c->have_eval, c->fp64, c->splat_size,
+                      c->sharded_staging || c->constants_pending, images != nullptr, RawEvents::masked(c)},
+                     c->staged ? g.B : 0, c->win_events.data()};
+    if (const RsFault f = rs_check(st, n_models, ref_weights, g.R, prior)) return fail(c, rs_code(f), "%s: %s", who, rs_why(f));
+    if (apply || own_w) {
+        if (const int rc = keep_order_ready(c, apply ? "eincm_event_responsibilities_spatial (EINCM_RS_APPLY)" : "eincm_event_responsibilities_spatial (EINCM_RS_STAGED_WEIGHTS)")) return rc;
+        if (own_w && weights_in) return fail(c, EINCM_ERR_ARG, "%s: weights_in must be NULL with EINCM_RS_STAGED_WEIGHTS", who);
+    }
+    const size_t npix = (size_t)g.H * g.W;
+    int bad_b = 0; int64_t bad_p = 0;
+    if (const RsSpatialFault f = rs_spatial_check(prior_images, flags, c->lp.staged, g.B, (int64_t)npix, &bad_b, &bad_p)) {
+        if (f == RSS_VALUE)
+            return fail(c, rs_spatial_code(f), "%s: %s: window %d, pixel (x %d, y %d) holds %g", who, rs_spatial_why(f), bad_b, (int)(bad_p % g.W),
+                        (int)(bad_p / g.W), (double)prior_images[(size_t)bad_b * npix + (size_t)bad_p]);
+        return fail(c, rs_spatial_code(f), "%s: %s", who, rs_spatial_why(f));
+    }
+    { const int rc = ensure_theta_image(c); if (rc) return rc; }
+    const int B = g.B, R = g.R, K = n_models, G = B / K;
+    OneShot op(c);
+    RawEvents ev(op, [](const int64_t* n, int b) { return rs_weights_offset(n, b); });
+    const int64_t n_events = rs_weights_total(ev.ne, B), n_labels = rs_labels_total(ev.ne, B, K);
+    if (n_events == 0) return EINCM_OK;
+    const size_t n_blk = (size_t)((ev.n_max + NT - 1) / NT), stack = (size_t)B * R * npix;
+    const bool any_w = (flags & EINCM_RS_EXCLUDE_SELF) && ev.any(weights_in);
+    const bool self_own = own_w && (flags & EINCM_RS_EXCLUDE_SELF);
+    const auto d_img = op.piece<float>(stack, images != nullptr);
+    const auto d_pimg = op.piece<float>((size_t)B * npix, prior_images != nullptr);
+    const auto d_rw = op.piece<float>((size_t)R);
+    const auto d_pi = op.piece<float>((size_t)B);
+    const auto d_win = op.piece<float>((size_t)n_events, any_w);
+    const auto d_has = op.piece<uint8_t>((size_t)B, any_w || self_own);
+    const auto d_wout = op.piece<float>((size_t)n_events, weights_out != nullptr || apply);
+    const auto d_lab = op.piece<uint8_t>((size_t)n_labels, labels != nullptr);
+    const auto d_part = op.piece<double>((size_t)B * n_blk, mass != nullptr);
+    const auto d_mass = op.piece<double>((size_t)B, mass != nullptr);
+    const auto d_uns = op.piece<unsigned long long>((size_t)G, n_unsupported != nullptr);
+    float* h_rw = op.host_buf<float>((size_t)R);                         // d_rw, d_pi and (self_own) d_has go up from these
+    float* h_pi = op.host_buf<float>((size_t)B);
+    uint8_t* h_all = op.host_buf<uint8_t>((size_t)B);
+    for (int r = 0; r < R; ++r) h_rw[r] = (float)ref_weights[r];
+    for (int b = 0; b < B; ++b) h_pi[b] = prior ? (float)prior[b] : 1.0f;
+    for (int b = 0; b < B; ++b) h_all[b] = 1;
+    HIPCHK(c, op.begin());
+    HIPCHK(c, ev.upload());
+    if (images) HIPCHK(c, op.up(d_img, images, stack * sizeof(float)));  // (host memory: the caller's, as prior_images, weights_in and the outputs)
+    if (prior_images) HIPCHK(c, op.up(d_pimg, prior_images, (size_t)B * npix * sizeof(float)));
+    HIPCHK(c, op.up(d_rw, h_rw, (size_t)R * sizeof(float)));
+    HIPCHK(c, op.up(d_pi, h_pi, (size_t)B * sizeof(float)));
+    if (any_w) HIPCHK(c, ev.upload_per_window(weights_in, (float*)d_win, d_has));
+    if (self_own) HIPCHK(c, op.up(d_has, h_all, (size_t)B));
+    const float* w_self = self_own ? (const float*)c->ord.stream : (const float*)d_win;
+    if (n_unsupported) HIPCHK(c, op.zero(d_uns, (size_t)G * sizeof(unsigned long long)));
+    const float* F = images ? (const float*)d_img : (const float*)c->d_iwe;
+    const float* P = prior_images ? (const float*)d_pimg : (const float*)c->lp.prior.p;
+    const dim3 grid((unsigned)n_blk, (unsigned)G);
+    HIPCHK(c, op.launch(rs_spatial_kernel(K), grid, dim3(NT), 0, g, ev.d_off, c->d_raw_x, c->d_raw_y, c->d_raw_t, c->d_Theta, c->d_edge_ts, F,
+                        d_rw, w_self, d_has, d_pi, flags, d_wout, d_lab, d_part, d_uns, P));
+    if (mass) {
+        HIPCHK(c, op.launch(k_rs_mass, dim3((unsigned)((B + NT - 1) / NT)), dim3(NT), 0, B, ev.d_off, d_part, (int64_t)n_blk, d_mass));
+        HIPCHK(c, op.down(mass, d_mass, (size_t)B * sizeof(double)));
+    }
+    if (weights_out) HIPCHK(c, op.down(weights_out, d_wout, (size_t)n_events * sizeof(float)));
+    if (labels) HIPCHK(c, op.down(labels, d_lab, (size_t)n_labels));
+    if (n_unsupported) HIPCHK(c, op.down(n_unsupported, d_uns, (size_t)G * sizeof(int64_t)));
+    if (apply) {
+        HIPCHK(c, hipMemcpyAsync(c->ord.stream, (const float*)d_wout, (size_t)n_events * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+        return reweight_staged(c, op);
+    }
     HIPCHK(c, op.sync());
     return EINCM_OK;
 }

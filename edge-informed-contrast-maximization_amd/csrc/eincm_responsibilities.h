@@ -83,6 +83,39 @@ inline const char* rs_why(RsFault f) {
     }
 }
 
+// ---- the E-step with a prior image (eincm_event_responsibilities_spatial) ----
+// What it refuses beyond rs_check, after it and in the order of the enum: the prior stack comes from exactly one source, the caller's
+// prior_images or (EINCM_RS_PRIOR_STAGED) the context's staged prior, and every value of the caller's is finite and >= 0.
+enum RsSpatialFault { RSS_OK = 0, RSS_BOTH, RSS_NEITHER, RSS_NOT_STAGED, RSS_VALUE };
+
+// prior_images: NULL or n_windows * npix floats.  An RSS_VALUE leaves the window in *where_b and the pixel (y * W + x) in *where_p.
+inline RsSpatialFault rs_spatial_check(const float* prior_images, uint32_t flags, bool prior_staged, int n_windows, int64_t npix,
+                                       int* where_b, int64_t* where_p) {
+    *where_b = -1; *where_p = -1;
+    const bool staged_asked = (flags & EINCM_RS_PRIOR_STAGED) != 0;
+    if (prior_images && staged_asked) return RSS_BOTH;
+    if (!prior_images && !staged_asked) return RSS_NEITHER;
+    if (staged_asked) return prior_staged ? RSS_OK : RSS_NOT_STAGED;
+    for (int b = 0; b < n_windows; ++b)
+        for (int64_t p = 0; p < npix; ++p) {
+            const float v = prior_images[(int64_t)b * npix + p];
+            if (!std::isfinite(v) || v < 0.0f) { *where_b = b; *where_p = p; return RSS_VALUE; }
+        }
+    return RSS_OK;
+}
+
+inline int rs_spatial_code(RsSpatialFault f) { return f == RSS_OK ? EINCM_OK : f == RSS_NOT_STAGED ? EINCM_ERR_STATE : EINCM_ERR_ARG; }
+
+inline const char* rs_spatial_why(RsSpatialFault f) {
+    switch (f) {
+        case RSS_BOTH: return "prior_images must be NULL with EINCM_RS_PRIOR_STAGED: the prior stack has one source";
+        case RSS_NEITHER: return "no prior stack: hand prior_images over, or set EINCM_RS_PRIOR_STAGED for the staged prior";
+        case RSS_NOT_STAGED: return "EINCM_RS_PRIOR_STAGED without a staged prior (eincm_label_prior since the last eincm_set_windows)";
+        case RSS_VALUE: return "prior_images must be finite and >= 0";
+        default: return "";
+    }
+}
+
 // The layout.  weights_out: the combined form of sc_block_offset, window b's block is n_events[b] floats.  labels: one byte per event of
 // a group, group after group; a group's event count is that of its first window.
 inline int64_t rs_weights_offset(const int64_t* n_events, int b) { return sc_block_offset(n_events, b, 1, true); }

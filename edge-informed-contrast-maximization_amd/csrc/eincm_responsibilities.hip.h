@@ -18,6 +18,9 @@
 
 namespace eincm {
 
+// (the one argument of k_responsibilities' pack)
+__device__ inline const float* rs_prior_stack(const float* prior_img) { return prior_img; }
+
 // One thread per event of a group, a loop over the models and over the reference times in the thread; p_l stays in registers (the
 // model loop is unrolled over the template's K, so p[] is never indexed at run time: no scratch).  grid (ceil(max_g n_g / NT), G):
 // blockIdx.y is the group; a block beyond its group's events leaves at once, as one.
@@ -25,7 +28,12 @@ namespace eincm {
 //   the group's labels at evoff[g*K] / K.  rw (R) floats.  w_in: the batch's weights in the layout of wout, or nullptr for ones;
 //   w_has (B): 0 where a window's weights are ones.  pi (B) floats.  wout, labels, part (B, gridDim.x), uns (G, zeroed): any may be
 //   nullptr.
-template <int K>
+// SP = 1 is the E-step with a prior image: one more argument, prior_img (B, H, W) floats, and
+//     c_l = pi_l * prior_img[g*K + l, y_e, x_e],   p_l = c_l * a_l
+//     unsupported: p_l = c_l and T is summed again; if that T is not > 0 or not finite either, p_l = pi_l and T is summed once more
+// with the event's raw pixel, the xs / ys read for the warp.  The event counts as unsupported once.  SP = 0 takes no such argument
+// (the pack is empty) and compiles to the instructions it had before SP existed (profiles/label_prior.md).
+template <int K, int SP = 0, typename... PriorImg>
 __global__ __launch_bounds__(NT) void k_responsibilities(Geom g, const int64_t* __restrict__ evoff, const int16_t* __restrict__ xs,
                                                           const int16_t* __restrict__ ys, const double* __restrict__ ts,
                                                           const double* __restrict__ Theta, const double* __restrict__ edge_ts,
@@ -33,9 +41,10 @@ __global__ __launch_bounds__(NT) void k_responsibilities(Geom g, const int64_t* 
                                                           const float* __restrict__ w_in, const uint8_t* __restrict__ w_has,
                                                           const float* __restrict__ pi, uint32_t flags, float* __restrict__ wout,
                                                           uint8_t* __restrict__ labels, double* __restrict__ part,
-                                                          unsigned long long* __restrict__ uns)
+                                                          unsigned long long* __restrict__ uns, PriorImg... prior_img)
 {
 #pragma clang fp contract(off)
+    static_assert(sizeof...(PriorImg) == (SP ? 1 : 0), "SP = 1 takes the prior stack, SP = 0 nothing");
     __shared__ double sm[K][NT / 64];
     const int grp = blockIdx.y, w0 = grp * K;
     const int64_t e0 = evoff[w0], n = evoff[w0 + 1] - e0;
@@ -44,6 +53,7 @@ __global__ __launch_bounds__(NT) void k_responsibilities(Geom g, const int64_t* 
     const bool live = i < n;
     const size_t npix = (size_t)g.H * g.W;
     float p[K];
+    [[maybe_unused]] float c[SP ? K : 1];            // SP: c_l, the first fallback's shares
     bool unsupported = false;
     if (live) {
 #pragma unroll
@@ -67,7 +77,12 @@ __global__ __launch_bounds__(NT) void k_responsibilities(Geom g, const int64_t* 
                 a = S - w * Q;
             }
             a = a > 0.0f ? a : 0.0f;
-            p[l] = pi[win] * a;
+            if constexpr (SP) {
+                c[l] = pi[win] * rs_prior_stack(prior_img...)[(size_t)win * npix + (size_t)y * g.W + x];
+                p[l] = c[l] * a;
+            } else {
+                p[l] = pi[win] * a;
+            }
         }
         float T = 0.0f;
 #pragma unroll
@@ -75,8 +90,18 @@ __global__ __launch_bounds__(NT) void k_responsibilities(Geom g, const int64_t* 
         if (!(T > 0.0f) || !(fabsf(T) <= 3.402823466e38f)) {
             unsupported = true;
             T = 0.0f;
+            if constexpr (SP) {
 #pragma unroll
-            for (int l = 0; l < K; ++l) { p[l] = pi[w0 + l]; T = T + p[l]; }
+                for (int l = 0; l < K; ++l) { p[l] = c[l]; T = T + p[l]; }
+                if (!(T > 0.0f) || !(fabsf(T) <= 3.402823466e38f)) {
+                    T = 0.0f;
+#pragma unroll
+                    for (int l = 0; l < K; ++l) { p[l] = pi[w0 + l]; T = T + p[l]; }
+                }
+            } else {
+#pragma unroll
+                for (int l = 0; l < K; ++l) { p[l] = pi[w0 + l]; T = T + p[l]; }
+            }
         }
         int lab = 0; float best = p[0];
 #pragma unroll
@@ -118,6 +143,10 @@ __global__ __launch_bounds__(NT) void k_responsibilities(Geom g, const int64_t* 
 template <int K = 1> static auto rs_kernel(int n_models) -> decltype(&k_responsibilities<1>) {
     if constexpr (K < EINCM_RS_MAX_MODELS) { if (n_models != K) return rs_kernel<K + 1>(n_models); }
     return k_responsibilities<K>;
+}
+template <int K = 1> static auto rs_spatial_kernel(int n_models) -> decltype(&k_responsibilities<1, 1, const float*>) {
+    if constexpr (K < EINCM_RS_MAX_MODELS) { if (n_models != K) return rs_spatial_kernel<K + 1>(n_models); }
+    return k_responsibilities<K, 1, const float*>;
 }
 
 // mass[b] = a window's block partials added in ascending block order from +0.  One thread per window; n_part is the row length of

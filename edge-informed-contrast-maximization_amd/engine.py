@@ -801,6 +801,58 @@ def check_densify_args(n_models, coeffs, n_windows, n_coeffs, mode, fallback, mi
     return K, c, flags, int(min_site_mass), max_dist2, want
 
 
+LP_OUTPUTS = ('prior', 'smoothed')
+
+
+def label_prior_layout(n_groups, n_models, sensor_size):
+    """The shapes of eincm_label_prior's two outputs and where a group's block starts in each, in elements of the output's own type
+    (csrc/eincm_label_prior.h: lp_prior_offset, lp_smoothed_offset, restated; tests/test_host_label_prior.py compares the two): a dict
+    name -> (shape, dtype, offsets (G,) int64).  'prior' is per window, window g * n_models + l model l of group g."""
+    G, K, H, W = int(n_groups), int(n_models), int(sensor_size[0]), int(sensor_size[1])
+    g = np.arange(G, dtype=np.int64)
+    return {'prior': ((G * K, H, W), np.float32, g * (K * H * W)), 'smoothed': ((G, K, H, W), np.uint64, g * (K * H * W))}
+
+
+def check_label_prior_args(n_models, radius, floor_mass, want):
+    """The arguments of Engine.label_prior, checked without a GPU: n_models an integer within 1 .. RS_MAX_MODELS, radius an integer
+    within 0 .. LP_MAX_RADIUS, floor_mass an integer within 0 .. 2^32 - 1, want a choice of LP_OUTPUTS without repeats that may be
+    empty (the prior is staged all the same).  What depends on the staged batch is left to the library, so that those refusals carry
+    the codes and the sentences of csrc/eincm_label_prior.h.  Returns (n_models, radius, floor_mass, want)."""
+    if isinstance(n_models, bool) or not isinstance(n_models, (int, np.integer)) or not 1 <= int(n_models) <= L.RS_MAX_MODELS:
+        raise ValueError(f'n_models must be an integer within 1 .. {L.RS_MAX_MODELS}, got {n_models!r}')
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= int(radius) <= L.LP_MAX_RADIUS:
+        raise ValueError(f'radius must be an integer within 0 .. {L.LP_MAX_RADIUS}, got {radius!r}')
+    if isinstance(floor_mass, bool) or not isinstance(floor_mass, (int, np.integer)) or not 0 <= int(floor_mass) <= 0xFFFFFFFF:
+        raise ValueError(f'floor_mass must be an integer within 0 .. 2^32 - 1 (4096 is one event of weight 1), got {floor_mass!r}')
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in LP_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a choice of {LP_OUTPUTS} without repeats, got {want!r}')
+    return int(n_models), int(radius), int(floor_mass), want
+
+
+def check_prior_images(prior_images, n_windows, sensor_size):
+    """The caller's prior stack of Engine.event_responsibilities_spatial as contiguous float32 (B, H, W), every value finite and >= 0 as
+    the float the kernel takes; (H, W) stands for it when B == 1.  None stays None (the staged prior).  Anything else is a ValueError,
+    raised before any library call."""
+    if prior_images is None:
+        return None
+    a = np.asarray(prior_images)
+    if a.dtype.kind not in 'fiub':
+        raise ValueError(f'prior_images must be numbers, got dtype {a.dtype}')
+    shape = (int(n_windows), int(sensor_size[0]), int(sensor_size[1]))
+    if a.ndim == 2 and shape[0] == 1:
+        a = a[None]
+    if a.shape != shape:
+        raise ValueError(f'prior_images must be {shape}' + (f' or {shape[1:]}' if shape[0] == 1 else '') + f', got {np.shape(prior_images)}')
+    with np.errstate(over='ignore'):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+    bad = ~np.isfinite(a) | (a < 0)
+    if bad.any():
+        b, y, x = (int(v) for v in np.argwhere(bad)[0])
+        raise ValueError(f'prior_images must be finite and >= 0: window {b}, pixel (x {x}, y {y}) holds {float(a[b, y, x])!r}')
+    return a
+
+
 def check_score_images(images, n_windows, n_refs, sensor_size):
     """The caller's image stack of Engine.event_scores as contiguous float32 (B,R,H,W); (R,H,W) stands for it when B == 1.  None stays
     None (the IWEs of the last evaluation).  Anything else is a ValueError, raised before any library call."""
@@ -1832,7 +1884,7 @@ class Engine:
         self._need_keep_order('apply_responsibilities')
         return self._responsibilities(n_models, images, ref_weights, prior, exclude_self, want, True)
 
-    def _responsibilities(self, n_models, images, ref_weights, prior, exclude_self, want, apply):
+    def _responsibilities(self, n_models, images, ref_weights, prior, exclude_self, want, apply, spatial=False, prior_images=None):
         if apply and isinstance(want, (tuple, list)) and len(want) == 0:
             K, pi, _ = check_responsibility_args(n_models, self.n_events if self.B else [], prior, RS_OUTPUTS)
             want = ()
@@ -1851,8 +1903,15 @@ class Engine:
         mass = np.zeros(B, dtype=np.float64) if 'mass' in want else None                # (a batch without events writes nothing)
         n_uns = np.zeros(G, dtype=np.int64) if 'n_unsupported' in want else None
         addr = lambda a: None if a is None else a.ctypes.data
-        self._check(self._lib.eincm_event_responsibilities(self._ctx, K, addr(imgs), addr(rw), per_window_ptrs(ws), addr(pi), flags,
-                                                           addr(weights), addr(labels), addr(mass), addr(n_uns)))
+        if spatial:
+            pimg = check_prior_images(prior_images, B, (self.H, self.W))
+            if pimg is None:
+                flags |= L.RS_PRIOR_STAGED
+            self._check(self._lib.eincm_event_responsibilities_spatial(self._ctx, K, addr(imgs), addr(rw), per_window_ptrs(ws), addr(pi),
+                                                                       addr(pimg), flags, addr(weights), addr(labels), addr(mass), addr(n_uns)))
+        else:
+            self._check(self._lib.eincm_event_responsibilities(self._ctx, K, addr(imgs), addr(rw), per_window_ptrs(ws), addr(pi), flags,
+                                                               addr(weights), addr(labels), addr(mass), addr(n_uns)))
         if apply:
             self._staged_weights = None     # (they are the device's now: staged_weights())
         out = {}
@@ -1865,6 +1924,45 @@ class Engine:
         if n_uns is not None:
             out['n_unsupported'] = n_uns
         return out
+
+    def label_prior(self, n_models, radius, floor_mass=4096, want=('prior',)):
+        """The per-pixel label prior of the E-step, one device operation.  The staged batch is G = B / n_models
+        groups of n_models consecutive windows, as compose_motions reads it, and 'mass' is that operator's: the staged weights quantised
+        to 1/4096 and summed per pixel and model.  Per pixel every model's mass is summed over the (2 radius + 1)^2 box around it,
+        clipped to the sensor; floor_mass (4096 is one event of weight 1) is added to every model's sum, which keeps a model alive where
+        it has no mass yet; the prior is the model's share of the K sums, 1 where they are all 0.  Returns a dict of ``want``: 'prior'
+        (B, H, W) float32, what event_responsibilities_spatial takes; 'smoothed' (G, n_models, H, W) uint64, the box sums.  want=() only
+        stages: whatever is downloaded, the prior stays on the device as the staged prior, which event_responsibilities_spatial reads in
+        place; set_windows drops it, set_weights and apply_responsibilities keep it.  Needs staged windows, no model and no evaluation.
+        Exact: equal to tests/_label_prior_witness.py byte for byte, and the same bytes on every run."""
+        K, r, floor, want = check_label_prior_args(n_models, radius, floor_mass, want)
+        lay = label_prior_layout(self.B // K, K, (self.H, self.W))
+        out = {name: np.zeros(lay[name][0], dtype=lay[name][1]) for name in want}
+        addr = lambda name: out[name].ctypes.data if name in out else None
+        self._check(self._lib.eincm_label_prior(self._ctx, K, r, floor, 0, addr('prior'), addr('smoothed')))
+        return out
+
+    def staged_prior(self):
+        """The staged prior, downloaded: (B, H, W) float32, what the last label_prior left.  For tests and tools."""
+        p = np.zeros((self.B, self.H, self.W), dtype=np.float32)
+        self._check(self._lib.eincm_get_staged_prior(self._ctx, p.ctypes.data))
+        return p
+
+    def event_responsibilities_spatial(self, n_models, prior_images=None, images=None, ref_weights=None, prior=None, exclude_self=True,
+                                       want=('weights', 'labels', 'mass')):
+        """event_responsibilities with a prior image: model l's mixing weight for an event is prior[b] times
+        prior_images[b] at the event's own pixel, so that an event is told what its neighbourhood belongs to.  prior_images: (B, H, W)
+        numbers, finite and >= 0, or (H, W) when B == 1; None reads the staged prior of label_prior on the device.  An event that no
+        model supports takes the shares of prior * prior_images, and those of prior alone where that product has no positive sum; it
+        is counted unsupported once.  Everything else is event_responsibilities'; with prior_images of ones, so are the bytes."""
+        return self._responsibilities(n_models, images, ref_weights, prior, exclude_self, want, False, True, prior_images)
+
+    def apply_responsibilities_spatial(self, n_models, prior_images=None, images=None, ref_weights=None, prior=None, exclude_self=True,
+                                       want=('labels', 'mass')):
+        """event_responsibilities_spatial whose result becomes the staged weights of all B windows, in place, as apply_responsibilities
+        does it.  The batch must have been staged with keep_order=True.  The staged prior stays as it is."""
+        self._need_keep_order('apply_responsibilities_spatial')
+        return self._responsibilities(n_models, images, ref_weights, prior, exclude_self, want, True, True, prior_images)
 
     def contrast_landscape(self, coeffs, t_ref=None, cell=1, keep=None, want=('sumsq', 'n_in')):
         """The contrast landscape over motion coefficients, one device operation: every staged window's raw

@@ -12,12 +12,16 @@ grid search on the contrast landscape (Engine.contrast_landscape), one motion af
 found before it do not explain.
 
 What the EM ends in - K coefficient vectors and one weight per event and model - becomes one flow field and a label image through
-segmented_flow (Engine.compose_motions): the form that flow_errors, advect_theta and a submission take."""
+segmented_flow (Engine.compose_motions): the form that flow_errors, advect_theta and a submission take.
+
+segment_motions_spatial runs the same loop with a spatially coherent E-step: the staged weights become a
+per-pixel label prior on the device (Engine.label_prior) and every event's mixing weights are read at its own pixel."""
 import numpy as np
 
 from . import _lib as L
 from . import batch_solver as bsol
 from . import motion
+from .engine import check_label_prior_args
 
 PRIORS = ('mass', 'uniform')
 
@@ -90,8 +94,25 @@ def segment_motions_in_place(engine, windows, model, coeffs0, params, n_iters=5,
     return _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, True, record_weights)
 
 
-def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, in_place, record_weights):
+def segment_motions_spatial(engine, windows, model, coeffs0, params, radius=2, floor_mass=4096, n_iters=5, maxiter=25, gtol=1e-6,
+                            weights0=None, prior='mass', min_mass=1.0, callback=None, in_place=True, record_weights=True):
+    """segment_motions with a spatially coherent E-step: after every staging, and before every E-step of the
+    in-place route, Engine.label_prior(K, radius, floor_mass) turns the staged weights - the ones the E-step is about to replace - into
+    a per-pixel prior that stays on the device, and the E-step is Engine.event_responsibilities_spatial (in_place:
+    apply_responsibilities_spatial) on that staged prior: model l's mixing weight for an event is its ``prior`` share times its share
+    of the mass around the event's pixel.  radius: 0 .. 8, the half-width of the box; floor_mass: what every model's box sum is
+    raised by (4096 is one event of weight 1).  in_place and record_weights as segment_motions_in_place takes them; the two routes
+    return the same bytes.  Everything else, and the history returned, is segment_motions'."""
+    return _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, in_place, record_weights,
+                    spatial=(radius, floor_mass))
+
+
+def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, in_place, record_weights,
+             spatial=None):
+    """spatial: None, or (radius, floor_mass): the label prior is formed after every staging and the E-step reads it."""
     c, weights = check_segment_args(windows, model, coeffs0, n_iters, weights0, prior, min_mass, in_place, record_weights)
+    if spatial is not None:
+        check_label_prior_args(c.shape[1], spatial[0], spatial[1], ())
     G, K = c.shape[:2]
     want = ('weights', 'labels', 'mass', 'n_unsupported')
     engine.set_motion_model(model)
@@ -108,13 +129,17 @@ def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, we
                 engine.set_weights([wts[g][l] for g in range(G) for l in range(K)])
         elif wts is not None:           # (None: the E-step has applied its own result)
             engine.set_weights([wts[g][l] for g in range(G) for l in range(K)])
+        if spatial is not None:         # the prior of the next E-step, from the weights it will replace; it stays on the device
+            engine.label_prior(K, spatial[0], spatial[1], want=())
 
     def e_step(coeffs, pi):
         engine.loss_grad_motion(coeffs.reshape(G * K, -1), params, want_grad=False, allow_nonfinite=True)
         if not in_place:
-            r = engine.event_responsibilities(K, prior=pi, exclude_self=True, want=want)
+            respond = engine.event_responsibilities if spatial is None else engine.event_responsibilities_spatial     # (on the staged prior)
+            r = respond(K, prior=pi, exclude_self=True, want=want)
             return [[np.array(r['weights'][g * K + l]) for l in range(K)] for g in range(G)], r
-        r = engine.apply_responsibilities(K, prior=pi, exclude_self=True, want=want[1:])
+        respond = engine.apply_responsibilities if spatial is None else engine.apply_responsibilities_spatial
+        r = respond(K, prior=pi, exclude_self=True, want=want[1:])
         return None, r
 
     def mixing(mass):

@@ -38,7 +38,9 @@ extern "C" {
                                *    the warped events on a grid of candidate motion coefficients), eincm_set_weights, eincm_get_stage_order,
                                *    eincm_get_staged_weights (a batch staged with EINCM_SW_KEEP_ORDER takes new weights in place), eincm_compose_motions
                                *    (a motion segmentation composed into one flow field and a label image), eincm_densify_motions (that
-                               *    composition made dense: every pixel takes the label of its nearest labelled pixel) */
+                               *    composition made dense: every pixel takes the label of its nearest labelled pixel), eincm_label_prior,
+                               *    eincm_get_staged_prior, eincm_event_responsibilities_spatial (a per-pixel label prior from the staged
+                               *    weights, and the E-step that reads a prior image stack) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -442,6 +444,55 @@ int eincm_compose_motions(eincm_ctx* ctx, int n_models, const double* coeffs, un
 #define EINCM_MD_UNBOUNDED 0xFFFFFFFFu   /* max_dist2: every pixel of a group with a site is reached */
 int eincm_densify_motions(eincm_ctx* ctx, int n_models, const double* coeffs, unsigned flags, uint32_t min_site_mass, uint32_t max_dist2,
                           double* theta, uint8_t* labels, uint32_t* dist2, int32_t* nearest, uint32_t* n_sites);
+
+/* The per-pixel label prior of a segmentation's E-step: every model's share of the mass that the staged
+ * weights put into a neighbourhood of a pixel.  The staged batch, n_models, q(w) and mass[g, l, p] are eincm_compose_motions'.  With
+ * r = radius, for group g, model l and sensor pixel p = (x, y):
+ *     S[g, l, p] = sum of mass[g, l, p'] over the sensor pixels p' = (x', y') with |y' - y| <= r and |x' - x| <= r, as uint64 (a pixel
+ *                  outside the sensor counts 0)
+ *     n_l = S[g, l, p] + floor_mass,   T = n_0 + n_1 + ... + n_{K-1}, as uint64
+ *     P[g * K + l, p] = T == 0 ? 1.0f : (float)((double)n_l / (double)T)
+ * T < 2^53 (a pixel's mass is below 2^32, a window holds at most 17^2 pixels, K <= 8), so both conversions to double are exact: one
+ * correctly rounded fp64 division and one rounding to float.
+ *   n_models    K, 1 .. EINCM_RS_MAX_MODELS         radius  r, 0 .. EINCM_LP_MAX_RADIUS
+ *   floor_mass  added to every model's sum (4096 is one event of weight 1): it keeps a model alive where it has no mass yet
+ *   flags       0; every bit is reserved
+ *   prior       NULL, or (B, H, W) floats            smoothed  NULL, or (G, n_models, H, W) uint64
+ * Whatever is downloaded, P stays in the context's device memory as the STAGED PRIOR, which eincm_event_responsibilities_spatial reads
+ * in place with EINCM_RS_PRIOR_STAGED.  It is allocated by the first call, dropped by the next eincm_set_windows (any form) and kept
+ * across eincm_set_weights and EINCM_RS_APPLY: an EM forms the prior from the weights that its E-step is about to replace.
+ * Integer up to one thread's division, no atomics across workgroups: every run gives the same bytes.  It needs staged windows and no
+ * evaluation, no motion model, and the splat window does not matter to it.  A batch with no events is valid: S = 0 everywhere.
+ * Refused before anything is written, in the order and with the codes of eincm_compose_motions for the faults the two share:
+ * EINCM_ERR_STATE an evaluation in flight; EINCM_ERR_STATE nothing staged; EINCM_ERR_UNSUPPORTED an EINCM_CF_FP64 context, an
+ * event-sharded staging; EINCM_ERR_ARG n_models outside 1 .. EINCM_RS_MAX_MODELS, B not a multiple of n_models, unequal n_events
+ * inside a group, radius outside 0 .. EINCM_LP_MAX_RADIUS, unknown flag bits; EINCM_ERR_UNSUPPORTED a 32x32 source tile of one window
+ * with 2^20 events or more.  A refused call leaves the staged prior as it was. */
+#define EINCM_LP_MAX_RADIUS 8
+int eincm_label_prior(eincm_ctx* ctx, int n_models, int radius, uint32_t floor_mass, unsigned flags, float* prior, uint64_t* smoothed);
+
+/* The staged prior, downloaded: (B, H, W) floats.  EINCM_ERR_STATE without one (no eincm_label_prior since the last eincm_set_windows). */
+int eincm_get_staged_prior(eincm_ctx* ctx, float* prior);
+
+/* The E-step with a prior image: eincm_event_responsibilities whose mixing weight of model l is
+ * prior[b] * P[b, y_e, x_e] at the event's raw pixel (x_e, y_e), the staged coordinates of event i of window b = g * K + l.  Every
+ * argument it shares with eincm_event_responsibilities means the same, and so does everything not restated here: s_l, q_l, a_l, the
+ * order of the sums, the correctly rounded division, the labels, mass, n_unsupported, EINCM_RS_STAGED_WEIGHTS and EINCM_RS_APPLY.
+ *     c_l  = (float)prior[b] * P[b, y_e, x_e]
+ *     p_l  = c_l * a_l,      T = sum_l p_l in ascending l from +0
+ *     T not > 0 or not finite: the event is unsupported, p_l = c_l and T is summed again; if that T is not > 0 or not finite either,
+ *     p_l = (float)prior[b] and T is summed once more.  The event counts as unsupported once, whichever fallback it ends on
+ *     w'_l = p_l / T
+ * in fp32 without contraction.  With P = 1 everywhere the four outputs are the bytes of eincm_event_responsibilities.
+ *   prior_images  (B, H, W) floats, each finite and >= 0, or NULL with EINCM_RS_PRIOR_STAGED: the staged prior of eincm_label_prior
+ *                 is read in place
+ * Refused as eincm_event_responsibilities refuses, in its order, and after that: EINCM_ERR_ARG prior_images together with
+ * EINCM_RS_PRIOR_STAGED; EINCM_ERR_ARG neither of the two; EINCM_ERR_STATE EINCM_RS_PRIOR_STAGED without a staged prior; EINCM_ERR_ARG
+ * a value of prior_images that is not finite or is < 0 (the message names window and pixel). */
+#define EINCM_RS_PRIOR_STAGED 8u   /* flags: the prior stack is the context's staged prior, not prior_images */
+int eincm_event_responsibilities_spatial(eincm_ctx* ctx, int n_models, const float* images, const double* ref_weights,
+                                         const float* const* weights_in, const double* prior, const float* prior_images, uint32_t flags,
+                                         float* weights_out, uint8_t* labels, double* mass, int64_t* n_unsupported);
 
 /* compute_weights_for_multi_reference (losses.py:39-46) */
 int eincm_multi_ref_weights(int n_refs, double* w);
