@@ -214,6 +214,11 @@ SIGNATURES = [
     ('eincm_get_staged_prior', C.c_int, [_P, C.c_void_p]),
     ('eincm_event_responsibilities_spatial', C.c_int, [_P, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # the label prior carried along the models' own motions to the next window (raw addresses, as above)
+    ('eincm_carry_label_prior', C.c_int, [_P, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_uint, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]),
+    ('eincm_adopt_carried_prior', C.c_int, [_P, C.c_int]),
+    ('eincm_get_carried_prior', C.c_int, [_P, C.c_void_p]),
     # a solved theta carried along its own flow to the next window (raw addresses, as above)
     ('eincm_theta_advect', C.c_int, [_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -48,6 +48,8 @@
 #include "eincm_motion_fill.hip.h"
 #include "eincm_label_prior.h"
 #include "eincm_label_prior.hip.h"
+#include "eincm_label_carry.h"
+#include "eincm_label_carry.hip.h"
 #include "eincm_theta_advect.h"
 #include "eincm_theta_advect.hip.h"
 #include "eincm_contrast_landscape.h"
@@ -266,6 +268,11 @@ struct eincm_ctx : PlanCtx {
         Grow<float> prior;             // (B, H, W), allocated by the first call
         bool staged = false;           // it belongs to the staged batch: dropped by the next staging, kept across a re-weighting
     } lp;
+
+    struct {                           // eincm_carry_label_prior: the carried prior, not the staged one
+        Grow<float> prior;             // (B, H, W) of the batch it was formed on, allocated by the first call
+        LcCarried of{false, 0, 0, 0, 0};       // valid once a call's result is whole; a staging leaves it alone: it is meant for the next batch
+    } lc;
 
     // pinned host staging
     double* h_theta = nullptr;     // (B,H,W,2) capacity
@@ -2716,6 +2723,105 @@ int eincm_get_staged_prior(eincm_ctx* c, float* prior) {
     OneShot op(c);                                  // no piece of the scratch: the frame is here for its drain
     HIPCHK(c, op.begin());
     HIPCHK(c, op.down(prior, c->lp.prior.p, (size_t)c->g.B * c->g.H * c->g.W * sizeof(float)));          // (host memory: the caller's)
+    HIPCHK(c, op.sync());
+    return EINCM_OK;
+}
+
+// The label prior carried to the next window (eincm_label_carry.hip.h): the mass images by k_ml_mass, as
+// eincm_label_prior forms them; every model's image pushed along that model's own field into u64 accumulators (k_lc_splat), resolved to
+// uint32 masses (k_lc_resolve), and k_label_prior, unchanged, on those.  The checks, their order and the layout are
+// eincm_label_carry.h's.  The result is written where it stays, c->lc.prior (grown before the frame begins), and marked valid once the
+// call has ended on its synchronisation; c->lp, the staged prior of the batch that is staged now, is not touched.
+int eincm_carry_label_prior(eincm_ctx* c, int n_models, const double* coeffs, int n_coeffs, const double* tau, int radius, uint32_t floor_mass,
+                            unsigned flags, float* prior, uint32_t* carried, uint64_t* accum, uint64_t* dropped) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    const auto& mo = c->motion;
+    const LpState st{!c->fl.idle(), c->staged, c->fp64, c->sharded_staging || c->constants_pending, c->staged ? g.B : 0, c->win_events.data(),
+                     c->h_tilecount.data(), c->staged ? (int64_t)c->h_tilecount.size() : 0};
+    const LcArgs la{coeffs != nullptr, tau != nullptr, mo.set, n_coeffs, mo.set ? mo.model.n_coeffs : 0, tau, flags};
+    int bad_b = 0; int64_t bad_i = 0;
+    if (const int f = lc_check(st, la, n_models, radius, &bad_b, &bad_i)) {
+        if (f == LP_CROWDED)
+            return fail(c, lc_code(f), "eincm_carry_label_prior: %s: window %d, tile %lld holds %d", lc_why(f), bad_b, (long long)bad_i,
+                        (int)c->h_tilecount[(size_t)bad_b * g.ntiles + (size_t)bad_i]);
+        if (f == LC_TAU) return fail(c, lc_code(f), "eincm_carry_label_prior: %s: group %d", lc_why(f), bad_b);
+        if (f == LC_WIDTH) return fail(c, lc_code(f), "eincm_carry_label_prior: %s: %d, the model has %d", lc_why(f), n_coeffs, mo.model.n_coeffs);
+        if (f == LC_EVENTS) return fail(c, lc_code(f), "eincm_carry_label_prior: %s: window %d", lc_why(f), bad_b);
+        return fail(c, lc_code(f), "eincm_carry_label_prior: %s", lc_why(f));
+    }
+    const int B = g.B, K = n_models, G = B / K, Kc = mo.model.n_coeffs;
+    const size_t npix = (size_t)g.H * g.W, bins = (size_t)B * g.ntiles, GK = (size_t)G * K;
+    OneShot op(c);
+    const auto d_off = op.piece<int32_t>(bins + 1);
+    const auto d_q = op.piece<double>((size_t)B * MOTION_NQ);
+    const auto d_tau = op.piece<double>((size_t)G);
+    const auto d_mass = op.piece<uint32_t>(GK * npix);
+    const auto d_part = op.piece<unsigned long long>(GK * g.ntiles);
+    const auto d_acc = op.piece<unsigned long long>(GK * npix + GK);    // A (G, K, H W) | dropped (G K): one clear for both
+    const auto d_car = op.piece<uint32_t>(GK * npix);
+    int32_t* h_off = op.host_buf<int32_t>(bins + 1);                     // d_off and d_q go up from these
+    double* h_q = op.host_buf<double>((size_t)B * MOTION_NQ);
+    int64_t run = 0;                                                     // (as eincm_compose_motions: the bins lie in (window, tile) order)
+    for (size_t i = 0; i < bins; ++i) { h_off[i] = (int32_t)run; run += c->h_tilecount[i]; }
+    h_off[bins] = (int32_t)run;
+    if (run != c->stage.N) return fail(c, EINCM_ERR_STATE, "eincm_carry_label_prior: internal: the tile populations do not add up to the staged events");
+    for (int b = 0; b < B; ++b) motion_q(mo.model, coeffs + (size_t)b * Kc, h_q + (size_t)b * MOTION_NQ);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, ensure(c, c->lc.prior, (size_t)B * npix));
+    c->lc.of.valid = false;                                              // (until this call's prior is whole)
+    HIPCHK(c, op.begin());
+    unsigned long long* const d_drop = (unsigned long long*)d_acc + GK * npix;
+    HIPCHK(c, op.up(d_off, h_off, (bins + 1) * sizeof(int32_t)));
+    HIPCHK(c, op.up(d_q, h_q, (size_t)B * MOTION_NQ * sizeof(double)));
+    HIPCHK(c, op.up(d_tau, tau, (size_t)G * sizeof(double)));           // (host memory: the caller's, as the outputs)
+    HIPCHK(c, op.zero(d_acc, (GK * npix + GK) * sizeof(unsigned long long)));
+    const MlGeom mg{g.H, g.W, g.tilesX, g.ntiles, K, 0u, 0.0, 0.0, 1.0};                   // (k_ml_mass reads no flag and no model)
+    const float* w = c->stage.weighted ? (const float*)c->d_w_g : nullptr;          // (an unweighted batch has no ev_w: q = 4096)
+    HIPCHK(c, op.launch(k_ml_mass, dim3((unsigned)g.ntiles, (unsigned)G), dim3(ML_NT), (size_t)K * ML_TILE_PIX * sizeof(uint32_t), mg, d_off,
+                        c->d_xy_g, w, d_mass, d_part));
+    const LcGeom cg{g.H, g.W, K, mo.model.cx, mo.model.cy, mo.model.scale};
+    HIPCHK(c, op.launch(k_lc_splat, dim3((unsigned)((npix + NT - 1) / NT), (unsigned)GK), dim3(NT), 0, cg, d_mass, d_q, d_tau, d_acc, d_drop));
+    HIPCHK(c, op.launch(k_lc_resolve, dim3((unsigned)((GK * npix + NT - 1) / NT)), dim3(NT), 0, GK * npix, d_acc, d_car));
+    const LpGeom lg{g.H, g.W, g.tilesX, radius, floor_mass};
+    HIPCHK(c, op.launch(lp_kernel(K), dim3((unsigned)g.ntiles, (unsigned)G), dim3(LP_NT), 0, lg, d_car, c->lc.prior.p, nullptr));
+    if (prior) HIPCHK(c, op.down(prior, c->lc.prior.p, (size_t)B * npix * sizeof(float)));
+    if (carried) HIPCHK(c, op.down(carried, d_car, GK * npix * sizeof(uint32_t)));
+    if (accum) HIPCHK(c, op.down(accum, d_acc, GK * npix * sizeof(uint64_t)));
+    if (dropped) HIPCHK(c, op.down(dropped, d_drop, GK * sizeof(uint64_t)));
+    HIPCHK(c, op.sync());
+    c->lc.of = LcCarried{true, K, B, g.H, g.W};
+    return EINCM_OK;
+}
+
+// The carried prior becomes the staged prior of the batch staged now: one copy on the device, and c->lp is as eincm_label_prior would
+// have left it, so the EINCM_RS_PRIOR_STAGED path of the spatial E-step reads it with no change.  The carried prior stays valid.
+int eincm_adopt_carried_prior(eincm_ctx* c, int n_models) {
+    if (!c) return EINCM_ERR_ARG;
+    const Geom& g = c->g;
+    if (const LcAdoptFault f = lc_adopt_check(!c->fl.idle(), c->staged, c->lc.of, n_models, c->staged ? g.B : 0, c->staged ? g.H : 0, c->staged ? g.W : 0))
+        return fail(c, lc_adopt_code(f), "eincm_adopt_carried_prior: %s", lc_adopt_why(f));
+    const size_t n = (size_t)g.B * g.H * g.W;
+    OneShot op(c);                                  // no piece of the scratch: the frame is here for its drain
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, ensure(c, c->lp.prior, n));
+    c->lp.staged = false;                           // (until the copy is whole)
+    HIPCHK(c, op.begin());
+    op.pending = true;
+    HIPCHK(c, hipMemcpyAsync(c->lp.prior.p, c->lc.prior.p, n * sizeof(float), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, op.sync());
+    c->lp.staged = true;
+    return EINCM_OK;
+}
+
+int eincm_get_carried_prior(eincm_ctx* c, float* prior) {
+    if (!c) return EINCM_ERR_ARG;
+    if (!prior) return fail(c, EINCM_ERR_ARG, "null pointer argument");
+    if (const int rc = not_in_flight(c, "eincm_get_carried_prior")) return rc;
+    if (!c->lc.of.valid) return fail(c, EINCM_ERR_STATE, "eincm_get_carried_prior: %s", lc_adopt_why(LCA_NONE));
+    OneShot op(c);                                  // no piece of the scratch: the frame is here for its drain
+    HIPCHK(c, op.begin());
+    HIPCHK(c, op.down(prior, c->lc.prior.p, (size_t)c->lc.of.n_windows * c->lc.of.H * c->lc.of.W * sizeof(float)));  // (host memory: the caller's)
     HIPCHK(c, op.sync());
     return EINCM_OK;
 }

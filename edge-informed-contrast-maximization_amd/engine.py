@@ -830,6 +830,53 @@ def check_label_prior_args(n_models, radius, floor_mass, want):
     return int(n_models), int(radius), int(floor_mass), want
 
 
+LC_OUTPUTS = ('prior', 'carried', 'accum', 'dropped')
+
+
+def label_carry_layout(n_groups, n_models, sensor_size):
+    """The shapes of eincm_carry_label_prior's four outputs and where a group's block starts in each, in elements of the output's own
+    type (csrc/eincm_label_carry.h: lc_prior_offset, lc_carried_offset, lc_accum_offset, lc_dropped_offset, restated;
+    tests/test_host_label_carry.py compares the two): a dict name -> (shape, dtype, offsets (G,) int64).  'prior' is per window, window
+    g * n_models + l model l of group g."""
+    G, K, H, W = int(n_groups), int(n_models), int(sensor_size[0]), int(sensor_size[1])
+    g = np.arange(G, dtype=np.int64)
+    return {'prior': ((G * K, H, W), np.float32, g * (K * H * W)), 'carried': ((G, K, H, W), np.uint32, g * (K * H * W)),
+            'accum': ((G, K, H, W), np.uint64, g * (K * H * W)), 'dropped': ((G, K), np.uint64, g * K)}
+
+
+def check_label_carry_args(n_models, coeffs, n_windows, n_coeffs, tau, radius, floor_mass, want):
+    """The arguments of Engine.carry_label_prior, checked without a GPU.  n_models, radius and floor_mass as check_label_prior_args
+    takes them; want a choice of LC_OUTPUTS without repeats that may be empty (the prior is carried all the same); coeffs a numeric
+    (B, K_c) array as check_compose_args takes it, except that its values need not be finite (a source whose field is not finite is
+    dropped); tau a finite number or (G,) of them, G = B / n_models where the engine knows B (n_windows 0: nothing staged - the library
+    refuses that itself).  What depends on the staged batch is left to the library, so that those refusals carry the codes and the
+    sentences of csrc/eincm_label_carry.h.  Returns (n_models, coeffs float64 C-contiguous, tau (G,) float64 or as handed over where G
+    is unknown, radius, floor_mass, want)."""
+    K, r, floor, _ = check_label_prior_args(n_models, radius, floor_mass, ())
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in LC_OUTPUTS for w in want) or len(set(want)) != len(want):
+        raise ValueError(f'want must be a choice of {LC_OUTPUTS} without repeats, got {want!r}')
+    c = np.asarray(coeffs)
+    if c.dtype.kind not in 'fiu':
+        raise ValueError(f'coeffs must be numeric, got dtype {c.dtype}')
+    rows = 'B' if not n_windows else str(int(n_windows))
+    cols = 'K_c' if n_coeffs is None else str(int(n_coeffs))
+    if c.ndim != 2 or (n_windows and c.shape[0] != n_windows) or (n_coeffs is not None and c.shape[1] != n_coeffs):
+        raise ValueError(f'coeffs must be ({rows}, {cols}): one row of model coefficients per staged window, got {np.shape(coeffs)}')
+    t = np.asarray(tau)
+    if t.dtype.kind not in 'fiu' or t.ndim > 1:
+        raise ValueError(f'tau must be a finite number or (G,) of them, got {tau!r}')
+    t = t.astype(np.float64)
+    if not np.isfinite(t).all():
+        raise ValueError(f'tau must be finite, got {tau!r}')
+    if n_windows and n_windows % K == 0:
+        G = n_windows // K
+        if t.shape not in ((), (G,)):
+            raise ValueError(f'tau must be a finite number or ({G},) of them, one per group, got shape {t.shape}')
+        t = np.ascontiguousarray(np.broadcast_to(t, (G,)))
+    return K, np.ascontiguousarray(c, dtype=np.float64), t, r, floor, want
+
+
 def check_prior_images(prior_images, n_windows, sensor_size):
     """The caller's prior stack of Engine.event_responsibilities_spatial as contiguous float32 (B, H, W), every value finite and >= 0 as
     the float the kernel takes; (H, W) stands for it when B == 1.  None stays None (the staged prior).  Anything else is a ValueError,
@@ -1028,6 +1075,7 @@ class Engine:
         self.motion_path = 'expanded'      # how loss_grad_motion evaluates (set_motion_path): 'expanded' | 'fused' | 'auto'
         self._weighted = False             # the staged batch carries per-event weights (set_windows; the property `weighted`)
         self._keep_order = False           # the staged batch kept its event order (set_windows(..., keep_order=True); the property `keep_order`)
+        self._carried_windows = 0          # B of the batch the carried prior was formed on (carry_label_prior; 0: none)
 
     # -- lifetime ---------------------------------------------------------------------------------
     def close(self):
@@ -1946,6 +1994,45 @@ class Engine:
         """The staged prior, downloaded: (B, H, W) float32, what the last label_prior left.  For tests and tools."""
         p = np.zeros((self.B, self.H, self.W), dtype=np.float32)
         self._check(self._lib.eincm_get_staged_prior(self._ctx, p.ctypes.data))
+        return p
+
+    def carry_label_prior(self, n_models, coeffs, tau=1.0, radius=2, floor_mass=4096, want=('prior',)):
+        """The label prior of the staged segmentation carried to the next window, one device operation.  The
+        staged batch, n_models and coeffs (B, K_c) are compose_motions'.  Every model's mass image is pushed along that model's own
+        field by tau (a number, or (G,): one per group; the displacement is model.field(coeffs) * tau pixels), split over the four
+        pixels around where it lands with weights that sum to 2^20, summed in uint64 and rounded back to uint32 masses, half up and
+        saturating at 2^32 - 1; label_prior's box sum and shares (radius, floor_mass) run on those.  Mass that leaves the sensor, or
+        whose landing is not finite, is dropped.  Returns a dict of ``want``: 'prior' (B, H, W) float32, what
+        event_responsibilities_spatial takes; 'carried' (G, n_models, H, W) uint32, the masses that arrived; 'accum' (G, n_models, H, W)
+        uint64, the sums before rounding; 'dropped' (G, n_models) uint64, in the units of 'accum': accum.sum() + dropped is 2^20 times
+        the model's mass.  want=() only carries: whatever is downloaded, the prior stays on the device as the carried prior, which
+        set_windows leaves alone and adopt_carried_prior makes the staged prior of the next batch.  The staged prior of this batch is
+        not touched.  Needs staged windows and a motion model, no evaluation; fp32 engines only, no sharded staging, no theta-grid
+        fields.  Exact: equal to tests/_label_carry_witness.py byte for byte, and the same bytes on every run."""
+        K, c, t, r, floor, want = check_label_carry_args(n_models, coeffs, self.B,
+                                                         None if self.motion_model is None else self.motion_model.n_coeffs, tau, radius,
+                                                         floor_mass, want)
+        t = np.ascontiguousarray(np.broadcast_to(t, (max(self.B // K, 1),)) if t.ndim == 0 else t)
+        lay = label_carry_layout(self.B // K, K, (self.H, self.W))
+        out = {name: np.zeros(lay[name][0], dtype=lay[name][1]) for name in want}
+        addr = lambda name: out[name].ctypes.data if name in out else None
+        self._check(self._lib.eincm_carry_label_prior(self._ctx, K, c.ctypes.data, c.shape[1], t.ctypes.data, r, floor, 0, addr('prior'),
+                                                      addr('carried'), addr('accum'), addr('dropped')))
+        self._carried_windows = self.B
+        return out
+
+    def adopt_carried_prior(self, n_models):
+        """The carried prior of carry_label_prior becomes the staged prior of the batch staged now, on the device: the next
+        event_responsibilities_spatial / apply_responsibilities_spatial without prior_images reads it.  The batch must have the B and
+        the n_models the prior was carried with.  The carried prior stays, so it can be adopted again after another staging."""
+        if isinstance(n_models, bool) or not isinstance(n_models, (int, np.integer)) or not 1 <= int(n_models) <= L.RS_MAX_MODELS:
+            raise ValueError(f'n_models must be an integer within 1 .. {L.RS_MAX_MODELS}, got {n_models!r}')
+        self._check(self._lib.eincm_adopt_carried_prior(self._ctx, int(n_models)))
+
+    def carried_prior(self):
+        """The carried prior, downloaded: (B, H, W) float32 of the batch it was formed on.  For tests and tools."""
+        p = np.zeros((max(self._carried_windows, 1), self.H, self.W), dtype=np.float32)     # (none carried: the library refuses)
+        self._check(self._lib.eincm_get_carried_prior(self._ctx, p.ctypes.data))
         return p
 
     def event_responsibilities_spatial(self, n_models, prior_images=None, images=None, ref_weights=None, prior=None, exclude_self=True,

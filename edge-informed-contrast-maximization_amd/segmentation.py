@@ -15,7 +15,11 @@ What the EM ends in - K coefficient vectors and one weight per event and model -
 segmented_flow (Engine.compose_motions): the form that flow_errors, advect_theta and a submission take.
 
 segment_motions_spatial runs the same loop with a spatially coherent E-step: the staged weights become a
-per-pixel label prior on the device (Engine.label_prior) and every event's mixing weights are read at its own pixel."""
+per-pixel label prior on the device (Engine.label_prior) and every event's mixing weights are read at its own pixel.
+
+segment_sequence segments consecutive windows one after the other and hands the segmentation itself on: after
+every window the staged weights become a label prior carried along each model's own motion (Engine.carry_label_prior), and the next
+window's first E-step reads it (Engine.adopt_carried_prior) instead of a prior formed from unit weights."""
 import numpy as np
 
 from . import _lib as L
@@ -24,6 +28,20 @@ from . import motion
 from .engine import check_label_prior_args
 
 PRIORS = ('mass', 'uniform')
+FIRST_PRIORS = (None, 'carried')
+
+
+def check_first_prior(first_prior, weights0, spatial=True):
+    """first_prior of segment_motions_spatial_primed, checked without a GPU: None or 'carried'; 'carried' replaces the prior of the
+    first E-step, the one on unit weights, so it raises together with weights0 (there is no such E-step then) and outside the spatial
+    EM."""
+    if first_prior not in FIRST_PRIORS:
+        raise ValueError(f'first_prior {first_prior!r} not supported; one of {FIRST_PRIORS}')
+    if first_prior is not None and not spatial:
+        raise ValueError("first_prior='carried' goes with the spatial E-step only (segment_motions_spatial_primed)")
+    if first_prior is not None and weights0 is not None:
+        raise ValueError("first_prior='carried' together with weights0: there is no first E-step on unit weights to use the carried prior")
+    return first_prior
 
 
 def check_segment_args(windows, model, coeffs0, n_iters, weights0, prior, min_mass, in_place=False, record_weights=True):
@@ -107,10 +125,25 @@ def segment_motions_spatial(engine, windows, model, coeffs0, params, radius=2, f
                     spatial=(radius, floor_mass))
 
 
+def segment_motions_spatial_primed(engine, windows, model, coeffs0, params, radius=2, floor_mass=4096, n_iters=5, maxiter=25, gtol=1e-6,
+                                   weights0=None, prior='mass', min_mass=1.0, callback=None, in_place=True, record_weights=True,
+                                   first_prior=None):
+    """segment_motions_spatial with one keyword more (its own signature is pinned by tests/test_label_prior_interface.py, so the keyword
+    lives here).  first_prior: None, or 'carried' (DESIGN.md section 33): the label_prior call after the FIRST staging - the one that
+    precedes the E-step at coeffs0 and would form its prior from unit weights, which tells an event nothing - is replaced by
+    Engine.adopt_carried_prior(K): that E-step reads the prior a previous window's Engine.carry_label_prior left on the device.  Every
+    later staging and iteration is unchanged, and with None the function returns segment_motions_spatial's bytes.  'carried' together
+    with weights0 raises: there is no such first E-step then."""
+    return _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, in_place, record_weights,
+                    spatial=(radius, floor_mass), first_prior=first_prior)
+
+
 def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, weights0, prior, min_mass, callback, in_place, record_weights,
-             spatial=None):
-    """spatial: None, or (radius, floor_mass): the label prior is formed after every staging and the E-step reads it."""
+             spatial=None, first_prior=None):
+    """spatial: None, or (radius, floor_mass): the label prior is formed after every staging and the E-step reads it.  first_prior:
+    None, or 'carried': after the first staging the engine's carried prior is adopted instead."""
     c, weights = check_segment_args(windows, model, coeffs0, n_iters, weights0, prior, min_mass, in_place, record_weights)
+    check_first_prior(first_prior, weights0, spatial is not None)
     if spatial is not None:
         check_label_prior_args(c.shape[1], spatial[0], spatial[1], ())
     G, K = c.shape[:2]
@@ -118,6 +151,7 @@ def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, we
     engine.set_motion_model(model)
     engine.set_motion_path('expanded')
     staged_once = []
+    adopt = [first_prior == 'carried']      # (true until the first staging has taken the carried prior)
 
     def stage(wts):
         if not in_place:
@@ -129,7 +163,10 @@ def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, we
                 engine.set_weights([wts[g][l] for g in range(G) for l in range(K)])
         elif wts is not None:           # (None: the E-step has applied its own result)
             engine.set_weights([wts[g][l] for g in range(G) for l in range(K)])
-        if spatial is not None:         # the prior of the next E-step, from the weights it will replace; it stays on the device
+        if spatial is not None and adopt[0]:       # the first E-step of a window that follows another: the previous window's labels, carried
+            adopt[0] = False
+            engine.adopt_carried_prior(K)
+        elif spatial is not None:       # the prior of the next E-step, from the weights it will replace; it stays on the device
             engine.label_prior(K, spatial[0], spatial[1], want=())
 
     def e_step(coeffs, pi):
@@ -176,6 +213,48 @@ def _segment(engine, windows, model, coeffs0, params, n_iters, maxiter, gtol, we
             callback(it, record)
         active = active & (r['mass'] >= min_mass)
     return history
+
+
+# ---- consecutive windows: the segmentation handed on ------------------------------------------------------------------
+def check_sequence_args(windows_seq, coeffs0, tau, em):
+    """The arguments of segment_sequence that are its own, checked without a GPU (every step's are checked by check_segment_args when
+    it runs).  Returns tau as float64, a number or (G,)."""
+    if len(windows_seq) < 1 or any(len(w) != len(windows_seq[0]) or len(w) < 1 for w in windows_seq):
+        raise ValueError('windows_seq must hold at least one step, every step the same number G >= 1 of (xs, ys, ts, edges, edge_ts) tuples')
+    for name in ('weights0', 'first_prior', 'in_place'):
+        if name in em and not (name == 'in_place' and em[name] is True):
+            raise ValueError(f'{name} is the sequence\'s own: every step after the first starts from the carried prior, on the batch staged once')
+    t = np.asarray(tau, dtype=np.float64)
+    if t.shape not in ((), (len(windows_seq[0]),)) or not np.isfinite(t).all():
+        raise ValueError(f'tau must be a finite number or ({len(windows_seq[0])},) of them, got {tau!r}')
+    return t
+
+
+def segment_sequence(engine, windows_seq, model, coeffs0, params, tau=1.0, radius=2, floor_mass=4096, **em):
+    """segment_motions_spatial over T consecutive steps, the segmentation handed from each to the next.
+    windows_seq: T lists of the same G (xs, ys, ts, edges, edge_ts) tuples; coeffs0 (G, K, n_coeffs) starts step 0; radius and
+    floor_mass are the label prior's, of the EM and of the carry alike; **em goes to every step (n_iters, maxiter, gtol, prior,
+    min_mass, callback, record_weights).  Step 0 is segment_motions_spatial from coeffs0.  After every step but the last,
+    Engine.carry_label_prior(K, last coeffs, tau, radius, floor_mass, want=()) runs on the batch that is still staged with the step's
+    final weights (the in-place route), and the next step is segment_motions_spatial_primed(coeffs0=last coeffs, first_prior='carried').
+
+    tau: how far the labels move along each model's field between two windows, in the field's own time unit: 1.0 moves them by one
+    window's displacement, right for windows that follow each other without a gap.  The coefficients are handed over as they are, as
+    the reference hands theta over in place: rescaling them (and tau) for windows of unequal duration is the caller's job.
+
+    Returns the T histories."""
+    t = check_sequence_args(windows_seq, coeffs0, tau, em)
+    em = {k: v for k, v in em.items() if k != 'in_place'}
+    histories, c = [], np.asarray(coeffs0, dtype=np.float64)
+    for step, windows in enumerate(windows_seq):
+        h = segment_motions_spatial_primed(engine, windows, model, c, params, radius=radius, floor_mass=floor_mass, in_place=True,
+                                           first_prior=None if step == 0 else 'carried', **em)
+        histories.append(h)
+        c = h[-1]['coeffs']
+        if step + 1 < len(windows_seq):
+            G, K = c.shape[:2]
+            engine.carry_label_prior(K, c.reshape(G * K, -1), t, radius, floor_mass, want=())
+    return histories
 
 
 # ---- the segmentation as one flow field and a label image (DESIGN.md section 30) ---------------------------------------------------------

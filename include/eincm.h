@@ -40,7 +40,8 @@ extern "C" {
                                *    (a motion segmentation composed into one flow field and a label image), eincm_densify_motions (that
                                *    composition made dense: every pixel takes the label of its nearest labelled pixel), eincm_label_prior,
                                *    eincm_get_staged_prior, eincm_event_responsibilities_spatial (a per-pixel label prior from the staged
-                               *    weights, and the E-step that reads a prior image stack) */
+                               *    weights, and the E-step that reads a prior image stack), eincm_carry_label_prior, eincm_adopt_carried_prior,
+                               *    eincm_get_carried_prior (a segmentation's label prior carried along the models' own motions to the next window) */
 
 #define EINCM_OK               0
 #define EINCM_ERR_ARG         -1   /* bad argument (shape, null pointer, out-of-range event coordinate) */
@@ -473,6 +474,50 @@ int eincm_label_prior(eincm_ctx* ctx, int n_models, int radius, uint32_t floor_m
 
 /* The staged prior, downloaded: (B, H, W) floats.  EINCM_ERR_STATE without one (no eincm_label_prior since the last eincm_set_windows). */
 int eincm_get_staged_prior(eincm_ctx* ctx, float* prior);
+
+/* A segmentation's label prior carried to the next window: every model's mass image is pushed along THAT
+ * MODEL'S OWN motion field, so that transparent layers each move their own way, and the label prior is formed on what arrives.  The
+ * staged batch, n_models, q(w) and mass[g, l, p] are eincm_compose_motions'; f_l(p) is its field of coeffs[g * K + l] at p, the bits of
+ * eincm_motion_field.  For group g and model l:
+ *     source    every sensor pixel p = (x, y) with M = mass[g, l, p] > 0 lands at q = p + f_l(p) * tau[g], each product and sum rounded
+ *               on its own in fp64.  q not finite or outside (-1, W) x (-1, H): the source deposits nothing
+ *     deposit   (x0, y0) = floor(q); the fractions are rounded to 10 bits each, ix = rint((qx - x0) * 1024), iy likewise, ties to even;
+ *               tap (x0 + dx, y0 + dy), dx, dy in {0, 1}, has the weight (dx ? ix : 1024 - ix) * (dy ? iy : 1024 - iy): the four sum
+ *               to 2^20.  accum[g, l, tap] += M * weight for every tap of weight > 0 on the sensor, as uint64; a tap off the sensor is
+ *               dropped
+ *     dropped[g, l] = the sum of M * weight over the dropped taps, plus M * 2^20 for every source that deposits nothing, so that
+ *               sum_p accum[g, l, p] + dropped[g, l] = 2^20 * sum_p mass[g, l, p] exactly
+ *     carried[g, l, p] = min((accum[g, l, p] + 2^19) >> 20, 2^32 - 1) as uint32: half up, saturating
+ *     prior     eincm_label_prior's P with carried in the place of mass, radius and floor_mass as there
+ * No accumulator overflows: accum <= 2^20 * 4096 * n_events of the model's window, and a batch holds at most 2 * 10^9 < 2^31 events.
+ *   n_models    K, 1 .. EINCM_RS_MAX_MODELS            coeffs   (B, n_coeffs) doubles, n_coeffs the motion model's (eincm_set_motion_model)
+ *   tau         (G) finite doubles: how far along its field every group's mass moves, in the field's own time unit (px per tau = 1);
+ *               0 leaves it where it is, a negative tau moves it backwards
+ *   radius, floor_mass   eincm_label_prior's             flags    0; every bit is reserved
+ *   prior       NULL, or (B, H, W) floats                carried  NULL, or (G, n_models, H, W) uint32
+ *   accum       NULL, or (G, n_models, H, W) uint64      dropped  NULL, or (G, n_models) uint64
+ * Whatever is downloaded, P stays in the context's device memory as the CARRIED PRIOR.  It is not the staged prior: that of the staged
+ * batch stays as it was, and eincm_set_windows leaves the carried prior alone.  An accepted call marks it invalid at its start and valid
+ * once its result is whole.  Integer up to k_label_prior's one division: 64-bit integer atomics, whose sums do not depend on the order
+ * of arrival, so every run gives the same bytes.  Coefficients that are not finite, or so large that f * tau is not, are accepted:
+ * their sources count in dropped.
+ * Refused before anything is written, in the order and with the codes of eincm_label_prior (all of them, its EINCM_ERR_UNSUPPORTED
+ * for an EINCM_CF_FP64 context, an event-sharded staging and a crowded tile included), then: EINCM_ERR_ARG coeffs or tau NULL;
+ * EINCM_ERR_ARG a tau that is not finite (the message names the group); EINCM_ERR_STATE no motion model set; EINCM_ERR_ARG n_coeffs
+ * other than the model's; EINCM_ERR_ARG unknown flag bits; EINCM_ERR_UNSUPPORTED a window of more than 2^32 - 1 events (staging
+ * refuses those long before).  A refused call leaves the carried prior as it was, valid or not. */
+int eincm_carry_label_prior(eincm_ctx* ctx, int n_models, const double* coeffs, int n_coeffs, const double* tau, int radius,
+                            uint32_t floor_mass, unsigned flags, float* prior, uint32_t* carried, uint64_t* accum, uint64_t* dropped);
+
+/* The carried prior becomes the staged prior of the batch that is staged now, by one copy on the device: afterwards
+ * eincm_event_responsibilities_spatial reads it with EINCM_RS_PRIOR_STAGED as it reads eincm_label_prior's.  The carried prior stays
+ * valid, so it can be adopted again after another staging.  Refused in this order: EINCM_ERR_STATE an evaluation in flight, nothing
+ * staged, no valid carried prior; EINCM_ERR_ARG n_models, the staged B or the sensor other than those the carried prior was formed
+ * with. */
+int eincm_adopt_carried_prior(eincm_ctx* ctx, int n_models);
+
+/* The carried prior, downloaded: (B, H, W) floats of the batch it was formed on.  EINCM_ERR_STATE without a valid one. */
+int eincm_get_carried_prior(eincm_ctx* ctx, float* prior);
 
 /* The E-step with a prior image: eincm_event_responsibilities whose mixing weight of model l is
  * prior[b] * P[b, y_e, x_e] at the event's raw pixel (x_e, y_e), the staged coordinates of event i of window b = g * K + l.  Every
